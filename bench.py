@@ -23,6 +23,8 @@ Prints ONE JSON line on rank 0.  Beyond the driver's contract it carries
   cpu_baseline         the oracle's like-for-like iteration on 1 thread, plus the reference-faithful iteration (identity
                        pairing, materialised rows, two N x 3 SVD least squares: what the reference costs) and an all-core figure
   N > 1                exchange actually used, exchange_fallback, per-rank pass times
+--dump-outputs DIR also writes what the last timed run returned (transform, diffs, last pairs) as DIR/<name>.npy: inputs are
+regenerated bit for bit from the arguments, so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -41,6 +43,33 @@ VALU_PEAK_GINST = 1228.8       # wave64 vector instructions per ns-second: 256 C
 PMC_FILE = os.path.join(ROOT, "profiles", "r3_pmc.json")
 N_SIMD = 256 * 4                # CUs x SIMDs
 CLOCK_GHZ = 2.4
+
+
+DUMP_CORR_ROWS = 1 << 21        # correspondence rows dumped at most: 2M x (8 + 4 + 8) B = 40 MB
+DUMP_SEED = 0x5EED
+
+
+def dump_outputs(eng, last, world):
+    """The arrays the timed path returned in its last step: the final 4x4 transform and the diff record of the run; with one rank
+    also the pairs of the last pass (target row per source row, as float64, and its squared distance) -- for a source of more
+    than DUMP_CORR_ROWS rows those of a fixed, seeded sample of rows (corr_rows)."""
+    import numpy as np
+    out = dict(transform=np.asarray(last["transform"], np.float32),
+               diff_final=np.asarray([last["diff_final"]], np.float32))
+    if "diffs" in last:
+        out["diffs"] = np.asarray(last["diffs"], np.float32)
+        out["diff_initial"] = np.asarray([last["diff_initial"]], np.float32)
+    if "sums" in last:
+        out["sums"] = np.asarray(last["sums"], np.float64)
+    if world == 1:
+        idx, d2 = eng.correspondences()
+        if len(idx) > DUMP_CORR_ROWS:
+            rows = np.sort(np.random.default_rng(DUMP_SEED).choice(len(idx), DUMP_CORR_ROWS, replace=False))
+            idx, d2 = idx[rows], d2[rows]
+            out["corr_rows"] = rows.astype(np.float64)
+        out["corr_index"] = idx.astype(np.float64)
+        out["corr_dist2"] = d2.astype(np.float32)
+    return out
 
 
 def main():
@@ -62,6 +91,9 @@ def main():
                          "record summed with torch.distributed.all_reduce between C calls (slow; lets the multi-rank scaffolding of "
                          "this file run where RCCL cannot, e.g. several ranks on ONE GPU with --dist-backend gloo)")
     ap.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"])
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the timed path returned in its last step as DIR/<name>.npy (rank 0; float32 / "
+                         "float64, at most 64 MB: correspondences of a large source are a fixed, seeded sample of its rows)")
     args = ap.parse_args()
 
     import numpy as np
@@ -193,12 +225,13 @@ def main():
                 dist.all_reduce(t, op=dist.ReduceOp.SUM)
                 eng.set_sums(t.cpu().numpy())
                 it = eng.step()
-            return
+            return dict(transform=eng.transform(), diff_final=it["diff"], sums=it["sums"])
         # begin + exactly k steps, inside one C call (symmicp_align with fixed_iters: myicp.cpp:122-142 without the stop rule)
         eng.set_config(max_iters=k)
         r = eng.align()
         if r["status"] != 0 or r["iters"] != k:
             raise SystemExit("symmicp_align failed: %s" % (r,))
+        return r
 
     # ---- warmup: W untimed steps ------------------------------------------------------------------
     run(W)
@@ -214,7 +247,7 @@ def main():
         eng.reset_stats()
         barrier_sync()
         t0 = time.perf_counter()
-        run(K)
+        last = run(K)
         barrier_sync()
         el = time.perf_counter() - t0
         if dist is not None:
@@ -226,6 +259,8 @@ def main():
         if best is None or el < best[0]:
             best = (el, st_timed, T_timed)
     elapsed, st_timed, T_timed = best
+    # what the last timed run handed its caller, read back before the instrumented run below replaces the engine's state
+    dump = dump_outputs(eng, last, world) if args.dump_outputs and rank == 0 else None
     err_truth_timed = float(np.abs(T_timed - d["truth"]).max())
     # ---- the same K steps once more with HIP events around EVERY kernel: the per-kernel table.  Kept out of the timed
     # region because each event record costs a few microseconds of GPU timeline, comparable to a converged pass's kernels;
@@ -445,6 +480,10 @@ def main():
                 out["predicted_per_rank_ms"] = open(os.path.join(ROOT, "profiles", "r3_predict_ranks_%d.log" % world)).read().strip().splitlines()[-1]
             except OSError:
                 out["predicted_per_rank_ms"] = None
+        if dump is not None:
+            os.makedirs(args.dump_outputs, exist_ok=True)
+            for name, a in dump.items():
+                np.save(os.path.join(args.dump_outputs, name + ".npy"), a)
         print(json.dumps(out), flush=True)
     if dist is not None:
         dist.barrier()

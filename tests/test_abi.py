@@ -16,6 +16,9 @@ def sym():
     if not os.path.exists(symmicp.LIB_PATH):
         import __graft_entry__ as ge
         ge.build()
+    # load through the package (torch's HIP runtime first): a bare dlopen here would map a second HIP runtime into the process,
+    # and every GPU test that runs after this module in the same process would find no device
+    symmicp.lib()
     return symmicp
 
 
@@ -129,20 +132,45 @@ def test_pcd_reader_rejects_malformed_headers(sym, tmp_path, bad):
         sym.pcd_read(str(p))
 
 
-def test_reference_main_cpp_compiles_unchanged_against_the_dropin(sym, tmp_path):
-    """The reference's own driver (ICP/main.cpp), byte for byte, builds against include/myicp.h +
-    include/stdafx.h + the pcl:: stand-in and links with libsymmicp.  Only where /root/reference is
-    mounted (it is not on the GPU box); the file is copied to a temp dir outside the repo so that its
-    quoted includes resolve to this repo's headers instead of the Windows-only originals."""
+def test_reference_style_client_compiles_against_the_dropin(sym, tmp_path):
+    """A client written the way the reference's driver uses the class -- only the precompiled header and myicp.h included,
+    MyICP's four reference methods, pcl:: clouds and the headless pcl::visualization::PCLVisualizer -- builds against
+    include/ (stdafx.h + the pcl:: stand-in) and links with libsymmicp.  Without a GPU the run must fail loudly, not
+    fall back to a CPU path."""
     import shutil
     import subprocess
-    ref = "/root/reference/ICP/main.cpp"
-    if not os.path.exists(ref):
-        pytest.skip("reference not mounted")
-    shutil.copy(ref, tmp_path / "main.cpp")
-    exe = tmp_path / "ref_main"
+    (tmp_path / "client.cpp").write_text(r"""
+#include "stdafx.h"
+#include "myicp.h"
+
+static pcl::PointCloud<pcl::PointXYZ>::Ptr as_xyz(const pcl::PointCloud<PointT>::Ptr &in)
+{
+    pcl::PointCloud<pcl::PointXYZ>::Ptr out(new pcl::PointCloud<pcl::PointXYZ>);
+    for (size_t i = 0; i < in->points.size(); i++) {
+        pcl::PointXYZ p;
+        p.x = in->points[i].x; p.y = in->points[i].y; p.z = in->points[i].z;
+        out->points.push_back(p);
+    }
+    return out;
+}
+
+int main()
+{
+    MyICP icp;
+    int st = icp.LoadCloud("cat.pcd", "cat_out.pcd");
+    cout << "load " << st << " src " << icp.GetSrcCloud()->points.size() << " tgt " << icp.GetTgtCloud()->points.size() << endl;
+    icp.RegisterSymm();
+    pcl::visualization::PCLVisualizer viewer("client");
+    viewer.addPointCloud(as_xyz(icp.GetSrcCloud()));
+    viewer.addPointCloud(as_xyz(icp.GetTgtCloud()), "target");
+    while (!viewer.wasStopped())
+        viewer.spinOnce();
+    return 0;
+}
+""")
+    exe = tmp_path / "client"
     libdir = os.path.dirname(sym.LIB_PATH)
-    r = subprocess.run(["g++", "-std=c++17", "-w", "-I", os.path.join(ROOT, "include"), str(tmp_path / "main.cpp"), "-o", str(exe),
+    r = subprocess.run(["g++", "-std=c++17", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), str(tmp_path / "client.cpp"), "-o", str(exe),
                         "-L", libdir, "-lsymmicp", "-Wl,-rpath," + libdir], capture_output=True, text=True)
     assert r.returncode == 0, r.stderr
     import torch
@@ -151,6 +179,7 @@ def test_reference_main_cpp_compiles_unchanged_against_the_dropin(sym, tmp_path)
         shutil.copy(os.path.join(GOLDEN, "cat.pcd"), tmp_path / "cat.pcd")
         shutil.copy(os.path.join(GOLDEN, "cat_out.pcd"), tmp_path / "cat_out.pcd")
         r = subprocess.run([str(exe)], cwd=tmp_path, capture_output=True, text=True, timeout=120)
+        assert "load 0 src 3400 tgt 3400" in r.stdout, r.stdout + r.stderr
         assert "no usable gfx950 HIP device" in r.stderr and "Result transform" not in r.stdout
 
 

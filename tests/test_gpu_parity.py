@@ -788,6 +788,36 @@ def test_bench_line_keeps_its_contract():
     assert abs(rr[2]["frac"] - rr[2]["achieved"] / 8000.0) < 1e-3
 
 
+def test_bench_dump_outputs_are_the_timed_runs_and_repeat(tmp_path):
+    """bench.py --dump-outputs DIR: the timed path's last results as .npy files (float32 / float64), the same whatever the
+    warmup, since the inputs are regenerated bit for bit from the arguments; --steps is the number of timed steps"""
+    import json
+    import subprocess
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    from symmicp import synth
+    truth = synth.c4_surface(20000)["truth"]
+    dumps = []
+    for w in (0, 2):
+        d = tmp_path / ("w%d" % w)
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--points", "20000", "--steps", "5", "--warmup", str(w),
+                            "--no-cpu-baseline", "--dump-outputs", str(d)], capture_output=True, text=True, timeout=600, cwd=root)
+        assert r.returncode == 0, r.stderr[-2000:]
+        line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
+        assert line["steps"] == 5 and line["ms_per_step"] > 0
+        files = sorted(os.listdir(d))
+        assert files == sorted(n + ".npy" for n in ("transform", "diffs", "diff_initial", "diff_final", "corr_index", "corr_dist2")), files
+        a = {f[:-4]: np.load(d / f) for f in files}
+        assert all(v.dtype in (np.float32, np.float64) for v in a.values())
+        assert sum(v.nbytes for v in a.values()) <= 64 << 20
+        assert a["transform"].shape == (4, 4) and len(a["diffs"]) == 5 and a["corr_index"].shape == (20000,)
+        assert abs(float(np.abs(a["transform"] - truth).max()) - line["final_transform_max_abs_err_vs_truth"]) < 1e-6
+        assert a["corr_index"].min() >= 0 and a["corr_index"].max() < 20000
+        dumps.append(a)
+    assert np.array_equal(dumps[0]["corr_index"], dumps[1]["corr_index"])
+    for k in ("transform", "diffs", "corr_dist2"):
+        np.testing.assert_allclose(dumps[0][k], dumps[1][k], rtol=1e-5, atol=1e-6)
+
+
 def test_bench_brute_force_is_priced_against_vector_issue():
     import json
     import subprocess
