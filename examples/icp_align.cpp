@@ -4,6 +4,8 @@
 //     --mode quirks|paper      arithmetic: the reference as written (default) or the paper-correct form
 //     --corr identity|tree     pairing: by row (default, what the reference does) or exact nearest neighbours
 //     --iters N                iteration cap            (default 10, ICP/myicp.cpp:6)
+//     --loss none|huber|tukey|cauchy|gm   robust loss of the paper loop (default none; not with --mode quirks)
+//     --loss-scale S           its scale (PAPER: in units of c = (p - q).(n_p + n_q), about twice the point-to-plane distance)
 //     --threshold D            stop once the summed pair distance is <= D   (default 1.0, ICP/myicp.cpp:6)
 //     --out aligned.pcd        write the source moved by the result (the reference only prints its result)
 //     --quiet                  no per-iteration lines
@@ -12,6 +14,7 @@
 //
 // The drop-in property itself -- the reference's ICP/main.cpp compiling byte-unchanged against include/myicp.h -- is
 // checked in the build container by tests/test_abi.py; this program is the repo's own driver for the same class.
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -22,7 +25,8 @@
 
 static int usage(const char *argv0, const char *complaint)
 {
-    std::fprintf(stderr, "%s\nusage: %s [--mode quirks|paper] [--corr identity|tree] [--iters N] [--threshold D] [--out file.pcd] [--quiet] [source.pcd target.pcd]\n",
+    std::fprintf(stderr, "%s\nusage: %s [--mode quirks|paper] [--corr identity|tree] [--iters N] [--threshold D] [--loss none|huber|tukey|cauchy|gm]"
+                 " [--loss-scale S] [--out file.pcd] [--quiet] [source.pcd target.pcd]\n",
                  complaint, argv0);
     return 64;
 }
@@ -32,6 +36,10 @@ int main(int argc, char **argv)
     std::vector<std::string> files;
     std::string out_path;
     MyICP icp;
+    bool quirks = true;                      // (the class default)
+    symmicp_loss loss = SYMMICP_LOSS_NONE;
+    float loss_scale = 0.f;
+    bool have_scale = false;
     for (int k = 1; k < argc; k++) {
         const std::string a = argv[k];
         auto value = [&](const char *what) -> const char * {
@@ -40,8 +48,8 @@ int main(int argc, char **argv)
         };
         if (a == "--mode") {
             const std::string v = value("--mode");
-            if (v == "quirks") icp.setMode(SYMMICP_MODE_QUIRKS);
-            else if (v == "paper") icp.setMode(SYMMICP_MODE_PAPER);
+            if (v == "quirks") { icp.setMode(SYMMICP_MODE_QUIRKS); quirks = true; }
+            else if (v == "paper") { icp.setMode(SYMMICP_MODE_PAPER); quirks = false; }
             else return usage(argv[0], "unknown --mode");
         } else if (a == "--corr") {
             const std::string v = value("--corr");
@@ -50,6 +58,21 @@ int main(int argc, char **argv)
             else return usage(argv[0], "unknown --corr");
         } else if (a == "--iters") icp.setMaximumIterations(std::atoi(value("--iters")));
         else if (a == "--threshold") icp.setDiffThreshold((float)std::atof(value("--threshold")));
+        else if (a == "--loss") {
+            const std::string v = value("--loss");
+            if (v == "none") loss = SYMMICP_LOSS_NONE;
+            else if (v == "huber") loss = SYMMICP_LOSS_HUBER;
+            else if (v == "tukey") loss = SYMMICP_LOSS_TUKEY;
+            else if (v == "cauchy") loss = SYMMICP_LOSS_CAUCHY;
+            else if (v == "gm") loss = SYMMICP_LOSS_GEMAN_MCCLURE;
+            else return usage(argv[0], "unknown --loss");
+        } else if (a == "--loss-scale") {
+            char *end = nullptr;
+            const char *v = value("--loss-scale");
+            loss_scale = std::strtof(v, &end);
+            if (end == v || *end) return usage(argv[0], "--loss-scale needs a number");
+            have_scale = true;
+        }
         else if (a == "--out") out_path = value("--out");
         else if (a == "--quiet") icp.setVerbose(false);
         else if (!a.empty() && a[0] == '-') return usage(argv[0], ("unknown option " + a).c_str());
@@ -57,6 +80,11 @@ int main(int argc, char **argv)
     }
     if (files.empty()) files = {"cat.pcd", "cat_out.pcd"};
     if (files.size() != 2) return usage(argv[0], "expected two PCD files");
+    if (loss != SYMMICP_LOSS_NONE) {
+        if (quirks) return usage(argv[0], "--loss needs --mode paper (quirks is the reference as written)");
+        if (!have_scale || !(loss_scale > 0.f) || !std::isfinite(loss_scale)) return usage(argv[0], "--loss needs --loss-scale S with S > 0");
+        icp.setRobustLoss(loss, loss_scale);
+    }
 
     icp.LoadCloud(files[0], files[1]);
     if (icp.GetSrcCloud()->points.empty() || icp.GetTgtCloud()->points.empty()) {

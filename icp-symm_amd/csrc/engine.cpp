@@ -8,6 +8,8 @@
 //   spin on the record's sequence word in host-mapped memory -> repeat.
 // There is no CPU fallback: without a HIP device every entry point fails loudly.
 #include "engine_internal.h"
+#include "robust_loss.h"
+#include <limits>
 
 void read_switches(Switches &w)
 {
@@ -212,11 +214,47 @@ int symmicp_set_config(symmicp_ctx *c, const symmicp_config *cfg)
     // correspondence kind decides device layouts: it can only change before clouds are set
     if ((c->n_t || c->n_loc) && cfg->corr != c->cfg.corr) return fail(c, SYMMICP_ERR_STATE, "corr cannot change after clouds are set");
     if ((c->n_t || c->n_loc) && cfg->sort_source != c->cfg.sort_source) return fail(c, SYMMICP_ERR_STATE, "sort_source cannot change after clouds are set");
+    if (cfg->mode == SYMMICP_MODE_QUIRKS && c->loss != SYMMICP_LOSS_NONE)
+        return fail(c, SYMMICP_ERR_ARG, "QUIRKS takes no robust loss (set SYMMICP_LOSS_NONE first)");
     int dev = c->cfg.device;
     c->cfg = *cfg;
     c->cfg.device = dev;
     c->begun = false;
     return SYMMICP_OK;
+}
+
+// ---- robust loss ---------------------------------------------------------------------------------
+static bool loss_args_ok(int loss, float scale)
+{
+    if (loss < SYMMICP_LOSS_NONE || loss > SYMMICP_LOSS_GEMAN_MCCLURE) return false;
+    return loss == SYMMICP_LOSS_NONE || (std::isfinite(scale) && scale > 0.f);
+}
+
+int symmicp_set_robust_loss(symmicp_ctx *c, int loss, float scale)
+{
+    if (!c) return SYMMICP_ERR_ARG;
+    if (!loss_args_ok(loss, scale)) return fail(c, SYMMICP_ERR_ARG, "robust loss: unknown loss, or scale not finite and > 0");
+    if (loss != SYMMICP_LOSS_NONE && c->cfg.mode == SYMMICP_MODE_QUIRKS) return fail(c, SYMMICP_ERR_ARG, "QUIRKS takes no robust loss");
+#if defined(RS_STAMPS) || defined(RS_STAMPS2)
+    if (loss != SYMMICP_LOSS_NONE) return fail(c, SYMMICP_ERR_ARG, "a build with RS_STAMPS keeps its stamps in slots 37..39: no robust loss");
+#endif
+    c->loss = loss;
+    c->loss_scale = loss == SYMMICP_LOSS_NONE ? 0.f : scale;
+    return SYMMICP_OK;
+}
+
+int symmicp_get_robust_loss(const symmicp_ctx *c, int *loss, float *scale)
+{
+    if (!c) return SYMMICP_ERR_ARG;
+    if (loss) *loss = c->loss;
+    if (scale) *scale = c->loss_scale;
+    return SYMMICP_OK;
+}
+
+float symmicp_robust_weight(int loss, float scale, float r)
+{
+    if (!loss_args_ok(loss, scale)) return std::numeric_limits<float>::quiet_NaN();
+    return loss == SYMMICP_LOSS_NONE ? 1.0f : robust_weight(loss, scale, r);
 }
 
 // host strided cloud -> device block of 6 planar arrays.  The usual layouts never touch a host staging loop: records with

@@ -131,6 +131,8 @@ struct symmicp_ctx {
     std::vector<void *> keep_extra;  // ... and those that did not fit
     ShmExchange shm;
     symmicp_config cfg{};
+    int loss = SYMMICP_LOSS_NONE;    // robust loss (symmicp_set_robust_loss) and its scale: read by every pass
+    float loss_scale = 0.f;
     int device = 0;
     hipStream_t stream = nullptr;
     std::string err;

@@ -43,6 +43,8 @@ static void fill_pass_args(symmicp_ctx *c, PassArgs &a, const float Xapply[16], 
     a.pkt_fallbacks = c->pkt_fallbacks;
     a.pkt_chunk = c->sw.packet_chunk;
     a.pkt_lds_pad = c->sw.packet_lds_pad;
+    a.loss = c->loss;
+    a.loss_scale = c->loss_scale;
 }
 
 static int run_pass(symmicp_ctx *c, const float Xapply[16], bool from_cur, bool writeback, bool first)
@@ -164,7 +166,7 @@ static int run_pass(symmicp_ctx *c, const float Xapply[16], bool from_cur, bool 
     if (int st = reduce_and_wait(optimistic ? 1 : 0)) return st;
     if (c->shm.slots) { if (int st = shm_exchange(c, c->h_sums)) return st; }
     // length of the work list (summed over ranks by the exchange, so every rank takes the same decision)
-    if (c->cfg.corr == SYMMICP_CORR_TREE && c->h_sums[kNSum - 3] != 0.0)
+    if (c->cfg.corr == SYMMICP_CORR_TREE && c->h_sums[kNSum - 1] >= kListDropped)
         return fail(c, SYMMICP_ERR_HIP, "a work-list shard overflowed: appends were dropped (internal capacity error)");
     long long list_len = (c->cfg.corr == SYMMICP_CORR_TREE) ? (long long)c->h_sums[kNSum - 1] : -1;
     c->last_uncertified = (c->cfg.corr == SYMMICP_CORR_TREE && !first) ? (long long)c->h_sums[kNSum - 2] : -1;
@@ -181,7 +183,7 @@ static int run_pass(symmicp_ctx *c, const float Xapply[16], bool from_cur, bool 
     if (c->dbg_trace && first) dump_packet_trace(c);
     if (c->ix.dbg) print_pass_counters(c, first, list_len);
     std::memcpy(c->last.s, c->h_sums, sizeof(double) * kNSum);
-    if (c->cfg.corr == SYMMICP_CORR_TREE) c->last.s[kNSum - 1] = c->last.s[kNSum - 2] = c->last.s[kNSum - 3] = 0.0;      // those slots carried the list length and the number of searched pairs, not sums
+    if (c->cfg.corr == SYMMICP_CORR_TREE) c->last.s[kNSum - 1] = c->last.s[kNSum - 2] = 0.0;      // those slots carried the list length and the number of searched pairs, not sums
     c->last_list_len = list_len;
     // the packet first pass has no work list; the pass after it (the cloud has just moved by its whole misalignment) always has one:
     // -2 = "expect a list" (no optimistic skip of the walk, which would only be repaired; a mid-sized walk grid)
@@ -443,7 +445,7 @@ static void fill_iter(symmicp_ctx *c, symmicp_iter_result *out, int status, floa
     out->iter = c->iters;
     out->diff = (float)c->last.s[33];
     out->rcond = rcond;
-    out->pairs = c->last.s[34];
+    out->pairs = c->last.s[c->loss != SYMMICP_LOSS_NONE ? 37 : 34];      // (with a robust loss slot 34 is the sum of the weights)
     if (incr) std::memcpy(out->increment, incr, sizeof(float) * 16); else identity16(out->increment);
     out->sums = c->last;
 }

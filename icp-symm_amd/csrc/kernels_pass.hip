@@ -19,6 +19,7 @@
 #include "device_common.h"
 #include "oct_walk.h"
 #include "solve_core.h"
+#include "robust_loss.h"
 #pragma clang fp contract(off)
 
 namespace symmicp {
@@ -26,14 +27,21 @@ namespace symmicp {
 // ---------------------------------------------------------------------------
 // small device helpers
 // ---------------------------------------------------------------------------
-struct Acc {
-    double v[kNAcc];
+template <int NA>
+struct AccN {
+    double v[NA];
 };
+typedef AccN<kNAcc> Acc;
+// W = true: the weighted instantiations of the accumulating kernels (robust loss), one accumulator more (slot 37: the pair count).
+// A separate instantiation, not a branch: the unweighted kernels keep their registers and occupancy (the fused pass is register-bound).
+template <bool W>
+using AccT = AccN<W ? kNAccW : kNAcc>;
 
-__device__ __forceinline__ void acc_zero(Acc &a)
+template <int NA>
+__device__ __forceinline__ void acc_zero(AccN<NA> &a)
 {
 #pragma unroll
-    for (int k = 0; k < kNAcc; k++) a.v[k] = 0.0;
+    for (int k = 0; k < NA; k++) a.v[k] = 0.0;
 }
 
 // rows of func.cpp:51-58 for one pair, accumulated in fp64
@@ -81,6 +89,67 @@ __device__ __forceinline__ void acc_pair(Acc &a, float px, float py, float pz, f
     a.v[36] += (double)d2;
 }
 
+// the kernels call one signature for both instantiations: the unweighted record ignores the loss
+__device__ __forceinline__ void acc_pair(Acc &a, float px, float py, float pz, float npx, float npy, float npz,
+                                         float qx, float qy, float qz, float nqx, float nqy, float nqz,
+                                         float d2, const float *pivot, int p2p, int, float)
+{
+    acc_pair(a, px, py, pz, npx, npy, npz, qx, qy, qz, nqx, nqy, nqz, d2, pivot, p2p);
+}
+
+// the same rows with the pair weighted by its robust-loss weight w (robust_loss.h) of r = c (PAPER) or |p - q| (P2P): every sum but
+// 33 and 36 is scaled by w, slot 34 sums w, slot 37 counts the pairs
+__device__ __forceinline__ void acc_pair(AccN<kNAccW> &a, float px, float py, float pz, float npx, float npy, float npz,
+                                         float qx, float qy, float qz, float nqx, float nqy, float nqz,
+                                         float d2, const float *pivot, int p2p, int loss, float scale)
+{
+    px -= pivot[0]; py -= pivot[1]; pz -= pivot[2];
+    qx -= pivot[0]; qy -= pivot[1]; qz -= pivot[2];
+    if (p2p) {
+        const float dist = sqrtf(d2);
+        const double w = (double)robust_weight(loss, scale, dist);
+        const double P[3] = {(double)px, (double)py, (double)pz}, Q[3] = {(double)qx, (double)qy, (double)qz};
+        const double WP[3] = {w * P[0], w * P[1], w * P[2]};
+#pragma unroll
+        for (int r = 0; r < 3; r++)
+#pragma unroll
+            for (int c = 0; c < 3; c++) a.v[3 * r + c] = __builtin_fma(WP[r], Q[c], a.v[3 * r + c]);
+#pragma unroll
+        for (int k = 0; k < 3; k++) { a.v[27 + k] += WP[k]; a.v[30 + k] = __builtin_fma(w, Q[k], a.v[30 + k]); }
+        a.v[33] += (double)dist;
+        a.v[34] += w;
+        a.v[36] += (double)d2;
+        a.v[37] += 1.0;
+        return;
+    }
+    float nx = npx + nqx, ny = npy + nqy, nz = npz + nqz;
+    float sx = px + qx, sy = py + qy, sz = pz + qz;
+    float dx = px - qx, dy = py - qy, dz = pz - qz;
+    float m0 = sy * nz - sz * ny;
+    float m1 = sz * nx - sx * nz;
+    float m2 = sx * ny - sy * nx;
+    float c = (dx * nx + dy * ny) + dz * nz;
+    const double w = (double)robust_weight(loss, scale, c);
+    const double v[6] = {(double)m0, (double)m1, (double)m2, (double)nx, (double)ny, (double)nz};
+    const double cd = (double)c, wc = w * cd;
+    int k = 0;
+#pragma unroll
+    for (int r = 0; r < 6; r++) {
+        const double wv = w * v[r];
+#pragma unroll
+        for (int s = r; s < 6; s++) { a.v[k] = __builtin_fma(wv, v[s], a.v[k]); k++; }
+    }
+#pragma unroll
+    for (int r = 0; r < 6; r++) a.v[21 + r] = __builtin_fma(v[r], wc, a.v[21 + r]);
+    a.v[27] = __builtin_fma(w, (double)px, a.v[27]); a.v[28] = __builtin_fma(w, (double)py, a.v[28]); a.v[29] = __builtin_fma(w, (double)pz, a.v[29]);
+    a.v[30] = __builtin_fma(w, (double)qx, a.v[30]); a.v[31] = __builtin_fma(w, (double)qy, a.v[31]); a.v[32] = __builtin_fma(w, (double)qz, a.v[32]);
+    a.v[33] += (double)sqrtf(d2);
+    a.v[34] += w;
+    a.v[35] = __builtin_fma(wc, cd, a.v[35]);
+    a.v[36] += (double)d2;
+    a.v[37] += 1.0;
+}
+
 // one step of a sum on the VALU's DPP cross-lane network (no LDS traffic): row_shr 1,2,4,8 builds 16-lane row sums.  A double moves
 // as two 32-bit DPP movs; lanes without a source read 0 (bound_ctrl), i.e. add +0.0.
 template <int CTRL, int ROW_MASK>
@@ -114,14 +183,16 @@ __device__ __forceinline__ double swap16_add(double a, double b)
 // record k of block b lands at partials[b * kNSum + k]: one contiguous 320-byte burst per block.  (Round 2 stored it transposed,
 // [k][block], so that the reduce could read along the blocks: 40 scattered 8-byte stores per block into lines shared with up to 15
 // other blocks -- on other XCDs, i.e. other L2s -- and a reduce whose load phase alone took 5.9 us of k_reduce_solve's 11.5.)
-__device__ __forceinline__ void acc_block_reduce_store(Acc &a, double *partials, uint32_t nblocks, uint32_t col)
+template <int NA>
+__device__ __forceinline__ void acc_block_reduce_store(AccN<NA> &a, double *partials, uint32_t nblocks, uint32_t col)
 {
-    static_assert(kNSum == 40 && kNAcc <= 40, "the halving below pairs value k with k + 20, then k + 10");
+    // (value 37 of the weighted record rides in the upper half-wave of h1[17], then in row 3 of h2[7])
+    static_assert(kNSum == 40 && NA <= 40, "the halving below pairs value k with k + 20, then k + 10");
     __shared__ double red[(kPassThreads / 64) * kNSum];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     double h1[20], h2[10];
 #pragma unroll
-    for (int k = 0; k < 20; k++) h1[k] = swap32_add(k < kNAcc ? a.v[k] : 0.0, k + 20 < kNAcc ? a.v[k + 20] : 0.0);
+    for (int k = 0; k < 20; k++) h1[k] = swap32_add(k < NA ? a.v[k] : 0.0, k + 20 < NA ? a.v[k + 20] : 0.0);
 #pragma unroll
     for (int k = 0; k < 10; k++) h2[k] = swap16_add(h1[k], h1[k + 10]);
 #pragma unroll
@@ -136,7 +207,7 @@ __device__ __forceinline__ void acc_block_reduce_store(Acc &a, double *partials,
     __syncthreads();
     if (threadIdx.x < kNSum) {
         double s = 0.0;
-        if (threadIdx.x < kNAcc) {
+        if (threadIdx.x < NA) {
 #pragma unroll
             for (int w = 0; w < kPassThreads / 64; w++) s += red[w * kNSum + threadIdx.x];
         }
@@ -145,7 +216,8 @@ __device__ __forceinline__ void acc_block_reduce_store(Acc &a, double *partials,
     (void)nblocks;
 }
 
-__device__ __forceinline__ void acc_block_reduce_store(Acc &a, double *partials, uint32_t nblocks) { acc_block_reduce_store(a, partials, nblocks, blockIdx.x); }
+template <int NA>
+__device__ __forceinline__ void acc_block_reduce_store(AccN<NA> &a, double *partials, uint32_t nblocks) { acc_block_reduce_store(a, partials, nblocks, blockIdx.x); }
 
 // ---------------------------------------------------------------------------
 // pass, identity pairing (what the reference does: myicp.cpp:130)
@@ -154,13 +226,13 @@ __device__ __forceinline__ void acc_block_reduce_store(Acc &a, double *partials,
 // VEC = 4: each thread handles 4 consecutive points per step with 16-byte loads/stores from the planar
 // arrays (needs n, the target offset and the array lengths to be multiples of 4 so every column stays
 // 16-byte aligned); VEC = 1 is the general form.
-template <int VEC>
+template <int VEC, bool W>
 __global__ __launch_bounds__(kPassThreads) void k_pass_identity(PassArgs a_in, CloudSoA tgt)
 {
     if (a_in.loop && a_in.loop->stop) return;
     PassArgs a = a_in;
     if (a_in.loop) a.X = a_in.loop->Xapply;        // device-driven loop: the transform k_reduce_solve left behind
-    Acc acc; acc_zero(acc);
+    AccT<W> acc; acc_zero(acc);
     const uint32_t stride = gridDim.x * blockDim.x * VEC;
     for (uint32_t i0 = (blockIdx.x * blockDim.x + threadIdx.x) * VEC; i0 < a.n; i0 += stride) {
         float x[VEC], y[VEC], z[VEC], nx[VEC], ny[VEC], nz[VEC], qx[VEC], qy[VEC], qz[VEC], qnx[VEC], qny[VEC], qnz[VEC];
@@ -214,7 +286,7 @@ __global__ __launch_bounds__(kPassThreads) void k_pass_identity(PassArgs a_in, C
         for (int k = 0; k < VEC; k++) {
             if (a.max_d2 > 0.0f && d2[k] > a.max_d2) continue;
             if (a.min_ndot > -1.0f && (npx[k] * qnx[k] + npy[k] * qny[k]) + npz[k] * qnz[k] < a.min_ndot) continue;
-            acc_pair(acc, px[k], py[k], pz[k], npx[k], npy[k], npz[k], qx[k], qy[k], qz[k], qnx[k], qny[k], qnz[k], d2[k], a.pivot, a.p2p);
+            acc_pair(acc, px[k], py[k], pz[k], npx[k], npy[k], npz[k], qx[k], qy[k], qz[k], qnx[k], qny[k], qnz[k], d2[k], a.pivot, a.p2p, a.loss, a.loss_scale);
         }
     }
     acc_block_reduce_store(acc, a.partials, gridDim.x);
@@ -224,9 +296,10 @@ __global__ __launch_bounds__(kPassThreads) void k_pass_identity(PassArgs a_in, C
 // pass, pairs given by a previous search kernel (brute force): best64[i] holds
 // (d2 bits << 32 | target row).  Target rows are gathered as float4.
 // ---------------------------------------------------------------------------
+template <bool W>
 __global__ __launch_bounds__(kPassThreads) void k_pass_indexed(PassArgs a, const float4 *__restrict__ tn)
 {
-    Acc acc; acc_zero(acc);
+    AccT<W> acc; acc_zero(acc);
     const uint32_t stride = gridDim.x * blockDim.x;
     for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < a.n; i += stride) {
         float x = a.in.x[i], y = a.in.y[i], z = a.in.z[i];
@@ -248,7 +321,7 @@ __global__ __launch_bounds__(kPassThreads) void k_pass_indexed(PassArgs a, const
         if (a.max_d2 > 0.0f && d2 > a.max_d2) continue;
         const float4 q = tn[2 * (size_t)j], nq = tn[2 * (size_t)j + 1];     // one 32-byte pair record
         if (a.min_ndot > -1.0f && (npx * nq.x + npy * nq.y) + npz * nq.z < a.min_ndot) continue;
-        acc_pair(acc, px, py, pz, npx, npy, npz, q.x, q.y, q.z, nq.x, nq.y, nq.z, d2, a.pivot, a.p2p);
+        acc_pair(acc, px, py, pz, npx, npy, npz, q.x, q.y, q.z, nq.x, nq.y, nq.z, d2, a.pivot, a.p2p, a.loss, a.loss_scale);
     }
     acc_block_reduce_store(acc, a.partials, gridDim.x);
 }
@@ -846,16 +919,19 @@ struct HotParams {
     float pivot[3];
     float max_d2, min_ndot;
     int32_t p2p;
+    int32_t loss;            // (set and read by the weighted instantiation only)
+    float loss_scale;
 };
 
-__device__ __forceinline__ void fused_accumulate(Acc &acc, const HotParams &h, float nx, float ny, float nz, float px, float py, float pz,
+template <int NA>
+__device__ __forceinline__ void fused_accumulate(AccN<NA> &acc, const HotParams &h, float nx, float ny, float nz, float px, float py, float pz,
                                                  const float4 &q, const float4 &nq, float d2)
 {
     const Affine &X = h.X;
     const float npx = xf_row(X.m + 0, nx, ny, nz, X.nrm_w), npy = xf_row(X.m + 4, nx, ny, nz, X.nrm_w), npz = xf_row(X.m + 8, nx, ny, nz, X.nrm_w);
     if (h.max_d2 > 0.0f && d2 > h.max_d2) return;
     if (h.min_ndot > -1.0f && (npx * nq.x + npy * nq.y) + npz * nq.z < h.min_ndot) return;
-    acc_pair(acc, px, py, pz, npx, npy, npz, q.x, q.y, q.z, nq.x, nq.y, nq.z, d2, h.pivot, h.p2p);
+    acc_pair(acc, px, py, pz, npx, npy, npz, q.x, q.y, q.z, nq.x, nq.y, nq.z, d2, h.pivot, h.p2p, h.loss, h.loss_scale);
 }
 
 #ifndef FUSED_WAVES
@@ -871,9 +947,11 @@ __device__ __forceinline__ void fused_accumulate(Acc &acc, const HotParams &h, f
 // that is still settling: the separate k_search_cells lets every block of 256 queries pay the latency of the whole scan machinery
 // for the dozen of them that need it; here a block streams several tiles and scans the failures 256 at a time (the walk and
 // k_accumulate follow as usual).  No normals, no record copies read, no sums: registers for 5 waves per SIMD.
-template <bool ACC>
+// W (with ACC): the weighted record of a robust loss.
+template <bool ACC, bool W>
 __global__ __launch_bounds__(kPassThreads, ACC ? FUSED_WAVES : COMPACT_WAVES) void k_pass_fused(PassArgs a, TargetIndex ix, WorkLists wl)
 {
+    static_assert(ACC || !W, "the search-only form has no sums to weight");
     constexpr int kList = ACC ? kFusedList : kFusedList / 2;      // (the search-only form keeps 5 workgroups per CU: its tile is 256 points)
     __shared__ uint32_t s_list[kList];
     __shared__ uint32_t s_cnt, s_total;
@@ -881,7 +959,7 @@ __global__ __launch_bounds__(kPassThreads, ACC ? FUSED_WAVES : COMPACT_WAVES) vo
     // device-driven loop: stop flag and transform come from device memory, written by the kernel just before this one -- a cold round trip.
     // They are requested here and first LOOKED AT behind the first tile's loads (which do not depend on them): one round trip, not two
     // (behind the barrier: scalar loads and LDS stores share a counter, and the barrier waits for it)
-    Acc acc;
+    AccT<W> acc;
     if (ACC) acc_zero(acc);
     if (threadIdx.x == 0) { s_cnt = 0; s_total = 0; }
     if (ACC && threadIdx.x == 0) {
@@ -915,6 +993,7 @@ __global__ __launch_bounds__(kPassThreads, ACC ? FUSED_WAVES : COMPACT_WAVES) vo
     for (int k = 0; k < 3; k++) h.pivot[k] = ACC ? in_vgpr(a.pivot[k]) : a.pivot[k];
     h.max_d2 = ACC ? in_vgpr(a.max_d2) : a.max_d2; h.min_ndot = ACC ? in_vgpr(a.min_ndot) : a.min_ndot;
     h.p2p = a.p2p;
+    if (W) { h.loss = a.loss; h.loss_scale = in_vgpr(a.loss_scale); }
 #ifdef RS_STAMPS2
     const unsigned long long fs0 = __builtin_amdgcn_s_memrealtime();
     unsigned long long fs1 = 0;
@@ -1275,9 +1354,10 @@ __global__ __launch_bounds__(kWalkThreads, 6) void k_search_walk(PassArgs a, Tar
 // The pair's distance is recomputed from the gathered q (bit-identical to the stored one) instead of being read.
 // (A 4-points-per-thread variant with 16-byte column loads was measured and is no faster: the two 16-byte gathers per
 // pair bound this kernel, not the column loads.  Few blocks are: each one ends in a 40-value block reduction.)
+template <bool W>
 __global__ __launch_bounds__(kPassThreads) void k_accumulate(PassArgs a, const float4 *__restrict__ tn)
 {
-    Acc acc; acc_zero(acc);
+    AccT<W> acc; acc_zero(acc);
     const uint32_t nbp = gridDim.x;
     // grid-stride over blocks of 256 points, XCD-contiguous
     const uint32_t total_blocks = (a.n + kPassThreads - 1) / kPassThreads;
@@ -1305,7 +1385,7 @@ __global__ __launch_bounds__(kPassThreads) void k_accumulate(PassArgs a, const f
         const float d2 = dist2(px, py, pz, q.x, q.y, q.z);
         if (a.max_d2 > 0.0f && d2 > a.max_d2) continue;
         if (a.min_ndot > -1.0f && (npx * nq.x + npy * nq.y) + npz * nq.z < a.min_ndot) continue;
-        acc_pair(acc, px, py, pz, npx, npy, npz, q.x, q.y, q.z, nq.x, nq.y, nq.z, d2, a.pivot, a.p2p);
+        acc_pair(acc, px, py, pz, npx, npy, npz, q.x, q.y, q.z, nq.x, nq.y, nq.z, d2, a.pivot, a.p2p, a.loss, a.loss_scale);
     }
     acc_block_reduce_store(acc, a.partials, gridDim.x);
 }
@@ -1318,13 +1398,14 @@ __global__ __launch_bounds__(kPassThreads) void k_accumulate(PassArgs a, const f
 // Straggler stage of a device-driven loop (after k_pass_fused and k_search_walk): the pairs of the work list's queries -- the fused pass
 // left them out and marked their record copies stale -- are gathered, their copies refreshed, their rows summed into `gridDim.x` partial
 // columns behind the fused pass's.  Launched whether or not the list is empty (the columns must be written).
+template <bool W>
 __global__ __launch_bounds__(kPassThreads) void k_accumulate_list(PassArgs a, const float4 *__restrict__ tn, ShardList list)
 {
     if (a.loop) {
         if (a.loop->stop) return;
         a.X = a.loop->Xapply;
     }
-    Acc acc; acc_zero(acc);
+    AccT<W> acc; acc_zero(acc);
     // block b: shards b, b + gridDim.x, ...; its waves take them in turn (a list is a handful of entries: what counts is that the
     // counters and entries of all shards are requested side by side, not one shard after the other)
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -1345,7 +1426,7 @@ __global__ __launch_bounds__(kPassThreads) void k_accumulate_list(PassArgs a, co
             const float d2 = dist2(px, py, pz, q.x, q.y, q.z);
             if (a.max_d2 > 0.0f && d2 > a.max_d2) continue;
             if (a.min_ndot > -1.0f && (npx * nq.x + npy * nq.y) + npz * nq.z < a.min_ndot) continue;
-            acc_pair(acc, px, py, pz, npx, npy, npz, q.x, q.y, q.z, nq.x, nq.y, nq.z, d2, a.pivot, a.p2p);
+            acc_pair(acc, px, py, pz, npx, npy, npz, q.x, q.y, q.z, nq.x, nq.y, nq.z, d2, a.pivot, a.p2p, a.loss, a.loss_scale);
         }
     }
     acc_block_reduce_store(acc, a.partials, a.partial_cols, a.partial_col0 + blockIdx.x);
@@ -1405,9 +1486,11 @@ __global__ __launch_bounds__(256) void k_final_reduce(const double *__restrict__
                 read_list_words(counters_to_clear, t, len, searched, dropped);
                 if (t == 0) {
                     s_len = len;
-                    // the record's spare slots: list length, pairs searched this pass (cells_tile), dropped appends (sl_push: must be 0)
-                    out_dev[kNSum - 1] = (double)len; out_dev[kNSum - 2] = (double)searched; out_dev[kNSum - 3] = (double)dropped;
-                    if (out_host) { out_host[kNSum - 1] = (double)len; out_host[kNSum - 2] = (double)searched; out_host[kNSum - 3] = (double)dropped; }
+                    // the record's spare slots: list length (+ kListDropped if appends were dropped -- sl_push: must not happen), pairs
+                    // searched this pass (cells_tile).  (Slot 37 is a sum: the pair count of a weighted record.)
+                    const double lenw = (double)len + (dropped ? kListDropped : 0.0);
+                    out_dev[kNSum - 1] = lenw; out_dev[kNSum - 2] = (double)searched;
+                    if (out_host) { out_host[kNSum - 1] = lenw; out_host[kNSum - 2] = (double)searched; }
                 }
             }
             __syncthreads();
@@ -1488,7 +1571,7 @@ __global__ __launch_bounds__(512) void k_reduce_solve(const double *__restrict__
             double x = 0.0;
 #pragma unroll
             for (int w = 0; w < 8; w++) x += s_part[w][t];
-            s_sum[t] = (t < kNAcc) ? x : 0.0;
+            s_sum[t] = (t < kNAccW) ? x : 0.0;
         }
     } else if (t < kNSum) s_sum[t] = rec;
     __syncthreads();
@@ -1507,7 +1590,7 @@ __global__ __launch_bounds__(512) void k_reduce_solve(const double *__restrict__
             for (int c = t; c < 2 * kShards; c += 512) counters_to_clear[c * kShardStride] = 0;
         } else if (t == 0) {
             // summed over the ranks by the all-reduce (k_final_reduce put them in the record)
-            s_len = (s_sum[kNSum - 3] != 0.0) ? 0xFFFFFFFFu : (uint32_t)s_sum[kNSum - 1];
+            s_len = (s_sum[kNSum - 1] >= kListDropped) ? 0xFFFFFFFFu : (uint32_t)s_sum[kNSum - 1];
             s_unc = (uint32_t)s_sum[kNSum - 2];
         }
     }
@@ -1524,7 +1607,7 @@ __global__ __launch_bounds__(512) void k_reduce_solve(const double *__restrict__
         if (cfg.tree && len > 0u && (!cfg.walk_in_loop || len == 0xFFFFFFFFu)) { if (t == 0) { loop->stop = 1; loop->reason = LOOP_REDO_PASS; } return; }
         it += 1;                                                        // this pass is complete
         LoopRecord &r = ring[it % ring_len];
-        if (t < kNSum) { const double v = (t >= kNAcc) ? 0.0 : s_sum[t]; r.sums[t] = v; if (REDUCE) out_dev[t] = v; }
+        if (t < kNSum) { const double v = (t >= kNAccW) ? 0.0 : s_sum[t]; r.sums[t] = v; if (REDUCE) out_dev[t] = v; }
         if (t == 0) {
             loop->iters = it;
             r.solved = 0;
@@ -1543,7 +1626,7 @@ __global__ __launch_bounds__(512) void k_reduce_solve(const double *__restrict__
     }
     // ---- func.cpp:76-102
     symmicp_sums S;
-    for (int k = 0; k < kNSum; k++) S.s[k] = (k >= kNAcc) ? 0.0 : s_sum[k];
+    for (int k = 0; k < kNSum; k++) S.s[k] = (k >= kNAccW) ? 0.0 : s_sum[k];
     float pbar[3], qbar[3], av[3], tv[3], rc = 0.f, Xi[16];
     const int st = (cfg.mode == SYMMICP_MODE_QUIRKS) ? solve::solve_quirks(S, pbar, qbar, av, tv, &rc, Xi, false)
                                                       : solve::solve_paper(S, cfg.pivot, pbar, qbar, av, tv, &rc, Xi, false);
@@ -1698,13 +1781,14 @@ void launch_identity_d2(const CloudSoA &in, const Affine &X, const CloudSoA &tgt
 // ---------------------------------------------------------------------------
 void launch_pass_identity(const PassArgs &a, CloudSoA tgt, int blocks, bool vec4_ok, hipStream_t s)
 {
-    if (vec4_ok) hipLaunchKernelGGL(k_pass_identity<4>, dim3(blocks), dim3(kPassThreads), 0, s, a, tgt);
-    else hipLaunchKernelGGL(k_pass_identity<1>, dim3(blocks), dim3(kPassThreads), 0, s, a, tgt);
+    const bool w = a.loss != SYMMICP_LOSS_NONE;
+    if (vec4_ok) hipLaunchKernelGGL((w ? k_pass_identity<4, true> : k_pass_identity<4, false>), dim3(blocks), dim3(kPassThreads), 0, s, a, tgt);
+    else hipLaunchKernelGGL((w ? k_pass_identity<1, true> : k_pass_identity<1, false>), dim3(blocks), dim3(kPassThreads), 0, s, a, tgt);
 }
 
 void launch_pass_indexed(const PassArgs &a, const float4 *tn, int blocks, hipStream_t s)
 {
-    hipLaunchKernelGGL(k_pass_indexed, dim3(blocks), dim3(kPassThreads), 0, s, a, tn);
+    hipLaunchKernelGGL(a.loss != SYMMICP_LOSS_NONE ? k_pass_indexed<true> : k_pass_indexed<false>, dim3(blocks), dim3(kPassThreads), 0, s, a, tn);
 }
 
 uint32_t shard_capacity(uint32_t n_points)
@@ -1734,7 +1818,7 @@ void launch_pass_tree_split(const PassArgs &a_in, const TargetIndex &ix, const W
     const uint32_t nbp = ((nb + 7u) / 8u) * 8u;
     if (ev) hipEventRecord(ev[0], s);
     if (stage != 2 && nbp) {      // (nbp == 0: a rank whose share is empty)
-        if (compact_blocks > 0) hipLaunchKernelGGL(k_pass_fused<false>, dim3(min((uint32_t)compact_blocks, nbp)), dim3(kPassThreads), 0, s, a, ix, wl);
+        if (compact_blocks > 0) hipLaunchKernelGGL((k_pass_fused<false, false>), dim3(min((uint32_t)compact_blocks, nbp)), dim3(kPassThreads), 0, s, a, ix, wl);
         else {
             const uint32_t chunk = tune.cells_chunk ? tune.cells_chunk : 16u;      // tiles per chunk
             // queries per tile: 256 while that fills the chip a few times over (256 CUs x 6-7 workgroups), else 128 or 64 (k_search_cells)
@@ -1764,13 +1848,13 @@ void launch_pass_tree_split(const PassArgs &a_in, const TargetIndex &ix, const W
         }
     }
     if (ev) hipEventRecord(ev[3], s);
-    hipLaunchKernelGGL(k_accumulate, dim3(acc_blocks), dim3(kPassThreads), 0, s, a, ix.tn);
+    hipLaunchKernelGGL(a.loss != SYMMICP_LOSS_NONE ? k_accumulate<true> : k_accumulate<false>, dim3(acc_blocks), dim3(kPassThreads), 0, s, a, ix.tn);
     if (ev) hipEventRecord(ev[4], s);
 }
 
 void launch_accumulate(const PassArgs &a, const float4 *tn, int blocks, hipStream_t s)
 {
-    hipLaunchKernelGGL(k_accumulate, dim3(blocks), dim3(kPassThreads), 0, s, a, tn);
+    hipLaunchKernelGGL(a.loss != SYMMICP_LOSS_NONE ? k_accumulate<true> : k_accumulate<false>, dim3(blocks), dim3(kPassThreads), 0, s, a, tn);
 }
 
 void launch_final_reduce(const double *partials, int blocks, double *out_dev, double *out_host_mapped, uint32_t *ticket,
@@ -1782,7 +1866,8 @@ void launch_final_reduce(const double *partials, int blocks, double *out_dev, do
 
 void launch_pass_fused(const PassArgs &a, const TargetIndex &ix, const WorkLists &wl, int blocks, hipStream_t s)
 {
-    hipLaunchKernelGGL(k_pass_fused<true>, dim3(blocks), dim3(kPassThreads), 0, s, a, ix, wl);
+    if (a.loss != SYMMICP_LOSS_NONE) hipLaunchKernelGGL((k_pass_fused<true, true>), dim3(blocks), dim3(kPassThreads), 0, s, a, ix, wl);
+    else hipLaunchKernelGGL((k_pass_fused<true, false>), dim3(blocks), dim3(kPassThreads), 0, s, a, ix, wl);
 }
 
 void launch_loop_stragglers(const PassArgs &a, const TargetIndex &ix, const WorkLists &wl, int list_blocks, const PassTuning &tune, hipStream_t s)
@@ -1790,7 +1875,7 @@ void launch_loop_stragglers(const PassArgs &a, const TargetIndex &ix, const Work
     // (short lists: the wave-per-entry regime; anything above the threshold strides one thread per entry over this grid)
     const uint32_t wave_mode_max = tune.wave_mode_max;
     hipLaunchKernelGGL(k_search_walk<false>, dim3(512), dim3(kWalkThreads), 0, s, a, ix, wl, wl.work, wave_mode_max, 0xFFFFFFFFu);
-    hipLaunchKernelGGL(k_accumulate_list, dim3(list_blocks), dim3(kPassThreads), 0, s, a, ix.tn, wl.work);
+    hipLaunchKernelGGL(a.loss != SYMMICP_LOSS_NONE ? k_accumulate_list<true> : k_accumulate_list<false>, dim3(list_blocks), dim3(kPassThreads), 0, s, a, ix.tn, wl.work);
 }
 
 void launch_reduce_solve(const double *partials, int blocks, double *out_dev, int mode, LoopState *loop, LoopConfig cfg, LoopRecord *ring, int ring_len,

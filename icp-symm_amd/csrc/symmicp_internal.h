@@ -10,6 +10,10 @@ namespace symmicp {
 
 constexpr int kNSum = SYMMICP_NSUM;   // 40 doubles per reduction record
 constexpr int kNAcc = 37;             // live accumulators (rest of the record is 0)
+constexpr int kNAccW = 38;            // ... of the weighted passes (robust loss): slot 37 = the unweighted pair count
+// TREE passes: the final reduce leaves the work list's length in slot 39 (and the pairs searched in 38); appends dropped for lack of
+// room (must not happen) add this to the length, so that it survives the sum over ranks
+constexpr double kListDropped = 4294967296.0;
 constexpr int kLeaf = 8;              // target points per leaf (8 x 16 B = one 128-B line)
 constexpr int kFan = 8;               // children per tree node
 constexpr int kMaxTreeLevels = 12;
@@ -152,6 +156,8 @@ struct PassArgs {
     uint32_t pkt_front_cap;             // ... frontier capacity per level (0: kFrontCap; smaller values force the depth-first fallback: tests)
     uint32_t *pkt_fallbacks;            // ... counts the packets that finished depth-first (may be null)
     uint32_t pkt_chunk, pkt_lds_pad;    // ... packets per XCD chunk (0: 64); extra dynamic LDS per workgroup (occupancy experiments)
+    int32_t loss;                       // robust loss (SYMMICP_LOSS_*): != NONE selects the weighted instantiation of every accumulating kernel
+    float loss_scale;                   // ... its scale (robust_loss.h)
 };
 
 // host-side launch tuning of the tree passes (environment switches, read once by the engine)

@@ -23,6 +23,9 @@ OK, ERR_ARG, ERR_SIZE, ERR_DEGENERATE, ERR_IO, ERR_HIP, ERR_STATE, ERR_COMM = ra
 MODE_QUIRKS, MODE_PAPER, MODE_P2P = 0, 1, 2
 CORR_IDENTITY, CORR_BRUTE, CORR_TREE = 0, 1, 2
 APPLY_DEFAULT, APPLY_INCREMENTAL, APPLY_CUMULATIVE = 0, 1, 2
+LOSS_NONE, LOSS_HUBER, LOSS_TUKEY, LOSS_CAUCHY, LOSS_GEMAN_MCCLURE = range(5)
+_LOSS_NAMES = {"none": LOSS_NONE, "huber": LOSS_HUBER, "tukey": LOSS_TUKEY, "cauchy": LOSS_CAUCHY,
+               "geman_mcclure": LOSS_GEMAN_MCCLURE}
 
 _STATUS_NAMES = {0: "OK", 1: "ERR_ARG", 2: "ERR_SIZE", 3: "ERR_DEGENERATE", 4: "ERR_IO", 5: "ERR_HIP",
                  6: "ERR_STATE", 7: "ERR_COMM"}
@@ -76,6 +79,7 @@ EXPORTS = [
     "symmicp_local_source_count", "symmicp_local_source_offset", "symmicp_get_certificates", "symmicp_solve", "symmicp_comm_get_unique_id",
     "symmicp_comm_init_rank", "symmicp_set_sums", "symmicp_comm_init_shm", "symmicp_shard_range", "symmicp_get_stats", "symmicp_reset_stats", "symmicp_enable_timing",
     "symmicp_pcd_read", "symmicp_pcd_write", "symmicp_estimate_normals", "symmicp_ctx_estimate_normals",
+    "symmicp_set_robust_loss", "symmicp_get_robust_loss", "symmicp_robust_weight",
 ]
 
 _lib = None
@@ -140,6 +144,10 @@ def lib():
     L.symmicp_pcd_read.restype = C.c_long
     L.symmicp_pcd_write.argtypes = [C.c_char_p, fp, fp, C.c_size_t, C.c_int]
     L.symmicp_estimate_normals.argtypes = [C.c_int, fp, C.c_size_t, C.c_size_t, C.c_size_t, C.c_int, fp, fp, fp]
+    L.symmicp_set_robust_loss.argtypes = [vp, C.c_int, C.c_float]
+    L.symmicp_get_robust_loss.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_float)]
+    L.symmicp_robust_weight.argtypes = [C.c_int, C.c_float, C.c_float]
+    L.symmicp_robust_weight.restype = C.c_float
     _lib = L
     return L
 
@@ -205,6 +213,27 @@ def solve(mode, sums, pivot=None):
         pv = _fptr(pivot)
     st = lib().symmicp_solve(mode, C.byref(S), pv, _fptr(pb), _fptr(qb), _fptr(a), _fptr(t), C.byref(rc), _fptr(X))
     return st, pb, qb, a, t, rc.value, X.reshape(4, 4)
+
+
+def loss_code(loss):
+    """a LOSS_* value from the enum or its name ("none", "huber", "tukey", "cauchy", "geman_mcclure"); unknown names raise
+    ValueError, unknown integers pass through (the library refuses them)"""
+    if isinstance(loss, str):
+        try:
+            return _LOSS_NAMES[loss.lower()]
+        except KeyError:
+            raise ValueError("unknown robust loss %r (one of %s)" % (loss, ", ".join(_LOSS_NAMES)))
+    return int(loss)
+
+
+def robust_weight(loss, scale, r):
+    """the weight the pass kernels give a pair of residual r (symmicp_robust_weight; NaN on bad arguments).  r may be an
+    array: the result is float32 of the same shape."""
+    f = lib().symmicp_robust_weight
+    code = loss_code(loss)
+    ra = np.asarray(r, np.float32)
+    out = np.array([f(code, float(scale), float(x)) for x in ra.reshape(-1)], np.float32).reshape(ra.shape)
+    return out if ra.ndim else float(out)
 
 
 def format_result(transform):
@@ -299,6 +328,16 @@ class Engine:
         for k in range(len(s.s)):
             s.s[k] = float(t[k])
         self._chk(self._L.symmicp_set_sums(self._h, C.byref(s)))
+
+    def set_robust_loss(self, loss, scale=1.0):
+        """M-estimator weights for the PAPER / P2P loop (LOSS_* or its name); takes effect at the next pass"""
+        self._chk(self._L.symmicp_set_robust_loss(self._h, loss_code(loss), float(scale)))
+
+    def robust_loss(self):
+        """-> (loss, scale)"""
+        lo, sc = C.c_int(0), C.c_float(0)
+        self._chk(self._L.symmicp_get_robust_loss(self._h, C.byref(lo), C.byref(sc)))
+        return lo.value, sc.value
 
     def set_source(self, xyz, nrm):
         xyz, nrm = _cloud(xyz), _cloud(nrm)
@@ -432,6 +471,11 @@ class MyICP:
         self.normals_src = self.normals_tgt = None
         self._final = np.eye(4, dtype=np.float32)
         self.last_result = None
+        self._loss = (LOSS_NONE, 0.0)
+
+    def setRobustLoss(self, loss, scale):
+        """robust loss of the next align (see Engine.set_robust_loss)"""
+        self._loss = (loss_code(loss), float(scale))
 
     def LoadCloud(self, src_path, tgt_path):
         # myicp.cpp:20-31 (reader status is ignored there; here a bad file raises)
@@ -469,6 +513,8 @@ class MyICP:
         assert self.cloud_src is not None and self.cloud_tgt is not None      # myicp.cpp:102
         self.estimateNormals()                                               # myicp.cpp:105
         with Engine(**self._cfg) as e:
+            if self._loss[0] != LOSS_NONE:
+                e.set_robust_loss(*self._loss)
             e.set_target(self.cloud_tgt, self.normals_tgt)
             e.set_source(self.cloud_src, self.normals_src)
             self.last_result = e.align(guess)

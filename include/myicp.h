@@ -47,6 +47,9 @@ public:
 	void setMode(symmicp_mode m) { mode_ = m; }                    // default SYMMICP_MODE_QUIRKS (= the reference)
 	void setCorrespondence(symmicp_corr c) { corr_ = c; }          // default SYMMICP_CORR_IDENTITY (= the reference)
 	void setVerbose(bool v) { verbose_ = v; }
+	// robust loss of the PAPER loop (symmicp_set_robust_loss; default SYMMICP_LOSS_NONE): checked by align(), which
+	// returns SYMMICP_ERR_ARG for a loss with SYMMICP_MODE_QUIRKS or a scale that is not finite and > 0
+	void setRobustLoss(symmicp_loss loss, float scale) { loss_ = loss; loss_scale_ = scale; }
 	const symmicp_result &lastResult() const { return result_; }
 	const char *lastError() const { return error_.c_str(); }
 
@@ -64,6 +67,8 @@ private:
 	symmicp_mode mode_;
 	symmicp_corr corr_;
 	bool verbose_, have_src_normals_, have_tgt_normals_;   // have_*: normals supplied by the caller through setInput*
+	symmicp_loss loss_;
+	float loss_scale_;
 	symmicp_ctx *ctx_;
 	int ctx_corr_;
 	float transform_[16];

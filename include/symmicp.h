@@ -67,6 +67,19 @@ typedef enum { SYMMICP_CORR_IDENTITY = 0, SYMMICP_CORR_BRUTE = 1, SYMMICP_CORR_T
  * to the original points (<= ~1e-6 relative drift, 24 B/point less traffic). */
 typedef enum { SYMMICP_APPLY_DEFAULT = 0, SYMMICP_APPLY_INCREMENTAL = 1, SYMMICP_APPLY_CUMULATIVE = 2 } symmicp_apply;
 
+/* Robust loss (symmicp_set_robust_loss): every pair is weighted by w(r / scale) of its residual r, run as iteratively
+ * reweighted least squares (each pass weights the pairs at their current position; the solve is the usual one on the
+ * weighted sums).  r is, in PAPER, c = (p - q) . (n_p + n_q), the quantity whose square the symmetric objective sums --
+ * so `scale` is in units of c, about TWICE the point-to-plane distance when the two normals agree -- and in P2P
+ * r = |p - q|.  With u = r / scale:
+ *   HUBER          1 if |u| <= 1, else 1/|u|
+ *   TUKEY          (1 - u^2)^2 if |u| < 1, else 0
+ *   CAUCHY         1 / (1 + u^2)
+ *   GEMAN_MCCLURE  1 / (1 + u^2)^2
+ * computed in fp32.  QUIRKS stays the reference as written: it takes no loss. */
+typedef enum { SYMMICP_LOSS_NONE = 0, SYMMICP_LOSS_HUBER = 1, SYMMICP_LOSS_TUKEY = 2,
+               SYMMICP_LOSS_CAUCHY = 3, SYMMICP_LOSS_GEMAN_MCCLURE = 4 } symmicp_loss;
+
 typedef struct {
     int32_t struct_size;       /* = sizeof(symmicp_config), checked */
     int32_t device;            /* HIP device ordinal; -1 = current */
@@ -95,7 +108,14 @@ typedef struct {
  *   [27..29] sum_i p_i        [30..32] sum_i q_i   (about `pivot`, see symmicp_get_pivot)
  *   [33] sum_i |p_i - q_i|   (evalDiff, func.cpp:19-32, over the current pairs)
  *   [34] number of pairs     [35] sum_i c_i^2      [36] sum_i |p_i - q_i|^2
- *   [37..39] reserved (0) */
+ *   [37..39] reserved (0)
+ * With a robust loss set (symmicp_set_robust_loss), w_i = the pair's weight:
+ *   [0..32], [35]  the same sums with every pair scaled by w_i: sum w v v^T, sum w v c, sum w p, sum w q, sum w c^2
+ *                  (P2P: sum w p q^T and the weighted coordinate sums)
+ *   [34] sum_i w_i (the solves centre on the weighted centroids)
+ *   [33], [36]     unweighted, as above (the stop rule and `diff` keep their meaning)
+ *   [37] number of pairs (what symmicp_iter_result.pairs reports then)
+ * With SYMMICP_LOSS_NONE the record is exactly the unweighted one and [37] stays 0. */
 typedef struct { double s[SYMMICP_NSUM]; } symmicp_sums;
 
 typedef struct {
@@ -103,7 +123,7 @@ typedef struct {
     int32_t iter;              /* iterations completed so far */
     float diff;                /* sum |p-q| after this iteration's update (myicp.cpp:141) */
     float rcond;               /* smallest/largest eigenvalue of the solved system(s) */
-    double pairs;              /* correspondences that entered the sums */
+    double pairs;              /* correspondences that entered the sums (slot 34, or slot 37 with a robust loss) */
     float increment[16];       /* row-major 4x4 of this iteration (func.cpp:91-101) */
     symmicp_sums sums;         /* record the NEXT solve will use (already all-reduced) */
 } symmicp_iter_result;
@@ -127,6 +147,16 @@ void symmicp_destroy(symmicp_ctx *ctx);                           /* MyICP::~MyI
 const char *symmicp_last_error(const symmicp_ctx *ctx);           /* (reference has none: asserts / silent NaN) */
 int symmicp_set_config(symmicp_ctx *ctx, const symmicp_config *cfg);   /* myicp.h:19 "todo add params" */
 int symmicp_version(void);
+/* Robust loss of the PAPER and P2P loops (symmicp_loss above; off = SYMMICP_LOSS_NONE, the default).  SYMMICP_ERR_ARG for
+ * an unknown loss, for a scale that is not finite and > 0 while loss != NONE, and for any loss in SYMMICP_MODE_QUIRKS
+ * (symmicp_set_config refuses to switch a context with a loss into QUIRKS the same way).  Takes effect at the next pass:
+ * it may be called between symmicp_step calls (e.g. to anneal the scale); a device-driven run inside symmicp_align keeps
+ * the values it started with.  Sharded runs: every rank sets the same values. */
+int symmicp_set_robust_loss(symmicp_ctx *ctx, int loss, float scale);
+int symmicp_get_robust_loss(const symmicp_ctx *ctx, int *loss, float *scale);
+/* the weight the kernels give a pair of residual r (the same fp32 source); NaN for an unknown loss, or for a scale that
+ * is not finite and > 0 with loss != NONE; 1 for SYMMICP_LOSS_NONE */
+float symmicp_robust_weight(int loss, float scale, float r);
 
 /* ---- clouds (replaces pasteInMatrix, func.cpp:5-15, myicp.cpp:110-111) --
  * Host arrays, element (i,k) at base[i*row_stride + k*col_stride] (floats):
