@@ -125,6 +125,17 @@ struct SymSolver {
     }
 };
 
+// Power of two that brings d > 0 into [0.5, 2) when applied twice (d * p * p): the symmetric equilibration D A D of the PAPER
+// system.  A power of two rounds nothing, and scaling d by 4^k moves p by exactly 2^-k, so the equilibrated system -- its solution
+// and its conditioning -- is the same bit for bit whatever power-of-two unit the clouds come in.  1 for d <= 0, inf or NaN.
+SYMMICP_HD inline double pow2_equilibrator(double d)
+{
+    if (!(d > 0.0 && d < (double)INFINITY)) return 1.0;
+    int e;
+    frexp(d, &e);                                                   // d = m 2^e, m in [0.5, 1)
+    return ldexp(1.0, -((e - (e & 1)) / 2));                        // 2^-floor(e/2)
+}
+
 struct Blocks {
     double MtM[3][3], NtN[3][3], MtN[3][3], Mtc[3], Ntc[3];
     double sp[3], sq[3], cnt;
@@ -283,8 +294,18 @@ SYMMICP_HD inline int solve_paper(const symmicp_sums &S, const float pivot[3], f
         }
         rhs[r] = -x; rhs[r + 3] = -y;
     }
+    // The unknowns are a rotation (no unit) and a translation (a length): for clouds scaled by s the blocks of A scale as s^2, s
+    // and 1, and so would its conditioning.  Solve and measure D A D (D y = D b, x = D y) instead, D from diag(A) in powers of two,
+    // so that the thresholds on rc below and in the device-driven loop are dimensionless.
+    double D[6];
+    for (int i = 0; i < 6; ++i) D[i] = pow2_equilibrator(sys.A[i][i]);
+    for (int i = 0; i < 6; ++i) {
+        for (int j = 0; j < 6; ++j) sys.A[i][j] *= D[i] * D[j];
+        rhs[i] *= D[i];
+    }
     const double rc = sys.solve(rhs, x6, exact_rc);
     if (rcond) *rcond = (float)rc;
+    for (int k = 0; k < 6; ++k) x6[k] *= D[k];
     for (int k = 0; k < 3; ++k) {
         a[k] = (float)x6[k]; t[k] = (float)x6[k + 3];
         pbar[k] = (float)(pb[k] + (pivot ? (double)pivot[k] : 0.0));

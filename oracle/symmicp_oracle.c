@@ -548,9 +548,22 @@ int orc_solve_paper(const double S[ORC_NSUM], const float pivot[3],
         }
         bc[r] = -x; bc[3 + r] = -y;
     }
-    double x6[6];
+    /* equilibrate: solve and measure D Gc D (D y = D bc, x = D y) with D = 2^-floor(e/2) from the
+     * diagonal Gc_ii = m 2^e.  Rotation and translation blocks scale as s^2, s, 1 with the clouds;
+     * the equilibrated system, its rc and its rounding do not change under power-of-two units. */
+    double D[6], x6[6];
+    for (int i = 0; i < 6; i++) {
+        double g = Gc[i * 6 + i];
+        D[i] = 1.0;
+        if (g > 0.0 && g < INFINITY) { int e; frexp(g, &e); D[i] = ldexp(1.0, -((e - (e & 1)) / 2)); }
+    }
+    for (int i = 0; i < 6; i++) {
+        for (int j = 0; j < 6; j++) Gc[i * 6 + j] *= D[i] * D[j];
+        bc[i] *= D[i];
+    }
     double rc = sym_solve(6, Gc, bc, x6);
     if (rcond) *rcond = rc;
+    for (int k = 0; k < 6; k++) x6[k] *= D[k];
     for (int k = 0; k < 3; k++) {
         a_out[k] = (float)x6[k]; t_out[k] = (float)x6[3 + k];
         pbar_out[k] = (float)(pb[k] + (pivot ? (double)pivot[k] : 0.0));

@@ -245,3 +245,32 @@ def test_sweep_order_is_a_coherent_permutation():
     def spread(q):          # mean bounding-box diagonal of 8 contiguous row ranges
         return np.mean([np.linalg.norm(q[k * 2500:(k + 1) * 2500].max(0) - q[k * 2500:(k + 1) * 2500].min(0)) for k in range(8)])
     assert spread(p) < 0.6 * spread(d["src"].astype(np.float64))
+
+
+def test_host_solve_is_equivariant_under_power_of_two_units(sym, oracle, cat):
+    """symmicp_solve (PAPER) on the cat pair's first-pass record in units 2^k times larger (k in -14..14): status 0, the same
+    rotation block and rc bit for bit, a translation exactly 2^k times larger.  Absolute thresholds on the conditioning of
+    the mixed rotation / translation system flagged the 2^14 copy degenerate."""
+    from _frames import scale_record
+    pivot = cat["tgt"].astype(np.float64).mean(0).astype(np.float32)
+    S = oracle.reduce40(cat["src"], cat["src_n"], cat["tgt"], cat["tgt_n"], pivot=pivot)
+    st0, pb0, qb0, a0, t0, rc0, X0 = sym.solve(sym.MODE_PAPER, S, pivot)
+    assert st0 == 0
+    for k in (-14, -8, 0, 8, 14):
+        s = np.float32(2.0 ** k)
+        st, pb, qb, a, t, rc, X = sym.solve(sym.MODE_PAPER, scale_record(S, float(s)), pivot * s)
+        assert st == 0, (k, st, rc)
+        assert np.array_equal(X[:3, :3], X0[:3, :3]), k
+        assert np.array_equal(X[:3, 3], X0[:3, 3] * s), (k, X[:3, 3], X0[:3, 3])
+        assert np.array_equal(a, a0) and np.array_equal(t, t0 * s), k
+        assert rc == rc0, (k, rc, rc0)
+    # the check keeps its teeth: a rank-deficient record (collinear bunny, one normal direction) is degenerate in every unit
+    from conftest import GOLDEN as G
+    bunny, _ = oracle.pcd_read(os.path.join(G, "txt2pcd_bunny1.pcd"))
+    n = np.tile(np.array([[0, 0, 1]], np.float32), (bunny.shape[0], 1))
+    tgt = bunny + np.array([0.01, 0.02, 0.0], np.float32)
+    pv = tgt.astype(np.float64).mean(0).astype(np.float32)
+    Sb = oracle.reduce40(bunny, n, tgt, n, pivot=pv)
+    for k in (-14, -8, 0, 8, 14):
+        s = np.float32(2.0 ** k)
+        assert sym.solve(sym.MODE_PAPER, scale_record(Sb, float(s)), pv * s)[0] == sym.ERR_DEGENERATE, k

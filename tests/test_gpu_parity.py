@@ -333,6 +333,30 @@ def test_degenerate_collinear_cloud_is_flagged(sym, bunny):
         assert np.isfinite(r["transform"]).all() and r["iters"] == 0
 
 
+def test_all_zero_normals_are_flagged(sym, oracle, cat):
+    """cat_out.pcd stores normal fields that are all zero, and cat.pcd has none.  The rows use n = n_p + n_q (func.cpp:51): with
+    the zero normals on both clouds every row is zero and the system is degenerate -- flagged before any update, transform finite.
+    With them on the target only, n = n_p and the run is an ordinary one: it must agree with the oracle."""
+    tgt, tn = sym.pcd_read(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "cat_out.pcd"))
+    assert tn is not None and not tn.any()
+    zeros = np.zeros_like(cat["src"])
+    for mode in (sym.MODE_QUIRKS, sym.MODE_PAPER):
+        for corr in (sym.CORR_IDENTITY, sym.CORR_TREE):
+            with sym.Engine(mode=mode, corr=corr) as e:
+                e.set_target(tgt, tn)
+                e.set_source(cat["src"], zeros)
+                r = e.align()
+            assert r["status"] == sym.ERR_DEGENERATE and r["iters"] == 0, (mode, corr, r["status"], r["iters"])
+            assert np.isfinite(r["transform"]).all()
+            with sym.Engine(mode=mode, corr=corr) as e:
+                e.set_target(tgt, tn)
+                e.set_source(cat["src"], cat["src_n"])
+                r = e.align()
+            ro = oracle.align(cat["src"], cat["src_n"], tgt, tn, mode=mode, corr=oracle.CORR_BRUTE if corr == sym.CORR_TREE else corr)
+            assert r["status"] == ro["status"] == 0 and r["iters"] == ro["iters"], (mode, corr, r["status"], r["iters"], ro["iters"])
+            assert np.abs(r["transform"] - ro["transform"]).max() < TOL_T
+
+
 def test_error_codes(sym, cat):
     with sym.Engine() as e:
         with pytest.raises(sym.SymmIcpError) as ei:
@@ -618,11 +642,12 @@ def test_cpp_driver_prints_the_reference_lines(cat, tmp_path):
     assert np.abs(T - cat["golden"]["quirks_identity_T"]).max() < 5e-4
     assert "  rotation:" in out and "  translation:" in out
     # the block is laid out as the reference's `cout << transform.matrix()` does (Eigen's default IOFormat: tests/test_format.py):
-    # what the driver printed is exactly the formatter's text for the 4x4 it printed (%g round-trips through fp32 to 6 digits only, so
-    # the check is on layout: every line of a matrix has the same length, columns are right-aligned, one space apart)
+    # each printed block is exactly the formatter's text for the values parsed back from it (%g to 6 digits reprints itself)
     import symmicp
     from test_format import eigen_block
-    assert "\n".join(out[k + 1:k + 5]) + "\n" == eigen_block(T.astype(np.float32)) or all(len(l) == len(out[k + 1]) for l in out[k + 1:k + 5])
+    for first, rows in ((k + 1, 4), (k + 6, 3), (k + 10, 3)):
+        block = out[first:first + rows]
+        assert "\n".join(block) + "\n" == eigen_block(np.array([[float(v) for v in l.split()] for l in block])), block
     assert all(len(l) == len(out[k + 1]) for l in out[k + 1:k + 5]) and all(len(l) == len(out[k + 6]) for l in out[k + 6:k + 9])
     assert out[k + 5] == "  rotation:" and out[k + 9] == "  translation:" and len({len(l) for l in out[k + 10:k + 13]}) == 1
     assert symmicp.format_result(T).split("\n")[0] == "Result transform:"

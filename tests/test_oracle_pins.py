@@ -218,3 +218,45 @@ def test_p2p_icp_in_oracle(oracle, cat):
     assert np.abs(r["transform"] - T).max() < 1e-5
     r = oracle.align(cat["src"], cat["src_n"], cat["tgt"], cat["tgt_n"], mode=oracle.MODE_P2P, corr=oracle.CORR_BRUTE, max_iters=60)
     assert r["status"] == 0 and np.abs(r["transform"] - T).max() < 1e-4
+
+
+# clouds in a different unit: a power-of-two scale s multiplies slot k of the PAPER record by exactly s ** dims[k]
+FRAME_EXPONENTS = (-14, -8, 0, 8, 14)
+
+
+def _cat_paper_record(oracle, cat):
+    pivot = cat["tgt"].astype(np.float64).mean(0).astype(np.float32)
+    return oracle.reduce40(cat["src"], cat["src_n"], cat["tgt"], cat["tgt_n"], pivot=pivot), pivot
+
+
+def test_paper_solve_is_equivariant_under_power_of_two_units(oracle, cat):
+    """The 6 x 6 PAPER system mixes a rotation (no unit) and a translation (a length): its blocks scale as s^2, s and 1.  The
+    solve equilibrates it, so the same problem in a unit 2^k times larger must solve to the same bits: rotation and rc
+    identical, translation and centroids exactly 2^k times larger -- and never flagged degenerate (a 3 km map in mm is
+    well posed)."""
+    from _frames import scale_record
+    S, pivot = _cat_paper_record(oracle, cat)
+    st0, pb0, qb0, a0, t0, rc0 = oracle.solve_paper(S, pivot)
+    assert st0 == 0 and rc0 > 1e-6
+    for k in FRAME_EXPONENTS:
+        s = 2.0 ** k
+        st, pb, qb, a, t, rc = oracle.solve_paper(scale_record(S, s), (pivot * np.float32(s)).astype(np.float32))
+        assert st == 0, (k, st, rc)
+        assert np.array_equal(a, a0), (k, a, a0)
+        assert np.array_equal(t, t0 * np.float32(s)), (k, t, t0)
+        assert np.array_equal(pb, pb0 * np.float32(s)) and np.array_equal(qb, qb0 * np.float32(s)), k
+        assert rc == rc0, (k, rc, rc0)
+
+
+def test_paper_solve_keeps_flagging_a_degenerate_record_in_every_unit(oracle, bunny):
+    """the equilibration must not make a rank-deficient system look usable: the collinear bunny (93 points on a line, one
+    normal direction) stays degenerate at every scale"""
+    from _frames import scale_record
+    n = np.tile(np.array([[0, 0, 1]], np.float32), (bunny.shape[0], 1))
+    tgt = bunny + np.array([0.01, 0.02, 0.0], np.float32)
+    pivot = tgt.astype(np.float64).mean(0).astype(np.float32)
+    S = oracle.reduce40(bunny, n, tgt, n, pivot=pivot)
+    for k in FRAME_EXPONENTS:
+        s = 2.0 ** k
+        st = oracle.solve_paper(scale_record(S, s), (pivot * np.float32(s)).astype(np.float32))[0]
+        assert st == oracle.ERR_DEGENERATE, k
