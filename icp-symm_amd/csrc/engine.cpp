@@ -847,12 +847,15 @@ int symmicp_get_certificates(symmicp_ctx *c, float *cert4, uint32_t *hood8, floa
 // Runs on a context the caller owns (its stream and arenas are reused: a tracker that estimates normals per scan pays no
 // context set-up); the context's target and source stay as they are -- what the estimate allocates behind the target's arrays
 // in the keep-arena is released again.
-int symmicp_ctx_estimate_normals(symmicp_ctx *c, const float *xyz, size_t row_stride, size_t col_stride, size_t n, int k,
-                                 const float viewpoint[3], float *nrm_out, float *curv_out)
+// symmicp_ctx_knn runs the same index build and walk, and reads back the neighbour set (rows, d2) instead of the normals.
+static bool normals_args_ok(const float *xyz, size_t n, int k)
 {
-    if (!c) return SYMMICP_ERR_ARG;
-    if (!xyz || !nrm_out || n == 0 || n > 0x7fffffffull) return fail(c, SYMMICP_ERR_ARG, "bad cloud");
-    if (k < 3 || k > 16 || (size_t)k > n) return fail(c, SYMMICP_ERR_ARG, "k out of range (3..16, <= n)");
+    return xyz && n != 0 && n <= 0x7fffffffull && k >= 3 && k <= 16 && (size_t)k <= n;
+}
+
+static int normals_or_knn(symmicp_ctx *c, const float *xyz, size_t row_stride, size_t col_stride, size_t n, int k,
+                          const float viewpoint[3], float *nrm_out, float *curv_out, int32_t *rows_out, float *d2_out)
+{
     HIP_TRY(c, hipSetDevice(c->device));
     if (c->keep.cap == 0) {
         // no target yet: give the keep-arena the size this cloud needs (a later set_target reuses it)
@@ -872,7 +875,7 @@ int symmicp_ctx_estimate_normals(symmicp_ctx *c, const float *xyz, size_t row_st
         c->target_surface_like = surf0;
     };
     // the cloud has no normals yet: stage xyz twice (the normal slots are ignored)
-    arena_begin(c->arena, n * (96 + 8 * row_stride + 16) + ((size_t)1 << 20));
+    arena_begin(c->arena, n * (96 + 8 * row_stride + (rows_out ? 8 * (size_t)k : 16)) + ((size_t)1 << 20));
     int st;
     {
         DevBuf<float> b;
@@ -883,29 +886,52 @@ int symmicp_ctx_estimate_normals(symmicp_ctx *c, const float *xyz, size_t row_st
     CloudSoA cl;
     soa_from_block(block, n, cl);
     TargetIndex ix{};
-    DevBuf<float> b_nrm, b_curv;
+    const bool knn = rows_out != nullptr;
+    // normals: [n][3] + [n]; neighbour set: [n][k] rows + [n][k] d2
+    DevBuf<float> b_a, b_b;
     bool ok = keep_alloc(c, (void **)&tq, sizeof(float4) * (n + 8)) == hipSuccess && keep_alloc(c, (void **)&tn, sizeof(float4) * 2 * n) == hipSuccess &&
-              b_nrm.alloc_temp(c->arena, 3 * n) == hipSuccess && b_curv.alloc_temp(c->arena, n) == hipSuccess;
+              b_a.alloc_temp(c->arena, (knn ? (size_t)k : 3) * n) == hipSuccess && b_b.alloc_temp(c->arena, (knn ? (size_t)k : 1) * n) == hipSuccess;
     if (!ok) { cleanup(); return fail(c, SYMMICP_ERR_HIP, "out of device memory"); }
-    d_nrm = b_nrm.p; d_curv = b_curv.p;
+    d_nrm = b_a.p; d_curv = b_b.p;
     st = build_index(c, cl, (uint32_t)n, /*want_grid=*/false, tq, tn, &boxes, &cells, &ix, nullptr, nullptr);
     if (st != SYMMICP_OK) { cleanup(); return st; }
-    const float vp0[3] = {0.f, 0.f, 0.f};
-    launch_normals_knn(ix, k, viewpoint ? viewpoint : vp0, d_nrm, d_curv, c->stream);
-    hipError_t e = hipMemcpyAsync(nrm_out, d_nrm, sizeof(float) * 3 * n, hipMemcpyDeviceToHost, c->stream);
-    if (e == hipSuccess && curv_out) e = hipMemcpyAsync(curv_out, d_curv, sizeof(float) * n, hipMemcpyDeviceToHost, c->stream);
+    hipError_t e;
+    if (knn) {
+        launch_knn(ix, k, (int32_t *)d_nrm, d_curv, c->stream);
+        e = hipMemcpyAsync(rows_out, d_nrm, sizeof(int32_t) * (size_t)k * n, hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(d2_out, d_curv, sizeof(float) * (size_t)k * n, hipMemcpyDeviceToHost, c->stream);
+    } else {
+        const float vp0[3] = {0.f, 0.f, 0.f};
+        launch_normals_knn(ix, k, viewpoint ? viewpoint : vp0, d_nrm, d_curv, c->stream);
+        e = hipMemcpyAsync(nrm_out, d_nrm, sizeof(float) * 3 * n, hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess && curv_out) e = hipMemcpyAsync(curv_out, d_curv, sizeof(float) * n, hipMemcpyDeviceToHost, c->stream);
+    }
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     if (e == hipSuccess) e = hipGetLastError();
     cleanup();
-    if (e != hipSuccess) return fail(c, SYMMICP_ERR_HIP, std::string("normals: ") + hipGetErrorString(e));
+    if (e != hipSuccess) return fail(c, SYMMICP_ERR_HIP, std::string(knn ? "knn: " : "normals: ") + hipGetErrorString(e));
     return SYMMICP_OK;
+}
+
+int symmicp_ctx_estimate_normals(symmicp_ctx *c, const float *xyz, size_t row_stride, size_t col_stride, size_t n, int k,
+                                 const float viewpoint[3], float *nrm_out, float *curv_out)
+{
+    if (!c) return SYMMICP_ERR_ARG;
+    if (!nrm_out || !normals_args_ok(xyz, n, k)) return fail(c, SYMMICP_ERR_ARG, "bad cloud or k (3..16, <= n)");
+    return normals_or_knn(c, xyz, row_stride, col_stride, n, k, viewpoint, nrm_out, curv_out, nullptr, nullptr);
+}
+
+int symmicp_ctx_knn(symmicp_ctx *c, const float *xyz, size_t row_stride, size_t col_stride, size_t n, int k, int32_t *rows_out, float *d2_out)
+{
+    if (!c) return SYMMICP_ERR_ARG;
+    if (!rows_out || !d2_out || !normals_args_ok(xyz, n, k)) return fail(c, SYMMICP_ERR_ARG, "bad cloud or k (3..16, <= n)");
+    return normals_or_knn(c, xyz, row_stride, col_stride, n, k, nullptr, nullptr, nullptr, rows_out, d2_out);
 }
 
 int symmicp_estimate_normals(int device, const float *xyz, size_t row_stride, size_t col_stride, size_t n, int k,
                              const float viewpoint[3], float *nrm_out, float *curv_out)
 {
-    if (!xyz || !nrm_out || n == 0 || n > 0x7fffffffull) return SYMMICP_ERR_ARG;
-    if (k < 3 || k > 16 || (size_t)k > n) return SYMMICP_ERR_ARG;
+    if (!nrm_out || !normals_args_ok(xyz, n, k)) return SYMMICP_ERR_ARG;
     symmicp_config cfg;
     symmicp_config_default(&cfg);
     cfg.device = device;

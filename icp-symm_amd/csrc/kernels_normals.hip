@@ -78,8 +78,11 @@ __device__ __forceinline__ void smallest_eigvec3(double a00, double a01, double 
     nz = (m == 0) ? V[2][0] : (m == 1 ? V[2][1] : V[2][2]);
 }
 
+// KNN = false is the shipped pre-step.  KNN = true stops after the walk and writes each point's k neighbours instead: original rows
+// and fp32 d2 in ascending (d2, row) order, row-major [row][k] (symmicp_ctx_knn, the tests' view of the set the moments use).
+template <bool KNN>
 __global__ __launch_bounds__(256) void k_normals_knn(TargetIndex ix, int k, float vx, float vy, float vz,
-                                                     float *nrm_out, float *curv_out)
+                                                     float *nrm_out, float *curv_out, int32_t *knn_rows, float *knn_d2)
 {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= ix.n) return;
@@ -163,13 +166,19 @@ __global__ __launch_bounds__(256) void k_normals_knn(TargetIndex ix, int k, floa
         if (level == ix.top && node >= ix.ntop) break;
     }
 
+    const int row_me = __float_as_int(me.w);
+    if constexpr (KNN) {
+#pragma unroll
+        for (int j = 0; j < kKnnMax; j++)
+            if (j < k) { knn_rows[(size_t)row_me * k + j] = bp[j] >= 0 ? br[j] : -1; knn_d2[(size_t)row_me * k + j] = bd[j]; }
+        return;
+    }
     // moments over the neighbours in ascending (d2,row) order, fp64
     double mx = 0, my = 0, mz = 0;
     int cnt = 0;
 #pragma unroll
     for (int j = 0; j < kKnnMax; j++)
         if (j < k && bp[j] >= 0) { float4 q = ix.tq[bp[j]]; mx += (double)q.x; my += (double)q.y; mz += (double)q.z; cnt++; }
-    const int row_me = __float_as_int(me.w);
     if (cnt < 3) {
         nrm_out[3 * (size_t)row_me] = nrm_out[3 * (size_t)row_me + 1] = nrm_out[3 * (size_t)row_me + 2] = __int_as_float(0x7fc00000);
         if (curv_out) curv_out[row_me] = __int_as_float(0x7fc00000);
@@ -200,7 +209,14 @@ __global__ __launch_bounds__(256) void k_normals_knn(TargetIndex ix, int k, floa
 
 void launch_normals_knn(const TargetIndex &ix, int k, const float vp[3], float *nrm_out, float *curv_out, hipStream_t s)
 {
-    hipLaunchKernelGGL(k_normals_knn, dim3((ix.n + 255) / 256), dim3(256), 0, s, ix, k, vp[0], vp[1], vp[2], nrm_out, curv_out);
+    hipLaunchKernelGGL(k_normals_knn<false>, dim3((ix.n + 255) / 256), dim3(256), 0, s, ix, k, vp[0], vp[1], vp[2], nrm_out, curv_out,
+                       nullptr, nullptr);
+}
+
+void launch_knn(const TargetIndex &ix, int k, int32_t *rows_out, float *d2_out, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_normals_knn<true>, dim3((ix.n + 255) / 256), dim3(256), 0, s, ix, k, 0.f, 0.f, 0.f, nullptr, nullptr,
+                       rows_out, d2_out);
 }
 
 }  // namespace symmicp

@@ -233,5 +233,6 @@ void launch_corr_out(const int32_t *pos, const unsigned long long *best64, const
 void launch_identity_d2(const CloudSoA &in, const Affine &X, const CloudSoA &tgt, uint32_t tgt_offset, uint32_t n, float *d2, hipStream_t s);
 void launch_pairs_d2(const CloudSoA &in, const Affine &X, const int32_t *pos, const float4 *tq, uint32_t n_t, uint32_t n, float *d2, hipStream_t s);
 void launch_normals_knn(const TargetIndex &ix, int k, const float vp[3], float *nrm_out, float *curv_out, hipStream_t s);
+void launch_knn(const TargetIndex &ix, int k, int32_t *rows_out, float *d2_out, hipStream_t s);
 
 }  // namespace symmicp

@@ -78,7 +78,7 @@ EXPORTS = [
     "symmicp_get_transform", "symmicp_format_result", "symmicp_get_pivot", "symmicp_get_correspondences", "symmicp_get_source",
     "symmicp_local_source_count", "symmicp_local_source_offset", "symmicp_get_certificates", "symmicp_solve", "symmicp_comm_get_unique_id",
     "symmicp_comm_init_rank", "symmicp_set_sums", "symmicp_comm_init_shm", "symmicp_shard_range", "symmicp_get_stats", "symmicp_reset_stats", "symmicp_enable_timing",
-    "symmicp_pcd_read", "symmicp_pcd_write", "symmicp_estimate_normals", "symmicp_ctx_estimate_normals",
+    "symmicp_pcd_read", "symmicp_pcd_write", "symmicp_estimate_normals", "symmicp_ctx_estimate_normals", "symmicp_ctx_knn",
     "symmicp_set_robust_loss", "symmicp_get_robust_loss", "symmicp_robust_weight",
 ]
 
@@ -144,6 +144,8 @@ def lib():
     L.symmicp_pcd_read.restype = C.c_long
     L.symmicp_pcd_write.argtypes = [C.c_char_p, fp, fp, C.c_size_t, C.c_int]
     L.symmicp_estimate_normals.argtypes = [C.c_int, fp, C.c_size_t, C.c_size_t, C.c_size_t, C.c_int, fp, fp, fp]
+    L.symmicp_ctx_estimate_normals.argtypes = [vp, fp, C.c_size_t, C.c_size_t, C.c_size_t, C.c_int, fp, fp, fp]
+    L.symmicp_ctx_knn.argtypes = [vp, fp, C.c_size_t, C.c_size_t, C.c_size_t, C.c_int, C.POINTER(C.c_int32), fp]
     L.symmicp_set_robust_loss.argtypes = [vp, C.c_int, C.c_float]
     L.symmicp_get_robust_loss.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_float)]
     L.symmicp_robust_weight.argtypes = [C.c_int, C.c_float, C.c_float]
@@ -256,6 +258,12 @@ def estimate_normals(xyz, k=10, viewpoint=(0.0, 0.0, 0.0), device=-1):
     if st != OK:
         raise SymmIcpError(st, "estimate_normals")
     return nrm, curv
+
+
+def knn(xyz, k=10, device=-1):
+    """the k nearest points of the same cloud, the set estimate_normals uses -> (rows [N,k] int32, d2 [N,k] f32), ascending (d2, row)"""
+    with Engine(device=device) as e:
+        return e.knn(xyz, k)
 
 
 def shard_range(n, nranks, rank):
@@ -438,6 +446,30 @@ class Engine:
         nrm = np.zeros((n, 3), np.float32)
         self._chk(self._L.symmicp_get_source(self._h, _fptr(xyz), _fptr(nrm), n))
         return xyz, nrm
+
+    def estimate_normals(self, xyz, k=10, viewpoint=(0.0, 0.0, 0.0)):
+        """estimate_normals on this context (symmicp_ctx_estimate_normals); its target and source stay as they are"""
+        xyz = _cloud(xyz)
+        return self.estimate_normals_strided(xyz, 3, 1, xyz.shape[0], k, viewpoint)
+
+    def estimate_normals_strided(self, buf, row_stride, col_stride, n, k=10, viewpoint=(0.0, 0.0, 0.0)):
+        """as estimate_normals, the cloud read from the f32 array `buf` as xyz[i][c] = buf.flat[i * row_stride + c * col_stride]"""
+        buf = np.ascontiguousarray(buf, np.float32)
+        nrm = np.zeros((n, 3), np.float32)
+        curv = np.zeros(n, np.float32)
+        vp = None if viewpoint is None else np.ascontiguousarray(viewpoint, np.float32)
+        self._chk(self._L.symmicp_ctx_estimate_normals(self._h, _fptr(buf), row_stride, col_stride, n, k,
+                                                       None if vp is None else _fptr(vp), _fptr(nrm), _fptr(curv)))
+        return nrm, curv
+
+    def knn(self, xyz, k=10):
+        """symmicp_ctx_knn: -> (rows [N,k] int32, d2 [N,k] f32), each point's k nearest points of the same cloud in ascending (d2, row)"""
+        xyz = _cloud(xyz)
+        n = xyz.shape[0]
+        rows = np.zeros((n, k), np.int32)
+        d2 = np.zeros((n, k), np.float32)
+        self._chk(self._L.symmicp_ctx_knn(self._h, _fptr(xyz), 3, 1, n, k, rows.ctypes.data_as(C.POINTER(C.c_int32)), _fptr(d2)))
+        return rows, d2
 
     def enable_timing(self, on=True):
         self._chk(self._L.symmicp_enable_timing(self._h, int(on)))      # 0 off, 1 per pass, 2 per kernel

@@ -216,6 +216,11 @@ int symmicp_estimate_normals(int device, const float *xyz, size_t row_stride, si
  * left alone): what MyICP::estimateNormals calls for both clouds before every alignment (myicp.cpp:105) */
 int symmicp_ctx_estimate_normals(symmicp_ctx *ctx, const float *xyz, size_t row_stride, size_t col_stride, size_t n, int k,
                                  const float viewpoint[3], float *nrm_out, float *curv_out);
+/* the k nearest points of the same cloud, the set the normals use: rows_out / d2_out [n][k] (row-major, both required), for every
+ * point its neighbours' rows and fp32 squared distances (dx*dx + dy*dy) + dz*dz in ascending (d2, row) order, the point itself
+ * included.  Same argument rules as symmicp_ctx_estimate_normals; the context's own clouds are left alone. */
+int symmicp_ctx_knn(symmicp_ctx *ctx, const float *xyz, size_t row_stride, size_t col_stride, size_t n, int k,
+                    int32_t *rows_out, float *d2_out);
 
 /* ---- multi-GPU (new: the reference is single-threaded) ----- */
 /* rank 0 creates an id, the application ships it to the other ranks (any channel),

@@ -7,6 +7,8 @@
 //         <dir>/guess.f32                               16 floats, row-major 4x4
 // writes  <dir>/out_paper_tree.f32, out_quirks_identity.f32        the 4x4 `align` returned
 //         <dir>/aligned_paper_tree.f32                              GetAlignedSrcCloud() as packed xyz
+//         <dir>/out_no_normals.f32      the 4x4 of a third run, on a fresh object given the clouds WITHOUT normals (align estimates
+//                                       them, k = 10, viewpoint 0: myicp.cpp:105), PAPER + TREE, 30 iterations, diff threshold 1
 // and checks by itself (exit code != 0 on failure): align's out == getFinalTransformation() == lastResult().transform,
 // GetAlignedSrcCloud() == X * source recomputed here, a second align on the same object works, getters hand out the clouds
 // that were set.  The numbers are compared with the oracle's golden values by the Python test.
@@ -111,6 +113,22 @@ int main(int argc, char **argv)
     st = icp.align(out3, nullptr);
     CHECK(ns != nt || st == SYMMICP_OK);
     CHECK(ns != nt || std::memcmp(out2, out3, sizeof(out2)) != 0);
+
+    // ---- clouds without normals: align estimates them on the object's own context (symmicp_ctx_estimate_normals, PointT stride)
+    {
+        MyICP bare;
+        bare.setVerbose(false);
+        bare.setInputSource(src.data(), nullptr, ns);
+        bare.setInputTarget(tgt.data(), nullptr, nt);
+        bare.setMode(SYMMICP_MODE_PAPER);
+        bare.setCorrespondence(SYMMICP_CORR_TREE);
+        bare.setMaximumIterations(30);
+        bare.setDiffThreshold(1.0f);
+        float out4[16];
+        st = bare.align(out4, guess.data());
+        CHECK(st == SYMMICP_OK);
+        dump(dir + "out_no_normals.f32", out4, 16);
+    }
     std::printf("myicp_surface: ok (%zu source, %zu target points; paper/tree %d iterations)\n", ns, nt, 0);
     return 0;
 }

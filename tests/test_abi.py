@@ -274,3 +274,20 @@ def test_host_solve_is_equivariant_under_power_of_two_units(sym, oracle, cat):
     for k in (-14, -8, 0, 8, 14):
         s = np.float32(2.0 ** k)
         assert sym.solve(sym.MODE_PAPER, scale_record(Sb, float(s)), pv * s)[0] == sym.ERR_DEGENERATE, k
+
+
+def test_estimate_normals_refuses_bad_arguments_before_any_device_work(sym, cat):
+    """symmicp_estimate_normals checks its arguments before it creates a context, so this runs without a GPU: k outside 3..16 or
+    above n, n = 0, and null inputs or outputs give ERR_ARG and leave the outputs untouched"""
+    import ctypes as C
+    L = sym.lib()
+    x = np.ascontiguousarray(cat["src"][:40])
+    n = len(x)
+    fp = lambda a: a.ctypes.data_as(C.POINTER(C.c_float))                # noqa: E731
+    nrm = np.full((n, 3), 7, np.float32)
+    curv = np.full(n, 7, np.float32)
+    for nn, k in ((n, 2), (n, 17), (n, n + 1), (0, 3), (10, 11)):
+        assert L.symmicp_estimate_normals(-1, fp(x), 3, 1, nn, k, None, fp(nrm), fp(curv)) == sym.ERR_ARG
+    assert L.symmicp_estimate_normals(-1, None, 3, 1, n, 10, None, fp(nrm), fp(curv)) == sym.ERR_ARG
+    assert L.symmicp_estimate_normals(-1, fp(x), 3, 1, n, 10, None, None, fp(curv)) == sym.ERR_ARG
+    assert (nrm == 7).all() and (curv == 7).all()
