@@ -1,11 +1,13 @@
 // examples/icp_align.cpp -- command-line registration of two PCD files on one MI355X through the MyICP class.
 //
 //   icp_align [options] [source.pcd target.pcd]
-//     --mode quirks|paper      arithmetic: the reference as written (default) or the paper-correct form
+//     --mode quirks|paper|plane  arithmetic: the reference as written (default), the paper-correct symmetric form, or
+//                              point-to-plane (target normals only: the source's are not estimated)
 //     --corr identity|tree     pairing: by row (default, what the reference does) or exact nearest neighbours
 //     --iters N                iteration cap            (default 10, ICP/myicp.cpp:6)
 //     --loss none|huber|tukey|cauchy|gm   robust loss of the paper loop (default none; not with --mode quirks)
-//     --loss-scale S           its scale (PAPER: in units of c = (p - q).(n_p + n_q), about twice the point-to-plane distance)
+//     --loss-scale S           its scale (PAPER: in units of c = (p - q).(n_p + n_q), about twice the point-to-plane distance;
+//                              PLANE: the point-to-plane distance itself)
 //     --threshold D            stop once the summed pair distance is <= D   (default 1.0, ICP/myicp.cpp:6)
 //     --out aligned.pcd        write the source moved by the result (the reference only prints its result)
 //     --quiet                  no per-iteration lines
@@ -25,7 +27,7 @@
 
 static int usage(const char *argv0, const char *complaint)
 {
-    std::fprintf(stderr, "%s\nusage: %s [--mode quirks|paper] [--corr identity|tree] [--iters N] [--threshold D] [--loss none|huber|tukey|cauchy|gm]"
+    std::fprintf(stderr, "%s\nusage: %s [--mode quirks|paper|plane] [--corr identity|tree] [--iters N] [--threshold D] [--loss none|huber|tukey|cauchy|gm]"
                  " [--loss-scale S] [--out file.pcd] [--quiet] [source.pcd target.pcd]\n",
                  complaint, argv0);
     return 64;
@@ -50,6 +52,7 @@ int main(int argc, char **argv)
             const std::string v = value("--mode");
             if (v == "quirks") { icp.setMode(SYMMICP_MODE_QUIRKS); quirks = true; }
             else if (v == "paper") { icp.setMode(SYMMICP_MODE_PAPER); quirks = false; }
+            else if (v == "plane") { icp.setMode(SYMMICP_MODE_PLANE); quirks = false; }
             else return usage(argv[0], "unknown --mode");
         } else if (a == "--corr") {
             const std::string v = value("--corr");
@@ -81,7 +84,7 @@ int main(int argc, char **argv)
     if (files.empty()) files = {"cat.pcd", "cat_out.pcd"};
     if (files.size() != 2) return usage(argv[0], "expected two PCD files");
     if (loss != SYMMICP_LOSS_NONE) {
-        if (quirks) return usage(argv[0], "--loss needs --mode paper (quirks is the reference as written)");
+        if (quirks) return usage(argv[0], "--loss needs --mode paper or plane (quirks is the reference as written)");
         if (!have_scale || !(loss_scale > 0.f) || !std::isfinite(loss_scale)) return usage(argv[0], "--loss needs --loss-scale S with S > 0");
         icp.setRobustLoss(loss, loss_scale);
     }

@@ -94,7 +94,7 @@ void symmicp_config_default(symmicp_config *cfg)
 static int check_cfg(const symmicp_config *cfg)
 {
     if (!cfg || cfg->struct_size != (int32_t)sizeof(symmicp_config)) return SYMMICP_ERR_ARG;
-    if (cfg->mode < SYMMICP_MODE_QUIRKS || cfg->mode > SYMMICP_MODE_P2P) return SYMMICP_ERR_ARG;
+    if (cfg->mode < SYMMICP_MODE_QUIRKS || cfg->mode > SYMMICP_MODE_PLANE) return SYMMICP_ERR_ARG;
     if (cfg->corr < SYMMICP_CORR_IDENTITY || cfg->corr > SYMMICP_CORR_TREE) return SYMMICP_ERR_ARG;
     if (cfg->apply < SYMMICP_APPLY_DEFAULT || cfg->apply > SYMMICP_APPLY_CUMULATIVE) return SYMMICP_ERR_ARG;
     if (cfg->max_iters < 0) return SYMMICP_ERR_ARG;
@@ -174,6 +174,7 @@ extern "C++" void forget_source(symmicp_ctx *c)
     c->worklist = c->wl_count = nullptr; c->cert = nullptr; c->certk = nullptr; c->hoodr = nullptr; c->pkt_tab = nullptr; c->pkt_count = 0; c->pairrec = nullptr;
     c->src0_block = c->cur_block = nullptr; c->src_order = nullptr; c->pos = nullptr; c->d2 = nullptr; c->best64 = nullptr;
     c->n_loc = c->n_s_total = c->src_off = 0;
+    c->src_no_normals = false;
 }
 
 static void free_source(symmicp_ctx *c)
@@ -216,6 +217,10 @@ int symmicp_set_config(symmicp_ctx *c, const symmicp_config *cfg)
     if ((c->n_t || c->n_loc) && cfg->sort_source != c->cfg.sort_source) return fail(c, SYMMICP_ERR_STATE, "sort_source cannot change after clouds are set");
     if (cfg->mode == SYMMICP_MODE_QUIRKS && c->loss != SYMMICP_LOSS_NONE)
         return fail(c, SYMMICP_ERR_ARG, "QUIRKS takes no robust loss (set SYMMICP_LOSS_NONE first)");
+    if (c->src_no_normals && cfg->mode != SYMMICP_MODE_PLANE)
+        return fail(c, SYMMICP_ERR_STATE, "the source was set without normals: only SYMMICP_MODE_PLANE can run on it");
+    if (c->src_no_normals && cfg->min_normal_dot > -1.0f)
+        return fail(c, SYMMICP_ERR_ARG, "min_normal_dot needs source normals (the source was set without them)");
     int dev = c->cfg.device;
     c->cfg = *cfg;
     c->cfg.device = dev;
@@ -259,7 +264,8 @@ float symmicp_robust_weight(int loss, float scale, float r)
 
 // host strided cloud -> device block of 6 planar arrays.  The usual layouts never touch a host staging loop: records with
 // contiguous x y z (packed AoS, PointXYZ, PointNormal) are copied as they are and split into columns on the device;
-// column-major matrices (Eigen) are copied column by column.  Anything else goes through a host transpose.
+// column-major matrices (Eigen) are copied column by column.  Anything else goes through a host transpose.  nrm == NULL: the normal
+// columns are zero-filled (a PLANE source: no kernel is ever handed an unallocated normal array).
 static int upload_planar(symmicp_ctx *c, const float *xyz, size_t xr, size_t xc, const float *nrm, size_t nr, size_t nc,
                          size_t n, DevBuf<float> &block, bool temp, double centroid[3])
 {
@@ -275,7 +281,9 @@ static int upload_planar(symmicp_ctx *c, const float *xyz, size_t xr, size_t xc,
     float *col[6];
     for (int k = 0; k < 6; k++) col[k] = block.p + (size_t)k * n;
     struct Part { const float *base; size_t rs, cs; int first_col; } parts[2] = {{xyz, xr, xc, 0}, {nrm, nr, nc, 3}};
+    if (!nrm) HIP_TRY(c, hipMemsetAsync(col[3], 0, sizeof(float) * 3 * n, c->stream));
     for (const Part &p : parts) {
+        if (!p.base) continue;
         if (p.cs == 1 && p.rs >= 3) {
             const size_t fl = (n - 1) * p.rs + 3;                  // floats from the first x to the last z
             DevBuf<float> raw;
@@ -574,7 +582,10 @@ int symmicp_set_target(symmicp_ctx *c, const float *xyz, size_t xr, size_t xc, c
 int symmicp_set_source(symmicp_ctx *c, const float *xyz, size_t xr, size_t xc, const float *nrm, size_t nr, size_t nc, size_t n)
 {
     if (!c) return SYMMICP_ERR_ARG;
-    if (!xyz || !nrm) return fail(c, SYMMICP_ERR_ARG, "null source cloud (myicp.cpp:102 assert)");
+    if (!xyz) return fail(c, SYMMICP_ERR_ARG, "null source cloud (myicp.cpp:102 assert)");
+    if (!nrm && c->cfg.mode != SYMMICP_MODE_PLANE) return fail(c, SYMMICP_ERR_ARG, "null source normals (only SYMMICP_MODE_PLANE runs without them)");
+    if (!nrm && c->cfg.min_normal_dot > -1.0f) return fail(c, SYMMICP_ERR_ARG, "min_normal_dot needs source normals");
+    if (!nrm) nr = nc = 0;
     if (n == 0 || n > 0x7fffffffull) return fail(c, SYMMICP_ERR_SIZE, "source size out of range");
     HIP_TRY(c, hipSetDevice(c->device));
     const double t0 = now_s();
@@ -590,8 +601,9 @@ int symmicp_set_source(symmicp_ctx *c, const float *xyz, size_t xr, size_t xc, c
     const size_t r0 = bc > 0 ? b0 : 0;
     arena_begin(c->arena, nu * (56 + 4 * (xr + nr)) + ((size_t)1 << 20));      // (+8 B per point: the packet table's temporaries)
     DevBuf<float> full;
-    int st = upload_planar(c, xyz + r0 * xr, xr, xc, nrm + r0 * nr, nr, nc, nu, full, /*temp=*/true, nullptr);
+    int st = upload_planar(c, xyz + r0 * xr, xr, xc, nrm ? nrm + r0 * nr : nullptr, nr, nc, nu, full, /*temp=*/true, nullptr);
     if (st != SYMMICP_OK) return st;
+    c->src_no_normals = !nrm;
     CloudSoA fs;
     soa_from_block(full.p, nu, fs);
     const uint32_t nl = bc > 0 ? (uint32_t)bc : 1;
@@ -974,6 +986,7 @@ int symmicp_get_stats(symmicp_ctx *c, symmicp_stats *out)
     if (c->cfg.corr == SYMMICP_CORR_IDENTITY) b = (int64_t)c->n_loc * 48;
     else b = (int64_t)c->n_loc * (48 + 4 + 4) + (int64_t)c->n_t * 12;
     if (incr) b += (int64_t)c->n_loc * 24;
+    else if (c->cfg.mode == SYMMICP_MODE_PLANE && !(c->cfg.min_normal_dot > -1.0f)) b -= (int64_t)c->n_loc * 12;      // (no source normals read)
     c->st.bytes_algorithmic_per_pass = b;
     {
         uint32_t fb = 0;

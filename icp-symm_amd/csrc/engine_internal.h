@@ -158,6 +158,7 @@ struct symmicp_ctx {
     float pivot[3] = {0, 0, 0};
     // source share
     uint32_t n_s_total = 0, n_loc = 0, src_off = 0;
+    bool src_no_normals = false;     // the source came without normals (PLANE only): its normal columns hold zeros
     char *src_all = nullptr;         // one allocation behind all per-source arrays below (reused by the next set_source)
     size_t src_all_cap = 0;
     float *src0_block = nullptr, *cur_block = nullptr;

@@ -16,6 +16,7 @@ static void fill_pass_args(symmicp_ctx *c, PassArgs &a, const float Xapply[16], 
     const bool paper = c->cfg.mode != SYMMICP_MODE_QUIRKS;          // PAPER and P2P take their sums about the pivot
     for (int k = 0; k < 3; k++) a.pivot[k] = paper ? c->pivot[k] : 0.0f;
     a.p2p = c->cfg.mode == SYMMICP_MODE_P2P ? 1 : 0;
+    a.plane = c->cfg.mode == SYMMICP_MODE_PLANE ? 1 : 0;
     a.max_d2 = c->cfg.max_corr_dist > 0.f ? c->cfg.max_corr_dist * c->cfg.max_corr_dist : 0.f;
     a.min_ndot = c->cfg.min_normal_dot;
     a.writeback = writeback ? 1 : 0;
@@ -479,6 +480,7 @@ int symmicp_step(symmicp_ctx *c, symmicp_iter_result *out)
     float pbar[3], qbar[3], a[3], t[3], rc = 0.f, Xi[16];
     int st = (c->cfg.mode == SYMMICP_MODE_QUIRKS) ? solve_quirks(c->last, pbar, qbar, a, t, &rc, Xi)
              : (c->cfg.mode == SYMMICP_MODE_PAPER) ? solve_paper(c->last, c->pivot, pbar, qbar, a, t, &rc, Xi)
+             : (c->cfg.mode == SYMMICP_MODE_PLANE) ? solve_plane(c->last, c->pivot, pbar, qbar, a, t, &rc, Xi)
                                                    : solve_p2p(c->last, c->pivot, &rc, Xi);
     if (st != SYMMICP_OK) {
         c->err = "degenerate system (rank-deficient normal equations or non-finite transform; func.cpp:70,96)";
@@ -627,6 +629,7 @@ int symmicp_solve(int mode, const symmicp_sums *sums, const float pivot[3], floa
     if (!sums || !pbar || !qbar || !a || !t || !out16) return SYMMICP_ERR_ARG;
     if (mode == SYMMICP_MODE_QUIRKS) return solve_quirks(*sums, pbar, qbar, a, t, rcond, out16);
     if (mode == SYMMICP_MODE_PAPER) return solve_paper(*sums, pivot, pbar, qbar, a, t, rcond, out16);
+    if (mode == SYMMICP_MODE_PLANE) return solve_plane(*sums, pivot, pbar, qbar, a, t, rcond, out16);
     if (mode == SYMMICP_MODE_P2P) {
         for (int k = 0; k < 3; k++) pbar[k] = qbar[k] = a[k] = t[k] = 0.f;
         return solve_p2p(*sums, pivot, rcond, out16);

@@ -150,6 +150,56 @@ __device__ __forceinline__ void acc_pair(AccN<kNAccW> &a, float px, float py, fl
     a.v[37] += 1.0;
 }
 
+// PLANE (point-to-plane): PAPER's slots with n_p = 0 and s = p + q replaced by p -- rows v = (p x n_q, n_q), c = (p - q) . n_q -- and,
+// in the weighted record (NA = kNAccW), PAPER's weighting with r = c.  Needs no source normal.
+template <int NA>
+__device__ __forceinline__ void acc_plane(AccN<NA> &a, float px, float py, float pz, float qx, float qy, float qz,
+                                          float nx, float ny, float nz, float d2, const float *pivot, int loss, float scale)
+{
+    constexpr bool W = NA == kNAccW;
+    px -= pivot[0]; py -= pivot[1]; pz -= pivot[2];
+    qx -= pivot[0]; qy -= pivot[1]; qz -= pivot[2];
+    float dx = px - qx, dy = py - qy, dz = pz - qz;
+    float m0 = py * nz - pz * ny;
+    float m1 = pz * nx - px * nz;
+    float m2 = px * ny - py * nx;
+    float c = (dx * nx + dy * ny) + dz * nz;
+    const double v[6] = {(double)m0, (double)m1, (double)m2, (double)nx, (double)ny, (double)nz};
+    const double cd = (double)c;
+    if constexpr (W) {
+        const double w = (double)robust_weight(loss, scale, c), wc = w * cd;
+        int k = 0;
+#pragma unroll
+        for (int r = 0; r < 6; r++) {
+            const double wv = w * v[r];
+#pragma unroll
+            for (int s = r; s < 6; s++) { a.v[k] = __builtin_fma(wv, v[s], a.v[k]); k++; }
+        }
+#pragma unroll
+        for (int r = 0; r < 6; r++) a.v[21 + r] = __builtin_fma(v[r], wc, a.v[21 + r]);
+        a.v[27] = __builtin_fma(w, (double)px, a.v[27]); a.v[28] = __builtin_fma(w, (double)py, a.v[28]); a.v[29] = __builtin_fma(w, (double)pz, a.v[29]);
+        a.v[30] = __builtin_fma(w, (double)qx, a.v[30]); a.v[31] = __builtin_fma(w, (double)qy, a.v[31]); a.v[32] = __builtin_fma(w, (double)qz, a.v[32]);
+        a.v[34] += w;
+        a.v[35] = __builtin_fma(wc, cd, a.v[35]);
+        a.v[37] += 1.0;
+    } else {
+        (void)loss; (void)scale;
+        int k = 0;
+#pragma unroll
+        for (int r = 0; r < 6; r++)
+#pragma unroll
+            for (int s = r; s < 6; s++) { a.v[k] = __builtin_fma(v[r], v[s], a.v[k]); k++; }
+#pragma unroll
+        for (int r = 0; r < 6; r++) a.v[21 + r] = __builtin_fma(v[r], cd, a.v[21 + r]);
+        a.v[27] += (double)px; a.v[28] += (double)py; a.v[29] += (double)pz;
+        a.v[30] += (double)qx; a.v[31] += (double)qy; a.v[32] += (double)qz;
+        a.v[34] += 1.0;
+        a.v[35] = __builtin_fma(cd, cd, a.v[35]);
+    }
+    a.v[33] += (double)sqrtf(d2);
+    a.v[36] += (double)d2;
+}
+
 // one step of a sum on the VALU's DPP cross-lane network (no LDS traffic): row_shr 1,2,4,8 builds 16-lane row sums.  A double moves
 // as two 32-bit DPP movs; lanes without a source read 0 (bound_ctrl), i.e. add +0.0.
 template <int CTRL, int ROW_MASK>
@@ -226,13 +276,16 @@ __device__ __forceinline__ void acc_block_reduce_store(AccN<NA> &a, double *part
 // VEC = 4: each thread handles 4 consecutive points per step with 16-byte loads/stores from the planar
 // arrays (needs n, the target offset and the array lengths to be multiples of 4 so every column stays
 // 16-byte aligned); VEC = 1 is the general form.
-template <int VEC, bool W>
+// PL: the PLANE instantiations (acc_plane).  Separate instantiations, not a branch, as W: the other kernels keep their registers.  They read
+// the source normals only to write them back or to gate on them.
+template <int VEC, bool W, bool PL>
 __global__ __launch_bounds__(kPassThreads) void k_pass_identity(PassArgs a_in, CloudSoA tgt)
 {
     if (a_in.loop && a_in.loop->stop) return;
     PassArgs a = a_in;
     if (a_in.loop) a.X = a_in.loop->Xapply;        // device-driven loop: the transform k_reduce_solve left behind
     AccT<W> acc; acc_zero(acc);
+    const bool need_n = !PL || a.writeback || a.min_ndot > -1.0f;
     const uint32_t stride = gridDim.x * blockDim.x * VEC;
     for (uint32_t i0 = (blockIdx.x * blockDim.x + threadIdx.x) * VEC; i0 < a.n; i0 += stride) {
         float x[VEC], y[VEC], z[VEC], nx[VEC], ny[VEC], nz[VEC], qx[VEC], qy[VEC], qz[VEC], qnx[VEC], qny[VEC], qnz[VEC];
@@ -241,9 +294,14 @@ __global__ __launch_bounds__(kPassThreads) void k_pass_identity(PassArgs a_in, C
             *reinterpret_cast<float4 *>(x) = *reinterpret_cast<const float4 *>(a.in.x + i0);
             *reinterpret_cast<float4 *>(y) = *reinterpret_cast<const float4 *>(a.in.y + i0);
             *reinterpret_cast<float4 *>(z) = *reinterpret_cast<const float4 *>(a.in.z + i0);
-            *reinterpret_cast<float4 *>(nx) = *reinterpret_cast<const float4 *>(a.in.nx + i0);
-            *reinterpret_cast<float4 *>(ny) = *reinterpret_cast<const float4 *>(a.in.ny + i0);
-            *reinterpret_cast<float4 *>(nz) = *reinterpret_cast<const float4 *>(a.in.nz + i0);
+            if (need_n) {
+                *reinterpret_cast<float4 *>(nx) = *reinterpret_cast<const float4 *>(a.in.nx + i0);
+                *reinterpret_cast<float4 *>(ny) = *reinterpret_cast<const float4 *>(a.in.ny + i0);
+                *reinterpret_cast<float4 *>(nz) = *reinterpret_cast<const float4 *>(a.in.nz + i0);
+            } else {
+#pragma unroll
+                for (int k = 0; k < VEC; k++) nx[k] = ny[k] = nz[k] = 0.0f;
+            }
             *reinterpret_cast<float4 *>(qx) = *reinterpret_cast<const float4 *>(tgt.x + j0);
             *reinterpret_cast<float4 *>(qy) = *reinterpret_cast<const float4 *>(tgt.y + j0);
             *reinterpret_cast<float4 *>(qz) = *reinterpret_cast<const float4 *>(tgt.z + j0);
@@ -252,7 +310,8 @@ __global__ __launch_bounds__(kPassThreads) void k_pass_identity(PassArgs a_in, C
             *reinterpret_cast<float4 *>(qnz) = *reinterpret_cast<const float4 *>(tgt.nz + j0);
         } else {
             x[0] = a.in.x[i0]; y[0] = a.in.y[i0]; z[0] = a.in.z[i0];
-            nx[0] = a.in.nx[i0]; ny[0] = a.in.ny[i0]; nz[0] = a.in.nz[i0];
+            if (need_n) { nx[0] = a.in.nx[i0]; ny[0] = a.in.ny[i0]; nz[0] = a.in.nz[i0]; }
+            else nx[0] = ny[0] = nz[0] = 0.0f;
             qx[0] = tgt.x[j0]; qy[0] = tgt.y[j0]; qz[0] = tgt.z[j0];
             qnx[0] = tgt.nx[j0]; qny[0] = tgt.ny[j0]; qnz[0] = tgt.nz[j0];
         }
@@ -286,7 +345,8 @@ __global__ __launch_bounds__(kPassThreads) void k_pass_identity(PassArgs a_in, C
         for (int k = 0; k < VEC; k++) {
             if (a.max_d2 > 0.0f && d2[k] > a.max_d2) continue;
             if (a.min_ndot > -1.0f && (npx[k] * qnx[k] + npy[k] * qny[k]) + npz[k] * qnz[k] < a.min_ndot) continue;
-            acc_pair(acc, px[k], py[k], pz[k], npx[k], npy[k], npz[k], qx[k], qy[k], qz[k], qnx[k], qny[k], qnz[k], d2[k], a.pivot, a.p2p, a.loss, a.loss_scale);
+            if (PL) acc_plane(acc, px[k], py[k], pz[k], qx[k], qy[k], qz[k], qnx[k], qny[k], qnz[k], d2[k], a.pivot, a.loss, a.loss_scale);
+            else acc_pair(acc, px[k], py[k], pz[k], npx[k], npy[k], npz[k], qx[k], qy[k], qz[k], qnx[k], qny[k], qnz[k], d2[k], a.pivot, a.p2p, a.loss, a.loss_scale);
         }
     }
     acc_block_reduce_store(acc, a.partials, gridDim.x);
@@ -296,14 +356,16 @@ __global__ __launch_bounds__(kPassThreads) void k_pass_identity(PassArgs a_in, C
 // pass, pairs given by a previous search kernel (brute force): best64[i] holds
 // (d2 bits << 32 | target row).  Target rows are gathered as float4.
 // ---------------------------------------------------------------------------
-template <bool W>
+template <bool W, bool PL>
 __global__ __launch_bounds__(kPassThreads) void k_pass_indexed(PassArgs a, const float4 *__restrict__ tn)
 {
     AccT<W> acc; acc_zero(acc);
+    const bool need_n = !PL || a.writeback || a.min_ndot > -1.0f;
     const uint32_t stride = gridDim.x * blockDim.x;
     for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < a.n; i += stride) {
         float x = a.in.x[i], y = a.in.y[i], z = a.in.z[i];
-        float nx = a.in.nx[i], ny = a.in.ny[i], nz = a.in.nz[i];
+        float nx = 0.0f, ny = 0.0f, nz = 0.0f;
+        if (need_n) { nx = a.in.nx[i]; ny = a.in.ny[i]; nz = a.in.nz[i]; }
         float px = xf_row(a.X.m + 0, x, y, z, 1.0f), py = xf_row(a.X.m + 4, x, y, z, 1.0f), pz = xf_row(a.X.m + 8, x, y, z, 1.0f);
         float npx = xf_row(a.X.m + 0, nx, ny, nz, a.X.nrm_w), npy = xf_row(a.X.m + 4, nx, ny, nz, a.X.nrm_w),
               npz = xf_row(a.X.m + 8, nx, ny, nz, a.X.nrm_w);
@@ -321,7 +383,8 @@ __global__ __launch_bounds__(kPassThreads) void k_pass_indexed(PassArgs a, const
         if (a.max_d2 > 0.0f && d2 > a.max_d2) continue;
         const float4 q = tn[2 * (size_t)j], nq = tn[2 * (size_t)j + 1];     // one 32-byte pair record
         if (a.min_ndot > -1.0f && (npx * nq.x + npy * nq.y) + npz * nq.z < a.min_ndot) continue;
-        acc_pair(acc, px, py, pz, npx, npy, npz, q.x, q.y, q.z, nq.x, nq.y, nq.z, d2, a.pivot, a.p2p, a.loss, a.loss_scale);
+        if (PL) acc_plane(acc, px, py, pz, q.x, q.y, q.z, nq.x, nq.y, nq.z, d2, a.pivot, a.loss, a.loss_scale);
+        else acc_pair(acc, px, py, pz, npx, npy, npz, q.x, q.y, q.z, nq.x, nq.y, nq.z, d2, a.pivot, a.p2p, a.loss, a.loss_scale);
     }
     acc_block_reduce_store(acc, a.partials, gridDim.x);
 }
@@ -923,11 +986,20 @@ struct HotParams {
     float loss_scale;
 };
 
-template <int NA>
+template <bool PL, int NA>
 __device__ __forceinline__ void fused_accumulate(AccN<NA> &acc, const HotParams &h, float nx, float ny, float nz, float px, float py, float pz,
                                                  const float4 &q, const float4 &nq, float d2)
 {
     const Affine &X = h.X;
+    if (PL) {      // (the source normal only for the gate: the rows do not use it)
+        if (h.max_d2 > 0.0f && d2 > h.max_d2) return;
+        if (h.min_ndot > -1.0f) {
+            const float npx = xf_row(X.m + 0, nx, ny, nz, X.nrm_w), npy = xf_row(X.m + 4, nx, ny, nz, X.nrm_w), npz = xf_row(X.m + 8, nx, ny, nz, X.nrm_w);
+            if ((npx * nq.x + npy * nq.y) + npz * nq.z < h.min_ndot) return;
+        }
+        acc_plane(acc, px, py, pz, q.x, q.y, q.z, nq.x, nq.y, nq.z, d2, h.pivot, h.loss, h.loss_scale);
+        return;
+    }
     const float npx = xf_row(X.m + 0, nx, ny, nz, X.nrm_w), npy = xf_row(X.m + 4, nx, ny, nz, X.nrm_w), npz = xf_row(X.m + 8, nx, ny, nz, X.nrm_w);
     if (h.max_d2 > 0.0f && d2 > h.max_d2) return;
     if (h.min_ndot > -1.0f && (npx * nq.x + npy * nq.y) + npz * nq.z < h.min_ndot) return;
@@ -947,11 +1019,13 @@ __device__ __forceinline__ void fused_accumulate(AccN<NA> &acc, const HotParams 
 // that is still settling: the separate k_search_cells lets every block of 256 queries pay the latency of the whole scan machinery
 // for the dozen of them that need it; here a block streams several tiles and scans the failures 256 at a time (the walk and
 // k_accumulate follow as usual).  No normals, no record copies read, no sums: registers for 5 waves per SIMD.
-// W (with ACC): the weighted record of a robust loss.
-template <bool ACC, bool W>
+// W (with ACC): the weighted record of a robust loss.  PL (with ACC): the PLANE record, source normals read only for min_normal_dot.
+template <bool ACC, bool W, bool PL>
 __global__ __launch_bounds__(kPassThreads, ACC ? FUSED_WAVES : COMPACT_WAVES) void k_pass_fused(PassArgs a, TargetIndex ix, WorkLists wl)
 {
     static_assert(ACC || !W, "the search-only form has no sums to weight");
+    static_assert(ACC || !PL, "the search-only form has no rows");
+    const bool need_n = !PL || a.min_ndot > -1.0f;      // (no write-back here)
     constexpr int kList = ACC ? kFusedList : kFusedList / 2;      // (the search-only form keeps 5 workgroups per CU: its tile is 256 points)
     __shared__ uint32_t s_list[kList];
     __shared__ uint32_t s_cnt, s_total;
@@ -1024,8 +1098,9 @@ __global__ __launch_bounds__(kPassThreads, ACC ? FUSED_WAVES : COMPACT_WAVES) vo
                 if (hood_test(a, ix, i, px, py, pz, dist2(px, py, pz, ce.x, ce.y, ce.z), pk, d2, __float_as_int(q.w), pw, d2w)) {
                     float4 qw = q, nqw = nq;
                     if (pw != pk) { qw = ix.tn[2 * (size_t)pw]; nqw = ix.tn[2 * (size_t)pw + 1]; }
-                    const float nx = a.in.nx[i], ny = a.in.ny[i], nz = a.in.nz[i];
-                    fused_accumulate(acc, h, nx, ny, nz, px, py, pz, qw, nqw, d2w);
+                    float nx = 0.0f, ny = 0.0f, nz = 0.0f;
+                    if (need_n) { nx = a.in.nx[i]; ny = a.in.ny[i]; nz = a.in.nz[i]; }
+                    fused_accumulate<PL>(acc, h, nx, ny, nz, px, py, pz, qw, nqw, d2w);
                     s_list[e] = 0xFFFFFFFFu;                       // settled (an idle lane of the scan below)
                 }
             }
@@ -1045,9 +1120,10 @@ __global__ __launch_bounds__(kPassThreads, ACC ? FUSED_WAVES : COMPACT_WAVES) vo
                 const float4 q = a.pairrec[2 * (size_t)i], nq = a.pairrec[2 * (size_t)i + 1];
                 if (nq.w != 0.0f) continue;                            // no target at all, or handed to the walk
                 const float x = a.in.x[i], y = a.in.y[i], z = a.in.z[i];
-                const float nx = a.in.nx[i], ny = a.in.ny[i], nz = a.in.nz[i];
+                float nx = 0.0f, ny = 0.0f, nz = 0.0f;
+                if (need_n) { nx = a.in.nx[i]; ny = a.in.ny[i]; nz = a.in.nz[i]; }
                 const float px = xf_row(X.m + 0, x, y, z, 1.0f), py = xf_row(X.m + 4, x, y, z, 1.0f), pz = xf_row(X.m + 8, x, y, z, 1.0f);
-                fused_accumulate(acc, h, nx, ny, nz, px, py, pz, q, nq, dist2(px, py, pz, q.x, q.y, q.z));
+                fused_accumulate<PL>(acc, h, nx, ny, nz, px, py, pz, q, nq, dist2(px, py, pz, q.x, q.y, q.z));
             }
         }
         __syncthreads();
@@ -1086,7 +1162,8 @@ __global__ __launch_bounds__(kPassThreads, ACC ? FUSED_WAVES : COMPACT_WAVES) vo
                 if (ACC) {
                     const size_t o = (size_t)i;
                     x[k] = gcol<float>(s_col[0])[o]; y[k] = gcol<float>(s_col[1])[o]; z[k] = gcol<float>(s_col[2])[o];
-                    nx[k] = gcol<float>(s_col[3])[o]; ny[k] = gcol<float>(s_col[4])[o]; nz[k] = gcol<float>(s_col[5])[o];
+                    if (need_n) { nx[k] = gcol<float>(s_col[3])[o]; ny[k] = gcol<float>(s_col[4])[o]; nz[k] = gcol<float>(s_col[5])[o]; }
+                    else nx[k] = ny[k] = nz[k] = 0.0f;
                     q[k] = as_float4(gcol<f32x4_t>(s_col[6])[2 * o]); nq[k] = as_float4(gcol<f32x4_t>(s_col[6])[2 * o + 1]);      // a fresh copy (w = 0) has the bits of tq[prev]
                     ce[k] = as_float4(gcol<f32x4_t>(s_col[7])[o]);
                 } else {
@@ -1124,7 +1201,7 @@ __global__ __launch_bounds__(kPassThreads, ACC ? FUSED_WAVES : COMPACT_WAVES) vo
                 }
                 if (certified) {
                     // (the refreshed distance is not stored: 4 of the pass's 76 bytes per point; symmicp_get_correspondences evaluates it)
-                    if (ACC) fused_accumulate(acc, h, nx[k], ny[k], nz[k], px, py, pz, q[k], nq[k], d2);
+                    if (ACC) fused_accumulate<PL>(acc, h, nx[k], ny[k], nz[k], px, py, pz, q[k], nq[k], d2);
                 } else {
                     s_list[atomicAdd(&s_cnt, 1u)] = i;                 // (room for a whole tile: see the flush below)
                 }
@@ -1354,10 +1431,11 @@ __global__ __launch_bounds__(kWalkThreads, 6) void k_search_walk(PassArgs a, Tar
 // The pair's distance is recomputed from the gathered q (bit-identical to the stored one) instead of being read.
 // (A 4-points-per-thread variant with 16-byte column loads was measured and is no faster: the two 16-byte gathers per
 // pair bound this kernel, not the column loads.  Few blocks are: each one ends in a 40-value block reduction.)
-template <bool W>
+template <bool W, bool PL>
 __global__ __launch_bounds__(kPassThreads) void k_accumulate(PassArgs a, const float4 *__restrict__ tn)
 {
     AccT<W> acc; acc_zero(acc);
+    const bool need_n = !PL || a.writeback || a.min_ndot > -1.0f;
     const uint32_t nbp = gridDim.x;
     // grid-stride over blocks of 256 points, XCD-contiguous
     const uint32_t total_blocks = (a.n + kPassThreads - 1) / kPassThreads;
@@ -1365,7 +1443,8 @@ __global__ __launch_bounds__(kPassThreads) void k_accumulate(PassArgs a, const f
         const uint32_t i = lb * kPassThreads + threadIdx.x;
         if (i >= a.n) continue;
         const float x = a.in.x[i], y = a.in.y[i], z = a.in.z[i];
-        const float nx = a.in.nx[i], ny = a.in.ny[i], nz = a.in.nz[i];
+        float nx = 0.0f, ny = 0.0f, nz = 0.0f;
+        if (need_n) { nx = a.in.nx[i]; ny = a.in.ny[i]; nz = a.in.nz[i]; }
         float4 q = a.pairrec[2 * (size_t)i], nq = a.pairrec[2 * (size_t)i + 1];            // the pair's own copy: coalesced
         if (nq.w == 2.0f) {
             // stale copy: the pair went through the tree walk this pass
@@ -1385,7 +1464,8 @@ __global__ __launch_bounds__(kPassThreads) void k_accumulate(PassArgs a, const f
         const float d2 = dist2(px, py, pz, q.x, q.y, q.z);
         if (a.max_d2 > 0.0f && d2 > a.max_d2) continue;
         if (a.min_ndot > -1.0f && (npx * nq.x + npy * nq.y) + npz * nq.z < a.min_ndot) continue;
-        acc_pair(acc, px, py, pz, npx, npy, npz, q.x, q.y, q.z, nq.x, nq.y, nq.z, d2, a.pivot, a.p2p, a.loss, a.loss_scale);
+        if (PL) acc_plane(acc, px, py, pz, q.x, q.y, q.z, nq.x, nq.y, nq.z, d2, a.pivot, a.loss, a.loss_scale);
+        else acc_pair(acc, px, py, pz, npx, npy, npz, q.x, q.y, q.z, nq.x, nq.y, nq.z, d2, a.pivot, a.p2p, a.loss, a.loss_scale);
     }
     acc_block_reduce_store(acc, a.partials, gridDim.x);
 }
@@ -1398,7 +1478,7 @@ __global__ __launch_bounds__(kPassThreads) void k_accumulate(PassArgs a, const f
 // Straggler stage of a device-driven loop (after k_pass_fused and k_search_walk): the pairs of the work list's queries -- the fused pass
 // left them out and marked their record copies stale -- are gathered, their copies refreshed, their rows summed into `gridDim.x` partial
 // columns behind the fused pass's.  Launched whether or not the list is empty (the columns must be written).
-template <bool W>
+template <bool W, bool PL>
 __global__ __launch_bounds__(kPassThreads) void k_accumulate_list(PassArgs a, const float4 *__restrict__ tn, ShardList list)
 {
     if (a.loop) {
@@ -1406,6 +1486,7 @@ __global__ __launch_bounds__(kPassThreads) void k_accumulate_list(PassArgs a, co
         a.X = a.loop->Xapply;
     }
     AccT<W> acc; acc_zero(acc);
+    const bool need_n = !PL || a.min_ndot > -1.0f;      // (no write-back here)
     // block b: shards b, b + gridDim.x, ...; its waves take them in turn (a list is a handful of entries: what counts is that the
     // counters and entries of all shards are requested side by side, not one shard after the other)
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -1414,7 +1495,8 @@ __global__ __launch_bounds__(kPassThreads) void k_accumulate_list(PassArgs a, co
         for (uint32_t e = lane; e < cnt; e += 64) {
             const uint32_t i = list.items[(size_t)shard * list.cap + e];
             const float x = a.in.x[i], y = a.in.y[i], z = a.in.z[i];
-            const float nx = a.in.nx[i], ny = a.in.ny[i], nz = a.in.nz[i];
+            float nx = 0.0f, ny = 0.0f, nz = 0.0f;
+            if (need_n) { nx = a.in.nx[i]; ny = a.in.ny[i]; nz = a.in.nz[i]; }
             const int32_t pos = a.pos_out[i];
             float4 q = make_float4(0.f, 0.f, 0.f, 0.f), nq = make_float4(0.f, 0.f, 0.f, 1.f);
             if (pos >= 0) { q = tn[2 * (size_t)pos]; nq = tn[2 * (size_t)pos + 1]; }
@@ -1426,7 +1508,8 @@ __global__ __launch_bounds__(kPassThreads) void k_accumulate_list(PassArgs a, co
             const float d2 = dist2(px, py, pz, q.x, q.y, q.z);
             if (a.max_d2 > 0.0f && d2 > a.max_d2) continue;
             if (a.min_ndot > -1.0f && (npx * nq.x + npy * nq.y) + npz * nq.z < a.min_ndot) continue;
-            acc_pair(acc, px, py, pz, npx, npy, npz, q.x, q.y, q.z, nq.x, nq.y, nq.z, d2, a.pivot, a.p2p, a.loss, a.loss_scale);
+            if (PL) acc_plane(acc, px, py, pz, q.x, q.y, q.z, nq.x, nq.y, nq.z, d2, a.pivot, a.loss, a.loss_scale);
+            else acc_pair(acc, px, py, pz, npx, npy, npz, q.x, q.y, q.z, nq.x, nq.y, nq.z, d2, a.pivot, a.p2p, a.loss, a.loss_scale);
         }
     }
     acc_block_reduce_store(acc, a.partials, a.partial_cols, a.partial_col0 + blockIdx.x);
@@ -1629,6 +1712,7 @@ __global__ __launch_bounds__(512) void k_reduce_solve(const double *__restrict__
     for (int k = 0; k < kNSum; k++) S.s[k] = (k >= kNAccW) ? 0.0 : s_sum[k];
     float pbar[3], qbar[3], av[3], tv[3], rc = 0.f, Xi[16];
     const int st = (cfg.mode == SYMMICP_MODE_QUIRKS) ? solve::solve_quirks(S, pbar, qbar, av, tv, &rc, Xi, false)
+                 : (cfg.mode == SYMMICP_MODE_PLANE)  ? solve::solve_plane(S, cfg.pivot, pbar, qbar, av, tv, &rc, Xi, false)
                                                       : solve::solve_paper(S, cfg.pivot, pbar, qbar, av, tv, &rc, Xi, false);
     if (st != SYMMICP_OK || !(rc > 1e-6f)) { loop->stop = 1; loop->reason = LOOP_HOST_SOLVE; return; }
 #ifdef RS_STAMPS
@@ -1779,16 +1863,26 @@ void launch_identity_d2(const CloudSoA &in, const Affine &X, const CloudSoA &tgt
 // ---------------------------------------------------------------------------
 // launchers
 // ---------------------------------------------------------------------------
-void launch_pass_identity(const PassArgs &a, CloudSoA tgt, int blocks, bool vec4_ok, hipStream_t s)
+// the instantiation of an accumulating kernel for the pass's record: weighted (robust loss) or not, PLANE or not
+template <typename K>
+static K pick(const PassArgs &a, K plain, K weighted, K plane, K plane_weighted)
 {
     const bool w = a.loss != SYMMICP_LOSS_NONE;
-    if (vec4_ok) hipLaunchKernelGGL((w ? k_pass_identity<4, true> : k_pass_identity<4, false>), dim3(blocks), dim3(kPassThreads), 0, s, a, tgt);
-    else hipLaunchKernelGGL((w ? k_pass_identity<1, true> : k_pass_identity<1, false>), dim3(blocks), dim3(kPassThreads), 0, s, a, tgt);
+    return a.plane ? (w ? plane_weighted : plane) : (w ? weighted : plain);
+}
+
+void launch_pass_identity(const PassArgs &a, CloudSoA tgt, int blocks, bool vec4_ok, hipStream_t s)
+{
+    if (vec4_ok) hipLaunchKernelGGL(pick(a, k_pass_identity<4, false, false>, k_pass_identity<4, true, false>, k_pass_identity<4, false, true>, k_pass_identity<4, true, true>),
+                                    dim3(blocks), dim3(kPassThreads), 0, s, a, tgt);
+    else hipLaunchKernelGGL(pick(a, k_pass_identity<1, false, false>, k_pass_identity<1, true, false>, k_pass_identity<1, false, true>, k_pass_identity<1, true, true>),
+                            dim3(blocks), dim3(kPassThreads), 0, s, a, tgt);
 }
 
 void launch_pass_indexed(const PassArgs &a, const float4 *tn, int blocks, hipStream_t s)
 {
-    hipLaunchKernelGGL(a.loss != SYMMICP_LOSS_NONE ? k_pass_indexed<true> : k_pass_indexed<false>, dim3(blocks), dim3(kPassThreads), 0, s, a, tn);
+    hipLaunchKernelGGL(pick(a, k_pass_indexed<false, false>, k_pass_indexed<true, false>, k_pass_indexed<false, true>, k_pass_indexed<true, true>),
+                       dim3(blocks), dim3(kPassThreads), 0, s, a, tn);
 }
 
 uint32_t shard_capacity(uint32_t n_points)
@@ -1818,7 +1912,7 @@ void launch_pass_tree_split(const PassArgs &a_in, const TargetIndex &ix, const W
     const uint32_t nbp = ((nb + 7u) / 8u) * 8u;
     if (ev) hipEventRecord(ev[0], s);
     if (stage != 2 && nbp) {      // (nbp == 0: a rank whose share is empty)
-        if (compact_blocks > 0) hipLaunchKernelGGL((k_pass_fused<false, false>), dim3(min((uint32_t)compact_blocks, nbp)), dim3(kPassThreads), 0, s, a, ix, wl);
+        if (compact_blocks > 0) hipLaunchKernelGGL((k_pass_fused<false, false, false>), dim3(min((uint32_t)compact_blocks, nbp)), dim3(kPassThreads), 0, s, a, ix, wl);
         else {
             const uint32_t chunk = tune.cells_chunk ? tune.cells_chunk : 16u;      // tiles per chunk
             // queries per tile: 256 while that fills the chip a few times over (256 CUs x 6-7 workgroups), else 128 or 64 (k_search_cells)
@@ -1848,13 +1942,15 @@ void launch_pass_tree_split(const PassArgs &a_in, const TargetIndex &ix, const W
         }
     }
     if (ev) hipEventRecord(ev[3], s);
-    hipLaunchKernelGGL(a.loss != SYMMICP_LOSS_NONE ? k_accumulate<true> : k_accumulate<false>, dim3(acc_blocks), dim3(kPassThreads), 0, s, a, ix.tn);
+    hipLaunchKernelGGL(pick(a, k_accumulate<false, false>, k_accumulate<true, false>, k_accumulate<false, true>, k_accumulate<true, true>),
+                       dim3(acc_blocks), dim3(kPassThreads), 0, s, a, ix.tn);
     if (ev) hipEventRecord(ev[4], s);
 }
 
 void launch_accumulate(const PassArgs &a, const float4 *tn, int blocks, hipStream_t s)
 {
-    hipLaunchKernelGGL(a.loss != SYMMICP_LOSS_NONE ? k_accumulate<true> : k_accumulate<false>, dim3(blocks), dim3(kPassThreads), 0, s, a, tn);
+    hipLaunchKernelGGL(pick(a, k_accumulate<false, false>, k_accumulate<true, false>, k_accumulate<false, true>, k_accumulate<true, true>),
+                       dim3(blocks), dim3(kPassThreads), 0, s, a, tn);
 }
 
 void launch_final_reduce(const double *partials, int blocks, double *out_dev, double *out_host_mapped, uint32_t *ticket,
@@ -1866,8 +1962,8 @@ void launch_final_reduce(const double *partials, int blocks, double *out_dev, do
 
 void launch_pass_fused(const PassArgs &a, const TargetIndex &ix, const WorkLists &wl, int blocks, hipStream_t s)
 {
-    if (a.loss != SYMMICP_LOSS_NONE) hipLaunchKernelGGL((k_pass_fused<true, true>), dim3(blocks), dim3(kPassThreads), 0, s, a, ix, wl);
-    else hipLaunchKernelGGL((k_pass_fused<true, false>), dim3(blocks), dim3(kPassThreads), 0, s, a, ix, wl);
+    hipLaunchKernelGGL(pick(a, k_pass_fused<true, false, false>, k_pass_fused<true, true, false>, k_pass_fused<true, false, true>, k_pass_fused<true, true, true>),
+                       dim3(blocks), dim3(kPassThreads), 0, s, a, ix, wl);
 }
 
 void launch_loop_stragglers(const PassArgs &a, const TargetIndex &ix, const WorkLists &wl, int list_blocks, const PassTuning &tune, hipStream_t s)
@@ -1875,7 +1971,8 @@ void launch_loop_stragglers(const PassArgs &a, const TargetIndex &ix, const Work
     // (short lists: the wave-per-entry regime; anything above the threshold strides one thread per entry over this grid)
     const uint32_t wave_mode_max = tune.wave_mode_max;
     hipLaunchKernelGGL(k_search_walk<false>, dim3(512), dim3(kWalkThreads), 0, s, a, ix, wl, wl.work, wave_mode_max, 0xFFFFFFFFu);
-    hipLaunchKernelGGL(a.loss != SYMMICP_LOSS_NONE ? k_accumulate_list<true> : k_accumulate_list<false>, dim3(list_blocks), dim3(kPassThreads), 0, s, a, ix.tn, wl.work);
+    hipLaunchKernelGGL(pick(a, k_accumulate_list<false, false>, k_accumulate_list<true, false>, k_accumulate_list<false, true>, k_accumulate_list<true, true>),
+                       dim3(list_blocks), dim3(kPassThreads), 0, s, a, ix.tn, wl.work);
 }
 
 void launch_reduce_solve(const double *partials, int blocks, double *out_dev, int mode, LoopState *loop, LoopConfig cfg, LoopRecord *ring, int ring_len,

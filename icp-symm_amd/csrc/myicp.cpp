@@ -6,7 +6,7 @@
 
 MyICP::MyICP() : max_iters(10), diff_threshold(1.f),                       // myicp.cpp:6
                  mode_(SYMMICP_MODE_QUIRKS), corr_(SYMMICP_CORR_IDENTITY), verbose_(true),
-                 have_src_normals_(false), have_tgt_normals_(false), loss_(SYMMICP_LOSS_NONE), loss_scale_(0.f), ctx_(nullptr), ctx_corr_(-1)
+                 have_src_normals_(false), have_tgt_normals_(false), loss_(SYMMICP_LOSS_NONE), loss_scale_(0.f), ctx_(nullptr), ctx_corr_(-1), ctx_no_src_normals_(false)
 {
 	cloud_src = pcl::PointCloud<PointT>::Ptr(new pcl::PointCloud<PointT>);
 	cloud_tgt = pcl::PointCloud<PointT>::Ptr(new pcl::PointCloud<PointT>);
@@ -32,6 +32,7 @@ symmicp_ctx *MyICP::context()
 		cfg.corr = corr_;
 		if (symmicp_create(&cfg, &ctx_) != SYMMICP_OK) { ctx_ = nullptr; return nullptr; }
 		ctx_corr_ = (int)corr_;
+		ctx_no_src_normals_ = false;
 	}
 	return ctx_;
 }
@@ -112,6 +113,11 @@ void MyICP::estimateNormals()
 	Job jobs[2] = {{cloud_src.get(), cloud_pn_src.get(), have_src_normals_}, {cloud_tgt.get(), cloud_pn_tgt.get(), have_tgt_normals_}};
 	for (Job &j : jobs) {
 		const size_t n = j.c->points.size();
+		// point-to-plane reads the target's normals only: the source's are not estimated (align() passes none unless the caller did)
+		if (mode_ == SYMMICP_MODE_PLANE && j.pn == cloud_pn_src.get() && !j.have) {
+			fill_pn(*j.c, nullptr, *j.pn);
+			continue;
+		}
 		if (j.have && j.pn->points.size() == n) {
 			for (size_t i = 0; i < n; i++) { j.pn->points[i].x = j.c->points[i].x; j.pn->points[i].y = j.c->points[i].y; j.pn->points[i].z = j.c->points[i].z; }
 			continue;
@@ -129,6 +135,8 @@ void MyICP::estimateNormals()
 int MyICP::align(float out4x4[16], const float *guess4x4)
 {
 	assert(cloud_src && cloud_tgt);                                        // myicp.cpp:102
+	const bool source_normals = mode_ != SYMMICP_MODE_PLANE || have_src_normals_;
+	if (ctx_ && ctx_no_src_normals_ && mode_ != SYMMICP_MODE_PLANE) { symmicp_destroy(ctx_); ctx_ = nullptr; }   // (it would refuse the mode)
 	symmicp_ctx *ctx = context();
 	if (!ctx) { error_ = "symmicp_create failed: no usable gfx950 HIP device (there is no CPU fallback)"; result_.status = SYMMICP_ERR_HIP; return SYMMICP_ERR_HIP; }
 	estimateNormals();                                                     // myicp.cpp:105
@@ -143,8 +151,11 @@ int MyICP::align(float out4x4[16], const float *guess4x4)
 	if (st == SYMMICP_OK) {
 		if (!cloud_pn_tgt->points.empty() && !cloud_pn_src->points.empty()) {
 			st = symmicp_set_target(ctx, &cloud_pn_tgt->points[0].x, fs, 1, &cloud_pn_tgt->points[0].normal_x, fs, 1, cloud_pn_tgt->points.size());
-			if (st == SYMMICP_OK)
-				st = symmicp_set_source(ctx, &cloud_pn_src->points[0].x, fs, 1, &cloud_pn_src->points[0].normal_x, fs, 1, cloud_pn_src->points.size());
+			if (st == SYMMICP_OK) {
+				st = symmicp_set_source(ctx, &cloud_pn_src->points[0].x, fs, 1, source_normals ? &cloud_pn_src->points[0].normal_x : nullptr, fs, 1,
+				                        cloud_pn_src->points.size());
+				ctx_no_src_normals_ = st == SYMMICP_OK && !source_normals;
+			}
 		} else {
 			st = SYMMICP_ERR_SIZE;
 		}

@@ -252,17 +252,10 @@ SYMMICP_HD inline int solve_quirks(const symmicp_sums &S, float pbar[3], float q
     return SYMMICP_OK;
 }
 
-// Rusinkiewicz 2019 as the reference's comments intend it (func.cpp:84,94): centred rows, joint
-// 6 x 6 system, T(qbar) R T(t cos) R T(-pbar).  The pass accumulated un-centred sums about
-// `pivot`; the centring is applied here algebraically:
-//   m~ = m - s x n, c~ = c - d.n with s = pbar+qbar, d = pbar-qbar (means about the pivot).
-SYMMICP_HD inline int solve_paper(const symmicp_sums &S, const float pivot[3], float pbar[3], float qbar[3], float a[3], float t[3],
-                float *rcond, float out16[16], bool exact_rc = true)
+// The joint 6 x 6 system of PAPER and PLANE from un-centred sums, centred algebraically: rows m~ = m - s x n, c~ = c - d . n
+// (PAPER: s = pbar + qbar, d = pbar - qbar; PLANE: s = pbar, d = 0), solved for x = (a, t) of A x = -b.  Returns the conditioning.
+SYMMICP_HD inline double solve_centred(const Blocks &B, const double s[3], const double d[3], float a[3], float t[3], float *rcond, bool exact_rc)
 {
-    const Blocks B = unpack(S);
-    if (!(B.cnt >= 6.0)) return SYMMICP_ERR_DEGENERATE;
-    double pb[3], qb[3], s[3], d[3];
-    for (int k = 0; k < 3; ++k) { pb[k] = B.sp[k] / B.cnt; qb[k] = B.sq[k] / B.cnt; s[k] = pb[k] + qb[k]; d[k] = pb[k] - qb[k]; }
     const double K[3][3] = {{0, -s[2], s[1]}, {s[2], 0, -s[0]}, {-s[1], s[0], 0}};   // K n = s x n
     double KN[3][3], MNKt[3][3], KNKt[3][3];
     for (int r = 0; r < 3; ++r)
@@ -306,8 +299,23 @@ SYMMICP_HD inline int solve_paper(const symmicp_sums &S, const float pivot[3], f
     const double rc = sys.solve(rhs, x6, exact_rc);
     if (rcond) *rcond = (float)rc;
     for (int k = 0; k < 6; ++k) x6[k] *= D[k];
+    for (int k = 0; k < 3; ++k) { a[k] = (float)x6[k]; t[k] = (float)x6[k + 3]; }
+    return rc;
+}
+
+// Rusinkiewicz 2019 as the reference's comments intend it (func.cpp:84,94): centred rows, joint
+// 6 x 6 system, T(qbar) R T(t cos) R T(-pbar).  The pass accumulated un-centred sums about
+// `pivot`; the centring is applied here algebraically:
+//   m~ = m - s x n, c~ = c - d.n with s = pbar+qbar, d = pbar-qbar (means about the pivot).
+SYMMICP_HD inline int solve_paper(const symmicp_sums &S, const float pivot[3], float pbar[3], float qbar[3], float a[3], float t[3],
+                float *rcond, float out16[16], bool exact_rc = true)
+{
+    const Blocks B = unpack(S);
+    if (!(B.cnt >= 6.0)) return SYMMICP_ERR_DEGENERATE;
+    double pb[3], qb[3], s[3], d[3];
+    for (int k = 0; k < 3; ++k) { pb[k] = B.sp[k] / B.cnt; qb[k] = B.sq[k] / B.cnt; s[k] = pb[k] + qb[k]; d[k] = pb[k] - qb[k]; }
+    const double rc = solve_centred(B, s, d, a, t, rcond, exact_rc);
     for (int k = 0; k < 3; ++k) {
-        a[k] = (float)x6[k]; t[k] = (float)x6[k + 3];
         pbar[k] = (float)(pb[k] + (pivot ? (double)pivot[k] : 0.0));
         qbar[k] = (float)(qb[k] + (pivot ? (double)pivot[k] : 0.0));
     }
@@ -325,6 +333,43 @@ SYMMICP_HD inline int solve_paper(const symmicp_sums &S, const float pivot[3], f
     X.translate(qbar);
     X.rotate(R);
     X.translate(tc);
+    X.rotate(R);
+    X.translate(mp);
+    X.store(out16);
+    if (!(rc > 1e-12)) return SYMMICP_ERR_DEGENERATE;
+    for (int k = 0; k < 16; ++k)
+        if (!finite32(out16[k])) return SYMMICP_ERR_DEGENERATE;
+    return SYMMICP_OK;
+}
+
+// Point-to-plane (Chen-Medioni): minimise sum ((R p + t - q) . n_q)^2, linearised about the weighted source centroid pbar
+// (about the pivot).  The pass accumulated PAPER's record with n_p = 0 and s = p: rows v = (p x n_q, n_q), c = (p - q) . n_q.
+// The centring is applied here algebraically: m~ = m - pbar x n (c needs none: the rotation turns about pbar, the translation
+// absorbs the rest).  Solved as PAPER's system (the same power-of-two equilibration, so 2^k-scaled clouds solve to the same bits);
+// the increment is T(pbar + t) R(|a|, a / |a|) T(-pbar) with pbar in the caller's frame.
+SYMMICP_HD inline int solve_plane(const symmicp_sums &S, const float pivot[3], float pbar[3], float qbar[3], float a[3], float t[3],
+                float *rcond, float out16[16], bool exact_rc = true)
+{
+    const Blocks B = unpack(S);
+    if (!(B.cnt >= 6.0)) return SYMMICP_ERR_DEGENERATE;
+    double pb[3], qb[3];
+    const double zero[3] = {0.0, 0.0, 0.0};
+    for (int k = 0; k < 3; ++k) { pb[k] = B.sp[k] / B.cnt; qb[k] = B.sq[k] / B.cnt; }
+    const double rc = solve_centred(B, pb, zero, a, t, rcond, exact_rc);
+    for (int k = 0; k < 3; ++k) {
+        pbar[k] = (float)(pb[k] + (pivot ? (double)pivot[k] : 0.0));
+        qbar[k] = (float)(qb[k] + (pivot ? (double)pivot[k] : 0.0));
+    }
+    const float na = sqrt((a[0] * a[0] + a[1] * a[1]) + a[2] * a[2]);
+    float R[3][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}};
+    if (na > 0.f) {
+        const float ax[3] = {a[0] / na, a[1] / na, a[2] / na};
+        angle_axis(na, ax, R);
+    }
+    const float pt[3] = {pbar[0] + t[0], pbar[1] + t[1], pbar[2] + t[2]};
+    const float mp[3] = {-pbar[0], -pbar[1], -pbar[2]};
+    Affine3 X;
+    X.translate(pt);
     X.rotate(R);
     X.translate(mp);
     X.store(out16);

@@ -158,6 +158,7 @@ struct PassArgs {
     uint32_t pkt_chunk, pkt_lds_pad;    // ... packets per XCD chunk (0: 64); extra dynamic LDS per workgroup (occupancy experiments)
     int32_t loss;                       // robust loss (SYMMICP_LOSS_*): != NONE selects the weighted instantiation of every accumulating kernel
     float loss_scale;                   // ... its scale (robust_loss.h)
+    int32_t plane;                      // SYMMICP_MODE_PLANE: the launchers pick the PLANE instantiations (acc_plane); read by the host only
 };
 
 // host-side launch tuning of the tree passes (environment switches, read once by the engine)

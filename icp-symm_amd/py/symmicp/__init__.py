@@ -20,7 +20,7 @@ LIB_PATH = os.environ.get("SYMMICP_LIB") or os.path.join(_ROOT, "lib", "libsymmi
 NSUM = 40
 UNIQUE_ID_BYTES = 128
 OK, ERR_ARG, ERR_SIZE, ERR_DEGENERATE, ERR_IO, ERR_HIP, ERR_STATE, ERR_COMM = range(8)
-MODE_QUIRKS, MODE_PAPER, MODE_P2P = 0, 1, 2
+MODE_QUIRKS, MODE_PAPER, MODE_P2P, MODE_PLANE = 0, 1, 2, 3
 CORR_IDENTITY, CORR_BRUTE, CORR_TREE = 0, 1, 2
 APPLY_DEFAULT, APPLY_INCREMENTAL, APPLY_CUMULATIVE = 0, 1, 2
 LOSS_NONE, LOSS_HUBER, LOSS_TUKEY, LOSS_CAUCHY, LOSS_GEMAN_MCCLURE = range(5)
@@ -348,8 +348,10 @@ class Engine:
         return lo.value, sc.value
 
     def set_source(self, xyz, nrm):
-        xyz, nrm = _cloud(xyz), _cloud(nrm)
-        self._chk(self._L.symmicp_set_source(self._h, _fptr(xyz), 3, 1, _fptr(nrm), 3, 1, xyz.shape[0]))
+        """nrm may be None in MODE_PLANE (the library holds zero source normals then)"""
+        xyz = _cloud(xyz)
+        nrm = None if nrm is None else _cloud(nrm)
+        self._chk(self._L.symmicp_set_source(self._h, _fptr(xyz), 3, 1, None if nrm is None else _fptr(nrm), 3, 1, xyz.shape[0]))
         self.n_source = xyz.shape[0]
 
     def set_target(self, xyz, nrm):
@@ -531,8 +533,9 @@ class MyICP:
         self.normals_tgt = None if normals is None else _cloud(normals)
 
     def estimateNormals(self):
-        # myicp.cpp:152-172: k = 10, flipped toward the origin
-        if self.normals_src is None:
+        # myicp.cpp:152-172: k = 10, flipped toward the origin.  Point-to-plane uses the target's normals only: in MODE_PLANE the
+        # source's are not estimated (the engine runs without them unless the caller supplied them)
+        if self.normals_src is None and self._cfg["mode"] != MODE_PLANE:
             self.normals_src, _ = estimate_normals(self.cloud_src, 10)
         if self.normals_tgt is None:
             self.normals_tgt, _ = estimate_normals(self.cloud_tgt, 10)

@@ -44,7 +44,7 @@ public:
 	MyICP &operator=(const MyICP &) = delete;
 	void setMaximumIterations(int n) { max_iters = n; }
 	void setDiffThreshold(float d) { diff_threshold = d; }
-	void setMode(symmicp_mode m) { mode_ = m; }                    // default SYMMICP_MODE_QUIRKS (= the reference)
+	void setMode(symmicp_mode m) { mode_ = m; }                    // default SYMMICP_MODE_QUIRKS (= the reference); PLANE estimates no source normals
 	void setCorrespondence(symmicp_corr c) { corr_ = c; }          // default SYMMICP_CORR_IDENTITY (= the reference)
 	void setVerbose(bool v) { verbose_ = v; }
 	// robust loss of the PAPER loop (symmicp_set_robust_loss; default SYMMICP_LOSS_NONE): checked by align(), which
@@ -71,6 +71,7 @@ private:
 	float loss_scale_;
 	symmicp_ctx *ctx_;
 	int ctx_corr_;
+	bool ctx_no_src_normals_;            // the context holds a source set without normals (PLANE): no other mode can run on it
 	float transform_[16];
 	symmicp_result result_;
 	std::string error_;

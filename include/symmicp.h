@@ -49,8 +49,12 @@ typedef enum {
  * normals rotated only.  P2P is the closed-form point-to-point fit of the reference's
  * regist.h:8-72 (registrateNPoint: centroids, 3x3 cross-covariance, SVD, reflection fix) run as an
  * ICP loop -- what the RegisterP2P stub (myicp.cpp:43-59) was heading for; record slots 0..8 then hold
- * sum p q^T instead of the symmetric-objective Gram matrix. */
-typedef enum { SYMMICP_MODE_QUIRKS = 0, SYMMICP_MODE_PAPER = 1, SYMMICP_MODE_P2P = 2 } symmicp_mode;
+ * sum p q^T instead of the symmetric-objective Gram matrix.  PLANE is point-to-plane ICP (Chen-Medioni):
+ * minimise sum ((R p + t - q) . n_q)^2 with the TARGET's normals only; pivot, CUMULATIVE default and rotated-only normals
+ * as PAPER.  Its record uses PAPER's slots with n_p = 0 and s = p + q replaced by p: v_i = (p_i x n_q, n_q),
+ * c_i = (p_i - q_i) . n_q, both points about the pivot; the increment is T(pbar + t) R T(-pbar) with R = AngleAxis(|a|, a/|a|)
+ * about the (weighted) source centroid.  PLANE alone needs no source normals: symmicp_set_source takes nrm == NULL then. */
+typedef enum { SYMMICP_MODE_QUIRKS = 0, SYMMICP_MODE_PAPER = 1, SYMMICP_MODE_P2P = 2, SYMMICP_MODE_PLANE = 3 } symmicp_mode;
 
 /* Correspondence.  IDENTITY is what the reference does (myicp.cpp:130, the
  * search is a todo at :128-131).  BRUTE and TREE are exact nearest neighbour
@@ -70,7 +74,8 @@ typedef enum { SYMMICP_APPLY_DEFAULT = 0, SYMMICP_APPLY_INCREMENTAL = 1, SYMMICP
 /* Robust loss (symmicp_set_robust_loss): every pair is weighted by w(r / scale) of its residual r, run as iteratively
  * reweighted least squares (each pass weights the pairs at their current position; the solve is the usual one on the
  * weighted sums).  r is, in PAPER, c = (p - q) . (n_p + n_q), the quantity whose square the symmetric objective sums --
- * so `scale` is in units of c, about TWICE the point-to-plane distance when the two normals agree -- and in P2P
+ * so `scale` is in units of c, about TWICE the point-to-plane distance when the two normals agree -- in PLANE
+ * r = c = (p - q) . n_q, the signed point-to-plane distance itself (`scale` in plain length units), and in P2P
  * r = |p - q|.  With u = r / scale:
  *   HUBER          1 if |u| <= 1, else 1/|u|
  *   TUKEY          (1 - u^2)^2 if |u| < 1, else 0
@@ -109,6 +114,8 @@ typedef struct {
  *   [33] sum_i |p_i - q_i|   (evalDiff, func.cpp:19-32, over the current pairs)
  *   [34] number of pairs     [35] sum_i c_i^2      [36] sum_i |p_i - q_i|^2
  *   [37..39] reserved (0)
+ * PLANE: v_i = (p_i x n_q, n_q) and c_i = (p_i - q_i) . n_q in fp32, unfused: m0 = py*nz - pz*ny, m1 = pz*nx - px*nz,
+ *   m2 = px*ny - py*nx, c = (dx*nx + dy*ny) + dz*nz with n = n_q, d = p - q (p, q about the pivot); every other slot as above.
  * With a robust loss set (symmicp_set_robust_loss), w_i = the pair's weight:
  *   [0..32], [35]  the same sums with every pair scaled by w_i: sum w v v^T, sum w v c, sum w p, sum w q, sum w c^2
  *                  (P2P: sum w p q^T and the weighted coordinate sums)
@@ -147,7 +154,7 @@ void symmicp_destroy(symmicp_ctx *ctx);                           /* MyICP::~MyI
 const char *symmicp_last_error(const symmicp_ctx *ctx);           /* (reference has none: asserts / silent NaN) */
 int symmicp_set_config(symmicp_ctx *ctx, const symmicp_config *cfg);   /* myicp.h:19 "todo add params" */
 int symmicp_version(void);
-/* Robust loss of the PAPER and P2P loops (symmicp_loss above; off = SYMMICP_LOSS_NONE, the default).  SYMMICP_ERR_ARG for
+/* Robust loss of the PAPER, PLANE and P2P loops (symmicp_loss above; off = SYMMICP_LOSS_NONE, the default).  SYMMICP_ERR_ARG for
  * an unknown loss, for a scale that is not finite and > 0 while loss != NONE, and for any loss in SYMMICP_MODE_QUIRKS
  * (symmicp_set_config refuses to switch a context with a loss into QUIRKS the same way).  Takes effect at the next pass:
  * it may be called between symmicp_step calls (e.g. to anneal the scale); a device-driven run inside symmicp_align keeps
@@ -167,7 +174,11 @@ float symmicp_robust_weight(int loss, float scale, float r);
  * Data is copied to the device; the caller keeps ownership.  With a
  * communicator attached every rank passes the FULL cloud (same pointer arithmetic on every rank) and uploads only its own
  * share: rows [begin, begin + count) of symmicp_shard_range, Morton-sorted on the device; the target is replicated.
- * set_target also builds the search index when corr != IDENTITY. */
+ * set_target also builds the search index when corr != IDENTITY.
+ * Source normals are optional in SYMMICP_MODE_PLANE, and only there: set_source with nrm == NULL (strides ignored) is
+ * accepted when cfg.mode == PLANE and SYMMICP_ERR_ARG in every other mode.  The engine then holds zero source normals:
+ * while such a source is set, symmicp_set_config refuses any other mode (SYMMICP_ERR_STATE), min_normal_dot > -1 is refused
+ * (SYMMICP_ERR_ARG: there is no source normal to gate on) and symmicp_get_source returns zero normals. */
 int symmicp_set_source(symmicp_ctx *ctx, const float *xyz, size_t xyz_row_stride, size_t xyz_col_stride,
                        const float *nrm, size_t nrm_row_stride, size_t nrm_col_stride, size_t n);
 int symmicp_set_target(symmicp_ctx *ctx, const float *xyz, size_t xyz_row_stride, size_t xyz_col_stride,
@@ -203,6 +214,7 @@ size_t symmicp_local_source_count(const symmicp_ctx *ctx);
 size_t symmicp_local_source_offset(const symmicp_ctx *ctx);
 
 /* ---- host-side pieces of func.cpp:76-102, exposed for parity tests ----- */
+/* PAPER and PLANE: pbar / qbar = the (weighted) centroids in the caller's frame, (a, t) the solved 6-vector; P2P: zeros */
 int symmicp_solve(int mode, const symmicp_sums *sums, const float pivot[3],
                   float pbar[3], float qbar[3], float a[3], float t[3], float *rcond, float out16[16]);
 
@@ -253,7 +265,8 @@ typedef struct {
     int32_t grid_level;        /* cells per axis = 2^grid_level */
     int32_t tree_levels;
     int64_t pass_blocks;
-    int64_t bytes_algorithmic_per_pass;  /* N_s*(48+4+4)+N_t*12 (NN) or N_s*48 (identity) [+24 N_s write-back] */
+    int64_t bytes_algorithmic_per_pass;  /* N_s*(48+4+4)+N_t*12 (NN) or N_s*48 (identity) [+24 N_s write-back]
+                                            [-12 N_s: PLANE reads no source normals without write-back and min_normal_dot] */
     /* per-kernel HIP-event time since the last reset (timing mode), slots:
      * 0 k_search_cells, 1 idle gap between cells and walk, 2 k_search_walk, 3 k_accumulate, 4 k_final_reduce,
      * 5 the single pass kernel of the IDENTITY / BRUTE modes (k_pass_identity, or k_nn_brute + k_pass_indexed),
