@@ -200,7 +200,11 @@ int symmicp_get_transform(const symmicp_ctx *ctx, float out16[16]);           /*
 size_t symmicp_format_result(const float transform16[16], char *buf, size_t cap);
 int symmicp_get_pivot(const symmicp_ctx *ctx, float out3[3]);
 /* current pairs in ORIGINAL numbering: idx[i] = target row paired with source row i
- * (rows of this rank's share; -1 = rejected), d2[i] = squared distance. Either may be NULL.  (SYMMICP_CORR_IDENTITY and _TREE evaluate
+ * (rows of this rank's share; -1 = rejected), d2[i] = squared distance. Either may be NULL.
+ * Where row i is written: a Morton-sorted source (BRUTE and TREE with cfg.sort_source) writes the share's pairs at the caller's rows,
+ * so cap >= the whole source's count and rows outside the share stay -1 / 0; an unsorted source (IDENTITY, or sort_source == 0)
+ * writes them at share rows 0 .. symmicp_local_source_count() - 1 (caller row = symmicp_local_source_offset() + i), cap >= the
+ * share's count.  With a single rank the two coincide.  (SYMMICP_CORR_IDENTITY and _TREE evaluate
  * the distances here, at the positions the last pass gave the points: a pass stores them only for the pairs it searched.) */
 int symmicp_get_correspondences(symmicp_ctx *ctx, int32_t *idx, float *d2, size_t cap);
 /* current (transformed) source points / normals of this rank's share, original row order, packed AoS. */

@@ -1,5 +1,6 @@
-"""Randomised exactness sweep: GPU tree search vs the oracle's exact NN, every pass of short alignments, over random
-sizes / cloud kinds / motions / apply modes / estimators.  Used by tests/test_gpu_parity.py (fixed number of cases) and
+"""Randomised exactness sweep: GPU pairs (tree, brute force, identity) vs the oracle's exact NN and the pass record vs the numpy
+record of _record_ref.py, every pass of short alignments, over random sizes / cloud kinds / motions / apply modes / estimators /
+robust losses / pair gates.  Used by tests/test_gpu_parity.py (fixed number of cases) and
 from the command line for longer runs:  python tests/_fuzz_nn.py [seconds] [seed]"""
 import os, sys, time
 ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
@@ -10,6 +11,7 @@ import numpy as np
 
 
 def run(budget_s=None, max_cases=None, seed=0, verbose=True):
+    import _record_ref as rec
     import symmicp as sym
     from symmicp import synth
     from oracle import oracle
@@ -45,31 +47,47 @@ def run(budget_s=None, max_cases=None, seed=0, verbose=True):
             R = synth.rotation(float(rng.uniform(0, 20)), rng.standard_normal(3))
             tgt = (src.astype(np.float64) @ R.T + rng.uniform(-0.05, 0.05, 3)).astype(np.float32); tn = (sn @ R.T).astype(np.float32)
         apply_mode = int(rng.choice([sym.APPLY_INCREMENTAL, sym.APPLY_CUMULATIVE]))
-        mode = int(rng.choice([sym.MODE_PAPER, sym.MODE_QUIRKS, sym.MODE_P2P]))
-        case = dict(kind_s=kind_s, kind_t=kind_t, n_s=n_s, n_t=tgt.shape[0], apply=apply_mode, mode=mode)
+        mode = int(rng.choice([sym.MODE_PAPER, sym.MODE_QUIRKS, sym.MODE_P2P, sym.MODE_PLANE]))
+        # identity pairing needs a row for row target; losses and gates on a third of the cases each
+        corr = int(rng.choice([sym.CORR_TREE, sym.CORR_TREE, sym.CORR_BRUTE, sym.CORR_IDENTITY] if n_s == len(tgt) else [sym.CORR_TREE, sym.CORR_BRUTE]))
+        loss = int(rng.choice([sym.LOSS_NONE, sym.LOSS_HUBER, sym.LOSS_CAUCHY])) if mode != sym.MODE_QUIRKS and rng.random() < 0.35 else 0
+        scale = float(rng.choice([0.01, 0.05, 0.2]))
+        mcd = 0.0
+        if rng.random() < 0.3:
+            d2_0 = rec.dist2(src, tgt) if corr == sym.CORR_IDENTITY else oracle.nn_grid(src, tgt)[1]
+            mcd = float(np.sqrt(np.median(d2_0)))
+        mnd = float(rng.choice([0.0, 0.5])) if rng.random() < 0.3 else -2.0
+        case = dict(kind_s=kind_s, kind_t=kind_t, n_s=n_s, n_t=tgt.shape[0], apply=apply_mode, mode=mode, corr=corr, loss=loss,
+                    scale=scale, max_corr_dist=mcd, min_normal_dot=mnd)
         cases += 1
-        with sym.Engine(mode=mode, corr=sym.CORR_TREE, apply=apply_mode, max_iters=6, fixed_iters=1) as e:
+        with sym.Engine(mode=mode, corr=corr, apply=apply_mode, max_iters=6, fixed_iters=1, max_corr_dist=mcd, min_normal_dot=mnd) as e:
             e.set_target(tgt, tn); e.set_source(src, sn)
+            if loss:
+                e.set_robust_loss(loss, scale)
             last = e.begin()
             for it in range(6):
                 idx, d2 = e.correspondences()
                 if apply_mode == sym.APPLY_INCREMENTAL:
-                    p, pn = e.source(); ri, rd = oracle.nn_grid(p, tgt)
-                    # the pass's 40-double record against a host recomputation from the returned pairs
-                    S = oracle.reduce40(p, pn, tgt, tn, idx=idx, pivot=None if mode == sym.MODE_QUIRKS else e.pivot(),
-                                        p2p=(mode == sym.MODE_P2P))
-                    g = np.asarray(last["sums"], np.float64)
-                    if np.abs(g - S).max() > 1e-9 * max(1.0, np.abs(S).max()):
-                        failures.append(dict(case, it=it, sums_err=float(np.abs(g - S).max() / max(1.0, np.abs(S).max()))))
-                        if verbose:
-                            print("SUMS", failures[-1], flush=True)
-                        break
+                    p, pn = e.source()                  # the points the pass accumulated, written back
                 else:
-                    ri, rd = oracle.nn_grid(src, tgt, X=e.transform())
+                    p, pn = rec.moved(e.transform(), src, sn, mode)
+                if corr == sym.CORR_IDENTITY:
+                    ri, rd = np.arange(n_s, dtype=np.int32), rec.dist2(p, tgt)
+                else:
+                    ri, rd = oracle.nn_grid(p, tgt)
                 if not (np.array_equal(idx, ri) and np.array_equal(d2, rd)):
                     failures.append(dict(case, it=it, nbad=int((idx != ri).sum())))
                     if verbose:
                         print("MISMATCH", failures[-1], flush=True)
+                    break
+                # the pass's 40-double record against the numpy record of the returned pairs, slot by slot
+                S, M, _ = rec.record(mode, p, pn, tgt, tn, idx, e.pivot(), loss, scale, rec.f32_max_d2(mcd), mnd)
+                try:
+                    rec.assert_record(last["sums"], S, M, rec.TOL_REC if loss else rec.TOL_EXACT)
+                except AssertionError as x:
+                    failures.append(dict(case, it=it, sums=str(x)[:300]))
+                    if verbose:
+                        print("SUMS", failures[-1], flush=True)
                     break
                 last = e.step(check=False)
                 if last["status"] != 0:

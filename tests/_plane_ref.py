@@ -7,64 +7,7 @@ it centres the rows directly from the points (m~ = (p - pbar) x n_q) in fp64, so
 np.linalg.solve and composes T(pbar + t) R(a) T(-pbar) in fp64."""
 import numpy as np
 
-NSUM = 40
-
-
-def np_weight(loss, scale, r):
-    """robust_loss.h in fp32 (0 = none)"""
-    r = np.asarray(r, np.float32)
-    one = np.float32(1)
-    with np.errstate(divide="ignore", over="ignore"):
-        u = r / np.float32(scale)
-        au = np.abs(u)
-        u2 = u * u
-        if loss == 1:
-            return np.where(au <= one, one, one / au).astype(np.float32)
-        if loss == 2:
-            t = one - u2
-            return np.where(au < one, t * t, np.float32(0)).astype(np.float32)
-        if loss == 3:
-            return (one / (one + u2)).astype(np.float32)
-        if loss == 4:
-            t = one + u2
-            return (one / (t * t)).astype(np.float32)
-    return np.ones_like(r)
-
-
-def plane_terms(p, q, nq, pivot, loss=0, scale=1.0, dtype=np.float32):
-    """per-pair terms [n, 38] of the PLANE record and the residuals r = c.  dtype float32: the kernels' rows (fp32, unfused, their
-    association); float64: the same rows in fp64 (an exact-as-possible record for the solve tests)."""
-    f = dtype
-    pv = np.asarray(pivot, f)
-    R = np.asarray(p, np.float32) - np.asarray(q, np.float32)          # (the pair's distance is taken before the pivot comes off)
-    d2 = (R[:, 0] * R[:, 0] + R[:, 1] * R[:, 1]) + R[:, 2] * R[:, 2]
-    P = np.asarray(p, f) - pv
-    Q = np.asarray(q, f) - pv
-    N = np.asarray(nq, f)
-    D = P - Q
-    m0 = P[:, 1] * N[:, 2] - P[:, 2] * N[:, 1]
-    m1 = P[:, 2] * N[:, 0] - P[:, 0] * N[:, 2]
-    m2 = P[:, 0] * N[:, 1] - P[:, 1] * N[:, 0]
-    c = (D[:, 0] * N[:, 0] + D[:, 1] * N[:, 1]) + D[:, 2] * N[:, 2]
-    n = len(P)
-    w = np_weight(loss, scale, c).astype(np.float64) if loss else np.ones(n)
-    V = np.stack([m0, m1, m2, N[:, 0], N[:, 1], N[:, 2]], 1).astype(np.float64)
-    T = np.zeros((n, 38))
-    k = 0
-    for a in range(6):
-        for b in range(a, 6):
-            T[:, k] = w * V[:, a] * V[:, b]
-            k += 1
-    cd = c.astype(np.float64)
-    T[:, 21:27] = V * (w * cd)[:, None]
-    T[:, 27:30] = w[:, None] * P.astype(np.float64)
-    T[:, 30:33] = w[:, None] * Q.astype(np.float64)
-    T[:, 33] = np.sqrt(d2)
-    T[:, 34] = w
-    T[:, 35] = w * cd * cd
-    T[:, 36] = d2
-    T[:, 37] = 1.0 if loss else 0.0
-    return T, c
+from _record_ref import NSUM, np_weight, plane_terms      # noqa: F401  (the terms live with the other modes' terms)
 
 
 def plane_record(p, q, nq, pivot, loss=0, scale=1.0, dtype=np.float32):

@@ -10,9 +10,9 @@ import os
 import numpy as np
 import pytest
 
-pytestmark = pytest.mark.gpu
+from _record_ref import TOL_REC, np_weight, record_terms, xf_rows
 
-TOL_REC = 1e-6
+pytestmark = pytest.mark.gpu
 
 
 @pytest.fixture(scope="module")
@@ -41,84 +41,6 @@ def c4(sym):
         _, _, r = engine_record(e, d, 0, 1.0)
     d["c_median"] = float(np.median(np.abs(r)))
     return d
-
-
-def np_weight(loss, scale, r):
-    r = np.asarray(r, np.float32)
-    one = np.float32(1)
-    with np.errstate(divide="ignore", over="ignore"):
-        u = r / np.float32(scale)
-        au = np.abs(u)
-        u2 = u * u
-        if loss == 1:
-            return np.where(au <= one, one, one / au).astype(np.float32)
-        if loss == 2:
-            t = one - u2
-            return np.where(au < one, t * t, np.float32(0)).astype(np.float32)
-        if loss == 3:
-            return (one / (one + u2)).astype(np.float32)
-        if loss == 4:
-            t = one + u2
-            return (one / (t * t)).astype(np.float32)
-    return np.ones_like(r)
-
-
-def record_terms(p, pn, q, qn, pivot, loss, scale, p2p=False):
-    """per-pair terms [n, 38] of the record (include/symmicp.h, symmicp_sums) and the residuals r, as the kernels form them"""
-    f32 = np.float32
-    pv = np.asarray(pivot, f32)
-    R = np.asarray(p, f32) - np.asarray(q, f32)                       # (the pair's distance is taken before the pivot comes off)
-    d2 = (R[:, 0] * R[:, 0] + R[:, 1] * R[:, 1]) + R[:, 2] * R[:, 2]
-    dist = np.sqrt(d2)
-    P = np.asarray(p, f32) - pv
-    Q = np.asarray(q, f32) - pv
-    D = P - Q
-    n = len(P)
-    T = np.zeros((n, 38))
-    if p2p:
-        r = dist
-        w = np_weight(loss, scale, r).astype(np.float64) if loss else np.ones(n)
-        P64, Q64 = P.astype(np.float64), Q.astype(np.float64)
-        for a in range(3):
-            for b in range(3):
-                T[:, 3 * a + b] = w * P64[:, a] * Q64[:, b]
-        T[:, 27:30] = w[:, None] * P64
-        T[:, 30:33] = w[:, None] * Q64
-    else:
-        N = np.asarray(pn, f32) + np.asarray(qn, f32)
-        S = P + Q
-        m0 = S[:, 1] * N[:, 2] - S[:, 2] * N[:, 1]
-        m1 = S[:, 2] * N[:, 0] - S[:, 0] * N[:, 2]
-        m2 = S[:, 0] * N[:, 1] - S[:, 1] * N[:, 0]
-        c = (D[:, 0] * N[:, 0] + D[:, 1] * N[:, 1]) + D[:, 2] * N[:, 2]
-        r = c
-        w = np_weight(loss, scale, r).astype(np.float64) if loss else np.ones(n)
-        V = np.stack([m0, m1, m2, N[:, 0], N[:, 1], N[:, 2]], 1).astype(np.float64)
-        k = 0
-        for a in range(6):
-            for b in range(a, 6):
-                T[:, k] = w * V[:, a] * V[:, b]
-                k += 1
-        cd = c.astype(np.float64)
-        T[:, 21:27] = V * (w * cd)[:, None]
-        T[:, 27:30] = w[:, None] * P.astype(np.float64)
-        T[:, 30:33] = w[:, None] * Q.astype(np.float64)
-        T[:, 35] = w * cd * cd
-    T[:, 33] = dist
-    T[:, 34] = w
-    T[:, 36] = d2
-    T[:, 37] = 1.0 if loss else 0.0
-    return T, r
-
-
-def xf_rows(X, v, w):
-    """xf_row of device_common.h on every row of v: ((m0 x + m1 y) + m2 z) + m3 w in fp32, unfused"""
-    X = np.asarray(X, np.float32).reshape(4, 4)
-    v = np.asarray(v, np.float32)
-    out = np.empty_like(v)
-    for r in range(3):
-        out[:, r] = ((X[r, 0] * v[:, 0] + X[r, 1] * v[:, 1]) + X[r, 2] * v[:, 2]) + X[r, 3] * np.float32(w)
-    return out
 
 
 def engine_record(e, d, loss, scale, p2p=False, identity=False):
