@@ -188,6 +188,9 @@ struct symmicp_ctx {
     LoopRecord *h_ring = nullptr, *h_ring_dev = nullptr;
     unsigned long long *h_done = nullptr, *h_done_dev = nullptr;
     unsigned long long batch_seq = 0;
+    bool loop_log_on = false;                            // symmicp_set_loop_log (tests): run_batch appends every device-driven pass
+    std::vector<symmicp_loop_log_entry> loop_log;        // ... of the last symmicp_align
+    int loop_log_batches = 0;
     int host_passes_since_bailout = 1000;   // batches resume after two clean host-driven passes
     unsigned long long seq = 0;
     // loop state

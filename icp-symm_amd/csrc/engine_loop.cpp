@@ -263,6 +263,11 @@ static int run_batch(symmicp_ctx *c, int want, float *diffs_before, int *n_done,
     ls.Xapply.nrm_w = lc.nrm_w;
     ls.iters = it0;
     *c->h_loop = ls;
+    symmicp_sums last0{};
+    if (c->loop_log_on) {
+        last0 = c->last;                                                        // the record the solve-only launch solves from
+        c->h_ring[it0 % symmicp_ctx::kRing].solved = 0;                         // (it writes its entry only when it solves)
+    }
     HIP_TRY(c, hipMemcpyAsync(c->d_loop, c->h_loop, sizeof(LoopState), hipMemcpyHostToDevice, c->stream));
     PassArgs a{};
     fill_pass_args(c, a, c->X, /*from_cur=*/incr, /*writeback=*/incr, /*first=*/false);
@@ -405,6 +410,21 @@ static int run_batch(symmicp_ctx *c, int want, float *diffs_before, int *n_done,
         c->st.loop_straggler_passes += n_stage;
     }
     (void)X0;
+    if (c->loop_log_on) {
+        // the batch's passes: it0 (the host's last pass, whose record the solve-only launch solved from) .. it1
+        for (int k = it0; k <= it1; k++) {
+            const LoopRecord &r = c->h_ring[k % symmicp_ctx::kRing];
+            symmicp_loop_log_entry e{};
+            std::memcpy(e.sums, k == it0 ? last0.s : r.sums, sizeof(e.sums));
+            std::memcpy(e.increment, r.increment, sizeof(e.increment));
+            std::memcpy(e.X, r.X, sizeof(e.X));
+            e.rcond = r.rcond; e.iter = k; e.status = r.status; e.solved = r.solved; e.list_len = k == it0 ? 0 : r.list_len;
+            e.reason = hl.reason; e.batch = c->loop_log_batches;
+            if (!e.solved) { std::memset(e.increment, 0, sizeof(e.increment)); std::memset(e.X, 0, sizeof(e.X)); e.rcond = 0.f; e.status = -1; }
+            c->loop_log.push_back(e);
+        }
+        c->loop_log_batches++;
+    }
     c->iters = it1;
     c->last_list_len = tree ? (it1 > it0 ? (long long)c->h_ring[it1 % symmicp_ctx::kRing].list_len : c->last_list_len) : -1;
     *n_done = it1 - it0;
@@ -568,6 +588,8 @@ int symmicp_align(symmicp_ctx *c, const float *guess16, symmicp_result *out)
     std::memset(out, 0, sizeof(*out));
     if (c->external_exchange) { out->status = SYMMICP_ERR_STATE; return fail(c, SYMMICP_ERR_STATE, "symmicp_align is not available with external exchange: drive begin/set_sums/step"); }
     const double t0 = now_s();
+    c->loop_log.clear();
+    c->loop_log_batches = 0;
     symmicp_iter_result it;
     int st = symmicp_begin(c, guess16, &it);
     if (st != SYMMICP_OK) { out->status = st; return st; }
@@ -635,6 +657,109 @@ int symmicp_solve(int mode, const symmicp_sums *sums, const float pivot[3], floa
         return solve_p2p(*sums, pivot, rcond, out16);
     }
     return SYMMICP_ERR_ARG;
+}
+
+// ---- test entry points of the device-driven loop ----
+int symmicp_ctx_solve_probe(symmicp_ctx *c, int mode, int exact_rc, const symmicp_sums *sums, size_t n, const float pivot[3], const float *X_in16,
+                            int32_t *status, float *pbar, float *qbar, float *a, float *t, float *rcond, float *out16, float *X_out16)
+{
+    if (!c) return SYMMICP_ERR_ARG;
+    if (mode != SYMMICP_MODE_QUIRKS && mode != SYMMICP_MODE_PAPER && mode != SYMMICP_MODE_PLANE) return fail(c, SYMMICP_ERR_ARG, "probe: QUIRKS, PAPER or PLANE");
+    if (!sums || n == 0 || n > (1u << 24) || !status || !pbar || !qbar || !a || !t || !rcond || !out16 || (X_in16 && !X_out16))
+        return fail(c, SYMMICP_ERR_ARG, "probe: bad arguments");
+    HIP_TRY(c, hipSetDevice(c->device));
+    // one allocation: records | pivot | X_in | status | pbar qbar a t | rcond | out16 | X_out
+    const size_t b_sums = sizeof(symmicp_sums) * n, b_f3 = sizeof(float) * 3 * n, b_16 = sizeof(float) * 16 * n;
+    const size_t o_piv = b_sums, o_xin = o_piv + 16, o_st = o_xin + b_16, o_pb = o_st + 4 * n, o_qb = o_pb + b_f3, o_a = o_qb + b_f3, o_t = o_a + b_f3,
+                 o_rc = o_t + b_f3, o_out = o_rc + 4 * n, o_xo = o_out + b_16, total = o_xo + b_16;
+    char *d = nullptr;
+    HIP_TRY(c, hipMalloc((void **)&d, total));
+    float piv[4] = {0.f, 0.f, 0.f, 0.f};
+    if (pivot) for (int k = 0; k < 3; k++) piv[k] = pivot[k];
+    int st = SYMMICP_OK;
+    if (hipMemcpy(d, sums, b_sums, hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(d + o_piv, piv, 16, hipMemcpyHostToDevice) != hipSuccess ||
+        (X_in16 && hipMemcpy(d + o_xin, X_in16, b_16, hipMemcpyHostToDevice) != hipSuccess))
+        st = fail(c, SYMMICP_ERR_HIP, "probe: upload");
+    if (st == SYMMICP_OK) {
+        launch_solve_probe(mode, exact_rc, (const symmicp_sums *)d, (int)n, (const float *)(d + o_piv), X_in16 ? (const float *)(d + o_xin) : nullptr,
+                           (int32_t *)(d + o_st), (float *)(d + o_pb), (float *)(d + o_qb), (float *)(d + o_a), (float *)(d + o_t), (float *)(d + o_rc),
+                           (float *)(d + o_out), (float *)(d + o_xo), c->stream);
+        if (hipGetLastError() != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) st = fail(c, SYMMICP_ERR_HIP, "probe: kernel");
+    }
+    if (st == SYMMICP_OK) {
+        const struct { size_t off, bytes; void *dst; } back[] = {{o_st, 4 * n, status}, {o_pb, b_f3, pbar}, {o_qb, b_f3, qbar}, {o_a, b_f3, a}, {o_t, b_f3, t},
+                                                              {o_rc, 4 * n, rcond}, {o_out, b_16, out16}, {o_xo, X_in16 ? b_16 : 0, X_out16}};
+        for (const auto &b : back)
+            if (b.bytes && hipMemcpy(b.dst, d + b.off, b.bytes, hipMemcpyDeviceToHost) != hipSuccess) { st = fail(c, SYMMICP_ERR_HIP, "probe: read back"); break; }
+    }
+    (void)hipFree(d);
+    return st;
+}
+
+int symmicp_ctx_loop_solve(symmicp_ctx *c, const symmicp_sums *sums, const float pivot[3], const float X_in16[16], const int32_t in_i[6], const float in_f[3],
+                           int32_t state_out[4], float X_out16[16], float Xapply_out12[12], float ring_inc16[16], float ring_X16[16], float *ring_rcond,
+                           int32_t ring_i2[2])
+{
+    if (!c) return SYMMICP_ERR_ARG;
+    if (!sums || !X_in16 || !in_i || !in_f || !state_out || !X_out16 || !Xapply_out12 || !ring_inc16 || !ring_X16 || !ring_rcond || !ring_i2)
+        return fail(c, SYMMICP_ERR_ARG, "loop_solve: bad arguments");
+    const int mode = in_i[0];
+    if (mode != SYMMICP_MODE_QUIRKS && mode != SYMMICP_MODE_PAPER && mode != SYMMICP_MODE_PLANE) return fail(c, SYMMICP_ERR_ARG, "loop_solve: QUIRKS, PAPER or PLANE");
+    HIP_TRY(c, hipSetDevice(c->device));
+    LoopConfig lc{};
+    lc.mode = mode; lc.fixed_iters = in_i[1]; lc.max_iters = in_i[2]; lc.incremental = in_i[5] ? 1 : 0; lc.tree = 0;
+    lc.diff_threshold = in_f[0]; lc.eps_rotation = in_f[1]; lc.eps_translation = in_f[2];
+    lc.nrm_w = (mode == SYMMICP_MODE_QUIRKS) ? 1.0f : 0.0f;
+    for (int k = 0; k < 3; k++) lc.pivot[k] = pivot ? pivot[k] : 0.f;
+    LoopState ls{};
+    std::memcpy(ls.X, X_in16, sizeof(ls.X));
+    for (int k = 0; k < 12; k++) ls.Xapply.m[k] = X_in16[k];
+    ls.Xapply.nrm_w = lc.nrm_w;
+    ls.iters = in_i[3];
+    ls.small_step = in_i[4];
+    // device copies: the record (where the solve-only launch reads it), the loop state, a ring of one entry
+    char *d = nullptr;
+    const size_t o_loop = 512, o_ring = o_loop + ((sizeof(LoopState) + 255) & ~(size_t)255), total = o_ring + sizeof(LoopRecord);
+    HIP_TRY(c, hipMalloc((void **)&d, total));
+    int st = SYMMICP_OK;
+    if (hipMemcpy(d, sums, sizeof(symmicp_sums), hipMemcpyHostToDevice) != hipSuccess || hipMemcpy(d + o_loop, &ls, sizeof(ls), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemset(d + o_ring, 0xFF, sizeof(LoopRecord)) != hipSuccess)
+        st = fail(c, SYMMICP_ERR_HIP, "loop_solve: upload");
+    if (st == SYMMICP_OK) {
+        launch_reduce_solve(nullptr, 0, (double *)d, 2, (LoopState *)(d + o_loop), lc, (LoopRecord *)(d + o_ring), 1, nullptr, c->stream);
+        if (hipGetLastError() != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) st = fail(c, SYMMICP_ERR_HIP, "loop_solve: kernel");
+    }
+    LoopState lo{};
+    LoopRecord r{};
+    if (st == SYMMICP_OK && (hipMemcpy(&lo, d + o_loop, sizeof(lo), hipMemcpyDeviceToHost) != hipSuccess ||
+                             hipMemcpy(&r, d + o_ring, sizeof(r), hipMemcpyDeviceToHost) != hipSuccess))
+        st = fail(c, SYMMICP_ERR_HIP, "loop_solve: read back");
+    (void)hipFree(d);
+    if (st != SYMMICP_OK) return st;
+    state_out[0] = lo.stop; state_out[1] = lo.reason; state_out[2] = lo.iters; state_out[3] = lo.small_step;
+    std::memcpy(X_out16, lo.X, sizeof(lo.X));
+    std::memcpy(Xapply_out12, lo.Xapply.m, sizeof(lo.Xapply.m));
+    std::memcpy(ring_inc16, r.increment, sizeof(r.increment));
+    std::memcpy(ring_X16, r.X, sizeof(r.X));
+    std::memcpy(ring_rcond, &r.rcond, sizeof(float));
+    ring_i2[0] = r.status; ring_i2[1] = r.solved;
+    return SYMMICP_OK;
+}
+
+int symmicp_set_loop_log(symmicp_ctx *c, int on)
+{
+    if (!c) return SYMMICP_ERR_ARG;
+    c->loop_log_on = on != 0;
+    if (!c->loop_log_on) { c->loop_log.clear(); c->loop_log.shrink_to_fit(); }
+    return SYMMICP_OK;
+}
+
+int symmicp_get_loop_log(const symmicp_ctx *c, symmicp_loop_log_entry *out, size_t cap, size_t *count)
+{
+    if (!c || !count) return SYMMICP_ERR_ARG;
+    *count = c->loop_log.size();
+    if (out) std::memcpy(out, c->loop_log.data(), sizeof(symmicp_loop_log_entry) * std::min(cap, c->loop_log.size()));
+    return SYMMICP_OK;
 }
 
 }  // extern "C"

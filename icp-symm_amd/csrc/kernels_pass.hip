@@ -1601,8 +1601,9 @@ __global__ __launch_bounds__(256) void k_final_reduce(const double *__restrict__
 //            the separate kernels (LOOP_REDO_PASS, the host takes over)
 //   loop     the reference's test `diff > threshold && iters++ < max_iters` (myicp.cpp:123) on the record's slot 33
 //   solve    estimateTransformSymm (func.cpp:76-102) from the record: the SAME source as the host solve (solve_core.h),
-//            run by one thread, with the pivot-ratio conditioning estimate; anything but a clean solve is handed back to
-//            the host's exact form (LOOP_HOST_SOLVE).  transform = increment * transform (myicp.cpp:138); the next pass
+//            run by one thread, with a guaranteed lower bound of the conditioning (SymSolver::solve, exact_rc = false); anything
+//            but a clean solve -- a status other than OK, or a bound at or below 1e-6, so that the exact ratio is above 1e-6 on
+//            every pass the device takes -- is handed back to the host's exact form (LOOP_HOST_SOLVE).  transform = increment * transform (myicp.cpp:138); the next pass
 //            reads it from the loop state.
 // Every pass leaves a LoopRecord in host-mapped memory (sums, increment, transform); the host reads them after the batch.
 // ---------------------------------------------------------------------------
@@ -1739,6 +1740,37 @@ __global__ __launch_bounds__(512) void k_reduce_solve(const double *__restrict__
         const double tn = sqrt((double)Xi[3] * Xi[3] + (double)Xi[7] * Xi[7] + (double)Xi[11] * Xi[11]);
         if (ang < cfg.eps_rotation && tn < cfg.eps_translation) loop->small_step = 1;
     }
+}
+
+// Test entry (symmicp_ctx_solve_probe): the device's solve_core.h on a batch of records, one thread per record, with either
+// conditioning estimate; then mat4_mul(increment, X_in) as k_reduce_solve composes it.  Off the hot path.
+__global__ __launch_bounds__(64) void k_solve_probe(int mode, int exact_rc, const symmicp_sums *__restrict__ sums, int n, const float *pivot,
+                                                    const float *__restrict__ X_in, int32_t *status, float *pbar, float *qbar, float *a, float *t,
+                                                    float *rcond, float *out16, float *X_out)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const symmicp_sums S = sums[i];
+    float pb[3] = {0.f, 0.f, 0.f}, qb[3] = {0.f, 0.f, 0.f}, av[3] = {0.f, 0.f, 0.f}, tv[3] = {0.f, 0.f, 0.f}, rc = 0.f, Xi[16], Xn[16];
+    for (int k = 0; k < 16; k++) Xi[k] = 0.f;
+    const bool ex = exact_rc != 0;
+    const int st = (mode == SYMMICP_MODE_QUIRKS) ? solve::solve_quirks(S, pb, qb, av, tv, &rc, Xi, ex)
+                 : (mode == SYMMICP_MODE_PLANE)  ? solve::solve_plane(S, pivot, pb, qb, av, tv, &rc, Xi, ex)
+                                                 : solve::solve_paper(S, pivot, pb, qb, av, tv, &rc, Xi, ex);
+    status[i] = st;
+    rcond[i] = rc;
+    for (int k = 0; k < 3; k++) { pbar[3 * i + k] = pb[k]; qbar[3 * i + k] = qb[k]; a[3 * i + k] = av[k]; t[3 * i + k] = tv[k]; }
+    for (int k = 0; k < 16; k++) out16[16 * (size_t)i + k] = Xi[k];
+    if (X_in) {
+        solve::mat4_mul(Xi, X_in + 16 * (size_t)i, Xn);
+        for (int k = 0; k < 16; k++) X_out[16 * (size_t)i + k] = Xn[k];
+    }
+}
+
+void launch_solve_probe(int mode, int exact_rc, const symmicp_sums *sums, int n, const float *pivot, const float *X_in, int32_t *status, float *pbar,
+                        float *qbar, float *a, float *t, float *rcond, float *out16, float *X_out, hipStream_t s)
+{
+    if (n > 0) hipLaunchKernelGGL(k_solve_probe, dim3((n + 63) / 64), dim3(64), 0, s, mode, exact_rc, sums, n, pivot, X_in, status, pbar, qbar, a, t, rcond, out16, X_out);
 }
 
 // last kernel of a batch: copy the loop state where the host can read it and publish the batch's sequence number

@@ -25,6 +25,11 @@ namespace solve {
 
 SYMMICP_HD inline bool finite32(float v) { return (v - v) == 0.0f; }      // false for inf and NaN
 
+// Status thresholds of the lower bound (exact_rc == false): ten times the host's thresholds on its Jacobi ratio (1e-12 for the
+// equilibrated 6 x 6 of PAPER and PLANE, 1e-10 for QUIRKS' 3 x 3).  A bound above them puts the exact ratio there too, and the
+// host's eigenvalues are off by O(u) lambda_max at most (~1e-14 of the ratio): a record the device accepts is one the host accepts.
+constexpr double kDeviceRcPaper = 1e-11, kDeviceRcQuirks = 1e-9;
+
 // Symmetric positive (semi)definite solve: Cholesky with the conditioning read
 // from a Jacobi eigenvalue sweep of the same matrix.  N <= 6.
 template <int N>
@@ -65,9 +70,14 @@ struct SymSolver {
     }
 
     // returns reciprocal condition number (|lambda|min / |lambda|max); x = A^-1 b when it is usable
-    // exact_rc == false (device-driven loop: one GPU thread, where 30 Jacobi sweeps would cost more than a whole pass): the
-    // ratio of the smallest to the largest Cholesky pivot instead, an upper bound of |lambda|min / |lambda|max; the caller
-    // hands anything suspicious back to the host's exact form.
+    // exact_rc == false (device-driven loop: one GPU thread, where 30 Jacobi sweeps would cost more than a whole pass): a
+    // guaranteed LOWER bound of lambda_min / lambda_max instead, so that a threshold on it implies the same threshold on the
+    // exact ratio.  For SPD A = L L^T: lambda_max <= tr(A) and 1 / lambda_min <= tr(A^-1) = ||L^-1||_F^2, so
+    // 1 / (tr(A) ||L^-1||_F^2) lies within a factor N^2 below the exact ratio.  The computed L is the exact factor of A + E with
+    // |E| <= (N+1) u |L| |L^T| (Higham, Thm 10.3), i.e. ||E||_2 <= ~7 u tr(A): 16 DBL_EPSILON (= 32 u) is taken off for that, and
+    // 1 % for the rounding of the triangular inverse (relative N^2 u cond(L), cond(L) = sqrt(cond(A)): 1e-8 at a ratio of 1e-18).
+    // (The ratio of the smallest to the largest pivot, used before, is an UPPER bound: it passed ill-conditioned Kahan-type
+    // systems at 1e-4 whose exact ratio is 1e-16.)
     SYMMICP_HD double solve(const double b[N], double x[N], bool exact_rc = true) const
     {
         double rc = 0.0;
@@ -104,9 +114,23 @@ struct SymSolver {
             return 0.0;
         }
         if (!exact_rc) {
-            double dmin = (double)INFINITY, dmax = 0.0;
-            for (int i = 0; i < N; ++i) { const double d = L[i][i] * L[i][i]; dmin = fmin(dmin, d); dmax = fmax(dmax, d); }
-            rc = dmax > 0.0 ? dmin / dmax : 0.0;
+            // ||L^-1||_F^2 column by column: w = L^-1 e_j by forward substitution with the pivots' reciprocals
+            double tr = 0.0, sw = 0.0;
+            for (int i = 0; i < N; ++i) tr += A[i][i];
+#pragma unroll
+            for (int j = 0; j < N; ++j) {
+                double w[N];
+                w[j] = inv[j];
+                sw += w[j] * w[j];
+                for (int i = j + 1; i < N; ++i) {
+                    double s = 0.0;
+                    for (int k = j; k < i; ++k) s -= L[i][k] * w[k];
+                    w[i] = s * inv[i];
+                    sw += w[i] * w[i];
+                }
+            }
+            rc = 0.99 / (tr * sw) - 16.0 * 0x1p-52;
+            if (!(rc > 0.0)) rc = 0.0;                                  // (also NaN, and inf * 0)
         }
         double y[N];
 #pragma unroll
@@ -246,7 +270,7 @@ SYMMICP_HD inline int solve_quirks(const symmicp_sums &S, float pbar[3], float q
     X.rotate(R);           // :98
     X.translate(qbar);     // :99
     X.store(out16);
-    if (!(rc > 1e-10)) return SYMMICP_ERR_DEGENERATE;
+    if (!(rc > (exact_rc ? 1e-10 : kDeviceRcQuirks))) return SYMMICP_ERR_DEGENERATE;
     for (int k = 0; k < 16; ++k)
         if (!finite32(out16[k])) return SYMMICP_ERR_DEGENERATE;
     return SYMMICP_OK;
@@ -336,7 +360,7 @@ SYMMICP_HD inline int solve_paper(const symmicp_sums &S, const float pivot[3], f
     X.rotate(R);
     X.translate(mp);
     X.store(out16);
-    if (!(rc > 1e-12)) return SYMMICP_ERR_DEGENERATE;
+    if (!(rc > (exact_rc ? 1e-12 : kDeviceRcPaper))) return SYMMICP_ERR_DEGENERATE;
     for (int k = 0; k < 16; ++k)
         if (!finite32(out16[k])) return SYMMICP_ERR_DEGENERATE;
     return SYMMICP_OK;
@@ -373,7 +397,7 @@ SYMMICP_HD inline int solve_plane(const symmicp_sums &S, const float pivot[3], f
     X.rotate(R);
     X.translate(mp);
     X.store(out16);
-    if (!(rc > 1e-12)) return SYMMICP_ERR_DEGENERATE;
+    if (!(rc > (exact_rc ? 1e-12 : kDeviceRcPaper))) return SYMMICP_ERR_DEGENERATE;
     for (int k = 0; k < 16; ++k)
         if (!finite32(out16[k])) return SYMMICP_ERR_DEGENERATE;
     return SYMMICP_OK;

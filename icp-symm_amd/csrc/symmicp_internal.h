@@ -191,6 +191,9 @@ void launch_loop_stragglers(const PassArgs &a, const TargetIndex &ix, const Work
 // mode 0: reduce + check + solve (single GPU); 1: the record is already in out_dev (after the all-reduce); 2: solve only (start of a batch)
 void launch_reduce_solve(const double *partials, int blocks, double *out_dev, int mode, LoopState *loop, LoopConfig cfg, LoopRecord *ring, int ring_len,
                          uint32_t *counters_to_clear, hipStream_t s);
+// test entry: solve_core.h on the device for n records, one thread each (symmicp_ctx_solve_probe); X_in may be null
+void launch_solve_probe(int mode, int exact_rc, const symmicp_sums *sums, int n, const float *pivot, const float *X_in, int32_t *status, float *pbar,
+                        float *qbar, float *a, float *t, float *rcond, float *out16, float *X_out, hipStream_t s);
 void launch_loop_end(const LoopState *loop, LoopState *host_copy, unsigned long long *done_flag, unsigned long long seq, hipStream_t s);
 void launch_publish(const double *sums_dev, double *out_host_mapped, unsigned long long seq, hipStream_t s);
 void launch_nn_brute(const CloudSoA &src, uint32_t n_s, const Affine &X, const float4 *tq, uint32_t n_t,

@@ -59,6 +59,16 @@ class Result(C.Structure):
                 ("transform", C.c_float * 16), ("diffs", C.c_float * 64), ("seconds_total", C.c_double)]
 
 
+class LoopLogEntry(C.Structure):
+    _fields_ = [("sums", C.c_double * NSUM), ("increment", C.c_float * 16), ("X", C.c_float * 16), ("rcond", C.c_float),
+                ("iter", C.c_int32), ("status", C.c_int32), ("solved", C.c_int32), ("list_len", C.c_int32), ("reason", C.c_int32),
+                ("batch", C.c_int32), ("reserved", C.c_int32)]
+
+
+# stop reasons of a device-driven run (symmicp_ctx_loop_solve state_out[1], LoopLogEntry.reason)
+LOOP_RUNNING, LOOP_DONE, LOOP_REDO_PASS, LOOP_HOST_SOLVE, LOOP_SLOW = 0, 1, 2, 3, 4
+
+
 class Stats(C.Structure):
     _fields_ = [("last_pass_ms", C.c_double), ("sum_pass_ms", C.c_double), ("passes", C.c_int64),
                 ("build_ms", C.c_double), ("upload_ms", C.c_double), ("grid_level", C.c_int32),
@@ -80,6 +90,7 @@ EXPORTS = [
     "symmicp_comm_init_rank", "symmicp_set_sums", "symmicp_comm_init_shm", "symmicp_shard_range", "symmicp_get_stats", "symmicp_reset_stats", "symmicp_enable_timing",
     "symmicp_pcd_read", "symmicp_pcd_write", "symmicp_estimate_normals", "symmicp_ctx_estimate_normals", "symmicp_ctx_knn",
     "symmicp_set_robust_loss", "symmicp_get_robust_loss", "symmicp_robust_weight",
+    "symmicp_ctx_solve_probe", "symmicp_ctx_loop_solve", "symmicp_set_loop_log", "symmicp_get_loop_log",
 ]
 
 _lib = None
@@ -150,6 +161,11 @@ def lib():
     L.symmicp_get_robust_loss.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_float)]
     L.symmicp_robust_weight.argtypes = [C.c_int, C.c_float, C.c_float]
     L.symmicp_robust_weight.restype = C.c_float
+    i32p = C.POINTER(C.c_int32)
+    L.symmicp_ctx_solve_probe.argtypes = [vp, C.c_int, C.c_int, C.POINTER(Sums), C.c_size_t, fp, fp, i32p, fp, fp, fp, fp, fp, fp, fp]
+    L.symmicp_ctx_loop_solve.argtypes = [vp, C.POINTER(Sums), fp, fp, i32p, fp, i32p, fp, fp, fp, fp, fp, i32p]
+    L.symmicp_set_loop_log.argtypes = [vp, C.c_int]
+    L.symmicp_get_loop_log.argtypes = [vp, C.POINTER(LoopLogEntry), C.c_size_t, C.POINTER(C.c_size_t)]
     _lib = L
     return L
 
@@ -487,6 +503,62 @@ class Engine:
         d["kernel_launches"] = list(s.kernel_launches)
         d["pass_ms_head"] = list(s.pass_ms_head)
         return d
+
+    # ---- test entry points of the device-driven loop ----
+    def solve_probe(self, mode, sums, exact_rc, pivot=None, X_in=None):
+        """the device's solve_core.h on records sums [n,40] (one thread each) -> dict of status [n], pbar qbar a t [n,3],
+        rcond [n], out16 [n,4,4] and, with X_in [n,4,4], X_out = out16 @ X_in as the device loop composes it (mat4_mul)"""
+        S = np.ascontiguousarray(np.asarray(sums, np.float64).reshape(-1, NSUM))
+        n = S.shape[0]
+        o = dict(status=np.zeros(n, np.int32), pbar=np.zeros((n, 3), np.float32), qbar=np.zeros((n, 3), np.float32),
+                 a=np.zeros((n, 3), np.float32), t=np.zeros((n, 3), np.float32), rcond=np.zeros(n, np.float32),
+                 out16=np.zeros((n, 4, 4), np.float32))
+        pv = None if pivot is None else _fptr(np.ascontiguousarray(pivot, np.float32))
+        xin = xout = None
+        if X_in is not None:
+            X_in = np.ascontiguousarray(np.asarray(X_in, np.float32).reshape(n, 4, 4))
+            o["X_out"] = np.zeros((n, 4, 4), np.float32)
+            xin, xout = _fptr(X_in), _fptr(o["X_out"])
+        self._chk(self._L.symmicp_ctx_solve_probe(self._h, int(mode), int(bool(exact_rc)), S.ctypes.data_as(C.POINTER(Sums)), n, pv, xin,
+                                                  o["status"].ctypes.data_as(C.POINTER(C.c_int32)), _fptr(o["pbar"]), _fptr(o["qbar"]),
+                                                  _fptr(o["a"]), _fptr(o["t"]), _fptr(o["rcond"]), _fptr(o["out16"]), xout))
+        return o
+
+    def loop_solve(self, mode, sums, X_in=None, pivot=None, diff_threshold=1.0, fixed_iters=0, max_iters=10, iters=0, small_step=0,
+                   eps_rotation=0.0, eps_translation=0.0, incremental=0):
+        """one solve-only launch of the device loop's end-of-pass kernel on record `sums` and the given loop state -> dict of stop,
+        reason, iters, small_step, X [4,4], Xapply [3,4] and the ring record it wrote: ring_increment, ring_X [4,4], ring_rcond,
+        ring_status, ring_solved (unwritten: 0xFF bytes, i.e. NaN floats and -1 integers)"""
+        S = Sums()
+        for k, v in enumerate(np.asarray(sums, np.float64).reshape(NSUM)):
+            S.s[k] = v
+        X_in = np.ascontiguousarray(np.eye(4, dtype=np.float32) if X_in is None else np.asarray(X_in, np.float32).reshape(16))
+        pv = None if pivot is None else _fptr(np.ascontiguousarray(pivot, np.float32))
+        ii = np.array([mode, fixed_iters, max_iters, iters, small_step, incremental], np.int32)
+        ff = np.array([diff_threshold, eps_rotation, eps_translation], np.float32)
+        st = np.zeros(4, np.int32); X = np.zeros(16, np.float32); Xa = np.zeros(12, np.float32)
+        ri = np.zeros(16, np.float32); rX = np.zeros(16, np.float32); rrc = np.zeros(1, np.float32); r2 = np.zeros(2, np.int32)
+        i32 = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
+        self._chk(self._L.symmicp_ctx_loop_solve(self._h, C.byref(S), pv, _fptr(X_in), i32(ii), _fptr(ff), i32(st), _fptr(X), _fptr(Xa),
+                                                 _fptr(ri), _fptr(rX), _fptr(rrc), i32(r2)))
+        return dict(stop=int(st[0]), reason=int(st[1]), iters=int(st[2]), small_step=int(st[3]), X=X.reshape(4, 4), Xapply=Xa.reshape(3, 4),
+                    ring_increment=ri.reshape(4, 4), ring_X=rX.reshape(4, 4), ring_rcond=float(rrc[0]), ring_status=int(r2[0]), ring_solved=int(r2[1]))
+
+    def set_loop_log(self, on=True):
+        self._chk(self._L.symmicp_set_loop_log(self._h, int(bool(on))))
+
+    def loop_log(self):
+        """the device-driven passes of the last align (set_loop_log first): a list of dicts, one per pass"""
+        n = C.c_size_t(0)
+        self._chk(self._L.symmicp_get_loop_log(self._h, None, 0, C.byref(n)))
+        buf = (LoopLogEntry * max(1, n.value))()
+        self._chk(self._L.symmicp_get_loop_log(self._h, buf, n.value, C.byref(n)))
+        out = []
+        for e in buf[:n.value]:
+            out.append(dict(sums=np.array(e.sums[:], np.float64), increment=np.array(e.increment[:], np.float32).reshape(4, 4),
+                            X=np.array(e.X[:], np.float32).reshape(4, 4), rcond=e.rcond, iter=e.iter, status=e.status, solved=e.solved,
+                            list_len=e.list_len, reason=e.reason, batch=e.batch))
+        return out
 
 
 class MyICP:

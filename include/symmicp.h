@@ -222,6 +222,41 @@ size_t symmicp_local_source_offset(const symmicp_ctx *ctx);
 int symmicp_solve(int mode, const symmicp_sums *sums, const float pivot[3],
                   float pbar[3], float qbar[3], float a[3], float t[3], float *rcond, float out16[16]);
 
+/* ---- test entry points of the device-driven loop (off the hot path; a test's view of what the device does with a record) ----- */
+/* The device's solve: solve_core.h compiled for gfx950, one thread per record, mode QUIRKS / PAPER / PLANE, with the host's exact
+ * conditioning (exact_rc = 1) or the device loop's lower bound (exact_rc = 0).  Per record i: status[i], pbar / qbar / a / t [i][3],
+ * rcond[i], out16[i][16] (the increment); with X_in16 != NULL also X_out16[i][16] = increment * X_in16[i] (mat4_mul, as the loop
+ * composes).  pivot may be NULL (PAPER / PLANE: zero). */
+int symmicp_ctx_solve_probe(symmicp_ctx *ctx, int mode, int exact_rc, const symmicp_sums *sums, size_t n, const float pivot[3],
+                            const float *X_in16, int32_t *status, float *pbar, float *qbar, float *a, float *t, float *rcond,
+                            float *out16, float *X_out16);
+/* One solve-only run of the device loop's end-of-pass kernel (the first launch of every device-driven batch) on a given record and
+ * loop state.  in_i = {mode, fixed_iters, max_iters, iters, small_step, incremental}, in_f = {diff_threshold, eps_rotation,
+ * eps_translation}, X_in16 the cumulative transform before it.  Read back: state_out = {stop, reason, iters, small_step} (LOOP_*:
+ * 0 running, 1 done, 3 handed back to the host solve), X_out16, Xapply_out12 (what the next pass would apply), and the ring record
+ * the kernel wrote (unwritten fields keep the pattern 0xFF bytes): ring_inc16, ring_X16, ring_rcond, ring_i2 = {status, solved}. */
+int symmicp_ctx_loop_solve(symmicp_ctx *ctx, const symmicp_sums *sums, const float pivot[3], const float X_in16[16], const int32_t in_i[6],
+                           const float in_f[3], int32_t state_out[4], float X_out16[16], float Xapply_out12[12], float ring_inc16[16],
+                           float ring_X16[16], float *ring_rcond, int32_t ring_i2[2]);
+/* One pass of a device-driven run, as symmicp_align's log keeps it: the pass's record, the increment solved from it and the
+ * transform after it (when solved), the batch's stop reason. */
+typedef struct {
+    double sums[SYMMICP_NSUM];
+    float increment[16], X[16];
+    float rcond;
+    int32_t iter;        /* iteration count after this pass (the reference's `iters`) */
+    int32_t status;      /* status of the device solve from this record */
+    int32_t solved;      /* 1: increment / X are valid (the device went on) */
+    int32_t list_len;    /* TREE: work-list length of this pass */
+    int32_t reason;      /* stop reason of the batch this pass belongs to (LOOP_* as above; 4: slow, 2: redo pass) */
+    int32_t batch;       /* 0, 1, ...: batches of this align */
+    int32_t reserved;
+} symmicp_loop_log_entry;
+/* on != 0: every later symmicp_align keeps the log of its device-driven passes (off by default: nothing is copied) */
+int symmicp_set_loop_log(symmicp_ctx *ctx, int on);
+/* the log of the last symmicp_align: *count entries in all, min(cap, *count) of them copied to out (out may be NULL) */
+int symmicp_get_loop_log(const symmicp_ctx *ctx, symmicp_loop_log_entry *out, size_t cap, size_t *count);
+
 /* ---- normals pre-step (replaces MyICP::estimateNormals, myicp.cpp:152-172: PCL NormalEstimation,
  * setKSearch(10), viewpoint (0,0,0)).  Exact k-NN (the point itself included) + PCA on the GPU.
  * xyz strided as in set_source; nrm_out packed AoS [n][3]; curv_out (lambda_min / trace) may be NULL;
