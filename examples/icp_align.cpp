@@ -1,13 +1,15 @@
 // examples/icp_align.cpp -- command-line registration of two PCD files on one MI355X through the MyICP class.
 //
 //   icp_align [options] [source.pcd target.pcd]
-//     --mode quirks|paper|plane  arithmetic: the reference as written (default), the paper-correct symmetric form, or
-//                              point-to-plane (target normals only: the source's are not estimated)
+//     --mode quirks|paper|plane|gicp  arithmetic: the reference as written (default), the paper-correct symmetric form,
+//                              point-to-plane (target normals only: the source's are not estimated), or plane-to-plane
+//                              (Generalized-ICP, covariances from the normals of both clouds)
+//     --gicp-epsilon E         the covariances' eps, 0 < E <= 1 (default 1e-3; --mode gicp only)
 //     --corr identity|tree     pairing: by row (default, what the reference does) or exact nearest neighbours
 //     --iters N                iteration cap            (default 10, ICP/myicp.cpp:6)
 //     --loss none|huber|tukey|cauchy|gm   robust loss of the paper loop (default none; not with --mode quirks)
 //     --loss-scale S           its scale (PAPER: in units of c = (p - q).(n_p + n_q), about twice the point-to-plane distance;
-//                              PLANE: the point-to-plane distance itself)
+//                              PLANE: the point-to-plane distance itself; GICP: the pair's Mahalanobis distance)
 //     --threshold D            stop once the summed pair distance is <= D   (default 1.0, ICP/myicp.cpp:6)
 //     --out aligned.pcd        write the source moved by the result (the reference only prints its result)
 //     --quiet                  no per-iteration lines
@@ -27,8 +29,8 @@
 
 static int usage(const char *argv0, const char *complaint)
 {
-    std::fprintf(stderr, "%s\nusage: %s [--mode quirks|paper|plane] [--corr identity|tree] [--iters N] [--threshold D] [--loss none|huber|tukey|cauchy|gm]"
-                 " [--loss-scale S] [--out file.pcd] [--quiet] [source.pcd target.pcd]\n",
+    std::fprintf(stderr, "%s\nusage: %s [--mode quirks|paper|plane|gicp] [--corr identity|tree] [--iters N] [--threshold D] [--loss none|huber|tukey|cauchy|gm]"
+                 " [--loss-scale S] [--gicp-epsilon E] [--out file.pcd] [--quiet] [source.pcd target.pcd]\n",
                  complaint, argv0);
     return 64;
 }
@@ -42,6 +44,8 @@ int main(int argc, char **argv)
     symmicp_loss loss = SYMMICP_LOSS_NONE;
     float loss_scale = 0.f;
     bool have_scale = false;
+    bool gicp = false, have_eps = false;
+    float gicp_eps = 0.f;
     for (int k = 1; k < argc; k++) {
         const std::string a = argv[k];
         auto value = [&](const char *what) -> const char * {
@@ -50,9 +54,10 @@ int main(int argc, char **argv)
         };
         if (a == "--mode") {
             const std::string v = value("--mode");
-            if (v == "quirks") { icp.setMode(SYMMICP_MODE_QUIRKS); quirks = true; }
-            else if (v == "paper") { icp.setMode(SYMMICP_MODE_PAPER); quirks = false; }
-            else if (v == "plane") { icp.setMode(SYMMICP_MODE_PLANE); quirks = false; }
+            if (v == "quirks") { icp.setMode(SYMMICP_MODE_QUIRKS); quirks = true; gicp = false; }
+            else if (v == "paper") { icp.setMode(SYMMICP_MODE_PAPER); quirks = false; gicp = false; }
+            else if (v == "plane") { icp.setMode(SYMMICP_MODE_PLANE); quirks = false; gicp = false; }
+            else if (v == "gicp") { icp.setMode(SYMMICP_MODE_GICP); quirks = false; gicp = true; }
             else return usage(argv[0], "unknown --mode");
         } else if (a == "--corr") {
             const std::string v = value("--corr");
@@ -75,6 +80,13 @@ int main(int argc, char **argv)
             loss_scale = std::strtof(v, &end);
             if (end == v || *end) return usage(argv[0], "--loss-scale needs a number");
             have_scale = true;
+        } else if (a == "--gicp-epsilon") {
+            char *end = nullptr;
+            const char *v = value("--gicp-epsilon");
+            gicp_eps = std::strtof(v, &end);
+            if (end == v || *end || !std::isfinite(gicp_eps) || !(gicp_eps > 0.f) || gicp_eps > 1.f)
+                return usage(argv[0], "--gicp-epsilon needs a number E with 0 < E <= 1");
+            have_eps = true;
         }
         else if (a == "--out") out_path = value("--out");
         else if (a == "--quiet") icp.setVerbose(false);
@@ -84,9 +96,13 @@ int main(int argc, char **argv)
     if (files.empty()) files = {"cat.pcd", "cat_out.pcd"};
     if (files.size() != 2) return usage(argv[0], "expected two PCD files");
     if (loss != SYMMICP_LOSS_NONE) {
-        if (quirks) return usage(argv[0], "--loss needs --mode paper or plane (quirks is the reference as written)");
+        if (quirks) return usage(argv[0], "--loss needs --mode paper, plane or gicp (quirks is the reference as written)");
         if (!have_scale || !(loss_scale > 0.f) || !std::isfinite(loss_scale)) return usage(argv[0], "--loss needs --loss-scale S with S > 0");
         icp.setRobustLoss(loss, loss_scale);
+    }
+    if (have_eps) {
+        if (!gicp) return usage(argv[0], "--gicp-epsilon needs --mode gicp");
+        icp.setGicpEpsilon(gicp_eps);
     }
 
     icp.LoadCloud(files[0], files[1]);

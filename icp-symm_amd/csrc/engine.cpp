@@ -94,7 +94,8 @@ void symmicp_config_default(symmicp_config *cfg)
 static int check_cfg(const symmicp_config *cfg)
 {
     if (!cfg || cfg->struct_size != (int32_t)sizeof(symmicp_config)) return SYMMICP_ERR_ARG;
-    if (cfg->mode < SYMMICP_MODE_QUIRKS || cfg->mode > SYMMICP_MODE_PLANE) return SYMMICP_ERR_ARG;
+    if (cfg->mode != SYMMICP_MODE_QUIRKS && cfg->mode != SYMMICP_MODE_PAPER && cfg->mode != SYMMICP_MODE_P2P && cfg->mode != SYMMICP_MODE_PLANE &&
+        cfg->mode != SYMMICP_MODE_GICP) return SYMMICP_ERR_ARG;      // (4 is unassigned)
     if (cfg->corr < SYMMICP_CORR_IDENTITY || cfg->corr > SYMMICP_CORR_TREE) return SYMMICP_ERR_ARG;
     if (cfg->apply < SYMMICP_APPLY_DEFAULT || cfg->apply > SYMMICP_APPLY_CUMULATIVE) return SYMMICP_ERR_ARG;
     if (cfg->max_iters < 0) return SYMMICP_ERR_ARG;
@@ -253,6 +254,22 @@ int symmicp_get_robust_loss(const symmicp_ctx *c, int *loss, float *scale)
     if (!c) return SYMMICP_ERR_ARG;
     if (loss) *loss = c->loss;
     if (scale) *scale = c->loss_scale;
+    return SYMMICP_OK;
+}
+
+// ---- GICP's covariances -------------------------------------------------------------------------
+int symmicp_set_gicp_epsilon(symmicp_ctx *c, float eps)
+{
+    if (!c) return SYMMICP_ERR_ARG;
+    if (!(std::isfinite(eps) && eps > 0.f && eps <= 1.f)) return fail(c, SYMMICP_ERR_ARG, "gicp epsilon: 0 < eps <= 1 and finite");
+    c->gicp_eps = eps;
+    return SYMMICP_OK;
+}
+
+int symmicp_get_gicp_epsilon(const symmicp_ctx *c, float *eps)
+{
+    if (!c || !eps) return SYMMICP_ERR_ARG;
+    *eps = c->gicp_eps;
     return SYMMICP_OK;
 }
 

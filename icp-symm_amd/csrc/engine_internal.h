@@ -133,6 +133,7 @@ struct symmicp_ctx {
     symmicp_config cfg{};
     int loss = SYMMICP_LOSS_NONE;    // robust loss (symmicp_set_robust_loss) and its scale: read by every pass
     float loss_scale = 0.f;
+    float gicp_eps = 1e-3f;          // SYMMICP_MODE_GICP's covariance eps (symmicp_set_gicp_epsilon): read by every GICP pass
     int device = 0;
     hipStream_t stream = nullptr;
     std::string err;

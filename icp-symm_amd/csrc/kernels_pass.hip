@@ -200,6 +200,102 @@ __device__ __forceinline__ void acc_plane(AccN<NA> &a, float px, float py, float
     a.v[36] += (double)d2;
 }
 
+// GICP (plane-to-plane, Segal et al. 2009): the pair's cost d^T M d with M = (C_p + C_q)^-1, C_x = I - k x x^T, k = 1 - eps, a = the
+// moved source normal, b = the target normal, d = p - q.  With u = a + b, v = a - b and cs = a . b clamped to [-1, 1] (so both lambdas
+// stay >= 2 eps whatever the normals), in closed form:
+//   M = 1/2 I + gu u u^T + gv v v^T,   gu = k / (4 (2 - k (1 + cs))),   gv = k / (4 (2 - k (1 - cs))).
+// Five rows of PLANE's form v = (p x l, l), c = l . d: u at weight gu, v at gv -- fp32, unfused, as acc_plane forms them -- and the three
+// axes at weight 1/2, summed directly as 1/2 J^T J and 1/2 J^T d (J = [-[p]x, I]) in fp64 from p and d.  Slots 27..32 per pair, as
+// PLANE's; slot 35 sums w d^T M d.  In the weighted record (NA = kNAccW) the pair's weight is that of r = sqrt(d^T M d) in fp32.
+template <int NA>
+__device__ __forceinline__ void acc_gicp(AccN<NA> &a, float px, float py, float pz, float ax, float ay, float az, float qx, float qy, float qz,
+                                         float bx, float by, float bz, float d2, const float *pivot, float gk, int loss, float scale)
+{
+    constexpr bool W = NA == kNAccW;
+    px -= pivot[0]; py -= pivot[1]; pz -= pivot[2];
+    qx -= pivot[0]; qy -= pivot[1]; qz -= pivot[2];
+    const float dx = px - qx, dy = py - qy, dz = pz - qz;
+    const float cs = fminf(fmaxf((ax * bx + ay * by) + az * bz, -1.0f), 1.0f);
+    const float gu = gk / (4.0f * (2.0f - gk * (1.0f + cs)));
+    const float gv = gk / (4.0f * (2.0f - gk * (1.0f - cs)));
+    const float ux = ax + bx, uy = ay + by, uz = az + bz;
+    const float vx = ax - bx, vy = ay - by, vz = az - bz;
+    const float cu = (dx * ux + dy * uy) + dz * uz;
+    const float cv = (dx * vx + dy * vy) + dz * vz;
+    double w = 1.0;
+    if constexpr (W) {
+        const float dd = (dx * dx + dy * dy) + dz * dz;
+        w = (double)robust_weight(loss, scale, sqrtf((0.5f * dd + (gu * cu) * cu) + (gv * cv) * cv));
+    } else {
+        (void)loss; (void)scale;
+    }
+    // the u row, then the v row
+    {
+        const double V[6] = {(double)(py * uz - pz * uy), (double)(pz * ux - px * uz), (double)(px * uy - py * ux), (double)ux, (double)uy, (double)uz};
+        const double wg = w * (double)gu, wc = wg * (double)cu;
+        int k = 0;
+#pragma unroll
+        for (int r = 0; r < 6; r++) {
+            const double wv = wg * V[r];
+#pragma unroll
+            for (int s = r; s < 6; s++) { a.v[k] = __builtin_fma(wv, V[s], a.v[k]); k++; }
+        }
+#pragma unroll
+        for (int r = 0; r < 6; r++) a.v[21 + r] = __builtin_fma(V[r], wc, a.v[21 + r]);
+        a.v[35] = __builtin_fma(wc, (double)cu, a.v[35]);
+    }
+    {
+        const double V[6] = {(double)(py * vz - pz * vy), (double)(pz * vx - px * vz), (double)(px * vy - py * vx), (double)vx, (double)vy, (double)vz};
+        const double wg = w * (double)gv, wc = wg * (double)cv;
+        int k = 0;
+#pragma unroll
+        for (int r = 0; r < 6; r++) {
+            const double wv = wg * V[r];
+#pragma unroll
+            for (int s = r; s < 6; s++) { a.v[k] = __builtin_fma(wv, V[s], a.v[k]); k++; }
+        }
+#pragma unroll
+        for (int r = 0; r < 6; r++) a.v[21 + r] = __builtin_fma(V[r], wc, a.v[21 + r]);
+        a.v[35] = __builtin_fma(wc, (double)cv, a.v[35]);
+    }
+    // the axis rows: 1/2 J^T J = 1/2 [[|p|^2 I - p p^T, [p]x], [[p]x^T, I]] and 1/2 J^T d = 1/2 (p x d, d)
+    const double Px = px, Py = py, Pz = pz, Dx = dx, Dy = dy, Dz = dz;
+    const double hw = 0.5 * w, hx = hw * Px, hy = hw * Py, hz = hw * Pz;
+    a.v[0] = __builtin_fma(hz, Pz, __builtin_fma(hy, Py, a.v[0]));
+    a.v[1] = __builtin_fma(-hx, Py, a.v[1]);
+    a.v[2] = __builtin_fma(-hx, Pz, a.v[2]);
+    a.v[4] -= hz; a.v[5] += hy;
+    a.v[6] = __builtin_fma(hz, Pz, __builtin_fma(hx, Px, a.v[6]));
+    a.v[7] = __builtin_fma(-hy, Pz, a.v[7]);
+    a.v[8] += hz; a.v[10] -= hx;
+    a.v[11] = __builtin_fma(hy, Py, __builtin_fma(hx, Px, a.v[11]));
+    a.v[12] -= hy; a.v[13] += hx;
+    a.v[15] += hw; a.v[18] += hw; a.v[20] += hw;
+    a.v[21] = __builtin_fma(hy, Dz, __builtin_fma(-hz, Dy, a.v[21]));
+    a.v[22] = __builtin_fma(hz, Dx, __builtin_fma(-hx, Dz, a.v[22]));
+    a.v[23] = __builtin_fma(hx, Dy, __builtin_fma(-hy, Dx, a.v[23]));
+    a.v[24] = __builtin_fma(hw, Dx, a.v[24]); a.v[25] = __builtin_fma(hw, Dy, a.v[25]); a.v[26] = __builtin_fma(hw, Dz, a.v[26]);
+    a.v[35] = __builtin_fma(hw, __builtin_fma(Dz, Dz, __builtin_fma(Dy, Dy, Dx * Dx)), a.v[35]);
+    a.v[27] = __builtin_fma(w, Px, a.v[27]); a.v[28] = __builtin_fma(w, Py, a.v[28]); a.v[29] = __builtin_fma(w, Pz, a.v[29]);
+    a.v[30] = __builtin_fma(w, (double)qx, a.v[30]); a.v[31] = __builtin_fma(w, (double)qy, a.v[31]); a.v[32] = __builtin_fma(w, (double)qz, a.v[32]);
+    a.v[33] += (double)sqrtf(d2);
+    a.v[34] += w;
+    a.v[36] += (double)d2;
+    if constexpr (W) a.v[37] += 1.0;
+}
+
+// The record of an accumulating kernel's instantiation (its OBJ parameter): the symmetric rows of PAPER / QUIRKS / P2P (acc_pair), PLANE's
+// (acc_plane) or GICP's (acc_gicp).  Separate instantiations, not a branch, as W: each kernel keeps the registers its own record needs.
+constexpr int kObjSym = 0, kObjPlane = 1, kObjGicp = 2;
+template <int OBJ, int NA>
+__device__ __forceinline__ void acc_obj(AccN<NA> &acc, float px, float py, float pz, float npx, float npy, float npz, float qx, float qy, float qz,
+                                        float nqx, float nqy, float nqz, float d2, const float *pivot, int p2p, float gk, int loss, float scale)
+{
+    if constexpr (OBJ == kObjPlane) acc_plane(acc, px, py, pz, qx, qy, qz, nqx, nqy, nqz, d2, pivot, loss, scale);
+    else if constexpr (OBJ == kObjGicp) acc_gicp(acc, px, py, pz, npx, npy, npz, qx, qy, qz, nqx, nqy, nqz, d2, pivot, gk, loss, scale);
+    else acc_pair(acc, px, py, pz, npx, npy, npz, qx, qy, qz, nqx, nqy, nqz, d2, pivot, p2p, loss, scale);
+}
+
 // one step of a sum on the VALU's DPP cross-lane network (no LDS traffic): row_shr 1,2,4,8 builds 16-lane row sums.  A double moves
 // as two 32-bit DPP movs; lanes without a source read 0 (bound_ctrl), i.e. add +0.0.
 template <int CTRL, int ROW_MASK>
@@ -276,16 +372,15 @@ __device__ __forceinline__ void acc_block_reduce_store(AccN<NA> &a, double *part
 // VEC = 4: each thread handles 4 consecutive points per step with 16-byte loads/stores from the planar
 // arrays (needs n, the target offset and the array lengths to be multiples of 4 so every column stays
 // 16-byte aligned); VEC = 1 is the general form.
-// PL: the PLANE instantiations (acc_plane).  Separate instantiations, not a branch, as W: the other kernels keep their registers.  They read
-// the source normals only to write them back or to gate on them.
-template <int VEC, bool W, bool PL>
+// OBJ: the record (acc_obj).  The PLANE instantiations read the source normals only to write them back or to gate on them.
+template <int VEC, bool W, int OBJ>
 __global__ __launch_bounds__(kPassThreads) void k_pass_identity(PassArgs a_in, CloudSoA tgt)
 {
     if (a_in.loop && a_in.loop->stop) return;
     PassArgs a = a_in;
     if (a_in.loop) a.X = a_in.loop->Xapply;        // device-driven loop: the transform k_reduce_solve left behind
     AccT<W> acc; acc_zero(acc);
-    const bool need_n = !PL || a.writeback || a.min_ndot > -1.0f;
+    const bool need_n = OBJ != kObjPlane || a.writeback || a.min_ndot > -1.0f;
     const uint32_t stride = gridDim.x * blockDim.x * VEC;
     for (uint32_t i0 = (blockIdx.x * blockDim.x + threadIdx.x) * VEC; i0 < a.n; i0 += stride) {
         float x[VEC], y[VEC], z[VEC], nx[VEC], ny[VEC], nz[VEC], qx[VEC], qy[VEC], qz[VEC], qnx[VEC], qny[VEC], qnz[VEC];
@@ -345,8 +440,7 @@ __global__ __launch_bounds__(kPassThreads) void k_pass_identity(PassArgs a_in, C
         for (int k = 0; k < VEC; k++) {
             if (a.max_d2 > 0.0f && d2[k] > a.max_d2) continue;
             if (a.min_ndot > -1.0f && (npx[k] * qnx[k] + npy[k] * qny[k]) + npz[k] * qnz[k] < a.min_ndot) continue;
-            if (PL) acc_plane(acc, px[k], py[k], pz[k], qx[k], qy[k], qz[k], qnx[k], qny[k], qnz[k], d2[k], a.pivot, a.loss, a.loss_scale);
-            else acc_pair(acc, px[k], py[k], pz[k], npx[k], npy[k], npz[k], qx[k], qy[k], qz[k], qnx[k], qny[k], qnz[k], d2[k], a.pivot, a.p2p, a.loss, a.loss_scale);
+            acc_obj<OBJ>(acc, px[k], py[k], pz[k], npx[k], npy[k], npz[k], qx[k], qy[k], qz[k], qnx[k], qny[k], qnz[k], d2[k], a.pivot, a.p2p, a.gicp_k, a.loss, a.loss_scale);
         }
     }
     acc_block_reduce_store(acc, a.partials, gridDim.x);
@@ -356,11 +450,11 @@ __global__ __launch_bounds__(kPassThreads) void k_pass_identity(PassArgs a_in, C
 // pass, pairs given by a previous search kernel (brute force): best64[i] holds
 // (d2 bits << 32 | target row).  Target rows are gathered as float4.
 // ---------------------------------------------------------------------------
-template <bool W, bool PL>
+template <bool W, int OBJ>
 __global__ __launch_bounds__(kPassThreads) void k_pass_indexed(PassArgs a, const float4 *__restrict__ tn)
 {
     AccT<W> acc; acc_zero(acc);
-    const bool need_n = !PL || a.writeback || a.min_ndot > -1.0f;
+    const bool need_n = OBJ != kObjPlane || a.writeback || a.min_ndot > -1.0f;
     const uint32_t stride = gridDim.x * blockDim.x;
     for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < a.n; i += stride) {
         float x = a.in.x[i], y = a.in.y[i], z = a.in.z[i];
@@ -383,8 +477,7 @@ __global__ __launch_bounds__(kPassThreads) void k_pass_indexed(PassArgs a, const
         if (a.max_d2 > 0.0f && d2 > a.max_d2) continue;
         const float4 q = tn[2 * (size_t)j], nq = tn[2 * (size_t)j + 1];     // one 32-byte pair record
         if (a.min_ndot > -1.0f && (npx * nq.x + npy * nq.y) + npz * nq.z < a.min_ndot) continue;
-        if (PL) acc_plane(acc, px, py, pz, q.x, q.y, q.z, nq.x, nq.y, nq.z, d2, a.pivot, a.loss, a.loss_scale);
-        else acc_pair(acc, px, py, pz, npx, npy, npz, q.x, q.y, q.z, nq.x, nq.y, nq.z, d2, a.pivot, a.p2p, a.loss, a.loss_scale);
+        acc_obj<OBJ>(acc, px, py, pz, npx, npy, npz, q.x, q.y, q.z, nq.x, nq.y, nq.z, d2, a.pivot, a.p2p, a.gicp_k, a.loss, a.loss_scale);
     }
     acc_block_reduce_store(acc, a.partials, gridDim.x);
 }
@@ -984,14 +1077,15 @@ struct HotParams {
     int32_t p2p;
     int32_t loss;            // (set and read by the weighted instantiation only)
     float loss_scale;
+    float gicp_k;            // (set and read by the GICP instantiation only)
 };
 
-template <bool PL, int NA>
+template <int OBJ, int NA>
 __device__ __forceinline__ void fused_accumulate(AccN<NA> &acc, const HotParams &h, float nx, float ny, float nz, float px, float py, float pz,
                                                  const float4 &q, const float4 &nq, float d2)
 {
     const Affine &X = h.X;
-    if (PL) {      // (the source normal only for the gate: the rows do not use it)
+    if (OBJ == kObjPlane) {      // (the source normal only for the gate: the rows do not use it)
         if (h.max_d2 > 0.0f && d2 > h.max_d2) return;
         if (h.min_ndot > -1.0f) {
             const float npx = xf_row(X.m + 0, nx, ny, nz, X.nrm_w), npy = xf_row(X.m + 4, nx, ny, nz, X.nrm_w), npz = xf_row(X.m + 8, nx, ny, nz, X.nrm_w);
@@ -1003,7 +1097,7 @@ __device__ __forceinline__ void fused_accumulate(AccN<NA> &acc, const HotParams 
     const float npx = xf_row(X.m + 0, nx, ny, nz, X.nrm_w), npy = xf_row(X.m + 4, nx, ny, nz, X.nrm_w), npz = xf_row(X.m + 8, nx, ny, nz, X.nrm_w);
     if (h.max_d2 > 0.0f && d2 > h.max_d2) return;
     if (h.min_ndot > -1.0f && (npx * nq.x + npy * nq.y) + npz * nq.z < h.min_ndot) return;
-    acc_pair(acc, px, py, pz, npx, npy, npz, q.x, q.y, q.z, nq.x, nq.y, nq.z, d2, h.pivot, h.p2p, h.loss, h.loss_scale);
+    acc_obj<OBJ>(acc, px, py, pz, npx, npy, npz, q.x, q.y, q.z, nq.x, nq.y, nq.z, d2, h.pivot, h.p2p, h.gicp_k, h.loss, h.loss_scale);
 }
 
 #ifndef FUSED_WAVES
@@ -1019,13 +1113,14 @@ __device__ __forceinline__ void fused_accumulate(AccN<NA> &acc, const HotParams 
 // that is still settling: the separate k_search_cells lets every block of 256 queries pay the latency of the whole scan machinery
 // for the dozen of them that need it; here a block streams several tiles and scans the failures 256 at a time (the walk and
 // k_accumulate follow as usual).  No normals, no record copies read, no sums: registers for 5 waves per SIMD.
-// W (with ACC): the weighted record of a robust loss.  PL (with ACC): the PLANE record, source normals read only for min_normal_dot.
-template <bool ACC, bool W, bool PL>
+// W (with ACC): the weighted record of a robust loss.  OBJ (with ACC): the record (acc_obj); PLANE's reads source normals only for
+// min_normal_dot.
+template <bool ACC, bool W, int OBJ>
 __global__ __launch_bounds__(kPassThreads, ACC ? FUSED_WAVES : COMPACT_WAVES) void k_pass_fused(PassArgs a, TargetIndex ix, WorkLists wl)
 {
     static_assert(ACC || !W, "the search-only form has no sums to weight");
-    static_assert(ACC || !PL, "the search-only form has no rows");
-    const bool need_n = !PL || a.min_ndot > -1.0f;      // (no write-back here)
+    static_assert(ACC || OBJ == kObjSym, "the search-only form has no rows");
+    const bool need_n = OBJ != kObjPlane || a.min_ndot > -1.0f;      // (no write-back here)
     constexpr int kList = ACC ? kFusedList : kFusedList / 2;      // (the search-only form keeps 5 workgroups per CU: its tile is 256 points)
     __shared__ uint32_t s_list[kList];
     __shared__ uint32_t s_cnt, s_total;
@@ -1068,6 +1163,7 @@ __global__ __launch_bounds__(kPassThreads, ACC ? FUSED_WAVES : COMPACT_WAVES) vo
     h.max_d2 = ACC ? in_vgpr(a.max_d2) : a.max_d2; h.min_ndot = ACC ? in_vgpr(a.min_ndot) : a.min_ndot;
     h.p2p = a.p2p;
     if (W) { h.loss = a.loss; h.loss_scale = in_vgpr(a.loss_scale); }
+    if (OBJ == kObjGicp) h.gicp_k = in_vgpr(a.gicp_k);
 #ifdef RS_STAMPS2
     const unsigned long long fs0 = __builtin_amdgcn_s_memrealtime();
     unsigned long long fs1 = 0;
@@ -1100,7 +1196,7 @@ __global__ __launch_bounds__(kPassThreads, ACC ? FUSED_WAVES : COMPACT_WAVES) vo
                     if (pw != pk) { qw = ix.tn[2 * (size_t)pw]; nqw = ix.tn[2 * (size_t)pw + 1]; }
                     float nx = 0.0f, ny = 0.0f, nz = 0.0f;
                     if (need_n) { nx = a.in.nx[i]; ny = a.in.ny[i]; nz = a.in.nz[i]; }
-                    fused_accumulate<PL>(acc, h, nx, ny, nz, px, py, pz, qw, nqw, d2w);
+                    fused_accumulate<OBJ>(acc, h, nx, ny, nz, px, py, pz, qw, nqw, d2w);
                     s_list[e] = 0xFFFFFFFFu;                       // settled (an idle lane of the scan below)
                 }
             }
@@ -1123,7 +1219,7 @@ __global__ __launch_bounds__(kPassThreads, ACC ? FUSED_WAVES : COMPACT_WAVES) vo
                 float nx = 0.0f, ny = 0.0f, nz = 0.0f;
                 if (need_n) { nx = a.in.nx[i]; ny = a.in.ny[i]; nz = a.in.nz[i]; }
                 const float px = xf_row(X.m + 0, x, y, z, 1.0f), py = xf_row(X.m + 4, x, y, z, 1.0f), pz = xf_row(X.m + 8, x, y, z, 1.0f);
-                fused_accumulate<PL>(acc, h, nx, ny, nz, px, py, pz, q, nq, dist2(px, py, pz, q.x, q.y, q.z));
+                fused_accumulate<OBJ>(acc, h, nx, ny, nz, px, py, pz, q, nq, dist2(px, py, pz, q.x, q.y, q.z));
             }
         }
         __syncthreads();
@@ -1201,7 +1297,7 @@ __global__ __launch_bounds__(kPassThreads, ACC ? FUSED_WAVES : COMPACT_WAVES) vo
                 }
                 if (certified) {
                     // (the refreshed distance is not stored: 4 of the pass's 76 bytes per point; symmicp_get_correspondences evaluates it)
-                    if (ACC) fused_accumulate<PL>(acc, h, nx[k], ny[k], nz[k], px, py, pz, q[k], nq[k], d2);
+                    if (ACC) fused_accumulate<OBJ>(acc, h, nx[k], ny[k], nz[k], px, py, pz, q[k], nq[k], d2);
                 } else {
                     s_list[atomicAdd(&s_cnt, 1u)] = i;                 // (room for a whole tile: see the flush below)
                 }
@@ -1431,11 +1527,11 @@ __global__ __launch_bounds__(kWalkThreads, 6) void k_search_walk(PassArgs a, Tar
 // The pair's distance is recomputed from the gathered q (bit-identical to the stored one) instead of being read.
 // (A 4-points-per-thread variant with 16-byte column loads was measured and is no faster: the two 16-byte gathers per
 // pair bound this kernel, not the column loads.  Few blocks are: each one ends in a 40-value block reduction.)
-template <bool W, bool PL>
+template <bool W, int OBJ>
 __global__ __launch_bounds__(kPassThreads) void k_accumulate(PassArgs a, const float4 *__restrict__ tn)
 {
     AccT<W> acc; acc_zero(acc);
-    const bool need_n = !PL || a.writeback || a.min_ndot > -1.0f;
+    const bool need_n = OBJ != kObjPlane || a.writeback || a.min_ndot > -1.0f;
     const uint32_t nbp = gridDim.x;
     // grid-stride over blocks of 256 points, XCD-contiguous
     const uint32_t total_blocks = (a.n + kPassThreads - 1) / kPassThreads;
@@ -1464,8 +1560,7 @@ __global__ __launch_bounds__(kPassThreads) void k_accumulate(PassArgs a, const f
         const float d2 = dist2(px, py, pz, q.x, q.y, q.z);
         if (a.max_d2 > 0.0f && d2 > a.max_d2) continue;
         if (a.min_ndot > -1.0f && (npx * nq.x + npy * nq.y) + npz * nq.z < a.min_ndot) continue;
-        if (PL) acc_plane(acc, px, py, pz, q.x, q.y, q.z, nq.x, nq.y, nq.z, d2, a.pivot, a.loss, a.loss_scale);
-        else acc_pair(acc, px, py, pz, npx, npy, npz, q.x, q.y, q.z, nq.x, nq.y, nq.z, d2, a.pivot, a.p2p, a.loss, a.loss_scale);
+        acc_obj<OBJ>(acc, px, py, pz, npx, npy, npz, q.x, q.y, q.z, nq.x, nq.y, nq.z, d2, a.pivot, a.p2p, a.gicp_k, a.loss, a.loss_scale);
     }
     acc_block_reduce_store(acc, a.partials, gridDim.x);
 }
@@ -1478,7 +1573,7 @@ __global__ __launch_bounds__(kPassThreads) void k_accumulate(PassArgs a, const f
 // Straggler stage of a device-driven loop (after k_pass_fused and k_search_walk): the pairs of the work list's queries -- the fused pass
 // left them out and marked their record copies stale -- are gathered, their copies refreshed, their rows summed into `gridDim.x` partial
 // columns behind the fused pass's.  Launched whether or not the list is empty (the columns must be written).
-template <bool W, bool PL>
+template <bool W, int OBJ>
 __global__ __launch_bounds__(kPassThreads) void k_accumulate_list(PassArgs a, const float4 *__restrict__ tn, ShardList list)
 {
     if (a.loop) {
@@ -1486,7 +1581,7 @@ __global__ __launch_bounds__(kPassThreads) void k_accumulate_list(PassArgs a, co
         a.X = a.loop->Xapply;
     }
     AccT<W> acc; acc_zero(acc);
-    const bool need_n = !PL || a.min_ndot > -1.0f;      // (no write-back here)
+    const bool need_n = OBJ != kObjPlane || a.min_ndot > -1.0f;      // (no write-back here)
     // block b: shards b, b + gridDim.x, ...; its waves take them in turn (a list is a handful of entries: what counts is that the
     // counters and entries of all shards are requested side by side, not one shard after the other)
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -1508,8 +1603,7 @@ __global__ __launch_bounds__(kPassThreads) void k_accumulate_list(PassArgs a, co
             const float d2 = dist2(px, py, pz, q.x, q.y, q.z);
             if (a.max_d2 > 0.0f && d2 > a.max_d2) continue;
             if (a.min_ndot > -1.0f && (npx * nq.x + npy * nq.y) + npz * nq.z < a.min_ndot) continue;
-            if (PL) acc_plane(acc, px, py, pz, q.x, q.y, q.z, nq.x, nq.y, nq.z, d2, a.pivot, a.loss, a.loss_scale);
-            else acc_pair(acc, px, py, pz, npx, npy, npz, q.x, q.y, q.z, nq.x, nq.y, nq.z, d2, a.pivot, a.p2p, a.loss, a.loss_scale);
+            acc_obj<OBJ>(acc, px, py, pz, npx, npy, npz, q.x, q.y, q.z, nq.x, nq.y, nq.z, d2, a.pivot, a.p2p, a.gicp_k, a.loss, a.loss_scale);
         }
     }
     acc_block_reduce_store(acc, a.partials, a.partial_cols, a.partial_col0 + blockIdx.x);
@@ -1713,7 +1807,7 @@ __global__ __launch_bounds__(512) void k_reduce_solve(const double *__restrict__
     for (int k = 0; k < kNSum; k++) S.s[k] = (k >= kNAccW) ? 0.0 : s_sum[k];
     float pbar[3], qbar[3], av[3], tv[3], rc = 0.f, Xi[16];
     const int st = (cfg.mode == SYMMICP_MODE_QUIRKS) ? solve::solve_quirks(S, pbar, qbar, av, tv, &rc, Xi, false)
-                 : (cfg.mode == SYMMICP_MODE_PLANE)  ? solve::solve_plane(S, cfg.pivot, pbar, qbar, av, tv, &rc, Xi, false)
+                 : (cfg.mode == SYMMICP_MODE_PLANE || cfg.mode == SYMMICP_MODE_GICP) ? solve::solve_plane(S, cfg.pivot, pbar, qbar, av, tv, &rc, Xi, false)
                                                       : solve::solve_paper(S, cfg.pivot, pbar, qbar, av, tv, &rc, Xi, false);
     if (st != SYMMICP_OK || !(rc > 1e-6f)) { loop->stop = 1; loop->reason = LOOP_HOST_SOLVE; return; }
 #ifdef RS_STAMPS
@@ -1755,7 +1849,7 @@ __global__ __launch_bounds__(64) void k_solve_probe(int mode, int exact_rc, cons
     for (int k = 0; k < 16; k++) Xi[k] = 0.f;
     const bool ex = exact_rc != 0;
     const int st = (mode == SYMMICP_MODE_QUIRKS) ? solve::solve_quirks(S, pb, qb, av, tv, &rc, Xi, ex)
-                 : (mode == SYMMICP_MODE_PLANE)  ? solve::solve_plane(S, pivot, pb, qb, av, tv, &rc, Xi, ex)
+                 : (mode == SYMMICP_MODE_PLANE || mode == SYMMICP_MODE_GICP) ? solve::solve_plane(S, pivot, pb, qb, av, tv, &rc, Xi, ex)
                                                  : solve::solve_paper(S, pivot, pb, qb, av, tv, &rc, Xi, ex);
     status[i] = st;
     rcond[i] = rc;
@@ -1895,25 +1989,31 @@ void launch_identity_d2(const CloudSoA &in, const Affine &X, const CloudSoA &tgt
 // ---------------------------------------------------------------------------
 // launchers
 // ---------------------------------------------------------------------------
-// the instantiation of an accumulating kernel for the pass's record: weighted (robust loss) or not, PLANE or not
+// the instantiation of an accumulating kernel for the pass's record: weighted (robust loss) or not; symmetric, PLANE or GICP
 template <typename K>
-static K pick(const PassArgs &a, K plain, K weighted, K plane, K plane_weighted)
+static K pick(const PassArgs &a, K plain, K weighted, K plane, K plane_weighted, K gicp, K gicp_weighted)
 {
     const bool w = a.loss != SYMMICP_LOSS_NONE;
-    return a.plane ? (w ? plane_weighted : plane) : (w ? weighted : plain);
+    return a.gicp ? (w ? gicp_weighted : gicp) : a.plane ? (w ? plane_weighted : plane) : (w ? weighted : plain);
 }
 
 void launch_pass_identity(const PassArgs &a, CloudSoA tgt, int blocks, bool vec4_ok, hipStream_t s)
 {
-    if (vec4_ok) hipLaunchKernelGGL(pick(a, k_pass_identity<4, false, false>, k_pass_identity<4, true, false>, k_pass_identity<4, false, true>, k_pass_identity<4, true, true>),
+    if (vec4_ok) hipLaunchKernelGGL(pick(a, k_pass_identity<4, false, kObjSym>, k_pass_identity<4, true, kObjSym>,
+                                            k_pass_identity<4, false, kObjPlane>, k_pass_identity<4, true, kObjPlane>,
+                                            k_pass_identity<4, false, kObjGicp>, k_pass_identity<4, true, kObjGicp>),
                                     dim3(blocks), dim3(kPassThreads), 0, s, a, tgt);
-    else hipLaunchKernelGGL(pick(a, k_pass_identity<1, false, false>, k_pass_identity<1, true, false>, k_pass_identity<1, false, true>, k_pass_identity<1, true, true>),
+    else hipLaunchKernelGGL(pick(a, k_pass_identity<1, false, kObjSym>, k_pass_identity<1, true, kObjSym>,
+                                    k_pass_identity<1, false, kObjPlane>, k_pass_identity<1, true, kObjPlane>,
+                                    k_pass_identity<1, false, kObjGicp>, k_pass_identity<1, true, kObjGicp>),
                             dim3(blocks), dim3(kPassThreads), 0, s, a, tgt);
 }
 
 void launch_pass_indexed(const PassArgs &a, const float4 *tn, int blocks, hipStream_t s)
 {
-    hipLaunchKernelGGL(pick(a, k_pass_indexed<false, false>, k_pass_indexed<true, false>, k_pass_indexed<false, true>, k_pass_indexed<true, true>),
+    hipLaunchKernelGGL(pick(a, k_pass_indexed<false, kObjSym>, k_pass_indexed<true, kObjSym>,
+                               k_pass_indexed<false, kObjPlane>, k_pass_indexed<true, kObjPlane>,
+                               k_pass_indexed<false, kObjGicp>, k_pass_indexed<true, kObjGicp>),
                        dim3(blocks), dim3(kPassThreads), 0, s, a, tn);
 }
 
@@ -1944,7 +2044,7 @@ void launch_pass_tree_split(const PassArgs &a_in, const TargetIndex &ix, const W
     const uint32_t nbp = ((nb + 7u) / 8u) * 8u;
     if (ev) hipEventRecord(ev[0], s);
     if (stage != 2 && nbp) {      // (nbp == 0: a rank whose share is empty)
-        if (compact_blocks > 0) hipLaunchKernelGGL((k_pass_fused<false, false, false>), dim3(min((uint32_t)compact_blocks, nbp)), dim3(kPassThreads), 0, s, a, ix, wl);
+        if (compact_blocks > 0) hipLaunchKernelGGL((k_pass_fused<false, false, kObjSym>), dim3(min((uint32_t)compact_blocks, nbp)), dim3(kPassThreads), 0, s, a, ix, wl);
         else {
             const uint32_t chunk = tune.cells_chunk ? tune.cells_chunk : 16u;      // tiles per chunk
             // queries per tile: 256 while that fills the chip a few times over (256 CUs x 6-7 workgroups), else 128 or 64 (k_search_cells)
@@ -1974,14 +2074,18 @@ void launch_pass_tree_split(const PassArgs &a_in, const TargetIndex &ix, const W
         }
     }
     if (ev) hipEventRecord(ev[3], s);
-    hipLaunchKernelGGL(pick(a, k_accumulate<false, false>, k_accumulate<true, false>, k_accumulate<false, true>, k_accumulate<true, true>),
+    hipLaunchKernelGGL(pick(a, k_accumulate<false, kObjSym>, k_accumulate<true, kObjSym>,
+                               k_accumulate<false, kObjPlane>, k_accumulate<true, kObjPlane>,
+                               k_accumulate<false, kObjGicp>, k_accumulate<true, kObjGicp>),
                        dim3(acc_blocks), dim3(kPassThreads), 0, s, a, ix.tn);
     if (ev) hipEventRecord(ev[4], s);
 }
 
 void launch_accumulate(const PassArgs &a, const float4 *tn, int blocks, hipStream_t s)
 {
-    hipLaunchKernelGGL(pick(a, k_accumulate<false, false>, k_accumulate<true, false>, k_accumulate<false, true>, k_accumulate<true, true>),
+    hipLaunchKernelGGL(pick(a, k_accumulate<false, kObjSym>, k_accumulate<true, kObjSym>,
+                               k_accumulate<false, kObjPlane>, k_accumulate<true, kObjPlane>,
+                               k_accumulate<false, kObjGicp>, k_accumulate<true, kObjGicp>),
                        dim3(blocks), dim3(kPassThreads), 0, s, a, tn);
 }
 
@@ -1994,7 +2098,9 @@ void launch_final_reduce(const double *partials, int blocks, double *out_dev, do
 
 void launch_pass_fused(const PassArgs &a, const TargetIndex &ix, const WorkLists &wl, int blocks, hipStream_t s)
 {
-    hipLaunchKernelGGL(pick(a, k_pass_fused<true, false, false>, k_pass_fused<true, true, false>, k_pass_fused<true, false, true>, k_pass_fused<true, true, true>),
+    hipLaunchKernelGGL(pick(a, k_pass_fused<true, false, kObjSym>, k_pass_fused<true, true, kObjSym>,
+                               k_pass_fused<true, false, kObjPlane>, k_pass_fused<true, true, kObjPlane>,
+                               k_pass_fused<true, false, kObjGicp>, k_pass_fused<true, true, kObjGicp>),
                        dim3(blocks), dim3(kPassThreads), 0, s, a, ix, wl);
 }
 
@@ -2003,7 +2109,9 @@ void launch_loop_stragglers(const PassArgs &a, const TargetIndex &ix, const Work
     // (short lists: the wave-per-entry regime; anything above the threshold strides one thread per entry over this grid)
     const uint32_t wave_mode_max = tune.wave_mode_max;
     hipLaunchKernelGGL(k_search_walk<false>, dim3(512), dim3(kWalkThreads), 0, s, a, ix, wl, wl.work, wave_mode_max, 0xFFFFFFFFu);
-    hipLaunchKernelGGL(pick(a, k_accumulate_list<false, false>, k_accumulate_list<true, false>, k_accumulate_list<false, true>, k_accumulate_list<true, true>),
+    hipLaunchKernelGGL(pick(a, k_accumulate_list<false, kObjSym>, k_accumulate_list<true, kObjSym>,
+                               k_accumulate_list<false, kObjPlane>, k_accumulate_list<true, kObjPlane>,
+                               k_accumulate_list<false, kObjGicp>, k_accumulate_list<true, kObjGicp>),
                        dim3(list_blocks), dim3(kPassThreads), 0, s, a, ix.tn, wl.work);
 }
 

@@ -159,6 +159,8 @@ struct PassArgs {
     int32_t loss;                       // robust loss (SYMMICP_LOSS_*): != NONE selects the weighted instantiation of every accumulating kernel
     float loss_scale;                   // ... its scale (robust_loss.h)
     int32_t plane;                      // SYMMICP_MODE_PLANE: the launchers pick the PLANE instantiations (acc_plane); read by the host only
+    int32_t gicp;                       // SYMMICP_MODE_GICP: the launchers pick the GICP instantiations (acc_gicp); read by the host only
+    float gicp_k;                       // ... 1 - eps of its covariances (symmicp_set_gicp_epsilon), fp32: read by the GICP instantiations only
 };
 
 // host-side launch tuning of the tree passes (environment switches, read once by the engine)

@@ -20,7 +20,7 @@ LIB_PATH = os.environ.get("SYMMICP_LIB") or os.path.join(_ROOT, "lib", "libsymmi
 NSUM = 40
 UNIQUE_ID_BYTES = 128
 OK, ERR_ARG, ERR_SIZE, ERR_DEGENERATE, ERR_IO, ERR_HIP, ERR_STATE, ERR_COMM = range(8)
-MODE_QUIRKS, MODE_PAPER, MODE_P2P, MODE_PLANE = 0, 1, 2, 3
+MODE_QUIRKS, MODE_PAPER, MODE_P2P, MODE_PLANE, MODE_GICP = 0, 1, 2, 3, 5      # (4 is unassigned)
 CORR_IDENTITY, CORR_BRUTE, CORR_TREE = 0, 1, 2
 APPLY_DEFAULT, APPLY_INCREMENTAL, APPLY_CUMULATIVE = 0, 1, 2
 LOSS_NONE, LOSS_HUBER, LOSS_TUKEY, LOSS_CAUCHY, LOSS_GEMAN_MCCLURE = range(5)
@@ -89,7 +89,7 @@ EXPORTS = [
     "symmicp_local_source_count", "symmicp_local_source_offset", "symmicp_get_certificates", "symmicp_solve", "symmicp_comm_get_unique_id",
     "symmicp_comm_init_rank", "symmicp_set_sums", "symmicp_comm_init_shm", "symmicp_shard_range", "symmicp_get_stats", "symmicp_reset_stats", "symmicp_enable_timing",
     "symmicp_pcd_read", "symmicp_pcd_write", "symmicp_estimate_normals", "symmicp_ctx_estimate_normals", "symmicp_ctx_knn",
-    "symmicp_set_robust_loss", "symmicp_get_robust_loss", "symmicp_robust_weight",
+    "symmicp_set_robust_loss", "symmicp_get_robust_loss", "symmicp_robust_weight", "symmicp_set_gicp_epsilon", "symmicp_get_gicp_epsilon",
     "symmicp_ctx_solve_probe", "symmicp_ctx_loop_solve", "symmicp_set_loop_log", "symmicp_get_loop_log",
 ]
 
@@ -161,6 +161,8 @@ def lib():
     L.symmicp_get_robust_loss.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_float)]
     L.symmicp_robust_weight.argtypes = [C.c_int, C.c_float, C.c_float]
     L.symmicp_robust_weight.restype = C.c_float
+    L.symmicp_set_gicp_epsilon.argtypes = [vp, C.c_float]
+    L.symmicp_get_gicp_epsilon.argtypes = [vp, C.POINTER(C.c_float)]
     i32p = C.POINTER(C.c_int32)
     L.symmicp_ctx_solve_probe.argtypes = [vp, C.c_int, C.c_int, C.POINTER(Sums), C.c_size_t, fp, fp, i32p, fp, fp, fp, fp, fp, fp, fp]
     L.symmicp_ctx_loop_solve.argtypes = [vp, C.POINTER(Sums), fp, fp, i32p, fp, i32p, fp, fp, fp, fp, fp, i32p]
@@ -354,7 +356,7 @@ class Engine:
         self._chk(self._L.symmicp_set_sums(self._h, C.byref(s)))
 
     def set_robust_loss(self, loss, scale=1.0):
-        """M-estimator weights for the PAPER / P2P loop (LOSS_* or its name); takes effect at the next pass"""
+        """M-estimator weights for the PAPER / PLANE / GICP / P2P loop (LOSS_* or its name); takes effect at the next pass"""
         self._chk(self._L.symmicp_set_robust_loss(self._h, loss_code(loss), float(scale)))
 
     def robust_loss(self):
@@ -362,6 +364,15 @@ class Engine:
         lo, sc = C.c_int(0), C.c_float(0)
         self._chk(self._L.symmicp_get_robust_loss(self._h, C.byref(lo), C.byref(sc)))
         return lo.value, sc.value
+
+    def set_gicp_epsilon(self, eps):
+        """the eps of MODE_GICP's covariances I - (1 - eps) n n^T (0 < eps <= 1; default 1e-3); takes effect at the next pass"""
+        self._chk(self._L.symmicp_set_gicp_epsilon(self._h, float(eps)))
+
+    def gicp_epsilon(self):
+        ep = C.c_float(0)
+        self._chk(self._L.symmicp_get_gicp_epsilon(self._h, C.byref(ep)))
+        return ep.value
 
     def set_source(self, xyz, nrm):
         """nrm may be None in MODE_PLANE (the library holds zero source normals then)"""
@@ -578,6 +589,11 @@ class MyICP:
         self._final = np.eye(4, dtype=np.float32)
         self.last_result = None
         self._loss = (LOSS_NONE, 0.0)
+        self._gicp_eps = None
+
+    def setGicpEpsilon(self, eps):
+        """the covariance eps of the next align in MODE_GICP (see Engine.set_gicp_epsilon)"""
+        self._gicp_eps = float(eps)
 
     def setRobustLoss(self, loss, scale):
         """robust loss of the next align (see Engine.set_robust_loss)"""
@@ -606,7 +622,7 @@ class MyICP:
 
     def estimateNormals(self):
         # myicp.cpp:152-172: k = 10, flipped toward the origin.  Point-to-plane uses the target's normals only: in MODE_PLANE the
-        # source's are not estimated (the engine runs without them unless the caller supplied them)
+        # source's are not estimated (the engine runs without them unless the caller supplied them); GICP needs both
         if self.normals_src is None and self._cfg["mode"] != MODE_PLANE:
             self.normals_src, _ = estimate_normals(self.cloud_src, 10)
         if self.normals_tgt is None:
@@ -622,6 +638,8 @@ class MyICP:
         with Engine(**self._cfg) as e:
             if self._loss[0] != LOSS_NONE:
                 e.set_robust_loss(*self._loss)
+            if self._gicp_eps is not None:
+                e.set_gicp_epsilon(self._gicp_eps)
             e.set_target(self.cloud_tgt, self.normals_tgt)
             e.set_source(self.cloud_src, self.normals_src)
             self.last_result = e.align(guess)

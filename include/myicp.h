@@ -44,12 +44,16 @@ public:
 	MyICP &operator=(const MyICP &) = delete;
 	void setMaximumIterations(int n) { max_iters = n; }
 	void setDiffThreshold(float d) { diff_threshold = d; }
-	void setMode(symmicp_mode m) { mode_ = m; }                    // default SYMMICP_MODE_QUIRKS (= the reference); PLANE estimates no source normals
+	void setMode(symmicp_mode m) { mode_ = m; }                    // default SYMMICP_MODE_QUIRKS (= the reference); PLANE estimates no source normals,
+	                                                               // GICP the normals of both clouds (as PAPER)
 	void setCorrespondence(symmicp_corr c) { corr_ = c; }          // default SYMMICP_CORR_IDENTITY (= the reference)
 	void setVerbose(bool v) { verbose_ = v; }
 	// robust loss of the PAPER loop (symmicp_set_robust_loss; default SYMMICP_LOSS_NONE): checked by align(), which
 	// returns SYMMICP_ERR_ARG for a loss with SYMMICP_MODE_QUIRKS or a scale that is not finite and > 0
 	void setRobustLoss(symmicp_loss loss, float scale) { loss_ = loss; loss_scale_ = scale; }
+	// the covariance eps of SYMMICP_MODE_GICP (symmicp_set_gicp_epsilon; default 1e-3): checked by align(), which returns
+	// SYMMICP_ERR_ARG unless 0 < eps <= 1
+	void setGicpEpsilon(float eps) { gicp_eps_ = eps; }
 	const symmicp_result &lastResult() const { return result_; }
 	const char *lastError() const { return error_.c_str(); }
 
@@ -69,6 +73,7 @@ private:
 	bool verbose_, have_src_normals_, have_tgt_normals_;   // have_*: normals supplied by the caller through setInput*
 	symmicp_loss loss_;
 	float loss_scale_;
+	float gicp_eps_;
 	symmicp_ctx *ctx_;
 	int ctx_corr_;
 	bool ctx_no_src_normals_;            // the context holds a source set without normals (PLANE): no other mode can run on it

@@ -53,8 +53,18 @@ typedef enum {
  * minimise sum ((R p + t - q) . n_q)^2 with the TARGET's normals only; pivot, CUMULATIVE default and rotated-only normals
  * as PAPER.  Its record uses PAPER's slots with n_p = 0 and s = p + q replaced by p: v_i = (p_i x n_q, n_q),
  * c_i = (p_i - q_i) . n_q, both points about the pivot; the increment is T(pbar + t) R T(-pbar) with R = AngleAxis(|a|, a/|a|)
- * about the (weighted) source centroid.  PLANE alone needs no source normals: symmicp_set_source takes nrm == NULL then. */
-typedef enum { SYMMICP_MODE_QUIRKS = 0, SYMMICP_MODE_PAPER = 1, SYMMICP_MODE_P2P = 2, SYMMICP_MODE_PLANE = 3 } symmicp_mode;
+ * about the (weighted) source centroid.  PLANE alone needs no source normals: symmicp_set_source takes nrm == NULL then.
+ * GICP is plane-to-plane ICP, the Generalized-ICP of Segal, Haehnel and Thrun (2009) with the usual regularised covariances
+ * built from the normals: C_x = I - (1 - eps) x x^T for a normal x (eps: symmicp_set_gicp_epsilon, default 1e-3).  It minimises
+ * sum d^T M d, d = R p + t - q, M = (C_q + R C_p R^T)^-1, linearised about the pivot as PLANE.  For the moved source normal a
+ * and the target normal b, with u = a + b, v = a - b and cs = a . b, M has the closed form
+ *   M = 1/2 I + gu u u^T + gv v v^T,  gu = (1 - eps) / (4 (2 - (1 - eps)(1 + cs))),  gv = (1 - eps) / (4 (2 - (1 - eps)(1 - cs)))
+ * (exact for unit normals).  The mode is DEFINED by this formula with cs clamped to [-1, 1], so that it holds for any input:
+ * zero normals give M = 1/2 I (a point-to-point pair), non-unit normals get the formula as stated.  GICP needs the normals of
+ * both clouds; pivot, CUMULATIVE default, rotated-only normals and the solve (PLANE's, about the weighted source centroid) as
+ * PLANE.  Mode 4 is unassigned. */
+typedef enum { SYMMICP_MODE_QUIRKS = 0, SYMMICP_MODE_PAPER = 1, SYMMICP_MODE_P2P = 2, SYMMICP_MODE_PLANE = 3,
+               SYMMICP_MODE_GICP = 5 } symmicp_mode;
 
 /* Correspondence.  IDENTITY is what the reference does (myicp.cpp:130, the
  * search is a todo at :128-131).  BRUTE and TREE are exact nearest neighbour
@@ -75,8 +85,9 @@ typedef enum { SYMMICP_APPLY_DEFAULT = 0, SYMMICP_APPLY_INCREMENTAL = 1, SYMMICP
  * reweighted least squares (each pass weights the pairs at their current position; the solve is the usual one on the
  * weighted sums).  r is, in PAPER, c = (p - q) . (n_p + n_q), the quantity whose square the symmetric objective sums --
  * so `scale` is in units of c, about TWICE the point-to-plane distance when the two normals agree -- in PLANE
- * r = c = (p - q) . n_q, the signed point-to-plane distance itself (`scale` in plain length units), and in P2P
- * r = |p - q|.  With u = r / scale:
+ * r = c = (p - q) . n_q, the signed point-to-plane distance itself (`scale` in plain length units), in GICP
+ * r = sqrt(d^T M d), the pair's Mahalanobis distance (about 1/sqrt(2) of |p - q| across the planes, larger along the normals),
+ * and in P2P r = |p - q|.  With u = r / scale:
  *   HUBER          1 if |u| <= 1, else 1/|u|
  *   TUKEY          (1 - u^2)^2 if |u| < 1, else 0
  *   CAUCHY         1 / (1 + u^2)
@@ -116,9 +127,15 @@ typedef struct {
  *   [37..39] reserved (0)
  * PLANE: v_i = (p_i x n_q, n_q) and c_i = (p_i - q_i) . n_q in fp32, unfused: m0 = py*nz - pz*ny, m1 = pz*nx - px*nz,
  *   m2 = px*ny - py*nx, c = (dx*nx + dy*ny) + dz*nz with n = n_q, d = p - q (p, q about the pivot); every other slot as above.
+ * GICP: five rows per pair of PLANE's form v = (p x l, l), c = l . d, each with a weight o (M = sum o l l^T, see symmicp_mode):
+ *   l = e_x, e_y, e_z at o = 1/2; l = u at gu; l = v at gv (u, v, gu, gv in fp32, unfused, cs clamped; rows as PLANE's with n = l)
+ *   [0..20]  sum_i sum_l o v v^T  (the axis rows summed as 1/2 J^T J, J = [-[p]x, I])     [21..26] sum_i sum_l o v c
+ *   [27..32] sum p, sum q once per PAIR, not per row (PLANE's solve centres on the source centroid)
+ *   [35] sum_i d^T M d (= sum_i sum_l o c^2)                every other slot as above.
+ *   The record has PLANE's shape: symmicp_solve(SYMMICP_MODE_GICP) is PLANE's solve.
  * With a robust loss set (symmicp_set_robust_loss), w_i = the pair's weight:
  *   [0..32], [35]  the same sums with every pair scaled by w_i: sum w v v^T, sum w v c, sum w p, sum w q, sum w c^2
- *                  (P2P: sum w p q^T and the weighted coordinate sums)
+ *                  (P2P: sum w p q^T and the weighted coordinate sums; GICP: every row of the pair scaled by w_i)
  *   [34] sum_i w_i (the solves centre on the weighted centroids)
  *   [33], [36]     unweighted, as above (the stop rule and `diff` keep their meaning)
  *   [37] number of pairs (what symmicp_iter_result.pairs reports then)
@@ -161,6 +178,12 @@ int symmicp_version(void);
  * the values it started with.  Sharded runs: every rank sets the same values. */
 int symmicp_set_robust_loss(symmicp_ctx *ctx, int loss, float scale);
 int symmicp_get_robust_loss(const symmicp_ctx *ctx, int *loss, float *scale);
+/* The eps of SYMMICP_MODE_GICP's covariances C = I - (1 - eps) n n^T: 0 < eps <= 1 and finite, else SYMMICP_ERR_ARG; default 1e-3
+ * (PCL's and Segal's).  Accepted in every mode, read by GICP only.  eps = 1 makes every pair point-to-point (M = 1/2 I).  Takes
+ * effect at the next pass; a device-driven run inside symmicp_align keeps the value it started with.  Sharded runs: every rank
+ * sets the same value. */
+int symmicp_set_gicp_epsilon(symmicp_ctx *ctx, float eps);
+int symmicp_get_gicp_epsilon(const symmicp_ctx *ctx, float *eps);
 /* the weight the kernels give a pair of residual r (the same fp32 source); NaN for an unknown loss, or for a scale that
  * is not finite and > 0 with loss != NONE; 1 for SYMMICP_LOSS_NONE */
 float symmicp_robust_weight(int loss, float scale, float r);
@@ -218,15 +241,15 @@ size_t symmicp_local_source_count(const symmicp_ctx *ctx);
 size_t symmicp_local_source_offset(const symmicp_ctx *ctx);
 
 /* ---- host-side pieces of func.cpp:76-102, exposed for parity tests ----- */
-/* PAPER and PLANE: pbar / qbar = the (weighted) centroids in the caller's frame, (a, t) the solved 6-vector; P2P: zeros */
+/* PAPER, PLANE and GICP: pbar / qbar = the (weighted) centroids in the caller's frame, (a, t) the solved 6-vector; P2P: zeros */
 int symmicp_solve(int mode, const symmicp_sums *sums, const float pivot[3],
                   float pbar[3], float qbar[3], float a[3], float t[3], float *rcond, float out16[16]);
 
 /* ---- test entry points of the device-driven loop (off the hot path; a test's view of what the device does with a record) ----- */
-/* The device's solve: solve_core.h compiled for gfx950, one thread per record, mode QUIRKS / PAPER / PLANE, with the host's exact
+/* The device's solve: solve_core.h compiled for gfx950, one thread per record, mode QUIRKS / PAPER / PLANE / GICP, with the host's exact
  * conditioning (exact_rc = 1) or the device loop's lower bound (exact_rc = 0).  Per record i: status[i], pbar / qbar / a / t [i][3],
  * rcond[i], out16[i][16] (the increment); with X_in16 != NULL also X_out16[i][16] = increment * X_in16[i] (mat4_mul, as the loop
- * composes).  pivot may be NULL (PAPER / PLANE: zero). */
+ * composes).  pivot may be NULL (PAPER / PLANE / GICP: zero). */
 int symmicp_ctx_solve_probe(symmicp_ctx *ctx, int mode, int exact_rc, const symmicp_sums *sums, size_t n, const float pivot[3],
                             const float *X_in16, int32_t *status, float *pbar, float *qbar, float *a, float *t, float *rcond,
                             float *out16, float *X_out16);
