@@ -11,6 +11,10 @@
 //     --loss-scale S           its scale (PAPER: in units of c = (p - q).(n_p + n_q), about twice the point-to-plane distance;
 //                              PLANE: the point-to-plane distance itself; GICP: the pair's Mahalanobis distance)
 //     --threshold D            stop once the summed pair distance is <= D   (default 1.0, ICP/myicp.cpp:6)
+//     --max-dist D             drop pairs farther apart than D (default 0: keep every pair)
+//     --scale LEAF:ITERS[:MAXDIST]   one level of a coarse-to-fine alignment (repeat it, coarse first): both clouds
+//                              voxel-downsampled with edge LEAF (0: as given), at most ITERS iterations, pairs farther than
+//                              MAXDIST dropped (default 0: none); each level starts from the one before.  Needs --corr tree
 //     --out aligned.pcd        write the source moved by the result (the reference only prints its result)
 //     --quiet                  no per-iteration lines
 //   Without file names it registers cat.pcd to cat_out.pcd from the working directory: the reference's own run.
@@ -30,7 +34,7 @@
 static int usage(const char *argv0, const char *complaint)
 {
     std::fprintf(stderr, "%s\nusage: %s [--mode quirks|paper|plane|gicp] [--corr identity|tree] [--iters N] [--threshold D] [--loss none|huber|tukey|cauchy|gm]"
-                 " [--loss-scale S] [--gicp-epsilon E] [--out file.pcd] [--quiet] [source.pcd target.pcd]\n",
+                 " [--loss-scale S] [--gicp-epsilon E] [--max-dist D] [--scale LEAF:ITERS[:MAXDIST]]... [--out file.pcd] [--quiet] [source.pcd target.pcd]\n",
                  complaint, argv0);
     return 64;
 }
@@ -46,6 +50,8 @@ int main(int argc, char **argv)
     bool have_scale = false;
     bool gicp = false, have_eps = false;
     float gicp_eps = 0.f;
+    bool tree = false;
+    std::vector<MyICP::VoxelLevel> levels;
     for (int k = 1; k < argc; k++) {
         const std::string a = argv[k];
         auto value = [&](const char *what) -> const char * {
@@ -61,8 +67,8 @@ int main(int argc, char **argv)
             else return usage(argv[0], "unknown --mode");
         } else if (a == "--corr") {
             const std::string v = value("--corr");
-            if (v == "identity") icp.setCorrespondence(SYMMICP_CORR_IDENTITY);
-            else if (v == "tree") icp.setCorrespondence(SYMMICP_CORR_TREE);
+            if (v == "identity") { icp.setCorrespondence(SYMMICP_CORR_IDENTITY); tree = false; }
+            else if (v == "tree") { icp.setCorrespondence(SYMMICP_CORR_TREE); tree = true; }
             else return usage(argv[0], "unknown --corr");
         } else if (a == "--iters") icp.setMaximumIterations(std::atoi(value("--iters")));
         else if (a == "--threshold") icp.setDiffThreshold((float)std::atof(value("--threshold")));
@@ -88,6 +94,33 @@ int main(int argc, char **argv)
                 return usage(argv[0], "--gicp-epsilon needs a number E with 0 < E <= 1");
             have_eps = true;
         }
+        else if (a == "--max-dist") {
+            char *end = nullptr;
+            const char *v = value("--max-dist");
+            const float d = std::strtof(v, &end);
+            if (end == v || *end || !std::isfinite(d)) return usage(argv[0], "--max-dist needs a number");
+            icp.setMaxCorrespondenceDistance(d);
+        } else if (a == "--scale") {
+            // LEAF:ITERS[:MAXDIST]
+            const char *v = value("--scale");
+            char *end = nullptr;
+            MyICP::VoxelLevel lv{0.f, 0, 0.f};
+            lv.leaf = std::strtof(v, &end);
+            bool ok = end != v && *end == ':' && std::isfinite(lv.leaf) && lv.leaf >= 0.f;
+            if (ok) {
+                const char *w = end + 1;
+                const long it = std::strtol(w, &end, 10);
+                ok = end != w && it >= 0 && it <= 1000000 && (*end == 0 || *end == ':');
+                lv.max_iters = (int)it;
+            }
+            if (ok && *end == ':') {
+                const char *w = end + 1;
+                lv.max_corr_dist = std::strtof(w, &end);
+                ok = end != w && *end == 0 && std::isfinite(lv.max_corr_dist);
+            }
+            if (!ok) return usage(argv[0], "--scale needs LEAF:ITERS[:MAXDIST] with LEAF >= 0 and ITERS >= 0");
+            levels.push_back(lv);
+        }
         else if (a == "--out") out_path = value("--out");
         else if (a == "--quiet") icp.setVerbose(false);
         else if (!a.empty() && a[0] == '-') return usage(argv[0], ("unknown option " + a).c_str());
@@ -99,6 +132,10 @@ int main(int argc, char **argv)
         if (quirks) return usage(argv[0], "--loss needs --mode paper, plane or gicp (quirks is the reference as written)");
         if (!have_scale || !(loss_scale > 0.f) || !std::isfinite(loss_scale)) return usage(argv[0], "--loss needs --loss-scale S with S > 0");
         icp.setRobustLoss(loss, loss_scale);
+    }
+    if (!levels.empty()) {
+        if (!tree) return usage(argv[0], "--scale needs --corr tree (identity pairing cannot pair clouds of different sizes)");
+        icp.setVoxelLevels(levels);
     }
     if (have_eps) {
         if (!gicp) return usage(argv[0], "--gicp-epsilon needs --mode gicp");

@@ -972,6 +972,136 @@ int symmicp_estimate_normals(int device, const float *xyz, size_t row_stride, si
     return st;
 }
 
+// ---- voxel-grid downsampling (kernels_voxel.hip; DESIGN.md 4, "Voxel downsampling") ---------------------------------------
+// Box (launch_bbox) -> grid set-up here in fp32 -> keys -> stable radix sort of (key, row) -> run heads, scan, first positions ->
+// kept voxels (>= min_points), scan, compaction -> sorted SoA gather -> per-voxel sequential means.  Temporaries come from the
+// context's arena only: its target, source, index and certificates are not touched.
+static int voxel_downsample(symmicp_ctx *c, const float *xyz, size_t xr, size_t xc, const float *nrm, size_t nr, size_t nc, size_t n,
+                            float leaf, int min_points, float *xyz_out, float *nrm_out, int32_t *count_out, int32_t *voxel_of, size_t cap,
+                            size_t *n_out)
+{
+    HIP_TRY(c, hipSetDevice(c->device));
+    const bool with_nrm = nrm_out != nullptr;
+    arena_begin(c->arena, n * (128 + 4 * (xr + (with_nrm ? nr : 0))) + ((size_t)1 << 20));
+    const uint32_t n32 = (uint32_t)n;
+    DevBuf<float> block;
+    int st = upload_planar(c, xyz, xr, xc, with_nrm ? nrm : nullptr, nr, nc, n, block, /*temp=*/true, nullptr);
+    if (st != SYMMICP_OK) return st;
+    CloudSoA cl;
+    soa_from_block(block.p, n, cl);
+
+    DevBuf<uint32_t> bbox;
+    HIP_TRY(c, bbox.alloc_temp(c->arena, 6));
+    launch_bbox(cl.x, cl.y, cl.z, n32, bbox.p, c->stream);
+    uint32_t hb[6];
+    HIP_TRY(c, hipMemcpyAsync(hb, bbox.p, sizeof(hb), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    // the grid, in fp32 with IEEE ops: floorf(v * inv) is monotone in v, so the box's ends give every point's cell range
+    const float inv = 1.0f / leaf;
+    int lo[3];
+    uint64_t dim[3];
+    for (int k = 0; k < 3; k++) {
+        const float bmin = ord2f(hb[k]), bmax = ord2f(hb[3 + k]);
+        if (!std::isfinite(bmin) || !std::isfinite(bmax)) return fail(c, SYMMICP_ERR_ARG, "cloud has non-finite coordinates");
+        const float flo = std::floor(bmin * inv), fhi = std::floor(bmax * inv);
+        if (!(flo >= -2147483648.0f && flo < 2147483648.0f && fhi >= -2147483648.0f && fhi < 2147483648.0f))
+            return fail(c, SYMMICP_ERR_ARG, "leaf size is too small for the input cloud: voxel indices overflow an int32");
+        lo[k] = (int)flo;
+        dim[k] = (uint64_t)((int64_t)(int)fhi - (int64_t)lo[k] + 1);
+    }
+    const unsigned __int128 total = (unsigned __int128)dim[0] * dim[1] * dim[2];
+    if (total > ((unsigned __int128)1 << 32))
+        return fail(c, SYMMICP_ERR_ARG, "leaf size is too small for the input cloud: more than 2^32 voxels in its box");
+    int bits = 0;
+    while (((unsigned __int128)1 << bits) < total) bits++;
+
+    DevBuf<uint32_t> keys, rows, kt, vt, ws, vid, first, kid, kfirst, kcount, scan_ws, words;
+    DevBuf<float> sorted, d_xyz, d_nrm;
+    DevBuf<int32_t> d_count, d_vof;
+    const size_t wse = radix_sort_ws_elems(n32);
+    HIP_TRY(c, keys.alloc_temp(c->arena, n));
+    HIP_TRY(c, rows.alloc_temp(c->arena, n));
+    HIP_TRY(c, kt.alloc_temp(c->arena, n));
+    HIP_TRY(c, vt.alloc_temp(c->arena, n));
+    HIP_TRY(c, ws.alloc_temp(c->arena, wse));
+    HIP_TRY(c, vid.alloc_temp(c->arena, n));
+    HIP_TRY(c, first.alloc_temp(c->arena, n + 1));
+    HIP_TRY(c, kid.alloc_temp(c->arena, n));
+    HIP_TRY(c, kfirst.alloc_temp(c->arena, n));
+    HIP_TRY(c, kcount.alloc_temp(c->arena, n));
+    HIP_TRY(c, scan_ws.alloc_temp(c->arena, n / 2048 + 2));
+    HIP_TRY(c, words.alloc_temp(c->arena, 2));
+    HIP_TRY(c, sorted.alloc_temp(c->arena, 6 * n));
+    launch_voxel_keys(cl, n32, inv, lo, dim[0], dim[1], keys.p, rows.p, c->stream);
+    radix_sort_pairs(keys.p, rows.p, kt.p, vt.p, n32, bits, ws.p, wse, c->stream);
+    launch_voxel_segments(keys.p, n32, vid.p, first.p, scan_ws.p, words.p, c->stream);
+    uint32_t m0 = 0, m = 0;
+    HIP_TRY(c, hipMemcpyAsync(&m0, words.p, sizeof(m0), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    launch_voxel_keep(first.p, m0, (uint32_t)min_points, kid.p, scan_ws.p, kfirst.p, kcount.p, words.p + 1, c->stream);
+    HIP_TRY(c, hipMemcpyAsync(&m, words.p + 1, sizeof(m), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    *n_out = m;
+    if (m > cap) return fail(c, SYMMICP_ERR_SIZE, "voxel_downsample: " + std::to_string(m) + " voxels do not fit cap " + std::to_string(cap));
+    CloudSoA sc;
+    soa_from_block(sorted.p, n, sc);
+    launch_gather_soa(cl, rows.p, n32, sc, c->stream);
+    HIP_TRY(c, d_xyz.alloc_temp(c->arena, 3 * (size_t)m));
+    HIP_TRY(c, d_count.alloc_temp(c->arena, m));
+    if (with_nrm) HIP_TRY(c, d_nrm.alloc_temp(c->arena, 3 * (size_t)m));
+    launch_voxel_mean(sc, kfirst.p, kcount.p, m, with_nrm ? 1 : 0, d_xyz.p, d_nrm.p, d_count.p, c->stream);
+    if (voxel_of) {
+        HIP_TRY(c, d_vof.alloc_temp(c->arena, n));
+        launch_voxel_of(keys.p, rows.p, vid.p, first.p, kid.p, n32, (uint32_t)min_points, d_vof.p, c->stream);
+    }
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpyAsync(xyz_out, d_xyz.p, sizeof(float) * 3 * m, hipMemcpyDeviceToHost, c->stream));
+    if (with_nrm) HIP_TRY(c, hipMemcpyAsync(nrm_out, d_nrm.p, sizeof(float) * 3 * m, hipMemcpyDeviceToHost, c->stream));
+    if (count_out) HIP_TRY(c, hipMemcpyAsync(count_out, d_count.p, sizeof(int32_t) * m, hipMemcpyDeviceToHost, c->stream));
+    if (voxel_of) HIP_TRY(c, hipMemcpyAsync(voxel_of, d_vof.p, sizeof(int32_t) * n, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    HIP_TRY(c, hipGetLastError());
+    return SYMMICP_OK;
+}
+
+static const char *voxel_args_error(const float *xyz, const float *nrm, size_t n, float leaf, int min_points, const float *xyz_out,
+                                    const float *nrm_out, const size_t *n_out)
+{
+    if (!xyz || !xyz_out || !n_out) return "voxel_downsample: xyz, xyz_out and n_out are required";
+    if (n == 0 || n > 0x7fffffffull) return "voxel_downsample: n must be in 1 .. 2^31 - 1";
+    if (!std::isfinite(leaf) || !(leaf > 0.f)) return "voxel_downsample: leaf must be finite and > 0";
+    if (min_points < 1) return "voxel_downsample: min_points must be >= 1";
+    if (nrm_out && !nrm) return "voxel_downsample: nrm_out needs nrm";
+    return nullptr;
+}
+
+int symmicp_ctx_voxel_downsample(symmicp_ctx *c, const float *xyz, size_t xyz_row_stride, size_t xyz_col_stride, const float *nrm,
+                                 size_t nrm_row_stride, size_t nrm_col_stride, size_t n, float leaf, int min_points, float *xyz_out,
+                                 float *nrm_out, int32_t *count_out, int32_t *voxel_of, size_t cap, size_t *n_out)
+{
+    if (!c) return SYMMICP_ERR_ARG;
+    if (const char *msg = voxel_args_error(xyz, nrm, n, leaf, min_points, xyz_out, nrm_out, n_out)) return fail(c, SYMMICP_ERR_ARG, msg);
+    return voxel_downsample(c, xyz, xyz_row_stride, xyz_col_stride, nrm, nrm_row_stride, nrm_col_stride, n, leaf, min_points, xyz_out, nrm_out,
+                            count_out, voxel_of, cap, n_out);
+}
+
+int symmicp_voxel_downsample(int device, const float *xyz, size_t xyz_row_stride, size_t xyz_col_stride, const float *nrm,
+                             size_t nrm_row_stride, size_t nrm_col_stride, size_t n, float leaf, int min_points, float *xyz_out,
+                             float *nrm_out, int32_t *count_out, int32_t *voxel_of, size_t cap, size_t *n_out)
+{
+    if (voxel_args_error(xyz, nrm, n, leaf, min_points, xyz_out, nrm_out, n_out)) return SYMMICP_ERR_ARG;
+    symmicp_config cfg;
+    symmicp_config_default(&cfg);
+    cfg.device = device;
+    symmicp_ctx *c = nullptr;
+    int st = symmicp_create(&cfg, &c);
+    if (st != SYMMICP_OK) return st;
+    st = symmicp_ctx_voxel_downsample(c, xyz, xyz_row_stride, xyz_col_stride, nrm, nrm_row_stride, nrm_col_stride, n, leaf, min_points,
+                                      xyz_out, nrm_out, count_out, voxel_of, cap, n_out);
+    symmicp_destroy(c);
+    return st;
+}
+
 // ---- stats -------------------------------------------------------------------------------------
 int symmicp_enable_timing(symmicp_ctx *c, int on)
 {

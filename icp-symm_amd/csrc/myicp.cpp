@@ -6,7 +6,7 @@
 
 MyICP::MyICP() : max_iters(10), diff_threshold(1.f),                       // myicp.cpp:6
                  mode_(SYMMICP_MODE_QUIRKS), corr_(SYMMICP_CORR_IDENTITY), verbose_(true),
-                 have_src_normals_(false), have_tgt_normals_(false), loss_(SYMMICP_LOSS_NONE), loss_scale_(0.f), gicp_eps_(1e-3f), ctx_(nullptr), ctx_corr_(-1), ctx_no_src_normals_(false)
+                 have_src_normals_(false), have_tgt_normals_(false), loss_(SYMMICP_LOSS_NONE), loss_scale_(0.f), gicp_eps_(1e-3f), max_corr_dist_(0.f), ctx_(nullptr), ctx_corr_(-1), ctx_no_src_normals_(false)
 {
 	cloud_src = pcl::PointCloud<PointT>::Ptr(new pcl::PointCloud<PointT>);
 	cloud_tgt = pcl::PointCloud<PointT>::Ptr(new pcl::PointCloud<PointT>);
@@ -144,11 +144,19 @@ int MyICP::align(float out4x4[16], const float *guess4x4)
 	symmicp_config_default(&cfg);
 	cfg.mode = mode_; cfg.corr = corr_; cfg.max_iters = max_iters; cfg.diff_threshold = diff_threshold;
 	cfg.verbose = verbose_ ? 1 : 0;
+	cfg.max_corr_dist = max_corr_dist_;
 	int st = symmicp_set_robust_loss(ctx, SYMMICP_LOSS_NONE, 0.f);        // (the context may carry a loss into a QUIRKS config)
 	if (st == SYMMICP_OK) st = symmicp_set_config(ctx, &cfg);
 	if (st == SYMMICP_OK) st = symmicp_set_robust_loss(ctx, loss_, loss_scale_);      // ERR_ARG: a loss with QUIRKS, or a bad scale
 	if (st == SYMMICP_OK) st = symmicp_set_gicp_epsilon(ctx, gicp_eps_);              // ERR_ARG: eps outside (0, 1]
 	const size_t fs = sizeof(pcl::PointNormal) / sizeof(float);            // pasteInMatrix, func.cpp:5-15
+	level_results_.clear();
+	if (st == SYMMICP_OK && !levels_.empty()) {
+		st = alignLevels(cfg, source_normals, guess4x4);
+		if (result_.iters > 0 || st == SYMMICP_OK) std::memcpy(transform_, result_.transform, sizeof(transform_));
+		if (out4x4) std::memcpy(out4x4, transform_, sizeof(transform_));
+		return st;
+	}
 	if (st == SYMMICP_OK) {
 		if (!cloud_pn_tgt->points.empty() && !cloud_pn_src->points.empty()) {
 			st = symmicp_set_target(ctx, &cloud_pn_tgt->points[0].x, fs, 1, &cloud_pn_tgt->points[0].normal_x, fs, 1, cloud_pn_tgt->points.size());
@@ -167,6 +175,64 @@ int MyICP::align(float out4x4[16], const float *guess4x4)
 	if (result_.iters > 0 || st == SYMMICP_OK) std::memcpy(transform_, result_.transform, sizeof(transform_));
 	if (out4x4) std::memcpy(out4x4, transform_, sizeof(transform_));
 	return st;
+}
+
+// the levels of setVoxelLevels on the object's context (cfg: align()'s configuration, already set on it)
+int MyICP::alignLevels(const symmicp_config &cfg0, bool source_normals, const float *guess4x4)
+{
+	symmicp_ctx *ctx = ctx_;
+	if (corr_ == SYMMICP_CORR_IDENTITY) {
+		error_ = "voxel levels need nearest-neighbour pairs (SYMMICP_CORR_IDENTITY pairs by row, and downsampled counts differ)";
+		result_.status = SYMMICP_ERR_ARG;
+		return SYMMICP_ERR_ARG;
+	}
+	if (cloud_pn_tgt->points.empty() || cloud_pn_src->points.empty()) { result_.status = SYMMICP_ERR_SIZE; return SYMMICP_ERR_SIZE; }
+	const size_t fs = sizeof(pcl::PointNormal) / sizeof(float);
+	struct Cloud { pcl::PointCloud<pcl::PointNormal> *pn; bool nrm; std::vector<float> xyz, n; size_t m; };
+	Cloud cl[2] = {{cloud_pn_src.get(), source_normals, {}, {}, 0}, {cloud_pn_tgt.get(), true, {}, {}, 0}};
+	float X[16];
+	const float *guess = guess4x4;
+	const size_t K = levels_.size();
+	for (size_t k = 0; k < K; k++) {
+		const VoxelLevel &lv = levels_[k];
+		for (Cloud &c : cl) {
+			const size_t n = c.pn->points.size();
+			const pcl::PointNormal *p = &c.pn->points[0];
+			c.xyz.resize(3 * n);
+			c.n.resize(c.nrm ? 3 * n : 0);
+			if (lv.leaf > 0.f) {
+				int st = symmicp_ctx_voxel_downsample(ctx, &p->x, fs, 1, c.nrm ? &p->normal_x : nullptr, fs, 1, n, lv.leaf, 1, c.xyz.data(),
+				                                      c.nrm ? c.n.data() : nullptr, nullptr, nullptr, n, &c.m);
+				if (st != SYMMICP_OK) { result_.status = st; error_ = symmicp_last_error(ctx); return st; }
+			} else {
+				for (size_t i = 0; i < n; i++) {
+					c.xyz[3 * i] = p[i].x; c.xyz[3 * i + 1] = p[i].y; c.xyz[3 * i + 2] = p[i].z;
+					if (c.nrm) { c.n[3 * i] = p[i].normal_x; c.n[3 * i + 1] = p[i].normal_y; c.n[3 * i + 2] = p[i].normal_z; }
+				}
+				c.m = n;
+			}
+		}
+		if (verbose_)
+			std::printf("level %zu/%zu: leaf %g, source %zu -> %zu, target %zu -> %zu\n", k + 1, K, (double)lv.leaf, cloud_pn_src->points.size(), cl[0].m,
+			            cloud_pn_tgt->points.size(), cl[1].m);
+		symmicp_config cfg = cfg0;
+		cfg.max_iters = lv.max_iters;
+		cfg.max_corr_dist = lv.max_corr_dist;
+		cfg.verbose = (verbose_ && k + 1 == K) ? 1 : 0;
+		int st = symmicp_set_config(ctx, &cfg);
+		if (st == SYMMICP_OK) st = symmicp_set_target(ctx, cl[1].xyz.data(), 3, 1, cl[1].n.data(), 3, 1, cl[1].m);
+		if (st == SYMMICP_OK) {
+			st = symmicp_set_source(ctx, cl[0].xyz.data(), 3, 1, cl[0].nrm ? cl[0].n.data() : nullptr, 3, 1, cl[0].m);
+			ctx_no_src_normals_ = st == SYMMICP_OK && !cl[0].nrm;
+		}
+		if (st == SYMMICP_OK) st = symmicp_align(ctx, guess, &result_);
+		else result_.status = st;
+		level_results_.push_back(result_);
+		if (st != SYMMICP_OK) { error_ = symmicp_last_error(ctx); return st; }
+		std::memcpy(X, result_.transform, sizeof(X));
+		guess = X;
+	}
+	return SYMMICP_OK;
 }
 
 pcl::PointCloud<PointT>::Ptr MyICP::GetAlignedSrcCloud() const

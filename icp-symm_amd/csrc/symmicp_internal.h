@@ -241,4 +241,18 @@ void launch_pairs_d2(const CloudSoA &in, const Affine &X, const int32_t *pos, co
 void launch_normals_knn(const TargetIndex &ix, int k, const float vp[3], float *nrm_out, float *curv_out, hipStream_t s);
 void launch_knn(const TargetIndex &ix, int k, int32_t *rows_out, float *d2_out, hipStream_t s);
 
+// voxel-grid downsampling (kernels_voxel.hip; symmicp_ctx_voxel_downsample): keys + iota rows; run heads -> exclusive scan -> first
+// position of every voxel (first[m0] = n) and the voxel count m0 in *m0_out; kept voxels (>= min_points) -> exclusive scan ->
+// their (first, count) and number m in *m_out; the per-voxel means; the output id of every row (-1: dropped voxel)
+void launch_voxel_keys(const CloudSoA &cl, uint32_t n, float inv, const int lo[3], uint64_t nx, uint64_t ny, uint32_t *keys, uint32_t *vals,
+                       hipStream_t s);
+void launch_voxel_segments(const uint32_t *keys, uint32_t n, uint32_t *vid_excl, uint32_t *first, uint32_t *scan_ws, uint32_t *m0_out,
+                           hipStream_t s);
+void launch_voxel_keep(const uint32_t *first, uint32_t m0, uint32_t min_points, uint32_t *kid_excl, uint32_t *scan_ws, uint32_t *kfirst,
+                       uint32_t *kcount, uint32_t *m_out, hipStream_t s);
+void launch_voxel_mean(const CloudSoA &sorted, const uint32_t *kfirst, const uint32_t *kcount, uint32_t m, int with_normals, float *xyz_out,
+                       float *nrm_out, int32_t *count_out, hipStream_t s);
+void launch_voxel_of(const uint32_t *keys, const uint32_t *rows, const uint32_t *vid_excl, const uint32_t *first, const uint32_t *kid_excl,
+                     uint32_t n, uint32_t min_points, int32_t *voxel_of, hipStream_t s);
+
 }  // namespace symmicp

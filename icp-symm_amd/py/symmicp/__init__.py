@@ -91,6 +91,7 @@ EXPORTS = [
     "symmicp_pcd_read", "symmicp_pcd_write", "symmicp_estimate_normals", "symmicp_ctx_estimate_normals", "symmicp_ctx_knn",
     "symmicp_set_robust_loss", "symmicp_get_robust_loss", "symmicp_robust_weight", "symmicp_set_gicp_epsilon", "symmicp_get_gicp_epsilon",
     "symmicp_ctx_solve_probe", "symmicp_ctx_loop_solve", "symmicp_set_loop_log", "symmicp_get_loop_log",
+    "symmicp_voxel_downsample", "symmicp_ctx_voxel_downsample",
 ]
 
 _lib = None
@@ -168,6 +169,10 @@ def lib():
     L.symmicp_ctx_loop_solve.argtypes = [vp, C.POINTER(Sums), fp, fp, i32p, fp, i32p, fp, fp, fp, fp, fp, i32p]
     L.symmicp_set_loop_log.argtypes = [vp, C.c_int]
     L.symmicp_get_loop_log.argtypes = [vp, C.POINTER(LoopLogEntry), C.c_size_t, C.POINTER(C.c_size_t)]
+    vox = [fp, C.c_size_t, C.c_size_t, fp, C.c_size_t, C.c_size_t, C.c_size_t, C.c_float, C.c_int, fp, fp, i32p, i32p, C.c_size_t,
+           C.POINTER(C.c_size_t)]
+    L.symmicp_voxel_downsample.argtypes = [C.c_int] + vox
+    L.symmicp_ctx_voxel_downsample.argtypes = [vp] + vox
     _lib = L
     return L
 
@@ -282,6 +287,41 @@ def knn(xyz, k=10, device=-1):
     """the k nearest points of the same cloud, the set estimate_normals uses -> (rows [N,k] int32, d2 [N,k] f32), ascending (d2, row)"""
     with Engine(device=device) as e:
         return e.knn(xyz, k)
+
+
+def _voxel_call(fn, head, xyz, nrm, leaf, min_points, cap=None, strides=None):
+    """shared body of voxel_downsample and Engine.voxel_downsample: fn(*head, <the C arguments>) -> (status, result dict or None,
+    n_out).  strides = (n, xyz row, xyz col, nrm row, nrm col) reads xyz / nrm as flat f32 buffers (tests of the strided layouts)."""
+    if strides is None:
+        xyz = _cloud(xyz)
+        nrm = None if nrm is None else _cloud(nrm)
+        n, xr, xc, nr, nc = xyz.shape[0], 3, 1, 3, 1
+    else:
+        xyz = np.ascontiguousarray(xyz, np.float32)
+        nrm = None if nrm is None else np.ascontiguousarray(nrm, np.float32)
+        n, xr, xc, nr, nc = strides
+    cap = n if cap is None else cap
+    out = np.zeros((max(cap, 1), 3), np.float32)
+    nout = None if nrm is None else np.zeros((max(cap, 1), 3), np.float32)
+    cnt = np.zeros(max(cap, 1), np.int32)
+    vof = np.zeros(max(n, 1), np.int32)
+    m = C.c_size_t(0)
+    i32 = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
+    st = fn(*head, _fptr(xyz), xr, xc, None if nrm is None else _fptr(nrm), nr, nc, n, float(leaf), int(min_points), _fptr(out),
+            None if nout is None else _fptr(nout), i32(cnt), i32(vof), cap, C.byref(m))
+    m = int(m.value)
+    if st != OK:
+        return st, None, m
+    return st, dict(xyz=out[:m].copy(), nrm=None if nout is None else nout[:m].copy(), count=cnt[:m].copy(), voxel_of=vof[:n].copy()), m
+
+
+def voxel_downsample(xyz, leaf, nrm=None, min_points=1, device=-1):
+    """voxel-grid downsampling on the GPU (symmicp_voxel_downsample): one point per occupied voxel of edge `leaf` with at least
+    min_points points, in ascending voxel key -> dict(xyz [m,3], nrm [m,3] or None, count [m], voxel_of [N] (-1: dropped))"""
+    st, r, _ = _voxel_call(lib().symmicp_voxel_downsample, (int(device),), xyz, nrm, leaf, min_points)
+    if st != OK:
+        raise SymmIcpError(st, "voxel_downsample")
+    return r
 
 
 def shard_range(n, nranks, rank):
@@ -500,6 +540,16 @@ class Engine:
         self._chk(self._L.symmicp_ctx_knn(self._h, _fptr(xyz), 3, 1, n, k, rows.ctypes.data_as(C.POINTER(C.c_int32)), _fptr(d2)))
         return rows, d2
 
+    def voxel_downsample(self, xyz, leaf, nrm=None, min_points=1):
+        """voxel_downsample on this context (symmicp_ctx_voxel_downsample); its target, source and index stay as they are"""
+        st, r, _ = _voxel_call(self._L.symmicp_ctx_voxel_downsample, (self._h,), xyz, nrm, leaf, min_points)
+        self._chk(st)
+        return r
+
+    def voxel_downsample_raw(self, xyz, leaf, nrm=None, min_points=1, cap=None, strides=None):
+        """the C call as it is: -> (status, result dict or None, n_out); cap defaults to N, strides as in _voxel_call"""
+        return _voxel_call(self._L.symmicp_ctx_voxel_downsample, (self._h,), xyz, nrm, leaf, min_points, cap, strides)
+
     def enable_timing(self, on=True):
         self._chk(self._L.symmicp_enable_timing(self._h, int(on)))      # 0 off, 1 per pass, 2 per kernel
 
@@ -590,7 +640,22 @@ class MyICP:
         self.last_result = None
         self._loss = (LOSS_NONE, 0.0)
         self._gicp_eps = None
+        self._levels = []
+        self.level_results = []
 
+    def setMaxCorrespondenceDistance(self, d):
+        """pairs farther apart than d are dropped (Config.max_corr_dist; <= 0: every pair is kept)"""
+        self._cfg["max_corr_dist"] = float(d)
+
+    def setVoxelLevels(self, levels):
+        """coarse-to-fine alignment: [(leaf, max_iters, max_corr_dist), ...], coarse first (leaf 0: the clouds as given).  align()
+        then runs one alignment per level on both clouds voxel-downsampled with the level's leaf (normals averaged), each from the
+        transform of the level before (the first from the caller's guess).  CORR_IDENTITY is refused (ERR_ARG).  [] = off."""
+        self._levels = [(float(l), int(i), float(d)) for l, i, d in levels]
+
+    def levelResults(self):
+        """one align() result dict per level of the last align()"""
+        return self.level_results
     def setGicpEpsilon(self, eps):
         """the covariance eps of the next align in MODE_GICP (see Engine.set_gicp_epsilon)"""
         self._gicp_eps = float(eps)
@@ -634,7 +699,11 @@ class MyICP:
 
     def align(self, guess=None):
         assert self.cloud_src is not None and self.cloud_tgt is not None      # myicp.cpp:102
+        if self._levels and self._cfg["corr"] == CORR_IDENTITY:
+            raise SymmIcpError(ERR_ARG, "voxel levels need nearest-neighbour pairs (CORR_IDENTITY pairs by row)")
         self.estimateNormals()                                               # myicp.cpp:105
+        if self._levels:
+            return self._align_levels(guess)
         with Engine(**self._cfg) as e:
             if self._loss[0] != LOSS_NONE:
                 e.set_robust_loss(*self._loss)
@@ -645,6 +714,39 @@ class MyICP:
             self.last_result = e.align(guess)
         self._final = self.last_result["transform"]
         return self.last_result
+
+    def _align_levels(self, guess):
+        verbose = bool(self._cfg["verbose"])
+        self.level_results = []
+        K = len(self._levels)
+        with Engine(**dict(self._cfg, verbose=0)) as e:
+            if self._loss[0] != LOSS_NONE:
+                e.set_robust_loss(*self._loss)
+            if self._gicp_eps is not None:
+                e.set_gicp_epsilon(self._gicp_eps)
+            X = guess
+            for k, (leaf, iters, dist) in enumerate(self._levels):
+                if leaf > 0:
+                    s = e.voxel_downsample(self.cloud_src, leaf, self.normals_src)
+                    t = e.voxel_downsample(self.cloud_tgt, leaf, self.normals_tgt)
+                    src, sn, tgt, tn = s["xyz"], s["nrm"], t["xyz"], t["nrm"]
+                else:
+                    src, sn, tgt, tn = self.cloud_src, self.normals_src, self.cloud_tgt, self.normals_tgt
+                if verbose:
+                    print("level %d/%d: leaf %g, source %d -> %d, target %d -> %d" % (k + 1, K, leaf, len(self.cloud_src), len(src),
+                                                                                      len(self.cloud_tgt), len(tgt)), flush=True)
+                e.set_config(max_iters=iters, max_corr_dist=dist, verbose=int(verbose and k + 1 == K))
+                e.set_target(tgt, tn)
+                e.set_source(src, sn)
+                r = e.align(X)
+                self.level_results.append(r)
+                if r["status"] != OK:
+                    break
+                X = r["transform"]
+        self.last_result = r
+        if r["status"] == OK or r["iters"] > 0:
+            self._final = r["transform"]
+        return r
 
     def RegisterSymm(self):
         self.align()

@@ -14,6 +14,7 @@
  * ("todo add params to specify iters & diff", ICP/myicp.h:19).
  */
 #pragma once
+#include <vector>
 #include "stdafx.h"
 #include "symmicp.h"
 
@@ -54,6 +55,17 @@ public:
 	// the covariance eps of SYMMICP_MODE_GICP (symmicp_set_gicp_epsilon; default 1e-3): checked by align(), which returns
 	// SYMMICP_ERR_ARG unless 0 < eps <= 1
 	void setGicpEpsilon(float eps) { gicp_eps_ = eps; }
+	// pairs farther apart than d are dropped (symmicp_config.max_corr_dist; <= 0, the default: every pair is kept)
+	void setMaxCorrespondenceDistance(float d) { max_corr_dist_ = d; }
+	// Coarse-to-fine alignment.  With levels set, align() estimates (or takes) the normals of the full clouds as before, then runs
+	// one alignment per level in the order given: both clouds voxel-downsampled with the level's leaf (symmicp_ctx_voxel_downsample,
+	// normals averaged; leaf 0: the clouds as given), max_iters and max_corr_dist from the level, started from the previous level's
+	// transform (the first from the caller's guess).  The result is the last level's: source -> target in original coordinates.
+	// Coarse levels run quiet; verbose prints one line per level and the last level's iterations and Result block.
+	// SYMMICP_CORR_IDENTITY is SYMMICP_ERR_ARG with levels (the downsampled counts differ).  Empty (the default): align() as without.
+	struct VoxelLevel { float leaf; int max_iters; float max_corr_dist; };
+	void setVoxelLevels(const std::vector<VoxelLevel> &levels) { levels_ = levels; }
+	const std::vector<symmicp_result> &levelResults() const { return level_results_; }   // one per level run by the last align()
 	const symmicp_result &lastResult() const { return result_; }
 	const char *lastError() const { return error_.c_str(); }
 
@@ -74,6 +86,10 @@ private:
 	symmicp_loss loss_;
 	float loss_scale_;
 	float gicp_eps_;
+	float max_corr_dist_;
+	std::vector<VoxelLevel> levels_;
+	std::vector<symmicp_result> level_results_;
+	int alignLevels(const symmicp_config &cfg, bool source_normals, const float *guess4x4);
 	symmicp_ctx *ctx_;
 	int ctx_corr_;
 	bool ctx_no_src_normals_;            // the context holds a source set without normals (PLANE): no other mode can run on it

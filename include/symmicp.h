@@ -296,6 +296,32 @@ int symmicp_ctx_estimate_normals(symmicp_ctx *ctx, const float *xyz, size_t row_
 int symmicp_ctx_knn(symmicp_ctx *ctx, const float *xyz, size_t row_stride, size_t col_stride, size_t n, int k,
                     int32_t *rows_out, float *d2_out);
 
+/* ---- voxel-grid downsampling (PCL's pcl::VoxelGrid, Open3D's voxel_down_sample), on the GPU -----------------------
+ * Every point falls into the cubic voxel of edge `leaf` that holds it; each occupied voxel with at least min_points points
+ * becomes one output point.  The arithmetic is exact and reproducible bit for bit ("Voxel downsampling"):
+ *   inv = 1.0f / leaf; per axis lo = floorf(min * inv), hi = floorf(max * inv) over the cloud's box, n_axis = hi - lo + 1;
+ *   a point's cell ix = (int)floorf(x * inv) - lo_x (likewise iy, iz), key = ix + nx * (iy + ny * iz) (x fastest, z slowest);
+ *   output = the occupied voxels in ascending key; xyz_out = the members' fp32 sum taken one point at a time in ascending row
+ *   order, divided by (float)count; nrm_out = the members' normal sum s in the same order divided by sqrtf((sx*sx + sy*sy) +
+ *   sz*sz) when that is > 0, else (0, 0, 0).  Every op is fp32, unfused, correctly rounded.
+ * xyz and nrm strided as in symmicp_set_source (nrm may be NULL, its strides ignored then).  Outputs: xyz_out / nrm_out packed
+ * AoS [m][3], count_out [m] (points per output voxel), voxel_of [n] (the output row of every input row, -1 for the rows of
+ * voxels dropped by min_points); count_out and voxel_of may be NULL; nrm_out requires nrm.  *n_out = m.
+ * SYMMICP_ERR_SIZE when m > cap (*n_out = m is set, nothing else is written; cap >= n always suffices).
+ * SYMMICP_ERR_ARG: NULL xyz / xyz_out / n_out; n == 0 or n > 2^31 - 1; a leaf that is not finite and > 0; min_points < 1;
+ * nrm_out without nrm; non-finite coordinates; a leaf too small for the cloud (some lo or hi outside [-2^31, 2^31), or
+ * nx * ny * nz > 2^32).
+ * The ctx form runs on the context's stream and temporary arena, like symmicp_ctx_estimate_normals: the context's source,
+ * target, index and certificates stay exactly as they were.  A sharded job downsamples the FULL cloud on every rank (the
+ * output is deterministic, so all ranks get the same cloud) and hands it to symmicp_set_source, which shards it. */
+int symmicp_ctx_voxel_downsample(symmicp_ctx *ctx, const float *xyz, size_t xyz_row_stride, size_t xyz_col_stride,
+                                 const float *nrm, size_t nrm_row_stride, size_t nrm_col_stride, size_t n, float leaf, int min_points,
+                                 float *xyz_out, float *nrm_out, int32_t *count_out, int32_t *voxel_of, size_t cap, size_t *n_out);
+/* the same on a context of its own, created on `device` (-1 = current) and destroyed again */
+int symmicp_voxel_downsample(int device, const float *xyz, size_t xyz_row_stride, size_t xyz_col_stride,
+                             const float *nrm, size_t nrm_row_stride, size_t nrm_col_stride, size_t n, float leaf, int min_points,
+                             float *xyz_out, float *nrm_out, int32_t *count_out, int32_t *voxel_of, size_t cap, size_t *n_out);
+
 /* ---- multi-GPU (new: the reference is single-threaded) ----- */
 /* rank 0 creates an id, the application ships it to the other ranks (any channel),
  * then every rank calls comm_init_rank BEFORE set_source.  One RCCL all-reduce of
