@@ -94,8 +94,7 @@ void symmicp_config_default(symmicp_config *cfg)
 static int check_cfg(const symmicp_config *cfg)
 {
     if (!cfg || cfg->struct_size != (int32_t)sizeof(symmicp_config)) return SYMMICP_ERR_ARG;
-    if (cfg->mode != SYMMICP_MODE_QUIRKS && cfg->mode != SYMMICP_MODE_PAPER && cfg->mode != SYMMICP_MODE_P2P && cfg->mode != SYMMICP_MODE_PLANE &&
-        cfg->mode != SYMMICP_MODE_GICP) return SYMMICP_ERR_ARG;      // (4 is unassigned)
+    if (!mode_known(cfg->mode)) return SYMMICP_ERR_ARG;
     if (cfg->corr < SYMMICP_CORR_IDENTITY || cfg->corr > SYMMICP_CORR_TREE) return SYMMICP_ERR_ARG;
     if (cfg->apply < SYMMICP_APPLY_DEFAULT || cfg->apply > SYMMICP_APPLY_CUMULATIVE) return SYMMICP_ERR_ARG;
     if (cfg->max_iters < 0) return SYMMICP_ERR_ARG;

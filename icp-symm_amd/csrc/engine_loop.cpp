@@ -16,8 +16,7 @@ static void fill_pass_args(symmicp_ctx *c, PassArgs &a, const float Xapply[16], 
     const bool paper = c->cfg.mode != SYMMICP_MODE_QUIRKS;          // PAPER and P2P take their sums about the pivot
     for (int k = 0; k < 3; k++) a.pivot[k] = paper ? c->pivot[k] : 0.0f;
     a.p2p = c->cfg.mode == SYMMICP_MODE_P2P ? 1 : 0;
-    a.plane = c->cfg.mode == SYMMICP_MODE_PLANE ? 1 : 0;
-    a.gicp = c->cfg.mode == SYMMICP_MODE_GICP ? 1 : 0;
+    a.obj = mode_obj(c->cfg.mode);
     a.gicp_k = 1.0f - c->gicp_eps;
     a.max_d2 = c->cfg.max_corr_dist > 0.f ? c->cfg.max_corr_dist * c->cfg.max_corr_dist : 0.f;
     a.min_ndot = c->cfg.min_normal_dot;
@@ -215,7 +214,7 @@ static bool batch_eligible(const symmicp_ctx *c)
     if (c->cfg.host_loop) return false;
     if (c->external_exchange || c->shm.slots) return false;               // those exchanges run on the host
     if (c->timing == 2 || c->ix.dbg) return false;                        // per-kernel tables and debug counters: host loop
-    if (c->cfg.mode == SYMMICP_MODE_P2P) return false;                    // (3x3 SVD by Jacobi sweeps: host)
+    if (!mode_device_solves(c->cfg.mode)) return false;                   // (P2P: 3x3 SVD by Jacobi sweeps: host)
     if (c->n_loc == 0 && !c->comm) return false;                          // (an empty share of an RCCL run takes part: every input below is global,
                                                                           // and a rank that stayed in the host loop would issue a different number of all-reduces)
     if (c->host_passes_since_bailout < 2) return false;
@@ -500,10 +499,7 @@ int symmicp_step(symmicp_ctx *c, symmicp_iter_result *out)
     c->sums_exchanged = false;
     HIP_TRY(c, hipSetDevice(c->device));
     float pbar[3], qbar[3], a[3], t[3], rc = 0.f, Xi[16];
-    int st = (c->cfg.mode == SYMMICP_MODE_QUIRKS) ? solve_quirks(c->last, pbar, qbar, a, t, &rc, Xi)
-             : (c->cfg.mode == SYMMICP_MODE_PAPER) ? solve_paper(c->last, c->pivot, pbar, qbar, a, t, &rc, Xi)
-             : (c->cfg.mode == SYMMICP_MODE_PLANE || c->cfg.mode == SYMMICP_MODE_GICP) ? solve_plane(c->last, c->pivot, pbar, qbar, a, t, &rc, Xi)
-                                                   : solve_p2p(c->last, c->pivot, &rc, Xi);
+    int st = (c->cfg.mode == SYMMICP_MODE_P2P) ? solve_p2p(c->last, c->pivot, &rc, Xi) : solve_mode(c->cfg.mode, c->last, c->pivot, pbar, qbar, a, t, &rc, Xi);
     if (st != SYMMICP_OK) {
         c->err = "degenerate system (rank-deficient normal equations or non-finite transform; func.cpp:70,96)";
         fill_iter(c, out, st, rc, nullptr);
@@ -651,14 +647,11 @@ int symmicp_solve(int mode, const symmicp_sums *sums, const float pivot[3], floa
                   float t[3], float *rcond, float out16[16])
 {
     if (!sums || !pbar || !qbar || !a || !t || !out16) return SYMMICP_ERR_ARG;
-    if (mode == SYMMICP_MODE_QUIRKS) return solve_quirks(*sums, pbar, qbar, a, t, rcond, out16);
-    if (mode == SYMMICP_MODE_PAPER) return solve_paper(*sums, pivot, pbar, qbar, a, t, rcond, out16);
-    if (mode == SYMMICP_MODE_PLANE || mode == SYMMICP_MODE_GICP) return solve_plane(*sums, pivot, pbar, qbar, a, t, rcond, out16);      // (GICP's record has PLANE's shape)
     if (mode == SYMMICP_MODE_P2P) {
         for (int k = 0; k < 3; k++) pbar[k] = qbar[k] = a[k] = t[k] = 0.f;
         return solve_p2p(*sums, pivot, rcond, out16);
     }
-    return SYMMICP_ERR_ARG;
+    return mode_device_solves(mode) ? solve_mode(mode, *sums, pivot, pbar, qbar, a, t, rcond, out16) : SYMMICP_ERR_ARG;
 }
 
 // ---- test entry points of the device-driven loop ----
@@ -666,8 +659,7 @@ int symmicp_ctx_solve_probe(symmicp_ctx *c, int mode, int exact_rc, const symmic
                             int32_t *status, float *pbar, float *qbar, float *a, float *t, float *rcond, float *out16, float *X_out16)
 {
     if (!c) return SYMMICP_ERR_ARG;
-    if (mode != SYMMICP_MODE_QUIRKS && mode != SYMMICP_MODE_PAPER && mode != SYMMICP_MODE_PLANE && mode != SYMMICP_MODE_GICP)
-        return fail(c, SYMMICP_ERR_ARG, "probe: QUIRKS, PAPER, PLANE or GICP");
+    if (!mode_device_solves(mode)) return fail(c, SYMMICP_ERR_ARG, "probe: QUIRKS, PAPER, PLANE or GICP");
     if (!sums || n == 0 || n > (1u << 24) || !status || !pbar || !qbar || !a || !t || !rcond || !out16 || (X_in16 && !X_out16))
         return fail(c, SYMMICP_ERR_ARG, "probe: bad arguments");
     HIP_TRY(c, hipSetDevice(c->device));
@@ -707,8 +699,7 @@ int symmicp_ctx_loop_solve(symmicp_ctx *c, const symmicp_sums *sums, const float
     if (!sums || !X_in16 || !in_i || !in_f || !state_out || !X_out16 || !Xapply_out12 || !ring_inc16 || !ring_X16 || !ring_rcond || !ring_i2)
         return fail(c, SYMMICP_ERR_ARG, "loop_solve: bad arguments");
     const int mode = in_i[0];
-    if (mode != SYMMICP_MODE_QUIRKS && mode != SYMMICP_MODE_PAPER && mode != SYMMICP_MODE_PLANE && mode != SYMMICP_MODE_GICP)
-        return fail(c, SYMMICP_ERR_ARG, "loop_solve: QUIRKS, PAPER, PLANE or GICP");
+    if (!mode_device_solves(mode)) return fail(c, SYMMICP_ERR_ARG, "loop_solve: QUIRKS, PAPER, PLANE or GICP");
     HIP_TRY(c, hipSetDevice(c->device));
     LoopConfig lc{};
     lc.mode = mode; lc.fixed_iters = in_i[1]; lc.max_iters = in_i[2]; lc.incremental = in_i[5] ? 1 : 0; lc.tree = 0;

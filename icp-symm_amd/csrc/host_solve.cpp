@@ -6,19 +6,9 @@
 
 namespace symmicp {
 
-int solve_quirks(const symmicp_sums &S, float pbar[3], float qbar[3], float a[3], float t[3], float *rcond, float out16[16])
+int solve_mode(int mode, const symmicp_sums &S, const float pivot[3], float pbar[3], float qbar[3], float a[3], float t[3], float *rcond, float out16[16])
 {
-    return solve::solve_quirks(S, pbar, qbar, a, t, rcond, out16);
-}
-
-int solve_paper(const symmicp_sums &S, const float pivot[3], float pbar[3], float qbar[3], float a[3], float t[3], float *rcond, float out16[16])
-{
-    return solve::solve_paper(S, pivot, pbar, qbar, a, t, rcond, out16);
-}
-
-int solve_plane(const symmicp_sums &S, const float pivot[3], float pbar[3], float qbar[3], float a[3], float t[3], float *rcond, float out16[16])
-{
-    return solve::solve_plane(S, pivot, pbar, qbar, a, t, rcond, out16);
+    return solve::solve_mode(mode, S, pivot, pbar, qbar, a, t, rcond, out16);
 }
 
 int solve_p2p(const symmicp_sums &S, const float pivot[3], float *rcond, float out16[16])

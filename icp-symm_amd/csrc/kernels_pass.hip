@@ -15,6 +15,7 @@
 // keep the association written: the CPU oracle uses the same expressions, so
 // nearest-neighbour choices compare bit for bit.
 #include <cstdlib>
+#include <type_traits>
 #include "symmicp_internal.h"
 #include "device_common.h"
 #include "oct_walk.h"
@@ -44,70 +45,51 @@ __device__ __forceinline__ void acc_zero(AccN<NA> &a)
     for (int k = 0; k < NA; k++) a.v[k] = 0.0;
 }
 
-// rows of func.cpp:51-58 for one pair, accumulated in fp64
-__device__ __forceinline__ void acc_pair(Acc &a, float px, float py, float pz, float npx, float npy, float npz,
-                                         float qx, float qy, float qz, float nqx, float nqy, float nqz,
-                                         float d2, const float *pivot, int p2p)
+// One row v with residual c at weight w (1 in an unweighted record: 1 x = x and fma(1, x, s) = s + x exactly) into the Gram (slots
+// 0..20, upper triangle row by row), the right-hand side (21..26) and the cost (35)
+template <int NA>
+__device__ __forceinline__ void acc_row(AccN<NA> &a, const double v[6], double c, double w)
 {
+    const double wc = w * c;
+    int k = 0;
+#pragma unroll
+    for (int r = 0; r < 6; r++) {
+        const double wv = w * v[r];
+#pragma unroll
+        for (int s = r; s < 6; s++) { a.v[k] = __builtin_fma(wv, v[s], a.v[k]); k++; }
+    }
+#pragma unroll
+    for (int r = 0; r < 6; r++) a.v[21 + r] = __builtin_fma(v[r], wc, a.v[21 + r]);
+    a.v[35] = __builtin_fma(wc, c, a.v[35]);
+}
+
+// The per-pair slots of the row-based records: the weighted sums of p and q (27..32), sqrt(d2) (33), the weight (34), d2 (36) and, in
+// the weighted record (NA = kNAccW), the pair count (37)
+template <int NA>
+__device__ __forceinline__ void acc_pair_sums(AccN<NA> &a, float px, float py, float pz, float qx, float qy, float qz, float d2, double w)
+{
+    a.v[27] = __builtin_fma(w, (double)px, a.v[27]); a.v[28] = __builtin_fma(w, (double)py, a.v[28]); a.v[29] = __builtin_fma(w, (double)pz, a.v[29]);
+    a.v[30] = __builtin_fma(w, (double)qx, a.v[30]); a.v[31] = __builtin_fma(w, (double)qy, a.v[31]); a.v[32] = __builtin_fma(w, (double)qz, a.v[32]);
+    a.v[33] += (double)sqrtf(d2);                                      // func.cpp:28
+    a.v[34] += w;
+    a.v[36] += (double)d2;
+    if constexpr (NA == kNAccW) a.v[37] += 1.0;
+}
+
+// rows of func.cpp:51-58 for one pair, accumulated in fp64.  In the weighted record (NA = kNAccW) the pair is weighted by its robust-loss
+// weight w (robust_loss.h) of r = c (PAPER) or |p - q| (P2P): every sum but 33 and 36 is scaled by w, slot 34 sums w, slot 37 counts the pairs
+template <int NA>
+__device__ __forceinline__ void acc_pair(AccN<NA> &a, float px, float py, float pz, float npx, float npy, float npz,
+                                         float qx, float qy, float qz, float nqx, float nqy, float nqz,
+                                         float d2, const float *pivot, int p2p, int loss, float scale)
+{
+    constexpr bool W = NA == kNAccW;
     px -= pivot[0]; py -= pivot[1]; pz -= pivot[2];
     qx -= pivot[0]; qy -= pivot[1]; qz -= pivot[2];
     if (p2p) {
         // point-to-point (regist.h:52): 3x3 cross-covariance sums, row-major in slots 0..8
-        const double P[3] = {(double)px, (double)py, (double)pz}, Q[3] = {(double)qx, (double)qy, (double)qz};
-#pragma unroll
-        for (int r = 0; r < 3; r++)
-#pragma unroll
-            for (int c = 0; c < 3; c++) a.v[3 * r + c] = __builtin_fma(P[r], Q[c], a.v[3 * r + c]);
-        a.v[27] += P[0]; a.v[28] += P[1]; a.v[29] += P[2];
-        a.v[30] += Q[0]; a.v[31] += Q[1]; a.v[32] += Q[2];
-        a.v[33] += (double)sqrtf(d2);
-        a.v[34] += 1.0;
-        a.v[36] += (double)d2;
-        return;
-    }
-    float nx = npx + nqx, ny = npy + nqy, nz = npz + nqz;            // func.cpp:51
-    float sx = px + qx, sy = py + qy, sz = pz + qz;
-    float dx = px - qx, dy = py - qy, dz = pz - qz;
-    float m0 = sy * nz - sz * ny;                                      // func.cpp:54
-    float m1 = sz * nx - sx * nz;
-    float m2 = sx * ny - sy * nx;
-    float c = (dx * nx + dy * ny) + dz * nz;                           // func.cpp:58
-    double v[6] = {(double)m0, (double)m1, (double)m2, (double)nx, (double)ny, (double)nz};
-    int k = 0;
-#pragma unroll
-    for (int r = 0; r < 6; r++)
-#pragma unroll
-        for (int s = r; s < 6; s++) { a.v[k] = __builtin_fma(v[r], v[s], a.v[k]); k++; }
-    double cd = (double)c;
-#pragma unroll
-    for (int r = 0; r < 6; r++) a.v[21 + r] = __builtin_fma(v[r], cd, a.v[21 + r]);
-    a.v[27] += (double)px; a.v[28] += (double)py; a.v[29] += (double)pz;
-    a.v[30] += (double)qx; a.v[31] += (double)qy; a.v[32] += (double)qz;
-    a.v[33] += (double)sqrtf(d2);                                      // func.cpp:28
-    a.v[34] += 1.0;
-    a.v[35] = __builtin_fma(cd, cd, a.v[35]);
-    a.v[36] += (double)d2;
-}
-
-// the kernels call one signature for both instantiations: the unweighted record ignores the loss
-__device__ __forceinline__ void acc_pair(Acc &a, float px, float py, float pz, float npx, float npy, float npz,
-                                         float qx, float qy, float qz, float nqx, float nqy, float nqz,
-                                         float d2, const float *pivot, int p2p, int, float)
-{
-    acc_pair(a, px, py, pz, npx, npy, npz, qx, qy, qz, nqx, nqy, nqz, d2, pivot, p2p);
-}
-
-// the same rows with the pair weighted by its robust-loss weight w (robust_loss.h) of r = c (PAPER) or |p - q| (P2P): every sum but
-// 33 and 36 is scaled by w, slot 34 sums w, slot 37 counts the pairs
-__device__ __forceinline__ void acc_pair(AccN<kNAccW> &a, float px, float py, float pz, float npx, float npy, float npz,
-                                         float qx, float qy, float qz, float nqx, float nqy, float nqz,
-                                         float d2, const float *pivot, int p2p, int loss, float scale)
-{
-    px -= pivot[0]; py -= pivot[1]; pz -= pivot[2];
-    qx -= pivot[0]; qy -= pivot[1]; qz -= pivot[2];
-    if (p2p) {
         const float dist = sqrtf(d2);
-        const double w = (double)robust_weight(loss, scale, dist);
+        const double w = W ? (double)robust_weight(loss, scale, dist) : 1.0;
         const double P[3] = {(double)px, (double)py, (double)pz}, Q[3] = {(double)qx, (double)qy, (double)qz};
         const double WP[3] = {w * P[0], w * P[1], w * P[2]};
 #pragma unroll
@@ -119,35 +101,20 @@ __device__ __forceinline__ void acc_pair(AccN<kNAccW> &a, float px, float py, fl
         a.v[33] += (double)dist;
         a.v[34] += w;
         a.v[36] += (double)d2;
-        a.v[37] += 1.0;
+        if constexpr (W) a.v[37] += 1.0;
         return;
     }
-    float nx = npx + nqx, ny = npy + nqy, nz = npz + nqz;
+    float nx = npx + nqx, ny = npy + nqy, nz = npz + nqz;            // func.cpp:51
     float sx = px + qx, sy = py + qy, sz = pz + qz;
     float dx = px - qx, dy = py - qy, dz = pz - qz;
-    float m0 = sy * nz - sz * ny;
+    float m0 = sy * nz - sz * ny;                                      // func.cpp:54
     float m1 = sz * nx - sx * nz;
     float m2 = sx * ny - sy * nx;
-    float c = (dx * nx + dy * ny) + dz * nz;
-    const double w = (double)robust_weight(loss, scale, c);
+    float c = (dx * nx + dy * ny) + dz * nz;                           // func.cpp:58
+    const double w = W ? (double)robust_weight(loss, scale, c) : 1.0;
     const double v[6] = {(double)m0, (double)m1, (double)m2, (double)nx, (double)ny, (double)nz};
-    const double cd = (double)c, wc = w * cd;
-    int k = 0;
-#pragma unroll
-    for (int r = 0; r < 6; r++) {
-        const double wv = w * v[r];
-#pragma unroll
-        for (int s = r; s < 6; s++) { a.v[k] = __builtin_fma(wv, v[s], a.v[k]); k++; }
-    }
-#pragma unroll
-    for (int r = 0; r < 6; r++) a.v[21 + r] = __builtin_fma(v[r], wc, a.v[21 + r]);
-    a.v[27] = __builtin_fma(w, (double)px, a.v[27]); a.v[28] = __builtin_fma(w, (double)py, a.v[28]); a.v[29] = __builtin_fma(w, (double)pz, a.v[29]);
-    a.v[30] = __builtin_fma(w, (double)qx, a.v[30]); a.v[31] = __builtin_fma(w, (double)qy, a.v[31]); a.v[32] = __builtin_fma(w, (double)qz, a.v[32]);
-    a.v[33] += (double)sqrtf(d2);
-    a.v[34] += w;
-    a.v[35] = __builtin_fma(wc, cd, a.v[35]);
-    a.v[36] += (double)d2;
-    a.v[37] += 1.0;
+    acc_row(a, v, (double)c, w);
+    acc_pair_sums(a, px, py, pz, qx, qy, qz, d2, w);
 }
 
 // PLANE (point-to-plane): PAPER's slots with n_p = 0 and s = p + q replaced by p -- rows v = (p x n_q, n_q), c = (p - q) . n_q -- and,
@@ -156,7 +123,6 @@ template <int NA>
 __device__ __forceinline__ void acc_plane(AccN<NA> &a, float px, float py, float pz, float qx, float qy, float qz,
                                           float nx, float ny, float nz, float d2, const float *pivot, int loss, float scale)
 {
-    constexpr bool W = NA == kNAccW;
     px -= pivot[0]; py -= pivot[1]; pz -= pivot[2];
     qx -= pivot[0]; qy -= pivot[1]; qz -= pivot[2];
     float dx = px - qx, dy = py - qy, dz = pz - qz;
@@ -164,40 +130,10 @@ __device__ __forceinline__ void acc_plane(AccN<NA> &a, float px, float py, float
     float m1 = pz * nx - px * nz;
     float m2 = px * ny - py * nx;
     float c = (dx * nx + dy * ny) + dz * nz;
+    const double w = NA == kNAccW ? (double)robust_weight(loss, scale, c) : 1.0;
     const double v[6] = {(double)m0, (double)m1, (double)m2, (double)nx, (double)ny, (double)nz};
-    const double cd = (double)c;
-    if constexpr (W) {
-        const double w = (double)robust_weight(loss, scale, c), wc = w * cd;
-        int k = 0;
-#pragma unroll
-        for (int r = 0; r < 6; r++) {
-            const double wv = w * v[r];
-#pragma unroll
-            for (int s = r; s < 6; s++) { a.v[k] = __builtin_fma(wv, v[s], a.v[k]); k++; }
-        }
-#pragma unroll
-        for (int r = 0; r < 6; r++) a.v[21 + r] = __builtin_fma(v[r], wc, a.v[21 + r]);
-        a.v[27] = __builtin_fma(w, (double)px, a.v[27]); a.v[28] = __builtin_fma(w, (double)py, a.v[28]); a.v[29] = __builtin_fma(w, (double)pz, a.v[29]);
-        a.v[30] = __builtin_fma(w, (double)qx, a.v[30]); a.v[31] = __builtin_fma(w, (double)qy, a.v[31]); a.v[32] = __builtin_fma(w, (double)qz, a.v[32]);
-        a.v[34] += w;
-        a.v[35] = __builtin_fma(wc, cd, a.v[35]);
-        a.v[37] += 1.0;
-    } else {
-        (void)loss; (void)scale;
-        int k = 0;
-#pragma unroll
-        for (int r = 0; r < 6; r++)
-#pragma unroll
-            for (int s = r; s < 6; s++) { a.v[k] = __builtin_fma(v[r], v[s], a.v[k]); k++; }
-#pragma unroll
-        for (int r = 0; r < 6; r++) a.v[21 + r] = __builtin_fma(v[r], cd, a.v[21 + r]);
-        a.v[27] += (double)px; a.v[28] += (double)py; a.v[29] += (double)pz;
-        a.v[30] += (double)qx; a.v[31] += (double)qy; a.v[32] += (double)qz;
-        a.v[34] += 1.0;
-        a.v[35] = __builtin_fma(cd, cd, a.v[35]);
-    }
-    a.v[33] += (double)sqrtf(d2);
-    a.v[36] += (double)d2;
+    acc_row(a, v, (double)c, w);
+    acc_pair_sums(a, px, py, pz, qx, qy, qz, d2, w);
 }
 
 // GICP (plane-to-plane, Segal et al. 2009): the pair's cost d^T M d with M = (C_p + C_q)^-1, C_x = I - k x x^T, k = 1 - eps, a = the
@@ -211,7 +147,6 @@ template <int NA>
 __device__ __forceinline__ void acc_gicp(AccN<NA> &a, float px, float py, float pz, float ax, float ay, float az, float qx, float qy, float qz,
                                          float bx, float by, float bz, float d2, const float *pivot, float gk, int loss, float scale)
 {
-    constexpr bool W = NA == kNAccW;
     px -= pivot[0]; py -= pivot[1]; pz -= pivot[2];
     qx -= pivot[0]; qy -= pivot[1]; qz -= pivot[2];
     const float dx = px - qx, dy = py - qy, dz = pz - qz;
@@ -223,41 +158,15 @@ __device__ __forceinline__ void acc_gicp(AccN<NA> &a, float px, float py, float 
     const float cu = (dx * ux + dy * uy) + dz * uz;
     const float cv = (dx * vx + dy * vy) + dz * vz;
     double w = 1.0;
-    if constexpr (W) {
+    if constexpr (NA == kNAccW) {
         const float dd = (dx * dx + dy * dy) + dz * dz;
         w = (double)robust_weight(loss, scale, sqrtf((0.5f * dd + (gu * cu) * cu) + (gv * cv) * cv));
-    } else {
-        (void)loss; (void)scale;
     }
     // the u row, then the v row
-    {
-        const double V[6] = {(double)(py * uz - pz * uy), (double)(pz * ux - px * uz), (double)(px * uy - py * ux), (double)ux, (double)uy, (double)uz};
-        const double wg = w * (double)gu, wc = wg * (double)cu;
-        int k = 0;
-#pragma unroll
-        for (int r = 0; r < 6; r++) {
-            const double wv = wg * V[r];
-#pragma unroll
-            for (int s = r; s < 6; s++) { a.v[k] = __builtin_fma(wv, V[s], a.v[k]); k++; }
-        }
-#pragma unroll
-        for (int r = 0; r < 6; r++) a.v[21 + r] = __builtin_fma(V[r], wc, a.v[21 + r]);
-        a.v[35] = __builtin_fma(wc, (double)cu, a.v[35]);
-    }
-    {
-        const double V[6] = {(double)(py * vz - pz * vy), (double)(pz * vx - px * vz), (double)(px * vy - py * vx), (double)vx, (double)vy, (double)vz};
-        const double wg = w * (double)gv, wc = wg * (double)cv;
-        int k = 0;
-#pragma unroll
-        for (int r = 0; r < 6; r++) {
-            const double wv = wg * V[r];
-#pragma unroll
-            for (int s = r; s < 6; s++) { a.v[k] = __builtin_fma(wv, V[s], a.v[k]); k++; }
-        }
-#pragma unroll
-        for (int r = 0; r < 6; r++) a.v[21 + r] = __builtin_fma(V[r], wc, a.v[21 + r]);
-        a.v[35] = __builtin_fma(wc, (double)cv, a.v[35]);
-    }
+    const double U[6] = {(double)(py * uz - pz * uy), (double)(pz * ux - px * uz), (double)(px * uy - py * ux), (double)ux, (double)uy, (double)uz};
+    acc_row(a, U, (double)cu, w * (double)gu);
+    const double V[6] = {(double)(py * vz - pz * vy), (double)(pz * vx - px * vz), (double)(px * vy - py * vx), (double)vx, (double)vy, (double)vz};
+    acc_row(a, V, (double)cv, w * (double)gv);
     // the axis rows: 1/2 J^T J = 1/2 [[|p|^2 I - p p^T, [p]x], [[p]x^T, I]] and 1/2 J^T d = 1/2 (p x d, d)
     const double Px = px, Py = py, Pz = pz, Dx = dx, Dy = dy, Dz = dz;
     const double hw = 0.5 * w, hx = hw * Px, hy = hw * Py, hz = hw * Pz;
@@ -276,17 +185,12 @@ __device__ __forceinline__ void acc_gicp(AccN<NA> &a, float px, float py, float 
     a.v[23] = __builtin_fma(hx, Dy, __builtin_fma(-hy, Dx, a.v[23]));
     a.v[24] = __builtin_fma(hw, Dx, a.v[24]); a.v[25] = __builtin_fma(hw, Dy, a.v[25]); a.v[26] = __builtin_fma(hw, Dz, a.v[26]);
     a.v[35] = __builtin_fma(hw, __builtin_fma(Dz, Dz, __builtin_fma(Dy, Dy, Dx * Dx)), a.v[35]);
-    a.v[27] = __builtin_fma(w, Px, a.v[27]); a.v[28] = __builtin_fma(w, Py, a.v[28]); a.v[29] = __builtin_fma(w, Pz, a.v[29]);
-    a.v[30] = __builtin_fma(w, (double)qx, a.v[30]); a.v[31] = __builtin_fma(w, (double)qy, a.v[31]); a.v[32] = __builtin_fma(w, (double)qz, a.v[32]);
-    a.v[33] += (double)sqrtf(d2);
-    a.v[34] += w;
-    a.v[36] += (double)d2;
-    if constexpr (W) a.v[37] += 1.0;
+    acc_pair_sums(a, px, py, pz, qx, qy, qz, d2, w);
 }
 
-// The record of an accumulating kernel's instantiation (its OBJ parameter): the symmetric rows of PAPER / QUIRKS / P2P (acc_pair), PLANE's
-// (acc_plane) or GICP's (acc_gicp).  Separate instantiations, not a branch, as W: each kernel keeps the registers its own record needs.
-constexpr int kObjSym = 0, kObjPlane = 1, kObjGicp = 2;
+// The record of an accumulating kernel's instantiation (its OBJ parameter, PassArgs::obj): the symmetric rows of PAPER / QUIRKS / P2P
+// (acc_pair), PLANE's (acc_plane) or GICP's (acc_gicp).  Separate instantiations, not a branch, as W: each kernel keeps the registers its
+// own record needs.
 template <int OBJ, int NA>
 __device__ __forceinline__ void acc_obj(AccN<NA> &acc, float px, float py, float pz, float npx, float npy, float npz, float qx, float qy, float qz,
                                         float nqx, float nqy, float nqz, float d2, const float *pivot, int p2p, float gk, int loss, float scale)
@@ -294,6 +198,48 @@ __device__ __forceinline__ void acc_obj(AccN<NA> &acc, float px, float py, float
     if constexpr (OBJ == kObjPlane) acc_plane(acc, px, py, pz, qx, qy, qz, nqx, nqy, nqz, d2, pivot, loss, scale);
     else if constexpr (OBJ == kObjGicp) acc_gicp(acc, px, py, pz, npx, npy, npz, qx, qy, qz, nqx, nqy, nqz, d2, pivot, gk, loss, scale);
     else acc_pair(acc, px, py, pz, npx, npy, npz, qx, qy, qz, nqx, nqy, nqz, d2, pivot, p2p, loss, scale);
+}
+
+// What the pair step reads of the pass's arguments.  k_pass_fused fills it through in_vgpr (see there); the other kernels take it as
+// it is (hot_params).
+struct HotParams {
+    Affine X;
+    float pivot[3];
+    float max_d2, min_ndot;
+    int32_t p2p;
+    int32_t loss;            // (set and read by the weighted instantiation only)
+    float loss_scale;
+    float gicp_k;            // (set and read by the GICP instantiation only)
+};
+
+__device__ __forceinline__ HotParams hot_params(const PassArgs &a)
+{
+    HotParams h;
+    h.X = a.X;
+#pragma unroll
+    for (int k = 0; k < 3; k++) h.pivot[k] = a.pivot[k];
+    h.max_d2 = a.max_d2; h.min_ndot = a.min_ndot;
+    h.p2p = a.p2p; h.loss = a.loss; h.loss_scale = a.loss_scale; h.gicp_k = a.gicp_k;
+    return h;
+}
+
+// Does an instantiation read the source normals?  Every record but PLANE's uses them; PLANE's reads them only to write them back or to
+// gate on them (min_normal_dot).
+template <int OBJ>
+__device__ __forceinline__ bool reads_src_normals(bool writeback, float min_ndot) { return OBJ != kObjPlane || writeback || min_ndot > -1.0f; }
+
+// The pair step of every accumulating kernel: the gates (max_correspondence_distance, then min_normal_dot), then the record.  (nx, ny, nz)
+// is the source normal as stored (zeros where the instantiation does not read it); it is moved here, for the gate and the rows (PLANE's
+// rows do not read it: there the compiler keeps it to the gate).
+template <int OBJ, int NA>
+__device__ __forceinline__ void pair_step(AccN<NA> &acc, const HotParams &h, float nx, float ny, float nz, float px, float py, float pz,
+                                          const float4 &q, const float4 &nq, float d2)
+{
+    if (h.max_d2 > 0.0f && d2 > h.max_d2) return;
+    const Affine &X = h.X;
+    const float npx = xf_row(X.m + 0, nx, ny, nz, X.nrm_w), npy = xf_row(X.m + 4, nx, ny, nz, X.nrm_w), npz = xf_row(X.m + 8, nx, ny, nz, X.nrm_w);
+    if (h.min_ndot > -1.0f && (npx * nq.x + npy * nq.y) + npz * nq.z < h.min_ndot) return;
+    acc_obj<OBJ>(acc, px, py, pz, npx, npy, npz, q.x, q.y, q.z, nq.x, nq.y, nq.z, d2, h.pivot, h.p2p, h.gicp_k, h.loss, h.loss_scale);
 }
 
 // one step of a sum on the VALU's DPP cross-lane network (no LDS traffic): row_shr 1,2,4,8 builds 16-lane row sums.  A double moves
@@ -330,7 +276,7 @@ __device__ __forceinline__ double swap16_add(double a, double b)
 // [k][block], so that the reduce could read along the blocks: 40 scattered 8-byte stores per block into lines shared with up to 15
 // other blocks -- on other XCDs, i.e. other L2s -- and a reduce whose load phase alone took 5.9 us of k_reduce_solve's 11.5.)
 template <int NA>
-__device__ __forceinline__ void acc_block_reduce_store(AccN<NA> &a, double *partials, uint32_t nblocks, uint32_t col)
+__device__ __forceinline__ void acc_block_reduce_store(AccN<NA> &a, double *partials, uint32_t col)
 {
     // (value 37 of the weighted record rides in the upper half-wave of h1[17], then in row 3 of h2[7])
     static_assert(kNSum == 40 && NA <= 40, "the halving below pairs value k with k + 20, then k + 10");
@@ -359,11 +305,7 @@ __device__ __forceinline__ void acc_block_reduce_store(AccN<NA> &a, double *part
         }
         partials[(size_t)col * kNSum + threadIdx.x] = s;
     }
-    (void)nblocks;
 }
-
-template <int NA>
-__device__ __forceinline__ void acc_block_reduce_store(AccN<NA> &a, double *partials, uint32_t nblocks) { acc_block_reduce_store(a, partials, nblocks, blockIdx.x); }
 
 // ---------------------------------------------------------------------------
 // pass, identity pairing (what the reference does: myicp.cpp:130)
@@ -380,7 +322,8 @@ __global__ __launch_bounds__(kPassThreads) void k_pass_identity(PassArgs a_in, C
     PassArgs a = a_in;
     if (a_in.loop) a.X = a_in.loop->Xapply;        // device-driven loop: the transform k_reduce_solve left behind
     AccT<W> acc; acc_zero(acc);
-    const bool need_n = OBJ != kObjPlane || a.writeback || a.min_ndot > -1.0f;
+    const HotParams h = hot_params(a);
+    const bool need_n = reads_src_normals<OBJ>(a.writeback, a.min_ndot);
     const uint32_t stride = gridDim.x * blockDim.x * VEC;
     for (uint32_t i0 = (blockIdx.x * blockDim.x + threadIdx.x) * VEC; i0 < a.n; i0 += stride) {
         float x[VEC], y[VEC], z[VEC], nx[VEC], ny[VEC], nz[VEC], qx[VEC], qy[VEC], qz[VEC], qnx[VEC], qny[VEC], qnz[VEC];
@@ -437,13 +380,10 @@ __global__ __launch_bounds__(kPassThreads) void k_pass_identity(PassArgs a_in, C
             else a.d2_out[i0] = d2[0];
         }
 #pragma unroll
-        for (int k = 0; k < VEC; k++) {
-            if (a.max_d2 > 0.0f && d2[k] > a.max_d2) continue;
-            if (a.min_ndot > -1.0f && (npx[k] * qnx[k] + npy[k] * qny[k]) + npz[k] * qnz[k] < a.min_ndot) continue;
-            acc_obj<OBJ>(acc, px[k], py[k], pz[k], npx[k], npy[k], npz[k], qx[k], qy[k], qz[k], qnx[k], qny[k], qnz[k], d2[k], a.pivot, a.p2p, a.gicp_k, a.loss, a.loss_scale);
-        }
+        for (int k = 0; k < VEC; k++)
+            pair_step<OBJ>(acc, h, nx[k], ny[k], nz[k], px[k], py[k], pz[k], make_float4(qx[k], qy[k], qz[k], 0.0f), make_float4(qnx[k], qny[k], qnz[k], 0.0f), d2[k]);
     }
-    acc_block_reduce_store(acc, a.partials, gridDim.x);
+    acc_block_reduce_store(acc, a.partials, blockIdx.x);
 }
 
 // ---------------------------------------------------------------------------
@@ -454,18 +394,18 @@ template <bool W, int OBJ>
 __global__ __launch_bounds__(kPassThreads) void k_pass_indexed(PassArgs a, const float4 *__restrict__ tn)
 {
     AccT<W> acc; acc_zero(acc);
-    const bool need_n = OBJ != kObjPlane || a.writeback || a.min_ndot > -1.0f;
+    const HotParams h = hot_params(a);
+    const bool need_n = reads_src_normals<OBJ>(a.writeback, a.min_ndot);
     const uint32_t stride = gridDim.x * blockDim.x;
     for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < a.n; i += stride) {
         float x = a.in.x[i], y = a.in.y[i], z = a.in.z[i];
         float nx = 0.0f, ny = 0.0f, nz = 0.0f;
         if (need_n) { nx = a.in.nx[i]; ny = a.in.ny[i]; nz = a.in.nz[i]; }
         float px = xf_row(a.X.m + 0, x, y, z, 1.0f), py = xf_row(a.X.m + 4, x, y, z, 1.0f), pz = xf_row(a.X.m + 8, x, y, z, 1.0f);
-        float npx = xf_row(a.X.m + 0, nx, ny, nz, a.X.nrm_w), npy = xf_row(a.X.m + 4, nx, ny, nz, a.X.nrm_w),
-              npz = xf_row(a.X.m + 8, nx, ny, nz, a.X.nrm_w);
         if (a.writeback) {
             a.out.x[i] = px; a.out.y[i] = py; a.out.z[i] = pz;
-            a.out.nx[i] = npx; a.out.ny[i] = npy; a.out.nz[i] = npz;
+            a.out.nx[i] = xf_row(a.X.m + 0, nx, ny, nz, a.X.nrm_w); a.out.ny[i] = xf_row(a.X.m + 4, nx, ny, nz, a.X.nrm_w);
+            a.out.nz[i] = xf_row(a.X.m + 8, nx, ny, nz, a.X.nrm_w);
         }
         unsigned long long b = a.best64[i];
         uint32_t j = (uint32_t)(b & 0xFFFFFFFFull);
@@ -474,12 +414,10 @@ __global__ __launch_bounds__(kPassThreads) void k_pass_indexed(PassArgs a, const
         if (a.pos_out) a.pos_out[i] = ok ? (int32_t)j : -1;
         if (a.d2_out) a.d2_out[i] = ok ? d2 : __int_as_float(0x7f800000);
         if (!ok) continue;
-        if (a.max_d2 > 0.0f && d2 > a.max_d2) continue;
-        const float4 q = tn[2 * (size_t)j], nq = tn[2 * (size_t)j + 1];     // one 32-byte pair record
-        if (a.min_ndot > -1.0f && (npx * nq.x + npy * nq.y) + npz * nq.z < a.min_ndot) continue;
-        acc_obj<OBJ>(acc, px, py, pz, npx, npy, npz, q.x, q.y, q.z, nq.x, nq.y, nq.z, d2, a.pivot, a.p2p, a.gicp_k, a.loss, a.loss_scale);
+        if (a.max_d2 > 0.0f && d2 > a.max_d2) continue;                  // (pair_step's gate, ahead of the gather it saves)
+        pair_step<OBJ>(acc, h, nx, ny, nz, px, py, pz, tn[2 * (size_t)j], tn[2 * (size_t)j + 1], d2);      // one 32-byte pair record
     }
-    acc_block_reduce_store(acc, a.partials, gridDim.x);
+    acc_block_reduce_store(acc, a.partials, blockIdx.x);
 }
 
 // ---------------------------------------------------------------------------
@@ -1053,7 +991,7 @@ __global__ __launch_bounds__(kPassThreads) void k_search_cells(PassArgs a, Targe
 // ---------------------------------------------------------------------------
 constexpr int kFusedList = 2048;      // (room for the uncertified points of several 256-point tiles between two flushes)
 
-// What the streaming loop of k_pass_fused needs of its arguments, held in VECTOR registers.  The kernel's three argument structs are ~150
+// k_pass_fused holds what its streaming loop needs of its arguments (HotParams) in VECTOR registers.  The kernel's three argument structs are ~150
 // scalars, all live across the loop (the scan behind it needs them); with 102 scalar registers per wave the compiler parked them in the
 // lanes of a vector register and fetched them back one v_readlane at a time: 85 of the loop's 291 vector instructions per tile.  Values
 // that pass through in_vgpr are opaque to it: they stay where they are (and VGPR operands issue faster than scalar ones).
@@ -1070,35 +1008,6 @@ __device__ __forceinline__ __attribute__((address_space(1))) T *gcol(unsigned lo
     return (__attribute__((address_space(1))) T *)base;
 }
 __device__ __forceinline__ float4 as_float4(f32x4_t v) { return make_float4(v.x, v.y, v.z, v.w); }
-struct HotParams {
-    Affine X;
-    float pivot[3];
-    float max_d2, min_ndot;
-    int32_t p2p;
-    int32_t loss;            // (set and read by the weighted instantiation only)
-    float loss_scale;
-    float gicp_k;            // (set and read by the GICP instantiation only)
-};
-
-template <int OBJ, int NA>
-__device__ __forceinline__ void fused_accumulate(AccN<NA> &acc, const HotParams &h, float nx, float ny, float nz, float px, float py, float pz,
-                                                 const float4 &q, const float4 &nq, float d2)
-{
-    const Affine &X = h.X;
-    if (OBJ == kObjPlane) {      // (the source normal only for the gate: the rows do not use it)
-        if (h.max_d2 > 0.0f && d2 > h.max_d2) return;
-        if (h.min_ndot > -1.0f) {
-            const float npx = xf_row(X.m + 0, nx, ny, nz, X.nrm_w), npy = xf_row(X.m + 4, nx, ny, nz, X.nrm_w), npz = xf_row(X.m + 8, nx, ny, nz, X.nrm_w);
-            if ((npx * nq.x + npy * nq.y) + npz * nq.z < h.min_ndot) return;
-        }
-        acc_plane(acc, px, py, pz, q.x, q.y, q.z, nq.x, nq.y, nq.z, d2, h.pivot, h.loss, h.loss_scale);
-        return;
-    }
-    const float npx = xf_row(X.m + 0, nx, ny, nz, X.nrm_w), npy = xf_row(X.m + 4, nx, ny, nz, X.nrm_w), npz = xf_row(X.m + 8, nx, ny, nz, X.nrm_w);
-    if (h.max_d2 > 0.0f && d2 > h.max_d2) return;
-    if (h.min_ndot > -1.0f && (npx * nq.x + npy * nq.y) + npz * nq.z < h.min_ndot) return;
-    acc_obj<OBJ>(acc, px, py, pz, npx, npy, npz, q.x, q.y, q.z, nq.x, nq.y, nq.z, d2, h.pivot, h.p2p, h.gicp_k, h.loss, h.loss_scale);
-}
 
 #ifndef FUSED_WAVES
 #define FUSED_WAVES 2
@@ -1120,7 +1029,7 @@ __global__ __launch_bounds__(kPassThreads, ACC ? FUSED_WAVES : COMPACT_WAVES) vo
 {
     static_assert(ACC || !W, "the search-only form has no sums to weight");
     static_assert(ACC || OBJ == kObjSym, "the search-only form has no rows");
-    const bool need_n = OBJ != kObjPlane || a.min_ndot > -1.0f;      // (no write-back here)
+    const bool need_n = reads_src_normals<OBJ>(false, a.min_ndot);      // (no write-back here)
     constexpr int kList = ACC ? kFusedList : kFusedList / 2;      // (the search-only form keeps 5 workgroups per CU: its tile is 256 points)
     __shared__ uint32_t s_list[kList];
     __shared__ uint32_t s_cnt, s_total;
@@ -1196,7 +1105,7 @@ __global__ __launch_bounds__(kPassThreads, ACC ? FUSED_WAVES : COMPACT_WAVES) vo
                     if (pw != pk) { qw = ix.tn[2 * (size_t)pw]; nqw = ix.tn[2 * (size_t)pw + 1]; }
                     float nx = 0.0f, ny = 0.0f, nz = 0.0f;
                     if (need_n) { nx = a.in.nx[i]; ny = a.in.ny[i]; nz = a.in.nz[i]; }
-                    fused_accumulate<OBJ>(acc, h, nx, ny, nz, px, py, pz, qw, nqw, d2w);
+                    pair_step<OBJ>(acc, h, nx, ny, nz, px, py, pz, qw, nqw, d2w);
                     s_list[e] = 0xFFFFFFFFu;                       // settled (an idle lane of the scan below)
                 }
             }
@@ -1219,7 +1128,7 @@ __global__ __launch_bounds__(kPassThreads, ACC ? FUSED_WAVES : COMPACT_WAVES) vo
                 float nx = 0.0f, ny = 0.0f, nz = 0.0f;
                 if (need_n) { nx = a.in.nx[i]; ny = a.in.ny[i]; nz = a.in.nz[i]; }
                 const float px = xf_row(X.m + 0, x, y, z, 1.0f), py = xf_row(X.m + 4, x, y, z, 1.0f), pz = xf_row(X.m + 8, x, y, z, 1.0f);
-                fused_accumulate<OBJ>(acc, h, nx, ny, nz, px, py, pz, q, nq, dist2(px, py, pz, q.x, q.y, q.z));
+                pair_step<OBJ>(acc, h, nx, ny, nz, px, py, pz, q, nq, dist2(px, py, pz, q.x, q.y, q.z));
             }
         }
         __syncthreads();
@@ -1297,7 +1206,7 @@ __global__ __launch_bounds__(kPassThreads, ACC ? FUSED_WAVES : COMPACT_WAVES) vo
                 }
                 if (certified) {
                     // (the refreshed distance is not stored: 4 of the pass's 76 bytes per point; symmicp_get_correspondences evaluates it)
-                    if (ACC) fused_accumulate<OBJ>(acc, h, nx[k], ny[k], nz[k], px, py, pz, q[k], nq[k], d2);
+                    if (ACC) pair_step<OBJ>(acc, h, nx[k], ny[k], nz[k], px, py, pz, q[k], nq[k], d2);
                 } else {
                     s_list[atomicAdd(&s_cnt, 1u)] = i;                 // (room for a whole tile: see the flush below)
                 }
@@ -1317,7 +1226,7 @@ __global__ __launch_bounds__(kPassThreads, ACC ? FUSED_WAVES : COMPACT_WAVES) vo
 #ifdef RS_STAMPS2
     const unsigned long long fs2 = __builtin_amdgcn_s_memrealtime();
 #endif
-    if (ACC) acc_block_reduce_store(acc, a.partials, a.partial_cols ? a.partial_cols : gridDim.x);
+    if (ACC) acc_block_reduce_store(acc, a.partials, blockIdx.x);
 #ifdef RS_STAMPS2
     if (ACC && blockIdx.x == 0 && threadIdx.x == 0) {
         double *dbg = a.partials + (size_t)8191 * kNSum;
@@ -1531,7 +1440,8 @@ template <bool W, int OBJ>
 __global__ __launch_bounds__(kPassThreads) void k_accumulate(PassArgs a, const float4 *__restrict__ tn)
 {
     AccT<W> acc; acc_zero(acc);
-    const bool need_n = OBJ != kObjPlane || a.writeback || a.min_ndot > -1.0f;
+    const HotParams h = hot_params(a);
+    const bool need_n = reads_src_normals<OBJ>(a.writeback, a.min_ndot);
     const uint32_t nbp = gridDim.x;
     // grid-stride over blocks of 256 points, XCD-contiguous
     const uint32_t total_blocks = (a.n + kPassThreads - 1) / kPassThreads;
@@ -1550,19 +1460,15 @@ __global__ __launch_bounds__(kPassThreads) void k_accumulate(PassArgs a, const f
             if (a.refresh_records) { a.pairrec[2 * (size_t)i] = q; a.pairrec[2 * (size_t)i + 1] = nq; }
         }
         const float px = xf_row(a.X.m + 0, x, y, z, 1.0f), py = xf_row(a.X.m + 4, x, y, z, 1.0f), pz = xf_row(a.X.m + 8, x, y, z, 1.0f);
-        const float npx = xf_row(a.X.m + 0, nx, ny, nz, a.X.nrm_w), npy = xf_row(a.X.m + 4, nx, ny, nz, a.X.nrm_w),
-                    npz = xf_row(a.X.m + 8, nx, ny, nz, a.X.nrm_w);
         if (a.writeback) {
             a.out.x[i] = px; a.out.y[i] = py; a.out.z[i] = pz;
-            a.out.nx[i] = npx; a.out.ny[i] = npy; a.out.nz[i] = npz;
+            a.out.nx[i] = xf_row(a.X.m + 0, nx, ny, nz, a.X.nrm_w); a.out.ny[i] = xf_row(a.X.m + 4, nx, ny, nz, a.X.nrm_w);
+            a.out.nz[i] = xf_row(a.X.m + 8, nx, ny, nz, a.X.nrm_w);
         }
         if (nq.w != 0.0f) continue;                       // no target for this point
-        const float d2 = dist2(px, py, pz, q.x, q.y, q.z);
-        if (a.max_d2 > 0.0f && d2 > a.max_d2) continue;
-        if (a.min_ndot > -1.0f && (npx * nq.x + npy * nq.y) + npz * nq.z < a.min_ndot) continue;
-        acc_obj<OBJ>(acc, px, py, pz, npx, npy, npz, q.x, q.y, q.z, nq.x, nq.y, nq.z, d2, a.pivot, a.p2p, a.gicp_k, a.loss, a.loss_scale);
+        pair_step<OBJ>(acc, h, nx, ny, nz, px, py, pz, q, nq, dist2(px, py, pz, q.x, q.y, q.z));
     }
-    acc_block_reduce_store(acc, a.partials, gridDim.x);
+    acc_block_reduce_store(acc, a.partials, blockIdx.x);
 }
 
 // The append lists' bookkeeping words, read by the 64 lanes of one wave at once (three independent loads per lane):
@@ -1581,7 +1487,8 @@ __global__ __launch_bounds__(kPassThreads) void k_accumulate_list(PassArgs a, co
         a.X = a.loop->Xapply;
     }
     AccT<W> acc; acc_zero(acc);
-    const bool need_n = OBJ != kObjPlane || a.min_ndot > -1.0f;      // (no write-back here)
+    const HotParams h = hot_params(a);
+    const bool need_n = reads_src_normals<OBJ>(false, a.min_ndot);      // (no write-back here)
     // block b: shards b, b + gridDim.x, ...; its waves take them in turn (a list is a handful of entries: what counts is that the
     // counters and entries of all shards are requested side by side, not one shard after the other)
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -1598,15 +1505,10 @@ __global__ __launch_bounds__(kPassThreads) void k_accumulate_list(PassArgs a, co
             a.pairrec[2 * (size_t)i] = q; a.pairrec[2 * (size_t)i + 1] = nq;
             if (nq.w != 0.0f) continue;                   // no target for this point
             const float px = xf_row(a.X.m + 0, x, y, z, 1.0f), py = xf_row(a.X.m + 4, x, y, z, 1.0f), pz = xf_row(a.X.m + 8, x, y, z, 1.0f);
-            const float npx = xf_row(a.X.m + 0, nx, ny, nz, a.X.nrm_w), npy = xf_row(a.X.m + 4, nx, ny, nz, a.X.nrm_w),
-                        npz = xf_row(a.X.m + 8, nx, ny, nz, a.X.nrm_w);
-            const float d2 = dist2(px, py, pz, q.x, q.y, q.z);
-            if (a.max_d2 > 0.0f && d2 > a.max_d2) continue;
-            if (a.min_ndot > -1.0f && (npx * nq.x + npy * nq.y) + npz * nq.z < a.min_ndot) continue;
-            acc_obj<OBJ>(acc, px, py, pz, npx, npy, npz, q.x, q.y, q.z, nq.x, nq.y, nq.z, d2, a.pivot, a.p2p, a.gicp_k, a.loss, a.loss_scale);
+            pair_step<OBJ>(acc, h, nx, ny, nz, px, py, pz, q, nq, dist2(px, py, pz, q.x, q.y, q.z));
         }
     }
-    acc_block_reduce_store(acc, a.partials, a.partial_cols, a.partial_col0 + blockIdx.x);
+    acc_block_reduce_store(acc, a.partials, a.partial_col0 + blockIdx.x);
 }
 
 __device__ __forceinline__ void read_list_words(const uint32_t *cnt, int t, uint32_t &len, uint32_t &searched, uint32_t &dropped)
@@ -1688,7 +1590,7 @@ __global__ __launch_bounds__(256) void k_final_reduce(const double *__restrict__
 
 // ---------------------------------------------------------------------------
 // k_reduce_solve: the end of one pass and the start of the next WITHOUT the host (device-driven runs of passes).
-//   reduce   partials[40][nblocks] -> the pass's record (one 512-thread block: wave w sums rows w, w+8, ...; fixed order).
+//   reduce   partials[nblocks][40] -> the pass's record (one 512-thread block: wave w sums the records of blocks w, w+8, ...; fixed order).
 //            Sharded runs reduce with k_final_reduce, all-reduce the record over the ranks and call this kernel with
 //            REDUCE = false: the record is then read from out_dev.
 //   check    a non-empty work list means the fused pass left queries to the tree walk: the pass has to be redone through
@@ -1806,9 +1708,7 @@ __global__ __launch_bounds__(512) void k_reduce_solve(const double *__restrict__
     symmicp_sums S;
     for (int k = 0; k < kNSum; k++) S.s[k] = (k >= kNAccW) ? 0.0 : s_sum[k];
     float pbar[3], qbar[3], av[3], tv[3], rc = 0.f, Xi[16];
-    const int st = (cfg.mode == SYMMICP_MODE_QUIRKS) ? solve::solve_quirks(S, pbar, qbar, av, tv, &rc, Xi, false)
-                 : (cfg.mode == SYMMICP_MODE_PLANE || cfg.mode == SYMMICP_MODE_GICP) ? solve::solve_plane(S, cfg.pivot, pbar, qbar, av, tv, &rc, Xi, false)
-                                                      : solve::solve_paper(S, cfg.pivot, pbar, qbar, av, tv, &rc, Xi, false);
+    const int st = solve::solve_mode(cfg.mode, S, cfg.pivot, pbar, qbar, av, tv, &rc, Xi, false);
     if (st != SYMMICP_OK || !(rc > 1e-6f)) { loop->stop = 1; loop->reason = LOOP_HOST_SOLVE; return; }
 #ifdef RS_STAMPS
     const unsigned long long ts2 = __builtin_amdgcn_s_memrealtime();
@@ -1848,9 +1748,7 @@ __global__ __launch_bounds__(64) void k_solve_probe(int mode, int exact_rc, cons
     float pb[3] = {0.f, 0.f, 0.f}, qb[3] = {0.f, 0.f, 0.f}, av[3] = {0.f, 0.f, 0.f}, tv[3] = {0.f, 0.f, 0.f}, rc = 0.f, Xi[16], Xn[16];
     for (int k = 0; k < 16; k++) Xi[k] = 0.f;
     const bool ex = exact_rc != 0;
-    const int st = (mode == SYMMICP_MODE_QUIRKS) ? solve::solve_quirks(S, pb, qb, av, tv, &rc, Xi, ex)
-                 : (mode == SYMMICP_MODE_PLANE || mode == SYMMICP_MODE_GICP) ? solve::solve_plane(S, pivot, pb, qb, av, tv, &rc, Xi, ex)
-                                                 : solve::solve_paper(S, pivot, pb, qb, av, tv, &rc, Xi, ex);
+    const int st = solve::solve_mode(mode, S, pivot, pb, qb, av, tv, &rc, Xi, ex);
     status[i] = st;
     rcond[i] = rc;
     for (int k = 0; k < 3; k++) { pbar[3 * i + k] = pb[k]; qbar[3 * i + k] = qb[k]; a[3 * i + k] = av[k]; t[3 * i + k] = tv[k]; }
@@ -1989,32 +1887,36 @@ void launch_identity_d2(const CloudSoA &in, const Affine &X, const CloudSoA &tgt
 // ---------------------------------------------------------------------------
 // launchers
 // ---------------------------------------------------------------------------
-// the instantiation of an accumulating kernel for the pass's record: weighted (robust loss) or not; symmetric, PLANE or GICP
-template <typename K>
-static K pick(const PassArgs &a, K plain, K weighted, K plane, K plane_weighted, K gicp, K gicp_weighted)
+// Calls f(W, OBJ) with the pass's instantiation as compile-time constants (std::integral_constant): W, weighted (robust loss) or not;
+// OBJ, the record (PassArgs::obj)
+template <typename F>
+static void with_instantiation(const PassArgs &a, F &&f)
 {
-    const bool w = a.loss != SYMMICP_LOSS_NONE;
-    return a.gicp ? (w ? gicp_weighted : gicp) : a.plane ? (w ? plane_weighted : plane) : (w ? weighted : plain);
+    auto obj = [&](auto W) {
+        if (a.obj == kObjGicp) f(W, std::integral_constant<int, kObjGicp>());
+        else if (a.obj == kObjPlane) f(W, std::integral_constant<int, kObjPlane>());
+        else f(W, std::integral_constant<int, kObjSym>());
+    };
+    if (a.loss != SYMMICP_LOSS_NONE) obj(std::true_type());
+    else obj(std::false_type());
 }
 
 void launch_pass_identity(const PassArgs &a, CloudSoA tgt, int blocks, bool vec4_ok, hipStream_t s)
 {
-    if (vec4_ok) hipLaunchKernelGGL(pick(a, k_pass_identity<4, false, kObjSym>, k_pass_identity<4, true, kObjSym>,
-                                            k_pass_identity<4, false, kObjPlane>, k_pass_identity<4, true, kObjPlane>,
-                                            k_pass_identity<4, false, kObjGicp>, k_pass_identity<4, true, kObjGicp>),
-                                    dim3(blocks), dim3(kPassThreads), 0, s, a, tgt);
-    else hipLaunchKernelGGL(pick(a, k_pass_identity<1, false, kObjSym>, k_pass_identity<1, true, kObjSym>,
-                                    k_pass_identity<1, false, kObjPlane>, k_pass_identity<1, true, kObjPlane>,
-                                    k_pass_identity<1, false, kObjGicp>, k_pass_identity<1, true, kObjGicp>),
-                            dim3(blocks), dim3(kPassThreads), 0, s, a, tgt);
+    with_instantiation(a, [&](auto W, auto OBJ) {
+        if (vec4_ok) hipLaunchKernelGGL((k_pass_identity<4, W, OBJ>), dim3(blocks), dim3(kPassThreads), 0, s, a, tgt);
+        else hipLaunchKernelGGL((k_pass_identity<1, W, OBJ>), dim3(blocks), dim3(kPassThreads), 0, s, a, tgt);
+    });
 }
 
 void launch_pass_indexed(const PassArgs &a, const float4 *tn, int blocks, hipStream_t s)
 {
-    hipLaunchKernelGGL(pick(a, k_pass_indexed<false, kObjSym>, k_pass_indexed<true, kObjSym>,
-                               k_pass_indexed<false, kObjPlane>, k_pass_indexed<true, kObjPlane>,
-                               k_pass_indexed<false, kObjGicp>, k_pass_indexed<true, kObjGicp>),
-                       dim3(blocks), dim3(kPassThreads), 0, s, a, tn);
+    with_instantiation(a, [&](auto W, auto OBJ) { hipLaunchKernelGGL((k_pass_indexed<W, OBJ>), dim3(blocks), dim3(kPassThreads), 0, s, a, tn); });
+}
+
+void launch_accumulate(const PassArgs &a, const float4 *tn, int blocks, hipStream_t s)
+{
+    with_instantiation(a, [&](auto W, auto OBJ) { hipLaunchKernelGGL((k_accumulate<W, OBJ>), dim3(blocks), dim3(kPassThreads), 0, s, a, tn); });
 }
 
 uint32_t shard_capacity(uint32_t n_points)
@@ -2074,19 +1976,8 @@ void launch_pass_tree_split(const PassArgs &a_in, const TargetIndex &ix, const W
         }
     }
     if (ev) hipEventRecord(ev[3], s);
-    hipLaunchKernelGGL(pick(a, k_accumulate<false, kObjSym>, k_accumulate<true, kObjSym>,
-                               k_accumulate<false, kObjPlane>, k_accumulate<true, kObjPlane>,
-                               k_accumulate<false, kObjGicp>, k_accumulate<true, kObjGicp>),
-                       dim3(acc_blocks), dim3(kPassThreads), 0, s, a, ix.tn);
+    launch_accumulate(a, ix.tn, acc_blocks, s);
     if (ev) hipEventRecord(ev[4], s);
-}
-
-void launch_accumulate(const PassArgs &a, const float4 *tn, int blocks, hipStream_t s)
-{
-    hipLaunchKernelGGL(pick(a, k_accumulate<false, kObjSym>, k_accumulate<true, kObjSym>,
-                               k_accumulate<false, kObjPlane>, k_accumulate<true, kObjPlane>,
-                               k_accumulate<false, kObjGicp>, k_accumulate<true, kObjGicp>),
-                       dim3(blocks), dim3(kPassThreads), 0, s, a, tn);
 }
 
 void launch_final_reduce(const double *partials, int blocks, double *out_dev, double *out_host_mapped, uint32_t *ticket,
@@ -2098,10 +1989,7 @@ void launch_final_reduce(const double *partials, int blocks, double *out_dev, do
 
 void launch_pass_fused(const PassArgs &a, const TargetIndex &ix, const WorkLists &wl, int blocks, hipStream_t s)
 {
-    hipLaunchKernelGGL(pick(a, k_pass_fused<true, false, kObjSym>, k_pass_fused<true, true, kObjSym>,
-                               k_pass_fused<true, false, kObjPlane>, k_pass_fused<true, true, kObjPlane>,
-                               k_pass_fused<true, false, kObjGicp>, k_pass_fused<true, true, kObjGicp>),
-                       dim3(blocks), dim3(kPassThreads), 0, s, a, ix, wl);
+    with_instantiation(a, [&](auto W, auto OBJ) { hipLaunchKernelGGL((k_pass_fused<true, W, OBJ>), dim3(blocks), dim3(kPassThreads), 0, s, a, ix, wl); });
 }
 
 void launch_loop_stragglers(const PassArgs &a, const TargetIndex &ix, const WorkLists &wl, int list_blocks, const PassTuning &tune, hipStream_t s)
@@ -2109,10 +1997,9 @@ void launch_loop_stragglers(const PassArgs &a, const TargetIndex &ix, const Work
     // (short lists: the wave-per-entry regime; anything above the threshold strides one thread per entry over this grid)
     const uint32_t wave_mode_max = tune.wave_mode_max;
     hipLaunchKernelGGL(k_search_walk<false>, dim3(512), dim3(kWalkThreads), 0, s, a, ix, wl, wl.work, wave_mode_max, 0xFFFFFFFFu);
-    hipLaunchKernelGGL(pick(a, k_accumulate_list<false, kObjSym>, k_accumulate_list<true, kObjSym>,
-                               k_accumulate_list<false, kObjPlane>, k_accumulate_list<true, kObjPlane>,
-                               k_accumulate_list<false, kObjGicp>, k_accumulate_list<true, kObjGicp>),
-                       dim3(list_blocks), dim3(kPassThreads), 0, s, a, ix.tn, wl.work);
+    with_instantiation(a, [&](auto W, auto OBJ) {
+        hipLaunchKernelGGL((k_accumulate_list<W, OBJ>), dim3(list_blocks), dim3(kPassThreads), 0, s, a, ix.tn, wl.work);
+    });
 }
 
 void launch_reduce_solve(const double *partials, int blocks, double *out_dev, int mode, LoopState *loop, LoopConfig cfg, LoopRecord *ring, int ring_len,

@@ -472,6 +472,16 @@ SYMMICP_HD inline int solve_p2p(const symmicp_sums &S, const float pivot[3], flo
     return SYMMICP_OK;
 }
 
+// The solve of a QUIRKS, PAPER, PLANE or GICP record (mode_device_solves, symmicp_internal.h); GICP's record has PLANE's shape.  P2P's
+// solve_p2p stays with its host callers.
+SYMMICP_HD inline int solve_mode(int mode, const symmicp_sums &S, const float pivot[3], float pbar[3], float qbar[3], float a[3], float t[3],
+                                 float *rcond, float out16[16], bool exact_rc = true)
+{
+    return (mode == SYMMICP_MODE_QUIRKS) ? solve_quirks(S, pbar, qbar, a, t, rcond, out16, exact_rc)
+         : (mode == SYMMICP_MODE_PLANE || mode == SYMMICP_MODE_GICP) ? solve_plane(S, pivot, pbar, qbar, a, t, rcond, out16, exact_rc)
+                                                                      : solve_paper(S, pivot, pbar, qbar, a, t, rcond, out16, exact_rc);
+}
+
 // transform = incre * transform (myicp.cpp:138), fp32, k sequential
 SYMMICP_HD inline void mat4_mul(const float A[16], const float B[16], float C[16])
 {

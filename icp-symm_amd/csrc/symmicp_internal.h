@@ -22,6 +22,19 @@ constexpr int kPassThreads = 256;
 constexpr int kBruteTile = 1024;      // target points staged in LDS per tile (16 KB)
 constexpr int kBruteQ = 4;            // queries per thread in the brute-force kernel
 
+// The modes symmicp_config accepts (4 is unassigned), and those whose record solve::solve_mode solves, on the host and on the device:
+// all but P2P, whose solve is host-only
+constexpr bool mode_device_solves(int mode)
+{
+    return mode == SYMMICP_MODE_QUIRKS || mode == SYMMICP_MODE_PAPER || mode == SYMMICP_MODE_PLANE || mode == SYMMICP_MODE_GICP;
+}
+constexpr bool mode_known(int mode) { return mode_device_solves(mode) || mode == SYMMICP_MODE_P2P; }
+
+// The record a mode's passes accumulate (PassArgs::obj, the OBJ parameter of every accumulating kernel): the symmetric rows of
+// QUIRKS / PAPER / P2P, PLANE's or GICP's
+constexpr int kObjSym = 0, kObjPlane = 1, kObjGicp = 2;
+constexpr int mode_obj(int mode) { return mode == SYMMICP_MODE_PLANE ? kObjPlane : mode == SYMMICP_MODE_GICP ? kObjGicp : kObjSym; }
+
 // 3x4 affine passed by value in kernel arguments (row-major), plus the weight
 // the translation column gets when it is applied to normals
 // (1 = reference quirk myicp.cpp:137, 0 = rotate only).
@@ -137,7 +150,7 @@ struct PassArgs {
     int32_t *pos_prev;                  // TREE: sorted position found by the previous pass (-1 = none); updated
     float *d2_out;                      // optional per-point squared distance (may be null)
     int32_t *pos_out;                   // sorted position / target row chosen this pass (may alias pos_prev)
-    double *partials;                   // [kNSum][blocks] (transposed)
+    double *partials;                   // [blocks][kNSum]: block b's record at partials[b * kNSum + k]
     // pair certificates (TREE): position of the query when its pair was last searched, and the radius around it known
     // to hold no other target point (see k_search_cells)
     float4 *pairrec;                    // TREE: per pair, its own copy of the target's (point, normal) record (2 float4)
@@ -158,8 +171,7 @@ struct PassArgs {
     uint32_t pkt_chunk, pkt_lds_pad;    // ... packets per XCD chunk (0: 64); extra dynamic LDS per workgroup (occupancy experiments)
     int32_t loss;                       // robust loss (SYMMICP_LOSS_*): != NONE selects the weighted instantiation of every accumulating kernel
     float loss_scale;                   // ... its scale (robust_loss.h)
-    int32_t plane;                      // SYMMICP_MODE_PLANE: the launchers pick the PLANE instantiations (acc_plane); read by the host only
-    int32_t gicp;                       // SYMMICP_MODE_GICP: the launchers pick the GICP instantiations (acc_gicp); read by the host only
+    int32_t obj;                        // the record (kObjSym / kObjPlane / kObjGicp, mode_obj): the launchers pick the instantiations; read by the host only
     float gicp_k;                       // ... 1 - eps of its covariances (symmicp_set_gicp_epsilon), fp32: read by the GICP instantiations only
 };
 
