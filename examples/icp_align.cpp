@@ -4,7 +4,7 @@
 //     --mode quirks|paper|plane|gicp  arithmetic: the reference as written (default), the paper-correct symmetric form,
 //                              point-to-plane (target normals only: the source's are not estimated), or plane-to-plane
 //                              (Generalized-ICP, covariances from the normals of both clouds)
-//     --gicp-epsilon E         the covariances' eps, 0 < E <= 1 (default 1e-3; --mode gicp only)
+//     --gicp-epsilon E         the covariances' eps, 2^-25 < E <= 1: 1 - E must differ from 1 in fp32 (default 1e-3; --mode gicp only)
 //     --corr identity|tree     pairing: by row (default, what the reference does) or exact nearest neighbours
 //     --iters N                iteration cap            (default 10, ICP/myicp.cpp:6)
 //     --loss none|huber|tukey|cauchy|gm   robust loss of the paper loop (default none; not with --mode quirks)
@@ -90,8 +90,8 @@ int main(int argc, char **argv)
             char *end = nullptr;
             const char *v = value("--gicp-epsilon");
             gicp_eps = std::strtof(v, &end);
-            if (end == v || *end || !std::isfinite(gicp_eps) || !(gicp_eps > 0.f) || gicp_eps > 1.f)
-                return usage(argv[0], "--gicp-epsilon needs a number E with 0 < E <= 1");
+            if (end == v || *end || !std::isfinite(gicp_eps) || !(gicp_eps > 0.f) || gicp_eps > 1.f || 1.0f - gicp_eps == 1.0f)
+                return usage(argv[0], "--gicp-epsilon needs a number E with 2^-25 < E <= 1 (1 - E must differ from 1 in fp32)");
             have_eps = true;
         }
         else if (a == "--max-dist") {

@@ -261,6 +261,9 @@ int symmicp_set_gicp_epsilon(symmicp_ctx *c, float eps)
 {
     if (!c) return SYMMICP_ERR_ARG;
     if (!(std::isfinite(eps) && eps > 0.f && eps <= 1.f)) return fail(c, SYMMICP_ERR_ARG, "gicp epsilon: 0 < eps <= 1 and finite");
+    // the kernels use 1 - eps in fp32 (fill_pass_args): an eps it rounds away (eps <= 2^-25) would make a pair of equal normals
+    // singular (lambda_u = 0, gamma_u = inf, a NaN record)
+    if (1.0f - eps == 1.0f) return fail(c, SYMMICP_ERR_ARG, "gicp epsilon: 1 - eps must differ from 1 in fp32 (eps > 2^-25)");
     c->gicp_eps = eps;
     return SYMMICP_OK;
 }

@@ -406,7 +406,8 @@ class Engine:
         return lo.value, sc.value
 
     def set_gicp_epsilon(self, eps):
-        """the eps of MODE_GICP's covariances I - (1 - eps) n n^T (0 < eps <= 1; default 1e-3); takes effect at the next pass"""
+        """the eps of MODE_GICP's covariances I - (1 - eps) n n^T (0 < eps <= 1 with 1 - eps != 1 in fp32, i.e. eps > 2^-25;
+        default 1e-3); takes effect at the next pass"""
         self._chk(self._L.symmicp_set_gicp_epsilon(self._h, float(eps)))
 
     def gicp_epsilon(self):

@@ -53,7 +53,7 @@ public:
 	// returns SYMMICP_ERR_ARG for a loss with SYMMICP_MODE_QUIRKS or a scale that is not finite and > 0
 	void setRobustLoss(symmicp_loss loss, float scale) { loss_ = loss; loss_scale_ = scale; }
 	// the covariance eps of SYMMICP_MODE_GICP (symmicp_set_gicp_epsilon; default 1e-3): checked by align(), which returns
-	// SYMMICP_ERR_ARG unless 0 < eps <= 1
+	// SYMMICP_ERR_ARG unless 0 < eps <= 1 and 1 - eps != 1 in fp32 (eps > 2^-25)
 	void setGicpEpsilon(float eps) { gicp_eps_ = eps; }
 	// pairs farther apart than d are dropped (symmicp_config.max_corr_dist; <= 0, the default: every pair is kept)
 	void setMaxCorrespondenceDistance(float d) { max_corr_dist_ = d; }

@@ -178,8 +178,10 @@ int symmicp_version(void);
  * the values it started with.  Sharded runs: every rank sets the same values. */
 int symmicp_set_robust_loss(symmicp_ctx *ctx, int loss, float scale);
 int symmicp_get_robust_loss(const symmicp_ctx *ctx, int *loss, float *scale);
-/* The eps of SYMMICP_MODE_GICP's covariances C = I - (1 - eps) n n^T: 0 < eps <= 1 and finite, else SYMMICP_ERR_ARG; default 1e-3
- * (PCL's and Segal's).  Accepted in every mode, read by GICP only.  eps = 1 makes every pair point-to-point (M = 1/2 I).  Takes
+/* The eps of SYMMICP_MODE_GICP's covariances C = I - (1 - eps) n n^T: 0 < eps <= 1, finite and 1.0f - eps != 1.0f (eps > 2^-25),
+ * else SYMMICP_ERR_ARG and the eps set before stays; default 1e-3 (PCL's and Segal's).  The kernels use fl32(1 - eps): an eps that
+ * rounds it to 1 would make a pair of equal normals singular, and an eps below ~1e-5 is quantised by up to 2^-25 / eps relative.
+ * Accepted in every mode, read by GICP only.  eps = 1 makes every pair point-to-point (M = 1/2 I).  Takes
  * effect at the next pass; a device-driven run inside symmicp_align keeps the value it started with.  Sharded runs: every rank
  * sets the same value. */
 int symmicp_set_gicp_epsilon(symmicp_ctx *ctx, float eps);

@@ -126,25 +126,65 @@ def gicp_matrices(pn, qn, eps=EPS_DEFAULT):
     return np.linalg.inv(Cp + Cq)
 
 
-def gicp_direct(p, pn, q, qn, pivot, eps=EPS_DEFAULT, w=None, centre=None):
-    """-> (H [6, 6], g [6], sum w d^T M d) about the pivot; centre: rotations about this point (about the pivot) instead"""
+def gicp_direct(p, pn, q, qn, pivot, eps=EPS_DEFAULT, w=None, centre=None, M=None):
+    """-> (H [6, 6], g [6], sum w d^T M d) about the pivot; centre: rotations about this point (about the pivot) instead; M: the
+    per-pair [n, 3, 3] to use instead of gicp_matrices (a test's mutant)"""
     pv = np.asarray(pivot, np.float64)
     P = np.asarray(p, np.float64) - pv
     Q = np.asarray(q, np.float64) - pv
     D = P - Q
     w = np.ones(len(P)) if w is None else np.asarray(w, np.float64)
     Pc = P if centre is None else P - np.asarray(centre, np.float64)
-    M = gicp_matrices(pn, qn, eps)
-    H = np.zeros((6, 6))
-    g = np.zeros(6)
-    e = 0.0
-    for i in range(len(P)):
-        J = np.concatenate([-skew(Pc[i]), np.eye(3)], 1)          # d(p + a x p + t) / d(a, t)
-        JM = J.T @ M[i]
-        H += w[i] * (JM @ J)
-        g += w[i] * (JM @ D[i])
-        e += w[i] * (D[i] @ M[i] @ D[i])
+    M = gicp_matrices(pn, qn, eps) if M is None else np.asarray(M, np.float64)
+    J = np.zeros((len(P), 3, 6))                                 # d(p + a x p + t) / d(a, t) = [-[p]x, I]
+    J[:, :, :3] = -np.stack([skew(v) for v in Pc]) if len(P) else 0.0
+    J[:, :, 3:] = np.eye(3)
+    JM = np.einsum("nij,nik->njk", J, M)
+    H = np.einsum("n,njk,nkl->jl", w, JM, J)
+    g = np.einsum("n,njk,nk->j", w, JM, D)
+    e = float(np.einsum("n,ni,nij,nj->", w, D, M, D))
     return H, g, e
+
+
+def direct_record(p, pn, q, qn, pivot, eps=EPS_DEFAULT, M=None):
+    """gicp_direct in the record's slots: 0..20 = H (upper triangle, row by row), 21..26 = g, 35 = sum d^T M d"""
+    H, g, e = gicp_direct(p, pn, q, qn, pivot, eps, M=M)
+    D = np.zeros(NSUM)
+    D[:21] = H[np.triu_indices(6)]
+    D[21:27] = g
+    D[35] = e
+    return D
+
+
+# The bar of a record against the fp64 definition.  The kernels' cs is an fp32 dot product of fp32-rounded normals, so gamma_u and
+# gamma_v carry a relative error of ~2^-24 / eps whatever the kernel does (d gamma_u / gamma_u ~ d cs / (2 eps) near cs = 1), and
+# non-unit normals move the closed form off the inverse by as much.  Slot k is held to FP64_C x 2^-24 / eps x (the sum of its terms'
+# magnitudes).  Measured at eps = 1e-3 on the fp32 restatement: 0.08 on the cat pair's first passes, 1.4 on the 200k surface pair
+# at its true pose (synth normals, |n|^2 - 1 up to ~1e-7); a record with gamma_u and gamma_v swapped, or the axis rows at weight 1,
+# misses it by 100x and more.
+FP64_C = 4.0
+FP64_SLOTS = list(range(27)) + [35]
+
+
+def fp64_excess(S, M, D, eps):
+    """max over the slots of FP64_SLOTS of |S - D| / (2^-24 / eps x M): <= FP64_C passes; a slot of no magnitude must be 0"""
+    S, M, D = (np.asarray(x, np.float64)[FP64_SLOTS] for x in (S, M, D))
+    err = np.abs(S - D)
+    bar = 2.0 ** -24 / float(eps) * M
+    assert not (err[bar == 0] > 1e-300).any()
+    return float((err[bar > 0] / bar[bar > 0]).max())
+
+
+def swapped_matrices(pn, qn, eps=EPS_DEFAULT):
+    """a mutant of the closed form in fp64: gamma_u on v v^T and gamma_v on u u^T"""
+    A = np.asarray(pn, np.float64)
+    B = np.asarray(qn, np.float64)
+    k = 1.0 - float(eps)
+    cs = np.clip((A * B).sum(1), -1.0, 1.0)
+    gu = k / (4 * (2 - k * (1 + cs)))
+    gv = k / (4 * (2 - k * (1 - cs)))
+    U, V = A + B, A - B
+    return 0.5 * np.eye(3)[None] + gv[:, None, None] * U[:, :, None] * U[:, None, :] + gu[:, None, None] * V[:, :, None] * V[:, None, :]
 
 
 def unpack_upper(S):

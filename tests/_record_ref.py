@@ -1,10 +1,10 @@
 """The fp64 reduction record of one pass (include/symmicp.h, symmicp_sums), rebuilt in numpy from the pass's own inputs.  Shared by
 the record tests of every mode: test_gpu_robust.py, test_gpu_plane.py (through _plane_ref), test_gpu_pass_matrix.py and _fuzz_nn.py.
 
-Per-pair terms repeat the kernels' fp32 expressions (acc_pair / acc_plane in icp-symm_amd/csrc/kernels_pass.hip, built with
--ffp-contract=off: every product and sum rounded on its own, in the kernels' association), are carried to fp64 exactly and summed
-there.  So a record agrees with the pass up to the order of the fp64 summation: a slot is compared at c x (sum of its terms'
-magnitudes) -- c = TOL_EXACT for the unweighted records, whose fp64 terms are exact products of fp32 values, and c = TOL_REC for the
+Per-pair terms repeat the kernels' fp32 expressions (acc_pair / acc_plane in icp-symm_amd/csrc/kernels_pass.hip, and acc_gicp
+through _gicp_ref.gicp_terms, built with -ffp-contract=off: every product and sum rounded on its own, in the kernels' association),
+are carried to fp64 exactly and summed there.  So a record agrees with the pass up to the order of the fp64 summation: a slot is
+compared at c x (sum of its terms' magnitudes) -- c = TOL_EXACT for the unweighted records, whose fp64 terms are exact products of fp32 values, and c = TOL_REC for the
 weighted ones, whose w * v_r * v_s rounds once more in a different place -- and the pair count (slot 37, or 34 unweighted) exactly.
 
 The two pair gates are applied as every kernel applies them (and the oracle, symmicp_oracle.c reduce_range): a pair is dropped when
@@ -16,7 +16,7 @@ NSUM = 40
 TOL_EXACT = 1e-12      # unweighted records: fp64 sums of exact terms, only the order differs
 TOL_REC = 1e-6         # weighted records
 
-MODE_QUIRKS, MODE_PAPER, MODE_P2P, MODE_PLANE = 0, 1, 2, 3       # symmicp_mode
+MODE_QUIRKS, MODE_PAPER, MODE_P2P, MODE_PLANE, MODE_GICP = 0, 1, 2, 3, 5       # symmicp_mode
 f32 = np.float32
 
 
@@ -52,8 +52,8 @@ def xf_rows(X, v, w):
 
 
 def moved(X, src, src_n, mode):
-    """the source as a pass moves it from the original rows (cumulative apply): points with the translation, normals without it --
-    except in QUIRKS, whose normals take the translation too (myicp.cpp:137, nrm_w = 1)"""
+    """the source as a pass moves it from the original rows (cumulative apply): points with the translation, normals without it
+    (PAPER, P2P, PLANE, GICP) -- except in QUIRKS, whose normals take the translation too (myicp.cpp:137, nrm_w = 1)"""
     return xf_rows(X, src, 1.0), xf_rows(X, src_n, 1.0 if mode == MODE_QUIRKS else 0.0)
 
 
@@ -168,15 +168,18 @@ def plane_terms(p, q, nq, pivot, loss=0, scale=1.0, dtype=np.float32):
     return T, c
 
 
-def pass_terms(mode, p, pn, q, qn, pivot, loss=0, scale=1.0):
-    """the terms of any mode's record: QUIRKS sums about the origin (the kernels get a zero pivot)"""
+def pass_terms(mode, p, pn, q, qn, pivot, loss=0, scale=1.0, eps=1e-3):
+    """the terms of any mode's record: QUIRKS sums about the origin (the kernels get a zero pivot); eps: GICP's covariance eps"""
     if mode == MODE_PLANE:
         return plane_terms(p, q, qn, pivot, loss, scale)
+    if mode == MODE_GICP:
+        from _gicp_ref import gicp_terms          # (imported here: _gicp_ref imports this module)
+        return gicp_terms(p, pn, q, qn, pivot, eps, loss, scale)
     pv = np.zeros(3, f32) if mode == MODE_QUIRKS else pivot
     return record_terms(p, pn, q, qn, pv, loss, scale, p2p=(mode == MODE_P2P))
 
 
-def record(mode, p, pn, q, qn, idx=None, pivot=(0.0, 0.0, 0.0), loss=0, scale=1.0, max_d2=0.0, min_ndot=-2.0):
+def record(mode, p, pn, q, qn, idx=None, pivot=(0.0, 0.0, 0.0), loss=0, scale=1.0, max_d2=0.0, min_ndot=-2.0, eps=1e-3):
     """-> (record [40], sum of |terms| [40], number of pairs the gates kept) of the pass whose moved source is (p, pn), target
     (q, qn) and pairs idx (row i -> target row idx[i]; -1: no pair; None: identity pairing)"""
     p, pn = np.asarray(p, f32), np.asarray(pn, f32)
@@ -187,7 +190,7 @@ def record(mode, p, pn, q, qn, idx=None, pivot=(0.0, 0.0, 0.0), loss=0, scale=1.
     has = idx >= 0
     p, pn, j = p[has], pn[has], idx[has]
     keep = gate(p, pn, q[j], qn[j], max_d2, min_ndot)
-    T, _ = pass_terms(mode, p[keep], pn[keep], q[j[keep]], qn[j[keep]], pivot, loss, scale)
+    T, _ = pass_terms(mode, p[keep], pn[keep], q[j[keep]], qn[j[keep]], pivot, loss, scale, eps)
     S = np.zeros(NSUM)
     M = np.zeros(NSUM)
     S[:38] = T.sum(0)

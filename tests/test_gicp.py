@@ -10,7 +10,8 @@ import numpy as np
 import pytest
 
 from _frames import scale_record
-from _gicp_ref import gicp_direct, gicp_record, gicp_solve, gicp_terms, unpack_upper
+from _gicp_ref import (FP64_C, direct_record, fp64_excess, gicp_direct, gicp_pass_record, gicp_record, gicp_solve, gicp_terms,
+                       swapped_matrices, unpack_upper)
 from _plane_ref import angle_axis, rot_err
 from conftest import ROOT
 
@@ -62,6 +63,16 @@ def test_create_accepts_mode_5_and_refuses_4(sym):
     for mode in (4, -1, 6):
         assert sym.solve(mode, S)[0] == sym.ERR_ARG, mode
     assert sym.solve(sym.MODE_GICP, S, np.full(3, 10.0, np.float32))[0] == 0
+
+
+def test_header_states_the_epsilon_rule():
+    """the setter's comment names the fp32 rule it enforces, and the driver's help line the range"""
+    hdr = open(os.path.join(ROOT, "include", "symmicp.h")).read()
+    i = hdr.index("int symmicp_set_gicp_epsilon")
+    doc = hdr[hdr.rindex("/*", 0, i):i]
+    assert "1.0f - eps != 1.0f" in doc and "2^-25" in doc, doc
+    drv = open(os.path.join(ROOT, "examples", "icp_align.cpp")).read()
+    assert "1.0f - gicp_eps == 1.0f" in drv and "2^-25 < E <= 1" in drv
 
 
 def test_epsilon_entry_points_refuse_a_null_context(sym):
@@ -134,6 +145,65 @@ def test_epsilon_one_does_not_read_the_normals():
     assert np.array_equal(S0, S1) and np.array_equal(S0, S2)
     S3, _ = gicp_record(p, npn, q, nq, pv, 1e-3)
     assert not np.array_equal(S0, S3)
+
+
+# ---- the fp32 record against the fp64 definition --------------------------------------------------------------------------------
+# the smallest eps the engine accepts: the float above 2^-25 (at 2^-25 and below, 1.0f - eps == 1.0f)
+EPS_MIN = float(np.nextafter(np.float32(2.0 ** -25), np.float32(1)))
+
+
+def _bar_case(cat, case):
+    """-> (p, pn, q, qn, pairs, pivot): the first pass of the cat pair at 15 degrees (identity pairs or nearest neighbours), or the
+    200k surface pair at its true pose with its nearest neighbours (the data of test_gpu_gicp.py's fp64 checks)"""
+    import _record_ref as R
+    from symmicp import synth
+    if case == "c4_truth":
+        d = synth.c4_surface(200000)
+        p, pn = R.moved(d["truth"], d["src"], d["src_n"], R.MODE_GICP)
+    else:
+        d = synth.perturbed(cat["src"], cat["src_n"])
+        p, pn = d["src"], d["src_n"]
+    idx = np.arange(len(p)) if case == "cat15_identity" else R.nn_ref(p, d["tgt"])[0]
+    pv = d["tgt"].astype(np.float64).mean(0).astype(np.float32)
+    return p, pn, d["tgt"], d["tgt_n"], idx, pv
+
+
+@pytest.mark.parametrize("case", ["cat15_identity", "cat15_nn", "c4_truth"])
+def test_fp32_record_meets_the_fp64_bar(cat, case):
+    """the kernels' record (restated in fp32) against gicp_direct's np.linalg.inv(C_p + C_q) on the same fp32 data: within
+    FP64_C x 2^-24 / eps of each slot's magnitude.  Two mutants of the closed form -- gamma_u and gamma_v swapped, the axis rows at
+    weight 1 instead of 1/2 -- miss that bar by 10x at least: a mistake the kernel and its restatement shared would fail here"""
+    p, pn, q, qn, idx, pv = _bar_case(cat, case)
+    eps = 1e-3
+    S, M, _ = gicp_pass_record(p, pn, q, qn, idx, pv, eps)
+    D = direct_record(p, pn, q[idx], qn[idx], pv, eps)
+    assert fp64_excess(S, M, D, eps) <= FP64_C, fp64_excess(S, M, D, eps)
+    Dswap = direct_record(p, pn, q[idx], qn[idx], pv, eps, M=swapped_matrices(pn, qn[idx], eps))
+    assert fp64_excess(Dswap, M, D, eps) >= 10 * FP64_C, fp64_excess(Dswap, M, D, eps)
+    S1, _, _ = gicp_pass_record(p, pn, q, qn, idx, pv, 1.0)          # eps = 1: the axis rows alone
+    assert fp64_excess(S + S1, M, D, eps) >= 10 * FP64_C, fp64_excess(S + S1, M, D, eps)
+
+
+@pytest.mark.parametrize("eps", [1.0, 1e-3, 1e-5, EPS_MIN])
+def test_edge_pairs_are_finite_in_fp32(eps):
+    """the closed form at its edges (test_gpu_gicp.py's hand-placed pairs) in the kernels' fp32: every record finite, and equal
+    normals keep lambda_u = 2 - fl32(1 - eps) 2 > 0 down to the smallest accepted eps"""
+    from _gicp_ref import gicp_k
+    k = gicp_k(eps)
+    assert k < np.float32(1) and np.float32(2) - k * np.float32(2) > 0
+    a = np.float32([[0, 0, 1], [0.6, 0.8, 0], [0.6, 0.8, 0], [1, 0, 0], [0, 0, 0], [0, 0, 1], [0, 0, 0], [0.6000001, 0.8, 0]])
+    b = np.float32([[0, 0, 1], [0.6, 0.8, 0], [-0.6, -0.8, 0], [0, 1, 0], [0, 1, 0], [0, 0, 0], [0, 0, 0], [0.6, 0.8000001, 0]])
+    p = np.float32(np.arange(24).reshape(8, 3) * 0.25)
+    q = p + np.float32([0.01, -0.02, 0.03])
+    T, r = gicp_terms(p, a, q, b, np.zeros(3, np.float32), eps)
+    assert np.isfinite(T).all() and np.isfinite(r).all()
+
+
+def test_eps_at_the_fp32_edge():
+    """2^-25 is the largest eps that 1.0f - eps rounds away; 1e-8 is below it; the next float up survives"""
+    f = np.float32
+    assert f(1) - f(2.0 ** -25) == f(1) and f(1) - f(1e-8) == f(1)
+    assert f(1) - f(EPS_MIN) == np.nextafter(f(1), f(0))
 
 
 # ---- the host solve --------------------------------------------------------------------------------------------------------
@@ -252,6 +322,9 @@ def _driver():
     (["--mode", "paper", "--gicp-epsilon", "0.01"], True),           # only with --mode gicp
     (["--gicp-epsilon", "0.01"], True),
     (["--mode", "gicps"], True),
+    (["--mode", "gicp", "--gicp-epsilon", "2.98023259e-08"], False),   # the float above 2^-25: fl32(1 - eps) < 1
+    (["--mode", "gicp", "--gicp-epsilon", "2.98023224e-08"], True),    # 2^-25: 1.0f - eps == 1.0f
+    (["--mode", "gicp", "--gicp-epsilon", "1e-8"], True),
 ])
 def test_driver_mode_gicp_usage(tmp_path, args, usage):
     """--mode gicp and --gicp-epsilon pass the driver's argument checks (the missing files then fail with ERR_IO before any device

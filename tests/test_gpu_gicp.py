@@ -11,11 +11,13 @@ import numpy as np
 import pytest
 
 from _frames import scale_record
-from _gicp_ref import gicp_pass_record, gicp_record, gicp_terms
+import _record_ref as R
+from _gicp_ref import FP64_C, direct_record, fp64_excess, gicp_pass_record, gicp_record, gicp_terms
 from _plane_ref import plane_record, rot_err
 
 pytestmark = pytest.mark.gpu
 
+EPS_MIN = float(np.nextafter(np.float32(2.0 ** -25), np.float32(1)))     # the smallest eps accepted: fl32(1 - eps) = 1 - 2^-24
 SCALES = {"none": 1.0, "huber": 3.0, "tukey": 60.0, "cauchy": 6.0, "geman_mcclure": 12.0}   # (cat15: r = sqrt(d^T M d) spans ~0 .. 100)
 
 
@@ -82,14 +84,24 @@ def test_epsilon_setter(sym):
     for mode in (sym.MODE_GICP, sym.MODE_PAPER, sym.MODE_QUIRKS):        # accepted in every mode, read by GICP only
         with sym.Engine(mode=mode) as e:
             assert e.gicp_epsilon() == np.float32(1e-3)
-            for bad in (0.0, -1e-3, 1.5, float("nan"), float("inf"), -float("inf")):
+            # (2^-25 and 1e-8: 1.0f - eps == 1.0f, a pair of equal normals would be singular)
+            for bad in (0.0, -1e-3, 1.5, float("nan"), float("inf"), -float("inf"), 1e-8, 2.0 ** -25):
                 with pytest.raises(sym.SymmIcpError) as x:
                     e.set_gicp_epsilon(bad)
                 assert x.value.status == sym.ERR_ARG, bad
                 assert e.gicp_epsilon() == np.float32(1e-3)
-            for good in (1.0, 1e-6, 0.25):
+            for good in (1.0, 1e-6, 0.25, EPS_MIN):
                 e.set_gicp_epsilon(good)
                 assert e.gicp_epsilon() == np.float32(good)
+            with pytest.raises(sym.SymmIcpError):
+                e.set_gicp_epsilon(2.0 ** -25)
+            assert e.gicp_epsilon() == np.float32(EPS_MIN)              # a refused eps leaves the one set before
+        import ctypes as C
+        with sym.Engine(mode=mode) as e:                                  # the C ABI itself
+            L = sym.lib()
+            for bad in (1e-8, 2.0 ** -25):
+                assert L.symmicp_set_gicp_epsilon(e._h, C.c_float(bad)) == sym.ERR_ARG
+            assert L.symmicp_set_gicp_epsilon(e._h, C.c_float(EPS_MIN)) == 0
 
 
 def test_gicp_needs_source_normals(sym, cat15):
@@ -168,6 +180,8 @@ def test_fused_pass_record(sym, oracle, c4, loss):
         keep = idx >= 0
         args = (p[keep], pn[keep], d["tgt"][idx[keep]], d["tgt_n"][idx[keep]], e.pivot())
         S, M = gicp_record(*args, 1e-3, sym.loss_code(loss), scale)
+        if loss == "none":          # the fused loop's final pairs against the fp64 definition
+            assert fp64_excess(S, M, direct_record(*args, 1e-3), 1e-3) <= FP64_C
         if loss != "none":
             w = gicp_terms(*args, 1e-3, 1, scale)[0][:, 34]
             assert w.sum() < 0.9 * len(w)                              # the weights bite
@@ -175,6 +189,91 @@ def test_fused_pass_record(sym, oracle, c4, loss):
         assert st == 0
         it = e.step()
         assert np.abs(it["increment"] - Xs).max() < 1e-6, (it["increment"], Xs)
+
+
+def edge_pairs():
+    """hand-placed pairs at the closed form's edges, 4 apart (every pairing pairs row i with row i), offsets of ~0.05:
+    a = b (cs clamps to 1: lambda_u = 2 eps), a = -b (u = 0, lambda_v = 2 eps), orthogonal normals, zero normals on either side and
+    on both (M = 1/2 I), slightly non-unit fp32 normals.  41 rows: the identity pass runs k_pass_identity<1>"""
+    s = np.float32(1.0000001)
+    A = [(0, 0, 1), (0.6, 0.8, 0), (0, 0, 1), (0.6, 0.8, 0), (1, 0, 0), (0, 0.6, 0.8), (0, 0, 0), (0, 1, 0), (0, 0, 0),
+         (0.6000001, 0.8, 0), (0, 0, s), (0.48, 0.6, 0.64)]
+    B = [(0, 0, 1), (0.6, 0.8, 0), (0, 0, -1), (-0.6, -0.8, 0), (0, 1, 0), (1, 0, 0), (0, 0, 1), (0, 0, 0), (0, 0, 0),
+         (0.6, 0.8000001, 0), (0, 0, s), (0.48, 0.6, 0.64)]
+    rng = np.random.default_rng(7)
+    n = 41
+    k = np.arange(n) % len(A)
+    g = np.stack(np.meshgrid(np.arange(4), np.arange(4), np.arange(3), indexing="ij"), -1).reshape(-1, 3)[:n]
+    tgt = (4.0 * g + 1.0).astype(np.float32)
+    src = (tgt + rng.uniform(-0.05, 0.05, size=(n, 3))).astype(np.float32)
+    sn = np.float32(A)[k]
+    tn = np.float32(B)[k]
+    return dict(src=src, src_n=sn, tgt=tgt, tgt_n=tn), k == 8
+
+
+@pytest.mark.parametrize("eps", [1.0, 1e-3, 1e-5, EPS_MIN])
+@pytest.mark.parametrize("corr", ["identity", "brute", "tree"])
+def test_edge_pairs_match_numpy_record(sym, corr, eps):
+    """the record of the edge pairs, every pairing, down to the smallest accepted eps: finite, the numpy record's (TOL_EXACT), and
+    the pairs with zero normals on both sides give the fp64 point-to-point record at weight 1/2 (M = 1/2 I)"""
+    d, zero = edge_pairs()
+    with sym.Engine(mode=sym.MODE_GICP, corr=_corr(sym, corr), max_iters=3, fixed_iters=1) as e:
+        e.set_gicp_epsilon(eps)
+        e.set_target(d["tgt"], d["tgt_n"])
+        e.set_source(d["src"], d["src_n"])
+        it = e.begin()
+        idx, _ = e.correspondences()
+        assert np.array_equal(idx, np.arange(len(d["src"])))
+        S, M, kept = gicp_pass_record(d["src"], d["src_n"], d["tgt"], d["tgt_n"], None, e.pivot(), eps)
+        assert np.isfinite(it["sums"]).all() and np.isfinite(S).all()
+        assert kept == len(d["src"])
+        R.assert_record(it["sums"], S, M, R.TOL_EXACT, "eps %g" % eps)
+    z = {k: v[zero] for k, v in d.items()}
+    with sym.Engine(mode=sym.MODE_GICP, corr=_corr(sym, corr), max_iters=3, fixed_iters=1) as e:
+        e.set_gicp_epsilon(eps)
+        e.set_target(z["tgt"], z["tgt_n"])
+        e.set_source(z["src"], z["src_n"])
+        gpu = np.asarray(e.begin()["sums"])
+        pv = e.pivot()
+        _, M, _ = gicp_pass_record(z["src"], z["src_n"], z["tgt"], z["tgt_n"], None, pv, eps)
+    # (the points about the pivot as the kernel forms them, in fp32; their differences are then exact)
+    P, Q = z["src"] - pv, z["tgt"] - pv
+    assert np.array_equal((P - Q).astype(np.float64), P.astype(np.float64) - Q.astype(np.float64))
+    D = direct_record(P, z["src_n"], Q, z["tgt_n"], np.zeros(3), eps)
+    sl = list(range(27)) + [35]
+    assert (np.abs(gpu[sl] - D[sl]) <= 1e-12 * np.maximum(M[sl], 1e-300)).all(), (gpu[sl], D[sl])
+
+
+def test_smallest_epsilon_cat_against_itself(sym, cat):
+    """eps = the float above 2^-25: the cat cloud against itself (every pair a = b, cs = 1, lambda_u = 2^-23) gives a finite
+    record, the numpy record's"""
+    with sym.Engine(mode=sym.MODE_GICP, corr=sym.CORR_IDENTITY, max_iters=3, fixed_iters=1) as e:
+        e.set_gicp_epsilon(EPS_MIN)
+        assert e.gicp_epsilon() == np.float32(EPS_MIN)
+        e.set_target(cat["src"], cat["src_n"])
+        e.set_source(cat["src"], cat["src_n"])
+        it = e.begin()
+        S, M, kept = gicp_pass_record(cat["src"], cat["src_n"], cat["src"], cat["src_n"], None, e.pivot(), EPS_MIN)
+    assert np.isfinite(it["sums"]).all() and np.isfinite(S).all()
+    R.assert_record(it["sums"], S, M, R.TOL_EXACT, "eps min")
+
+
+# ---- fp64: the record against the definition, not a restatement -------------------------------------------------------------------
+@pytest.mark.parametrize("corr", ["identity", "brute", "tree"])
+def test_first_pass_meets_the_fp64_bar(sym, cat15, corr):
+    """the first pass of every pairing against gicp_direct (np.linalg.inv(C_p + C_q) in fp64) at _gicp_ref's bar, FP64_C x
+    2^-24 / eps of each slot's magnitude: a mistake the kernel and gicp_terms shared (a wrong lambda, gamma_u and gamma_v swapped, a
+    lost 1/2 on the axis rows) fails here though it passes every restated-record test"""
+    d = cat15
+    with sym.Engine(mode=sym.MODE_GICP, corr=_corr(sym, corr), max_iters=3, fixed_iters=1) as e:
+        e.set_target(d["tgt"], d["tgt_n"])
+        e.set_source(d["src"], d["src_n"])
+        gpu = np.asarray(e.begin()["sums"])
+        idx, _ = e.correspondences()
+        pv = e.pivot()
+    _, M, _ = gicp_pass_record(d["src"], d["src_n"], d["tgt"], d["tgt_n"], idx, pv)
+    D = direct_record(d["src"], d["src_n"], d["tgt"][idx], d["tgt_n"][idx], pv, 1e-3)
+    assert fp64_excess(gpu, M, D, 1e-3) <= FP64_C, fp64_excess(gpu, M, D, 1e-3)
 
 
 # ---- 3. epsilon and the normals ---------------------------------------------------------------------------------------------------

@@ -8,7 +8,9 @@ own moved source, its pairs (checked bit for bit against the oracle's brute forc
   2. the gate boundaries: pairs exactly at max_d2 and min_ndot and one ulp either side, through every pass kernel;
   3. sharded runs of every pairing (external exchange, unaligned shares);
   4. the device-driven loop with gates against the host loop."""
+import math
 import os
+import re
 import subprocess
 import sys
 
@@ -30,7 +32,7 @@ def sym():
 
 
 def mode_code(sym, mode):
-    return {"quirks": sym.MODE_QUIRKS, "paper": sym.MODE_PAPER, "p2p": sym.MODE_P2P, "plane": sym.MODE_PLANE}[mode]
+    return {"quirks": sym.MODE_QUIRKS, "paper": sym.MODE_PAPER, "p2p": sym.MODE_P2P, "plane": sym.MODE_PLANE, "gicp": sym.MODE_GICP}[mode]
 
 
 def corr_code(sym, corr):
@@ -56,11 +58,12 @@ def pass_record(e, d, mode, loss, scale, max_d2, min_ndot, incremental, identity
 
 
 # ---- 1. the matrix ----------------------------------------------------------------------------------------------------
-MODES = ["quirks", "paper", "p2p", "plane"]
+MODES = ["quirks", "paper", "p2p", "plane", "gicp"]          # (appended: earlier cases keep their ids and sizes)
 CORRS = ["identity", "brute", "tree"]
 GATES = ["none", "dist", "normal", "both"]
 SIZES = [3400, 1201, 2002, 203]            # 0, 1, 2, 3 mod 4 (203 < one block of 256)
-HUBER = {"quirks": 1.0, "paper": 2.0, "p2p": None, "plane": 1.0}          # cat: c of the 15-degree start spans ~0 .. 100
+# cat: c of the 15-degree start spans ~0 .. 100 (GICP: r = sqrt(d^T M d), test_gpu_gicp.py's scale)
+HUBER = {"quirks": 1.0, "paper": 2.0, "p2p": None, "plane": 1.0, "gicp": 3.0}
 MATRIX = [(m, c, g, l, a) for m in MODES for c in CORRS for g in GATES for l in ("none", "huber") for a in ("incr", "cumul")
           if not (m == "quirks" and l == "huber")]
 N_PASSES = 4
@@ -133,18 +136,22 @@ def test_matrix_identity_grid_stride_in_a_subprocess(sym):
     if os.environ.get("SYMMICP_ID_BLOCKS"):
         pytest.skip("already the child")
     env = dict(os.environ, SYMMICP_ID_BLOCKS="1", SYMMICP_PASS_BLOCKS="1")
+    n_ident = sum(1 for c in MATRIX if c[1] == "identity")            # (every mode's, GICP's included)
     r = subprocess.run([sys.executable, "-m", "pytest", os.path.abspath(__file__), "-q", "-x", "-m", "gpu", "-p", "no:cacheprovider",
-                        "-k", "test_matrix and identity and not subprocess", "-W", "ignore"],
+                        "-k", "test_matrix and identity and not subprocess and not kernels", "-W", "ignore"],
                        env=env, capture_output=True, text=True, timeout=900, cwd=os.path.dirname(HERE))
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-2000:]
-    assert " passed" in r.stdout and "failed" not in r.stdout
+    assert re.search(r"\b%d passed" % n_ident, r.stdout) and "failed" not in r.stdout, r.stdout[-500:]
 
 
 def test_matrix_takes_both_identity_kernels():
-    """the sizes reach k_pass_identity<1> (the run_pass vec4 test: n, n_t and the shard offset all multiples of 4) and <4>"""
-    ident = [SIZES[MATRIX.index(c) % len(SIZES)] for c in MATRIX if c[1] == "identity"]
-    assert {n % 4 for n in ident} == {0, 1, 2, 3}
-    assert min(ident) < 256
+    """the sizes reach k_pass_identity<1> (the run_pass vec4 test: n, n_t and the shard offset all multiples of 4) and <4>, in every
+    mode on its own (each mode has its own instantiations), and the one-block grid"""
+    for mode in [None] + MODES:
+        ident = [SIZES[MATRIX.index(c) % len(SIZES)] for c in MATRIX if c[1] == "identity" and mode in (None, c[0])]
+        assert {n % 4 for n in ident} == {0, 1, 2, 3}, mode
+        assert min(ident) < 256, mode
+    assert sum(1 for c in MATRIX if c[0] == "gicp") == 48
 
 
 # ---- the fused pass ---------------------------------------------------------------------------------------------------------
@@ -166,7 +173,7 @@ def with_converged_gates(d, flip=7):
     idx = R.nn_ref(p, d["tgt"])[0]
     pn = R.moved(d["truth"], d["src"][::10], d["src_n"][::10], R.MODE_PAPER)[1]
     d["c_scale"] = {m: float(np.quantile(np.abs(R.pass_terms(m, p, pn, d["tgt"][idx], d["tgt_n"][idx], np.zeros(3, np.float32))[1]), 0.9))
-                    for m in (R.MODE_PAPER, R.MODE_PLANE)}
+                    for m in (R.MODE_PAPER, R.MODE_PLANE, R.MODE_GICP)}
     return d
 
 
@@ -190,7 +197,8 @@ def assert_gates_bite(n, kept, far_only, bent_only):
     assert 0 < kept < n - far_only - bent_only + 1, (kept, n)
 
 
-@pytest.mark.parametrize("mode,loss", [("paper", "none"), ("paper", "huber"), ("plane", "none"), ("plane", "huber")])
+@pytest.mark.parametrize("mode,loss", [("paper", "none"), ("paper", "huber"), ("plane", "none"), ("plane", "huber"), ("gicp", "none"),
+                                       ("gicp", "huber")])
 def test_fused_pass_record_with_both_gates(sym, c4, mode, loss):
     """a converged alignment runs pass after pass on the device (k_pass_fused), both gates biting in those passes.  The record the
     device loop leaves must be the numpy record of the pairs it left: its diff (slot 33) is the last device pass's, and the next host
@@ -227,97 +235,117 @@ def test_fused_pass_record_with_both_gates(sym, c4, mode, loss):
 
 
 # ---- 2. gate boundaries -------------------------------------------------------------------------------------------------------
+GRID = 2.0 ** -15       # every coordinate and offset of the boundary data: their sums, differences and squares are exact in fp32
+
+
 def exact_offset(t):
-    """an offset (a, b, 0) -- a on a 2^-12 grid, b free -- whose fp32 dist2 from the origin is exactly t"""
+    """an offset (a, b, 0) -- a >= b >= 0 on the 2^-15 grid -- whose fp32 dist2 from the origin is exactly t (a^2 + b^2 = t with
+    no rounding; t in [2^-7, 2^-6), on its 2^-30 grid), or None"""
     t = np.float32(t)
-    a0 = np.round(np.sqrt(float(t) / 2) * 4096)
-    for ka in range(40):
-        a = np.float32((a0 + ka) / 4096)
-        rest = float(t) - float(a) * float(a)
-        if rest <= 0:
-            continue
-        b = np.float32(np.sqrt(rest))
-        for _ in range(64):
-            b = np.nextafter(b, np.float32(0))
-        for _ in range(128):
-            if np.float32(a * a) + np.float32(b * b) == t:
-                return np.array([a, b, 0], np.float32)
-            b = np.nextafter(b, np.float32(1))
-    raise AssertionError("no exact offset for %r" % t)
+    T = float(t) / GRID ** 2
+    assert T == int(T)
+    T = int(T)
+    for A in range(math.isqrt(T // 2), math.isqrt(T) + 1):
+        B = math.isqrt(max(T - A * A, 0))
+        if A >= B and A * A + B * B == T:
+            off = np.array([A * GRID, B * GRID, 0], np.float32)
+            assert R.dist2(off[None], np.zeros((1, 3), np.float32))[0] == t
+            return off
+    return None
 
 
-# max_corr_dist whose fp32 square differs from the fp32 rounding of its double square: an engine that squared in double would keep
-# (or drop) the pairs one ulp off
+# max_corr_dist whose fp32 square differs from the fp32 rounding of its double square (an engine that squared in double would keep
+# or drop the pairs one ulp off) and whose square, one ulp below and one above are each the fp32 dist2 of a grid offset
 def pinned_mcd():
     for k in range(1, 100000):
         m = 0.1 + k * 1e-6
-        if R.f32_max_d2(m) != np.float32(m * m):
+        M = R.f32_max_d2(m)
+        if M != np.float32(m * m) and all(exact_offset(t) is not None
+                                          for t in (np.nextafter(M, np.float32(0)), M, np.nextafter(M, np.float32(1)))):
             return m
     raise AssertionError
 
 
+# three rows +, three rows - in a 3 x 3 block of the (x, z) lattice whose two centroids agree: +-signed offsets on them add up to
+# zero, and so do their moments (sum of s_r q_r x off = 0)
+BALANCED = [((0, 0), 1), ((2, 1), 1), ((1, 2), 1), ((2, 0), -1), ((0, 2), -1), ((1, 1), -1)]
+
+
 def boundary_data(n_cells, mcd, mnd):
     """source row i sits next to target row i on a 3-D lattice of spacing 4 (the pairing of every kind is row i -> row i):
-    18 rows at d2 = max_d2 - 1 ulp, max_d2, max_d2 + 1 ulp (6 each; target on y = 0, offset in x and y, so that p - q is exact);
+    18 rows at d2 = max_d2 - 1 ulp, max_d2, max_d2 + 1 ulp (6 each, offsets in x and y; normals along z);
     18 rows at ndot = min_ndot - 1 ulp, min_ndot, min_ndot + 1 ulp (normals along z, offset along y); the rest on their target
-    with axis normals.  Every offset lies in the plane of its normals (c = 0 for every pair) and comes with its negative (the
-    centroids agree): the solve returns the identity, and the points stay where they are pass after pass."""
+    with axis normals.  Every offset lies in the plane of its normals (c = 0 for every pair: PAPER, PLANE and GICP's u and v
+    rows) and every six rows of one offset are signed as BALANCED (a y level each), so that the offsets and their moments about
+    any point cancel exactly (GICP's axis rows, 1/2 J^T d): the solve returns the identity, and the points stay where they are pass
+    after pass."""
     g = int(np.ceil(n_cells ** (1 / 3)))
     L = np.stack(np.meshgrid(np.arange(g), np.arange(g), np.arange(g), indexing="ij"), -1).reshape(-1, 3)[:n_cells]
+    row = {tuple(v): i for i, v in enumerate(L)}
     tgt = (4.0 * L).astype(np.float32)
     src = tgt.copy()
     axes = np.eye(3, dtype=np.float32)
     tn = axes[np.arange(n_cells) % 3].copy()
     sn = tn.copy()
-    on_y0 = np.flatnonzero(L[:, 1] == 0)
-    d_rows = on_y0[:18]
-    n_rows = np.setdiff1d(np.arange(n_cells), on_y0)[:18]
+    # the six rows of group k: y level k, x in 0..2, z in 0..2 (distance rows) or 3..5 (normal rows)
+    group = lambda k, z0: [(row[(x, k, z0 + z)], sg) for (x, z), sg in BALANCED]                  # noqa: E731
+    d_rows, n_rows = [], []
     M = R.f32_max_d2(mcd)
     for k, t in enumerate([np.nextafter(M, np.float32(0)), M, np.nextafter(M, np.float32(1))]):
-        off = exact_offset(t)                         # in x, y; normals along z
-        for h, r in enumerate(d_rows[6 * k:6 * k + 6]):
-            src[r] = tgt[r] + off if h % 2 else tgt[r] - off
+        off = exact_offset(t)
+        for r, sg in group(k, 0):
+            src[r] = tgt[r] + np.float32(sg) * off
             assert R.dist2(src[r:r + 1], tgt[r:r + 1])[0] == t
             sn[r] = tn[r] = (0, 0, 1)
+            d_rows.append(r)
     G = np.float32(mnd)
     for k, t in enumerate([np.nextafter(G, np.float32(-1)), G, np.nextafter(G, np.float32(2))]):
-        for h, r in enumerate(n_rows[6 * k:6 * k + 6]):
-            src[r] = tgt[r] + np.float32([0, 0.0625 if h % 2 else -0.0625, 0])
+        for r, sg in group(k, 3):
+            src[r] = tgt[r] + np.float32([0, 0.0625 * sg, 0])
             sn[r] = (0, 0, 1)
             tn[r] = (0, 0, t)
+            n_rows.append(r)
     d = dict(src=src, src_n=sn, tgt=tgt, tgt_n=tn)
     keep = R.gate(src, sn, tgt, tn, M, G)
     drop = np.concatenate([d_rows[12:], n_rows[:6]])
     assert keep.sum() == n_cells - 12 and not keep[drop].any()     # exactly the 6 + 6 rows beyond a bound drop
+    off = (src - tgt).astype(np.float64)
+    assert not off.sum(0).any() and not np.cross(tgt.astype(np.float64), off).sum(0).any()
     return d
 
 
-@pytest.mark.parametrize("corr,n", [("identity", 216), ("identity", 215), ("identity", 217), ("brute", 215), ("tree", 215)])
-def test_gate_boundaries_are_kept(sym, corr, n):
+BOUNDARY_CASES = [("identity", 216), ("identity", 215), ("identity", 217), ("brute", 215), ("tree", 215)]
+
+
+# (PAPER's cases keep the ids they had before GICP's joined them)
+@pytest.mark.parametrize("mode,corr,n", [pytest.param(m, c, n, id=("" if m == "paper" else m + "-") + "%s-%d" % (c, n))
+                                         for m in ("paper", "gicp") for c, n in BOUNDARY_CASES])
+def test_gate_boundaries_are_kept(sym, mode, corr, n):
     """the first pass (identity transform) over the boundary pairs: k_pass_identity<4> (n = 216) and <1>, k_pass_indexed, k_accumulate"""
     mcd, mnd = pinned_mcd(), 0.75
     d = boundary_data(n, mcd, mnd)
     M = R.f32_max_d2(mcd)
-    with sym.Engine(mode=sym.MODE_PAPER, corr=corr_code(sym, corr), max_iters=3, fixed_iters=1, max_corr_dist=mcd, min_normal_dot=mnd) as e:
+    m = mode_code(sym, mode)
+    with sym.Engine(mode=m, corr=corr_code(sym, corr), max_iters=3, fixed_iters=1, max_corr_dist=mcd, min_normal_dot=mnd) as e:
         e.set_target(d["tgt"], d["tgt_n"])
         e.set_source(d["src"], d["src_n"])
         it = e.begin()
         idx, d2 = e.correspondences()
         assert np.array_equal(idx, np.arange(n)) and np.array_equal(d2, R.dist2(d["src"], d["tgt"]))
-        S, Mg, kept = R.record(sym.MODE_PAPER, d["src"], d["src_n"], d["tgt"], d["tgt_n"], None, e.pivot(), 0, 1.0, M, mnd)
+        S, Mg, kept = R.record(m, d["src"], d["src_n"], d["tgt"], d["tgt_n"], None, e.pivot(), 0, 1.0, M, mnd)
         assert kept == n - 12
         assert it["sums"][34] == kept, (it["sums"][34], kept)
         R.assert_record(it["sums"], S, Mg, R.TOL_EXACT, "begin")
 
 
-@pytest.mark.parametrize("mode", ["paper", "plane"])
+@pytest.mark.parametrize("mode", ["paper", "plane", "gicp"])
 def test_gate_boundaries_through_the_fused_pass(sym, mode):
     """the device-driven loop over the boundary pairs: k_pass_fused's fused_accumulate gates.  The diff of every pass (slot 33,
     sum of sqrt(d2) over the kept pairs) counts the kept distance-boundary and normal-boundary pairs"""
     mcd, mnd = pinned_mcd(), 0.75
     n = 216
     d = boundary_data(n, mcd, mnd)
-    m = mode_code(sym, mode)                          # (fused_accumulate's PLANE and non-PLANE branches gate apart)
+    m = mode_code(sym, mode)                          # (each OBJ instantiation of the fused pass gates on its own)
     M = R.f32_max_d2(mcd)
     with sym.Engine(mode=m, corr=sym.CORR_TREE, max_iters=12, fixed_iters=1, max_corr_dist=mcd, min_normal_dot=mnd) as e:
         e.set_target(d["tgt"], d["tgt_n"])
@@ -340,7 +368,7 @@ def test_max_d2_is_the_fp32_square():
 
 # ---- 3. sharded pass kinds -------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("world", [3, 5])
-@pytest.mark.parametrize("mode", ["paper", "p2p", "plane"])
+@pytest.mark.parametrize("mode", ["paper", "p2p", "plane", "gicp"])
 @pytest.mark.parametrize("corr", ["identity", "brute", "tree"])
 def test_sharded_pass_kinds(sym, cat, world, mode, corr):
     """external exchange over `world` ranks (shares whose offsets are not all multiples of 4),
@@ -443,21 +471,24 @@ def identity_with_outliers(cat):
     return dict(d, mcd=mcd)
 
 
-@pytest.mark.parametrize("case", ["paper_tree", "plane_tree", "paper_identity_ragged", "paper_tree_stragglers"])
+@pytest.mark.parametrize("case", ["paper_tree", "plane_tree", "paper_identity_ragged", "paper_tree_stragglers", "gicp_tree",
+                                  "gicp_identity_ragged"])
 def test_device_loop_with_gates_matches_host_loop(sym, cat, c4, case, request):
     """as test_device_loop_matches_host_loop (test_gpu_parity.py), with both gates biting in the passes the device runs: the last
     device pass's diff (slot 33) is the numpy record's at the final pose, with the gates' drops"""
-    mnd = 0.5 if case == "paper_identity_ragged" else 0.0
-    if case == "paper_identity_ragged":
+    mode = mode_code(sym, case.split("_")[0])
+    ragged = case.endswith("_identity_ragged")
+    mnd = 0.5 if ragged else 0.0
+    if ragged:
         d = identity_with_outliers(cat)
         assert len(d["src"]) % 4 != 0
-        kw = dict(mode=sym.MODE_PAPER, corr=sym.CORR_IDENTITY, max_iters=8, fixed_iters=1)
+        kw = dict(mode=mode, corr=sym.CORR_IDENTITY, max_iters=8, fixed_iters=1)
     elif case == "paper_tree_stragglers":
         d = request.getfixturevalue("c5s")
-        kw = dict(mode=sym.MODE_PAPER, corr=sym.CORR_TREE, max_iters=40, fixed_iters=1)
+        kw = dict(mode=mode, corr=sym.CORR_TREE, max_iters=40, fixed_iters=1)
     else:
         d = c4
-        kw = dict(mode=sym.MODE_PAPER if case == "paper_tree" else sym.MODE_PLANE, corr=sym.CORR_TREE, max_iters=25, fixed_iters=1)
+        kw = dict(mode=mode, corr=sym.CORR_TREE, max_iters=25, fixed_iters=1)
     kw.update(max_corr_dist=d["mcd"], min_normal_dot=mnd)
     res = {}
     for host_loop in (1, 0):
@@ -467,7 +498,7 @@ def test_device_loop_with_gates_matches_host_loop(sym, cat, c4, case, request):
             r = e.align()
             st = e.stats()
             if host_loop == 0:
-                if case == "paper_identity_ragged":
+                if ragged:
                     p, pn = R.moved(e.transform(), d["src"], d["src_n"], kw["mode"])
                     S, _, kept = R.record(kw["mode"], p, pn, d["tgt"], d["tgt_n"], None, e.pivot(), 0, 1.0, R.f32_max_d2(d["mcd"]), mnd)
                     q, qn = d["tgt"], d["tgt_n"]
