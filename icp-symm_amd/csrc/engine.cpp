@@ -974,6 +974,194 @@ int symmicp_estimate_normals(int device, const float *xyz, size_t row_stride, si
     return st;
 }
 
+// ---- radius search and FPFH features (kernels_fpfh.hip; DESIGN.md 4, "FPFH features and radius search") ------------------
+// Both run like the normals pre-step: upload the caller's cloud, build the box tree over its Morton order behind the target's
+// arrays in the keep-arena, walk it per point, release everything again.  The context's own clouds, index and certificates
+// are not touched.
+struct ScratchIndex {
+    size_t keep_off0 = 0, extra0 = 0;
+    bool surf0 = false;
+    TargetIndex ix{};
+};
+
+static void scratch_index_end(symmicp_ctx *c, const ScratchIndex &si)
+{
+    (void)hipStreamSynchronize(c->stream);
+    while (c->keep_extra.size() > si.extra0) { hipFree(c->keep_extra.back()); c->keep_extra.pop_back(); }
+    c->keep.off = si.keep_off0;
+    c->target_surface_like = si.surf0;
+}
+
+// nrm may be NULL (zero normals).  temp_bytes: what the caller will take from the arena afterwards.  On failure everything is released.
+static int scratch_index_begin(symmicp_ctx *c, const float *xyz, size_t xr, size_t xc, const float *nrm, size_t nr, size_t nc, size_t n,
+                               size_t temp_bytes, ScratchIndex &si)
+{
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (c->keep.cap == 0) {
+        // no target yet: give the keep-arena the size this cloud needs (a later set_target reuses it)
+        const size_t want = n * 96 + ((size_t)4 << 20);
+        if (hipMalloc((void **)&c->keep.base, want) == hipSuccess) { c->keep.cap = want; c->keep.off = 0; }
+        else (void)hipGetLastError();
+    }
+    si.keep_off0 = c->keep.off;
+    si.extra0 = c->keep_extra.size();
+    si.surf0 = c->target_surface_like;
+    arena_begin(c->arena, n * (96 + 4 * (xr + (nrm ? nr : 0))) + temp_bytes + ((size_t)1 << 20));
+    float *block = nullptr;
+    {
+        DevBuf<float> b;
+        int st = upload_planar(c, xyz, xr, xc, nrm, nr, nc, n, b, /*temp=*/false, nullptr);
+        if (st != SYMMICP_OK) { scratch_index_end(c, si); return st; }
+        block = b.release();
+    }
+    CloudSoA cl;
+    soa_from_block(block, n, cl);
+    float4 *tq = nullptr, *tn = nullptr, *boxes = nullptr;
+    uint2 *cells = nullptr;
+    if (keep_alloc(c, (void **)&tq, sizeof(float4) * (n + 8)) != hipSuccess || keep_alloc(c, (void **)&tn, sizeof(float4) * 2 * n) != hipSuccess) {
+        (void)hipGetLastError();
+        scratch_index_end(c, si);
+        return fail(c, SYMMICP_ERR_HIP, "out of device memory");
+    }
+    int st = build_index(c, cl, (uint32_t)n, /*want_grid=*/false, tq, tn, &boxes, &cells, &si.ix, nullptr, nullptr);
+    if (st != SYMMICP_OK) scratch_index_end(c, si);
+    return st;
+}
+
+static const char *radius_args_error(const float *xyz, size_t n, float radius, const int32_t *count_out, const int64_t *offsets_out,
+                                     const int32_t *rows_out, const size_t *total_out)
+{
+    if (!xyz || !count_out || !total_out) return "radius_search: xyz, count_out and total_out are required";
+    if (rows_out && !offsets_out) return "radius_search: rows_out needs offsets_out";
+    if (n == 0 || n > 0x7fffffffull) return "radius_search: n must be in 1 .. 2^31 - 1";
+    if (!std::isfinite(radius) || !(radius > 0.f)) return "radius_search: radius must be finite and > 0";
+    return nullptr;
+}
+
+static int radius_search(symmicp_ctx *c, const float *xyz, size_t xr, size_t xc, size_t n, float radius, int32_t *count_out,
+                         int64_t *offsets_out, int32_t *rows_out, float *d2_out, size_t cap, size_t *total_out)
+{
+    ScratchIndex si;
+    int st = scratch_index_begin(c, xyz, xr, xc, nullptr, 0, 0, n, n * 8 + 8192, si);
+    if (st != SYMMICP_OK) return st;
+    const float r2 = radius * radius;
+    // the body in a lambda: every exit goes through scratch_index_end
+    auto body = [&]() -> int {
+        DevBuf<int32_t> d_count, d_rows;
+        DevBuf<uint32_t> d_offs, scan_ws;
+        DevBuf<float> d_d2;
+        HIP_TRY(c, d_count.alloc_temp(c->arena, n));
+        HIP_TRY(c, d_offs.alloc_temp(c->arena, n));
+        HIP_TRY(c, scan_ws.alloc_temp(c->arena, n / 2048 + 2));
+        launch_radius_count(si.ix, r2, d_count.p, c->stream);
+        HIP_TRY(c, hipMemcpyAsync(d_offs.p, d_count.p, sizeof(uint32_t) * n, hipMemcpyDeviceToDevice, c->stream));
+        launch_exclusive_scan(d_offs.p, (uint32_t)n, scan_ws.p, c->stream);
+        HIP_TRY(c, hipMemcpyAsync(count_out, d_count.p, sizeof(int32_t) * n, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        HIP_TRY(c, hipGetLastError());
+        uint64_t total = 0;
+        for (size_t i = 0; i < n; i++) total += (uint64_t)(uint32_t)count_out[i];
+        *total_out = (size_t)total;
+        if (offsets_out) {
+            int64_t at = 0;
+            for (size_t i = 0; i < n; i++) { offsets_out[i] = at; at += count_out[i]; }
+            offsets_out[n] = at;
+        }
+        if (!rows_out) return SYMMICP_OK;
+        if (total > cap) return fail(c, SYMMICP_ERR_SIZE, "radius_search: " + std::to_string(total) + " neighbours do not fit cap " + std::to_string(cap));
+        // the device's offsets are 32-bit words (launch_exclusive_scan)
+        if (total > 0xffffffffull) return fail(c, SYMMICP_ERR_SIZE, "radius_search: more than 2^32 - 1 neighbours in all; use a smaller radius or split the cloud");
+        if (total == 0) return SYMMICP_OK;
+        HIP_TRY(c, d_rows.alloc_temp(c->arena, total));
+        if (d2_out) HIP_TRY(c, d_d2.alloc_temp(c->arena, total));
+        launch_radius_fill(si.ix, r2, d_offs.p, d_rows.p, d_d2.p, c->stream);
+        HIP_TRY(c, hipMemcpyAsync(rows_out, d_rows.p, sizeof(int32_t) * total, hipMemcpyDeviceToHost, c->stream));
+        if (d2_out) HIP_TRY(c, hipMemcpyAsync(d2_out, d_d2.p, sizeof(float) * total, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        HIP_TRY(c, hipGetLastError());
+        return SYMMICP_OK;
+    };
+    st = body();
+    scratch_index_end(c, si);
+    return st;
+}
+
+int symmicp_ctx_radius_search(symmicp_ctx *c, const float *xyz, size_t row_stride, size_t col_stride, size_t n, float radius,
+                              int32_t *count_out, int64_t *offsets_out, int32_t *rows_out, float *d2_out, size_t cap, size_t *total_out)
+{
+    if (!c) return SYMMICP_ERR_ARG;
+    if (const char *msg = radius_args_error(xyz, n, radius, count_out, offsets_out, rows_out, total_out)) return fail(c, SYMMICP_ERR_ARG, msg);
+    return radius_search(c, xyz, row_stride, col_stride, n, radius, count_out, offsets_out, rows_out, d2_out, cap, total_out);
+}
+
+int symmicp_radius_search(int device, const float *xyz, size_t row_stride, size_t col_stride, size_t n, float radius, int32_t *count_out,
+                          int64_t *offsets_out, int32_t *rows_out, float *d2_out, size_t cap, size_t *total_out)
+{
+    if (radius_args_error(xyz, n, radius, count_out, offsets_out, rows_out, total_out)) return SYMMICP_ERR_ARG;
+    symmicp_config cfg;
+    symmicp_config_default(&cfg);
+    cfg.device = device;
+    symmicp_ctx *c = nullptr;
+    int st = symmicp_create(&cfg, &c);
+    if (st != SYMMICP_OK) return st;
+    st = symmicp_ctx_radius_search(c, xyz, row_stride, col_stride, n, radius, count_out, offsets_out, rows_out, d2_out, cap, total_out);
+    symmicp_destroy(c);
+    return st;
+}
+
+static const char *fpfh_args_error(const float *xyz, const float *nrm, size_t n, float radius, const float *fpfh_out)
+{
+    if (!xyz || !nrm || !fpfh_out) return "fpfh: xyz, nrm and fpfh_out are required";
+    if (n == 0 || n > 0x7fffffffull) return "fpfh: n must be in 1 .. 2^31 - 1";
+    if (!std::isfinite(radius) || !(radius > 0.f)) return "fpfh: radius must be finite and > 0";
+    return nullptr;
+}
+
+int symmicp_ctx_fpfh(symmicp_ctx *c, const float *xyz, size_t xyz_row_stride, size_t xyz_col_stride, const float *nrm, size_t nrm_row_stride,
+                     size_t nrm_col_stride, size_t n, float radius, float *fpfh_out, float *spfh_out, int32_t *count_out)
+{
+    if (!c) return SYMMICP_ERR_ARG;
+    if (const char *msg = fpfh_args_error(xyz, nrm, n, radius, fpfh_out)) return fail(c, SYMMICP_ERR_ARG, msg);
+    ScratchIndex si;
+    int st = scratch_index_begin(c, xyz, xyz_row_stride, xyz_col_stride, nrm, nrm_row_stride, nrm_col_stride, n, n * (36 + 33 + 33 + 1) * 4 + 8192, si);
+    if (st != SYMMICP_OK) return st;
+    const float r2 = radius * radius;
+    auto body = [&]() -> int {
+        DevBuf<float> d_sorted, d_spfh, d_fpfh;
+        DevBuf<int32_t> d_count;
+        HIP_TRY(c, d_sorted.alloc_temp(c->arena, n * 36));
+        HIP_TRY(c, d_fpfh.alloc_temp(c->arena, n * 33));
+        HIP_TRY(c, d_count.alloc_temp(c->arena, n));
+        if (spfh_out) HIP_TRY(c, d_spfh.alloc_temp(c->arena, n * 33));
+        launch_spfh(si.ix, r2, d_sorted.p, d_spfh.p, d_count.p, c->stream);
+        launch_fpfh(si.ix, r2, d_sorted.p, d_fpfh.p, c->stream);
+        HIP_TRY(c, hipMemcpyAsync(fpfh_out, d_fpfh.p, sizeof(float) * 33 * n, hipMemcpyDeviceToHost, c->stream));
+        if (spfh_out) HIP_TRY(c, hipMemcpyAsync(spfh_out, d_spfh.p, sizeof(float) * 33 * n, hipMemcpyDeviceToHost, c->stream));
+        if (count_out) HIP_TRY(c, hipMemcpyAsync(count_out, d_count.p, sizeof(int32_t) * n, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        HIP_TRY(c, hipGetLastError());
+        return SYMMICP_OK;
+    };
+    st = body();
+    scratch_index_end(c, si);
+    return st;
+}
+
+int symmicp_fpfh(int device, const float *xyz, size_t xyz_row_stride, size_t xyz_col_stride, const float *nrm, size_t nrm_row_stride,
+                 size_t nrm_col_stride, size_t n, float radius, float *fpfh_out, float *spfh_out, int32_t *count_out)
+{
+    if (fpfh_args_error(xyz, nrm, n, radius, fpfh_out)) return SYMMICP_ERR_ARG;
+    symmicp_config cfg;
+    symmicp_config_default(&cfg);
+    cfg.device = device;
+    symmicp_ctx *c = nullptr;
+    int st = symmicp_create(&cfg, &c);
+    if (st != SYMMICP_OK) return st;
+    st = symmicp_ctx_fpfh(c, xyz, xyz_row_stride, xyz_col_stride, nrm, nrm_row_stride, nrm_col_stride, n, radius, fpfh_out, spfh_out, count_out);
+    symmicp_destroy(c);
+    return st;
+}
+
 // ---- voxel-grid downsampling (kernels_voxel.hip; DESIGN.md 4, "Voxel downsampling") ---------------------------------------
 // Box (launch_bbox) -> grid set-up here in fp32 -> keys -> stable radix sort of (key, row) -> run heads, scan, first positions ->
 // kept voxels (>= min_points), scan, compaction -> sorted SoA gather -> per-voxel sequential means.  Temporaries come from the

@@ -267,4 +267,12 @@ void launch_voxel_mean(const CloudSoA &sorted, const uint32_t *kfirst, const uin
 void launch_voxel_of(const uint32_t *keys, const uint32_t *rows, const uint32_t *vid_excl, const uint32_t *first, const uint32_t *kid_excl,
                      uint32_t n, uint32_t min_points, int32_t *voxel_of, hipStream_t s);
 
+// radius search and FPFH (kernels_fpfh.hip; symmicp_ctx_radius_search, symmicp_ctx_fpfh): one thread per sorted point, the box-tree
+// walk with the fixed bound r2.  count / offs / spfh_rows / fpfh_rows are indexed by ORIGINAL row, spfh_sorted ([n][36] floats)
+// by sorted position; the fill pass writes list `row` from offs[row] on, in ascending sorted position.
+void launch_radius_count(const TargetIndex &ix, float r2, int32_t *count_rows, hipStream_t s);
+void launch_radius_fill(const TargetIndex &ix, float r2, const uint32_t *offs_rows, int32_t *rows_out, float *d2_out, hipStream_t s);
+void launch_spfh(const TargetIndex &ix, float r2, float *spfh_sorted, float *spfh_rows /* may be null */, int32_t *count_rows, hipStream_t s);
+void launch_fpfh(const TargetIndex &ix, float r2, const float *spfh_sorted, float *fpfh_rows, hipStream_t s);
+
 }  // namespace symmicp

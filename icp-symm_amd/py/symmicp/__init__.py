@@ -92,6 +92,7 @@ EXPORTS = [
     "symmicp_set_robust_loss", "symmicp_get_robust_loss", "symmicp_robust_weight", "symmicp_set_gicp_epsilon", "symmicp_get_gicp_epsilon",
     "symmicp_ctx_solve_probe", "symmicp_ctx_loop_solve", "symmicp_set_loop_log", "symmicp_get_loop_log",
     "symmicp_voxel_downsample", "symmicp_ctx_voxel_downsample",
+    "symmicp_radius_search", "symmicp_ctx_radius_search", "symmicp_fpfh", "symmicp_ctx_fpfh",
 ]
 
 _lib = None
@@ -173,6 +174,12 @@ def lib():
            C.POINTER(C.c_size_t)]
     L.symmicp_voxel_downsample.argtypes = [C.c_int] + vox
     L.symmicp_ctx_voxel_downsample.argtypes = [vp] + vox
+    rad = [fp, C.c_size_t, C.c_size_t, C.c_size_t, C.c_float, i32p, C.POINTER(C.c_int64), i32p, fp, C.c_size_t, C.POINTER(C.c_size_t)]
+    L.symmicp_radius_search.argtypes = [C.c_int] + rad
+    L.symmicp_ctx_radius_search.argtypes = [vp] + rad
+    fpf = [fp, C.c_size_t, C.c_size_t, fp, C.c_size_t, C.c_size_t, C.c_size_t, C.c_float, fp, fp, i32p]
+    L.symmicp_fpfh.argtypes = [C.c_int] + fpf
+    L.symmicp_ctx_fpfh.argtypes = [vp] + fpf
     _lib = L
     return L
 
@@ -322,6 +329,90 @@ def voxel_downsample(xyz, leaf, nrm=None, min_points=1, device=-1):
     if st != OK:
         raise SymmIcpError(st, "voxel_downsample")
     return r
+
+
+def _i32ptr(a):
+    return a.ctypes.data_as(C.POINTER(C.c_int32))
+
+
+def _radius_call(fn, head, xyz, radius, cap=None, strides=None, want_d2=True):
+    """shared body of radius_search and Engine.radius_search_raw: fn(*head, <the C arguments>) -> (status, count [n] int32,
+    offsets [n + 1] int64, rows [cap] int32 or None, d2 [cap] f32 or None, total).  cap None: the counts only (rows_out == NULL).
+    strides = (n, row stride, col stride) reads xyz as a flat f32 buffer."""
+    if strides is None:
+        xyz = _cloud(xyz)
+        n, xr, xc = xyz.shape[0], 3, 1
+    else:
+        xyz = np.ascontiguousarray(xyz, np.float32)
+        n, xr, xc = strides
+    count = np.zeros(max(n, 1), np.int32)
+    offs = np.zeros(max(n, 1) + 1, np.int64)
+    rows = d2 = None
+    if cap is not None:
+        rows = np.full(max(cap, 1), -1, np.int32)
+        d2 = np.full(max(cap, 1), -1.0, np.float32) if want_d2 else None
+    total = C.c_size_t(0)
+    st = fn(*head, _fptr(xyz), xr, xc, n, float(radius), _i32ptr(count), offs.ctypes.data_as(C.POINTER(C.c_int64)),
+            None if rows is None else _i32ptr(rows), None if d2 is None else _fptr(d2), 0 if cap is None else cap, C.byref(total))
+    return st, count[:n], offs[:n + 1], rows, d2, int(total.value)
+
+
+def _sort_lists(offs, rows, d2):
+    """every CSR list ordered by (d2, row)"""
+    seg = np.repeat(np.arange(len(offs) - 1), np.diff(offs))
+    o = np.lexsort((rows, d2, seg))
+    return rows[o], d2[o]
+
+
+def _radius_search(fn, head, xyz, radius, sort):
+    st, count, offs, _, _, total = _radius_call(fn, head, xyz, radius)
+    if st != OK:
+        return st, None
+    st, count, offs, rows, d2, total = _radius_call(fn, head, xyz, radius, cap=total)
+    if st != OK:
+        return st, None
+    rows, d2 = rows[:total], d2[:total]
+    if sort and total:
+        rows, d2 = _sort_lists(offs, rows, d2)
+    return st, (count.copy(), offs.copy(), rows.copy(), d2.copy())
+
+
+def radius_search(xyz, radius, device=-1, sort=True):
+    """exact fixed-radius neighbours of every point in its own cloud (symmicp_radius_search): N(i) = {j != i : d2(i, j) <= r * r},
+    fp32 -> (count [N] int32, offsets [N + 1] int64, rows [total] int32, d2 [total] f32), list i = rows[offsets[i]:offsets[i + 1]];
+    sort=True orders every list by (d2, row) on the host (the library's order is the index's sorted order)"""
+    st, r = _radius_search(lib().symmicp_radius_search, (int(device),), xyz, radius, sort)
+    if st != OK:
+        raise SymmIcpError(st, "radius_search")
+    return r
+
+
+def _fpfh_call(fn, head, xyz, nrm, radius, want_spfh, strides=None):
+    """fn(*head, <the C arguments>) -> (status, fpfh [n,33], spfh [n,33] or None, count [n] or None).
+    strides = (n, xyz row, xyz col, nrm row, nrm col) reads xyz / nrm as flat f32 buffers."""
+    if strides is None:
+        xyz, nrm = _cloud(xyz), _cloud(nrm)
+        if nrm.shape != xyz.shape:
+            raise ValueError("normals must match the cloud")
+        n, xr, xc, nr, nc = xyz.shape[0], 3, 1, 3, 1
+    else:
+        xyz, nrm = np.ascontiguousarray(xyz, np.float32), np.ascontiguousarray(nrm, np.float32)
+        n, xr, xc, nr, nc = strides
+    f = np.zeros((max(n, 1), 33), np.float32)
+    s = np.zeros((max(n, 1), 33), np.float32) if want_spfh else None
+    k = np.zeros(max(n, 1), np.int32) if want_spfh else None
+    st = fn(*head, _fptr(xyz), xr, xc, _fptr(nrm), nr, nc, n, float(radius), _fptr(f), None if s is None else _fptr(s),
+            None if k is None else _i32ptr(k))
+    return st, f[:n], None if s is None else s[:n], None if k is None else k[:n]
+
+
+def fpfh(xyz, nrm, radius, device=-1, want_spfh=False):
+    """Fast Point Feature Histograms on the GPU (symmicp_fpfh; include/symmicp.h defines the arithmetic) -> fpfh [N,33] f32, or with
+    want_spfh dict(fpfh=, spfh= [N,33], count= [N] neighbours within the radius).  Cost grows with the neighbour count."""
+    st, f, s, k = _fpfh_call(lib().symmicp_fpfh, (int(device),), xyz, nrm, radius, want_spfh)
+    if st != OK:
+        raise SymmIcpError(st, "fpfh")
+    return dict(fpfh=f, spfh=s, count=k) if want_spfh else f
 
 
 def shard_range(n, nranks, rank):
@@ -550,6 +641,30 @@ class Engine:
     def voxel_downsample_raw(self, xyz, leaf, nrm=None, min_points=1, cap=None, strides=None):
         """the C call as it is: -> (status, result dict or None, n_out); cap defaults to N, strides as in _voxel_call"""
         return _voxel_call(self._L.symmicp_ctx_voxel_downsample, (self._h,), xyz, nrm, leaf, min_points, cap, strides)
+
+    def radius_search(self, xyz, radius, sort=True):
+        """radius_search on this context (symmicp_ctx_radius_search, both calls of the cap protocol) -> (count, offsets, rows, d2);
+        its target, source and index stay as they are"""
+        st, r = _radius_search(self._L.symmicp_ctx_radius_search, (self._h,), xyz, radius, sort)
+        self._chk(st)
+        return r
+
+    def radius_search_raw(self, xyz, radius, cap=None, strides=None, want_d2=True):
+        """the C call as it is -> (status, count, offsets, rows or None, d2 or None, total); cap None: counts only (rows_out NULL);
+        strides = (n, row stride, col stride) over a flat f32 buffer"""
+        return _radius_call(self._L.symmicp_ctx_radius_search, (self._h,), xyz, radius, cap, strides, want_d2)
+
+    def fpfh(self, xyz, nrm, radius, want_spfh=False):
+        """fpfh on this context (symmicp_ctx_fpfh) -> fpfh [N,33], or with want_spfh dict(fpfh=, spfh=, count=)"""
+        st, f, s, k = _fpfh_call(self._L.symmicp_ctx_fpfh, (self._h,), xyz, nrm, radius, want_spfh)
+        self._chk(st)
+        return dict(fpfh=f, spfh=s, count=k) if want_spfh else f
+
+    def fpfh_strided(self, xyz, nrm, radius, strides, want_spfh=True):
+        """as fpfh(want_spfh=True), the clouds read from flat f32 buffers: strides = (n, xyz row, xyz col, nrm row, nrm col)"""
+        st, f, s, k = _fpfh_call(self._L.symmicp_ctx_fpfh, (self._h,), xyz, nrm, radius, want_spfh, strides)
+        self._chk(st)
+        return dict(fpfh=f, spfh=s, count=k)
 
     def enable_timing(self, on=True):
         self._chk(self._L.symmicp_enable_timing(self._h, int(on)))      # 0 off, 1 per pass, 2 per kernel

@@ -298,6 +298,66 @@ int symmicp_ctx_estimate_normals(symmicp_ctx *ctx, const float *xyz, size_t row_
 int symmicp_ctx_knn(symmicp_ctx *ctx, const float *xyz, size_t row_stride, size_t col_stride, size_t n, int k,
                     int32_t *rows_out, float *d2_out);
 
+/* ---- fixed-radius neighbour search (PCL's radiusSearch), exact, on the GPU ------------------------------------------------
+ * For a cloud of n points and a radius r (finite, > 0): r2 = r * r in fp32, d2(i, j) = (dx*dx + dy*dy) + dz*dz in fp32,
+ * unfused (the distance of symmicp_ctx_knn).  The neighbourhood of row i is
+ *     N(i) = { j != i : d2(i, j) <= r2 }     compared in fp32.  The point itself is left out by ROW: a duplicate of it, at
+ *                                             d2 == 0, is a member.
+ * count_out [n] = |N(i)| (required).  With rows_out != NULL also the lists, in CSR form: offsets_out [n + 1] (int64, required
+ * then; written whenever it is given), rows_out [total] and d2_out [total] (d2_out may be NULL); list i is
+ * rows_out[offsets_out[i] .. offsets_out[i + 1]).  *total_out = the sum of the counts (required).
+ * SYMMICP_ERR_SIZE when rows_out is given and total > cap: *total_out, count_out and offsets_out are set, the lists are not
+ * written -- call again with room for *total_out entries.  Lists of more than 2^32 - 1 entries in all are refused the same way
+ * whatever the cap (the device's offsets are 32-bit words); the counts are still right.
+ * Order inside a list: ascending position in the index's sorted (Morton) order -- deterministic for a given cloud, not otherwise
+ * specified; callers that need (d2, row) order sort (the Python wrapper does, on the host).
+ * SYMMICP_ERR_ARG: NULL xyz / count_out / total_out; rows_out without offsets_out; n == 0 or n > 2^31 - 1; a radius that is not
+ * finite and > 0; non-finite coordinates (the index build refuses them, as it does for symmicp_ctx_knn).
+ * xyz strided as in symmicp_set_source.  The ctx form runs on the context's stream and arenas like symmicp_ctx_knn: the
+ * context's source, target, index and certificates stay exactly as they were. */
+int symmicp_ctx_radius_search(symmicp_ctx *ctx, const float *xyz, size_t row_stride, size_t col_stride, size_t n, float radius,
+                              int32_t *count_out, int64_t *offsets_out, int32_t *rows_out, float *d2_out, size_t cap,
+                              size_t *total_out);
+/* the same on a context of its own, created on `device` (-1 = current) and destroyed again */
+int symmicp_radius_search(int device, const float *xyz, size_t row_stride, size_t col_stride, size_t n, float radius,
+                          int32_t *count_out, int64_t *offsets_out, int32_t *rows_out, float *d2_out, size_t cap, size_t *total_out);
+
+/* ---- Fast Point Feature Histograms (Rusu, Blodow, Beetz 2009; PCL's FPFHEstimation, Open3D's compute_fpfh_feature) --------
+ * fpfh_out [n][33] (required), spfh_out [n][33] and count_out [n] (= |N(i)|) may be NULL; xyz and nrm (both required) strided as
+ * in symmicp_set_source.  Neighbourhoods are N(i) of the radius search above.  Every operation below is fp32, unfused and in
+ * the association written; sqrtf and / are correctly rounded, atan2f is the device library's.
+ *   dot(a, b) = (a.x*b.x + a.y*b.y) + a.z*b.z        cross(a, b) = (a.y*b.z - a.z*b.y, a.z*b.x - a.x*b.z, a.x*b.y - a.y*b.x)
+ * Pair features of row i (point p, normal n) with j in N(i) (point q, normal m):
+ *   d = q - p;  f4 = sqrtf(d2(i, j));  a1 = dot(n, d) / f4;  a2 = dot(m, d) / f4;
+ *   if fabsf(a1) < fabsf(a2):  A = m, B = n, d = -d, f3 = -a2      (PCL: the frame sits on the point whose normal makes the
+ *   else:                      A = n, B = m,         f3 = a1        smaller angle with the line between the two)
+ *   v = cross(d, A);  vn = sqrtf(dot(v, v));  v = (v.x / vn, v.y / vn, v.z / vn);  w = cross(A, v);
+ *   f2 = dot(v, B);  f1 = atan2f(dot(w, B), dot(A, B)).
+ *   The pair is VALID iff f4 > 0, vn > 0 and f1, f2, f3 are all finite; an invalid pair adds nothing (zero or NaN normals and
+ *   duplicate points are thereby well defined: their histograms are emptier, or all zero).
+ * Bins, 11 per feature, each clamped to [0, 10] (PI = 3.14159274f, INV_2PI = 0.159154937f):
+ *   b1 = floorf((11.0f * (f1 + PI)) * INV_2PI);  b2 = floorf((11.0f * (f2 + 1.0f)) * 0.5f);  b3 = floorf((11.0f * (f3 + 1.0f)) * 0.5f).
+ *   Layout of the 33 floats: [0..10] f1, [11..21] f2, [22..32] f3 (PCL's order).
+ * SPFH: c_i[b] = the number of valid pairs of i in bin b (an integer: the order of the walk does not matter; 32-bit counters,
+ *   exact for every count a cloud of n <= 2^31 - 1 points can give), spfh_i[b] = (100.0f * (float)c_i[b]) / (float)k_i with
+ *   k_i = |N(i)| (invalid pairs count in k_i); all zero when k_i == 0.
+ * FPFH: s_i[b] = the sum over j in N(i) with d2(i, j) > 0, in the list order of the radius search (ascending sorted position),
+ *   of spfh_j[b] * w_ij, w_ij = 1.0f / d2(i, j), starting from 0.0f; per 11-bin block t = the sum of the block's s_i[b] in
+ *   ascending b starting from 0.0f, and fpfh_i[b] = s_i[b] * (100.0f / t) if t > 0 and t is finite, else 0 for the whole block
+ *   (near-duplicate points give weights that overflow fp32; the rule keeps NaN and Inf out of the output).  As in PCL the
+ *   point's own SPFH enters only through its neighbours; each block sums to 100 (within rounding) or is exactly 0.
+ * Cost grows with the neighbour count (there is no max_nn cap): two walks of the tree, |N(i)| pair features per point.
+ * SYMMICP_ERR_ARG: NULL xyz / nrm / fpfh_out; n == 0 or n > 2^31 - 1; a radius that is not finite and > 0; non-finite
+ * coordinates.  The ctx form leaves the context's source, target, index and certificates exactly as they were.  A sharded job
+ * computes the features of the FULL cloud on every rank (the output is deterministic). */
+int symmicp_ctx_fpfh(symmicp_ctx *ctx, const float *xyz, size_t xyz_row_stride, size_t xyz_col_stride,
+                     const float *nrm, size_t nrm_row_stride, size_t nrm_col_stride, size_t n, float radius,
+                     float *fpfh_out, float *spfh_out, int32_t *count_out);
+/* the same on a context of its own, created on `device` (-1 = current) and destroyed again */
+int symmicp_fpfh(int device, const float *xyz, size_t xyz_row_stride, size_t xyz_col_stride,
+                 const float *nrm, size_t nrm_row_stride, size_t nrm_col_stride, size_t n, float radius,
+                 float *fpfh_out, float *spfh_out, int32_t *count_out);
+
 /* ---- voxel-grid downsampling (PCL's pcl::VoxelGrid, Open3D's voxel_down_sample), on the GPU -----------------------
  * Every point falls into the cubic voxel of edge `leaf` that holds it; each occupied voxel with at least min_points points
  * becomes one output point.  The arithmetic is exact and reproducible bit for bit ("Voxel downsampling"):
