@@ -15,6 +15,12 @@
 //     --scale LEAF:ITERS[:MAXDIST]   one level of a coarse-to-fine alignment (repeat it, coarse first): both clouds
 //                              voxel-downsampled with edge LEAF (0: as given), at most ITERS iterations, pairs farther than
 //                              MAXDIST dropped (default 0: none); each level starts from the one before.  Needs --corr tree
+//     --init global            start from a global registration instead of the identity: FPFH features of both clouds, their mutual
+//                              nearest neighbours in feature space, RANSAC on those matches (clouds any angle apart)
+//     --fpfh-radius R          its feature radius (required with --init global; some 8 to 12 point spacings)
+//     --ransac-dist D          its inlier distance (required; some 2 point spacings)
+//     --ransac-iters H         hypotheses drawn (default 100000)      --seed S   of the draws (default 0)
+//     --init-voxel L           both clouds voxel-downsampled with edge L for the initialisation (default 0: as given)
 //     --out aligned.pcd        write the source moved by the result (the reference only prints its result)
 //     --quiet                  no per-iteration lines
 //   Without file names it registers cat.pcd to cat_out.pcd from the working directory: the reference's own run.
@@ -34,7 +40,7 @@
 static int usage(const char *argv0, const char *complaint)
 {
     std::fprintf(stderr, "%s\nusage: %s [--mode quirks|paper|plane|gicp] [--corr identity|tree] [--iters N] [--threshold D] [--loss none|huber|tukey|cauchy|gm]"
-                 " [--loss-scale S] [--gicp-epsilon E] [--max-dist D] [--scale LEAF:ITERS[:MAXDIST]]... [--out file.pcd] [--quiet] [source.pcd target.pcd]\n",
+                 " [--loss-scale S] [--gicp-epsilon E] [--max-dist D] [--scale LEAF:ITERS[:MAXDIST]]... [--init global --fpfh-radius R --ransac-dist D [--ransac-iters H] [--seed S] [--init-voxel L]] [--out file.pcd] [--quiet] [source.pcd target.pcd]\n",
                  complaint, argv0);
     return 64;
 }
@@ -52,6 +58,13 @@ int main(int argc, char **argv)
     float gicp_eps = 0.f;
     bool tree = false;
     std::vector<MyICP::VoxelLevel> levels;
+    bool init_global = false, have_init_option = false;
+    MyICP::GlobalInit ginit;
+    auto number = [&](const char *what, const char *v, float &out) {
+        char *end = nullptr;
+        out = std::strtof(v, &end);
+        if (end == v || *end || !std::isfinite(out)) { std::fprintf(stderr, "%s needs a number\n", what); std::exit(64); }
+    };
     for (int k = 1; k < argc; k++) {
         const std::string a = argv[k];
         auto value = [&](const char *what) -> const char * {
@@ -121,6 +134,21 @@ int main(int argc, char **argv)
             if (!ok) return usage(argv[0], "--scale needs LEAF:ITERS[:MAXDIST] with LEAF >= 0 and ITERS >= 0");
             levels.push_back(lv);
         }
+        else if (a == "--init") {
+            const std::string v = value("--init");
+            if (v == "global") init_global = true;
+            else if (v == "identity") init_global = false;
+            else return usage(argv[0], "unknown --init (global or identity)");
+        }
+        else if (a == "--fpfh-radius") { number("--fpfh-radius", value("--fpfh-radius"), ginit.fpfh_radius); have_init_option = true; }
+        else if (a == "--ransac-dist") { number("--ransac-dist", value("--ransac-dist"), ginit.max_dist); have_init_option = true; }
+        else if (a == "--init-voxel") { number("--init-voxel", value("--init-voxel"), ginit.voxel_leaf); have_init_option = true; }
+        else if (a == "--ransac-iters") {
+            const long h = std::atol(value("--ransac-iters"));
+            if (h < 1 || h > (1l << 24)) return usage(argv[0], "--ransac-iters needs 1 .. 16777216");
+            ginit.hypotheses = (unsigned)h; have_init_option = true;
+        }
+        else if (a == "--seed") { ginit.seed = std::strtoull(value("--seed"), nullptr, 10); have_init_option = true; }
         else if (a == "--out") out_path = value("--out");
         else if (a == "--quiet") icp.setVerbose(false);
         else if (!a.empty() && a[0] == '-') return usage(argv[0], ("unknown option " + a).c_str());
@@ -137,6 +165,12 @@ int main(int argc, char **argv)
         if (!tree) return usage(argv[0], "--scale needs --corr tree (identity pairing cannot pair clouds of different sizes)");
         icp.setVoxelLevels(levels);
     }
+    if (init_global) {
+        if (!(ginit.fpfh_radius > 0.f) || !(ginit.max_dist > 0.f)) return usage(argv[0], "--init global needs --fpfh-radius R and --ransac-dist D, both > 0");
+        if (ginit.voxel_leaf < 0.f) return usage(argv[0], "--init-voxel needs L >= 0");
+        if (!tree) return usage(argv[0], "--init global needs --corr tree (identity pairing assumes the clouds correspond row by row)");
+        icp.setGlobalInit(ginit);
+    } else if (have_init_option) return usage(argv[0], "--fpfh-radius, --ransac-dist, --ransac-iters, --seed and --init-voxel need --init global");
     if (have_eps) {
         if (!gicp) return usage(argv[0], "--gicp-epsilon needs --mode gicp");
         icp.setGicpEpsilon(gicp_eps);
@@ -149,7 +183,7 @@ int main(int argc, char **argv)
     }
     icp.RegisterSymm();
     const symmicp_result &r = icp.lastResult();
-    if (r.status != SYMMICP_OK) return r.status;
+    if (r.status != SYMMICP_OK) return r.status;          // (RegisterSymm has printed lastError(): a failed initialisation among them)
 
     if (!out_path.empty()) {
         pcl::PointCloud<PointT>::Ptr moved = icp.GetAlignedSrcCloud();

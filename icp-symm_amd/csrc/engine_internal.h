@@ -3,6 +3,7 @@
 //   engine.cpp           lifetime, configuration, uploads, index build, set_target / set_source, getters, normals pre-step, statistics
 //   engine_loop.cpp      the iteration loop: one pass (run_pass), device-driven runs of passes (run_batch), begin / step / align, result block
 //   engine_exchange.cpp  multi-GPU: RCCL (loaded lazily), shared-memory exchange, communicator entry points
+//   engine_global.cpp    feature matching and RANSAC (symmicp_ctx_feature_nn, symmicp_ctx_feature_correspondences, symmicp_ctx_ransac)
 //   engine_debug.cpp     SYMMICP_DEBUG_COUNTERS / SYMMICP_DEBUG_TRACE dumps
 #pragma once
 #include <hip/hip_runtime.h>
@@ -93,6 +94,7 @@ struct Switches {
     bool no_hood = false, no_cert = false, walk_full_grid = false, host_loop = false, no_loop_stragglers = false, force_comm = false;
     int budget_walk = -1, optimistic = -1, compact = -1;      // -1 auto, 0 never, 1 always
     int pass_blocks = 2048, id_blocks = 2048, acc_blocks = 512, fused_blocks = 512, compact_blocks = 1280;
+    int feature_nn_splits = 0, feature_nn_queries = 0;      // symmicp_ctx_feature_nn: candidate splits / queries per thread (0: chosen from the sizes)
     PassTuning tune;                       // wave_mode_max, cells_chunk, walk_budget
 };
 

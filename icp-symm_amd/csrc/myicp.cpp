@@ -1,6 +1,7 @@
 // myicp.cpp -- MyICP on top of the libsymmicp C-ABI (drop-in for reference ICP/myicp.cpp:6-172).
 #include <cstdio>
 #include <cstring>
+#include <string>
 #include <vector>
 #include "myicp.h"
 
@@ -151,6 +152,15 @@ int MyICP::align(float out4x4[16], const float *guess4x4)
 	if (st == SYMMICP_OK) st = symmicp_set_gicp_epsilon(ctx, gicp_eps_);              // ERR_ARG: eps outside (0, 1]
 	const size_t fs = sizeof(pcl::PointNormal) / sizeof(float);            // pasteInMatrix, func.cpp:5-15
 	level_results_.clear();
+	if (st == SYMMICP_OK && have_global_ && !guess4x4) {
+		st = globalInit(ctx);
+		if (st != SYMMICP_OK) {
+			result_.status = st;
+			if (out4x4) std::memcpy(out4x4, transform_, sizeof(transform_));
+			return st;
+		}
+		guess4x4 = global_result_.transform;
+	}
 	if (st == SYMMICP_OK && !levels_.empty()) {
 		st = alignLevels(cfg, source_normals, guess4x4);
 		if (result_.iters > 0 || st == SYMMICP_OK) std::memcpy(transform_, result_.transform, sizeof(transform_));
@@ -175,6 +185,70 @@ int MyICP::align(float out4x4[16], const float *guess4x4)
 	if (result_.iters > 0 || st == SYMMICP_OK) std::memcpy(transform_, result_.transform, sizeof(transform_));
 	if (out4x4) std::memcpy(out4x4, transform_, sizeof(transform_));
 	return st;
+}
+
+// setGlobalInit's steps on the object's context: downsample, normals, FPFH, correspondences, RANSAC -> global_result_
+int MyICP::globalInit(symmicp_ctx *ctx)
+{
+	const GlobalInit &g = global_;
+	std::memset(&global_result_, 0, sizeof(global_result_));
+	for (int k = 0; k < 16; k++) global_result_.transform[k] = (k % 5 == 0) ? 1.f : 0.f;
+	global_result_.ransac.best_hypothesis = -1;
+	auto failed = [&](int st, const std::string &what) {
+		const char *msg = symmicp_last_error(ctx);
+		error_ = "global initialisation: " + what + (msg && msg[0] ? std::string(": ") + msg : std::string());
+		global_result_.status = st;
+		return st;
+	};
+	if (cloud_pn_src->points.empty() || cloud_pn_tgt->points.empty()) return failed(SYMMICP_ERR_SIZE, "empty cloud");
+	const size_t fs = sizeof(pcl::PointNormal) / sizeof(float);
+	struct Cloud { pcl::PointCloud<pcl::PointNormal> *pn; bool have; std::vector<float> xyz, n, f; size_t m; };
+	Cloud cl[2] = {{cloud_pn_src.get(), have_src_normals_, {}, {}, {}, 0}, {cloud_pn_tgt.get(), have_tgt_normals_, {}, {}, {}, 0}};
+	for (Cloud &c : cl) {
+		const size_t n = c.pn->points.size();
+		const pcl::PointNormal *p = &c.pn->points[0];
+		c.xyz.resize(3 * n);
+		c.n.resize(3 * n);
+		if (g.voxel_leaf > 0.f) {
+			int st = symmicp_ctx_voxel_downsample(ctx, &p->x, fs, 1, c.have ? &p->normal_x : nullptr, fs, 1, n, g.voxel_leaf, 1, c.xyz.data(),
+			                                      c.have ? c.n.data() : nullptr, nullptr, nullptr, n, &c.m);
+			if (st != SYMMICP_OK) return failed(st, "voxel downsampling");
+		} else {
+			for (size_t i = 0; i < n; i++) {
+				c.xyz[3 * i] = p[i].x; c.xyz[3 * i + 1] = p[i].y; c.xyz[3 * i + 2] = p[i].z;
+				if (c.have) { c.n[3 * i] = p[i].normal_x; c.n[3 * i + 1] = p[i].normal_y; c.n[3 * i + 2] = p[i].normal_z; }
+			}
+			c.m = n;
+		}
+		if (!c.have) {
+			int st = symmicp_ctx_estimate_normals(ctx, c.xyz.data(), 3, 1, c.m, g.normal_k, nullptr, c.n.data(), nullptr);
+			if (st != SYMMICP_OK) return failed(st, "normals of the downsampled cloud");
+		}
+		c.f.resize(33 * c.m);
+		int st = symmicp_ctx_fpfh(ctx, c.xyz.data(), 3, 1, c.n.data(), 3, 1, c.m, g.fpfh_radius, c.f.data(), nullptr, nullptr);
+		if (st != SYMMICP_OK) return failed(st, "FPFH features");
+	}
+	global_result_.source_points = cl[0].m;
+	global_result_.target_points = cl[1].m;
+	std::vector<int32_t> pairs(2 * cl[0].m);
+	size_t count = 0;
+	int st = symmicp_ctx_feature_correspondences(ctx, cl[0].f.data(), cl[0].m, cl[1].f.data(), cl[1].m, g.mutual ? 1 : 0, g.max_ratio, pairs.data(),
+	                                             nullptr, cl[0].m, &count);
+	if (st != SYMMICP_OK) return failed(st, "feature correspondences");
+	global_result_.correspondences = count;
+	if (count < 3) return failed(SYMMICP_ERR_NO_CONSENSUS, "fewer than 3 feature correspondences");
+	symmicp_ransac_config rc;
+	symmicp_ransac_config_default(&rc);
+	rc.hypotheses = g.hypotheses; rc.seed = g.seed; rc.max_dist = g.max_dist; rc.edge_ratio = g.edge_ratio; rc.refits = g.refits;
+	st = symmicp_ctx_ransac(ctx, cl[0].xyz.data(), 3, 1, cl[0].m, cl[1].xyz.data(), 3, 1, cl[1].m, pairs.data(), count, &rc, global_result_.transform,
+	                        &global_result_.ransac, nullptr, nullptr, nullptr);
+	if (verbose_)
+		std::printf("global init: %zu -> %zu source and %zu -> %zu target points, %zu correspondences, %d of %u hypotheses evaluated, %d -> %d inliers\n",
+		            cloud_pn_src->points.size(), cl[0].m, cloud_pn_tgt->points.size(), cl[1].m, count, global_result_.ransac.evaluated, rc.hypotheses,
+		            global_result_.ransac.inliers_ransac, global_result_.ransac.inliers_final);
+	if (st != SYMMICP_OK) return failed(st, "RANSAC");
+	global_result_.status = SYMMICP_OK;
+	return SYMMICP_OK;
 }
 
 // the levels of setVoxelLevels on the object's context (cfg: align()'s configuration, already set on it)

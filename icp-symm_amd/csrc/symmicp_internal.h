@@ -275,4 +275,16 @@ void launch_radius_fill(const TargetIndex &ix, float r2, const uint32_t *offs_ro
 void launch_spfh(const TargetIndex &ix, float r2, float *spfh_sorted, float *spfh_rows /* may be null */, int32_t *count_rows, hipStream_t s);
 void launch_fpfh(const TargetIndex &ix, float r2, const float *spfh_sorted, float *fpfh_rows, hipStream_t s);
 
+
+// feature matching and RANSAC (kernels_global.hip; symmicp_ctx_feature_nn, symmicp_ctx_ransac).  feature_nn: fa / fb packed [n][33];
+// splits > 1 needs feature_nn_partial_bytes of `partial`.  ransac: pq8 [m][8] = p.xyz, 0, q.xyz, 0 about the pivots; hyp [H][12].
+void launch_feature_nn(const float *fa, uint32_t na, const float *fb, uint32_t nb, int queries_per_thread, uint32_t splits, void *partial,
+                       int32_t *nn_out, float *d2_out, float *second_out, hipStream_t s);
+size_t feature_nn_partial_bytes(uint32_t na, uint32_t splits);
+void launch_ransac_hyp(const float *pq8, uint32_t m, uint32_t H, unsigned long long base, float max_dist2, float edge2, float *hyp,
+                       uint8_t *status, int32_t *inliers, uint32_t *surv, uint32_t *n_surv, hipStream_t s);
+void launch_ransac_eval(const float *pq8, uint32_t m, const float *hyp, const uint32_t *surv, const uint32_t *n_surv, uint32_t n_surv_host,
+                        float max_dist2, int32_t *inliers, hipStream_t s);
+void launch_ransac_argmax(const uint8_t *status, const int32_t *inliers, uint32_t H, unsigned long long *best, hipStream_t s);
+
 }  // namespace symmicp

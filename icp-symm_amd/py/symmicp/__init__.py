@@ -20,6 +20,8 @@ LIB_PATH = os.environ.get("SYMMICP_LIB") or os.path.join(_ROOT, "lib", "libsymmi
 NSUM = 40
 UNIQUE_ID_BYTES = 128
 OK, ERR_ARG, ERR_SIZE, ERR_DEGENERATE, ERR_IO, ERR_HIP, ERR_STATE, ERR_COMM = range(8)
+ERR_NO_CONSENSUS = 8
+RANSAC_EVALUATED, RANSAC_REPEATED, RANSAC_EDGE, RANSAC_DEGENERATE, RANSAC_FAR = range(5)      # per-hypothesis status of ransac()
 MODE_QUIRKS, MODE_PAPER, MODE_P2P, MODE_PLANE, MODE_GICP = 0, 1, 2, 3, 5      # (4 is unassigned)
 CORR_IDENTITY, CORR_BRUTE, CORR_TREE = 0, 1, 2
 APPLY_DEFAULT, APPLY_INCREMENTAL, APPLY_CUMULATIVE = 0, 1, 2
@@ -28,7 +30,7 @@ _LOSS_NAMES = {"none": LOSS_NONE, "huber": LOSS_HUBER, "tukey": LOSS_TUKEY, "cau
                "geman_mcclure": LOSS_GEMAN_MCCLURE}
 
 _STATUS_NAMES = {0: "OK", 1: "ERR_ARG", 2: "ERR_SIZE", 3: "ERR_DEGENERATE", 4: "ERR_IO", 5: "ERR_HIP",
-                 6: "ERR_STATE", 7: "ERR_COMM"}
+                 6: "ERR_STATE", 7: "ERR_COMM", 8: "ERR_NO_CONSENSUS"}
 
 
 class SymmIcpError(RuntimeError):
@@ -78,6 +80,16 @@ class Stats(C.Structure):
                 ("allreduce_ms", C.c_double), ("allreduce_timed", C.c_int64)]
 
 
+class RansacConfig(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("hypotheses", C.c_uint32), ("seed", C.c_uint64), ("max_dist", C.c_float),
+                ("edge_ratio", C.c_float), ("refits", C.c_int32), ("reserved", C.c_int32)]
+
+
+class RansacResult(C.Structure):
+    _fields_ = [("best_hypothesis", C.c_int32), ("evaluated", C.c_int32), ("inliers_ransac", C.c_int32), ("inliers_final", C.c_int32),
+                ("rmse_final", C.c_double), ("transform", C.c_double * 16)]
+
+
 KERNEL_SLOTS = ["k_search_cells", "(gap)", "k_search_walk", "k_accumulate", "k_final_reduce", "single_pass_kernel", "whole_pass"]
 
 
@@ -93,6 +105,8 @@ EXPORTS = [
     "symmicp_ctx_solve_probe", "symmicp_ctx_loop_solve", "symmicp_set_loop_log", "symmicp_get_loop_log",
     "symmicp_voxel_downsample", "symmicp_ctx_voxel_downsample",
     "symmicp_radius_search", "symmicp_ctx_radius_search", "symmicp_fpfh", "symmicp_ctx_fpfh",
+    "symmicp_feature_nn", "symmicp_ctx_feature_nn", "symmicp_feature_correspondences", "symmicp_ctx_feature_correspondences",
+    "symmicp_ransac_config_default", "symmicp_ransac", "symmicp_ctx_ransac", "symmicp_ctx_ransac_hypotheses",
 ]
 
 _lib = None
@@ -180,6 +194,19 @@ def lib():
     fpf = [fp, C.c_size_t, C.c_size_t, fp, C.c_size_t, C.c_size_t, C.c_size_t, C.c_float, fp, fp, i32p]
     L.symmicp_fpfh.argtypes = [C.c_int] + fpf
     L.symmicp_ctx_fpfh.argtypes = [vp] + fpf
+    fnn = [fp, C.c_size_t, fp, C.c_size_t, i32p, fp, fp]
+    L.symmicp_feature_nn.argtypes = [C.c_int] + fnn
+    L.symmicp_ctx_feature_nn.argtypes = [vp] + fnn
+    fco = [fp, C.c_size_t, fp, C.c_size_t, C.c_int, C.c_float, i32p, fp, C.c_size_t, C.POINTER(C.c_size_t)]
+    L.symmicp_feature_correspondences.argtypes = [C.c_int] + fco
+    L.symmicp_ctx_feature_correspondences.argtypes = [vp] + fco
+    u8p = C.POINTER(C.c_uint8)
+    rsc = [fp, C.c_size_t, C.c_size_t, C.c_size_t, fp, C.c_size_t, C.c_size_t, C.c_size_t, i32p, C.c_size_t, C.POINTER(RansacConfig)]
+    L.symmicp_ransac_config_default.argtypes = [C.POINTER(RansacConfig)]
+    L.symmicp_ransac_config_default.restype = None
+    L.symmicp_ransac.argtypes = [C.c_int] + rsc + [fp, C.POINTER(RansacResult), u8p, u8p, i32p]
+    L.symmicp_ctx_ransac.argtypes = [vp] + rsc + [fp, C.POINTER(RansacResult), u8p, u8p, i32p]
+    L.symmicp_ctx_ransac_hypotheses.argtypes = [vp] + rsc + [fp, u8p, fp]
     _lib = L
     return L
 
@@ -413,6 +440,99 @@ def fpfh(xyz, nrm, radius, device=-1, want_spfh=False):
     if st != OK:
         raise SymmIcpError(st, "fpfh")
     return dict(fpfh=f, spfh=s, count=k) if want_spfh else f
+
+
+def _features(f):
+    f = np.ascontiguousarray(f, dtype=np.float32)
+    if f.ndim != 2 or f.shape[1] != 33:
+        raise ValueError("features must be [N,33]")
+    return f
+
+
+def _feature_nn_call(fn, head, fa, fb):
+    """fn(*head, <the C arguments>) -> (status, nn [na] int32, d2 [na] f32, second [na] f32)"""
+    fa, fb = _features(fa), _features(fb)
+    na = fa.shape[0]
+    nn = np.full(max(na, 1), -1, np.int32)
+    d2 = np.zeros(max(na, 1), np.float32)
+    sec = np.zeros(max(na, 1), np.float32)
+    st = fn(*head, _fptr(fa), na, _fptr(fb), fb.shape[0], _i32ptr(nn), _fptr(d2), _fptr(sec))
+    return st, nn[:na], d2[:na], sec[:na]
+
+
+def feature_nn(fa, fb, device=-1):
+    """exact nearest neighbour of every row of fa among the rows of fb in the 33-d feature space (symmicp_feature_nn;
+    include/symmicp.h defines the arithmetic) -> (nn [na] int32, d2 [na] f32, second [na] f32); ties go to the lowest row"""
+    st, nn, d2, sec = _feature_nn_call(lib().symmicp_feature_nn, (int(device),), fa, fb)
+    if st != OK:
+        raise SymmIcpError(st, "feature_nn")
+    return nn, d2, sec
+
+
+def _feature_corr_call(fn, head, fa, fb, mutual, max_ratio, cap=None):
+    """fn(*head, <the C arguments>) -> (status, pairs [count,2] int32 or None, d2 [count] or None, count); cap None: na"""
+    fa, fb = _features(fa), _features(fb)
+    na = fa.shape[0]
+    cap = na if cap is None else cap
+    pairs = np.full((max(cap, 1), 2), -1, np.int32)
+    d2 = np.zeros(max(cap, 1), np.float32)
+    cnt = C.c_size_t(0)
+    st = fn(*head, _fptr(fa), na, _fptr(fb), fb.shape[0], int(bool(mutual)), float(max_ratio), _i32ptr(pairs) if cap > 0 else None,
+            _fptr(d2) if cap > 0 else None, cap, C.byref(cnt))
+    n = int(cnt.value)
+    if st != OK:
+        return st, None, None, n
+    return st, pairs[:n].copy(), d2[:n].copy(), n
+
+
+def feature_correspondences(fa, fb, mutual=True, max_ratio=0.0, device=-1):
+    """the matches ransac() consumes (symmicp_feature_correspondences): (i, nn(i)) for every row i of fa that passes the mutual
+    test (nn of nn(i) is i) and the ratio test (d2 <= max_ratio^2 * second; <= 0: off) -> (pairs [count,2] int32, d2 [count] f32)"""
+    st, pairs, d2, _ = _feature_corr_call(lib().symmicp_feature_correspondences, (int(device),), fa, fb, mutual, max_ratio)
+    if st != OK:
+        raise SymmIcpError(st, "feature_correspondences")
+    return pairs, d2
+
+
+def ransac_config(max_dist, hypotheses=100000, seed=0, edge_ratio=0.9, refits=1):
+    cfg = RansacConfig()
+    lib().symmicp_ransac_config_default(C.byref(cfg))
+    cfg.max_dist, cfg.hypotheses, cfg.seed, cfg.edge_ratio, cfg.refits = float(max_dist), int(hypotheses), int(seed), float(edge_ratio), int(refits)
+    return cfg
+
+
+def _ransac_call(fn, head, src, tgt, pairs, cfg, want_hypotheses=False):
+    """fn(*head, <the C arguments>) -> (status, result dict).  The dict is filled on failure too (identity transform)."""
+    src, tgt = _cloud(src), _cloud(tgt)
+    pairs = np.ascontiguousarray(pairs, np.int32)
+    if pairs.ndim != 2 or pairs.shape[1] != 2:
+        raise ValueError("pairs must be [m,2]")
+    m, H = pairs.shape[0], int(cfg.hypotheses)
+    X = np.zeros(16, np.float32)
+    res = RansacResult()
+    mask = np.zeros(max(m, 1), np.uint8)
+    status = np.zeros(max(H, 1), np.uint8) if want_hypotheses else None
+    inl = np.zeros(max(H, 1), np.int32) if want_hypotheses else None
+    u8 = lambda a: None if a is None else a.ctypes.data_as(C.POINTER(C.c_uint8))
+    st = fn(*head, _fptr(src), 3, 1, src.shape[0], _fptr(tgt), 3, 1, tgt.shape[0], _i32ptr(pairs), m, C.byref(cfg), _fptr(X), C.byref(res),
+            u8(mask), u8(status), None if inl is None else _i32ptr(inl))
+    r = dict(status=st, transform=X.reshape(4, 4), transform64=np.array(res.transform[:], np.float64).reshape(4, 4),
+             best_hypothesis=res.best_hypothesis, evaluated=res.evaluated, inliers_ransac=res.inliers_ransac,
+             inliers_final=res.inliers_final, rmse_final=res.rmse_final, inlier_mask=mask[:m].astype(bool))
+    if want_hypotheses:
+        r["hyp_status"], r["hyp_inliers"] = status[:H], inl[:H]
+    return st, r
+
+
+def ransac(src, tgt, pairs, max_dist, hypotheses=100000, seed=0, edge_ratio=0.9, refits=1, device=-1, want_hypotheses=False):
+    """a rigid transform from correspondences with outliers (symmicp_ransac) -> dict(transform [4,4] f32, transform64, best_hypothesis,
+    evaluated, inliers_ransac, inliers_final, rmse_final, inlier_mask [m] bool[, hyp_status [H], hyp_inliers [H]]).  Raises
+    SymmIcpError (ERR_NO_CONSENSUS) when no hypothesis reaches 3 inliers."""
+    st, r = _ransac_call(lib().symmicp_ransac, (int(device),), src, tgt, pairs, ransac_config(max_dist, hypotheses, seed, edge_ratio, refits),
+                         want_hypotheses)
+    if st != OK:
+        raise SymmIcpError(st, "ransac")
+    return r
 
 
 def shard_range(n, nranks, rank):
@@ -666,6 +786,45 @@ class Engine:
         self._chk(st)
         return dict(fpfh=f, spfh=s, count=k)
 
+    def feature_nn(self, fa, fb):
+        """feature_nn on this context (symmicp_ctx_feature_nn) -> (nn, d2, second)"""
+        st, nn, d2, sec = _feature_nn_call(self._L.symmicp_ctx_feature_nn, (self._h,), fa, fb)
+        self._chk(st)
+        return nn, d2, sec
+
+    def feature_correspondences(self, fa, fb, mutual=True, max_ratio=0.0):
+        """feature_correspondences on this context -> (pairs [count,2], d2 [count])"""
+        st, pairs, d2, _ = _feature_corr_call(self._L.symmicp_ctx_feature_correspondences, (self._h,), fa, fb, mutual, max_ratio)
+        self._chk(st)
+        return pairs, d2
+
+    def feature_correspondences_raw(self, fa, fb, mutual=True, max_ratio=0.0, cap=None):
+        """the C call as it is -> (status, pairs or None, d2 or None, count)"""
+        return _feature_corr_call(self._L.symmicp_ctx_feature_correspondences, (self._h,), fa, fb, mutual, max_ratio, cap)
+
+    def ransac(self, src, tgt, pairs, max_dist, hypotheses=100000, seed=0, edge_ratio=0.9, refits=1, want_hypotheses=False, check=True):
+        """ransac on this context (symmicp_ctx_ransac) -> the dict of symmicp.ransac; check=False returns it on failure too (status set)"""
+        st, r = _ransac_call(self._L.symmicp_ctx_ransac, (self._h,), src, tgt, pairs, ransac_config(max_dist, hypotheses, seed, edge_ratio, refits),
+                             want_hypotheses)
+        if check:
+            self._chk(st)
+        return r
+
+    def ransac_hypotheses(self, src, tgt, pairs, max_dist, hypotheses=100000, seed=0, edge_ratio=0.9):
+        """test entry (symmicp_ctx_ransac_hypotheses): what the device computed for every hypothesis -> (hyp [H,12] f32 = R row-major
+        then t about the pivots, status [H] uint8, pivots [2,3] f32 = cs, ct)"""
+        src, tgt = _cloud(src), _cloud(tgt)
+        pairs = np.ascontiguousarray(pairs, np.int32)
+        cfg = ransac_config(max_dist, hypotheses, seed, edge_ratio, 0)
+        H = int(hypotheses)
+        hyp = np.zeros((H, 12), np.float32)
+        status = np.zeros(H, np.uint8)
+        piv = np.zeros(6, np.float32)
+        self._chk(self._L.symmicp_ctx_ransac_hypotheses(self._h, _fptr(src), 3, 1, src.shape[0], _fptr(tgt), 3, 1, tgt.shape[0], _i32ptr(pairs),
+                                                        pairs.shape[0], C.byref(cfg), _fptr(hyp), status.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                                        _fptr(piv)))
+        return hyp, status, piv.reshape(2, 3)
+
     def enable_timing(self, on=True):
         self._chk(self._L.symmicp_enable_timing(self._h, int(on)))      # 0 off, 1 per pass, 2 per kernel
 
@@ -758,6 +917,9 @@ class MyICP:
         self._gicp_eps = None
         self._levels = []
         self.level_results = []
+        self._global = None
+        self.global_result = None
+        self._have_src = self._have_tgt = False         # normals supplied by the caller through setInput* (not estimated here)
 
     def setMaxCorrespondenceDistance(self, d):
         """pairs farther apart than d are dropped (Config.max_corr_dist; <= 0: every pair is kept)"""
@@ -768,6 +930,50 @@ class MyICP:
         then runs one alignment per level on both clouds voxel-downsampled with the level's leaf (normals averaged), each from the
         transform of the level before (the first from the caller's guess).  CORR_IDENTITY is refused (ERR_ARG).  [] = off."""
         self._levels = [(float(l), int(i), float(d)) for l, i, d in levels]
+
+    def setGlobalInit(self, fpfh_radius, max_dist, voxel_leaf=0.0, normal_k=10, hypotheses=100000, seed=0, mutual=True, max_ratio=0.0,
+                      edge_ratio=0.9, refits=1):
+        """global initialisation: with it set and no guess given, align() first voxel-downsamples both clouds with voxel_leaf (0: as
+        given), estimates normals on the downsampled clouds when the caller supplied none (normal_k neighbours, viewpoint at the
+        origin), computes FPFH features at fpfh_radius, their correspondences and a RANSAC transform, and starts the ordinary
+        alignment (voxel levels included) from it.  A failure (ERR_NO_CONSENSUS among them) raises SymmIcpError.  FPFH matching
+        needs normals oriented alike in both clouds."""
+        self._global = dict(fpfh_radius=float(fpfh_radius), max_dist=float(max_dist), voxel_leaf=float(voxel_leaf), normal_k=int(normal_k),
+                            hypotheses=int(hypotheses), seed=int(seed), mutual=bool(mutual), max_ratio=float(max_ratio),
+                            edge_ratio=float(edge_ratio), refits=int(refits))
+
+    def clearGlobalInit(self):
+        self._global = None
+
+    def globalResult(self):
+        """the RANSAC result dict of the last align() that ran the initialisation (plus correspondences, source_points, target_points)"""
+        return self.global_result
+
+    def _global_init(self, e):
+        g = self._global
+        clouds = []
+        for xyz, nrm in ((self.cloud_src, self.normals_src if self._have_src else None),
+                         (self.cloud_tgt, self.normals_tgt if self._have_tgt else None)):
+            if g["voxel_leaf"] > 0:
+                d = e.voxel_downsample(xyz, g["voxel_leaf"], nrm)
+                xyz, nrm = d["xyz"], d["nrm"]
+            if nrm is None:
+                nrm, _ = e.estimate_normals(xyz, g["normal_k"])
+            clouds.append((xyz, e.fpfh(xyz, nrm, g["fpfh_radius"])))
+        (src, fs), (tgt, ft) = clouds
+        pairs, _ = e.feature_correspondences(fs, ft, g["mutual"], g["max_ratio"])
+        if len(pairs) < 3:
+            raise SymmIcpError(ERR_NO_CONSENSUS, "global initialisation: fewer than 3 feature correspondences")
+        r = e.ransac(src, tgt, pairs, g["max_dist"], g["hypotheses"], g["seed"], g["edge_ratio"], g["refits"], check=False)
+        r.update(correspondences=len(pairs), source_points=len(src), target_points=len(tgt))
+        self.global_result = r
+        if self._cfg["verbose"]:
+            print("global init: %d -> %d source and %d -> %d target points, %d correspondences, %d of %d hypotheses evaluated, %d -> %d inliers"
+                  % (len(self.cloud_src), len(src), len(self.cloud_tgt), len(tgt), len(pairs), r["evaluated"], g["hypotheses"],
+                     r["inliers_ransac"], r["inliers_final"]), flush=True)
+        if r["status"] != OK:
+            raise SymmIcpError(r["status"], "global initialisation: RANSAC: " + (e._L.symmicp_last_error(e._h) or b"").decode())
+        return r["transform"]
 
     def levelResults(self):
         """one align() result dict per level of the last align()"""
@@ -785,6 +991,7 @@ class MyICP:
         self.cloud_src, _ = pcd_read(src_path)
         self.cloud_tgt, _ = pcd_read(tgt_path)
         self.normals_src = self.normals_tgt = None
+        self._have_src = self._have_tgt = False
         return 0
 
     def GetSrcCloud(self):
@@ -796,10 +1003,12 @@ class MyICP:
     def setInputSource(self, xyz, normals=None):
         self.cloud_src = _cloud(xyz)
         self.normals_src = None if normals is None else _cloud(normals)
+        self._have_src = normals is not None
 
     def setInputTarget(self, xyz, normals=None):
         self.cloud_tgt = _cloud(xyz)
         self.normals_tgt = None if normals is None else _cloud(normals)
+        self._have_tgt = normals is not None
 
     def estimateNormals(self):
         # myicp.cpp:152-172: k = 10, flipped toward the origin.  Point-to-plane uses the target's normals only: in MODE_PLANE the
@@ -821,6 +1030,8 @@ class MyICP:
         if self._levels:
             return self._align_levels(guess)
         with Engine(**self._cfg) as e:
+            if self._global is not None and guess is None:
+                guess = self._global_init(e)
             if self._loss[0] != LOSS_NONE:
                 e.set_robust_loss(*self._loss)
             if self._gicp_eps is not None:
@@ -841,6 +1052,8 @@ class MyICP:
             if self._gicp_eps is not None:
                 e.set_gicp_epsilon(self._gicp_eps)
             X = guess
+            if self._global is not None and guess is None:
+                X = self._global_init(e)
             for k, (leaf, iters, dist) in enumerate(self._levels):
                 if leaf > 0:
                     s = e.voxel_downsample(self.cloud_src, leaf, self.normals_src)

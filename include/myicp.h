@@ -66,6 +66,35 @@ public:
 	struct VoxelLevel { float leaf; int max_iters; float max_corr_dist; };
 	void setVoxelLevels(const std::vector<VoxelLevel> &levels) { levels_ = levels; }
 	const std::vector<symmicp_result> &levelResults() const { return level_results_; }   // one per level run by the last align()
+	// Global initialisation (feature matching and RANSAC, include/symmicp.h): with it set and no guess4x4 given, align() first
+	// voxel-downsamples both clouds with voxel_leaf (0: the clouds as given), estimates normals on the downsampled clouds when the
+	// caller supplied none (normal_k neighbours, viewpoint at the origin), computes FPFH features of both at fpfh_radius, their
+	// correspondences (mutual, max_ratio) and a RANSAC transform (max_dist, hypotheses, seed, edge_ratio, refits), and starts the
+	// ordinary alignment (voxel levels included) from it.  A failure of any step -- SYMMICP_ERR_NO_CONSENSUS from RANSAC among
+	// them -- is returned from align() with lastError() saying so; there is no silent fall-back to the identity.  FPFH matching
+	// needs normals oriented alike in both clouds: with estimated normals that is the caller's viewpoint to arrange.
+	struct GlobalInit {
+		float voxel_leaf = 0.f;
+		int normal_k = 10;
+		float fpfh_radius = 0.f;      // required: finite, > 0
+		float max_dist = 0.f;         // required: finite, > 0
+		unsigned hypotheses = 100000;
+		unsigned long long seed = 0;
+		bool mutual = true;
+		float max_ratio = 0.f;
+		float edge_ratio = 0.9f;
+		int refits = 1;
+	};
+	struct GlobalResult {
+		symmicp_ransac_result ransac;  // of the last align() that ran the initialisation
+		float transform[16];           // row-major 4x4, source -> target: the guess the alignment started from
+		size_t correspondences;
+		size_t source_points, target_points;   // after downsampling
+		int status;                    // symmicp_status of the initialisation
+	};
+	void setGlobalInit(const GlobalInit &g) { global_ = g; have_global_ = true; }
+	void clearGlobalInit() { have_global_ = false; }
+	const GlobalResult &globalResult() const { return global_result_; }
 	const symmicp_result &lastResult() const { return result_; }
 	const char *lastError() const { return error_.c_str(); }
 
@@ -90,6 +119,10 @@ private:
 	std::vector<VoxelLevel> levels_;
 	std::vector<symmicp_result> level_results_;
 	int alignLevels(const symmicp_config &cfg, bool source_normals, const float *guess4x4);
+	GlobalInit global_;
+	bool have_global_ = false;
+	GlobalResult global_result_{};
+	int globalInit(symmicp_ctx *ctx);
 	symmicp_ctx *ctx_;
 	int ctx_corr_;
 	bool ctx_no_src_normals_;            // the context holds a source set without normals (PLANE): no other mode can run on it

@@ -37,7 +37,8 @@ typedef enum {
     SYMMICP_ERR_IO = 4,
     SYMMICP_ERR_HIP = 5,           /* HIP runtime error or no gfx950-capable device */
     SYMMICP_ERR_STATE = 6,         /* call out of order (e.g. step before begin) */
-    SYMMICP_ERR_COMM = 7           /* RCCL or shared-memory exchange error */
+    SYMMICP_ERR_COMM = 7,          /* RCCL or shared-memory exchange error */
+    SYMMICP_ERR_NO_CONSENSUS = 8   /* symmicp_ctx_ransac: no hypothesis was evaluated, or the best one has fewer than 3 inliers */
 } symmicp_status;
 
 /* Arithmetic mode.  QUIRKS reproduces the reference exactly as written:
@@ -357,6 +358,112 @@ int symmicp_ctx_fpfh(symmicp_ctx *ctx, const float *xyz, size_t xyz_row_stride, 
 int symmicp_fpfh(int device, const float *xyz, size_t xyz_row_stride, size_t xyz_col_stride,
                  const float *nrm, size_t nrm_row_stride, size_t nrm_col_stride, size_t n, float radius,
                  float *fpfh_out, float *spfh_out, int32_t *count_out);
+
+/* ---- feature matching and RANSAC: global registration from FPFH features ("Feature matching and RANSAC") -------
+ * All three run on the context's stream and temporary arena; the context's source, target, index and certificates stay exactly
+ * as they were.  A sharded job computes the full result on every rank (the outputs are deterministic).
+ *
+ * FPFH matching relies on normals that are oriented alike in both clouds: two scans of one surface whose normals point to
+ * different sides of it give unrelated histograms.  Estimated normals are flipped towards a viewpoint; choosing viewpoints that
+ * orient both clouds consistently is the caller's part.
+ *
+ * symmicp_ctx_feature_nn: exact nearest neighbour in feature space.  fa [na][33] (queries) and fb [nb][33] (candidates), packed
+ * fp32 as symmicp_ctx_fpfh writes them.  Defined by its arithmetic (fp32, unfused):
+ *     D(i, j):    acc = 0.0f;  for b = 0 .. 32 ascending:  t = fa[i][b] - fb[j][b];  acc = acc + t * t
+ *     nn(i)     = the j that minimises (D(i, j), j) lexicographically      (ties go to the lowest candidate row)
+ *     second(i) = min over j != nn(i) of D(i, j); +INF when nb == 1
+ * nn_out [na] (required), d2_out [na] = D(i, nn(i)) and d2_second_out [na] = second(i) (each may be NULL).  The result is a
+ * function of the inputs alone.
+ * SYMMICP_ERR_ARG: NULL fa / fb / nn_out; na or nb == 0 or > 2^31 - 1; a non-finite value in fa or fb. */
+int symmicp_ctx_feature_nn(symmicp_ctx *ctx, const float *fa, size_t na, const float *fb, size_t nb,
+                           int32_t *nn_out, float *d2_out, float *d2_second_out);
+/* the same on a context of its own, created on `device` (-1 = current) and destroyed again */
+int symmicp_feature_nn(int device, const float *fa, size_t na, const float *fb, size_t nb,
+                       int32_t *nn_out, float *d2_out, float *d2_second_out);
+/* The matches RANSAC consumes, defined by feature_nn: with nn_ab, d2, second = feature_nn(fa -> fb) and, if mutual != 0,
+ * nn_ba = feature_nn(fb -> fa), pair (i, nn_ab(i)) is kept iff
+ *     (mutual == 0 or nn_ba(nn_ab(i)) == i)  and  (max_ratio <= 0 or d2(i) <= (max_ratio * max_ratio) * second(i), in fp32).
+ * pairs_out [cap][2] (row of fa, row of fb) in ascending i, d2_out [cap] (may be NULL), *count_out = the number kept.
+ * SYMMICP_ERR_SIZE when the count exceeds cap: *count_out is set, nothing else is written (cap >= na always suffices;
+ * pairs_out may be NULL with cap == 0 to ask for the count).
+ * SYMMICP_ERR_ARG: as feature_nn; NULL count_out; NULL pairs_out with cap > 0; a max_ratio that is NaN. */
+int symmicp_ctx_feature_correspondences(symmicp_ctx *ctx, const float *fa, size_t na, const float *fb, size_t nb, int mutual,
+                                        float max_ratio, int32_t *pairs_out, float *d2_out, size_t cap, size_t *count_out);
+int symmicp_feature_correspondences(int device, const float *fa, size_t na, const float *fb, size_t nb, int mutual,
+                                    float max_ratio, int32_t *pairs_out, float *d2_out, size_t cap, size_t *count_out);
+
+/* symmicp_ctx_ransac: a rigid transform from correspondences with outliers -- Open3D's
+ * registration_ransac_based_on_correspondence (three-pair samples, edge-length pre-rejection, inliers counted over the
+ * correspondence set, a least-squares refit on the winner's inliers), arranged as a pure function of its inputs.
+ *   Pivots.  cs, ct = the fp64 means of the m source / target points of the pairs, rounded to fp32; the device works on
+ *     p_k = src[pairs[k][0]] - cs, q_k = tgt[pairs[k][1]] - ct (fp32).  The returned transform is in the caller's coordinates
+ *     (composed in fp64 on the host).
+ *   Samples.  Hypothesis h (0 <= h < hypotheses) draws c_k = ((u(3h + k) >> 32) * m) >> 32, k = 0, 1, 2, where u(i) is value i
+ *     of the SplitMix64 sequence of (seed, stream 0):
+ *       mix64(z):  z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9;  z = (z ^ (z >> 27)) * 0x94D049BB133111EB;  return z ^ (z >> 31)
+ *       base = mix64(seed * 0x9E3779B97F4A7C15 + 0x2545F4914F6CDD1D);   u(i) = mix64(base + (i + 1) * 0x9E3779B97F4A7C15)
+ *     (64-bit wrap-around arithmetic).  No rejection loop; every hypothesis gets a status, the checks in this order, with
+ *     a, b, c = the sample's p (likewise q) and e = edge_ratio:
+ *       1 REPEATED    two draws are equal
+ *       2 EDGE        for an edge x-y of the triangle |p_x - p_y|^2 < e^2 |q_x - q_y|^2 or |q_x - q_y|^2 < e^2 |p_x - p_y|^2
+ *                     (edges 0-1, 1-2, 2-0; off when e <= 0)
+ *       3 DEGENERATE  |(b - a) x (c - a)|^2 < 1e-4 |b - a|^2 |c - a|^2, or that product not > 0, in either cloud (the sine of the
+ *                     angle at a below 0.01: this bounds how much the frames amplify fp32 rounding)
+ *       4 FAR         one of the three sample pairs is farther than max_dist under the hypothesis
+ *       0 EVALUATED
+ *   Hypothesis.  Orthonormal frames: e1 = (b - a) / |b - a|, e3 = (e1 x (c - a)) / |e1 x (c - a)|, e2 = e3 x e1, F = [e1 e2 e3];
+ *     R = F_q F_p^T, t = mean(q) - R mean(p) (means of the three sample points).
+ *   Score.  inliers(h) = the number of k with |R p_k + t - q_k|^2 <= max_dist^2 (fp32).  The winner is the evaluated hypothesis
+ *     with the most inliers, ties to the lowest h.  None evaluated, or a winner with fewer than 3 inliers:
+ *     SYMMICP_ERR_NO_CONSENSUS, transform = identity.
+ *   Refit.  `refits` times: R, t = the least-squares rigid fit (Horn's quaternion method, a proper rotation) to the current
+ *     inlier set, in fp64 on the host in ascending k and in the caller's coordinates; then the inlier set is recomputed under
+ *     it in fp64 (|R x + t - y|^2 <= max_dist^2).  A refit that leaves fewer than 3 inliers is SYMMICP_ERR_NO_CONSENSUS.
+ * src_xyz (ns points) and tgt_xyz (nt points) strided as in symmicp_set_source; pairs [m][2] int32 (source row, target row).
+ * Outputs: transform16 (row-major 4x4, source -> target; required), result (required), inlier_mask_out [m] (uint8, the final
+ * inlier set; with refits == 0 the winner's), status_out [hypotheses] (uint8) and inliers_out [hypotheses] (int32, 0 unless
+ * evaluated); the last three may be NULL.
+ * SYMMICP_ERR_ARG: NULL src_xyz / tgt_xyz / pairs / cfg / transform16 / result; ns, nt == 0 or > 2^31 - 1; m < 3 or > 2^31 - 1;
+ * a pair row out of range; cfg->struct_size != sizeof(symmicp_ransac_config); hypotheses outside 1 .. 2^24; max_dist not finite
+ * and > 0; edge_ratio > 1 or NaN; refits outside 0 .. 8; a non-finite coordinate among the paired points. */
+typedef struct {
+    uint32_t struct_size;      /* = sizeof(symmicp_ransac_config), checked */
+    uint32_t hypotheses;       /* H, 1 .. 2^24 */
+    uint64_t seed;
+    float max_dist;            /* finite, > 0 */
+    float edge_ratio;          /* 0 < e <= 1, default 0.9; <= 0: the edge check is off */
+    int32_t refits;            /* 0 .. 8, default 1 */
+    int32_t reserved;
+} symmicp_ransac_config;
+typedef struct {
+    int32_t best_hypothesis;   /* -1: none */
+    int32_t evaluated;         /* hypotheses with status EVALUATED */
+    int32_t inliers_ransac;    /* the winner's inliers (fp32, on the device) */
+    int32_t inliers_final;     /* after the refits */
+    double rmse_final;         /* over the final inliers */
+    double transform[16];      /* the result in fp64, row-major; transform16 is this matrix rounded to fp32 */
+} symmicp_ransac_result;
+#define SYMMICP_RANSAC_EVALUATED 0
+#define SYMMICP_RANSAC_REPEATED 1
+#define SYMMICP_RANSAC_EDGE 2
+#define SYMMICP_RANSAC_DEGENERATE 3
+#define SYMMICP_RANSAC_FAR 4
+/* hypotheses 100 000, seed 0, max_dist 0 (the caller sets it), edge_ratio 0.9, refits 1 */
+void symmicp_ransac_config_default(symmicp_ransac_config *cfg);
+int symmicp_ctx_ransac(symmicp_ctx *ctx, const float *src_xyz, size_t src_row_stride, size_t src_col_stride, size_t ns,
+                       const float *tgt_xyz, size_t tgt_row_stride, size_t tgt_col_stride, size_t nt,
+                       const int32_t *pairs, size_t m, const symmicp_ransac_config *cfg, float transform16[16],
+                       symmicp_ransac_result *result, uint8_t *inlier_mask_out, uint8_t *status_out, int32_t *inliers_out);
+int symmicp_ransac(int device, const float *src_xyz, size_t src_row_stride, size_t src_col_stride, size_t ns,
+                   const float *tgt_xyz, size_t tgt_row_stride, size_t tgt_col_stride, size_t nt,
+                   const int32_t *pairs, size_t m, const symmicp_ransac_config *cfg, float transform16[16],
+                   symmicp_ransac_result *result, uint8_t *inlier_mask_out, uint8_t *status_out, int32_t *inliers_out);
+/* test entry: the 12 floats (R row-major, then t, about the pivots) the device computed for every hypothesis: hyp_out
+ * [hypotheses][12], written for status EVALUATED and FAR, zero otherwise; pivots_out [6] = cs, ct.  Arguments as above. */
+int symmicp_ctx_ransac_hypotheses(symmicp_ctx *ctx, const float *src_xyz, size_t src_row_stride, size_t src_col_stride, size_t ns,
+                                  const float *tgt_xyz, size_t tgt_row_stride, size_t tgt_col_stride, size_t nt,
+                                  const int32_t *pairs, size_t m, const symmicp_ransac_config *cfg, float *hyp_out,
+                                  uint8_t *status_out, float pivots_out[6]);
 
 /* ---- voxel-grid downsampling (PCL's pcl::VoxelGrid, Open3D's voxel_down_sample), on the GPU -----------------------
  * Every point falls into the cubic voxel of edge `leaf` that holds it; each occupied voxel with at least min_points points
