@@ -168,12 +168,13 @@ extern "C++" void free_target(symmicp_ctx *c)
     hipFree(c->dbg); hipFree(c->dbg_trace); c->dbg_trace = nullptr;
     c->ctop = nullptr; c->dbg = nullptr; c->ix = TargetIndex{}; c->tgt_block = nullptr; c->tq = nullptr; c->tn = nullptr; c->boxes = nullptr; c->cells = nullptr; c->onodes = nullptr;
     c->have_index = false; c->n_t = 0;
+    c->notes = IndexNotes{};
 }
 
 extern "C++" void forget_source(symmicp_ctx *c)
 {
     // (the arrays live in one block, c->src_all, which is kept for the next source of the same or a smaller size)
-    c->worklist = c->wl_count = nullptr; c->cert = nullptr; c->certk = nullptr; c->hoodr = nullptr; c->pkt_tab = nullptr; c->pkt_count = 0; c->pairrec = nullptr;
+    c->worklist = c->wl_count = nullptr; c->cert = nullptr; c->certk = nullptr; c->hoodr = nullptr; c->pkt_tab = nullptr; c->pkt_count = 0; c->pkt_cost_keyed = false; c->pairrec = nullptr;
     c->src0_block = c->cur_block = nullptr; c->src_order = nullptr; c->pos = nullptr; c->d2 = nullptr; c->best64 = nullptr;
     c->n_loc = c->n_s_total = c->src_off = 0;
     c->src_no_normals = false;
@@ -426,12 +427,13 @@ static int build_octree(symmicp_ctx *c, const uint32_t *keys, const float4 *tq, 
 // on failure the caller's free_target() / cleanup releases them.
 static int build_index(symmicp_ctx *c, const CloudSoA &cl, uint32_t n, bool want_grid, float4 *tq, float4 *tn,
                        float4 **boxes_out, uint2 **cells_out, TargetIndex *ix_out, int32_t *glevel_out, int32_t *nlevels_out,
-                       float4 **onodes_out = nullptr, uint32_t **ctop_out = nullptr)
+                       float4 **onodes_out = nullptr, uint32_t **ctop_out = nullptr, IndexNotes *notes = nullptr)
 {
     DevBuf<uint32_t> order, keys;
     float origin[3], h0;
     int st = morton_order(c, cl, n, order, &keys, origin, &h0);
     if (st != SYMMICP_OK) return st;
+    if (notes) { *notes = IndexNotes{}; for (int k = 0; k < 3; k++) notes->origin[k] = origin[k]; notes->h0 = h0; }
     launch_gather_f4(cl.x, cl.y, cl.z, cl.nx, cl.ny, cl.nz, order.p, n, tq, tn, c->stream);
     TargetIndex ix{};
     ix.tq = tq; ix.tn = tn; ix.n = n;
@@ -443,6 +445,7 @@ static int build_index(symmicp_ctx *c, const CloudSoA &cl, uint32_t n, bool want
         uint32_t hh[16];
         HIP_TRY(c, hipMemcpyAsync(hh, hist.p, sizeof(hh), hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(c, hipStreamSynchronize(c->stream));
+        if (notes) std::memcpy(notes->hist, hh, sizeof(hh));
         // finest level whose occupied cells still hold >= ppc points on average
         const double ppc = c->sw.grid_ppc;
         int lcap = c->sw.grid_maxlevel;                  // the table is two-level: memory follows the occupied super-cells
@@ -490,6 +493,7 @@ static int build_index(symmicp_ctx *c, const CloudSoA &cl, uint32_t n, bool want
         const int tshift = 3 * (kMortonBits - ltop);
         const bool last_starts = (n == 1) || (tshift < 30 && (kl[1] >> tshift) != (kl[0] >> tshift));
         const size_t nblocks = (size_t)last_excl + (last_starts ? 1 : 0);
+        if (notes) { notes->nblocks = (uint32_t)nblocks; notes->ctop_len = (uint32_t)ntop; }
         HIP_TRY(c, keep_alloc(c, (void **)ctop_out, sizeof(uint32_t) * ntop));
         HIP_TRY(c, hipMemsetAsync(*ctop_out, 0xFF, sizeof(uint32_t) * ntop, c->stream));
         HIP_TRY(c, keep_alloc(c, (void **)cells_out, sizeof(uint2) * nblocks * 512));
@@ -531,6 +535,7 @@ static int build_index(symmicp_ctx *c, const CloudSoA &cl, uint32_t n, bool want
     if (onodes_out) {
         uint32_t leaf_max = c->target_surface_like ? 24u : 8u;      // (packets: 12 / 16 / 20 / 24 / 28 points per leaf: 0.425 / 0.411 / 0.394 / 0.389 / 0.394 ms first pass of the 1M surface pair)
         if (c->sw.oct_leaf > 0) leaf_max = (uint32_t)c->sw.oct_leaf;
+        if (notes) notes->leaf_max = leaf_max;
         st = build_octree(c, keys.p, tq, n, leaf_max, onodes_out, &ix);
         if (st != SYMMICP_OK) return st;
     }
@@ -583,7 +588,7 @@ int symmicp_set_target(symmicp_ctx *c, const float *xyz, size_t xr, size_t xc, c
         return SYMMICP_OK;
     }
     st = build_index(c, c->tgt, c->n_t, /*want_grid=*/true, c->tq, c->tn, &c->boxes, &c->cells, &c->ix, &c->st.grid_level, &c->st.tree_levels,
-                     &c->onodes, &c->ctop);
+                     &c->onodes, &c->ctop, &c->notes);
     if (st != SYMMICP_OK) { free_target(c); return st; }
     if (c->sw.debug_counters) {
         HIP_TRY(c, hipMalloc((void **)&c->dbg, 12 * sizeof(unsigned long long)));
@@ -718,7 +723,8 @@ int symmicp_set_source(symmicp_ctx *c, const float *xyz, size_t xr, size_t xc, c
             HIP_TRY(c, hipStreamSynchronize(c->stream));
             if (npk < nblk || npk > cap) { forget_source(c); return fail(c, SYMMICP_ERR_HIP, "packet table: count out of range"); }
             // the target is known already: key the start order by what a packet will cost (its distance to the target), not by its extent alone
-            if (c->have_index && c->ix.onodes && key_bits > 0 && c->sw.packet_cost_key) launch_packet_cost(c->src0, runs.p, npk, c->ix, keys.p, key_bits, c->stream);
+            c->pkt_cost_keyed = c->have_index && c->ix.onodes && key_bits > 0 && c->sw.packet_cost_key;
+            if (c->pkt_cost_keyed) launch_packet_cost(c->src0, runs.p, npk, c->ix, keys.p, key_bits, c->stream);
             radix_sort_pairs(keys.p, vals.p, kt.p, vt.p, npk, key_bits > 0 ? key_bits : 32, ws.p, wse, c->stream);
             c->pkt_tab = reinterpret_cast<uint32_t *>(c->src_all + o_pkt);
             c->pkt_count = npk;

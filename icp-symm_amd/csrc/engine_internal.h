@@ -5,6 +5,7 @@
 //   engine_exchange.cpp  multi-GPU: RCCL (loaded lazily), shared-memory exchange, communicator entry points
 //   engine_global.cpp    feature matching and RANSAC (symmicp_ctx_feature_nn, symmicp_ctx_feature_correspondences, symmicp_ctx_ransac)
 //   engine_debug.cpp     SYMMICP_DEBUG_COUNTERS / SYMMICP_DEBUG_TRACE dumps
+//   engine_probe.cpp     test entries: read-back of the target index and the source share, the sort and the scan on caller arrays
 #pragma once
 #include <hip/hip_runtime.h>
 #include <dlfcn.h>
@@ -84,7 +85,7 @@ struct Switches {
     double grid_ppc = 3.0;                 // points per occupied cell the grid level is chosen for (2.0 until the end of round 3: one level finer on the surface pairs -- 15 (query, cell) items of ~1 point per probe instead of 8 of ~4; 1M pair 12 740 -> 13 230 iter/s at 20 iterations, 250k / 4M +3 %, scan pairs and the 100k cube unchanged)
     int grid_maxlevel = kMortonBits, grid_level = -1;      // -1: chosen from the cloud; 0 disables the grid phase
     int first_pass = -1;                   // -1: decided per target (build_index); 0: per-thread walk; 1: packets
-    int oct_leaf = 0;                      // octree leaf size (0: 16 on surface-like targets, 8 otherwise)
+    int oct_leaf = 0;                      // octree leaf size (0: 24 on surface-like targets, 8 otherwise)
     bool packet_order = true;              // packets started longest-first
     bool packet_cost_key = true;           // ... keyed by their distance to the target when it is known at set_source (0: by radius alone)
     float packet_jump = -1.0f;             // cut factor of k_packet_runs (< 0: the default, 0: never cut)
@@ -126,6 +127,14 @@ struct ShmExchange {
     bool owner = false;
 };
 
+// What build_index knew and the index itself does not keep: a few words per target, read back by symmicp_ctx_index_info (tests)
+struct IndexNotes {
+    float origin[3] = {0, 0, 0}, h0 = 0.f;      // Morton frame: bounding-box minimum and the finest cell edge
+    uint32_t hist[16] = {};                    // level histogram the grid level and the surface-like flag were decided from
+    uint32_t leaf_max = 0;                     // octree leaf size in force
+    uint32_t nblocks = 0, ctop_len = 0;        // occupied super-cell blocks of the cell table, length of ctop
+};
+
 struct symmicp_ctx {
     Switches sw;                     // environment switches as they stood at symmicp_create
     Arena arena;                     // temporaries of one public call
@@ -158,6 +167,7 @@ struct symmicp_ctx {
     TargetIndex ix{};
     bool have_index = false;
     bool target_surface_like = false;   // decides the first-pass regime (build_index)
+    IndexNotes notes;                   // (tests: symmicp_ctx_index_info)
     float pivot[3] = {0, 0, 0};
     // source share
     uint32_t n_s_total = 0, n_loc = 0, src_off = 0;
@@ -175,6 +185,7 @@ struct symmicp_ctx {
     float *hoodr = nullptr;          // ... (T, radius hint) per source point
     uint32_t *pkt_tab = nullptr;     // TREE: the first pass's packets, (first query, count) in start order (widest first)
     uint32_t pkt_count = 0;
+    bool pkt_cost_keyed = false;     // ... started by their distance to the target (k_packet_cost), not by their radius
     uint32_t *pkt_fallbacks = nullptr;  // device counter: packets of first passes that finished depth-first (k_search_packet)
     unsigned long long *best64 = nullptr;
     uint32_t *worklist = nullptr, *wl_count = nullptr;   // the sharded work list + its counters

@@ -1,0 +1,149 @@
+// engine_probe.cpp -- test entries of the index build (include/symmicp.h, "test entry points of the index build"): read-back of the
+// target index and of the source share, and the build's two primitives (the radix sort and the exclusive scan) on caller arrays.
+// Nothing here is on a hot path, and nothing here changes the context: the read-backs copy device arrays to the host, the
+// primitives work in the scratch arena, which is dead between public calls anyway.
+#include "engine_internal.h"
+
+namespace {
+
+int copy_back(symmicp_ctx *c, void *dst, const void *src, size_t bytes)
+{
+    if (!dst || !bytes) return SYMMICP_OK;
+    if (!src) return fail(c, SYMMICP_ERR_STATE, "probe: the context does not hold this array");
+    HIP_TRY(c, hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c->stream));
+    return SYMMICP_OK;
+}
+
+bool has_target_index(const symmicp_ctx *c) { return c->have_index && c->cfg.corr == SYMMICP_CORR_TREE && c->tq && c->boxes && c->onodes; }
+
+void fill_info(const symmicp_ctx *c, symmicp_index_info *o)
+{
+    const TargetIndex &ix = c->ix;
+    std::memset(o, 0, sizeof(*o));
+    o->struct_size = (int32_t)sizeof(*o);
+    o->n = ix.n;
+    o->grid_level = ix.glevel;
+    o->gdim = ix.gdim;
+    for (int k = 0; k < 3; k++) o->origin[k] = c->notes.origin[k];
+    o->h0 = c->notes.h0;
+    o->h = ix.h;
+    o->inv_h = ix.inv_h;
+    o->tree_levels = ix.top + 1;
+    o->top = ix.top;
+    o->ntop = ix.ntop;
+    static_assert(sizeof(o->level_off) == sizeof(ix.level_off) && sizeof(o->olevel_off) == sizeof(ix.olevel_off), "info mirrors TargetIndex");
+    std::memcpy(o->level_off, ix.level_off, sizeof(o->level_off));
+    o->n_boxes = ix.level_off[ix.top] + ix.ntop;          // (the top level is not padded)
+    std::memcpy(o->olevel_off, ix.olevel_off, sizeof(o->olevel_off));
+    o->n_onodes = ix.olevel_off[kMortonBits + 1];
+    o->n_blocks = c->notes.nblocks;
+    o->ctop_len = c->notes.ctop_len;
+    o->leaf_max = c->notes.leaf_max;
+    o->surface_like = c->target_surface_like ? 1 : 0;
+    std::memcpy(o->level_hist, c->notes.hist, sizeof(o->level_hist));
+}
+
+}  // namespace
+
+extern "C" {
+
+int symmicp_ctx_index_info(symmicp_ctx *c, symmicp_index_info *info)
+{
+    if (!c) return SYMMICP_ERR_ARG;
+    if (!info || info->struct_size != (int32_t)sizeof(symmicp_index_info)) return fail(c, SYMMICP_ERR_ARG, "index_info: null info or wrong struct_size");
+    if (!has_target_index(c)) return fail(c, SYMMICP_ERR_STATE, "index_info: no target index (SYMMICP_CORR_TREE after set_target)");
+    fill_info(c, info);
+    return SYMMICP_OK;
+}
+
+int symmicp_ctx_index_arrays(symmicp_ctx *c, float *tq, float *tn, float *boxes, uint32_t *ctop, uint32_t *cells, float *onodes)
+{
+    if (!c) return SYMMICP_ERR_ARG;
+    if (!has_target_index(c)) return fail(c, SYMMICP_ERR_STATE, "index_arrays: no target index (SYMMICP_CORR_TREE after set_target)");
+    symmicp_index_info o;
+    fill_info(c, &o);
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t f4 = sizeof(float4);
+    const struct { void *dst; const void *src; size_t bytes; } parts[] = {
+        {tq, c->tq, f4 * o.n},
+        {tn, c->tn, f4 * 2 * o.n},
+        {boxes, c->boxes, f4 * 2 * o.n_boxes},
+        {ctop, c->ctop, sizeof(uint32_t) * (o.grid_level > 0 ? o.ctop_len : 0)},
+        {cells, c->cells, sizeof(uint2) * 512 * (size_t)(o.grid_level > 0 ? o.n_blocks : 0)},
+        {onodes, c->onodes, f4 * 2 * o.n_onodes},
+    };
+    for (const auto &p : parts) {
+        const int st = copy_back(c, p.dst, p.src, p.bytes);
+        if (st != SYMMICP_OK) { (void)hipStreamSynchronize(c->stream); return st; }
+    }
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return SYMMICP_OK;
+}
+
+int symmicp_ctx_source_share(symmicp_ctx *c, size_t *n_local, size_t *pkt_count, int32_t *sorted, int32_t *cost_keyed, uint32_t *order,
+                             uint32_t *pkt_tab)
+{
+    if (!c) return SYMMICP_ERR_ARG;
+    if (!c->src0_block) return fail(c, SYMMICP_ERR_STATE, "source_share: no source (set_source first)");
+    if (order && !c->src_order) return fail(c, SYMMICP_ERR_STATE, "source_share: the share is not sorted (it is in the caller's order)");
+    if (n_local) *n_local = c->n_loc;
+    if (pkt_count) *pkt_count = c->pkt_tab ? c->pkt_count : 0;
+    if (sorted) *sorted = c->src_order ? 1 : 0;
+    if (cost_keyed) *cost_keyed = (c->pkt_tab && c->pkt_cost_keyed) ? 1 : 0;
+    if (!order && !pkt_tab) return SYMMICP_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    int st = copy_back(c, order, c->src_order, sizeof(uint32_t) * c->n_loc);
+    if (st == SYMMICP_OK && c->pkt_tab) st = copy_back(c, pkt_tab, c->pkt_tab, sizeof(uint32_t) * 2 * c->pkt_count);
+    const hipError_t e = hipStreamSynchronize(c->stream);
+    if (st != SYMMICP_OK) return st;
+    HIP_TRY(c, e);
+    return SYMMICP_OK;
+}
+
+int symmicp_ctx_radix_sort_probe(symmicp_ctx *c, uint32_t *keys, uint32_t *vals, size_t n, int key_bits)
+{
+    if (!c) return SYMMICP_ERR_ARG;
+    if (key_bits < 0 || key_bits > 32 || n > 0x7fffffffull || (n && (!keys || !vals))) return fail(c, SYMMICP_ERR_ARG, "radix_sort_probe: bad arguments");
+    if (n == 0) return SYMMICP_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    const uint32_t m = (uint32_t)n;
+    const size_t wse = radix_sort_ws_elems(m), bytes = sizeof(uint32_t) * n;
+    arena_begin(c->arena, 4 * (bytes + 256) + sizeof(uint32_t) * wse + 4096);
+    DevBuf<uint32_t> k, v, kt, vt, ws;
+    HIP_TRY(c, k.alloc_temp(c->arena, n));
+    HIP_TRY(c, v.alloc_temp(c->arena, n));
+    HIP_TRY(c, kt.alloc_temp(c->arena, n));
+    HIP_TRY(c, vt.alloc_temp(c->arena, n));
+    HIP_TRY(c, ws.alloc_temp(c->arena, wse));
+    HIP_TRY(c, hipMemcpyAsync(k.p, keys, bytes, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(v.p, vals, bytes, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));        // (pageable host memory: the copies are done before the buffers may go)
+    radix_sort_pairs(k.p, v.p, kt.p, vt.p, m, key_bits, ws.p, wse, c->stream);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpyAsync(keys, k.p, bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(vals, v.p, bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return SYMMICP_OK;
+}
+
+int symmicp_ctx_scan_probe(symmicp_ctx *c, uint32_t *data, size_t n)
+{
+    if (!c) return SYMMICP_ERR_ARG;
+    if (n > 0x7fffffffull || (n && !data)) return fail(c, SYMMICP_ERR_ARG, "scan_probe: bad arguments");
+    if (n == 0) return SYMMICP_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t bytes = sizeof(uint32_t) * n, tiles = n / 2048 + 2;       // (as build_octree sizes the scan's scratch)
+    arena_begin(c->arena, bytes + sizeof(uint32_t) * tiles + 4096);
+    DevBuf<uint32_t> d, ws;
+    HIP_TRY(c, d.alloc_temp(c->arena, n));
+    HIP_TRY(c, ws.alloc_temp(c->arena, tiles));
+    HIP_TRY(c, hipMemcpyAsync(d.p, data, bytes, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    launch_exclusive_scan(d.p, (uint32_t)n, ws.p, c->stream);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpyAsync(data, d.p, bytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return SYMMICP_OK;
+}
+
+}  // extern "C"

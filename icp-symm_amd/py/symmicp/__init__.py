@@ -90,6 +90,15 @@ class RansacResult(C.Structure):
                 ("rmse_final", C.c_double), ("transform", C.c_double * 16)]
 
 
+class IndexInfo(C.Structure):
+    """symmicp_index_info: what symmicp_ctx_index_info reads back of a target index (tests)"""
+    _fields_ = [("struct_size", C.c_int32), ("n", C.c_uint32), ("grid_level", C.c_int32), ("gdim", C.c_int32), ("origin", C.c_float * 3),
+                ("h0", C.c_float), ("h", C.c_float), ("inv_h", C.c_float), ("tree_levels", C.c_int32), ("top", C.c_int32), ("ntop", C.c_uint32),
+                ("level_off", C.c_uint32 * 12), ("n_boxes", C.c_uint32), ("olevel_off", C.c_uint32 * 12), ("n_onodes", C.c_uint32),
+                ("n_blocks", C.c_uint32), ("ctop_len", C.c_uint32), ("leaf_max", C.c_uint32), ("surface_like", C.c_int32),
+                ("level_hist", C.c_uint32 * 16)]
+
+
 KERNEL_SLOTS = ["k_search_cells", "(gap)", "k_search_walk", "k_accumulate", "k_final_reduce", "single_pass_kernel", "whole_pass"]
 
 
@@ -107,6 +116,7 @@ EXPORTS = [
     "symmicp_radius_search", "symmicp_ctx_radius_search", "symmicp_fpfh", "symmicp_ctx_fpfh",
     "symmicp_feature_nn", "symmicp_ctx_feature_nn", "symmicp_feature_correspondences", "symmicp_ctx_feature_correspondences",
     "symmicp_ransac_config_default", "symmicp_ransac", "symmicp_ctx_ransac", "symmicp_ctx_ransac_hypotheses",
+    "symmicp_ctx_index_info", "symmicp_ctx_index_arrays", "symmicp_ctx_source_share", "symmicp_ctx_radix_sort_probe", "symmicp_ctx_scan_probe",
 ]
 
 _lib = None
@@ -207,6 +217,12 @@ def lib():
     L.symmicp_ransac.argtypes = [C.c_int] + rsc + [fp, C.POINTER(RansacResult), u8p, u8p, i32p]
     L.symmicp_ctx_ransac.argtypes = [vp] + rsc + [fp, C.POINTER(RansacResult), u8p, u8p, i32p]
     L.symmicp_ctx_ransac_hypotheses.argtypes = [vp] + rsc + [fp, u8p, fp]
+    u32p, szp = C.POINTER(C.c_uint32), C.POINTER(C.c_size_t)
+    L.symmicp_ctx_index_info.argtypes = [vp, C.POINTER(IndexInfo)]
+    L.symmicp_ctx_index_arrays.argtypes = [vp, fp, fp, fp, u32p, u32p, fp]
+    L.symmicp_ctx_source_share.argtypes = [vp, szp, szp, i32p, i32p, u32p, u32p]
+    L.symmicp_ctx_radix_sort_probe.argtypes = [vp, u32p, u32p, C.c_size_t, C.c_int]
+    L.symmicp_ctx_scan_probe.argtypes = [vp, u32p, C.c_size_t]
     _lib = L
     return L
 
@@ -879,6 +895,64 @@ class Engine:
                                                  _fptr(ri), _fptr(rX), _fptr(rrc), i32(r2)))
         return dict(stop=int(st[0]), reason=int(st[1]), iters=int(st[2]), small_step=int(st[3]), X=X.reshape(4, 4), Xapply=Xa.reshape(3, 4),
                     ring_increment=ri.reshape(4, 4), ring_X=rX.reshape(4, 4), ring_rcond=float(rrc[0]), ring_status=int(r2[0]), ring_solved=int(r2[1]))
+
+    # ---- test entry points of the index build (read-only) ----
+    def index_info(self):
+        """symmicp_ctx_index_info -> dict of the target index's scalars (arrays as numpy)"""
+        o = IndexInfo()
+        o.struct_size = C.sizeof(IndexInfo)
+        self._chk(self._L.symmicp_ctx_index_info(self._h, C.byref(o)))
+        d = {k: getattr(o, k) for k, _ in IndexInfo._fields_ if k != "struct_size"}
+        d["origin"] = np.array(o.origin, np.float32)
+        for k in ("h0", "h", "inv_h"):
+            d[k] = np.float32(d[k])
+        d["level_off"] = np.array(o.level_off, np.uint32)
+        d["olevel_off"] = np.array(o.olevel_off, np.uint32)
+        d["level_hist"] = np.array(o.level_hist, np.uint32)
+        d["surface_like"] = bool(o.surface_like)
+        return d
+
+    def index_arrays(self):
+        """symmicp_ctx_index_info + symmicp_ctx_index_arrays -> the info dict plus tq [n,4], tn [n,2,4], boxes [n_boxes,2,4], onodes
+        [n_onodes,2,4] (f32; integer words keep their bits: view them as uint32), ctop [ctop_len] and cells [n_blocks * 512, 2] (uint32)"""
+        d = self.index_info()
+        gl = d["grid_level"] > 0
+        d["tq"] = np.zeros((d["n"], 4), np.float32)
+        d["tn"] = np.zeros((d["n"], 2, 4), np.float32)
+        d["boxes"] = np.zeros((d["n_boxes"], 2, 4), np.float32)
+        d["ctop"] = np.zeros(d["ctop_len"] if gl else 0, np.uint32)
+        d["cells"] = np.zeros(((d["n_blocks"] if gl else 0) * 512, 2), np.uint32)
+        d["onodes"] = np.zeros((d["n_onodes"], 2, 4), np.float32)
+        u32 = lambda a: a.ctypes.data_as(C.POINTER(C.c_uint32)) if a.size else None
+        self._chk(self._L.symmicp_ctx_index_arrays(self._h, _fptr(d["tq"]), _fptr(d["tn"]), _fptr(d["boxes"]), u32(d["ctop"]), u32(d["cells"]),
+                                                   _fptr(d["onodes"])))
+        return d
+
+    def source_share(self):
+        """symmicp_ctx_source_share -> dict(n_local, pkt_count, sorted, cost_keyed, order [n_local] uint32 or None, pkt_tab [pkt_count,2])"""
+        nl, npk, so, ck = C.c_size_t(0), C.c_size_t(0), C.c_int32(0), C.c_int32(0)
+        self._chk(self._L.symmicp_ctx_source_share(self._h, C.byref(nl), C.byref(npk), C.byref(so), C.byref(ck), None, None))
+        order = np.zeros(nl.value, np.uint32) if so.value else None
+        tab = np.zeros((npk.value, 2), np.uint32)
+        u32 = lambda a: a.ctypes.data_as(C.POINTER(C.c_uint32)) if a is not None and a.size else None
+        self._chk(self._L.symmicp_ctx_source_share(self._h, None, None, None, None, u32(order), u32(tab)))
+        return dict(n_local=nl.value, pkt_count=npk.value, sorted=bool(so.value), cost_keyed=bool(ck.value), order=order, pkt_tab=tab)
+
+    def radix_sort_probe(self, keys, vals, key_bits):
+        """the build's radix sort on host arrays (symmicp_ctx_radix_sort_probe) -> (keys, vals) sorted, as new uint32 arrays"""
+        k = np.array(keys, np.uint32).reshape(-1)
+        v = np.array(vals, np.uint32).reshape(-1)
+        if k.shape != v.shape:
+            raise ValueError("keys and vals differ in length")
+        u32 = lambda a: a.ctypes.data_as(C.POINTER(C.c_uint32))
+        self._chk(self._L.symmicp_ctx_radix_sort_probe(self._h, u32(k), u32(v), k.size, int(key_bits)))
+        return k, v
+
+    def scan_probe(self, data):
+        """the build's exclusive scan on a host array (symmicp_ctx_scan_probe) -> new uint32 array"""
+        d = np.array(data, np.uint32).reshape(-1)
+        self._chk(self._L.symmicp_ctx_scan_probe(self._h, d.ctypes.data_as(C.POINTER(C.c_uint32)), d.size))
+        return d
 
     def set_loop_log(self, on=True):
         self._chk(self._L.symmicp_set_loop_log(self._h, int(bool(on))))

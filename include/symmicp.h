@@ -283,6 +283,45 @@ int symmicp_set_loop_log(symmicp_ctx *ctx, int on);
 /* the log of the last symmicp_align: *count entries in all, min(cap, *count) of them copied to out (out may be NULL) */
 int symmicp_get_loop_log(const symmicp_ctx *ctx, symmicp_loop_log_entry *out, size_t cap, size_t *count);
 
+/* ---- test entry points of the index build (off the hot path; read-only: clouds, index, certificates and statistics stay as they
+ * were).  What a test compares with its own restatement of the build (tests/_index_ref.py). ----- */
+typedef struct {
+    int32_t struct_size;        /* sizeof(symmicp_index_info), set by the caller */
+    uint32_t n;                 /* target points */
+    int32_t grid_level;         /* level of the cell table (0: none) */
+    int32_t gdim;               /* 1 << grid_level (0 without a table) */
+    float origin[3];            /* bounding-box minimum: the Morton frame */
+    float h0, h, inv_h;         /* finest cell edge; cell edge at grid_level and its inverse (0 without a table) */
+    int32_t tree_levels;        /* levels of the box tree: top + 1 */
+    int32_t top;                /* index of its top level */
+    uint32_t ntop;              /* nodes in the top level */
+    uint32_t level_off[12];     /* first node of every box-tree level */
+    uint32_t n_boxes;           /* nodes of the box tree in all, padding included: boxes holds 2 float4 per node */
+    uint32_t olevel_off[12];    /* first node of octree level 0 .. 10, and their total */
+    uint32_t n_onodes;          /* = olevel_off[11]: onodes holds 2 float4 per node */
+    uint32_t n_blocks;          /* occupied super-cells: cells holds n_blocks * 512 (first, last + 1) pairs */
+    uint32_t ctop_len;          /* length of ctop */
+    uint32_t leaf_max;          /* octree leaf size in force */
+    int32_t surface_like;       /* the first-pass regime decided for this target (1: packets) */
+    uint32_t level_hist[16];    /* [l], l = 1 .. 10: adjacent sorted pairs whose keys first differ at octree level l */
+} symmicp_index_info;
+/* the target index of a SYMMICP_CORR_TREE context after symmicp_set_target (SYMMICP_ERR_STATE without one) */
+int symmicp_ctx_index_info(symmicp_ctx *ctx, symmicp_index_info *info);
+/* copies of its arrays, each may be NULL: tq [n][4], tn [n][2][4], boxes [n_boxes][2][4], ctop [ctop_len], cells [n_blocks * 512][2],
+ * onodes [n_onodes][2][4] (floats as the device holds them: integer words keep their bits) */
+int symmicp_ctx_index_arrays(symmicp_ctx *ctx, float *tq, float *tn, float *boxes, uint32_t *ctop, uint32_t *cells, float *onodes);
+/* this rank's source share after symmicp_set_source.  Sizes: *n_local points, *pkt_count packets (0: no table, the first pass takes 64
+ * queries as they lie), *sorted != 0: the share is in Morton order, *cost_keyed != 0: the packets are started by their distance to the
+ * target.  Arrays, each may be NULL: order [n_local] = the caller's row of every share position (SYMMICP_ERR_STATE when asked of an
+ * unsorted share), pkt_tab [pkt_count][2] = (first query, count) in start order.  Any size pointer may be NULL. */
+int symmicp_ctx_source_share(symmicp_ctx *ctx, size_t *n_local, size_t *pkt_count, int32_t *sorted, int32_t *cost_keyed, uint32_t *order,
+                             uint32_t *pkt_tab);
+/* the build's primitives on host arrays, run on the context's stream with its scratch arena.  Stable ascending sort of (keys, vals) by
+ * the low key_bits bits (0 .. 32, keys < 2^key_bits; the voxel sort passes 0 for a single voxel: no pass runs), in place; exclusive prefix sum of data (mod 2^32), in place.  n == 0 is OK and
+ * launches nothing; n < 2^31. */
+int symmicp_ctx_radix_sort_probe(symmicp_ctx *ctx, uint32_t *keys, uint32_t *vals, size_t n, int key_bits);
+int symmicp_ctx_scan_probe(symmicp_ctx *ctx, uint32_t *data, size_t n);
+
 /* ---- normals pre-step (replaces MyICP::estimateNormals, myicp.cpp:152-172: PCL NormalEstimation,
  * setKSearch(10), viewpoint (0,0,0)).  Exact k-NN (the point itself included) + PCA on the GPU.
  * xyz strided as in set_source; nrm_out packed AoS [n][3]; curv_out (lambda_min / trace) may be NULL;
