@@ -12,6 +12,8 @@
 //                              PLANE: the point-to-plane distance itself; GICP: the pair's Mahalanobis distance)
 //     --threshold D            stop once the summed pair distance is <= D   (default 1.0, ICP/myicp.cpp:6)
 //     --max-dist D             drop pairs farther apart than D (default 0: keep every pair)
+//     --trim F                 trimmed ICP: every pass keeps the closest fraction F of its pairs, 0 < F <= 1 (default 1: all of them;
+//                              for clouds that overlap only in part; not with --mode quirks)
 //     --scale LEAF:ITERS[:MAXDIST]   one level of a coarse-to-fine alignment (repeat it, coarse first): both clouds
 //                              voxel-downsampled with edge LEAF (0: as given), at most ITERS iterations, pairs farther than
 //                              MAXDIST dropped (default 0: none); each level starts from the one before.  Needs --corr tree
@@ -40,7 +42,7 @@
 static int usage(const char *argv0, const char *complaint)
 {
     std::fprintf(stderr, "%s\nusage: %s [--mode quirks|paper|plane|gicp] [--corr identity|tree] [--iters N] [--threshold D] [--loss none|huber|tukey|cauchy|gm]"
-                 " [--loss-scale S] [--gicp-epsilon E] [--max-dist D] [--scale LEAF:ITERS[:MAXDIST]]... [--init global --fpfh-radius R --ransac-dist D [--ransac-iters H] [--seed S] [--init-voxel L]] [--out file.pcd] [--quiet] [source.pcd target.pcd]\n",
+                 " [--loss-scale S] [--gicp-epsilon E] [--max-dist D] [--trim F] [--scale LEAF:ITERS[:MAXDIST]]... [--init global --fpfh-radius R --ransac-dist D [--ransac-iters H] [--seed S] [--init-voxel L]] [--out file.pcd] [--quiet] [source.pcd target.pcd]\n",
                  complaint, argv0);
     return 64;
 }
@@ -57,6 +59,7 @@ int main(int argc, char **argv)
     bool gicp = false, have_eps = false;
     float gicp_eps = 0.f;
     bool tree = false;
+    float trim = 1.f;
     std::vector<MyICP::VoxelLevel> levels;
     bool init_global = false, have_init_option = false;
     MyICP::GlobalInit ginit;
@@ -113,6 +116,11 @@ int main(int argc, char **argv)
             const float d = std::strtof(v, &end);
             if (end == v || *end || !std::isfinite(d)) return usage(argv[0], "--max-dist needs a number");
             icp.setMaxCorrespondenceDistance(d);
+        } else if (a == "--trim") {
+            char *end = nullptr;
+            const char *v = value("--trim");
+            trim = std::strtof(v, &end);
+            if (end == v || *end || !(trim > 0.f) || trim > 1.f) return usage(argv[0], "--trim needs a fraction F with 0 < F <= 1");
         } else if (a == "--scale") {
             // LEAF:ITERS[:MAXDIST]
             const char *v = value("--scale");
@@ -160,6 +168,10 @@ int main(int argc, char **argv)
         if (quirks) return usage(argv[0], "--loss needs --mode paper, plane or gicp (quirks is the reference as written)");
         if (!have_scale || !(loss_scale > 0.f) || !std::isfinite(loss_scale)) return usage(argv[0], "--loss needs --loss-scale S with S > 0");
         icp.setRobustLoss(loss, loss_scale);
+    }
+    if (trim < 1.f) {
+        if (quirks) return usage(argv[0], "--trim below 1 needs --mode paper, plane or gicp (quirks is the reference as written)");
+        icp.setTrimFraction(trim);
     }
     if (!levels.empty()) {
         if (!tree) return usage(argv[0], "--scale needs --corr tree (identity pairing cannot pair clouds of different sizes)");

@@ -199,6 +199,7 @@ void symmicp_destroy(symmicp_ctx *c)
     free_target(c);
     free_source(c);
     hipFree(c->partials); hipFree(c->d_sums); hipFree(c->ticket); hipFree(c->arena.base); hipFree(c->keep.base);
+    hipFree(c->trim_keys); hipFree(c->trim_ws);
     if (c->h_sums) hipHostFree(c->h_sums);
     hipFree(c->d_loop);
     if (c->h_loop) hipHostFree(c->h_loop);
@@ -220,6 +221,8 @@ int symmicp_set_config(symmicp_ctx *c, const symmicp_config *cfg)
     if ((c->n_t || c->n_loc) && cfg->sort_source != c->cfg.sort_source) return fail(c, SYMMICP_ERR_STATE, "sort_source cannot change after clouds are set");
     if (cfg->mode == SYMMICP_MODE_QUIRKS && c->loss != SYMMICP_LOSS_NONE)
         return fail(c, SYMMICP_ERR_ARG, "QUIRKS takes no robust loss (set SYMMICP_LOSS_NONE first)");
+    if (cfg->mode == SYMMICP_MODE_QUIRKS && c->trim_frac < 1.0f)
+        return fail(c, SYMMICP_ERR_ARG, "QUIRKS takes no trim fraction below 1 (set 1 first)");
     if (c->src_no_normals && cfg->mode != SYMMICP_MODE_PLANE)
         return fail(c, SYMMICP_ERR_STATE, "the source was set without normals: only SYMMICP_MODE_PLANE can run on it");
     if (c->src_no_normals && cfg->min_normal_dot > -1.0f)
@@ -228,6 +231,7 @@ int symmicp_set_config(symmicp_ctx *c, const symmicp_config *cfg)
     c->cfg = *cfg;
     c->cfg.device = dev;
     c->begun = false;
+    c->trim_valid = false;
     return SYMMICP_OK;
 }
 
@@ -256,6 +260,34 @@ int symmicp_get_robust_loss(const symmicp_ctx *c, int *loss, float *scale)
     if (!c) return SYMMICP_ERR_ARG;
     if (loss) *loss = c->loss;
     if (scale) *scale = c->loss_scale;
+    return SYMMICP_OK;
+}
+
+// ---- trimmed ICP ---------------------------------------------------------------------------------
+int symmicp_set_trim_fraction(symmicp_ctx *c, float fraction)
+{
+    if (!c) return SYMMICP_ERR_ARG;
+    if (!(fraction > 0.f && fraction <= 1.f)) return fail(c, SYMMICP_ERR_ARG, "trim fraction: 0 < fraction <= 1");      // (NaN fails both)
+    if (fraction < 1.f && c->cfg.mode == SYMMICP_MODE_QUIRKS) return fail(c, SYMMICP_ERR_ARG, "QUIRKS takes no trim fraction below 1");
+    if (fraction < 1.f && c->nranks > 1) return fail(c, SYMMICP_ERR_STATE, "trimming needs a quantile over all ranks: single-rank contexts only");
+    c->trim_frac = fraction;
+    return SYMMICP_OK;
+}
+
+int symmicp_get_trim_fraction(const symmicp_ctx *c, float *fraction)
+{
+    if (!c || !fraction) return SYMMICP_ERR_ARG;
+    *fraction = c->trim_frac;
+    return SYMMICP_OK;
+}
+
+int symmicp_get_trim_state(const symmicp_ctx *c, uint64_t *candidates, uint64_t *kept, float *tau_d2)
+{
+    if (!c) return SYMMICP_ERR_ARG;
+    if (!c->begun || !c->trim_valid) return SYMMICP_ERR_STATE;      // (const context: no message)
+    if (candidates) *candidates = c->trim_nc;
+    if (kept) *kept = c->trim_kept;
+    if (tau_d2) std::memcpy(tau_d2, &c->trim_tau, sizeof(float));
     return SYMMICP_OK;
 }
 
@@ -617,6 +649,7 @@ int symmicp_set_source(symmicp_ctx *c, const float *xyz, size_t xr, size_t xc, c
     const double t0 = now_s();
     forget_source(c);
     c->begun = false;
+    c->trim_valid = false;
     // This rank's share is a contiguous block of the CALLER's rows, and only those rows are uploaded and sorted: set_source costs
     // 1/nranks of the single-GPU call on every rank (round 1 uploaded and sorted the whole cloud on every rank and kept a
     // slice of the global Morton order).  Any partition of the source is exact -- queries are independent given the
@@ -824,7 +857,9 @@ int symmicp_get_correspondences(symmicp_ctx *c, int32_t *idx, float *d2, size_t 
         X.nrm_w = 0.f;
         launch_pairs_d2(incr ? c->cur : c->src0, X, c->pos, c->tq, c->n_t, c->n_loc, c->d2, c->stream);
     }
-    launch_corr_out(c->pos, c->best64, c->d2, c->tq, c->src_order, c->n_loc, mode, c->src_off, d_idx.p, d_d2.p, c->stream);
+    // (after a trimmed pass a row that was no candidate, or was trimmed away, is reported as rejected)
+    launch_corr_out(c->pos, c->best64, c->d2, c->tq, c->src_order, c->n_loc, mode, c->src_off, d_idx.p, d_d2.p,
+                    c->trim_valid ? c->trim_keys : nullptr, c->trim_tau, c->stream);
     if (idx) HIP_TRY(c, hipMemcpyAsync(idx, d_idx.p, sizeof(int32_t) * need, hipMemcpyDeviceToHost, c->stream));
     if (d2) HIP_TRY(c, hipMemcpyAsync(d2, d_d2.p, sizeof(float) * need, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));

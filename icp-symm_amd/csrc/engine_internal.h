@@ -145,6 +145,13 @@ struct symmicp_ctx {
     int loss = SYMMICP_LOSS_NONE;    // robust loss (symmicp_set_robust_loss) and its scale: read by every pass
     float loss_scale = 0.f;
     float gicp_eps = 1e-3f;          // SYMMICP_MODE_GICP's covariance eps (symmicp_set_gicp_epsilon): read by every GICP pass
+    // trimmed ICP (symmicp_set_trim_fraction): the fraction (1 = off), the per-row keys and the select's workspace (allocated by the
+    // first trimmed pass), and what the most recent pass left (symmicp_get_trim_state; trim_valid: that pass was trimmed)
+    float trim_frac = 1.0f;
+    uint32_t *trim_keys = nullptr, *trim_ws = nullptr;
+    size_t trim_keys_cap = 0;
+    bool trim_valid = false;
+    uint32_t trim_nc = 0, trim_kept = 0, trim_tau = 0;
     int device = 0;
     hipStream_t stream = nullptr;
     std::string err;

@@ -47,10 +47,31 @@ static void fill_pass_args(symmicp_ctx *c, PassArgs &a, const float Xapply[16], 
     a.pkt_lds_pad = c->sw.packet_lds_pad;
     a.loss = c->loss;
     a.loss_scale = c->loss_scale;
+    // trimmed pass (run_pass has made sure of the buffers); the result lands behind the record's sequence word in host-mapped memory
+    const bool trim = c->trim_frac < 1.0f && c->trim_keys && c->trim_ws;
+    a.trim_keys = trim ? c->trim_keys : nullptr;
+    a.trim_ws = trim ? c->trim_ws : nullptr;
+    a.trim_host = trim ? reinterpret_cast<uint32_t *>(c->h_sums_dev + kNSum + 1) : nullptr;
+    a.trim_rho = c->trim_frac;
 }
 
 static int run_pass(symmicp_ctx *c, const float Xapply[16], bool from_cur, bool writeback, bool first)
 {
+    // Trimmed pass (trim_frac < 1): search as always, then the keys of the candidates and the exact select of tau (kernels_select.hip:
+    // one memset and six launches, issued by the pass launchers in front of the accumulating kernel), then the accumulation over the
+    // pairs at or below tau and the final reduce.  With trim_frac == 1 nothing below differs from an untrimmed build.
+    const bool trim = c->trim_frac < 1.0f;
+    if (trim) {
+        const size_t want = c->n_loc ? c->n_loc : 1;
+        if (c->trim_keys_cap < want) {
+            hipFree(c->trim_keys);
+            c->trim_keys = nullptr; c->trim_keys_cap = 0;
+            HIP_TRY(c, hipMalloc((void **)&c->trim_keys, sizeof(uint32_t) * want));
+            c->trim_keys_cap = want;
+        }
+        if (!c->trim_ws) HIP_TRY(c, hipMalloc((void **)&c->trim_ws, sizeof(uint32_t) * kTrimWsWords));
+    }
+    c->trim_valid = false;
     PassArgs a{};
     fill_pass_args(c, a, Xapply, from_cur, writeback, first);
     int blocks = (int)((c->n_loc + kPassThreads - 1) / kPassThreads);
@@ -113,6 +134,7 @@ static int run_pass(symmicp_ctx *c, const float Xapply[16], bool from_cur, bool 
             // after all the pass is repaired below (walk, accumulate and reduce again).
             optimistic = c->sw.optimistic >= 0 ? c->sw.optimistic == 1 : (!first && c->last_list_len == 0);      // (SYMMICP_OPTIMISTIC: "0" never, "1" always)
             if (writeback) optimistic = false;      // in-place write-back: a repair would transform the cloud twice
+            if (trim) optimistic = false;           // the keys are taken from final pairs
             // per-kernel events only in timing mode 2; mode 1 brackets the pass (events 0 and 4)
             if (first && c->target_surface_like) launch_pass_tree_first(a, c->ix, c->wl, ab, c->stream, c->timing == 2 ? ev : nullptr);
             else
@@ -180,6 +202,11 @@ static int run_pass(symmicp_ctx *c, const float Xapply[16], bool from_cur, bool 
         if (int st = reduce_and_wait(0)) return st;
         if (c->shm.slots) { if (int st = shm_exchange(c, c->h_sums)) return st; }
     }
+    if (trim) {
+        const volatile uint32_t *w = reinterpret_cast<const volatile uint32_t *>(c->h_sums + kNSum + 1);      // (written before the record: same stream)
+        c->trim_nc = w[0]; c->trim_kept = w[1]; c->trim_tau = w[2];
+        c->trim_valid = true;
+    }
     if (ev) c->ev_used++;
     c->t_last_done = now_s(); c->n_pass_timed++;
     if (c->dbg_trace && first) dump_packet_trace(c);
@@ -211,6 +238,7 @@ static uint32_t loop_scan_limit(uint32_t n) { const uint32_t f = n / 256; return
 static bool batch_eligible(const symmicp_ctx *c)
 {
     if (c->sw.host_loop) return false;                                    // SYMMICP_HOST_LOOP=1: never batch (A/B runs, tests)
+    if (c->trim_frac < 1.0f) return false;                                // trimmed passes: the fused pass and the device loop have no select
     if (c->cfg.host_loop) return false;
     if (c->external_exchange || c->shm.slots) return false;               // those exchanges run on the host
     if (c->timing == 2 || c->ix.dbg) return false;                        // per-kernel tables and debug counters: host loop

@@ -126,6 +126,28 @@ int symmicp_ctx_radix_sort_probe(symmicp_ctx *c, uint32_t *keys, uint32_t *vals,
     return SYMMICP_OK;
 }
 
+int symmicp_ctx_select_probe(symmicp_ctx *c, const uint32_t *keys, size_t n, uint64_t k, uint32_t *kth_out, uint64_t *n_le_out)
+{
+    if (!c) return SYMMICP_ERR_ARG;
+    if (!keys || !kth_out || !n_le_out || n == 0 || n > 0x7fffffffull || k < 1 || k > n) return fail(c, SYMMICP_ERR_ARG, "select_probe: bad arguments");
+    HIP_TRY(c, hipSetDevice(c->device));
+    const size_t bytes = sizeof(uint32_t) * n;
+    arena_begin(c->arena, bytes + sizeof(uint32_t) * kTrimWsWords + 4096);
+    DevBuf<uint32_t> d, ws;
+    HIP_TRY(c, d.alloc_temp(c->arena, n));
+    HIP_TRY(c, ws.alloc_temp(c->arena, kTrimWsWords));      // (its own workspace: the context's trim state stays as it was)
+    HIP_TRY(c, hipMemcpyAsync(d.p, keys, bytes, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    launch_select_probe(d.p, (uint32_t)n, (uint32_t)k, ws.p, c->stream);
+    HIP_TRY(c, hipGetLastError());
+    uint32_t state[8] = {};
+    HIP_TRY(c, hipMemcpyAsync(state, ws.p, sizeof(state), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    *kth_out = state[kTrimTauWord];
+    *n_le_out = state[4];
+    return SYMMICP_OK;
+}
+
 int symmicp_ctx_scan_probe(symmicp_ctx *c, uint32_t *data, size_t n)
 {
     if (!c) return SYMMICP_ERR_ARG;

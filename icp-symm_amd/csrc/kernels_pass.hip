@@ -231,14 +231,19 @@ __device__ __forceinline__ bool reads_src_normals(bool writeback, float min_ndot
 // The pair step of every accumulating kernel: the gates (max_correspondence_distance, then min_normal_dot), then the record.  (nx, ny, nz)
 // is the source normal as stored (zeros where the instantiation does not read it); it is moved here, for the gate and the rows (PLANE's
 // rows do not read it: there the compiler keeps it to the gate).
-template <int OBJ, int NA>
+// T = true: the trimming instantiations (symmicp_set_trim_fraction below 1): a pair that passed the gates -- a candidate -- is kept only
+// if its d2 bits are <= tau, the order statistic kernels_select.hip left for this pass (ties at tau are kept).  A separate instantiation,
+// as W: the untrimmed kernels are the code they were.  tau has its own "off" (T = false), apart from max_d2, whose 0 means "keep all":
+// tau = 0 keeps the pairs at distance 0 only.
+template <int OBJ, bool T = false, int NA>
 __device__ __forceinline__ void pair_step(AccN<NA> &acc, const HotParams &h, float nx, float ny, float nz, float px, float py, float pz,
-                                          const float4 &q, const float4 &nq, float d2)
+                                          const float4 &q, const float4 &nq, float d2, uint32_t tau = 0u)
 {
     if (h.max_d2 > 0.0f && d2 > h.max_d2) return;
     const Affine &X = h.X;
     const float npx = xf_row(X.m + 0, nx, ny, nz, X.nrm_w), npy = xf_row(X.m + 4, nx, ny, nz, X.nrm_w), npz = xf_row(X.m + 8, nx, ny, nz, X.nrm_w);
     if (h.min_ndot > -1.0f && (npx * nq.x + npy * nq.y) + npz * nq.z < h.min_ndot) return;
+    if (T && __float_as_uint(d2) > tau) return;
     acc_obj<OBJ>(acc, px, py, pz, npx, npy, npz, q.x, q.y, q.z, nq.x, nq.y, nq.z, d2, h.pivot, h.p2p, h.gicp_k, h.loss, h.loss_scale);
 }
 
@@ -315,7 +320,7 @@ __device__ __forceinline__ void acc_block_reduce_store(AccN<NA> &a, double *part
 // arrays (needs n, the target offset and the array lengths to be multiples of 4 so every column stays
 // 16-byte aligned); VEC = 1 is the general form.
 // OBJ: the record (acc_obj).  The PLANE instantiations read the source normals only to write them back or to gate on them.
-template <int VEC, bool W, int OBJ>
+template <int VEC, bool W, int OBJ, bool T>
 __global__ __launch_bounds__(kPassThreads) void k_pass_identity(PassArgs a_in, CloudSoA tgt)
 {
     if (a_in.loop && a_in.loop->stop) return;
@@ -323,6 +328,7 @@ __global__ __launch_bounds__(kPassThreads) void k_pass_identity(PassArgs a_in, C
     if (a_in.loop) a.X = a_in.loop->Xapply;        // device-driven loop: the transform k_reduce_solve left behind
     AccT<W> acc; acc_zero(acc);
     const HotParams h = hot_params(a);
+    const uint32_t tau = T ? a.trim_ws[kTrimTauWord] : 0u;
     const bool need_n = reads_src_normals<OBJ>(a.writeback, a.min_ndot);
     const uint32_t stride = gridDim.x * blockDim.x * VEC;
     for (uint32_t i0 = (blockIdx.x * blockDim.x + threadIdx.x) * VEC; i0 < a.n; i0 += stride) {
@@ -381,7 +387,7 @@ __global__ __launch_bounds__(kPassThreads) void k_pass_identity(PassArgs a_in, C
         }
 #pragma unroll
         for (int k = 0; k < VEC; k++)
-            pair_step<OBJ>(acc, h, nx[k], ny[k], nz[k], px[k], py[k], pz[k], make_float4(qx[k], qy[k], qz[k], 0.0f), make_float4(qnx[k], qny[k], qnz[k], 0.0f), d2[k]);
+            pair_step<OBJ, T>(acc, h, nx[k], ny[k], nz[k], px[k], py[k], pz[k], make_float4(qx[k], qy[k], qz[k], 0.0f), make_float4(qnx[k], qny[k], qnz[k], 0.0f), d2[k], tau);
     }
     acc_block_reduce_store(acc, a.partials, blockIdx.x);
 }
@@ -390,11 +396,12 @@ __global__ __launch_bounds__(kPassThreads) void k_pass_identity(PassArgs a_in, C
 // pass, pairs given by a previous search kernel (brute force): best64[i] holds
 // (d2 bits << 32 | target row).  Target rows are gathered as float4.
 // ---------------------------------------------------------------------------
-template <bool W, int OBJ>
+template <bool W, int OBJ, bool T>
 __global__ __launch_bounds__(kPassThreads) void k_pass_indexed(PassArgs a, const float4 *__restrict__ tn)
 {
     AccT<W> acc; acc_zero(acc);
     const HotParams h = hot_params(a);
+    const uint32_t tau = T ? a.trim_ws[kTrimTauWord] : 0u;
     const bool need_n = reads_src_normals<OBJ>(a.writeback, a.min_ndot);
     const uint32_t stride = gridDim.x * blockDim.x;
     for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < a.n; i += stride) {
@@ -415,7 +422,7 @@ __global__ __launch_bounds__(kPassThreads) void k_pass_indexed(PassArgs a, const
         if (a.d2_out) a.d2_out[i] = ok ? d2 : __int_as_float(0x7f800000);
         if (!ok) continue;
         if (a.max_d2 > 0.0f && d2 > a.max_d2) continue;                  // (pair_step's gate, ahead of the gather it saves)
-        pair_step<OBJ>(acc, h, nx, ny, nz, px, py, pz, tn[2 * (size_t)j], tn[2 * (size_t)j + 1], d2);      // one 32-byte pair record
+        pair_step<OBJ, T>(acc, h, nx, ny, nz, px, py, pz, tn[2 * (size_t)j], tn[2 * (size_t)j + 1], d2, tau);      // one 32-byte pair record
     }
     acc_block_reduce_store(acc, a.partials, blockIdx.x);
 }
@@ -1436,11 +1443,12 @@ __global__ __launch_bounds__(kWalkThreads, 6) void k_search_walk(PassArgs a, Tar
 // The pair's distance is recomputed from the gathered q (bit-identical to the stored one) instead of being read.
 // (A 4-points-per-thread variant with 16-byte column loads was measured and is no faster: the two 16-byte gathers per
 // pair bound this kernel, not the column loads.  Few blocks are: each one ends in a 40-value block reduction.)
-template <bool W, int OBJ>
+template <bool W, int OBJ, bool T>
 __global__ __launch_bounds__(kPassThreads) void k_accumulate(PassArgs a, const float4 *__restrict__ tn)
 {
     AccT<W> acc; acc_zero(acc);
     const HotParams h = hot_params(a);
+    const uint32_t tau = T ? a.trim_ws[kTrimTauWord] : 0u;
     const bool need_n = reads_src_normals<OBJ>(a.writeback, a.min_ndot);
     const uint32_t nbp = gridDim.x;
     // grid-stride over blocks of 256 points, XCD-contiguous
@@ -1466,7 +1474,7 @@ __global__ __launch_bounds__(kPassThreads) void k_accumulate(PassArgs a, const f
             a.out.nz[i] = xf_row(a.X.m + 8, nx, ny, nz, a.X.nrm_w);
         }
         if (nq.w != 0.0f) continue;                       // no target for this point
-        pair_step<OBJ>(acc, h, nx, ny, nz, px, py, pz, q, nq, dist2(px, py, pz, q.x, q.y, q.z));
+        pair_step<OBJ, T>(acc, h, nx, ny, nz, px, py, pz, q, nq, dist2(px, py, pz, q.x, q.y, q.z), tau);
     }
     acc_block_reduce_store(acc, a.partials, blockIdx.x);
 }
@@ -1901,22 +1909,37 @@ static void with_instantiation(const PassArgs &a, F &&f)
     else obj(std::false_type());
 }
 
-void launch_pass_identity(const PassArgs &a, CloudSoA tgt, int blocks, bool vec4_ok, hipStream_t s)
+// ... and T: a trimmed pass (PassArgs::trim_keys set): the keys and the select (kernels_select.hip) run in front of its accumulating
+// kernel, whose trimming instantiation reads the tau they leave.  The kernels of the device-driven loop have no such instantiation
+// (batch_eligible keeps a trimming context in the host loop).
+template <typename F>
+static void with_trim(const PassArgs &a, F &&f)
 {
     with_instantiation(a, [&](auto W, auto OBJ) {
-        if (vec4_ok) hipLaunchKernelGGL((k_pass_identity<4, W, OBJ>), dim3(blocks), dim3(kPassThreads), 0, s, a, tgt);
-        else hipLaunchKernelGGL((k_pass_identity<1, W, OBJ>), dim3(blocks), dim3(kPassThreads), 0, s, a, tgt);
+        if (a.trim_keys) f(W, OBJ, std::true_type());
+        else f(W, OBJ, std::false_type());
+    });
+}
+
+void launch_pass_identity(const PassArgs &a, CloudSoA tgt, int blocks, bool vec4_ok, hipStream_t s)
+{
+    if (a.trim_keys) launch_trim_select(a, SYMMICP_CORR_IDENTITY, tgt, nullptr, s);
+    with_trim(a, [&](auto W, auto OBJ, auto T) {
+        if (vec4_ok) hipLaunchKernelGGL((k_pass_identity<4, W, OBJ, T>), dim3(blocks), dim3(kPassThreads), 0, s, a, tgt);
+        else hipLaunchKernelGGL((k_pass_identity<1, W, OBJ, T>), dim3(blocks), dim3(kPassThreads), 0, s, a, tgt);
     });
 }
 
 void launch_pass_indexed(const PassArgs &a, const float4 *tn, int blocks, hipStream_t s)
 {
-    with_instantiation(a, [&](auto W, auto OBJ) { hipLaunchKernelGGL((k_pass_indexed<W, OBJ>), dim3(blocks), dim3(kPassThreads), 0, s, a, tn); });
+    if (a.trim_keys) launch_trim_select(a, SYMMICP_CORR_BRUTE, CloudSoA{}, tn, s);
+    with_trim(a, [&](auto W, auto OBJ, auto T) { hipLaunchKernelGGL((k_pass_indexed<W, OBJ, T>), dim3(blocks), dim3(kPassThreads), 0, s, a, tn); });
 }
 
 void launch_accumulate(const PassArgs &a, const float4 *tn, int blocks, hipStream_t s)
 {
-    with_instantiation(a, [&](auto W, auto OBJ) { hipLaunchKernelGGL((k_accumulate<W, OBJ>), dim3(blocks), dim3(kPassThreads), 0, s, a, tn); });
+    if (a.trim_keys) launch_trim_select(a, SYMMICP_CORR_TREE, CloudSoA{}, tn, s);
+    with_trim(a, [&](auto W, auto OBJ, auto T) { hipLaunchKernelGGL((k_accumulate<W, OBJ, T>), dim3(blocks), dim3(kPassThreads), 0, s, a, tn); });
 }
 
 uint32_t shard_capacity(uint32_t n_points)

@@ -173,7 +173,16 @@ struct PassArgs {
     float loss_scale;                   // ... its scale (robust_loss.h)
     int32_t obj;                        // the record (kObjSym / kObjPlane / kObjGicp, mode_obj): the launchers pick the instantiations; read by the host only
     float gicp_k;                       // ... 1 - eps of its covariances (symmicp_set_gicp_epsilon), fp32: read by the GICP instantiations only
+    // trimmed ICP (symmicp_set_trim_fraction below 1; kernels_select.hip).  trim_keys != null selects the trimming instantiation (T) of the
+    // pass's accumulating kernel, which keeps a pair only if its d2 bits are <= the tau the select left in trim_ws[kTrimTauWord]; the
+    // launchers run the keys and the select in front of it.  Null (the default): nothing is launched and the kernels are the untrimmed ones.
+    uint32_t *trim_keys;                // [n] per share row: the candidate's d2 bits, 0xFFFFFFFF otherwise
+    uint32_t *trim_ws;                  // [kTrimWsWords] the select's state and histograms
+    uint32_t *trim_host;                // host-mapped (n_c, kept, tau bits) of the pass
+    float trim_rho;
 };
+constexpr uint32_t kTrimWsWords = 16 + 3 * 2048;
+constexpr uint32_t kTrimTauWord = 3;
 
 // host-side launch tuning of the tree passes (environment switches, read once by the engine)
 struct PassTuning {
@@ -246,7 +255,13 @@ void launch_iota_f4(const float *x, const float *y, const float *z, const float 
 void launch_unpermute(const CloudSoA &cur, const uint32_t *order, uint32_t n, float *xyz_aos, float *nrm_aos, hipStream_t s);
 void launch_corr_out(const int32_t *pos, const unsigned long long *best64, const float *d2, const float4 *tq,
                      const uint32_t *src_order, uint32_t n, int mode, uint32_t tgt_offset, int32_t *idx_out, float *d2_out,
-                     hipStream_t s);
+                     const uint32_t *trim_keys /* null, or: rows whose key is above trim_tau report -1 */, uint32_t trim_tau, hipStream_t s);
+
+// trimmed ICP (kernels_select.hip): the keys of the pass's candidates and the exact radix select of the k-th smallest, k = ceil(rho n_c) --
+// one memset and six launches; called by the pass launchers when a.trim_keys is set.  corr: symmicp_corr (which of tgt / tn is read)
+void launch_trim_select(const PassArgs &a, int corr, CloudSoA tgt, const float4 *tn, hipStream_t s);
+// test entry: the select alone on n keys, rank k (1-based); afterwards ws[kTrimTauWord] = the k-th smallest key, ws[4] = keys <= it
+void launch_select_probe(const uint32_t *keys, uint32_t n, uint32_t k, uint32_t *ws, hipStream_t s);
 
 void launch_identity_d2(const CloudSoA &in, const Affine &X, const CloudSoA &tgt, uint32_t tgt_offset, uint32_t n, float *d2, hipStream_t s);
 void launch_pairs_d2(const CloudSoA &in, const Affine &X, const int32_t *pos, const float4 *tq, uint32_t n_t, uint32_t n, float *d2, hipStream_t s);

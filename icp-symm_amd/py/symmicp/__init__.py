@@ -117,6 +117,7 @@ EXPORTS = [
     "symmicp_feature_nn", "symmicp_ctx_feature_nn", "symmicp_feature_correspondences", "symmicp_ctx_feature_correspondences",
     "symmicp_ransac_config_default", "symmicp_ransac", "symmicp_ctx_ransac", "symmicp_ctx_ransac_hypotheses",
     "symmicp_ctx_index_info", "symmicp_ctx_index_arrays", "symmicp_ctx_source_share", "symmicp_ctx_radix_sort_probe", "symmicp_ctx_scan_probe",
+    "symmicp_set_trim_fraction", "symmicp_get_trim_fraction", "symmicp_get_trim_state", "symmicp_ctx_select_probe",
 ]
 
 _lib = None
@@ -223,6 +224,11 @@ def lib():
     L.symmicp_ctx_source_share.argtypes = [vp, szp, szp, i32p, i32p, u32p, u32p]
     L.symmicp_ctx_radix_sort_probe.argtypes = [vp, u32p, u32p, C.c_size_t, C.c_int]
     L.symmicp_ctx_scan_probe.argtypes = [vp, u32p, C.c_size_t]
+    u64p = C.POINTER(C.c_uint64)
+    L.symmicp_set_trim_fraction.argtypes = [vp, C.c_float]
+    L.symmicp_get_trim_fraction.argtypes = [vp, fp]
+    L.symmicp_get_trim_state.argtypes = [vp, u64p, u64p, fp]
+    L.symmicp_ctx_select_probe.argtypes = [vp, u32p, C.c_size_t, C.c_uint64, u32p, u64p]
     _lib = L
     return L
 
@@ -642,6 +648,22 @@ class Engine:
         self._chk(self._L.symmicp_get_gicp_epsilon(self._h, C.byref(ep)))
         return ep.value
 
+    def set_trim_fraction(self, fraction):
+        """trimmed ICP: every pass keeps the closest `fraction` of its candidate pairs (0 < fraction <= 1; 1 = off, the default);
+        takes effect at the next pass"""
+        self._chk(self._L.symmicp_set_trim_fraction(self._h, float(fraction)))
+
+    def trim_fraction(self):
+        fr = C.c_float(0)
+        self._chk(self._L.symmicp_get_trim_fraction(self._h, C.byref(fr)))
+        return fr.value
+
+    def trim_state(self):
+        """-> (candidates, kept, tau_d2 as np.float32) of the most recent pass; ERR_STATE if it was not trimmed"""
+        nc, kept, tau = C.c_uint64(0), C.c_uint64(0), C.c_float(0)
+        self._chk(self._L.symmicp_get_trim_state(self._h, C.byref(nc), C.byref(kept), C.byref(tau)))
+        return nc.value, kept.value, np.float32(tau.value)
+
     def set_source(self, xyz, nrm):
         """nrm may be None in MODE_PLANE (the library holds zero source normals then)"""
         xyz = _cloud(xyz)
@@ -948,6 +970,14 @@ class Engine:
         self._chk(self._L.symmicp_ctx_radix_sort_probe(self._h, u32(k), u32(v), k.size, int(key_bits)))
         return k, v
 
+    def select_probe(self, keys, k):
+        """the trimmed pass's radix select on a host array (symmicp_ctx_select_probe) -> (the k-th smallest key, 1 <= k <= n; the
+        number of keys <= it)"""
+        a = np.ascontiguousarray(np.asarray(keys, np.uint32).reshape(-1))
+        kth, nle = C.c_uint32(0), C.c_uint64(0)
+        self._chk(self._L.symmicp_ctx_select_probe(self._h, a.ctypes.data_as(C.POINTER(C.c_uint32)), a.size, int(k), C.byref(kth), C.byref(nle)))
+        return kth.value, nle.value
+
     def scan_probe(self, data):
         """the build's exclusive scan on a host array (symmicp_ctx_scan_probe) -> new uint32 array"""
         d = np.array(data, np.uint32).reshape(-1)
@@ -989,6 +1019,7 @@ class MyICP:
         self.last_result = None
         self._loss = (LOSS_NONE, 0.0)
         self._gicp_eps = None
+        self._trim = 1.0
         self._levels = []
         self.level_results = []
         self._global = None
@@ -1056,6 +1087,10 @@ class MyICP:
         """the covariance eps of the next align in MODE_GICP (see Engine.set_gicp_epsilon)"""
         self._gicp_eps = float(eps)
 
+    def setTrimFraction(self, fraction):
+        """trimmed ICP for the next align, every voxel level included (see Engine.set_trim_fraction; 1 = off)"""
+        self._trim = float(fraction)
+
     def setRobustLoss(self, loss, scale):
         """robust loss of the next align (see Engine.set_robust_loss)"""
         self._loss = (loss_code(loss), float(scale))
@@ -1110,6 +1145,8 @@ class MyICP:
                 e.set_robust_loss(*self._loss)
             if self._gicp_eps is not None:
                 e.set_gicp_epsilon(self._gicp_eps)
+            if self._trim != 1.0:
+                e.set_trim_fraction(self._trim)
             e.set_target(self.cloud_tgt, self.normals_tgt)
             e.set_source(self.cloud_src, self.normals_src)
             self.last_result = e.align(guess)
@@ -1125,6 +1162,8 @@ class MyICP:
                 e.set_robust_loss(*self._loss)
             if self._gicp_eps is not None:
                 e.set_gicp_epsilon(self._gicp_eps)
+            if self._trim != 1.0:
+                e.set_trim_fraction(self._trim)
             X = guess
             if self._global is not None and guess is None:
                 X = self._global_init(e)

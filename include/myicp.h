@@ -55,6 +55,10 @@ public:
 	// the covariance eps of SYMMICP_MODE_GICP (symmicp_set_gicp_epsilon; default 1e-3): checked by align(), which returns
 	// SYMMICP_ERR_ARG unless 0 < eps <= 1 and 1 - eps != 1 in fp32 (eps > 2^-25)
 	void setGicpEpsilon(float eps) { gicp_eps_ = eps; }
+	// trimmed ICP (symmicp_set_trim_fraction; default 1 = off): every pass keeps the closest `fraction` of its pairs -- for clouds that
+	// overlap only in part.  Applies to single-level runs and to every level of setVoxelLevels; checked by align(), which returns
+	// SYMMICP_ERR_ARG unless 0 < fraction <= 1, and for a fraction below 1 with SYMMICP_MODE_QUIRKS
+	void setTrimFraction(float fraction) { trim_fraction_ = fraction; }
 	// pairs farther apart than d are dropped (symmicp_config.max_corr_dist; <= 0, the default: every pair is kept)
 	void setMaxCorrespondenceDistance(float d) { max_corr_dist_ = d; }
 	// Coarse-to-fine alignment.  With levels set, align() estimates (or takes) the normals of the full clouds as before, then runs
@@ -115,6 +119,7 @@ private:
 	symmicp_loss loss_;
 	float loss_scale_;
 	float gicp_eps_;
+	float trim_fraction_;
 	float max_corr_dist_;
 	std::vector<VoxelLevel> levels_;
 	std::vector<symmicp_result> level_results_;

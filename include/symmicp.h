@@ -187,6 +187,33 @@ int symmicp_get_robust_loss(const symmicp_ctx *ctx, int *loss, float *scale);
  * sets the same value. */
 int symmicp_set_gicp_epsilon(symmicp_ctx *ctx, float eps);
 int symmicp_get_gicp_epsilon(const symmicp_ctx *ctx, float *eps);
+/* Trimmed ICP (Chetverikov, Stepanov, Krsek 2002/2005; PCL's CorrespondenceRejectorTrimmed, libpointmatcher's
+ * TrimmedDistOutlierFilter): each pass keeps the closest fraction rho of its pairs -- the rejection rule for clouds that overlap only
+ * in part.  A pure function of the pass:
+ *   Candidates  the pairs of the pass that exist (a target row >= 0) and pass the gates (max_corr_dist, then min_normal_dot), exactly
+ *               as every accumulating kernel applies them; n_c = their number.
+ *   Distance    d2 = the pair's fp32 squared distance (dx*dx + dy*dy) + dz*dz at the moved position: the same bits the accumulating
+ *               kernels evaluate.
+ *   Threshold   k = ceil((double)rho * (double)n_c) with rho the fp32 fraction, clamped to [1, n_c]; tau = the k-th smallest
+ *               candidate d2.
+ *   Kept set    the candidates with d2 <= tau.  Ties at tau are all kept, so the kept count is >= k.  n_c == 0: nothing is kept
+ *               (tau is reported as 0) and the solve reports SYMMICP_ERR_DEGENERATE as it does for any empty record.
+ *   Off         rho == 1, the default: nothing new is launched, every result is bit for bit that of a build without trimming.
+ *   Record      the ordinary one over the kept set: slots 33, 34, 36 and 37 count kept pairs only, exactly as a pair dropped by
+ *               max_corr_dist is left out; a robust loss weights the kept pairs.
+ * All symmicp_corr values; modes PAPER, P2P, PLANE and GICP.  QUIRKS stays the reference as written: a fraction below 1 is
+ * SYMMICP_ERR_ARG there, and symmicp_set_config refuses to switch a trimming context into QUIRKS the same way.
+ * SYMMICP_ERR_ARG unless 0 < fraction <= 1 (NaN is refused too); the fraction set before stays.  Takes effect at the next pass: it may
+ * be called between symmicp_step calls.  tau is an exact order statistic found on the device every pass (a radix select over the d2
+ * bits); the fused pass and the device-driven loop are not extended: with a fraction below 1 symmicp_align runs every iteration in
+ * the host loop (as cfg.host_loop does).  symmicp_get_correspondences then reports a pair that was trimmed away -- or gated: not a
+ * candidate -- as rejected (-1).  Sharded contexts would need a quantile over all ranks and are out of scope: a fraction below 1 on a
+ * context with nranks > 1, and symmicp_comm_init_rank / _shm with nranks > 1 on a trimming context, return SYMMICP_ERR_STATE. */
+int symmicp_set_trim_fraction(symmicp_ctx *ctx, float fraction);
+int symmicp_get_trim_fraction(const symmicp_ctx *ctx, float *fraction);
+/* n_c, the kept count and tau of the most recent pass (each pointer may be NULL); SYMMICP_ERR_STATE if no pass has run or that pass
+ * was not trimmed */
+int symmicp_get_trim_state(const symmicp_ctx *ctx, uint64_t *candidates, uint64_t *kept, float *tau_d2);
 /* the weight the kernels give a pair of residual r (the same fp32 source); NaN for an unknown loss, or for a scale that
  * is not finite and > 0 with loss != NONE; 1 for SYMMICP_LOSS_NONE */
 float symmicp_robust_weight(int loss, float scale, float r);
@@ -321,6 +348,9 @@ int symmicp_ctx_source_share(symmicp_ctx *ctx, size_t *n_local, size_t *pkt_coun
  * launches nothing; n < 2^31. */
 int symmicp_ctx_radix_sort_probe(symmicp_ctx *ctx, uint32_t *keys, uint32_t *vals, size_t n, int key_bits);
 int symmicp_ctx_scan_probe(symmicp_ctx *ctx, uint32_t *data, size_t n);
+/* the trimmed pass's exact radix select on a host array: *kth_out = the k-th smallest key (1 <= k <= n, n < 2^31), *n_le_out = the
+ * number of keys <= it.  Same stream and scratch arena; the context's trim fraction and trim state stay as they were. */
+int symmicp_ctx_select_probe(symmicp_ctx *ctx, const uint32_t *keys, size_t n, uint64_t k, uint32_t *kth_out, uint64_t *n_le_out);
 
 /* ---- normals pre-step (replaces MyICP::estimateNormals, myicp.cpp:152-172: PCL NormalEstimation,
  * setKSearch(10), viewpoint (0,0,0)).  Exact k-NN (the point itself included) + PCA on the GPU.
