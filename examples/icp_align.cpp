@@ -1,9 +1,11 @@
 // examples/icp_align.cpp -- command-line registration of two PCD files on one MI355X through the MyICP class.
 //
 //   icp_align [options] [source.pcd target.pcd]
-//     --mode quirks|paper|plane|gicp  arithmetic: the reference as written (default), the paper-correct symmetric form,
-//                              point-to-plane (target normals only: the source's are not estimated), or plane-to-plane
-//                              (Generalized-ICP, covariances from the normals of both clouds)
+//     --mode quirks|paper|plane|gicp|color  arithmetic: the reference as written (default), the paper-correct symmetric form,
+//                              point-to-plane (target normals only: the source's are not estimated), plane-to-plane
+//                              (Generalized-ICP, covariances from the normals of both clouds), or colored ICP (point-to-plane rows
+//                              plus intensity rows: both files need an `intensity` or `rgb` field; no --scale levels)
+//     --color-weight L         colored ICP: the weight of the geometric rows, 0 <= L <= 1 (default 0.968; --mode color only)
 //     --gicp-epsilon E         the covariances' eps, 2^-25 < E <= 1: 1 - E must differ from 1 in fp32 (default 1e-3; --mode gicp only)
 //     --corr identity|tree     pairing: by row (default, what the reference does) or exact nearest neighbours
 //     --iters N                iteration cap            (default 10, ICP/myicp.cpp:6)
@@ -41,7 +43,7 @@
 
 static int usage(const char *argv0, const char *complaint)
 {
-    std::fprintf(stderr, "%s\nusage: %s [--mode quirks|paper|plane|gicp] [--corr identity|tree] [--iters N] [--threshold D] [--loss none|huber|tukey|cauchy|gm]"
+    std::fprintf(stderr, "%s\nusage: %s [--mode quirks|paper|plane|gicp|color] [--color-weight L] [--corr identity|tree] [--iters N] [--threshold D] [--loss none|huber|tukey|cauchy|gm]"
                  " [--loss-scale S] [--gicp-epsilon E] [--max-dist D] [--trim F] [--scale LEAF:ITERS[:MAXDIST]]... [--init global --fpfh-radius R --ransac-dist D [--ransac-iters H] [--seed S] [--init-voxel L]] [--out file.pcd] [--quiet] [source.pcd target.pcd]\n",
                  complaint, argv0);
     return 64;
@@ -59,6 +61,8 @@ int main(int argc, char **argv)
     bool gicp = false, have_eps = false;
     float gicp_eps = 0.f;
     bool tree = false;
+    bool color = false, have_color_weight = false;
+    float color_weight = 0.f;
     float trim = 1.f;
     std::vector<MyICP::VoxelLevel> levels;
     bool init_global = false, have_init_option = false;
@@ -76,10 +80,12 @@ int main(int argc, char **argv)
         };
         if (a == "--mode") {
             const std::string v = value("--mode");
+            color = false;
             if (v == "quirks") { icp.setMode(SYMMICP_MODE_QUIRKS); quirks = true; gicp = false; }
             else if (v == "paper") { icp.setMode(SYMMICP_MODE_PAPER); quirks = false; gicp = false; }
             else if (v == "plane") { icp.setMode(SYMMICP_MODE_PLANE); quirks = false; gicp = false; }
             else if (v == "gicp") { icp.setMode(SYMMICP_MODE_GICP); quirks = false; gicp = true; }
+            else if (v == "color") { icp.setMode(SYMMICP_MODE_COLOR); quirks = false; gicp = false; color = true; }
             else return usage(argv[0], "unknown --mode");
         } else if (a == "--corr") {
             const std::string v = value("--corr");
@@ -109,6 +115,13 @@ int main(int argc, char **argv)
             if (end == v || *end || !std::isfinite(gicp_eps) || !(gicp_eps > 0.f) || gicp_eps > 1.f || 1.0f - gicp_eps == 1.0f)
                 return usage(argv[0], "--gicp-epsilon needs a number E with 2^-25 < E <= 1 (1 - E must differ from 1 in fp32)");
             have_eps = true;
+        }
+        else if (a == "--color-weight") {
+            char *end = nullptr;
+            const char *v = value("--color-weight");
+            color_weight = std::strtof(v, &end);
+            if (end == v || *end || !(color_weight >= 0.f) || color_weight > 1.f) return usage(argv[0], "--color-weight needs a number L with 0 <= L <= 1");
+            have_color_weight = true;
         }
         else if (a == "--max-dist") {
             char *end = nullptr;
@@ -173,6 +186,11 @@ int main(int argc, char **argv)
         if (quirks) return usage(argv[0], "--trim below 1 needs --mode paper, plane or gicp (quirks is the reference as written)");
         icp.setTrimFraction(trim);
     }
+    if (have_color_weight) {
+        if (!color) return usage(argv[0], "--color-weight needs --mode color");
+        icp.setColorWeight(color_weight);
+    }
+    if (color && !levels.empty()) return usage(argv[0], "--mode color does not run --scale levels (intensities are not averaged per voxel yet)");
     if (!levels.empty()) {
         if (!tree) return usage(argv[0], "--scale needs --corr tree (identity pairing cannot pair clouds of different sizes)");
         icp.setVoxelLevels(levels);
@@ -192,6 +210,10 @@ int main(int argc, char **argv)
     if (icp.GetSrcCloud()->points.empty() || icp.GetTgtCloud()->points.empty()) {
         std::fprintf(stderr, "%s\n", icp.lastError()[0] ? icp.lastError() : "empty cloud");
         return SYMMICP_ERR_IO;
+    }
+    if (color && !icp.haveIntensities()) {
+        std::fprintf(stderr, "--mode color needs colours in both files: an `intensity` or an `rgb` field per point\n");
+        return SYMMICP_ERR_STATE;
     }
     icp.RegisterSymm();
     const symmicp_result &r = icp.lastResult();

@@ -168,6 +168,7 @@ extern "C++" void free_target(symmicp_ctx *c)
     hipFree(c->dbg); hipFree(c->dbg_trace); c->dbg_trace = nullptr;
     c->ctop = nullptr; c->dbg = nullptr; c->ix = TargetIndex{}; c->tgt_block = nullptr; c->tq = nullptr; c->tn = nullptr; c->boxes = nullptr; c->cells = nullptr; c->onodes = nullptr;
     c->have_index = false; c->n_t = 0;
+    c->have_tgt_color = false;
     c->notes = IndexNotes{};
 }
 
@@ -178,6 +179,7 @@ extern "C++" void forget_source(symmicp_ctx *c)
     c->src0_block = c->cur_block = nullptr; c->src_order = nullptr; c->pos = nullptr; c->d2 = nullptr; c->best64 = nullptr;
     c->n_loc = c->n_s_total = c->src_off = 0;
     c->src_no_normals = false;
+    c->have_src_int = false;
 }
 
 static void free_source(symmicp_ctx *c)
@@ -200,6 +202,7 @@ void symmicp_destroy(symmicp_ctx *c)
     free_source(c);
     hipFree(c->partials); hipFree(c->d_sums); hipFree(c->ticket); hipFree(c->arena.base); hipFree(c->keep.base);
     hipFree(c->trim_keys); hipFree(c->trim_ws);
+    hipFree(c->tgt_color); hipFree(c->src_int);
     if (c->h_sums) hipHostFree(c->h_sums);
     hipFree(c->d_loop);
     if (c->h_loop) hipHostFree(c->h_loop);
@@ -223,6 +226,8 @@ int symmicp_set_config(symmicp_ctx *c, const symmicp_config *cfg)
         return fail(c, SYMMICP_ERR_ARG, "QUIRKS takes no robust loss (set SYMMICP_LOSS_NONE first)");
     if (cfg->mode == SYMMICP_MODE_QUIRKS && c->trim_frac < 1.0f)
         return fail(c, SYMMICP_ERR_ARG, "QUIRKS takes no trim fraction below 1 (set 1 first)");
+    if (cfg->mode == SYMMICP_MODE_COLOR && c->nranks > 1)
+        return fail(c, SYMMICP_ERR_STATE, "SYMMICP_MODE_COLOR runs on single-rank contexts only");
     if (c->src_no_normals && cfg->mode != SYMMICP_MODE_PLANE)
         return fail(c, SYMMICP_ERR_STATE, "the source was set without normals: only SYMMICP_MODE_PLANE can run on it");
     if (c->src_no_normals && cfg->min_normal_dot > -1.0f)
@@ -307,6 +312,115 @@ int symmicp_get_gicp_epsilon(const symmicp_ctx *c, float *eps)
 {
     if (!c || !eps) return SYMMICP_ERR_ARG;
     *eps = c->gicp_eps;
+    return SYMMICP_OK;
+}
+
+// ---- colored ICP: lambda and the per-point attributes ---------------------------------------------
+int symmicp_set_color_weight(symmicp_ctx *c, float lambda)
+{
+    if (!c) return SYMMICP_ERR_ARG;
+    if (!(std::isfinite(lambda) && lambda >= 0.f && lambda <= 1.f)) return fail(c, SYMMICP_ERR_ARG, "color weight: 0 <= lambda <= 1 and finite");
+    c->color_lam = lambda;
+    return SYMMICP_OK;
+}
+
+int symmicp_get_color_weight(const symmicp_ctx *c, float *lambda)
+{
+    if (!c || !lambda) return SYMMICP_ERR_ARG;
+    *lambda = c->color_lam;
+    return SYMMICP_OK;
+}
+
+// the caller's strided values, staged contiguously and checked (false: a non-finite value)
+static bool stage_finite(const float *base, size_t rs, size_t cs, size_t n, int cols, std::vector<float> &out)
+{
+    out.resize(n * (size_t)cols);
+    bool ok = true;
+    for (size_t i = 0; i < n; i++)
+        for (int k = 0; k < cols; k++) {
+            const float v = base[i * rs + (size_t)k * cs];
+            ok = ok && std::isfinite(v);
+            out[i * (size_t)cols + k] = v;
+        }
+    return ok;
+}
+
+int symmicp_set_source_intensity(symmicp_ctx *c, const float *intensity, size_t stride, size_t n)
+{
+    if (!c) return SYMMICP_ERR_ARG;
+    if (!intensity) return fail(c, SYMMICP_ERR_ARG, "null source intensity");
+    if (!c->src0_block) return fail(c, SYMMICP_ERR_STATE, "symmicp_set_source_intensity follows symmicp_set_source");
+    if (n != c->n_s_total) return fail(c, SYMMICP_ERR_SIZE, "source intensity: n differs from the source's count");
+    std::vector<float> host;
+    if (!stage_finite(intensity, stride, 0, n, 1, host)) return fail(c, SYMMICP_ERR_ARG, "source intensity: non-finite value");
+    HIP_TRY(c, hipSetDevice(c->device));
+    c->have_src_int = false;
+    c->begun = false;
+    const size_t want = c->n_loc ? c->n_loc : 1;
+    if (c->src_int_cap < want) {
+        hipFree(c->src_int);
+        c->src_int = nullptr; c->src_int_cap = 0;
+        HIP_TRY(c, hipMalloc((void **)&c->src_int, sizeof(float) * want));
+        c->src_int_cap = want;
+    }
+    arena_begin(c->arena, n * 4 + 4096);
+    DevBuf<float> raw;
+    HIP_TRY(c, raw.alloc_temp(c->arena, n));
+    HIP_TRY(c, hipMemcpyAsync(raw.p, host.data(), sizeof(float) * n, hipMemcpyHostToDevice, c->stream));
+    launch_color_permute_source(raw.p, c->src_order, c->src_off, c->n_loc, c->src_int, c->stream);
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    HIP_TRY(c, hipGetLastError());
+    c->have_src_int = true;
+    return SYMMICP_OK;
+}
+
+int symmicp_set_target_intensity(symmicp_ctx *c, const float *intensity, size_t stride, const float *grad, size_t grs, size_t gcs, size_t n)
+{
+    if (!c) return SYMMICP_ERR_ARG;
+    if (!intensity || !grad) return fail(c, SYMMICP_ERR_ARG, "null target intensity or gradient (symmicp_ctx_intensity_gradient estimates one)");
+    if (!c->tgt_block) return fail(c, SYMMICP_ERR_STATE, "symmicp_set_target_intensity follows symmicp_set_target");
+    if (n != c->n_t) return fail(c, SYMMICP_ERR_SIZE, "target intensity: n differs from the target's count");
+    if (c->cfg.corr != SYMMICP_CORR_IDENTITY && !c->tq) return fail(c, SYMMICP_ERR_STATE, "target was set under a different corr mode");
+    std::vector<float> hi, hg;
+    if (!stage_finite(intensity, stride, 0, n, 1, hi) || !stage_finite(grad, grs, gcs, n, 3, hg))
+        return fail(c, SYMMICP_ERR_ARG, "target intensity or gradient: non-finite value");
+    HIP_TRY(c, hipSetDevice(c->device));
+    c->have_tgt_color = false;
+    c->begun = false;
+    if (c->tgt_color_cap < n) {
+        hipFree(c->tgt_color);
+        c->tgt_color = nullptr; c->tgt_color_cap = 0;
+        HIP_TRY(c, hipMalloc((void **)&c->tgt_color, sizeof(float4) * n));
+        c->tgt_color_cap = n;
+    }
+    arena_begin(c->arena, n * 16 + 8192);
+    DevBuf<float> di, dg;
+    HIP_TRY(c, di.alloc_temp(c->arena, n));
+    HIP_TRY(c, dg.alloc_temp(c->arena, 3 * n));
+    HIP_TRY(c, hipMemcpyAsync(di.p, hi.data(), sizeof(float) * n, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(dg.p, hg.data(), sizeof(float) * 3 * n, hipMemcpyHostToDevice, c->stream));
+    // (identity pairing reads the planar target in the caller's order; BRUTE's tq is in that order too and says so in its w words)
+    launch_color_permute_target(di.p, dg.p, c->cfg.corr == SYMMICP_CORR_IDENTITY ? nullptr : c->tq, (uint32_t)n, c->tgt_color, c->stream);
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    HIP_TRY(c, hipGetLastError());
+    c->have_tgt_color = true;
+    return SYMMICP_OK;
+}
+
+int symmicp_get_source_intensity(symmicp_ctx *c, float *intensity, size_t cap)
+{
+    if (!c || !intensity) return SYMMICP_ERR_ARG;
+    if (!c->src0_block || !c->have_src_int) return fail(c, SYMMICP_ERR_STATE, "no source intensity is set");
+    const size_t need = c->src_order ? c->n_s_total : c->n_loc;
+    if (cap < need) return fail(c, SYMMICP_ERR_SIZE, "output too small");
+    HIP_TRY(c, hipSetDevice(c->device));
+    arena_begin(c->arena, need * 4 + 4096);
+    DevBuf<float> out;
+    HIP_TRY(c, out.alloc_temp(c->arena, need));
+    HIP_TRY(c, hipMemsetAsync(out.p, 0, sizeof(float) * need, c->stream));
+    launch_color_unpermute_source(c->src_int, c->src_order, c->n_loc, out.p, c->stream);
+    HIP_TRY(c, hipMemcpyAsync(intensity, out.p, sizeof(float) * need, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
     return SYMMICP_OK;
 }
 
@@ -1205,6 +1319,68 @@ int symmicp_fpfh(int device, const float *xyz, size_t xyz_row_stride, size_t xyz
     return st;
 }
 
+// ---- intensity gradient of colored ICP (kernels_color.hip; DESIGN.md 4, "Colored ICP") ------------------------------------
+// Like the FPFH entry: the cloud's own scratch index, the exact k-NN walk of the normals pre-step (launch_knn: rows in (d2, row) order),
+// then the tangent-plane moments and the 3x3 solve per point.
+static const char *gradient_args_error(const float *xyz, const float *nrm, const float *intensity, size_t n, int k, const float *grad_out)
+{
+    if (!xyz || !nrm || !intensity || !grad_out) return "intensity gradient: xyz, nrm, intensity and grad_out are required";
+    if (n == 0 || n > 0x7fffffffull) return "intensity gradient: n must be in 1 .. 2^31 - 1";
+    if (k < 3 || k > 16 || (size_t)k > n) return "intensity gradient: k must be in 3 .. 16 and <= n";
+    return nullptr;
+}
+
+int symmicp_ctx_intensity_gradient(symmicp_ctx *c, const float *xyz, size_t xyz_row_stride, size_t xyz_col_stride, const float *nrm,
+                                   size_t nrm_row_stride, size_t nrm_col_stride, const float *intensity, size_t intensity_stride, size_t n,
+                                   int k, float *grad_out)
+{
+    if (!c) return SYMMICP_ERR_ARG;
+    if (const char *msg = gradient_args_error(xyz, nrm, intensity, n, k, grad_out)) return fail(c, SYMMICP_ERR_ARG, msg);
+    std::vector<float> hi(n);
+    for (size_t i = 0; i < n; i++) hi[i] = intensity[i * intensity_stride];
+    ScratchIndex si;
+    int st = scratch_index_begin(c, xyz, xyz_row_stride, xyz_col_stride, nrm, nrm_row_stride, nrm_col_stride, n,
+                                 n * (8 * (size_t)k + 4 + 16 + 12) + 8192, si);
+    if (st != SYMMICP_OK) return st;
+    auto body = [&]() -> int {
+        DevBuf<int32_t> d_rows;
+        DevBuf<float> d_d2, d_int, d_grad;
+        DevBuf<float4> d_rec;
+        HIP_TRY(c, d_rows.alloc_temp(c->arena, n * (size_t)k));
+        HIP_TRY(c, d_d2.alloc_temp(c->arena, n * (size_t)k));
+        HIP_TRY(c, d_int.alloc_temp(c->arena, n));
+        HIP_TRY(c, d_rec.alloc_temp(c->arena, n));
+        HIP_TRY(c, d_grad.alloc_temp(c->arena, 3 * n));
+        HIP_TRY(c, hipMemcpyAsync(d_int.p, hi.data(), sizeof(float) * n, hipMemcpyHostToDevice, c->stream));
+        launch_knn(si.ix, k, d_rows.p, d_d2.p, c->stream);
+        launch_color_gradient(si.ix, d_int.p, d_rows.p, k, d_rec.p, d_grad.p, c->stream);
+        HIP_TRY(c, hipMemcpyAsync(grad_out, d_grad.p, sizeof(float) * 3 * n, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        HIP_TRY(c, hipGetLastError());
+        return SYMMICP_OK;
+    };
+    st = body();
+    scratch_index_end(c, si);
+    return st;
+}
+
+int symmicp_intensity_gradient(int device, const float *xyz, size_t xyz_row_stride, size_t xyz_col_stride, const float *nrm,
+                               size_t nrm_row_stride, size_t nrm_col_stride, const float *intensity, size_t intensity_stride, size_t n,
+                               int k, float *grad_out)
+{
+    if (gradient_args_error(xyz, nrm, intensity, n, k, grad_out)) return SYMMICP_ERR_ARG;
+    symmicp_config cfg;
+    symmicp_config_default(&cfg);
+    cfg.device = device;
+    symmicp_ctx *c = nullptr;
+    int st = symmicp_create(&cfg, &c);
+    if (st != SYMMICP_OK) return st;
+    st = symmicp_ctx_intensity_gradient(c, xyz, xyz_row_stride, xyz_col_stride, nrm, nrm_row_stride, nrm_col_stride, intensity, intensity_stride,
+                                        n, k, grad_out);
+    symmicp_destroy(c);
+    return st;
+}
+
 // ---- voxel-grid downsampling (kernels_voxel.hip; DESIGN.md 4, "Voxel downsampling") ---------------------------------------
 // Box (launch_bbox) -> grid set-up here in fp32 -> keys -> stable radix sort of (key, row) -> run heads, scan, first positions ->
 // kept voxels (>= min_points), scan, compaction -> sorted SoA gather -> per-voxel sequential means.  Temporaries come from the
@@ -1366,7 +1542,8 @@ int symmicp_get_stats(symmicp_ctx *c, symmicp_stats *out)
     if (c->cfg.corr == SYMMICP_CORR_IDENTITY) b = (int64_t)c->n_loc * 48;
     else b = (int64_t)c->n_loc * (48 + 4 + 4) + (int64_t)c->n_t * 12;
     if (incr) b += (int64_t)c->n_loc * 24;
-    else if (c->cfg.mode == SYMMICP_MODE_PLANE && !(c->cfg.min_normal_dot > -1.0f)) b -= (int64_t)c->n_loc * 12;      // (no source normals read)
+    else if ((c->cfg.mode == SYMMICP_MODE_PLANE || c->cfg.mode == SYMMICP_MODE_COLOR) && !(c->cfg.min_normal_dot > -1.0f)) b -= (int64_t)c->n_loc * 12;      // (no source normals read)
+    if (c->cfg.mode == SYMMICP_MODE_COLOR) b += (int64_t)c->n_loc * (4 + 16);      // the source's intensity per point, the target's (gradient, intensity) per pair
     c->st.bytes_algorithmic_per_pass = b;
     {
         uint32_t fb = 0;

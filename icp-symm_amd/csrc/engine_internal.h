@@ -145,6 +145,14 @@ struct symmicp_ctx {
     int loss = SYMMICP_LOSS_NONE;    // robust loss (symmicp_set_robust_loss) and its scale: read by every pass
     float loss_scale = 0.f;
     float gicp_eps = 1e-3f;          // SYMMICP_MODE_GICP's covariance eps (symmicp_set_gicp_epsilon): read by every GICP pass
+    // colored ICP (SYMMICP_MODE_COLOR): lambda, and the attributes in the order the clouds are kept in -- (gradient, intensity) per target
+    // point (the order of tn; of the planar target with identity pairing), the intensity per share row.  Own allocations, kept for the
+    // next cloud; have_*: set by symmicp_set_*_intensity, dropped by the cloud's next set_target / set_source
+    float color_lam = 0.968f;
+    float4 *tgt_color = nullptr;
+    float *src_int = nullptr;
+    size_t tgt_color_cap = 0, src_int_cap = 0;
+    bool have_tgt_color = false, have_src_int = false;
     // trimmed ICP (symmicp_set_trim_fraction): the fraction (1 = off), the per-row keys and the select's workspace (allocated by the
     // first trimmed pass), and what the most recent pass left (symmicp_get_trim_state; trim_valid: that pass was trimmed)
     float trim_frac = 1.0f;

@@ -18,6 +18,10 @@ static void fill_pass_args(symmicp_ctx *c, PassArgs &a, const float Xapply[16], 
     a.p2p = c->cfg.mode == SYMMICP_MODE_P2P ? 1 : 0;
     a.obj = mode_obj(c->cfg.mode);
     a.gicp_k = 1.0f - c->gicp_eps;
+    a.tgt_color = c->tgt_color;
+    a.src_int = c->src_int;
+    a.color_lam = c->color_lam;
+    a.color_om = 1.0f - c->color_lam;
     a.max_d2 = c->cfg.max_corr_dist > 0.f ? c->cfg.max_corr_dist * c->cfg.max_corr_dist : 0.f;
     a.min_ndot = c->cfg.min_normal_dot;
     a.writeback = writeback ? 1 : 0;
@@ -239,6 +243,7 @@ static bool batch_eligible(const symmicp_ctx *c)
 {
     if (c->sw.host_loop) return false;                                    // SYMMICP_HOST_LOOP=1: never batch (A/B runs, tests)
     if (c->trim_frac < 1.0f) return false;                                // trimmed passes: the fused pass and the device loop have no select
+    if (c->cfg.mode == SYMMICP_MODE_COLOR) return false;                  // colored ICP: the fused pass and the straggler stage have no COLOR form
     if (c->cfg.host_loop) return false;
     if (c->external_exchange || c->shm.slots) return false;               // those exchanges run on the host
     if (c->timing == 2 || c->ix.dbg) return false;                        // per-kernel tables and debug counters: host loop
@@ -485,6 +490,11 @@ static int check_ready(symmicp_ctx *c)
         return fail(c, SYMMICP_ERR_SIZE, "identity pairing needs N_s == N_t (func.cpp:21)");
     if (c->cfg.corr == SYMMICP_CORR_TREE && !c->have_index) return fail(c, SYMMICP_ERR_STATE, "target index missing");
     if (c->cfg.corr != SYMMICP_CORR_IDENTITY && !c->tq) return fail(c, SYMMICP_ERR_STATE, "target was set under a different corr mode");
+    if (c->cfg.mode == SYMMICP_MODE_COLOR) {
+        if (c->nranks > 1) return fail(c, SYMMICP_ERR_STATE, "SYMMICP_MODE_COLOR runs on single-rank contexts only");
+        if (!c->have_src_int || !c->have_tgt_color)
+            return fail(c, SYMMICP_ERR_STATE, "SYMMICP_MODE_COLOR needs symmicp_set_source_intensity and symmicp_set_target_intensity after the clouds");
+    }
     return SYMMICP_OK;
 }
 
@@ -527,7 +537,7 @@ int symmicp_step(symmicp_ctx *c, symmicp_iter_result *out)
     c->sums_exchanged = false;
     HIP_TRY(c, hipSetDevice(c->device));
     float pbar[3], qbar[3], a[3], t[3], rc = 0.f, Xi[16];
-    int st = (c->cfg.mode == SYMMICP_MODE_P2P) ? solve_p2p(c->last, c->pivot, &rc, Xi) : solve_mode(c->cfg.mode, c->last, c->pivot, pbar, qbar, a, t, &rc, Xi);
+    int st = (c->cfg.mode == SYMMICP_MODE_P2P) ? solve_p2p(c->last, c->pivot, &rc, Xi) : solve_mode(mode_solves_as(c->cfg.mode), c->last, c->pivot, pbar, qbar, a, t, &rc, Xi);
     if (st != SYMMICP_OK) {
         c->err = "degenerate system (rank-deficient normal equations or non-finite transform; func.cpp:70,96)";
         fill_iter(c, out, st, rc, nullptr);
@@ -679,6 +689,7 @@ int symmicp_solve(int mode, const symmicp_sums *sums, const float pivot[3], floa
         for (int k = 0; k < 3; k++) pbar[k] = qbar[k] = a[k] = t[k] = 0.f;
         return solve_p2p(*sums, pivot, rcond, out16);
     }
+    mode = mode_solves_as(mode);      // (COLOR's record has PLANE's shape)
     return mode_device_solves(mode) ? solve_mode(mode, *sums, pivot, pbar, qbar, a, t, rcond, out16) : SYMMICP_ERR_ARG;
 }
 

@@ -188,14 +188,51 @@ __device__ __forceinline__ void acc_gicp(AccN<NA> &a, float px, float py, float 
     acc_pair_sums(a, px, py, pz, qx, qy, qz, d2, w);
 }
 
+// COLOR (colored ICP, Park et al. 2017): two rows of PLANE's form per pair -- the geometric row v = (p x n_q, n_q), c_G = (p - q) . n_q at
+// weight lam, formed exactly as acc_plane forms it, and the photometric row v = (p x g, g), c_C = (p - q) . g + (I_q - I_p) at weight
+// om = 1.0f - lam, g = the target's intensity gradient -- fp32, unfused.  Slots 27..34, 36, 37 once per pair, as PLANE's; slot 35 sums
+// w (lam c_G^2 + om c_C^2).  In the weighted record (NA = kNAccW) the pair's weight is that of r = sqrtf((lam c_G) c_G + (om c_C) c_C) and
+// scales both rows, as GICP's does.  At lam = 1 (om = 0) every photometric term is an exact zero: the record is PLANE's bit for bit.
+template <int NA>
+__device__ __forceinline__ void acc_color(AccN<NA> &a, float px, float py, float pz, float qx, float qy, float qz, float nx, float ny, float nz,
+                                          const float4 &gi, float ip, float d2, const float *pivot, float lam, float om, int loss, float scale)
+{
+    px -= pivot[0]; py -= pivot[1]; pz -= pivot[2];
+    qx -= pivot[0]; qy -= pivot[1]; qz -= pivot[2];
+    const float dx = px - qx, dy = py - qy, dz = pz - qz;
+    const float m0 = py * nz - pz * ny;
+    const float m1 = pz * nx - px * nz;
+    const float m2 = px * ny - py * nx;
+    const float cg = (dx * nx + dy * ny) + dz * nz;
+    const float gx = gi.x, gy = gi.y, gz = gi.z;
+    const float k0 = py * gz - pz * gy;
+    const float k1 = pz * gx - px * gz;
+    const float k2 = px * gy - py * gx;
+    const float cc = ((dx * gx + dy * gy) + dz * gz) + (gi.w - ip);
+    const double w = NA == kNAccW ? (double)robust_weight(loss, scale, sqrtf((lam * cg) * cg + (om * cc) * cc)) : 1.0;
+    const double G[6] = {(double)m0, (double)m1, (double)m2, (double)nx, (double)ny, (double)nz};
+    acc_row(a, G, (double)cg, w * (double)lam);
+    const double C[6] = {(double)k0, (double)k1, (double)k2, (double)gx, (double)gy, (double)gz};
+    acc_row(a, C, (double)cc, w * (double)om);
+    acc_pair_sums(a, px, py, pz, qx, qy, qz, d2, w);
+}
+
 // The record of an accumulating kernel's instantiation (its OBJ parameter, PassArgs::obj): the symmetric rows of PAPER / QUIRKS / P2P
-// (acc_pair), PLANE's (acc_plane) or GICP's (acc_gicp).  Separate instantiations, not a branch, as W: each kernel keeps the registers its
-// own record needs.
+// (acc_pair), PLANE's (acc_plane), GICP's (acc_gicp) or COLOR's (acc_color; `color` = the pair's extra data, read by that one only).
+// Separate instantiations, not a branch, as W: each kernel keeps the registers its own record needs.
+struct ColorPair {
+    float4 gi;               // the target's (gradient xyz, intensity)
+    float ip;                // the source point's intensity
+    float lam, om;
+};
+
 template <int OBJ, int NA>
 __device__ __forceinline__ void acc_obj(AccN<NA> &acc, float px, float py, float pz, float npx, float npy, float npz, float qx, float qy, float qz,
-                                        float nqx, float nqy, float nqz, float d2, const float *pivot, int p2p, float gk, int loss, float scale)
+                                        float nqx, float nqy, float nqz, float d2, const float *pivot, int p2p, float gk, int loss, float scale,
+                                        const ColorPair *color = nullptr)
 {
-    if constexpr (OBJ == kObjPlane) acc_plane(acc, px, py, pz, qx, qy, qz, nqx, nqy, nqz, d2, pivot, loss, scale);
+    if constexpr (OBJ == kObjColor) acc_color(acc, px, py, pz, qx, qy, qz, nqx, nqy, nqz, color->gi, color->ip, d2, pivot, color->lam, color->om, loss, scale);
+    else if constexpr (OBJ == kObjPlane) acc_plane(acc, px, py, pz, qx, qy, qz, nqx, nqy, nqz, d2, pivot, loss, scale);
     else if constexpr (OBJ == kObjGicp) acc_gicp(acc, px, py, pz, npx, npy, npz, qx, qy, qz, nqx, nqy, nqz, d2, pivot, gk, loss, scale);
     else acc_pair(acc, px, py, pz, npx, npy, npz, qx, qy, qz, nqx, nqy, nqz, d2, pivot, p2p, loss, scale);
 }
@@ -223,28 +260,41 @@ __device__ __forceinline__ HotParams hot_params(const PassArgs &a)
     return h;
 }
 
-// Does an instantiation read the source normals?  Every record but PLANE's uses them; PLANE's reads them only to write them back or to
-// gate on them (min_normal_dot).
+// Does an instantiation read the source normals?  Every record but PLANE's and COLOR's uses them; those read them only to write them
+// back or to gate on them (min_normal_dot).
 template <int OBJ>
-__device__ __forceinline__ bool reads_src_normals(bool writeback, float min_ndot) { return OBJ != kObjPlane || writeback || min_ndot > -1.0f; }
+__device__ __forceinline__ bool reads_src_normals(bool writeback, float min_ndot)
+{
+    return (OBJ != kObjPlane && OBJ != kObjColor) || writeback || min_ndot > -1.0f;
+}
 
 // The pair step of every accumulating kernel: the gates (max_correspondence_distance, then min_normal_dot), then the record.  (nx, ny, nz)
 // is the source normal as stored (zeros where the instantiation does not read it); it is moved here, for the gate and the rows (PLANE's
-// rows do not read it: there the compiler keeps it to the gate).
+// and COLOR's rows do not read it: there the compiler keeps it to the gate).  color: the COLOR instantiations' extra data (null elsewhere).
 // T = true: the trimming instantiations (symmicp_set_trim_fraction below 1): a pair that passed the gates -- a candidate -- is kept only
 // if its d2 bits are <= tau, the order statistic kernels_select.hip left for this pass (ties at tau are kept).  A separate instantiation,
 // as W: the untrimmed kernels are the code they were.  tau has its own "off" (T = false), apart from max_d2, whose 0 means "keep all":
 // tau = 0 keeps the pairs at distance 0 only.
 template <int OBJ, bool T = false, int NA>
 __device__ __forceinline__ void pair_step(AccN<NA> &acc, const HotParams &h, float nx, float ny, float nz, float px, float py, float pz,
-                                          const float4 &q, const float4 &nq, float d2, uint32_t tau = 0u)
+                                          const float4 &q, const float4 &nq, float d2, uint32_t tau = 0u, const ColorPair *color = nullptr)
 {
     if (h.max_d2 > 0.0f && d2 > h.max_d2) return;
     const Affine &X = h.X;
     const float npx = xf_row(X.m + 0, nx, ny, nz, X.nrm_w), npy = xf_row(X.m + 4, nx, ny, nz, X.nrm_w), npz = xf_row(X.m + 8, nx, ny, nz, X.nrm_w);
     if (h.min_ndot > -1.0f && (npx * nq.x + npy * nq.y) + npz * nq.z < h.min_ndot) return;
     if (T && __float_as_uint(d2) > tau) return;
-    acc_obj<OBJ>(acc, px, py, pz, npx, npy, npz, q.x, q.y, q.z, nq.x, nq.y, nq.z, d2, h.pivot, h.p2p, h.gicp_k, h.loss, h.loss_scale);
+    acc_obj<OBJ>(acc, px, py, pz, npx, npy, npz, q.x, q.y, q.z, nq.x, nq.y, nq.z, d2, h.pivot, h.p2p, h.gicp_k, h.loss, h.loss_scale, color);
+}
+
+// The COLOR instantiations' extra data of one pair: the target's (gradient, intensity) at sorted position / row j, the source's at i
+__device__ __forceinline__ ColorPair color_pair(const PassArgs &a, uint32_t i, uint32_t j)
+{
+    ColorPair c;
+    c.gi = a.tgt_color[j];
+    c.ip = a.src_int[i];
+    c.lam = a.color_lam; c.om = a.color_om;
+    return c;
 }
 
 // one step of a sum on the VALU's DPP cross-lane network (no LDS traffic): row_shr 1,2,4,8 builds 16-lane row sums.  A double moves
@@ -386,8 +436,13 @@ __global__ __launch_bounds__(kPassThreads) void k_pass_identity(PassArgs a_in, C
             else a.d2_out[i0] = d2[0];
         }
 #pragma unroll
-        for (int k = 0; k < VEC; k++)
+        for (int k = 0; k < VEC; k++) {
+            if constexpr (OBJ == kObjColor) {
+                const ColorPair cp = color_pair(a, i0 + k, j0 + k);
+                pair_step<OBJ, T>(acc, h, nx[k], ny[k], nz[k], px[k], py[k], pz[k], make_float4(qx[k], qy[k], qz[k], 0.0f), make_float4(qnx[k], qny[k], qnz[k], 0.0f), d2[k], tau, &cp);
+            } else
             pair_step<OBJ, T>(acc, h, nx[k], ny[k], nz[k], px[k], py[k], pz[k], make_float4(qx[k], qy[k], qz[k], 0.0f), make_float4(qnx[k], qny[k], qnz[k], 0.0f), d2[k], tau);
+        }
     }
     acc_block_reduce_store(acc, a.partials, blockIdx.x);
 }
@@ -422,6 +477,10 @@ __global__ __launch_bounds__(kPassThreads) void k_pass_indexed(PassArgs a, const
         if (a.d2_out) a.d2_out[i] = ok ? d2 : __int_as_float(0x7f800000);
         if (!ok) continue;
         if (a.max_d2 > 0.0f && d2 > a.max_d2) continue;                  // (pair_step's gate, ahead of the gather it saves)
+        if constexpr (OBJ == kObjColor) {
+            const ColorPair cp = color_pair(a, i, j);
+            pair_step<OBJ, T>(acc, h, nx, ny, nz, px, py, pz, tn[2 * (size_t)j], tn[2 * (size_t)j + 1], d2, tau, &cp);
+        } else
         pair_step<OBJ, T>(acc, h, nx, ny, nz, px, py, pz, tn[2 * (size_t)j], tn[2 * (size_t)j + 1], d2, tau);      // one 32-byte pair record
     }
     acc_block_reduce_store(acc, a.partials, blockIdx.x);
@@ -1474,6 +1533,10 @@ __global__ __launch_bounds__(kPassThreads) void k_accumulate(PassArgs a, const f
             a.out.nz[i] = xf_row(a.X.m + 8, nx, ny, nz, a.X.nrm_w);
         }
         if (nq.w != 0.0f) continue;                       // no target for this point
+        if constexpr (OBJ == kObjColor) {
+            const ColorPair cp = color_pair(a, i, (uint32_t)a.pos_out[i]);      // (gathered by the pair's sorted position: the record copy holds no colour)
+            pair_step<OBJ, T>(acc, h, nx, ny, nz, px, py, pz, q, nq, dist2(px, py, pz, q.x, q.y, q.z), tau, &cp);
+        } else
         pair_step<OBJ, T>(acc, h, nx, ny, nz, px, py, pz, q, nq, dist2(px, py, pz, q.x, q.y, q.z), tau);
     }
     acc_block_reduce_store(acc, a.partials, blockIdx.x);
@@ -1915,6 +1978,17 @@ static void with_instantiation(const PassArgs &a, F &&f)
 template <typename F>
 static void with_trim(const PassArgs &a, F &&f)
 {
+    if (a.obj == kObjColor) {
+        // COLOR's instantiations exist for the host loop's accumulating kernels only (with_instantiation, which also serves the fused
+        // pass and the straggler stage, does not know them: batch_eligible keeps a COLOR context in the host loop)
+        auto trim = [&](auto W) {
+            if (a.trim_keys) f(W, std::integral_constant<int, kObjColor>(), std::true_type());
+            else f(W, std::integral_constant<int, kObjColor>(), std::false_type());
+        };
+        if (a.loss != SYMMICP_LOSS_NONE) trim(std::true_type());
+        else trim(std::false_type());
+        return;
+    }
     with_instantiation(a, [&](auto W, auto OBJ) {
         if (a.trim_keys) f(W, OBJ, std::true_type());
         else f(W, OBJ, std::false_type());

@@ -51,11 +51,24 @@ static bool load_one(const std::string &path, pcl::PointCloud<PointT> &out)
 	return true;
 }
 
+// the file's intensities (an `intensity` or `rgb` field), empty when it has none
+static void load_intensity(const std::string &path, size_t n, std::vector<float> &out)
+{
+	out.clear();
+	int kind = 0;
+	const long m = symmicp_pcd_read_intensity(path.c_str(), nullptr, 0, &kind);
+	if (m <= 0 || kind == 0 || (size_t)m != n) return;
+	out.resize(n);
+	if (symmicp_pcd_read_intensity(path.c_str(), out.data(), n, &kind) != m) out.clear();
+}
+
 int MyICP::LoadCloud(std::string src_path, std::string tgt_path)
 {
 	// myicp.cpp:20-31: x,y,z are kept, other fields dropped; the reference ignores reader status and returns 0
 	if (!load_one(src_path, *cloud_src)) error_ = "cannot read " + src_path;
 	if (!load_one(tgt_path, *cloud_tgt)) error_ = "cannot read " + tgt_path;
+	load_intensity(src_path, cloud_src->points.size(), src_int_);
+	load_intensity(tgt_path, cloud_tgt->points.size(), tgt_int_);
 	have_src_normals_ = have_tgt_normals_ = false;
 	return 0;
 }
@@ -93,6 +106,7 @@ void MyICP::setInputSource(const float *xyz, const float *normals, size_t n)
 	for (size_t i = 0; i < n; i++) { cloud_src->points[i].x = xyz[3 * i]; cloud_src->points[i].y = xyz[3 * i + 1]; cloud_src->points[i].z = xyz[3 * i + 2]; }
 	cloud_src->width = (uint32_t)n;
 	have_src_normals_ = normals != nullptr;
+	src_int_.clear();
 	fill_pn(*cloud_src, normals, *cloud_pn_src);
 }
 
@@ -102,6 +116,7 @@ void MyICP::setInputTarget(const float *xyz, const float *normals, size_t n)
 	for (size_t i = 0; i < n; i++) { cloud_tgt->points[i].x = xyz[3 * i]; cloud_tgt->points[i].y = xyz[3 * i + 1]; cloud_tgt->points[i].z = xyz[3 * i + 2]; }
 	cloud_tgt->width = (uint32_t)n;
 	have_tgt_normals_ = normals != nullptr;
+	tgt_int_.clear();
 	fill_pn(*cloud_tgt, normals, *cloud_pn_tgt);
 }
 
@@ -152,6 +167,12 @@ int MyICP::align(float out4x4[16], const float *guess4x4)
 	if (st == SYMMICP_OK) st = symmicp_set_trim_fraction(ctx, trim_fraction_);        // ERR_ARG: outside (0, 1], or below 1 with QUIRKS
 	if (st == SYMMICP_OK) st = symmicp_set_robust_loss(ctx, loss_, loss_scale_);      // ERR_ARG: a loss with QUIRKS, or a bad scale
 	if (st == SYMMICP_OK) st = symmicp_set_gicp_epsilon(ctx, gicp_eps_);              // ERR_ARG: eps outside (0, 1]
+	if (st == SYMMICP_OK) st = symmicp_set_color_weight(ctx, color_weight_);          // ERR_ARG: lambda outside [0, 1]
+	if (st == SYMMICP_OK && mode_ == SYMMICP_MODE_COLOR && !levels_.empty()) {
+		error_ = "SYMMICP_MODE_COLOR does not run voxel levels (intensities are not averaged per voxel yet)";
+		result_.status = SYMMICP_ERR_ARG;
+		return SYMMICP_ERR_ARG;
+	}
 	const size_t fs = sizeof(pcl::PointNormal) / sizeof(float);            // pasteInMatrix, func.cpp:5-15
 	level_results_.clear();
 	if (st == SYMMICP_OK && have_global_ && !guess4x4) {
@@ -177,6 +198,14 @@ int MyICP::align(float out4x4[16], const float *guess4x4)
 				                        cloud_pn_src->points.size());
 				ctx_no_src_normals_ = st == SYMMICP_OK && !source_normals;
 			}
+			if (st == SYMMICP_OK && mode_ == SYMMICP_MODE_COLOR) {
+				st = setColorAttributes(ctx);
+				if (st != SYMMICP_OK) {
+					result_.status = st;
+					if (out4x4) std::memcpy(out4x4, transform_, sizeof(transform_));
+					return st;
+				}
+			}
 		} else {
 			st = SYMMICP_ERR_SIZE;
 		}
@@ -186,6 +215,24 @@ int MyICP::align(float out4x4[16], const float *guess4x4)
 	if (st != SYMMICP_OK) error_ = symmicp_last_error(ctx);
 	if (result_.iters > 0 || st == SYMMICP_OK) std::memcpy(transform_, result_.transform, sizeof(transform_));
 	if (out4x4) std::memcpy(out4x4, transform_, sizeof(transform_));
+	return st;
+}
+
+// SYMMICP_MODE_COLOR: the target's intensity gradient on its tangent planes (k = 10, the normals align() uses), then both attributes
+int MyICP::setColorAttributes(symmicp_ctx *ctx)
+{
+	const size_t ns = cloud_pn_src->points.size(), nt = cloud_pn_tgt->points.size();
+	if (src_int_.size() != ns || tgt_int_.size() != nt) {
+		error_ = "SYMMICP_MODE_COLOR needs an intensity per point of both clouds (setSourceIntensity / setTargetIntensity, or files with an intensity or rgb field)";
+		return SYMMICP_ERR_STATE;
+	}
+	const size_t fs = sizeof(pcl::PointNormal) / sizeof(float);
+	std::vector<float> grad(3 * nt);
+	int st = symmicp_ctx_intensity_gradient(ctx, &cloud_pn_tgt->points[0].x, fs, 1, &cloud_pn_tgt->points[0].normal_x, fs, 1, tgt_int_.data(), 1, nt, 10,
+	                                        grad.data());
+	if (st == SYMMICP_OK) st = symmicp_set_target_intensity(ctx, tgt_int_.data(), 1, grad.data(), 3, 1, nt);
+	if (st == SYMMICP_OK) st = symmicp_set_source_intensity(ctx, src_int_.data(), 1, ns);
+	if (st != SYMMICP_OK) error_ = symmicp_last_error(ctx);
 	return st;
 }
 

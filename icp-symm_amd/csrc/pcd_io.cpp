@@ -167,6 +167,55 @@ extern "C" long symmicp_pcd_read(const char *path, float *xyz, float *nrm, size_
     return h.points;
 }
 
+// One scalar intensity per point: a field named `intensity`, else PCL's packed rgb / rgba (0x00RRGGBB in a 4-byte U or F field; an
+// ascii F value is parsed as a float and its bits are taken), I = (r + g + b) / 765
+extern "C" long symmicp_pcd_read_intensity(const char *path, float *out, size_t cap, int *kind)
+{
+    if (kind) *kind = 0;
+    if (!path) return -SYMMICP_ERR_ARG;
+    FILE *f = std::fopen(path, "rb");
+    if (!f) return -SYMMICP_ERR_IO;
+    Header h;
+    if (!parse_header(f, h)) { std::fclose(f); return -SYMMICP_ERR_IO; }
+    int fi = h.find("intensity"), k = 1;
+    if (fi >= 0 && !loadable(h.fields[fi])) { std::fclose(f); return -SYMMICP_ERR_IO; }
+    if (fi < 0) {
+        fi = h.find("rgb");
+        if (fi < 0) fi = h.find("rgba");
+        k = 2;
+        if (fi >= 0 && !(h.fields[fi].size == 4 && (h.fields[fi].type == 'U' || h.fields[fi].type == 'F'))) { std::fclose(f); return -SYMMICP_ERR_IO; }
+    }
+    if (fi < 0) { std::fclose(f); return 0; }
+    if (kind) *kind = k;
+    if (!out) { std::fclose(f); return h.points; }
+    if ((size_t)h.points > cap) { std::fclose(f); return -SYMMICP_ERR_SIZE; }
+    const Field &fd = h.fields[fi];
+    auto from_rgb = [](uint32_t w) { return (float)(((w >> 16) & 255u) + ((w >> 8) & 255u) + (w & 255u)) / 765.0f; };
+    if (h.binary) {
+        std::vector<unsigned char> rec((size_t)h.record);
+        for (long i = 0; i < h.points; ++i) {
+            if (std::fread(rec.data(), 1, rec.size(), f) != rec.size()) { std::fclose(f); return -SYMMICP_ERR_IO; }
+            if (k == 1) out[i] = load_scalar(rec.data() + fd.offset, fd);
+            else { uint32_t w; std::memcpy(&w, rec.data() + fd.offset, 4); out[i] = from_rgb(w); }
+        }
+    } else {
+        char line[8192];
+        for (long i = 0; i < h.points; ++i) {
+            if (!std::fgets(line, sizeof line, f)) { std::fclose(f); return -SYMMICP_ERR_IO; }
+            char *s = line, *e = line;
+            bool ok = true;
+            for (int col = 0; col < fd.column && ok; ++col) { std::strtod(s, &e); ok = e != s; s = e; }      // the columns in front
+            if (!ok) { std::fclose(f); return -SYMMICP_ERR_IO; }
+            if (k == 1) { const double d = std::strtod(s, &e); out[i] = (float)d; }
+            else if (fd.type == 'F') { const float v = std::strtof(s, &e); uint32_t w; std::memcpy(&w, &v, 4); out[i] = from_rgb(w); }
+            else { const unsigned long long w = std::strtoull(s, &e, 10); out[i] = from_rgb((uint32_t)w); }
+            if (e == s) { std::fclose(f); return -SYMMICP_ERR_IO; }
+        }
+    }
+    std::fclose(f);
+    return h.points;
+}
+
 // writer: the call the reference keeps commented out at main.cpp:51-52 / test.cpp:58 (savePCDFile)
 extern "C" int symmicp_pcd_write(const char *path, const float *xyz, const float *nrm, size_t n, int binary)
 {

@@ -23,17 +23,21 @@ constexpr int kBruteTile = 1024;      // target points staged in LDS per tile (1
 constexpr int kBruteQ = 4;            // queries per thread in the brute-force kernel
 
 // The modes symmicp_config accepts (4 is unassigned), and those whose record solve::solve_mode solves, on the host and on the device:
-// all but P2P, whose solve is host-only
+// all but P2P, whose solve is host-only, and COLOR, which stays in the host loop (its record has PLANE's shape: mode_solves_as maps it)
 constexpr bool mode_device_solves(int mode)
 {
     return mode == SYMMICP_MODE_QUIRKS || mode == SYMMICP_MODE_PAPER || mode == SYMMICP_MODE_PLANE || mode == SYMMICP_MODE_GICP;
 }
-constexpr bool mode_known(int mode) { return mode_device_solves(mode) || mode == SYMMICP_MODE_P2P; }
+constexpr bool mode_known(int mode) { return mode_device_solves(mode) || mode == SYMMICP_MODE_P2P || mode == SYMMICP_MODE_COLOR; }
+constexpr int mode_solves_as(int mode) { return mode == SYMMICP_MODE_COLOR ? SYMMICP_MODE_PLANE : mode; }
 
 // The record a mode's passes accumulate (PassArgs::obj, the OBJ parameter of every accumulating kernel): the symmetric rows of
-// QUIRKS / PAPER / P2P, PLANE's or GICP's
-constexpr int kObjSym = 0, kObjPlane = 1, kObjGicp = 2;
-constexpr int mode_obj(int mode) { return mode == SYMMICP_MODE_PLANE ? kObjPlane : mode == SYMMICP_MODE_GICP ? kObjGicp : kObjSym; }
+// QUIRKS / PAPER / P2P, PLANE's, GICP's or COLOR's (host-loop kernels only: the fused pass and the straggler stage have no COLOR form)
+constexpr int kObjSym = 0, kObjPlane = 1, kObjGicp = 2, kObjColor = 3;
+constexpr int mode_obj(int mode)
+{
+    return mode == SYMMICP_MODE_PLANE ? kObjPlane : mode == SYMMICP_MODE_GICP ? kObjGicp : mode == SYMMICP_MODE_COLOR ? kObjColor : kObjSym;
+}
 
 // 3x4 affine passed by value in kernel arguments (row-major), plus the weight
 // the translation column gets when it is applied to normals
@@ -180,6 +184,10 @@ struct PassArgs {
     uint32_t *trim_ws;                  // [kTrimWsWords] the select's state and histograms
     uint32_t *trim_host;                // host-mapped (n_c, kept, tau bits) of the pass
     float trim_rho;
+    // colored ICP (SYMMICP_MODE_COLOR; read by the kObjColor instantiations only)
+    const float4 *tgt_color;            // per target point, in the order of tn (IDENTITY: of the planar target): (gradient xyz, intensity)
+    const float *src_int;               // per share row: the source point's intensity
+    float color_lam, color_om;          // lambda and omega = 1.0f - lambda
 };
 constexpr uint32_t kTrimWsWords = 16 + 3 * 2048;
 constexpr uint32_t kTrimTauWord = 3;
@@ -267,6 +275,16 @@ void launch_identity_d2(const CloudSoA &in, const Affine &X, const CloudSoA &tgt
 void launch_pairs_d2(const CloudSoA &in, const Affine &X, const int32_t *pos, const float4 *tq, uint32_t n_t, uint32_t n, float *d2, hipStream_t s);
 void launch_normals_knn(const TargetIndex &ix, int k, const float vp[3], float *nrm_out, float *curv_out, hipStream_t s);
 void launch_knn(const TargetIndex &ix, int k, int32_t *rows_out, float *d2_out, hipStream_t s);
+
+// colored ICP (kernels_color.hip).  The attributes into engine order: dst[i] = (grad[row(i)], intensity[row(i)]) with row(i) the w word of
+// tq[i] (tq == null: i), and dst[i] = intensity[order ? order[i] : off + i]; the read-back scatters the other way (out[order ? order[i] : i], as launch_unpermute).  The gradient
+// (symmicp_ctx_intensity_gradient): rec_rows [n] = (xyz, intensity) by original row, scattered from the index; then one thread per sorted
+// point over the neighbour rows launch_knn left in knn_rows [n][k]
+void launch_color_permute_target(const float *intensity, const float *grad3, const float4 *tq, uint32_t n, float4 *dst, hipStream_t s);
+void launch_color_permute_source(const float *intensity, const uint32_t *order, uint32_t off, uint32_t n, float *dst, hipStream_t s);
+void launch_color_unpermute_source(const float *src_int, const uint32_t *order, uint32_t n, float *out_rows, hipStream_t s);
+void launch_color_gradient(const TargetIndex &ix, const float *intensity_rows, const int32_t *knn_rows, int k, float4 *rec_rows, float *grad_rows,
+                           hipStream_t s);
 
 // voxel-grid downsampling (kernels_voxel.hip; symmicp_ctx_voxel_downsample): keys + iota rows; run heads -> exclusive scan -> first
 // position of every voxel (first[m0] = n) and the voxel count m0 in *m0_out; kept voxels (>= min_points) -> exclusive scan ->

@@ -22,7 +22,7 @@ UNIQUE_ID_BYTES = 128
 OK, ERR_ARG, ERR_SIZE, ERR_DEGENERATE, ERR_IO, ERR_HIP, ERR_STATE, ERR_COMM = range(8)
 ERR_NO_CONSENSUS = 8
 RANSAC_EVALUATED, RANSAC_REPEATED, RANSAC_EDGE, RANSAC_DEGENERATE, RANSAC_FAR = range(5)      # per-hypothesis status of ransac()
-MODE_QUIRKS, MODE_PAPER, MODE_P2P, MODE_PLANE, MODE_GICP = 0, 1, 2, 3, 5      # (4 is unassigned)
+MODE_QUIRKS, MODE_PAPER, MODE_P2P, MODE_PLANE, MODE_GICP, MODE_COLOR = 0, 1, 2, 3, 5, 7      # (4 and 6 are unassigned)
 CORR_IDENTITY, CORR_BRUTE, CORR_TREE = 0, 1, 2
 APPLY_DEFAULT, APPLY_INCREMENTAL, APPLY_CUMULATIVE = 0, 1, 2
 LOSS_NONE, LOSS_HUBER, LOSS_TUKEY, LOSS_CAUCHY, LOSS_GEMAN_MCCLURE = range(5)
@@ -118,6 +118,8 @@ EXPORTS = [
     "symmicp_ransac_config_default", "symmicp_ransac", "symmicp_ctx_ransac", "symmicp_ctx_ransac_hypotheses",
     "symmicp_ctx_index_info", "symmicp_ctx_index_arrays", "symmicp_ctx_source_share", "symmicp_ctx_radix_sort_probe", "symmicp_ctx_scan_probe",
     "symmicp_set_trim_fraction", "symmicp_get_trim_fraction", "symmicp_get_trim_state", "symmicp_ctx_select_probe",
+    "symmicp_set_color_weight", "symmicp_get_color_weight", "symmicp_set_source_intensity", "symmicp_set_target_intensity",
+    "symmicp_get_source_intensity", "symmicp_intensity_gradient", "symmicp_ctx_intensity_gradient", "symmicp_pcd_read_intensity",
 ]
 
 _lib = None
@@ -229,6 +231,16 @@ def lib():
     L.symmicp_get_trim_fraction.argtypes = [vp, fp]
     L.symmicp_get_trim_state.argtypes = [vp, u64p, u64p, fp]
     L.symmicp_ctx_select_probe.argtypes = [vp, u32p, C.c_size_t, C.c_uint64, u32p, u64p]
+    L.symmicp_set_color_weight.argtypes = [vp, C.c_float]
+    L.symmicp_get_color_weight.argtypes = [vp, fp]
+    L.symmicp_set_source_intensity.argtypes = [vp, fp, C.c_size_t, C.c_size_t]
+    L.symmicp_set_target_intensity.argtypes = [vp, fp, C.c_size_t, fp, C.c_size_t, C.c_size_t, C.c_size_t]
+    L.symmicp_get_source_intensity.argtypes = [vp, fp, C.c_size_t]
+    grd = [fp, C.c_size_t, C.c_size_t, fp, C.c_size_t, C.c_size_t, fp, C.c_size_t, C.c_size_t, C.c_int, fp]
+    L.symmicp_intensity_gradient.argtypes = [C.c_int] + grd
+    L.symmicp_ctx_intensity_gradient.argtypes = [vp] + grd
+    L.symmicp_pcd_read_intensity.argtypes = [C.c_char_p, fp, C.c_size_t, C.POINTER(C.c_int)]
+    L.symmicp_pcd_read_intensity.restype = C.c_long
     _lib = L
     return L
 
@@ -267,6 +279,23 @@ def pcd_read(path):
     if r != n:
         raise SymmIcpError(-r if r < 0 else ERR_IO, "pcd_read(%s)" % path)
     return xyz, (nrm if hn.value else None)
+
+
+def pcd_read_intensity(path):
+    """one scalar per point of a PCD file -> (intensity [N] f32 or None, kind): kind 1 = an `intensity` field, 2 = PCL's packed
+    `rgb` / `rgba` turned into (r + g + b) / 765, 0 = the file has neither (None)"""
+    L = lib()
+    kind = C.c_int(0)
+    n = L.symmicp_pcd_read_intensity(os.fsencode(path), None, 0, C.byref(kind))
+    if n < 0:
+        raise SymmIcpError(-n, "pcd_read_intensity(%s)" % path)
+    if kind.value == 0:
+        return None, 0
+    out = np.zeros(n, np.float32)
+    r = L.symmicp_pcd_read_intensity(os.fsencode(path), _fptr(out), n, C.byref(kind))
+    if r != n:
+        raise SymmIcpError(-r if r < 0 else ERR_IO, "pcd_read_intensity(%s)" % path)
+    return out, kind.value
 
 
 def pcd_write(path, xyz, nrm=None, binary=False):
@@ -337,6 +366,26 @@ def estimate_normals(xyz, k=10, viewpoint=(0.0, 0.0, 0.0), device=-1):
     if st != OK:
         raise SymmIcpError(st, "estimate_normals")
     return nrm, curv
+
+
+def _scalar(a, n=None):
+    a = np.ascontiguousarray(a, dtype=np.float32).reshape(-1)
+    if n is not None and a.shape[0] != n:
+        raise ValueError("one value per point expected")
+    return a
+
+
+def intensity_gradient(xyz, nrm, intensity, k=10, device=-1):
+    """the intensity's gradient on every point's tangent plane (symmicp_intensity_gradient: the k-NN set of knn() without the point
+    itself, a least-squares fit in fp64) -> [N,3] f32, exactly 0 where the neighbourhood is degenerate"""
+    xyz, nrm = _cloud(xyz), _cloud(nrm)
+    n = xyz.shape[0]
+    it = _scalar(intensity, n)
+    g = np.zeros((n, 3), np.float32)
+    st = lib().symmicp_intensity_gradient(device, _fptr(xyz), 3, 1, _fptr(nrm), 3, 1, _fptr(it), 1, n, k, _fptr(g))
+    if st != OK:
+        raise SymmIcpError(st, "intensity_gradient")
+    return g
 
 
 def knn(xyz, k=10, device=-1):
@@ -657,6 +706,44 @@ class Engine:
         fr = C.c_float(0)
         self._chk(self._L.symmicp_get_trim_fraction(self._h, C.byref(fr)))
         return fr.value
+
+    def set_color_weight(self, lam):
+        """MODE_COLOR: the geometric rows weigh lam, the photometric ones 1 - lam (0 <= lam <= 1; default 0.968); takes effect at
+        the next pass"""
+        self._chk(self._L.symmicp_set_color_weight(self._h, float(lam)))
+
+    def color_weight(self):
+        lam = C.c_float(0)
+        self._chk(self._L.symmicp_get_color_weight(self._h, C.byref(lam)))
+        return lam.value
+
+    def set_source_intensity(self, intensity):
+        """MODE_COLOR: one scalar per source point, after set_source (a new set_source drops it)"""
+        it = _scalar(intensity)
+        self._chk(self._L.symmicp_set_source_intensity(self._h, _fptr(it), 1, it.shape[0]))
+
+    def set_target_intensity(self, intensity, grad):
+        """MODE_COLOR: one scalar and its tangent-plane gradient [N,3] (intensity_gradient) per target point, after set_target"""
+        it = _scalar(intensity)
+        g = _cloud(grad)
+        if g.shape[0] != it.shape[0]:
+            raise ValueError("one gradient per intensity expected")
+        self._chk(self._L.symmicp_set_target_intensity(self._h, _fptr(it), 1, _fptr(g), 3, 1, it.shape[0]))
+
+    def source_intensity(self):
+        """the source's intensities as the engine holds them, read back in the caller's row order"""
+        out = np.zeros(self.n_source, np.float32)
+        self._chk(self._L.symmicp_get_source_intensity(self._h, _fptr(out), self.n_source))
+        return out
+
+    def intensity_gradient(self, xyz, nrm, intensity, k=10):
+        """intensity_gradient on this context (symmicp_ctx_intensity_gradient); its target, source and index stay as they are"""
+        xyz, nrm = _cloud(xyz), _cloud(nrm)
+        n = xyz.shape[0]
+        it = _scalar(intensity, n)
+        g = np.zeros((n, 3), np.float32)
+        self._chk(self._L.symmicp_ctx_intensity_gradient(self._h, _fptr(xyz), 3, 1, _fptr(nrm), 3, 1, _fptr(it), 1, n, k, _fptr(g)))
+        return g
 
     def trim_state(self):
         """-> (candidates, kept, tau_d2 as np.float32) of the most recent pass; ERR_STATE if it was not trimmed"""
@@ -1020,6 +1107,8 @@ class MyICP:
         self._loss = (LOSS_NONE, 0.0)
         self._gicp_eps = None
         self._trim = 1.0
+        self._color_weight = None
+        self.intensity_src = self.intensity_tgt = None
         self._levels = []
         self.level_results = []
         self._global = None
@@ -1033,8 +1122,12 @@ class MyICP:
     def setVoxelLevels(self, levels):
         """coarse-to-fine alignment: [(leaf, max_iters, max_corr_dist), ...], coarse first (leaf 0: the clouds as given).  align()
         then runs one alignment per level on both clouds voxel-downsampled with the level's leaf (normals averaged), each from the
-        transform of the level before (the first from the caller's guess).  CORR_IDENTITY is refused (ERR_ARG).  [] = off."""
-        self._levels = [(float(l), int(i), float(d)) for l, i, d in levels]
+        transform of the level before (the first from the caller's guess).  CORR_IDENTITY is refused (ERR_ARG), and so is MODE_COLOR
+        (intensities are not averaged per voxel yet).  [] = off."""
+        levels = [(float(l), int(i), float(d)) for l, i, d in levels]
+        if levels and self._cfg["mode"] == MODE_COLOR:
+            raise SymmIcpError(ERR_ARG, "MODE_COLOR does not run voxel levels (intensities are not averaged per voxel yet)")
+        self._levels = levels
 
     def setGlobalInit(self, fpfh_radius, max_dist, voxel_leaf=0.0, normal_k=10, hypotheses=100000, seed=0, mutual=True, max_ratio=0.0,
                       edge_ratio=0.9, refits=1):
@@ -1087,6 +1180,10 @@ class MyICP:
         """the covariance eps of the next align in MODE_GICP (see Engine.set_gicp_epsilon)"""
         self._gicp_eps = float(eps)
 
+    def setColorWeight(self, lam):
+        """lambda of the next align in MODE_COLOR (see Engine.set_color_weight)"""
+        self._color_weight = float(lam)
+
     def setTrimFraction(self, fraction):
         """trimmed ICP for the next align, every voxel level included (see Engine.set_trim_fraction; 1 = off)"""
         self._trim = float(fraction)
@@ -1099,6 +1196,8 @@ class MyICP:
         # myicp.cpp:20-31 (reader status is ignored there; here a bad file raises)
         self.cloud_src, _ = pcd_read(src_path)
         self.cloud_tgt, _ = pcd_read(tgt_path)
+        self.intensity_src, _ = pcd_read_intensity(src_path)      # (None for files without an `intensity` or `rgb` field)
+        self.intensity_tgt, _ = pcd_read_intensity(tgt_path)
         self.normals_src = self.normals_tgt = None
         self._have_src = self._have_tgt = False
         return 0
@@ -1109,13 +1208,15 @@ class MyICP:
     def GetTgtCloud(self):
         return self.cloud_tgt
 
-    def setInputSource(self, xyz, normals=None):
+    def setInputSource(self, xyz, normals=None, intensity=None):
         self.cloud_src = _cloud(xyz)
+        self.intensity_src = None if intensity is None else _scalar(intensity, self.cloud_src.shape[0])
         self.normals_src = None if normals is None else _cloud(normals)
         self._have_src = normals is not None
 
-    def setInputTarget(self, xyz, normals=None):
+    def setInputTarget(self, xyz, normals=None, intensity=None):
         self.cloud_tgt = _cloud(xyz)
+        self.intensity_tgt = None if intensity is None else _scalar(intensity, self.cloud_tgt.shape[0])
         self.normals_tgt = None if normals is None else _cloud(normals)
         self._have_tgt = normals is not None
 
@@ -1135,6 +1236,11 @@ class MyICP:
         assert self.cloud_src is not None and self.cloud_tgt is not None      # myicp.cpp:102
         if self._levels and self._cfg["corr"] == CORR_IDENTITY:
             raise SymmIcpError(ERR_ARG, "voxel levels need nearest-neighbour pairs (CORR_IDENTITY pairs by row)")
+        color = self._cfg["mode"] == MODE_COLOR
+        if color and self._levels:
+            raise SymmIcpError(ERR_ARG, "MODE_COLOR does not run voxel levels (intensities are not averaged per voxel yet)")
+        if color and (self.intensity_src is None or self.intensity_tgt is None):
+            raise SymmIcpError(ERR_STATE, "MODE_COLOR needs an intensity per point of both clouds (setInputSource / setInputTarget, or files with one)")
         self.estimateNormals()                                               # myicp.cpp:105
         if self._levels:
             return self._align_levels(guess)
@@ -1147,8 +1253,15 @@ class MyICP:
                 e.set_gicp_epsilon(self._gicp_eps)
             if self._trim != 1.0:
                 e.set_trim_fraction(self._trim)
+            if self._color_weight is not None:
+                e.set_color_weight(self._color_weight)
             e.set_target(self.cloud_tgt, self.normals_tgt)
             e.set_source(self.cloud_src, self.normals_src)
+            if color:
+                # the target's intensity gradient on its tangent planes, k = 10 (the neighbourhood of the normals)
+                grad = e.intensity_gradient(self.cloud_tgt, self.normals_tgt, self.intensity_tgt, 10)
+                e.set_target_intensity(self.intensity_tgt, grad)
+                e.set_source_intensity(self.intensity_src)
             self.last_result = e.align(guess)
         self._final = self.last_result["transform"]
         return self.last_result

@@ -9,6 +9,7 @@ CPU oracle.
                      the same surface moved by 3 deg + small t (no exact twins)
   c5_scan(n)     C5: scan-like rings ray-cast onto the C4 surface + a ground plane, range noise
   perturbed(xyz, nrm, deg, axis, t)  C2 substitute: a cloud against its own rigid perturbation
+  ridge_textured(n)  a textured extruded ridge: geometry alone leaves the slide along it free (colored ICP's test pair)
 """
 import numpy as np
 
@@ -113,6 +114,39 @@ def c4_surface(n=1_000_000, seed=0xC4):
     tn = nt @ R.T
     return dict(src=ps.astype(np.float32), src_n=ns.astype(np.float32), tgt=tgt.astype(np.float32),
                 tgt_n=tn.astype(np.float32), truth=rigid4(R, t))
+
+
+def _ridge(u, v):
+    """an extruded profile: z = 0.05 sin(10 pi u + 1), constant along v (geometry cannot fix a translation along v)"""
+    z = 0.05 * np.sin(10 * np.pi * u + 1.0)
+    dzu = 0.5 * np.pi * np.cos(10 * np.pi * u + 1.0)
+    nrm = np.stack([-dzu, np.zeros_like(u), np.ones_like(u)], 1)
+    nrm /= np.linalg.norm(nrm, axis=1, keepdims=True)
+    return np.stack([u, v, z], 1), nrm
+
+
+def _ridge_texture(u, v):
+    return 0.5 + 0.2 * np.sin(2 * np.pi * (2 * u + 0.3)) * np.cos(3 * np.pi * v) + 0.15 * np.sin(2 * np.pi * (3 * v + u))
+
+
+def ridge_textured(n=20_000, seed=0xC7, slide=0.03):
+    """Colored ICP's pair: two samplings (seed, seed + 1) of the ridge z = 0.05 sin(10 pi u + 1) with analytic normals and the
+    intensity I(u, v) = 0.5 + 0.2 sin(2 pi (2u + 0.3)) cos(3 pi v) + 0.15 sin(2 pi (3v + u)) painted on it.  The source is slid by
+    -slide along the ridge (v), the target moved by C4's motion (3 deg about (2, -1, 4), t = (0.004, 0.003, -0.002)):
+    truth = motion * translate(0, slide, 0).  The geometry alone leaves the slide free; only the texture fixes it.
+    spacing = sqrt(1 / n).  All arrays fp32, as c4_surface's."""
+    us, vs = uniform01(seed, n, 0), uniform01(seed, n, 1)
+    ut, vt = uniform01(seed + 1, n, 0), uniform01(seed + 1, n, 1)
+    ps, ns = _ridge(us, vs)
+    pt, nt = _ridge(ut, vt)
+    R = rotation(3.0, (2, -1, 4))
+    t = np.array([0.004, 0.003, -0.002])
+    src = ps.copy()
+    src[:, 1] -= slide
+    truth = rigid4(R, t) @ rigid4(np.eye(3), np.array([0.0, slide, 0.0]))
+    return dict(src=src.astype(np.float32), src_n=ns.astype(np.float32), src_i=_ridge_texture(us, vs).astype(np.float32),
+                tgt=(pt @ R.T + t).astype(np.float32), tgt_n=(nt @ R.T).astype(np.float32),
+                tgt_i=_ridge_texture(ut, vt).astype(np.float32), truth=truth, spacing=float(np.sqrt(1.0 / n)))
 
 
 def _height(x, y):

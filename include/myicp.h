@@ -59,6 +59,15 @@ public:
 	// overlap only in part.  Applies to single-level runs and to every level of setVoxelLevels; checked by align(), which returns
 	// SYMMICP_ERR_ARG unless 0 < fraction <= 1, and for a fraction below 1 with SYMMICP_MODE_QUIRKS
 	void setTrimFraction(float fraction) { trim_fraction_ = fraction; }
+	// Colored ICP (SYMMICP_MODE_COLOR): one scalar intensity per point of each cloud, n = the cloud's count, set after setInput* /
+	// LoadCloud (LoadCloud keeps the intensities of files that carry an `intensity` or `rgb` field; setInput* drops the cloud's).
+	// align() estimates the target's intensity gradient itself (symmicp_ctx_intensity_gradient, k = 10).  In COLOR align() returns
+	// SYMMICP_ERR_STATE when either cloud has no intensities, and SYMMICP_ERR_ARG with voxel levels (not supported yet).
+	void setSourceIntensity(const float *intensity, size_t n) { src_int_.assign(intensity, intensity + n); }
+	void setTargetIntensity(const float *intensity, size_t n) { tgt_int_.assign(intensity, intensity + n); }
+	// lambda of the geometric rows (symmicp_set_color_weight; default 0.968): checked by align(), SYMMICP_ERR_ARG outside [0, 1]
+	void setColorWeight(float lambda) { color_weight_ = lambda; }
+	bool haveIntensities() const { return !src_int_.empty() && !tgt_int_.empty(); }   // both clouds carry one (set, or loaded from the files)
 	// pairs farther apart than d are dropped (symmicp_config.max_corr_dist; <= 0, the default: every pair is kept)
 	void setMaxCorrespondenceDistance(float d) { max_corr_dist_ = d; }
 	// Coarse-to-fine alignment.  With levels set, align() estimates (or takes) the normals of the full clouds as before, then runs
@@ -121,6 +130,9 @@ private:
 	float gicp_eps_;
 	float trim_fraction_;
 	float max_corr_dist_;
+	float color_weight_ = 0.968f;
+	std::vector<float> src_int_, tgt_int_;
+	int setColorAttributes(symmicp_ctx *ctx);   // COLOR: the target's gradient and both intensities, after set_target / set_source
 	std::vector<VoxelLevel> levels_;
 	std::vector<symmicp_result> level_results_;
 	int alignLevels(const symmicp_config &cfg, bool source_normals, const float *guess4x4);

@@ -63,9 +63,17 @@ typedef enum {
  * (exact for unit normals).  The mode is DEFINED by this formula with cs clamped to [-1, 1], so that it holds for any input:
  * zero normals give M = 1/2 I (a point-to-point pair), non-unit normals get the formula as stated.  GICP needs the normals of
  * both clouds; pivot, CUMULATIVE default, rotated-only normals and the solve (PLANE's, about the weighted source centroid) as
- * PLANE.  Mode 4 is unassigned. */
+ * PLANE.  COLOR is colored ICP (Park, Zhou, Koltun 2017; Open3D's registration_colored_icp) on one scalar intensity per point: every
+ * pair carries PLANE's geometric row at weight lambda and a photometric row at weight omega = 1.0f - lambda (fp32), the difference
+ * between the source point's intensity I_p and a first-order model of the target's intensity on its tangent plane, I_q + g_q . (p - q)
+ * with g_q the target's intensity gradient (tangent to the surface; symmicp_ctx_intensity_gradient estimates it).  The mode is
+ * DEFINED by its rows (see symmicp_sums); pivot, CUMULATIVE default, rotated-only normals, the gates, trimming and the solve are
+ * PLANE's, and only the target's normals enter the rows.  Source normals stay required (nrm == NULL is PLANE-only); they are read
+ * under PLANE's rule (write-back or min_normal_dot).  lambda: symmicp_set_color_weight; the attributes: symmicp_set_source_intensity
+ * and symmicp_set_target_intensity.  Out of scope, refused: sharded contexts (nranks > 1: SYMMICP_ERR_STATE), the fused pass and the
+ * device-driven loop (symmicp_align runs the host loop, as it does for a trimming context).  Modes 4 and 6 are unassigned. */
 typedef enum { SYMMICP_MODE_QUIRKS = 0, SYMMICP_MODE_PAPER = 1, SYMMICP_MODE_P2P = 2, SYMMICP_MODE_PLANE = 3,
-               SYMMICP_MODE_GICP = 5 } symmicp_mode;
+               SYMMICP_MODE_GICP = 5, SYMMICP_MODE_COLOR = 7 } symmicp_mode;
 
 /* Correspondence.  IDENTITY is what the reference does (myicp.cpp:130, the
  * search is a todo at :128-131).  BRUTE and TREE are exact nearest neighbour
@@ -88,6 +96,7 @@ typedef enum { SYMMICP_APPLY_DEFAULT = 0, SYMMICP_APPLY_INCREMENTAL = 1, SYMMICP
  * so `scale` is in units of c, about TWICE the point-to-plane distance when the two normals agree -- in PLANE
  * r = c = (p - q) . n_q, the signed point-to-plane distance itself (`scale` in plain length units), in GICP
  * r = sqrt(d^T M d), the pair's Mahalanobis distance (about 1/sqrt(2) of |p - q| across the planes, larger along the normals),
+ * in COLOR r = sqrtf((lambda*c_G)*c_G + (omega*c_C)*c_C) (both rows are scaled by the pair's weight, as GICP scales its rows),
  * and in P2P r = |p - q|.  With u = r / scale:
  *   HUBER          1 if |u| <= 1, else 1/|u|
  *   TUKEY          (1 - u^2)^2 if |u| < 1, else 0
@@ -134,6 +143,12 @@ typedef struct {
  *   [27..32] sum p, sum q once per PAIR, not per row (PLANE's solve centres on the source centroid)
  *   [35] sum_i d^T M d (= sum_i sum_l o c^2)                every other slot as above.
  *   The record has PLANE's shape: symmicp_solve(SYMMICP_MODE_GICP) is PLANE's solve.
+ * COLOR: two rows per pair of PLANE's form, fp32, unfused, in the association written; p, q about the pivot, d = p - q, n = n_q, g = g_q:
+ *   geometric    v = (p x n, n) formed exactly as PLANE's, c_G = (dx*nx + dy*ny) + dz*nz, at weight lambda
+ *   photometric  v = (p x g, g) formed the same way,      c_C = ((dx*gx + dy*gy) + dz*gz) + (I_q - I_p), at weight omega = 1.0f - lambda
+ *   [0..26] sum o v v^T and sum o v c over both rows     [35] sum (lambda c_G^2 + omega c_C^2)
+ *   [27..34], [36], [37] once per pair, as PLANE.  symmicp_solve(SYMMICP_MODE_COLOR) is PLANE's solve.
+ *   At lambda = 1 every photometric term is multiplied by an exact zero: for finite g and I the record is PLANE's, bit for bit.
  * With a robust loss set (symmicp_set_robust_loss), w_i = the pair's weight:
  *   [0..32], [35]  the same sums with every pair scaled by w_i: sum w v v^T, sum w v c, sum w p, sum w q, sum w c^2
  *                  (P2P: sum w p q^T and the weighted coordinate sums; GICP: every row of the pair scaled by w_i)
@@ -187,6 +202,11 @@ int symmicp_get_robust_loss(const symmicp_ctx *ctx, int *loss, float *scale);
  * sets the same value. */
 int symmicp_set_gicp_epsilon(symmicp_ctx *ctx, float eps);
 int symmicp_get_gicp_epsilon(const symmicp_ctx *ctx, float *eps);
+/* The lambda of SYMMICP_MODE_COLOR: the geometric rows weigh lambda, the photometric ones 1.0f - lambda.  0 <= lambda <= 1 and
+ * finite, else SYMMICP_ERR_ARG and the value set before stays; default 0.968f (Open3D's lambda_geometric).  Accepted in every mode,
+ * read by COLOR only.  Takes effect at the next pass. */
+int symmicp_set_color_weight(symmicp_ctx *ctx, float lambda);
+int symmicp_get_color_weight(const symmicp_ctx *ctx, float *lambda);
 /* Trimmed ICP (Chetverikov, Stepanov, Krsek 2002/2005; PCL's CorrespondenceRejectorTrimmed, libpointmatcher's
  * TrimmedDistOutlierFilter): each pass keeps the closest fraction rho of its pairs -- the rejection rule for clouds that overlap only
  * in part.  A pure function of the pass:
@@ -237,6 +257,20 @@ int symmicp_set_source(symmicp_ctx *ctx, const float *xyz, size_t xyz_row_stride
 int symmicp_set_target(symmicp_ctx *ctx, const float *xyz, size_t xyz_row_stride, size_t xyz_col_stride,
                        const float *nrm, size_t nrm_row_stride, size_t nrm_col_stride, size_t n);
 
+/* Per-point attributes of SYMMICP_MODE_COLOR: one scalar intensity per source point; one intensity and its gradient (3 floats,
+ * tangent to the surface: symmicp_ctx_intensity_gradient, or the caller's own) per target point.  intensity[i * stride], grad
+ * element (i, k) at grad[i * grad_row_stride + k * grad_col_stride], rows as the cloud's.  Each call follows the cloud's
+ * symmicp_set_source / symmicp_set_target (SYMMICP_ERR_STATE before it); n must equal that cloud's count (SYMMICP_ERR_SIZE); a NULL
+ * pointer or a non-finite value is SYMMICP_ERR_ARG.  The engine keeps the values in the order it keeps the cloud (the target index's
+ * Morton order; the order of a sorted source share).  A new symmicp_set_source / symmicp_set_target drops that cloud's attribute.
+ * Accepted in every mode, read by COLOR only: there symmicp_begin / symmicp_align without both is SYMMICP_ERR_STATE.
+ * symmicp_get_source_intensity reads the source's values back in the caller's row order (cap >= the source's count; rows outside
+ * this rank's share stay 0). */
+int symmicp_set_source_intensity(symmicp_ctx *ctx, const float *intensity, size_t stride, size_t n);
+int symmicp_set_target_intensity(symmicp_ctx *ctx, const float *intensity, size_t stride,
+                                 const float *grad, size_t grad_row_stride, size_t grad_col_stride, size_t n);
+int symmicp_get_source_intensity(symmicp_ctx *ctx, float *intensity, size_t cap);
+
 /* ---- the loop (replaces MyICP::RegisterSymm, myicp.cpp:117-142) -------- */
 /* align = begin + step until the stop rule of myicp.cpp:123. guess16 may be NULL (identity). */
 int symmicp_align(symmicp_ctx *ctx, const float *guess16, symmicp_result *out);
@@ -271,7 +305,7 @@ size_t symmicp_local_source_count(const symmicp_ctx *ctx);
 size_t symmicp_local_source_offset(const symmicp_ctx *ctx);
 
 /* ---- host-side pieces of func.cpp:76-102, exposed for parity tests ----- */
-/* PAPER, PLANE and GICP: pbar / qbar = the (weighted) centroids in the caller's frame, (a, t) the solved 6-vector; P2P: zeros */
+/* PAPER, PLANE, GICP and COLOR (PLANE's solve): pbar / qbar = the (weighted) centroids in the caller's frame, (a, t) the solved 6-vector; P2P: zeros */
 int symmicp_solve(int mode, const symmicp_sums *sums, const float pivot[3],
                   float pbar[3], float qbar[3], float a[3], float t[3], float *rcond, float out16[16]);
 
@@ -367,6 +401,32 @@ int symmicp_ctx_estimate_normals(symmicp_ctx *ctx, const float *xyz, size_t row_
  * included.  Same argument rules as symmicp_ctx_estimate_normals; the context's own clouds are left alone. */
 int symmicp_ctx_knn(symmicp_ctx *ctx, const float *xyz, size_t row_stride, size_t col_stride, size_t n, int k,
                     int32_t *rows_out, float *d2_out);
+
+/* ---- intensity gradient on the tangent plane (the target attribute of SYMMICP_MODE_COLOR) --------------------------------------
+ * grad_out [n][3] packed (required); xyz, nrm (both required) strided as in symmicp_set_source; intensity[i * stride]; 3 <= k <= 16
+ * and k <= n.  For row i with normal n, every step in fp64 from the fp32 inputs, unfused, sums in the order written:
+ *   1. neighbours j = the k-NN set of symmicp_ctx_knn without row i itself, in its ascending (d2, row) order
+ *   2. x = x_j - x_i;  s = (x.x*n.x + x.y*n.y) + x.z*n.z;  e_j = x - s n
+ *   3. M = sum_j e_j e_j^T (upper triangle)      4. r = sum_j e_j (I_j - I_i)      5. mu = ((M00 + M11) + M22) / 2
+ *   6. A = M + mu n n^T, A_ab = M_ab + (mu * n_a) * n_b
+ *   7. g = adj(A) r / det A by the symmetric 3x3 adjugate: c00 = A11*A22 - A12*A12, c01 = A02*A12 - A01*A22, c02 = A01*A12 - A02*A11,
+ *      c11 = A00*A22 - A02*A02, c12 = A01*A02 - A00*A12, c22 = A00*A11 - A01*A01, det = (A00*c00 + A01*c01) + A02*c02,
+ *      g_x = ((c00*r0 + c01*r1) + c02*r2) / det, g_y = ((c01*r0 + c11*r1) + c12*r2) / det, g_z = ((c02*r0 + c12*r1) + c22*r2) / det
+ *   8. g = 0 unless det > 1e-12 * t*t*t with t = ((A00 + A11) + A22) / 3 (collinear or duplicate neighbourhoods; a zero normal
+ *      on a flat neighbourhood)
+ *   9. g rounded to fp32.
+ * mu stands in for the normal direction: r is orthogonal to n and M n = 0, so g is tangent and does not depend on mu in exact
+ * arithmetic, and A's condition number is the ratio of the two tangent moments.
+ * SYMMICP_ERR_ARG: NULL xyz / nrm / intensity / grad_out; n == 0 or n > 2^31 - 1; k outside 3 .. 16 or above n; non-finite
+ * coordinates.  The ctx form runs on the context's stream and arenas like symmicp_ctx_knn: the context's source, target, index,
+ * attributes and certificates stay exactly as they were. */
+int symmicp_ctx_intensity_gradient(symmicp_ctx *ctx, const float *xyz, size_t xyz_row_stride, size_t xyz_col_stride,
+                                   const float *nrm, size_t nrm_row_stride, size_t nrm_col_stride,
+                                   const float *intensity, size_t intensity_stride, size_t n, int k, float *grad_out);
+/* the same on a context of its own, created on `device` (-1 = current) and destroyed again */
+int symmicp_intensity_gradient(int device, const float *xyz, size_t xyz_row_stride, size_t xyz_col_stride,
+                               const float *nrm, size_t nrm_row_stride, size_t nrm_col_stride,
+                               const float *intensity, size_t intensity_stride, size_t n, int k, float *grad_out);
 
 /* ---- fixed-radius neighbour search (PCL's radiusSearch), exact, on the GPU ------------------------------------------------
  * For a cloud of n points and a radius r (finite, > 0): r2 = r * r in fp32, d2(i, j) = (dx*dx + dy*dy) + dz*dz in fp32,
@@ -592,7 +652,8 @@ typedef struct {
     int32_t tree_levels;
     int64_t pass_blocks;
     int64_t bytes_algorithmic_per_pass;  /* N_s*(48+4+4)+N_t*12 (NN) or N_s*48 (identity) [+24 N_s write-back]
-                                            [-12 N_s: PLANE reads no source normals without write-back and min_normal_dot] */
+                                            [-12 N_s: PLANE and COLOR read no source normals without write-back and min_normal_dot]
+                                            [+20 N_s in COLOR: 4 B of source intensity per point, 16 B of target (gradient, intensity) per pair] */
     /* per-kernel HIP-event time since the last reset (timing mode), slots:
      * 0 k_search_cells, 1 idle gap between cells and walk, 2 k_search_walk, 3 k_accumulate, 4 k_final_reduce,
      * 5 the single pass kernel of the IDENTITY / BRUTE modes (k_pass_identity, or k_nn_brute + k_pass_indexed),
@@ -628,6 +689,11 @@ int symmicp_enable_timing(symmicp_ctx *ctx, int on);
  * xyz==NULL to query the count.  nrm may be NULL.  *has_normals reports normal_x/y/z fields. */
 long symmicp_pcd_read(const char *path, float *xyz, float *nrm, size_t cap, int *has_normals);
 int symmicp_pcd_write(const char *path, const float *xyz, const float *nrm, size_t n, int binary);
+/* One scalar intensity per point of a PCD file, in file order.  A field named `intensity` (any scalar type the reader loads):
+ * *kind = 1.  Else a field named `rgb` or `rgba`, PCL's packed 0x00RRGGBB in a 4-byte U or F field (an ASCII F value is parsed as
+ * a float and its bits are taken): I = (float)(r + g + b) / 765.0f, *kind = 2.  Neither: *kind = 0 and the count returned is 0.
+ * Returns the point count (>= 0) or -symmicp_status; out == NULL queries the count; kind may be NULL. */
+long symmicp_pcd_read_intensity(const char *path, float *out, size_t cap, int *kind);
 
 #ifdef __cplusplus
 }
