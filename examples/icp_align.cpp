@@ -16,6 +16,9 @@
 //     --max-dist D             drop pairs farther apart than D (default 0: keep every pair)
 //     --trim F                 trimmed ICP: every pass keeps the closest fraction F of its pairs, 0 < F <= 1 (default 1: all of them;
 //                              for clouds that overlap only in part; not with --mode quirks)
+//     --one-to-one             of the source points paired with one target point only the closest is kept (not with --mode quirks)
+//     --median-factor F        drop pairs farther apart than F times the median pair distance, F > 0 (default 0: off; not with --trim
+//                              below 1, not with --mode quirks)
 //     --scale LEAF:ITERS[:MAXDIST]   one level of a coarse-to-fine alignment (repeat it, coarse first): both clouds
 //                              voxel-downsampled with edge LEAF (0: as given), at most ITERS iterations, pairs farther than
 //                              MAXDIST dropped (default 0: none); each level starts from the one before.  Needs --corr tree
@@ -44,7 +47,7 @@
 static int usage(const char *argv0, const char *complaint)
 {
     std::fprintf(stderr, "%s\nusage: %s [--mode quirks|paper|plane|gicp|color] [--color-weight L] [--corr identity|tree] [--iters N] [--threshold D] [--loss none|huber|tukey|cauchy|gm]"
-                 " [--loss-scale S] [--gicp-epsilon E] [--max-dist D] [--trim F] [--scale LEAF:ITERS[:MAXDIST]]... [--init global --fpfh-radius R --ransac-dist D [--ransac-iters H] [--seed S] [--init-voxel L]] [--out file.pcd] [--quiet] [source.pcd target.pcd]\n",
+                 " [--loss-scale S] [--gicp-epsilon E] [--max-dist D] [--trim F] [--one-to-one] [--median-factor F] [--scale LEAF:ITERS[:MAXDIST]]... [--init global --fpfh-radius R --ransac-dist D [--ransac-iters H] [--seed S] [--init-voxel L]] [--out file.pcd] [--quiet] [source.pcd target.pcd]\n",
                  complaint, argv0);
     return 64;
 }
@@ -64,6 +67,8 @@ int main(int argc, char **argv)
     bool color = false, have_color_weight = false;
     float color_weight = 0.f;
     float trim = 1.f;
+    bool one_to_one = false;
+    float median_factor = 0.f;
     std::vector<MyICP::VoxelLevel> levels;
     bool init_global = false, have_init_option = false;
     MyICP::GlobalInit ginit;
@@ -134,6 +139,13 @@ int main(int argc, char **argv)
             const char *v = value("--trim");
             trim = std::strtof(v, &end);
             if (end == v || *end || !(trim > 0.f) || trim > 1.f) return usage(argv[0], "--trim needs a fraction F with 0 < F <= 1");
+        } else if (a == "--one-to-one") {
+            one_to_one = true;
+        } else if (a == "--median-factor") {
+            char *end = nullptr;
+            const char *v = value("--median-factor");
+            median_factor = std::strtof(v, &end);
+            if (end == v || *end || !std::isfinite(median_factor) || !(median_factor > 0.f)) return usage(argv[0], "--median-factor needs a number F > 0");
         } else if (a == "--scale") {
             // LEAF:ITERS[:MAXDIST]
             const char *v = value("--scale");
@@ -191,6 +203,12 @@ int main(int argc, char **argv)
         icp.setColorWeight(color_weight);
     }
     if (color && !levels.empty()) return usage(argv[0], "--mode color does not run --scale levels (intensities are not averaged per voxel yet)");
+    if (one_to_one || median_factor > 0.f) {
+        if (quirks) return usage(argv[0], "--one-to-one and --median-factor need --mode paper, plane or gicp (quirks is the reference as written)");
+        if (median_factor > 0.f && trim < 1.f) return usage(argv[0], "--median-factor and --trim below 1 exclude each other");
+        icp.setOneToOne(one_to_one);
+        icp.setMedianFactor(median_factor);
+    }
     if (!levels.empty()) {
         if (!tree) return usage(argv[0], "--scale needs --corr tree (identity pairing cannot pair clouds of different sizes)");
         icp.setVoxelLevels(levels);

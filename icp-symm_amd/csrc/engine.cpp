@@ -201,7 +201,7 @@ void symmicp_destroy(symmicp_ctx *c)
     free_target(c);
     free_source(c);
     hipFree(c->partials); hipFree(c->d_sums); hipFree(c->ticket); hipFree(c->arena.base); hipFree(c->keep.base);
-    hipFree(c->trim_keys); hipFree(c->trim_ws);
+    hipFree(c->trim_keys); hipFree(c->trim_ws); hipFree(c->uniq_table);
     hipFree(c->tgt_color); hipFree(c->src_int);
     if (c->h_sums) hipHostFree(c->h_sums);
     hipFree(c->d_loop);
@@ -226,6 +226,8 @@ int symmicp_set_config(symmicp_ctx *c, const symmicp_config *cfg)
         return fail(c, SYMMICP_ERR_ARG, "QUIRKS takes no robust loss (set SYMMICP_LOSS_NONE first)");
     if (cfg->mode == SYMMICP_MODE_QUIRKS && c->trim_frac < 1.0f)
         return fail(c, SYMMICP_ERR_ARG, "QUIRKS takes no trim fraction below 1 (set 1 first)");
+    if (cfg->mode == SYMMICP_MODE_QUIRKS && (c->one_to_one || c->med_factor > 0.0f))
+        return fail(c, SYMMICP_ERR_ARG, "QUIRKS takes no one-to-one or median-distance rejector (switch them off first)");
     if (cfg->mode == SYMMICP_MODE_COLOR && c->nranks > 1)
         return fail(c, SYMMICP_ERR_STATE, "SYMMICP_MODE_COLOR runs on single-rank contexts only");
     if (c->src_no_normals && cfg->mode != SYMMICP_MODE_PLANE)
@@ -237,6 +239,7 @@ int symmicp_set_config(symmicp_ctx *c, const symmicp_config *cfg)
     c->cfg.device = dev;
     c->begun = false;
     c->trim_valid = false;
+    c->rej_valid = c->rej_new = false;
     return SYMMICP_OK;
 }
 
@@ -275,6 +278,7 @@ int symmicp_set_trim_fraction(symmicp_ctx *c, float fraction)
     if (!(fraction > 0.f && fraction <= 1.f)) return fail(c, SYMMICP_ERR_ARG, "trim fraction: 0 < fraction <= 1");      // (NaN fails both)
     if (fraction < 1.f && c->cfg.mode == SYMMICP_MODE_QUIRKS) return fail(c, SYMMICP_ERR_ARG, "QUIRKS takes no trim fraction below 1");
     if (fraction < 1.f && c->nranks > 1) return fail(c, SYMMICP_ERR_STATE, "trimming needs a quantile over all ranks: single-rank contexts only");
+    if (fraction < 1.f && c->med_factor > 0.0f) return fail(c, SYMMICP_ERR_ARG, "a trim fraction below 1 and a median factor exclude each other (set the factor to 0 first)");
     c->trim_frac = fraction;
     return SYMMICP_OK;
 }
@@ -291,6 +295,52 @@ int symmicp_get_trim_state(const symmicp_ctx *c, uint64_t *candidates, uint64_t 
     if (!c) return SYMMICP_ERR_ARG;
     if (!c->begun || !c->trim_valid) return SYMMICP_ERR_STATE;      // (const context: no message)
     if (candidates) *candidates = c->trim_nc;
+    if (kept) *kept = c->trim_kept;
+    if (tau_d2) std::memcpy(tau_d2, &c->trim_tau, sizeof(float));
+    return SYMMICP_OK;
+}
+
+// ---- one-to-one and median-distance rejectors ------------------------------------------------------
+int symmicp_set_one_to_one(symmicp_ctx *c, int on)
+{
+    if (!c) return SYMMICP_ERR_ARG;
+    if (on && c->cfg.mode == SYMMICP_MODE_QUIRKS) return fail(c, SYMMICP_ERR_ARG, "QUIRKS takes no one-to-one rejector");
+    if (on && c->nranks > 1) return fail(c, SYMMICP_ERR_STATE, "the one-to-one claim needs a minimum over all ranks: single-rank contexts only");
+    c->one_to_one = on != 0;
+    return SYMMICP_OK;
+}
+
+int symmicp_get_one_to_one(const symmicp_ctx *c, int *on)
+{
+    if (!c || !on) return SYMMICP_ERR_ARG;
+    *on = c->one_to_one ? 1 : 0;
+    return SYMMICP_OK;
+}
+
+int symmicp_set_median_factor(symmicp_ctx *c, float factor)
+{
+    if (!c) return SYMMICP_ERR_ARG;
+    if (!(factor == 0.f || (std::isfinite(factor) && factor > 0.f))) return fail(c, SYMMICP_ERR_ARG, "median factor: 0 (off), or finite and > 0");
+    if (factor > 0.f && c->cfg.mode == SYMMICP_MODE_QUIRKS) return fail(c, SYMMICP_ERR_ARG, "QUIRKS takes no median-distance rejector");
+    if (factor > 0.f && c->nranks > 1) return fail(c, SYMMICP_ERR_STATE, "the median needs a quantile over all ranks: single-rank contexts only");
+    if (factor > 0.f && c->trim_frac < 1.0f) return fail(c, SYMMICP_ERR_ARG, "a median factor and a trim fraction below 1 exclude each other (set the fraction to 1 first)");
+    c->med_factor = factor == 0.f ? 0.f : factor;      // (-0 is off too)
+    return SYMMICP_OK;
+}
+
+int symmicp_get_median_factor(const symmicp_ctx *c, float *factor)
+{
+    if (!c || !factor) return SYMMICP_ERR_ARG;
+    *factor = c->med_factor;
+    return SYMMICP_OK;
+}
+
+int symmicp_get_rejection_state(const symmicp_ctx *c, uint64_t *gated, uint64_t *unique, uint64_t *kept, float *tau_d2)
+{
+    if (!c) return SYMMICP_ERR_ARG;
+    if (!c->begun || !c->rej_new) return SYMMICP_ERR_STATE;      // (const context: no message)
+    if (gated) *gated = c->rej_gated;
+    if (unique) *unique = c->rej_unique;
     if (kept) *kept = c->trim_kept;
     if (tau_d2) std::memcpy(tau_d2, &c->trim_tau, sizeof(float));
     return SYMMICP_OK;
@@ -764,6 +814,7 @@ int symmicp_set_source(symmicp_ctx *c, const float *xyz, size_t xr, size_t xc, c
     forget_source(c);
     c->begun = false;
     c->trim_valid = false;
+    c->rej_valid = c->rej_new = false;
     // This rank's share is a contiguous block of the CALLER's rows, and only those rows are uploaded and sorted: set_source costs
     // 1/nranks of the single-GPU call on every rank (round 1 uploaded and sorted the whole cloud on every rank and kept a
     // slice of the global Morton order).  Any partition of the source is exact -- queries are independent given the
@@ -971,9 +1022,9 @@ int symmicp_get_correspondences(symmicp_ctx *c, int32_t *idx, float *d2, size_t 
         X.nrm_w = 0.f;
         launch_pairs_d2(incr ? c->cur : c->src0, X, c->pos, c->tq, c->n_t, c->n_loc, c->d2, c->stream);
     }
-    // (after a trimmed pass a row that was no candidate, or was trimmed away, is reported as rejected)
+    // (after a pass with a rejector -- trim fraction, one-to-one, median -- a row that was no candidate, or was rejected, is reported as rejected)
     launch_corr_out(c->pos, c->best64, c->d2, c->tq, c->src_order, c->n_loc, mode, c->src_off, d_idx.p, d_d2.p,
-                    c->trim_valid ? c->trim_keys : nullptr, c->trim_tau, c->stream);
+                    c->rej_valid ? c->trim_keys : nullptr, c->trim_tau, c->stream);
     if (idx) HIP_TRY(c, hipMemcpyAsync(idx, d_idx.p, sizeof(int32_t) * need, hipMemcpyDeviceToHost, c->stream));
     if (d2) HIP_TRY(c, hipMemcpyAsync(d2, d_d2.p, sizeof(float) * need, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));

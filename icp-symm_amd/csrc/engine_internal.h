@@ -160,6 +160,16 @@ struct symmicp_ctx {
     size_t trim_keys_cap = 0;
     bool trim_valid = false;
     uint32_t trim_nc = 0, trim_kept = 0, trim_tau = 0;
+    // the one-to-one and median-distance rejectors (symmicp_set_one_to_one / symmicp_set_median_factor): they share trim_keys, trim_ws and
+    // the trimming instantiations.  uniq_table: the claim table, one word per target point, allocated by the first one-to-one pass.
+    // rej_valid: the most recent pass ran a rejector of any kind (its keys say which rows were kept); rej_new: one of these two
+    // (symmicp_get_rejection_state); rej_gated = n_c, rej_unique = n_u (= n_c without one-to-one)
+    bool one_to_one = false;
+    float med_factor = 0.0f;
+    unsigned long long *uniq_table = nullptr;
+    size_t uniq_table_cap = 0;
+    bool rej_valid = false, rej_new = false;
+    uint32_t rej_gated = 0, rej_unique = 0;
     int device = 0;
     hipStream_t stream = nullptr;
     std::string err;

@@ -5,6 +5,11 @@
 extern "C" {
 
 // ---- one pass over the source share ------------------------------------------------------------
+// The rejectors of a pass (symmicp.h: trim fraction, one-to-one, median distance).  Identity pairs are one-to-one as they are: the option
+// launches nothing there.
+static bool pass_claims(const symmicp_ctx *c) { return c->one_to_one && c->cfg.corr != SYMMICP_CORR_IDENTITY; }
+static bool pass_rejects(const symmicp_ctx *c) { return c->trim_frac < 1.0f || c->med_factor > 0.0f || pass_claims(c); }
+
 static void fill_pass_args(symmicp_ctx *c, PassArgs &a, const float Xapply[16], bool from_cur, bool writeback, bool first)
 {
     a.in = from_cur ? c->cur : c->src0;
@@ -51,11 +56,17 @@ static void fill_pass_args(symmicp_ctx *c, PassArgs &a, const float Xapply[16], 
     a.pkt_lds_pad = c->sw.packet_lds_pad;
     a.loss = c->loss;
     a.loss_scale = c->loss_scale;
-    // trimmed pass (run_pass has made sure of the buffers); the result lands behind the record's sequence word in host-mapped memory
-    const bool trim = c->trim_frac < 1.0f && c->trim_keys && c->trim_ws;
+    // pass with a rejector (run_pass has made sure of the buffers); the result lands behind the record's sequence word in host-mapped memory
+    const bool trim = pass_rejects(c) && c->trim_keys && c->trim_ws;
     a.trim_keys = trim ? c->trim_keys : nullptr;
     a.trim_ws = trim ? c->trim_ws : nullptr;
     a.trim_host = trim ? reinterpret_cast<uint32_t *>(c->h_sums_dev + kNSum + 1) : nullptr;
+    const bool uniq = trim && pass_claims(c) && c->uniq_table;
+    a.uniq_table = uniq ? c->uniq_table : nullptr;
+    a.uniq_order = uniq ? c->src_order : nullptr;
+    a.uniq_n_t = uniq ? (uint32_t)c->n_t : 0u;
+    a.trim_uniq = uniq ? 1 : 0;
+    a.med_f2 = trim && c->med_factor > 0.0f ? c->med_factor * c->med_factor : 0.0f;
     a.trim_rho = c->trim_frac;
 }
 
@@ -63,8 +74,19 @@ static int run_pass(symmicp_ctx *c, const float Xapply[16], bool from_cur, bool 
 {
     // Trimmed pass (trim_frac < 1): search as always, then the keys of the candidates and the exact select of tau (kernels_select.hip:
     // one memset and six launches, issued by the pass launchers in front of the accumulating kernel), then the accumulation over the
-    // pairs at or below tau and the final reduce.  With trim_frac == 1 nothing below differs from an untrimmed build.
-    const bool trim = c->trim_frac < 1.0f;
+    // pairs at or below tau and the final reduce.  The one-to-one claim (one memset and k_unique_claim in front of the keys) and the
+    // median factor (tau = factor^2 x the select's median, then a counting pass) go the same way: any of the three makes this a rejecting
+    // pass.  With none of them set nothing below differs from a build without them.
+    const bool trim = pass_rejects(c);
+    if (trim && pass_claims(c)) {
+        const size_t want = c->n_t ? c->n_t : 1;
+        if (c->uniq_table_cap < want) {
+            hipFree(c->uniq_table);
+            c->uniq_table = nullptr; c->uniq_table_cap = 0;
+            HIP_TRY(c, hipMalloc((void **)&c->uniq_table, sizeof(unsigned long long) * want));
+            c->uniq_table_cap = want;
+        }
+    }
     if (trim) {
         const size_t want = c->n_loc ? c->n_loc : 1;
         if (c->trim_keys_cap < want) {
@@ -76,6 +98,7 @@ static int run_pass(symmicp_ctx *c, const float Xapply[16], bool from_cur, bool 
         if (!c->trim_ws) HIP_TRY(c, hipMalloc((void **)&c->trim_ws, sizeof(uint32_t) * kTrimWsWords));
     }
     c->trim_valid = false;
+    c->rej_valid = c->rej_new = false;
     PassArgs a{};
     fill_pass_args(c, a, Xapply, from_cur, writeback, first);
     int blocks = (int)((c->n_loc + kPassThreads - 1) / kPassThreads);
@@ -209,7 +232,10 @@ static int run_pass(symmicp_ctx *c, const float Xapply[16], bool from_cur, bool 
     if (trim) {
         const volatile uint32_t *w = reinterpret_cast<const volatile uint32_t *>(c->h_sums + kNSum + 1);      // (written before the record: same stream)
         c->trim_nc = w[0]; c->trim_kept = w[1]; c->trim_tau = w[2];
-        c->trim_valid = true;
+        c->rej_gated = w[3]; c->rej_unique = w[0];
+        c->trim_valid = c->trim_frac < 1.0f;
+        c->rej_valid = true;
+        c->rej_new = c->med_factor > 0.0f || c->one_to_one;
     }
     if (ev) c->ev_used++;
     c->t_last_done = now_s(); c->n_pass_timed++;
@@ -242,7 +268,7 @@ static uint32_t loop_scan_limit(uint32_t n) { const uint32_t f = n / 256; return
 static bool batch_eligible(const symmicp_ctx *c)
 {
     if (c->sw.host_loop) return false;                                    // SYMMICP_HOST_LOOP=1: never batch (A/B runs, tests)
-    if (c->trim_frac < 1.0f) return false;                                // trimmed passes: the fused pass and the device loop have no select
+    if (pass_rejects(c)) return false;                                    // trimmed and other rejecting passes: the fused pass and the device loop have no select
     if (c->cfg.mode == SYMMICP_MODE_COLOR) return false;                  // colored ICP: the fused pass and the straggler stage have no COLOR form
     if (c->cfg.host_loop) return false;
     if (c->external_exchange || c->shm.slots) return false;               // those exchanges run on the host

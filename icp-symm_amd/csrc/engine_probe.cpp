@@ -148,6 +148,30 @@ int symmicp_ctx_select_probe(symmicp_ctx *c, const uint32_t *keys, size_t n, uin
     return SYMMICP_OK;
 }
 
+int symmicp_ctx_unique_probe(symmicp_ctx *c, const int32_t *tgt_row, const uint32_t *d2_bits, size_t n, size_t n_t, uint8_t *winner_out)
+{
+    if (!c) return SYMMICP_ERR_ARG;
+    if (!tgt_row || !d2_bits || !winner_out || n == 0 || n > 0x7fffffffull || n_t == 0 || n_t > 0x7fffffffull) return fail(c, SYMMICP_ERR_ARG, "unique_probe: bad arguments");
+    HIP_TRY(c, hipSetDevice(c->device));
+    arena_begin(c->arena, (sizeof(int32_t) + sizeof(uint32_t) + 1) * n + sizeof(unsigned long long) * n_t + 4096);
+    DevBuf<int32_t> d_row;
+    DevBuf<uint32_t> d_d2;
+    DevBuf<unsigned long long> table;      // (its own table: the context's claim table and rejection state stay as they were)
+    DevBuf<uint8_t> d_win;
+    HIP_TRY(c, table.alloc_temp(c->arena, n_t));
+    HIP_TRY(c, d_row.alloc_temp(c->arena, n));
+    HIP_TRY(c, d_d2.alloc_temp(c->arena, n));
+    HIP_TRY(c, d_win.alloc_temp(c->arena, n));
+    HIP_TRY(c, hipMemcpyAsync(d_row.p, tgt_row, sizeof(int32_t) * n, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(d_d2.p, d2_bits, sizeof(uint32_t) * n, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    launch_unique_probe(d_row.p, d_d2.p, (uint32_t)n, table.p, (uint32_t)n_t, d_win.p, c->stream);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpyAsync(winner_out, d_win.p, n, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return SYMMICP_OK;
+}
+
 int symmicp_ctx_scan_probe(symmicp_ctx *c, uint32_t *data, size_t n)
 {
     if (!c) return SYMMICP_ERR_ARG;

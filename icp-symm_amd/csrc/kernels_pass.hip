@@ -275,6 +275,8 @@ __device__ __forceinline__ bool reads_src_normals(bool writeback, float min_ndot
 // if its d2 bits are <= tau, the order statistic kernels_select.hip left for this pass (ties at tau are kept).  A separate instantiation,
 // as W: the untrimmed kernels are the code they were.  tau has its own "off" (T = false), apart from max_d2, whose 0 means "keep all":
 // tau = 0 keeps the pairs at distance 0 only.
+// The one-to-one and median-distance rejectors run through the same instantiations: the median only derives tau differently, and with
+// PassArgs::trim_uniq set (a runtime flag, not another template axis) the kernel drops the rows whose key is the sentinel before this step.
 template <int OBJ, bool T = false, int NA>
 __device__ __forceinline__ void pair_step(AccN<NA> &acc, const HotParams &h, float nx, float ny, float nz, float px, float py, float pz,
                                           const float4 &q, const float4 &nq, float d2, uint32_t tau = 0u, const ColorPair *color = nullptr)
@@ -477,6 +479,7 @@ __global__ __launch_bounds__(kPassThreads) void k_pass_indexed(PassArgs a, const
         if (a.d2_out) a.d2_out[i] = ok ? d2 : __int_as_float(0x7f800000);
         if (!ok) continue;
         if (a.max_d2 > 0.0f && d2 > a.max_d2) continue;                  // (pair_step's gate, ahead of the gather it saves)
+        if (T && a.trim_uniq && a.trim_keys[i] == 0xFFFFFFFFu) continue;      // one-to-one: the row lost its target (or is no candidate)
         if constexpr (OBJ == kObjColor) {
             const ColorPair cp = color_pair(a, i, j);
             pair_step<OBJ, T>(acc, h, nx, ny, nz, px, py, pz, tn[2 * (size_t)j], tn[2 * (size_t)j + 1], d2, tau, &cp);
@@ -1533,6 +1536,7 @@ __global__ __launch_bounds__(kPassThreads) void k_accumulate(PassArgs a, const f
             a.out.nz[i] = xf_row(a.X.m + 8, nx, ny, nz, a.X.nrm_w);
         }
         if (nq.w != 0.0f) continue;                       // no target for this point
+        if (T && a.trim_uniq && a.trim_keys[i] == 0xFFFFFFFFu) continue;      // one-to-one: the row lost its target (or is no candidate)
         if constexpr (OBJ == kObjColor) {
             const ColorPair cp = color_pair(a, i, (uint32_t)a.pos_out[i]);      // (gathered by the pair's sorted position: the record copy holds no colour)
             pair_step<OBJ, T>(acc, h, nx, ny, nz, px, py, pz, q, nq, dist2(px, py, pz, q.x, q.y, q.z), tau, &cp);

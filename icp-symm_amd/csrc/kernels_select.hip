@@ -1,5 +1,5 @@
-// kernels_select.hip -- trimmed ICP (symmicp_set_trim_fraction) for gfx950: the keys of a pass's candidate pairs and the exact
-// order statistic over them.
+// kernels_select.hip -- pair rejection by rank for gfx950 (trimmed ICP, symmicp_set_trim_fraction; one-to-one and median distance below):
+// the keys of a pass's candidate pairs and the exact order statistic over them.
 //
 // A trimmed pass keeps the closest fraction rho of its candidate pairs (include/symmicp.h has the definition).  Between the search
 // and the accumulating kernel of the pass run
@@ -15,6 +15,14 @@
 // leaves tau, n_c and the kept count (keys <= tau, ties included) in device memory for the accumulating kernel and in host-mapped
 // memory for symmicp_get_trim_state.  Every step is launch-bound (4 B per row and digit), so there is no host round trip in between.
 //
+// The one-to-one and median-distance rejectors (symmicp_set_one_to_one / symmicp_set_median_factor) use the same keys and the same select:
+//   k_unique_claim   in front of the keys: every candidate claims its target with (d2 bits << 32 | caller row) by a 64-bit atomicMin on a
+//                    table of one word per target point; k_trim_keys<UNIQ> then gives every candidate that is not the minimum of its
+//                    target the sentinel, so the select's population is the winners
+//   k_median_tau     behind the select at rho = 0.5: tau = factor^2 x the median; k_count_le counts the keys <= tau, k_reject_publish
+//                    hands (population, kept, tau, n_c) to the host; k_reject_all does both for one-to-one alone (every winner is kept)
+// launch_trim_select has the order.
+//
 // The gates below are pair_step's (kernels_pass.hip), on the same fp32 expressions: unfused, in the association written.
 #include "symmicp_internal.h"
 #include "device_common.h"
@@ -26,7 +34,7 @@ constexpr int kSelThreads = 256;
 constexpr uint32_t kSelBins = 2048;           // bins of the widest digit (11 bits)
 constexpr uint32_t kSelMaxBlocks = 1024;      // grid-stride beyond this
 // workspace words (PassArgs::trim_ws): the state, then one histogram per digit
-enum { SEL_NC = 0, SEL_K = 1, SEL_PREFIX = 2, SEL_TAU = 3, SEL_KEPT = 4, SEL_K0 = 5, SEL_STATE_WORDS = 16 };
+enum { SEL_NC = 0, SEL_K = 1, SEL_PREFIX = 2, SEL_TAU = 3, SEL_KEPT = 4, SEL_K0 = 5, SEL_GATED = 6, SEL_MED = 7, SEL_STATE_WORDS = 16 };
 static_assert(kTrimWsWords == SEL_STATE_WORDS + 3 * kSelBins, "symmicp_internal.h sizes the workspace");
 static_assert(kTrimTauWord == SEL_TAU, "the accumulating kernels read tau from this word");
 
@@ -71,16 +79,122 @@ __device__ __forceinline__ void hist_merge(const uint32_t *h, uint32_t *ghist)
     }
 }
 
+// Candidate status of share row i -- a pair that exists and passes pair_step's gates -- with its d2 and the target position j the pass
+// holds for it (IDENTITY: the target row; BRUTE: best64's low word; TREE: pos_out).  One source for the keys and for the one-to-one claim.
 // CORR: 0 identity (target row = tgt_offset + i), 1 brute (best64), 2 tree (pos_out -> the target's pair record)
 template <int CORR>
+__device__ __forceinline__ bool pair_candidate(const PassArgs &a, const CloudSoA &tgt, const float4 *__restrict__ tn, bool gate_n, uint32_t i,
+                                               float &d2, uint32_t &j)
+{
+    bool cand = false;
+    d2 = 0.0f; j = 0u;
+    const float x = a.in.x[i], y = a.in.y[i], z = a.in.z[i];
+    const float px = xf_row(a.X.m + 0, x, y, z, 1.0f), py = xf_row(a.X.m + 4, x, y, z, 1.0f), pz = xf_row(a.X.m + 8, x, y, z, 1.0f);
+    float nqx = 0.0f, nqy = 0.0f, nqz = 0.0f;
+    if (CORR == 0) {
+        j = a.tgt_offset + i;
+        d2 = dist2(px, py, pz, tgt.x[j], tgt.y[j], tgt.z[j]);
+        cand = true;
+        if (gate_n) { nqx = tgt.nx[j]; nqy = tgt.ny[j]; nqz = tgt.nz[j]; }
+    } else if (CORR == 1) {
+        const unsigned long long b = a.best64[i];
+        cand = b != ~0ull;
+        d2 = __uint_as_float((uint32_t)(b >> 32));
+        j = (uint32_t)(b & 0xFFFFFFFFull);
+        if (cand && gate_n) { const float4 nq = tn[2 * (size_t)j + 1]; nqx = nq.x; nqy = nq.y; nqz = nq.z; }
+    } else {
+        const int32_t pos = a.pos_out[i];
+        cand = pos >= 0;
+        if (cand) {
+            j = (uint32_t)pos;
+            const float4 q = tn[2 * (size_t)pos];
+            d2 = dist2(px, py, pz, q.x, q.y, q.z);
+            if (gate_n) { const float4 nq = tn[2 * (size_t)pos + 1]; nqx = nq.x; nqy = nq.y; nqz = nq.z; }
+        }
+    }
+    if (cand && a.max_d2 > 0.0f && d2 > a.max_d2) cand = false;
+    if (cand && gate_n) {
+        const float nx = a.in.nx[i], ny = a.in.ny[i], nz = a.in.nz[i];
+        const float npx = xf_row(a.X.m + 0, nx, ny, nz, a.X.nrm_w), npy = xf_row(a.X.m + 4, nx, ny, nz, a.X.nrm_w),
+                    npz = xf_row(a.X.m + 8, nx, ny, nz, a.X.nrm_w);
+        if ((npx * nqx + npy * nqy) + npz * nqz < a.min_ndot) cand = false;
+    }
+    return cand;
+}
+
+// ---- one-to-one (symmicp_set_one_to_one) ---------------------------------------------------------
+// Every candidate claims its target with K = (d2 bits << 32 | caller row); the table keeps the minimum.  An integer minimum does not
+// depend on the order of the claims, so the winners are reproducible bit for bit; ties in d2 go to the lowest caller row.
+__device__ __forceinline__ unsigned long long claim_key(uint32_t d2_bits, uint32_t row) { return ((unsigned long long)d2_bits << 32) | row; }
+__device__ __forceinline__ uint32_t caller_row(const PassArgs &a, uint32_t i) { return a.uniq_order ? a.uniq_order[i] : i; }
+
+// One claim.  A claim that the entry already beats cannot win -- the entry only falls -- so it is read first; a stale read costs one
+// atomic more, never a winner.
+__device__ __forceinline__ void claim(unsigned long long *table, uint32_t j, unsigned long long key)
+{
+    if (__hip_atomic_load(&table[j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) > key) atomicMin(&table[j], key);
+}
+
+// The claims of one wave.  Source points outside the overlap pair with the target's boundary, and neighbours in the share's Morton
+// order pair with the same few boundary points: such a wave would send most of its 64 atomics to a handful of addresses, where they
+// serialise.  So lanes that hold the same target combine first: up to eight rounds of (first live lane's target, ballot, minimum of the
+// keys over those lanes, one claim).  A round whose leader is alone ends the rounds -- a wave inside the overlap, whose targets are
+// mostly distinct, pays one round -- and whatever is left claims on its own.  `valid` may differ per lane; the call is wave-uniform.
+__device__ __forceinline__ void claim_wave(unsigned long long *table, uint32_t j, unsigned long long key, bool valid)
+{
+    const int lane = threadIdx.x & 63;
+    unsigned long long live = __ballot(valid);
+#pragma unroll 1
+    for (int r = 0; r < 8 && live; r++) {
+        const int lead = __ffsll((long long)live) - 1;
+        const uint32_t jl = (uint32_t)__shfl((int)j, lead, 64);
+        const bool mine = valid && j == jl;
+        const unsigned long long same = __ballot(mine);
+        if (__popcll(same) == 1) break;
+        unsigned long long v = mine ? key : ~0ull;
+#pragma unroll
+        for (int off = 32; off >= 1; off >>= 1) {
+            const unsigned long long o = __shfl_xor(v, off, 64);
+            v = o < v ? o : v;
+        }
+        if (lane == lead) claim(table, jl, v);
+        if (mine) valid = false;
+        live &= ~same;
+    }
+    if (valid) claim(table, j, key);
+}
+
+template <int CORR>
+__global__ __launch_bounds__(kSelThreads) void k_unique_claim(PassArgs a, CloudSoA tgt, const float4 *__restrict__ tn)
+{
+    const bool gate_n = a.min_ndot > -1.0f;
+    const uint32_t stride = gridDim.x * kSelThreads;
+    // (whole waves stay in the loop: claim_wave is wave-uniform)
+    for (uint32_t base = blockIdx.x * kSelThreads; base < a.n; base += stride) {
+        const uint32_t i = base + threadIdx.x;
+        bool cand = false;
+        float d2 = 0.0f;
+        uint32_t j = 0u;
+        unsigned long long key = ~0ull;
+        if (i < a.n) {
+            cand = pair_candidate<CORR>(a, tgt, tn, gate_n, i, d2, j) && j < a.uniq_n_t;
+            if (cand) key = claim_key(__float_as_uint(d2), caller_row(a, i));
+        }
+        claim_wave(a.uniq_table, j, key, cand);
+    }
+}
+
+// UNIQ: the table of k_unique_claim is complete: a candidate that did not win its target gets the sentinel and leaves the population
+// (SEL_NC and the histogram); SEL_GATED counts the candidates either way.
+template <int CORR, bool UNIQ>
 __global__ __launch_bounds__(kSelThreads) void k_trim_keys(PassArgs a, CloudSoA tgt, const float4 *__restrict__ tn)
 {
     __shared__ uint32_t h[kSelBins];
-    __shared__ uint32_t s_count;
-    if (threadIdx.x == 0) s_count = 0u;
+    __shared__ uint32_t s_count, s_gated;
+    if (threadIdx.x == 0) { s_count = 0u; s_gated = 0u; }
     hist_zero(h);
     const bool gate_n = a.min_ndot > -1.0f;
-    uint32_t mine = 0u;
+    uint32_t mine = 0u, gated = 0u;
     const uint32_t stride = gridDim.x * kSelThreads;
     // (whole waves stay in the loop: hist_add is wave-uniform)
     for (uint32_t base = blockIdx.x * kSelThreads; base < a.n; base += stride) {
@@ -88,43 +202,20 @@ __global__ __launch_bounds__(kSelThreads) void k_trim_keys(PassArgs a, CloudSoA 
         bool cand = false;
         float d2 = 0.0f;
         if (i < a.n) {
-            const float x = a.in.x[i], y = a.in.y[i], z = a.in.z[i];
-            const float px = xf_row(a.X.m + 0, x, y, z, 1.0f), py = xf_row(a.X.m + 4, x, y, z, 1.0f), pz = xf_row(a.X.m + 8, x, y, z, 1.0f);
-            float nqx = 0.0f, nqy = 0.0f, nqz = 0.0f;
-            if (CORR == 0) {
-                const uint32_t j = a.tgt_offset + i;
-                d2 = dist2(px, py, pz, tgt.x[j], tgt.y[j], tgt.z[j]);
-                cand = true;
-                if (gate_n) { nqx = tgt.nx[j]; nqy = tgt.ny[j]; nqz = tgt.nz[j]; }
-            } else if (CORR == 1) {
-                const unsigned long long b = a.best64[i];
-                cand = b != ~0ull;
-                d2 = __uint_as_float((uint32_t)(b >> 32));
-                if (cand && gate_n) { const float4 nq = tn[2 * (size_t)(uint32_t)(b & 0xFFFFFFFFull) + 1]; nqx = nq.x; nqy = nq.y; nqz = nq.z; }
-            } else {
-                const int32_t pos = a.pos_out[i];
-                cand = pos >= 0;
-                if (cand) {
-                    const float4 q = tn[2 * (size_t)pos];
-                    d2 = dist2(px, py, pz, q.x, q.y, q.z);
-                    if (gate_n) { const float4 nq = tn[2 * (size_t)pos + 1]; nqx = nq.x; nqy = nq.y; nqz = nq.z; }
-                }
-            }
-            if (cand && a.max_d2 > 0.0f && d2 > a.max_d2) cand = false;
-            if (cand && gate_n) {
-                const float nx = a.in.nx[i], ny = a.in.ny[i], nz = a.in.nz[i];
-                const float npx = xf_row(a.X.m + 0, nx, ny, nz, a.X.nrm_w), npy = xf_row(a.X.m + 4, nx, ny, nz, a.X.nrm_w),
-                            npz = xf_row(a.X.m + 8, nx, ny, nz, a.X.nrm_w);
-                if ((npx * nqx + npy * nqy) + npz * nqz < a.min_ndot) cand = false;
-            }
+            uint32_t j;
+            cand = pair_candidate<CORR>(a, tgt, tn, gate_n, i, d2, j);
+            gated += cand ? 1u : 0u;
+            if (UNIQ && cand) cand = j < a.uniq_n_t && a.uniq_table[j] == claim_key(__float_as_uint(d2), caller_row(a, i));
             a.trim_keys[i] = cand ? __float_as_uint(d2) : 0xFFFFFFFFu;
         }
         hist_add(h, sel_digit<0>(__float_as_uint(d2)), cand);
         mine += cand ? 1u : 0u;
     }
     if (mine) atomicAdd(&s_count, mine);
+    if (gated) atomicAdd(&s_gated, gated);
     hist_merge(h, a.trim_ws + SEL_STATE_WORDS);
     if (threadIdx.x == 0 && s_count) atomicAdd(a.trim_ws + SEL_NC, s_count);
+    if (threadIdx.x == 0 && s_gated) atomicAdd(a.trim_ws + SEL_GATED, s_gated);
 }
 
 // histogram of digit PASS over the keys whose earlier digits equal the prefix fixed so far (PASS 0: every key)
@@ -192,14 +283,14 @@ __global__ __launch_bounds__(kSelThreads) void k_select_scan(uint32_t *ws, float
         if (PASS == 2) {
             const uint32_t kept = ws[SEL_K0] - (k - before) + bins[j];
             ws[SEL_TAU] = prefix; ws[SEL_KEPT] = kept;
-            if (out_host) { out_host[0] = ws[SEL_NC]; out_host[1] = kept; out_host[2] = prefix; }
+            if (out_host) { out_host[0] = ws[SEL_NC]; out_host[1] = kept; out_host[2] = prefix; out_host[3] = ws[SEL_GATED]; }
         }
     }
     if (k == 0u && t == 0) {
         ws[SEL_K] = 0u;
         if (PASS == 2) {
             ws[SEL_TAU] = 0u; ws[SEL_KEPT] = 0u;
-            if (out_host) { out_host[0] = ws[SEL_NC]; out_host[1] = 0u; out_host[2] = 0u; }
+            if (out_host) { out_host[0] = ws[SEL_NC]; out_host[1] = 0u; out_host[2] = 0u; out_host[3] = ws[SEL_GATED]; }
         }
     }
 }
@@ -221,14 +312,80 @@ static void launch_select_tail(const uint32_t *keys, uint32_t n, uint32_t *ws, f
     hipLaunchKernelGGL(k_select_scan<2>, dim3(1), dim3(kSelThreads), 0, s, ws, rho, k_fixed, n, out_host);
 }
 
+// ---- tau without a fixed fraction -------------------------------------------------------------------
+// One-to-one alone: every non-sentinel key is kept (tau = +Inf: a candidate's d2 is never NaN for finite clouds and transforms).
+__global__ void k_reject_all(uint32_t *ws, uint32_t *out_host)
+{
+    const uint32_t nc = ws[SEL_NC];
+    ws[SEL_TAU] = 0x7F800000u; ws[SEL_KEPT] = nc;
+    if (out_host) { out_host[0] = nc; out_host[1] = nc; out_host[2] = 0x7F800000u; out_host[3] = ws[SEL_GATED]; }
+}
+
+// Median distance: the select (rho = 0.5) left the median in SEL_TAU; tau = f2 * med, one fp32 product.  Population 0: tau = 0.  A NaN
+// product (f2 overflowed to +Inf and med = 0) counts as +Inf: everything is kept.
+__global__ void k_median_tau(uint32_t *ws, float f2)
+{
+    const uint32_t med = ws[SEL_TAU];
+    float tau = ws[SEL_NC] ? f2 * __uint_as_float(med) : 0.0f;
+    if (tau != tau) tau = __uint_as_float(0x7F800000u);
+    ws[SEL_MED] = med; ws[SEL_TAU] = __float_as_uint(tau); ws[SEL_KEPT] = 0u;
+}
+
+// ... and the kept count: the keys <= tau (the sentinel is above every tau)
+__global__ __launch_bounds__(kSelThreads) void k_count_le(const uint32_t *__restrict__ keys, uint32_t n, uint32_t *ws)
+{
+    __shared__ uint32_t s_count;
+    if (threadIdx.x == 0) s_count = 0u;
+    __syncthreads();
+    const uint32_t tau = ws[SEL_TAU];
+    uint32_t mine = 0u;
+    const uint32_t stride = gridDim.x * kSelThreads;
+    for (uint32_t i = blockIdx.x * kSelThreads + threadIdx.x; i < n; i += stride) mine += keys[i] <= tau ? 1u : 0u;
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) mine += (uint32_t)__shfl_xor((int)mine, off, 64);
+    if ((threadIdx.x & 63) == 0 && mine) atomicAdd(&s_count, mine);
+    __syncthreads();
+    if (threadIdx.x == 0 && s_count) atomicAdd(ws + SEL_KEPT, s_count);
+}
+
+__global__ void k_reject_publish(const uint32_t *ws, uint32_t *out_host)
+{
+    out_host[0] = ws[SEL_NC]; out_host[1] = ws[SEL_KEPT]; out_host[2] = ws[SEL_TAU]; out_host[3] = ws[SEL_GATED];
+}
+
+template <bool UNIQ>
+static void launch_keys(const PassArgs &a, int corr, CloudSoA tgt, const float4 *tn, uint32_t nb, hipStream_t s)
+{
+    if (corr == SYMMICP_CORR_IDENTITY) hipLaunchKernelGGL((k_trim_keys<0, UNIQ>), dim3(nb), dim3(kSelThreads), 0, s, a, tgt, tn);
+    else if (corr == SYMMICP_CORR_BRUTE) hipLaunchKernelGGL((k_trim_keys<1, UNIQ>), dim3(nb), dim3(kSelThreads), 0, s, a, tgt, tn);
+    else hipLaunchKernelGGL((k_trim_keys<2, UNIQ>), dim3(nb), dim3(kSelThreads), 0, s, a, tgt, tn);
+}
+
+// The rejection steps of a pass, behind its search and in front of its accumulating kernel:
+//   one-to-one (a.uniq_table; never IDENTITY, whose pairs are one-to-one)   memset of the table, k_unique_claim
+//   keys                                                                    memset of the workspace, k_trim_keys
+//   tau: trim fraction            the select (5 launches), which publishes
+//        median factor            the select at rho = 0.5, k_median_tau, k_count_le, k_reject_publish
+//        neither                  k_reject_all
+// The table is reset by a memset every pass: 8 B per target point at the HBM roof, against a claim that gathers 32 B per source point.
 void launch_trim_select(const PassArgs &a, int corr, CloudSoA tgt, const float4 *tn, hipStream_t s)
 {
     hipMemsetAsync(a.trim_ws, 0, sizeof(uint32_t) * kTrimWsWords, s);
     const uint32_t nb = sel_blocks(a.n);
-    if (corr == SYMMICP_CORR_IDENTITY) hipLaunchKernelGGL(k_trim_keys<0>, dim3(nb), dim3(kSelThreads), 0, s, a, tgt, tn);
-    else if (corr == SYMMICP_CORR_BRUTE) hipLaunchKernelGGL(k_trim_keys<1>, dim3(nb), dim3(kSelThreads), 0, s, a, tgt, tn);
-    else hipLaunchKernelGGL(k_trim_keys<2>, dim3(nb), dim3(kSelThreads), 0, s, a, tgt, tn);
-    launch_select_tail(a.trim_keys, a.n, a.trim_ws, a.trim_rho, 0u, a.trim_host, s);
+    const bool uniq = a.uniq_table && corr != SYMMICP_CORR_IDENTITY;
+    if (uniq) {
+        hipMemsetAsync(a.uniq_table, 0xFF, sizeof(unsigned long long) * a.uniq_n_t, s);
+        if (corr == SYMMICP_CORR_BRUTE) hipLaunchKernelGGL(k_unique_claim<1>, dim3(nb), dim3(kSelThreads), 0, s, a, tgt, tn);
+        else hipLaunchKernelGGL(k_unique_claim<2>, dim3(nb), dim3(kSelThreads), 0, s, a, tgt, tn);
+        launch_keys<true>(a, corr, tgt, tn, nb, s);
+    } else launch_keys<false>(a, corr, tgt, tn, nb, s);
+    if (a.med_f2 > 0.0f) {
+        launch_select_tail(a.trim_keys, a.n, a.trim_ws, 0.5f, 0u, nullptr, s);
+        hipLaunchKernelGGL(k_median_tau, dim3(1), dim3(1), 0, s, a.trim_ws, a.med_f2);
+        hipLaunchKernelGGL(k_count_le, dim3(nb), dim3(kSelThreads), 0, s, a.trim_keys, a.n, a.trim_ws);
+        hipLaunchKernelGGL(k_reject_publish, dim3(1), dim3(1), 0, s, a.trim_ws, a.trim_host);
+    } else if (a.trim_rho < 1.0f) launch_select_tail(a.trim_keys, a.n, a.trim_ws, a.trim_rho, 0u, a.trim_host, s);
+    else hipLaunchKernelGGL(k_reject_all, dim3(1), dim3(1), 0, s, a.trim_ws, a.trim_host);
 }
 
 void launch_select_probe(const uint32_t *keys, uint32_t n, uint32_t k, uint32_t *ws, hipStream_t s)
@@ -237,5 +394,37 @@ void launch_select_probe(const uint32_t *keys, uint32_t n, uint32_t k, uint32_t 
     hipLaunchKernelGGL(k_select_hist<0>, dim3(sel_blocks(n)), dim3(kSelThreads), 0, s, keys, n, ws);
     launch_select_tail(keys, n, ws, 1.0f, k, nullptr, s);
 }
+
+// the claim and the winner test of the probe: the pass's claim_wave and key on rows given as arrays
+__global__ __launch_bounds__(kSelThreads) void k_probe_claim(const int32_t *__restrict__ tgt_row, const uint32_t *__restrict__ d2_bits, uint32_t n,
+                                                             unsigned long long *table, uint32_t n_t)
+{
+    const uint32_t stride = gridDim.x * kSelThreads;
+    for (uint32_t base = blockIdx.x * kSelThreads; base < n; base += stride) {
+        const uint32_t i = base + threadIdx.x;
+        const int32_t j = i < n ? tgt_row[i] : -1;
+        const bool cand = j >= 0 && (uint32_t)j < n_t;
+        claim_wave(table, cand ? (uint32_t)j : 0u, cand ? claim_key(d2_bits[i], i) : ~0ull, cand);
+    }
+}
+
+__global__ __launch_bounds__(kSelThreads) void k_probe_winner(const int32_t *__restrict__ tgt_row, const uint32_t *__restrict__ d2_bits, uint32_t n,
+                                                              const unsigned long long *__restrict__ table, uint32_t n_t, uint8_t *winner)
+{
+    const uint32_t stride = gridDim.x * kSelThreads;
+    for (uint32_t i = blockIdx.x * kSelThreads + threadIdx.x; i < n; i += stride) {
+        const int32_t j = tgt_row[i];
+        winner[i] = (j >= 0 && (uint32_t)j < n_t && table[j] == claim_key(d2_bits[i], i)) ? 1 : 0;
+    }
+}
+
+void launch_unique_probe(const int32_t *tgt_row, const uint32_t *d2_bits, uint32_t n, unsigned long long *table, uint32_t n_t,
+                         uint8_t *winner_out, hipStream_t s)
+{
+    hipMemsetAsync(table, 0xFF, sizeof(unsigned long long) * n_t, s);
+    hipLaunchKernelGGL(k_probe_claim, dim3(sel_blocks(n)), dim3(kSelThreads), 0, s, tgt_row, d2_bits, n, table, n_t);
+    hipLaunchKernelGGL(k_probe_winner, dim3(sel_blocks(n)), dim3(kSelThreads), 0, s, tgt_row, d2_bits, n, table, n_t, winner_out);
+}
+
 
 }  // namespace symmicp

@@ -182,8 +182,15 @@ struct PassArgs {
     // launchers run the keys and the select in front of it.  Null (the default): nothing is launched and the kernels are the untrimmed ones.
     uint32_t *trim_keys;                // [n] per share row: the candidate's d2 bits, 0xFFFFFFFF otherwise
     uint32_t *trim_ws;                  // [kTrimWsWords] the select's state and histograms
-    uint32_t *trim_host;                // host-mapped (n_c, kept, tau bits) of the pass
+    uint32_t *trim_host;                // host-mapped (the select's population, kept, tau bits, n_c) of the pass
     float trim_rho;
+    // The one-to-one and median-distance rejectors (symmicp_set_one_to_one / symmicp_set_median_factor) run through the same keys, the
+    // same select and the same T instantiations: a pass with any of the three has trim_keys set.
+    unsigned long long *uniq_table;     // one-to-one: [uniq_n_t] per target position the smallest claim (d2 bits << 32 | caller row); null: off
+    const uint32_t *uniq_order;         // ... share row -> caller row (null: the share is in caller order)
+    uint32_t uniq_n_t;                  // ... entries of the table
+    int32_t trim_uniq;                  // the accumulating kernel reads trim_keys[i] and drops the sentinel rows: losers of the claim
+    float med_f2;                       // median distance: factor * factor in fp32 (0: off): tau = med_f2 * the select's median
     // colored ICP (SYMMICP_MODE_COLOR; read by the kObjColor instantiations only)
     const float4 *tgt_color;            // per target point, in the order of tn (IDENTITY: of the planar target): (gradient xyz, intensity)
     const float *src_int;               // per share row: the source point's intensity
@@ -270,6 +277,10 @@ void launch_corr_out(const int32_t *pos, const unsigned long long *best64, const
 void launch_trim_select(const PassArgs &a, int corr, CloudSoA tgt, const float4 *tn, hipStream_t s);
 // test entry: the select alone on n keys, rank k (1-based); afterwards ws[kTrimTauWord] = the k-th smallest key, ws[4] = keys <= it
 void launch_select_probe(const uint32_t *keys, uint32_t n, uint32_t k, uint32_t *ws, hipStream_t s);
+// test entry: the one-to-one claim alone (k_unique_claim's claim_wave and the winner test) on n rows given as (target row, d2 bits), the row
+// being the array index; tgt_row < 0 or >= n_t: no pair.  table: [n_t] scratch; winner_out[i] = 1 where row i wins its target
+void launch_unique_probe(const int32_t *tgt_row, const uint32_t *d2_bits, uint32_t n, unsigned long long *table, uint32_t n_t,
+                         uint8_t *winner_out, hipStream_t s);
 
 void launch_identity_d2(const CloudSoA &in, const Affine &X, const CloudSoA &tgt, uint32_t tgt_offset, uint32_t n, float *d2, hipStream_t s);
 void launch_pairs_d2(const CloudSoA &in, const Affine &X, const int32_t *pos, const float4 *tq, uint32_t n_t, uint32_t n, float *d2, hipStream_t s);

@@ -118,6 +118,8 @@ EXPORTS = [
     "symmicp_ransac_config_default", "symmicp_ransac", "symmicp_ctx_ransac", "symmicp_ctx_ransac_hypotheses",
     "symmicp_ctx_index_info", "symmicp_ctx_index_arrays", "symmicp_ctx_source_share", "symmicp_ctx_radix_sort_probe", "symmicp_ctx_scan_probe",
     "symmicp_set_trim_fraction", "symmicp_get_trim_fraction", "symmicp_get_trim_state", "symmicp_ctx_select_probe",
+    "symmicp_set_one_to_one", "symmicp_get_one_to_one", "symmicp_set_median_factor", "symmicp_get_median_factor",
+    "symmicp_get_rejection_state", "symmicp_ctx_unique_probe",
     "symmicp_set_color_weight", "symmicp_get_color_weight", "symmicp_set_source_intensity", "symmicp_set_target_intensity",
     "symmicp_get_source_intensity", "symmicp_intensity_gradient", "symmicp_ctx_intensity_gradient", "symmicp_pcd_read_intensity",
 ]
@@ -230,6 +232,12 @@ def lib():
     L.symmicp_set_trim_fraction.argtypes = [vp, C.c_float]
     L.symmicp_get_trim_fraction.argtypes = [vp, fp]
     L.symmicp_get_trim_state.argtypes = [vp, u64p, u64p, fp]
+    L.symmicp_set_one_to_one.argtypes = [vp, C.c_int]
+    L.symmicp_get_one_to_one.argtypes = [vp, C.POINTER(C.c_int)]
+    L.symmicp_set_median_factor.argtypes = [vp, C.c_float]
+    L.symmicp_get_median_factor.argtypes = [vp, fp]
+    L.symmicp_get_rejection_state.argtypes = [vp, u64p, u64p, u64p, fp]
+    L.symmicp_ctx_unique_probe.argtypes = [vp, i32p, u32p, C.c_size_t, C.c_size_t, C.POINTER(C.c_uint8)]
     L.symmicp_ctx_select_probe.argtypes = [vp, u32p, C.c_size_t, C.c_uint64, u32p, u64p]
     L.symmicp_set_color_weight.argtypes = [vp, C.c_float]
     L.symmicp_get_color_weight.argtypes = [vp, fp]
@@ -745,6 +753,32 @@ class Engine:
         self._chk(self._L.symmicp_ctx_intensity_gradient(self._h, _fptr(xyz), 3, 1, _fptr(nrm), 3, 1, _fptr(it), 1, n, k, _fptr(g)))
         return g
 
+    def set_one_to_one(self, on):
+        """one-to-one rejection: of the source points paired with one target point only the closest is kept (ties: the lowest row);
+        takes effect at the next pass"""
+        self._chk(self._L.symmicp_set_one_to_one(self._h, 1 if on else 0))
+
+    def one_to_one(self):
+        on = C.c_int(0)
+        self._chk(self._L.symmicp_get_one_to_one(self._h, C.byref(on)))
+        return bool(on.value)
+
+    def set_median_factor(self, factor):
+        """median-distance rejection: every pass keeps the pairs with d <= factor x the median pair distance (0 = off, the default);
+        takes effect at the next pass"""
+        self._chk(self._L.symmicp_set_median_factor(self._h, float(factor)))
+
+    def median_factor(self):
+        f = C.c_float(0)
+        self._chk(self._L.symmicp_get_median_factor(self._h, C.byref(f)))
+        return f.value
+
+    def rejection_state(self):
+        """-> (n_c, n_u, kept, tau_d2 as np.float32) of the most recent pass; ERR_STATE if it ran neither one-to-one nor the median"""
+        nc, nu, kept, tau = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0), C.c_float(0)
+        self._chk(self._L.symmicp_get_rejection_state(self._h, C.byref(nc), C.byref(nu), C.byref(kept), C.byref(tau)))
+        return nc.value, nu.value, kept.value, np.float32(tau.value)
+
     def trim_state(self):
         """-> (candidates, kept, tau_d2 as np.float32) of the most recent pass; ERR_STATE if it was not trimmed"""
         nc, kept, tau = C.c_uint64(0), C.c_uint64(0), C.c_float(0)
@@ -1065,6 +1099,18 @@ class Engine:
         self._chk(self._L.symmicp_ctx_select_probe(self._h, a.ctypes.data_as(C.POINTER(C.c_uint32)), a.size, int(k), C.byref(kth), C.byref(nle)))
         return kth.value, nle.value
 
+    def unique_probe(self, tgt_row, d2_bits, n_t):
+        """the one-to-one claim on host arrays (symmicp_ctx_unique_probe): row i claims target row tgt_row[i] (< 0: no pair) with the
+        key (d2_bits[i] << 32 | i) -> bool array, True where row i wins its target"""
+        r = np.ascontiguousarray(np.asarray(tgt_row, np.int32).reshape(-1))
+        d = np.ascontiguousarray(np.asarray(d2_bits, np.uint32).reshape(-1))
+        if r.size != d.size:
+            raise ValueError("unique_probe: tgt_row and d2_bits differ in length")
+        w = np.zeros(r.size, np.uint8)
+        self._chk(self._L.symmicp_ctx_unique_probe(self._h, r.ctypes.data_as(C.POINTER(C.c_int32)), d.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                                   r.size, int(n_t), w.ctypes.data_as(C.POINTER(C.c_uint8))))
+        return w.astype(bool)
+
     def scan_probe(self, data):
         """the build's exclusive scan on a host array (symmicp_ctx_scan_probe) -> new uint32 array"""
         d = np.array(data, np.uint32).reshape(-1)
@@ -1107,6 +1153,8 @@ class MyICP:
         self._loss = (LOSS_NONE, 0.0)
         self._gicp_eps = None
         self._trim = 1.0
+        self._one_to_one = False
+        self._median = 0.0
         self._color_weight = None
         self.intensity_src = self.intensity_tgt = None
         self._levels = []
@@ -1188,6 +1236,14 @@ class MyICP:
         """trimmed ICP for the next align, every voxel level included (see Engine.set_trim_fraction; 1 = off)"""
         self._trim = float(fraction)
 
+    def setOneToOne(self, on):
+        """one-to-one rejection for the next align, every voxel level included (see Engine.set_one_to_one)"""
+        self._one_to_one = bool(on)
+
+    def setMedianFactor(self, factor):
+        """median-distance rejection for the next align, every voxel level included (see Engine.set_median_factor; 0 = off)"""
+        self._median = float(factor)
+
     def setRobustLoss(self, loss, scale):
         """robust loss of the next align (see Engine.set_robust_loss)"""
         self._loss = (loss_code(loss), float(scale))
@@ -1253,6 +1309,10 @@ class MyICP:
                 e.set_gicp_epsilon(self._gicp_eps)
             if self._trim != 1.0:
                 e.set_trim_fraction(self._trim)
+            if self._one_to_one:
+                e.set_one_to_one(True)
+            if self._median != 0.0:
+                e.set_median_factor(self._median)
             if self._color_weight is not None:
                 e.set_color_weight(self._color_weight)
             e.set_target(self.cloud_tgt, self.normals_tgt)
@@ -1277,6 +1337,10 @@ class MyICP:
                 e.set_gicp_epsilon(self._gicp_eps)
             if self._trim != 1.0:
                 e.set_trim_fraction(self._trim)
+            if self._one_to_one:
+                e.set_one_to_one(True)
+            if self._median != 0.0:
+                e.set_median_factor(self._median)
             X = guess
             if self._global is not None and guess is None:
                 X = self._global_init(e)

@@ -59,6 +59,12 @@ public:
 	// overlap only in part.  Applies to single-level runs and to every level of setVoxelLevels; checked by align(), which returns
 	// SYMMICP_ERR_ARG unless 0 < fraction <= 1, and for a fraction below 1 with SYMMICP_MODE_QUIRKS
 	void setTrimFraction(float fraction) { trim_fraction_ = fraction; }
+	// one-to-one and median-distance rejection (symmicp_set_one_to_one / symmicp_set_median_factor; default off / 0 = off): of the source
+	// points paired with one target point only the closest is kept; pairs farther than factor x the median pair distance are dropped.
+	// Apply like setTrimFraction, every level of setVoxelLevels included; checked by align(), which returns SYMMICP_ERR_ARG with
+	// SYMMICP_MODE_QUIRKS, for a factor that is neither 0 nor finite and > 0, and for a factor > 0 with a trim fraction below 1
+	void setOneToOne(bool on) { one_to_one_ = on; }
+	void setMedianFactor(float factor) { median_factor_ = factor; }
 	// Colored ICP (SYMMICP_MODE_COLOR): one scalar intensity per point of each cloud, n = the cloud's count, set after setInput* /
 	// LoadCloud (LoadCloud keeps the intensities of files that carry an `intensity` or `rgb` field; setInput* drops the cloud's).
 	// align() estimates the target's intensity gradient itself (symmicp_ctx_intensity_gradient, k = 10).  In COLOR align() returns
@@ -129,6 +135,8 @@ private:
 	float loss_scale_;
 	float gicp_eps_;
 	float trim_fraction_;
+	bool one_to_one_;
+	float median_factor_;
 	float max_corr_dist_;
 	float color_weight_ = 0.968f;
 	std::vector<float> src_int_, tgt_int_;

@@ -234,6 +234,42 @@ int symmicp_get_trim_fraction(const symmicp_ctx *ctx, float *fraction);
 /* n_c, the kept count and tau of the most recent pass (each pointer may be NULL); SYMMICP_ERR_STATE if no pass has run or that pass
  * was not trimmed */
 int symmicp_get_trim_state(const symmicp_ctx *ctx, uint64_t *candidates, uint64_t *kept, float *tau_d2);
+/* One-to-one and median-distance rejection (PCL's CorrespondenceRejectorOneToOne and CorrespondenceRejectorMedianDistance): two more
+ * rules for clouds that overlap only in part, neither of which needs to know the overlap.  Both are pure functions of the pass,
+ * reproducible bit for bit, and off by default; with both off nothing new is launched and every result is bit for bit what it is
+ * without them.
+ *   Candidates  as for trimming: the pairs that exist (a target row >= 0) and pass max_corr_dist, then min_normal_dot; n_c = their
+ *               number.  d2 = the fp32 (dx*dx + dy*dy) + dz*dz at the moved position, the bits the accumulating kernels evaluate.
+ *   One-to-one  (symmicp_set_one_to_one, on != 0).  The key of candidate i is K(i) = ((uint64)bits(d2_i) << 32) | r_i with r_i the source
+ *               point's row in the caller's numbering.  The winner of target row j is the candidate paired with j that has the smallest
+ *               K: the closest one, ties in d2 going to the lowest caller row.  A candidate survives iff it is the winner of its target;
+ *               n_u = the number of survivors = the number of distinct target rows among the candidates.  A gated pair claims nothing:
+ *               the gates come first.  SYMMICP_CORR_IDENTITY pairs are one-to-one as they are: the option is accepted there, launches
+ *               nothing and n_u = n_c.
+ *   Median      (symmicp_set_median_factor; 0 = off, the default; else finite and > 0, otherwise SYMMICP_ERR_ARG and the factor set
+ *               before stays).  Over the population below, of size n: med = the k-th smallest d2 with k = ceil(0.5 n), the threshold of a
+ *               trim fraction 0.5; f2 = factor * factor and tau = f2 * med, two unfused fp32 products.  A pair is kept iff
+ *               bits(d2) <= bits(tau); tau = +Inf keeps all (so does the NaN of f2 = +Inf times med = 0, which counts as +Inf).  n == 0:
+ *               tau is reported as 0 and nothing is kept.
+ *   Order       the gates, then one-to-one, then the quantile rule (trim fraction or median), whose population is the one-to-one
+ *               survivors when one-to-one is on, else the candidates.  A trim fraction below 1 together with a median factor > 0 is
+ *               refused: whichever setter comes second returns SYMMICP_ERR_ARG.  With one-to-one alone every survivor is kept and tau is
+ *               reported as +Inf.
+ *   Record      the ordinary one over the kept set, as for trimming: slots 33, 34, 36 and 37 count kept pairs only, a robust loss weights
+ *               the kept pairs, and symmicp_get_correspondences reports every rejected row as -1.
+ * Scope as for trimming: all symmicp_corr values; every mode but QUIRKS, which refuses both options with SYMMICP_ERR_ARG (and
+ * symmicp_set_config refuses to switch such a context into QUIRKS); nranks > 1 is SYMMICP_ERR_STATE in both directions (the claim table
+ * would need a minimum over all ranks); symmicp_align runs every iteration in the host loop, and a TREE pass that rejects never skips
+ * its tree walk.  Both setters take effect at the next pass and may be called between symmicp_step calls.  On the device: a claim of
+ * target rows by 64-bit integer minimum (order-independent), then the keys and the radix select of trimming. */
+int symmicp_set_one_to_one(symmicp_ctx *ctx, int on);
+int symmicp_get_one_to_one(const symmicp_ctx *ctx, int *on);
+int symmicp_set_median_factor(symmicp_ctx *ctx, float factor);
+int symmicp_get_median_factor(const symmicp_ctx *ctx, float *factor);
+/* n_c, n_u (= n_c when one-to-one is off), the kept count and tau of the most recent pass (each pointer may be NULL);
+ * SYMMICP_ERR_STATE if no pass has run or that pass ran neither of these two rejectors.  symmicp_get_trim_state keeps working for
+ * trimmed passes; its `candidates` is the select's population (n_u with one-to-one on). */
+int symmicp_get_rejection_state(const symmicp_ctx *ctx, uint64_t *gated, uint64_t *unique, uint64_t *kept, float *tau_d2);
 /* the weight the kernels give a pair of residual r (the same fp32 source); NaN for an unknown loss, or for a scale that
  * is not finite and > 0 with loss != NONE; 1 for SYMMICP_LOSS_NONE */
 float symmicp_robust_weight(int loss, float scale, float r);
@@ -385,6 +421,10 @@ int symmicp_ctx_scan_probe(symmicp_ctx *ctx, uint32_t *data, size_t n);
 /* the trimmed pass's exact radix select on a host array: *kth_out = the k-th smallest key (1 <= k <= n, n < 2^31), *n_le_out = the
  * number of keys <= it.  Same stream and scratch arena; the context's trim fraction and trim state stay as they were. */
 int symmicp_ctx_select_probe(symmicp_ctx *ctx, const uint32_t *keys, size_t n, uint64_t k, uint32_t *kth_out, uint64_t *n_le_out);
+/* the one-to-one claim on host arrays: row i (the array index is the caller row) claims target row tgt_row[i] with the key
+ * (d2_bits[i] << 32 | i); tgt_row[i] < 0 (or >= n_t): no pair.  winner_out[i] = 1 iff row i wins its target.  n, n_t < 2^31.  Same
+ * stream and scratch arena; the context's clouds, pairs, options and states stay as they were. */
+int symmicp_ctx_unique_probe(symmicp_ctx *ctx, const int32_t *tgt_row, const uint32_t *d2_bits, size_t n, size_t n_t, uint8_t *winner_out);
 
 /* ---- normals pre-step (replaces MyICP::estimateNormals, myicp.cpp:152-172: PCL NormalEstimation,
  * setKSearch(10), viewpoint (0,0,0)).  Exact k-NN (the point itself included) + PCA on the GPU.
