@@ -19,6 +19,8 @@
 //     --one-to-one             of the source points paired with one target point only the closest is kept (not with --mode quirks)
 //     --median-factor F        drop pairs farther apart than F times the median pair distance, F > 0 (default 0: off; not with --trim
 //                              below 1, not with --mode quirks)
+//     --reciprocal             keep a pair only if the source point is also the nearest source point of its target point (implies
+//                              --one-to-one; needs --corr tree, not with --mode quirks)
 //     --scale LEAF:ITERS[:MAXDIST]   one level of a coarse-to-fine alignment (repeat it, coarse first): both clouds
 //                              voxel-downsampled with edge LEAF (0: as given), at most ITERS iterations, pairs farther than
 //                              MAXDIST dropped (default 0: none); each level starts from the one before.  Needs --corr tree
@@ -47,7 +49,7 @@
 static int usage(const char *argv0, const char *complaint)
 {
     std::fprintf(stderr, "%s\nusage: %s [--mode quirks|paper|plane|gicp|color] [--color-weight L] [--corr identity|tree] [--iters N] [--threshold D] [--loss none|huber|tukey|cauchy|gm]"
-                 " [--loss-scale S] [--gicp-epsilon E] [--max-dist D] [--trim F] [--one-to-one] [--median-factor F] [--scale LEAF:ITERS[:MAXDIST]]... [--init global --fpfh-radius R --ransac-dist D [--ransac-iters H] [--seed S] [--init-voxel L]] [--out file.pcd] [--quiet] [source.pcd target.pcd]\n",
+                 " [--loss-scale S] [--gicp-epsilon E] [--max-dist D] [--trim F] [--one-to-one] [--reciprocal] [--median-factor F] [--scale LEAF:ITERS[:MAXDIST]]... [--init global --fpfh-radius R --ransac-dist D [--ransac-iters H] [--seed S] [--init-voxel L]] [--out file.pcd] [--quiet] [source.pcd target.pcd]\n",
                  complaint, argv0);
     return 64;
 }
@@ -67,7 +69,7 @@ int main(int argc, char **argv)
     bool color = false, have_color_weight = false;
     float color_weight = 0.f;
     float trim = 1.f;
-    bool one_to_one = false;
+    bool one_to_one = false, reciprocal = false;
     float median_factor = 0.f;
     std::vector<MyICP::VoxelLevel> levels;
     bool init_global = false, have_init_option = false;
@@ -141,6 +143,8 @@ int main(int argc, char **argv)
             if (end == v || *end || !(trim > 0.f) || trim > 1.f) return usage(argv[0], "--trim needs a fraction F with 0 < F <= 1");
         } else if (a == "--one-to-one") {
             one_to_one = true;
+        } else if (a == "--reciprocal") {
+            reciprocal = true;
         } else if (a == "--median-factor") {
             char *end = nullptr;
             const char *v = value("--median-factor");
@@ -208,6 +212,11 @@ int main(int argc, char **argv)
         if (median_factor > 0.f && trim < 1.f) return usage(argv[0], "--median-factor and --trim below 1 exclude each other");
         icp.setOneToOne(one_to_one);
         icp.setMedianFactor(median_factor);
+    }
+    if (reciprocal) {
+        if (quirks) return usage(argv[0], "--reciprocal needs --mode paper, plane, gicp or color (quirks is the reference as written)");
+        if (!tree) return usage(argv[0], "--reciprocal needs --corr tree (identity pairs were never searched)");
+        icp.setReciprocalCorrespondences(true);
     }
     if (!levels.empty()) {
         if (!tree) return usage(argv[0], "--scale needs --corr tree (identity pairing cannot pair clouds of different sizes)");

@@ -180,6 +180,7 @@ extern "C++" void forget_source(symmicp_ctx *c)
     c->n_loc = c->n_s_total = c->src_off = 0;
     c->src_no_normals = false;
     c->have_src_int = false;
+    drop_reverse_index(c->src_ix, false);
 }
 
 static void free_source(symmicp_ctx *c)
@@ -203,6 +204,7 @@ void symmicp_destroy(symmicp_ctx *c)
     hipFree(c->partials); hipFree(c->d_sums); hipFree(c->ticket); hipFree(c->arena.base); hipFree(c->keep.base);
     hipFree(c->trim_keys); hipFree(c->trim_ws); hipFree(c->uniq_table);
     hipFree(c->tgt_color); hipFree(c->src_int);
+    drop_reverse_index(c->src_ix, true);
     if (c->h_sums) hipHostFree(c->h_sums);
     hipFree(c->d_loop);
     if (c->h_loop) hipHostFree(c->h_loop);
@@ -228,6 +230,10 @@ int symmicp_set_config(symmicp_ctx *c, const symmicp_config *cfg)
         return fail(c, SYMMICP_ERR_ARG, "QUIRKS takes no trim fraction below 1 (set 1 first)");
     if (cfg->mode == SYMMICP_MODE_QUIRKS && (c->one_to_one || c->med_factor > 0.0f))
         return fail(c, SYMMICP_ERR_ARG, "QUIRKS takes no one-to-one or median-distance rejector (switch them off first)");
+    if (c->reciprocal && cfg->mode == SYMMICP_MODE_QUIRKS)
+        return fail(c, SYMMICP_ERR_ARG, "QUIRKS takes no reciprocal correspondences (switch them off first)");
+    if (c->reciprocal && cfg->corr == SYMMICP_CORR_IDENTITY)
+        return fail(c, SYMMICP_ERR_ARG, "identity pairs were never searched: no reciprocal correspondences (switch them off first)");
     if (cfg->mode == SYMMICP_MODE_COLOR && c->nranks > 1)
         return fail(c, SYMMICP_ERR_STATE, "SYMMICP_MODE_COLOR runs on single-rank contexts only");
     if (c->src_no_normals && cfg->mode != SYMMICP_MODE_PLANE)
@@ -240,6 +246,7 @@ int symmicp_set_config(symmicp_ctx *c, const symmicp_config *cfg)
     c->begun = false;
     c->trim_valid = false;
     c->rej_valid = c->rej_new = false;
+    c->recip_valid = false;
     return SYMMICP_OK;
 }
 
@@ -343,6 +350,46 @@ int symmicp_get_rejection_state(const symmicp_ctx *c, uint64_t *gated, uint64_t 
     if (unique) *unique = c->rej_unique;
     if (kept) *kept = c->trim_kept;
     if (tau_d2) std::memcpy(tau_d2, &c->trim_tau, sizeof(float));
+    return SYMMICP_OK;
+}
+
+// ---- reciprocal correspondences ---------------------------------------------------------------------
+int symmicp_set_reciprocal(symmicp_ctx *c, int on)
+{
+    if (!c) return SYMMICP_ERR_ARG;
+    if (on && c->cfg.mode == SYMMICP_MODE_QUIRKS) return fail(c, SYMMICP_ERR_ARG, "QUIRKS takes no reciprocal correspondences");
+    if (on && c->cfg.corr == SYMMICP_CORR_IDENTITY) return fail(c, SYMMICP_ERR_ARG, "identity pairs were never searched: no reciprocal correspondences");
+    if (on && c->nranks > 1) return fail(c, SYMMICP_ERR_STATE, "reciprocal correspondences need the claim and the source index over all ranks: single-rank contexts only");
+    c->reciprocal = on != 0;
+    return SYMMICP_OK;
+}
+
+int symmicp_get_reciprocal(const symmicp_ctx *c, int *on)
+{
+    if (!c || !on) return SYMMICP_ERR_ARG;
+    *on = c->reciprocal ? 1 : 0;
+    return SYMMICP_OK;
+}
+
+int symmicp_get_reciprocal_state(const symmicp_ctx *c, uint64_t *claimed, uint64_t *reciprocal)
+{
+    if (!c) return SYMMICP_ERR_ARG;
+    if (!c->begun || !c->recip_valid) return SYMMICP_ERR_STATE;      // (const context: no message)
+    if (claimed) *claimed = c->recip_claimed;
+    if (reciprocal) *reciprocal = c->recip_n;
+    return SYMMICP_OK;
+}
+
+// (include/symmicp.h has the definition: fp64 from the fp32 entries -- every product is exact there -- one rounding to fp32 per entry)
+int symmicp_inverse_rigid(const float X16[16], float out12[12])
+{
+    if (!X16 || !out12) return SYMMICP_ERR_ARG;
+    const double t0 = X16[3], t1 = X16[7], t2 = X16[11];
+    for (int r = 0; r < 3; r++) {
+        const double a = X16[r], b = X16[4 + r], d = X16[8 + r];
+        out12[4 * r + 0] = X16[r]; out12[4 * r + 1] = X16[4 + r]; out12[4 * r + 2] = X16[8 + r];
+        out12[4 * r + 3] = (float)(-((a * t0 + b * t1) + d * t2));
+    }
     return SYMMICP_OK;
 }
 
@@ -741,6 +788,62 @@ static int build_index(symmicp_ctx *c, const CloudSoA &cl, uint32_t n, bool want
     return SYMMICP_OK;
 }
 
+extern "C++" void drop_reverse_index(ReverseIndex &ri, bool release)
+{
+    for (void *p : ri.extra) hipFree(p);
+    ri.extra.clear();
+    ri.keep.off = 0;
+    ri.ix = TargetIndex{};
+    ri.valid = false;
+    if (release) { hipFree(ri.keep.base); ri.keep = Arena{}; }
+}
+
+// The source index of reciprocal passes: build_index as the k-NN path calls it (no grid; leaves of 8 points whatever the target looks
+// like and whatever SYMMICP_OCT_LEAF says), with the keep-arena swapped for ri's for the length of the build.  The pair records (tn) are not needed: they go to the scratch
+// arena.  Persistent: tq 16 B, the octree ~64 B and the run tree ~5 B per point.
+extern "C++" int build_reverse_index(symmicp_ctx *c, const CloudSoA &cl, uint32_t n, const uint32_t *labels, ReverseIndex &ri)
+{
+    drop_reverse_index(ri, false);
+    const size_t want = (size_t)n * 96 + ((size_t)4 << 20);
+    if (ri.keep.cap < want) {
+        hipFree(ri.keep.base);
+        ri.keep = Arena{};
+        if (hipMalloc((void **)&ri.keep.base, want) == hipSuccess) ri.keep.cap = want;
+        else (void)hipGetLastError();      // every keep_alloc then falls back to its own hipMalloc
+    }
+    arena_begin(c->arena, (size_t)n * 128 + ((size_t)1 << 20));
+    const bool surf0 = c->target_surface_like;
+    const int leaf0 = c->sw.oct_leaf;
+    c->target_surface_like = false;
+    c->sw.oct_leaf = 0;                   // (SYMMICP_OCT_LEAF tunes the target's octree for the packet search: not this one)
+    std::swap(c->keep, ri.keep);
+    std::swap(c->keep_extra, ri.extra);
+    auto body = [&]() -> int {
+        float4 *tq = nullptr, *boxes = nullptr, *onodes = nullptr;
+        uint2 *cells = nullptr;
+        DevBuf<float4> tn;
+        HIP_TRY(c, keep_alloc(c, (void **)&tq, sizeof(float4) * ((size_t)n + 8)));
+        HIP_TRY(c, hipMemsetAsync(tq + n, 0, sizeof(float4) * 8, c->stream));
+        HIP_TRY(c, tn.alloc_temp(c->arena, 2 * (size_t)n));
+        TargetIndex ix{};
+        int st = build_index(c, cl, n, /*want_grid=*/false, tq, tn.p, &boxes, &cells, &ix, nullptr, nullptr, &onodes);
+        if (st != SYMMICP_OK) return st;
+        launch_relabel_tq(tq, n, labels, c->stream);
+        HIP_TRY(c, hipStreamSynchronize(c->stream));      // (tn is about to go out of scope)
+        HIP_TRY(c, hipGetLastError());
+        ri.ix = ix;
+        return SYMMICP_OK;
+    };
+    const int st = body();
+    std::swap(c->keep, ri.keep);
+    std::swap(c->keep_extra, ri.extra);
+    c->target_surface_like = surf0;
+    c->sw.oct_leaf = leaf0;
+    if (st != SYMMICP_OK) { (void)hipStreamSynchronize(c->stream); drop_reverse_index(ri, false); return st; }
+    ri.valid = true;
+    return SYMMICP_OK;
+}
+
 int symmicp_set_target(symmicp_ctx *c, const float *xyz, size_t xr, size_t xc, const float *nrm, size_t nr, size_t nc, size_t n)
 {
     if (!c) return SYMMICP_ERR_ARG;
@@ -815,6 +918,7 @@ int symmicp_set_source(symmicp_ctx *c, const float *xyz, size_t xr, size_t xc, c
     c->begun = false;
     c->trim_valid = false;
     c->rej_valid = c->rej_new = false;
+    c->recip_valid = false;
     // This rank's share is a contiguous block of the CALLER's rows, and only those rows are uploaded and sorted: set_source costs
     // 1/nranks of the single-GPU call on every rank (round 1 uploaded and sorted the whole cloud on every rank and kept a
     // slice of the global Morton order).  Any partition of the source is exact -- queries are independent given the

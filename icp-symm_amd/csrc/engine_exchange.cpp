@@ -65,6 +65,7 @@ int symmicp_comm_init_rank(symmicp_ctx *c, int nranks, int rank, const void *uid
     if (c->src0_block) return fail(c, SYMMICP_ERR_STATE, "attach the communicator before symmicp_set_source");
     if (nranks > 1 && c->trim_frac < 1.0f) return fail(c, SYMMICP_ERR_STATE, "a trimming context (symmicp_set_trim_fraction below 1) cannot be sharded: the threshold is a quantile over all ranks");
     if (nranks > 1 && (c->one_to_one || c->med_factor > 0.0f)) return fail(c, SYMMICP_ERR_STATE, "a context with the one-to-one or the median-distance rejector cannot be sharded: the claim and the median span all ranks");
+    if (nranks > 1 && c->reciprocal) return fail(c, SYMMICP_ERR_STATE, "a context with reciprocal correspondences cannot be sharded: the claim and the source index span all ranks");
     if (nranks > 1 && c->cfg.mode == SYMMICP_MODE_COLOR) return fail(c, SYMMICP_ERR_STATE, "a SYMMICP_MODE_COLOR context cannot be sharded");
     // a 1-rank communicator is legal RCCL; it is only built on request (exercises the RCCL path on one GPU)
     if (nranks == 1 && !c->sw.force_comm) { c->nranks = 1; c->rank = 0; return SYMMICP_OK; }
@@ -93,6 +94,7 @@ int symmicp_comm_init_shm(symmicp_ctx *c, int nranks, int rank, const char *job_
     if (c->src0_block) return fail(c, SYMMICP_ERR_STATE, "attach the exchange before symmicp_set_source");
     if (nranks > 1 && c->trim_frac < 1.0f) return fail(c, SYMMICP_ERR_STATE, "a trimming context (symmicp_set_trim_fraction below 1) cannot be sharded: the threshold is a quantile over all ranks");
     if (nranks > 1 && (c->one_to_one || c->med_factor > 0.0f)) return fail(c, SYMMICP_ERR_STATE, "a context with the one-to-one or the median-distance rejector cannot be sharded: the claim and the median span all ranks");
+    if (nranks > 1 && c->reciprocal) return fail(c, SYMMICP_ERR_STATE, "a context with reciprocal correspondences cannot be sharded: the claim and the source index span all ranks");
     if (nranks > 1 && c->cfg.mode == SYMMICP_MODE_COLOR) return fail(c, SYMMICP_ERR_STATE, "a SYMMICP_MODE_COLOR context cannot be sharded");
     if (c->comm || c->shm.slots) return fail(c, SYMMICP_ERR_STATE, "a communicator is already attached");
     std::string name = std::string("/symmicp_") + job_name;

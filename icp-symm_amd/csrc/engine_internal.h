@@ -135,6 +135,16 @@ struct IndexNotes {
     uint32_t nblocks = 0, ctop_len = 0;        // occupied super-cell blocks of the cell table, length of ctop
 };
 
+// An index with storage of its own, for the reverse search of reciprocal passes: build_index allocates through the context's keep-arena,
+// which belongs to the target (set_target, the k-NN, radius and FPFH entries rewind it), so build_reverse_index points it at this one
+// for the length of the build.
+struct ReverseIndex {
+    Arena keep;
+    std::vector<void *> extra;
+    TargetIndex ix{};
+    bool valid = false;
+};
+
 struct symmicp_ctx {
     Switches sw;                     // environment switches as they stood at symmicp_create
     Arena arena;                     // temporaries of one public call
@@ -170,6 +180,15 @@ struct symmicp_ctx {
     size_t uniq_table_cap = 0;
     bool rej_valid = false, rej_new = false;
     uint32_t rej_gated = 0, rej_unique = 0;
+    // reciprocal correspondences (symmicp_set_reciprocal): the index over the original source (src_ix, built by the first reciprocal pass
+    // after a set_source, dropped by the next one), what the pass's launcher reads (recip_args: the index and the inverse of c->X), and
+    // n_u / n_r of the most recent pass (symmicp_get_reciprocal_state; recip_valid: that pass was reciprocal)
+    bool reciprocal = false;
+    ReverseIndex src_ix;
+    uint64_t src_ix_builds = 0;      // builds of src_ix by passes since symmicp_create (symmicp_ctx_reciprocal_info: tests)
+    RecipArgs recip_args{};
+    bool recip_valid = false;
+    uint32_t recip_claimed = 0, recip_n = 0;
     int device = 0;
     hipStream_t stream = nullptr;
     std::string err;
@@ -315,6 +334,10 @@ inline int resolved_apply(const symmicp_config &c)
 void free_target(symmicp_ctx *c);
 void forget_source(symmicp_ctx *c);
 void flush_events(symmicp_ctx *c);
+// the octree over cl (n points, a planar cloud in device memory) into ri's own storage, its tq relabelled through labels (device,
+// [n]; null: the row).  Rewinds the context's scratch arena.  release: back to the state before the first build (the storage is freed).
+int build_reverse_index(symmicp_ctx *c, const CloudSoA &cl, uint32_t n, const uint32_t *labels, ReverseIndex &ri);
+void drop_reverse_index(ReverseIndex &ri, bool release);
 // engine_exchange.cpp
 void shm_close(symmicp_ctx *c);
 int shm_exchange(symmicp_ctx *c, double *rec);      // rec[40]: this rank's record in, the sum over ranks out

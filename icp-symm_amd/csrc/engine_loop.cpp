@@ -6,8 +6,9 @@ extern "C" {
 
 // ---- one pass over the source share ------------------------------------------------------------
 // The rejectors of a pass (symmicp.h: trim fraction, one-to-one, median distance).  Identity pairs are one-to-one as they are: the option
-// launches nothing there.
-static bool pass_claims(const symmicp_ctx *c) { return c->one_to_one && c->cfg.corr != SYMMICP_CORR_IDENTITY; }
+// launches nothing there.  Reciprocal correspondences (never IDENTITY: the setter and set_config see to it) imply the claim.
+static bool pass_claims(const symmicp_ctx *c) { return (c->one_to_one || c->reciprocal) && c->cfg.corr != SYMMICP_CORR_IDENTITY; }
+static bool pass_reciprocal(const symmicp_ctx *c) { return c->reciprocal && c->cfg.corr != SYMMICP_CORR_IDENTITY; }
 static bool pass_rejects(const symmicp_ctx *c) { return c->trim_frac < 1.0f || c->med_factor > 0.0f || pass_claims(c); }
 
 static void fill_pass_args(symmicp_ctx *c, PassArgs &a, const float Xapply[16], bool from_cur, bool writeback, bool first)
@@ -65,7 +66,7 @@ static void fill_pass_args(symmicp_ctx *c, PassArgs &a, const float Xapply[16], 
     a.uniq_table = uniq ? c->uniq_table : nullptr;
     a.uniq_order = uniq ? c->src_order : nullptr;
     a.uniq_n_t = uniq ? (uint32_t)c->n_t : 0u;
-    a.trim_uniq = uniq ? 1 : 0;
+    a.trim_uniq = uniq ? (pass_reciprocal(c) && c->src_ix.valid ? 2 : 1) : 0;      // (2: run_pass has left the RecipArgs behind the table)
     a.med_f2 = trim && c->med_factor > 0.0f ? c->med_factor * c->med_factor : 0.0f;
     a.trim_rho = c->trim_frac;
 }
@@ -79,7 +80,7 @@ static int run_pass(symmicp_ctx *c, const float Xapply[16], bool from_cur, bool 
     // pass.  With none of them set nothing below differs from a build without them.
     const bool trim = pass_rejects(c);
     if (trim && pass_claims(c)) {
-        const size_t want = c->n_t ? c->n_t : 1;
+        const size_t want = (c->n_t ? c->n_t : 1) + (pass_reciprocal(c) ? kRecipTailWords : 0);      // (the tail: what a reciprocal pass hands its kernel)
         if (c->uniq_table_cap < want) {
             hipFree(c->uniq_table);
             c->uniq_table = nullptr; c->uniq_table_cap = 0;
@@ -97,8 +98,27 @@ static int run_pass(symmicp_ctx *c, const float Xapply[16], bool from_cur, bool 
         }
         if (!c->trim_ws) HIP_TRY(c, hipMalloc((void **)&c->trim_ws, sizeof(uint32_t) * kTrimWsWords));
     }
+    if (trim && pass_reciprocal(c)) {
+        // the source index: once per set_source, over the whole original source, labelled with the caller's rows; and this pass's inverse
+        if (!c->src_ix.valid) {
+            const double t0 = now_s();
+            if (int st = build_reverse_index(c, c->src0, c->n_loc, c->src_order, c->src_ix)) return st;
+            c->src_ix_builds++;
+            if (c->sw.debug_host) {
+                std::fprintf(stderr, "[symmicp host] source index: %u points, %zu bytes in its arena (+%zu allocations beside it), built in %.3f ms\n", c->n_loc,
+                             c->src_ix.keep.off, c->src_ix.extra.size(), (now_s() - t0) * 1e3);
+            }
+        }
+        c->recip_args.six = c->src_ix.ix;
+        symmicp_inverse_rigid(c->X, c->recip_args.inv.m);
+        c->recip_args.inv.nrm_w = 0.0f;
+        // (a pageable source that the next pass overwrites: safe because a copy this small is staged before the call returns, and because
+        // the host loop waits for every pass's record before it comes here again.  A loop that queued rejecting passes would need a slot per pass)
+        HIP_TRY(c, hipMemcpyAsync(c->uniq_table + c->n_t, &c->recip_args, sizeof(RecipArgs), hipMemcpyHostToDevice, c->stream));
+    }
     c->trim_valid = false;
     c->rej_valid = c->rej_new = false;
+    c->recip_valid = false;
     PassArgs a{};
     fill_pass_args(c, a, Xapply, from_cur, writeback, first);
     int blocks = (int)((c->n_loc + kPassThreads - 1) / kPassThreads);
@@ -235,7 +255,9 @@ static int run_pass(symmicp_ctx *c, const float Xapply[16], bool from_cur, bool 
         c->rej_gated = w[3]; c->rej_unique = w[0];
         c->trim_valid = c->trim_frac < 1.0f;
         c->rej_valid = true;
-        c->rej_new = c->med_factor > 0.0f || c->one_to_one;
+        c->rej_new = c->med_factor > 0.0f || c->one_to_one || c->reciprocal;
+        c->recip_valid = a.trim_uniq == 2;
+        c->recip_claimed = w[4]; c->recip_n = w[5];
     }
     if (ev) c->ev_used++;
     c->t_last_done = now_s(); c->n_pass_timed++;

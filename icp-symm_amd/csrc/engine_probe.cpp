@@ -172,6 +172,61 @@ int symmicp_ctx_unique_probe(symmicp_ctx *c, const int32_t *tgt_row, const uint3
     return SYMMICP_OK;
 }
 
+int symmicp_ctx_reverse_nn_probe(symmicp_ctx *c, const float *db_xyz, const int32_t *labels, size_t n_db, const float *q_xyz, size_t n_q,
+                                 const float *X16, int32_t *label_out, float *d2_out)
+{
+    if (!c) return SYMMICP_ERR_ARG;
+    if (!db_xyz || !q_xyz || !label_out || !d2_out || n_db == 0 || n_db > 0x7fffffffull || n_q == 0 || n_q > 0x7fffffffull)
+        return fail(c, SYMMICP_ERR_ARG, "reverse_nn_probe: bad arguments");
+    if (labels)
+        for (size_t i = 0; i < n_db; i++)
+            if (labels[i] < 0) return fail(c, SYMMICP_ERR_ARG, "reverse_nn_probe: labels must be below 2^31");
+    HIP_TRY(c, hipSetDevice(c->device));
+    Affine inv{};
+    float Xid[16];
+    identity16(Xid);
+    symmicp_inverse_rigid(X16 ? X16 : Xid, inv.m);
+    // everything in allocations of its own (the index's build rewinds the scratch arena): db as a planar cloud, the labels, the queries, the results
+    const size_t o_db = 0, o_lab = o_db + ((sizeof(float) * 3 * n_db + 255) & ~(size_t)255), o_raw = o_lab + ((sizeof(uint32_t) * n_db + 255) & ~(size_t)255),
+                 raw_n = std::max(n_db, n_q), o_out = o_raw + ((sizeof(float) * 3 * raw_n + 255) & ~(size_t)255),
+                 o_d2 = o_out + ((sizeof(int32_t) * n_q + 255) & ~(size_t)255), total = o_d2 + sizeof(float) * n_q;
+    char *d = nullptr;
+    HIP_TRY(c, hipMalloc((void **)&d, total));
+    ReverseIndex ri;       // (its own index: the context's source index stays as it was)
+    auto body = [&]() -> int {
+        float *raw = reinterpret_cast<float *>(d + o_raw), *col = reinterpret_cast<float *>(d + o_db);
+        HIP_TRY(c, hipMemcpyAsync(raw, db_xyz, sizeof(float) * 3 * n_db, hipMemcpyHostToDevice, c->stream));
+        if (labels) HIP_TRY(c, hipMemcpyAsync(d + o_lab, labels, sizeof(uint32_t) * n_db, hipMemcpyHostToDevice, c->stream));
+        launch_deinterleave3(raw, 3, 0, (uint32_t)n_db, col, col + n_db, col + 2 * n_db, c->stream);
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        CloudSoA cl{col, col + n_db, col + 2 * n_db, col, col + n_db, col + 2 * n_db};      // (no normals: the build reads the slots and nothing keeps them)
+        if (int st = build_reverse_index(c, cl, (uint32_t)n_db, labels ? reinterpret_cast<const uint32_t *>(d + o_lab) : nullptr, ri)) return st;
+        HIP_TRY(c, hipMemcpyAsync(raw, q_xyz, sizeof(float) * 3 * n_q, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        launch_reverse_nn_probe(ri.ix, inv, raw, (uint32_t)n_q, reinterpret_cast<int32_t *>(d + o_out), reinterpret_cast<float *>(d + o_d2), c->stream);
+        HIP_TRY(c, hipGetLastError());
+        HIP_TRY(c, hipMemcpyAsync(label_out, d + o_out, sizeof(int32_t) * n_q, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(d2_out, d + o_d2, sizeof(float) * n_q, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        return SYMMICP_OK;
+    };
+    const int st = body();
+    (void)hipStreamSynchronize(c->stream);
+    drop_reverse_index(ri, true);
+    (void)hipFree(d);
+    return st;
+}
+
+int symmicp_ctx_reciprocal_info(const symmicp_ctx *c, int32_t *index_valid, uint64_t *index_bytes, uint64_t *index_builds, uint64_t *table_words)
+{
+    if (!c) return SYMMICP_ERR_ARG;
+    if (index_valid) *index_valid = c->src_ix.valid ? 1 : 0;
+    if (index_bytes) *index_bytes = c->src_ix.keep.cap;
+    if (index_builds) *index_builds = c->src_ix_builds;
+    if (table_words) *table_words = c->uniq_table_cap;
+    return SYMMICP_OK;
+}
+
 int symmicp_ctx_scan_probe(symmicp_ctx *c, uint32_t *data, size_t n)
 {
     if (!c) return SYMMICP_ERR_ARG;

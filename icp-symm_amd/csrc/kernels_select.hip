@@ -21,11 +21,16 @@
 //                    target the sentinel, so the select's population is the winners
 //   k_median_tau     behind the select at rho = 0.5: tau = factor^2 x the median; k_count_le counts the keys <= tau, k_reject_publish
 //                    hands (population, kept, tau, n_c) to the host; k_reject_all does both for one-to-one alone (every winner is kept)
+// Reciprocal correspondences (symmicp_set_reciprocal) add one kernel between the claim and the keys:
+//   k_recip_check    per claimed target j: q_j through the inverse of the pass's transform, one exact walk of the octree over the ORIGINAL
+//                    source (oct_walk.h), and a winner that is not the reverse neighbour loses its claim (the entry goes back to ~0), so
+//                    k_trim_keys<UNIQ> finds no winner there; counts the claimed targets (n_u) and the survivors (n_r)
 // launch_trim_select has the order.
 //
 // The gates below are pair_step's (kernels_pass.hip), on the same fp32 expressions: unfused, in the association written.
 #include "symmicp_internal.h"
 #include "device_common.h"
+#include "oct_walk.h"
 #pragma clang fp contract(off)
 
 namespace symmicp {
@@ -34,9 +39,10 @@ constexpr int kSelThreads = 256;
 constexpr uint32_t kSelBins = 2048;           // bins of the widest digit (11 bits)
 constexpr uint32_t kSelMaxBlocks = 1024;      // grid-stride beyond this
 // workspace words (PassArgs::trim_ws): the state, then one histogram per digit
-enum { SEL_NC = 0, SEL_K = 1, SEL_PREFIX = 2, SEL_TAU = 3, SEL_KEPT = 4, SEL_K0 = 5, SEL_GATED = 6, SEL_MED = 7, SEL_STATE_WORDS = 16 };
+enum { SEL_NC = 0, SEL_K = 1, SEL_PREFIX = 2, SEL_TAU = 3, SEL_KEPT = 4, SEL_K0 = 5, SEL_GATED = 6, SEL_MED = 7, SEL_CLAIMED = 8, SEL_RECIP = 9, SEL_STATE_WORDS = 16 };
 static_assert(kTrimWsWords == SEL_STATE_WORDS + 3 * kSelBins, "symmicp_internal.h sizes the workspace");
 static_assert(kTrimTauWord == SEL_TAU, "the accumulating kernels read tau from this word");
+static_assert(kTrimClaimedWord == SEL_CLAIMED && kTrimRecipWord == SEL_RECIP, "the host reads n_u and n_r of a reciprocal pass from these words");
 
 template <int PASS> __device__ __forceinline__ uint32_t sel_digit(uint32_t key)
 {
@@ -184,6 +190,77 @@ __global__ __launch_bounds__(kSelThreads) void k_unique_claim(PassArgs a, CloudS
     }
 }
 
+// ---- reciprocal correspondences (symmicp_set_reciprocal) -------------------------------------------
+// back(j): target point q through the inverse of the pass's transform (fp32, unfused: xf_row with w = 1), then the exact walk of the
+// source's octree.  Its tq carries the caller's row in w, so the walk's tie-break (lowest row) and Best::row speak the claim key's language.
+__device__ __forceinline__ void reverse_nn(const TargetIndex &six, const Affine &inv, float qx, float qy, float qz, Best &b)
+{
+    const float yx = xf_row(inv.m + 0, qx, qy, qz, 1.0f), yy = xf_row(inv.m + 4, qx, qy, qz, 1.0f), yz = xf_row(inv.m + 8, qx, qy, qz, 1.0f);
+    b.d2 = __int_as_float(0x7f800000); b.pos = -1; b.row = 0x7fffffff;
+    oct_walk(six, yx, yy, yz, b);
+}
+
+// In partial overlap two thirds of the table's entries are unclaimed, and a lane without a claim would idle through its neighbours' whole
+// walks.  So a block compacts the claimed slots of its tiles into a ring in LDS (ballot + mbcnt per wave, the waves' counts through LDS)
+// and walks only when the ring holds a full block of items, or at the end: every walk round but the last has all its lanes at work.  The
+// ring's counters are block-uniform registers.  A vetoed entry is written back as ~0 by the one lane that owns it: no other thread of
+// this launch reads it.
+constexpr int kRecipThreads = 256;
+constexpr uint32_t kRecipRing = 2 * kRecipThreads;      // under a block of items before a tile is appended, at most a block more after
+
+// q_j is the point half of the target's pair record tn[2 j] in both pairings: TREE keeps the records in the index's order (ix.tq[j]'s bits),
+// BRUTE in the caller's (the planar target's bits); the table is indexed the same way.
+__global__ __launch_bounds__(kRecipThreads) void k_recip_check(unsigned long long *table, uint32_t n_t, const float4 *__restrict__ tn,
+                                                               const RecipArgs *__restrict__ ra, uint32_t *ws)
+{
+    const TargetIndex &six = ra->six;      // (uniform loads from device memory: the index and the inverse are not kernel arguments)
+    const Affine inv = ra->inv;
+    __shared__ uint32_t ring[kRecipRing];
+    __shared__ uint32_t s_wave[kRecipThreads / 64];
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    const uint32_t ntiles = (n_t + kRecipThreads - 1) / kRecipThreads;
+    uint32_t head = 0u, tail = 0u, claimed = 0u, surv = 0u;
+    for (uint32_t tile = blockIdx.x;; tile += gridDim.x) {
+        const bool more = tile < ntiles;                   // (block-uniform)
+        if (more) {
+            const uint32_t j = tile * kRecipThreads + threadIdx.x;
+            const bool c = j < n_t && table[j] != ~0ull;
+            const unsigned long long m = __ballot(c);
+            if (lane == 0) s_wave[wave] = (uint32_t)__popcll(m);
+            __syncthreads();                               // (also: every wave has left the walk round that read the ring before it is written)
+            uint32_t off = 0u, total = 0u;
+#pragma unroll
+            for (uint32_t w = 0; w < kRecipThreads / 64; w++) { const uint32_t v = s_wave[w]; off += w < wave ? v : 0u; total += v; }
+            if (c) ring[(tail + off + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u))) % kRecipRing] = j;
+            tail += total;
+            claimed += c ? 1u : 0u;
+            __syncthreads();
+        }
+        while (tail - head >= (uint32_t)kRecipThreads || (!more && tail != head)) {
+            const uint32_t left = tail - head, take = left < (uint32_t)kRecipThreads ? left : (uint32_t)kRecipThreads;
+            if (threadIdx.x < take) {
+                const uint32_t j = ring[(head + threadIdx.x) % kRecipRing];
+                const unsigned long long key = table[j];
+                const float4 q = tn[2 * (size_t)j];
+                Best b;
+                reverse_nn(six, inv, q.x, q.y, q.z, b);
+                if ((uint32_t)b.row != (uint32_t)(key & 0xFFFFFFFFull)) table[j] = ~0ull;
+                else surv++;
+            }
+            head += take;
+        }
+        if (!more) break;
+    }
+    // n_u and n_r: one atomic per wave and word
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+        claimed += (uint32_t)__shfl_xor((int)claimed, off, 64);
+        surv += (uint32_t)__shfl_xor((int)surv, off, 64);
+    }
+    if (lane == 0 && claimed) atomicAdd(ws + SEL_CLAIMED, claimed);
+    if (lane == 0 && surv) atomicAdd(ws + SEL_RECIP, surv);
+}
+
 // UNIQ: the table of k_unique_claim is complete: a candidate that did not win its target gets the sentinel and leaves the population
 // (SEL_NC and the histogram); SEL_GATED counts the candidates either way.
 template <int CORR, bool UNIQ>
@@ -283,14 +360,14 @@ __global__ __launch_bounds__(kSelThreads) void k_select_scan(uint32_t *ws, float
         if (PASS == 2) {
             const uint32_t kept = ws[SEL_K0] - (k - before) + bins[j];
             ws[SEL_TAU] = prefix; ws[SEL_KEPT] = kept;
-            if (out_host) { out_host[0] = ws[SEL_NC]; out_host[1] = kept; out_host[2] = prefix; out_host[3] = ws[SEL_GATED]; }
+            if (out_host) { out_host[0] = ws[SEL_NC]; out_host[1] = kept; out_host[2] = prefix; out_host[3] = ws[SEL_GATED]; out_host[4] = ws[SEL_CLAIMED]; out_host[5] = ws[SEL_RECIP]; }
         }
     }
     if (k == 0u && t == 0) {
         ws[SEL_K] = 0u;
         if (PASS == 2) {
             ws[SEL_TAU] = 0u; ws[SEL_KEPT] = 0u;
-            if (out_host) { out_host[0] = ws[SEL_NC]; out_host[1] = 0u; out_host[2] = 0u; out_host[3] = ws[SEL_GATED]; }
+            if (out_host) { out_host[0] = ws[SEL_NC]; out_host[1] = 0u; out_host[2] = 0u; out_host[3] = ws[SEL_GATED]; out_host[4] = ws[SEL_CLAIMED]; out_host[5] = ws[SEL_RECIP]; }
         }
     }
 }
@@ -318,7 +395,7 @@ __global__ void k_reject_all(uint32_t *ws, uint32_t *out_host)
 {
     const uint32_t nc = ws[SEL_NC];
     ws[SEL_TAU] = 0x7F800000u; ws[SEL_KEPT] = nc;
-    if (out_host) { out_host[0] = nc; out_host[1] = nc; out_host[2] = 0x7F800000u; out_host[3] = ws[SEL_GATED]; }
+    if (out_host) { out_host[0] = nc; out_host[1] = nc; out_host[2] = 0x7F800000u; out_host[3] = ws[SEL_GATED]; out_host[4] = ws[SEL_CLAIMED]; out_host[5] = ws[SEL_RECIP]; }
 }
 
 // Median distance: the select (rho = 0.5) left the median in SEL_TAU; tau = f2 * med, one fp32 product.  Population 0: tau = 0.  A NaN
@@ -351,6 +428,7 @@ __global__ __launch_bounds__(kSelThreads) void k_count_le(const uint32_t *__rest
 __global__ void k_reject_publish(const uint32_t *ws, uint32_t *out_host)
 {
     out_host[0] = ws[SEL_NC]; out_host[1] = ws[SEL_KEPT]; out_host[2] = ws[SEL_TAU]; out_host[3] = ws[SEL_GATED];
+    out_host[4] = ws[SEL_CLAIMED]; out_host[5] = ws[SEL_RECIP];
 }
 
 template <bool UNIQ>
@@ -363,6 +441,7 @@ static void launch_keys(const PassArgs &a, int corr, CloudSoA tgt, const float4 
 
 // The rejection steps of a pass, behind its search and in front of its accumulating kernel:
 //   one-to-one (a.uniq_table; never IDENTITY, whose pairs are one-to-one)   memset of the table, k_unique_claim
+//   reciprocal (a.trim_uniq == 2: the table's tail holds the RecipArgs)     k_recip_check
 //   keys                                                                    memset of the workspace, k_trim_keys
 //   tau: trim fraction            the select (5 launches), which publishes
 //        median factor            the select at rho = 0.5, k_median_tau, k_count_le, k_reject_publish
@@ -377,6 +456,9 @@ void launch_trim_select(const PassArgs &a, int corr, CloudSoA tgt, const float4 
         hipMemsetAsync(a.uniq_table, 0xFF, sizeof(unsigned long long) * a.uniq_n_t, s);
         if (corr == SYMMICP_CORR_BRUTE) hipLaunchKernelGGL(k_unique_claim<1>, dim3(nb), dim3(kSelThreads), 0, s, a, tgt, tn);
         else hipLaunchKernelGGL(k_unique_claim<2>, dim3(nb), dim3(kSelThreads), 0, s, a, tgt, tn);
+        if (a.trim_uniq == 2)
+            hipLaunchKernelGGL(k_recip_check, dim3(sel_blocks(a.uniq_n_t)), dim3(kRecipThreads), 0, s, a.uniq_table, a.uniq_n_t, tn,
+                               reinterpret_cast<const RecipArgs *>(a.uniq_table + a.uniq_n_t), a.trim_ws);
         launch_keys<true>(a, corr, tgt, tn, nb, s);
     } else launch_keys<false>(a, corr, tgt, tn, nb, s);
     if (a.med_f2 > 0.0f) {
@@ -424,6 +506,35 @@ void launch_unique_probe(const int32_t *tgt_row, const uint32_t *d2_bits, uint32
     hipMemsetAsync(table, 0xFF, sizeof(unsigned long long) * n_t, s);
     hipLaunchKernelGGL(k_probe_claim, dim3(sel_blocks(n)), dim3(kSelThreads), 0, s, tgt_row, d2_bits, n, table, n_t);
     hipLaunchKernelGGL(k_probe_winner, dim3(sel_blocks(n)), dim3(kSelThreads), 0, s, tgt_row, d2_bits, n, table, n_t, winner_out);
+}
+
+
+// ---- reciprocal correspondences: the relabelling of the source index and the test entry of the reverse search ----
+__global__ __launch_bounds__(kSelThreads) void k_relabel_tq(float4 *tq, uint32_t n, const uint32_t *__restrict__ labels)
+{
+    const uint32_t i = blockIdx.x * kSelThreads + threadIdx.x;
+    if (i < n) tq[i].w = __uint_as_float(labels[__float_as_uint(tq[i].w)]);
+}
+
+void launch_relabel_tq(float4 *tq, uint32_t n, const uint32_t *labels, hipStream_t s)
+{
+    if (labels && n) hipLaunchKernelGGL(k_relabel_tq, dim3((n + kSelThreads - 1) / kSelThreads), dim3(kSelThreads), 0, s, tq, n, labels);
+}
+
+__global__ __launch_bounds__(kRecipThreads) void k_reverse_nn_probe(TargetIndex six, Affine inv, const float *__restrict__ q_xyz, uint32_t n_q,
+                                                                    int32_t *label_out, float *d2_out)
+{
+    const uint32_t i = blockIdx.x * kRecipThreads + threadIdx.x;
+    if (i >= n_q) return;
+    Best b;
+    reverse_nn(six, inv, q_xyz[3 * (size_t)i], q_xyz[3 * (size_t)i + 1], q_xyz[3 * (size_t)i + 2], b);
+    label_out[i] = b.row;
+    d2_out[i] = b.d2;
+}
+
+void launch_reverse_nn_probe(const TargetIndex &six, const Affine &inv, const float *q_xyz, uint32_t n_q, int32_t *label_out, float *d2_out, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_reverse_nn_probe, dim3((n_q + kRecipThreads - 1) / kRecipThreads), dim3(kRecipThreads), 0, s, six, inv, q_xyz, n_q, label_out, d2_out);
 }
 
 

@@ -7,7 +7,7 @@
 
 MyICP::MyICP() : max_iters(10), diff_threshold(1.f),                       // myicp.cpp:6
                  mode_(SYMMICP_MODE_QUIRKS), corr_(SYMMICP_CORR_IDENTITY), verbose_(true),
-                 have_src_normals_(false), have_tgt_normals_(false), loss_(SYMMICP_LOSS_NONE), loss_scale_(0.f), gicp_eps_(1e-3f), trim_fraction_(1.f), one_to_one_(false), median_factor_(0.f), max_corr_dist_(0.f), ctx_(nullptr), ctx_corr_(-1), ctx_no_src_normals_(false)
+                 have_src_normals_(false), have_tgt_normals_(false), loss_(SYMMICP_LOSS_NONE), loss_scale_(0.f), gicp_eps_(1e-3f), trim_fraction_(1.f), one_to_one_(false), reciprocal_(false), median_factor_(0.f), max_corr_dist_(0.f), ctx_(nullptr), ctx_corr_(-1), ctx_no_src_normals_(false)
 {
 	cloud_src = pcl::PointCloud<PointT>::Ptr(new pcl::PointCloud<PointT>);
 	cloud_tgt = pcl::PointCloud<PointT>::Ptr(new pcl::PointCloud<PointT>);
@@ -165,9 +165,11 @@ int MyICP::align(float out4x4[16], const float *guess4x4)
 	if (st == SYMMICP_OK) st = symmicp_set_trim_fraction(ctx, 1.f);        // (... or a trim fraction)
 	if (st == SYMMICP_OK) st = symmicp_set_one_to_one(ctx, 0);             // (... or a rejector)
 	if (st == SYMMICP_OK) st = symmicp_set_median_factor(ctx, 0.f);
+	if (st == SYMMICP_OK) st = symmicp_set_reciprocal(ctx, 0);
 	if (st == SYMMICP_OK) st = symmicp_set_config(ctx, &cfg);
 	if (st == SYMMICP_OK) st = symmicp_set_trim_fraction(ctx, trim_fraction_);        // ERR_ARG: outside (0, 1], or below 1 with QUIRKS
 	if (st == SYMMICP_OK) st = symmicp_set_one_to_one(ctx, one_to_one_ ? 1 : 0);      // ERR_ARG: with QUIRKS
+	if (st == SYMMICP_OK) st = symmicp_set_reciprocal(ctx, reciprocal_ ? 1 : 0);      // ERR_ARG: with QUIRKS or identity pairing
 	if (st == SYMMICP_OK) st = symmicp_set_median_factor(ctx, median_factor_);        // ERR_ARG: not 0 or finite and > 0, with QUIRKS, or with a trim fraction below 1
 	if (st == SYMMICP_OK) st = symmicp_set_robust_loss(ctx, loss_, loss_scale_);      // ERR_ARG: a loss with QUIRKS, or a bad scale
 	if (st == SYMMICP_OK) st = symmicp_set_gicp_epsilon(ctx, gicp_eps_);              // ERR_ARG: eps outside (0, 1]

@@ -189,14 +189,25 @@ struct PassArgs {
     unsigned long long *uniq_table;     // one-to-one: [uniq_n_t] per target position the smallest claim (d2 bits << 32 | caller row); null: off
     const uint32_t *uniq_order;         // ... share row -> caller row (null: the share is in caller order)
     uint32_t uniq_n_t;                  // ... entries of the table
-    int32_t trim_uniq;                  // the accumulating kernel reads trim_keys[i] and drops the sentinel rows: losers of the claim
+    int32_t trim_uniq;                  // != 0: the accumulating kernel reads trim_keys[i] and drops the sentinel rows: losers of the claim.  2: a reciprocal
+                                        // pass (symmicp_set_reciprocal): launch_trim_select runs k_recip_check between the claim and the keys, on the
+                                        // RecipArgs the host left in device memory behind the table's uniq_n_t entries
     float med_f2;                       // median distance: factor * factor in fp32 (0: off): tau = med_f2 * the select's median
     // colored ICP (SYMMICP_MODE_COLOR; read by the kObjColor instantiations only)
     const float4 *tgt_color;            // per target point, in the order of tn (IDENTITY: of the planar target): (gradient xyz, intensity)
     const float *src_int;               // per share row: the source point's intensity
     float color_lam, color_om;          // lambda and omega = 1.0f - lambda
 };
+// what a reciprocal pass adds to the claim (kernels_select.hip, k_recip_check): the index over the ORIGINAL source, whose tq carries the
+// caller's row in w, and the 3x4 inverse of the pass's cumulative transform (symmicp_inverse_rigid).  Read by the kernel from device memory
+// (the tail of the claim table), so PassArgs, an argument of every pass kernel, carries nothing for it
+struct RecipArgs {
+    TargetIndex six;
+    Affine inv;
+};
+constexpr size_t kRecipTailWords = (sizeof(RecipArgs) + 7) / 8;      // 64-bit words the claim table is allocated beyond its entries
 constexpr uint32_t kTrimWsWords = 16 + 3 * 2048;
+constexpr uint32_t kTrimClaimedWord = 8, kTrimRecipWord = 9;      // reciprocal passes: n_u and n_r (0 otherwise), published behind the four words of trim_host
 constexpr uint32_t kTrimTauWord = 3;
 
 // host-side launch tuning of the tree passes (environment switches, read once by the engine)
@@ -281,6 +292,11 @@ void launch_select_probe(const uint32_t *keys, uint32_t n, uint32_t k, uint32_t 
 // being the array index; tgt_row < 0 or >= n_t: no pair.  table: [n_t] scratch; winner_out[i] = 1 where row i wins its target
 void launch_unique_probe(const int32_t *tgt_row, const uint32_t *d2_bits, uint32_t n, unsigned long long *table, uint32_t n_t,
                          uint8_t *winner_out, hipStream_t s);
+
+// reciprocal correspondences: tq[i].w = labels[tq[i].w] over an index's sorted points (labels == null: nothing is launched); and the
+// test entry of the reverse search: queries [n_q][3] through inv and the walk -> back() and d2' per query
+void launch_relabel_tq(float4 *tq, uint32_t n, const uint32_t *labels, hipStream_t s);
+void launch_reverse_nn_probe(const TargetIndex &six, const Affine &inv, const float *q_xyz, uint32_t n_q, int32_t *label_out, float *d2_out, hipStream_t s);
 
 void launch_identity_d2(const CloudSoA &in, const Affine &X, const CloudSoA &tgt, uint32_t tgt_offset, uint32_t n, float *d2, hipStream_t s);
 void launch_pairs_d2(const CloudSoA &in, const Affine &X, const int32_t *pos, const float4 *tq, uint32_t n_t, uint32_t n, float *d2, hipStream_t s);

@@ -120,6 +120,8 @@ EXPORTS = [
     "symmicp_set_trim_fraction", "symmicp_get_trim_fraction", "symmicp_get_trim_state", "symmicp_ctx_select_probe",
     "symmicp_set_one_to_one", "symmicp_get_one_to_one", "symmicp_set_median_factor", "symmicp_get_median_factor",
     "symmicp_get_rejection_state", "symmicp_ctx_unique_probe",
+    "symmicp_set_reciprocal", "symmicp_get_reciprocal", "symmicp_get_reciprocal_state", "symmicp_inverse_rigid", "symmicp_ctx_reverse_nn_probe",
+    "symmicp_ctx_reciprocal_info",
     "symmicp_set_color_weight", "symmicp_get_color_weight", "symmicp_set_source_intensity", "symmicp_set_target_intensity",
     "symmicp_get_source_intensity", "symmicp_intensity_gradient", "symmicp_ctx_intensity_gradient", "symmicp_pcd_read_intensity",
 ]
@@ -238,6 +240,12 @@ def lib():
     L.symmicp_get_median_factor.argtypes = [vp, fp]
     L.symmicp_get_rejection_state.argtypes = [vp, u64p, u64p, u64p, fp]
     L.symmicp_ctx_unique_probe.argtypes = [vp, i32p, u32p, C.c_size_t, C.c_size_t, C.POINTER(C.c_uint8)]
+    L.symmicp_set_reciprocal.argtypes = [vp, C.c_int]
+    L.symmicp_get_reciprocal.argtypes = [vp, C.POINTER(C.c_int)]
+    L.symmicp_get_reciprocal_state.argtypes = [vp, u64p, u64p]
+    L.symmicp_inverse_rigid.argtypes = [fp, fp]
+    L.symmicp_ctx_reciprocal_info.argtypes = [vp, i32p, u64p, u64p, u64p]
+    L.symmicp_ctx_reverse_nn_probe.argtypes = [vp, fp, i32p, C.c_size_t, fp, C.c_size_t, fp, i32p, fp]
     L.symmicp_ctx_select_probe.argtypes = [vp, u32p, C.c_size_t, C.c_uint64, u32p, u64p]
     L.symmicp_set_color_weight.argtypes = [vp, C.c_float]
     L.symmicp_get_color_weight.argtypes = [vp, fp]
@@ -352,6 +360,17 @@ def robust_weight(loss, scale, r):
     ra = np.asarray(r, np.float32)
     out = np.array([f(code, float(scale), float(x)) for x in ra.reshape(-1)], np.float32).reshape(ra.shape)
     return out if ra.ndim else float(out)
+
+
+def inverse_rigid(transform):
+    """the 3x4 inverse a reciprocal pass carries the target through (symmicp_inverse_rigid): the rotation block transposed and
+    -R^T t, formed in fp64 and rounded to fp32 -> (3, 4) float32; needs no GPU"""
+    X = np.ascontiguousarray(np.asarray(transform, np.float32).reshape(16))
+    out = np.zeros(12, np.float32)
+    st = lib().symmicp_inverse_rigid(_fptr(X), _fptr(out))
+    if st != 0:
+        raise SymmIcpError(st, "symmicp_inverse_rigid")
+    return out.reshape(3, 4)
 
 
 def format_result(transform):
@@ -763,6 +782,22 @@ class Engine:
         self._chk(self._L.symmicp_get_one_to_one(self._h, C.byref(on)))
         return bool(on.value)
 
+    def set_reciprocal(self, on):
+        """reciprocal correspondences: a pair (p, q) is kept only if p is also the nearest source point of q (implies one-to-one);
+        takes effect at the next pass"""
+        self._chk(self._L.symmicp_set_reciprocal(self._h, 1 if on else 0))
+
+    def get_reciprocal(self):
+        on = C.c_int(0)
+        self._chk(self._L.symmicp_get_reciprocal(self._h, C.byref(on)))
+        return bool(on.value)
+
+    def reciprocal_state(self):
+        """-> (n_u = claimed targets, n_r = reciprocal survivors) of the most recent pass; ERR_STATE if it was not reciprocal"""
+        nu, nr = C.c_uint64(0), C.c_uint64(0)
+        self._chk(self._L.symmicp_get_reciprocal_state(self._h, C.byref(nu), C.byref(nr)))
+        return nu.value, nr.value
+
     def set_median_factor(self, factor):
         """median-distance rejection: every pass keeps the pairs with d <= factor x the median pair distance (0 = off, the default);
         takes effect at the next pass"""
@@ -1111,6 +1146,29 @@ class Engine:
                                                    r.size, int(n_t), w.ctypes.data_as(C.POINTER(C.c_uint8))))
         return w.astype(bool)
 
+    def reverse_nn_probe(self, db, queries, labels=None, X=None):
+        """the reverse search of a reciprocal pass on host arrays (symmicp_ctx_reverse_nn_probe): the index over db relabelled with
+        `labels` (distinct, < 2^31; None: the row), the queries carried through inverse_rigid(X) (None: identity)
+        -> (label of the nearest db point, ties to the lowest label: int32 [n_q]; its fp32 d2 [n_q])"""
+        d, q = _cloud(db), _cloud(queries)
+        lab = None if labels is None else np.ascontiguousarray(np.asarray(labels, np.int32).reshape(-1))
+        if lab is not None and lab.size != d.shape[0]:
+            raise ValueError("reverse_nn_probe: one label per db point")
+        Xa = None if X is None else np.ascontiguousarray(np.asarray(X, np.float32).reshape(16))
+        out = np.zeros(q.shape[0], np.int32)
+        d2 = np.zeros(q.shape[0], np.float32)
+        self._chk(self._L.symmicp_ctx_reverse_nn_probe(self._h, _fptr(d), None if lab is None else lab.ctypes.data_as(C.POINTER(C.c_int32)), d.shape[0],
+                                                       _fptr(q), q.shape[0], None if Xa is None else _fptr(Xa),
+                                                       out.ctypes.data_as(C.POINTER(C.c_int32)), _fptr(d2)))
+        return out, d2
+
+    def reciprocal_info(self):
+        """what reciprocal correspondences hold on this context (symmicp_ctx_reciprocal_info) -> dict(index_valid, index_bytes,
+        index_builds, table_words)"""
+        v, b, n, t = C.c_int32(0), C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        self._chk(self._L.symmicp_ctx_reciprocal_info(self._h, C.byref(v), C.byref(b), C.byref(n), C.byref(t)))
+        return dict(index_valid=bool(v.value), index_bytes=b.value, index_builds=n.value, table_words=t.value)
+
     def scan_probe(self, data):
         """the build's exclusive scan on a host array (symmicp_ctx_scan_probe) -> new uint32 array"""
         d = np.array(data, np.uint32).reshape(-1)
@@ -1154,6 +1212,7 @@ class MyICP:
         self._gicp_eps = None
         self._trim = 1.0
         self._one_to_one = False
+        self._reciprocal = False
         self._median = 0.0
         self._color_weight = None
         self.intensity_src = self.intensity_tgt = None
@@ -1240,6 +1299,10 @@ class MyICP:
         """one-to-one rejection for the next align, every voxel level included (see Engine.set_one_to_one)"""
         self._one_to_one = bool(on)
 
+    def setReciprocalCorrespondences(self, on):
+        """reciprocal correspondences for the next align, every voxel level included (see Engine.set_reciprocal)"""
+        self._reciprocal = bool(on)
+
     def setMedianFactor(self, factor):
         """median-distance rejection for the next align, every voxel level included (see Engine.set_median_factor; 0 = off)"""
         self._median = float(factor)
@@ -1311,6 +1374,8 @@ class MyICP:
                 e.set_trim_fraction(self._trim)
             if self._one_to_one:
                 e.set_one_to_one(True)
+            if self._reciprocal:
+                e.set_reciprocal(True)
             if self._median != 0.0:
                 e.set_median_factor(self._median)
             if self._color_weight is not None:
@@ -1339,6 +1404,8 @@ class MyICP:
                 e.set_trim_fraction(self._trim)
             if self._one_to_one:
                 e.set_one_to_one(True)
+            if self._reciprocal:
+                e.set_reciprocal(True)
             if self._median != 0.0:
                 e.set_median_factor(self._median)
             X = guess

@@ -65,6 +65,10 @@ public:
 	// SYMMICP_MODE_QUIRKS, for a factor that is neither 0 nor finite and > 0, and for a factor > 0 with a trim fraction below 1
 	void setOneToOne(bool on) { one_to_one_ = on; }
 	void setMedianFactor(float factor) { median_factor_ = factor; }
+	// reciprocal correspondences (symmicp_set_reciprocal; default off; PCL's setUseReciprocalCorrespondences): a pair (p, q) is kept only
+	// if p is also the nearest source point of q; implies one-to-one.  Applies like setOneToOne, every level of setVoxelLevels included;
+	// checked by align(), which returns SYMMICP_ERR_ARG with SYMMICP_MODE_QUIRKS and with SYMMICP_CORR_IDENTITY
+	void setReciprocalCorrespondences(bool on) { reciprocal_ = on; }
 	// Colored ICP (SYMMICP_MODE_COLOR): one scalar intensity per point of each cloud, n = the cloud's count, set after setInput* /
 	// LoadCloud (LoadCloud keeps the intensities of files that carry an `intensity` or `rgb` field; setInput* drops the cloud's).
 	// align() estimates the target's intensity gradient itself (symmicp_ctx_intensity_gradient, k = 10).  In COLOR align() returns
@@ -136,6 +140,7 @@ private:
 	float gicp_eps_;
 	float trim_fraction_;
 	bool one_to_one_;
+	bool reciprocal_;
 	float median_factor_;
 	float max_corr_dist_;
 	float color_weight_ = 0.968f;

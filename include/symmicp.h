@@ -268,8 +268,48 @@ int symmicp_set_median_factor(symmicp_ctx *ctx, float factor);
 int symmicp_get_median_factor(const symmicp_ctx *ctx, float *factor);
 /* n_c, n_u (= n_c when one-to-one is off), the kept count and tau of the most recent pass (each pointer may be NULL);
  * SYMMICP_ERR_STATE if no pass has run or that pass ran neither of these two rejectors.  symmicp_get_trim_state keeps working for
- * trimmed passes; its `candidates` is the select's population (n_u with one-to-one on). */
+ * trimmed passes; its `candidates` is the select's population (n_u with one-to-one on).  `unique` is the select's population too: on a
+ * reciprocal pass (symmicp_set_reciprocal) it is n_r, and symmicp_get_reciprocal_state has n_u. */
 int symmicp_get_rejection_state(const symmicp_ctx *ctx, uint64_t *gated, uint64_t *unique, uint64_t *kept, float *tau_d2);
+/* Reciprocal correspondences (PCL's setUseReciprocalCorrespondences): a pair (p, q) counts only if q is the nearest target point of p
+ * AND p is the nearest source point of q.  symmicp_set_reciprocal(on != 0; off by default) is a pure function of the pass and
+ * reproducible bit for bit.  The moving cloud is never re-indexed: the source is indexed once, in the frame symmicp_set_source received
+ * it in, and every target point is carried into that frame by the inverse of the pass's transform.
+ *   Inverse     X = the cumulative row-major 4x4 of the pass: it takes the original source to the positions this pass pairs, and it is
+ *               what symmicp_get_transform returns after the call that ran the pass.  With R_rc = X[4r + c] and t_r = X[4r + 3], row r of
+ *               the 3x4 inverse is (R_0r, R_1r, R_2r, -((R_0r t_0 + R_1r t_1) + R_2r t_2)), formed in fp64 from the fp32 entries (the
+ *               products of two fp32 values are exact in fp64, so contraction cannot change it), then each entry rounded to fp32.  X's
+ *               bottom row is ignored.  The rule is defined by this arithmetic whatever X is: for a guess that is not rigid it is not an
+ *               inverse, and that is the caller's business.  symmicp_inverse_rigid below is this function.
+ *   Back-       y_j = the three inverse rows applied to target point q_j with w = 1, in fp32 and unfused:
+ *   projection  ((m0 x + m1 y) + m2 z) + m3.
+ *   Reverse     back(j) = the source row i that minimises (d2'(i, j), r_i) lexicographically, with d2'(i, j) the fp32
+ *   neighbour   (dx dx + dy dy) + dz dz of d = y_j - p_i, p_i the ORIGINAL source point as symmicp_set_source received it (never the
+ *               written-back copy, in either apply mode) and r_i the caller's row.  The minimum runs over ALL source rows of the context,
+ *               not only the candidates.
+ *   Rule        Candidates as for one-to-one (the pair exists and passes max_corr_dist, then min_normal_dot).  The one-to-one claim runs
+ *               first -- reciprocal implies it, with the same key K -- and the winner i of target j survives iff back(j) == r_i.
+ *               n_u = the number of claimed targets, n_r = the number of survivors.  The quantile rule (trim fraction or median factor)
+ *               then runs over the survivors exactly as it does over one-to-one's; with no quantile rule every survivor is kept and
+ *               tau = +Inf.  Turning symmicp_set_one_to_one on as well changes nothing.
+ *   Properties  The kept set is a subset of what one-to-one alone keeps in the same pass (its survivors), whatever quantile rule runs.
+ *               In exact arithmetic and for rigid X the survivors are PCL's reciprocal set; the forward search runs in the target's
+ *               frame and the reverse one in the source's, so near-ties at rounding level may resolve differently.
+ *   Off         nothing new is launched or allocated, and results are bit for bit what they are without it.
+ * Scope: every mode but QUIRKS (SYMMICP_ERR_ARG from the setter, and symmicp_set_config refuses to switch a reciprocal context into
+ * QUIRKS); BRUTE and TREE pairings -- SYMMICP_CORR_IDENTITY is refused the same way in both directions, because its pairs were never
+ * searched; nranks > 1 is SYMMICP_ERR_STATE in both directions, as for one-to-one; symmicp_align runs the host loop, and a rejecting
+ * TREE pass never skips its walk.  The setter takes effect at the next pass.  On the device: an octree over the source, built at the
+ * first reciprocal pass after a symmicp_set_source and kept until the next one, and between the claim and the keys one exact
+ * nearest-neighbour walk of it per claimed target, which vetoes the claim of a winner that is not the reverse neighbour. */
+int symmicp_set_reciprocal(symmicp_ctx *ctx, int on);
+int symmicp_get_reciprocal(const symmicp_ctx *ctx, int *on);
+/* n_u (claimed targets) and n_r (reciprocal survivors) of the most recent pass (each pointer may be NULL); SYMMICP_ERR_STATE if no pass
+ * has run or that pass was not reciprocal.  On a reciprocal pass symmicp_get_rejection_state's `unique` is the select's population,
+ * so n_r. */
+int symmicp_get_reciprocal_state(const symmicp_ctx *ctx, uint64_t *claimed, uint64_t *reciprocal);
+/* the 3x4 inverse of the definition above (a pure host function); SYMMICP_ERR_ARG for a NULL pointer */
+int symmicp_inverse_rigid(const float X16[16], float out12[12]);
 /* the weight the kernels give a pair of residual r (the same fp32 source); NaN for an unknown loss, or for a scale that
  * is not finite and > 0 with loss != NONE; 1 for SYMMICP_LOSS_NONE */
 float symmicp_robust_weight(int loss, float scale, float r);
@@ -426,6 +466,20 @@ int symmicp_ctx_select_probe(symmicp_ctx *ctx, const uint32_t *keys, size_t n, u
  * stream and scratch arena; the context's clouds, pairs, options and states stay as they were. */
 int symmicp_ctx_unique_probe(symmicp_ctx *ctx, const int32_t *tgt_row, const uint32_t *d2_bits, size_t n, size_t n_t, uint8_t *winner_out);
 
+/* the reverse search of a reciprocal pass on host arrays: builds the index over db [n_db][3] exactly as the pass builds the source's,
+ * relabels it with the given distinct labels (< 2^31; NULL: the row), carries the queries q_xyz [n_q][3] through
+ * symmicp_inverse_rigid(X16) (NULL: identity) and returns back() and d2' for every query.  n_db, n_q in 1 .. 2^31 - 1.  Same stream and
+ * scratch arena; the context's clouds, indexes, options and states stay as they were. */
+int symmicp_ctx_reverse_nn_probe(symmicp_ctx *ctx, const float *db_xyz, const int32_t *labels, size_t n_db, const float *q_xyz, size_t n_q,
+                                 const float *X16, int32_t *label_out, float *d2_out);
+
+/* what reciprocal correspondences hold on this context (each pointer may be NULL): *index_valid != 0: the source index exists;
+ * *index_bytes: the device bytes of its arena (0: never built; the arena is kept across symmicp_set_source calls and reused);
+ * *index_builds: the builds of it by passes since symmicp_create -- one per symmicp_set_source followed by a reciprocal pass, none
+ * otherwise (the probe above builds an index of its own and is not counted); *table_words: the 64-bit words allocated for the
+ * one-to-one claim table (0: none; the target's size for one-to-one passes; more, by the reverse search's arguments, once a
+ * reciprocal pass has run). */
+int symmicp_ctx_reciprocal_info(const symmicp_ctx *ctx, int32_t *index_valid, uint64_t *index_bytes, uint64_t *index_builds, uint64_t *table_words);
 /* ---- normals pre-step (replaces MyICP::estimateNormals, myicp.cpp:152-172: PCL NormalEstimation,
  * setKSearch(10), viewpoint (0,0,0)).  Exact k-NN (the point itself included) + PCA on the GPU.
  * xyz strided as in set_source; nrm_out packed AoS [n][3]; curv_out (lambda_min / trace) may be NULL;
