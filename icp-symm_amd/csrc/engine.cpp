@@ -180,7 +180,7 @@ extern "C++" void forget_source(symmicp_ctx *c)
     c->n_loc = c->n_s_total = c->src_off = 0;
     c->src_no_normals = false;
     c->have_src_int = false;
-    drop_reverse_index(c->src_ix, false);
+    drop_reverse_index(c->rej.src_ix, false);
 }
 
 static void free_source(symmicp_ctx *c)
@@ -202,9 +202,9 @@ void symmicp_destroy(symmicp_ctx *c)
     free_target(c);
     free_source(c);
     hipFree(c->partials); hipFree(c->d_sums); hipFree(c->ticket); hipFree(c->arena.base); hipFree(c->keep.base);
-    hipFree(c->trim_keys); hipFree(c->trim_ws); hipFree(c->uniq_table);
+    hipFree(c->rej.keys); hipFree(c->rej.ws); hipFree(c->rej.table);
     hipFree(c->tgt_color); hipFree(c->src_int);
-    drop_reverse_index(c->src_ix, true);
+    drop_reverse_index(c->rej.src_ix, true);
     if (c->h_sums) hipHostFree(c->h_sums);
     hipFree(c->d_loop);
     if (c->h_loop) hipHostFree(c->h_loop);
@@ -226,13 +226,13 @@ int symmicp_set_config(symmicp_ctx *c, const symmicp_config *cfg)
     if ((c->n_t || c->n_loc) && cfg->sort_source != c->cfg.sort_source) return fail(c, SYMMICP_ERR_STATE, "sort_source cannot change after clouds are set");
     if (cfg->mode == SYMMICP_MODE_QUIRKS && c->loss != SYMMICP_LOSS_NONE)
         return fail(c, SYMMICP_ERR_ARG, "QUIRKS takes no robust loss (set SYMMICP_LOSS_NONE first)");
-    if (cfg->mode == SYMMICP_MODE_QUIRKS && c->trim_frac < 1.0f)
+    if (cfg->mode == SYMMICP_MODE_QUIRKS && c->rej.trims())
         return fail(c, SYMMICP_ERR_ARG, "QUIRKS takes no trim fraction below 1 (set 1 first)");
-    if (cfg->mode == SYMMICP_MODE_QUIRKS && (c->one_to_one || c->med_factor > 0.0f))
+    if (cfg->mode == SYMMICP_MODE_QUIRKS && (c->rej.one_to_one || c->rej.median()))
         return fail(c, SYMMICP_ERR_ARG, "QUIRKS takes no one-to-one or median-distance rejector (switch them off first)");
-    if (c->reciprocal && cfg->mode == SYMMICP_MODE_QUIRKS)
+    if (c->rej.reciprocal && cfg->mode == SYMMICP_MODE_QUIRKS)
         return fail(c, SYMMICP_ERR_ARG, "QUIRKS takes no reciprocal correspondences (switch them off first)");
-    if (c->reciprocal && cfg->corr == SYMMICP_CORR_IDENTITY)
+    if (c->rej.reciprocal && cfg->corr == SYMMICP_CORR_IDENTITY)
         return fail(c, SYMMICP_ERR_ARG, "identity pairs were never searched: no reciprocal correspondences (switch them off first)");
     if (cfg->mode == SYMMICP_MODE_COLOR && c->nranks > 1)
         return fail(c, SYMMICP_ERR_STATE, "SYMMICP_MODE_COLOR runs on single-rank contexts only");
@@ -244,9 +244,7 @@ int symmicp_set_config(symmicp_ctx *c, const symmicp_config *cfg)
     c->cfg = *cfg;
     c->cfg.device = dev;
     c->begun = false;
-    c->trim_valid = false;
-    c->rej_valid = c->rej_new = false;
-    c->recip_valid = false;
+    c->rej.invalidate();
     return SYMMICP_OK;
 }
 
@@ -285,25 +283,25 @@ int symmicp_set_trim_fraction(symmicp_ctx *c, float fraction)
     if (!(fraction > 0.f && fraction <= 1.f)) return fail(c, SYMMICP_ERR_ARG, "trim fraction: 0 < fraction <= 1");      // (NaN fails both)
     if (fraction < 1.f && c->cfg.mode == SYMMICP_MODE_QUIRKS) return fail(c, SYMMICP_ERR_ARG, "QUIRKS takes no trim fraction below 1");
     if (fraction < 1.f && c->nranks > 1) return fail(c, SYMMICP_ERR_STATE, "trimming needs a quantile over all ranks: single-rank contexts only");
-    if (fraction < 1.f && c->med_factor > 0.0f) return fail(c, SYMMICP_ERR_ARG, "a trim fraction below 1 and a median factor exclude each other (set the factor to 0 first)");
-    c->trim_frac = fraction;
+    if (fraction < 1.f && c->rej.median()) return fail(c, SYMMICP_ERR_ARG, "a trim fraction below 1 and a median factor exclude each other (set the factor to 0 first)");
+    c->rej.trim_frac = fraction;
     return SYMMICP_OK;
 }
 
 int symmicp_get_trim_fraction(const symmicp_ctx *c, float *fraction)
 {
     if (!c || !fraction) return SYMMICP_ERR_ARG;
-    *fraction = c->trim_frac;
+    *fraction = c->rej.trim_frac;
     return SYMMICP_OK;
 }
 
 int symmicp_get_trim_state(const symmicp_ctx *c, uint64_t *candidates, uint64_t *kept, float *tau_d2)
 {
     if (!c) return SYMMICP_ERR_ARG;
-    if (!c->begun || !c->trim_valid) return SYMMICP_ERR_STATE;      // (const context: no message)
-    if (candidates) *candidates = c->trim_nc;
-    if (kept) *kept = c->trim_kept;
-    if (tau_d2) std::memcpy(tau_d2, &c->trim_tau, sizeof(float));
+    if (!c->begun || !c->rej.trim_state_valid()) return SYMMICP_ERR_STATE;      // (const context: no message)
+    if (candidates) *candidates = c->rej.last.population;
+    if (kept) *kept = c->rej.last.kept;
+    if (tau_d2) std::memcpy(tau_d2, &c->rej.last.tau_bits, sizeof(float));
     return SYMMICP_OK;
 }
 
@@ -313,14 +311,14 @@ int symmicp_set_one_to_one(symmicp_ctx *c, int on)
     if (!c) return SYMMICP_ERR_ARG;
     if (on && c->cfg.mode == SYMMICP_MODE_QUIRKS) return fail(c, SYMMICP_ERR_ARG, "QUIRKS takes no one-to-one rejector");
     if (on && c->nranks > 1) return fail(c, SYMMICP_ERR_STATE, "the one-to-one claim needs a minimum over all ranks: single-rank contexts only");
-    c->one_to_one = on != 0;
+    c->rej.one_to_one = on != 0;
     return SYMMICP_OK;
 }
 
 int symmicp_get_one_to_one(const symmicp_ctx *c, int *on)
 {
     if (!c || !on) return SYMMICP_ERR_ARG;
-    *on = c->one_to_one ? 1 : 0;
+    *on = c->rej.one_to_one ? 1 : 0;
     return SYMMICP_OK;
 }
 
@@ -330,26 +328,26 @@ int symmicp_set_median_factor(symmicp_ctx *c, float factor)
     if (!(factor == 0.f || (std::isfinite(factor) && factor > 0.f))) return fail(c, SYMMICP_ERR_ARG, "median factor: 0 (off), or finite and > 0");
     if (factor > 0.f && c->cfg.mode == SYMMICP_MODE_QUIRKS) return fail(c, SYMMICP_ERR_ARG, "QUIRKS takes no median-distance rejector");
     if (factor > 0.f && c->nranks > 1) return fail(c, SYMMICP_ERR_STATE, "the median needs a quantile over all ranks: single-rank contexts only");
-    if (factor > 0.f && c->trim_frac < 1.0f) return fail(c, SYMMICP_ERR_ARG, "a median factor and a trim fraction below 1 exclude each other (set the fraction to 1 first)");
-    c->med_factor = factor == 0.f ? 0.f : factor;      // (-0 is off too)
+    if (factor > 0.f && c->rej.trims()) return fail(c, SYMMICP_ERR_ARG, "a median factor and a trim fraction below 1 exclude each other (set the fraction to 1 first)");
+    c->rej.med_factor = factor == 0.f ? 0.f : factor;      // (-0 is off too)
     return SYMMICP_OK;
 }
 
 int symmicp_get_median_factor(const symmicp_ctx *c, float *factor)
 {
     if (!c || !factor) return SYMMICP_ERR_ARG;
-    *factor = c->med_factor;
+    *factor = c->rej.med_factor;
     return SYMMICP_OK;
 }
 
 int symmicp_get_rejection_state(const symmicp_ctx *c, uint64_t *gated, uint64_t *unique, uint64_t *kept, float *tau_d2)
 {
     if (!c) return SYMMICP_ERR_ARG;
-    if (!c->begun || !c->rej_new) return SYMMICP_ERR_STATE;      // (const context: no message)
-    if (gated) *gated = c->rej_gated;
-    if (unique) *unique = c->rej_unique;
-    if (kept) *kept = c->trim_kept;
-    if (tau_d2) std::memcpy(tau_d2, &c->trim_tau, sizeof(float));
+    if (!c->begun || !c->rej.rejection_state_valid()) return SYMMICP_ERR_STATE;      // (const context: no message)
+    if (gated) *gated = c->rej.last.gated;
+    if (unique) *unique = c->rej.last.population;      // (the claim's winners; without a claim every candidate)
+    if (kept) *kept = c->rej.last.kept;
+    if (tau_d2) std::memcpy(tau_d2, &c->rej.last.tau_bits, sizeof(float));
     return SYMMICP_OK;
 }
 
@@ -360,23 +358,23 @@ int symmicp_set_reciprocal(symmicp_ctx *c, int on)
     if (on && c->cfg.mode == SYMMICP_MODE_QUIRKS) return fail(c, SYMMICP_ERR_ARG, "QUIRKS takes no reciprocal correspondences");
     if (on && c->cfg.corr == SYMMICP_CORR_IDENTITY) return fail(c, SYMMICP_ERR_ARG, "identity pairs were never searched: no reciprocal correspondences");
     if (on && c->nranks > 1) return fail(c, SYMMICP_ERR_STATE, "reciprocal correspondences need the claim and the source index over all ranks: single-rank contexts only");
-    c->reciprocal = on != 0;
+    c->rej.reciprocal = on != 0;
     return SYMMICP_OK;
 }
 
 int symmicp_get_reciprocal(const symmicp_ctx *c, int *on)
 {
     if (!c || !on) return SYMMICP_ERR_ARG;
-    *on = c->reciprocal ? 1 : 0;
+    *on = c->rej.reciprocal ? 1 : 0;
     return SYMMICP_OK;
 }
 
 int symmicp_get_reciprocal_state(const symmicp_ctx *c, uint64_t *claimed, uint64_t *reciprocal)
 {
     if (!c) return SYMMICP_ERR_ARG;
-    if (!c->begun || !c->recip_valid) return SYMMICP_ERR_STATE;      // (const context: no message)
-    if (claimed) *claimed = c->recip_claimed;
-    if (reciprocal) *reciprocal = c->recip_n;
+    if (!c->begun || !c->rej.reciprocal_state_valid()) return SYMMICP_ERR_STATE;      // (const context: no message)
+    if (claimed) *claimed = c->rej.last.claimed;
+    if (reciprocal) *reciprocal = c->rej.last.reciprocal;
     return SYMMICP_OK;
 }
 
@@ -453,13 +451,7 @@ int symmicp_set_source_intensity(symmicp_ctx *c, const float *intensity, size_t 
     HIP_TRY(c, hipSetDevice(c->device));
     c->have_src_int = false;
     c->begun = false;
-    const size_t want = c->n_loc ? c->n_loc : 1;
-    if (c->src_int_cap < want) {
-        hipFree(c->src_int);
-        c->src_int = nullptr; c->src_int_cap = 0;
-        HIP_TRY(c, hipMalloc((void **)&c->src_int, sizeof(float) * want));
-        c->src_int_cap = want;
-    }
+    HIP_TRY(c, grow(c->src_int, c->src_int_cap, c->n_loc ? c->n_loc : 1));
     arena_begin(c->arena, n * 4 + 4096);
     DevBuf<float> raw;
     HIP_TRY(c, raw.alloc_temp(c->arena, n));
@@ -484,12 +476,7 @@ int symmicp_set_target_intensity(symmicp_ctx *c, const float *intensity, size_t 
     HIP_TRY(c, hipSetDevice(c->device));
     c->have_tgt_color = false;
     c->begun = false;
-    if (c->tgt_color_cap < n) {
-        hipFree(c->tgt_color);
-        c->tgt_color = nullptr; c->tgt_color_cap = 0;
-        HIP_TRY(c, hipMalloc((void **)&c->tgt_color, sizeof(float4) * n));
-        c->tgt_color_cap = n;
-    }
+    HIP_TRY(c, grow(c->tgt_color, c->tgt_color_cap, n));
     arena_begin(c->arena, n * 16 + 8192);
     DevBuf<float> di, dg;
     HIP_TRY(c, di.alloc_temp(c->arena, n));
@@ -916,9 +903,7 @@ int symmicp_set_source(symmicp_ctx *c, const float *xyz, size_t xr, size_t xc, c
     const double t0 = now_s();
     forget_source(c);
     c->begun = false;
-    c->trim_valid = false;
-    c->rej_valid = c->rej_new = false;
-    c->recip_valid = false;
+    c->rej.invalidate();
     // This rank's share is a contiguous block of the CALLER's rows, and only those rows are uploaded and sorted: set_source costs
     // 1/nranks of the single-GPU call on every rank (round 1 uploaded and sorted the whole cloud on every rank and kept a
     // slice of the global Morton order).  Any partition of the source is exact -- queries are independent given the
@@ -951,12 +936,7 @@ int symmicp_set_source(symmicp_ctx *c, const float *xyz, size_t xr, size_t xc, c
     const size_t o_pkt = tree ? take(sizeof(uint32_t) * 2 * 8 * ((nl + 63) / 64)) : 0;        // (a block of 64 queries may be cut into 8 packets: kMaxRunsPerBlock)
     const size_t o_prec = tree ? take(sizeof(float4) * 2 * nl) : 0;
     const size_t o_wl = tree ? take(sizeof(uint32_t) * 2 * per_list) : 0, o_cnt = tree ? take(sizeof(uint32_t) * 2 * ncount) : 0;      // work + retry lists
-    if (off > c->src_all_cap) {
-        hipFree(c->src_all);
-        c->src_all = nullptr; c->src_all_cap = 0;
-        HIP_TRY(c, hipMalloc((void **)&c->src_all, off));
-        c->src_all_cap = off;
-    }
+    HIP_TRY(c, grow(c->src_all, c->src_all_cap, off));
     c->n_s_total = (uint32_t)n;
     c->src_off = (uint32_t)b0;
     c->n_loc = (uint32_t)bc;
@@ -1128,7 +1108,7 @@ int symmicp_get_correspondences(symmicp_ctx *c, int32_t *idx, float *d2, size_t 
     }
     // (after a pass with a rejector -- trim fraction, one-to-one, median -- a row that was no candidate, or was rejected, is reported as rejected)
     launch_corr_out(c->pos, c->best64, c->d2, c->tq, c->src_order, c->n_loc, mode, c->src_off, d_idx.p, d_d2.p,
-                    c->rej_valid ? c->trim_keys : nullptr, c->trim_tau, c->stream);
+                    c->rej.keys_valid() ? c->rej.keys : nullptr, c->rej.last.tau_bits, c->stream);
     if (idx) HIP_TRY(c, hipMemcpyAsync(idx, d_idx.p, sizeof(int32_t) * need, hipMemcpyDeviceToHost, c->stream));
     if (d2) HIP_TRY(c, hipMemcpyAsync(d2, d_d2.p, sizeof(float) * need, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));

@@ -58,15 +58,23 @@ int symmicp_shard_range(size_t n, int nranks, int rank, size_t *begin, size_t *c
     return SYMMICP_OK;
 }
 
+// what keeps a context on one rank: every rejector (its quantile, claim or source index spans all ranks) and COLOR
+static int refuse_sharding(symmicp_ctx *c, int nranks)
+{
+    if (nranks <= 1) return SYMMICP_OK;
+    if (c->rej.trims()) return fail(c, SYMMICP_ERR_STATE, "a trimming context (symmicp_set_trim_fraction below 1) cannot be sharded: the threshold is a quantile over all ranks");
+    if (c->rej.one_to_one || c->rej.median()) return fail(c, SYMMICP_ERR_STATE, "a context with the one-to-one or the median-distance rejector cannot be sharded: the claim and the median span all ranks");
+    if (c->rej.reciprocal) return fail(c, SYMMICP_ERR_STATE, "a context with reciprocal correspondences cannot be sharded: the claim and the source index span all ranks");
+    if (c->cfg.mode == SYMMICP_MODE_COLOR) return fail(c, SYMMICP_ERR_STATE, "a SYMMICP_MODE_COLOR context cannot be sharded");
+    return SYMMICP_OK;
+}
+
 int symmicp_comm_init_rank(symmicp_ctx *c, int nranks, int rank, const void *uid)
 {
     if (!c) return SYMMICP_ERR_ARG;
     if (nranks < 1 || rank < 0 || rank >= nranks) return fail(c, SYMMICP_ERR_ARG, "bad rank/nranks");
     if (c->src0_block) return fail(c, SYMMICP_ERR_STATE, "attach the communicator before symmicp_set_source");
-    if (nranks > 1 && c->trim_frac < 1.0f) return fail(c, SYMMICP_ERR_STATE, "a trimming context (symmicp_set_trim_fraction below 1) cannot be sharded: the threshold is a quantile over all ranks");
-    if (nranks > 1 && (c->one_to_one || c->med_factor > 0.0f)) return fail(c, SYMMICP_ERR_STATE, "a context with the one-to-one or the median-distance rejector cannot be sharded: the claim and the median span all ranks");
-    if (nranks > 1 && c->reciprocal) return fail(c, SYMMICP_ERR_STATE, "a context with reciprocal correspondences cannot be sharded: the claim and the source index span all ranks");
-    if (nranks > 1 && c->cfg.mode == SYMMICP_MODE_COLOR) return fail(c, SYMMICP_ERR_STATE, "a SYMMICP_MODE_COLOR context cannot be sharded");
+    if (int st = refuse_sharding(c, nranks)) return st;
     // a 1-rank communicator is legal RCCL; it is only built on request (exercises the RCCL path on one GPU)
     if (nranks == 1 && !c->sw.force_comm) { c->nranks = 1; c->rank = 0; return SYMMICP_OK; }
     if (!uid) {
@@ -92,10 +100,7 @@ int symmicp_comm_init_shm(symmicp_ctx *c, int nranks, int rank, const char *job_
     if (!c) return SYMMICP_ERR_ARG;
     if (nranks < 1 || rank < 0 || rank >= nranks || !job_name || !*job_name) return fail(c, SYMMICP_ERR_ARG, "bad rank/nranks/name");
     if (c->src0_block) return fail(c, SYMMICP_ERR_STATE, "attach the exchange before symmicp_set_source");
-    if (nranks > 1 && c->trim_frac < 1.0f) return fail(c, SYMMICP_ERR_STATE, "a trimming context (symmicp_set_trim_fraction below 1) cannot be sharded: the threshold is a quantile over all ranks");
-    if (nranks > 1 && (c->one_to_one || c->med_factor > 0.0f)) return fail(c, SYMMICP_ERR_STATE, "a context with the one-to-one or the median-distance rejector cannot be sharded: the claim and the median span all ranks");
-    if (nranks > 1 && c->reciprocal) return fail(c, SYMMICP_ERR_STATE, "a context with reciprocal correspondences cannot be sharded: the claim and the source index span all ranks");
-    if (nranks > 1 && c->cfg.mode == SYMMICP_MODE_COLOR) return fail(c, SYMMICP_ERR_STATE, "a SYMMICP_MODE_COLOR context cannot be sharded");
+    if (int st = refuse_sharding(c, nranks)) return st;
     if (c->comm || c->shm.slots) return fail(c, SYMMICP_ERR_STATE, "a communicator is already attached");
     std::string name = std::string("/symmicp_") + job_name;
     for (char &ch : name) if (ch == '/' && &ch != &name[0]) ch = '_';

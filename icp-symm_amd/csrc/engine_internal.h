@@ -145,6 +145,45 @@ struct ReverseIndex {
     bool valid = false;
 };
 
+// The rejectors of a context (symmicp_set_trim_fraction / _one_to_one / _median_factor / _reciprocal): what is set, the buffers a rejecting
+// pass runs on (allocated by the first such pass, kept for the next), and what the most recent pass left for the three state getters.
+struct Rejectors {
+    float trim_frac = 1.0f, med_factor = 0.0f;    // 1 and 0: off
+    bool one_to_one = false, reciprocal = false;
+    uint32_t *keys = nullptr, *ws = nullptr;      // per share row; the select's workspace
+    unsigned long long *table = nullptr;          // the claim table: one word per target point, and behind them a reciprocal pass's RecipArgs
+    size_t keys_cap = 0, table_cap = 0;
+    ReverseIndex src_ix;             // reciprocal: the index over the original source, built by the first reciprocal pass after a set_source
+    uint64_t src_ix_builds = 0;      // ... builds since symmicp_create (symmicp_ctx_reciprocal_info: tests)
+    RecipArgs recip_args{};          // ... host copy of what the pass's kernel reads: that index and the inverse of c->X
+    // the most recent pass: which rejectors were set when it ran (0: it rejected nothing, or there was none since set_config / set_source)
+    enum : uint32_t { kTrim = 1, kMedian = 2, kOneToOne = 4, kReciprocal = 8 };
+    uint32_t ran = 0;
+    RejectRecord last{};
+    void invalidate() { ran = 0; }
+
+    bool trims() const { return trim_frac < 1.0f; }
+    bool median() const { return med_factor > 0.0f; }
+    // Identity pairs are one-to-one as they are: the option launches nothing there.  Reciprocal correspondences (never IDENTITY: the setter
+    // and set_config see to it) imply the claim.
+    bool claims(int corr) const { return (one_to_one || reciprocal) && corr != SYMMICP_CORR_IDENTITY; }
+    bool checks_back(int corr) const { return reciprocal && corr != SYMMICP_CORR_IDENTITY; }
+    bool rejects(int corr) const { return trims() || median() || claims(corr); }
+    uint32_t settings_mask(int corr) const
+    {
+        if (!rejects(corr)) return 0u;
+        return (trims() ? kTrim : 0u) | (median() ? kMedian : 0u) | (one_to_one ? kOneToOne : 0u) | (checks_back(corr) ? kReciprocal : 0u);
+    }
+    // what the getters may report: the keys (symmicp_get_correspondences) after any rejecting pass, symmicp_get_trim_state after a trimmed
+    // one, symmicp_get_rejection_state after one with any of the other three, symmicp_get_reciprocal_state after a reciprocal one
+    bool keys_valid() const { return ran != 0u; }
+    bool trim_state_valid() const { return (ran & kTrim) != 0u; }
+    bool rejection_state_valid() const { return (ran & (kMedian | kOneToOne | kReciprocal)) != 0u; }
+    bool reciprocal_state_valid() const { return (ran & kReciprocal) != 0u; }
+    // 64-bit words of the claim table for n_t target points
+    static size_t table_words(size_t n_t, bool with_recip_tail) { return (n_t ? n_t : 1) + (with_recip_tail ? kRecipTailWords : 0); }
+};
+
 struct symmicp_ctx {
     Switches sw;                     // environment switches as they stood at symmicp_create
     Arena arena;                     // temporaries of one public call
@@ -163,32 +202,7 @@ struct symmicp_ctx {
     float *src_int = nullptr;
     size_t tgt_color_cap = 0, src_int_cap = 0;
     bool have_tgt_color = false, have_src_int = false;
-    // trimmed ICP (symmicp_set_trim_fraction): the fraction (1 = off), the per-row keys and the select's workspace (allocated by the
-    // first trimmed pass), and what the most recent pass left (symmicp_get_trim_state; trim_valid: that pass was trimmed)
-    float trim_frac = 1.0f;
-    uint32_t *trim_keys = nullptr, *trim_ws = nullptr;
-    size_t trim_keys_cap = 0;
-    bool trim_valid = false;
-    uint32_t trim_nc = 0, trim_kept = 0, trim_tau = 0;
-    // the one-to-one and median-distance rejectors (symmicp_set_one_to_one / symmicp_set_median_factor): they share trim_keys, trim_ws and
-    // the trimming instantiations.  uniq_table: the claim table, one word per target point, allocated by the first one-to-one pass.
-    // rej_valid: the most recent pass ran a rejector of any kind (its keys say which rows were kept); rej_new: one of these two
-    // (symmicp_get_rejection_state); rej_gated = n_c, rej_unique = n_u (= n_c without one-to-one)
-    bool one_to_one = false;
-    float med_factor = 0.0f;
-    unsigned long long *uniq_table = nullptr;
-    size_t uniq_table_cap = 0;
-    bool rej_valid = false, rej_new = false;
-    uint32_t rej_gated = 0, rej_unique = 0;
-    // reciprocal correspondences (symmicp_set_reciprocal): the index over the original source (src_ix, built by the first reciprocal pass
-    // after a set_source, dropped by the next one), what the pass's launcher reads (recip_args: the index and the inverse of c->X), and
-    // n_u / n_r of the most recent pass (symmicp_get_reciprocal_state; recip_valid: that pass was reciprocal)
-    bool reciprocal = false;
-    ReverseIndex src_ix;
-    uint64_t src_ix_builds = 0;      // builds of src_ix by passes since symmicp_create (symmicp_ctx_reciprocal_info: tests)
-    RecipArgs recip_args{};
-    bool recip_valid = false;
-    uint32_t recip_claimed = 0, recip_n = 0;
+    Rejectors rej;                   // trim fraction, one-to-one, median distance, reciprocal: settings, buffers, the last pass's result
     int device = 0;
     hipStream_t stream = nullptr;
     std::string err;
@@ -291,6 +305,18 @@ struct DevBuf {
     T *release() { T *q = p; p = nullptr; return q; }           // (owned buffers only)
 };
 
+// a context-owned device array that only grows: at least `want` elements afterwards, contents dead
+template <typename T>
+inline hipError_t grow(T *&p, size_t &cap, size_t want)
+{
+    if (cap >= want) return hipSuccess;
+    hipFree(p);
+    p = nullptr; cap = 0;
+    const hipError_t e = hipMalloc((void **)&p, sizeof(T) * want);
+    if (e == hipSuccess) cap = want;
+    return e;
+}
+
 // persistent allocation for the target: from the context's keep-arena when it fits, else its own hipMalloc (tracked)
 hipError_t keep_alloc(symmicp_ctx *c, void **out, size_t bytes);
 // rewind the arena and make sure it holds `want` bytes (contents are dead: called at the start of a public call)
@@ -322,6 +348,11 @@ inline void identity16(float X[16])
 {
     for (int k = 0; k < 16; k++) X[k] = (k % 5 == 0) ? 1.f : 0.f;
 }
+
+// the pass-time questions about the rejectors, for the loop, the exchange and the configuration alike
+inline bool pass_claims(const symmicp_ctx *c) { return c->rej.claims(c->cfg.corr); }
+inline bool pass_reciprocal(const symmicp_ctx *c) { return c->rej.checks_back(c->cfg.corr); }
+inline bool pass_rejects(const symmicp_ctx *c) { return c->rej.rejects(c->cfg.corr); }
 
 inline int resolved_apply(const symmicp_config &c)
 {

@@ -5,13 +5,71 @@
 extern "C" {
 
 // ---- one pass over the source share ------------------------------------------------------------
-// The rejectors of a pass (symmicp.h: trim fraction, one-to-one, median distance).  Identity pairs are one-to-one as they are: the option
-// launches nothing there.  Reciprocal correspondences (never IDENTITY: the setter and set_config see to it) imply the claim.
-static bool pass_claims(const symmicp_ctx *c) { return (c->one_to_one || c->reciprocal) && c->cfg.corr != SYMMICP_CORR_IDENTITY; }
-static bool pass_reciprocal(const symmicp_ctx *c) { return c->reciprocal && c->cfg.corr != SYMMICP_CORR_IDENTITY; }
-static bool pass_rejects(const symmicp_ctx *c) { return c->trim_frac < 1.0f || c->med_factor > 0.0f || pass_claims(c); }
+// The rejectors of the next pass (symmicp.h: trim fraction, one-to-one, median distance, reciprocal): the buffers, for a reciprocal pass the
+// source index and this pass's RecipArgs in device memory, and what the pass kernels read.  With none set: nothing is touched, r stays zero
+// and the pass is the one of a build without rejectors.  The result lands behind the record's sequence word in host-mapped memory.
+static int prepare_rejectors(symmicp_ctx *c, RejectArgs &r)
+{
+    Rejectors &j = c->rej;
+    r = RejectArgs{};
+    if (!pass_rejects(c)) return SYMMICP_OK;
+    HIP_TRY(c, grow(j.keys, j.keys_cap, c->n_loc ? c->n_loc : 1));
+    if (!j.ws) HIP_TRY(c, hipMalloc((void **)&j.ws, sizeof(uint32_t) * kRejectWsWords));
+    r.keys = j.keys; r.ws = j.ws;
+    r.host = reinterpret_cast<RejectRecord *>(c->h_sums_dev + kNSum + 1);
+    r.rho = j.trim_frac; r.med_f2 = j.median() ? j.med_factor * j.med_factor : 0.0f;
+    if (!pass_claims(c)) return SYMMICP_OK;
+    HIP_TRY(c, grow(j.table, j.table_cap, Rejectors::table_words(c->n_t, pass_reciprocal(c))));
+    r.table = j.table; r.n_t = c->n_t; r.order = c->src_order;
+    r.claim = kClaimOneToOne;
+    if (!pass_reciprocal(c)) return SYMMICP_OK;
+    // the source index: once per set_source, over the whole original source, labelled with the caller's rows; and this pass's inverse
+    if (!j.src_ix.valid) {
+        const double t0 = now_s();
+        if (int st = build_reverse_index(c, c->src0, c->n_loc, c->src_order, j.src_ix)) return st;
+        j.src_ix_builds++;
+        if (c->sw.debug_host) {
+            std::fprintf(stderr, "[symmicp host] source index: %u points, %zu bytes in its arena (+%zu allocations beside it), built in %.3f ms\n", c->n_loc,
+                         j.src_ix.keep.off, j.src_ix.extra.size(), (now_s() - t0) * 1e3);
+        }
+    }
+    j.recip_args.six = j.src_ix.ix;
+    symmicp_inverse_rigid(c->X, j.recip_args.inv.m);
+    j.recip_args.inv.nrm_w = 0.0f;
+    RecipArgs *tail = reinterpret_cast<RecipArgs *>(j.table + c->n_t);      // (table_words left the room)
+    // (a pageable source that the next pass overwrites: safe because a copy this small is staged before the call returns, and because
+    // the host loop waits for every pass's record before it comes here again.  A loop that queued rejecting passes would need a slot per pass)
+    HIP_TRY(c, hipMemcpyAsync(tail, &j.recip_args, sizeof(RecipArgs), hipMemcpyHostToDevice, c->stream));
+    r.recip = tail; r.claim = kClaimReciprocal;
+    return SYMMICP_OK;
+}
 
-static void fill_pass_args(symmicp_ctx *c, PassArgs &a, const float Xapply[16], bool from_cur, bool writeback, bool first)
+// Waits until the device has written seq to a host-mapped word: a spin instead of a stream-synchronise wake-up.  A stream that ends
+// without the word (kernel fault), or limit_seconds of nothing, falls back to the synchronise and its error.  spun: the time in the spin is added
+static int wait_for_word(symmicp_ctx *c, const volatile unsigned long long *flag, unsigned long long seq, double limit_seconds, const char *what,
+                         double *spun = nullptr)
+{
+    const double t0 = now_s();
+    unsigned spins = 0;
+    bool got = false;
+    while (!(got = (*flag == seq))) {
+        __builtin_ia32_pause();
+        if ((++spins & 0xFFFu) == 0) {
+            if (hipStreamQuery(c->stream) != hipErrorNotReady) { got = (*flag == seq); break; }
+            if (now_s() - t0 > limit_seconds) break;
+        }
+    }
+    __atomic_thread_fence(__ATOMIC_ACQUIRE);
+    if (spun) *spun += now_s() - t0;
+    if (!got) {
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        HIP_TRY(c, hipGetLastError());
+        if (*flag != seq) return fail(c, SYMMICP_ERR_HIP, what);
+    }
+    return SYMMICP_OK;
+}
+
+static void fill_pass_args(symmicp_ctx *c, PassArgs &a, const RejectArgs &rej, const float Xapply[16], bool from_cur, bool writeback, bool first)
 {
     a.in = from_cur ? c->cur : c->src0;
     a.out = c->cur;
@@ -57,70 +115,19 @@ static void fill_pass_args(symmicp_ctx *c, PassArgs &a, const float Xapply[16], 
     a.pkt_lds_pad = c->sw.packet_lds_pad;
     a.loss = c->loss;
     a.loss_scale = c->loss_scale;
-    // pass with a rejector (run_pass has made sure of the buffers); the result lands behind the record's sequence word in host-mapped memory
-    const bool trim = pass_rejects(c) && c->trim_keys && c->trim_ws;
-    a.trim_keys = trim ? c->trim_keys : nullptr;
-    a.trim_ws = trim ? c->trim_ws : nullptr;
-    a.trim_host = trim ? reinterpret_cast<uint32_t *>(c->h_sums_dev + kNSum + 1) : nullptr;
-    const bool uniq = trim && pass_claims(c) && c->uniq_table;
-    a.uniq_table = uniq ? c->uniq_table : nullptr;
-    a.uniq_order = uniq ? c->src_order : nullptr;
-    a.uniq_n_t = uniq ? (uint32_t)c->n_t : 0u;
-    a.trim_uniq = uniq ? (pass_reciprocal(c) && c->src_ix.valid ? 2 : 1) : 0;      // (2: run_pass has left the RecipArgs behind the table)
-    a.med_f2 = trim && c->med_factor > 0.0f ? c->med_factor * c->med_factor : 0.0f;
-    a.trim_rho = c->trim_frac;
+    a.rej = rej;
 }
 
 static int run_pass(symmicp_ctx *c, const float Xapply[16], bool from_cur, bool writeback, bool first)
 {
-    // Trimmed pass (trim_frac < 1): search as always, then the keys of the candidates and the exact select of tau (kernels_select.hip:
-    // one memset and six launches, issued by the pass launchers in front of the accumulating kernel), then the accumulation over the
-    // pairs at or below tau and the final reduce.  The one-to-one claim (one memset and k_unique_claim in front of the keys) and the
-    // median factor (tau = factor^2 x the select's median, then a counting pass) go the same way: any of the three makes this a rejecting
-    // pass.  With none of them set nothing below differs from a build without them.
-    const bool trim = pass_rejects(c);
-    if (trim && pass_claims(c)) {
-        const size_t want = (c->n_t ? c->n_t : 1) + (pass_reciprocal(c) ? kRecipTailWords : 0);      // (the tail: what a reciprocal pass hands its kernel)
-        if (c->uniq_table_cap < want) {
-            hipFree(c->uniq_table);
-            c->uniq_table = nullptr; c->uniq_table_cap = 0;
-            HIP_TRY(c, hipMalloc((void **)&c->uniq_table, sizeof(unsigned long long) * want));
-            c->uniq_table_cap = want;
-        }
-    }
-    if (trim) {
-        const size_t want = c->n_loc ? c->n_loc : 1;
-        if (c->trim_keys_cap < want) {
-            hipFree(c->trim_keys);
-            c->trim_keys = nullptr; c->trim_keys_cap = 0;
-            HIP_TRY(c, hipMalloc((void **)&c->trim_keys, sizeof(uint32_t) * want));
-            c->trim_keys_cap = want;
-        }
-        if (!c->trim_ws) HIP_TRY(c, hipMalloc((void **)&c->trim_ws, sizeof(uint32_t) * kTrimWsWords));
-    }
-    if (trim && pass_reciprocal(c)) {
-        // the source index: once per set_source, over the whole original source, labelled with the caller's rows; and this pass's inverse
-        if (!c->src_ix.valid) {
-            const double t0 = now_s();
-            if (int st = build_reverse_index(c, c->src0, c->n_loc, c->src_order, c->src_ix)) return st;
-            c->src_ix_builds++;
-            if (c->sw.debug_host) {
-                std::fprintf(stderr, "[symmicp host] source index: %u points, %zu bytes in its arena (+%zu allocations beside it), built in %.3f ms\n", c->n_loc,
-                             c->src_ix.keep.off, c->src_ix.extra.size(), (now_s() - t0) * 1e3);
-            }
-        }
-        c->recip_args.six = c->src_ix.ix;
-        symmicp_inverse_rigid(c->X, c->recip_args.inv.m);
-        c->recip_args.inv.nrm_w = 0.0f;
-        // (a pageable source that the next pass overwrites: safe because a copy this small is staged before the call returns, and because
-        // the host loop waits for every pass's record before it comes here again.  A loop that queued rejecting passes would need a slot per pass)
-        HIP_TRY(c, hipMemcpyAsync(c->uniq_table + c->n_t, &c->recip_args, sizeof(RecipArgs), hipMemcpyHostToDevice, c->stream));
-    }
-    c->trim_valid = false;
-    c->rej_valid = c->rej_new = false;
-    c->recip_valid = false;
+    // A rejecting pass: search as always, then the claim, the keys of the candidates and tau (kernels_select.hip: issued by the pass
+    // launchers in front of the accumulating kernel), then the accumulation over the pairs at or below tau and the final reduce.
     PassArgs a{};
-    fill_pass_args(c, a, Xapply, from_cur, writeback, first);
+    RejectArgs rej;
+    if (int st = prepare_rejectors(c, rej)) return st;
+    c->rej.invalidate();
+    fill_pass_args(c, a, rej, Xapply, from_cur, writeback, first);
+    const bool rejecting = pass_rejects(a);
     int blocks = (int)((c->n_loc + kPassThreads - 1) / kPassThreads);
     int cap = c->sw.pass_blocks;
     if (cap > 8192) cap = 8192;
@@ -181,7 +188,7 @@ static int run_pass(symmicp_ctx *c, const float Xapply[16], bool from_cur, bool 
             // after all the pass is repaired below (walk, accumulate and reduce again).
             optimistic = c->sw.optimistic >= 0 ? c->sw.optimistic == 1 : (!first && c->last_list_len == 0);      // (SYMMICP_OPTIMISTIC: "0" never, "1" always)
             if (writeback) optimistic = false;      // in-place write-back: a repair would transform the cloud twice
-            if (trim) optimistic = false;           // the keys are taken from final pairs
+            if (rejecting) optimistic = false;      // the keys are taken from final pairs
             // per-kernel events only in timing mode 2; mode 1 brackets the pass (events 0 and 4)
             if (first && c->target_surface_like) launch_pass_tree_first(a, c->ix, c->wl, ab, c->stream, c->timing == 2 ? ev : nullptr);
             else
@@ -215,24 +222,7 @@ static int run_pass(symmicp_ctx *c, const float Xapply[16], bool from_cur, bool 
         }
         // the final-reduce time is only separated out in per-kernel mode; otherwise event 5 is event 4 again
         if (ev && c->ev_split[c->ev_used] != 1) hipEventRecord(ev[5], c->stream);
-        const double t_spin = now_s();
-        unsigned spins = 0;
-        bool got = false;
-        while (!(got = (*flag == seq))) {
-            __builtin_ia32_pause();
-            if ((++spins & 0xFFFu) == 0) {
-                if (hipStreamQuery(c->stream) != hipErrorNotReady) { got = (*flag == seq); break; }
-                if (now_s() - t_spin > 30.0) break;
-            }
-        }
-        __atomic_thread_fence(__ATOMIC_ACQUIRE);
-        c->t_spin += now_s() - t_spin;
-        if (!got) {
-            HIP_TRY(c, hipStreamSynchronize(c->stream));
-            HIP_TRY(c, hipGetLastError());
-            if (*flag != seq) return fail(c, SYMMICP_ERR_HIP, "pass finished without publishing its record");
-        }
-        return SYMMICP_OK;
+        return wait_for_word(c, flag, seq, 30.0, "pass finished without publishing its record", &c->t_spin);
     };
     if (int st = reduce_and_wait(optimistic ? 1 : 0)) return st;
     if (c->shm.slots) { if (int st = shm_exchange(c, c->h_sums)) return st; }
@@ -249,15 +239,9 @@ static int run_pass(symmicp_ctx *c, const float Xapply[16], bool from_cur, bool 
         if (int st = reduce_and_wait(0)) return st;
         if (c->shm.slots) { if (int st = shm_exchange(c, c->h_sums)) return st; }
     }
-    if (trim) {
-        const volatile uint32_t *w = reinterpret_cast<const volatile uint32_t *>(c->h_sums + kNSum + 1);      // (written before the record: same stream)
-        c->trim_nc = w[0]; c->trim_kept = w[1]; c->trim_tau = w[2];
-        c->rej_gated = w[3]; c->rej_unique = w[0];
-        c->trim_valid = c->trim_frac < 1.0f;
-        c->rej_valid = true;
-        c->rej_new = c->med_factor > 0.0f || c->one_to_one || c->reciprocal;
-        c->recip_valid = a.trim_uniq == 2;
-        c->recip_claimed = w[4]; c->recip_n = w[5];
+    if (rejecting) {
+        std::memcpy(&c->rej.last, c->h_sums + kNSum + 1, sizeof(RejectRecord));      // (written before the record: same stream)
+        c->rej.ran = c->rej.settings_mask(c->cfg.corr);
     }
     if (ev) c->ev_used++;
     c->t_last_done = now_s(); c->n_pass_timed++;
@@ -336,8 +320,6 @@ static int run_batch(symmicp_ctx *c, int want, float *diffs_before, int *n_done,
     lc.list_limit = kLoopListLimit;
     if (lc.max_iters > c->cfg.max_iters) lc.max_iters = c->cfg.max_iters;
     const int it0 = c->iters;
-    float X0[16];
-    std::memcpy(X0, c->X, sizeof(X0));
     // loop state as the host loop left it
     LoopState ls{};
     std::memcpy(ls.X, c->X, sizeof(ls.X));
@@ -352,7 +334,7 @@ static int run_batch(symmicp_ctx *c, int want, float *diffs_before, int *n_done,
     }
     HIP_TRY(c, hipMemcpyAsync(c->d_loop, c->h_loop, sizeof(LoopState), hipMemcpyHostToDevice, c->stream));
     PassArgs a{};
-    fill_pass_args(c, a, c->X, /*from_cur=*/incr, /*writeback=*/incr, /*first=*/false);
+    fill_pass_args(c, a, RejectArgs{}, c->X, /*from_cur=*/incr, /*writeback=*/incr, /*first=*/false);      // (batch_eligible: no rejector)
     a.loop = c->d_loop;
     int blocks;
     bool vec4 = false;
@@ -431,23 +413,7 @@ static int run_batch(symmicp_ctx *c, int want, float *diffs_before, int *n_done,
         }
         const unsigned long long seq = ++c->batch_seq;
         launch_loop_end(c->d_loop, c->h_loop_dev, c->h_done_dev, seq, c->stream);
-        volatile unsigned long long *flag = reinterpret_cast<volatile unsigned long long *>(c->h_done);
-        const double t_spin = now_s();
-        unsigned spins = 0;
-        bool got = false;
-        while (!(got = (*flag == seq))) {
-            __builtin_ia32_pause();
-            if ((++spins & 0xFFFu) == 0) {
-                if (hipStreamQuery(c->stream) != hipErrorNotReady) { got = (*flag == seq); break; }
-                if (now_s() - t_spin > 60.0) break;
-            }
-        }
-        __atomic_thread_fence(__ATOMIC_ACQUIRE);
-        if (!got) {
-            HIP_TRY(c, hipStreamSynchronize(c->stream));
-            HIP_TRY(c, hipGetLastError());
-            if (*flag != seq) return fail(c, SYMMICP_ERR_HIP, "batch finished without publishing its end flag");
-        }
+        if (int st = wait_for_word(c, c->h_done, seq, 60.0, "batch finished without publishing its end flag")) return st;
         enq += nq;
         first_chunk = false;
         // passes of this chunk that did run (a pass that has to be redone ran too); the events of the no-op launches behind a
@@ -491,7 +457,6 @@ static int run_batch(symmicp_ctx *c, int want, float *diffs_before, int *n_done,
         c->st.loop_passes += it1 - it0;
         c->st.loop_straggler_passes += n_stage;
     }
-    (void)X0;
     if (c->loop_log_on) {
         // the batch's passes: it0 (the host's last pass, whose record the solve-only launch solved from) .. it1
         for (int k = it0; k <= it1; k++) {

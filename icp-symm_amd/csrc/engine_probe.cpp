@@ -132,10 +132,10 @@ int symmicp_ctx_select_probe(symmicp_ctx *c, const uint32_t *keys, size_t n, uin
     if (!keys || !kth_out || !n_le_out || n == 0 || n > 0x7fffffffull || k < 1 || k > n) return fail(c, SYMMICP_ERR_ARG, "select_probe: bad arguments");
     HIP_TRY(c, hipSetDevice(c->device));
     const size_t bytes = sizeof(uint32_t) * n;
-    arena_begin(c->arena, bytes + sizeof(uint32_t) * kTrimWsWords + 4096);
+    arena_begin(c->arena, bytes + sizeof(uint32_t) * kRejectWsWords + 4096);
     DevBuf<uint32_t> d, ws;
     HIP_TRY(c, d.alloc_temp(c->arena, n));
-    HIP_TRY(c, ws.alloc_temp(c->arena, kTrimWsWords));      // (its own workspace: the context's trim state stays as it was)
+    HIP_TRY(c, ws.alloc_temp(c->arena, kRejectWsWords));      // (its own workspace: the context's trim state stays as it was)
     HIP_TRY(c, hipMemcpyAsync(d.p, keys, bytes, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     launch_select_probe(d.p, (uint32_t)n, (uint32_t)k, ws.p, c->stream);
@@ -143,7 +143,7 @@ int symmicp_ctx_select_probe(symmicp_ctx *c, const uint32_t *keys, size_t n, uin
     uint32_t state[8] = {};
     HIP_TRY(c, hipMemcpyAsync(state, ws.p, sizeof(state), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    *kth_out = state[kTrimTauWord];
+    *kth_out = state[kRejectTauWord];
     *n_le_out = state[4];
     return SYMMICP_OK;
 }
@@ -220,10 +220,10 @@ int symmicp_ctx_reverse_nn_probe(symmicp_ctx *c, const float *db_xyz, const int3
 int symmicp_ctx_reciprocal_info(const symmicp_ctx *c, int32_t *index_valid, uint64_t *index_bytes, uint64_t *index_builds, uint64_t *table_words)
 {
     if (!c) return SYMMICP_ERR_ARG;
-    if (index_valid) *index_valid = c->src_ix.valid ? 1 : 0;
-    if (index_bytes) *index_bytes = c->src_ix.keep.cap;
-    if (index_builds) *index_builds = c->src_ix_builds;
-    if (table_words) *table_words = c->uniq_table_cap;
+    if (index_valid) *index_valid = c->rej.src_ix.valid ? 1 : 0;
+    if (index_bytes) *index_bytes = c->rej.src_ix.keep.cap;
+    if (index_builds) *index_builds = c->rej.src_ix_builds;
+    if (table_words) *table_words = c->rej.table_cap;
     return SYMMICP_OK;
 }
 

@@ -258,7 +258,7 @@ __global__ __launch_bounds__(256) void k_corr_out(const int32_t *__restrict__ po
                                                   const float *__restrict__ d2, const float4 *__restrict__ tq,
                                                   const uint32_t *__restrict__ src_order, uint32_t n, int mode,
                                                   uint32_t tgt_offset, int32_t *idx_out, float *d2_out,
-                                                  const uint32_t *__restrict__ trim_keys, uint32_t trim_tau)
+                                                  const uint32_t *__restrict__ rej_keys, uint32_t rej_tau)
 {
     uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
@@ -267,7 +267,7 @@ __global__ __launch_bounds__(256) void k_corr_out(const int32_t *__restrict__ po
     if (mode == 0) row = (int32_t)(tgt_offset + i);
     else if (mode == 1) { unsigned long long b = best64[i]; row = (b == ~0ull) ? -1 : (int32_t)(uint32_t)(b & 0xFFFFFFFFull); }
     else { int32_t p = pos[i]; row = (p < 0) ? -1 : __float_as_int(tq[p].w); }
-    if (trim_keys && trim_keys[i] > trim_tau) row = -1;      // trimmed pass: not a candidate (the sentinel), or trimmed away
+    if (rej_keys && rej_keys[i] > rej_tau) row = -1;      // trimmed pass: not a candidate (the sentinel), or trimmed away
     if (idx_out) idx_out[r] = row;
     if (d2_out) d2_out[r] = d2 ? d2[i] : 0.0f;
 }
@@ -525,10 +525,10 @@ void launch_unpermute(const CloudSoA &cur, const uint32_t *order, uint32_t n, fl
 
 void launch_corr_out(const int32_t *pos, const unsigned long long *best64, const float *d2, const float4 *tq,
                      const uint32_t *src_order, uint32_t n, int mode, uint32_t tgt_offset, int32_t *idx_out, float *d2_out,
-                     const uint32_t *trim_keys, uint32_t trim_tau, hipStream_t s)
+                     const uint32_t *rej_keys, uint32_t rej_tau, hipStream_t s)
 {
     hipLaunchKernelGGL(k_corr_out, dim3(nblk(n, 256)), dim3(256), 0, s, pos, best64, d2, tq, src_order, n, mode, tgt_offset,
-                       idx_out, d2_out, trim_keys, trim_tau);
+                       idx_out, d2_out, rej_keys, rej_tau);
 }
 
 void launch_level_hist(const uint32_t *keys, uint32_t n, uint32_t *hist16, hipStream_t s)

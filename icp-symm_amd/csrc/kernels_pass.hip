@@ -276,7 +276,7 @@ __device__ __forceinline__ bool reads_src_normals(bool writeback, float min_ndot
 // as W: the untrimmed kernels are the code they were.  tau has its own "off" (T = false), apart from max_d2, whose 0 means "keep all":
 // tau = 0 keeps the pairs at distance 0 only.
 // The one-to-one and median-distance rejectors run through the same instantiations: the median only derives tau differently, and with
-// PassArgs::trim_uniq set (a runtime flag, not another template axis) the kernel drops the rows whose key is the sentinel before this step.
+// a claim in RejectArgs::claim (a runtime flag, not another template axis) the kernel drops the rows whose key is the sentinel before this step.
 template <int OBJ, bool T = false, int NA>
 __device__ __forceinline__ void pair_step(AccN<NA> &acc, const HotParams &h, float nx, float ny, float nz, float px, float py, float pz,
                                           const float4 &q, const float4 &nq, float d2, uint32_t tau = 0u, const ColorPair *color = nullptr)
@@ -380,7 +380,7 @@ __global__ __launch_bounds__(kPassThreads) void k_pass_identity(PassArgs a_in, C
     if (a_in.loop) a.X = a_in.loop->Xapply;        // device-driven loop: the transform k_reduce_solve left behind
     AccT<W> acc; acc_zero(acc);
     const HotParams h = hot_params(a);
-    const uint32_t tau = T ? a.trim_ws[kTrimTauWord] : 0u;
+    const uint32_t tau = T ? a.rej.ws[kRejectTauWord] : 0u;
     const bool need_n = reads_src_normals<OBJ>(a.writeback, a.min_ndot);
     const uint32_t stride = gridDim.x * blockDim.x * VEC;
     for (uint32_t i0 = (blockIdx.x * blockDim.x + threadIdx.x) * VEC; i0 < a.n; i0 += stride) {
@@ -458,7 +458,7 @@ __global__ __launch_bounds__(kPassThreads) void k_pass_indexed(PassArgs a, const
 {
     AccT<W> acc; acc_zero(acc);
     const HotParams h = hot_params(a);
-    const uint32_t tau = T ? a.trim_ws[kTrimTauWord] : 0u;
+    const uint32_t tau = T ? a.rej.ws[kRejectTauWord] : 0u;
     const bool need_n = reads_src_normals<OBJ>(a.writeback, a.min_ndot);
     const uint32_t stride = gridDim.x * blockDim.x;
     for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < a.n; i += stride) {
@@ -479,7 +479,7 @@ __global__ __launch_bounds__(kPassThreads) void k_pass_indexed(PassArgs a, const
         if (a.d2_out) a.d2_out[i] = ok ? d2 : __int_as_float(0x7f800000);
         if (!ok) continue;
         if (a.max_d2 > 0.0f && d2 > a.max_d2) continue;                  // (pair_step's gate, ahead of the gather it saves)
-        if (T && a.trim_uniq && a.trim_keys[i] == 0xFFFFFFFFu) continue;      // one-to-one: the row lost its target (or is no candidate)
+        if (T && a.rej.claim != kClaimNone && a.rej.keys[i] == 0xFFFFFFFFu) continue;      // one-to-one: the row lost its target (or is no candidate)
         if constexpr (OBJ == kObjColor) {
             const ColorPair cp = color_pair(a, i, j);
             pair_step<OBJ, T>(acc, h, nx, ny, nz, px, py, pz, tn[2 * (size_t)j], tn[2 * (size_t)j + 1], d2, tau, &cp);
@@ -1510,7 +1510,7 @@ __global__ __launch_bounds__(kPassThreads) void k_accumulate(PassArgs a, const f
 {
     AccT<W> acc; acc_zero(acc);
     const HotParams h = hot_params(a);
-    const uint32_t tau = T ? a.trim_ws[kTrimTauWord] : 0u;
+    const uint32_t tau = T ? a.rej.ws[kRejectTauWord] : 0u;
     const bool need_n = reads_src_normals<OBJ>(a.writeback, a.min_ndot);
     const uint32_t nbp = gridDim.x;
     // grid-stride over blocks of 256 points, XCD-contiguous
@@ -1536,7 +1536,7 @@ __global__ __launch_bounds__(kPassThreads) void k_accumulate(PassArgs a, const f
             a.out.nz[i] = xf_row(a.X.m + 8, nx, ny, nz, a.X.nrm_w);
         }
         if (nq.w != 0.0f) continue;                       // no target for this point
-        if (T && a.trim_uniq && a.trim_keys[i] == 0xFFFFFFFFu) continue;      // one-to-one: the row lost its target (or is no candidate)
+        if (T && a.rej.claim != kClaimNone && a.rej.keys[i] == 0xFFFFFFFFu) continue;      // one-to-one: the row lost its target (or is no candidate)
         if constexpr (OBJ == kObjColor) {
             const ColorPair cp = color_pair(a, i, (uint32_t)a.pos_out[i]);      // (gathered by the pair's sorted position: the record copy holds no colour)
             pair_step<OBJ, T>(acc, h, nx, ny, nz, px, py, pz, q, nq, dist2(px, py, pz, q.x, q.y, q.z), tau, &cp);
@@ -1605,7 +1605,7 @@ __device__ __forceinline__ void read_list_words(const uint32_t *cnt, int t, uint
 // and, when given, a host-mapped copy (single-GPU read-back without a memcpy).
 // ---------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_final_reduce(const double *__restrict__ partials, int nblocks,
-                                                      double *out_dev, double *out_host, uint32_t *ticket,
+                                                      double *out_dev, double *out_mapped, uint32_t *ticket,
                                                       unsigned long long seq, uint32_t *counters_to_clear, int keep_nonempty)
 {
     __shared__ double red[256];
@@ -1622,7 +1622,7 @@ __global__ __launch_bounds__(256) void k_final_reduce(const double *__restrict__
     __shared__ int last;
     if (t == 0) {
         out_dev[k] = red[0];
-        if (out_host) out_host[k] = red[0];
+        if (out_mapped) out_mapped[k] = red[0];
         // the block that takes the last ticket publishes the sequence number the host spins on
         __threadfence_system();
         last = (atomicAdd(ticket, 1u) == gridDim.x - 1);
@@ -1644,7 +1644,7 @@ __global__ __launch_bounds__(256) void k_final_reduce(const double *__restrict__
                     // searched this pass (cells_tile).  (Slot 37 is a sum: the pair count of a weighted record.)
                     const double lenw = (double)len + (dropped ? kListDropped : 0.0);
                     out_dev[kNSum - 1] = lenw; out_dev[kNSum - 2] = (double)searched;
-                    if (out_host) { out_host[kNSum - 1] = lenw; out_host[kNSum - 2] = (double)searched; }
+                    if (out_mapped) { out_mapped[kNSum - 1] = lenw; out_mapped[kNSum - 2] = (double)searched; }
                 }
             }
             __syncthreads();
@@ -1655,9 +1655,9 @@ __global__ __launch_bounds__(256) void k_final_reduce(const double *__restrict__
         }
         if (t == 0) {
             *ticket = 0;
-            if (out_host) {
+            if (out_mapped) {
                 __threadfence_system();
-                reinterpret_cast<volatile unsigned long long *>(out_host)[kNSum] = seq;
+                reinterpret_cast<volatile unsigned long long *>(out_mapped)[kNSum] = seq;
             }
         }
     }
@@ -1851,14 +1851,14 @@ __global__ __launch_bounds__(64) void k_loop_end(const LoopState *loop, LoopStat
 }
 
 // multi-GPU: after the RCCL all-reduce, copy the record to host-mapped memory and publish the sequence number
-__global__ __launch_bounds__(64) void k_publish(const double *__restrict__ sums_dev, double *out_host, unsigned long long seq)
+__global__ __launch_bounds__(64) void k_publish(const double *__restrict__ sums_dev, double *out_mapped, unsigned long long seq)
 {
-    if (threadIdx.x < kNSum) out_host[threadIdx.x] = sums_dev[threadIdx.x];
+    if (threadIdx.x < kNSum) out_mapped[threadIdx.x] = sums_dev[threadIdx.x];
     __threadfence_system();
     __syncthreads();
     if (threadIdx.x == 0) {
         __threadfence_system();
-        reinterpret_cast<volatile unsigned long long *>(out_host)[kNSum] = seq;
+        reinterpret_cast<volatile unsigned long long *>(out_mapped)[kNSum] = seq;
     }
 }
 
@@ -1976,8 +1976,8 @@ static void with_instantiation(const PassArgs &a, F &&f)
     else obj(std::false_type());
 }
 
-// ... and T: a trimmed pass (PassArgs::trim_keys set): the keys and the select (kernels_select.hip) run in front of its accumulating
-// kernel, whose trimming instantiation reads the tau they leave.  The kernels of the device-driven loop have no such instantiation
+// ... and T: a rejecting pass (pass_rejects): the claim, the keys and the select (kernels_select.hip) run in front of its accumulating
+// kernel, whose T instantiation reads the tau they leave.  The kernels of the device-driven loop have no such instantiation
 // (batch_eligible keeps a trimming context in the host loop).
 template <typename F>
 static void with_trim(const PassArgs &a, F &&f)
@@ -1986,7 +1986,7 @@ static void with_trim(const PassArgs &a, F &&f)
         // COLOR's instantiations exist for the host loop's accumulating kernels only (with_instantiation, which also serves the fused
         // pass and the straggler stage, does not know them: batch_eligible keeps a COLOR context in the host loop)
         auto trim = [&](auto W) {
-            if (a.trim_keys) f(W, std::integral_constant<int, kObjColor>(), std::true_type());
+            if (pass_rejects(a)) f(W, std::integral_constant<int, kObjColor>(), std::true_type());
             else f(W, std::integral_constant<int, kObjColor>(), std::false_type());
         };
         if (a.loss != SYMMICP_LOSS_NONE) trim(std::true_type());
@@ -1994,14 +1994,14 @@ static void with_trim(const PassArgs &a, F &&f)
         return;
     }
     with_instantiation(a, [&](auto W, auto OBJ) {
-        if (a.trim_keys) f(W, OBJ, std::true_type());
+        if (pass_rejects(a)) f(W, OBJ, std::true_type());
         else f(W, OBJ, std::false_type());
     });
 }
 
 void launch_pass_identity(const PassArgs &a, CloudSoA tgt, int blocks, bool vec4_ok, hipStream_t s)
 {
-    if (a.trim_keys) launch_trim_select(a, SYMMICP_CORR_IDENTITY, tgt, nullptr, s);
+    if (pass_rejects(a)) launch_reject(a, SYMMICP_CORR_IDENTITY, tgt, nullptr, s);
     with_trim(a, [&](auto W, auto OBJ, auto T) {
         if (vec4_ok) hipLaunchKernelGGL((k_pass_identity<4, W, OBJ, T>), dim3(blocks), dim3(kPassThreads), 0, s, a, tgt);
         else hipLaunchKernelGGL((k_pass_identity<1, W, OBJ, T>), dim3(blocks), dim3(kPassThreads), 0, s, a, tgt);
@@ -2010,13 +2010,13 @@ void launch_pass_identity(const PassArgs &a, CloudSoA tgt, int blocks, bool vec4
 
 void launch_pass_indexed(const PassArgs &a, const float4 *tn, int blocks, hipStream_t s)
 {
-    if (a.trim_keys) launch_trim_select(a, SYMMICP_CORR_BRUTE, CloudSoA{}, tn, s);
+    if (pass_rejects(a)) launch_reject(a, SYMMICP_CORR_BRUTE, CloudSoA{}, tn, s);
     with_trim(a, [&](auto W, auto OBJ, auto T) { hipLaunchKernelGGL((k_pass_indexed<W, OBJ, T>), dim3(blocks), dim3(kPassThreads), 0, s, a, tn); });
 }
 
 void launch_accumulate(const PassArgs &a, const float4 *tn, int blocks, hipStream_t s)
 {
-    if (a.trim_keys) launch_trim_select(a, SYMMICP_CORR_TREE, CloudSoA{}, tn, s);
+    if (pass_rejects(a)) launch_reject(a, SYMMICP_CORR_TREE, CloudSoA{}, tn, s);
     with_trim(a, [&](auto W, auto OBJ, auto T) { hipLaunchKernelGGL((k_accumulate<W, OBJ, T>), dim3(blocks), dim3(kPassThreads), 0, s, a, tn); });
 }
 

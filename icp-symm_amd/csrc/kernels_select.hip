@@ -3,7 +3,7 @@
 //
 // A trimmed pass keeps the closest fraction rho of its candidate pairs (include/symmicp.h has the definition).  Between the search
 // and the accumulating kernel of the pass run
-//   k_trim_keys      per share row: the bits of the candidate's fp32 d2 -- non-negative floats order as their bit patterns -- or the
+//   k_reject_keys    per share row: the bits of the candidate's fp32 d2 -- non-negative floats order as their bit patterns -- or the
 //                    sentinel 0xFFFFFFFF for a row without a pair or dropped by a gate; counts the candidates (n_c) and builds the
 //                    histogram of the keys' first digit on the way
 //   k_select_scan    one workgroup: k = ceil(rho n_c) in fp64 (first digit only), prefix sum over the digit's bins, the bin that
@@ -12,20 +12,20 @@
 // as keys, scan, hist, scan, hist, scan: an exact radix select over 32-bit keys in 11 + 11 + 10 bits.  Histograms are per-block in
 // LDS (2048 bins, 8 KB), filled with wave-aggregated LDS atomics (the keys of a pass cluster: a handful of first digits hold them
 // all) and merged into the global one with integer atomics: order-independent, so tau is reproducible bit for bit.  The last scan
-// leaves tau, n_c and the kept count (keys <= tau, ties included) in device memory for the accumulating kernel and in host-mapped
-// memory for symmicp_get_trim_state.  Every step is launch-bound (4 B per row and digit), so there is no host round trip in between.
+// leaves tau, n_c and the kept count (keys <= tau, ties included) in device memory for the accumulating kernel and, as a RejectRecord, in
+// host-mapped memory for the state getters.  Every step is launch-bound (4 B per row and digit), so there is no host round trip in between.
 //
 // The one-to-one and median-distance rejectors (symmicp_set_one_to_one / symmicp_set_median_factor) use the same keys and the same select:
 //   k_unique_claim   in front of the keys: every candidate claims its target with (d2 bits << 32 | caller row) by a 64-bit atomicMin on a
-//                    table of one word per target point; k_trim_keys<UNIQ> then gives every candidate that is not the minimum of its
+//                    table of one word per target point; k_reject_keys<UNIQ> then gives every candidate that is not the minimum of its
 //                    target the sentinel, so the select's population is the winners
 //   k_median_tau     behind the select at rho = 0.5: tau = factor^2 x the median; k_count_le counts the keys <= tau, k_reject_publish
-//                    hands (population, kept, tau, n_c) to the host; k_reject_all does both for one-to-one alone (every winner is kept)
+//                    hands the RejectRecord to the host; k_reject_all does both for one-to-one alone (every winner is kept)
 // Reciprocal correspondences (symmicp_set_reciprocal) add one kernel between the claim and the keys:
 //   k_recip_check    per claimed target j: q_j through the inverse of the pass's transform, one exact walk of the octree over the ORIGINAL
 //                    source (oct_walk.h), and a winner that is not the reverse neighbour loses its claim (the entry goes back to ~0), so
-//                    k_trim_keys<UNIQ> finds no winner there; counts the claimed targets (n_u) and the survivors (n_r)
-// launch_trim_select has the order.
+//                    k_reject_keys<UNIQ> finds no winner there; counts the claimed targets (n_u) and the survivors (n_r)
+// launch_reject has the order.
 //
 // The gates below are pair_step's (kernels_pass.hip), on the same fp32 expressions: unfused, in the association written.
 #include "symmicp_internal.h"
@@ -38,11 +38,16 @@ namespace symmicp {
 constexpr int kSelThreads = 256;
 constexpr uint32_t kSelBins = 2048;           // bins of the widest digit (11 bits)
 constexpr uint32_t kSelMaxBlocks = 1024;      // grid-stride beyond this
-// workspace words (PassArgs::trim_ws): the state, then one histogram per digit
+// workspace words (RejectArgs::ws): the state, then one histogram per digit
 enum { SEL_NC = 0, SEL_K = 1, SEL_PREFIX = 2, SEL_TAU = 3, SEL_KEPT = 4, SEL_K0 = 5, SEL_GATED = 6, SEL_MED = 7, SEL_CLAIMED = 8, SEL_RECIP = 9, SEL_STATE_WORDS = 16 };
-static_assert(kTrimWsWords == SEL_STATE_WORDS + 3 * kSelBins, "symmicp_internal.h sizes the workspace");
-static_assert(kTrimTauWord == SEL_TAU, "the accumulating kernels read tau from this word");
-static_assert(kTrimClaimedWord == SEL_CLAIMED && kTrimRecipWord == SEL_RECIP, "the host reads n_u and n_r of a reciprocal pass from these words");
+static_assert(kRejectWsWords == SEL_STATE_WORDS + 3 * kSelBins, "symmicp_internal.h sizes the workspace");
+static_assert(kRejectTauWord == SEL_TAU, "the accumulating kernels read tau from this word");
+
+// the pass's result for the host, from the workspace as the last step of the pass left it (out == null: a probe, or not the last step)
+__device__ __forceinline__ void publish_record(const uint32_t *ws, RejectRecord *out)
+{
+    if (out) *out = RejectRecord{ws[SEL_NC], ws[SEL_KEPT], ws[SEL_TAU], ws[SEL_GATED], ws[SEL_CLAIMED], ws[SEL_RECIP]};
+}
 
 template <int PASS> __device__ __forceinline__ uint32_t sel_digit(uint32_t key)
 {
@@ -132,7 +137,7 @@ __device__ __forceinline__ bool pair_candidate(const PassArgs &a, const CloudSoA
 // Every candidate claims its target with K = (d2 bits << 32 | caller row); the table keeps the minimum.  An integer minimum does not
 // depend on the order of the claims, so the winners are reproducible bit for bit; ties in d2 go to the lowest caller row.
 __device__ __forceinline__ unsigned long long claim_key(uint32_t d2_bits, uint32_t row) { return ((unsigned long long)d2_bits << 32) | row; }
-__device__ __forceinline__ uint32_t caller_row(const PassArgs &a, uint32_t i) { return a.uniq_order ? a.uniq_order[i] : i; }
+__device__ __forceinline__ uint32_t caller_row(const PassArgs &a, uint32_t i) { return a.rej.order ? a.rej.order[i] : i; }
 
 // One claim.  A claim that the entry already beats cannot win -- the entry only falls -- so it is read first; a stale read costs one
 // atomic more, never a winner.
@@ -183,10 +188,10 @@ __global__ __launch_bounds__(kSelThreads) void k_unique_claim(PassArgs a, CloudS
         uint32_t j = 0u;
         unsigned long long key = ~0ull;
         if (i < a.n) {
-            cand = pair_candidate<CORR>(a, tgt, tn, gate_n, i, d2, j) && j < a.uniq_n_t;
+            cand = pair_candidate<CORR>(a, tgt, tn, gate_n, i, d2, j) && j < a.rej.n_t;
             if (cand) key = claim_key(__float_as_uint(d2), caller_row(a, i));
         }
-        claim_wave(a.uniq_table, j, key, cand);
+        claim_wave(a.rej.table, j, key, cand);
     }
 }
 
@@ -264,7 +269,7 @@ __global__ __launch_bounds__(kRecipThreads) void k_recip_check(unsigned long lon
 // UNIQ: the table of k_unique_claim is complete: a candidate that did not win its target gets the sentinel and leaves the population
 // (SEL_NC and the histogram); SEL_GATED counts the candidates either way.
 template <int CORR, bool UNIQ>
-__global__ __launch_bounds__(kSelThreads) void k_trim_keys(PassArgs a, CloudSoA tgt, const float4 *__restrict__ tn)
+__global__ __launch_bounds__(kSelThreads) void k_reject_keys(PassArgs a, CloudSoA tgt, const float4 *__restrict__ tn)
 {
     __shared__ uint32_t h[kSelBins];
     __shared__ uint32_t s_count, s_gated;
@@ -282,17 +287,17 @@ __global__ __launch_bounds__(kSelThreads) void k_trim_keys(PassArgs a, CloudSoA 
             uint32_t j;
             cand = pair_candidate<CORR>(a, tgt, tn, gate_n, i, d2, j);
             gated += cand ? 1u : 0u;
-            if (UNIQ && cand) cand = j < a.uniq_n_t && a.uniq_table[j] == claim_key(__float_as_uint(d2), caller_row(a, i));
-            a.trim_keys[i] = cand ? __float_as_uint(d2) : 0xFFFFFFFFu;
+            if (UNIQ && cand) cand = j < a.rej.n_t && a.rej.table[j] == claim_key(__float_as_uint(d2), caller_row(a, i));
+            a.rej.keys[i] = cand ? __float_as_uint(d2) : 0xFFFFFFFFu;
         }
         hist_add(h, sel_digit<0>(__float_as_uint(d2)), cand);
         mine += cand ? 1u : 0u;
     }
     if (mine) atomicAdd(&s_count, mine);
     if (gated) atomicAdd(&s_gated, gated);
-    hist_merge(h, a.trim_ws + SEL_STATE_WORDS);
-    if (threadIdx.x == 0 && s_count) atomicAdd(a.trim_ws + SEL_NC, s_count);
-    if (threadIdx.x == 0 && s_gated) atomicAdd(a.trim_ws + SEL_GATED, s_gated);
+    hist_merge(h, a.rej.ws + SEL_STATE_WORDS);
+    if (threadIdx.x == 0 && s_count) atomicAdd(a.rej.ws + SEL_NC, s_count);
+    if (threadIdx.x == 0 && s_gated) atomicAdd(a.rej.ws + SEL_GATED, s_gated);
 }
 
 // histogram of digit PASS over the keys whose earlier digits equal the prefix fixed so far (PASS 0: every key)
@@ -315,7 +320,7 @@ __global__ __launch_bounds__(kSelThreads) void k_select_hist(const uint32_t *__r
 // k_fixed (the probe), else ceil(rho n_c) in fp64 clamped to [1, n_c].  PASS 2 completes tau and the kept count:
 // (keys below tau) + (keys equal to tau) = (k0 - rank inside the last bin) + that bin's count.  n_c == 0: tau = 0, nothing kept.
 template <int PASS>
-__global__ __launch_bounds__(kSelThreads) void k_select_scan(uint32_t *ws, float rho, uint32_t k_fixed, uint32_t n_fixed, uint32_t *out_host)
+__global__ __launch_bounds__(kSelThreads) void k_select_scan(uint32_t *ws, float rho, uint32_t k_fixed, uint32_t n_fixed, RejectRecord *out_host)
 {
     constexpr uint32_t kPer = kSelBins / kSelThreads;      // consecutive bins per thread
     __shared__ uint32_t incl[kSelThreads];
@@ -360,14 +365,14 @@ __global__ __launch_bounds__(kSelThreads) void k_select_scan(uint32_t *ws, float
         if (PASS == 2) {
             const uint32_t kept = ws[SEL_K0] - (k - before) + bins[j];
             ws[SEL_TAU] = prefix; ws[SEL_KEPT] = kept;
-            if (out_host) { out_host[0] = ws[SEL_NC]; out_host[1] = kept; out_host[2] = prefix; out_host[3] = ws[SEL_GATED]; out_host[4] = ws[SEL_CLAIMED]; out_host[5] = ws[SEL_RECIP]; }
+            publish_record(ws, out_host);
         }
     }
     if (k == 0u && t == 0) {
         ws[SEL_K] = 0u;
         if (PASS == 2) {
             ws[SEL_TAU] = 0u; ws[SEL_KEPT] = 0u;
-            if (out_host) { out_host[0] = ws[SEL_NC]; out_host[1] = 0u; out_host[2] = 0u; out_host[3] = ws[SEL_GATED]; out_host[4] = ws[SEL_CLAIMED]; out_host[5] = ws[SEL_RECIP]; }
+            publish_record(ws, out_host);
         }
     }
 }
@@ -379,7 +384,7 @@ static uint32_t sel_blocks(uint32_t n)
 }
 
 // scan 0, hist 1, scan 1, hist 2, scan 2: the five launches behind the first histogram
-static void launch_select_tail(const uint32_t *keys, uint32_t n, uint32_t *ws, float rho, uint32_t k_fixed, uint32_t *out_host, hipStream_t s)
+static void launch_select_tail(const uint32_t *keys, uint32_t n, uint32_t *ws, float rho, uint32_t k_fixed, RejectRecord *out_host, hipStream_t s)
 {
     const uint32_t nb = sel_blocks(n);
     hipLaunchKernelGGL(k_select_scan<0>, dim3(1), dim3(kSelThreads), 0, s, ws, rho, k_fixed, n, nullptr);
@@ -391,11 +396,10 @@ static void launch_select_tail(const uint32_t *keys, uint32_t n, uint32_t *ws, f
 
 // ---- tau without a fixed fraction -------------------------------------------------------------------
 // One-to-one alone: every non-sentinel key is kept (tau = +Inf: a candidate's d2 is never NaN for finite clouds and transforms).
-__global__ void k_reject_all(uint32_t *ws, uint32_t *out_host)
+__global__ void k_reject_all(uint32_t *ws, RejectRecord *out_host)
 {
-    const uint32_t nc = ws[SEL_NC];
-    ws[SEL_TAU] = 0x7F800000u; ws[SEL_KEPT] = nc;
-    if (out_host) { out_host[0] = nc; out_host[1] = nc; out_host[2] = 0x7F800000u; out_host[3] = ws[SEL_GATED]; out_host[4] = ws[SEL_CLAIMED]; out_host[5] = ws[SEL_RECIP]; }
+    ws[SEL_TAU] = 0x7F800000u; ws[SEL_KEPT] = ws[SEL_NC];
+    publish_record(ws, out_host);
 }
 
 // Median distance: the select (rho = 0.5) left the median in SEL_TAU; tau = f2 * med, one fp32 product.  Population 0: tau = 0.  A NaN
@@ -425,54 +429,49 @@ __global__ __launch_bounds__(kSelThreads) void k_count_le(const uint32_t *__rest
     if (threadIdx.x == 0 && s_count) atomicAdd(ws + SEL_KEPT, s_count);
 }
 
-__global__ void k_reject_publish(const uint32_t *ws, uint32_t *out_host)
-{
-    out_host[0] = ws[SEL_NC]; out_host[1] = ws[SEL_KEPT]; out_host[2] = ws[SEL_TAU]; out_host[3] = ws[SEL_GATED];
-    out_host[4] = ws[SEL_CLAIMED]; out_host[5] = ws[SEL_RECIP];
-}
+__global__ void k_reject_publish(const uint32_t *ws, RejectRecord *out_host) { publish_record(ws, out_host); }
 
 template <bool UNIQ>
 static void launch_keys(const PassArgs &a, int corr, CloudSoA tgt, const float4 *tn, uint32_t nb, hipStream_t s)
 {
-    if (corr == SYMMICP_CORR_IDENTITY) hipLaunchKernelGGL((k_trim_keys<0, UNIQ>), dim3(nb), dim3(kSelThreads), 0, s, a, tgt, tn);
-    else if (corr == SYMMICP_CORR_BRUTE) hipLaunchKernelGGL((k_trim_keys<1, UNIQ>), dim3(nb), dim3(kSelThreads), 0, s, a, tgt, tn);
-    else hipLaunchKernelGGL((k_trim_keys<2, UNIQ>), dim3(nb), dim3(kSelThreads), 0, s, a, tgt, tn);
+    if (corr == SYMMICP_CORR_IDENTITY) hipLaunchKernelGGL((k_reject_keys<0, UNIQ>), dim3(nb), dim3(kSelThreads), 0, s, a, tgt, tn);
+    else if (corr == SYMMICP_CORR_BRUTE) hipLaunchKernelGGL((k_reject_keys<1, UNIQ>), dim3(nb), dim3(kSelThreads), 0, s, a, tgt, tn);
+    else hipLaunchKernelGGL((k_reject_keys<2, UNIQ>), dim3(nb), dim3(kSelThreads), 0, s, a, tgt, tn);
 }
 
 // The rejection steps of a pass, behind its search and in front of its accumulating kernel:
-//   one-to-one (a.uniq_table; never IDENTITY, whose pairs are one-to-one)   memset of the table, k_unique_claim
-//   reciprocal (a.trim_uniq == 2: the table's tail holds the RecipArgs)     k_recip_check
-//   keys                                                                    memset of the workspace, k_trim_keys
+//   one-to-one (r.claim; never IDENTITY, whose pairs are one-to-one)   memset of the table, k_unique_claim
+//   reciprocal (kClaimReciprocal: r.recip is this pass's RecipArgs)     k_recip_check
+//   keys                                                                memset of the workspace, k_reject_keys
 //   tau: trim fraction            the select (5 launches), which publishes
 //        median factor            the select at rho = 0.5, k_median_tau, k_count_le, k_reject_publish
 //        neither                  k_reject_all
 // The table is reset by a memset every pass: 8 B per target point at the HBM roof, against a claim that gathers 32 B per source point.
-void launch_trim_select(const PassArgs &a, int corr, CloudSoA tgt, const float4 *tn, hipStream_t s)
+void launch_reject(const PassArgs &a, int corr, CloudSoA tgt, const float4 *tn, hipStream_t s)
 {
-    hipMemsetAsync(a.trim_ws, 0, sizeof(uint32_t) * kTrimWsWords, s);
+    const RejectArgs &r = a.rej;
+    hipMemsetAsync(r.ws, 0, sizeof(uint32_t) * kRejectWsWords, s);
     const uint32_t nb = sel_blocks(a.n);
-    const bool uniq = a.uniq_table && corr != SYMMICP_CORR_IDENTITY;
-    if (uniq) {
-        hipMemsetAsync(a.uniq_table, 0xFF, sizeof(unsigned long long) * a.uniq_n_t, s);
+    if (r.claim != kClaimNone && corr != SYMMICP_CORR_IDENTITY) {
+        hipMemsetAsync(r.table, 0xFF, sizeof(unsigned long long) * r.n_t, s);
         if (corr == SYMMICP_CORR_BRUTE) hipLaunchKernelGGL(k_unique_claim<1>, dim3(nb), dim3(kSelThreads), 0, s, a, tgt, tn);
         else hipLaunchKernelGGL(k_unique_claim<2>, dim3(nb), dim3(kSelThreads), 0, s, a, tgt, tn);
-        if (a.trim_uniq == 2)
-            hipLaunchKernelGGL(k_recip_check, dim3(sel_blocks(a.uniq_n_t)), dim3(kRecipThreads), 0, s, a.uniq_table, a.uniq_n_t, tn,
-                               reinterpret_cast<const RecipArgs *>(a.uniq_table + a.uniq_n_t), a.trim_ws);
+        if (r.claim == kClaimReciprocal)
+            hipLaunchKernelGGL(k_recip_check, dim3(sel_blocks(r.n_t)), dim3(kRecipThreads), 0, s, r.table, r.n_t, tn, r.recip, r.ws);
         launch_keys<true>(a, corr, tgt, tn, nb, s);
     } else launch_keys<false>(a, corr, tgt, tn, nb, s);
-    if (a.med_f2 > 0.0f) {
-        launch_select_tail(a.trim_keys, a.n, a.trim_ws, 0.5f, 0u, nullptr, s);
-        hipLaunchKernelGGL(k_median_tau, dim3(1), dim3(1), 0, s, a.trim_ws, a.med_f2);
-        hipLaunchKernelGGL(k_count_le, dim3(nb), dim3(kSelThreads), 0, s, a.trim_keys, a.n, a.trim_ws);
-        hipLaunchKernelGGL(k_reject_publish, dim3(1), dim3(1), 0, s, a.trim_ws, a.trim_host);
-    } else if (a.trim_rho < 1.0f) launch_select_tail(a.trim_keys, a.n, a.trim_ws, a.trim_rho, 0u, a.trim_host, s);
-    else hipLaunchKernelGGL(k_reject_all, dim3(1), dim3(1), 0, s, a.trim_ws, a.trim_host);
+    if (r.med_f2 > 0.0f) {
+        launch_select_tail(r.keys, a.n, r.ws, 0.5f, 0u, nullptr, s);
+        hipLaunchKernelGGL(k_median_tau, dim3(1), dim3(1), 0, s, r.ws, r.med_f2);
+        hipLaunchKernelGGL(k_count_le, dim3(nb), dim3(kSelThreads), 0, s, r.keys, a.n, r.ws);
+        hipLaunchKernelGGL(k_reject_publish, dim3(1), dim3(1), 0, s, r.ws, r.host);
+    } else if (r.rho < 1.0f) launch_select_tail(r.keys, a.n, r.ws, r.rho, 0u, r.host, s);
+    else hipLaunchKernelGGL(k_reject_all, dim3(1), dim3(1), 0, s, r.ws, r.host);
 }
 
 void launch_select_probe(const uint32_t *keys, uint32_t n, uint32_t k, uint32_t *ws, hipStream_t s)
 {
-    hipMemsetAsync(ws, 0, sizeof(uint32_t) * kTrimWsWords, s);
+    hipMemsetAsync(ws, 0, sizeof(uint32_t) * kRejectWsWords, s);
     hipLaunchKernelGGL(k_select_hist<0>, dim3(sel_blocks(n)), dim3(kSelThreads), 0, s, keys, n, ws);
     launch_select_tail(keys, n, ws, 1.0f, k, nullptr, s);
 }

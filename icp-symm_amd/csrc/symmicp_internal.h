@@ -138,6 +138,42 @@ struct LoopRecord {          // one per pass, host-mapped
     int32_t list_len, reserved;      // work-list length of this pass (queries handed to the tree walk)
 };
 
+// ---- pair rejection (kernels_select.hip): trim fraction, one-to-one, median distance, reciprocal ----
+// what a reciprocal pass adds to the claim (k_recip_check): the index over the ORIGINAL source, whose tq carries the caller's row in w,
+// and the 3x4 inverse of the pass's cumulative transform (symmicp_inverse_rigid).  Read by the kernel from device memory (the tail of
+// the claim table), so PassArgs, an argument of every pass kernel, carries a pointer for it and nothing more
+struct RecipArgs {
+    TargetIndex six;
+    Affine inv;
+};
+constexpr size_t kRecipTailWords = (sizeof(RecipArgs) + 7) / 8;      // 64-bit words the claim table is allocated beyond its entries
+constexpr uint32_t kRejectWsWords = 16 + 3 * 2048;                   // the select's state and its three histograms
+constexpr uint32_t kRejectTauWord = 3;                               // ... where the accumulating kernels find the pass's tau
+// What a rejecting pass leaves for the host, behind the record's sequence word in host-mapped memory
+struct RejectRecord {
+    uint32_t population;                // the select's population: the candidates (n_c), with a claim its winners (n_u)
+    uint32_t kept, tau_bits;            // keys <= tau; tau as fp32 bits
+    uint32_t gated;                     // n_c: pairs that exist and pass the gates
+    uint32_t claimed, reciprocal;       // reciprocal passes: targets claimed (n_u), claims the reverse search confirmed (n_r); 0 otherwise
+};
+enum RejectClaim : int32_t { kClaimNone = 0, kClaimOneToOne = 1, kClaimReciprocal = 2 };
+// The rejectors of one pass.  keys != null makes it a rejecting pass (pass_rejects): the launchers run the claim, the keys and the select
+// (launch_reject) in front of the T instantiation of the pass's accumulating kernel, which keeps a pair only if its d2 bits are <= the
+// tau in ws[kRejectTauWord].  All of them run through the same keys, the same select and the same T instantiations.
+struct RejectArgs {
+    uint32_t *keys;                     // [n] per share row: the candidate's d2 bits, 0xFFFFFFFF otherwise
+    uint32_t *ws;                       // [kRejectWsWords]
+    RejectRecord *host;                 // host-mapped: the pass's result
+    unsigned long long *table;          // claim: [n_t] per target position the smallest claim (d2 bits << 32 | caller row)
+    const uint32_t *order;              // ... share row -> caller row (null: the share is in caller order)
+    const RecipArgs *recip;             // kClaimReciprocal: in device memory, filled in by the host before the pass
+    uint32_t n_t;                       // claim: entries of the table
+    int32_t claim;                      // RejectClaim.  != none: the accumulating kernel reads keys[i] and drops the sentinel rows, the claim's losers
+    float rho;                          // trim fraction (1: off)
+    float med_f2;                       // median distance: factor * factor in fp32 (0: off): tau = med_f2 * the select's median
+};
+static_assert(sizeof(RejectArgs) == 64 && sizeof(RejectRecord) == 24, "RejectArgs takes the room of the nine fields it replaced");
+
 struct PassArgs {
     // source share (planar).  `in` is read; if writeback, `out` receives the transformed points/normals
     CloudSoA in, out;
@@ -177,38 +213,16 @@ struct PassArgs {
     float loss_scale;                   // ... its scale (robust_loss.h)
     int32_t obj;                        // the record (kObjSym / kObjPlane / kObjGicp, mode_obj): the launchers pick the instantiations; read by the host only
     float gicp_k;                       // ... 1 - eps of its covariances (symmicp_set_gicp_epsilon), fp32: read by the GICP instantiations only
-    // trimmed ICP (symmicp_set_trim_fraction below 1; kernels_select.hip).  trim_keys != null selects the trimming instantiation (T) of the
-    // pass's accumulating kernel, which keeps a pair only if its d2 bits are <= the tau the select left in trim_ws[kTrimTauWord]; the
-    // launchers run the keys and the select in front of it.  Null (the default): nothing is launched and the kernels are the untrimmed ones.
-    uint32_t *trim_keys;                // [n] per share row: the candidate's d2 bits, 0xFFFFFFFF otherwise
-    uint32_t *trim_ws;                  // [kTrimWsWords] the select's state and histograms
-    uint32_t *trim_host;                // host-mapped (the select's population, kept, tau bits, n_c) of the pass
-    float trim_rho;
-    // The one-to-one and median-distance rejectors (symmicp_set_one_to_one / symmicp_set_median_factor) run through the same keys, the
-    // same select and the same T instantiations: a pass with any of the three has trim_keys set.
-    unsigned long long *uniq_table;     // one-to-one: [uniq_n_t] per target position the smallest claim (d2 bits << 32 | caller row); null: off
-    const uint32_t *uniq_order;         // ... share row -> caller row (null: the share is in caller order)
-    uint32_t uniq_n_t;                  // ... entries of the table
-    int32_t trim_uniq;                  // != 0: the accumulating kernel reads trim_keys[i] and drops the sentinel rows: losers of the claim.  2: a reciprocal
-                                        // pass (symmicp_set_reciprocal): launch_trim_select runs k_recip_check between the claim and the keys, on the
-                                        // RecipArgs the host left in device memory behind the table's uniq_n_t entries
-    float med_f2;                       // median distance: factor * factor in fp32 (0: off): tau = med_f2 * the select's median
+    RejectArgs rej;                     // the pass's rejectors (above); zeroed: none, and the kernels are the plain ones
     // colored ICP (SYMMICP_MODE_COLOR; read by the kObjColor instantiations only)
     const float4 *tgt_color;            // per target point, in the order of tn (IDENTITY: of the planar target): (gradient xyz, intensity)
     const float *src_int;               // per share row: the source point's intensity
     float color_lam, color_om;          // lambda and omega = 1.0f - lambda
 };
-// what a reciprocal pass adds to the claim (kernels_select.hip, k_recip_check): the index over the ORIGINAL source, whose tq carries the
-// caller's row in w, and the 3x4 inverse of the pass's cumulative transform (symmicp_inverse_rigid).  Read by the kernel from device memory
-// (the tail of the claim table), so PassArgs, an argument of every pass kernel, carries nothing for it
-struct RecipArgs {
-    TargetIndex six;
-    Affine inv;
-};
-constexpr size_t kRecipTailWords = (sizeof(RecipArgs) + 7) / 8;      // 64-bit words the claim table is allocated beyond its entries
-constexpr uint32_t kTrimWsWords = 16 + 3 * 2048;
-constexpr uint32_t kTrimClaimedWord = 8, kTrimRecipWord = 9;      // reciprocal passes: n_u and n_r (0 otherwise), published behind the four words of trim_host
-constexpr uint32_t kTrimTauWord = 3;
+// (the layout the kernels without a rejector were compiled against before RejectArgs: they read the same offsets, so their code is the same)
+static_assert(sizeof(PassArgs) == 432 && offsetof(PassArgs, rej) == 344 && offsetof(PassArgs, tgt_color) == 408 && offsetof(PassArgs, src_int) == 416,
+              "PassArgs keeps its layout");
+__host__ __device__ inline bool pass_rejects(const PassArgs &a) { return a.rej.keys != nullptr; }
 
 // host-side launch tuning of the tree passes (environment switches, read once by the engine)
 struct PassTuning {
@@ -281,12 +295,12 @@ void launch_iota_f4(const float *x, const float *y, const float *z, const float 
 void launch_unpermute(const CloudSoA &cur, const uint32_t *order, uint32_t n, float *xyz_aos, float *nrm_aos, hipStream_t s);
 void launch_corr_out(const int32_t *pos, const unsigned long long *best64, const float *d2, const float4 *tq,
                      const uint32_t *src_order, uint32_t n, int mode, uint32_t tgt_offset, int32_t *idx_out, float *d2_out,
-                     const uint32_t *trim_keys /* null, or: rows whose key is above trim_tau report -1 */, uint32_t trim_tau, hipStream_t s);
+                     const uint32_t *rej_keys /* null, or: rows whose key is above rej_tau report -1 */, uint32_t rej_tau, hipStream_t s);
 
-// trimmed ICP (kernels_select.hip): the keys of the pass's candidates and the exact radix select of the k-th smallest, k = ceil(rho n_c) --
-// one memset and six launches; called by the pass launchers when a.trim_keys is set.  corr: symmicp_corr (which of tgt / tn is read)
-void launch_trim_select(const PassArgs &a, int corr, CloudSoA tgt, const float4 *tn, hipStream_t s);
-// test entry: the select alone on n keys, rank k (1-based); afterwards ws[kTrimTauWord] = the k-th smallest key, ws[4] = keys <= it
+// the rejection steps of a pass (kernels_select.hip has the order); called by the pass launchers when pass_rejects(a).  corr: symmicp_corr
+// (which of tgt / tn is read)
+void launch_reject(const PassArgs &a, int corr, CloudSoA tgt, const float4 *tn, hipStream_t s);
+// test entry: the select alone on n keys, rank k (1-based); afterwards ws[kRejectTauWord] = the k-th smallest key, ws[4] = keys <= it
 void launch_select_probe(const uint32_t *keys, uint32_t n, uint32_t k, uint32_t *ws, hipStream_t s);
 // test entry: the one-to-one claim alone (k_unique_claim's claim_wave and the winner test) on n rows given as (target row, d2 bits), the row
 // being the array index; tgt_row < 0 or >= n_t: no pair.  table: [n_t] scratch; winner_out[i] = 1 where row i wins its target

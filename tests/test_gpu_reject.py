@@ -6,7 +6,8 @@ symmicp_set_median_factor, the claim of target rows behind the first, and what t
      bits), the record, the pair count and the reported pairs -- modes x pairings x rejections, with a Huber loss, with both gates,
      COLOR, IDENTITY, ties in d2 under both source orders, ragged sizes;
   3. off means off: both options switched off explicitly are bit for bit a context that never heard of them, a trimmed context is what
-     it was, a rejecting align stays in the host loop, a setter acts at the next pass;
+     it was, a rejecting align stays in the host loop, a setter acts at the next pass; which of the three state getters answers
+     after a pass with which rejectors (with the reciprocal one of test_gpu_recip.py), and that none does after set_config / set_source;
   4. the refusals;
   5. the partial-overlap pair through Engine, MyICP (Python and C++) and the command-line driver.
 The pairs of a pass come from a twin context without rejection driven by the same transforms (its pairs and distances are held to
@@ -474,6 +475,87 @@ def test_setters_act_at_the_next_pass(sym, cat):
             e.rejection_state()
         assert x.value.status == sym.ERR_STATE
         assert (e.correspondences()[0] >= 0).all()
+
+
+# ---- 3b. which getter answers after which pass -----------------------------------------------------------------------------------------
+# Every allowed combination of the four rejectors on a 300-point source against a 257-point target (both ragged against 64 and 256:
+# the tail lanes of the claim and the key kernels), and one IDENTITY row (257 against 257: identity pairing needs equal sizes).  The
+# three state getters answer exactly after the passes their rejectors ran in; the expected figures are the numpy restatements' over
+# the oracle's brute-force pairs.
+QUANTILES = {"rho0.7": dict(rho=0.7), "median2": dict(factor=2.0), "noquantile": {}}
+VALIDITY = [(c, q, o, r) for c in ("brute", "tree") for q in QUANTILES for o in (False, True) for r in (False, True)]
+VALIDITY.append(("identity", "rho0.7", False, False))
+
+
+@pytest.fixture(scope="module")
+def ragged():
+    """-> the clouds, and the pairs of the first pass from the identity (the oracle's brute force), shared and left unchanged"""
+    from symmicp import synth
+    d = synth.c4_surface(300)
+    d = dict(src=d["src"], src_n=d["src_n"], tgt=d["tgt"][:257].copy(), tgt_n=d["tgt_n"][:257].copy())
+    d["idx"] = R.nn_ref(d["src"], d["tgt"])[0]
+    return d
+
+
+def _getter(sym, call):
+    """-> (status, values)"""
+    try:
+        return 0, call()
+    except sym.SymmIcpError as x:
+        return x.status, None
+
+
+@pytest.mark.parametrize("corr,quantile,o2o,recip", VALIDITY, ids=["%s-%s-%s-%s" % (c, q, "o2o" if o else "many", "recip" if r else "forward") for c, q, o, r in VALIDITY])
+def test_getters_validity_matrix(sym, ragged, corr, quantile, o2o, recip):
+    import _recip_ref as RC
+    identity = corr == "identity"
+    m = sym.MODE_PAPER
+    n_s = 257 if identity else 300
+    src, src_n, tgt, tgt_n = ragged["src"][:n_s], ragged["src_n"][:n_s], ragged["tgt"], ragged["tgt_n"]
+    idx = None if identity else ragged["idx"]
+    rho, factor = QUANTILES[quantile].get("rho", 1.0), QUANTILES[quantile].get("factor", 0.0)
+    p, pn = R.moved(np.eye(4), src, src_n, m)
+    if recip:
+        ref = RC.recip_pass(p, pn, tgt, tgt_n, idx, src, np.eye(4, dtype=f32), factor=factor, rho=rho)
+        population, claimed = ref["n_r"], ref["n_u"]
+    else:
+        ref = J.reject_pass(p, pn, tgt, tgt_n, idx, one_to_one=o2o, factor=factor, rho=rho)
+        population, claimed = ref["n_u"], None
+    want_trim = (population, ref["n_kept"], tau_bits(ref["tau"])) if rho < 1 else None
+    want_rej = (ref["n_c"], population, ref["n_kept"], tau_bits(ref["tau"])) if (factor > 0 or o2o or recip) else None
+    want_recip = (claimed, population) if recip else None
+    with sym.Engine(mode=m, corr=corr_code(sym, corr), max_iters=4, fixed_iters=1) as e:
+        e.set_target(tgt, tgt_n)
+        e.set_source(src, src_n)
+        apply_rejection(e, dict(one_to_one=o2o, **QUANTILES[quantile]))
+        if recip:
+            e.set_reciprocal(True)
+
+        def states():
+            return [_getter(sym, g) for g in (e.trim_state, e.rejection_state, e.reciprocal_state)]
+        assert [s for s, _ in states()] == [sym.ERR_STATE] * 3          # no pass yet
+        e.begin()
+        (st_t, t), (st_j, j), (st_r, r) = states()
+        print("%s %s o2o=%d recip=%d: trim %s rejection %s reciprocal %s" % (corr, quantile, o2o, recip, t, j, r))
+        assert (st_t, st_j, st_r) == tuple(0 if w is not None else sym.ERR_STATE for w in (want_trim, want_rej, want_recip))
+        if want_trim:
+            assert (t[0], t[1], tau_bits(t[2])) == want_trim
+        if want_rej:
+            assert (j[0], j[1], j[2], tau_bits(j[3])) == want_rej
+        if want_recip:
+            assert tuple(r) == want_recip and r[0] >= r[1]
+            assert j[1] == r[1]                                         # the select's population is the survivors
+        if want_trim and want_rej:
+            assert t[1] == j[2] and tau_bits(t[2]) == tau_bits(j[3]) and j[1] == t[0]
+        if want_rej and (identity or not (o2o or recip)):
+            assert j[1] == j[0]                                         # no claim: every candidate is "unique"
+        # ... and none of them answers for a pass that has not run under the new configuration or on the new source
+        e.set_config(max_iters=5)
+        assert [s for s, _ in states()] == [sym.ERR_STATE] * 3
+        e.begin()
+        assert [s for s, _ in states()] == [st_t, st_j, st_r]
+        e.set_source(src, src_n)
+        assert [s for s, _ in states()] == [sym.ERR_STATE] * 3
 
 
 # ---- 4. refusals --------------------------------------------------------------------------------------------------------------------
