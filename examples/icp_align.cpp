@@ -30,6 +30,9 @@
 //     --ransac-dist D          its inlier distance (required; some 2 point spacings)
 //     --ransac-iters H         hypotheses drawn (default 100000)      --seed S   of the draws (default 0)
 //     --init-voxel L           both clouds voxel-downsampled with edge L for the initialisation (default 0: as given)
+//     --init-keypoints iss     match and run RANSAC on the ISS keypoints of both clouds only (features still come from the full clouds)
+//     --iss-radius R           their salient radius (required with --init-keypoints iss; some 6 point spacings)
+//     --iss-nms-radius R2      their non-maximum radius (default: two thirds of R)   --iss-min-neighbors K   (default 5)
 //     --out aligned.pcd        write the source moved by the result (the reference only prints its result)
 //     --quiet                  no per-iteration lines
 //   Without file names it registers cat.pcd to cat_out.pcd from the working directory: the reference's own run.
@@ -49,7 +52,7 @@
 static int usage(const char *argv0, const char *complaint)
 {
     std::fprintf(stderr, "%s\nusage: %s [--mode quirks|paper|plane|gicp|color] [--color-weight L] [--corr identity|tree] [--iters N] [--threshold D] [--loss none|huber|tukey|cauchy|gm]"
-                 " [--loss-scale S] [--gicp-epsilon E] [--max-dist D] [--trim F] [--one-to-one] [--reciprocal] [--median-factor F] [--scale LEAF:ITERS[:MAXDIST]]... [--init global --fpfh-radius R --ransac-dist D [--ransac-iters H] [--seed S] [--init-voxel L]] [--out file.pcd] [--quiet] [source.pcd target.pcd]\n",
+                 " [--loss-scale S] [--gicp-epsilon E] [--max-dist D] [--trim F] [--one-to-one] [--reciprocal] [--median-factor F] [--scale LEAF:ITERS[:MAXDIST]]... [--init global --fpfh-radius R --ransac-dist D [--ransac-iters H] [--seed S] [--init-voxel L] [--init-keypoints iss --iss-radius R [--iss-nms-radius R2] [--iss-min-neighbors K]]] [--out file.pcd] [--quiet] [source.pcd target.pcd]\n",
                  complaint, argv0);
     return 64;
 }
@@ -72,7 +75,7 @@ int main(int argc, char **argv)
     bool one_to_one = false, reciprocal = false;
     float median_factor = 0.f;
     std::vector<MyICP::VoxelLevel> levels;
-    bool init_global = false, have_init_option = false;
+    bool init_global = false, have_init_option = false, have_iss_option = false;
     MyICP::GlobalInit ginit;
     auto number = [&](const char *what, const char *v, float &out) {
         char *end = nullptr;
@@ -185,6 +188,16 @@ int main(int argc, char **argv)
             if (h < 1 || h > (1l << 24)) return usage(argv[0], "--ransac-iters needs 1 .. 16777216");
             ginit.hypotheses = (unsigned)h; have_init_option = true;
         }
+        else if (a == "--init-keypoints") {
+            const std::string v = value("--init-keypoints");
+            if (v == "iss") ginit.iss = true;
+            else if (v == "none") ginit.iss = false;
+            else return usage(argv[0], "unknown --init-keypoints (iss or none)");
+            have_init_option = true;
+        }
+        else if (a == "--iss-radius") { number("--iss-radius", value("--iss-radius"), ginit.iss_salient_radius); have_iss_option = true; }
+        else if (a == "--iss-nms-radius") { number("--iss-nms-radius", value("--iss-nms-radius"), ginit.iss_non_max_radius); have_iss_option = true; }
+        else if (a == "--iss-min-neighbors") { ginit.iss_min_neighbors = std::atoi(value("--iss-min-neighbors")); have_iss_option = true; }
         else if (a == "--seed") { ginit.seed = std::strtoull(value("--seed"), nullptr, 10); have_init_option = true; }
         else if (a == "--out") out_path = value("--out");
         else if (a == "--quiet") icp.setVerbose(false);
@@ -226,8 +239,15 @@ int main(int argc, char **argv)
         if (!(ginit.fpfh_radius > 0.f) || !(ginit.max_dist > 0.f)) return usage(argv[0], "--init global needs --fpfh-radius R and --ransac-dist D, both > 0");
         if (ginit.voxel_leaf < 0.f) return usage(argv[0], "--init-voxel needs L >= 0");
         if (!tree) return usage(argv[0], "--init global needs --corr tree (identity pairing assumes the clouds correspond row by row)");
+        if (have_iss_option && !ginit.iss) return usage(argv[0], "--iss-radius, --iss-nms-radius and --iss-min-neighbors need --init-keypoints iss");
+        if (ginit.iss) {
+            if (!(ginit.iss_salient_radius > 0.f)) return usage(argv[0], "--init-keypoints iss needs --iss-radius R > 0");
+            if (ginit.iss_non_max_radius == 0.f) ginit.iss_non_max_radius = ginit.iss_salient_radius * (2.0f / 3.0f);
+            if (!(ginit.iss_non_max_radius > 0.f)) return usage(argv[0], "--iss-nms-radius needs R2 > 0");
+            if (ginit.iss_min_neighbors < 1) return usage(argv[0], "--iss-min-neighbors needs K >= 1");
+        }
         icp.setGlobalInit(ginit);
-    } else if (have_init_option) return usage(argv[0], "--fpfh-radius, --ransac-dist, --ransac-iters, --seed and --init-voxel need --init global");
+    } else if (have_init_option || have_iss_option) return usage(argv[0], "--fpfh-radius, --ransac-dist, --ransac-iters, --seed, --init-voxel and --init-keypoints need --init global");
     if (have_eps) {
         if (!gicp) return usage(argv[0], "--gicp-epsilon needs --mode gicp");
         icp.setGicpEpsilon(gicp_eps);

@@ -1454,6 +1454,98 @@ int symmicp_fpfh(int device, const float *xyz, size_t xyz_row_stride, size_t xyz
     return st;
 }
 
+// ---- ISS keypoints (kernels_keypoints.hip; DESIGN.md 4, "ISS keypoints") ---------------------------------------------------
+// Like the FPFH entry: the cloud's own scratch index, the radius walk twice (saliency at the salient radius, non-maximum
+// suppression at the other), then the flags scanned over rows and the kept rows scattered in ascending order.
+static const char *iss_args_error(const float *xyz, size_t xr, size_t xc, size_t n, const symmicp_iss_config *cfg, const int32_t *rows_out, size_t cap,
+                                  const size_t *count_out)
+{
+    if (!xyz || !cfg || !count_out) return "iss_keypoints: xyz, cfg and count_out are required";
+    if (!rows_out && cap > 0) return "iss_keypoints: rows_out is required when cap > 0";
+    if (n == 0 || n > 0x7fffffffull) return "iss_keypoints: n must be in 1 .. 2^31 - 1";
+    if (cfg->struct_size != sizeof(symmicp_iss_config)) return "iss_keypoints: cfg->struct_size is not sizeof(symmicp_iss_config)";
+    if (!std::isfinite(cfg->salient_radius) || !(cfg->salient_radius > 0.f)) return "iss_keypoints: salient_radius must be finite and > 0";
+    if (!std::isfinite(cfg->non_max_radius) || !(cfg->non_max_radius > 0.f)) return "iss_keypoints: non_max_radius must be finite and > 0";
+    if (!(cfg->gamma21 > 0.f) || !(cfg->gamma21 <= 1.f)) return "iss_keypoints: gamma21 must be in (0, 1]";
+    if (!(cfg->gamma32 > 0.f) || !(cfg->gamma32 <= 1.f)) return "iss_keypoints: gamma32 must be in (0, 1]";
+    if (cfg->min_neighbors < 1) return "iss_keypoints: min_neighbors must be >= 1";
+    for (size_t i = 0; i < n; i++)
+        for (int a = 0; a < 3; a++)
+            if (!std::isfinite(xyz[i * xr + a * xc])) return "iss_keypoints: a coordinate is not finite";
+    return nullptr;
+}
+
+void symmicp_iss_config_default(symmicp_iss_config *cfg)
+{
+    if (!cfg) return;
+    std::memset(cfg, 0, sizeof(*cfg));
+    cfg->struct_size = (uint32_t)sizeof(*cfg);
+    cfg->gamma21 = 0.975f;
+    cfg->gamma32 = 0.975f;
+    cfg->min_neighbors = 5;
+}
+
+int symmicp_ctx_iss_keypoints(symmicp_ctx *c, const float *xyz, size_t row_stride, size_t col_stride, size_t n, const symmicp_iss_config *cfg,
+                              int32_t *rows_out, size_t cap, size_t *count_out, float *saliency_out, int32_t *neighbors_out)
+{
+    if (!c) return SYMMICP_ERR_ARG;
+    if (const char *msg = iss_args_error(xyz, row_stride, col_stride, n, cfg, rows_out, cap, count_out)) return fail(c, SYMMICP_ERR_ARG, msg);
+    ScratchIndex si;
+    int st = scratch_index_begin(c, xyz, row_stride, col_stride, nullptr, 0, 0, n, n * 6 * 4 + 16384, si);
+    if (st != SYMMICP_OK) return st;
+    const float rs2 = cfg->salient_radius * cfg->salient_radius, rn2 = cfg->non_max_radius * cfg->non_max_radius;
+    auto body = [&]() -> int {
+        DevBuf<float> d_sorted, d_srows;
+        DevBuf<int32_t> d_k, d_rows;
+        DevBuf<uint32_t> d_flag, d_pos, scan_ws;
+        HIP_TRY(c, d_sorted.alloc_temp(c->arena, n));
+        HIP_TRY(c, d_srows.alloc_temp(c->arena, n));
+        HIP_TRY(c, d_k.alloc_temp(c->arena, n));
+        HIP_TRY(c, d_flag.alloc_temp(c->arena, n));
+        HIP_TRY(c, d_pos.alloc_temp(c->arena, n));
+        HIP_TRY(c, scan_ws.alloc_temp(c->arena, n / 2048 + 2));
+        launch_iss_saliency(si.ix, rs2, cfg->min_neighbors, cfg->gamma21, cfg->gamma32, d_sorted.p, d_srows.p, d_k.p, c->stream);
+        launch_iss_nms(si.ix, rn2, cfg->min_neighbors, d_sorted.p, d_flag.p, c->stream);
+        HIP_TRY(c, hipMemcpyAsync(d_pos.p, d_flag.p, sizeof(uint32_t) * n, hipMemcpyDeviceToDevice, c->stream));
+        launch_exclusive_scan(d_pos.p, (uint32_t)n, scan_ws.p, c->stream);
+        uint32_t last_pos = 0, last_flag = 0;
+        HIP_TRY(c, hipMemcpyAsync(&last_pos, d_pos.p + (n - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(&last_flag, d_flag.p + (n - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+        if (saliency_out) HIP_TRY(c, hipMemcpyAsync(saliency_out, d_srows.p, sizeof(float) * n, hipMemcpyDeviceToHost, c->stream));
+        if (neighbors_out) HIP_TRY(c, hipMemcpyAsync(neighbors_out, d_k.p, sizeof(int32_t) * n, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        HIP_TRY(c, hipGetLastError());
+        const size_t count = (size_t)last_pos + last_flag;
+        *count_out = count;
+        if (count > cap) return fail(c, SYMMICP_ERR_SIZE, "iss_keypoints: " + std::to_string(count) + " keypoints do not fit cap " + std::to_string(cap));
+        if (count == 0) return SYMMICP_OK;
+        HIP_TRY(c, d_rows.alloc_temp(c->arena, count));
+        launch_iss_scatter(d_flag.p, d_pos.p, (uint32_t)n, d_rows.p, c->stream);
+        HIP_TRY(c, hipMemcpyAsync(rows_out, d_rows.p, sizeof(int32_t) * count, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        HIP_TRY(c, hipGetLastError());
+        return SYMMICP_OK;
+    };
+    st = body();
+    scratch_index_end(c, si);
+    return st;
+}
+
+int symmicp_iss_keypoints(int device, const float *xyz, size_t row_stride, size_t col_stride, size_t n, const symmicp_iss_config *cfg,
+                          int32_t *rows_out, size_t cap, size_t *count_out, float *saliency_out, int32_t *neighbors_out)
+{
+    if (iss_args_error(xyz, row_stride, col_stride, n, cfg, rows_out, cap, count_out)) return SYMMICP_ERR_ARG;
+    symmicp_config ccfg;
+    symmicp_config_default(&ccfg);
+    ccfg.device = device;
+    symmicp_ctx *c = nullptr;
+    int st = symmicp_create(&ccfg, &c);
+    if (st != SYMMICP_OK) return st;
+    st = symmicp_ctx_iss_keypoints(c, xyz, row_stride, col_stride, n, cfg, rows_out, cap, count_out, saliency_out, neighbors_out);
+    symmicp_destroy(c);
+    return st;
+}
+
 // ---- intensity gradient of colored ICP (kernels_color.hip; DESIGN.md 4, "Colored ICP") ------------------------------------
 // Like the FPFH entry: the cloud's own scratch index, the exact k-NN walk of the normals pre-step (launch_knn: rows in (d2, row) order),
 // then the tangent-plane moments and the 3x3 solve per point.

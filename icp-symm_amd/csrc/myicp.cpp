@@ -285,11 +285,36 @@ int MyICP::globalInit(symmicp_ctx *ctx)
 	}
 	global_result_.source_points = cl[0].m;
 	global_result_.target_points = cl[1].m;
-	std::vector<int32_t> pairs(2 * cl[0].m);
+	// with iss: the features were computed on the full (downsampled) clouds, whose neighbourhoods stay dense; only the keypoints' rows
+	// of them are matched, and the pairs are mapped back to rows of the downsampled clouds for RANSAC
+	std::vector<int32_t> kp[2];
+	std::vector<float> kf[2];
+	if (g.iss) {
+		symmicp_iss_config ic;
+		symmicp_iss_config_default(&ic);
+		ic.salient_radius = g.iss_salient_radius; ic.non_max_radius = g.iss_non_max_radius;
+		ic.gamma21 = g.iss_gamma21; ic.gamma32 = g.iss_gamma32; ic.min_neighbors = g.iss_min_neighbors;
+		for (int w = 0; w < 2; w++) {
+			kp[w].resize(cl[w].m);
+			size_t k = 0;
+			int st = symmicp_ctx_iss_keypoints(ctx, cl[w].xyz.data(), 3, 1, cl[w].m, &ic, kp[w].data(), cl[w].m, &k, nullptr, nullptr);
+			if (st != SYMMICP_OK) return failed(st, "ISS keypoints");
+			kp[w].resize(k);
+			(w == 0 ? global_result_.source_keypoints : global_result_.target_keypoints) = k;
+			kf[w].resize(33 * k);
+			for (size_t i = 0; i < k; i++) std::memcpy(&kf[w][33 * i], &cl[w].f[33 * (size_t)kp[w][i]], 33 * sizeof(float));
+		}
+		if (kp[0].size() < 3 || kp[1].size() < 3)
+			return failed(SYMMICP_ERR_NO_CONSENSUS, "ISS keypoints: fewer than 3 keypoints (" + std::to_string(kp[0].size()) + " in the source, " +
+			                                            std::to_string(kp[1].size()) + " in the target)");
+	}
+	const size_t na = g.iss ? kp[0].size() : cl[0].m, nb = g.iss ? kp[1].size() : cl[1].m;
+	std::vector<int32_t> pairs(2 * na);
 	size_t count = 0;
-	int st = symmicp_ctx_feature_correspondences(ctx, cl[0].f.data(), cl[0].m, cl[1].f.data(), cl[1].m, g.mutual ? 1 : 0, g.max_ratio, pairs.data(),
-	                                             nullptr, cl[0].m, &count);
+	int st = symmicp_ctx_feature_correspondences(ctx, g.iss ? kf[0].data() : cl[0].f.data(), na, g.iss ? kf[1].data() : cl[1].f.data(), nb,
+	                                             g.mutual ? 1 : 0, g.max_ratio, pairs.data(), nullptr, na, &count);
 	if (st != SYMMICP_OK) return failed(st, "feature correspondences");
+	if (g.iss) for (size_t k = 0; k < count; k++) { pairs[2 * k] = kp[0][(size_t)pairs[2 * k]]; pairs[2 * k + 1] = kp[1][(size_t)pairs[2 * k + 1]]; }
 	global_result_.correspondences = count;
 	if (count < 3) return failed(SYMMICP_ERR_NO_CONSENSUS, "fewer than 3 feature correspondences");
 	symmicp_ransac_config rc;
@@ -297,7 +322,11 @@ int MyICP::globalInit(symmicp_ctx *ctx)
 	rc.hypotheses = g.hypotheses; rc.seed = g.seed; rc.max_dist = g.max_dist; rc.edge_ratio = g.edge_ratio; rc.refits = g.refits;
 	st = symmicp_ctx_ransac(ctx, cl[0].xyz.data(), 3, 1, cl[0].m, cl[1].xyz.data(), 3, 1, cl[1].m, pairs.data(), count, &rc, global_result_.transform,
 	                        &global_result_.ransac, nullptr, nullptr, nullptr);
-	if (verbose_)
+	if (verbose_ && g.iss)
+		std::printf("global init: %zu -> %zu source and %zu -> %zu target points, %zu and %zu ISS keypoints, %zu correspondences, %d of %u hypotheses evaluated, %d -> %d inliers\n",
+		            cloud_pn_src->points.size(), cl[0].m, cloud_pn_tgt->points.size(), cl[1].m, kp[0].size(), kp[1].size(), count,
+		            global_result_.ransac.evaluated, rc.hypotheses, global_result_.ransac.inliers_ransac, global_result_.ransac.inliers_final);
+	else if (verbose_)
 		std::printf("global init: %zu -> %zu source and %zu -> %zu target points, %zu correspondences, %d of %u hypotheses evaluated, %d -> %d inliers\n",
 		            cloud_pn_src->points.size(), cl[0].m, cloud_pn_tgt->points.size(), cl[1].m, count, global_result_.ransac.evaluated, rc.hypotheses,
 		            global_result_.ransac.inliers_ransac, global_result_.ransac.inliers_final);

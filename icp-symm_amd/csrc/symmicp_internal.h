@@ -349,6 +349,13 @@ void launch_radius_fill(const TargetIndex &ix, float r2, const uint32_t *offs_ro
 void launch_spfh(const TargetIndex &ix, float r2, float *spfh_sorted, float *spfh_rows /* may be null */, int32_t *count_rows, hipStream_t s);
 void launch_fpfh(const TargetIndex &ix, float r2, const float *spfh_sorted, float *fpfh_rows, hipStream_t s);
 
+// ISS keypoints (kernels_keypoints.hip; symmicp_ctx_iss_keypoints): the same walk at the salient radius (s_sorted by sorted position,
+// s_rows / k_rows by ORIGINAL row) and at the non-maximum radius (flag_rows by original row: 1 = keypoint); after an exclusive scan of
+// the flags into pos_rows the scatter writes the kept rows in ascending order
+void launch_iss_saliency(const TargetIndex &ix, float r2, int32_t min_neighbors, float gamma21, float gamma32, float *s_sorted, float *s_rows,
+                         int32_t *k_rows, hipStream_t s);
+void launch_iss_nms(const TargetIndex &ix, float r2, int32_t min_neighbors, const float *s_sorted, uint32_t *flag_rows, hipStream_t s);
+void launch_iss_scatter(const uint32_t *flag_rows, const uint32_t *pos_rows, uint32_t n, int32_t *rows_out, hipStream_t s);
 
 // feature matching and RANSAC (kernels_global.hip; symmicp_ctx_feature_nn, symmicp_ctx_ransac).  feature_nn: fa / fb packed [n][33];
 // splits > 1 needs feature_nn_partial_bytes of `partial`.  ransac: pq8 [m][8] = p.xyz, 0, q.xyz, 0 about the pivots; hyp [H][12].

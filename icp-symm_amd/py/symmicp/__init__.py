@@ -90,6 +90,11 @@ class RansacResult(C.Structure):
                 ("rmse_final", C.c_double), ("transform", C.c_double * 16)]
 
 
+class IssConfig(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("salient_radius", C.c_float), ("non_max_radius", C.c_float), ("gamma21", C.c_float),
+                ("gamma32", C.c_float), ("min_neighbors", C.c_int32), ("reserved", C.c_int32)]
+
+
 class IndexInfo(C.Structure):
     """symmicp_index_info: what symmicp_ctx_index_info reads back of a target index (tests)"""
     _fields_ = [("struct_size", C.c_int32), ("n", C.c_uint32), ("grid_level", C.c_int32), ("gdim", C.c_int32), ("origin", C.c_float * 3),
@@ -124,6 +129,7 @@ EXPORTS = [
     "symmicp_ctx_reciprocal_info",
     "symmicp_set_color_weight", "symmicp_get_color_weight", "symmicp_set_source_intensity", "symmicp_set_target_intensity",
     "symmicp_get_source_intensity", "symmicp_intensity_gradient", "symmicp_ctx_intensity_gradient", "symmicp_pcd_read_intensity",
+    "symmicp_iss_config_default", "symmicp_iss_keypoints", "symmicp_ctx_iss_keypoints",
 ]
 
 _lib = None
@@ -257,6 +263,11 @@ def lib():
     L.symmicp_ctx_intensity_gradient.argtypes = [vp] + grd
     L.symmicp_pcd_read_intensity.argtypes = [C.c_char_p, fp, C.c_size_t, C.POINTER(C.c_int)]
     L.symmicp_pcd_read_intensity.restype = C.c_long
+    iss = [fp, C.c_size_t, C.c_size_t, C.c_size_t, C.POINTER(IssConfig), i32p, C.c_size_t, szp, fp, i32p]
+    L.symmicp_iss_config_default.argtypes = [C.POINTER(IssConfig)]
+    L.symmicp_iss_config_default.restype = None
+    L.symmicp_iss_keypoints.argtypes = [C.c_int] + iss
+    L.symmicp_ctx_iss_keypoints.argtypes = [vp] + iss
     _lib = L
     return L
 
@@ -538,6 +549,53 @@ def fpfh(xyz, nrm, radius, device=-1, want_spfh=False):
     if st != OK:
         raise SymmIcpError(st, "fpfh")
     return dict(fpfh=f, spfh=s, count=k) if want_spfh else f
+
+
+def iss_config(salient_radius, non_max_radius, gamma21=0.975, gamma32=0.975, min_neighbors=5):
+    cfg = IssConfig()
+    lib().symmicp_iss_config_default(C.byref(cfg))
+    cfg.salient_radius, cfg.non_max_radius = float(salient_radius), float(non_max_radius)
+    cfg.gamma21, cfg.gamma32, cfg.min_neighbors = float(gamma21), float(gamma32), int(min_neighbors)
+    return cfg
+
+
+def _iss_call(fn, head, xyz, cfg, cap=None, strides=None, want=True):
+    """fn(*head, <the C arguments>) -> (status, rows [cap] int32 or None, count, saliency [n] f32 or None, neighbors [n] int32 or
+    None).  cap None: the count only (rows_out == NULL, cap 0).  strides = (n, row stride, col stride) reads xyz as a flat f32 buffer."""
+    if strides is None:
+        xyz = _cloud(xyz)
+        n, xr, xc = xyz.shape[0], 3, 1
+    else:
+        xyz = np.ascontiguousarray(xyz, np.float32)
+        n, xr, xc = strides
+    rows = None if cap is None else np.full(max(cap, 1), -1, np.int32)
+    sal = np.zeros(max(n, 1), np.float32) if want else None
+    nb = np.zeros(max(n, 1), np.int32) if want else None
+    count = C.c_size_t(0)
+    st = fn(*head, _fptr(xyz), xr, xc, n, C.byref(cfg), None if rows is None else _i32ptr(rows), 0 if cap is None else cap, C.byref(count),
+            None if sal is None else _fptr(sal), None if nb is None else _i32ptr(nb))
+    return st, rows, int(count.value), None if sal is None else sal[:n], None if nb is None else nb[:n]
+
+
+def _iss_keypoints(fn, head, xyz, cfg, return_saliency):
+    """one call with cap = n, which always suffices (a count query first would run the kernels twice) -> (status, rows or
+    dict(rows=, saliency=, neighbors=))"""
+    st, rows, count, sal, nb = _iss_call(fn, head, xyz, cfg, cap=len(xyz), want=return_saliency)
+    if st != OK:
+        return st, None
+    rows = rows[:count].copy()
+    return st, (dict(rows=rows, saliency=sal, neighbors=nb) if return_saliency else rows)
+
+
+def iss_keypoints(xyz, salient_radius, non_max_radius, gamma21=0.975, gamma32=0.975, min_neighbors=5, return_saliency=False, device=-1):
+    """Intrinsic Shape Signatures keypoints on the GPU (symmicp_iss_keypoints; include/symmicp.h defines the arithmetic) -> the
+    keypoint rows [K] int32 in ascending order, or with return_saliency dict(rows=, saliency= [N] f32, neighbors= [N] int32:
+    the counts within salient_radius).  Exact ties of the saliency go to the lowest row."""
+    cfg = iss_config(salient_radius, non_max_radius, gamma21, gamma32, min_neighbors)
+    st, r = _iss_keypoints(lib().symmicp_iss_keypoints, (int(device),), xyz, cfg, return_saliency)
+    if st != OK:
+        raise SymmIcpError(st, "iss_keypoints")
+    return r
 
 
 def _features(f):
@@ -980,6 +1038,18 @@ class Engine:
         self._chk(st)
         return dict(fpfh=f, spfh=s, count=k)
 
+    def iss_keypoints(self, xyz, salient_radius, non_max_radius, gamma21=0.975, gamma32=0.975, min_neighbors=5, return_saliency=False):
+        """iss_keypoints on this context (symmicp_ctx_iss_keypoints, one call with cap = n)"""
+        cfg = iss_config(salient_radius, non_max_radius, gamma21, gamma32, min_neighbors)
+        st, r = _iss_keypoints(self._L.symmicp_ctx_iss_keypoints, (self._h,), xyz, cfg, return_saliency)
+        self._chk(st)
+        return r
+
+    def iss_keypoints_raw(self, xyz, cfg, cap=None, strides=None):
+        """one call of symmicp_ctx_iss_keypoints with a caller-chosen cap (None: rows_out == NULL) -> (status, rows, count, saliency,
+        neighbors); nothing is raised"""
+        return _iss_call(self._L.symmicp_ctx_iss_keypoints, (self._h,), xyz, cfg, cap, strides)
+
     def feature_nn(self, fa, fb):
         """feature_nn on this context (symmicp_ctx_feature_nn) -> (nn, d2, second)"""
         st, nn, d2, sec = _feature_nn_call(self._L.symmicp_ctx_feature_nn, (self._h,), fa, fb)
@@ -1237,15 +1307,20 @@ class MyICP:
         self._levels = levels
 
     def setGlobalInit(self, fpfh_radius, max_dist, voxel_leaf=0.0, normal_k=10, hypotheses=100000, seed=0, mutual=True, max_ratio=0.0,
-                      edge_ratio=0.9, refits=1):
+                      edge_ratio=0.9, refits=1, iss=False, iss_salient_radius=0.0, iss_non_max_radius=0.0, iss_gamma21=0.975, iss_gamma32=0.975,
+                      iss_min_neighbors=5):
         """global initialisation: with it set and no guess given, align() first voxel-downsamples both clouds with voxel_leaf (0: as
         given), estimates normals on the downsampled clouds when the caller supplied none (normal_k neighbours, viewpoint at the
         origin), computes FPFH features at fpfh_radius, their correspondences and a RANSAC transform, and starts the ordinary
         alignment (voxel levels included) from it.  A failure (ERR_NO_CONSENSUS among them) raises SymmIcpError.  FPFH matching
-        needs normals oriented alike in both clouds."""
+        needs normals oriented alike in both clouds.  With iss the features are still computed on the full (downsampled) clouds, but only
+        the rows of their ISS keypoints (Engine.iss_keypoints with the iss_* values) are matched and given to RANSAC; fewer than 3
+        keypoints in either cloud raises ERR_NO_CONSENSUS (no fall-back to the full cloud)."""
         self._global = dict(fpfh_radius=float(fpfh_radius), max_dist=float(max_dist), voxel_leaf=float(voxel_leaf), normal_k=int(normal_k),
                             hypotheses=int(hypotheses), seed=int(seed), mutual=bool(mutual), max_ratio=float(max_ratio),
-                            edge_ratio=float(edge_ratio), refits=int(refits))
+                            edge_ratio=float(edge_ratio), refits=int(refits), iss=bool(iss), iss_salient_radius=float(iss_salient_radius),
+                            iss_non_max_radius=float(iss_non_max_radius), iss_gamma21=float(iss_gamma21), iss_gamma32=float(iss_gamma32),
+                            iss_min_neighbors=int(iss_min_neighbors))
 
     def clearGlobalInit(self):
         self._global = None
@@ -1266,13 +1341,31 @@ class MyICP:
                 nrm, _ = e.estimate_normals(xyz, g["normal_k"])
             clouds.append((xyz, e.fpfh(xyz, nrm, g["fpfh_radius"])))
         (src, fs), (tgt, ft) = clouds
-        pairs, _ = e.feature_correspondences(fs, ft, g["mutual"], g["max_ratio"])
+        kp = None
+        if g["iss"]:
+            try:
+                kp = [e.iss_keypoints(x, g["iss_salient_radius"], g["iss_non_max_radius"], g["iss_gamma21"], g["iss_gamma32"], g["iss_min_neighbors"])
+                      for x in (src, tgt)]
+            except SymmIcpError as err:
+                raise SymmIcpError(err.status, "global initialisation: ISS keypoints: " + (e._L.symmicp_last_error(e._h) or b"").decode())
+            if min(len(kp[0]), len(kp[1])) < 3:
+                raise SymmIcpError(ERR_NO_CONSENSUS, "global initialisation: ISS keypoints: fewer than 3 keypoints (%d in the source, %d in the target)"
+                                   % (len(kp[0]), len(kp[1])))
+            pairs, _ = e.feature_correspondences(fs[kp[0]], ft[kp[1]], g["mutual"], g["max_ratio"])
+            pairs = np.stack([kp[0][pairs[:, 0]], kp[1][pairs[:, 1]]], 1).astype(np.int32)
+        else:
+            pairs, _ = e.feature_correspondences(fs, ft, g["mutual"], g["max_ratio"])
         if len(pairs) < 3:
             raise SymmIcpError(ERR_NO_CONSENSUS, "global initialisation: fewer than 3 feature correspondences")
         r = e.ransac(src, tgt, pairs, g["max_dist"], g["hypotheses"], g["seed"], g["edge_ratio"], g["refits"], check=False)
-        r.update(correspondences=len(pairs), source_points=len(src), target_points=len(tgt))
+        r.update(correspondences=len(pairs), source_points=len(src), target_points=len(tgt),
+                 source_keypoints=0 if kp is None else len(kp[0]), target_keypoints=0 if kp is None else len(kp[1]))
         self.global_result = r
-        if self._cfg["verbose"]:
+        if self._cfg["verbose"] and kp is not None:
+            print("global init: %d -> %d source and %d -> %d target points, %d and %d ISS keypoints, %d correspondences, %d of %d hypotheses evaluated, "
+                  "%d -> %d inliers" % (len(self.cloud_src), len(src), len(self.cloud_tgt), len(tgt), len(kp[0]), len(kp[1]), len(pairs), r["evaluated"],
+                                        g["hypotheses"], r["inliers_ransac"], r["inliers_final"]), flush=True)
+        elif self._cfg["verbose"]:
             print("global init: %d -> %d source and %d -> %d target points, %d correspondences, %d of %d hypotheses evaluated, %d -> %d inliers"
                   % (len(self.cloud_src), len(src), len(self.cloud_tgt), len(tgt), len(pairs), r["evaluated"], g["hypotheses"],
                      r["inliers_ransac"], r["inliers_final"]), flush=True)

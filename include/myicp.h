@@ -107,12 +107,22 @@ public:
 		float max_ratio = 0.f;
 		float edge_ratio = 0.9f;
 		int refits = 1;
+		// ISS keypoints (symmicp_ctx_iss_keypoints; off by default): the features are still computed on the full (downsampled) clouds,
+		// but only the keypoints' rows of them are matched, and RANSAC runs on those pairs (mapped back to rows of the downsampled
+		// clouds).  Matching cost falls from quadratic in the cloud to quadratic in the keypoint count.  Fewer than 3 keypoints in
+		// either cloud is SYMMICP_ERR_NO_CONSENSUS from align(); there is no fall-back to the full cloud.
+		bool iss = false;
+		float iss_salient_radius = 0.f;   // required with iss: finite, > 0
+		float iss_non_max_radius = 0.f;   // required with iss: finite, > 0
+		float iss_gamma21 = 0.975f, iss_gamma32 = 0.975f;
+		int iss_min_neighbors = 5;
 	};
 	struct GlobalResult {
 		symmicp_ransac_result ransac;  // of the last align() that ran the initialisation
 		float transform[16];           // row-major 4x4, source -> target: the guess the alignment started from
 		size_t correspondences;
 		size_t source_points, target_points;   // after downsampling
+		size_t source_keypoints, target_keypoints;   // with GlobalInit::iss: the ISS keypoints of each (0 without)
 		int status;                    // symmicp_status of the initialisation
 	};
 	void setGlobalInit(const GlobalInit &g) { global_ = g; have_global_ = true; }

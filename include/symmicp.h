@@ -582,6 +582,54 @@ int symmicp_fpfh(int device, const float *xyz, size_t xyz_row_stride, size_t xyz
                  const float *nrm, size_t nrm_row_stride, size_t nrm_col_stride, size_t n, float radius,
                  float *fpfh_out, float *spfh_out, int32_t *count_out);
 
+/* ---- Intrinsic Shape Signatures keypoints (Zhong 2009; PCL's ISSKeypoint3D, Open3D's compute_iss_keypoints) ----------------
+ * The salient points of a cloud of n points: those whose neighbourhood spreads in all three directions, and that are the
+ * most salient of their surroundings.  Global registration describes and matches these few instead of every point.  Defined by
+ * its arithmetic; the result is a function of the inputs alone, bit for bit.
+ * Neighbourhoods.  N_r(i) is N(i) of the radius search above at radius r: r2 = r * r in fp32, d2 the fp32
+ *   (dx*dx + dy*dy) + dz*dz, members d2 <= r2; row i itself is left out by ROW (a duplicate of it is a member); list order =
+ *   ascending position in the index's sorted order.  rs = cfg->salient_radius, rn = cfg->non_max_radius.
+ * Saliency.  k = |N_rs(i)| (neighbors_out[i]).  If k < min_neighbors: s_i = 0.  Else, for j in N_rs(i) in list order,
+ *   e = x_j - x_i per component in fp32; the six upper entries of S accumulate (double)e_a * (double)e_b in fp64, starting from
+ *   0.0 (the products are exact, the sums run in list order); C = S / (double)k per entry.
+ *   l1 >= l2 >= l3 = the eigenvalues of C in fp64 by cyclic Jacobi rotations (sweeps over the pairs (0,1), (0,2), (1,2), at most
+ *   12, until the squared off-diagonal sum is below 1e-300; rotation angle from theta = (a_qq - a_pp) / (2 a_pq),
+ *   t = sign(theta) / (|theta| + sqrt(theta^2 + 1)); eigenvalues only), for which |l - exact| <= 1e-13 * l1 holds.
+ *   The point is SALIENT iff  l2 < (double)gamma21 * l1  and  l3 < (double)gamma32 * l2  and  (float)l3 > 0
+ *   (products, not quotients: no division by zero; an exactly planar or collinear neighbourhood is never salient).
+ *   s_i = (float)l3 if salient, else 0 (saliency_out[i]).  The paper's per-neighbour weights are not applied (as in Open3D).
+ * Non-maximum suppression.  Row i is a keypoint iff  s_i > 0,  |N_rn(i)| >= min_neighbors,  and no j in N_rn(i) has
+ *   s_j > s_i, or s_j == s_i with row j < row i.  A pure function of the fp32 array s and the exact neighbourhoods.
+ *   Ties go to the LOWEST ROW: a deliberate departure from Open3D, which keeps both points of an exact tie (and so returns two
+ *   keypoints one spacing apart on symmetric data).
+ * Output.  rows_out [cap]: the keypoint rows in ascending order; *count_out their number (required).  SYMMICP_ERR_SIZE when the
+ *   count exceeds cap: *count_out, saliency_out and neighbors_out are written, the rows are not -- call again with room
+ *   (rows_out may be NULL with cap == 0 to ask for the count).  saliency_out [n] and neighbors_out [n] may be NULL.
+ * Cost grows with the neighbour counts (there is no max_nn cap): one walk of the tree per radius; the second walk is skipped
+ *   for points with s_i == 0.
+ * SYMMICP_ERR_ARG, all decided on the host before a device is needed: NULL xyz / cfg / count_out; NULL rows_out with cap > 0;
+ *   n == 0 or n > 2^31 - 1; cfg->struct_size != sizeof(symmicp_iss_config); a radius that is not finite and > 0; a gamma outside
+ *   (0, 1] or NaN; min_neighbors < 1; non-finite coordinates.
+ * xyz strided as in symmicp_set_source.  The ctx form runs on the context's stream and temporary arena: the context's clouds,
+ * index, attributes, certificates and states stay exactly as they were.  A sharded job computes the keypoints of the FULL
+ * cloud on every rank (the output is deterministic). */
+typedef struct {
+    uint32_t struct_size;     /* = sizeof(symmicp_iss_config), checked */
+    float salient_radius;     /* finite, > 0 (the caller sets it; default 0) */
+    float non_max_radius;     /* finite, > 0 (default 0) */
+    float gamma21, gamma32;   /* each finite, in (0, 1]; default 0.975f */
+    int32_t min_neighbors;    /* >= 1; default 5 */
+    int32_t reserved;
+} symmicp_iss_config;
+void symmicp_iss_config_default(symmicp_iss_config *cfg);
+int symmicp_ctx_iss_keypoints(symmicp_ctx *ctx, const float *xyz, size_t row_stride, size_t col_stride, size_t n,
+                              const symmicp_iss_config *cfg, int32_t *rows_out, size_t cap, size_t *count_out,
+                              float *saliency_out, int32_t *neighbors_out);
+/* the same on a context of its own, created on `device` (-1 = current) and destroyed again */
+int symmicp_iss_keypoints(int device, const float *xyz, size_t row_stride, size_t col_stride, size_t n,
+                          const symmicp_iss_config *cfg, int32_t *rows_out, size_t cap, size_t *count_out,
+                          float *saliency_out, int32_t *neighbors_out);
+
 /* ---- feature matching and RANSAC: global registration from FPFH features ("Feature matching and RANSAC") -------
  * All three run on the context's stream and temporary arena; the context's source, target, index and certificates stay exactly
  * as they were.  A sharded job computes the full result on every rank (the outputs are deterministic).
