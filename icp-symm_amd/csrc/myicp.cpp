@@ -224,6 +224,63 @@ int MyICP::align(float out4x4[16], const float *guess4x4)
 	return st;
 }
 
+// Multi-start refinement: one problem per guess on the object's clouds, one batch (symmicp_ctx_batch_align)
+int MyICP::alignMultiStart(const float *guesses4x4, size_t n_guesses, float out4x4[16])
+{
+	assert(cloud_src && cloud_tgt);
+	multi_results_.clear();
+	best_start_ = -1;
+	symmicp_ctx *ctx = context();
+	if (!ctx) { error_ = "symmicp_create failed: no usable gfx950 HIP device (there is no CPU fallback)"; return SYMMICP_ERR_HIP; }
+	const size_t ns = cloud_src->points.size(), nt = cloud_tgt->points.size();
+	symmicp_batch_config cfg;
+	symmicp_batch_config_default(&cfg);
+	cfg.mode = mode_; cfg.max_iters = max_iters; cfg.diff_threshold = diff_threshold; cfg.max_corr_dist = max_corr_dist_;
+	const bool in_scope = (mode_ == SYMMICP_MODE_PAPER || mode_ == SYMMICP_MODE_P2P || mode_ == SYMMICP_MODE_PLANE) &&
+	                      ns <= SYMMICP_BATCH_MAX_POINTS && nt <= SYMMICP_BATCH_MAX_POINTS;
+	if (in_scope) estimateNormals();      // (a call the batch refuses needs none)
+	else { fill_pn(*cloud_src, nullptr, *cloud_pn_src); fill_pn(*cloud_tgt, nullptr, *cloud_pn_tgt); }
+	const bool source_normals = mode_ != SYMMICP_MODE_PLANE || have_src_normals_;
+	// the packed pools of the batch call
+	std::vector<float> sx(3 * ns), sn(3 * ns), tx(3 * nt), tn(3 * nt);
+	for (size_t i = 0; i < ns; i++) {
+		const pcl::PointNormal &p = cloud_pn_src->points[i];
+		sx[3 * i] = p.x; sx[3 * i + 1] = p.y; sx[3 * i + 2] = p.z; sn[3 * i] = p.normal_x; sn[3 * i + 1] = p.normal_y; sn[3 * i + 2] = p.normal_z;
+	}
+	for (size_t i = 0; i < nt; i++) {
+		const pcl::PointNormal &p = cloud_pn_tgt->points[i];
+		tx[3 * i] = p.x; tx[3 * i + 1] = p.y; tx[3 * i + 2] = p.z; tn[3 * i] = p.normal_x; tn[3 * i + 1] = p.normal_y; tn[3 * i + 2] = p.normal_z;
+	}
+	std::vector<symmicp_batch_problem> problems(n_guesses, symmicp_batch_problem{0u, (uint32_t)ns, 0u, (uint32_t)nt});
+	multi_results_.resize(n_guesses);
+	int st = symmicp_ctx_batch_align(ctx, sx.data(), source_normals ? sn.data() : nullptr, ns, tx.data(), tn.data(), nt, problems.data(), guesses4x4,
+	                                 n_guesses, &cfg, multi_results_.data(), nullptr, nullptr);
+	if (st != SYMMICP_OK) { error_ = symmicp_last_error(ctx); multi_results_.clear(); return st; }
+	for (size_t k = 0; k < n_guesses; k++) {
+		const symmicp_batch_result &r = multi_results_[k];
+		if (r.status != SYMMICP_OK) continue;
+		if (best_start_ < 0) { best_start_ = (int)k; continue; }
+		const symmicp_batch_result &b = multi_results_[(size_t)best_start_];
+		if (r.pairs > b.pairs || (r.pairs == b.pairs && r.diff_final < b.diff_final)) best_start_ = (int)k;
+	}
+	if (best_start_ < 0) { error_ = "alignMultiStart: no start ended with SYMMICP_OK"; st = SYMMICP_ERR_DEGENERATE; }
+	else {
+		const symmicp_batch_result &b = multi_results_[(size_t)best_start_];
+		std::memcpy(transform_, b.transform, sizeof(transform_));
+		std::memset(&result_, 0, sizeof(result_));
+		result_.status = b.status; result_.iters = b.iters; result_.diff_initial = b.diff_initial; result_.diff_final = b.diff_final;
+		std::memcpy(result_.transform, b.transform, sizeof(b.transform));
+		std::memcpy(result_.diffs, b.diffs, sizeof(b.diffs));
+		if (verbose_) {
+			char buf[1024];
+			symmicp_format_result(transform_, buf, sizeof(buf));
+			std::fputs(buf, stdout);
+		}
+	}
+	if (out4x4) std::memcpy(out4x4, transform_, sizeof(transform_));
+	return st;
+}
+
 // SYMMICP_MODE_COLOR: the target's intensity gradient on its tangent planes (k = 10, the normals align() uses), then both attributes
 int MyICP::setColorAttributes(symmicp_ctx *ctx)
 {

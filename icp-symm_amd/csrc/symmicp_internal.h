@@ -232,6 +232,33 @@ struct PassTuning {
     uint32_t walk_budget = 160u;        // node visits of the budgeted walk (sharded first passes on volume-like targets)
 };
 
+// ---- batched alignment (kernels_batch.hip, engine_batch.cpp): one workgroup per problem, the whole loop inside it ----
+constexpr int kBatchThreads = 512;        // workgroup size of k_batch_align
+constexpr int kBatchQ = 4;                // queries per thread in registers
+constexpr int kBatchChunk = kBatchThreads * kBatchQ;      // queries per sweep of the target (2048)
+constexpr int kBatchTile = SYMMICP_BATCH_MAX_POINTS;      // target points staged in LDS, once per problem: the whole cloud (3 x 16 KB planar)
+constexpr int kBatchMerge = 1024;         // largest source that is searched with the target split over the workgroup's waves
+// How many ways the target is split for a source of n rows: the largest power of two S with (kBatchThreads / S) * kBatchQ >= n and whole
+// waves per split, so that a source of <= 1024 rows still occupies every wave (8 for <= 256 rows, 4 for <= 512, 2 for <= 1024, else 1)
+__host__ __device__ constexpr uint32_t batch_splits(uint32_t n) { return n <= 256u ? 8u : n <= 512u ? 4u : n <= 1024u ? 2u : 1u; }
+static_assert(kBatchThreads / 8 >= 64 && (kBatchThreads / 2) * kBatchQ == kBatchMerge, "a split is at least one wave; two splits cover kBatchMerge rows");
+struct BatchProblem {                     // one per workgroup, in start order (descending src_count x tgt_count)
+    uint32_t src_first, src_count, tgt_first, tgt_count;
+    float pivot[3];
+    uint32_t slot;                        // the problem's index in the caller's arrays (guess, out, traces)
+};
+struct BatchArgs {
+    const float *src_xyz, *src_nrm, *tgt_xyz, *tgt_nrm;      // packed [n][3] pools; src_nrm may be null (zeros)
+    const BatchProblem *problems;
+    const float *guess;                   // [B][16] by slot, or null (identity)
+    symmicp_batch_result *out;            // [B] by slot, zeroed by the host
+    float *trace_X;                       // [B][max_iters + 1][16] by slot, zeroed, or null
+    double *trace_sums;                   // [B][max_iters + 1][40], or null
+    int32_t mode, max_iters, fixed_iters;
+    float diff_threshold, max_d2, min_ndot, eps_rotation, eps_translation;
+};
+void launch_batch_align(const BatchArgs &a, uint32_t n_problems, hipStream_t s);
+
 // ---- kernel launchers (kernels.hip) ---------------------------------------
 void launch_pass_identity(const PassArgs &a, CloudSoA tgt, int blocks, bool vec4_ok, hipStream_t s);
 void launch_pass_indexed(const PassArgs &a, const float4 *tn /* pair records */, int blocks, hipStream_t s);

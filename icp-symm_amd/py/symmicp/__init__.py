@@ -95,6 +95,25 @@ class IssConfig(C.Structure):
                 ("gamma32", C.c_float), ("min_neighbors", C.c_int32), ("reserved", C.c_int32)]
 
 
+class BatchProblem(C.Structure):
+    """symmicp_batch_problem: the row ranges of one problem in the packed pools"""
+    _fields_ = [("src_first", C.c_uint32), ("src_count", C.c_uint32), ("tgt_first", C.c_uint32), ("tgt_count", C.c_uint32)]
+
+
+class BatchConfig(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("mode", C.c_int32), ("max_iters", C.c_int32), ("fixed_iters", C.c_int32),
+                ("diff_threshold", C.c_float), ("max_corr_dist", C.c_float), ("min_normal_dot", C.c_float), ("eps_rotation", C.c_float),
+                ("eps_translation", C.c_float), ("reserved", C.c_int32 * 3)]
+
+
+class BatchResult(C.Structure):
+    _fields_ = [("status", C.c_int32), ("iters", C.c_int32), ("diff_initial", C.c_float), ("diff_final", C.c_float), ("rcond", C.c_float),
+                ("pivot", C.c_float * 3), ("transform", C.c_float * 16), ("diffs", C.c_float * 64), ("pairs", C.c_double), ("sums", Sums)]
+
+
+BATCH_MAX_POINTS = 4096      # SYMMICP_BATCH_MAX_POINTS
+
+
 class IndexInfo(C.Structure):
     """symmicp_index_info: what symmicp_ctx_index_info reads back of a target index (tests)"""
     _fields_ = [("struct_size", C.c_int32), ("n", C.c_uint32), ("grid_level", C.c_int32), ("gdim", C.c_int32), ("origin", C.c_float * 3),
@@ -130,6 +149,7 @@ EXPORTS = [
     "symmicp_set_color_weight", "symmicp_get_color_weight", "symmicp_set_source_intensity", "symmicp_set_target_intensity",
     "symmicp_get_source_intensity", "symmicp_intensity_gradient", "symmicp_ctx_intensity_gradient", "symmicp_pcd_read_intensity",
     "symmicp_iss_config_default", "symmicp_iss_keypoints", "symmicp_ctx_iss_keypoints",
+    "symmicp_batch_config_default", "symmicp_batch_align", "symmicp_ctx_batch_align",
 ]
 
 _lib = None
@@ -268,6 +288,12 @@ def lib():
     L.symmicp_iss_config_default.restype = None
     L.symmicp_iss_keypoints.argtypes = [C.c_int] + iss
     L.symmicp_ctx_iss_keypoints.argtypes = [vp] + iss
+    bat = [fp, fp, C.c_size_t, fp, fp, C.c_size_t, C.POINTER(BatchProblem), fp, C.c_size_t, C.POINTER(BatchConfig), C.POINTER(BatchResult), fp,
+           C.POINTER(C.c_double)]
+    L.symmicp_batch_config_default.argtypes = [C.POINTER(BatchConfig)]
+    L.symmicp_batch_config_default.restype = None
+    L.symmicp_batch_align.argtypes = [C.c_int] + bat
+    L.symmicp_ctx_batch_align.argtypes = [vp] + bat
     _lib = L
     return L
 
@@ -691,6 +717,81 @@ def ransac(src, tgt, pairs, max_dist, hypotheses=100000, seed=0, edge_ratio=0.9,
     return r
 
 
+def batch_config(**kw):
+    """symmicp_batch_config with its defaults (PAPER, 10 iterations, threshold 1, gates and eps rule off), then the given fields"""
+    cfg = BatchConfig()
+    lib().symmicp_batch_config_default(C.byref(cfg))
+    for k, v in kw.items():
+        if not hasattr(cfg, k) or k == "reserved":
+            raise AttributeError(k)
+        setattr(cfg, k, v)
+    return cfg
+
+
+def batch_problems(problems):
+    """[(src_first, src_count, tgt_first, tgt_count), ...] (or an [B, 4] array) -> a ctypes array of symmicp_batch_problem"""
+    rows = np.asarray(problems, np.int64).reshape(-1, 4)
+    if rows.size and (rows.min() < 0 or rows.max() > 0xFFFFFFFF):
+        raise ValueError("problem rows must fit 32 unsigned bits")
+    return (BatchProblem * max(len(rows), 1))(*[BatchProblem(*[int(v) for v in r]) for r in rows]), len(rows)
+
+
+def _batch_call(fn, head, src, src_n, tgt, tgt_n, problems, guesses, cfg, trace):
+    """fn(*head, <the C arguments>) -> (status, results (a ctypes array of BatchResult), trace_X [B, max_iters + 1, 4, 4] f32 or None,
+    trace_sums [B, max_iters + 1, 40] f64 or None)"""
+    src, tgt, tgt_n = _cloud(src), _cloud(tgt), _cloud(tgt_n)
+    src_n = None if src_n is None else _cloud(src_n)
+    if (src_n is not None and len(src_n) != len(src)) or len(tgt_n) != len(tgt):
+        raise ValueError("a normal per point")
+    probs, B = batch_problems(problems)
+    g = None
+    if guesses is not None:
+        g = np.ascontiguousarray(guesses, np.float32).reshape(-1, 16)
+        if len(g) != B:
+            raise ValueError("one 4x4 guess per problem")
+    out = (BatchResult * max(B, 1))()
+    rows = max(int(cfg.max_iters), 0) + 1
+    tX = np.zeros((max(B, 1), rows, 16), np.float32) if trace else None
+    tS = np.zeros((max(B, 1), rows, NSUM), np.float64) if trace else None
+    st = fn(*head, _fptr(src), None if src_n is None else _fptr(src_n), len(src), _fptr(tgt), _fptr(tgt_n), len(tgt), probs,
+            None if g is None else _fptr(g), B, C.byref(cfg), out, None if tX is None else _fptr(tX),
+            None if tS is None else tS.ctypes.data_as(C.POINTER(C.c_double)))
+    return st, out, (None if tX is None else tX[:B].reshape(B, rows, 4, 4)), (None if tS is None else tS[:B])
+
+
+def _batch_dicts(out, B):
+    res = []
+    for b in range(B):
+        r = out[b]
+        res.append(dict(status=r.status, iters=r.iters, diff_initial=r.diff_initial, diff_final=r.diff_final, rcond=r.rcond,
+                        pivot=np.array(r.pivot[:], np.float32), transform=np.array(r.transform[:], np.float32).reshape(4, 4),
+                        diffs=np.array(r.diffs[:min(max(r.iters, 0) + 1, 64)], np.float32), pairs=r.pairs,
+                        sums=np.array(r.sums.s[:], np.float64), raw=bytes(r)))
+    return res
+
+
+def _batch_align(fn, head, src, src_n, tgt, tgt_n, problems, guesses, trace, cfg):
+    c = batch_config(**cfg)
+    st, out, tX, tS = _batch_call(fn, head, src, src_n, tgt, tgt_n, problems, guesses, c, trace)
+    if st != OK:
+        return st, None
+    res = _batch_dicts(out, len(np.asarray(problems).reshape(-1, 4)))
+    return st, ((res, tX, tS) if trace else res)
+
+
+def batch_align(src, src_n, tgt, tgt_n, problems, guesses=None, trace=False, device=-1, **cfg):
+    """Many small ICP problems in one launch (symmicp_batch_align; include/symmicp.h has the contract).  src / src_n and tgt / tgt_n
+    are packed [n, 3] pools, problems [(src_first, src_count, tgt_first, tgt_count), ...] row ranges of them (at most BATCH_MAX_POINTS
+    rows each), guesses [B, 4, 4] or None, cfg the fields of BatchConfig (mode, max_iters, fixed_iters, diff_threshold,
+    max_corr_dist, min_normal_dot, eps_rotation, eps_translation).  -> one dict per problem (status, iters, diff_initial, diff_final,
+    rcond, pivot, transform, diffs, pairs, sums, raw = the result struct's bytes); with trace also trace_X [B, max_iters + 1, 4, 4]
+    and trace_sums [B, max_iters + 1, 40]: (results, trace_X, trace_sums).  A degenerate problem is reported in its own status."""
+    st, r = _batch_align(lib().symmicp_batch_align, (int(device),), src, src_n, tgt, tgt_n, problems, guesses, trace, cfg)
+    if st != OK:
+        raise SymmIcpError(st, "batch_align")
+    return r
+
+
 def shard_range(n, nranks, rank):
     b, c = C.c_size_t(0), C.c_size_t(0)
     st = lib().symmicp_shard_range(n, nranks, rank, C.byref(b), C.byref(c))
@@ -1089,6 +1190,21 @@ class Engine:
                                                         _fptr(piv)))
         return hyp, status, piv.reshape(2, 3)
 
+    def batch_align(self, src, src_n, tgt, tgt_n, problems, guesses=None, trace=False, **cfg):
+        """batch_align on this context's stream and scratch arena; its clouds, options and loop state stay as they are"""
+        st, r = _batch_align(self._L.symmicp_ctx_batch_align, (self._h,), src, src_n, tgt, tgt_n, problems, guesses, trace, cfg)
+        self._chk(st)
+        return r
+
+    def batch_align_raw(self, src, src_n, tgt, tgt_n, problems, guesses, cfg, trace=False):
+        """the C call as it is, cfg a BatchConfig -> (status, results array, trace_X, trace_sums) (tests)"""
+        return _batch_call(self._L.symmicp_ctx_batch_align, (self._h,), src, src_n, tgt, tgt_n, problems, guesses, cfg, trace)
+
+    def align_multistart(self, src, src_n, tgt, tgt_n, guesses, **cfg):
+        """one pair refined from every guess [B, 4, 4] in one batch -> one result dict per guess"""
+        g = np.ascontiguousarray(guesses, np.float32).reshape(-1, 16)
+        return self.batch_align(src, src_n, tgt, tgt_n, [(0, len(src), 0, len(tgt))] * len(g), g, **cfg)
+
     def enable_timing(self, on=True):
         self._chk(self._L.symmicp_enable_timing(self._h, int(on)))      # 0 off, 1 per pass, 2 per kernel
 
@@ -1291,6 +1407,43 @@ class MyICP:
         self._global = None
         self.global_result = None
         self._have_src = self._have_tgt = False         # normals supplied by the caller through setInput* (not estimated here)
+        self.multistart_results = []
+
+    def alignMultiStart(self, guesses):
+        """one batch on the object's clouds, a problem per guess [B, 4, 4] (Engine.align_multistart with the object's mode, max_iters,
+        diff_threshold, max_corr_dist, fixed_iters, min_normal_dot and eps rule; normals estimated as align does).  Adopts as final
+        transformation the result with status OK and the most pairs -- ties to the smaller diff_final, then the lowest index -- and
+        returns its index (-1: no problem ended OK; the final transformation stays).  Clouds above BATCH_MAX_POINTS points or a mode
+        other than PAPER, P2P and PLANE raise the batch call's error: there is no fallback to a loop."""
+        assert self.cloud_src is not None and self.cloud_tgt is not None
+        keys = ("mode", "max_iters", "diff_threshold", "max_corr_dist", "fixed_iters", "min_normal_dot", "eps_rotation", "eps_translation")
+        cfg = {k: self._cfg[k] for k in keys if k in self._cfg}
+        batch_config(**cfg)
+        g = np.ascontiguousarray(guesses, np.float32).reshape(-1, 16)
+        if self._cfg["mode"] in (MODE_PAPER, MODE_P2P, MODE_PLANE) and max(len(self.cloud_src), len(self.cloud_tgt)) <= BATCH_MAX_POINTS and len(g):
+            self.estimateNormals()
+        else:      # (the call refuses: no normals are estimated for it)
+            z = np.zeros_like
+            st, _ = _batch_align(lib().symmicp_batch_align, (int(self._cfg.get("device", -1)),), self.cloud_src, z(self.cloud_src), self.cloud_tgt,
+                                 z(self.cloud_tgt), [(0, len(self.cloud_src), 0, len(self.cloud_tgt))] * len(g), g if len(g) else None, False, cfg)
+            raise SymmIcpError(st if st != OK else ERR_ARG, "alignMultiStart")
+        with Engine(**dict(self._cfg, verbose=0)) as e:
+            self.multistart_results = e.align_multistart(self.cloud_src, self.normals_src, self.cloud_tgt, self.normals_tgt, g, **cfg)
+        best = -1
+        for k, r in enumerate(self.multistart_results):
+            if r["status"] == OK and (best < 0 or (r["pairs"], -r["diff_final"]) > (self.multistart_results[best]["pairs"],
+                                                                                   -self.multistart_results[best]["diff_final"])):
+                best = k
+        if best >= 0:
+            self.last_result = self.multistart_results[best]
+            self._final = self.last_result["transform"]
+            if self._cfg["verbose"]:
+                print(format_result(self._final), end="", flush=True)
+        return best
+
+    def multiStartResults(self):
+        """every result of the last alignMultiStart, in the order of its guesses"""
+        return self.multistart_results
 
     def setMaxCorrespondenceDistance(self, d):
         """pairs farther apart than d are dropped (Config.max_corr_dist; <= 0: every pair is kept)"""

@@ -129,6 +129,16 @@ public:
 	void clearGlobalInit() { have_global_ = false; }
 	const GlobalResult &globalResult() const { return global_result_; }
 	const symmicp_result &lastResult() const { return result_; }
+	// Multi-start refinement: ONE batch on the object's clouds and context (symmicp_ctx_batch_align, include/symmicp.h), a problem per
+	// guess (n_guesses row-major 4x4 matrices), with the object's mode, max_iters, diff_threshold and max correspondence distance;
+	// normals are estimated as align() does.  Every result stays available through multiStartResults().  Adopted as final
+	// transformation: the result with status SYMMICP_OK and the most pairs; ties go to the smaller diff_final, then to the lowest
+	// index (bestStart(); -1 and the final transformation unchanged when no problem ended OK: the call then returns
+	// SYMMICP_ERR_DEGENERATE).  Clouds above SYMMICP_BATCH_MAX_POINTS points, or a mode other than PAPER, P2P and PLANE, return the
+	// batch call's error: there is no fallback to a loop of align() calls.
+	int alignMultiStart(const float *guesses4x4, size_t n_guesses, float out4x4[16] = nullptr);
+	const std::vector<symmicp_batch_result> &multiStartResults() const { return multi_results_; }
+	int bestStart() const { return best_start_; }
 	const char *lastError() const { return error_.c_str(); }
 
 private:
@@ -168,5 +178,7 @@ private:
 	bool ctx_no_src_normals_;            // the context holds a source set without normals (PLANE): no other mode can run on it
 	float transform_[16];
 	symmicp_result result_;
+	std::vector<symmicp_batch_result> multi_results_;
+	int best_start_ = -1;
 	std::string error_;
 };

@@ -826,6 +826,77 @@ int symmicp_reset_stats(symmicp_ctx *ctx);
  * 1M-point iteration; mode 2 is for profiling, not for throughput runs) */
 int symmicp_enable_timing(symmicp_ctx *ctx, int on);
 
+/* ---- batched alignment: many small ICP problems in one launch ------------------------------------------------------------------
+ * B independent problems of at most SYMMICP_BATCH_MAX_POINTS points per cloud, each run to its end by ONE workgroup: its brute-force
+ * search, its rows, its record and its solve never leave the workgroup, and nothing returns to the host before every problem has
+ * ended.  Multi-start refinement (one pair, many guesses), many object pairs, keypoint-sized scan pairs.
+ *   Clouds      packed [n][3] pools src_xyz / src_nrm [ns_total][3] and tgt_xyz / tgt_nrm [nt_total][3].  Problem b reads the source
+ *               rows [src_first, src_first + src_count) and the target rows [tgt_first, tgt_first + tgt_count); the ranges of different
+ *               problems may overlap or coincide.  src_nrm may be NULL in PLANE only (with min_normal_dot <= -1), as for
+ *               symmicp_set_source: the source normals are zeros then.
+ *   Pivot       the mean of the problem's target rows, summed in fp64 in row order, divided by the count and rounded to fp32; reported.
+ *   Start       X_0 = guess16 + 16 b (row-major 4x4), or the identity when guess16 is NULL; iters = 0.
+ *   Pass k      moves the ORIGINAL source rows by X_k in fp32, unfused: ((m0 x + m1 y) + m2 z) + m3 w, points with w = 1, normals with
+ *               w = 0.  Row i pairs with the target row j that minimises (d2, j) over the problem's target rows in the caller's order,
+ *               d2 = (dx dx + dy dy) + dz dz in fp32 -- exact brute force, ties to the lowest row.  The gates: the pair is dropped when
+ *               max_corr_dist > 0 and d2 > max_corr_dist * max_corr_dist (the fp32 square), then when min_normal_dot > -1 and the moved
+ *               source normal . target normal < min_normal_dot.  The mode's record (symmicp_sums: PAPER's, P2P's or PLANE's rows in fp32
+ *               about `pivot`, summed in fp64) is formed by the same source the pass kernels of a context use.
+ *   Loop        diff = (float)record[33]; diff_initial = the diff of pass 0.  Then symmicp_align's loop:
+ *                 while ((fixed_iters || diff > diff_threshold) && iters < max_iters) {
+ *                     iters++; if (iters <= 64) diffs[iters - 1] = diff;
+ *                     increment = the solve of the record: symmicp_solve's arithmetic (exact conditioning) and acceptance; on failure
+ *                                 iters--, status = SYMMICP_ERR_DEGENERATE, stop
+ *                     X = increment * X (4x4 product in fp32);  run the next pass with X;  diff = (float)record[33]
+ *                     if (eps_rotation > 0 && eps_translation > 0 && !fixed_iters && the increment rotates by less than eps_rotation
+ *                         and translates by less than eps_translation) stop
+ *                 }
+ *   Result      status (SYMMICP_OK or SYMMICP_ERR_DEGENERATE: that problem alone; the call still returns SYMMICP_OK and no other
+ *               problem is affected), iters, diff_initial, diff_final, rcond of the last solve (0 if none ran), pivot, transform = the
+ *               last X, diffs, and the last pass's record with its pair count (slot 34).
+ *   Traces      trace_X [B][max_iters + 1][16] and trace_sums [B][max_iters + 1][40] (each may be NULL): X_k and the record of pass k
+ *               for every pass that ran; rows not reached stay zero.
+ *   Purity      a problem's outputs are a function of its own rows, guess and the configuration only: bit for bit the same whatever
+ *               B, the problem's place in the batch, the other problems, or the run (fixed-order sums, no floating-point atomics).
+ * SYMMICP_ERR_ARG, decided on the host before a device is needed: NULL src_xyz, tgt_xyz, tgt_nrm, problems, cfg or out; a wrong
+ * struct_size; a mode other than PAPER, P2P and PLANE; B == 0 or B > 2^20; a count of 0; a range outside its pool; max_iters outside
+ * 0 .. 1000; a non-finite diff_threshold, max_corr_dist, min_normal_dot, eps_rotation or eps_translation; NULL src_nrm outside PLANE,
+ * or together with min_normal_dot > -1; a non-finite coordinate (or normal component) in a row some problem uses.  SYMMICP_ERR_SIZE: a
+ * count above SYMMICP_BATCH_MAX_POINTS (the message names the limit): above it the tree search of a context wins.
+ * Out of scope, refused or absent: QUIRKS, GICP and COLOR (SYMMICP_ERR_ARG); robust losses, trimming, one-to-one, median and
+ * reciprocal rejection, tree search (the configuration has no field for them); sharding one batch over ranks (each rank may run its
+ * own).  The ctx form runs on the context's stream and scratch arena: its clouds, index, certificates, options and loop state stay
+ * exactly as they were, so it may be called between two symmicp_step calls.  The other form creates a context on `device`
+ * (-1 = current) and destroys it again. */
+#define SYMMICP_BATCH_MAX_POINTS 4096      /* per cloud of a problem; above it the tree search wins: use a context */
+typedef struct { uint32_t src_first, src_count, tgt_first, tgt_count; } symmicp_batch_problem;
+typedef struct {
+    uint32_t struct_size;         /* = sizeof(symmicp_batch_config), checked */
+    int32_t mode;                 /* SYMMICP_MODE_PAPER, _P2P or _PLANE */
+    int32_t max_iters;            /* 0 .. 1000; default 10 */
+    int32_t fixed_iters;          /* != 0: ignore the threshold (and the eps rule), run exactly max_iters iterations */
+    float diff_threshold, max_corr_dist, min_normal_dot, eps_rotation, eps_translation;   /* as symmicp_config */
+    int32_t reserved[3];
+} symmicp_batch_config;
+typedef struct {
+    int32_t status, iters;
+    float diff_initial, diff_final, rcond;    /* rcond of the last solve */
+    float pivot[3];
+    float transform[16];
+    float diffs[64];
+    double pairs;                             /* slot 34 of the last record */
+    symmicp_sums sums;                        /* the last pass's record */
+} symmicp_batch_result;
+void symmicp_batch_config_default(symmicp_batch_config *cfg);      /* PAPER, 10 iterations, threshold 1, every gate and the eps rule off */
+int symmicp_ctx_batch_align(symmicp_ctx *ctx, const float *src_xyz, const float *src_nrm, size_t ns_total,
+                            const float *tgt_xyz, const float *tgt_nrm, size_t nt_total,
+                            const symmicp_batch_problem *problems, const float *guess16, size_t B,
+                            const symmicp_batch_config *cfg, symmicp_batch_result *out, float *trace_X, double *trace_sums);
+int symmicp_batch_align(int device, const float *src_xyz, const float *src_nrm, size_t ns_total,
+                        const float *tgt_xyz, const float *tgt_nrm, size_t nt_total,
+                        const symmicp_batch_problem *problems, const float *guess16, size_t B,
+                        const symmicp_batch_config *cfg, symmicp_batch_result *out, float *trace_X, double *trace_sums);
+
 /* ---- PCD I/O (replaces pcl::PCDReader use in MyICP::LoadCloud, myicp.cpp:20-31) */
 /* returns point count (>=0) or -symmicp_status.  xyz/nrm packed AoS (3 floats per point); pass
  * xyz==NULL to query the count.  nrm may be NULL.  *has_normals reports normal_x/y/z fields. */
