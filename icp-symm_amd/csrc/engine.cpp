@@ -43,6 +43,8 @@ void read_switches(Switches &w)
     w.budget_walk = tri("SYMMICP_BUDGET_WALK");
     w.optimistic = tri("SYMMICP_OPTIMISTIC");
     w.compact = tri("SYMMICP_COMPACT");
+    w.cert_pass = (int)num("SYMMICP_CERT_PASS", 1);
+    w.cert_head = (int)num("SYMMICP_CERT_HEAD", 4);
     w.pass_blocks = (int)num("SYMMICP_PASS_BLOCKS", 2048);
     w.id_blocks = (int)num("SYMMICP_ID_BLOCKS", 2048);
     w.acc_blocks = (int)num("SYMMICP_ACC_BLOCKS", 512);

@@ -94,6 +94,8 @@ struct Switches {
     double hood_frac = 0.8;                // scans keep neighbourhoods once the previous pass searched under this fraction of the pairs
     bool no_hood = false, no_cert = false, walk_full_grid = false, host_loop = false, no_loop_stragglers = false, force_comm = false;
     int budget_walk = -1, optimistic = -1, compact = -1;      // -1 auto, 0 never, 1 always
+    int cert_pass = 1;                     // k_pass_certified in the device loop: 0 never, 1 by run_batch's rule, 2 from the first device pass whatever the counts say
+    int cert_head = 4;                     // ... passes of the fused head of a run that goes out in one piece (run_batch)
     int pass_blocks = 2048, id_blocks = 2048, acc_blocks = 512, fused_blocks = 512, compact_blocks = 1280;
     int feature_nn_splits = 0, feature_nn_queries = 0;      // symmicp_ctx_feature_nn: candidate splits / queries per thread (0: chosen from the sizes)
     PassTuning tune;                       // wave_mode_max, cells_chunk, walk_budget
@@ -254,6 +256,8 @@ struct symmicp_ctx {
     uint32_t *ticket = nullptr;          // ticket of the final reduce
     long long last_list_len = -1;        // work-list length of the last pass (all ranks); -1 = unknown (full walk grid)
     long long last_uncertified = -1;     // TREE: pairs the last pass had to search again (all ranks); -1 = unknown
+    long long last_scans = -1;           // ... and those of them that reached a scan, a probe or the walk; -1 = unknown
+    bool cert_pass_failed = false;       // a certified-only pass of this alignment came back incomplete: the kernel is not chosen again
     // device-driven runs of passes (run_batch): loop state in device memory, per-pass records + end flag in host-mapped memory
     static constexpr int kRing = 65;
     LoopState *d_loop = nullptr, *h_loop = nullptr, *h_loop_dev = nullptr;

@@ -230,7 +230,13 @@ static int run_pass(symmicp_ctx *c, const float Xapply[16], bool from_cur, bool 
     if (c->cfg.corr == SYMMICP_CORR_TREE && c->h_sums[kNSum - 1] >= kListDropped)
         return fail(c, SYMMICP_ERR_HIP, "a work-list shard overflowed: appends were dropped (internal capacity error)");
     long long list_len = (c->cfg.corr == SYMMICP_CORR_TREE) ? (long long)c->h_sums[kNSum - 1] : -1;
-    c->last_uncertified = (c->cfg.corr == SYMMICP_CORR_TREE && !first) ? (long long)c->h_sums[kNSum - 2] : -1;
+    c->last_uncertified = c->last_scans = -1;
+    if (c->cfg.corr == SYMMICP_CORR_TREE && !first) {
+        // (slot 38: the pairs searched + kScanUnit x those that reached a scan, k_final_reduce)
+        const double sr = c->h_sums[kNSum - 2], sc = std::floor(sr / kScanUnit);
+        c->last_uncertified = (long long)(sr - sc * kScanUnit);
+        c->last_scans = (long long)sc;
+    }
     if (optimistic && list_len > 0) {
         // the walk was skipped but some queries needed it: their pairs are provisional, so are the sums
         c->st.kernel_launches[7]++;
@@ -318,8 +324,17 @@ static int run_batch(symmicp_ctx *c, int want, float *diffs_before, int *n_done,
     const bool no_stage = c->sw.no_loop_stragglers;      // A/B runs
     bool stragglers = tree && c->last_list_len > 0 && !no_stage;
     lc.list_limit = kLoopListLimit;
+    // The certified-only pass (k_pass_certified) runs a chunk when the last complete pass left no work list and sent no pair to a scan
+    // (and the chunk carries no straggler stage); a pass of it that comes back incomplete is redone by the host like any pass with an
+    // unexpected list, and the kernel is then left alone for the rest of the alignment: one repeated pass at most.
+    // SYMMICP_CERT_PASS: 0 never, 2 from the first device pass whatever the counts say (tests of the redo path, A/B runs).
+    const int cert_mode = (tree && c->cert && !c->sw.no_cert && !c->cert_pass_failed) ? c->sw.cert_pass : 0;
+    if (cert_mode == 2) stragglers = false;
+    bool cert_chunk = false;                           // this chunk's pass kernel (plan_chunk below)
+    uint8_t pass_kernel[symmicp_ctx::kRing] = {};      // by iteration % kRing: 1 = the certified-only kernel ran (or was to run) that pass
     if (lc.max_iters > c->cfg.max_iters) lc.max_iters = c->cfg.max_iters;
     const int it0 = c->iters;
+    const long long list0 = c->last_list_len, scans0 = c->last_scans;
     // loop state as the host loop left it
     LoopState ls{};
     std::memcpy(ls.X, c->X, sizeof(ls.X));
@@ -360,8 +375,26 @@ static int run_batch(symmicp_ctx *c, int want, float *diffs_before, int *n_done,
     if (timed_run && c->ev_used + want > symmicp_ctx::kEvRing) flush_events(c);
     // (a run that only a bail-out can stop -- fixed iteration count, no increment criterion, no work list at entry -- is enqueued in one
     // piece: every chunk boundary is a host look at the loop state, ~12 us of idle GPU)
-    const bool unstoppable = lc.fixed_iters && !(lc.eps_rotation > 0.f && lc.eps_translation > 0.f) && !stragglers;
-    int enq = 0, chunk = unstoppable ? want : 4, n_stage = 0;
+    const bool one_piece = lc.fixed_iters && !(lc.eps_rotation > 0.f && lc.eps_translation > 0.f);
+    int enq = 0, n_stage = 0;
+    // ... but its head goes out in short chunks of fused passes while the last complete pass still scanned: a run starts while a few
+    // hundred pairs are still settling and single scans trickle on for some passes (1M surface pair, scans per device pass: 159 113 1 8
+    // 3 1 0 0 ...), so one short head would see a scan and leave the whole run to the fused kernel.  kCertHeads chunks at most; the rest
+    // goes out in one piece with the kernel the last head's last pass allows.  (A boundary is paid back by two certified-only passes.)
+    constexpr int kCertHeads = 3;
+    int heads_left = (one_piece && !stragglers && cert_mode == 1 && c->sw.cert_head > 0) ? kCertHeads : 0;
+    // The plan of the next chunk, from the last complete pass (its work list and scan count; `left` passes to go, `prev` passes in the
+    // chunk before, 0: none): which kernel runs it (cert_chunk) and how many passes it holds.  All of the chunking is here: with the
+    // straggler stage on, chunks stay at 4 (the stage can only be dropped between chunks); a run that can stop by itself doubles them;
+    // a run that only a bail-out can stop sends fused heads while passes still scan and then the rest in one piece.
+    auto plan_chunk = [&](long long list_len, long long scans, int left, int prev) -> int {
+        cert_chunk = cert_mode == 2 || (cert_mode == 1 && !stragglers && list_len == 0 && scans == 0);
+        if (stragglers) return 4;
+        if (!one_piece) return prev ? 2 * prev : 4;
+        if (!cert_chunk && heads_left > 0 && left > c->sw.cert_head) { heads_left--; return c->sw.cert_head; }
+        return left;
+    };
+    int chunk = plan_chunk(c->last_list_len, c->last_scans, want, 0);
     bool first_chunk = true;
     while (enq < want) {
         const int nq = (want - enq < chunk) ? want - enq : chunk;
@@ -384,7 +417,9 @@ static int run_batch(symmicp_ctx *c, int want, float *diffs_before, int *n_done,
                 hipEventRecord(ev[0], c->stream);
             }
             if (tree) {
-                launch_pass_fused(a, c->ix, c->wl, fused_blocks, c->stream);
+                pass_kernel[(it_before + 1 + p) % symmicp_ctx::kRing] = cert_chunk ? 1 : 0;      // (the pass this launch is when no stop comes before it)
+                if (cert_chunk) launch_pass_certified(a, c->ix, c->wl, fused_blocks, c->stream);
+                else launch_pass_fused(a, c->ix, c->wl, fused_blocks, c->stream);
                 if (stragglers) launch_loop_stragglers(a, c->ix, c->wl, kListBlocks, c->sw.tune, c->stream);
             }
             else launch_pass_identity(a, c->tgt, blocks, vec4, c->stream);
@@ -441,9 +476,9 @@ static int run_batch(symmicp_ctx *c, int want, float *diffs_before, int *n_done,
         // with the stage on, chunks stay short: the stage (two more launches per pass) can only be dropped between chunks, and lists die out
         // within a few passes of a run's start (8M scan pair: 8 8 6 2 | 2 0 1 0 | 0 ...); once it is off and only a bail-out can stop the run,
         // the rest goes out in one piece
-        if (stragglers) chunk = 4;
-        else if (lc.fixed_iters && !(lc.eps_rotation > 0.f && lc.eps_translation > 0.f)) chunk = want;
-        else chunk *= 2;
+        if (cert_mode == 2) stragglers = false;
+        const LoopRecord &lr = c->h_ring[c->h_loop->iters % symmicp_ctx::kRing];      // the last complete pass (this chunk completed one: no stop)
+        chunk = plan_chunk(lr.list_len, lr.reserved, want - enq, chunk);
     }
     const LoopState &hl = *c->h_loop;
     const int it1 = hl.iters;                         // passes complete
@@ -467,6 +502,10 @@ static int run_batch(symmicp_ctx *c, int want, float *diffs_before, int *n_done,
             std::memcpy(e.X, r.X, sizeof(e.X));
             e.rcond = r.rcond; e.iter = k; e.status = r.status; e.solved = r.solved; e.list_len = k == it0 ? 0 : r.list_len;
             e.reason = hl.reason; e.batch = c->loop_log_batches;
+            // which kernel ran the pass (0: k_pass_fused or the host, 1: k_pass_certified); + 0x100 on the batch's last entry when the pass
+            // behind it ran certified-only and was handed back incomplete
+            e.reserved = k == it0 ? 0 : pass_kernel[k % symmicp_ctx::kRing];
+            if (k == it1 && hl.reason == LOOP_REDO_PASS && pass_kernel[(it1 + 1) % symmicp_ctx::kRing]) e.reserved |= 0x100;
             if (!e.solved) { std::memset(e.increment, 0, sizeof(e.increment)); std::memset(e.X, 0, sizeof(e.X)); e.rcond = 0.f; e.status = -1; }
             c->loop_log.push_back(e);
         }
@@ -476,17 +515,23 @@ static int run_batch(symmicp_ctx *c, int want, float *diffs_before, int *n_done,
     c->last_list_len = tree ? (it1 > it0 ? (long long)c->h_ring[it1 % symmicp_ctx::kRing].list_len : c->last_list_len) : -1;
     *n_done = it1 - it0;
     *small_step = hl.reason == LOOP_DONE && hl.small_step != 0;
-    if (tree && it1 > it0) c->last_uncertified = c->h_ring[it1 % symmicp_ctx::kRing].pad;
+    if (tree && it1 > it0) { c->last_uncertified = c->h_ring[it1 % symmicp_ctx::kRing].pad; c->last_scans = c->h_ring[it1 % symmicp_ctx::kRing].reserved; }
+    int n_cert = 0;
+    for (int k = it0 + 1; k <= it1; k++) n_cert += pass_kernel[k % symmicp_ctx::kRing];
+    if (hl.reason == LOOP_REDO_PASS && pass_kernel[(it1 + 1) % symmicp_ctx::kRing]) c->cert_pass_failed = true;
     if (c->sw.debug_host && it1 - it0 >= 2) {      // (a library built with -DRS_STAMPS leaves k_reduce_solve's phase durations in the spare slots of each record)
         const double *q = c->h_ring[(it1 - 1) % symmicp_ctx::kRing].sums;
         if (q[37] != 0.0) std::fprintf(stderr, "[symmicp host] k_reduce_solve stamps of pass %d: load + reduce %.2f us (loop state there after %.2f us), bookkeeping + solve %.2f us, publish %.2f us\n", it1 - 1, std::floor(q[37]) * 0.01, (q[37] - std::floor(q[37])) * 1e4 * 0.01, q[38] * 0.01, q[39] * 0.01);
     }
     if (c->sw.debug_host && tree) {
-        std::fprintf(stderr, "[symmicp host] batch: work list / searched pairs after each device pass:");
-        for (int k = it0 + 1; k <= it1; k++) std::fprintf(stderr, " %d/%d", c->h_ring[k % symmicp_ctx::kRing].list_len, c->h_ring[k % symmicp_ctx::kRing].pad);
+        std::fprintf(stderr, "[symmicp host] batch: work list / searched pairs / scanned pairs after each device pass (c: certified-only kernel):");
+        for (int k = it0 + 1; k <= it1; k++) {
+            const LoopRecord &r = c->h_ring[k % symmicp_ctx::kRing];
+            std::fprintf(stderr, " %d/%d/%d%s", r.list_len, r.pad, r.reserved, pass_kernel[k % symmicp_ctx::kRing] ? "c" : "");
+        }
         std::fprintf(stderr, "\n");
     }
-    if (c->sw.debug_host) std::fprintf(stderr, "[symmicp host] batch: %d of %d passes on the device (%d enqueued), reason %d, %d with the straggler stage, list after %lld\n", it1 - it0, want, enq, hl.reason, n_stage, (long long)c->last_list_len);
+    if (c->sw.debug_host) std::fprintf(stderr, "[symmicp host] batch: %d of %d passes on the device (%d enqueued), reason %d, %d with the straggler stage, %d certified-only%s, list after %lld (host pass before: list %lld, scanned %lld)\n", it1 - it0, want, enq, hl.reason, n_stage, n_cert, c->cert_pass_failed ? " (now off: a pass came back incomplete)" : "", (long long)c->last_list_len, list0, scans0);
     if (hl.reason == LOOP_SLOW) c->host_passes_since_bailout = 1;      // one host pass, then look again
     if (hl.reason == LOOP_REDO_PASS || hl.reason == LOOP_HOST_SOLVE) {
         c->host_passes_since_bailout = 0;
@@ -637,6 +682,7 @@ int symmicp_align(symmicp_ctx *c, const float *guess16, symmicp_result *out)
     std::memset(out, 0, sizeof(*out));
     if (c->external_exchange) { out->status = SYMMICP_ERR_STATE; return fail(c, SYMMICP_ERR_STATE, "symmicp_align is not available with external exchange: drive begin/set_sums/step"); }
     const double t0 = now_s();
+    c->cert_pass_failed = false;
     c->loop_log.clear();
     c->loop_log_batches = 0;
     symmicp_iter_result it;

@@ -284,11 +284,12 @@ __device__ __forceinline__ float cert_word(float L, bool hood)
 // Neighbourhood test of pair i (its single certificate has failed or does not exist).  In: the query's position, delta^2 = m2 to the
 // reference, the current winner (sorted position, d2, row).  True: the nearest neighbour is provably a member of S; pos_w / d2w are
 // the winner's, and everything the change needs is stored (position, record copy, moved reference).
-__device__ __forceinline__ bool hood_test(const PassArgs &a, const TargetIndex &ix, uint32_t i, float px, float py, float pz, float m2,
-                                          int32_t pos_a, float d2a, int32_t rowa, int32_t &pos_w, float &d2w)
+// hood_test_set: the same with the pair's set (w0, w1 = certk[2 i], certk[2 i + 1]) and radius (T = hoodr[i].x) already loaded -- a caller
+// that requests them together with everything else addressed by i saves a round trip (k_pass_certified).
+__device__ __forceinline__ bool hood_test_set(const PassArgs &a, const TargetIndex &ix, uint32_t i, float px, float py, float pz, float m2,
+                                              int32_t pos_a, float d2a, int32_t rowa, const uint4 &w0, const uint4 &w1, const float T,
+                                              int32_t &pos_w, float &d2w)
 {
-    const uint4 w0 = a.certk[2 * (size_t)i], w1 = a.certk[2 * (size_t)i + 1];
-    const float T = a.hoodr[i].x;
     const uint32_t cand[kHoodSlots] = {w0.x, w0.y, w0.z, w0.w, w1.x, w1.y, w1.z, w1.w};
     float4 q[kHoodSlots];
 #pragma unroll
@@ -323,6 +324,14 @@ __device__ __forceinline__ bool hood_test(const PassArgs &a, const TargetIndex &
         a.cert[i].w = cert_word(0.0f, true);       // the moved radius would leave no room: reference and T stay, the old single certificate goes
     }
     return true;
+}
+
+__device__ __forceinline__ bool hood_test(const PassArgs &a, const TargetIndex &ix, uint32_t i, float px, float py, float pz, float m2,
+                                          int32_t pos_a, float d2a, int32_t rowa, int32_t &pos_w, float &d2w)
+{
+    const uint4 w0 = a.certk[2 * (size_t)i], w1 = a.certk[2 * (size_t)i + 1];
+    const float T = a.hoodr[i].x;
+    return hood_test_set(a, ix, i, px, py, pz, m2, pos_a, d2a, rowa, w0, w1, T, pos_w, d2w);
 }
 
 // One tile of 256 queries (i >= a.n: idle lane).  Called by k_search_cells (tile = block) and by k_pass_fused (the queries its
@@ -783,14 +792,14 @@ __global__ __launch_bounds__(kPassThreads, ACC ? FUSED_WAVES : COMPACT_WAVES) vo
     const bool need_n = reads_src_normals<OBJ>(false, a.min_ndot);      // (no write-back here)
     constexpr int kList = ACC ? kFusedList : kFusedList / 2;      // (the search-only form keeps 5 workgroups per CU: its tile is 256 points)
     __shared__ uint32_t s_list[kList];
-    __shared__ uint32_t s_cnt, s_total;
+    __shared__ uint32_t s_cnt, s_total, s_hood;      // (s_hood: listed pairs their neighbourhood settled)
     __shared__ unsigned long long s_col[ACC ? 10 : 1];      // base addresses of the streamed columns (read back at the top of every tile: see in_vgpr)
     // device-driven loop: stop flag and transform come from device memory, written by the kernel just before this one -- a cold round trip.
     // They are requested here and first LOOKED AT behind the first tile's loads (which do not depend on them): one round trip, not two
     // (behind the barrier: scalar loads and LDS stores share a counter, and the barrier waits for it)
     AccT<W> acc;
     if (ACC) acc_zero(acc);
-    if (threadIdx.x == 0) { s_cnt = 0; s_total = 0; }
+    if (threadIdx.x == 0) { s_cnt = 0; s_total = 0; s_hood = 0; }
     if (ACC && threadIdx.x == 0) {
         s_col[0] = (unsigned long long)a.in.x; s_col[1] = (unsigned long long)a.in.y; s_col[2] = (unsigned long long)a.in.z;
         s_col[3] = (unsigned long long)a.in.nx; s_col[4] = (unsigned long long)a.in.ny; s_col[5] = (unsigned long long)a.in.nz;
@@ -858,6 +867,7 @@ __global__ __launch_bounds__(kPassThreads, ACC ? FUSED_WAVES : COMPACT_WAVES) vo
                     if (need_n) { nx = a.in.nx[i]; ny = a.in.ny[i]; nz = a.in.nz[i]; }
                     pair_step<OBJ>(acc, h, nx, ny, nz, px, py, pz, qw, nqw, d2w);
                     s_list[e] = 0xFFFFFFFFu;                       // settled (an idle lane of the scan below)
+                    atomicAdd(&s_hood, 1u);
                 }
             }
             __syncthreads();
@@ -974,6 +984,9 @@ __global__ __launch_bounds__(kPassThreads, ACC ? FUSED_WAVES : COMPACT_WAVES) vo
     flush();
     // pairs that had to be searched (see cells_tile)
     if (threadIdx.x == 0 && s_total) atomicAdd(wl.work.counts + shard * kShardStride + 1, s_total);
+    // ... and those of them that never reached a scan (word 3): "searched" counts every listed pair, but what run_batch needs to know before
+    // it chooses k_pass_certified is whether any pair was really scanned, probed or walked: searched - settled
+    if (ACC && threadIdx.x == 0 && s_hood) atomicAdd(wl.work.counts + shard * kShardStride + 3, s_hood);
 #ifdef RS_STAMPS2
     const unsigned long long fs2 = __builtin_amdgcn_s_memrealtime();
 #endif
@@ -984,6 +997,119 @@ __global__ __launch_bounds__(kPassThreads, ACC ? FUSED_WAVES : COMPACT_WAVES) vo
         dbg[0] = (double)(fs1 - fs0); dbg[1] = (double)(fs2 - fs1); dbg[2] = (double)(__builtin_amdgcn_s_memrealtime() - fs2);
     }
 #endif
+}
+
+// ---------------------------------------------------------------------------
+// k_pass_certified: the pass of a converged alignment in which NO pair needs a scan -- k_accumulate's loop plus the certificate.  In
+// such a pass k_pass_fused carries its scan machinery for nothing (34 KB of LDS, ~240 registers, ~150 argument scalars live across
+// the loop, a barrier and a counter check per tile).  Here the loop has no barrier, no LDS traffic and no store:
+//   stream   the tiles in k_pass_fused<true>'s order; per point the single-certificate test (the expression of cells_tile, phase 1)
+//            and the pair step; a pair that fails goes to a small list in LDS
+//   settle   after the loop, once: the neighbourhood certificate of the listed pairs (hood_test, as the first stage of
+//            k_pass_fused's flush: record refresh when the winner changes, accumulation on success)
+// There is no scan.  Every pair that is still unsettled -- no neighbourhood, a stale record copy, no target, a failed test, a list
+// that overflowed -- makes the pass INCOMPLETE: the block adds their number to its shard's work-list count word (no entry is
+// appended), so k_reduce_solve stops the loop with LOOP_REDO_PASS and the host repeats the pass through the search kernels, as for
+// a work list that turns up without the straggler stage.  run_batch chooses this kernel for a chunk of passes after a complete pass
+// that scanned nothing, and never again in an alignment once a pass of it came back incomplete.
+// ---------------------------------------------------------------------------
+constexpr uint32_t kCertList = kPassThreads;      // (one settle round; a converged 1M-point pass lists under one pair per block)
+
+template <bool W, int OBJ>
+__global__ __launch_bounds__(kPassThreads) void k_pass_certified(PassArgs a, TargetIndex ix, WorkLists wl)
+{
+    const bool need_n = reads_src_normals<OBJ>(false, a.min_ndot);      // (no write-back here)
+    __shared__ uint32_t s_list[kCertList];
+    __shared__ uint32_t s_cnt, s_bad;
+    AccT<W> acc; acc_zero(acc);
+    if (threadIdx.x == 0) { s_cnt = 0; s_bad = 0; }
+    __syncthreads();
+    // stop flag and transform of a device-driven loop: requested here, looked at behind the first tile's loads (see k_pass_fused)
+    int stop = 0;
+    HotParams h = hot_params(a);
+    if (a.loop) {
+        stop = a.loop->stop;
+        const float4 *xp = reinterpret_cast<const float4 *>(&in_vgpr(a.loop)->Xapply);
+        const float4 r0 = xp[0], r1 = xp[1], r2 = xp[2];
+        h.X.m[0] = r0.x; h.X.m[1] = r0.y; h.X.m[2] = r0.z; h.X.m[3] = r0.w;
+        h.X.m[4] = r1.x; h.X.m[5] = r1.y; h.X.m[6] = r1.z; h.X.m[7] = r1.w;
+        h.X.m[8] = r2.x; h.X.m[9] = r2.y; h.X.m[10] = r2.z; h.X.m[11] = r2.w;
+        h.X.nrm_w = reinterpret_cast<const float *>(xp)[12];
+    }
+    const Affine &X = h.X;
+    const uint32_t tiles = (a.n + kPassThreads - 1) / kPassThreads;
+    const uint32_t tiles_p = ((tiles + 7u) / 8u) * 8u;
+    for (uint32_t t = blockIdx.x; t < tiles_p; t += gridDim.x) {
+        const uint32_t i = xcd_remap(t, tiles_p) * kPassThreads + threadIdx.x;
+        const bool live = i < a.n;
+        float x = 0.f, y = 0.f, z = 0.f, nx = 0.f, ny = 0.f, nz = 0.f;
+        float4 q = make_float4(0.f, 0.f, 0.f, 0.f), nq = make_float4(0.f, 0.f, 0.f, 2.0f), ce = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (live) {
+            x = a.in.x[i]; y = a.in.y[i]; z = a.in.z[i];
+            if (need_n) { nx = a.in.nx[i]; ny = a.in.ny[i]; nz = a.in.nz[i]; }
+            q = a.pairrec[2 * (size_t)i]; nq = a.pairrec[2 * (size_t)i + 1];
+            ce = a.cert[i];
+        }
+        if (stop) return;                 // (uniform; nothing has been written yet)
+        if (!live) continue;
+        const float px = xf_row(X.m + 0, x, y, z, 1.0f), py = xf_row(X.m + 4, x, y, z, 1.0f), pz = xf_row(X.m + 8, x, y, z, 1.0f);
+        bool certified = false;
+        float d2 = 0.0f;
+        if (nq.w == 0.0f) {
+            d2 = dist2(px, py, pz, q.x, q.y, q.z);
+            const float m2 = dist2(px, py, pz, ce.x, ce.y, ce.z);
+            certified = (__builtin_amdgcn_sqrtf(d2) + __builtin_amdgcn_sqrtf(m2)) * 1.000002f < ce.w;          // cells_tile, phase 1
+        }
+        if (certified) pair_step<OBJ>(acc, h, nx, ny, nz, px, py, pz, q, nq, d2);
+        else {
+            const uint32_t e = atomicAdd(&s_cnt, 1u);
+            if (e < kCertList) s_list[e] = i;
+        }
+    }
+    __syncthreads();
+    const uint32_t cnt = s_cnt;
+    if (cnt) {                            // (uniform)
+        const uint32_t m = min(cnt, kCertList);
+        if (threadIdx.x < m) {
+            const uint32_t i = s_list[threadIdx.x];
+            bool settled = false;
+            // one round trip for everything addressed by i (the set and its radius too, whether or not the test will run: the settle stage
+            // is a chain of dependent loads at the end of the slowest blocks), a second one for the set's members
+            const float4 ce = a.cert[i];
+            const float4 q = a.pairrec[2 * (size_t)i], nq = a.pairrec[2 * (size_t)i + 1];
+            const int32_t pk = a.pos_prev[i];
+            const float x = a.in.x[i], y = a.in.y[i], z = a.in.z[i];
+            float nx = 0.0f, ny = 0.0f, nz = 0.0f;
+            if (need_n) { nx = a.in.nx[i]; ny = a.in.ny[i]; nz = a.in.nz[i]; }
+            uint4 w0 = make_uint4(kHoodNone, kHoodNone, kHoodNone, kHoodNone), w1 = w0;
+            float T = 0.0f;
+            if (a.certk) { w0 = a.certk[2 * (size_t)i]; w1 = a.certk[2 * (size_t)i + 1]; T = a.hoodr[i].x; }
+            if (a.certk && (__float_as_uint(ce.w) & 1u)) {
+                if (nq.w == 0.0f && (uint32_t)pk < ix.n) {
+                    const float px = xf_row(X.m + 0, x, y, z, 1.0f), py = xf_row(X.m + 4, x, y, z, 1.0f), pz = xf_row(X.m + 8, x, y, z, 1.0f);
+                    const float d2 = dist2(px, py, pz, q.x, q.y, q.z);
+                    int32_t pw; float d2w;
+                    if (d2 <= __int_as_float(0x7f800000) &&
+                        hood_test_set(a, ix, i, px, py, pz, dist2(px, py, pz, ce.x, ce.y, ce.z), pk, d2, __float_as_int(q.w), w0, w1, T, pw, d2w)) {
+                        float4 qw = q, nqw = nq;
+                        if (pw != pk) { qw = ix.tn[2 * (size_t)pw]; nqw = ix.tn[2 * (size_t)pw + 1]; }
+                        pair_step<OBJ>(acc, h, nx, ny, nz, px, py, pz, qw, nqw, d2w);
+                        settled = true;
+                    }
+                }
+            }
+            if (!settled) atomicAdd(&s_bad, 1u);
+        }
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            const uint32_t shard = blockIdx.x & (kShards - 1);
+            const uint32_t bad = s_bad + (cnt - m);
+            if (bad) atomicAdd(wl.work.counts + shard * kShardStride, bad);       // the pass is incomplete (no entry: nothing walks this "list")
+            atomicAdd(wl.work.counts + shard * kShardStride + 1, cnt);            // pairs searched, as k_pass_fused counts them
+            atomicAdd(wl.work.counts + shard * kShardStride + 3, cnt - bad);      // ... and those their neighbourhood settled
+        }
+    }
+    acc_block_reduce_store(acc, a.partials, blockIdx.x);
 }
 
 // ---------------------------------------------------------------------------
@@ -1232,6 +1358,7 @@ __global__ __launch_bounds__(kPassThreads) void k_accumulate(PassArgs a, const f
 //   word 0 of shard t   entries in shard t of the work list          -> len      (summed over the shards)
 //   word 1 of shard t   pairs searched this pass, counted per shard  -> searched
 //   word 2 of a list    appends dropped because a shard was full     -> dropped  (work + retry list; must be 0)
+//   word 3 of shard t   searched pairs their neighbourhood settled   -> scans = searched - that: the pairs that reached a scan, a probe or the walk
 // Results are valid in every lane.
 // Straggler stage of a device-driven loop (after k_pass_fused and k_search_walk): the pairs of the work list's queries -- the fused pass
 // left them out and marked their record copies stale -- are gathered, their copies refreshed, their rows summed into `gridDim.x` partial
@@ -1268,17 +1395,18 @@ __global__ __launch_bounds__(kPassThreads) void k_accumulate_list(PassArgs a, co
     acc_block_reduce_store(acc, a.partials, a.partial_col0 + blockIdx.x);
 }
 
-__device__ __forceinline__ void read_list_words(const uint32_t *cnt, int t, uint32_t &len, uint32_t &searched, uint32_t &dropped)
+__device__ __forceinline__ void read_list_words(const uint32_t *cnt, int t, uint32_t &len, uint32_t &searched, uint32_t &dropped, uint32_t &scans)
 {
-    uint32_t v = cnt[t * kShardStride], u = cnt[t * kShardStride + 1];
+    uint32_t v = cnt[t * kShardStride], u = cnt[t * kShardStride + 1], sc = cnt[t * kShardStride + 3];
     uint32_t d = (t < 2) ? cnt[t * kShards * kShardStride + 2] : 0u;
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) {
         v += (uint32_t)__shfl_xor((int)v, off, 64);
         u += (uint32_t)__shfl_xor((int)u, off, 64);
         d += (uint32_t)__shfl_xor((int)d, off, 64);
+        sc += (uint32_t)__shfl_xor((int)sc, off, 64);
     }
-    len = v; searched = u; dropped = d;
+    len = v; searched = u; dropped = d; scans = u > sc ? u - sc : 0u;
 }
 
 // ---------------------------------------------------------------------------
@@ -1318,20 +1446,21 @@ __global__ __launch_bounds__(256) void k_final_reduce(const double *__restrict__
         if (counters_to_clear) {
             __shared__ uint32_t s_len;
             if (t < 64) {
-                uint32_t len, searched, dropped;
-                read_list_words(counters_to_clear, t, len, searched, dropped);
+                uint32_t len, searched, dropped, scans;
+                read_list_words(counters_to_clear, t, len, searched, dropped, scans);
                 if (t == 0) {
                     s_len = len;
                     // the record's spare slots: list length (+ kListDropped if appends were dropped -- sl_push: must not happen), pairs
-                    // searched this pass (cells_tile).  (Slot 37 is a sum: the pair count of a weighted record.)
-                    const double lenw = (double)len + (dropped ? kListDropped : 0.0);
-                    out_dev[kNSum - 1] = lenw; out_dev[kNSum - 2] = (double)searched;
-                    if (out_mapped) { out_mapped[kNSum - 1] = lenw; out_mapped[kNSum - 2] = (double)searched; }
+                    // searched this pass (cells_tile) with, above its 32 bits, those of them that reached a scan (kScanUnit: both counts
+                    // stay exact in the sum over ranks).  (Slot 37 is a sum: the pair count of a weighted record.)
+                    const double lenw = (double)len + (dropped ? kListDropped : 0.0), srw = (double)searched + (double)scans * kScanUnit;
+                    out_dev[kNSum - 1] = lenw; out_dev[kNSum - 2] = srw;
+                    if (out_mapped) { out_mapped[kNSum - 1] = lenw; out_mapped[kNSum - 2] = srw; }
                 }
             }
             __syncthreads();
             if (t < 2) counters_to_clear[t * kShards * kShardStride + 2] = 0;
-            if (t < kShards) counters_to_clear[t * kShardStride + 1] = 0;
+            if (t < kShards) { counters_to_clear[t * kShardStride + 1] = 0; counters_to_clear[t * kShardStride + 3] = 0; }
             if (!(keep_nonempty && s_len > 0u))
                 for (int c = t; c < 2 * kShards; c += 256) counters_to_clear[c * kShardStride] = 0;      // work list and retry list
         }
@@ -1365,7 +1494,7 @@ __global__ __launch_bounds__(512) void k_reduce_solve(const double *__restrict__
                                                        LoopConfig cfg, LoopRecord *ring, int ring_len, uint32_t *counters_to_clear)
 {
     __shared__ double s_sum[kNSum];
-    __shared__ uint32_t s_len, s_unc;
+    __shared__ uint32_t s_len, s_unc, s_scan;
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
 #ifdef RS_STAMPS
     const unsigned long long ts0 = __builtin_amdgcn_s_memrealtime();
@@ -1373,11 +1502,12 @@ __global__ __launch_bounds__(512) void k_reduce_solve(const double *__restrict__
     // This block is one chain of dependent steps behind a kernel boundary: everything it reads from memory is requested up front, in one
     // round trip (the loop state, the work list's counters, the partial records), instead of one round trip per step (12 -> ~9 us).
     const LoopState ls = *loop;                       // (wave-uniform: scalar loads)
-    uint32_t cw0 = 0, cw1 = 0, cw2 = 0;               // wave 0: the shard counters (see read_list_words)
+    uint32_t cw0 = 0, cw1 = 0, cw2 = 0, cw3 = 0;      // wave 0: the shard counters (see read_list_words)
     const bool want_counters = !solve_only && REDUCE && counters_to_clear && t < 64;
     if (want_counters) {
         cw0 = counters_to_clear[t * kShardStride]; cw1 = counters_to_clear[t * kShardStride + 1];
         cw2 = (t < 2) ? counters_to_clear[t * kShards * kShardStride + 2] : 0u;
+        cw3 = counters_to_clear[t * kShardStride + 3];
     }
     // lane k < 40 of wave w sums slot k of the records of blocks w, w + 8, w + 16, ...: every load is one contiguous 320-byte record,
     // nothing has to cross lanes, the order is fixed.  All loads of a thread are issued before its first sum.
@@ -1400,7 +1530,7 @@ __global__ __launch_bounds__(512) void k_reduce_solve(const double *__restrict__
 #ifdef RS_STAMPS
     const unsigned long long tsA = __builtin_amdgcn_s_memrealtime();
 #endif
-    if (t == 0) { s_len = 0; s_unc = 0; }
+    if (t == 0) { s_len = 0; s_unc = 0; s_scan = 0; }
     if (!solve_only && REDUCE) {
         if (lane < kNSum) s_part[wave][lane] = accw;
         __syncthreads();
@@ -1420,15 +1550,17 @@ __global__ __launch_bounds__(512) void k_reduce_solve(const double *__restrict__
                     cw0 += (uint32_t)__shfl_xor((int)cw0, off, 64);
                     cw1 += (uint32_t)__shfl_xor((int)cw1, off, 64);
                     cw2 += (uint32_t)__shfl_xor((int)cw2, off, 64);
+                    cw3 += (uint32_t)__shfl_xor((int)cw3, off, 64);
                 }
-                if (t == 0) { s_len = cw2 ? 0xFFFFFFFFu : cw0; s_unc = cw1; }      // dropped appends: the host redoes the pass and reports
+                if (t == 0) { s_len = cw2 ? 0xFFFFFFFFu : cw0; s_unc = cw1; s_scan = cw1 > cw3 ? cw1 - cw3 : 0u; }      // dropped appends: the host redoes the pass and reports
             }
-            if (t < kShards) counters_to_clear[t * kShardStride + 1] = 0;
+            if (t < kShards) { counters_to_clear[t * kShardStride + 1] = 0; counters_to_clear[t * kShardStride + 3] = 0; }
             for (int c = t; c < 2 * kShards; c += 512) counters_to_clear[c * kShardStride] = 0;
         } else if (t == 0) {
             // summed over the ranks by the all-reduce (k_final_reduce put them in the record)
             s_len = (s_sum[kNSum - 1] >= kListDropped) ? 0xFFFFFFFFu : (uint32_t)s_sum[kNSum - 1];
-            s_unc = (uint32_t)s_sum[kNSum - 2];
+            const double sr = s_sum[kNSum - 2], sc = floor(sr / kScanUnit);
+            s_unc = (uint32_t)(sr - sc * kScanUnit); s_scan = (uint32_t)sc;
         }
     }
     __syncthreads();
@@ -1438,7 +1570,7 @@ __global__ __launch_bounds__(512) void k_reduce_solve(const double *__restrict__
     // (every thread takes the same decisions from the same words; the record is written by 40 lanes at once, not by one lane 40 times)
     int it = ls.iters;
     if (!solve_only) {
-        const uint32_t len = s_len, unc = s_unc;
+        const uint32_t len = s_len, unc = s_unc, scans = s_scan;
         // a non-empty work list: handled by the straggler stage of this very pass, or the pass has to be redone by the host; dropped
         // appends (0xFFFFFFFF) always go back
         if (cfg.tree && len > 0u && (!cfg.walk_in_loop || len == 0xFFFFFFFFu)) { if (t == 0) { loop->stop = 1; loop->reason = LOOP_REDO_PASS; } return; }
@@ -1449,7 +1581,7 @@ __global__ __launch_bounds__(512) void k_reduce_solve(const double *__restrict__
             loop->iters = it;
             r.solved = 0;
             r.pad = (int32_t)unc;
-            r.list_len = (int32_t)len; r.reserved = 0;
+            r.list_len = (int32_t)len; r.reserved = (int32_t)scans;
         }
         // many pairs had to be searched again (the cloud moved): the separate kernels do that faster; this pass is complete
         if (cfg.tree && (unc > cfg.uncertified_limit || (cfg.walk_in_loop && len > cfg.list_limit))) { if (t == 0) { loop->stop = 1; loop->reason = LOOP_SLOW; } return; }
@@ -1773,6 +1905,11 @@ void launch_final_reduce(const double *partials, int blocks, double *out_dev, do
 void launch_pass_fused(const PassArgs &a, const TargetIndex &ix, const WorkLists &wl, int blocks, hipStream_t s)
 {
     with_instantiation(a, [&](auto W, auto OBJ) { hipLaunchKernelGGL((k_pass_fused<true, W, OBJ>), dim3(blocks), dim3(kPassThreads), 0, s, a, ix, wl); });
+}
+
+void launch_pass_certified(const PassArgs &a, const TargetIndex &ix, const WorkLists &wl, int blocks, hipStream_t s)
+{
+    with_instantiation(a, [&](auto W, auto OBJ) { hipLaunchKernelGGL((k_pass_certified<W, OBJ>), dim3(blocks), dim3(kPassThreads), 0, s, a, ix, wl); });
 }
 
 void launch_loop_stragglers(const PassArgs &a, const TargetIndex &ix, const WorkLists &wl, int list_blocks, const PassTuning &tune, hipStream_t s)

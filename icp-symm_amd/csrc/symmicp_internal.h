@@ -14,6 +14,8 @@ constexpr int kNAccW = 38;            // ... of the weighted passes (robust loss
 // TREE passes: the final reduce leaves the work list's length in slot 39 (and the pairs searched in 38); appends dropped for lack of
 // room (must not happen) add this to the length, so that it survives the sum over ranks
 constexpr double kListDropped = 4294967296.0;
+// ... and slot 38 carries two counts: the pairs searched (below 2^32) + kScanUnit x those of them that reached a scan
+constexpr double kScanUnit = 4294967296.0;
 constexpr int kLeaf = 8;              // target points per leaf (8 x 16 B = one 128-B line)
 constexpr int kFan = 8;               // children per tree node
 constexpr int kMaxTreeLevels = 12;
@@ -135,7 +137,7 @@ struct LoopRecord {          // one per pass, host-mapped
     int32_t status;                  // status of that solve
     int32_t solved;                  // 1: increment / X are valid (the loop went on)
     int32_t pad;                     // (pairs searched in this pass)
-    int32_t list_len, reserved;      // work-list length of this pass (queries handed to the tree walk)
+    int32_t list_len, reserved;      // work-list length of this pass (queries handed to the tree walk); reserved: pairs that reached a scan
 };
 
 // ---- pair rejection (kernels_select.hip): trim fraction, one-to-one, median distance, reciprocal ----
@@ -276,6 +278,8 @@ void launch_final_reduce(const double *partials, int blocks, double *out_dev, do
                          unsigned long long seq, uint32_t *counters_to_clear, int keep_nonempty, hipStream_t s);
 // fused pass of a converged alignment (k_pass_fused) and the device-side end of a pass (k_reduce_solve): see kernels_pass.hip
 void launch_pass_fused(const PassArgs &a, const TargetIndex &ix, const WorkLists &wl, int blocks, hipStream_t s);
+// ... the same pass for a chunk in which no pair needs a scan (k_pass_certified): an unsettled pair makes the pass incomplete (LOOP_REDO_PASS)
+void launch_pass_certified(const PassArgs &a, const TargetIndex &ix, const WorkLists &wl, int blocks, hipStream_t s);
 // device-driven loop, straggler stage behind a fused pass: the work list through the tree walk, then its pairs into `list_blocks` more partial columns
 void launch_loop_stragglers(const PassArgs &a, const TargetIndex &ix, const WorkLists &wl, int list_blocks, const PassTuning &tune, hipStream_t s);
 // mode 0: reduce + check + solve (single GPU); 1: the record is already in out_dev (after the all-reduce); 2: solve only (start of a batch)

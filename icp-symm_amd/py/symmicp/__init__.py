@@ -1374,7 +1374,10 @@ class Engine:
         for e in buf[:n.value]:
             out.append(dict(sums=np.array(e.sums[:], np.float64), increment=np.array(e.increment[:], np.float32).reshape(4, 4),
                             X=np.array(e.X[:], np.float32).reshape(4, 4), rcond=e.rcond, iter=e.iter, status=e.status, solved=e.solved,
-                            list_len=e.list_len, reason=e.reason, batch=e.batch))
+                            list_len=e.list_len, reason=e.reason, batch=e.batch,
+                            # the pass's kernel (0: fused, 1: certified-only); on a batch's last entry: the pass behind it ran
+                            # certified-only and was handed back to the host incomplete
+                            kernel=e.reserved & 0xff, redo_certified=bool(e.reserved & 0x100)))
         return out
 
 

@@ -413,7 +413,8 @@ typedef struct {
     int32_t list_len;    /* TREE: work-list length of this pass */
     int32_t reason;      /* stop reason of the batch this pass belongs to (LOOP_* as above; 4: slow, 2: redo pass) */
     int32_t batch;       /* 0, 1, ...: batches of this align */
-    int32_t reserved;
+    int32_t reserved;    /* TREE: the kernel that ran this pass: 0 fused, 1 certified-only (SYMMICP_CERT_PASS); + 0x100 on a batch's last
+                          * entry when the pass behind it ran certified-only and was handed back to the host incomplete */
 } symmicp_loop_log_entry;
 /* on != 0: every later symmicp_align keeps the log of its device-driven passes (off by default: nothing is copied) */
 int symmicp_set_loop_log(symmicp_ctx *ctx, int on);
