@@ -33,6 +33,9 @@
 //     --init-keypoints iss     match and run RANSAC on the ISS keypoints of both clouds only (features still come from the full clouds)
 //     --iss-radius R           their salient radius (required with --init-keypoints iss; some 6 point spacings)
 //     --iss-nms-radius R2      their non-maximum radius (default: two thirds of R)   --iss-min-neighbors K   (default 5)
+//     --evaluate D             after the result block, one line with the result's fitness, inlier RMSE and inliers / source points at
+//                              distance D (> 0) on the full clouds: the share of source points with a target point within D
+//     --information            with --evaluate: also the six rows of the 6x6 information matrix (rotation first, about the origin)
 //     --out aligned.pcd        write the source moved by the result (the reference only prints its result)
 //     --quiet                  no per-iteration lines
 //   Without file names it registers cat.pcd to cat_out.pcd from the working directory: the reference's own run.
@@ -52,7 +55,7 @@
 static int usage(const char *argv0, const char *complaint)
 {
     std::fprintf(stderr, "%s\nusage: %s [--mode quirks|paper|plane|gicp|color] [--color-weight L] [--corr identity|tree] [--iters N] [--threshold D] [--loss none|huber|tukey|cauchy|gm]"
-                 " [--loss-scale S] [--gicp-epsilon E] [--max-dist D] [--trim F] [--one-to-one] [--reciprocal] [--median-factor F] [--scale LEAF:ITERS[:MAXDIST]]... [--init global --fpfh-radius R --ransac-dist D [--ransac-iters H] [--seed S] [--init-voxel L] [--init-keypoints iss --iss-radius R [--iss-nms-radius R2] [--iss-min-neighbors K]]] [--out file.pcd] [--quiet] [source.pcd target.pcd]\n",
+                 " [--loss-scale S] [--gicp-epsilon E] [--max-dist D] [--trim F] [--one-to-one] [--reciprocal] [--median-factor F] [--scale LEAF:ITERS[:MAXDIST]]... [--init global --fpfh-radius R --ransac-dist D [--ransac-iters H] [--seed S] [--init-voxel L] [--init-keypoints iss --iss-radius R [--iss-nms-radius R2] [--iss-min-neighbors K]]] [--evaluate D [--information]] [--out file.pcd] [--quiet] [source.pcd target.pcd]\n",
                  complaint, argv0);
     return 64;
 }
@@ -77,6 +80,8 @@ int main(int argc, char **argv)
     std::vector<MyICP::VoxelLevel> levels;
     bool init_global = false, have_init_option = false, have_iss_option = false;
     MyICP::GlobalInit ginit;
+    bool evaluate = false, information = false;
+    float eval_dist = 0.f;
     auto number = [&](const char *what, const char *v, float &out) {
         char *end = nullptr;
         out = std::strtof(v, &end);
@@ -199,6 +204,12 @@ int main(int argc, char **argv)
         else if (a == "--iss-nms-radius") { number("--iss-nms-radius", value("--iss-nms-radius"), ginit.iss_non_max_radius); have_iss_option = true; }
         else if (a == "--iss-min-neighbors") { ginit.iss_min_neighbors = std::atoi(value("--iss-min-neighbors")); have_iss_option = true; }
         else if (a == "--seed") { ginit.seed = std::strtoull(value("--seed"), nullptr, 10); have_init_option = true; }
+        else if (a == "--evaluate") {
+            number("--evaluate", value("--evaluate"), eval_dist);
+            if (!(eval_dist > 0.f)) return usage(argv[0], "--evaluate needs a distance D > 0");
+            evaluate = true;
+        }
+        else if (a == "--information") information = true;
         else if (a == "--out") out_path = value("--out");
         else if (a == "--quiet") icp.setVerbose(false);
         else if (!a.empty() && a[0] == '-') return usage(argv[0], ("unknown option " + a).c_str());
@@ -248,6 +259,7 @@ int main(int argc, char **argv)
         }
         icp.setGlobalInit(ginit);
     } else if (have_init_option || have_iss_option) return usage(argv[0], "--fpfh-radius, --ransac-dist, --ransac-iters, --seed, --init-voxel and --init-keypoints need --init global");
+    if (information && !evaluate) return usage(argv[0], "--information needs --evaluate D");
     if (have_eps) {
         if (!gicp) return usage(argv[0], "--gicp-epsilon needs --mode gicp");
         icp.setGicpEpsilon(gicp_eps);
@@ -265,6 +277,21 @@ int main(int argc, char **argv)
     icp.RegisterSymm();
     const symmicp_result &r = icp.lastResult();
     if (r.status != SYMMICP_OK) return r.status;          // (RegisterSymm has printed lastError(): a failed initialisation among them)
+
+    if (evaluate) {
+        symmicp_evaluation e;
+        const int st = icp.evaluate(eval_dist, &e);
+        if (st != SYMMICP_OK) { std::fprintf(stderr, "%s\n", icp.lastError()); return st; }
+        std::printf("Evaluation at %g: fitness %.6f  inlier rmse %.6g  inliers %llu / %zu\n", (double)eval_dist, e.fitness, e.rmse,
+                    (unsigned long long)e.inliers, icp.GetSrcCloud()->points.size());
+        if (information) {
+            std::printf("  information:\n");
+            for (int r6 = 0; r6 < 6; r6++) {
+                for (int c6 = 0; c6 < 6; c6++) std::printf("%s%.9g", c6 ? " " : "", e.information[6 * r6 + c6]);
+                std::printf("\n");
+            }
+        }
+    }
 
     if (!out_path.empty()) {
         pcl::PointCloud<PointT>::Ptr moved = icp.GetAlignedSrcCloud();

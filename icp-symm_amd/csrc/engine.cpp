@@ -570,7 +570,7 @@ static float ord2f(uint32_t o)
 }
 
 // Morton order of a planar cloud: fills order[n] (sorted position -> row) and, optionally, keeps the sorted keys.
-static int morton_order(symmicp_ctx *c, const CloudSoA &cl, uint32_t n, DevBuf<uint32_t> &vals, DevBuf<uint32_t> *keys_out,
+extern "C++" int morton_order(symmicp_ctx *c, const CloudSoA &cl, uint32_t n, DevBuf<uint32_t> &vals, DevBuf<uint32_t> *keys_out,
                         float origin[3], float *h0_out)
 {
     DevBuf<uint32_t> bbox, keys_local, kt, vt, ws;

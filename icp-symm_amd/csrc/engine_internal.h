@@ -6,6 +6,7 @@
 //   engine_global.cpp    feature matching and RANSAC (symmicp_ctx_feature_nn, symmicp_ctx_feature_correspondences, symmicp_ctx_ransac)
 //   engine_debug.cpp     SYMMICP_DEBUG_COUNTERS / SYMMICP_DEBUG_TRACE dumps
 //   engine_probe.cpp     test entries: read-back of the target index and the source share, the sort and the scan on caller arrays
+//   engine_eval.cpp      registration evaluation (symmicp_evaluate_registration, symmicp_evaluate, symmicp_information_from_sums)
 #pragma once
 #include <hip/hip_runtime.h>
 #include <dlfcn.h>
@@ -19,6 +20,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <limits>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -373,6 +375,9 @@ void flush_events(symmicp_ctx *c);
 // [n]; null: the row).  Rewinds the context's scratch arena.  release: back to the state before the first build (the storage is freed).
 int build_reverse_index(symmicp_ctx *c, const CloudSoA &cl, uint32_t n, const uint32_t *labels, ReverseIndex &ri);
 void drop_reverse_index(ReverseIndex &ri, bool release);
+// Morton order of a planar cloud, temporaries and result from the context's scratch arena: vals[n] = sorted position -> row (keys_out:
+// null, or it keeps the sorted keys); origin / h0_out: the Morton frame.  SYMMICP_ERR_ARG for non-finite coordinates.
+int morton_order(symmicp_ctx *c, const CloudSoA &cl, uint32_t n, DevBuf<uint32_t> &vals, DevBuf<uint32_t> *keys_out, float origin[3], float *h0_out);
 // engine_exchange.cpp
 void shm_close(symmicp_ctx *c);
 int shm_exchange(symmicp_ctx *c, double *rec);      // rec[40]: this rank's record in, the sum over ranks out

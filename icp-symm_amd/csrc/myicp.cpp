@@ -281,6 +281,50 @@ int MyICP::alignMultiStart(const float *guesses4x4, size_t n_guesses, float out4
 	return st;
 }
 
+// Registration evaluation on the full clouds as the object holds them (pcl::PointXYZ rows of 4 floats), K transforms in one call
+static int evaluate_clouds(symmicp_ctx *ctx, const pcl::PointCloud<PointT> &src, const pcl::PointCloud<PointT> &tgt, const float *X16, size_t K,
+                           float max_dist, symmicp_evaluation *out)
+{
+	const size_t stride = sizeof(PointT) / sizeof(float);
+	return symmicp_ctx_evaluate_registration(ctx, src.points.empty() ? nullptr : &src.points[0].x, stride, 1, src.points.size(),
+	                                         tgt.points.empty() ? nullptr : &tgt.points[0].x, stride, 1, tgt.points.size(), X16, K, max_dist, out,
+	                                         nullptr, nullptr);
+}
+
+int MyICP::evaluate(float max_dist, symmicp_evaluation *out, const float *transform4x4)
+{
+	assert(cloud_src && cloud_tgt);
+	symmicp_ctx *ctx = context();
+	if (!ctx) { error_ = "symmicp_create failed: no usable gfx950 HIP device (there is no CPU fallback)"; return SYMMICP_ERR_HIP; }
+	const int st = evaluate_clouds(ctx, *cloud_src, *cloud_tgt, transform4x4 ? transform4x4 : transform_, 1, max_dist, out);
+	if (st != SYMMICP_OK) error_ = symmicp_last_error(ctx);
+	return st;
+}
+
+double MyICP::getFitnessScore(double max_range)
+{
+	// (a range that fp32 cannot hold is no limit)
+	const float d = max_range >= (double)std::numeric_limits<float>::max() ? 0.f : (float)max_range;
+	symmicp_evaluation e;
+	if (evaluate(d, &e) != SYMMICP_OK || e.inliers == 0) return std::numeric_limits<double>::max();
+	return e.mean_d2;
+}
+
+int MyICP::evaluateStarts(float max_dist, std::vector<symmicp_evaluation> &out)
+{
+	assert(cloud_src && cloud_tgt);
+	out.clear();
+	if (multi_results_.empty()) { error_ = "evaluateStarts: alignMultiStart comes first"; return SYMMICP_ERR_STATE; }
+	symmicp_ctx *ctx = context();
+	if (!ctx) { error_ = "symmicp_create failed: no usable gfx950 HIP device (there is no CPU fallback)"; return SYMMICP_ERR_HIP; }
+	std::vector<float> X(16 * multi_results_.size());
+	for (size_t k = 0; k < multi_results_.size(); k++) std::memcpy(&X[16 * k], multi_results_[k].transform, sizeof(float) * 16);
+	out.resize(multi_results_.size());
+	const int st = evaluate_clouds(ctx, *cloud_src, *cloud_tgt, X.data(), multi_results_.size(), max_dist, out.data());
+	if (st != SYMMICP_OK) { error_ = symmicp_last_error(ctx); out.clear(); }
+	return st;
+}
+
 // SYMMICP_MODE_COLOR: the target's intensity gradient on its tangent planes (k = 10, the normals align() uses), then both attributes
 int MyICP::setColorAttributes(symmicp_ctx *ctx)
 {

@@ -399,4 +399,30 @@ void launch_ransac_eval(const float *pq8, uint32_t m, const float *hyp, const ui
                         float max_dist2, int32_t *inliers, hipStream_t s);
 void launch_ransac_argmax(const uint8_t *status, const int32_t *inliers, uint32_t H, unsigned long long *best, hipStream_t s);
 
+// registration evaluation (kernels_eval.hip; symmicp_ctx_evaluate_registration, symmicp_evaluate): K transforms of one source against one
+// indexed target whose tq carries the caller's row in w.  The search runs over source positions (order: position -> caller row, null: the
+// position; gather: the coordinates are stored by caller row and read through order), the sums over caller rows in an order that is a
+// function of ns alone.  nn / d2 [K][ns] by caller row; partials [K][eval_sum_blocks(ns)][kEvalNSum]; sums [K][kEvalNSum] =
+// inliers, sum d2, sum q (3), upper triangle of sum q q^T (6).
+constexpr int kEvalThreads = 256;
+constexpr int kEvalSearchThreads = 64;        // workgroup of k_eval_search: one wave (256: 5 % slower at K = 64; tiles dealt out strided: 25 - 45 % slower)
+constexpr uint32_t kEvalRows = 1024;          // caller rows per block and trip of k_eval_sums
+constexpr uint32_t kEvalMaxBlocks = 4096;     // ... and the most blocks per transform
+constexpr int kEvalNSum = 11;
+struct EvalArgs {
+    TargetIndex ix;
+    const float *sx, *sy, *sz;                // source coordinates, planar
+    const uint32_t *order;
+    int32_t gather;
+    uint32_t ns;
+    const float *X12;                         // [K][12]: the three top rows of every transform
+    float r2;                                 // max_dist^2 in fp32, +Inf without a gate
+    const float *tx, *ty, *tz;                // target coordinates by caller row, planar
+    int32_t *nn;
+    float *d2;
+    double *partials;
+};
+uint32_t eval_sum_blocks(uint32_t ns);
+void launch_eval(const EvalArgs &a, uint32_t K, double *sums, hipStream_t s);
+
 }  // namespace symmicp

@@ -114,6 +114,15 @@ class BatchResult(C.Structure):
 BATCH_MAX_POINTS = 4096      # SYMMICP_BATCH_MAX_POINTS
 
 
+class Evaluation(C.Structure):
+    """symmicp_evaluation: fitness, inlier RMSE, the inlier sums and the 6x6 information matrix of one transform"""
+    _fields_ = [("inliers", C.c_uint64), ("fitness", C.c_double), ("rmse", C.c_double), ("mean_d2", C.c_double), ("sum_d2", C.c_double),
+                ("sum_q", C.c_double * 3), ("sum_qq", C.c_double * 6), ("information", C.c_double * 36)]
+
+
+EVAL_MAX_TRANSFORMS = 4096
+
+
 class IndexInfo(C.Structure):
     """symmicp_index_info: what symmicp_ctx_index_info reads back of a target index (tests)"""
     _fields_ = [("struct_size", C.c_int32), ("n", C.c_uint32), ("grid_level", C.c_int32), ("gdim", C.c_int32), ("origin", C.c_float * 3),
@@ -150,6 +159,7 @@ EXPORTS = [
     "symmicp_get_source_intensity", "symmicp_intensity_gradient", "symmicp_ctx_intensity_gradient", "symmicp_pcd_read_intensity",
     "symmicp_iss_config_default", "symmicp_iss_keypoints", "symmicp_ctx_iss_keypoints",
     "symmicp_batch_config_default", "symmicp_batch_align", "symmicp_ctx_batch_align",
+    "symmicp_information_from_sums", "symmicp_evaluate_registration", "symmicp_ctx_evaluate_registration", "symmicp_evaluate",
 ]
 
 _lib = None
@@ -294,6 +304,12 @@ def lib():
     L.symmicp_batch_config_default.restype = None
     L.symmicp_batch_align.argtypes = [C.c_int] + bat
     L.symmicp_ctx_batch_align.argtypes = [vp] + bat
+    dp, evp = C.POINTER(C.c_double), C.POINTER(Evaluation)
+    L.symmicp_information_from_sums.argtypes = [C.c_uint64, dp, dp, dp]
+    evl = [fp, C.c_size_t, C.c_size_t, C.c_size_t, fp, C.c_size_t, C.c_size_t, C.c_size_t, fp, C.c_size_t, C.c_float, evp, i32p, fp]
+    L.symmicp_evaluate_registration.argtypes = [C.c_int] + evl
+    L.symmicp_ctx_evaluate_registration.argtypes = [vp] + evl
+    L.symmicp_evaluate.argtypes = [vp, fp, C.c_size_t, C.c_float, evp, i32p, fp]
     _lib = L
     return L
 
@@ -792,6 +808,75 @@ def batch_align(src, src_n, tgt, tgt_n, problems, guesses=None, trace=False, dev
     return r
 
 
+def information_from_sums(n, sum_q, sum_qq):
+    """the [6, 6] float64 information matrix (rotation first) of n inliers with sum q = sum_q [3] and the upper triangle of sum q q^T =
+    sum_qq [6] (xx, xy, xz, yy, yz, zz): symmicp_information_from_sums, a pure host function"""
+    q = np.ascontiguousarray(sum_q, np.float64).reshape(3)
+    qq = np.ascontiguousarray(sum_qq, np.float64).reshape(6)
+    out = np.zeros(36, np.float64)
+    dp = C.POINTER(C.c_double)
+    st = lib().symmicp_information_from_sums(int(n), q.ctypes.data_as(dp), qq.ctypes.data_as(dp), out.ctypes.data_as(dp))
+    if st != OK:
+        raise SymmIcpError(st, "information_from_sums")
+    return out.reshape(6, 6)
+
+
+def _transforms(transforms):
+    """None, one [4, 4] or [K, 4, 4] -> (contiguous [K, 16] float32 or None, K, single)"""
+    if transforms is None:
+        return None, 1, True
+    X = np.ascontiguousarray(transforms, np.float32)
+    single = X.ndim == 2
+    X = X.reshape(-1, 16)
+    return X, len(X), single
+
+
+def _eval_dicts(out, K, nn, d2):
+    res = []
+    for k in range(K):
+        e = out[k]
+        r = dict(inliers=int(e.inliers), fitness=e.fitness, rmse=e.rmse, mean_d2=e.mean_d2, sum_d2=e.sum_d2,
+                 sum_q=np.array(e.sum_q[:], np.float64), sum_qq=np.array(e.sum_qq[:], np.float64),
+                 information=np.array(e.information[:], np.float64).reshape(6, 6), raw=bytes(e))
+        if nn is not None:
+            r.update(nn=nn[k], d2=d2[k])
+        res.append(r)
+    return res
+
+
+def _eval_call(fn, head, clouds, transforms, max_dist, want_pairs, ns):
+    """fn(*head, <cloud arguments>, X, K, max_dist, out, nn, d2) -> (status, one dict per transform or None, single)"""
+    X, K, single = _transforms(transforms)
+    out = (Evaluation * max(K, 1))()
+    rows = K if 1 <= K <= EVAL_MAX_TRANSFORMS else 1
+    nn = np.empty((rows, ns), np.int32) if want_pairs else None
+    d2 = np.empty((rows, ns), np.float32) if want_pairs else None
+    st = fn(*head, *clouds, None if X is None else _fptr(X), K, float(max_dist), out, None if nn is None else _i32ptr(nn),
+            None if d2 is None else _fptr(d2))
+    return st, (_eval_dicts(out, K, nn, d2) if st == OK else None), single
+
+
+def _eval_clouds(src, tgt, strides=None):
+    """packed [n, 3] clouds, or with strides = (src_row, src_col, ns, tgt_row, tgt_col, nt) raw float32 buffers"""
+    if strides is None:
+        src, tgt = _cloud(src), _cloud(tgt)
+        return (_fptr(src), 3, 1, len(src), _fptr(tgt), 3, 1, len(tgt)), len(src), (src, tgt)
+    sr, sc, ns, tr, tc, nt = strides
+    return (_fptr(src), sr, sc, ns, _fptr(tgt), tr, tc, nt), ns, (src, tgt)
+
+
+def evaluate_registration(src, tgt, transforms=None, max_dist=0.0, device=-1, want_pairs=False):
+    """How good an alignment is (symmicp_evaluate_registration; include/symmicp.h has the definition): for every transform ([4, 4],
+    [K, 4, 4], or None for the identity) a dict with inliers, fitness, rmse, mean_d2 (PCL's getFitnessScore), sum_d2, sum_q, sum_qq and
+    information ([6, 6] float64, rotation first, about the caller's origin); with want_pairs also nn [ns] (the target row, -1 for a
+    row that is no inlier) and d2 [ns].  max_dist <= 0: every row is an inlier.  One transform in -> one dict out; [K, 4, 4] -> a list."""
+    args, ns, keep = _eval_clouds(src, tgt)
+    st, r, single = _eval_call(lib().symmicp_evaluate_registration, (int(device),), args, transforms, max_dist, want_pairs, ns)
+    if st != OK:
+        raise SymmIcpError(st, "evaluate_registration")
+    return r[0] if single else r
+
+
 def shard_range(n, nranks, rank):
     b, c = C.c_size_t(0), C.c_size_t(0)
     st = lib().symmicp_shard_range(n, nranks, rank, C.byref(b), C.byref(c))
@@ -1200,6 +1285,29 @@ class Engine:
         """the C call as it is, cfg a BatchConfig -> (status, results array, trace_X, trace_sums) (tests)"""
         return _batch_call(self._L.symmicp_ctx_batch_align, (self._h,), src, src_n, tgt, tgt_n, problems, guesses, cfg, trace)
 
+    def evaluate_registration(self, src, tgt, transforms=None, max_dist=0.0, want_pairs=False):
+        """evaluate_registration on this context's stream and temporary memory (symmicp_ctx_evaluate_registration): the context's clouds,
+        index, certificates, options and states stay as they were"""
+        args, ns, keep = _eval_clouds(src, tgt)
+        st, r, single = _eval_call(self._L.symmicp_ctx_evaluate_registration, (self._h,), args, transforms, max_dist, want_pairs, ns)
+        self._chk(st)
+        return r[0] if single else r
+
+    def evaluate_registration_raw(self, src, tgt, strides, transforms=None, max_dist=0.0, want_pairs=False):
+        """the same on raw float32 buffers with strides = (src_row, src_col, ns, tgt_row, tgt_col, nt) -> (status, list of dicts or None)"""
+        args, ns, keep = _eval_clouds(src, tgt, strides)
+        st, r, _ = _eval_call(self._L.symmicp_ctx_evaluate_registration, (self._h,), args, transforms, max_dist, want_pairs, ns)
+        return st, r
+
+    def evaluate(self, transforms=None, max_dist=0.0, want_pairs=False):
+        """the same function on the clouds this context holds (symmicp_evaluate): nothing is uploaded, the source is the one set_source
+        received and every transform is applied to it as it is (not composed with the context's).  transforms None: the context's
+        current cumulative transform, what transform() returns.  Rows are the caller's for both clouds.  The context stays as it was."""
+        ns = int(self._L.symmicp_local_source_count(self._h))
+        st, r, single = _eval_call(self._L.symmicp_evaluate, (self._h,), (), transforms, max_dist, want_pairs, ns)
+        self._chk(st)
+        return r[0] if single else r
+
     def align_multistart(self, src, src_n, tgt, tgt_n, guesses, **cfg):
         """one pair refined from every guess [B, 4, 4] in one batch -> one result dict per guess"""
         g = np.ascontiguousarray(guesses, np.float32).reshape(-1, 16)
@@ -1443,6 +1551,28 @@ class MyICP:
             if self._cfg["verbose"]:
                 print(format_result(self._final), end="", flush=True)
         return best
+
+    def evaluate(self, max_dist, transform=None):
+        """fitness, inlier RMSE and information matrix of `transform` (None: the final transformation) on the object's full clouds at
+        max_dist (evaluate_registration's dict; <= 0: every point counts)"""
+        assert self.cloud_src is not None and self.cloud_tgt is not None
+        X = self._final if transform is None else np.asarray(transform, np.float32).reshape(4, 4)
+        return evaluate_registration(self.cloud_src, self.cloud_tgt, X, max_dist, device=int(self._cfg.get("device", -1)))
+
+    def getFitnessScore(self, max_range=float(np.finfo(np.float64).max)):
+        """PCL's getFitnessScore: the mean squared distance from the moved source points to their nearest target points, over those
+        within max_range; the largest double when none is.  (max_range is rounded to fp32; the largest double means no limit.)"""
+        d = float(np.float32(min(max_range, float(np.finfo(np.float32).max))))
+        r = self.evaluate(0.0 if d >= float(np.finfo(np.float32).max) else d)
+        return r["mean_d2"] if r["inliers"] > 0 else float(np.finfo(np.float64).max)
+
+    def evaluateStarts(self, max_dist):
+        """every multiStartResults() transform scored on the full clouds at one common distance, in one call: a list of
+        evaluate_registration dicts in the order of the guesses ([] before an alignMultiStart)"""
+        if not self.multistart_results:
+            return []
+        X = np.stack([r["transform"] for r in self.multistart_results])
+        return evaluate_registration(self.cloud_src, self.cloud_tgt, X, max_dist, device=int(self._cfg.get("device", -1)))
 
     def multiStartResults(self):
         """every result of the last alignMultiStart, in the order of its guesses"""

@@ -14,6 +14,7 @@
  * ("todo add params to specify iters & diff", ICP/myicp.h:19).
  */
 #pragma once
+#include <limits>
 #include <vector>
 #include "stdafx.h"
 #include "symmicp.h"
@@ -139,6 +140,17 @@ public:
 	int alignMultiStart(const float *guesses4x4, size_t n_guesses, float out4x4[16] = nullptr);
 	const std::vector<symmicp_batch_result> &multiStartResults() const { return multi_results_; }
 	int bestStart() const { return best_start_; }
+	// Registration evaluation (symmicp_ctx_evaluate_registration, include/symmicp.h) on the object's FULL clouds: fitness, inlier RMSE,
+	// the inlier sums and the 6x6 information matrix of transform4x4 (row-major; null: the final transformation) at max_dist (<= 0:
+	// every point counts).  Returns a symmicp_status; the object's context and results stay as they were.
+	int evaluate(float max_dist, symmicp_evaluation *out, const float *transform4x4 = nullptr);
+	// PCL's getFitnessScore for the final transformation: the mean squared distance from the moved source points to their nearest
+	// target points, over those within max_range (a distance, rounded to fp32; the default: no limit), and
+	// std::numeric_limits<double>::max() when none is within range or the evaluation fails (lastError() says why).
+	double getFitnessScore(double max_range = std::numeric_limits<double>::max());
+	// every multiStartResults() transform scored on the full clouds at one common distance, in ONE call: out[k] belongs to guess k.
+	// alignMultiStart's own choice of winner does not change.  SYMMICP_ERR_STATE before an alignMultiStart.
+	int evaluateStarts(float max_dist, std::vector<symmicp_evaluation> &out);
 	const char *lastError() const { return error_.c_str(); }
 
 private:

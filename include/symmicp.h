@@ -763,6 +763,75 @@ int symmicp_voxel_downsample(int device, const float *xyz, size_t xyz_row_stride
                              const float *nrm, size_t nrm_row_stride, size_t nrm_col_stride, size_t n, float leaf, int min_points,
                              float *xyz_out, float *nrm_out, int32_t *count_out, int32_t *voxel_of, size_t cap, size_t *n_out);
 
+/* ---- registration evaluation: fitness, inlier RMSE, information matrix (PCL's getFitnessScore, Open3D's evaluate_registration and
+ * get_information_matrix_from_point_clouds) -----------------------------------------------------------------------------------------
+ * How good an alignment is, as a pure function of (source, target, transform, distance): exact, reproducible bit for bit, and it leaves a
+ * context exactly as it found it.  Several transforms are evaluated in one call, so that the results of a multi-start or a list of
+ * RANSAC hypotheses are ranked on the full clouds at one common distance.  For a source of ns points, a target of nt points, a row-major
+ * 4x4 X and max_dist:
+ *   Moved point   y_i = the three top rows of X applied to source row i with w = 1, in fp32 and unfused: ((m0 x + m1 y) + m2 z) + m3.
+ *                 X's bottom row is ignored.
+ *   Neighbour     nn(i) = the target row j that minimises (d2(i, j), j) lexicographically, d2 the fp32 (dx dx + dy dy) + dz dz of
+ *                 y_i - q_j (the distance of every pass; ties go to the lowest caller row).  The search is exact.
+ *   Inlier        r2 = max_dist * max_dist in fp32.  Row i is an inlier iff max_dist <= 0 or d2_i <= r2 -- the rule by which the passes apply
+ *                 max_corr_dist.
+ *   Per point     nn_out[i], d2_out[i] (each may be NULL): nn(i) and d2_i for an inlier, -1 and +Inf otherwise.
+ *   Sums          over the inliers: inliers = their count, sum_d2 = sum (double)d2_i, sum_q = sum q, sum_qq = the upper triangle
+ *                 (xx, xy, xz, yy, yz, zz) of sum q q^T, q = q_nn(i) in the CALLER's coordinates widened to fp64 (the products are exact).
+ *                 Order: a function of ns alone.  With T = 1024, B = min(ceil(ns / T), 4096): lane t (0 .. 255) of block b (0 .. B - 1)
+ *                 adds the terms of the caller rows tile * T + 256 j + t, for tile = b, b + B, ... and j = 0 .. 3, in that order; the 256
+ *                 lane sums of a block are added pairwise (t += t + 128, then + 64, ... + 1); the B block sums are added by lane t over
+ *                 the blocks t, t + 256, ... ascending and then by the same pairwise tree.  No floating-point atomics.
+ *   Derived       fitness = inliers / ns; mean_d2 = sum_d2 / inliers (PCL's getFitnessScore); rmse = sqrt(sum_d2 / inliers); rmse and
+ *                 mean_d2 are 0 when there are no inliers.
+ *   Information   information[36], row-major, rotation first, translation last: Open3D's GetInformationMatrixFromPointClouds,
+ *                 L = sum G^T G over the inliers, where for q = (x, y, z) the rows of G are (0, z, -y, 1, 0, 0), (-z, 0, x, 0, 1, 0) and
+ *                 (y, -x, 0, 0, 0, 1).  Computed in fp64 on the host from the sums by its closed form (symmicp_information_from_sums):
+ *                 with S = sum_qq, s = sum_q, n = inliers, the rotation block is tr(S) I - S with the diagonal Syy + Szz, Sxx + Szz,
+ *                 Sxx + Syy and the off-diagonals -Sxy, -Sxz, -Syz; the rotation-translation block is [s]x = (0, -sz, sy; sz, 0, -sx;
+ *                 -sy, sx, 0), the translation-rotation block its transpose, the translation block n I.  The information is about the
+ *                 CALLER's origin, as Open3D's is: a back end that linearises about another point moves it there itself.
+ *   Purity        K is 1 .. 4096; result k is a function of X_k alone: bit for bit the same whatever K, whatever its place in the list,
+ *                 and from run to run.
+ * Target -> source (Chamfer's other half, the covered share of the target) is the same call with the clouds swapped and the rows of
+ * symmicp_inverse_rigid(X) as the transform.
+ * Out of scope: sharded contexts; point-to-plane residual statistics; a pose covariance from the record; the pose-graph optimiser. */
+typedef struct {
+    uint64_t inliers;
+    double fitness;            /* inliers / ns */
+    double rmse;               /* sqrt(sum_d2 / inliers); 0 without inliers */
+    double mean_d2;            /* sum_d2 / inliers (PCL's getFitnessScore); 0 without inliers */
+    double sum_d2;
+    double sum_q[3];
+    double sum_qq[6];          /* xx, xy, xz, yy, yz, zz */
+    double information[36];    /* row-major 6x6, rotation first */
+} symmicp_evaluation;
+/* the closed form above: a pure host function (SYMMICP_ERR_ARG for a NULL pointer) */
+int symmicp_information_from_sums(uint64_t n, const double sum_q[3], const double sum_qq[6], double out36[36]);
+/* On host arrays strided as in symmicp_set_source.  X16 [K][16] (NULL: the identity, K == 1); out [K]; nn_out / d2_out [K][ns] or NULL.
+ * Runs on the context's stream and temporary memory, like symmicp_ctx_radius_search: the context's clouds, index, certificates, options
+ * and states stay as they were.
+ * SYMMICP_ERR_ARG, all decided on the host before a device is needed: a NULL cloud or out; ns or nt of 0 or above 2^31 - 1; K outside
+ * 1 .. 4096; NULL X16 with K != 1; a non-finite entry in the top three rows of any X_k; a max_dist that is NaN or +-Inf; non-finite
+ * coordinates.  (nn_out and d2_out are sized by the caller.) */
+int symmicp_ctx_evaluate_registration(symmicp_ctx *ctx, const float *src_xyz, size_t src_row_stride, size_t src_col_stride, size_t ns,
+                                      const float *tgt_xyz, size_t tgt_row_stride, size_t tgt_col_stride, size_t nt,
+                                      const float *X16, size_t K, float max_dist, symmicp_evaluation *out, int32_t *nn_out, float *d2_out);
+/* the same on a context of its own, created on `device` (-1 = current) and destroyed again */
+int symmicp_evaluate_registration(int device, const float *src_xyz, size_t src_row_stride, size_t src_col_stride, size_t ns,
+                                  const float *tgt_xyz, size_t tgt_row_stride, size_t tgt_col_stride, size_t nt,
+                                  const float *X16, size_t K, float max_dist, symmicp_evaluation *out, int32_t *nn_out, float *d2_out);
+/* The same function on the clouds the context already holds; nothing is uploaded.  The source is the source as symmicp_set_source
+ * received it -- never the written-back copy, in either apply mode and either source order -- and each X_k is applied to THAT source: it
+ * is not composed with the context's transform.  X16 == NULL with K == 1 means the context's current cumulative transform, what
+ * symmicp_get_transform returns.  Rows are in the caller's numbering for both clouds.  Every symmicp_corr is accepted: a TREE context
+ * walks its own index, the others build a temporary one that is dropped before returning.  The result is bit for bit that of the
+ * host-array form on the same clouds.  It may be called between two symmicp_step calls: pairs, certificates, rejection states, loop
+ * state, loop log and the pass counts of symmicp_stats stay exactly as they were.
+ * SYMMICP_ERR_ARG as above (out, K, X16, max_dist).  SYMMICP_ERR_STATE: before both clouds are set; on a sharded context (nranks > 1: the
+ * sums would need an exchange; out of scope, as for the rejectors). */
+int symmicp_evaluate(symmicp_ctx *ctx, const float *X16, size_t K, float max_dist, symmicp_evaluation *out, int32_t *nn_out, float *d2_out);
+
 /* ---- multi-GPU (new: the reference is single-threaded) ----- */
 /* rank 0 creates an id, the application ships it to the other ranks (any channel),
  * then every rank calls comm_init_rank BEFORE set_source.  One RCCL all-reduce of
