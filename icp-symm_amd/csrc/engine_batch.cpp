@@ -181,13 +181,7 @@ int symmicp_batch_align(int device, const float *src_xyz, const float *src_nrm, 
 {
     std::string msg;
     if (const int st = batch_args_error(src_xyz, src_nrm, ns_total, tgt_xyz, tgt_nrm, nt_total, problems, B, cfg, out, msg)) return st;
-    symmicp_config ccfg;
-    symmicp_config_default(&ccfg);
-    ccfg.device = device;
-    symmicp_ctx *c = nullptr;
-    int st = symmicp_create(&ccfg, &c);
-    if (st != SYMMICP_OK) return st;
-    st = symmicp_ctx_batch_align(c, src_xyz, src_nrm, ns_total, tgt_xyz, tgt_nrm, nt_total, problems, guess16, B, cfg, out, trace_X, trace_sums);
-    symmicp_destroy(c);
-    return st;
+    return with_own_context(device, [&](symmicp_ctx *c) {
+        return symmicp_ctx_batch_align(c, src_xyz, src_nrm, ns_total, tgt_xyz, tgt_nrm, nt_total, problems, guess16, B, cfg, out, trace_X, trace_sums);
+    });
 }

@@ -1,0 +1,487 @@
+// engine_cloud_ops.cpp -- the stand-alone cloud operations of libsymmicp: normals and k-NN, radius search, FPFH, ISS keypoints, the
+// intensity gradient of colored ICP, voxel-grid downsampling.  Each runs on a context the caller owns (symmicp_ctx_*), whose target,
+// source, index and certificates stay as they are, or as a one-shot on a context of its own (with_own_context).
+#include "engine_internal.h"
+
+// ---- the scratch index of an operation ------------------------------------------------------------------------------------
+// The caller's cloud uploaded and a box tree built over its Morton order, behind the target's arrays in the keep-arena; the destructor
+// gives all of it back (stream sync, the overflow allocations freed, keep.off and target_surface_like restored), on every exit.
+// Declare it BEFORE the DevBufs that work on its index: they have to be destroyed before this destructor syncs and rewinds.
+namespace {
+struct ScratchIndex {
+    TargetIndex ix{};
+    ScratchIndex() = default;
+    ScratchIndex(const ScratchIndex &) = delete;
+    ScratchIndex &operator=(const ScratchIndex &) = delete;
+    ~ScratchIndex()
+    {
+        if (!c) return;      // begin() never got as far as saving the state
+        (void)hipStreamSynchronize(c->stream);
+        while (c->keep_extra.size() > extra0) { hipFree(c->keep_extra.back()); c->keep_extra.pop_back(); }
+        c->keep.off = keep_off0;
+        c->target_surface_like = surf0;
+    }
+    // nrm may be NULL (zero normals).  temp_bytes: what the caller will take from the arena afterwards.
+    int begin(symmicp_ctx *ctx, const float *xyz, size_t xr, size_t xc, const float *nrm, size_t nr, size_t nc, size_t n, size_t temp_bytes)
+    {
+        HIP_TRY(ctx, hipSetDevice(ctx->device));
+        if (ctx->keep.cap == 0) {
+            // no target yet: give the keep-arena the size this cloud needs (a later set_target reuses it)
+            const size_t want = n * 96 + ((size_t)4 << 20);
+            if (hipMalloc((void **)&ctx->keep.base, want) == hipSuccess) { ctx->keep.cap = want; ctx->keep.off = 0; }
+            else (void)hipGetLastError();
+        }
+        c = ctx;
+        keep_off0 = c->keep.off;
+        extra0 = c->keep_extra.size();
+        surf0 = c->target_surface_like;
+        arena_begin(c->arena, n * (96 + 4 * (xr + (nrm ? nr : 0))) + temp_bytes + ((size_t)1 << 20));
+        DevBuf<float> block;      // (from the keep-arena: not owned)
+        if (int st = upload_planar(c, xyz, xr, xc, nrm, nr, nc, n, block, /*temp=*/false, nullptr)) return st;
+        CloudSoA cl;
+        soa_from_block(block.p, n, cl);
+        float4 *tq = nullptr, *tn = nullptr, *boxes = nullptr;
+        uint2 *cells = nullptr;
+        if (keep_alloc(c, (void **)&tq, sizeof(float4) * (n + 8)) != hipSuccess || keep_alloc(c, (void **)&tn, sizeof(float4) * 2 * n) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(c, SYMMICP_ERR_HIP, "out of device memory");
+        }
+        return build_index(c, cl, (uint32_t)n, /*want_grid=*/false, tq, tn, &boxes, &cells, &ix, nullptr, nullptr);
+    }
+
+private:
+    symmicp_ctx *c = nullptr;      // set once the three words below are saved
+    size_t keep_off0 = 0, extra0 = 0;
+    bool surf0 = false;
+};
+}  // namespace
+
+extern "C" {
+
+// ---- normals pre-step (MyICP::estimateNormals, myicp.cpp:152-172) --------------------------------
+// Runs on a context the caller owns (its stream and arenas are reused: a tracker that estimates normals per scan pays no
+// context set-up); the context's target and source stay as they are -- what the estimate allocates behind the target's arrays
+// in the keep-arena is released again.
+// symmicp_ctx_knn runs the same index build and walk, and reads back the neighbour set (rows, d2) instead of the normals.
+static bool normals_args_ok(const float *xyz, size_t n, int k)
+{
+    return xyz && n != 0 && n <= 0x7fffffffull && k >= 3 && k <= 16 && (size_t)k <= n;
+}
+
+static int normals_or_knn(symmicp_ctx *c, const float *xyz, size_t row_stride, size_t col_stride, size_t n, int k,
+                          const float viewpoint[3], float *nrm_out, float *curv_out, int32_t *rows_out, float *d2_out)
+{
+    const bool knn = rows_out != nullptr;
+    ScratchIndex si;
+    // the cloud has no normals yet: stage xyz twice (the normal slots are ignored)
+    if (int st = si.begin(c, xyz, row_stride, col_stride, xyz, row_stride, col_stride, n, n * (knn ? 8 * (size_t)k : 16))) return st;
+    // normals: [n][3] + [n]; neighbour set: [n][k] rows + [n][k] d2
+    DevBuf<float> b_a, b_b;
+    HIP_TRY(c, b_a.alloc_temp(c->arena, (knn ? (size_t)k : 3) * n));
+    HIP_TRY(c, b_b.alloc_temp(c->arena, (knn ? (size_t)k : 1) * n));
+    if (knn) {
+        launch_knn(si.ix, k, (int32_t *)b_a.p, b_b.p, c->stream);
+        HIP_TRY(c, hipMemcpyAsync(rows_out, b_a.p, sizeof(int32_t) * (size_t)k * n, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(d2_out, b_b.p, sizeof(float) * (size_t)k * n, hipMemcpyDeviceToHost, c->stream));
+    } else {
+        const float vp0[3] = {0.f, 0.f, 0.f};
+        launch_normals_knn(si.ix, k, viewpoint ? viewpoint : vp0, b_a.p, b_b.p, c->stream);
+        HIP_TRY(c, hipMemcpyAsync(nrm_out, b_a.p, sizeof(float) * 3 * n, hipMemcpyDeviceToHost, c->stream));
+        if (curv_out) HIP_TRY(c, hipMemcpyAsync(curv_out, b_b.p, sizeof(float) * n, hipMemcpyDeviceToHost, c->stream));
+    }
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    HIP_TRY(c, hipGetLastError());
+    return SYMMICP_OK;
+}
+
+int symmicp_ctx_estimate_normals(symmicp_ctx *c, const float *xyz, size_t row_stride, size_t col_stride, size_t n, int k,
+                                 const float viewpoint[3], float *nrm_out, float *curv_out)
+{
+    if (!c) return SYMMICP_ERR_ARG;
+    if (!nrm_out || !normals_args_ok(xyz, n, k)) return fail(c, SYMMICP_ERR_ARG, "bad cloud or k (3..16, <= n)");
+    return normals_or_knn(c, xyz, row_stride, col_stride, n, k, viewpoint, nrm_out, curv_out, nullptr, nullptr);
+}
+
+int symmicp_ctx_knn(symmicp_ctx *c, const float *xyz, size_t row_stride, size_t col_stride, size_t n, int k, int32_t *rows_out, float *d2_out)
+{
+    if (!c) return SYMMICP_ERR_ARG;
+    if (!rows_out || !d2_out || !normals_args_ok(xyz, n, k)) return fail(c, SYMMICP_ERR_ARG, "bad cloud or k (3..16, <= n)");
+    return normals_or_knn(c, xyz, row_stride, col_stride, n, k, nullptr, nullptr, nullptr, rows_out, d2_out);
+}
+
+int symmicp_estimate_normals(int device, const float *xyz, size_t row_stride, size_t col_stride, size_t n, int k,
+                             const float viewpoint[3], float *nrm_out, float *curv_out)
+{
+    if (!nrm_out || !normals_args_ok(xyz, n, k)) return SYMMICP_ERR_ARG;
+    return with_own_context(device, [&](symmicp_ctx *c) {
+        return symmicp_ctx_estimate_normals(c, xyz, row_stride, col_stride, n, k, viewpoint, nrm_out, curv_out);
+    });
+}
+
+// ---- radius search and FPFH features (kernels_fpfh.hip; DESIGN.md 4, "FPFH features and radius search") ------------------
+// Both run like the normals pre-step above: a ScratchIndex over the caller's cloud, walked per point.  The context's own clouds, index
+// and certificates are not touched.
+static const char *radius_args_error(const float *xyz, size_t n, float radius, const int32_t *count_out, const int64_t *offsets_out,
+                                     const int32_t *rows_out, const size_t *total_out)
+{
+    if (!xyz || !count_out || !total_out) return "radius_search: xyz, count_out and total_out are required";
+    if (rows_out && !offsets_out) return "radius_search: rows_out needs offsets_out";
+    if (n == 0 || n > 0x7fffffffull) return "radius_search: n must be in 1 .. 2^31 - 1";
+    if (!std::isfinite(radius) || !(radius > 0.f)) return "radius_search: radius must be finite and > 0";
+    return nullptr;
+}
+
+static int radius_search(symmicp_ctx *c, const float *xyz, size_t xr, size_t xc, size_t n, float radius, int32_t *count_out,
+                         int64_t *offsets_out, int32_t *rows_out, float *d2_out, size_t cap, size_t *total_out)
+{
+    ScratchIndex si;
+    if (int st = si.begin(c, xyz, xr, xc, nullptr, 0, 0, n, n * 8 + 8192)) return st;
+    const float r2 = radius * radius;
+    DevBuf<int32_t> d_count, d_rows;
+    DevBuf<uint32_t> d_offs, scan_ws;
+    DevBuf<float> d_d2;
+    HIP_TRY(c, d_count.alloc_temp(c->arena, n));
+    HIP_TRY(c, d_offs.alloc_temp(c->arena, n));
+    HIP_TRY(c, scan_ws.alloc_temp(c->arena, n / 2048 + 2));
+    launch_radius_count(si.ix, r2, d_count.p, c->stream);
+    HIP_TRY(c, hipMemcpyAsync(d_offs.p, d_count.p, sizeof(uint32_t) * n, hipMemcpyDeviceToDevice, c->stream));
+    launch_exclusive_scan(d_offs.p, (uint32_t)n, scan_ws.p, c->stream);
+    HIP_TRY(c, hipMemcpyAsync(count_out, d_count.p, sizeof(int32_t) * n, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    HIP_TRY(c, hipGetLastError());
+    uint64_t total = 0;
+    for (size_t i = 0; i < n; i++) total += (uint64_t)(uint32_t)count_out[i];
+    *total_out = (size_t)total;
+    if (offsets_out) {
+        int64_t at = 0;
+        for (size_t i = 0; i < n; i++) { offsets_out[i] = at; at += count_out[i]; }
+        offsets_out[n] = at;
+    }
+    if (!rows_out) return SYMMICP_OK;
+    if (total > cap) return fail(c, SYMMICP_ERR_SIZE, "radius_search: " + std::to_string(total) + " neighbours do not fit cap " + std::to_string(cap));
+    // the device's offsets are 32-bit words (launch_exclusive_scan)
+    if (total > 0xffffffffull) return fail(c, SYMMICP_ERR_SIZE, "radius_search: more than 2^32 - 1 neighbours in all; use a smaller radius or split the cloud");
+    if (total == 0) return SYMMICP_OK;
+    HIP_TRY(c, d_rows.alloc_temp(c->arena, total));
+    if (d2_out) HIP_TRY(c, d_d2.alloc_temp(c->arena, total));
+    launch_radius_fill(si.ix, r2, d_offs.p, d_rows.p, d_d2.p, c->stream);
+    HIP_TRY(c, hipMemcpyAsync(rows_out, d_rows.p, sizeof(int32_t) * total, hipMemcpyDeviceToHost, c->stream));
+    if (d2_out) HIP_TRY(c, hipMemcpyAsync(d2_out, d_d2.p, sizeof(float) * total, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    HIP_TRY(c, hipGetLastError());
+    return SYMMICP_OK;
+}
+
+int symmicp_ctx_radius_search(symmicp_ctx *c, const float *xyz, size_t row_stride, size_t col_stride, size_t n, float radius,
+                              int32_t *count_out, int64_t *offsets_out, int32_t *rows_out, float *d2_out, size_t cap, size_t *total_out)
+{
+    if (!c) return SYMMICP_ERR_ARG;
+    if (const char *msg = radius_args_error(xyz, n, radius, count_out, offsets_out, rows_out, total_out)) return fail(c, SYMMICP_ERR_ARG, msg);
+    return radius_search(c, xyz, row_stride, col_stride, n, radius, count_out, offsets_out, rows_out, d2_out, cap, total_out);
+}
+
+int symmicp_radius_search(int device, const float *xyz, size_t row_stride, size_t col_stride, size_t n, float radius, int32_t *count_out,
+                          int64_t *offsets_out, int32_t *rows_out, float *d2_out, size_t cap, size_t *total_out)
+{
+    if (radius_args_error(xyz, n, radius, count_out, offsets_out, rows_out, total_out)) return SYMMICP_ERR_ARG;
+    return with_own_context(device, [&](symmicp_ctx *c) {
+        return symmicp_ctx_radius_search(c, xyz, row_stride, col_stride, n, radius, count_out, offsets_out, rows_out, d2_out, cap, total_out);
+    });
+}
+
+static const char *fpfh_args_error(const float *xyz, const float *nrm, size_t n, float radius, const float *fpfh_out)
+{
+    if (!xyz || !nrm || !fpfh_out) return "fpfh: xyz, nrm and fpfh_out are required";
+    if (n == 0 || n > 0x7fffffffull) return "fpfh: n must be in 1 .. 2^31 - 1";
+    if (!std::isfinite(radius) || !(radius > 0.f)) return "fpfh: radius must be finite and > 0";
+    return nullptr;
+}
+
+int symmicp_ctx_fpfh(symmicp_ctx *c, const float *xyz, size_t xyz_row_stride, size_t xyz_col_stride, const float *nrm, size_t nrm_row_stride,
+                     size_t nrm_col_stride, size_t n, float radius, float *fpfh_out, float *spfh_out, int32_t *count_out)
+{
+    if (!c) return SYMMICP_ERR_ARG;
+    if (const char *msg = fpfh_args_error(xyz, nrm, n, radius, fpfh_out)) return fail(c, SYMMICP_ERR_ARG, msg);
+    ScratchIndex si;
+    if (int st = si.begin(c, xyz, xyz_row_stride, xyz_col_stride, nrm, nrm_row_stride, nrm_col_stride, n, n * (36 + 33 + 33 + 1) * 4 + 8192)) return st;
+    const float r2 = radius * radius;
+    DevBuf<float> d_sorted, d_spfh, d_fpfh;
+    DevBuf<int32_t> d_count;
+    HIP_TRY(c, d_sorted.alloc_temp(c->arena, n * 36));
+    HIP_TRY(c, d_fpfh.alloc_temp(c->arena, n * 33));
+    HIP_TRY(c, d_count.alloc_temp(c->arena, n));
+    if (spfh_out) HIP_TRY(c, d_spfh.alloc_temp(c->arena, n * 33));
+    launch_spfh(si.ix, r2, d_sorted.p, d_spfh.p, d_count.p, c->stream);
+    launch_fpfh(si.ix, r2, d_sorted.p, d_fpfh.p, c->stream);
+    HIP_TRY(c, hipMemcpyAsync(fpfh_out, d_fpfh.p, sizeof(float) * 33 * n, hipMemcpyDeviceToHost, c->stream));
+    if (spfh_out) HIP_TRY(c, hipMemcpyAsync(spfh_out, d_spfh.p, sizeof(float) * 33 * n, hipMemcpyDeviceToHost, c->stream));
+    if (count_out) HIP_TRY(c, hipMemcpyAsync(count_out, d_count.p, sizeof(int32_t) * n, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    HIP_TRY(c, hipGetLastError());
+    return SYMMICP_OK;
+}
+
+int symmicp_fpfh(int device, const float *xyz, size_t xyz_row_stride, size_t xyz_col_stride, const float *nrm, size_t nrm_row_stride,
+                 size_t nrm_col_stride, size_t n, float radius, float *fpfh_out, float *spfh_out, int32_t *count_out)
+{
+    if (fpfh_args_error(xyz, nrm, n, radius, fpfh_out)) return SYMMICP_ERR_ARG;
+    return with_own_context(device, [&](symmicp_ctx *c) {
+        return symmicp_ctx_fpfh(c, xyz, xyz_row_stride, xyz_col_stride, nrm, nrm_row_stride, nrm_col_stride, n, radius, fpfh_out, spfh_out, count_out);
+    });
+}
+
+// ---- ISS keypoints (kernels_keypoints.hip; DESIGN.md 4, "ISS keypoints") ---------------------------------------------------
+// Like the FPFH entry above: the cloud's own scratch index, the radius walk twice (saliency at the salient radius, non-maximum
+// suppression at the other), then the flags scanned over rows and the kept rows scattered in ascending order.
+static const char *iss_args_error(const float *xyz, size_t xr, size_t xc, size_t n, const symmicp_iss_config *cfg, const int32_t *rows_out, size_t cap,
+                                  const size_t *count_out)
+{
+    if (!xyz || !cfg || !count_out) return "iss_keypoints: xyz, cfg and count_out are required";
+    if (!rows_out && cap > 0) return "iss_keypoints: rows_out is required when cap > 0";
+    if (n == 0 || n > 0x7fffffffull) return "iss_keypoints: n must be in 1 .. 2^31 - 1";
+    if (cfg->struct_size != sizeof(symmicp_iss_config)) return "iss_keypoints: cfg->struct_size is not sizeof(symmicp_iss_config)";
+    if (!std::isfinite(cfg->salient_radius) || !(cfg->salient_radius > 0.f)) return "iss_keypoints: salient_radius must be finite and > 0";
+    if (!std::isfinite(cfg->non_max_radius) || !(cfg->non_max_radius > 0.f)) return "iss_keypoints: non_max_radius must be finite and > 0";
+    if (!(cfg->gamma21 > 0.f) || !(cfg->gamma21 <= 1.f)) return "iss_keypoints: gamma21 must be in (0, 1]";
+    if (!(cfg->gamma32 > 0.f) || !(cfg->gamma32 <= 1.f)) return "iss_keypoints: gamma32 must be in (0, 1]";
+    if (cfg->min_neighbors < 1) return "iss_keypoints: min_neighbors must be >= 1";
+    for (size_t i = 0; i < n; i++)
+        for (int a = 0; a < 3; a++)
+            if (!std::isfinite(xyz[i * xr + a * xc])) return "iss_keypoints: a coordinate is not finite";
+    return nullptr;
+}
+
+void symmicp_iss_config_default(symmicp_iss_config *cfg)
+{
+    if (!cfg) return;
+    std::memset(cfg, 0, sizeof(*cfg));
+    cfg->struct_size = (uint32_t)sizeof(*cfg);
+    cfg->gamma21 = 0.975f;
+    cfg->gamma32 = 0.975f;
+    cfg->min_neighbors = 5;
+}
+
+int symmicp_ctx_iss_keypoints(symmicp_ctx *c, const float *xyz, size_t row_stride, size_t col_stride, size_t n, const symmicp_iss_config *cfg,
+                              int32_t *rows_out, size_t cap, size_t *count_out, float *saliency_out, int32_t *neighbors_out)
+{
+    if (!c) return SYMMICP_ERR_ARG;
+    if (const char *msg = iss_args_error(xyz, row_stride, col_stride, n, cfg, rows_out, cap, count_out)) return fail(c, SYMMICP_ERR_ARG, msg);
+    ScratchIndex si;
+    if (int st = si.begin(c, xyz, row_stride, col_stride, nullptr, 0, 0, n, n * 6 * 4 + 16384)) return st;
+    const float rs2 = cfg->salient_radius * cfg->salient_radius, rn2 = cfg->non_max_radius * cfg->non_max_radius;
+    DevBuf<float> d_sorted, d_srows;
+    DevBuf<int32_t> d_k, d_rows;
+    DevBuf<uint32_t> d_flag, d_pos, scan_ws;
+    HIP_TRY(c, d_sorted.alloc_temp(c->arena, n));
+    HIP_TRY(c, d_srows.alloc_temp(c->arena, n));
+    HIP_TRY(c, d_k.alloc_temp(c->arena, n));
+    HIP_TRY(c, d_flag.alloc_temp(c->arena, n));
+    HIP_TRY(c, d_pos.alloc_temp(c->arena, n));
+    HIP_TRY(c, scan_ws.alloc_temp(c->arena, n / 2048 + 2));
+    launch_iss_saliency(si.ix, rs2, cfg->min_neighbors, cfg->gamma21, cfg->gamma32, d_sorted.p, d_srows.p, d_k.p, c->stream);
+    launch_iss_nms(si.ix, rn2, cfg->min_neighbors, d_sorted.p, d_flag.p, c->stream);
+    HIP_TRY(c, hipMemcpyAsync(d_pos.p, d_flag.p, sizeof(uint32_t) * n, hipMemcpyDeviceToDevice, c->stream));
+    launch_exclusive_scan(d_pos.p, (uint32_t)n, scan_ws.p, c->stream);
+    uint32_t last_pos = 0, last_flag = 0;
+    HIP_TRY(c, hipMemcpyAsync(&last_pos, d_pos.p + (n - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(&last_flag, d_flag.p + (n - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    if (saliency_out) HIP_TRY(c, hipMemcpyAsync(saliency_out, d_srows.p, sizeof(float) * n, hipMemcpyDeviceToHost, c->stream));
+    if (neighbors_out) HIP_TRY(c, hipMemcpyAsync(neighbors_out, d_k.p, sizeof(int32_t) * n, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    HIP_TRY(c, hipGetLastError());
+    const size_t count = (size_t)last_pos + last_flag;
+    *count_out = count;
+    if (count > cap) return fail(c, SYMMICP_ERR_SIZE, "iss_keypoints: " + std::to_string(count) + " keypoints do not fit cap " + std::to_string(cap));
+    if (count == 0) return SYMMICP_OK;
+    HIP_TRY(c, d_rows.alloc_temp(c->arena, count));
+    launch_iss_scatter(d_flag.p, d_pos.p, (uint32_t)n, d_rows.p, c->stream);
+    HIP_TRY(c, hipMemcpyAsync(rows_out, d_rows.p, sizeof(int32_t) * count, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    HIP_TRY(c, hipGetLastError());
+    return SYMMICP_OK;
+}
+
+int symmicp_iss_keypoints(int device, const float *xyz, size_t row_stride, size_t col_stride, size_t n, const symmicp_iss_config *cfg,
+                          int32_t *rows_out, size_t cap, size_t *count_out, float *saliency_out, int32_t *neighbors_out)
+{
+    if (iss_args_error(xyz, row_stride, col_stride, n, cfg, rows_out, cap, count_out)) return SYMMICP_ERR_ARG;
+    return with_own_context(device, [&](symmicp_ctx *c) {
+        return symmicp_ctx_iss_keypoints(c, xyz, row_stride, col_stride, n, cfg, rows_out, cap, count_out, saliency_out, neighbors_out);
+    });
+}
+
+// ---- intensity gradient of colored ICP (kernels_color.hip; DESIGN.md 4, "Colored ICP") ------------------------------------
+// Like the FPFH entry above: the cloud's own scratch index, the exact k-NN walk of the normals pre-step (launch_knn: rows in (d2, row) order),
+// then the tangent-plane moments and the 3x3 solve per point.
+static const char *gradient_args_error(const float *xyz, const float *nrm, const float *intensity, size_t n, int k, const float *grad_out)
+{
+    if (!xyz || !nrm || !intensity || !grad_out) return "intensity gradient: xyz, nrm, intensity and grad_out are required";
+    if (n == 0 || n > 0x7fffffffull) return "intensity gradient: n must be in 1 .. 2^31 - 1";
+    if (k < 3 || k > 16 || (size_t)k > n) return "intensity gradient: k must be in 3 .. 16 and <= n";
+    return nullptr;
+}
+
+int symmicp_ctx_intensity_gradient(symmicp_ctx *c, const float *xyz, size_t xyz_row_stride, size_t xyz_col_stride, const float *nrm,
+                                   size_t nrm_row_stride, size_t nrm_col_stride, const float *intensity, size_t intensity_stride, size_t n,
+                                   int k, float *grad_out)
+{
+    if (!c) return SYMMICP_ERR_ARG;
+    if (const char *msg = gradient_args_error(xyz, nrm, intensity, n, k, grad_out)) return fail(c, SYMMICP_ERR_ARG, msg);
+    std::vector<float> hi(n);
+    for (size_t i = 0; i < n; i++) hi[i] = intensity[i * intensity_stride];
+    ScratchIndex si;
+    if (int st = si.begin(c, xyz, xyz_row_stride, xyz_col_stride, nrm, nrm_row_stride, nrm_col_stride, n,
+                        n * (8 * (size_t)k + 4 + 16 + 12) + 8192)) return st;
+    DevBuf<int32_t> d_rows;
+    DevBuf<float> d_d2, d_int, d_grad;
+    DevBuf<float4> d_rec;
+    HIP_TRY(c, d_rows.alloc_temp(c->arena, n * (size_t)k));
+    HIP_TRY(c, d_d2.alloc_temp(c->arena, n * (size_t)k));
+    HIP_TRY(c, d_int.alloc_temp(c->arena, n));
+    HIP_TRY(c, d_rec.alloc_temp(c->arena, n));
+    HIP_TRY(c, d_grad.alloc_temp(c->arena, 3 * n));
+    HIP_TRY(c, hipMemcpyAsync(d_int.p, hi.data(), sizeof(float) * n, hipMemcpyHostToDevice, c->stream));
+    launch_knn(si.ix, k, d_rows.p, d_d2.p, c->stream);
+    launch_color_gradient(si.ix, d_int.p, d_rows.p, k, d_rec.p, d_grad.p, c->stream);
+    HIP_TRY(c, hipMemcpyAsync(grad_out, d_grad.p, sizeof(float) * 3 * n, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    HIP_TRY(c, hipGetLastError());
+    return SYMMICP_OK;
+}
+
+int symmicp_intensity_gradient(int device, const float *xyz, size_t xyz_row_stride, size_t xyz_col_stride, const float *nrm,
+                               size_t nrm_row_stride, size_t nrm_col_stride, const float *intensity, size_t intensity_stride, size_t n,
+                               int k, float *grad_out)
+{
+    if (gradient_args_error(xyz, nrm, intensity, n, k, grad_out)) return SYMMICP_ERR_ARG;
+    return with_own_context(device, [&](symmicp_ctx *c) {
+        return symmicp_ctx_intensity_gradient(c, xyz, xyz_row_stride, xyz_col_stride, nrm, nrm_row_stride, nrm_col_stride, intensity, intensity_stride,
+                                              n, k, grad_out);
+    });
+}
+
+// ---- voxel-grid downsampling (kernels_voxel.hip; DESIGN.md 4, "Voxel downsampling") ---------------------------------------
+// Box (launch_bbox) -> grid set-up here in fp32 -> keys -> stable radix sort of (key, row) -> run heads, scan, first positions ->
+// kept voxels (>= min_points), scan, compaction -> sorted SoA gather -> per-voxel sequential means.  Temporaries come from the
+// context's arena only: its target, source, index and certificates are not touched.
+static int voxel_downsample(symmicp_ctx *c, const float *xyz, size_t xr, size_t xc, const float *nrm, size_t nr, size_t nc, size_t n,
+                            float leaf, int min_points, float *xyz_out, float *nrm_out, int32_t *count_out, int32_t *voxel_of, size_t cap,
+                            size_t *n_out)
+{
+    HIP_TRY(c, hipSetDevice(c->device));
+    const bool with_nrm = nrm_out != nullptr;
+    arena_begin(c->arena, n * (128 + 4 * (xr + (with_nrm ? nr : 0))) + ((size_t)1 << 20));
+    const uint32_t n32 = (uint32_t)n;
+    DevBuf<float> block;
+    int st = upload_planar(c, xyz, xr, xc, with_nrm ? nrm : nullptr, nr, nc, n, block, /*temp=*/true, nullptr);
+    if (st != SYMMICP_OK) return st;
+    CloudSoA cl;
+    soa_from_block(block.p, n, cl);
+
+    DevBuf<uint32_t> bbox;
+    HIP_TRY(c, bbox.alloc_temp(c->arena, 6));
+    launch_bbox(cl.x, cl.y, cl.z, n32, bbox.p, c->stream);
+    uint32_t hb[6];
+    HIP_TRY(c, hipMemcpyAsync(hb, bbox.p, sizeof(hb), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    // the grid, in fp32 with IEEE ops: floorf(v * inv) is monotone in v, so the box's ends give every point's cell range
+    const float inv = 1.0f / leaf;
+    int lo[3];
+    uint64_t dim[3];
+    for (int k = 0; k < 3; k++) {
+        const float bmin = ord2f(hb[k]), bmax = ord2f(hb[3 + k]);
+        if (!std::isfinite(bmin) || !std::isfinite(bmax)) return fail(c, SYMMICP_ERR_ARG, "cloud has non-finite coordinates");
+        const float flo = std::floor(bmin * inv), fhi = std::floor(bmax * inv);
+        if (!(flo >= -2147483648.0f && flo < 2147483648.0f && fhi >= -2147483648.0f && fhi < 2147483648.0f))
+            return fail(c, SYMMICP_ERR_ARG, "leaf size is too small for the input cloud: voxel indices overflow an int32");
+        lo[k] = (int)flo;
+        dim[k] = (uint64_t)((int64_t)(int)fhi - (int64_t)lo[k] + 1);
+    }
+    const unsigned __int128 total = (unsigned __int128)dim[0] * dim[1] * dim[2];
+    if (total > ((unsigned __int128)1 << 32))
+        return fail(c, SYMMICP_ERR_ARG, "leaf size is too small for the input cloud: more than 2^32 voxels in its box");
+    int bits = 0;
+    while (((unsigned __int128)1 << bits) < total) bits++;
+
+    DevBuf<uint32_t> keys, rows, kt, vt, ws, vid, first, kid, kfirst, kcount, scan_ws, words;
+    DevBuf<float> sorted, d_xyz, d_nrm;
+    DevBuf<int32_t> d_count, d_vof;
+    const size_t wse = radix_sort_ws_elems(n32);
+    HIP_TRY(c, keys.alloc_temp(c->arena, n));
+    HIP_TRY(c, rows.alloc_temp(c->arena, n));
+    HIP_TRY(c, kt.alloc_temp(c->arena, n));
+    HIP_TRY(c, vt.alloc_temp(c->arena, n));
+    HIP_TRY(c, ws.alloc_temp(c->arena, wse));
+    HIP_TRY(c, vid.alloc_temp(c->arena, n));
+    HIP_TRY(c, first.alloc_temp(c->arena, n + 1));
+    HIP_TRY(c, kid.alloc_temp(c->arena, n));
+    HIP_TRY(c, kfirst.alloc_temp(c->arena, n));
+    HIP_TRY(c, kcount.alloc_temp(c->arena, n));
+    HIP_TRY(c, scan_ws.alloc_temp(c->arena, n / 2048 + 2));
+    HIP_TRY(c, words.alloc_temp(c->arena, 2));
+    HIP_TRY(c, sorted.alloc_temp(c->arena, 6 * n));
+    launch_voxel_keys(cl, n32, inv, lo, dim[0], dim[1], keys.p, rows.p, c->stream);
+    radix_sort_pairs(keys.p, rows.p, kt.p, vt.p, n32, bits, ws.p, wse, c->stream);
+    launch_voxel_segments(keys.p, n32, vid.p, first.p, scan_ws.p, words.p, c->stream);
+    uint32_t m0 = 0, m = 0;
+    HIP_TRY(c, hipMemcpyAsync(&m0, words.p, sizeof(m0), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    launch_voxel_keep(first.p, m0, (uint32_t)min_points, kid.p, scan_ws.p, kfirst.p, kcount.p, words.p + 1, c->stream);
+    HIP_TRY(c, hipMemcpyAsync(&m, words.p + 1, sizeof(m), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    *n_out = m;
+    if (m > cap) return fail(c, SYMMICP_ERR_SIZE, "voxel_downsample: " + std::to_string(m) + " voxels do not fit cap " + std::to_string(cap));
+    CloudSoA sc;
+    soa_from_block(sorted.p, n, sc);
+    launch_gather_soa(cl, rows.p, n32, sc, c->stream);
+    HIP_TRY(c, d_xyz.alloc_temp(c->arena, 3 * (size_t)m));
+    HIP_TRY(c, d_count.alloc_temp(c->arena, m));
+    if (with_nrm) HIP_TRY(c, d_nrm.alloc_temp(c->arena, 3 * (size_t)m));
+    launch_voxel_mean(sc, kfirst.p, kcount.p, m, with_nrm ? 1 : 0, d_xyz.p, d_nrm.p, d_count.p, c->stream);
+    if (voxel_of) {
+        HIP_TRY(c, d_vof.alloc_temp(c->arena, n));
+        launch_voxel_of(keys.p, rows.p, vid.p, first.p, kid.p, n32, (uint32_t)min_points, d_vof.p, c->stream);
+    }
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpyAsync(xyz_out, d_xyz.p, sizeof(float) * 3 * m, hipMemcpyDeviceToHost, c->stream));
+    if (with_nrm) HIP_TRY(c, hipMemcpyAsync(nrm_out, d_nrm.p, sizeof(float) * 3 * m, hipMemcpyDeviceToHost, c->stream));
+    if (count_out) HIP_TRY(c, hipMemcpyAsync(count_out, d_count.p, sizeof(int32_t) * m, hipMemcpyDeviceToHost, c->stream));
+    if (voxel_of) HIP_TRY(c, hipMemcpyAsync(voxel_of, d_vof.p, sizeof(int32_t) * n, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    HIP_TRY(c, hipGetLastError());
+    return SYMMICP_OK;
+}
+
+static const char *voxel_args_error(const float *xyz, const float *nrm, size_t n, float leaf, int min_points, const float *xyz_out,
+                                    const float *nrm_out, const size_t *n_out)
+{
+    if (!xyz || !xyz_out || !n_out) return "voxel_downsample: xyz, xyz_out and n_out are required";
+    if (n == 0 || n > 0x7fffffffull) return "voxel_downsample: n must be in 1 .. 2^31 - 1";
+    if (!std::isfinite(leaf) || !(leaf > 0.f)) return "voxel_downsample: leaf must be finite and > 0";
+    if (min_points < 1) return "voxel_downsample: min_points must be >= 1";
+    if (nrm_out && !nrm) return "voxel_downsample: nrm_out needs nrm";
+    return nullptr;
+}
+
+int symmicp_ctx_voxel_downsample(symmicp_ctx *c, const float *xyz, size_t xyz_row_stride, size_t xyz_col_stride, const float *nrm,
+                                 size_t nrm_row_stride, size_t nrm_col_stride, size_t n, float leaf, int min_points, float *xyz_out,
+                                 float *nrm_out, int32_t *count_out, int32_t *voxel_of, size_t cap, size_t *n_out)
+{
+    if (!c) return SYMMICP_ERR_ARG;
+    if (const char *msg = voxel_args_error(xyz, nrm, n, leaf, min_points, xyz_out, nrm_out, n_out)) return fail(c, SYMMICP_ERR_ARG, msg);
+    return voxel_downsample(c, xyz, xyz_row_stride, xyz_col_stride, nrm, nrm_row_stride, nrm_col_stride, n, leaf, min_points, xyz_out, nrm_out,
+                            count_out, voxel_of, cap, n_out);
+}
+
+int symmicp_voxel_downsample(int device, const float *xyz, size_t xyz_row_stride, size_t xyz_col_stride, const float *nrm,
+                             size_t nrm_row_stride, size_t nrm_col_stride, size_t n, float leaf, int min_points, float *xyz_out,
+                             float *nrm_out, int32_t *count_out, int32_t *voxel_of, size_t cap, size_t *n_out)
+{
+    if (voxel_args_error(xyz, nrm, n, leaf, min_points, xyz_out, nrm_out, n_out)) return SYMMICP_ERR_ARG;
+    return with_own_context(device, [&](symmicp_ctx *c) {
+        return symmicp_ctx_voxel_downsample(c, xyz, xyz_row_stride, xyz_col_stride, nrm, nrm_row_stride, nrm_col_stride, n, leaf, min_points,
+                                            xyz_out, nrm_out, count_out, voxel_of, cap, n_out);
+    });
+}
+
+}  // extern "C"

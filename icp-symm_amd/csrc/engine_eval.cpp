@@ -187,16 +187,10 @@ int symmicp_evaluate_registration(int device, const float *src_xyz, size_t src_r
 {
     if (eval_args_error(src_xyz, src_row_stride, src_col_stride, ns, tgt_xyz, tgt_row_stride, tgt_col_stride, nt, X16, K, max_dist, out))
         return SYMMICP_ERR_ARG;
-    symmicp_config ccfg;
-    symmicp_config_default(&ccfg);
-    ccfg.device = device;
-    symmicp_ctx *c = nullptr;
-    int st = symmicp_create(&ccfg, &c);
-    if (st != SYMMICP_OK) return st;
-    st = symmicp_ctx_evaluate_registration(c, src_xyz, src_row_stride, src_col_stride, ns, tgt_xyz, tgt_row_stride, tgt_col_stride, nt, X16, K,
-                                           max_dist, out, nn_out, d2_out);
-    symmicp_destroy(c);
-    return st;
+    return with_own_context(device, [&](symmicp_ctx *c) {
+        return symmicp_ctx_evaluate_registration(c, src_xyz, src_row_stride, src_col_stride, ns, tgt_xyz, tgt_row_stride, tgt_col_stride, nt, X16, K,
+                                                 max_dist, out, nn_out, d2_out);
+    });
 }
 
 int symmicp_evaluate(symmicp_ctx *c, const float *X16, size_t K, float max_dist, symmicp_evaluation *out, int32_t *nn_out, float *d2_out)

@@ -388,35 +388,21 @@ int symmicp_ctx_ransac_hypotheses(symmicp_ctx *c, const float *src_xyz, size_t s
 }
 
 // ---- the same three on a context of their own ----
-static int own_context(int device, symmicp_ctx **c)
-{
-    symmicp_config cfg;
-    symmicp_config_default(&cfg);
-    cfg.device = device;
-    return symmicp_create(&cfg, c);
-}
-
 int symmicp_feature_nn(int device, const float *fa, size_t na, const float *fb, size_t nb, int32_t *nn_out, float *d2_out, float *d2_second_out)
 {
     if (!nn_out || features_error(fa, na, fb, nb)) return SYMMICP_ERR_ARG;
-    symmicp_ctx *c = nullptr;
-    int st = own_context(device, &c);
-    if (st != SYMMICP_OK) return st;
-    st = symmicp_ctx_feature_nn(c, fa, na, fb, nb, nn_out, d2_out, d2_second_out);
-    symmicp_destroy(c);
-    return st;
+    return with_own_context(device, [&](symmicp_ctx *c) {
+        return symmicp_ctx_feature_nn(c, fa, na, fb, nb, nn_out, d2_out, d2_second_out);
+    });
 }
 
 int symmicp_feature_correspondences(int device, const float *fa, size_t na, const float *fb, size_t nb, int mutual, float max_ratio,
                                     int32_t *pairs_out, float *d2_out, size_t cap, size_t *count_out)
 {
     if (corr_args_error(fa, na, fb, nb, max_ratio, pairs_out, cap, count_out)) return SYMMICP_ERR_ARG;
-    symmicp_ctx *c = nullptr;
-    int st = own_context(device, &c);
-    if (st != SYMMICP_OK) return st;
-    st = symmicp_ctx_feature_correspondences(c, fa, na, fb, nb, mutual, max_ratio, pairs_out, d2_out, cap, count_out);
-    symmicp_destroy(c);
-    return st;
+    return with_own_context(device, [&](symmicp_ctx *c) {
+        return symmicp_ctx_feature_correspondences(c, fa, na, fb, nb, mutual, max_ratio, pairs_out, d2_out, cap, count_out);
+    });
 }
 
 int symmicp_ransac(int device, const float *src_xyz, size_t src_row_stride, size_t src_col_stride, size_t ns, const float *tgt_xyz,
@@ -424,13 +410,10 @@ int symmicp_ransac(int device, const float *src_xyz, size_t src_row_stride, size
                    float transform16[16], symmicp_ransac_result *result, uint8_t *inlier_mask_out, uint8_t *status_out, int32_t *inliers_out)
 {
     if (!transform16 || !result || ransac_args_error(src_xyz, src_row_stride, src_col_stride, ns, tgt_xyz, tgt_row_stride, tgt_col_stride, nt, pairs, m, cfg)) return SYMMICP_ERR_ARG;
-    symmicp_ctx *c = nullptr;
-    int st = own_context(device, &c);
-    if (st != SYMMICP_OK) return st;
-    st = symmicp_ctx_ransac(c, src_xyz, src_row_stride, src_col_stride, ns, tgt_xyz, tgt_row_stride, tgt_col_stride, nt, pairs, m, cfg, transform16,
-                            result, inlier_mask_out, status_out, inliers_out);
-    symmicp_destroy(c);
-    return st;
+    return with_own_context(device, [&](symmicp_ctx *c) {
+        return symmicp_ctx_ransac(c, src_xyz, src_row_stride, src_col_stride, ns, tgt_xyz, tgt_row_stride, tgt_col_stride, nt, pairs, m, cfg, transform16,
+                                  result, inlier_mask_out, status_out, inliers_out);
+    });
 }
 
 }  // extern "C"

@@ -1,6 +1,8 @@
 // engine_internal.h -- what the host-side translation units of libsymmicp share: the context, its scratch arenas, the environment
 // switches, the RCCL loader and the helpers every entry point uses.
-//   engine.cpp           lifetime, configuration, uploads, index build, set_target / set_source, getters, normals pre-step, statistics
+//   engine.cpp           lifetime, configuration, uploads, index build, set_target / set_source, getters, statistics
+//   engine_cloud_ops.cpp stand-alone cloud operations on a scratch index: normals and k-NN, radius search, FPFH, ISS keypoints, intensity
+//                        gradient; voxel downsampling
 //   engine_loop.cpp      the iteration loop: one pass (run_pass), device-driven runs of passes (run_batch), begin / step / align, result block
 //   engine_exchange.cpp  multi-GPU: RCCL (loaded lazily), shared-memory exchange, communicator entry points
 //   engine_global.cpp    feature matching and RANSAC (symmicp_ctx_feature_nn, symmicp_ctx_feature_correspondences, symmicp_ctx_ransac)
@@ -140,7 +142,7 @@ struct IndexNotes {
 };
 
 // An index with storage of its own, for the reverse search of reciprocal passes: build_index allocates through the context's keep-arena,
-// which belongs to the target (set_target, the k-NN, radius and FPFH entries rewind it), so build_reverse_index points it at this one
+// which belongs to the target (set_target and the ScratchIndex of engine_cloud_ops.cpp rewind it), so build_reverse_index points it at this one
 // for the length of the build.
 struct ReverseIndex {
     Arena keep;
@@ -350,6 +352,15 @@ inline void soa_from_block(float *block, size_t n, CloudSoA &s)
     s.x = block; s.y = block + n; s.z = block + 2 * n; s.nx = block + 3 * n; s.ny = block + 4 * n; s.nz = block + 5 * n;
 }
 
+// a float from its order-preserving uint32 key (launch_bbox, the Morton frame)
+inline float ord2f(uint32_t o)
+{
+    uint32_t u = (o & 0x80000000u) ? (o & 0x7fffffffu) : ~o;
+    float f;
+    std::memcpy(&f, &u, 4);
+    return f;
+}
+
 inline void identity16(float X[16])
 {
     for (int k = 0; k < 16; k++) X[k] = (k % 5 == 0) ? 1.f : 0.f;
@@ -375,9 +386,36 @@ void flush_events(symmicp_ctx *c);
 // [n]; null: the row).  Rewinds the context's scratch arena.  release: back to the state before the first build (the storage is freed).
 int build_reverse_index(symmicp_ctx *c, const CloudSoA &cl, uint32_t n, const uint32_t *labels, ReverseIndex &ri);
 void drop_reverse_index(ReverseIndex &ri, bool release);
+// host strided cloud -> device block of 6 planar arrays, from the scratch arena (temp) or the keep-arena; nrm null: zero normals;
+// centroid: null, or the fp64 mean of xyz in row order.  (This and build_index are shared by two files of the library only: hidden, so
+// the library's dynamic symbols stay what they were.)
+__attribute__((visibility("hidden")))
+int upload_planar(symmicp_ctx *c, const float *xyz, size_t xr, size_t xc, const float *nrm, size_t nr, size_t nc, size_t n, DevBuf<float> &block,
+                  bool temp, double centroid[3]);
+// the index over cl (n points, planar, device memory) into tq / tn and what it allocates through keep_alloc; does not rewind the scratch
+// arena.  The outputs belong to the caller's context as soon as they are set: on failure the caller's free_target() / scope releases them.
+__attribute__((visibility("hidden")))
+int build_index(symmicp_ctx *c, const CloudSoA &cl, uint32_t n, bool want_grid, float4 *tq, float4 *tn, float4 **boxes_out, uint2 **cells_out,
+                TargetIndex *ix_out, int32_t *glevel_out, int32_t *nlevels_out, float4 **onodes_out = nullptr, uint32_t **ctop_out = nullptr,
+                IndexNotes *notes = nullptr);
 // Morton order of a planar cloud, temporaries and result from the context's scratch arena: vals[n] = sorted position -> row (keys_out:
 // null, or it keeps the sorted keys); origin / h0_out: the Morton frame.  SYMMICP_ERR_ARG for non-finite coordinates.
 int morton_order(symmicp_ctx *c, const CloudSoA &cl, uint32_t n, DevBuf<uint32_t> &vals, DevBuf<uint32_t> *keys_out, float origin[3], float *h0_out);
+// A one-shot entry: f(c) on a default context of its own on `device`, destroyed again.  The entry checks its arguments first, so that a
+// bad call returns SYMMICP_ERR_ARG without touching the device.
+template <class F>
+inline int with_own_context(int device, F &&f)
+{
+    symmicp_config cfg;
+    symmicp_config_default(&cfg);
+    cfg.device = device;
+    symmicp_ctx *c = nullptr;
+    int st = symmicp_create(&cfg, &c);
+    if (st != SYMMICP_OK) return st;
+    st = f(c);
+    symmicp_destroy(c);
+    return st;
+}
 // engine_exchange.cpp
 void shm_close(symmicp_ctx *c);
 int shm_exchange(symmicp_ctx *c, double *rec);      // rec[40]: this rank's record in, the sum over ranks out
