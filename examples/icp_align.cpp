@@ -36,7 +36,12 @@
 //     --evaluate D             after the result block, one line with the result's fitness, inlier RMSE and inliers / source points at
 //                              distance D (> 0) on the full clouds: the share of source points with a target point within D
 //     --information            with --evaluate: also the six rows of the 6x6 information matrix (rotation first, about the origin)
-//     --out aligned.pcd        write the source moved by the result (the reference only prints its result)
+//     --sor K:S                statistical outlier removal of both clouds right after loading: a point goes when its mean distance to
+//                              its K nearest neighbours (1 .. 64) exceeds the cloud's mean + S standard deviations
+//     --ror R:M                radius outlier removal of both clouds (after --sor when both are given): a point goes with fewer than
+//                              M other points within R.  Unless --quiet each filter prints one line with the counts before and after
+//     --out aligned.pcd        write the source moved by the result (the reference only prints its result; after --sor / --ror the
+//                              filtered source)
 //     --quiet                  no per-iteration lines
 //   Without file names it registers cat.pcd to cat_out.pcd from the working directory: the reference's own run.
 // Exit code: the symmicp status of the alignment (0 = ok).
@@ -55,7 +60,7 @@
 static int usage(const char *argv0, const char *complaint)
 {
     std::fprintf(stderr, "%s\nusage: %s [--mode quirks|paper|plane|gicp|color] [--color-weight L] [--corr identity|tree] [--iters N] [--threshold D] [--loss none|huber|tukey|cauchy|gm]"
-                 " [--loss-scale S] [--gicp-epsilon E] [--max-dist D] [--trim F] [--one-to-one] [--reciprocal] [--median-factor F] [--scale LEAF:ITERS[:MAXDIST]]... [--init global --fpfh-radius R --ransac-dist D [--ransac-iters H] [--seed S] [--init-voxel L] [--init-keypoints iss --iss-radius R [--iss-nms-radius R2] [--iss-min-neighbors K]]] [--evaluate D [--information]] [--out file.pcd] [--quiet] [source.pcd target.pcd]\n",
+                 " [--loss-scale S] [--gicp-epsilon E] [--max-dist D] [--trim F] [--one-to-one] [--reciprocal] [--median-factor F] [--scale LEAF:ITERS[:MAXDIST]]... [--init global --fpfh-radius R --ransac-dist D [--ransac-iters H] [--seed S] [--init-voxel L] [--init-keypoints iss --iss-radius R [--iss-nms-radius R2] [--iss-min-neighbors K]]] [--evaluate D [--information]] [--sor K:S] [--ror R:M] [--out file.pcd] [--quiet] [source.pcd target.pcd]\n",
                  complaint, argv0);
     return 64;
 }
@@ -82,6 +87,9 @@ int main(int argc, char **argv)
     MyICP::GlobalInit ginit;
     bool evaluate = false, information = false;
     float eval_dist = 0.f;
+    int sor_k = 0, ror_min = 0;              // 0: the filter is off
+    float sor_mul = 0.f, ror_radius = 0.f;
+    bool quiet = false;
     auto number = [&](const char *what, const char *v, float &out) {
         char *end = nullptr;
         out = std::strtof(v, &end);
@@ -211,7 +219,35 @@ int main(int argc, char **argv)
         }
         else if (a == "--information") information = true;
         else if (a == "--out") out_path = value("--out");
-        else if (a == "--quiet") icp.setVerbose(false);
+        else if (a == "--sor") {
+            // K:S
+            const char *v = value("--sor");
+            char *end = nullptr;
+            const long kk = std::strtol(v, &end, 10);
+            bool ok = end != v && *end == ':' && kk >= 1 && kk <= 64;
+            if (ok) {
+                const char *w = end + 1;
+                sor_mul = std::strtof(w, &end);
+                ok = end != w && *end == 0 && std::isfinite(sor_mul);
+            }
+            if (!ok) return usage(argv[0], "--sor needs K:S with 1 <= K <= 64 neighbours and a finite multiplier S");
+            sor_k = (int)kk;
+        }
+        else if (a == "--ror") {
+            // R:M
+            const char *v = value("--ror");
+            char *end = nullptr;
+            ror_radius = std::strtof(v, &end);
+            bool ok = end != v && *end == ':' && std::isfinite(ror_radius) && ror_radius > 0.f;
+            if (ok) {
+                const char *w = end + 1;
+                const long m = std::strtol(w, &end, 10);
+                ok = end != w && *end == 0 && m >= 1 && m <= 0x7fffffffl;
+                ror_min = (int)m;
+            }
+            if (!ok) return usage(argv[0], "--ror needs R:M with a radius R > 0 and M >= 1 neighbours");
+        }
+        else if (a == "--quiet") { icp.setVerbose(false); quiet = true; }
         else if (!a.empty() && a[0] == '-') return usage(argv[0], ("unknown option " + a).c_str());
         else files.push_back(a);
     }
@@ -273,6 +309,16 @@ int main(int argc, char **argv)
     if (color && !icp.haveIntensities()) {
         std::fprintf(stderr, "--mode color needs colours in both files: an `intensity` or an `rgb` field per point\n");
         return SYMMICP_ERR_STATE;
+    }
+    // outlier removal right after loading, the statistical filter first
+    for (int f = 0; f < 2; f++) {
+        if (f == 0 ? sor_k == 0 : ror_min == 0) continue;
+        const size_t ns = icp.GetSrcCloud()->points.size(), nt = icp.GetTgtCloud()->points.size();
+        const int st = f == 0 ? icp.removeStatisticalOutliers(sor_k, sor_mul) : icp.removeRadiusOutliers(ror_radius, ror_min);
+        if (st != SYMMICP_OK) { std::fprintf(stderr, "%s\n", icp.lastError()); return st; }
+        if (!quiet)
+            std::printf("%s outlier removal: source %zu -> %zu, target %zu -> %zu\n", f == 0 ? "statistical" : "radius", ns,
+                        icp.GetSrcCloud()->points.size(), nt, icp.GetTgtCloud()->points.size());
     }
     icp.RegisterSymm();
     const symmicp_result &r = icp.lastResult();

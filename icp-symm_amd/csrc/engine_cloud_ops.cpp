@@ -1,4 +1,4 @@
-// engine_cloud_ops.cpp -- the stand-alone cloud operations of libsymmicp: normals and k-NN, radius search, FPFH, ISS keypoints, the
+// engine_cloud_ops.cpp -- the stand-alone cloud operations of libsymmicp: normals and k-NN, radius search, FPFH, ISS keypoints, outlier removal, the
 // intensity gradient of colored ICP, voxel-grid downsampling.  Each runs on a context the caller owns (symmicp_ctx_*), whose target,
 // source, index and certificates stay as they are, or as a one-shot on a context of its own (with_own_context).
 #include "engine_internal.h"
@@ -54,6 +54,19 @@ private:
     size_t keep_off0 = 0, extra0 = 0;
     bool surf0 = false;
 };
+
+// the host compaction of the outlier filters, with the cap protocol of the ISS entry: the count always, the rows (ascending) when they fit
+template <class Keep>
+int outlier_compact(symmicp_ctx *c, const char *who, size_t n, Keep &&keep, int32_t *rows_out, size_t cap, size_t *count_out)
+{
+    size_t count = 0;
+    for (size_t i = 0; i < n; i++) count += keep(i) ? 1 : 0;
+    *count_out = count;
+    if (count > cap) return fail(c, SYMMICP_ERR_SIZE, std::string(who) + ": " + std::to_string(count) + " kept rows do not fit cap " + std::to_string(cap));
+    size_t at = 0;
+    for (size_t i = 0; i < n; i++) if (keep(i)) rows_out[at++] = (int32_t)i;
+    return SYMMICP_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -307,6 +320,114 @@ int symmicp_iss_keypoints(int device, const float *xyz, size_t row_stride, size_
     if (iss_args_error(xyz, row_stride, col_stride, n, cfg, rows_out, cap, count_out)) return SYMMICP_ERR_ARG;
     return with_own_context(device, [&](symmicp_ctx *c) {
         return symmicp_ctx_iss_keypoints(c, xyz, row_stride, col_stride, n, cfg, rows_out, cap, count_out, saliency_out, neighbors_out);
+    });
+}
+
+// ---- statistical and radius outlier removal (kernels_outlier.hip, kernels_fpfh.hip; DESIGN.md 4, "Outlier removal") -------------------
+// Like the ISS entry above: the cloud's own scratch index and one walk per point (the k-NN mean distance, or the radius count of the
+// radius search).  The per-point values are read back; the statistics and the compaction are O(n), sequential by definition, and
+// run on the host.
+static const char *outlier_args_error(const float *xyz, size_t xr, size_t xc, size_t n, const int32_t *rows_out, size_t cap,
+                                      const size_t *count_out)
+{
+    if (!xyz || !count_out) return "outlier removal: xyz and count_out are required";
+    if (!rows_out && cap > 0) return "outlier removal: rows_out is required when cap > 0";
+    if (n == 0 || n > 0x7fffffffull) return "outlier removal: n must be in 1 .. 2^31 - 1";
+    for (size_t i = 0; i < n; i++)
+        for (int a = 0; a < 3; a++)
+            if (!std::isfinite(xyz[i * xr + a * xc])) return "outlier removal: a coordinate is not finite";
+    return nullptr;
+}
+
+static const char *sor_args_error(const float *xyz, size_t xr, size_t xc, size_t n, int k, float std_mul, const int32_t *rows_out, size_t cap,
+                                  const size_t *count_out)
+{
+    if (!xyz || !count_out) return "statistical_outlier_removal: xyz and count_out are required";
+    if (n == 0 || n > 0x7fffffffull) return "statistical_outlier_removal: n must be in 1 .. 2^31 - 1";
+    if (k < 1 || k > 64 || (size_t)k > n - 1) return "statistical_outlier_removal: k must be in 1 .. 64 and <= n - 1";
+    if (!std::isfinite(std_mul)) return "statistical_outlier_removal: std_mul must be finite";
+    return outlier_args_error(xyz, xr, xc, n, rows_out, cap, count_out);
+}
+
+static const char *ror_args_error(const float *xyz, size_t xr, size_t xc, size_t n, float radius, int min_neighbors, const int32_t *rows_out,
+                                  size_t cap, const size_t *count_out)
+{
+    if (!xyz || !count_out) return "radius_outlier_removal: xyz and count_out are required";
+    if (n == 0 || n > 0x7fffffffull) return "radius_outlier_removal: n must be in 1 .. 2^31 - 1";
+    if (!std::isfinite(radius) || !(radius > 0.f)) return "radius_outlier_removal: radius must be finite and > 0";
+    if (min_neighbors < 1) return "radius_outlier_removal: min_neighbors must be >= 1";
+    return outlier_args_error(xyz, xr, xc, n, rows_out, cap, count_out);
+}
+
+int symmicp_ctx_statistical_outlier_removal(symmicp_ctx *c, const float *xyz, size_t row_stride, size_t col_stride, size_t n, int k, float std_mul,
+                                            int32_t *rows_out, size_t cap, size_t *count_out, double *mean_dist_out, double stats_out[3])
+{
+    if (!c) return SYMMICP_ERR_ARG;
+    if (const char *msg = sor_args_error(xyz, row_stride, col_stride, n, k, std_mul, rows_out, cap, count_out)) return fail(c, SYMMICP_ERR_ARG, msg);
+    std::vector<double> own;
+    double *m = mean_dist_out;
+    {
+        ScratchIndex si;
+        if (int st = si.begin(c, xyz, row_stride, col_stride, nullptr, 0, 0, n, n * 8 + 8192)) return st;
+        DevBuf<double> d_mean;
+        HIP_TRY(c, d_mean.alloc_temp(c->arena, n));
+        launch_knn_mean_dist(si.ix, k, d_mean.p, c->stream);
+        HIP_TRY(c, hipGetLastError());
+        if (!m) { own.resize(n); m = own.data(); }
+        HIP_TRY(c, hipMemcpyAsync(m, d_mean.p, sizeof(double) * n, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        HIP_TRY(c, hipGetLastError());
+    }
+    // PCL's formula, sequentially in row order (this file is built with -ffp-contract=off: nothing here is fused)
+    double s1 = 0.0, s2 = 0.0;
+    for (size_t i = 0; i < n; i++) { s1 = s1 + m[i]; s2 = s2 + m[i] * m[i]; }
+    const double dn = (double)n;
+    const double mu = s1 / dn;
+    const double var = (s2 - s1 * s1 / dn) / (dn - 1.0);
+    const double sd = std::sqrt(var < 0.0 ? 0.0 : var);      // (a NaN variance stays NaN: the threshold then keeps nothing)
+    const double thr = mu + (double)std_mul * sd;
+    if (stats_out) { stats_out[0] = mu; stats_out[1] = sd; stats_out[2] = thr; }
+    return outlier_compact(c, "statistical_outlier_removal", n, [&](size_t i) { return m[i] <= thr; }, rows_out, cap, count_out);
+}
+
+int symmicp_statistical_outlier_removal(int device, const float *xyz, size_t row_stride, size_t col_stride, size_t n, int k, float std_mul,
+                                        int32_t *rows_out, size_t cap, size_t *count_out, double *mean_dist_out, double stats_out[3])
+{
+    if (sor_args_error(xyz, row_stride, col_stride, n, k, std_mul, rows_out, cap, count_out)) return SYMMICP_ERR_ARG;
+    return with_own_context(device, [&](symmicp_ctx *c) {
+        return symmicp_ctx_statistical_outlier_removal(c, xyz, row_stride, col_stride, n, k, std_mul, rows_out, cap, count_out, mean_dist_out,
+                                                       stats_out);
+    });
+}
+
+int symmicp_ctx_radius_outlier_removal(symmicp_ctx *c, const float *xyz, size_t row_stride, size_t col_stride, size_t n, float radius,
+                                       int min_neighbors, int32_t *rows_out, size_t cap, size_t *count_out, int32_t *neighbors_out)
+{
+    if (!c) return SYMMICP_ERR_ARG;
+    if (const char *msg = ror_args_error(xyz, row_stride, col_stride, n, radius, min_neighbors, rows_out, cap, count_out)) return fail(c, SYMMICP_ERR_ARG, msg);
+    std::vector<int32_t> own;
+    int32_t *nb = neighbors_out;
+    {
+        ScratchIndex si;
+        if (int st = si.begin(c, xyz, row_stride, col_stride, nullptr, 0, 0, n, n * 4 + 8192)) return st;
+        DevBuf<int32_t> d_count;
+        HIP_TRY(c, d_count.alloc_temp(c->arena, n));
+        launch_radius_count(si.ix, radius * radius, d_count.p, c->stream);
+        HIP_TRY(c, hipGetLastError());
+        if (!nb) { own.resize(n); nb = own.data(); }
+        HIP_TRY(c, hipMemcpyAsync(nb, d_count.p, sizeof(int32_t) * n, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        HIP_TRY(c, hipGetLastError());
+    }
+    return outlier_compact(c, "radius_outlier_removal", n, [&](size_t i) { return nb[i] >= min_neighbors; }, rows_out, cap, count_out);
+}
+
+int symmicp_radius_outlier_removal(int device, const float *xyz, size_t row_stride, size_t col_stride, size_t n, float radius, int min_neighbors,
+                                   int32_t *rows_out, size_t cap, size_t *count_out, int32_t *neighbors_out)
+{
+    if (ror_args_error(xyz, row_stride, col_stride, n, radius, min_neighbors, rows_out, cap, count_out)) return SYMMICP_ERR_ARG;
+    return with_own_context(device, [&](symmicp_ctx *c) {
+        return symmicp_ctx_radius_outlier_removal(c, xyz, row_stride, col_stride, n, radius, min_neighbors, rows_out, cap, count_out, neighbors_out);
     });
 }
 

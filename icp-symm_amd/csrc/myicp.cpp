@@ -148,6 +148,58 @@ void MyICP::estimateNormals()
 	}
 }
 
+// Outlier removal: the kept rows of both clouds first (an error leaves both as they were), then every per-point array of each cloud
+// compacted in row order.  The point-normal clouds follow only while they still match their clouds row for row.
+int MyICP::removeOutliers(bool statistical, int k, float std_mul, float radius, int min_neighbors)
+{
+	assert(cloud_src && cloud_tgt);
+	removed_src_ = removed_tgt_ = 0;
+	symmicp_ctx *ctx = context();
+	if (!ctx) { error_ = "symmicp_create failed: no usable gfx950 HIP device (there is no CPU fallback)"; return SYMMICP_ERR_HIP; }
+	pcl::PointCloud<PointT> *clouds[2] = {cloud_src.get(), cloud_tgt.get()};
+	std::vector<int32_t> rows[2];
+	for (int s = 0; s < 2; s++) {
+		const size_t n = clouds[s]->points.size();
+		if (n == 0) { error_ = "outlier removal: a cloud is empty"; return SYMMICP_ERR_SIZE; }
+		rows[s].resize(n);
+		size_t count = 0;
+		const float *xyz = &clouds[s]->points[0].x;
+		const size_t fs = sizeof(PointT) / sizeof(float);
+		const int st = statistical ? symmicp_ctx_statistical_outlier_removal(ctx, xyz, fs, 1, n, k, std_mul, rows[s].data(), n, &count, nullptr, nullptr)
+		                           : symmicp_ctx_radius_outlier_removal(ctx, xyz, fs, 1, n, radius, min_neighbors, rows[s].data(), n, &count, nullptr);
+		if (st != SYMMICP_OK) { error_ = symmicp_last_error(ctx); return st; }
+		rows[s].resize(count);
+	}
+	pcl::PointCloud<pcl::PointNormal> *pns[2] = {cloud_pn_src.get(), cloud_pn_tgt.get()};
+	std::vector<float> *ints[2] = {&src_int_, &tgt_int_};
+	for (int s = 0; s < 2; s++) {
+		const size_t n = clouds[s]->points.size(), m = rows[s].size();
+		const bool with_pn = pns[s]->points.size() == n, with_int = ints[s]->size() == n;
+		for (size_t j = 0; j < m; j++) {      // rows ascend: rows[j] >= j, so the copy never reads a slot it has written
+			const size_t i = (size_t)rows[s][j];
+			clouds[s]->points[j] = clouds[s]->points[i];
+			if (with_pn) pns[s]->points[j] = pns[s]->points[i];
+			if (with_int) (*ints[s])[j] = (*ints[s])[i];
+		}
+		clouds[s]->points.resize(m);
+		clouds[s]->width = (uint32_t)m; clouds[s]->height = 1;
+		if (with_pn) { pns[s]->points.resize(m); pns[s]->width = (uint32_t)m; pns[s]->height = 1; }
+		if (with_int) ints[s]->resize(m);
+		(s == 0 ? removed_src_ : removed_tgt_) = n - m;
+	}
+	return SYMMICP_OK;
+}
+
+int MyICP::removeStatisticalOutliers(int k, float std_mul)
+{
+	return removeOutliers(true, k, std_mul, 0.f, 0);
+}
+
+int MyICP::removeRadiusOutliers(float radius, int min_neighbors)
+{
+	return removeOutliers(false, 0, 0.f, radius, min_neighbors);
+}
+
 int MyICP::align(float out4x4[16], const float *guess4x4)
 {
 	assert(cloud_src && cloud_tgt);                                        // myicp.cpp:102

@@ -388,6 +388,11 @@ void launch_iss_saliency(const TargetIndex &ix, float r2, int32_t min_neighbors,
 void launch_iss_nms(const TargetIndex &ix, float r2, int32_t min_neighbors, const float *s_sorted, uint32_t *flag_rows, hipStream_t s);
 void launch_iss_scatter(const uint32_t *flag_rows, const uint32_t *pos_rows, uint32_t n, int32_t *rows_out, hipStream_t s);
 
+// statistical outlier removal (kernels_outlier.hip; symmicp_ctx_statistical_outlier_removal): one thread per sorted point, the box-tree
+// walk pruned by the k-th smallest distance so far (1 <= k <= 64, k <= n - 1; the candidate list lives in LDS sized from k);
+// mean_rows [n] by ORIGINAL row = the fp64 mean of sqrt(d2) over the k nearest other points
+void launch_knn_mean_dist(const TargetIndex &ix, int k, double *mean_rows, hipStream_t s);
+
 // feature matching and RANSAC (kernels_global.hip; symmicp_ctx_feature_nn, symmicp_ctx_ransac).  feature_nn: fa / fb packed [n][33];
 // splits > 1 needs feature_nn_partial_bytes of `partial`.  ransac: pq8 [m][8] = p.xyz, 0, q.xyz, 0 about the pivots; hyp [H][12].
 void launch_feature_nn(const float *fa, uint32_t na, const float *fb, uint32_t nb, int queries_per_thread, uint32_t splits, void *partial,

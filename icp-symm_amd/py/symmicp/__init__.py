@@ -160,6 +160,8 @@ EXPORTS = [
     "symmicp_iss_config_default", "symmicp_iss_keypoints", "symmicp_ctx_iss_keypoints",
     "symmicp_batch_config_default", "symmicp_batch_align", "symmicp_ctx_batch_align",
     "symmicp_information_from_sums", "symmicp_evaluate_registration", "symmicp_ctx_evaluate_registration", "symmicp_evaluate",
+    "symmicp_statistical_outlier_removal", "symmicp_ctx_statistical_outlier_removal",
+    "symmicp_radius_outlier_removal", "symmicp_ctx_radius_outlier_removal",
 ]
 
 _lib = None
@@ -310,6 +312,12 @@ def lib():
     L.symmicp_evaluate_registration.argtypes = [C.c_int] + evl
     L.symmicp_ctx_evaluate_registration.argtypes = [vp] + evl
     L.symmicp_evaluate.argtypes = [vp, fp, C.c_size_t, C.c_float, evp, i32p, fp]
+    sor = [fp, C.c_size_t, C.c_size_t, C.c_size_t, C.c_int, C.c_float, i32p, C.c_size_t, szp, dp, dp]
+    L.symmicp_statistical_outlier_removal.argtypes = [C.c_int] + sor
+    L.symmicp_ctx_statistical_outlier_removal.argtypes = [vp] + sor
+    ror = [fp, C.c_size_t, C.c_size_t, C.c_size_t, C.c_float, C.c_int, i32p, C.c_size_t, szp, i32p]
+    L.symmicp_radius_outlier_removal.argtypes = [C.c_int] + ror
+    L.symmicp_ctx_radius_outlier_removal.argtypes = [vp] + ror
     _lib = L
     return L
 
@@ -637,6 +645,76 @@ def iss_keypoints(xyz, salient_radius, non_max_radius, gamma21=0.975, gamma32=0.
     st, r = _iss_keypoints(lib().symmicp_iss_keypoints, (int(device),), xyz, cfg, return_saliency)
     if st != OK:
         raise SymmIcpError(st, "iss_keypoints")
+    return r
+
+
+def _outlier_cloud(xyz, strides):
+    if strides is None:
+        xyz = _cloud(xyz)
+        return xyz, xyz.shape[0], 3, 1
+    n, xr, xc = strides
+    return np.ascontiguousarray(xyz, np.float32), n, xr, xc
+
+
+def _sor_call(fn, head, xyz, k, std_mul, cap=None, strides=None, want=True):
+    """fn(*head, <the C arguments>) -> (status, rows [cap] int32 or None, count, mean_dist [n] f64 or None, stats [3] f64 = (mu, sd, thr)
+    or None).  cap None: the count only (rows_out == NULL, cap 0).  strides = (n, row stride, col stride) reads xyz as a flat f32 buffer."""
+    xyz, n, xr, xc = _outlier_cloud(xyz, strides)
+    rows = None if cap is None else np.full(max(cap, 1), -1, np.int32)
+    md = np.zeros(max(n, 1), np.float64) if want else None
+    stats = np.zeros(3, np.float64) if want else None
+    dptr = lambda a: None if a is None else a.ctypes.data_as(C.POINTER(C.c_double))
+    count = C.c_size_t(0)
+    st = fn(*head, _fptr(xyz), xr, xc, n, int(k), float(std_mul), None if rows is None else _i32ptr(rows), 0 if cap is None else cap,
+            C.byref(count), dptr(md), dptr(stats))
+    return st, rows, int(count.value), None if md is None else md[:n], stats
+
+
+def _ror_call(fn, head, xyz, radius, min_neighbors, cap=None, strides=None, want=True):
+    """as _sor_call -> (status, rows [cap] int32 or None, count, neighbors [n] int32 or None)"""
+    xyz, n, xr, xc = _outlier_cloud(xyz, strides)
+    rows = None if cap is None else np.full(max(cap, 1), -1, np.int32)
+    nb = np.zeros(max(n, 1), np.int32) if want else None
+    count = C.c_size_t(0)
+    st = fn(*head, _fptr(xyz), xr, xc, n, float(radius), int(min_neighbors), None if rows is None else _i32ptr(rows), 0 if cap is None else cap,
+            C.byref(count), None if nb is None else _i32ptr(nb))
+    return st, rows, int(count.value), None if nb is None else nb[:n]
+
+
+def _remove_statistical_outlier(fn, head, xyz, k, std_mul, return_stats):
+    """one call with cap = n, which always suffices -> (status, rows or dict(rows=, mean_dist=, mu=, sd=, thr=))"""
+    st, rows, count, md, stats = _sor_call(fn, head, xyz, k, std_mul, cap=len(xyz), want=return_stats)
+    if st != OK:
+        return st, None
+    rows = rows[:count].copy()
+    return st, (dict(rows=rows, mean_dist=md, mu=float(stats[0]), sd=float(stats[1]), thr=float(stats[2])) if return_stats else rows)
+
+
+def _remove_radius_outlier(fn, head, xyz, radius, min_neighbors, return_counts):
+    st, rows, count, nb = _ror_call(fn, head, xyz, radius, min_neighbors, cap=len(xyz), want=return_counts)
+    if st != OK:
+        return st, None
+    rows = rows[:count].copy()
+    return st, (dict(rows=rows, neighbors=nb) if return_counts else rows)
+
+
+def remove_statistical_outlier(xyz, k=20, std_mul=2.0, return_stats=False, device=-1):
+    """Statistical outlier removal on the GPU (symmicp_statistical_outlier_removal; include/symmicp.h defines the arithmetic) -> the
+    kept rows [K] int32 in ascending order: those whose mean distance to their k nearest neighbours (1 <= k <= 64) is at most
+    mu + std_mul * sd over the cloud.  With return_stats dict(rows=, mean_dist= [N] f64, mu=, sd=, thr=)."""
+    st, r = _remove_statistical_outlier(lib().symmicp_statistical_outlier_removal, (int(device),), xyz, k, std_mul, return_stats)
+    if st != OK:
+        raise SymmIcpError(st, "remove_statistical_outlier")
+    return r
+
+
+def remove_radius_outlier(xyz, radius, min_neighbors, return_counts=False, device=-1):
+    """Radius outlier removal on the GPU (symmicp_radius_outlier_removal) -> the kept rows [K] int32 in ascending order: those with at
+    least min_neighbors OTHER points within radius (the neighbourhoods of radius_search; PCL and Open3D count the point itself).  With
+    return_counts dict(rows=, neighbors= [N] int32)."""
+    st, r = _remove_radius_outlier(lib().symmicp_radius_outlier_removal, (int(device),), xyz, radius, min_neighbors, return_counts)
+    if st != OK:
+        raise SymmIcpError(st, "remove_radius_outlier")
     return r
 
 
@@ -1236,6 +1314,28 @@ class Engine:
         neighbors); nothing is raised"""
         return _iss_call(self._L.symmicp_ctx_iss_keypoints, (self._h,), xyz, cfg, cap, strides)
 
+    def remove_statistical_outlier(self, xyz, k=20, std_mul=2.0, return_stats=False):
+        """remove_statistical_outlier on this context (symmicp_ctx_statistical_outlier_removal, one call with cap = n)"""
+        st, r = _remove_statistical_outlier(self._L.symmicp_ctx_statistical_outlier_removal, (self._h,), xyz, k, std_mul, return_stats)
+        self._chk(st)
+        return r
+
+    def remove_statistical_outlier_raw(self, xyz, k, std_mul, cap=None, strides=None):
+        """one call of symmicp_ctx_statistical_outlier_removal with a caller-chosen cap (None: rows_out == NULL) -> (status, rows, count,
+        mean_dist, stats); nothing is raised"""
+        return _sor_call(self._L.symmicp_ctx_statistical_outlier_removal, (self._h,), xyz, k, std_mul, cap, strides)
+
+    def remove_radius_outlier(self, xyz, radius, min_neighbors, return_counts=False):
+        """remove_radius_outlier on this context (symmicp_ctx_radius_outlier_removal, one call with cap = n)"""
+        st, r = _remove_radius_outlier(self._L.symmicp_ctx_radius_outlier_removal, (self._h,), xyz, radius, min_neighbors, return_counts)
+        self._chk(st)
+        return r
+
+    def remove_radius_outlier_raw(self, xyz, radius, min_neighbors, cap=None, strides=None):
+        """one call of symmicp_ctx_radius_outlier_removal with a caller-chosen cap (None: rows_out == NULL) -> (status, rows, count,
+        neighbors); nothing is raised"""
+        return _ror_call(self._L.symmicp_ctx_radius_outlier_removal, (self._h,), xyz, radius, min_neighbors, cap, strides)
+
     def feature_nn(self, fa, fb):
         """feature_nn on this context (symmicp_ctx_feature_nn) -> (nn, d2, second)"""
         st, nn, d2, sec = _feature_nn_call(self._L.symmicp_ctx_feature_nn, (self._h,), fa, fb)
@@ -1519,6 +1619,7 @@ class MyICP:
         self.global_result = None
         self._have_src = self._have_tgt = False         # normals supplied by the caller through setInput* (not estimated here)
         self.multistart_results = []
+        self._removed = (0, 0)
 
     def alignMultiStart(self, guesses):
         """one batch on the object's clouds, a problem per guess [B, 4, 4] (Engine.align_multistart with the object's mode, max_iters,
@@ -1717,6 +1818,32 @@ class MyICP:
         self.intensity_tgt = None if intensity is None else _scalar(intensity, self.cloud_tgt.shape[0])
         self.normals_tgt = None if normals is None else _cloud(normals)
         self._have_tgt = normals is not None
+
+    def _filter_clouds(self, keep_rows):
+        """keep_rows(engine, cloud) -> kept rows; edits both clouds, their normals and intensities in place, in row order"""
+        assert self.cloud_src is not None and self.cloud_tgt is not None
+        with Engine(verbose=0) as e:
+            ks, kt = keep_rows(e, self.cloud_src), keep_rows(e, self.cloud_tgt)
+        self._removed = (len(self.cloud_src) - len(ks), len(self.cloud_tgt) - len(kt))
+        pick = lambda a, rows: None if a is None else np.ascontiguousarray(a[rows])
+        self.cloud_src, self.normals_src, self.intensity_src = (pick(a, ks) for a in (self.cloud_src, self.normals_src, self.intensity_src))
+        self.cloud_tgt, self.normals_tgt, self.intensity_tgt = (pick(a, kt) for a in (self.cloud_tgt, self.normals_tgt, self.intensity_tgt))
+        return OK
+
+    def removeStatisticalOutliers(self, k, std_mul):
+        """A one-shot edit of BOTH held clouds, as running PCL's StatisticalOutlierRemoval before RegisterSymm (not a stored option):
+        each cloud is filtered by its own statistics (Engine.remove_statistical_outlier); the points, the normals (supplied ones stay
+        'supplied') and the intensities keep the surviving rows, in row order.  -> status; outliersRemoved() has the counts.  With
+        identity pairing a later align reports ERR_SIZE when the two counts end up unequal, as it does for any unequal clouds."""
+        return self._filter_clouds(lambda e, x: e.remove_statistical_outlier(x, k, std_mul))
+
+    def removeRadiusOutliers(self, radius, min_neighbors):
+        """as removeStatisticalOutliers, with Engine.remove_radius_outlier (at least min_neighbors other points within radius)"""
+        return self._filter_clouds(lambda e, x: e.remove_radius_outlier(x, radius, min_neighbors))
+
+    def outliersRemoved(self):
+        """(source, target) points removed by the last removeStatisticalOutliers / removeRadiusOutliers"""
+        return self._removed
 
     def estimateNormals(self):
         # myicp.cpp:152-172: k = 10, flipped toward the origin.  Point-to-plane uses the target's normals only: in MODE_PLANE the

@@ -151,6 +151,16 @@ public:
 	// every multiStartResults() transform scored on the full clouds at one common distance, in ONE call: out[k] belongs to guess k.
 	// alignMultiStart's own choice of winner does not change.  SYMMICP_ERR_STATE before an alignMultiStart.
 	int evaluateStarts(float max_dist, std::vector<symmicp_evaluation> &out);
+	// Outlier removal (symmicp_ctx_statistical_outlier_removal / symmicp_ctx_radius_outlier_removal, include/symmicp.h): a one-shot
+	// edit of BOTH held clouds, the same as a user running PCL's filter before RegisterSymm -- not a stored option.  Each cloud is
+	// filtered by its own statistics; the point clouds, the point-normal clouds (normals the caller supplied included: they stay
+	// "supplied") and the per-point intensities keep the surviving rows, in row order.  Returns a symmicp_status; on an error
+	// neither cloud is changed.  outliersRemoved reports how many points the last call took from each cloud (either may be null).
+	// With SYMMICP_CORR_IDENTITY a later align() returns SYMMICP_ERR_SIZE if the two counts end up unequal, as it does for any
+	// two clouds of different sizes.
+	int removeStatisticalOutliers(int k, float std_mul);
+	int removeRadiusOutliers(float radius, int min_neighbors);
+	void outliersRemoved(size_t *src, size_t *tgt) const { if (src) *src = removed_src_; if (tgt) *tgt = removed_tgt_; }
 	const char *lastError() const { return error_.c_str(); }
 
 private:
@@ -192,5 +202,7 @@ private:
 	symmicp_result result_;
 	std::vector<symmicp_batch_result> multi_results_;
 	int best_start_ = -1;
+	size_t removed_src_ = 0, removed_tgt_ = 0;
+	int removeOutliers(bool statistical, int k, float std_mul, float radius, int min_neighbors);
 	std::string error_;
 };

@@ -631,6 +631,50 @@ int symmicp_iss_keypoints(int device, const float *xyz, size_t row_stride, size_
                           const symmicp_iss_config *cfg, int32_t *rows_out, size_t cap, size_t *count_out,
                           float *saliency_out, int32_t *neighbors_out);
 
+/* ---- statistical and radius outlier removal (PCL's StatisticalOutlierRemoval / RadiusOutlierRemoval, Open3D's
+ * remove_statistical_outlier / remove_radius_outlier; DESIGN.md 4, "Outlier removal") ------------------------------------------
+ * The rows of a cloud of n points that are NOT stray: the filter a pipeline runs between loading a scan and downsampling,
+ * normals, keypoints and features.  Each filter is defined by its arithmetic; the result is a function of the inputs alone, bit
+ * for bit.
+ * Common.  xyz strided as in symmicp_set_source.  d2(i, j) is the fp32 (dx*dx + dy*dy) + dz*dz, unfused: the distance of
+ *   symmicp_ctx_knn and of the radius search.  A point is never its own neighbour: it is left out by ROW, so a duplicate of it
+ *   (d2 == 0) is a neighbour.
+ * Statistical outlier removal.  1 <= k <= 64, k <= n - 1, std_mul finite.
+ *   D_i = the multiset of the k smallest d2(i, j) over j != i (ties at the k-th value do not matter: only the values enter).
+ *   m_i = ( sum of sqrt((double)d2) over D_i in ascending d2, starting from 0.0 ) / (double)k, in fp64 (mean_dist_out[i]).
+ *   The statistics are PCL's formula, on the host, sequentially in ascending row order, unfused:
+ *     S1 = sum m_i;  S2 = sum m_i * m_i;  mu = S1 / n;  var = (S2 - S1 * S1 / n) / (n - 1);  sd = sqrt(max(var, 0));
+ *     thr = mu + (double)std_mul * sd.                                                  stats_out[3] = {mu, sd, thr}.
+ *   Row i is KEPT iff m_i <= thr.  A NaN threshold keeps nothing; it can arise only when an fp32 d2 overflows (an infinite
+ *   m_i makes var NaN, and max(var, 0) here passes a NaN on).
+ * Radius outlier removal.  radius finite and > 0, min_neighbors >= 1.
+ *   Row i is KEPT iff |N(i)| >= min_neighbors, N(i) exactly the neighbourhood of symmicp_ctx_radius_search: r2 = r * r in
+ *   fp32, members d2 <= r2, the point itself excluded.  neighbors_out[i] = |N(i)|.
+ *   PCL's RadiusOutlierRemoval and Open3D's remove_radius_outlier count the point itself among its neighbours (their radius
+ *   search returns it).  PCL keeps a point with at least min_pts of them: min_neighbors = min_pts - 1 here.  Open3D keeps a
+ *   point with MORE than nb_points of them: min_neighbors = nb_points here.
+ * Output.  rows_out [cap]: the kept rows in ascending order; *count_out their number (required).  SYMMICP_ERR_SIZE when the
+ *   count exceeds cap: *count_out and the per-point arrays (and stats_out) are written, the rows are not -- call again with room
+ *   (rows_out may be NULL with cap == 0 to ask for the count).  mean_dist_out [n], stats_out [3], neighbors_out [n] may be NULL.
+ * SYMMICP_ERR_ARG, all decided on the host before a device is needed: NULL xyz / count_out; NULL rows_out with cap > 0;
+ *   n == 0 or n > 2^31 - 1; k outside 1 .. 64 or above n - 1; std_mul not finite; a radius that is not finite and > 0;
+ *   min_neighbors < 1; non-finite coordinates.
+ * The ctx forms run on the context's stream and arenas: the context's clouds, index, attributes, certificates and states stay
+ * exactly as they were.  A sharded job filters the FULL cloud on every rank (the output is deterministic). */
+int symmicp_ctx_statistical_outlier_removal(symmicp_ctx *ctx, const float *xyz, size_t row_stride, size_t col_stride, size_t n,
+                                            int k, float std_mul, int32_t *rows_out, size_t cap, size_t *count_out,
+                                            double *mean_dist_out, double stats_out[3]);
+/* the same on a context of its own, created on `device` (-1 = current) and destroyed again */
+int symmicp_statistical_outlier_removal(int device, const float *xyz, size_t row_stride, size_t col_stride, size_t n,
+                                        int k, float std_mul, int32_t *rows_out, size_t cap, size_t *count_out,
+                                        double *mean_dist_out, double stats_out[3]);
+int symmicp_ctx_radius_outlier_removal(symmicp_ctx *ctx, const float *xyz, size_t row_stride, size_t col_stride, size_t n,
+                                       float radius, int min_neighbors, int32_t *rows_out, size_t cap, size_t *count_out,
+                                       int32_t *neighbors_out);
+int symmicp_radius_outlier_removal(int device, const float *xyz, size_t row_stride, size_t col_stride, size_t n,
+                                   float radius, int min_neighbors, int32_t *rows_out, size_t cap, size_t *count_out,
+                                   int32_t *neighbors_out);
+
 /* ---- feature matching and RANSAC: global registration from FPFH features ("Feature matching and RANSAC") -------
  * All three run on the context's stream and temporary arena; the context's source, target, index and certificates stay exactly
  * as they were.  A sharded job computes the full result on every rank (the outputs are deterministic).
