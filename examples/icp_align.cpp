@@ -1,10 +1,17 @@
 // examples/icp_align.cpp -- command-line registration of two PCD files on one MI355X through the MyICP class.
 //
 //   icp_align [options] [source.pcd target.pcd]
-//     --mode quirks|paper|plane|gicp|color  arithmetic: the reference as written (default), the paper-correct symmetric form,
+//     --mode quirks|paper|plane|gicp|color|ndt  arithmetic: the reference as written (default), the paper-correct symmetric form,
 //                              point-to-plane (target normals only: the source's are not estimated), plane-to-plane
-//                              (Generalized-ICP, covariances from the normals of both clouds), or colored ICP (point-to-plane rows
-//                              plus intensity rows: both files need an `intensity` or `rgb` field; no --scale levels)
+//                              (Generalized-ICP, covariances from the normals of both clouds), colored ICP (point-to-plane rows
+//                              plus intensity rows: both files need an `intensity` or `rgb` field; no --scale levels), or the
+//                              Normal Distributions Transform (source points against the Gaussians of the target's voxels: no
+//                              normals, no search; needs --ndt-resolution; no --loss, --trim, rejectors, --scale or --init global)
+//     --ndt-resolution L       NDT: the voxel edge, L > 0 (required with --mode ndt)
+//     --ndt-neighbors 1|7      NDT: a point meets its own voxel, or that and its six face neighbours (default 7)
+//     --ndt-min-points N       NDT: voxels with fewer points carry no Gaussian, N >= 3 (default 6)
+//     --ndt-level L:ITERS      NDT: one level of a coarse-to-fine run (repeat it, coarse first): resolution L, at most ITERS
+//                              iterations, each level started from the one before (replaces --ndt-resolution and --iters)
 //     --color-weight L         colored ICP: the weight of the geometric rows, 0 <= L <= 1 (default 0.968; --mode color only)
 //     --gicp-epsilon E         the covariances' eps, 2^-25 < E <= 1: 1 - E must differ from 1 in fp32 (default 1e-3; --mode gicp only)
 //     --corr identity|tree     pairing: by row (default, what the reference does) or exact nearest neighbours
@@ -59,7 +66,7 @@
 
 static int usage(const char *argv0, const char *complaint)
 {
-    std::fprintf(stderr, "%s\nusage: %s [--mode quirks|paper|plane|gicp|color] [--color-weight L] [--corr identity|tree] [--iters N] [--threshold D] [--loss none|huber|tukey|cauchy|gm]"
+    std::fprintf(stderr, "%s\nusage: %s [--mode quirks|paper|plane|gicp|color|ndt] [--ndt-resolution L] [--ndt-neighbors 1|7] [--ndt-min-points N] [--ndt-level L:ITERS]... [--color-weight L] [--corr identity|tree] [--iters N] [--threshold D] [--loss none|huber|tukey|cauchy|gm]"
                  " [--loss-scale S] [--gicp-epsilon E] [--max-dist D] [--trim F] [--one-to-one] [--reciprocal] [--median-factor F] [--scale LEAF:ITERS[:MAXDIST]]... [--init global --fpfh-radius R --ransac-dist D [--ransac-iters H] [--seed S] [--init-voxel L] [--init-keypoints iss --iss-radius R [--iss-nms-radius R2] [--iss-min-neighbors K]]] [--evaluate D [--information]] [--sor K:S] [--ror R:M] [--out file.pcd] [--quiet] [source.pcd target.pcd]\n",
                  complaint, argv0);
     return 64;
@@ -90,6 +97,10 @@ int main(int argc, char **argv)
     int sor_k = 0, ror_min = 0;              // 0: the filter is off
     float sor_mul = 0.f, ror_radius = 0.f;
     bool quiet = false;
+    bool ndt = false, have_ndt_option = false;
+    float ndt_resolution = 0.f;
+    int ndt_neighbors = 7, ndt_min_points = 6;
+    std::vector<MyICP::NdtLevel> ndt_levels;
     auto number = [&](const char *what, const char *v, float &out) {
         char *end = nullptr;
         out = std::strtof(v, &end);
@@ -104,7 +115,9 @@ int main(int argc, char **argv)
         if (a == "--mode") {
             const std::string v = value("--mode");
             color = false;
-            if (v == "quirks") { icp.setMode(SYMMICP_MODE_QUIRKS); quirks = true; gicp = false; }
+            ndt = false;
+            if (v == "ndt") { icp.setMode(SYMMICP_MODE_NDT); quirks = false; gicp = false; ndt = true; }
+            else if (v == "quirks") { icp.setMode(SYMMICP_MODE_QUIRKS); quirks = true; gicp = false; }
             else if (v == "paper") { icp.setMode(SYMMICP_MODE_PAPER); quirks = false; gicp = false; }
             else if (v == "plane") { icp.setMode(SYMMICP_MODE_PLANE); quirks = false; gicp = false; }
             else if (v == "gicp") { icp.setMode(SYMMICP_MODE_GICP); quirks = false; gicp = true; }
@@ -115,6 +128,33 @@ int main(int argc, char **argv)
             if (v == "identity") { icp.setCorrespondence(SYMMICP_CORR_IDENTITY); tree = false; }
             else if (v == "tree") { icp.setCorrespondence(SYMMICP_CORR_TREE); tree = true; }
             else return usage(argv[0], "unknown --corr");
+        } else if (a == "--ndt-resolution") {
+            number("--ndt-resolution", value("--ndt-resolution"), ndt_resolution);
+            if (!(ndt_resolution > 0.f)) return usage(argv[0], "--ndt-resolution needs a length L > 0");
+            have_ndt_option = true;
+        } else if (a == "--ndt-neighbors") {
+            ndt_neighbors = std::atoi(value("--ndt-neighbors"));
+            if (ndt_neighbors != 1 && ndt_neighbors != 7) return usage(argv[0], "--ndt-neighbors needs 1 or 7");
+            have_ndt_option = true;
+        } else if (a == "--ndt-min-points") {
+            ndt_min_points = std::atoi(value("--ndt-min-points"));
+            if (ndt_min_points < 3) return usage(argv[0], "--ndt-min-points needs N >= 3");
+            have_ndt_option = true;
+        } else if (a == "--ndt-level") {
+            const char *v = value("--ndt-level");
+            char *end = nullptr;
+            MyICP::NdtLevel lv{0.f, 0};
+            lv.resolution = std::strtof(v, &end);
+            bool ok = end != v && *end == ':' && std::isfinite(lv.resolution) && lv.resolution > 0.f;
+            if (ok) {
+                const char *w = end + 1;
+                const long it = std::strtol(w, &end, 10);
+                ok = end != w && !*end && it >= 0 && it <= 1000000;
+                lv.max_iters = (int)it;
+            }
+            if (!ok) return usage(argv[0], "--ndt-level needs L:ITERS with L > 0 and ITERS >= 0");
+            ndt_levels.push_back(lv);
+            have_ndt_option = true;
         } else if (a == "--iters") icp.setMaximumIterations(std::atoi(value("--iters")));
         else if (a == "--threshold") icp.setDiffThreshold((float)std::atof(value("--threshold")));
         else if (a == "--loss") {
@@ -253,6 +293,15 @@ int main(int argc, char **argv)
     }
     if (files.empty()) files = {"cat.pcd", "cat_out.pcd"};
     if (files.size() != 2) return usage(argv[0], "expected two PCD files");
+    if (have_ndt_option && !ndt) return usage(argv[0], "--ndt-resolution, --ndt-neighbors, --ndt-min-points and --ndt-level need --mode ndt");
+    if (ndt) {
+        if (ndt_levels.empty() && !(ndt_resolution > 0.f)) return usage(argv[0], "--mode ndt needs --ndt-resolution L (or --ndt-level L:ITERS)");
+        if (loss != SYMMICP_LOSS_NONE || trim < 1.f || one_to_one || reciprocal || median_factor > 0.f)
+            return usage(argv[0], "--mode ndt takes no --loss, --trim, --one-to-one, --reciprocal or --median-factor (its weights are the voxel Gaussians')");
+        if (!levels.empty() || init_global) return usage(argv[0], "--mode ndt runs neither --scale levels (--ndt-level is its coarse-to-fine) nor --init global");
+        icp.setNdt(ndt_levels.empty() ? ndt_resolution : ndt_levels[0].resolution, ndt_neighbors, ndt_min_points);
+        icp.setNdtLevels(ndt_levels);
+    }
     if (loss != SYMMICP_LOSS_NONE) {
         if (quirks) return usage(argv[0], "--loss needs --mode paper, plane or gicp (quirks is the reference as written)");
         if (!have_scale || !(loss_scale > 0.f) || !std::isfinite(loss_scale)) return usage(argv[0], "--loss needs --loss-scale S with S > 0");

@@ -102,6 +102,7 @@ static int check_cfg(const symmicp_config *cfg)
     if (cfg->corr < SYMMICP_CORR_IDENTITY || cfg->corr > SYMMICP_CORR_TREE) return SYMMICP_ERR_ARG;
     if (cfg->apply < SYMMICP_APPLY_DEFAULT || cfg->apply > SYMMICP_APPLY_CUMULATIVE) return SYMMICP_ERR_ARG;
     if (cfg->max_iters < 0) return SYMMICP_ERR_ARG;
+    if (cfg->mode == SYMMICP_MODE_NDT && ndt_config_refusal(*cfg)) return SYMMICP_ERR_ARG;
     return SYMMICP_OK;
 }
 
@@ -145,6 +146,8 @@ int symmicp_create(const symmicp_config *cfg, symmicp_ctx **out)
     for (int k = 0; ok && k < symmicp_ctx::kEvRing * symmicp_ctx::kEvPer; k++) ok = hipEventCreateWithFlags(&c->ev[k], hipEventDisableSystemFence) == hipSuccess;      // timing only: no system-scope cache flush per record
     if (!ok) { symmicp_destroy(c); return SYMMICP_ERR_HIP; }
     c->pkt_fallbacks = c->ticket + 1;
+    symmicp_ndt_config_default(&c->ndt.cfg);
+    symmicp_ndt_gauss((double)c->ndt.cfg.outlier_ratio, &c->ndt.d1, &c->ndt.d2);
     identity16(c->X);
     *out = c;
     return SYMMICP_OK;
@@ -171,6 +174,7 @@ extern "C++" void free_target(symmicp_ctx *c)
     c->ctop = nullptr; c->dbg = nullptr; c->ix = TargetIndex{}; c->tgt_block = nullptr; c->tq = nullptr; c->tn = nullptr; c->boxes = nullptr; c->cells = nullptr; c->onodes = nullptr;
     c->have_index = false; c->n_t = 0;
     c->have_tgt_color = false;
+    c->ndt.map.valid = false; c->ndt.pass_valid = false;
     c->notes = IndexNotes{};
 }
 
@@ -206,6 +210,7 @@ void symmicp_destroy(symmicp_ctx *c)
     hipFree(c->partials); hipFree(c->d_sums); hipFree(c->ticket); hipFree(c->arena.base); hipFree(c->keep.base);
     hipFree(c->rej.keys); hipFree(c->rej.ws); hipFree(c->rej.table);
     hipFree(c->tgt_color); hipFree(c->src_int);
+    c->ndt.map.release();
     drop_reverse_index(c->rej.src_ix, true);
     if (c->h_sums) hipHostFree(c->h_sums);
     hipFree(c->d_loop);
@@ -238,7 +243,15 @@ int symmicp_set_config(symmicp_ctx *c, const symmicp_config *cfg)
         return fail(c, SYMMICP_ERR_ARG, "identity pairs were never searched: no reciprocal correspondences (switch them off first)");
     if (cfg->mode == SYMMICP_MODE_COLOR && c->nranks > 1)
         return fail(c, SYMMICP_ERR_STATE, "SYMMICP_MODE_COLOR runs on single-rank contexts only");
-    if (c->src_no_normals && cfg->mode != SYMMICP_MODE_PLANE)
+    if (cfg->mode == SYMMICP_MODE_NDT) {
+        // (check_cfg has refused min_normal_dot > -1 and the incremental apply)
+        if (const char *msg = ndt_context_refusal(c)) return fail(c, SYMMICP_ERR_ARG, msg);
+        if (c->nranks > 1) return fail(c, SYMMICP_ERR_STATE, "SYMMICP_MODE_NDT runs on single-rank contexts only");
+    }
+    // an NDT context holds a voxel map where the others hold an index, and its source has none of their per-pair arrays
+    if ((cfg->mode == SYMMICP_MODE_NDT) != (c->cfg.mode == SYMMICP_MODE_NDT) && (c->tgt_block || c->src0_block))
+        return fail(c, SYMMICP_ERR_STATE, "the mode cannot change into or out of SYMMICP_MODE_NDT after clouds are set");
+    if (c->src_no_normals && cfg->mode != SYMMICP_MODE_PLANE && cfg->mode != SYMMICP_MODE_NDT)
         return fail(c, SYMMICP_ERR_STATE, "the source was set without normals: only SYMMICP_MODE_PLANE can run on it");
     if (c->src_no_normals && cfg->min_normal_dot > -1.0f)
         return fail(c, SYMMICP_ERR_ARG, "min_normal_dot needs source normals (the source was set without them)");
@@ -262,6 +275,7 @@ int symmicp_set_robust_loss(symmicp_ctx *c, int loss, float scale)
     if (!c) return SYMMICP_ERR_ARG;
     if (!loss_args_ok(loss, scale)) return fail(c, SYMMICP_ERR_ARG, "robust loss: unknown loss, or scale not finite and > 0");
     if (loss != SYMMICP_LOSS_NONE && c->cfg.mode == SYMMICP_MODE_QUIRKS) return fail(c, SYMMICP_ERR_ARG, "QUIRKS takes no robust loss");
+    if (loss != SYMMICP_LOSS_NONE && ndt_mode(c)) return fail(c, SYMMICP_ERR_ARG, "SYMMICP_MODE_NDT takes no robust loss");
 #if defined(RS_STAMPS) || defined(RS_STAMPS2)
     if (loss != SYMMICP_LOSS_NONE) return fail(c, SYMMICP_ERR_ARG, "a build with RS_STAMPS keeps its stamps in slots 37..39: no robust loss");
 #endif
@@ -284,6 +298,7 @@ int symmicp_set_trim_fraction(symmicp_ctx *c, float fraction)
     if (!c) return SYMMICP_ERR_ARG;
     if (!(fraction > 0.f && fraction <= 1.f)) return fail(c, SYMMICP_ERR_ARG, "trim fraction: 0 < fraction <= 1");      // (NaN fails both)
     if (fraction < 1.f && c->cfg.mode == SYMMICP_MODE_QUIRKS) return fail(c, SYMMICP_ERR_ARG, "QUIRKS takes no trim fraction below 1");
+    if (fraction < 1.f && ndt_mode(c)) return fail(c, SYMMICP_ERR_ARG, "SYMMICP_MODE_NDT takes no trim fraction below 1");
     if (fraction < 1.f && c->nranks > 1) return fail(c, SYMMICP_ERR_STATE, "trimming needs a quantile over all ranks: single-rank contexts only");
     if (fraction < 1.f && c->rej.median()) return fail(c, SYMMICP_ERR_ARG, "a trim fraction below 1 and a median factor exclude each other (set the factor to 0 first)");
     c->rej.trim_frac = fraction;
@@ -312,6 +327,7 @@ int symmicp_set_one_to_one(symmicp_ctx *c, int on)
 {
     if (!c) return SYMMICP_ERR_ARG;
     if (on && c->cfg.mode == SYMMICP_MODE_QUIRKS) return fail(c, SYMMICP_ERR_ARG, "QUIRKS takes no one-to-one rejector");
+    if (on && ndt_mode(c)) return fail(c, SYMMICP_ERR_ARG, "SYMMICP_MODE_NDT takes no one-to-one rejector");
     if (on && c->nranks > 1) return fail(c, SYMMICP_ERR_STATE, "the one-to-one claim needs a minimum over all ranks: single-rank contexts only");
     c->rej.one_to_one = on != 0;
     return SYMMICP_OK;
@@ -329,6 +345,7 @@ int symmicp_set_median_factor(symmicp_ctx *c, float factor)
     if (!c) return SYMMICP_ERR_ARG;
     if (!(factor == 0.f || (std::isfinite(factor) && factor > 0.f))) return fail(c, SYMMICP_ERR_ARG, "median factor: 0 (off), or finite and > 0");
     if (factor > 0.f && c->cfg.mode == SYMMICP_MODE_QUIRKS) return fail(c, SYMMICP_ERR_ARG, "QUIRKS takes no median-distance rejector");
+    if (factor > 0.f && ndt_mode(c)) return fail(c, SYMMICP_ERR_ARG, "SYMMICP_MODE_NDT takes no median-distance rejector");
     if (factor > 0.f && c->nranks > 1) return fail(c, SYMMICP_ERR_STATE, "the median needs a quantile over all ranks: single-rank contexts only");
     if (factor > 0.f && c->rej.trims()) return fail(c, SYMMICP_ERR_ARG, "a median factor and a trim fraction below 1 exclude each other (set the fraction to 1 first)");
     c->rej.med_factor = factor == 0.f ? 0.f : factor;      // (-0 is off too)
@@ -358,6 +375,7 @@ int symmicp_set_reciprocal(symmicp_ctx *c, int on)
 {
     if (!c) return SYMMICP_ERR_ARG;
     if (on && c->cfg.mode == SYMMICP_MODE_QUIRKS) return fail(c, SYMMICP_ERR_ARG, "QUIRKS takes no reciprocal correspondences");
+    if (on && ndt_mode(c)) return fail(c, SYMMICP_ERR_ARG, "SYMMICP_MODE_NDT takes no reciprocal correspondences");
     if (on && c->cfg.corr == SYMMICP_CORR_IDENTITY) return fail(c, SYMMICP_ERR_ARG, "identity pairs were never searched: no reciprocal correspondences");
     if (on && c->nranks > 1) return fail(c, SYMMICP_ERR_STATE, "reciprocal correspondences need the claim and the source index over all ranks: single-rank contexts only");
     c->rej.reciprocal = on != 0;
@@ -828,7 +846,8 @@ extern "C++" int build_reverse_index(symmicp_ctx *c, const CloudSoA &cl, uint32_
 int symmicp_set_target(symmicp_ctx *c, const float *xyz, size_t xr, size_t xc, const float *nrm, size_t nr, size_t nc, size_t n)
 {
     if (!c) return SYMMICP_ERR_ARG;
-    if (!xyz || !nrm) return fail(c, SYMMICP_ERR_ARG, "null target cloud (myicp.cpp:102 assert)");
+    if (!xyz || (!nrm && !ndt_mode(c))) return fail(c, SYMMICP_ERR_ARG, "null target cloud (myicp.cpp:102 assert)");
+    if (!nrm) nr = nc = 0;
     if (n == 0 || n > 0x7fffffffull) return fail(c, SYMMICP_ERR_SIZE, "target size out of range");
     HIP_TRY(c, hipSetDevice(c->device));
     const double t0 = now_s();
@@ -855,6 +874,14 @@ int symmicp_set_target(symmicp_ctx *c, const float *xyz, size_t xr, size_t xc, c
     c->n_t = (uint32_t)n;
     for (int k = 0; k < 3; k++) c->pivot[k] = (float)cen[k];
     c->st.upload_ms += (now_s() - t0) * 1e3;
+    if (ndt_mode(c)) {
+        // NDT reads no index and no pair records: the voxel map over the planar copy (cfg.corr is not read in this mode)
+        const double t1 = now_s();
+        st = ndt_build_target_map(c);
+        if (st != SYMMICP_OK) { free_target(c); return st; }
+        c->st.build_ms = (now_s() - t1) * 1e3;
+        return SYMMICP_OK;
+    }
     if (c->cfg.corr == SYMMICP_CORR_IDENTITY) return SYMMICP_OK;
 
     const double t1 = now_s();
@@ -889,7 +916,8 @@ int symmicp_set_source(symmicp_ctx *c, const float *xyz, size_t xr, size_t xc, c
 {
     if (!c) return SYMMICP_ERR_ARG;
     if (!xyz) return fail(c, SYMMICP_ERR_ARG, "null source cloud (myicp.cpp:102 assert)");
-    if (!nrm && c->cfg.mode != SYMMICP_MODE_PLANE) return fail(c, SYMMICP_ERR_ARG, "null source normals (only SYMMICP_MODE_PLANE runs without them)");
+    if (!nrm && c->cfg.mode != SYMMICP_MODE_PLANE && !ndt_mode(c))
+        return fail(c, SYMMICP_ERR_ARG, "null source normals (only SYMMICP_MODE_PLANE and SYMMICP_MODE_NDT run without them)");
     if (!nrm && c->cfg.min_normal_dot > -1.0f) return fail(c, SYMMICP_ERR_ARG, "min_normal_dot needs source normals");
     if (!nrm) nr = nc = 0;
     if (n == 0 || n > 0x7fffffffull) return fail(c, SYMMICP_ERR_SIZE, "source size out of range");
@@ -914,8 +942,10 @@ int symmicp_set_source(symmicp_ctx *c, const float *xyz, size_t xr, size_t xc, c
     CloudSoA fs;
     soa_from_block(full.p, nu, fs);
     const uint32_t nl = bc > 0 ? (uint32_t)bc : 1;
-    const bool sorted = c->cfg.corr != SYMMICP_CORR_IDENTITY && c->cfg.sort_source;
-    const bool tree = c->cfg.corr == SYMMICP_CORR_TREE, brute = c->cfg.corr == SYMMICP_CORR_BRUTE;
+    // (NDT: cfg.corr is not read; the share is sorted as BRUTE / TREE sort it and carries none of their per-pair arrays)
+    const bool ndt = ndt_mode(c);
+    const bool sorted = (ndt || c->cfg.corr != SYMMICP_CORR_IDENTITY) && c->cfg.sort_source;
+    const bool tree = !ndt && c->cfg.corr == SYMMICP_CORR_TREE, brute = !ndt && c->cfg.corr == SYMMICP_CORR_BRUTE;
     // every per-source array in ONE allocation (a hipFree costs ~100 us, and a tracker calls this once per frame)
     const uint32_t cap = shard_capacity(nl);
     const size_t per_list = (size_t)kShards * cap, ncount = (size_t)kShards * kShardStride;
@@ -1077,6 +1107,17 @@ int symmicp_get_correspondences(symmicp_ctx *c, int32_t *idx, float *d2, size_t 
     HIP_TRY(c, d_d2.alloc_temp(c->arena, need));
     HIP_TRY(c, hipMemsetAsync(d_idx.p, 0xFF, sizeof(int32_t) * need, c->stream));
     HIP_TRY(c, hipMemsetAsync(d_d2.p, 0, sizeof(float) * need, c->stream));
+    if (ndt_mode(c)) {
+        // the map row of every point's own cell at the last pass's transform, and d2 to that voxel's mean
+        NdtPassArgs na;
+        ndt_pass_args(c, c->X, na);
+        launch_ndt_corr(na, c->src_order, d_idx.p, d_d2.p, c->stream);
+        if (idx) HIP_TRY(c, hipMemcpyAsync(idx, d_idx.p, sizeof(int32_t) * need, hipMemcpyDeviceToHost, c->stream));
+        if (d2) HIP_TRY(c, hipMemcpyAsync(d2, d_d2.p, sizeof(float) * need, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        HIP_TRY(c, hipGetLastError());
+        return SYMMICP_OK;
+    }
     const int mode = c->cfg.corr == SYMMICP_CORR_IDENTITY ? 0 : (c->cfg.corr == SYMMICP_CORR_BRUTE ? 1 : 2);
     if (mode == 0 && d2) {
         // the identity pass streams without storing distances: evaluate them now from the current source positions

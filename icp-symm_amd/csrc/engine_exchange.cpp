@@ -66,6 +66,7 @@ static int refuse_sharding(symmicp_ctx *c, int nranks)
     if (c->rej.one_to_one || c->rej.median()) return fail(c, SYMMICP_ERR_STATE, "a context with the one-to-one or the median-distance rejector cannot be sharded: the claim and the median span all ranks");
     if (c->rej.reciprocal) return fail(c, SYMMICP_ERR_STATE, "a context with reciprocal correspondences cannot be sharded: the claim and the source index span all ranks");
     if (c->cfg.mode == SYMMICP_MODE_COLOR) return fail(c, SYMMICP_ERR_STATE, "a SYMMICP_MODE_COLOR context cannot be sharded");
+    if (c->cfg.mode == SYMMICP_MODE_NDT) return fail(c, SYMMICP_ERR_STATE, "a SYMMICP_MODE_NDT context cannot be sharded");
     return SYMMICP_OK;
 }
 

@@ -9,6 +9,7 @@
 //   engine_debug.cpp     SYMMICP_DEBUG_COUNTERS / SYMMICP_DEBUG_TRACE dumps
 //   engine_probe.cpp     test entries: read-back of the target index and the source share, the sort and the scan on caller arrays
 //   engine_eval.cpp      registration evaluation (symmicp_evaluate_registration, symmicp_evaluate, symmicp_information_from_sums)
+//   engine_ndt.cpp       SYMMICP_MODE_NDT: configuration, Gauss constants, the voxel map (build, read-back, symmicp_ctx_ndt_map), pass arguments
 #pragma once
 #include <hip/hip_runtime.h>
 #include <dlfcn.h>
@@ -190,6 +191,33 @@ struct Rejectors {
     static size_t table_words(size_t n_t, bool with_recip_tail) { return (n_t ? n_t : 1) + (with_recip_tail ? kRecipTailWords : 0); }
 };
 
+// The voxel map of SYMMICP_MODE_NDT in device memory (kernels_ndt.hip): own allocations that only grow, kept for the next target
+struct NdtMap {
+    float4 *rec = nullptr;               // [m][4]
+    double *cov = nullptr;               // [m][6]
+    uint32_t *key = nullptr;             // [m]
+    unsigned long long *table = nullptr;
+    size_t rec_cap = 0, cov_cap = 0, key_cap = 0, table_cap = 0;
+    uint32_t m = 0;
+    NdtGrid g{};                         // what the kernels read of it
+    int32_t dims[3] = {0, 0, 0};
+    bool valid = false;
+    void release()
+    {
+        hipFree(rec); hipFree(cov); hipFree(key); hipFree(table);
+        *this = NdtMap{};
+    }
+};
+// NDT on a context: the configuration, the constants derived from it, the target's map and what the most recent pass left
+struct NdtState {
+    symmicp_ndt_config cfg{};
+    double d1 = 0.0, d2 = 0.0;           // symmicp_ndt_gauss(cfg.outlier_ratio)
+    NdtMap map;
+    bool pass_valid = false;
+    double score = 0.0;
+    uint64_t items = 0;
+};
+
 struct symmicp_ctx {
     Switches sw;                     // environment switches as they stood at symmicp_create
     Arena arena;                     // temporaries of one public call
@@ -208,6 +236,7 @@ struct symmicp_ctx {
     float *src_int = nullptr;
     size_t tgt_color_cap = 0, src_int_cap = 0;
     bool have_tgt_color = false, have_src_int = false;
+    NdtState ndt;                    // SYMMICP_MODE_NDT: configuration, the target's voxel map, the last pass's score
     Rejectors rej;                   // trim fraction, one-to-one, median distance, reciprocal: settings, buffers, the last pass's result
     int device = 0;
     hipStream_t stream = nullptr;
@@ -416,6 +445,15 @@ inline int with_own_context(int device, F &&f)
     symmicp_destroy(c);
     return st;
 }
+// engine_ndt.cpp
+inline bool ndt_mode(const symmicp_ctx *c) { return c->cfg.mode == SYMMICP_MODE_NDT; }
+// what keeps a configuration out of NDT (null: nothing): min_normal_dot and the incremental apply; and what keeps a context out of it
+const char *ndt_config_refusal(const symmicp_config &cfg);
+const char *ndt_context_refusal(const symmicp_ctx *c);
+// the map over the context's planar target (c->tgt, c->n_t) into c->ndt.map; rewinds the scratch arena
+int ndt_build_target_map(symmicp_ctx *c);
+// the arguments of a pass (or of the correspondence read-back) at the cumulative transform X
+void ndt_pass_args(const symmicp_ctx *c, const float X[16], NdtPassArgs &a);
 // engine_exchange.cpp
 void shm_close(symmicp_ctx *c);
 int shm_exchange(symmicp_ctx *c, double *rec);      // rec[40]: this rank's record in, the sum over ranks out

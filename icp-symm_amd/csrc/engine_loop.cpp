@@ -128,6 +128,9 @@ static int run_pass(symmicp_ctx *c, const float Xapply[16], bool from_cur, bool 
     c->rej.invalidate();
     fill_pass_args(c, a, rej, Xapply, from_cur, writeback, first);
     const bool rejecting = pass_rejects(a);
+    // (NDT: cfg.corr is not read -- no search, no work list, no rejector)
+    const bool ndt = ndt_mode(c);
+    const bool tree_pass = !ndt && c->cfg.corr == SYMMICP_CORR_TREE;
     int blocks = (int)((c->n_loc + kPassThreads - 1) / kPassThreads);
     int cap = c->sw.pass_blocks;
     if (cap > 8192) cap = 8192;
@@ -146,7 +149,18 @@ static int run_pass(symmicp_ctx *c, const float Xapply[16], bool from_cur, bool 
         c->ev_weight[c->ev_used] = 1;
     }
     // (in per-kernel mode the split launcher records ev[0] itself)
-    if (ev && !(c->timing == 2 && c->cfg.corr == SYMMICP_CORR_TREE)) hipEventRecord(ev[0], c->stream);
+    if (ev && !(c->timing == 2 && tree_pass)) hipEventRecord(ev[0], c->stream);
+    if (ndt) {
+        // one accumulating kernel over (point, voxel) items, its grid capped like the others' (2 blocks per CU)
+        const int acc_cap = c->sw.acc_blocks;
+        const int nb_all = (int)((c->n_loc + kPassThreads - 1) / kPassThreads);
+        blocks = nb_all < acc_cap ? nb_all : acc_cap;
+        if (blocks < 1) blocks = 1;
+        c->pass_blocks = blocks;
+        NdtPassArgs na;
+        ndt_pass_args(c, Xapply, na);
+        launch_pass_ndt(na, blocks, c->stream);
+    } else
     switch (c->cfg.corr) {
     case SYMMICP_CORR_IDENTITY: {
         // 16-byte column loads need every planar column (length n_loc / n_t) and the shard offset to keep 16-B alignment
@@ -212,7 +226,7 @@ static int run_pass(symmicp_ctx *c, const float Xapply[16], bool from_cur, bool 
         const unsigned long long seq = ++c->seq;
         volatile unsigned long long *flag = reinterpret_cast<volatile unsigned long long *>(c->h_sums + kNSum);
         launch_final_reduce(c->partials, blocks, c->d_sums, c->comm ? nullptr : c->h_sums_dev, c->ticket, seq,
-                            c->cfg.corr == SYMMICP_CORR_TREE ? c->wl_count : nullptr, keep_nonempty, c->stream);
+                            tree_pass ? c->wl_count : nullptr, keep_nonempty, c->stream);
         if (c->comm) {
             if (ev) { hipEventRecord(ev[6], c->stream); c->ev_coll[c->ev_used] = 1; }
             int r = g_rccl.AllReduce(c->d_sums, c->d_sums, kNSum, kNcclFloat64, kNcclSum, c->comm, c->stream);
@@ -227,11 +241,11 @@ static int run_pass(symmicp_ctx *c, const float Xapply[16], bool from_cur, bool 
     if (int st = reduce_and_wait(optimistic ? 1 : 0)) return st;
     if (c->shm.slots) { if (int st = shm_exchange(c, c->h_sums)) return st; }
     // length of the work list (summed over ranks by the exchange, so every rank takes the same decision)
-    if (c->cfg.corr == SYMMICP_CORR_TREE && c->h_sums[kNSum - 1] >= kListDropped)
+    if (tree_pass && c->h_sums[kNSum - 1] >= kListDropped)
         return fail(c, SYMMICP_ERR_HIP, "a work-list shard overflowed: appends were dropped (internal capacity error)");
-    long long list_len = (c->cfg.corr == SYMMICP_CORR_TREE) ? (long long)c->h_sums[kNSum - 1] : -1;
+    long long list_len = tree_pass ? (long long)c->h_sums[kNSum - 1] : -1;
     c->last_uncertified = c->last_scans = -1;
-    if (c->cfg.corr == SYMMICP_CORR_TREE && !first) {
+    if (tree_pass && !first) {
         // (slot 38: the pairs searched + kScanUnit x those that reached a scan, k_final_reduce)
         const double sr = c->h_sums[kNSum - 2], sc = std::floor(sr / kScanUnit);
         c->last_uncertified = (long long)(sr - sc * kScanUnit);
@@ -254,11 +268,16 @@ static int run_pass(symmicp_ctx *c, const float Xapply[16], bool from_cur, bool 
     if (c->dbg_trace && first) dump_packet_trace(c);
     if (c->ix.dbg) print_pass_counters(c, first, list_len);
     std::memcpy(c->last.s, c->h_sums, sizeof(double) * kNSum);
-    if (c->cfg.corr == SYMMICP_CORR_TREE) c->last.s[kNSum - 1] = c->last.s[kNSum - 2] = 0.0;      // those slots carried the list length and the number of searched pairs, not sums
+    if (tree_pass) c->last.s[kNSum - 1] = c->last.s[kNSum - 2] = 0.0;      // those slots carried the list length and the number of searched pairs, not sums
     c->last_list_len = list_len;
     // the packet first pass has no work list; the pass after it (the cloud has just moved by its whole misalignment) always has one:
     // -2 = "expect a list" (no optimistic skip of the walk, which would only be repaired; a mid-sized walk grid)
-    if (first && c->cfg.corr == SYMMICP_CORR_TREE && c->target_surface_like) c->last_list_len = -2;
+    if (first && tree_pass && c->target_surface_like) c->last_list_len = -2;
+    if (ndt) {
+        c->ndt.score = -c->ndt.d1 * c->last.s[34];
+        c->ndt.items = (uint64_t)c->last.s[37];
+        c->ndt.pass_valid = true;
+    }
     c->st.passes++;
     return SYMMICP_OK;
 }
@@ -544,6 +563,12 @@ static int run_batch(symmicp_ctx *c, int want, float *diffs_before, int *n_done,
 static int check_ready(symmicp_ctx *c)
 {
     if (!c->tgt_block || !c->src0_block) return fail(c, SYMMICP_ERR_STATE, "source and target must be set first (myicp.cpp:102)");
+    if (ndt_mode(c)) {
+        // (cfg.corr is not read: none of the rules below applies)
+        if (c->nranks > 1) return fail(c, SYMMICP_ERR_STATE, "SYMMICP_MODE_NDT runs on single-rank contexts only");
+        if (!c->ndt.map.valid) return fail(c, SYMMICP_ERR_STATE, "the target's NDT map is missing");
+        return SYMMICP_OK;
+    }
     if (c->cfg.corr == SYMMICP_CORR_IDENTITY && c->n_s_total != c->n_t)
         return fail(c, SYMMICP_ERR_SIZE, "identity pairing needs N_s == N_t (func.cpp:21)");
     if (c->cfg.corr == SYMMICP_CORR_TREE && !c->have_index) return fail(c, SYMMICP_ERR_STATE, "target index missing");
@@ -563,7 +588,7 @@ static void fill_iter(symmicp_ctx *c, symmicp_iter_result *out, int status, floa
     out->iter = c->iters;
     out->diff = (float)c->last.s[33];
     out->rcond = rcond;
-    out->pairs = c->last.s[c->loss != SYMMICP_LOSS_NONE ? 37 : 34];      // (with a robust loss slot 34 is the sum of the weights)
+    out->pairs = c->last.s[(c->loss != SYMMICP_LOSS_NONE || ndt_mode(c)) ? 37 : 34];      // (with a robust loss, and in NDT, slot 34 is the sum of the weights)
     if (incr) std::memcpy(out->increment, incr, sizeof(float) * 16); else identity16(out->increment);
     out->sums = c->last;
 }

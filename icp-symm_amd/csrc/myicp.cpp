@@ -26,13 +26,16 @@ MyICP::~MyICP()
 // arenas and the loaded code objects.  The correspondence kind decides device layouts, so changing it means a new context.
 symmicp_ctx *MyICP::context()
 {
-	if (ctx_ && ctx_corr_ != (int)corr_) { symmicp_destroy(ctx_); ctx_ = nullptr; }
+	const bool ndt = mode_ == SYMMICP_MODE_NDT;      // (the mode cannot change into or out of NDT on a context that holds clouds)
+	if (ctx_ && (ctx_corr_ != (int)corr_ || ctx_ndt_ != ndt)) { symmicp_destroy(ctx_); ctx_ = nullptr; }
 	if (!ctx_) {
 		symmicp_config cfg;
 		symmicp_config_default(&cfg);
 		cfg.corr = corr_;
+		if (ndt) cfg.mode = SYMMICP_MODE_NDT;
 		if (symmicp_create(&cfg, &ctx_) != SYMMICP_OK) { ctx_ = nullptr; return nullptr; }
 		ctx_corr_ = (int)corr_;
+		ctx_ndt_ = ndt;
 		ctx_no_src_normals_ = false;
 	}
 	return ctx_;
@@ -203,6 +206,7 @@ int MyICP::removeRadiusOutliers(float radius, int min_neighbors)
 int MyICP::align(float out4x4[16], const float *guess4x4)
 {
 	assert(cloud_src && cloud_tgt);                                        // myicp.cpp:102
+	if (mode_ == SYMMICP_MODE_NDT) return alignNdt(out4x4, guess4x4);       // (no normals pre-step, no index)
 	const bool source_normals = mode_ != SYMMICP_MODE_PLANE || have_src_normals_;
 	if (ctx_ && ctx_no_src_normals_ && mode_ != SYMMICP_MODE_PLANE) { symmicp_destroy(ctx_); ctx_ = nullptr; }   // (it would refuse the mode)
 	symmicp_ctx *ctx = context();
@@ -274,6 +278,67 @@ int MyICP::align(float out4x4[16], const float *guess4x4)
 	if (result_.iters > 0 || st == SYMMICP_OK) std::memcpy(transform_, result_.transform, sizeof(transform_));
 	if (out4x4) std::memcpy(out4x4, transform_, sizeof(transform_));
 	return st;
+}
+
+// SYMMICP_MODE_NDT: the clouds as they are (no normals), the options the mode refuses applied so that the library says so, then one
+// alignment per level -- symmicp_set_ndt, symmicp_set_config (the level's iterations), symmicp_align from the level before.
+int MyICP::alignNdt(float out4x4[16], const float *guess4x4)
+{
+	auto done = [&](int st) {
+		if (st != SYMMICP_OK) result_.status = st;
+		if (out4x4) std::memcpy(out4x4, transform_, sizeof(transform_));
+		return st;
+	};
+	level_results_.clear();
+	symmicp_ctx *ctx = context();
+	if (!ctx) { error_ = "symmicp_create failed: no usable gfx950 HIP device (there is no CPU fallback)"; return done(SYMMICP_ERR_HIP); }
+	if (!levels_.empty() || have_global_) {
+		error_ = "SYMMICP_MODE_NDT runs neither voxel levels (setNdtLevels is its coarse-to-fine) nor the global initialisation";
+		return done(SYMMICP_ERR_ARG);
+	}
+	if (cloud_src->points.empty() || cloud_tgt->points.empty()) { error_ = "a cloud is empty"; return done(SYMMICP_ERR_SIZE); }
+	std::vector<NdtLevel> levels = ndt_levels_;
+	if (levels.empty()) levels.push_back(NdtLevel{ndt_resolution_, max_iters});
+	symmicp_config cfg;
+	symmicp_config_default(&cfg);
+	cfg.mode = SYMMICP_MODE_NDT; cfg.corr = corr_; cfg.diff_threshold = diff_threshold;
+	cfg.max_corr_dist = max_corr_dist_;
+	cfg.max_iters = levels[0].max_iters; cfg.verbose = 0;
+	symmicp_ndt_config ncfg;
+	symmicp_ndt_config_default(&ncfg);
+	ncfg.resolution = levels[0].resolution; ncfg.neighbors = ndt_neighbors_; ncfg.min_points = ndt_min_points_;
+	int st = symmicp_set_config(ctx, &cfg);
+	if (st == SYMMICP_OK) st = symmicp_set_trim_fraction(ctx, trim_fraction_);        // ERR_ARG below 1: NDT takes none of these
+	if (st == SYMMICP_OK) st = symmicp_set_one_to_one(ctx, one_to_one_ ? 1 : 0);
+	if (st == SYMMICP_OK) st = symmicp_set_reciprocal(ctx, reciprocal_ ? 1 : 0);
+	if (st == SYMMICP_OK) st = symmicp_set_median_factor(ctx, median_factor_);
+	if (st == SYMMICP_OK) st = symmicp_set_robust_loss(ctx, loss_, loss_scale_);
+	if (st == SYMMICP_OK) st = symmicp_set_ndt(ctx, &ncfg);                           // ERR_ARG: setNdt's values
+	const size_t fs = sizeof(PointT) / sizeof(float);
+	if (st == SYMMICP_OK) st = symmicp_set_target(ctx, &cloud_tgt->points[0].x, fs, 1, nullptr, 0, 0, cloud_tgt->points.size());
+	if (st == SYMMICP_OK) st = symmicp_set_source(ctx, &cloud_src->points[0].x, fs, 1, nullptr, 0, 0, cloud_src->points.size());
+	if (st != SYMMICP_OK) { error_ = symmicp_last_error(ctx); return done(st); }
+	float prev[16];                       // (symmicp_align clears result_ before it reads its guess: the level before is kept apart)
+	const float *guess = guess4x4;
+	for (size_t k = 0; k < levels.size(); k++) {
+		if (k) {
+			ncfg.resolution = levels[k].resolution;
+			st = symmicp_set_ndt(ctx, &ncfg);
+		}
+		if (verbose_ && !ndt_levels_.empty())
+			std::printf("NDT level %zu/%zu: resolution %g, %d iterations\n", k + 1, levels.size(), (double)levels[k].resolution, levels[k].max_iters);
+		cfg.max_iters = levels[k].max_iters;
+		cfg.verbose = (verbose_ && k + 1 == levels.size()) ? 1 : 0;
+		if (st == SYMMICP_OK) st = symmicp_set_config(ctx, &cfg);
+		if (st == SYMMICP_OK) st = symmicp_align(ctx, guess, &result_);
+		else result_.status = st;
+		level_results_.push_back(result_);
+		if (st != SYMMICP_OK) { error_ = symmicp_last_error(ctx); break; }
+		std::memcpy(prev, result_.transform, sizeof(prev));
+		guess = prev;
+	}
+	if (result_.iters > 0 || st == SYMMICP_OK) std::memcpy(transform_, result_.transform, sizeof(transform_));
+	return done(st);
 }
 
 // Multi-start refinement: one problem per guess on the object's clouds, one batch (symmicp_ctx_batch_align)

@@ -24,14 +24,17 @@ constexpr int kPassThreads = 256;
 constexpr int kBruteTile = 1024;      // target points staged in LDS per tile (16 KB)
 constexpr int kBruteQ = 4;            // queries per thread in the brute-force kernel
 
-// The modes symmicp_config accepts (4 is unassigned), and those whose record solve::solve_mode solves, on the host and on the device:
-// all but P2P, whose solve is host-only, and COLOR, which stays in the host loop (its record has PLANE's shape: mode_solves_as maps it)
+// The modes symmicp_config accepts (4, 6 and 8 are unassigned), and those whose record solve::solve_mode solves, on the host and on the device: all but P2P, whose
+// solve is host-only, and COLOR and NDT, which stay in the host loop (their records have PLANE's shape: mode_solves_as maps them)
 constexpr bool mode_device_solves(int mode)
 {
     return mode == SYMMICP_MODE_QUIRKS || mode == SYMMICP_MODE_PAPER || mode == SYMMICP_MODE_PLANE || mode == SYMMICP_MODE_GICP;
 }
-constexpr bool mode_known(int mode) { return mode_device_solves(mode) || mode == SYMMICP_MODE_P2P || mode == SYMMICP_MODE_COLOR; }
-constexpr int mode_solves_as(int mode) { return mode == SYMMICP_MODE_COLOR ? SYMMICP_MODE_PLANE : mode; }
+constexpr bool mode_known(int mode)
+{
+    return mode_device_solves(mode) || mode == SYMMICP_MODE_P2P || mode == SYMMICP_MODE_COLOR || mode == SYMMICP_MODE_NDT;
+}
+constexpr int mode_solves_as(int mode) { return (mode == SYMMICP_MODE_COLOR || mode == SYMMICP_MODE_NDT) ? SYMMICP_MODE_PLANE : mode; }
 
 // The record a mode's passes accumulate (PassArgs::obj, the OBJ parameter of every accumulating kernel): the symmetric rows of
 // QUIRKS / PAPER / P2P, PLANE's, GICP's or COLOR's (host-loop kernels only: the fused pass and the straggler stage have no COLOR form)
@@ -371,6 +374,43 @@ void launch_voxel_mean(const CloudSoA &sorted, const uint32_t *kfirst, const uin
                        float *nrm_out, int32_t *count_out, hipStream_t s);
 void launch_voxel_of(const uint32_t *keys, const uint32_t *rows, const uint32_t *vid_excl, const uint32_t *first, const uint32_t *kid_excl,
                      uint32_t n, uint32_t min_points, int32_t *voxel_of, hipStream_t s);
+
+// NDT (kernels_ndt.hip; SYMMICP_MODE_NDT, symmicp_ctx_ndt_map).  The map of a cloud: per kept voxel (ascending key) a record of 4
+// float4 -- (mean xyz, count as int bits), then (axis l_r xyz, o_r) for r = 0, 1, 2 -- its key, and the 6 doubles of its covariance; and
+// an open-addressing table over the keys: a power of two >= 2 m entries of (key << 32 | row + 1), 0 = empty, probed linearly from
+// (key * 0x9E3779B1) >> shift.  A lookup is exact (a row is found iff the voxel exists) and costs one 8-byte load per probe.
+struct NdtGrid {
+    float inv;                          // 1.0f / resolution
+    float lo[3], hi[3];                 // the box's cells as floats (|.| < 2^23: exact)
+    int32_t lo_i[3];
+    uint32_t nx, ny;                    // key = ix + nx * (iy + ny * iz)
+    const float4 *rec;                  // [m][4]
+    const unsigned long long *table;
+    uint32_t shift, mask;               // 32 - log2(capacity), capacity - 1
+};
+struct NdtPassArgs {
+    const float *x, *y, *z;             // the source share as set (planar): read through X every pass
+    uint32_t n;
+    Affine X;
+    float pivot[3];
+    float max_d2;                       // <= 0: keep every item
+    float h;                            // (float)(0.5 * d2) of the Gauss constants
+    int32_t neighbors;                  // 1 or 7
+    NdtGrid g;
+    double *partials;                   // [blocks][kNSum], as every accumulating kernel writes them
+};
+// sorted: the cloud gathered in (key, row) order; skeys: the sorted keys; (kfirst, kcount): the voxels with >= min_points points.  One
+// thread per such voxel: rec / cov / key at its index, valid[o] = 1 unless the voxel is dropped (lambda_max not finite or <= 0)
+void launch_ndt_voxels(const CloudSoA &sorted, const uint32_t *skeys, const uint32_t *kfirst, const uint32_t *kcount, uint32_t m, float eig_ratio,
+                       float4 *rec, double *cov, uint32_t *key, uint32_t *valid, hipStream_t s);
+// the valid voxels, dense in the same order: pos = the exclusive scan of valid
+void launch_ndt_compact(const float4 *rec, const double *cov, const uint32_t *key, const uint32_t *valid, const uint32_t *pos, uint32_t m,
+                        float4 *rec_out, double *cov_out, uint32_t *key_out, hipStream_t s);
+// table: capacity entries, zeroed by the caller
+void launch_ndt_insert(const uint32_t *key, uint32_t m, unsigned long long *table, uint32_t shift, uint32_t mask, hipStream_t s);
+void launch_pass_ndt(const NdtPassArgs &a, int blocks, hipStream_t s);
+// per share row i, at [order ? order[i] : i]: the map row of the moved point's own cell (-1: none) and the pass's d2 to its mean (0: none)
+void launch_ndt_corr(const NdtPassArgs &a, const uint32_t *order, int32_t *idx_out, float *d2_out, hipStream_t s);
 
 // radius search and FPFH (kernels_fpfh.hip; symmicp_ctx_radius_search, symmicp_ctx_fpfh): one thread per sorted point, the box-tree
 // walk with the fixed bound r2.  count / offs / spfh_rows / fpfh_rows are indexed by ORIGINAL row, spfh_sorted ([n][36] floats)

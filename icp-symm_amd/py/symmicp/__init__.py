@@ -22,7 +22,7 @@ UNIQUE_ID_BYTES = 128
 OK, ERR_ARG, ERR_SIZE, ERR_DEGENERATE, ERR_IO, ERR_HIP, ERR_STATE, ERR_COMM = range(8)
 ERR_NO_CONSENSUS = 8
 RANSAC_EVALUATED, RANSAC_REPEATED, RANSAC_EDGE, RANSAC_DEGENERATE, RANSAC_FAR = range(5)      # per-hypothesis status of ransac()
-MODE_QUIRKS, MODE_PAPER, MODE_P2P, MODE_PLANE, MODE_GICP, MODE_COLOR = 0, 1, 2, 3, 5, 7      # (4 and 6 are unassigned)
+MODE_QUIRKS, MODE_PAPER, MODE_P2P, MODE_PLANE, MODE_GICP, MODE_COLOR, MODE_NDT = 0, 1, 2, 3, 5, 7, 9      # (4, 6 and 8 are unassigned)
 CORR_IDENTITY, CORR_BRUTE, CORR_TREE = 0, 1, 2
 APPLY_DEFAULT, APPLY_INCREMENTAL, APPLY_CUMULATIVE = 0, 1, 2
 LOSS_NONE, LOSS_HUBER, LOSS_TUKEY, LOSS_CAUCHY, LOSS_GEMAN_MCCLURE = range(5)
@@ -95,6 +95,11 @@ class IssConfig(C.Structure):
                 ("gamma32", C.c_float), ("min_neighbors", C.c_int32), ("reserved", C.c_int32)]
 
 
+class NdtConfig(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("resolution", C.c_float), ("min_points", C.c_int32), ("eig_ratio", C.c_float),
+                ("outlier_ratio", C.c_float), ("neighbors", C.c_int32)]
+
+
 class BatchProblem(C.Structure):
     """symmicp_batch_problem: the row ranges of one problem in the packed pools"""
     _fields_ = [("src_first", C.c_uint32), ("src_count", C.c_uint32), ("tgt_first", C.c_uint32), ("tgt_count", C.c_uint32)]
@@ -162,6 +167,8 @@ EXPORTS = [
     "symmicp_information_from_sums", "symmicp_evaluate_registration", "symmicp_ctx_evaluate_registration", "symmicp_evaluate",
     "symmicp_statistical_outlier_removal", "symmicp_ctx_statistical_outlier_removal",
     "symmicp_radius_outlier_removal", "symmicp_ctx_radius_outlier_removal",
+    "symmicp_ndt_config_default", "symmicp_set_ndt", "symmicp_get_ndt", "symmicp_ndt_gauss", "symmicp_ndt_weight", "symmicp_get_ndt_state",
+    "symmicp_ctx_ndt_map", "symmicp_ndt_map", "symmicp_get_ndt_map",
 ]
 
 _lib = None
@@ -318,6 +325,20 @@ def lib():
     ror = [fp, C.c_size_t, C.c_size_t, C.c_size_t, C.c_float, C.c_int, i32p, C.c_size_t, szp, i32p]
     L.symmicp_radius_outlier_removal.argtypes = [C.c_int] + ror
     L.symmicp_ctx_radius_outlier_removal.argtypes = [vp] + ror
+    ndp = C.POINTER(NdtConfig)
+    L.symmicp_ndt_config_default.argtypes = [ndp]
+    L.symmicp_ndt_config_default.restype = None
+    L.symmicp_set_ndt.argtypes = [vp, ndp]
+    L.symmicp_get_ndt.argtypes = [vp, ndp]
+    L.symmicp_ndt_gauss.argtypes = [C.c_double, dp, dp]
+    L.symmicp_ndt_weight.argtypes = [C.c_float]
+    L.symmicp_ndt_weight.restype = C.c_float
+    L.symmicp_get_ndt_state.argtypes = [vp, dp, u64p]
+    nmo = [u32p, i32p, fp, dp, fp, fp, i32p, C.c_size_t, szp]
+    nmi = [fp, C.c_size_t, C.c_size_t, C.c_size_t, ndp]
+    L.symmicp_ndt_map.argtypes = [C.c_int] + nmi + nmo
+    L.symmicp_ctx_ndt_map.argtypes = [vp] + nmi + nmo
+    L.symmicp_get_ndt_map.argtypes = [vp] + nmo
     _lib = L
     return L
 
@@ -519,6 +540,70 @@ def voxel_downsample(xyz, leaf, nrm=None, min_points=1, device=-1):
 
 def _i32ptr(a):
     return a.ctypes.data_as(C.POINTER(C.c_int32))
+
+
+def ndt_config(resolution=1.0, min_points=6, eig_ratio=0.01, outlier_ratio=0.55, neighbors=7):
+    """a symmicp_ndt_config (the defaults are PCL's)"""
+    cfg = NdtConfig()
+    lib().symmicp_ndt_config_default(C.byref(cfg))
+    cfg.resolution, cfg.min_points, cfg.eig_ratio = float(resolution), int(min_points), float(eig_ratio)
+    cfg.outlier_ratio, cfg.neighbors = float(outlier_ratio), int(neighbors)
+    return cfg
+
+
+def ndt_weight(x):
+    """symmicp_ndt_weight: the NDT pass's plain-arithmetic exp(x) on (-64, 0] in fp32 (0 at and below -64 and for NaN) -> np.float32"""
+    return np.float32(lib().symmicp_ndt_weight(C.c_float(float(np.float32(x)))))
+
+
+def ndt_gauss(outlier_ratio=0.55):
+    """symmicp_ndt_gauss: the Gauss constants (d1, d2) of an outlier ratio in (0, 1), fp64"""
+    d1, d2 = C.c_double(0), C.c_double(0)
+    st = lib().symmicp_ndt_gauss(C.c_double(float(outlier_ratio)), C.byref(d1), C.byref(d2))
+    if st != OK:
+        raise SymmIcpError(st, "ndt_gauss: the outlier ratio must lie in (0, 1)")
+    return d1.value, d2.value
+
+
+def _ndt_map_call(fn, head, cap, want=True):
+    """shared tail of the three map entries: fn(*head, <the outputs>) -> (status, map dict or None, m)"""
+    c1 = max(int(cap), 1)
+    key, cnt = np.zeros(c1, np.uint32), np.zeros(c1, np.int32)
+    mean, cov = np.zeros((c1, 3), np.float32), np.zeros((c1, 6), np.float64)
+    axes, inv_eig = np.zeros((c1, 3, 3), np.float32), np.zeros((c1, 3), np.float32)
+    grid = np.zeros(6, np.int32)
+    m = C.c_size_t(0)
+    dptr = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))
+    if want:
+        st = fn(*head, key.ctypes.data_as(C.POINTER(C.c_uint32)), _i32ptr(cnt), _fptr(mean), dptr(cov), _fptr(axes), _fptr(inv_eig), _i32ptr(grid),
+                int(cap), C.byref(m))
+    else:
+        st = fn(*head, None, None, None, None, None, None, None, int(cap), C.byref(m))
+    m = int(m.value)
+    if st != OK:
+        return st, None, m
+    return st, dict(key=key[:m].copy(), count=cnt[:m].copy(), mean=mean[:m].copy(), cov=cov[:m].copy(), axes=axes[:m].copy(),
+                    inv_eig=inv_eig[:m].copy(), grid=grid.copy()), m
+
+
+def _ndt_map(fn, head, xyz, cfg, cap=None, strides=None, want=True):
+    if strides is None:
+        xyz = _cloud(xyz)
+        n, xr, xc = xyz.shape[0], 3, 1
+    else:
+        xyz = np.ascontiguousarray(xyz, np.float32)
+        n, xr, xc = strides
+    cap = n if cap is None else cap
+    return _ndt_map_call(fn, tuple(head) + (_fptr(xyz), xr, xc, n, C.byref(cfg)), cap, want)
+
+
+def ndt_map(xyz, resolution, min_points=6, eig_ratio=0.01, outlier_ratio=0.55, neighbors=7, device=-1):
+    """the NDT voxel map of a cloud (symmicp_ndt_map): per kept voxel, in ascending key -> dict(key [m] u32, count [m], mean [m,3],
+    cov [m,6] f64 (xx xy xz yy yz zz), axes [m,3,3] (axis r at [:, r]), inv_eig [m,3], grid = lo xyz + n xyz)"""
+    st, r, _ = _ndt_map(lib().symmicp_ndt_map, (int(device),), xyz, ndt_config(resolution, min_points, eig_ratio, outlier_ratio, neighbors))
+    if st != OK:
+        raise SymmIcpError(st, "ndt_map")
+    return r
 
 
 def _radius_call(fn, head, xyz, radius, cap=None, strides=None, want_d2=True):
@@ -1150,9 +1235,50 @@ class Engine:
         self.n_source = xyz.shape[0]
 
     def set_target(self, xyz, nrm):
-        xyz, nrm = _cloud(xyz), _cloud(nrm)
-        self._chk(self._L.symmicp_set_target(self._h, _fptr(xyz), 3, 1, _fptr(nrm), 3, 1, xyz.shape[0]))
+        """nrm may be None in MODE_NDT (the target's voxel map needs no normals)"""
+        xyz = _cloud(xyz)
+        nrm = None if nrm is None else _cloud(nrm)
+        self._chk(self._L.symmicp_set_target(self._h, _fptr(xyz), 3, 1, None if nrm is None else _fptr(nrm), 3, 1, xyz.shape[0]))
         self.n_target = xyz.shape[0]
+
+    def set_ndt(self, resolution=1.0, min_points=6, eig_ratio=0.01, outlier_ratio=0.55, neighbors=7):
+        """the parameters of MODE_NDT (symmicp_set_ndt); on an NDT context that holds a target the map is rebuilt at once"""
+        cfg = ndt_config(resolution, min_points, eig_ratio, outlier_ratio, neighbors)
+        self._chk(self._L.symmicp_set_ndt(self._h, C.byref(cfg)))
+
+    def get_ndt(self):
+        """-> dict(resolution, min_points, eig_ratio, outlier_ratio, neighbors)"""
+        cfg = NdtConfig()
+        self._chk(self._L.symmicp_get_ndt(self._h, C.byref(cfg)))
+        return dict(resolution=cfg.resolution, min_points=cfg.min_points, eig_ratio=cfg.eig_ratio, outlier_ratio=cfg.outlier_ratio,
+                    neighbors=cfg.neighbors)
+
+    def ndt_map(self, xyz, resolution, min_points=6, eig_ratio=0.01, outlier_ratio=0.55, neighbors=7):
+        """ndt_map on this context (symmicp_ctx_ndt_map); its clouds, index, map and loop state stay as they are"""
+        st, r, _ = self.ndt_map_raw(xyz, ndt_config(resolution, min_points, eig_ratio, outlier_ratio, neighbors))
+        self._chk(st)
+        return r
+
+    def ndt_map_raw(self, xyz, cfg, cap=None, strides=None, want=True):
+        """-> (status, map or None, m): the call as it is (tests of the cap protocol, the strides and the refusals)"""
+        return _ndt_map(self._L.symmicp_ctx_ndt_map, (self._h,), xyz, cfg, cap, strides, want)
+
+    def get_ndt_map(self, cap=None):
+        """the map an NDT context holds after set_target (symmicp_get_ndt_map), as ndt_map returns it"""
+        if cap is None:
+            st, _, m = _ndt_map_call(self._L.symmicp_get_ndt_map, (self._h,), 0, want=False)
+            if st not in (OK, ERR_SIZE):
+                self._chk(st)
+            cap = m
+        st, r, _ = _ndt_map_call(self._L.symmicp_get_ndt_map, (self._h,), cap)
+        self._chk(st)
+        return r
+
+    def ndt_state(self):
+        """-> (score, items) of the most recent pass of an NDT context: -d1 x the sum of the weights, the number of (point, voxel) items"""
+        sc, it = C.c_double(0), C.c_uint64(0)
+        self._chk(self._L.symmicp_get_ndt_state(self._h, C.byref(sc), C.byref(it)))
+        return sc.value, it.value
 
     def set_source_strided(self, xyz, xr, xc, nrm, nr, nc, n):
         self._chk(self._L.symmicp_set_source(self._h, _fptr(xyz), xr, xc, _fptr(nrm), nr, nc, n))
@@ -1614,6 +1740,8 @@ class MyICP:
         self._color_weight = None
         self.intensity_src = self.intensity_tgt = None
         self._levels = []
+        self._ndt = dict(resolution=1.0, neighbors=7, min_points=6)
+        self._ndt_levels = []
         self.level_results = []
         self._global = None
         self.global_result = None
@@ -1692,6 +1820,55 @@ class MyICP:
         if levels and self._cfg["mode"] == MODE_COLOR:
             raise SymmIcpError(ERR_ARG, "MODE_COLOR does not run voxel levels (intensities are not averaged per voxel yet)")
         self._levels = levels
+
+    def setNdt(self, resolution, neighbors=7, min_points=6):
+        """the parameters of MODE_NDT (Engine.set_ndt): the voxel edge, the neighbourhood (1 or 7) and the fewest points of a voxel"""
+        self._ndt = dict(resolution=float(resolution), neighbors=int(neighbors), min_points=int(min_points))
+
+    def setNdtLevels(self, levels):
+        """coarse-to-fine NDT: [(resolution, max_iters), ...], coarse first.  align() in MODE_NDT then runs, per level, set_ndt with the
+        level's resolution (the target's map is rebuilt at once) and an alignment of max_iters iterations started from the level
+        before (the first from the caller's guess): bit for bit the transform of the same calls made by hand.  [] = off."""
+        self._ndt_levels = [(float(r), int(i)) for r, i in levels]
+
+    def _align_ndt(self, guess):
+        """MODE_NDT: no normals are estimated, no index is built; the clouds go in as they are"""
+        if self._levels or self._global is not None:
+            raise SymmIcpError(ERR_ARG, "MODE_NDT runs neither voxel levels (setNdtLevels is its coarse-to-fine) nor the global initialisation")
+        verbose = bool(self._cfg["verbose"])
+        levels = self._ndt_levels or [(self._ndt["resolution"], self._cfg["max_iters"])]
+        self.level_results = []
+        K = len(levels)
+        with Engine(**dict(self._cfg, verbose=0)) as e:
+            if self._loss[0] != LOSS_NONE:
+                e.set_robust_loss(*self._loss)
+            if self._trim != 1.0:
+                e.set_trim_fraction(self._trim)
+            if self._one_to_one:
+                e.set_one_to_one(True)
+            if self._reciprocal:
+                e.set_reciprocal(True)
+            if self._median != 0.0:
+                e.set_median_factor(self._median)
+            e.set_ndt(**dict(self._ndt, resolution=levels[0][0]))
+            e.set_target(self.cloud_tgt, None)
+            e.set_source(self.cloud_src, None)
+            X = guess
+            for k, (res, iters) in enumerate(levels):
+                if k:
+                    e.set_ndt(**dict(self._ndt, resolution=res))
+                if verbose and self._ndt_levels:
+                    print("NDT level %d/%d: resolution %g, %d iterations" % (k + 1, K, res, iters), flush=True)
+                e.set_config(max_iters=iters, verbose=int(verbose and k + 1 == K))
+                r = e.align(X)
+                self.level_results.append(r)
+                if r["status"] != OK:
+                    break
+                X = r["transform"]
+        self.last_result = r
+        if r["status"] == OK or r["iters"] > 0:
+            self._final = r["transform"]
+        return r
 
     def setGlobalInit(self, fpfh_radius, max_dist, voxel_leaf=0.0, normal_k=10, hypotheses=100000, seed=0, mutual=True, max_ratio=0.0,
                       edge_ratio=0.9, refits=1, iss=False, iss_salient_radius=0.0, iss_non_max_radius=0.0, iss_gamma21=0.975, iss_gamma32=0.975,
@@ -1859,6 +2036,8 @@ class MyICP:
 
     def align(self, guess=None):
         assert self.cloud_src is not None and self.cloud_tgt is not None      # myicp.cpp:102
+        if self._cfg["mode"] == MODE_NDT:
+            return self._align_ndt(guess)                                    # (both normals pre-steps are skipped)
         if self._levels and self._cfg["corr"] == CORR_IDENTITY:
             raise SymmIcpError(ERR_ARG, "voxel levels need nearest-neighbour pairs (CORR_IDENTITY pairs by row)")
         color = self._cfg["mode"] == MODE_COLOR

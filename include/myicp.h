@@ -89,6 +89,16 @@ public:
 	// SYMMICP_CORR_IDENTITY is SYMMICP_ERR_ARG with levels (the downsampled counts differ).  Empty (the default): align() as without.
 	struct VoxelLevel { float leaf; int max_iters; float max_corr_dist; };
 	void setVoxelLevels(const std::vector<VoxelLevel> &levels) { levels_ = levels; }
+	// NDT registration (SYMMICP_MODE_NDT, include/symmicp.h): the voxel edge, the neighbourhood (1: the point's own voxel, 7: and its six
+	// face neighbours) and the fewest points a voxel needs; checked by align() (SYMMICP_ERR_ARG as symmicp_set_ndt).  In this mode
+	// align() skips both normals pre-steps (the clouds go in without normals) and builds no index; robust losses, the rejectors, voxel
+	// levels and the global initialisation are SYMMICP_ERR_ARG.
+	void setNdt(float resolution, int neighbors = 7, int min_points = 6) { ndt_resolution_ = resolution; ndt_neighbors_ = neighbors; ndt_min_points_ = min_points; }
+	// Coarse-to-fine NDT, coarse first: per level symmicp_set_ndt with the level's resolution (the target's map is rebuilt at once) and an
+	// alignment of max_iters iterations started from the level before (the first from the caller's guess) -- bit for bit the transform
+	// of the same calls made by hand.  levelResults() has one result per level.  Empty (the default): one alignment at setNdt's resolution.
+	struct NdtLevel { float resolution; int max_iters; };
+	void setNdtLevels(const std::vector<NdtLevel> &levels) { ndt_levels_ = levels; }
 	const std::vector<symmicp_result> &levelResults() const { return level_results_; }   // one per level run by the last align()
 	// Global initialisation (feature matching and RANSAC, include/symmicp.h): with it set and no guess4x4 given, align() first
 	// voxel-downsamples both clouds with voxel_leaf (0: the clouds as given), estimates normals on the downsampled clouds when the
@@ -191,12 +201,17 @@ private:
 	std::vector<VoxelLevel> levels_;
 	std::vector<symmicp_result> level_results_;
 	int alignLevels(const symmicp_config &cfg, bool source_normals, const float *guess4x4);
+	float ndt_resolution_ = 1.f;
+	int ndt_neighbors_ = 7, ndt_min_points_ = 6;
+	std::vector<NdtLevel> ndt_levels_;
+	int alignNdt(float out4x4[16], const float *guess4x4);
 	GlobalInit global_;
 	bool have_global_ = false;
 	GlobalResult global_result_{};
 	int globalInit(symmicp_ctx *ctx);
 	symmicp_ctx *ctx_;
 	int ctx_corr_;
+	bool ctx_ndt_ = false;               // the context was created for SYMMICP_MODE_NDT (it holds a voxel map, not an index: no other mode runs on it)
 	bool ctx_no_src_normals_;            // the context holds a source set without normals (PLANE): no other mode can run on it
 	float transform_[16];
 	symmicp_result result_;

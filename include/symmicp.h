@@ -71,9 +71,12 @@ typedef enum {
  * PLANE's, and only the target's normals enter the rows.  Source normals stay required (nrm == NULL is PLANE-only); they are read
  * under PLANE's rule (write-back or min_normal_dot).  lambda: symmicp_set_color_weight; the attributes: symmicp_set_source_intensity
  * and symmicp_set_target_intensity.  Out of scope, refused: sharded contexts (nranks > 1: SYMMICP_ERR_STATE), the fused pass and the
- * device-driven loop (symmicp_align runs the host loop, as it does for a trimming context).  Modes 4 and 6 are unassigned. */
+ * device-driven loop (symmicp_align runs the host loop, as it does for a trimming context).  NDT is the Normal Distributions
+ * Transform (Biber and Strasser 2003, Magnusson 2009; pcl::NormalDistributionsTransform): a source point is paired with the Gaussian
+ * of the target VOXEL it falls into, not with a target point -- no search, no normals, no index; its definition has a section of its
+ * own below ("NDT registration").  Modes 4, 6 and 8 are unassigned and stay refused. */
 typedef enum { SYMMICP_MODE_QUIRKS = 0, SYMMICP_MODE_PAPER = 1, SYMMICP_MODE_P2P = 2, SYMMICP_MODE_PLANE = 3,
-               SYMMICP_MODE_GICP = 5, SYMMICP_MODE_COLOR = 7 } symmicp_mode;
+               SYMMICP_MODE_GICP = 5, SYMMICP_MODE_COLOR = 7, SYMMICP_MODE_NDT = 9 } symmicp_mode;
 
 /* Correspondence.  IDENTITY is what the reference does (myicp.cpp:130, the
  * search is a todo at :128-131).  BRUTE and TREE are exact nearest neighbour
@@ -806,6 +809,88 @@ int symmicp_ctx_voxel_downsample(symmicp_ctx *ctx, const float *xyz, size_t xyz_
 int symmicp_voxel_downsample(int device, const float *xyz, size_t xyz_row_stride, size_t xyz_col_stride,
                              const float *nrm, size_t nrm_row_stride, size_t nrm_col_stride, size_t n, float leaf, int min_points,
                              float *xyz_out, float *nrm_out, int32_t *count_out, int32_t *voxel_of, size_t cap, size_t *n_out);
+
+/* ---- NDT registration (SYMMICP_MODE_NDT): voxel Gaussians on the GPU --------------------------------------------------------------
+ * The mode is DEFINED by the arithmetic below ("NDT"; tests/_ndt_ref.py is the same in numpy).  Every fp32 expression is
+ * unfused, in the association written.
+ *
+ * Parameters (symmicp_ndt_config; symmicp_ndt_config_default: resolution 1, min_points 6, eig_ratio 0.01, outlier_ratio 0.55,
+ * neighbors 7 -- PCL's values, 7 being its "direct 7" neighbourhood).  SYMMICP_ERR_ARG for a wrong struct_size, a resolution that is
+ * not finite and > 0, min_points < 3, eig_ratio outside (0, 1], outlier_ratio outside (0, 1), neighbors other than 1 or 7; a refused
+ * setter leaves the configuration as it was.
+ *
+ * Grid.  symmicp_ctx_voxel_downsample's, over the target's box, with leaf = resolution: inv = 1.0f / resolution; per axis
+ *   lo = floorf(min * inv), hi = floorf(max * inv), n_axis = hi - lo + 1; key = ix + nx * (iy + ny * iz).  The same refusals, and one
+ *   more: every |lo| and |hi| must be < 2^23 (cell coordinates are then exact as floats), else SYMMICP_ERR_ARG.
+ * Map.  For every occupied voxel with count >= min_points, in ascending key:
+ *   mu64 = the fp64 sum of the members, one point at a time in ascending caller row, divided by count; mean = (float)mu64.
+ *   C = sum (x - mu64)(x - mu64)^T / (count - 1): fp64 products and sums, unfused, same order; its upper triangle (xx xy xz yy yz zz) is
+ *   kept as 6 doubles.  Eigen-decomposition of C by the fp64 cyclic Jacobi of the normals pre-step.  The voxel is dropped unless
+ *   lambda_max is finite and > 0.  lambda'_r = max(lambda_r, eig_ratio * lambda_max); axes l_r = the eigenvectors rounded to fp32, in
+ *   ascending lambda; o_r = (float)(1 / lambda'_r); M = sum_r o_r l_r l_r^T is the voxel's inverse covariance.  Dropped voxels do not
+ *   exist: a map row is a kept voxel, rows ascend with the key.
+ * Gauss constants.  symmicp_ndt_gauss(outlier_ratio p_o, &d1, &d2), a pure host function in fp64 (a context calls it with its fp32
+ *   outlier_ratio widened to fp64):
+ *   c1 = 10 (1 - p_o), c2 = p_o, d3 = -log c2, d1 = -log(c1 + c2) - d3, d2 = -2 log((-log(c1 exp(-1/2) + c2) - d3) / d1).
+ *   This is PCL's formula with c2 taken at resolution 1.  PCL divides c2 by resolution^3, which ties the weight to the unit of length;
+ *   here the same cloud in other units, with the resolution scaled along, takes the same steps.  At 0.55: d1 = -2.217225244...,
+ *   d2 = 0.433123004....  The pass's constant is h = (float)(0.5 * d2).  SYMMICP_ERR_ARG for a ratio outside (0, 1) or a NULL pointer.
+ * Weight.  symmicp_ndt_weight(x), one source for host and device, a plain-arithmetic exp(x) on (-64, 0]:
+ *   if !(x > -64.0f) return 0 (NaN too); if x > 0, x = 0; k = rintf(x * 1.44269504f); r = (x - k * 0.693359375f) - k * (-2.12194440e-4f);
+ *   p = Horner over r with 1.9875691500e-4f, 1.3981999507e-3f, 8.3334519073e-3f, 4.1665795894e-2f, 1.6666665459e-1f, 5.0000001201e-1f;
+ *   y = (p * (r * r) + r) + 1.0f; return ldexpf(y, (int)k).
+ * A pass.  y_i = the three top rows of X applied to source row i in fp32 (as every mode moves a point); g = floorf(y * inv) per axis,
+ *   kept as floats.  Candidate cells: g itself (neighbors = 1), and g +- 1 on each single axis as well (neighbors = 7).  A candidate is
+ *   an ITEM iff lo <= g <= hi on all three axes (float compares) and the map holds that cell's voxel.  Per item, with p = y - pivot,
+ *   mu = mean - pivot (fp32 subtractions), d = p - mu:
+ *     c_r = (dx*lx + dy*ly) + dz*lz for each axis l_r; the row v_r = (p x l_r, l_r) formed exactly as PLANE forms (p x n, n);
+ *     m = ((o0*c0)*c0 + (o1*c1)*c1) + (o2*c2)*c2;  w = symmicp_ndt_weight(-(h * m));  d2 = (dx*dx + dy*dy) + dz*dz.
+ *     With max_corr_dist > 0 the item is dropped when d2 > max_corr_dist^2 (the rule of every mode).
+ *   The three rows enter the record as PLANE rows at weight (double)w * (double)o_r:
+ *     [0..26] sum w o v v^T, sum w o v c   [27..32] sum w p, sum w mu   [33] sum sqrtf(d2)   [34] sum w   [35] sum w m   [36] sum d2
+ *     [37] the number of items (what symmicp_iter_result.pairs reports).
+ * Solve.  symmicp_solve(SYMMICP_MODE_NDT) is PLANE's solve: each step is the Gauss-Newton (IRLS) step of the NDT score; the constant
+ *   -d1 d2 cancels out of it.  The score of a pass is -d1 * [34]: symmicp_get_ndt_state reports it and the item count of the most recent
+ *   pass (SYMMICP_ERR_STATE before one).
+ * Engine.  cfg.corr is not read in this mode: symmicp_set_target builds the map instead of an index (and the N_s = N_t rule of identity
+ *   pairing does not apply); nrm == NULL is accepted for both clouds; cfg.sort_source is honoured as BRUTE / TREE honour it.
+ *   symmicp_align runs the host loop.  symmicp_set_ndt on an NDT context that holds a target rebuilds the map at once from the planar
+ *   copy the context keeps -- bit for bit the map of a fresh symmicp_set_target -- and resets the loop state as symmicp_set_target does.
+ *   symmicp_get_correspondences reports per caller row the map row of the point's OWN cell (-1: no voxel there) and d2 to that voxel's
+ *   mean as a pass forms it (0 when there is none).  symmicp_evaluate builds a temporary index, as every non-TREE context does.
+ * Refused: a robust loss, a trim fraction below 1, one-to-one, a median factor, reciprocal correspondences, min_normal_dot > -1 and
+ *   SYMMICP_APPLY_INCREMENTAL (SYMMICP_ERR_ARG, from the setter on an NDT context and from symmicp_set_config into NDT alike);
+ *   nranks > 1 (SYMMICP_ERR_STATE, both ways round); symmicp_set_config into or out of NDT while a cloud is set (SYMMICP_ERR_STATE);
+ *   symmicp_batch_align in this mode (SYMMICP_ERR_ARG).
+ *
+ * symmicp_ctx_ndt_map builds the map of any cloud on a context the caller owns and leaves that context untouched; every output may be
+ * NULL: key_out [m], count_out [m], mean_out [m][3], cov_out [m][6], axes_out [m][3][3] (axis r at [m][r][0..2]), inv_eig_out [m][3]
+ * (o_r), grid_out = lo xyz, n xyz.  *m_out = m always (required); SYMMICP_ERR_SIZE when m > cap, nothing else is written then.  Its
+ * argument checks (NULL xyz / cfg / m_out, n == 0 or > 2^31 - 1, the configuration's rules, non-finite coordinates) are decided on the
+ * host before a device is needed.  symmicp_ndt_map is the same on a context of its own; symmicp_get_ndt_map reads the map an NDT context
+ * holds (SYMMICP_ERR_STATE without one). */
+typedef struct {
+    int32_t struct_size;       /* = sizeof(symmicp_ndt_config), checked */
+    float   resolution;        /* voxel edge */
+    int32_t min_points;        /* voxels with fewer points have no Gaussian (>= 3) */
+    float   eig_ratio;         /* eigenvalues are raised to eig_ratio * the largest */
+    float   outlier_ratio;     /* p_o of the Gauss constants */
+    int32_t neighbors;         /* 1: the point's own cell; 7: and its six face neighbours */
+} symmicp_ndt_config;
+void symmicp_ndt_config_default(symmicp_ndt_config *cfg);
+int symmicp_set_ndt(symmicp_ctx *ctx, const symmicp_ndt_config *cfg);
+int symmicp_get_ndt(const symmicp_ctx *ctx, symmicp_ndt_config *cfg);
+int symmicp_ndt_gauss(double outlier_ratio, double *d1, double *d2);
+float symmicp_ndt_weight(float x);
+int symmicp_get_ndt_state(const symmicp_ctx *ctx, double *score, uint64_t *items);
+int symmicp_ctx_ndt_map(symmicp_ctx *ctx, const float *xyz, size_t row_stride, size_t col_stride, size_t n, const symmicp_ndt_config *cfg,
+                        uint32_t *key_out, int32_t *count_out, float *mean_out, double *cov_out, float *axes_out, float *inv_eig_out,
+                        int32_t grid_out[6], size_t cap, size_t *m_out);
+int symmicp_ndt_map(int device, const float *xyz, size_t row_stride, size_t col_stride, size_t n, const symmicp_ndt_config *cfg,
+                    uint32_t *key_out, int32_t *count_out, float *mean_out, double *cov_out, float *axes_out, float *inv_eig_out,
+                    int32_t grid_out[6], size_t cap, size_t *m_out);
+int symmicp_get_ndt_map(symmicp_ctx *ctx, uint32_t *key_out, int32_t *count_out, float *mean_out, double *cov_out, float *axes_out,
+                        float *inv_eig_out, int32_t grid_out[6], size_t cap, size_t *m_out);
 
 /* ---- registration evaluation: fitness, inlier RMSE, information matrix (PCL's getFitnessScore, Open3D's evaluate_registration and
  * get_information_matrix_from_point_clouds) -----------------------------------------------------------------------------------------
