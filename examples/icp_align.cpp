@@ -36,6 +36,11 @@
 //     --fpfh-radius R          its feature radius (required with --init global; some 8 to 12 point spacings)
 //     --ransac-dist D          its inlier distance (required; some 2 point spacings)
 //     --ransac-iters H         hypotheses drawn (default 100000)      --seed S   of the draws (default 0)
+//     --init fgr               the same with Fast Global Registration in RANSAC's place (a tuple test and a graduated-non-convexity
+//                              loop on those matches: no hypothesis count, no lucky sample); takes --fpfh-radius, --seed, --init-voxel and
+//                              --init-keypoints as --init global does, and
+//     --fgr-dist D             its inlier distance (required; some 2 point spacings)
+//     --fgr-iters N            iterations of the loop (default 64)    --fgr-tuples N   tuples kept (default 1000; 0: the tuple test off)
 //     --init-voxel L           both clouds voxel-downsampled with edge L for the initialisation (default 0: as given)
 //     --init-keypoints iss     match and run RANSAC on the ISS keypoints of both clouds only (features still come from the full clouds)
 //     --iss-radius R           their salient radius (required with --init-keypoints iss; some 6 point spacings)
@@ -67,7 +72,7 @@
 static int usage(const char *argv0, const char *complaint)
 {
     std::fprintf(stderr, "%s\nusage: %s [--mode quirks|paper|plane|gicp|color|ndt] [--ndt-resolution L] [--ndt-neighbors 1|7] [--ndt-min-points N] [--ndt-level L:ITERS]... [--color-weight L] [--corr identity|tree] [--iters N] [--threshold D] [--loss none|huber|tukey|cauchy|gm]"
-                 " [--loss-scale S] [--gicp-epsilon E] [--max-dist D] [--trim F] [--one-to-one] [--reciprocal] [--median-factor F] [--scale LEAF:ITERS[:MAXDIST]]... [--init global --fpfh-radius R --ransac-dist D [--ransac-iters H] [--seed S] [--init-voxel L] [--init-keypoints iss --iss-radius R [--iss-nms-radius R2] [--iss-min-neighbors K]]] [--evaluate D [--information]] [--sor K:S] [--ror R:M] [--out file.pcd] [--quiet] [source.pcd target.pcd]\n",
+                 " [--loss-scale S] [--gicp-epsilon E] [--max-dist D] [--trim F] [--one-to-one] [--reciprocal] [--median-factor F] [--scale LEAF:ITERS[:MAXDIST]]... [--init global --fpfh-radius R --ransac-dist D [--ransac-iters H] [--seed S] [--init-voxel L] [--init-keypoints iss --iss-radius R [--iss-nms-radius R2] [--iss-min-neighbors K]]] [--init fgr --fpfh-radius R --fgr-dist D [--fgr-iters N] [--fgr-tuples N] [--seed S] [--init-voxel L] [--init-keypoints iss ...]] [--evaluate D [--information]] [--sor K:S] [--ror R:M] [--out file.pcd] [--quiet] [source.pcd target.pcd]\n",
                  complaint, argv0);
     return 64;
 }
@@ -90,7 +95,7 @@ int main(int argc, char **argv)
     bool one_to_one = false, reciprocal = false;
     float median_factor = 0.f;
     std::vector<MyICP::VoxelLevel> levels;
-    bool init_global = false, have_init_option = false, have_iss_option = false;
+    bool init_global = false, have_init_option = false, have_iss_option = false, have_fgr_option = false, have_ransac_option = false;
     MyICP::GlobalInit ginit;
     bool evaluate = false, information = false;
     float eval_dist = 0.f;
@@ -229,17 +234,29 @@ int main(int argc, char **argv)
         }
         else if (a == "--init") {
             const std::string v = value("--init");
-            if (v == "global") init_global = true;
+            if (v == "global") { init_global = true; ginit.method = MyICP::GlobalInit::RANSAC; }
+            else if (v == "fgr") { init_global = true; ginit.method = MyICP::GlobalInit::FGR; }
             else if (v == "identity") init_global = false;
-            else return usage(argv[0], "unknown --init (global or identity)");
+            else return usage(argv[0], "unknown --init (global, fgr or identity)");
+        }
+        else if (a == "--fgr-dist") { number("--fgr-dist", value("--fgr-dist"), ginit.max_dist); have_init_option = true; have_fgr_option = true; }
+        else if (a == "--fgr-iters") {
+            ginit.fgr_iterations = std::atoi(value("--fgr-iters"));
+            if (ginit.fgr_iterations < 1 || ginit.fgr_iterations > 1024) return usage(argv[0], "--fgr-iters needs 1 .. 1024");
+            have_init_option = true; have_fgr_option = true;
+        }
+        else if (a == "--fgr-tuples") {
+            const long n = std::atol(value("--fgr-tuples"));
+            if (n < 0 || n > (1l << 18)) return usage(argv[0], "--fgr-tuples needs 0 .. 262144 (0: the tuple test off)");
+            ginit.fgr_max_tuples = (unsigned)n; have_init_option = true; have_fgr_option = true;
         }
         else if (a == "--fpfh-radius") { number("--fpfh-radius", value("--fpfh-radius"), ginit.fpfh_radius); have_init_option = true; }
-        else if (a == "--ransac-dist") { number("--ransac-dist", value("--ransac-dist"), ginit.max_dist); have_init_option = true; }
+        else if (a == "--ransac-dist") { number("--ransac-dist", value("--ransac-dist"), ginit.max_dist); have_init_option = true; have_ransac_option = true; }
         else if (a == "--init-voxel") { number("--init-voxel", value("--init-voxel"), ginit.voxel_leaf); have_init_option = true; }
         else if (a == "--ransac-iters") {
             const long h = std::atol(value("--ransac-iters"));
             if (h < 1 || h > (1l << 24)) return usage(argv[0], "--ransac-iters needs 1 .. 16777216");
-            ginit.hypotheses = (unsigned)h; have_init_option = true;
+            ginit.hypotheses = (unsigned)h; have_init_option = true; have_ransac_option = true;
         }
         else if (a == "--init-keypoints") {
             const std::string v = value("--init-keypoints");
@@ -332,6 +349,10 @@ int main(int argc, char **argv)
         icp.setVoxelLevels(levels);
     }
     if (init_global) {
+        const bool fgr = ginit.method == MyICP::GlobalInit::FGR;
+        if (have_fgr_option && !fgr) return usage(argv[0], "--fgr-dist, --fgr-iters and --fgr-tuples need --init fgr");
+        if (have_ransac_option && fgr) return usage(argv[0], "--ransac-dist and --ransac-iters need --init global (--init fgr takes --fgr-dist)");
+        if (fgr && !(ginit.fpfh_radius > 0.f && ginit.max_dist > 0.f)) return usage(argv[0], "--init fgr needs --fpfh-radius R and --fgr-dist D, both > 0");
         if (!(ginit.fpfh_radius > 0.f) || !(ginit.max_dist > 0.f)) return usage(argv[0], "--init global needs --fpfh-radius R and --ransac-dist D, both > 0");
         if (ginit.voxel_leaf < 0.f) return usage(argv[0], "--init-voxel needs L >= 0");
         if (!tree) return usage(argv[0], "--init global needs --corr tree (identity pairing assumes the clouds correspond row by row)");
@@ -343,7 +364,7 @@ int main(int argc, char **argv)
             if (ginit.iss_min_neighbors < 1) return usage(argv[0], "--iss-min-neighbors needs K >= 1");
         }
         icp.setGlobalInit(ginit);
-    } else if (have_init_option || have_iss_option) return usage(argv[0], "--fpfh-radius, --ransac-dist, --ransac-iters, --seed, --init-voxel and --init-keypoints need --init global");
+    } else if (have_init_option || have_iss_option) return usage(argv[0], "--fpfh-radius, --ransac-dist, --ransac-iters, --fgr-dist, --fgr-iters, --fgr-tuples, --seed, --init-voxel and --init-keypoints need --init global or --init fgr");
     if (information && !evaluate) return usage(argv[0], "--information needs --evaluate D");
     if (have_eps) {
         if (!gicp) return usage(argv[0], "--gicp-epsilon needs --mode gicp");

@@ -535,6 +535,26 @@ int MyICP::globalInit(symmicp_ctx *ctx)
 	if (g.iss) for (size_t k = 0; k < count; k++) { pairs[2 * k] = kp[0][(size_t)pairs[2 * k]]; pairs[2 * k + 1] = kp[1][(size_t)pairs[2 * k + 1]]; }
 	global_result_.correspondences = count;
 	if (count < 3) return failed(SYMMICP_ERR_NO_CONSENSUS, "fewer than 3 feature correspondences");
+	if (g.method == GlobalInit::FGR) {
+		symmicp_fgr_config fc;
+		symmicp_fgr_config_default(&fc);
+		fc.max_dist = g.max_dist; fc.seed = g.seed; fc.iterations = g.fgr_iterations; fc.division_factor = g.fgr_division_factor;
+		fc.tuple_scale = g.fgr_tuple_scale; fc.max_tuples = g.fgr_max_tuples;
+		st = symmicp_ctx_fgr(ctx, cl[0].xyz.data(), 3, 1, cl[0].m, cl[1].xyz.data(), 3, 1, cl[1].m, pairs.data(), count, &fc, global_result_.transform,
+		                     &global_result_.fgr, nullptr, nullptr, nullptr, nullptr, nullptr);
+		if (verbose_)
+			std::printf("global init: %zu -> %zu source and %zu -> %zu target points, %zu and %zu ISS keypoints, %zu correspondences, FGR: %u tuples accepted, "
+			            "%u set elements, %d iterations, %d inliers\n",
+			            cloud_pn_src->points.size(), cl[0].m, cloud_pn_tgt->points.size(), cl[1].m, g.iss ? kp[0].size() : (size_t)0,
+			            g.iss ? kp[1].size() : (size_t)0, count, global_result_.fgr.tuples_accepted, global_result_.fgr.set_size,
+			            global_result_.fgr.iterations, global_result_.fgr.inliers);
+		if (st != SYMMICP_OK) {
+			for (int k = 0; k < 16; k++) global_result_.transform[k] = (k % 5 == 0) ? 1.f : 0.f;      // (a degenerate loop leaves its X_k: not a guess)
+			return failed(st, "FGR");
+		}
+		global_result_.status = SYMMICP_OK;
+		return SYMMICP_OK;
+	}
 	symmicp_ransac_config rc;
 	symmicp_ransac_config_default(&rc);
 	rc.hypotheses = g.hypotheses; rc.seed = g.seed; rc.max_dist = g.max_dist; rc.edge_ratio = g.edge_ratio; rc.refits = g.refits;

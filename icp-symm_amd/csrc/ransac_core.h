@@ -58,21 +58,34 @@ template <class T> __host__ __device__ inline void rc_frame(const T u[3], const 
     rc_cross(e3, e1, e2);
 }
 
+// the base of the sequence of (seed, stream 1): the tuple trials of symmicp_ctx_fgr
+__host__ __device__ inline unsigned long long ransac_base_stream1(unsigned long long seed)
+{
+    return ransac_mix64(seed * 0x9E3779B97F4A7C15ull + 0xD1B54A32D192ED03ull + 0x2545F4914F6CDD1Dull);
+}
+
+// the EDGE check: does an edge of the sample triangle (0-1, 1-2, 2-0) differ between the clouds by more than the ratio whose square is
+// edge2?  Shared by the RANSAC hypotheses and the tuple test of symmicp_ctx_fgr.
+template <class T>
+__host__ __device__ inline bool ransac_edge_fails(const T P[3][3], const T Q[3][3], T edge2)
+{
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+        const int a = k, b = (k + 1) % 3;
+        const T dp[3] = {P[a][0] - P[b][0], P[a][1] - P[b][1], P[a][2] - P[b][2]};
+        const T dq[3] = {Q[a][0] - Q[b][0], Q[a][1] - Q[b][1], Q[a][2] - Q[b][2]};
+        const T lp = rc_dot(dp, dp), lq = rc_dot(dq, dq);
+        if (lp < edge2 * lq || lq < edge2 * lp) return true;
+    }
+    return false;
+}
+
 // status of the hypothesis drawn as c[0..2] with sample points P[k], Q[k]; Rt is written for EVALUATED and FAR
 template <class T>
 __host__ __device__ inline int ransac_hypothesis(const uint32_t c[3], const T P[3][3], const T Q[3][3], T edge2, T max_dist2, T Rt[12])
 {
     if (c[0] == c[1] || c[1] == c[2] || c[0] == c[2]) return SYMMICP_RANSAC_REPEATED;
-    if (edge2 > (T)0) {
-#pragma unroll
-        for (int k = 0; k < 3; k++) {
-            const int a = k, b = (k + 1) % 3;
-            const T dp[3] = {P[a][0] - P[b][0], P[a][1] - P[b][1], P[a][2] - P[b][2]};
-            const T dq[3] = {Q[a][0] - Q[b][0], Q[a][1] - Q[b][1], Q[a][2] - Q[b][2]};
-            const T lp = rc_dot(dp, dp), lq = rc_dot(dq, dq);
-            if (lp < edge2 * lq || lq < edge2 * lp) return SYMMICP_RANSAC_EDGE;
-        }
-    }
+    if (edge2 > (T)0 && ransac_edge_fails<T>(P, Q, edge2)) return SYMMICP_RANSAC_EDGE;
     const T up[3] = {P[1][0] - P[0][0], P[1][1] - P[0][1], P[1][2] - P[0][2]}, vp[3] = {P[2][0] - P[0][0], P[2][1] - P[0][1], P[2][2] - P[0][2]};
     const T uq[3] = {Q[1][0] - Q[0][0], Q[1][1] - Q[0][1], Q[1][2] - Q[0][2]}, vq[3] = {Q[2][0] - Q[0][0], Q[2][1] - Q[0][1], Q[2][2] - Q[0][2]};
     T wp[3], wq[3];

@@ -444,6 +444,35 @@ void launch_ransac_eval(const float *pq8, uint32_t m, const float *hyp, const ui
                         float max_dist2, int32_t *inliers, hipStream_t s);
 void launch_ransac_argmax(const uint8_t *status, const int32_t *inliers, uint32_t H, unsigned long long *best, hipStream_t s);
 
+// Fast Global Registration (kernels_fgr.hip; symmicp_ctx_fgr).  pq8 as RANSAC's.  Tuple test: flags [trials + 1] (the last word 0) = 1 for
+// an accepted trial; after an exclusive scan of them (rank [trials + 1], rank[trials] = the accepted count) the scatter writes the
+// draws of the trials of rank < max_tuples to set [3 * max_tuples].  The loop: one workgroup, every pass of it in one launch.
+constexpr int kFgrThreads = 512;          // workgroup size of k_fgr_optimize
+constexpr uint32_t kFgrResident = 4096;   // the largest set that stays on chip (gathered once into 96 KB of LDS); above it every pass streams from global memory
+struct FgrOut {                           // what the loop leaves (device memory)
+    float X[16];
+    float mu;
+    int32_t iters, status, reserved;
+    double sums[kNSum];                   // the record of the last pass run
+};
+struct FgrArgs {
+    const float4 *pq;                     // [m][2]: (p, 0), (q, 0)
+    const int32_t *set;                   // [M] rows of pq, or null: element e is row e
+    uint32_t M;
+    float X0[16];                         // X of the first pass
+    float mu0, delta2, division;          // mu before the first pass's schedule step
+    int32_t iterations, decrease_every;
+    int32_t pass_only;                    // 1: one pass at (X0, mu0), no schedule and no solve (symmicp_ctx_fgr_pass)
+    float *weight;                        // [M] or null: l of every element, rewritten each pass
+    float *X_trace;                       // [iterations + 1][16], zeroed, or null
+    double *sums_trace;                   // [iterations][kNSum], zeroed, or null
+    float *mu_trace;                      // [iterations], zeroed, or null
+    FgrOut *out;
+};
+void launch_fgr_tuples(const float *pq8, uint32_t m, uint32_t trials, unsigned long long base, float edge2, uint32_t *flags, hipStream_t s);
+void launch_fgr_scatter(const uint32_t *rank, uint32_t m, uint32_t trials, unsigned long long base, uint32_t max_tuples, int32_t *set, hipStream_t s);
+void launch_fgr_optimize(const FgrArgs &a, hipStream_t s);
+
 // registration evaluation (kernels_eval.hip; symmicp_ctx_evaluate_registration, symmicp_evaluate): K transforms of one source against one
 // indexed target whose tq carries the caller's row in w.  The search runs over source positions (order: position -> caller row, null: the
 // position; gather: the coordinates are stored by caller row and read through order), the sums over caller rows in an order that is a

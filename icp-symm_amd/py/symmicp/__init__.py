@@ -90,6 +90,17 @@ class RansacResult(C.Structure):
                 ("rmse_final", C.c_double), ("transform", C.c_double * 16)]
 
 
+class FgrConfig(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("iterations", C.c_int32), ("decrease_every", C.c_int32), ("max_tuples", C.c_uint32),
+                ("tuple_trials", C.c_uint32), ("max_dist", C.c_float), ("division_factor", C.c_float), ("tuple_scale", C.c_float),
+                ("seed", C.c_uint64)]
+
+
+class FgrResult(C.Structure):
+    _fields_ = [("iterations", C.c_int32), ("inliers", C.c_int32), ("tuples_accepted", C.c_uint32), ("set_size", C.c_uint32),
+                ("mu", C.c_float), ("reserved", C.c_int32), ("weight_sum", C.c_double), ("rmse", C.c_double), ("transform", C.c_double * 16)]
+
+
 class IssConfig(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("salient_radius", C.c_float), ("non_max_radius", C.c_float), ("gamma21", C.c_float),
                 ("gamma32", C.c_float), ("min_neighbors", C.c_int32), ("reserved", C.c_int32)]
@@ -154,6 +165,7 @@ EXPORTS = [
     "symmicp_radius_search", "symmicp_ctx_radius_search", "symmicp_fpfh", "symmicp_ctx_fpfh",
     "symmicp_feature_nn", "symmicp_ctx_feature_nn", "symmicp_feature_correspondences", "symmicp_ctx_feature_correspondences",
     "symmicp_ransac_config_default", "symmicp_ransac", "symmicp_ctx_ransac", "symmicp_ctx_ransac_hypotheses",
+    "symmicp_fgr_config_default", "symmicp_fgr", "symmicp_ctx_fgr", "symmicp_ctx_fgr_pass",
     "symmicp_ctx_index_info", "symmicp_ctx_index_arrays", "symmicp_ctx_source_share", "symmicp_ctx_radix_sort_probe", "symmicp_ctx_scan_probe",
     "symmicp_set_trim_fraction", "symmicp_get_trim_fraction", "symmicp_get_trim_state", "symmicp_ctx_select_probe",
     "symmicp_set_one_to_one", "symmicp_get_one_to_one", "symmicp_set_median_factor", "symmicp_get_median_factor",
@@ -269,6 +281,12 @@ def lib():
     L.symmicp_ransac.argtypes = [C.c_int] + rsc + [fp, C.POINTER(RansacResult), u8p, u8p, i32p]
     L.symmicp_ctx_ransac.argtypes = [vp] + rsc + [fp, C.POINTER(RansacResult), u8p, u8p, i32p]
     L.symmicp_ctx_ransac_hypotheses.argtypes = [vp] + rsc + [fp, u8p, fp]
+    fgc = rsc[:-1] + [C.POINTER(FgrConfig), fp, C.POINTER(FgrResult), i32p, fp, fp, C.POINTER(C.c_double), fp]
+    L.symmicp_fgr_config_default.argtypes = [C.POINTER(FgrConfig)]
+    L.symmicp_fgr_config_default.restype = None
+    L.symmicp_fgr.argtypes = [C.c_int] + fgc
+    L.symmicp_ctx_fgr.argtypes = [vp] + fgc
+    L.symmicp_ctx_fgr_pass.argtypes = [vp, fp, fp, C.c_size_t, fp, C.c_float, C.POINTER(C.c_double), fp]
     u32p, szp = C.POINTER(C.c_uint32), C.POINTER(C.c_size_t)
     L.symmicp_ctx_index_info.argtypes = [vp, C.POINTER(IndexInfo)]
     L.symmicp_ctx_index_arrays.argtypes = [vp, fp, fp, fp, u32p, u32p, fp]
@@ -896,6 +914,54 @@ def ransac(src, tgt, pairs, max_dist, hypotheses=100000, seed=0, edge_ratio=0.9,
     return r
 
 
+def fgr_config(max_dist, iterations=64, decrease_every=4, division_factor=1.4, tuple_scale=0.95, max_tuples=1000, tuple_trials=0, seed=0):
+    cfg = FgrConfig()
+    lib().symmicp_fgr_config_default(C.byref(cfg))
+    cfg.max_dist, cfg.iterations, cfg.decrease_every, cfg.division_factor = float(max_dist), int(iterations), int(decrease_every), float(division_factor)
+    cfg.tuple_scale, cfg.max_tuples, cfg.tuple_trials, cfg.seed = float(tuple_scale), int(max_tuples), int(tuple_trials), int(seed)
+    return cfg
+
+
+def _fgr_call(fn, head, src, tgt, pairs, cfg, want_trace=False):
+    """fn(*head, <the C arguments>) -> (status, result dict).  The dict is filled on failure too."""
+    src, tgt = _cloud(src), _cloud(tgt)
+    pairs = np.ascontiguousarray(pairs, np.int32)
+    if pairs.ndim != 2 or pairs.shape[1] != 2:
+        raise ValueError("pairs must be [m,2]")
+    m, K = pairs.shape[0], max(int(cfg.iterations), 0)
+    cap = max(3 * int(cfg.max_tuples) if cfg.max_tuples else m, 1)
+    X = np.zeros(16, np.float32)
+    res = FgrResult()
+    sel = np.zeros(cap, np.int32)
+    weight = np.zeros(cap, np.float32)
+    trX = np.zeros((K + 1, 16), np.float32) if want_trace else None
+    trS = np.zeros((max(K, 1), 40), np.float64) if want_trace else None
+    trM = np.zeros(max(K, 1), np.float32) if want_trace else None
+    st = fn(*head, _fptr(src), 3, 1, src.shape[0], _fptr(tgt), 3, 1, tgt.shape[0], _i32ptr(pairs), m, C.byref(cfg), _fptr(X), C.byref(res),
+            _i32ptr(sel), _fptr(weight), None if trX is None else _fptr(trX),
+            None if trS is None else trS.ctypes.data_as(C.POINTER(C.c_double)), None if trM is None else _fptr(trM))
+    M = int(res.set_size)
+    r = dict(status=st, transform=X.reshape(4, 4), transform64=np.array(res.transform[:], np.float64).reshape(4, 4),
+             iterations=res.iterations, inliers=res.inliers, tuples_accepted=res.tuples_accepted, set_size=M, mu=np.float32(res.mu),
+             weight_sum=res.weight_sum, rmse=res.rmse, set=sel[:M].copy(), weights=weight[:M].copy())
+    if want_trace:
+        r["X_trace"], r["sums_trace"], r["mu_trace"] = trX.reshape(K + 1, 4, 4), trS[:K], trM[:K]
+    return st, r
+
+
+def fgr(src, tgt, pairs, max_dist, iterations=64, decrease_every=4, division_factor=1.4, tuple_scale=0.95, max_tuples=1000, tuple_trials=0,
+        seed=0, device=-1, want_trace=False):
+    """Fast Global Registration from correspondences with outliers (symmicp_fgr): a tuple test, then the whole graduated-non-convexity
+    loop in one launch -> dict(transform [4,4] f32, transform64, iterations, inliers, rmse, tuples_accepted, set_size, set [M], weights [M],
+    mu, weight_sum[, X_trace [K+1,4,4], sums_trace [K,40], mu_trace [K]]).  Raises SymmIcpError (ERR_NO_CONSENSUS: no trial passed the
+    tuple test; ERR_DEGENERATE: a solve failed)."""
+    st, r = _fgr_call(lib().symmicp_fgr, (int(device),), src, tgt, pairs,
+                      fgr_config(max_dist, iterations, decrease_every, division_factor, tuple_scale, max_tuples, tuple_trials, seed), want_trace)
+    if st != OK:
+        raise SymmIcpError(st, "fgr")
+    return r
+
+
 def batch_config(**kw):
     """symmicp_batch_config with its defaults (PAPER, 10 iterations, threshold 1, gates and eps rule off), then the given fields"""
     cfg = BatchConfig()
@@ -1501,6 +1567,28 @@ class Engine:
                                                         _fptr(piv)))
         return hyp, status, piv.reshape(2, 3)
 
+    def fgr(self, src, tgt, pairs, max_dist, iterations=64, decrease_every=4, division_factor=1.4, tuple_scale=0.95, max_tuples=1000,
+            tuple_trials=0, seed=0, want_trace=False, check=True):
+        """fgr on this context (symmicp_ctx_fgr) -> the dict of symmicp.fgr; check=False returns it on failure too (status set)"""
+        st, r = _fgr_call(self._L.symmicp_ctx_fgr, (self._h,), src, tgt, pairs,
+                          fgr_config(max_dist, iterations, decrease_every, division_factor, tuple_scale, max_tuples, tuple_trials, seed), want_trace)
+        if check:
+            self._chk(st)
+        return r
+
+    def fgr_pass(self, p, q, X, mu):
+        """test entry (symmicp_ctx_fgr_pass): one pass of the FGR loop on pivoted points p, q [M,3] at X and mu, through the loop
+        kernel's accumulation and reduction -> (record [40] f64, weights [M] f32)"""
+        p, q = _cloud(p), _cloud(q)
+        if p.shape != q.shape:
+            raise ValueError("p and q must have the same shape")
+        X = np.ascontiguousarray(X, np.float32).reshape(16)
+        sums = np.zeros(40, np.float64)
+        w = np.zeros(max(len(p), 1), np.float32)
+        self._chk(self._L.symmicp_ctx_fgr_pass(self._h, _fptr(p), _fptr(q), len(p), _fptr(X), C.c_float(mu),
+                                               sums.ctypes.data_as(C.POINTER(C.c_double)), _fptr(w)))
+        return sums, w[:len(p)]
+
     def batch_align(self, src, src_n, tgt, tgt_n, problems, guesses=None, trace=False, **cfg):
         """batch_align on this context's stream and scratch arena; its clouds, options and loop state stay as they are"""
         st, r = _batch_align(self._L.symmicp_ctx_batch_align, (self._h,), src, src_n, tgt, tgt_n, problems, guesses, trace, cfg)
@@ -1872,25 +1960,32 @@ class MyICP:
 
     def setGlobalInit(self, fpfh_radius, max_dist, voxel_leaf=0.0, normal_k=10, hypotheses=100000, seed=0, mutual=True, max_ratio=0.0,
                       edge_ratio=0.9, refits=1, iss=False, iss_salient_radius=0.0, iss_non_max_radius=0.0, iss_gamma21=0.975, iss_gamma32=0.975,
-                      iss_min_neighbors=5):
+                      iss_min_neighbors=5, method="ransac", fgr_iterations=64, fgr_division_factor=1.4, fgr_tuple_scale=0.95, fgr_max_tuples=1000):
         """global initialisation: with it set and no guess given, align() first voxel-downsamples both clouds with voxel_leaf (0: as
         given), estimates normals on the downsampled clouds when the caller supplied none (normal_k neighbours, viewpoint at the
         origin), computes FPFH features at fpfh_radius, their correspondences and a RANSAC transform, and starts the ordinary
         alignment (voxel levels included) from it.  A failure (ERR_NO_CONSENSUS among them) raises SymmIcpError.  FPFH matching
         needs normals oriented alike in both clouds.  With iss the features are still computed on the full (downsampled) clouds, but only
         the rows of their ISS keypoints (Engine.iss_keypoints with the iss_* values) are matched and given to RANSAC; fewer than 3
-        keypoints in either cloud raises ERR_NO_CONSENSUS (no fall-back to the full cloud)."""
+        keypoints in either cloud raises ERR_NO_CONSENSUS (no fall-back to the full cloud).  method "fgr" gives the correspondences to
+        Fast Global Registration (Engine.fgr with max_dist, seed and the fgr_* values) instead of RANSAC, which is not run then; every
+        other step is the same."""
+        if method not in ("ransac", "fgr"):
+            raise ValueError("method must be 'ransac' or 'fgr'")
         self._global = dict(fpfh_radius=float(fpfh_radius), max_dist=float(max_dist), voxel_leaf=float(voxel_leaf), normal_k=int(normal_k),
                             hypotheses=int(hypotheses), seed=int(seed), mutual=bool(mutual), max_ratio=float(max_ratio),
                             edge_ratio=float(edge_ratio), refits=int(refits), iss=bool(iss), iss_salient_radius=float(iss_salient_radius),
                             iss_non_max_radius=float(iss_non_max_radius), iss_gamma21=float(iss_gamma21), iss_gamma32=float(iss_gamma32),
-                            iss_min_neighbors=int(iss_min_neighbors))
+                            iss_min_neighbors=int(iss_min_neighbors), method=method, fgr_iterations=int(fgr_iterations),
+                            fgr_division_factor=float(fgr_division_factor), fgr_tuple_scale=float(fgr_tuple_scale),
+                            fgr_max_tuples=int(fgr_max_tuples))
 
     def clearGlobalInit(self):
         self._global = None
 
     def globalResult(self):
-        """the RANSAC result dict of the last align() that ran the initialisation (plus correspondences, source_points, target_points)"""
+        """the RANSAC (or, with method "fgr", the FGR) result dict of the last align() that ran the initialisation (plus method,
+        correspondences, source_points, target_points)"""
         return self.global_result
 
     def _global_init(self, e):
@@ -1921,10 +2016,25 @@ class MyICP:
             pairs, _ = e.feature_correspondences(fs, ft, g["mutual"], g["max_ratio"])
         if len(pairs) < 3:
             raise SymmIcpError(ERR_NO_CONSENSUS, "global initialisation: fewer than 3 feature correspondences")
-        r = e.ransac(src, tgt, pairs, g["max_dist"], g["hypotheses"], g["seed"], g["edge_ratio"], g["refits"], check=False)
+        fgr = g["method"] == "fgr"
+        if fgr:
+            r = e.fgr(src, tgt, pairs, g["max_dist"], iterations=g["fgr_iterations"], division_factor=g["fgr_division_factor"],
+                      tuple_scale=g["fgr_tuple_scale"], max_tuples=g["fgr_max_tuples"], seed=g["seed"], check=False)
+        else:
+            r = e.ransac(src, tgt, pairs, g["max_dist"], g["hypotheses"], g["seed"], g["edge_ratio"], g["refits"], check=False)
+        r.update(method=g["method"])
         r.update(correspondences=len(pairs), source_points=len(src), target_points=len(tgt),
                  source_keypoints=0 if kp is None else len(kp[0]), target_keypoints=0 if kp is None else len(kp[1]))
         self.global_result = r
+        if fgr:
+            if self._cfg["verbose"]:
+                print("global init: %d -> %d source and %d -> %d target points, %d and %d ISS keypoints, %d correspondences, FGR: %d tuples accepted, "
+                      "%d set elements, %d iterations, %d inliers" % (len(self.cloud_src), len(src), len(self.cloud_tgt), len(tgt), r["source_keypoints"],
+                                                                      r["target_keypoints"], len(pairs), r["tuples_accepted"], r["set_size"],
+                                                                      r["iterations"], r["inliers"]), flush=True)
+            if r["status"] != OK:
+                raise SymmIcpError(r["status"], "global initialisation: FGR: " + (e._L.symmicp_last_error(e._h) or b"").decode())
+            return r["transform"]
         if self._cfg["verbose"] and kp is not None:
             print("global init: %d -> %d source and %d -> %d target points, %d and %d ISS keypoints, %d correspondences, %d of %d hypotheses evaluated, "
                   "%d -> %d inliers" % (len(self.cloud_src), len(src), len(self.cloud_tgt), len(tgt), len(kp[0]), len(kp[1]), len(pairs), r["evaluated"],

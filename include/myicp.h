@@ -127,6 +127,15 @@ public:
 		float iss_non_max_radius = 0.f;   // required with iss: finite, > 0
 		float iss_gamma21 = 0.975f, iss_gamma32 = 0.975f;
 		int iss_min_neighbors = 5;
+		// The estimator the correspondences go to: RANSAC (the default) or Fast Global Registration (symmicp_ctx_fgr: a tuple test and a
+		// graduated-non-convexity loop, no hypothesis count to tune).  FGR shares max_dist and seed with RANSAC and ignores hypotheses,
+		// edge_ratio and refits; with it RANSAC is not run, every other step is the same, and a failure is returned as RANSAC's is.
+		enum Method { RANSAC = 0, FGR = 1 };
+		Method method = RANSAC;
+		int fgr_iterations = 64;
+		float fgr_division_factor = 1.4f;
+		float fgr_tuple_scale = 0.95f;
+		unsigned fgr_max_tuples = 1000;
 	};
 	struct GlobalResult {
 		symmicp_ransac_result ransac;  // of the last align() that ran the initialisation
@@ -135,6 +144,7 @@ public:
 		size_t source_points, target_points;   // after downsampling
 		size_t source_keypoints, target_keypoints;   // with GlobalInit::iss: the ISS keypoints of each (0 without)
 		int status;                    // symmicp_status of the initialisation
+		symmicp_fgr_result fgr;        // with GlobalInit::FGR: its result (ransac stays zero), else zero
 	};
 	void setGlobalInit(const GlobalInit &g) { global_ = g; have_global_ = true; }
 	void clearGlobalInit() { have_global_ = false; }

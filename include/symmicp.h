@@ -38,7 +38,8 @@ typedef enum {
     SYMMICP_ERR_HIP = 5,           /* HIP runtime error or no gfx950-capable device */
     SYMMICP_ERR_STATE = 6,         /* call out of order (e.g. step before begin) */
     SYMMICP_ERR_COMM = 7,          /* RCCL or shared-memory exchange error */
-    SYMMICP_ERR_NO_CONSENSUS = 8   /* symmicp_ctx_ransac: no hypothesis was evaluated, or the best one has fewer than 3 inliers */
+    SYMMICP_ERR_NO_CONSENSUS = 8   /* symmicp_ctx_ransac: no hypothesis was evaluated, or the best one has fewer than 3 inliers;
+                                      symmicp_ctx_fgr: no trial passed the tuple test */
 } symmicp_status;
 
 /* Arithmetic mode.  QUIRKS reproduces the reference exactly as written:
@@ -783,6 +784,78 @@ int symmicp_ctx_ransac_hypotheses(symmicp_ctx *ctx, const float *src_xyz, size_t
                                   const float *tgt_xyz, size_t tgt_row_stride, size_t tgt_col_stride, size_t nt,
                                   const int32_t *pairs, size_t m, const symmicp_ransac_config *cfg, float *hyp_out,
                                   uint8_t *status_out, float pivots_out[6]);
+
+/* symmicp_ctx_fgr: Fast Global Registration (Zhou, Park, Koltun, ECCV 2016; Open3D's registration_fgr_based_on_correspondence):
+ * a rigid transform from correspondences with outliers by a tuple test and a graduated-non-convexity (GNC) loop, the whole loop in
+ * one launch.  A pure function of its inputs: no hypothesis count, no lucky sample.  Arguments and pivots as symmicp_ctx_ransac.
+ *   Pivots.  cs, ct = the fp64 means of the m paired source / target points, rounded to fp32; the device works on
+ *     p_k = src[pairs[k][0]] - cs, q_k = tgt[pairs[k][1]] - ct (fp32): FGR's centring, so the loop starts from the identity.
+ *   Tuple test.  Trial t (0 <= t < tuple_trials; 0 means min(100 m, 2^24)) draws c_j = ((u(3t + j) >> 32) * m) >> 32, j = 0, 1, 2,
+ *     u = the SplitMix64 sequence of (seed, stream 1): RANSAC's with
+ *       base = mix64(seed * 0x9E3779B97F4A7C15 + 0xD1B54A32D192ED03 + 0x2545F4914F6CDD1D).
+ *     A trial is accepted iff its draws are distinct and no edge fails RANSAC's EDGE check with e = tuple_scale (e^2 in fp32).
+ *     The optimisation set is the draws of the first min(accepted, max_tuples) accepted trials in ascending t, three per tuple,
+ *     duplicates kept (a pair in several tuples counts several times); M = its length.  max_tuples == 0: the set is all m pairs
+ *     in order, M = m.  No accepted trial: SYMMICP_ERR_NO_CONSENSUS, transform = identity.
+ *   Schedule (fp32).  D2 = the maximum over all m pairs of max(|p|^2, |q|^2), |v|^2 = (x x + y y) + z z; mu = D2;
+ *     d2 = max_dist * max_dist.  At the top of iteration k = 0 .. iterations - 1: if k % decrease_every == 0 and mu > d2 then
+ *     mu = mu / division_factor, and if then mu < d2, mu = d2.
+ *   Pass k at X_k (X_0 = I), for each element of the set (fp32, unfused):  p' = ((X0 x + X1 y) + X2 z) + X3 per row;
+ *     d = p' - q; r2 = (dx dx + dy dy) + dz dz; t = mu / (mu + r2); l = t * t (the line-process weight: Geman-McClure at scale
+ *     sqrt(mu)).  Three rows of PLANE's form with n = e_x, e_y, e_z -- v = (p' x n, n), c = d . n -- each at weight l, accumulated
+ *     in fp64 into a record of PLANE's weighted shape about a zero pivot: [0..20] sum l v v^T, [21..26] sum l v c,
+ *     [27..29] sum l p', [30..32] sum l q, [33] 0, [34] sum l, [35] sum l r2, [36] sum r2, [37] M.
+ *   Solve.  symmicp_solve(SYMMICP_MODE_PLANE, ...) on that record, run on the device; X_{k+1} = increment * X_k (fp32).  A solve
+ *     that fails ends the loop: SYMMICP_ERR_DEGENERATE with the iterations completed and X_k as the transform.
+ *   Result.  T = T(ct) X T(-cs) in fp64 on the host, transform16 its fp32 rounding; inliers and rmse over all m pairs at
+ *     |T x - y|^2 <= max_dist^2 (fp64).  There is no refit after the loop.
+ * Outputs: transform16, result (required); set_out [3 * max_tuples, or m when max_tuples == 0] (int32 rows of `pairs`; the first
+ * set_size are written); weight_out [same capacity]: l of the last pass run; X_trace [iterations + 1][16] (X_k; rows after the
+ * last one reached are zero), sums_trace [iterations][40], mu_trace [iterations]; all five may be NULL.
+ * SYMMICP_ERR_ARG: NULL src_xyz / tgt_xyz / pairs / cfg / transform16 / result; ns, nt == 0 or > 2^31 - 1; m < 3 or > 2^31 - 1;
+ * m > 2^20 with max_tuples == 0; a pair row out of range; a non-finite paired coordinate; cfg->struct_size; max_dist not finite
+ * and > 0; iterations outside 1 .. 1024; decrease_every < 1; division_factor not finite and > 1; tuple_scale outside (0, 1];
+ * max_tuples > 2^18; tuple_trials > 2^24. */
+typedef struct {
+    uint32_t struct_size;      /* = sizeof(symmicp_fgr_config), checked */
+    int32_t iterations;        /* 1 .. 1024, default 64 */
+    int32_t decrease_every;    /* >= 1, default 4 */
+    uint32_t max_tuples;       /* 0 .. 2^18, default 1000; 0: the tuple test is off */
+    uint32_t tuple_trials;     /* 1 .. 2^24; default 0: min(100 m, 2^24) */
+    float max_dist;            /* delta: finite, > 0 */
+    float division_factor;     /* finite, > 1, default 1.4 */
+    float tuple_scale;         /* 0 < s <= 1, default 0.95 */
+    uint64_t seed;
+} symmicp_fgr_config;
+typedef struct {
+    int32_t iterations;        /* iterations completed */
+    int32_t inliers;           /* pairs within max_dist of the result, of all m */
+    uint32_t tuples_accepted;  /* trials that passed the tuple test (0 with the test off) */
+    uint32_t set_size;         /* M */
+    float mu;                  /* of the last pass run */
+    int32_t reserved;
+    double weight_sum;         /* sum l of the last pass run */
+    double rmse;               /* over the inliers */
+    double transform[16];      /* the result in fp64, row-major; transform16 is this matrix rounded to fp32 */
+} symmicp_fgr_result;
+/* iterations 64, decrease_every 4, max_tuples 1000, tuple_trials 0, max_dist 0 (the caller sets it), division_factor 1.4,
+ * tuple_scale 0.95, seed 0 */
+void symmicp_fgr_config_default(symmicp_fgr_config *cfg);
+int symmicp_ctx_fgr(symmicp_ctx *ctx, const float *src_xyz, size_t src_row_stride, size_t src_col_stride, size_t ns,
+                    const float *tgt_xyz, size_t tgt_row_stride, size_t tgt_col_stride, size_t nt,
+                    const int32_t *pairs, size_t m, const symmicp_fgr_config *cfg, float transform16[16],
+                    symmicp_fgr_result *result, int32_t *set_out, float *weight_out, float *X_trace, double *sums_trace,
+                    float *mu_trace);
+int symmicp_fgr(int device, const float *src_xyz, size_t src_row_stride, size_t src_col_stride, size_t ns,
+                const float *tgt_xyz, size_t tgt_row_stride, size_t tgt_col_stride, size_t nt,
+                const int32_t *pairs, size_t m, const symmicp_fgr_config *cfg, float transform16[16],
+                symmicp_fgr_result *result, int32_t *set_out, float *weight_out, float *X_trace, double *sums_trace,
+                float *mu_trace);
+/* test entry: one pass of the loop on host arrays p, q [M][3] (already pivoted; 1 <= M <= 2^20) at X16 and mu, through the loop
+ * kernel's own accumulation and reduction: sums_out [40] (required), weight_out [M] (may be NULL).
+ * SYMMICP_ERR_ARG: NULL p / q / X16 / sums_out; M out of range; a non-finite value in p, q, X16 or mu. */
+int symmicp_ctx_fgr_pass(symmicp_ctx *ctx, const float *p, const float *q, size_t M, const float X16[16], float mu,
+                         double *sums_out, float *weight_out);
 
 /* ---- voxel-grid downsampling (PCL's pcl::VoxelGrid, Open3D's voxel_down_sample), on the GPU -----------------------
  * Every point falls into the cubic voxel of edge `leaf` that holds it; each occupied voxel with at least min_points points
