@@ -10,6 +10,7 @@
 //   engine_probe.cpp     test entries: read-back of the target index and the source share, the sort and the scan on caller arrays
 //   engine_eval.cpp      registration evaluation (symmicp_evaluate_registration, symmicp_evaluate, symmicp_information_from_sums)
 //   engine_fgr.cpp       Fast Global Registration (symmicp_ctx_fgr, symmicp_ctx_fgr_pass)
+//   engine_posegraph.cpp pose-graph optimisation (symmicp_ctx_posegraph_optimize, symmicp_ctx_posegraph_pass, the two host helpers)
 //   engine_ndt.cpp       SYMMICP_MODE_NDT: configuration, Gauss constants, the voxel map (build, read-back, symmicp_ctx_ndt_map), pass arguments
 #pragma once
 #include <hip/hip_runtime.h>

@@ -473,6 +473,35 @@ void launch_fgr_tuples(const float *pq8, uint32_t m, uint32_t trials, unsigned l
 void launch_fgr_scatter(const uint32_t *rank, uint32_t m, uint32_t trials, unsigned long long base, uint32_t max_tuples, int32_t *set, hipStream_t s);
 void launch_fgr_optimize(const FgrArgs &a, hipStream_t s);
 
+// pose-graph optimisation (kernels_posegraph.hip; symmicp_ctx_posegraph_optimize): one launch of one workgroup = one Levenberg-Marquardt
+// iteration at the poses X: edge errors and blocks, the nodes' gathers, the block-Jacobi PCG, the trial poses and their cost, a record.
+// Every array is fp64 in device memory.  An edge owns two slots of the incidence list (CSR by node, sorted by edge index): slot_s in its
+// source's list, slot_t in its target's; what an edge contributes to a node goes to its slot, and the node adds its slots in order.
+constexpr int kPgThreads = 256;           // workgroup size of k_posegraph_iteration
+struct PgRecord {                         // what one launch leaves (device memory)
+    double cost, cost_trial, model_decrease, grad_max, delta_max, hdiag_max, lambda, cg_residual;
+    int32_t cg_iterations, status;
+};
+struct PgArgs {
+    uint32_t n, m;
+    int32_t ref, cg_max;
+    double mu, lambda, cg_tol;            // lambda < 0: 1e-5 * the largest diagonal entry of H (the first iteration)
+    const double *X;                      // [n][12]: the top three rows of every pose
+    double *Xtrial;                       // [n][12]: X Exp(d); the reference node's rows copied
+    const int32_t *es, *et, *eunc;        // [m]
+    const double *T;                      // planar [12][m]: R_T row-major, t_T
+    const double *L;                      // planar [21][m]: the upper triangle of the information matrix, row-major
+    const uint32_t *off;                  // [n + 1]: the incidence list's row starts
+    const uint32_t *slot_s, *slot_t;      // [m]
+    double *e, *c, *l, *l_trial;          // [m][6], [m], [m], [m]
+    double *slot_v;                       // [2 m][6]: gradient terms, then the matvec's terms
+    double *slot_h;                       // [2 m][36]: diagonal-block terms
+    double *g, *hdiag, *chol;             // [n][6], [n][36], [n][21]: the lower Cholesky factor of H_ii + lambda I, row-major triangle
+    double *x, *r, *z, *p;                // [n][6]: the solve's vectors (x = d)
+    PgRecord *rec;
+};
+void launch_posegraph_iteration(const PgArgs &a, hipStream_t s);
+
 // registration evaluation (kernels_eval.hip; symmicp_ctx_evaluate_registration, symmicp_evaluate): K transforms of one source against one
 // indexed target whose tq carries the caller's row in w.  The search runs over source positions (order: position -> caller row, null: the
 // position; gather: the coordinates are stored by caller row and read through order), the sums over caller rows in an order that is a

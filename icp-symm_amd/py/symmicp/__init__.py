@@ -139,6 +139,37 @@ class Evaluation(C.Structure):
 EVAL_MAX_TRANSFORMS = 4096
 
 
+class PoseEdge(C.Structure):
+    """symmicp_pose_edge: T takes the source node's frame to the target node's (align with cloud s as source, cloud t as target), the
+    information matrix is that pair's evaluation (rotation first), uncertain = 1 for a loop closure"""
+    _fields_ = [("source", C.c_int32), ("target", C.c_int32), ("uncertain", C.c_int32), ("reserved", C.c_int32),
+                ("transform", C.c_double * 16), ("information", C.c_double * 36)]
+
+
+class PosegraphConfig(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("max_iterations", C.c_int32), ("reference_node", C.c_int32), ("cg_max_iterations", C.c_int32),
+                ("max_dist", C.c_double), ("preference_loop_closure", C.c_double), ("line_process_weight", C.c_double),
+                ("edge_prune_threshold", C.c_double), ("min_relative_decrease", C.c_double), ("min_increment", C.c_double),
+                ("cg_tolerance", C.c_double)]
+
+
+class PosegraphResult(C.Structure):
+    _fields_ = [("status", C.c_int32), ("iterations", C.c_int32), ("accepted_steps", C.c_int32), ("stop_reason", C.c_int32),
+                ("pruned", C.c_int32), ("cg_iterations", C.c_int32), ("cost_initial", C.c_double), ("cost_final", C.c_double),
+                ("mu", C.c_double), ("lambda_final", C.c_double), ("grad_max", C.c_double)]
+
+
+class PosegraphIteration(C.Structure):
+    """symmicp_posegraph_iteration: the record of one Levenberg-Marquardt iteration"""
+    _fields_ = [("cost", C.c_double), ("cost_trial", C.c_double), ("model_decrease", C.c_double), ("grad_max", C.c_double),
+                ("delta_max", C.c_double), ("hdiag_max", C.c_double), ("lambda_", C.c_double), ("cg_residual", C.c_double),
+                ("cg_iterations", C.c_int32), ("accepted", C.c_int32), ("status", C.c_int32), ("reserved", C.c_int32)]
+
+
+POSEGRAPH_MAX_NODES, POSEGRAPH_MAX_EDGES = 1024, 16384
+POSEGRAPH_STOP_MAX_ITERATIONS, POSEGRAPH_STOP_DECREASE, POSEGRAPH_STOP_INCREMENT = 1, 2, 3
+
+
 class IndexInfo(C.Structure):
     """symmicp_index_info: what symmicp_ctx_index_info reads back of a target index (tests)"""
     _fields_ = [("struct_size", C.c_int32), ("n", C.c_uint32), ("grid_level", C.c_int32), ("gdim", C.c_int32), ("origin", C.c_float * 3),
@@ -181,6 +212,8 @@ EXPORTS = [
     "symmicp_radius_outlier_removal", "symmicp_ctx_radius_outlier_removal",
     "symmicp_ndt_config_default", "symmicp_set_ndt", "symmicp_get_ndt", "symmicp_ndt_gauss", "symmicp_ndt_weight", "symmicp_get_ndt_state",
     "symmicp_ctx_ndt_map", "symmicp_ndt_map", "symmicp_get_ndt_map",
+    "symmicp_posegraph_config_default", "symmicp_posegraph_optimize", "symmicp_ctx_posegraph_optimize", "symmicp_ctx_posegraph_pass",
+    "symmicp_posegraph_edge_error", "symmicp_posegraph_line_weight",
 ]
 
 _lib = None
@@ -357,6 +390,17 @@ def lib():
     L.symmicp_ndt_map.argtypes = [C.c_int] + nmi + nmo
     L.symmicp_ctx_ndt_map.argtypes = [vp] + nmi + nmo
     L.symmicp_get_ndt_map.argtypes = [vp] + nmo
+    pgc, pge, pgi = C.POINTER(PosegraphConfig), C.POINTER(PoseEdge), C.POINTER(PosegraphIteration)
+    pgo = [dp, C.c_size_t, pge, C.c_size_t, pgc, dp, C.POINTER(PosegraphResult), dp, C.POINTER(C.c_uint8), pgi]
+    L.symmicp_posegraph_config_default.argtypes = [pgc]
+    L.symmicp_posegraph_config_default.restype = None
+    L.symmicp_posegraph_optimize.argtypes = [C.c_int] + pgo
+    L.symmicp_ctx_posegraph_optimize.argtypes = [vp] + pgo
+    L.symmicp_ctx_posegraph_pass.argtypes = [vp, dp, C.c_size_t, pge, C.c_size_t, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_int32,
+                                             dp, dp, dp, dp, dp, dp, pgi]
+    L.symmicp_posegraph_edge_error.argtypes = [dp, dp, dp, dp]
+    L.symmicp_posegraph_line_weight.argtypes = [C.c_double, C.c_double]
+    L.symmicp_posegraph_line_weight.restype = C.c_double
     _lib = L
     return L
 
@@ -1106,6 +1150,156 @@ def evaluate_registration(src, tgt, transforms=None, max_dist=0.0, device=-1, wa
     return r[0] if single else r
 
 
+def _dptr(a):
+    return a.ctypes.data_as(C.POINTER(C.c_double))
+
+
+def posegraph_config(max_dist=0.0, max_iterations=100, reference_node=0, cg_max_iterations=0, preference_loop_closure=1.0,
+                     line_process_weight=0.0, edge_prune_threshold=0.25, min_relative_decrease=1e-6, min_increment=1e-9, cg_tolerance=1e-10):
+    cfg = PosegraphConfig()
+    lib().symmicp_posegraph_config_default(C.byref(cfg))
+    cfg.max_dist, cfg.max_iterations, cfg.reference_node, cfg.cg_max_iterations = float(max_dist), int(max_iterations), int(reference_node), int(cg_max_iterations)
+    cfg.preference_loop_closure, cfg.line_process_weight, cfg.edge_prune_threshold = float(preference_loop_closure), float(line_process_weight), float(edge_prune_threshold)
+    cfg.min_relative_decrease, cfg.min_increment, cfg.cg_tolerance = float(min_relative_decrease), float(min_increment), float(cg_tolerance)
+    return cfg
+
+
+def pose_edges(edges):
+    """a (PoseEdge * m) array from one, or from a sequence of PoseEdge or of (source, target, uncertain, T [4,4], information [6,6])"""
+    if isinstance(edges, C.Array) and edges._type_ is PoseEdge:
+        return edges
+    out = (PoseEdge * max(len(edges), 1))()
+    for k, e in enumerate(edges):
+        if isinstance(e, PoseEdge):
+            out[k] = e
+            continue
+        s, t, unc, T, L = e
+        T, L = np.ascontiguousarray(T, np.float64), np.ascontiguousarray(L, np.float64)
+        if T.shape != (4, 4) or L.shape != (6, 6):
+            raise ValueError("an edge is (source, target, uncertain, T [4,4], information [6,6])")
+        out[k].source, out[k].target, out[k].uncertain = int(s), int(t), int(bool(unc))
+        out[k].transform[:] = T.reshape(16).tolist()
+        out[k].information[:] = L.reshape(36).tolist()
+    return out
+
+
+def _poses(poses):
+    X = np.ascontiguousarray(poses, np.float64)
+    if X.ndim != 3 or X.shape[1:] != (4, 4):
+        raise ValueError("poses must be [n,4,4]")
+    return X
+
+
+def _posegraph_call(fn, head, poses, edges, cfg, want_trace=False):
+    """fn(*head, <the C arguments>) -> (status, result dict).  The dict is filled on failure too."""
+    X, m = _poses(poses), len(edges)
+    E = pose_edges(edges)
+    out = np.zeros_like(X)
+    res = PosegraphResult()
+    w, pr = np.zeros(max(m, 1), np.float64), np.zeros(max(m, 1), np.uint8)
+    K = max(int(cfg.max_iterations), 1)
+    tr = (PosegraphIteration * K)() if want_trace else None
+    st = fn(*head, _dptr(X), len(X), E, m, C.byref(cfg), _dptr(out), C.byref(res), _dptr(w), pr.ctypes.data_as(C.POINTER(C.c_uint8)), tr)
+    r = dict(status=st, poses=out, weights=w[:m], pruned=pr[:m].astype(bool), iterations=res.iterations, accepted_steps=res.accepted_steps,
+             stop_reason=res.stop_reason, pruned_count=res.pruned, cg_iterations=res.cg_iterations, cost_initial=res.cost_initial,
+             cost_final=res.cost_final, mu=res.mu, lambda_final=res.lambda_final, grad_max=res.grad_max)
+    if want_trace:
+        r["trace"] = [_pg_iteration(tr[k]) for k in range(min(max(res.iterations, 0), K))]
+    return st, r
+
+
+def _pg_iteration(t):
+    return dict(cost=t.cost, cost_trial=t.cost_trial, model_decrease=t.model_decrease, grad_max=t.grad_max, delta_max=t.delta_max,
+                hdiag_max=t.hdiag_max, lam=t.lambda_, cg_residual=t.cg_residual, cg_iterations=t.cg_iterations, accepted=bool(t.accepted),
+                status=t.status)
+
+
+def posegraph_optimize(poses, edges, max_dist=0.0, device=-1, want_trace=False, **cfg):
+    """Multiway registration's back end (symmicp_posegraph_optimize; include/symmicp.h has the definitions): Levenberg-Marquardt over the
+    poses [n,4,4] (node frame -> world) of a pose graph whose edges are PoseEdge or (source, target, uncertain, T, information) entries,
+    with a line process on the uncertain ones -> dict(poses [n,4,4] f64, weights [m], pruned [m] bool, iterations, accepted_steps,
+    stop_reason, pruned_count, cg_iterations, cost_initial, cost_final, mu, lambda_final, grad_max[, trace]).  cfg: the fields of
+    posegraph_config.  Raises SymmIcpError."""
+    st, r = _posegraph_call(lib().symmicp_posegraph_optimize, (int(device),), poses, edges, posegraph_config(max_dist, **cfg), want_trace)
+    if st != OK:
+        raise SymmIcpError(st, "posegraph_optimize")
+    return r
+
+
+def posegraph_edge_error(Xs, Xt, T):
+    """e = (w, tau) of one edge at the poses Xs, Xt (symmicp_posegraph_edge_error, a pure host function)"""
+    a = [np.ascontiguousarray(v, np.float64).reshape(16) for v in (Xs, Xt, T)]
+    e = np.zeros(6, np.float64)
+    st = lib().symmicp_posegraph_edge_error(_dptr(a[0]), _dptr(a[1]), _dptr(a[2]), _dptr(e))
+    if st != OK:
+        raise SymmIcpError(st, "posegraph_edge_error")
+    return e
+
+
+def posegraph_line_weight(mu, c):
+    return float(lib().symmicp_posegraph_line_weight(float(mu), float(c)))
+
+
+def build_pose_graph(clouds, normals, pairs, max_dist, **engine_kwargs):
+    """The front end of multiway registration: every pair (s, t, uncertain, guess or None) of `pairs` is registered with cloud s as source
+    and cloud t as target on one Engine(**engine_kwargs) (set_target, set_source, align from the guess) and scored by
+    evaluate_registration at max_dist -> (edges, poses): the edges as (s, t, uncertain, T [4,4] f64 -- the fp32 result with its rotation
+    block moved to the nearest rotation --, information [6,6]) and initial
+    poses [n,4,4] chained along the certain edges from node 0 (X_s = X_t T; a node no certain edge reaches is chained along an uncertain
+    one)."""
+    n = len(clouds)
+    edges = []
+    with Engine(**engine_kwargs) as e:
+        for s, t, unc, guess in pairs:
+            e.set_target(clouds[t], normals[t])
+            e.set_source(clouds[s], normals[s])
+            r = e.align(guess, check=True)
+            ev = e.evaluate_registration(clouds[s], clouds[t], r["transform"], max_dist)
+            edges.append((int(s), int(t), int(bool(unc)), _nearest_rigid(r["transform"]), ev["information"]))
+    poses = [None] * n
+    poses[0] = np.eye(4)
+    for certain_only in (True, False):
+        grown = True
+        while grown:
+            grown = False
+            for s, t, unc, T, _ in edges:
+                if unc and certain_only:
+                    continue
+                if poses[t] is not None and poses[s] is None:
+                    poses[s], grown = poses[t] @ T, True
+                elif poses[s] is not None and poses[t] is None:
+                    poses[t], grown = poses[s] @ _inverse_rigid64(T), True
+    if any(p is None for p in poses):
+        raise ValueError("the pairs do not connect every cloud to cloud 0")
+    return edges, np.stack(poses)
+
+
+def _nearest_rigid(T):
+    """an fp32 transform as fp64 with its rotation block moved to the nearest rotation (SVD): an fp32 rotation is orthonormal to 1e-7
+    only, and chained poses would add that up"""
+    out = np.eye(4)
+    U, _, Vt = np.linalg.svd(np.asarray(T, np.float64)[:3, :3])
+    out[:3, :3] = U @ np.diag([1.0, 1.0, np.linalg.det(U @ Vt)]) @ Vt
+    out[:3, 3] = np.asarray(T, np.float64)[:3, 3]
+    return out
+
+
+def _inverse_rigid64(T):
+    T = np.asarray(T, np.float64)
+    out = np.eye(4)
+    out[:3, :3] = T[:3, :3].T
+    out[:3, 3] = -T[:3, :3].T @ T[:3, 3]
+    return out
+
+
+def multiway_registration(clouds, normals, pairs, max_dist, device=-1, want_trace=False, engine_kwargs=None, **cfg):
+    """build_pose_graph followed by posegraph_optimize -> its dict, plus edges and initial_poses"""
+    edges, poses = build_pose_graph(clouds, normals, pairs, max_dist, **(engine_kwargs or {}))
+    r = posegraph_optimize(poses, edges, max_dist, device=device, want_trace=want_trace, **cfg)
+    r.update(edges=edges, initial_poses=poses)
+    return r
+
+
 def shard_range(n, nranks, rank):
     b, c = C.c_size_t(0), C.c_size_t(0)
     st = lib().symmicp_shard_range(n, nranks, rank, C.byref(b), C.byref(c))
@@ -1588,6 +1782,30 @@ class Engine:
         self._chk(self._L.symmicp_ctx_fgr_pass(self._h, _fptr(p), _fptr(q), len(p), _fptr(X), C.c_float(mu),
                                                sums.ctypes.data_as(C.POINTER(C.c_double)), _fptr(w)))
         return sums, w[:len(p)]
+
+    def posegraph_optimize(self, poses, edges, max_dist=0.0, want_trace=False, check=True, **cfg):
+        """posegraph_optimize on this context's stream and scratch arena (symmicp_ctx_posegraph_optimize): its clouds, index, options and
+        states stay as they were; check=False returns the dict on failure too (status set)"""
+        st, r = _posegraph_call(self._L.symmicp_ctx_posegraph_optimize, (self._h,), poses, edges, posegraph_config(max_dist, **cfg), want_trace)
+        if check:
+            self._chk(st)
+        return r
+
+    def posegraph_pass(self, poses, edges, reference_node, mu, lam, cg_tolerance=1e-10, cg_max_iterations=0):
+        """test entry (symmicp_ctx_posegraph_pass): one launch of the iteration kernel at the given poses, mu and lambda ->
+        dict(e [m,6], c [m], l [m], g [n,6], hdiag [n,6,6], delta [n,6], cost, cost_trial, cg_iterations, cg_residual, ...)"""
+        X, m = _poses(poses), len(edges)
+        E = pose_edges(edges)
+        n = len(X)
+        e, c, l = np.zeros((m, 6)), np.zeros(m), np.zeros(m)
+        g, h, d = np.zeros((n, 6)), np.zeros((n, 6, 6)), np.zeros((n, 6))
+        rec = PosegraphIteration()
+        self._chk(self._L.symmicp_ctx_posegraph_pass(self._h, _dptr(X), n, E, m, int(reference_node), float(mu), float(lam), float(cg_tolerance),
+                                                     int(cg_max_iterations), _dptr(e), _dptr(c), _dptr(l), _dptr(g), _dptr(h), _dptr(d),
+                                                     C.byref(rec)))
+        r = _pg_iteration(rec)
+        r.update(e=e, c=c, l=l, g=g, hdiag=h, delta=d)
+        return r
 
     def batch_align(self, src, src_n, tgt, tgt_n, problems, guesses=None, trace=False, **cfg):
         """batch_align on this context's stream and scratch arena; its clouds, options and loop state stay as they are"""

@@ -997,7 +997,8 @@ int symmicp_get_ndt_map(symmicp_ctx *ctx, uint32_t *key_out, int32_t *count_out,
  *                 and from run to run.
  * Target -> source (Chamfer's other half, the covered share of the target) is the same call with the clouds swapped and the rows of
  * symmicp_inverse_rigid(X) as the transform.
- * Out of scope: sharded contexts; point-to-plane residual statistics; a pose covariance from the record; the pose-graph optimiser. */
+ * Out of scope: sharded contexts; point-to-plane residual statistics; a pose covariance from the record.  (The pose-graph optimiser that consumes the
+ * information matrix is symmicp_ctx_posegraph_optimize, below.) */
 typedef struct {
     uint64_t inliers;
     double fitness;            /* inliers / ns */
@@ -1033,6 +1034,133 @@ int symmicp_evaluate_registration(int device, const float *src_xyz, size_t src_r
  * SYMMICP_ERR_ARG as above (out, K, X16, max_dist).  SYMMICP_ERR_STATE: before both clouds are set; on a sharded context (nranks > 1: the
  * sums would need an exchange; out of scope, as for the rejectors). */
 int symmicp_evaluate(symmicp_ctx *ctx, const float *X16, size_t K, float max_dist, symmicp_evaluation *out, int32_t *nn_out, float *d2_out);
+
+/* ---- multiway registration: pose-graph optimisation (Choi, Zhou, Koltun, CVPR 2015; Open3D's global_optimization is the inspiration,
+ * the definitions below are the yardstick) --------------------------------------------------------------------------------------------
+ * Makes the pairwise transforms of more than two scans consistent: Levenberg-Marquardt over the poses, with a line process that switches
+ * false loop closures off.  It consumes the information matrix of symmicp_evaluation.  Everything is fp64.  A pure function of its
+ * arguments, bit for bit the same from run to run; the context's clouds, index, options and states stay as they were.
+ *   Graph        n nodes (2 .. 1024); node i has a pose X_i: row-major 4x4, the top three rows are read, taking node i's frame to the
+ *                world.  m edges (1 .. 16384); edge (source s, target t, T, L, uncertain), s != t: T takes s's frame to t's frame --
+ *                what symmicp_align returns with cloud s as source and cloud t as target; L = symmicp_evaluation.information of that
+ *                pair (rotation first, about the target's origin; only the upper triangle is read); uncertain = 0 for odometry, anything
+ *                else for a loop closure.  Several edges between the same two nodes are allowed, in either direction.
+ *   Edge error   E = X_t^-1 X_s T^-1, both inverses the rigid ones (R^T, -R^T t): E acts on t's frame, a target point q lands at E q
+ *                under the current poses, which is why L = sum G^T G of the evaluation applies to it.  e = (w, tau): tau = E's
+ *                translation, w = the rotation vector of E's rotation R, angle in [0, pi]:
+ *                  v = ((R21 - R12) / 2, (R02 - R20) / 2, (R10 - R01) / 2), c = clamp(((R00 + R11 + R22) - 1) / 2, -1, 1), s2 = v . v;
+ *                  s2 >= 1e-8:            w = v * (atan2(sqrt(s2), c) / sqrt(s2));
+ *                  s2 < 1e-8 and c > 0:   w = v * (1 + s2 / 6 + 3 s2^2 / 40)             (the series of asin(s) / s);
+ *                  s2 < 1e-8 and c <= 0:  (near pi) w = atan2(sqrt(s2), c) * a, a the unit axis from the symmetric part: i = the largest
+ *                                         diagonal entry (lowest i on ties), a_i = sqrt(max((R_ii - c) / (1 - c), 0)),
+ *                                         a_j = (R_ij + R_ji) / (2 (1 - c) a_i), the whole of it negated if a . v < 0.
+ *                c = e^T L e (L the symmetric matrix of the upper triangle).
+ *   Line process l = 1 for a certain edge, l = (mu / (mu + c))^2 for an uncertain one.  Cost F = sum over certain edges of c + sum over
+ *                uncertain edges of mu c / (mu + c): the line-process objective with l eliminated.  mu = line_process_weight if that is
+ *                > 0; otherwise, with at least one uncertain edge, mu = preference_loop_closure * max_dist^2 * (the mean over ALL edges
+ *                of L[35], the inlier count of the translation block), in fp64 on the host; a graph without uncertain edges has no mu
+ *                (reported as line_process_weight).
+ *   Update       X_i <- X_i Exp(d_i), d = (w, tau), Exp(d) = [exp([w]x) tau; 0 1]; exp([w]x) = I + A [w]x + B [w]x^2 with t2 = w . w,
+ *                A = sin(t) / t, B = (1 - cos(t)) / t2, t = sqrt(t2), and below t2 = 1e-8 the series A = 1 - t2 / 6 + t2^2 / 120,
+ *                B = 1 / 2 - t2 / 24 + t2^2 / 720.  The reference node takes no update: its pose comes back bit for bit (all 16 values).
+ *                The other poses come back with the bottom row 0 0 0 1.
+ *   Linearised   to first order about E = I (exact at a consistent graph): J_t = -I, J_s = Ad(T) = [R_T 0; [t_T]x R_T  R_T].  Per edge,
+ *                with W = l L:  H_ss += Ad^T W Ad, H_tt += W, H_st -= Ad^T W, g_s += Ad^T W e, g_t -= W e.
+ *   Step         (H + lambda I) d = -g over the free nodes, by a block-Jacobi preconditioned conjugate gradient on the device: the
+ *                preconditioner is the 6x6 Cholesky factor of H_ii + lambda I of every node; the solve stops at
+ *                r . r <= cg_tolerance^2 * g . g or after cg_max_iterations (0: 6 (n - 1)).
+ *   Control      on the host, from one record per iteration.  lambda_0 = 1e-5 * the largest diagonal entry of H at the initial poses.
+ *                Iteration: linearise at X, solve, X' = X Exp(d), F' = F(X').  Accepted iff F' < F; then X <- X',
+ *                lambda <- lambda * max(1 / 3, 1 - (2 rho - 1)^3) with rho = (F - F') / (d . (lambda d - g)), nu = 2, and the loop
+ *                stops if F - F' <= min_relative_decrease * F (stop reason 2).  Rejected: lambda <- lambda * nu, nu <- 2 nu.  After
+ *                either: stop if max |d| <= min_increment (3), then if the iteration count has reached max_iterations (1).
+ *   Pruning      after the loop an uncertain edge with l < edge_prune_threshold at the final poses is reported as pruned.  There is
+ *                no second optimisation without them.
+ *   Order        every sum has a fixed order: a node's blocks are added over its incident edges by ascending edge index; dot products
+ *                and the cost are per-thread partial sums over a fixed stride followed by a pairwise tree.  No floating-point atomics.
+ * SYMMICP_ERR_ARG, all decided on the host before a device is needed, with every output untouched: NULL poses_in / edges / cfg /
+ * poses_out / result; a wrong struct_size; n outside 2 .. 1024 or m outside 1 .. 16384; a node index out of range or s == t; a graph that
+ * is not connected; reference_node outside 0 .. n - 1; a non-finite entry in the top three rows of any X, of any T, or in the upper
+ * triangle of any L; a rotation block of an X or a T with max |R^T R - I| > 1e-6; max_iterations outside 1 .. 10000; cg_max_iterations
+ * outside 0 .. 100000; line_process_weight not finite or < 0; when mu has to be derived, max_dist or preference_loop_closure not finite
+ * and > 0; edge_prune_threshold outside [0, 1]; min_relative_decrease or min_increment not finite or < 0; cg_tolerance outside (0, 1).
+ * SYMMICP_ERR_DEGENERATE: a node block H_ii + lambda I that is not finite or not positive definite on the device; poses_out holds the
+ * last accepted poses.
+ * Out of scope: sharded contexts (nranks > 1: SYMMICP_ERR_STATE); graphs above the caps; re-optimisation after pruning; exact
+ * (non-first-order) Jacobians. */
+#define SYMMICP_POSEGRAPH_MAX_NODES 1024
+#define SYMMICP_POSEGRAPH_MAX_EDGES 16384
+typedef struct {
+    int32_t source, target;    /* s, t */
+    int32_t uncertain;         /* 0: odometry; else a loop closure */
+    int32_t reserved;
+    double transform[16];      /* T, row-major; the top three rows are read */
+    double information[36];    /* L, row-major, rotation first; the upper triangle is read */
+} symmicp_pose_edge;
+typedef struct {
+    uint32_t struct_size;          /* = sizeof(symmicp_posegraph_config), checked */
+    int32_t max_iterations;        /* 1 .. 10000, default 100 */
+    int32_t reference_node;        /* default 0 */
+    int32_t cg_max_iterations;     /* default 0: 6 (n - 1) */
+    double max_dist;               /* the distance the information matrices were evaluated at; read when mu is derived */
+    double preference_loop_closure;/* default 1.0 */
+    double line_process_weight;    /* mu; default 0: derived */
+    double edge_prune_threshold;   /* default 0.25 */
+    double min_relative_decrease;  /* default 1e-6 */
+    double min_increment;          /* default 1e-9 */
+    double cg_tolerance;           /* default 1e-10 */
+} symmicp_posegraph_config;
+typedef struct {
+    int32_t status;                /* what the call returned */
+    int32_t iterations;            /* linearisations = launches of the iteration kernel */
+    int32_t accepted_steps;
+    int32_t stop_reason;           /* 1 max_iterations, 2 relative decrease, 3 increment; 0: the call failed */
+    int32_t pruned;                /* uncertain edges with l < edge_prune_threshold */
+    int32_t cg_iterations;         /* over all iterations */
+    double cost_initial, cost_final;
+    double mu;
+    double lambda_final;           /* lambda after the last iteration's update */
+    double grad_max;               /* max |g| at the last linearisation */
+} symmicp_posegraph_result;
+/* one record per iteration, as the device left it and the host judged it (trace_out) */
+typedef struct {
+    double cost, cost_trial;       /* F(X), F(X') */
+    double model_decrease;         /* d . (lambda d - g) */
+    double grad_max, delta_max;    /* max |g|, max |d| */
+    double hdiag_max;              /* the largest diagonal entry of H */
+    double lambda;                 /* of this iteration's solve */
+    double cg_residual;            /* sqrt(r . r / g . g) when the solve stopped */
+    int32_t cg_iterations;
+    int32_t accepted;              /* 1: F' < F */
+    int32_t status;                /* SYMMICP_OK or SYMMICP_ERR_DEGENERATE */
+    int32_t reserved;
+} symmicp_posegraph_iteration;
+/* max_iterations 100, reference_node 0, cg_max_iterations 0, max_dist 0 (the caller sets it), preference_loop_closure 1,
+ * line_process_weight 0, edge_prune_threshold 0.25, min_relative_decrease 1e-6, min_increment 1e-9, cg_tolerance 1e-10 */
+void symmicp_posegraph_config_default(symmicp_posegraph_config *cfg);
+/* poses_in, poses_out [n][16] (they may be the same array); result (required); weight_out [m]: l at the final poses; pruned_out [m]: 1 for
+ * a pruned edge; trace_out [max_iterations]: the first result->iterations records are written; the three may be NULL.  Runs on the
+ * context's stream and temporary memory. */
+int symmicp_ctx_posegraph_optimize(symmicp_ctx *ctx, const double *poses_in, size_t n, const symmicp_pose_edge *edges, size_t m,
+                                   const symmicp_posegraph_config *cfg, double *poses_out, symmicp_posegraph_result *result,
+                                   double *weight_out, uint8_t *pruned_out, symmicp_posegraph_iteration *trace_out);
+/* the same on a context of its own, created on `device` (-1 = current) and destroyed again */
+int symmicp_posegraph_optimize(int device, const double *poses_in, size_t n, const symmicp_pose_edge *edges, size_t m,
+                               const symmicp_posegraph_config *cfg, double *poses_out, symmicp_posegraph_result *result,
+                               double *weight_out, uint8_t *pruned_out, symmicp_posegraph_iteration *trace_out);
+/* test entry: one launch of the iteration kernel at the given poses, mu (finite, > 0) and lambda (finite, >= 0), with the solve's
+ * cg_tolerance (in (0, 1)) and cg_max_iterations (0: 6 (n - 1)).  Outputs, each may be NULL: e_out [m][6], c_out [m], l_out [m],
+ * g_out [n][6], hdiag_out [n][36] (H_ii without lambda), delta_out [n][6] -- the rows of the reference node are zero in the three --
+ * and record_out: cost, cost_trial = F(X Exp(d)), the solve's iterations and residual (accepted = 0).
+ * SYMMICP_ERR_ARG as for the optimiser (graph, poses, reference_node), and for mu, lambda, cg_tolerance, cg_max_iterations out of range. */
+int symmicp_ctx_posegraph_pass(symmicp_ctx *ctx, const double *poses, size_t n, const symmicp_pose_edge *edges, size_t m,
+                               int32_t reference_node, double mu, double lambda, double cg_tolerance, int32_t cg_max_iterations,
+                               double *e_out, double *c_out, double *l_out, double *g_out, double *hdiag_out, double *delta_out,
+                               symmicp_posegraph_iteration *record_out);
+/* pure host helpers: e of one edge by the definition above (e6_out = (w, tau); SYMMICP_ERR_ARG for a NULL pointer), and l of an
+ * uncertain edge */
+int symmicp_posegraph_edge_error(const double Xs16[16], const double Xt16[16], const double T16[16], double e6_out[6]);
+double symmicp_posegraph_line_weight(double mu, double c);
 
 /* ---- multi-GPU (new: the reference is single-threaded) ----- */
 /* rank 0 creates an id, the application ships it to the other ranks (any channel),
