@@ -52,7 +52,9 @@
 //                              its K nearest neighbours (1 .. 64) exceeds the cloud's mean + S standard deviations
 //     --ror R:M                radius outlier removal of both clouds (after --sor when both are given): a point goes with fewer than
 //                              M other points within R.  Unless --quiet each filter prints one line with the counts before and after
-//     --out aligned.pcd        write the source moved by the result (the reference only prints its result; after --sor / --ror the
+//     --min-cluster EPS:M      small-cluster removal of both clouds (after --sor and --ror): every connected part of a cloud (points
+//                              closer than EPS) with fewer than M points goes -- floating blobs that pass both point filters
+//     --out aligned.pcd        write the source moved by the result (the reference only prints its result; after --sor / --ror / --min-cluster the
 //                              filtered source)
 //     --quiet                  no per-iteration lines
 //   Without file names it registers cat.pcd to cat_out.pcd from the working directory: the reference's own run.
@@ -72,7 +74,7 @@
 static int usage(const char *argv0, const char *complaint)
 {
     std::fprintf(stderr, "%s\nusage: %s [--mode quirks|paper|plane|gicp|color|ndt] [--ndt-resolution L] [--ndt-neighbors 1|7] [--ndt-min-points N] [--ndt-level L:ITERS]... [--color-weight L] [--corr identity|tree] [--iters N] [--threshold D] [--loss none|huber|tukey|cauchy|gm]"
-                 " [--loss-scale S] [--gicp-epsilon E] [--max-dist D] [--trim F] [--one-to-one] [--reciprocal] [--median-factor F] [--scale LEAF:ITERS[:MAXDIST]]... [--init global --fpfh-radius R --ransac-dist D [--ransac-iters H] [--seed S] [--init-voxel L] [--init-keypoints iss --iss-radius R [--iss-nms-radius R2] [--iss-min-neighbors K]]] [--init fgr --fpfh-radius R --fgr-dist D [--fgr-iters N] [--fgr-tuples N] [--seed S] [--init-voxel L] [--init-keypoints iss ...]] [--evaluate D [--information]] [--sor K:S] [--ror R:M] [--out file.pcd] [--quiet] [source.pcd target.pcd]\n",
+                 " [--loss-scale S] [--gicp-epsilon E] [--max-dist D] [--trim F] [--one-to-one] [--reciprocal] [--median-factor F] [--scale LEAF:ITERS[:MAXDIST]]... [--init global --fpfh-radius R --ransac-dist D [--ransac-iters H] [--seed S] [--init-voxel L] [--init-keypoints iss --iss-radius R [--iss-nms-radius R2] [--iss-min-neighbors K]]] [--init fgr --fpfh-radius R --fgr-dist D [--fgr-iters N] [--fgr-tuples N] [--seed S] [--init-voxel L] [--init-keypoints iss ...]] [--evaluate D [--information]] [--sor K:S] [--ror R:M] [--min-cluster EPS:M] [--out file.pcd] [--quiet] [source.pcd target.pcd]\n",
                  complaint, argv0);
     return 64;
 }
@@ -101,6 +103,8 @@ int main(int argc, char **argv)
     float eval_dist = 0.f;
     int sor_k = 0, ror_min = 0;              // 0: the filter is off
     float sor_mul = 0.f, ror_radius = 0.f;
+    int cluster_min = 0;
+    float cluster_eps = 0.f;
     bool quiet = false;
     bool ndt = false, have_ndt_option = false;
     float ndt_resolution = 0.f;
@@ -304,6 +308,20 @@ int main(int argc, char **argv)
             }
             if (!ok) return usage(argv[0], "--ror needs R:M with a radius R > 0 and M >= 1 neighbours");
         }
+        else if (a == "--min-cluster") {
+            // EPS:M
+            const char *v = value("--min-cluster");
+            char *end = nullptr;
+            cluster_eps = std::strtof(v, &end);
+            bool ok = end != v && *end == ':' && std::isfinite(cluster_eps) && cluster_eps > 0.f;
+            if (ok) {
+                const char *w = end + 1;
+                const long m = std::strtol(w, &end, 10);
+                ok = end != w && *end == 0 && m >= 1 && m <= 0x7fffffffl;
+                cluster_min = (int)m;
+            }
+            if (!ok) return usage(argv[0], "--min-cluster needs EPS:M with a distance EPS > 0 and M >= 1 points");
+        }
         else if (a == "--quiet") { icp.setVerbose(false); quiet = true; }
         else if (!a.empty() && a[0] == '-') return usage(argv[0], ("unknown option " + a).c_str());
         else files.push_back(a);
@@ -389,6 +407,14 @@ int main(int argc, char **argv)
         if (!quiet)
             std::printf("%s outlier removal: source %zu -> %zu, target %zu -> %zu\n", f == 0 ? "statistical" : "radius", ns,
                         icp.GetSrcCloud()->points.size(), nt, icp.GetTgtCloud()->points.size());
+    }
+    if (cluster_min > 0) {
+        const size_t ns = icp.GetSrcCloud()->points.size(), nt = icp.GetTgtCloud()->points.size();
+        const int st = icp.removeSmallClusters(cluster_eps, cluster_min);
+        if (st != SYMMICP_OK) { std::fprintf(stderr, "%s\n", icp.lastError()); return st; }
+        if (!quiet)
+            std::printf("small cluster removal: source %zu -> %zu, target %zu -> %zu\n", ns, icp.GetSrcCloud()->points.size(), nt,
+                        icp.GetTgtCloud()->points.size());
     }
     icp.RegisterSymm();
     const symmicp_result &r = icp.lastResult();

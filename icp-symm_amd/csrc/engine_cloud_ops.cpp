@@ -1,4 +1,4 @@
-// engine_cloud_ops.cpp -- the stand-alone cloud operations of libsymmicp: normals and k-NN, radius search, FPFH, ISS keypoints, outlier removal, the
+// engine_cloud_ops.cpp -- the stand-alone cloud operations of libsymmicp: normals and k-NN, radius search, FPFH, ISS keypoints, outlier removal, clustering, the
 // intensity gradient of colored ICP, voxel-grid downsampling.  Each runs on a context the caller owns (symmicp_ctx_*), whose target,
 // source, index and certificates stay as they are, or as a one-shot on a context of its own (with_own_context).
 #include "engine_internal.h"
@@ -428,6 +428,101 @@ int symmicp_radius_outlier_removal(int device, const float *xyz, size_t row_stri
     if (ror_args_error(xyz, row_stride, col_stride, n, radius, min_neighbors, rows_out, cap, count_out)) return SYMMICP_ERR_ARG;
     return with_own_context(device, [&](symmicp_ctx *c) {
         return symmicp_ctx_radius_outlier_removal(c, xyz, row_stride, col_stride, n, radius, min_neighbors, rows_out, cap, count_out, neighbors_out);
+    });
+}
+
+// ---- DBSCAN / Euclidean cluster extraction (kernels_cluster.hip, kernels_fpfh.hip; DESIGN.md 4, "Clustering") -------------------------
+// Like the radius filter above: the cloud's own scratch index, the count pass of the radius search (the core test), then the union-find
+// over the implicit radius graph and the border pass.  The per-row representative is read back; the dense numbering, the sizes and the
+// size filter are O(n), sequential by definition, and run on the host.
+static const char *cluster_args_error(const float *xyz, size_t xr, size_t xc, size_t n, const symmicp_cluster_config *cfg, const int32_t *labels_out,
+                                      const size_t *clusters_out, const int32_t *sizes_out, size_t cap)
+{
+    if (!xyz || !cfg || !labels_out || !clusters_out) return "cluster: xyz, cfg, labels_out and clusters_out are required";
+    if (!sizes_out && cap > 0) return "cluster: sizes_out is required when cap > 0";
+    if (n == 0 || n > 0x7fffffffull) return "cluster: n must be in 1 .. 2^31 - 1";
+    if (cfg->struct_size != sizeof(symmicp_cluster_config)) return "cluster: cfg->struct_size is not sizeof(symmicp_cluster_config)";
+    if (!std::isfinite(cfg->eps) || !(cfg->eps > 0.f)) return "cluster: eps must be finite and > 0";
+    if (cfg->min_points < 1) return "cluster: min_points must be >= 1";
+    if (cfg->min_cluster_size < 0 || cfg->max_cluster_size < 0) return "cluster: min_cluster_size and max_cluster_size must be >= 0";
+    if (cfg->min_cluster_size > 0 && cfg->max_cluster_size > 0 && cfg->max_cluster_size < cfg->min_cluster_size)
+        return "cluster: max_cluster_size is below min_cluster_size";
+    for (size_t i = 0; i < n; i++)
+        for (int a = 0; a < 3; a++)
+            if (!std::isfinite(xyz[i * xr + a * xc])) return "cluster: a coordinate is not finite";
+    return nullptr;
+}
+
+void symmicp_cluster_config_default(symmicp_cluster_config *cfg)
+{
+    if (!cfg) return;
+    std::memset(cfg, 0, sizeof(*cfg));
+    cfg->struct_size = (uint32_t)sizeof(*cfg);
+    cfg->min_points = 1;
+}
+
+int symmicp_ctx_cluster(symmicp_ctx *c, const float *xyz, size_t row_stride, size_t col_stride, size_t n, const symmicp_cluster_config *cfg,
+                        int32_t *labels_out, size_t *clusters_out, int32_t *sizes_out, size_t cap, uint8_t *core_out, int32_t *neighbors_out)
+{
+    if (!c) return SYMMICP_ERR_ARG;
+    if (const char *msg = cluster_args_error(xyz, row_stride, col_stride, n, cfg, labels_out, clusters_out, sizes_out, cap)) return fail(c, SYMMICP_ERR_ARG, msg);
+    std::vector<int32_t> own;
+    std::vector<uint32_t> root(n);
+    int32_t *nb = neighbors_out;
+    const int32_t need = cfg->min_points - 1;
+    {
+        ScratchIndex si;
+        if (int st = si.begin(c, xyz, row_stride, col_stride, nullptr, 0, 0, n, n * 8 + 8192)) return st;
+        DevBuf<int32_t> d_count;
+        DevBuf<uint32_t> d_parent;
+        DevBuf<unsigned long long> d_stats;
+        HIP_TRY(c, d_count.alloc_temp(c->arena, n));
+        HIP_TRY(c, d_parent.alloc_temp(c->arena, n));
+        if (c->sw.debug_counters) {
+            HIP_TRY(c, d_stats.alloc_temp(c->arena, 2));
+            HIP_TRY(c, hipMemsetAsync(d_stats.p, 0, 2 * sizeof(unsigned long long), c->stream));
+        }
+        const float r2 = cfg->eps * cfg->eps;
+        launch_radius_count(si.ix, r2, d_count.p, c->stream);
+        launch_cluster_roots(si.ix, r2, d_count.p, cfg->min_points, d_parent.p, d_stats.p, c->stream);
+        HIP_TRY(c, hipGetLastError());
+        if (!nb) { own.resize(n); nb = own.data(); }
+        unsigned long long stats[2] = {0, 0};
+        HIP_TRY(c, hipMemcpyAsync(nb, d_count.p, sizeof(int32_t) * n, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(root.data(), d_parent.p, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, c->stream));
+        if (d_stats.p) HIP_TRY(c, hipMemcpyAsync(stats, d_stats.p, sizeof(stats), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        HIP_TRY(c, hipGetLastError());
+        if (d_stats.p) std::fprintf(stderr, "symmicp cluster: n %zu, %llu unions, %llu lost compare-and-swaps\n", n, stats[0], stats[1]);
+    }
+    if (core_out) for (size_t i = 0; i < n; i++) core_out[i] = nb[i] >= need ? 1 : 0;
+    // clusters numbered in ascending order of their representative (its lowest core row), sizes = core + border rows
+    std::vector<int32_t> label(n, -1), size;
+    for (size_t i = 0; i < n; i++)
+        if (root[i] == (uint32_t)i && nb[i] >= need) { label[i] = (int32_t)size.size(); size.push_back(0); }
+    for (size_t i = 0; i < n; i++) {
+        if (root[i] == kClusterNoise) continue;
+        if (root[i] >= n || label[root[i]] < 0) return fail(c, SYMMICP_ERR_HIP, "cluster: a row's representative is not a cluster's lowest core row");
+        size[(size_t)label[root[i]]]++;
+    }
+    // the size filter: the clusters that stay, renumbered in the same order
+    const int32_t lo = cfg->min_cluster_size, hi = cfg->max_cluster_size;
+    std::vector<int32_t> renum(size.size(), -1), kept;
+    for (size_t k = 0; k < size.size(); k++)
+        if ((lo == 0 || size[k] >= lo) && (hi == 0 || size[k] <= hi)) { renum[k] = (int32_t)kept.size(); kept.push_back(size[k]); }
+    for (size_t i = 0; i < n; i++) labels_out[i] = root[i] == kClusterNoise ? -1 : renum[(size_t)label[root[i]]];
+    *clusters_out = kept.size();
+    if (kept.size() > cap) return fail(c, SYMMICP_ERR_SIZE, "cluster: " + std::to_string(kept.size()) + " clusters do not fit cap " + std::to_string(cap));
+    for (size_t k = 0; k < kept.size(); k++) sizes_out[k] = kept[k];
+    return SYMMICP_OK;
+}
+
+int symmicp_cluster(int device, const float *xyz, size_t row_stride, size_t col_stride, size_t n, const symmicp_cluster_config *cfg,
+                    int32_t *labels_out, size_t *clusters_out, int32_t *sizes_out, size_t cap, uint8_t *core_out, int32_t *neighbors_out)
+{
+    if (cluster_args_error(xyz, row_stride, col_stride, n, cfg, labels_out, clusters_out, sizes_out, cap)) return SYMMICP_ERR_ARG;
+    return with_own_context(device, [&](symmicp_ctx *c) {
+        return symmicp_ctx_cluster(c, xyz, row_stride, col_stride, n, cfg, labels_out, clusters_out, sizes_out, cap, core_out, neighbors_out);
     });
 }
 

@@ -153,7 +153,7 @@ void MyICP::estimateNormals()
 
 // Outlier removal: the kept rows of both clouds first (an error leaves both as they were), then every per-point array of each cloud
 // compacted in row order.  The point-normal clouds follow only while they still match their clouds row for row.
-int MyICP::removeOutliers(bool statistical, int k, float std_mul, float radius, int min_neighbors)
+int MyICP::removeOutliers(int filter, int k, float std_mul, float radius, int min_neighbors)
 {
 	assert(cloud_src && cloud_tgt);
 	removed_src_ = removed_tgt_ = 0;
@@ -168,8 +168,23 @@ int MyICP::removeOutliers(bool statistical, int k, float std_mul, float radius, 
 		size_t count = 0;
 		const float *xyz = &clouds[s]->points[0].x;
 		const size_t fs = sizeof(PointT) / sizeof(float);
-		const int st = statistical ? symmicp_ctx_statistical_outlier_removal(ctx, xyz, fs, 1, n, k, std_mul, rows[s].data(), n, &count, nullptr, nullptr)
-		                           : symmicp_ctx_radius_outlier_removal(ctx, xyz, fs, 1, n, radius, min_neighbors, rows[s].data(), n, &count, nullptr);
+		int st;
+		if (filter == 2) {
+			// small clusters: the rows whose label survives the size filter (the labels land in rows[s] and are compacted in place)
+			symmicp_cluster_config cfg;
+			symmicp_cluster_config_default(&cfg);
+			cfg.eps = radius;
+			cfg.min_cluster_size = min_neighbors;
+			size_t clusters = 0;
+			if (min_neighbors < 1) { error_ = "cluster: min_size must be >= 1"; return SYMMICP_ERR_ARG; }
+			st = symmicp_ctx_cluster(ctx, xyz, fs, 1, n, &cfg, rows[s].data(), &clusters, nullptr, 0, nullptr, nullptr);
+			if (st == SYMMICP_ERR_SIZE) st = SYMMICP_OK;      // (the sizes were not asked for: the labels are written)
+			if (st == SYMMICP_OK)
+				for (size_t i = 0; i < n; i++) if (rows[s][i] >= 0) rows[s][count++] = (int32_t)i;
+		} else {
+			st = filter == 0 ? symmicp_ctx_statistical_outlier_removal(ctx, xyz, fs, 1, n, k, std_mul, rows[s].data(), n, &count, nullptr, nullptr)
+			                 : symmicp_ctx_radius_outlier_removal(ctx, xyz, fs, 1, n, radius, min_neighbors, rows[s].data(), n, &count, nullptr);
+		}
 		if (st != SYMMICP_OK) { error_ = symmicp_last_error(ctx); return st; }
 		rows[s].resize(count);
 	}
@@ -195,12 +210,17 @@ int MyICP::removeOutliers(bool statistical, int k, float std_mul, float radius, 
 
 int MyICP::removeStatisticalOutliers(int k, float std_mul)
 {
-	return removeOutliers(true, k, std_mul, 0.f, 0);
+	return removeOutliers(0, k, std_mul, 0.f, 0);
 }
 
 int MyICP::removeRadiusOutliers(float radius, int min_neighbors)
 {
-	return removeOutliers(false, 0, 0.f, radius, min_neighbors);
+	return removeOutliers(1, 0, 0.f, radius, min_neighbors);
+}
+
+int MyICP::removeSmallClusters(float eps, int min_size)
+{
+	return removeOutliers(2, 0, 0.f, eps, min_size);
 }
 
 int MyICP::align(float out4x4[16], const float *guess4x4)

@@ -433,6 +433,13 @@ void launch_iss_scatter(const uint32_t *flag_rows, const uint32_t *pos_rows, uin
 // mean_rows [n] by ORIGINAL row = the fp64 mean of sqrt(d2) over the k nearest other points
 void launch_knn_mean_dist(const TargetIndex &ix, int k, double *mean_rows, hipStream_t s);
 
+// DBSCAN / Euclidean clustering (kernels_cluster.hip; symmicp_ctx_cluster): count_rows = launch_radius_count's at the same r2.  Leaves in
+// parent_rows [n], by ORIGINAL row, the representative (lowest core row) of the row's cluster, or kClusterNoise.  stats (may be null):
+// two zeroed words, += unite calls and lost compare-and-swaps of the union kernel.
+constexpr uint32_t kClusterNoise = 0xffffffffu;
+void launch_cluster_roots(const TargetIndex &ix, float r2, const int32_t *count_rows, int32_t min_points, uint32_t *parent_rows,
+                          unsigned long long *stats, hipStream_t s);
+
 // feature matching and RANSAC (kernels_global.hip; symmicp_ctx_feature_nn, symmicp_ctx_ransac).  feature_nn: fa / fb packed [n][33];
 // splits > 1 needs feature_nn_partial_bytes of `partial`.  ransac: pq8 [m][8] = p.xyz, 0, q.xyz, 0 about the pivots; hyp [H][12].
 void launch_feature_nn(const float *fa, uint32_t na, const float *fb, uint32_t nb, int queries_per_thread, uint32_t splits, void *partial,

@@ -106,6 +106,12 @@ class IssConfig(C.Structure):
                 ("gamma32", C.c_float), ("min_neighbors", C.c_int32), ("reserved", C.c_int32)]
 
 
+class ClusterConfig(C.Structure):
+    """symmicp_cluster_config"""
+    _fields_ = [("struct_size", C.c_uint32), ("eps", C.c_float), ("min_points", C.c_int32), ("min_cluster_size", C.c_int32),
+                ("max_cluster_size", C.c_int32), ("reserved", C.c_int32)]
+
+
 class NdtConfig(C.Structure):
     _fields_ = [("struct_size", C.c_int32), ("resolution", C.c_float), ("min_points", C.c_int32), ("eig_ratio", C.c_float),
                 ("outlier_ratio", C.c_float), ("neighbors", C.c_int32)]
@@ -210,6 +216,7 @@ EXPORTS = [
     "symmicp_information_from_sums", "symmicp_evaluate_registration", "symmicp_ctx_evaluate_registration", "symmicp_evaluate",
     "symmicp_statistical_outlier_removal", "symmicp_ctx_statistical_outlier_removal",
     "symmicp_radius_outlier_removal", "symmicp_ctx_radius_outlier_removal",
+    "symmicp_cluster_config_default", "symmicp_cluster", "symmicp_ctx_cluster",
     "symmicp_ndt_config_default", "symmicp_set_ndt", "symmicp_get_ndt", "symmicp_ndt_gauss", "symmicp_ndt_weight", "symmicp_get_ndt_state",
     "symmicp_ctx_ndt_map", "symmicp_ndt_map", "symmicp_get_ndt_map",
     "symmicp_posegraph_config_default", "symmicp_posegraph_optimize", "symmicp_ctx_posegraph_optimize", "symmicp_ctx_posegraph_pass",
@@ -376,6 +383,11 @@ def lib():
     ror = [fp, C.c_size_t, C.c_size_t, C.c_size_t, C.c_float, C.c_int, i32p, C.c_size_t, szp, i32p]
     L.symmicp_radius_outlier_removal.argtypes = [C.c_int] + ror
     L.symmicp_ctx_radius_outlier_removal.argtypes = [vp] + ror
+    clu = [fp, C.c_size_t, C.c_size_t, C.c_size_t, C.POINTER(ClusterConfig), i32p, szp, i32p, C.c_size_t, u8p, i32p]
+    L.symmicp_cluster_config_default.argtypes = [C.POINTER(ClusterConfig)]
+    L.symmicp_cluster_config_default.restype = None
+    L.symmicp_cluster.argtypes = [C.c_int] + clu
+    L.symmicp_ctx_cluster.argtypes = [vp] + clu
     ndp = C.POINTER(NdtConfig)
     L.symmicp_ndt_config_default.argtypes = [ndp]
     L.symmicp_ndt_config_default.restype = None
@@ -863,6 +875,99 @@ def remove_radius_outlier(xyz, radius, min_neighbors, return_counts=False, devic
     if st != OK:
         raise SymmIcpError(st, "remove_radius_outlier")
     return r
+
+
+def cluster_config(eps, min_points=1, min_cluster_size=0, max_cluster_size=0):
+    cfg = ClusterConfig()
+    lib().symmicp_cluster_config_default(C.byref(cfg))
+    cfg.eps, cfg.min_points = float(eps), int(min_points)
+    cfg.min_cluster_size, cfg.max_cluster_size = int(min_cluster_size), int(max_cluster_size)
+    return cfg
+
+
+def _cluster_call(fn, head, xyz, cfg, cap=None, strides=None, want=True):
+    """fn(*head, <the C arguments>) -> (status, labels [n] int32, clusters, sizes [cap] int32 or None, core [n] uint8 or None,
+    neighbors [n] int32 or None).  cap None: sizes_out == NULL, cap 0.  strides = (n, row stride, col stride) reads xyz as a flat f32
+    buffer."""
+    xyz, n, xr, xc = _outlier_cloud(xyz, strides)
+    labels = np.full(max(n, 1), -2, np.int32)
+    sizes = None if cap is None else np.full(max(cap, 1), -1, np.int32)
+    core = np.zeros(max(n, 1), np.uint8) if want else None
+    nb = np.zeros(max(n, 1), np.int32) if want else None
+    clusters = C.c_size_t(0)
+    st = fn(*head, _fptr(xyz), xr, xc, n, C.byref(cfg), _i32ptr(labels), C.byref(clusters), None if sizes is None else _i32ptr(sizes),
+            0 if cap is None else cap, None if core is None else core.ctypes.data_as(C.POINTER(C.c_uint8)), None if nb is None else _i32ptr(nb))
+    return st, labels[:n], int(clusters.value), sizes, None if core is None else core[:n], None if nb is None else nb[:n]
+
+
+def _cluster_dbscan(fn, head, xyz, cfg, return_info):
+    """one call with cap = n, which always suffices -> (status, labels or dict(labels=, clusters=, sizes=, core=, neighbors=))"""
+    st, labels, clusters, sizes, core, nb = _cluster_call(fn, head, xyz, cfg, cap=len(xyz), want=return_info)
+    if st != OK:
+        return st, None
+    if not return_info:
+        return st, labels
+    return st, dict(labels=labels, clusters=clusters, sizes=sizes[:clusters].copy(), core=core.astype(bool), neighbors=nb)
+
+
+def cluster_dbscan(xyz, eps, min_points=1, min_cluster_size=0, max_cluster_size=0, return_info=False, device=-1):
+    """DBSCAN on the GPU (symmicp_cluster; include/symmicp.h defines the result) -> labels [N] int32: the cluster of every row,
+    numbered in ascending order of the clusters' lowest core rows, -1 for noise.  A row is core with at least min_points points
+    within eps, ITSELF counted (min_points = 1: Euclidean clustering, every point core).  A border row joins the cluster of its
+    nearest core neighbour.  Clusters whose size lies outside [min_cluster_size, max_cluster_size] (0 = no bound) become noise.
+    With return_info dict(labels=, clusters=, sizes= [clusters] int32, core= [N] bool, neighbors= [N] int32)."""
+    cfg = cluster_config(eps, min_points, min_cluster_size, max_cluster_size)
+    st, r = _cluster_dbscan(lib().symmicp_cluster, (int(device),), xyz, cfg, return_info)
+    if st != OK:
+        raise SymmIcpError(st, "cluster_dbscan")
+    return r
+
+
+def clusters_from_labels(labels):
+    """labels [N] (-1 = noise) -> PCL's shape: a list of ascending row arrays (int32), largest cluster first, exact size ties by lowest
+    label (= lowest representative row)"""
+    labels = np.asarray(labels)
+    rows = np.nonzero(labels >= 0)[0]
+    order = rows[np.argsort(labels[rows], kind="stable")]
+    sizes = np.bincount(labels[rows]) if len(rows) else np.zeros(0, np.int64)
+    parts = np.split(order.astype(np.int32), np.cumsum(sizes)[:-1]) if len(sizes) else []
+    return [parts[k] for k in np.argsort(-sizes, kind="stable")]
+
+
+def euclidean_clusters(xyz, tolerance, min_size=1, max_size=0, device=-1):
+    """PCL's EuclideanClusterExtraction on the GPU (symmicp_cluster with min_points = 1): the connected parts of the cloud under
+    'closer than tolerance', those of min_size .. max_size points (0 = no bound) -> a list of ascending row arrays, largest first."""
+    return clusters_from_labels(cluster_dbscan(xyz, tolerance, 1, min_size, max_size, device=device))
+
+
+def pack_clusters(xyz, nrm, labels):
+    """the bridge from labels to batch_align: the rows of every cluster with at most BATCH_MAX_POINTS points, packed cluster after
+    cluster (ascending label, ascending row) -> dict(xyz= [M,3], nrm= [M,3] or None, ranges= [K,2] int64 (first, count) rows of the
+    pools, labels= [K] the packed clusters' labels, rows= [M] the original row of every packed row, skipped= [(label, size), ...] the
+    clusters above BATCH_MAX_POINTS, which are not packed).  A batch problem of cluster a of one cloud against cluster b of another is
+    (ranges_s[a, 0], ranges_s[a, 1], ranges_t[b, 0], ranges_t[b, 1])."""
+    xyz = _cloud(xyz)
+    nrm = None if nrm is None else _cloud(nrm)
+    labels = np.asarray(labels)
+    if len(labels) != len(xyz) or (nrm is not None and len(nrm) != len(xyz)):
+        raise ValueError("a label and a normal per point")
+    rows, ranges, kept, skipped, at = [], [], [], [], 0
+    sizes = np.bincount(labels[labels >= 0]) if (labels >= 0).any() else np.zeros(0, np.int64)
+    order = np.argsort(np.where(labels >= 0, labels, len(sizes)), kind="stable")
+    first = np.concatenate([[0], np.cumsum(sizes)])
+    for k, m in enumerate(sizes.tolist()):
+        if m == 0:
+            continue
+        if m > BATCH_MAX_POINTS:
+            skipped.append((k, m))
+            continue
+        rows.append(order[first[k]:first[k] + m])
+        ranges.append((at, m))
+        kept.append(k)
+        at += m
+    rows = np.concatenate(rows).astype(np.int32) if rows else np.zeros(0, np.int32)
+    return dict(xyz=np.ascontiguousarray(xyz[rows]), nrm=None if nrm is None else np.ascontiguousarray(nrm[rows]),
+                ranges=np.array(ranges, np.int64).reshape(-1, 2), labels=np.array(kept, np.int32), rows=rows, skipped=skipped)
 
 
 def _features(f):
@@ -1717,6 +1822,18 @@ class Engine:
         self._chk(st)
         return r
 
+    def cluster_dbscan(self, xyz, eps, min_points=1, min_cluster_size=0, max_cluster_size=0, return_info=False):
+        """cluster_dbscan on this context (symmicp_ctx_cluster, one call with cap = n)"""
+        cfg = cluster_config(eps, min_points, min_cluster_size, max_cluster_size)
+        st, r = _cluster_dbscan(self._L.symmicp_ctx_cluster, (self._h,), xyz, cfg, return_info)
+        self._chk(st)
+        return r
+
+    def cluster_dbscan_raw(self, xyz, cfg, cap=None, strides=None):
+        """one call of symmicp_ctx_cluster with a caller-chosen cap (None: sizes_out == NULL) -> (status, labels, clusters, sizes, core,
+        neighbors)"""
+        return _cluster_call(self._L.symmicp_ctx_cluster, (self._h,), xyz, cfg, cap, strides)
+
     def remove_radius_outlier_raw(self, xyz, radius, min_neighbors, cap=None, strides=None):
         """one call of symmicp_ctx_radius_outlier_removal with a caller-chosen cap (None: rows_out == NULL) -> (status, rows, count,
         neighbors); nothing is raised"""
@@ -2346,8 +2463,15 @@ class MyICP:
         """as removeStatisticalOutliers, with Engine.remove_radius_outlier (at least min_neighbors other points within radius)"""
         return self._filter_clouds(lambda e, x: e.remove_radius_outlier(x, radius, min_neighbors))
 
+    def removeSmallClusters(self, eps, min_size):
+        """as removeStatisticalOutliers, with Engine.cluster_dbscan: every connected part of a cloud (points closer than eps, min_points =
+        1) with fewer than min_size points goes -- the floating blobs whose points have close neighbours and pass both filters above"""
+        if int(min_size) < 1:
+            raise SymmIcpError(ERR_ARG, "removeSmallClusters: min_size must be >= 1")
+        return self._filter_clouds(lambda e, x: np.nonzero(e.cluster_dbscan(x, eps, 1, min_size, 0) >= 0)[0].astype(np.int32))
+
     def outliersRemoved(self):
-        """(source, target) points removed by the last removeStatisticalOutliers / removeRadiusOutliers"""
+        """(source, target) points removed by the last removeStatisticalOutliers / removeRadiusOutliers / removeSmallClusters"""
         return self._removed
 
     def estimateNormals(self):

@@ -180,6 +180,10 @@ public:
 	// two clouds of different sizes.
 	int removeStatisticalOutliers(int k, float std_mul);
 	int removeRadiusOutliers(float radius, int min_neighbors);
+	// The same edit by connectivity (symmicp_ctx_cluster with min_points = 1 and min_cluster_size = min_size): every connected part of a
+	// cloud -- points closer than eps -- with fewer than min_size points goes.  A floating blob of a dozen points passes both filters
+	// above, because each of its points has close neighbours; this one removes it.
+	int removeSmallClusters(float eps, int min_size);
 	void outliersRemoved(size_t *src, size_t *tgt) const { if (src) *src = removed_src_; if (tgt) *tgt = removed_tgt_; }
 	const char *lastError() const { return error_.c_str(); }
 
@@ -228,6 +232,6 @@ private:
 	std::vector<symmicp_batch_result> multi_results_;
 	int best_start_ = -1;
 	size_t removed_src_ = 0, removed_tgt_ = 0;
-	int removeOutliers(bool statistical, int k, float std_mul, float radius, int min_neighbors);
+	int removeOutliers(int filter, int k, float std_mul, float radius, int min_neighbors);      // filter: 0 statistical, 1 radius, 2 small clusters
 	std::string error_;
 };

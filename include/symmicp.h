@@ -679,6 +679,58 @@ int symmicp_radius_outlier_removal(int device, const float *xyz, size_t row_stri
                                    float radius, int min_neighbors, int32_t *rows_out, size_t cap, size_t *count_out,
                                    int32_t *neighbors_out);
 
+/* ---- DBSCAN and Euclidean cluster extraction (Ester et al. 1996; PCL's EuclideanClusterExtraction, Open3D's cluster_dbscan,
+ * scikit-learn's DBSCAN; DESIGN.md 4, "Clustering") -------------------------------------------------------------------------
+ * Splits a cloud of n points into its connected parts: the objects that symmicp_batch_align aligns pair by pair, and the small
+ * floating blobs that the per-point outlier filters above cannot see.  Defined by its arithmetic; the result is a function of
+ * the inputs alone, bit for bit (it does not depend on the order in which the device meets the edges).
+ * Neighbourhoods.  N(i) is exactly the neighbourhood of symmicp_ctx_radius_search at radius eps: r2 = eps * eps in fp32, d2 the
+ *   fp32 (dx*dx + dy*dy) + dz*dz, unfused, members d2 <= r2; row i itself is left out by ROW (a duplicate of it is a member).
+ *   d2(i, j) == d2(j, i) exactly, so the graph i -- j iff j in N(i) is symmetric.  neighbors_out[i] = |N(i)|.
+ * Core points.  Row i is CORE iff |N(i)| + 1 >= min_points (core_out[i] = 1): min_points counts the point itself, as Open3D and
+ *   scikit-learn do.  min_points = 1 makes every point core: PCL's Euclidean clustering at tolerance eps.
+ * Clusters.  A cluster is a connected component of that graph restricted to the core rows; its REPRESENTATIVE is its lowest core
+ *   row.
+ * Border points.  A non-core row with at least one core neighbour joins ONE cluster: among its core neighbours j the one with
+ *   the smallest d2 (compared as fp32 bits), an exact tie going to the cluster whose representative row is lowest -- the minimum
+ *   of the 64-bit key (d2 bits << 32) | representative(j).  A deliberate departure from PCL, Open3D and scikit-learn, where a
+ *   border point goes to whichever cluster their scan order reaches first (a function of the row order, and for parallel
+ *   implementations of the schedule).
+ * Noise.  Every other row: label -1.
+ * Labels.  The clusters are numbered 0 .. C - 1 in ascending order of their representative row.  On every core row and every noise
+ *   row this is scikit-learn's DBSCAN(eps, min_samples = min_points).labels_; only border rows can differ.
+ * Size filter.  A cluster's size is its core rows plus its border rows.  With min_cluster_size > 0 or max_cluster_size > 0 a
+ *   cluster whose size lies outside [min, max] (0 = no bound on that side) becomes noise (-1), and the remaining clusters are
+ *   renumbered in the same order.  core_out and neighbors_out describe the points BEFORE the size filter.
+ * Output.  labels_out [n] and *clusters_out (the number of clusters after the filter) are required.  sizes_out [cap]: the sizes
+ *   of clusters 0 .. C - 1.  SYMMICP_ERR_SIZE when C exceeds cap: the labels, the count and the per-point arrays are written,
+ *   the sizes are not -- call again with room (sizes_out may be NULL with cap == 0).  core_out [n] and neighbors_out [n] may be
+ *   NULL.
+ * Cost grows with the neighbour counts (there is no max_nn cap): three walks of the tree for min_points > 1 (count, union,
+ *   border), two for min_points == 1.  The radius graph is never stored.
+ * SYMMICP_ERR_ARG, all decided on the host before a device is needed: NULL xyz / cfg / labels_out / clusters_out; NULL sizes_out
+ *   with cap > 0; n == 0 or n > 2^31 - 1; cfg->struct_size != sizeof(symmicp_cluster_config); eps not finite or not > 0;
+ *   min_points < 1; a negative size bound, or max_cluster_size < min_cluster_size with both > 0; non-finite coordinates.
+ * xyz strided as in symmicp_set_source.  The ctx form runs on the context's stream and arenas: the context's clouds, index,
+ * attributes, certificates and states stay exactly as they were.  A sharded job computes the full result on every rank (the
+ * output is deterministic). */
+typedef struct {
+    uint32_t struct_size;       /* = sizeof(symmicp_cluster_config), checked */
+    float    eps;               /* finite, > 0 (the caller sets it; default 0) */
+    int32_t  min_points;        /* >= 1, counts the point itself; default 1 */
+    int32_t  min_cluster_size;  /* >= 0, 0 = none */
+    int32_t  max_cluster_size;  /* >= 0, 0 = none; if both > 0, max >= min */
+    int32_t  reserved;
+} symmicp_cluster_config;
+void symmicp_cluster_config_default(symmicp_cluster_config *cfg);
+int symmicp_ctx_cluster(symmicp_ctx *ctx, const float *xyz, size_t row_stride, size_t col_stride, size_t n,
+                        const symmicp_cluster_config *cfg, int32_t *labels_out, size_t *clusters_out, int32_t *sizes_out,
+                        size_t cap, uint8_t *core_out, int32_t *neighbors_out);
+/* the same on a context of its own, created on `device` (-1 = current) and destroyed again */
+int symmicp_cluster(int device, const float *xyz, size_t row_stride, size_t col_stride, size_t n,
+                    const symmicp_cluster_config *cfg, int32_t *labels_out, size_t *clusters_out, int32_t *sizes_out,
+                    size_t cap, uint8_t *core_out, int32_t *neighbors_out);
+
 /* ---- feature matching and RANSAC: global registration from FPFH features ("Feature matching and RANSAC") -------
  * All three run on the context's stream and temporary arena; the context's source, target, index and certificates stay exactly
  * as they were.  A sharded job computes the full result on every rank (the outputs are deterministic).
