@@ -1,4 +1,5 @@
-// device_common.h -- small device helpers shared by the pass kernels (kernels_pass.hip, kernels_packet.hip).
+// device_common.h -- small device helpers shared by the pass kernels (kernels_pass.hip, kernels_packet.hip) and, for the distance
+// pair, by the walks of the cloud operations (box_walk.h).
 //
 // fp32 expressions here must stay UNFUSED (the including file is compiled with -ffp-contract=off and carries
 // `#pragma clang fp contract(off)`) and keep the association written: the CPU oracle uses the same expressions, so

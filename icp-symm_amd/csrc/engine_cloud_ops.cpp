@@ -55,6 +55,23 @@ private:
     bool surf0 = false;
 };
 
+// the tail of every read-back: wait for the stream, then report what a launch on it left behind
+int stream_done(symmicp_ctx *c)
+{
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    HIP_TRY(c, hipGetLastError());
+    return SYMMICP_OK;
+}
+
+// the argument check of ISS, outlier removal and clustering: every coordinate of the cloud is finite
+bool coords_finite(const float *xyz, size_t xr, size_t xc, size_t n)
+{
+    for (size_t i = 0; i < n; i++)
+        for (int a = 0; a < 3; a++)
+            if (!std::isfinite(xyz[i * xr + a * xc])) return false;
+    return true;
+}
+
 // the host compaction of the outlier filters, with the cap protocol of the ISS entry: the count always, the rows (ascending) when they fit
 template <class Keep>
 int outlier_compact(symmicp_ctx *c, const char *who, size_t n, Keep &&keep, int32_t *rows_out, size_t cap, size_t *count_out)
@@ -102,9 +119,7 @@ static int normals_or_knn(symmicp_ctx *c, const float *xyz, size_t row_stride, s
         HIP_TRY(c, hipMemcpyAsync(nrm_out, b_a.p, sizeof(float) * 3 * n, hipMemcpyDeviceToHost, c->stream));
         if (curv_out) HIP_TRY(c, hipMemcpyAsync(curv_out, b_b.p, sizeof(float) * n, hipMemcpyDeviceToHost, c->stream));
     }
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    HIP_TRY(c, hipGetLastError());
-    return SYMMICP_OK;
+    return stream_done(c);
 }
 
 int symmicp_ctx_estimate_normals(symmicp_ctx *c, const float *xyz, size_t row_stride, size_t col_stride, size_t n, int k,
@@ -160,8 +175,7 @@ static int radius_search(symmicp_ctx *c, const float *xyz, size_t xr, size_t xc,
     HIP_TRY(c, hipMemcpyAsync(d_offs.p, d_count.p, sizeof(uint32_t) * n, hipMemcpyDeviceToDevice, c->stream));
     launch_exclusive_scan(d_offs.p, (uint32_t)n, scan_ws.p, c->stream);
     HIP_TRY(c, hipMemcpyAsync(count_out, d_count.p, sizeof(int32_t) * n, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    HIP_TRY(c, hipGetLastError());
+    if (int st = stream_done(c)) return st;
     uint64_t total = 0;
     for (size_t i = 0; i < n; i++) total += (uint64_t)(uint32_t)count_out[i];
     *total_out = (size_t)total;
@@ -180,9 +194,7 @@ static int radius_search(symmicp_ctx *c, const float *xyz, size_t xr, size_t xc,
     launch_radius_fill(si.ix, r2, d_offs.p, d_rows.p, d_d2.p, c->stream);
     HIP_TRY(c, hipMemcpyAsync(rows_out, d_rows.p, sizeof(int32_t) * total, hipMemcpyDeviceToHost, c->stream));
     if (d2_out) HIP_TRY(c, hipMemcpyAsync(d2_out, d_d2.p, sizeof(float) * total, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    HIP_TRY(c, hipGetLastError());
-    return SYMMICP_OK;
+    return stream_done(c);
 }
 
 int symmicp_ctx_radius_search(symmicp_ctx *c, const float *xyz, size_t row_stride, size_t col_stride, size_t n, float radius,
@@ -229,9 +241,7 @@ int symmicp_ctx_fpfh(symmicp_ctx *c, const float *xyz, size_t xyz_row_stride, si
     HIP_TRY(c, hipMemcpyAsync(fpfh_out, d_fpfh.p, sizeof(float) * 33 * n, hipMemcpyDeviceToHost, c->stream));
     if (spfh_out) HIP_TRY(c, hipMemcpyAsync(spfh_out, d_spfh.p, sizeof(float) * 33 * n, hipMemcpyDeviceToHost, c->stream));
     if (count_out) HIP_TRY(c, hipMemcpyAsync(count_out, d_count.p, sizeof(int32_t) * n, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    HIP_TRY(c, hipGetLastError());
-    return SYMMICP_OK;
+    return stream_done(c);
 }
 
 int symmicp_fpfh(int device, const float *xyz, size_t xyz_row_stride, size_t xyz_col_stride, const float *nrm, size_t nrm_row_stride,
@@ -258,9 +268,7 @@ static const char *iss_args_error(const float *xyz, size_t xr, size_t xc, size_t
     if (!(cfg->gamma21 > 0.f) || !(cfg->gamma21 <= 1.f)) return "iss_keypoints: gamma21 must be in (0, 1]";
     if (!(cfg->gamma32 > 0.f) || !(cfg->gamma32 <= 1.f)) return "iss_keypoints: gamma32 must be in (0, 1]";
     if (cfg->min_neighbors < 1) return "iss_keypoints: min_neighbors must be >= 1";
-    for (size_t i = 0; i < n; i++)
-        for (int a = 0; a < 3; a++)
-            if (!std::isfinite(xyz[i * xr + a * xc])) return "iss_keypoints: a coordinate is not finite";
+    if (!coords_finite(xyz, xr, xc, n)) return "iss_keypoints: a coordinate is not finite";
     return nullptr;
 }
 
@@ -300,8 +308,7 @@ int symmicp_ctx_iss_keypoints(symmicp_ctx *c, const float *xyz, size_t row_strid
     HIP_TRY(c, hipMemcpyAsync(&last_flag, d_flag.p + (n - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
     if (saliency_out) HIP_TRY(c, hipMemcpyAsync(saliency_out, d_srows.p, sizeof(float) * n, hipMemcpyDeviceToHost, c->stream));
     if (neighbors_out) HIP_TRY(c, hipMemcpyAsync(neighbors_out, d_k.p, sizeof(int32_t) * n, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    HIP_TRY(c, hipGetLastError());
+    if (int st = stream_done(c)) return st;
     const size_t count = (size_t)last_pos + last_flag;
     *count_out = count;
     if (count > cap) return fail(c, SYMMICP_ERR_SIZE, "iss_keypoints: " + std::to_string(count) + " keypoints do not fit cap " + std::to_string(cap));
@@ -309,9 +316,7 @@ int symmicp_ctx_iss_keypoints(symmicp_ctx *c, const float *xyz, size_t row_strid
     HIP_TRY(c, d_rows.alloc_temp(c->arena, count));
     launch_iss_scatter(d_flag.p, d_pos.p, (uint32_t)n, d_rows.p, c->stream);
     HIP_TRY(c, hipMemcpyAsync(rows_out, d_rows.p, sizeof(int32_t) * count, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    HIP_TRY(c, hipGetLastError());
-    return SYMMICP_OK;
+    return stream_done(c);
 }
 
 int symmicp_iss_keypoints(int device, const float *xyz, size_t row_stride, size_t col_stride, size_t n, const symmicp_iss_config *cfg,
@@ -333,9 +338,7 @@ static const char *outlier_args_error(const float *xyz, size_t xr, size_t xc, si
     if (!xyz || !count_out) return "outlier removal: xyz and count_out are required";
     if (!rows_out && cap > 0) return "outlier removal: rows_out is required when cap > 0";
     if (n == 0 || n > 0x7fffffffull) return "outlier removal: n must be in 1 .. 2^31 - 1";
-    for (size_t i = 0; i < n; i++)
-        for (int a = 0; a < 3; a++)
-            if (!std::isfinite(xyz[i * xr + a * xc])) return "outlier removal: a coordinate is not finite";
+    if (!coords_finite(xyz, xr, xc, n)) return "outlier removal: a coordinate is not finite";
     return nullptr;
 }
 
@@ -375,8 +378,7 @@ int symmicp_ctx_statistical_outlier_removal(symmicp_ctx *c, const float *xyz, si
         HIP_TRY(c, hipGetLastError());
         if (!m) { own.resize(n); m = own.data(); }
         HIP_TRY(c, hipMemcpyAsync(m, d_mean.p, sizeof(double) * n, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        HIP_TRY(c, hipGetLastError());
+        if (int st = stream_done(c)) return st;
     }
     // PCL's formula, sequentially in row order (this file is built with -ffp-contract=off: nothing here is fused)
     double s1 = 0.0, s2 = 0.0;
@@ -416,8 +418,7 @@ int symmicp_ctx_radius_outlier_removal(symmicp_ctx *c, const float *xyz, size_t 
         HIP_TRY(c, hipGetLastError());
         if (!nb) { own.resize(n); nb = own.data(); }
         HIP_TRY(c, hipMemcpyAsync(nb, d_count.p, sizeof(int32_t) * n, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        HIP_TRY(c, hipGetLastError());
+        if (int st = stream_done(c)) return st;
     }
     return outlier_compact(c, "radius_outlier_removal", n, [&](size_t i) { return nb[i] >= min_neighbors; }, rows_out, cap, count_out);
 }
@@ -447,9 +448,7 @@ static const char *cluster_args_error(const float *xyz, size_t xr, size_t xc, si
     if (cfg->min_cluster_size < 0 || cfg->max_cluster_size < 0) return "cluster: min_cluster_size and max_cluster_size must be >= 0";
     if (cfg->min_cluster_size > 0 && cfg->max_cluster_size > 0 && cfg->max_cluster_size < cfg->min_cluster_size)
         return "cluster: max_cluster_size is below min_cluster_size";
-    for (size_t i = 0; i < n; i++)
-        for (int a = 0; a < 3; a++)
-            if (!std::isfinite(xyz[i * xr + a * xc])) return "cluster: a coordinate is not finite";
+    if (!coords_finite(xyz, xr, xc, n)) return "cluster: a coordinate is not finite";
     return nullptr;
 }
 
@@ -491,8 +490,7 @@ int symmicp_ctx_cluster(symmicp_ctx *c, const float *xyz, size_t row_stride, siz
         HIP_TRY(c, hipMemcpyAsync(nb, d_count.p, sizeof(int32_t) * n, hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(c, hipMemcpyAsync(root.data(), d_parent.p, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, c->stream));
         if (d_stats.p) HIP_TRY(c, hipMemcpyAsync(stats, d_stats.p, sizeof(stats), hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        HIP_TRY(c, hipGetLastError());
+        if (int st = stream_done(c)) return st;
         if (d_stats.p) std::fprintf(stderr, "symmicp cluster: n %zu, %llu unions, %llu lost compare-and-swaps\n", n, stats[0], stats[1]);
     }
     if (core_out) for (size_t i = 0; i < n; i++) core_out[i] = nb[i] >= need ? 1 : 0;
@@ -560,9 +558,7 @@ int symmicp_ctx_intensity_gradient(symmicp_ctx *c, const float *xyz, size_t xyz_
     launch_knn(si.ix, k, d_rows.p, d_d2.p, c->stream);
     launch_color_gradient(si.ix, d_int.p, d_rows.p, k, d_rec.p, d_grad.p, c->stream);
     HIP_TRY(c, hipMemcpyAsync(grad_out, d_grad.p, sizeof(float) * 3 * n, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    HIP_TRY(c, hipGetLastError());
-    return SYMMICP_OK;
+    return stream_done(c);
 }
 
 int symmicp_intensity_gradient(int device, const float *xyz, size_t xyz_row_stride, size_t xyz_col_stride, const float *nrm,
@@ -663,9 +659,7 @@ static int voxel_downsample(symmicp_ctx *c, const float *xyz, size_t xr, size_t 
     if (with_nrm) HIP_TRY(c, hipMemcpyAsync(nrm_out, d_nrm.p, sizeof(float) * 3 * m, hipMemcpyDeviceToHost, c->stream));
     if (count_out) HIP_TRY(c, hipMemcpyAsync(count_out, d_count.p, sizeof(int32_t) * m, hipMemcpyDeviceToHost, c->stream));
     if (voxel_of) HIP_TRY(c, hipMemcpyAsync(voxel_of, d_vof.p, sizeof(int32_t) * n, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    HIP_TRY(c, hipGetLastError());
-    return SYMMICP_OK;
+    return stream_done(c);
 }
 
 static const char *voxel_args_error(const float *xyz, const float *nrm, size_t n, float leaf, int min_points, const float *xyz_out,

@@ -2,7 +2,7 @@
 // DESIGN.md 4 "Clustering" has the measurements; tests/_cluster_ref.py restates it in numpy).
 //
 // The clusters are the connected components of the radius graph on the CORE rows.  That graph is never stored (1M points with 30
-// neighbours each would be 30M edges): every kernel walks the box tree with the exact radius walk of radius_walk.h and meets the edges
+// neighbours each would be 30M edges): every kernel walks the box tree with the exact radius walk of box_walk.h and meets the edges
 // of its point on the way.  The core flags are the counts of launch_radius_count (kernels_fpfh.hip) compared with min_points - 1.
 //
 //   k_cluster_init     parent[row] = row
@@ -17,7 +17,7 @@
 // No loop in these kernels waits for another thread (cluster_core.h): a lost compare-and-swap descends and goes on.
 #include "symmicp_internal.h"
 #pragma clang fp contract(off)
-#include "radius_walk.h"          // radius_walk, stage_level_off
+#include "box_walk.h"             // radius_walk, stage_level_off
 #include "cluster_core.h"
 
 namespace symmicp {

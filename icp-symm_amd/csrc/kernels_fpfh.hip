@@ -2,10 +2,9 @@
 // PCL FPFHEstimation) on gfx950.  include/symmicp.h defines the arithmetic; tests/_fpfh_ref.py restates it in numpy.
 //
 // All four kernels run one thread per point in the index's sorted (Morton) order and walk the implicit 8-ary box tree in
-// pre-order, as k_normals_knn does, with a FIXED bound r2 instead of a shrinking one.  The fp32 box distance is a lower bound
-// of the fp32 point distance of every point in the box (subtraction, square and sum are monotone under rounding, and both use
-// the association (dx*dx + dy*dy) + dz*dz), so pruning at boxdist2 > r2 loses no member of { d2 <= r2 }.  The walk meets the
-// leaves, and the points in them, in ascending sorted position: that is the order of the radius lists and of the FPFH sums.
+// pre-order, as k_normals_knn does, with a FIXED bound r2 instead of a shrinking one (radius_walk, box_walk.h: pruning loses no
+// member of { d2 <= r2 }).  The walk meets the leaves, and the points in them, in ascending sorted position: that is the order of
+// the radius lists and of the FPFH sums.
 //
 //   k_radius<false>  count pass:  count[row] = |N(row)|
 //   k_radius<true>   fill pass:   the same walk again, writing (row, d2) from offs[row] on (no atomics)
@@ -17,7 +16,7 @@
 // and working the queues off wave-wide was measured and gained nothing.
 #include "symmicp_internal.h"
 #pragma clang fp contract(off)
-#include "radius_walk.h"          // f_dist2, f_boxdist2, radius_walk, stage_level_off (shared with kernels_keypoints.hip)
+#include "box_walk.h"             // radius_walk, stage_level_off
 
 namespace symmicp {
 

@@ -1,12 +1,12 @@
 // kernels_keypoints.hip -- Intrinsic Shape Signatures keypoints (Zhong 2009; PCL's ISSKeypoint3D, Open3D's compute_iss_keypoints)
 // on gfx950.  include/symmicp.h defines the arithmetic; tests/_iss_ref.py restates it in numpy.
 //
-// Both stages run one thread per point in the index's sorted (Morton) order over the exact radius walk of radius_walk.h, which
+// Both stages run one thread per point in the index's sorted (Morton) order over the exact radius walk of box_walk.h, which
 // meets the neighbours in ascending sorted position: that is the order of the fp64 sums.
 //
 //   k_iss_saliency  the walk at the salient radius: e = x_j - x_i in fp32, the six upper entries of the scatter matrix summed in
 //                   fp64 (the products of two fp32 values are exact in fp64), C = S / k, its eigenvalues by cyclic Jacobi
-//                   rotations (the rotations of smallest_eigvec3 in kernels_normals.hip without the vector matrix), the two
+//                   rotations (jacobi3 of eig3.h, without the vector matrix), the two
 //                   ratio tests as products.  Six fp64 accumulators and the count live in registers.  Writes the saliency by
 //                   sorted position (what k_iss_nms gathers: 4 B per neighbour) and, with the count, by original row.
 //   k_iss_nms       the walk at the non-maximum radius: a point with s > 0 stays a keypoint unless a neighbour has a larger
@@ -15,41 +15,19 @@
 //   k_iss_scatter   after the exclusive scan of the flags over rows: rows_out[pos[row]] = row -- ascending rows, no atomics.
 #include "symmicp_internal.h"
 #pragma clang fp contract(off)
-#include "radius_walk.h"
+#include "box_walk.h"
+#include "eig3.h"
 
 namespace symmicp {
 
 constexpr int kIssThreads = 256;
 
-// eigenvalues of the symmetric 3x3 (fp64) by cyclic Jacobi: the sweeps, thresholds and rotation formulas of smallest_eigvec3
-// (kernels_normals.hip), without the eigenvector matrix; l1 >= l2 >= l3
+// eigenvalues of the symmetric 3x3 (fp64) by cyclic Jacobi (jacobi3, eig3.h), without the eigenvector matrix; l1 >= l2 >= l3
 __device__ __forceinline__ void eigvals3(double a00, double a01, double a02, double a11, double a12, double a22, double &l1, double &l2,
                                          double &l3)
 {
     double A[3][3] = {{a00, a01, a02}, {a01, a11, a12}, {a02, a12, a22}};
-    for (int sweep = 0; sweep < 12; sweep++) {
-        double off = A[0][1] * A[0][1] + A[0][2] * A[0][2] + A[1][2] * A[1][2];
-        if (off < 1e-300) break;
-#pragma unroll
-        for (int pq = 0; pq < 3; pq++) {
-            const int p = (pq == 2) ? 1 : 0, q = (pq == 0) ? 1 : 2;
-            double apq = A[p][q];
-            if (fabs(apq) < 1e-300) continue;
-            double theta = (A[q][q] - A[p][p]) / (2.0 * apq);
-            double t = (theta >= 0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
-            double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
-#pragma unroll
-            for (int k = 0; k < 3; k++) {
-                double kp = A[k][p], kq = A[k][q];
-                A[k][p] = c * kp - s * kq; A[k][q] = s * kp + c * kq;
-            }
-#pragma unroll
-            for (int k = 0; k < 3; k++) {
-                double pk = A[p][k], qk = A[q][k];
-                A[p][k] = c * pk - s * qk; A[q][k] = s * pk + c * qk;
-            }
-        }
-    }
+    jacobi3<false>(A, nullptr);
     double w0 = A[0][0], w1 = A[1][1], w2 = A[2][2], t;
     if (w0 < w1) { t = w0; w0 = w1; w1 = t; }
     if (w1 < w2) { t = w1; w1 = w2; w2 = t; }

@@ -1,17 +1,15 @@
 // kernels_outlier.hip -- the hot kernel of statistical outlier removal on gfx950 (symmicp_ctx_statistical_outlier_removal; DESIGN.md 4,
 // "Outlier removal"): per point the exact mean distance to its k nearest neighbours, k up to 64.
 // One thread per point in the index's sorted (Morton) order walks the implicit 8-ary box tree in pre-order, pruned by the current k-th
-// smallest distance, as k_normals_knn does (kernels_normals.hip).  That kernel keeps (d2, row, position) of k <= 16 candidates in
-// registers; here k runs to 64 and only the DISTANCES matter (ties at the k-th value leave the multiset of values unchanged), so the
+// smallest distance (box_walk.h has the proof that this loses no point), as k_normals_knn does (kernels_normals.hip).  That kernel
+// keeps (d2, row, position) of k <= 16 candidates in registers; here k runs to 64 and only the DISTANCES matter (ties at the k-th value leave the multiset of values unchanged), so the
 // list is one fp32 per slot, in LDS, slot-major: list[slot * blockDim + tid].  A lane's bank is tid % 32 whatever slot it touches, so
 // lanes inserting at different depths never conflict.  The list is a max-heap (the root is the k-th smallest so far, the pruning bound);
 // it is heap-sorted in place at the end, because the fp64 sum has to run in ascending d2.  Block and LDS are sized from k at launch
 // (outlier_block).
-// The fp32 box distance is a lower bound of the fp32 point distance of every point in the box (radius_walk.h), so pruning at
-// boxdist2 > bound loses no point with d2 <= bound.
 #include "symmicp_internal.h"
 #pragma clang fp contract(off)
-#include "radius_walk.h"          // f_dist2, f_boxdist2, stage_level_off
+#include "box_walk.h"             // dist2, boxdist2, stage_level_off
 
 namespace symmicp {
 
@@ -77,22 +75,25 @@ __global__ __launch_bounds__(256) void k_knn_mean_dist(TargetIndex ix, int k, do
     for (uint32_t jj = w0; jj < w1; jj++) {
         if (jj == i) continue;
         const float4 q = ix.tq[jj];
-        const float d2 = f_dist2(px, py, pz, q.x, q.y, q.z);
+        const float d2 = dist2(px, py, pz, q.x, q.y, q.z);
         if (d2 < worst) worst = heap_replace_root(mine, stride, k, d2);
     }
 
+    // The loop of box_walk (box_walk.h), written out.  Through box_walk the compiler emits the same instructions with one scalar move
+    // placed ahead of the walk, which pushes the walk 4 bytes on: the two sift loops inside it no longer start on a 64-byte line, and
+    // the kernel measured 3 to 7 % slower at every k on 1M points ("Outlier removal").
     int level = ix.top;
     uint32_t node = 0;
     while (true) {
         const float4 *bx = ix.boxes + 2 * ((size_t)loff[level] + node);
         const float4 lo = bx[0], hi = bx[1];
-        const bool hit = (f_boxdist2(px, py, pz, lo, hi) <= worst) && (lo.x <= hi.x);
+        const bool hit = (boxdist2(px, py, pz, lo, hi) <= worst) && (lo.x <= hi.x);
         if (hit && level > 0) { level--; node <<= 3; continue; }
         if (hit) {
             const uint32_t j0 = node * kLeaf, j1 = min(j0 + kLeaf, ix.n);
             for (uint32_t jj = j0; jj < j1; jj++) {
                 const float4 q = ix.tq[jj];
-                const float d2 = f_dist2(px, py, pz, q.x, q.y, q.z);
+                const float d2 = dist2(px, py, pz, q.x, q.y, q.z);
                 if (d2 < worst && jj - w0 >= w1 - w0) worst = heap_replace_root(mine, stride, k, d2);
             }
         }

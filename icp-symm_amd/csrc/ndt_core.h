@@ -6,6 +6,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>
+#include "eig3.h"
 #pragma clang fp contract(off)
 
 namespace symmicp {
@@ -28,40 +29,13 @@ __host__ __device__ inline float ndt_weight(float x)
     return ldexpf(y, (int)k);
 }
 
-// The cyclic Jacobi of the normals pre-step (kernels_normals.hip, smallest_eigvec3: the same sweeps, rotations and thresholds) on a
-// symmetric 3x3 in fp64, keeping all three vectors: lam[r] ascending (ties keep the diagonal's order), vec[r] = the eigenvector of lam[r].
+// The eigen-decomposition of a symmetric 3x3 in fp64 (jacobi3, eig3.h), keeping all three vectors: lam[r] ascending (ties keep the
+// diagonal's order), vec[r] = the eigenvector of lam[r].
 __host__ __device__ inline void ndt_eig3(double a00, double a01, double a02, double a11, double a12, double a22, double lam[3], double vec[3][3])
 {
     double A[3][3] = {{a00, a01, a02}, {a01, a11, a12}, {a02, a12, a22}};
     double V[3][3] = {{1, 0, 0}, {0, 1, 0}, {0, 0, 1}};
-    for (int sweep = 0; sweep < 12; sweep++) {
-        const double off = A[0][1] * A[0][1] + A[0][2] * A[0][2] + A[1][2] * A[1][2];
-        if (off < 1e-300) break;
-#pragma unroll
-        for (int pq = 0; pq < 3; pq++) {
-            const int p = (pq == 2) ? 1 : 0, q = (pq == 0) ? 1 : 2;
-            const double apq = A[p][q];
-            if (fabs(apq) < 1e-300) continue;
-            const double theta = (A[q][q] - A[p][p]) / (2.0 * apq);
-            const double t = (theta >= 0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
-            const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
-#pragma unroll
-            for (int k = 0; k < 3; k++) {
-                const double kp = A[k][p], kq = A[k][q];
-                A[k][p] = c * kp - s * kq; A[k][q] = s * kp + c * kq;
-            }
-#pragma unroll
-            for (int k = 0; k < 3; k++) {
-                const double pk = A[p][k], qk = A[q][k];
-                A[p][k] = c * pk - s * qk; A[q][k] = s * pk + c * qk;
-            }
-#pragma unroll
-            for (int k = 0; k < 3; k++) {
-                const double kp = V[k][p], kq = V[k][q];
-                V[k][p] = c * kp - s * kq; V[k][q] = s * kp + c * kq;
-            }
-        }
-    }
+    jacobi3<true>(A, V);
     double w0 = A[0][0], w1 = A[1][1], w2 = A[2][2];
     double v0[3] = {V[0][0], V[1][0], V[2][0]}, v1[3] = {V[0][1], V[1][1], V[2][1]}, v2[3] = {V[0][2], V[1][2], V[2][2]};
     // a stable three-element sort by static swaps (no indexed registers)
