@@ -1040,7 +1040,7 @@ int symmicp_set_source(symmicp_ctx *c, const float *xyz, size_t xr, size_t xc, c
     }
     HIP_TRY(c, hipStreamSynchronize(c->stream));       // (the arena-backed upload is read by the gather above)
     HIP_TRY(c, hipGetLastError());
-    c->last_list_len = -1;
+    c->fb.forget_list();
     c->st.upload_ms += (now_s() - t0) * 1e3;
     return SYMMICP_OK;
 }

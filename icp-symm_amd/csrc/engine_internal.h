@@ -3,7 +3,8 @@
 //   engine.cpp           lifetime, configuration, uploads, index build, set_target / set_source, getters, statistics
 //   engine_cloud_ops.cpp stand-alone cloud operations on a scratch index: normals and k-NN, radius search, FPFH, ISS keypoints, intensity
 //                        gradient; voxel downsampling
-//   engine_loop.cpp      the iteration loop: one pass (run_pass), device-driven runs of passes (run_batch), begin / step / align, result block
+//   engine_loop.cpp      the iteration loop: one pass (run_pass), device-driven runs of passes (run_batch), begin / step / align, result block;
+//                        what it launches is decided by the plain functions of loop_plan.h (no HIP, no context: tests/cpp/loop_plan.cpp)
 //   engine_exchange.cpp  multi-GPU: RCCL (loaded lazily), shared-memory exchange, communicator entry points
 //   engine_global.cpp    feature matching and RANSAC (symmicp_ctx_feature_nn, symmicp_ctx_feature_correspondences, symmicp_ctx_ransac)
 //   engine_debug.cpp     SYMMICP_DEBUG_COUNTERS / SYMMICP_DEBUG_TRACE dumps
@@ -33,6 +34,7 @@
 #include "symmicp.h"
 #include "symmicp_internal.h"
 #include "host_solve.h"
+#include "loop_plan.h"
 
 
 namespace symmicp {}
@@ -289,9 +291,7 @@ struct symmicp_ctx {
     int pass_blocks = 0;
     double *partials = nullptr, *d_sums = nullptr, *h_sums = nullptr, *h_sums_dev = nullptr;   // h_sums: 40 doubles + sequence word
     uint32_t *ticket = nullptr;          // ticket of the final reduce
-    long long last_list_len = -1;        // work-list length of the last pass (all ranks); -1 = unknown (full walk grid)
-    long long last_uncertified = -1;     // TREE: pairs the last pass had to search again (all ranks); -1 = unknown
-    long long last_scans = -1;           // ... and those of them that reached a scan, a probe or the walk; -1 = unknown
+    PassFeedback fb;                     // what the last pass tells the next: its work list and the pairs it searched and scanned (loop_plan.h)
     bool cert_pass_failed = false;       // a certified-only pass of this alignment came back incomplete: the kernel is not chosen again
     // device-driven runs of passes (run_batch): loop state in device memory, per-pass records + end flag in host-mapped memory
     static constexpr int kRing = 65;
@@ -462,3 +462,9 @@ int shm_exchange(symmicp_ctx *c, double *rec);      // rec[40]: this rank's reco
 // engine_debug.cpp
 void dump_packet_trace(symmicp_ctx *c);
 void print_pass_counters(symmicp_ctx *c, bool first, long long list_len);
+// SYMMICP_DEBUG_HOST: what a device-driven run (passes it0 + 1 .. it1 of `want`, `enq` enqueued) did; pass_kernel: by iteration % kRing,
+// 1 = the certified-only kernel; before: the feedback of the host pass in front of the run
+void print_batch_summary(const symmicp_ctx *c, int it0, int it1, int want, int enq, int n_stage, const uint8_t *pass_kernel, const PassFeedback &before);
+// the record of iteration k in the ring of a device-driven run
+inline int ring_slot(int k) { return k % symmicp_ctx::kRing; }
+inline LoopRecord &ring_at(const symmicp_ctx *c, int k) { return c->h_ring[ring_slot(k)]; }

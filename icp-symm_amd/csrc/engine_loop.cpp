@@ -69,7 +69,30 @@ static int wait_for_word(symmicp_ctx *c, const volatile unsigned long long *flag
     return SYMMICP_OK;
 }
 
-static void fill_pass_args(symmicp_ctx *c, PassArgs &a, const RejectArgs &rej, const float Xapply[16], bool from_cur, bool writeback, bool first)
+static_assert(kPlanTile == (uint32_t)kPassThreads, "loop_plan.h sizes grids in tiles of kPassThreads points");
+
+// the pass honours the pair certificates (not the first pass of an alignment: they are not valid yet)
+static bool pass_uses_slack(const symmicp_ctx *c, bool first) { return !first && c->cert && !c->sw.no_cert; }
+
+// The plan of the next pass (plan_tree_pass, loop_plan.h) from the context: the feedback of the pass before, the sizes and the switches.
+// (Every kind of pass asks: the pass arguments carry make_hood and budget_walk whatever the correspondences.)
+static TreePassPlan plan_pass(const symmicp_ctx *c, bool first, bool writeback)
+{
+    TreePassIn in{};
+    in.first = first; in.writeback = writeback; in.rejecting = pass_rejects(c);
+    in.fb = c->fb;
+    in.n_s_total = c->n_s_total; in.n_loc = c->n_loc; in.nranks = c->nranks;
+    in.use_slack = pass_uses_slack(c, first);
+    in.have_certk = c->certk && !c->sw.no_hood;
+    in.walk_full_grid = c->sw.walk_full_grid;
+    in.optimistic = c->sw.optimistic; in.compact = c->sw.compact; in.budget_walk = c->sw.budget_walk;
+    in.hood_frac = c->sw.hood_frac;
+    in.acc_blocks = c->sw.acc_blocks; in.compact_blocks = c->sw.compact_blocks;
+    return plan_tree_pass(in);
+}
+
+static void fill_pass_args(symmicp_ctx *c, PassArgs &a, const RejectArgs &rej, const TreePassPlan &plan, const float Xapply[16], bool from_cur, bool writeback,
+                           bool first)
 {
     a.in = from_cur ? c->cur : c->src0;
     a.out = c->cur;
@@ -98,13 +121,10 @@ static void fill_pass_args(symmicp_ctx *c, PassArgs &a, const RejectArgs &rej, c
     a.cert = reinterpret_cast<float4 *>(c->cert);
     a.certk = c->sw.no_hood ? nullptr : reinterpret_cast<uint4 *>(c->certk);
     a.hoodr = reinterpret_cast<float2 *>(c->hoodr);
-    // neighbourhoods are worth their stores once the alignment is settling (the previous pass searched under 80 % of the pairs: 8M scan pair
-    // 2 680 iter/s at 50 %, 2 776 at 80 %, 2 742 always; 1M surface pair 16 050 / 15 960 / 15 700)
-    a.make_hood = (a.certk && !first && c->last_uncertified >= 0 && (double)c->last_uncertified < c->sw.hood_frac * (double)c->n_s_total) ? 1 : 0;
+    a.make_hood = plan.make_hood ? 1 : 0;
     a.pairrec = c->pairrec;
-    // sharded runs: the first pass over a small share is bound by its slowest walks, not by throughput
-    a.budget_walk = c->sw.budget_walk >= 0 ? c->sw.budget_walk : (first && c->nranks > 1 && c->n_loc < 400000u);      // (SYMMICP_BUDGET_WALK: "0" never, "1" always)
-    a.use_slack = (!first && c->cert && !c->sw.no_cert) ? 1 : 0;
+    a.budget_walk = plan.budget_walk ? 1 : 0;
+    a.use_slack = pass_uses_slack(c, first) ? 1 : 0;
     a.loop = nullptr;
     a.pkt_tab = reinterpret_cast<const uint2 *>(c->pkt_tab);
     a.pkt_count = c->pkt_count;
@@ -118,161 +138,142 @@ static void fill_pass_args(symmicp_ctx *c, PassArgs &a, const RejectArgs &rej, c
     a.rej = rej;
 }
 
+// The pass's events in timing mode (null without): a slot of the ring, event 0 in front of the pass
+static hipEvent_t *begin_pass_events(symmicp_ctx *c, bool tree_pass)
+{
+    if (!c->timing) return nullptr;
+    if (c->ev_used == symmicp_ctx::kEvRing) flush_events(c);
+    hipEvent_t *ev = c->ev + c->ev_used * symmicp_ctx::kEvPer;
+    c->ev_split[c->ev_used] = (c->timing == 1 || c->timing == 3) ? 1 : 0;
+    c->ev_weight[c->ev_used] = 1;
+    // (in per-kernel mode the split launcher records ev[0] itself)
+    if (!(c->timing == 2 && tree_pass)) hipEventRecord(ev[0], c->stream);
+    return ev;
+}
+
+// The launchers of a pass's search and accumulation, one per kind of correspondence.  Each returns the number of partial records it leaves.
+// (NDT: cfg.corr is not read -- no search, no work list, no rejector)
+static int launch_ndt(symmicp_ctx *c, const float Xapply[16])
+{
+    const int blocks = ndt_blocks(c->n_loc, c->sw.acc_blocks);
+    NdtPassArgs na;
+    ndt_pass_args(c, Xapply, na);
+    launch_pass_ndt(na, blocks, c->stream);
+    return blocks;
+}
+
+static int launch_identity(symmicp_ctx *c, const PassArgs &a)
+{
+    const int cap = identity_vec4(c->n_loc, c->n_t, c->src_off) ? c->sw.id_blocks : host_pass_cap(c->sw.pass_blocks);
+    const IdentityGrid g = identity_grid(c->n_loc, c->n_t, c->src_off, cap);
+    launch_pass_identity(a, c->tgt, g.blocks, g.vec4, c->stream);
+    return g.blocks;
+}
+
+static int launch_brute(symmicp_ctx *c, const PassArgs &a)
+{
+    const int blocks = capped_blocks(c->n_loc, host_pass_cap(c->sw.pass_blocks), false, 1);
+    launch_nn_brute(a.in, c->n_loc, a.X, c->tq, c->n_t, c->best64, c->stream);
+    launch_pass_indexed(a, c->tn, blocks, c->stream);
+    return blocks;
+}
+
+static int launch_tree(symmicp_ctx *c, const PassArgs &a, const TreePassPlan &plan, bool first, hipEvent_t *ev)
+{
+    // per-kernel events only in timing mode 2; mode 1 brackets the pass (events 0 and 4)
+    hipEvent_t *kernel_ev = c->timing == 2 ? ev : nullptr;
+    if (first && c->target_surface_like) launch_pass_tree_first(a, c->ix, c->wl, plan.acc_blocks, c->stream, kernel_ev);
+    else launch_pass_tree_split(a, c->ix, c->wl, plan.acc_blocks, plan.walk_blocks, plan.optimistic ? 1 : 0, plan.compact_blocks, c->sw.tune, c->stream, kernel_ev);
+    if (kernel_ev) c->ev_split[c->ev_used] = 2;
+    return plan.acc_blocks;
+}
+
+// sums the record in d_sums over the ranks, in the stream.  A failure leaves the cleanup to the caller
+static int allreduce_record(symmicp_ctx *c)
+{
+    const int r = g_rccl.AllReduce(c->d_sums, c->d_sums, kNSum, kNcclFloat64, kNcclSum, c->comm, c->stream);
+    if (r != 0) return fail(c, SYMMICP_ERR_COMM, std::string("ncclAllReduce: ") + (g_rccl.GetErrorString ? g_rccl.GetErrorString(r) : "?"));
+    return SYMMICP_OK;
+}
+
+// Final reduce (+ all-reduce or shared-memory exchange over ranks), then wait for the record.  It arrives in host-mapped memory followed
+// by its sequence number: spin on that word instead of paying a stream-synchronise wake-up per iteration.  A stuck stream (kernel fault)
+// is caught by the fallback.
+static int reduce_and_wait(symmicp_ctx *c, int blocks, bool tree_pass, hipEvent_t *ev, int keep_nonempty)
+{
+    const unsigned long long seq = ++c->seq;
+    volatile unsigned long long *flag = reinterpret_cast<volatile unsigned long long *>(c->h_sums + kNSum);
+    launch_final_reduce(c->partials, blocks, c->d_sums, c->comm ? nullptr : c->h_sums_dev, c->ticket, seq, tree_pass ? c->wl_count : nullptr, keep_nonempty,
+                        c->stream);
+    if (c->comm) {
+        if (ev) { hipEventRecord(ev[6], c->stream); c->ev_coll[c->ev_used] = 1; }
+        if (int st = allreduce_record(c)) return st;
+        if (ev) hipEventRecord(ev[7], c->stream);
+        launch_publish(c->d_sums, c->h_sums_dev, seq, c->stream);
+    }
+    // the final-reduce time is only separated out in per-kernel mode; otherwise event 5 is event 4 again
+    if (ev && c->ev_split[c->ev_used] != 1) hipEventRecord(ev[5], c->stream);
+    if (int st = wait_for_word(c, flag, seq, 30.0, "pass finished without publishing its record", &c->t_spin)) return st;
+    return c->shm.slots ? shm_exchange(c, c->h_sums) : SYMMICP_OK;
+}
+
+// What a TREE pass's record says beside its sums (the two feedback slots, summed over ranks by the exchange, so every rank takes the same
+// decision): overflow check, the counts, the repair of an optimistic pass, the list.  *list_len: the work list's length
+static int absorb_tree_feedback(symmicp_ctx *c, const PassArgs &a, int blocks, bool first, bool optimistic, hipEvent_t *ev, uint64_t *list_len)
+{
+    const FeedbackWords w = feedback_decode(c->h_sums[kFeedbackListSlot], c->h_sums[kFeedbackCountSlot]);
+    if (w.dropped) return fail(c, SYMMICP_ERR_HIP, "a work-list shard overflowed: appends were dropped (internal capacity error)");
+    *list_len = (uint64_t)w.list_len;
+    if (first) c->fb.forget_counts(); else c->fb.set_counts((uint64_t)w.searched, (uint64_t)w.scans);
+    if (optimistic && *list_len > 0) {
+        // the walk was skipped but some queries needed it: their pairs are provisional, so are the sums
+        c->st.kernel_launches[7]++;
+        launch_pass_tree_split(a, c->ix, c->wl, blocks, repair_walk_blocks(*list_len), 2, 0, c->sw.tune, c->stream, nullptr);
+        if (ev && c->ev_split[c->ev_used] != 2) hipEventRecord(ev[4], c->stream);
+        if (int st = reduce_and_wait(c, blocks, true, ev, 0)) return st;
+    }
+    // (the packet first pass has no work list; the pass after it always has one)
+    if (first && c->target_surface_like) c->fb.expect_list(); else c->fb.set_list(*list_len);
+    return SYMMICP_OK;
+}
+
 static int run_pass(symmicp_ctx *c, const float Xapply[16], bool from_cur, bool writeback, bool first)
 {
     // A rejecting pass: search as always, then the claim, the keys of the candidates and tau (kernels_select.hip: issued by the pass
     // launchers in front of the accumulating kernel), then the accumulation over the pairs at or below tau and the final reduce.
-    PassArgs a{};
     RejectArgs rej;
     if (int st = prepare_rejectors(c, rej)) return st;
     c->rej.invalidate();
-    fill_pass_args(c, a, rej, Xapply, from_cur, writeback, first);
-    const bool rejecting = pass_rejects(a);
-    // (NDT: cfg.corr is not read -- no search, no work list, no rejector)
+    const TreePassPlan plan = plan_pass(c, first, writeback);
+    PassArgs a{};
+    fill_pass_args(c, a, rej, plan, Xapply, from_cur, writeback, first);
     const bool ndt = ndt_mode(c);
     const bool tree_pass = !ndt && c->cfg.corr == SYMMICP_CORR_TREE;
-    int blocks = (int)((c->n_loc + kPassThreads - 1) / kPassThreads);
-    int cap = c->sw.pass_blocks;
-    if (cap > 8192) cap = 8192;
-    if (blocks > cap) blocks = cap;
-    if (blocks < 1) blocks = 1;
-    c->pass_blocks = blocks;
     const double t_l0 = now_s();
     if (c->t_last_done > 0) c->t_between += t_l0 - c->t_last_done;
-    hipEvent_t *ev = nullptr;
-    uint32_t walk_blocks = 0;
-    bool optimistic = false;
-    if (c->timing) {
-        if (c->ev_used == symmicp_ctx::kEvRing) flush_events(c);
-        ev = c->ev + c->ev_used * symmicp_ctx::kEvPer;
-        c->ev_split[c->ev_used] = (c->timing == 1 || c->timing == 3) ? 1 : 0;
-        c->ev_weight[c->ev_used] = 1;
-    }
-    // (in per-kernel mode the split launcher records ev[0] itself)
-    if (ev && !(c->timing == 2 && tree_pass)) hipEventRecord(ev[0], c->stream);
-    if (ndt) {
-        // one accumulating kernel over (point, voxel) items, its grid capped like the others' (2 blocks per CU)
-        const int acc_cap = c->sw.acc_blocks;
-        const int nb_all = (int)((c->n_loc + kPassThreads - 1) / kPassThreads);
-        blocks = nb_all < acc_cap ? nb_all : acc_cap;
-        if (blocks < 1) blocks = 1;
-        c->pass_blocks = blocks;
-        NdtPassArgs na;
-        ndt_pass_args(c, Xapply, na);
-        launch_pass_ndt(na, blocks, c->stream);
-    } else
-    switch (c->cfg.corr) {
-    case SYMMICP_CORR_IDENTITY: {
-        // 16-byte column loads need every planar column (length n_loc / n_t) and the shard offset to keep 16-B alignment
-        const bool vec4 = (c->n_loc % 4 == 0) && (c->n_t % 4 == 0) && (c->src_off % 4 == 0);
-        if (vec4) {
-            const int id_cap = c->sw.id_blocks;
-            const int nb4 = (int)((c->n_loc / 4 + kPassThreads - 1) / kPassThreads);
-            blocks = nb4 < id_cap ? (nb4 > 0 ? nb4 : 1) : id_cap;
-            c->pass_blocks = blocks;
-        }
-        launch_pass_identity(a, c->tgt, blocks, vec4, c->stream);
-        break;
-    }
-    case SYMMICP_CORR_BRUTE:
-        launch_nn_brute(a.in, c->n_loc, a.X, c->tq, c->n_t, c->best64, c->stream);
-        launch_pass_indexed(a, c->tn, blocks, c->stream);
-        break;
-    default:
-        {
-            // the accumulate kernel is streaming with a 40-value block reduction at the end of every block: 2 blocks per
-            // CU measured best (18 us at 512 blocks, 23 us at 2048, 1M points); a multiple of 8 for the XCD remap
-            const int acc_cap = c->sw.acc_blocks;
-            const int nb_all = (int)((c->n_loc + kPassThreads - 1) / kPassThreads);
-            int ab = nb_all < acc_cap ? ((nb_all + 7) / 8) * 8 : acc_cap;
-            if (ab < 8) ab = 8;                     // (a rank whose share is empty still writes its zero record)
-            c->pass_blocks = blocks = ab;
-            // Walk grid: any size is correct (the kernel strides over the list); sized from the previous pass's list
-            // length, which only shrinks while an alignment converges.  Unknown or long lists get the full grid.
-            if (!first && c->last_list_len >= 0 && c->last_list_len <= 50000) {
-                walk_blocks = (uint32_t)(2 * c->last_list_len);
-                if (walk_blocks < 256u) walk_blocks = 256u;
-                if (walk_blocks > 8192u) walk_blocks = 8192u;
-            }
-            if (!first && c->last_list_len == -2) walk_blocks = 16384u;
-            if (c->sw.walk_full_grid) walk_blocks = 0;
-            // Once an alignment has converged the work list stays empty (every pair is certified or settled by the cell
-            // scan), and an empty walk launch still costs ~6 us of a ~50 us pass.  So after a pass with an empty list the
-            // walk is skipped; the final reduce reports the list's length, and in the rare case that it is not empty
-            // after all the pass is repaired below (walk, accumulate and reduce again).
-            optimistic = c->sw.optimistic >= 0 ? c->sw.optimistic == 1 : (!first && c->last_list_len == 0);      // (SYMMICP_OPTIMISTIC: "0" never, "1" always)
-            if (writeback) optimistic = false;      // in-place write-back: a repair would transform the cloud twice
-            if (rejecting) optimistic = false;      // the keys are taken from final pairs
-            // per-kernel events only in timing mode 2; mode 1 brackets the pass (events 0 and 4)
-            if (first && c->target_surface_like) launch_pass_tree_first(a, c->ix, c->wl, ab, c->stream, c->timing == 2 ? ev : nullptr);
-            else
-            {
-                // Sparse scans (the previous pass searched under a tenth of the pairs): the streaming kernel compacts the
-                // failures of several tiles into full scan rounds; blocks enough to fill the chip at 5 waves per SIMD
-                const int cp_blocks = c->sw.compact_blocks;
-                const bool compact = a.use_slack && (c->sw.compact >= 0 ? c->sw.compact == 1 : (c->last_uncertified >= 0 && c->last_uncertified < (long long)(c->n_s_total / 10)));
-                launch_pass_tree_split(a, c->ix, c->wl, ab, walk_blocks, optimistic ? 1 : 0, compact ? cp_blocks : 0, c->sw.tune, c->stream, c->timing == 2 ? ev : nullptr);
-            }
-            if (ev && c->timing == 2) c->ev_split[c->ev_used] = 2;
-        }
-        break;
-    }
+    hipEvent_t *ev = begin_pass_events(c, tree_pass);
+    const int blocks = ndt                                     ? launch_ndt(c, Xapply)
+                     : c->cfg.corr == SYMMICP_CORR_IDENTITY    ? launch_identity(c, a)
+                     : c->cfg.corr == SYMMICP_CORR_BRUTE       ? launch_brute(c, a)
+                                                               : launch_tree(c, a, plan, first, ev);
+    c->pass_blocks = blocks;
     if (ev && c->ev_split[c->ev_used] != 2) hipEventRecord(ev[4], c->stream);
     c->t_launch += now_s() - t_l0;
-    // Final reduce (+ all-reduce over ranks), then wait for the record.  It arrives in host-mapped memory followed by its
-    // sequence number: spin on that word instead of paying a stream-synchronise wake-up per iteration.  A stuck stream
-    // (kernel fault) is caught by the fallback.
-    auto reduce_and_wait = [&](int keep_nonempty) -> int {
-        const unsigned long long seq = ++c->seq;
-        volatile unsigned long long *flag = reinterpret_cast<volatile unsigned long long *>(c->h_sums + kNSum);
-        launch_final_reduce(c->partials, blocks, c->d_sums, c->comm ? nullptr : c->h_sums_dev, c->ticket, seq,
-                            tree_pass ? c->wl_count : nullptr, keep_nonempty, c->stream);
-        if (c->comm) {
-            if (ev) { hipEventRecord(ev[6], c->stream); c->ev_coll[c->ev_used] = 1; }
-            int r = g_rccl.AllReduce(c->d_sums, c->d_sums, kNSum, kNcclFloat64, kNcclSum, c->comm, c->stream);
-            if (r != 0) return fail(c, SYMMICP_ERR_COMM, std::string("ncclAllReduce: ") + (g_rccl.GetErrorString ? g_rccl.GetErrorString(r) : "?"));
-            if (ev) hipEventRecord(ev[7], c->stream);
-            launch_publish(c->d_sums, c->h_sums_dev, seq, c->stream);
-        }
-        // the final-reduce time is only separated out in per-kernel mode; otherwise event 5 is event 4 again
-        if (ev && c->ev_split[c->ev_used] != 1) hipEventRecord(ev[5], c->stream);
-        return wait_for_word(c, flag, seq, 30.0, "pass finished without publishing its record", &c->t_spin);
-    };
-    if (int st = reduce_and_wait(optimistic ? 1 : 0)) return st;
-    if (c->shm.slots) { if (int st = shm_exchange(c, c->h_sums)) return st; }
-    // length of the work list (summed over ranks by the exchange, so every rank takes the same decision)
-    if (tree_pass && c->h_sums[kNSum - 1] >= kListDropped)
-        return fail(c, SYMMICP_ERR_HIP, "a work-list shard overflowed: appends were dropped (internal capacity error)");
-    long long list_len = tree_pass ? (long long)c->h_sums[kNSum - 1] : -1;
-    c->last_uncertified = c->last_scans = -1;
-    if (tree_pass && !first) {
-        // (slot 38: the pairs searched + kScanUnit x those that reached a scan, k_final_reduce)
-        const double sr = c->h_sums[kNSum - 2], sc = std::floor(sr / kScanUnit);
-        c->last_uncertified = (long long)(sr - sc * kScanUnit);
-        c->last_scans = (long long)sc;
-    }
-    if (optimistic && list_len > 0) {
-        // the walk was skipped but some queries needed it: their pairs are provisional, so are the sums
-        c->st.kernel_launches[7]++;
-        launch_pass_tree_split(a, c->ix, c->wl, blocks, list_len <= 50000 ? 8192u : 0u, 2, 0, c->sw.tune, c->stream, nullptr);
-        if (ev && c->ev_split[c->ev_used] != 2) hipEventRecord(ev[4], c->stream);
-        if (int st = reduce_and_wait(0)) return st;
-        if (c->shm.slots) { if (int st = shm_exchange(c, c->h_sums)) return st; }
-    }
-    if (rejecting) {
+    const bool optimistic = tree_pass && plan.optimistic;
+    if (int st = reduce_and_wait(c, blocks, tree_pass, ev, optimistic ? 1 : 0)) return st;
+    uint64_t list_len = 0;
+    if (tree_pass) { if (int st = absorb_tree_feedback(c, a, blocks, first, optimistic, ev, &list_len)) return st; }
+    else { c->fb.forget_counts(); c->fb.forget_list(); }
+    if (pass_rejects(a)) {
         std::memcpy(&c->rej.last, c->h_sums + kNSum + 1, sizeof(RejectRecord));      // (written before the record: same stream)
         c->rej.ran = c->rej.settings_mask(c->cfg.corr);
     }
     if (ev) c->ev_used++;
     c->t_last_done = now_s(); c->n_pass_timed++;
     if (c->dbg_trace && first) dump_packet_trace(c);
-    if (c->ix.dbg) print_pass_counters(c, first, list_len);
+    if (c->ix.dbg) print_pass_counters(c, first, tree_pass ? (long long)list_len : -1);
     std::memcpy(c->last.s, c->h_sums, sizeof(double) * kNSum);
-    if (tree_pass) c->last.s[kNSum - 1] = c->last.s[kNSum - 2] = 0.0;      // those slots carried the list length and the number of searched pairs, not sums
-    c->last_list_len = list_len;
-    // the packet first pass has no work list; the pass after it (the cloud has just moved by its whole misalignment) always has one:
-    // -2 = "expect a list" (no optimistic skip of the walk, which would only be repaired; a mid-sized walk grid)
-    if (first && tree_pass && c->target_surface_like) c->last_list_len = -2;
+    if (tree_pass) c->last.s[kFeedbackListSlot] = c->last.s[kFeedbackCountSlot] = 0.0;      // those slots carried the feedback, not sums
     if (ndt) {
         c->ndt.score = -c->ndt.d1 * c->last.s[34];
         c->ndt.items = (uint64_t)c->last.s[37];
@@ -289,274 +290,275 @@ static int run_pass(symmicp_ctx *c, const float Xapply[16], bool from_cur, bool 
 // transform from device memory, and the loop test of myicp.cpp:123 sets a stop flag every later kernel of the batch
 // honours.  The host solve stays the reference: anything but a clean, well-conditioned solve, and any pass that needs
 // the tree walk, stops the batch and the host loop takes that iteration (LOOP_HOST_SOLVE / LOOP_REDO_PASS).
-// work lists up to this length are walked inside a device-driven loop (straggler stage); longer ones go back to the host, which sizes the walk
-static constexpr uint32_t kLoopListLimit = 8192;
-// Scans are what the fused pass is slow at (two waves per SIMD: a dense cell's dependent loads are not hidden; ~6 ns per scanned pair
-// against 0.3 in k_search_cells), so a run starts once the last pass searched under 0.4 % of the pairs and under 8192 of them -- the
-// separate kernels win above that whatever the cloud's size (8M scan pair: 328 us fused against 150 + 80 at 30 k scans) -- and is left
-// (LOOP_SLOW) at four times as many.
-static uint32_t loop_scan_limit(uint32_t n) { const uint32_t f = n / 256; return f < 8192u ? f : 8192u; }
-static bool batch_eligible(const symmicp_ctx *c)
+// When a run may start, how it is cut into chunks and which kernel runs a chunk: batch_eligible and ChunkPlanner, loop_plan.h.
+static bool may_start_batch(const symmicp_ctx *c)
 {
-    if (c->sw.host_loop) return false;                                    // SYMMICP_HOST_LOOP=1: never batch (A/B runs, tests)
-    if (pass_rejects(c)) return false;                                    // trimmed and other rejecting passes: the fused pass and the device loop have no select
-    if (c->cfg.mode == SYMMICP_MODE_COLOR) return false;                  // colored ICP: the fused pass and the straggler stage have no COLOR form
-    if (c->cfg.host_loop) return false;
-    if (c->external_exchange || c->shm.slots) return false;               // those exchanges run on the host
-    if (c->timing == 2 || c->ix.dbg) return false;                        // per-kernel tables and debug counters: host loop
-    if (!mode_device_solves(c->cfg.mode)) return false;                   // (P2P: 3x3 SVD by Jacobi sweeps: host)
-    if (c->n_loc == 0 && !c->comm) return false;                          // (an empty share of an RCCL run takes part: every input below is global,
-                                                                          // and a rank that stayed in the host loop would issue a different number of all-reduces)
-    if (c->host_passes_since_bailout < 2) return false;
+    BatchEligibleIn in{};
+    in.host_loop_switch = c->sw.host_loop;
+    in.rejecting = pass_rejects(c);
+    in.color = c->cfg.mode == SYMMICP_MODE_COLOR;
+    in.host_loop_config = c->cfg.host_loop != 0;
+    in.host_exchange = c->external_exchange || c->shm.slots;
+    in.host_diagnostics = c->timing == 2 || c->ix.dbg;
+    in.device_solves = mode_device_solves(c->cfg.mode);
+    in.empty_share_alone = c->n_loc == 0 && !c->comm;
+    in.host_passes_since_bailout = c->host_passes_since_bailout;
+    in.identity = c->cfg.corr == SYMMICP_CORR_IDENTITY;
+    in.tree = c->cfg.corr == SYMMICP_CORR_TREE;
+    in.incremental = resolved_apply(c->cfg) == SYMMICP_APPLY_INCREMENTAL;
+    in.certificates = c->cert && !c->sw.no_cert;
+    in.no_loop_stragglers = c->sw.no_loop_stragglers;
+    in.n_s_total = c->n_s_total;
+    in.fb = c->fb;
+    return batch_eligible(in);
+}
+
+static constexpr int kListBlocks = 8;      // partial columns of the straggler stage
+static constexpr int kEvSampleStride = 4;  // timing mode 3: passes of a device-driven run that carry events
+
+// A device-driven run: what its chunks share
+struct BatchRun {
+    LoopConfig lc;
+    PassArgs a;
+    ChunkPlanner planner;
+    bool tree, vec4;
+    bool timed;                      // timing modes 1 and 3: passes carry events, every ev_stride-th of the run
+    int ev_stride;
+    int want, it0;                   // passes asked for; c->iters at entry
+    int blocks_full;                 // partial columns of a pass without the straggler stage
+    uint32_t *counters;              // the work list's counters (TREE)
+    int enq, n_stage;                // passes enqueued so far; passes that ran with the straggler stage
+    uint8_t pass_kernel[symmicp_ctx::kRing];      // by iteration % kRing: 1 = the certified-only kernel ran (or was to run) that pass
+    symmicp_sums last0;              // loop log: the record the solve-only launch solves from
+    PassFeedback fb0;                // the feedback of the host pass in front of the run
+};
+// ... and one chunk of it
+struct Chunk {
+    int nq, it_before, ev_used0;     // passes; c->iters and c->ev_used in front of it
+    bool certified, stage;           // the certified-only kernel runs its passes; they carry the straggler stage
+    int fused_blocks, blocks;        // grid of the pass kernel; partial columns in all
+};
+
+static LoopConfig make_loop_config(const symmicp_ctx *c, int want)
+{
+    LoopConfig lc{};
+    lc.mode = c->cfg.mode; lc.fixed_iters = c->cfg.fixed_iters; lc.max_iters = c->iters + want;
+    lc.incremental = resolved_apply(c->cfg) == SYMMICP_APPLY_INCREMENTAL ? 1 : 0; lc.tree = c->cfg.corr == SYMMICP_CORR_TREE ? 1 : 0;
+    lc.diff_threshold = c->cfg.diff_threshold; lc.eps_rotation = c->cfg.eps_rotation; lc.eps_translation = c->cfg.eps_translation;
+    lc.nrm_w = (c->cfg.mode == SYMMICP_MODE_QUIRKS) ? 1.0f : 0.0f;
+    for (int k = 0; k < 3; k++) lc.pivot[k] = c->pivot[k];
+    lc.uncertified_limit = loop_slow_limit(c->n_s_total);
+    lc.list_limit = kLoopListLimit;
+    if (lc.max_iters > c->cfg.max_iters) lc.max_iters = c->cfg.max_iters;
+    return lc;
+}
+
+// The run's constants, the loop state as the host loop left it (in device memory), the pass arguments and the grid
+static int begin_batch(symmicp_ctx *c, BatchRun &run, int want)
+{
     const bool incr = resolved_apply(c->cfg) == SYMMICP_APPLY_INCREMENTAL;
-    if (c->cfg.corr == SYMMICP_CORR_IDENTITY) return true;
-    // TREE: the fused pass is for converged alignments: under 0.4 % of the pairs searched again, a short work list at most (stragglers
-    // outside the overlap: real scans always have some)
-    if (c->cfg.corr == SYMMICP_CORR_TREE)
-        return !incr && c->last_list_len >= 0 && c->last_list_len <= (c->sw.no_loop_stragglers ? 0ll : (long long)kLoopListLimit) && c->last_uncertified >= 0 &&
-               c->last_uncertified <= (long long)(loop_scan_limit(c->n_s_total) / (c->last_list_len > 0 ? 2 : 1)) && c->cert && !c->sw.no_cert;      // (the straggler stage costs two launches per pass)
-    return false;
+    run.tree = c->cfg.corr == SYMMICP_CORR_TREE;
+    run.want = want; run.it0 = c->iters; run.fb0 = c->fb;
+    run.lc = make_loop_config(c, want);
+    const int cert_mode = (run.tree && c->cert && !c->sw.no_cert && !c->cert_pass_failed) ? c->sw.cert_pass : 0;
+    const bool one_piece = run.lc.fixed_iters && !(run.lc.eps_rotation > 0.f && run.lc.eps_translation > 0.f);
+    run.planner = ChunkPlanner(run.tree && !c->sw.no_loop_stragglers, c->fb.has_list(), cert_mode, one_piece, c->sw.cert_head);
+    LoopState ls{};
+    std::memcpy(ls.X, c->X, sizeof(ls.X));
+    for (int k = 0; k < 12; k++) ls.Xapply.m[k] = c->X[k];
+    ls.Xapply.nrm_w = run.lc.nrm_w;
+    ls.iters = run.it0;
+    *c->h_loop = ls;
+    if (c->loop_log_on) {
+        run.last0 = c->last;
+        ring_at(c, run.it0).solved = 0;                                        // (the solve-only launch writes its entry only when it solves)
+    }
+    HIP_TRY(c, hipMemcpyAsync(c->d_loop, c->h_loop, sizeof(LoopState), hipMemcpyHostToDevice, c->stream));
+    fill_pass_args(c, run.a, RejectArgs{}, plan_pass(c, /*first=*/false, /*writeback=*/incr), c->X, /*from_cur=*/incr, /*writeback=*/incr, /*first=*/false);      // (batch_eligible: no rejector)
+    run.a.loop = c->d_loop;
+    if (run.tree) run.blocks_full = fused_pass_blocks(c->n_loc, c->sw.fused_blocks);
+    else {
+        const IdentityGrid g = identity_grid(c->n_loc, c->n_t, c->src_off, c->sw.id_blocks);
+        run.blocks_full = g.blocks; run.vec4 = g.vec4;
+    }
+    c->pass_blocks = run.blocks_full;
+    run.counters = run.tree ? c->wl_count : nullptr;
+    run.timed = c->timing == 1 || c->timing == 3;
+    run.ev_stride = c->timing == 3 ? kEvSampleStride : 1;      // mode 3: every 4th pass of the run
+    if (run.timed && c->ev_used + want > symmicp_ctx::kEvRing) flush_events(c);
+    return SYMMICP_OK;
+}
+
+// The chunk `plan` asks for: its variant of the pass (partial columns, what a non-empty list means to the solve)
+static Chunk begin_chunk(symmicp_ctx *c, BatchRun &run, const ChunkPlan &plan)
+{
+    Chunk ch{};
+    ch.nq = (run.want - run.enq < plan.passes) ? run.want - run.enq : plan.passes;
+    ch.it_before = c->h_loop->iters;
+    ch.ev_used0 = c->ev_used;
+    ch.certified = plan.certified;
+    ch.stage = run.planner.stragglers();
+    // (with the stage: 512 partial columns in all, k_reduce_solve's fast path)
+    ch.fused_blocks = (ch.stage && run.blocks_full + kListBlocks > 512) ? 512 - kListBlocks : run.blocks_full;
+    ch.blocks = ch.fused_blocks + (ch.stage ? kListBlocks : 0);
+    run.a.partial_cols = ch.stage ? (uint32_t)ch.blocks : 0u;
+    run.a.partial_col0 = (uint32_t)ch.fused_blocks;
+    run.lc.walk_in_loop = ch.stage ? 1 : 0;
+    return ch;
+}
+
+// Pass p of the chunk: (pass, reduce, [all-reduce,] solve)
+static int enqueue_pass(symmicp_ctx *c, BatchRun &run, const Chunk &ch, int p)
+{
+    hipEvent_t *ev = nullptr;
+    if (run.timed && (run.enq + p) % run.ev_stride == 0 && c->ev_used < symmicp_ctx::kEvRing) {
+        ev = c->ev + c->ev_used * symmicp_ctx::kEvPer;
+        c->ev_split[c->ev_used] = 1;
+        c->ev_weight[c->ev_used] = 1;
+        hipEventRecord(ev[0], c->stream);
+    }
+    if (run.tree) {
+        run.pass_kernel[ring_slot(ch.it_before + 1 + p)] = ch.certified ? 1 : 0;      // (the pass this launch is when no stop comes before it)
+        if (ch.certified) launch_pass_certified(run.a, c->ix, c->wl, ch.fused_blocks, c->stream);
+        else launch_pass_fused(run.a, c->ix, c->wl, ch.fused_blocks, c->stream);
+        if (ch.stage) launch_loop_stragglers(run.a, c->ix, c->wl, kListBlocks, c->sw.tune, c->stream);
+    }
+    else launch_pass_identity(run.a, c->tgt, ch.blocks, run.vec4, c->stream);
+    if (ev) { hipEventRecord(ev[4], c->stream); c->ev_used++; }
+    if (!(c->comm || ch.blocks > 512)) {
+        launch_reduce_solve(c->partials, ch.blocks, c->d_sums, 0, c->d_loop, run.lc, c->h_ring_dev, symmicp_ctx::kRing, run.counters, c->stream);
+        return SYMMICP_OK;
+    }
+    // sharded: the record is summed over the ranks before the solve; many partial records (an 8M-point identity pass): the 40-block
+    // reduce is faster than one block's
+    launch_final_reduce(c->partials, ch.blocks, c->d_sums, nullptr, c->ticket, 0ull, run.counters, 0, c->stream);
+    if (c->comm) {
+        if (ev) { hipEventRecord(ev[6], c->stream); c->ev_coll[c->ev_used - 1] = 1; }
+        if (int st = allreduce_record(c)) {
+            // passes are already queued behind this point and (incremental mode) write into `cur`: drain the stream and make the
+            // context ask for a fresh symmicp_begin -- its loop state no longer describes device memory
+            (void)hipStreamSynchronize(c->stream);
+            c->begun = false;
+            c->ev_used = 0;
+            return st;
+        }
+        if (ev) hipEventRecord(ev[7], c->stream);
+    }
+    launch_reduce_solve(c->partials, ch.blocks, c->d_sums, 1, c->d_loop, run.lc, c->h_ring_dev, symmicp_ctx::kRing, run.counters, c->stream);
+    return SYMMICP_OK;
+}
+
+// The end of a chunk: the loop state comes back, the events of launches that did nothing go
+static int close_chunk(symmicp_ctx *c, BatchRun &run, const Chunk &ch)
+{
+    const unsigned long long seq = ++c->batch_seq;
+    launch_loop_end(c->d_loop, c->h_loop_dev, c->h_done_dev, seq, c->stream);
+    if (int st = wait_for_word(c, c->h_done, seq, 60.0, "batch finished without publishing its end flag")) return st;
+    // passes of this chunk that did run (a pass that has to be redone ran too); the events of the no-op launches behind a stop are dropped
+    const int ran = (c->h_loop->iters - ch.it_before) + (c->h_loop->reason == LOOP_REDO_PASS ? 1 : 0);
+    if (run.timed && ran >= 0) {
+        int sampled_ran = 0;                      // event pairs of the passes that ran; each stands for the passes up to the next pair
+        for (int p = 0; p < ran && p < ch.nq; p++) {
+            if ((run.enq + p) % run.ev_stride != 0) continue;
+            if (ch.ev_used0 + sampled_ran < symmicp_ctx::kEvRing) {
+                const int left = (ran < ch.nq ? ran : ch.nq) - p;
+                c->ev_weight[ch.ev_used0 + sampled_ran] = left < run.ev_stride ? left : run.ev_stride;
+            }
+            sampled_ran++;
+        }
+        if (ch.ev_used0 + sampled_ran < c->ev_used) c->ev_used = ch.ev_used0 + sampled_ran;
+    }
+    run.enq += ch.nq;
+    if (ch.stage) run.n_stage += c->h_loop->iters - ch.it_before;
+    return SYMMICP_OK;
+}
+
+// The ring into the context: on return c->iters, c->X, c->last and c->fb describe the last complete pass
+static int finish_batch(symmicp_ctx *c, const BatchRun &run, float *diffs_before, int *n_done, bool *small_step)
+{
+    const LoopState &hl = *c->h_loop;
+    const int it0 = run.it0, it1 = hl.iters;          // passes complete
+    if (it1 < it0 || it1 > it0 + run.want) return fail(c, SYMMICP_ERR_HIP, "device loop state out of range");
+    // the diffs the reference prints before iterations it0+1 .. it1 (+1 when the loop went on into a pass that was not completed)
+    for (int k = it0; k < it1; k++) diffs_before[k - it0] = (k == it0) ? (float)c->last.s[33] : (float)ring_at(c, k).sums[33];
+    if (it1 > it0) {
+        const LoopRecord &r = ring_at(c, it1);
+        std::memcpy(c->last.s, r.sums, sizeof(double) * kNSum);
+        std::memcpy(c->X, ring_at(c, it1 - 1).X, sizeof(float) * 16);      // transform the last complete pass applied
+        c->st.passes += it1 - it0;
+        c->st.loop_passes += it1 - it0;
+        c->st.loop_straggler_passes += run.n_stage;
+        if (run.tree) { c->fb.set_list_from_record(r.list_len); c->fb.set_counts_from_record(r.searched, r.scans); }
+    }
+    if (!run.tree) c->fb.forget_list();
+    c->iters = it1;
+    *n_done = it1 - it0;
+    *small_step = hl.reason == LOOP_DONE && hl.small_step != 0;
+    const bool redo = hl.reason == LOOP_REDO_PASS;
+    if (redo && run.pass_kernel[ring_slot(it1 + 1)]) c->cert_pass_failed = true;
+    if (c->sw.debug_host) print_batch_summary(c, it0, it1, run.want, run.enq, run.n_stage, run.pass_kernel, run.fb0);
+    if (hl.reason == LOOP_SLOW) c->host_passes_since_bailout = 1;      // one host pass, then look again
+    if (redo || hl.reason == LOOP_HOST_SOLVE) {
+        c->host_passes_since_bailout = 0;
+        c->fb.forget_list();                          // the host's next pass runs the full search
+        c->st.kernel_launches[7]++;                   // counted with the repairs
+    }
+    return SYMMICP_OK;
+}
+
+// the batch's passes: it0 (the host's last pass, whose record the solve-only launch solved from) .. the last complete one
+static void append_loop_log(symmicp_ctx *c, const BatchRun &run)
+{
+    const LoopState &hl = *c->h_loop;
+    const int it0 = run.it0, it1 = hl.iters;
+    for (int k = it0; k <= it1; k++) {
+        const LoopRecord &r = ring_at(c, k);
+        symmicp_loop_log_entry e{};
+        std::memcpy(e.sums, k == it0 ? run.last0.s : r.sums, sizeof(e.sums));
+        std::memcpy(e.increment, r.increment, sizeof(e.increment));
+        std::memcpy(e.X, r.X, sizeof(e.X));
+        e.rcond = r.rcond; e.iter = k; e.status = r.status; e.solved = r.solved; e.list_len = k == it0 ? 0 : r.list_len;
+        e.reason = hl.reason; e.batch = c->loop_log_batches;
+        // which kernel ran the pass (0: k_pass_fused or the host, 1: k_pass_certified); + 0x100 on the batch's last entry when the pass
+        // behind it ran certified-only and was handed back incomplete
+        e.reserved = k == it0 ? 0 : run.pass_kernel[ring_slot(k)];
+        if (k == it1 && hl.reason == LOOP_REDO_PASS && run.pass_kernel[ring_slot(it1 + 1)]) e.reserved |= 0x100;
+        if (!e.solved) { std::memset(e.increment, 0, sizeof(e.increment)); std::memset(e.X, 0, sizeof(e.X)); e.rcond = 0.f; e.status = -1; }
+        c->loop_log.push_back(e);
+    }
+    c->loop_log_batches++;
 }
 
 // Runs up to `want` iterations on the device.  On return c->iters, c->X and c->last describe the last COMPLETE pass, exactly as
 // if symmicp_step had been called (c->iters - iters_before) times; diffs_before[k] = the diff the reference prints before
 // iteration iters_before + 1 + k.  *small_step: the increment rule ended the alignment.
-static constexpr int kListBlocks = 8;      // partial columns of the straggler stage
-static constexpr int kEvSampleStride = 4;  // timing mode 3: passes of a device-driven run that carry events
 static int run_batch(symmicp_ctx *c, int want, float *diffs_before, int *n_done, bool *small_step)
 {
     *n_done = 0;
     *small_step = false;
     if (want > symmicp_ctx::kRing - 1) want = symmicp_ctx::kRing - 1;
     if (want <= 0) return SYMMICP_OK;
-    const bool incr = resolved_apply(c->cfg) == SYMMICP_APPLY_INCREMENTAL;
-    const bool tree = c->cfg.corr == SYMMICP_CORR_TREE;
-    LoopConfig lc{};
-    lc.mode = c->cfg.mode; lc.fixed_iters = c->cfg.fixed_iters; lc.max_iters = c->iters + want; lc.incremental = incr ? 1 : 0; lc.tree = tree ? 1 : 0;
-    lc.diff_threshold = c->cfg.diff_threshold; lc.eps_rotation = c->cfg.eps_rotation; lc.eps_translation = c->cfg.eps_translation;
-    lc.nrm_w = (c->cfg.mode == SYMMICP_MODE_QUIRKS) ? 1.0f : 0.0f;
-    for (int k = 0; k < 3; k++) lc.pivot[k] = c->pivot[k];
-    lc.uncertified_limit = 4 * loop_scan_limit(c->n_s_total);
-    // stragglers: while passes leave a work list, every fused pass is followed by the walk over the list and the accumulation of its
-    // pairs (two more launches per pass, ~10 us); decided per chunk of passes from the lists the previous chunk left.  Without the stage
-    // a list that turns up stops the loop: the host redoes that pass and the next batch starts with the stage.
-    const bool no_stage = c->sw.no_loop_stragglers;      // A/B runs
-    bool stragglers = tree && c->last_list_len > 0 && !no_stage;
-    lc.list_limit = kLoopListLimit;
-    // The certified-only pass (k_pass_certified) runs a chunk when the last complete pass left no work list and sent no pair to a scan
-    // (and the chunk carries no straggler stage); a pass of it that comes back incomplete is redone by the host like any pass with an
-    // unexpected list, and the kernel is then left alone for the rest of the alignment: one repeated pass at most.
-    // SYMMICP_CERT_PASS: 0 never, 2 from the first device pass whatever the counts say (tests of the redo path, A/B runs).
-    const int cert_mode = (tree && c->cert && !c->sw.no_cert && !c->cert_pass_failed) ? c->sw.cert_pass : 0;
-    if (cert_mode == 2) stragglers = false;
-    bool cert_chunk = false;                           // this chunk's pass kernel (plan_chunk below)
-    uint8_t pass_kernel[symmicp_ctx::kRing] = {};      // by iteration % kRing: 1 = the certified-only kernel ran (or was to run) that pass
-    if (lc.max_iters > c->cfg.max_iters) lc.max_iters = c->cfg.max_iters;
-    const int it0 = c->iters;
-    const long long list0 = c->last_list_len, scans0 = c->last_scans;
-    // loop state as the host loop left it
-    LoopState ls{};
-    std::memcpy(ls.X, c->X, sizeof(ls.X));
-    for (int k = 0; k < 12; k++) ls.Xapply.m[k] = c->X[k];
-    ls.Xapply.nrm_w = lc.nrm_w;
-    ls.iters = it0;
-    *c->h_loop = ls;
-    symmicp_sums last0{};
-    if (c->loop_log_on) {
-        last0 = c->last;                                                        // the record the solve-only launch solves from
-        c->h_ring[it0 % symmicp_ctx::kRing].solved = 0;                         // (it writes its entry only when it solves)
-    }
-    HIP_TRY(c, hipMemcpyAsync(c->d_loop, c->h_loop, sizeof(LoopState), hipMemcpyHostToDevice, c->stream));
-    PassArgs a{};
-    fill_pass_args(c, a, RejectArgs{}, c->X, /*from_cur=*/incr, /*writeback=*/incr, /*first=*/false);      // (batch_eligible: no rejector)
-    a.loop = c->d_loop;
-    int blocks;
-    bool vec4 = false;
-    if (tree) {
-        const int fb = c->sw.fused_blocks;
-        const int tiles = (int)((c->n_loc + kPassThreads - 1) / kPassThreads);
-        blocks = tiles < fb ? tiles : fb;
-        if (blocks < 1) blocks = 1;             // (an empty share still writes its zero record)
-    } else {
-        vec4 = (c->n_loc % 4 == 0) && (c->n_t % 4 == 0) && (c->src_off % 4 == 0);
-        const int id_cap = c->sw.id_blocks;
-        const int nb = (int)(((vec4 ? c->n_loc / 4 : c->n_loc) + kPassThreads - 1) / kPassThreads);
-        blocks = nb < id_cap ? (nb > 0 ? nb : 1) : id_cap;
-    }
-    const int fused_blocks_full = blocks;
-    c->pass_blocks = blocks;
-    uint32_t *counters = tree ? c->wl_count : nullptr;
-    // The record of the last complete pass is in d_sums: solve from it, then (pass, reduce, [all-reduce,] solve) per iteration.
-    // Passes are enqueued in chunks of 4, 8, 16, ... with one look at the loop state between chunks: a loop that stops early
-    // (convergence, a pass that has to be redone) leaves at most one chunk of no-op launches behind.
-    const bool timed_run = c->timing == 1 || c->timing == 3;
-    const int ev_stride = c->timing == 3 ? kEvSampleStride : 1;      // mode 3: every 4th pass of the run
-    if (timed_run && c->ev_used + want > symmicp_ctx::kEvRing) flush_events(c);
-    // (a run that only a bail-out can stop -- fixed iteration count, no increment criterion, no work list at entry -- is enqueued in one
-    // piece: every chunk boundary is a host look at the loop state, ~12 us of idle GPU)
-    const bool one_piece = lc.fixed_iters && !(lc.eps_rotation > 0.f && lc.eps_translation > 0.f);
-    int enq = 0, n_stage = 0;
-    // ... but its head goes out in short chunks of fused passes while the last complete pass still scanned: a run starts while a few
-    // hundred pairs are still settling and single scans trickle on for some passes (1M surface pair, scans per device pass: 159 113 1 8
-    // 3 1 0 0 ...), so one short head would see a scan and leave the whole run to the fused kernel.  kCertHeads chunks at most; the rest
-    // goes out in one piece with the kernel the last head's last pass allows.  (A boundary is paid back by two certified-only passes.)
-    constexpr int kCertHeads = 3;
-    int heads_left = (one_piece && !stragglers && cert_mode == 1 && c->sw.cert_head > 0) ? kCertHeads : 0;
-    // The plan of the next chunk, from the last complete pass (its work list and scan count; `left` passes to go, `prev` passes in the
-    // chunk before, 0: none): which kernel runs it (cert_chunk) and how many passes it holds.  All of the chunking is here: with the
-    // straggler stage on, chunks stay at 4 (the stage can only be dropped between chunks); a run that can stop by itself doubles them;
-    // a run that only a bail-out can stop sends fused heads while passes still scan and then the rest in one piece.
-    auto plan_chunk = [&](long long list_len, long long scans, int left, int prev) -> int {
-        cert_chunk = cert_mode == 2 || (cert_mode == 1 && !stragglers && list_len == 0 && scans == 0);
-        if (stragglers) return 4;
-        if (!one_piece) return prev ? 2 * prev : 4;
-        if (!cert_chunk && heads_left > 0 && left > c->sw.cert_head) { heads_left--; return c->sw.cert_head; }
-        return left;
-    };
-    int chunk = plan_chunk(c->last_list_len, c->last_scans, want, 0);
-    bool first_chunk = true;
-    while (enq < want) {
-        const int nq = (want - enq < chunk) ? want - enq : chunk;
-        const int it_before = first_chunk ? it0 : c->h_loop->iters;
-        const int ev_used0 = c->ev_used;
-        // this chunk's variant: partial columns, what a non-empty list means to the solve
-        // (with the stage: 512 partial columns in all, k_reduce_solve's fast path)
-        const int fused_blocks = (stragglers && fused_blocks_full + kListBlocks > 512) ? 512 - kListBlocks : fused_blocks_full;
-        blocks = fused_blocks + (stragglers ? kListBlocks : 0);
-        a.partial_cols = stragglers ? (uint32_t)blocks : 0u;
-        a.partial_col0 = (uint32_t)fused_blocks;
-        lc.walk_in_loop = stragglers ? 1 : 0;
-        if (first_chunk) launch_reduce_solve(c->partials, blocks, c->d_sums, 2, c->d_loop, lc, c->h_ring_dev, symmicp_ctx::kRing, counters, c->stream);
-        for (int p = 0; p < nq; p++) {
-            hipEvent_t *ev = nullptr;
-            if (timed_run && (enq + p) % ev_stride == 0 && c->ev_used < symmicp_ctx::kEvRing) {
-                ev = c->ev + c->ev_used * symmicp_ctx::kEvPer;
-                c->ev_split[c->ev_used] = 1;
-                c->ev_weight[c->ev_used] = 1;
-                hipEventRecord(ev[0], c->stream);
-            }
-            if (tree) {
-                pass_kernel[(it_before + 1 + p) % symmicp_ctx::kRing] = cert_chunk ? 1 : 0;      // (the pass this launch is when no stop comes before it)
-                if (cert_chunk) launch_pass_certified(a, c->ix, c->wl, fused_blocks, c->stream);
-                else launch_pass_fused(a, c->ix, c->wl, fused_blocks, c->stream);
-                if (stragglers) launch_loop_stragglers(a, c->ix, c->wl, kListBlocks, c->sw.tune, c->stream);
-            }
-            else launch_pass_identity(a, c->tgt, blocks, vec4, c->stream);
-            if (ev) { hipEventRecord(ev[4], c->stream); c->ev_used++; }
-            if (c->comm || blocks > 512) {
-                // sharded: the record is summed over the ranks before the solve; many partial records (an 8M-point identity pass):
-                // the 40-block reduce is faster than one block's
-                launch_final_reduce(c->partials, blocks, c->d_sums, nullptr, c->ticket, 0ull, counters, 0, c->stream);
-                if (c->comm) {
-                    if (ev) { hipEventRecord(ev[6], c->stream); c->ev_coll[c->ev_used - 1] = 1; }
-                    int r = g_rccl.AllReduce(c->d_sums, c->d_sums, kNSum, kNcclFloat64, kNcclSum, c->comm, c->stream);
-                    if (r != 0) {
-                        // passes are already queued behind this point and (incremental mode) write into `cur`: drain the stream and make the
-                        // context ask for a fresh symmicp_begin -- its loop state no longer describes device memory
-                        (void)hipStreamSynchronize(c->stream);
-                        c->begun = false;
-                        c->ev_used = 0;
-                        return fail(c, SYMMICP_ERR_COMM, std::string("ncclAllReduce: ") + (g_rccl.GetErrorString ? g_rccl.GetErrorString(r) : "?"));
-                    }
-                    if (ev) hipEventRecord(ev[7], c->stream);
-                }
-                launch_reduce_solve(c->partials, blocks, c->d_sums, 1, c->d_loop, lc, c->h_ring_dev, symmicp_ctx::kRing, counters, c->stream);
-            } else {
-                launch_reduce_solve(c->partials, blocks, c->d_sums, 0, c->d_loop, lc, c->h_ring_dev, symmicp_ctx::kRing, counters, c->stream);
-            }
-        }
-        const unsigned long long seq = ++c->batch_seq;
-        launch_loop_end(c->d_loop, c->h_loop_dev, c->h_done_dev, seq, c->stream);
-        if (int st = wait_for_word(c, c->h_done, seq, 60.0, "batch finished without publishing its end flag")) return st;
-        enq += nq;
-        first_chunk = false;
-        // passes of this chunk that did run (a pass that has to be redone ran too); the events of the no-op launches behind a
-        // stop are dropped
-        const int ran = (c->h_loop->iters - it_before) + (c->h_loop->reason == LOOP_REDO_PASS ? 1 : 0);
-        if (timed_run && ran >= 0) {
-            int sampled_ran = 0;                      // event pairs of the passes that ran; each stands for the passes up to the next pair
-            for (int p = 0; p < ran && p < nq; p++) {
-                if ((enq - nq + p) % ev_stride != 0) continue;
-                if (ev_used0 + sampled_ran < symmicp_ctx::kEvRing) {
-                    const int left = (ran < nq ? ran : nq) - p;
-                    c->ev_weight[ev_used0 + sampled_ran] = left < ev_stride ? left : ev_stride;
-                }
-                sampled_ran++;
-            }
-            if (ev_used0 + sampled_ran < c->ev_used) c->ev_used = ev_used0 + sampled_ran;
-        }
-        if (stragglers) n_stage += c->h_loop->iters - it_before;
+    BatchRun run{};
+    if (int st = begin_batch(c, run, want)) return st;
+    ChunkPlan plan = run.planner.next(c->fb.list_len, c->fb.scans, want, 0);
+    while (run.enq < want) {
+        const Chunk ch = begin_chunk(c, run, plan);
+        // the record of the last complete pass is in d_sums: solve from it first
+        if (run.enq == 0) launch_reduce_solve(c->partials, ch.blocks, c->d_sums, 2, c->d_loop, run.lc, c->h_ring_dev, symmicp_ctx::kRing, run.counters, c->stream);
+        for (int p = 0; p < ch.nq; p++)
+            if (int st = enqueue_pass(c, run, ch, p)) return st;
+        if (int st = close_chunk(c, run, ch)) return st;
         if (c->h_loop->stop) break;
-        if (tree && !no_stage) {
-            // the stage stays (or comes) on while any pass of this chunk left a list
-            stragglers = false;
-            for (int k = it_before + 1; k <= c->h_loop->iters; k++) stragglers = stragglers || c->h_ring[k % symmicp_ctx::kRing].list_len > 0;
+        if (run.tree) {
+            bool any_list = false;
+            for (int k = ch.it_before + 1; k <= c->h_loop->iters; k++) any_list = any_list || ring_at(c, k).list_len > 0;
+            run.planner.after_chunk(any_list);
         }
-        // with the stage on, chunks stay short: the stage (two more launches per pass) can only be dropped between chunks, and lists die out
-        // within a few passes of a run's start (8M scan pair: 8 8 6 2 | 2 0 1 0 | 0 ...); once it is off and only a bail-out can stop the run,
-        // the rest goes out in one piece
-        if (cert_mode == 2) stragglers = false;
-        const LoopRecord &lr = c->h_ring[c->h_loop->iters % symmicp_ctx::kRing];      // the last complete pass (this chunk completed one: no stop)
-        chunk = plan_chunk(lr.list_len, lr.reserved, want - enq, chunk);
+        const LoopRecord &lr = ring_at(c, c->h_loop->iters);      // the last complete pass (this chunk completed one: no stop)
+        plan = run.planner.next((uint64_t)lr.list_len, (uint64_t)lr.scans, want - run.enq, plan.passes);
     }
-    const LoopState &hl = *c->h_loop;
-    const int it1 = hl.iters;                         // passes complete
-    if (it1 < it0 || it1 > it0 + want) return fail(c, SYMMICP_ERR_HIP, "device loop state out of range");
-    // the diffs the reference prints before iterations it0+1 .. it1 (+1 when the loop went on into a pass that was not completed)
-    for (int k = it0; k < it1; k++) diffs_before[k - it0] = (k == it0) ? (float)c->last.s[33] : (float)c->h_ring[k % symmicp_ctx::kRing].sums[33];
-    if (it1 > it0) {
-        std::memcpy(c->last.s, c->h_ring[it1 % symmicp_ctx::kRing].sums, sizeof(double) * kNSum);
-        std::memcpy(c->X, c->h_ring[(it1 - 1) % symmicp_ctx::kRing].X, sizeof(float) * 16);      // transform the last complete pass applied
-        c->st.passes += it1 - it0;
-        c->st.loop_passes += it1 - it0;
-        c->st.loop_straggler_passes += n_stage;
-    }
-    if (c->loop_log_on) {
-        // the batch's passes: it0 (the host's last pass, whose record the solve-only launch solved from) .. it1
-        for (int k = it0; k <= it1; k++) {
-            const LoopRecord &r = c->h_ring[k % symmicp_ctx::kRing];
-            symmicp_loop_log_entry e{};
-            std::memcpy(e.sums, k == it0 ? last0.s : r.sums, sizeof(e.sums));
-            std::memcpy(e.increment, r.increment, sizeof(e.increment));
-            std::memcpy(e.X, r.X, sizeof(e.X));
-            e.rcond = r.rcond; e.iter = k; e.status = r.status; e.solved = r.solved; e.list_len = k == it0 ? 0 : r.list_len;
-            e.reason = hl.reason; e.batch = c->loop_log_batches;
-            // which kernel ran the pass (0: k_pass_fused or the host, 1: k_pass_certified); + 0x100 on the batch's last entry when the pass
-            // behind it ran certified-only and was handed back incomplete
-            e.reserved = k == it0 ? 0 : pass_kernel[k % symmicp_ctx::kRing];
-            if (k == it1 && hl.reason == LOOP_REDO_PASS && pass_kernel[(it1 + 1) % symmicp_ctx::kRing]) e.reserved |= 0x100;
-            if (!e.solved) { std::memset(e.increment, 0, sizeof(e.increment)); std::memset(e.X, 0, sizeof(e.X)); e.rcond = 0.f; e.status = -1; }
-            c->loop_log.push_back(e);
-        }
-        c->loop_log_batches++;
-    }
-    c->iters = it1;
-    c->last_list_len = tree ? (it1 > it0 ? (long long)c->h_ring[it1 % symmicp_ctx::kRing].list_len : c->last_list_len) : -1;
-    *n_done = it1 - it0;
-    *small_step = hl.reason == LOOP_DONE && hl.small_step != 0;
-    if (tree && it1 > it0) { c->last_uncertified = c->h_ring[it1 % symmicp_ctx::kRing].pad; c->last_scans = c->h_ring[it1 % symmicp_ctx::kRing].reserved; }
-    int n_cert = 0;
-    for (int k = it0 + 1; k <= it1; k++) n_cert += pass_kernel[k % symmicp_ctx::kRing];
-    if (hl.reason == LOOP_REDO_PASS && pass_kernel[(it1 + 1) % symmicp_ctx::kRing]) c->cert_pass_failed = true;
-    if (c->sw.debug_host && it1 - it0 >= 2) {      // (a library built with -DRS_STAMPS leaves k_reduce_solve's phase durations in the spare slots of each record)
-        const double *q = c->h_ring[(it1 - 1) % symmicp_ctx::kRing].sums;
-        if (q[37] != 0.0) std::fprintf(stderr, "[symmicp host] k_reduce_solve stamps of pass %d: load + reduce %.2f us (loop state there after %.2f us), bookkeeping + solve %.2f us, publish %.2f us\n", it1 - 1, std::floor(q[37]) * 0.01, (q[37] - std::floor(q[37])) * 1e4 * 0.01, q[38] * 0.01, q[39] * 0.01);
-    }
-    if (c->sw.debug_host && tree) {
-        std::fprintf(stderr, "[symmicp host] batch: work list / searched pairs / scanned pairs after each device pass (c: certified-only kernel):");
-        for (int k = it0 + 1; k <= it1; k++) {
-            const LoopRecord &r = c->h_ring[k % symmicp_ctx::kRing];
-            std::fprintf(stderr, " %d/%d/%d%s", r.list_len, r.pad, r.reserved, pass_kernel[k % symmicp_ctx::kRing] ? "c" : "");
-        }
-        std::fprintf(stderr, "\n");
-    }
-    if (c->sw.debug_host) std::fprintf(stderr, "[symmicp host] batch: %d of %d passes on the device (%d enqueued), reason %d, %d with the straggler stage, %d certified-only%s, list after %lld (host pass before: list %lld, scanned %lld)\n", it1 - it0, want, enq, hl.reason, n_stage, n_cert, c->cert_pass_failed ? " (now off: a pass came back incomplete)" : "", (long long)c->last_list_len, list0, scans0);
-    if (hl.reason == LOOP_SLOW) c->host_passes_since_bailout = 1;      // one host pass, then look again
-    if (hl.reason == LOOP_REDO_PASS || hl.reason == LOOP_HOST_SOLVE) {
-        c->host_passes_since_bailout = 0;
-        c->last_list_len = -1;                        // the host's next pass runs the full search
-        c->st.kernel_launches[7]++;                   // counted with the repairs
-    }
+    if (int st = finish_batch(c, run, diffs_before, n_done, small_step)) return st;
+    if (c->loop_log_on) append_loop_log(c, run);
     return SYMMICP_OK;
 }
 
@@ -718,7 +720,7 @@ int symmicp_align(symmicp_ctx *c, const float *guess16, symmicp_result *out)
     int iters = 0;
     // myicp.cpp:123: while (diff > diff_threshold && iters++ < max_iters)
     while ((c->cfg.fixed_iters || diff > c->cfg.diff_threshold) && iters < c->cfg.max_iters) {
-        if (batch_eligible(c)) {
+        if (may_start_batch(c)) {
             // the same loop, run by the device for the iterations that are left (run_batch); afterwards this loop goes on from the
             // last complete pass -- and ends by its own test where the device loop ended by the same test
             float db[symmicp_ctx::kRing];
@@ -743,14 +745,8 @@ int symmicp_align(symmicp_ctx *c, const float *guess16, symmicp_result *out)
         if (st != SYMMICP_OK) { iters--; break; }
         c->host_passes_since_bailout++;
         diff = it.diff;                                             // myicp.cpp:141
-        if (c->cfg.eps_rotation > 0.f && c->cfg.eps_translation > 0.f && !c->cfg.fixed_iters) {
-            // convergence on the increment (the reference only has the diff threshold, myicp.cpp:123)
-            const float *Xi = it.increment;
-            const double tr = ((double)Xi[0] + Xi[5] + Xi[10] - 1.0) * 0.5;
-            const double ang = std::acos(tr > 1.0 ? 1.0 : (tr < -1.0 ? -1.0 : tr));
-            const double tn = std::sqrt((double)Xi[3] * Xi[3] + (double)Xi[7] * Xi[7] + (double)Xi[11] * Xi[11]);
-            if (ang < c->cfg.eps_rotation && tn < c->cfg.eps_translation) break;
-        }
+        // convergence on the increment (the reference only has the diff threshold, myicp.cpp:123)
+        if (c->cfg.eps_rotation > 0.f && c->cfg.eps_translation > 0.f && !c->cfg.fixed_iters && small_increment(it.increment, c->cfg.eps_rotation, c->cfg.eps_translation)) break;
     }
     out->status = st;
     out->iters = iters;

@@ -18,4 +18,6 @@ int solve_p2p(const symmicp_sums &S, const float pivot[3], float *rcond, float o
 
 void mat4_mul(const float A[16], const float B[16], float C[16]) { solve::mat4_mul(A, B, C); }
 
+bool small_increment(const float Xi[16], float eps_rotation, float eps_translation) { return solve::small_increment(Xi, eps_rotation, eps_translation); }
+
 }  // namespace symmicp

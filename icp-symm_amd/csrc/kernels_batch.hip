@@ -72,13 +72,8 @@ __device__ __noinline__ void batch_stop_and_solve(const BatchArgs &a, const Batc
             solve::mat4_mul(Xi, L.X, Xn);                             // myicp.cpp:138
             for (int k = 0; k < 16; k++) L.X[k] = Xn[k];
             go = 1;
-            if (a.eps_rotation > 0.f && a.eps_translation > 0.f && !a.fixed_iters) {
-                // convergence on the increment (symmicp_align): the pass that applies this increment still runs
-                const double tr = ((double)Xi[0] + Xi[5] + Xi[10] - 1.0) * 0.5;
-                const double ang = acos(tr > 1.0 ? 1.0 : (tr < -1.0 ? -1.0 : tr));
-                const double tn = sqrt((double)Xi[3] * Xi[3] + (double)Xi[7] * Xi[7] + (double)Xi[11] * Xi[11]);
-                if (ang < a.eps_rotation && tn < a.eps_translation) L.small_step = 1;
-            }
+            // convergence on the increment (symmicp_align): the pass that applies this increment still runs
+            if (a.eps_rotation > 0.f && a.eps_translation > 0.f && !a.fixed_iters && solve::small_increment(Xi, a.eps_rotation, a.eps_translation)) L.small_step = 1;
         }
     }
     L.go = go;

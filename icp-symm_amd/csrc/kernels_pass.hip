@@ -20,8 +20,9 @@
 #include "device_common.h"
 #include "oct_walk.h"
 #include "solve_core.h"
+#include "loop_plan.h"       // the codec of the record's two feedback slots
 #include "robust_loss.h"
-#include "pass_rows.h"      // the accumulators, the rows of a pair, the gates and the wave sum (shared with kernels_batch.hip)
+#include "pass_rows.h"     // the accumulators, the rows of a pair, the gates and the wave sum (shared with kernels_batch.hip)
 #pragma clang fp contract(off)
 
 namespace symmicp {
@@ -1450,12 +1451,12 @@ __global__ __launch_bounds__(256) void k_final_reduce(const double *__restrict__
                 read_list_words(counters_to_clear, t, len, searched, dropped, scans);
                 if (t == 0) {
                     s_len = len;
-                    // the record's spare slots: list length (+ kListDropped if appends were dropped -- sl_push: must not happen), pairs
-                    // searched this pass (cells_tile) with, above its 32 bits, those of them that reached a scan (kScanUnit: both counts
-                    // stay exact in the sum over ranks).  (Slot 37 is a sum: the pair count of a weighted record.)
+                    // the record's spare slots (feedback_encode, loop_plan.h): the list's length and whether appends were dropped (sl_push: must
+                    // not happen); the pairs searched this pass (cells_tile) and those of them that reached a scan
+                    // (feedback_encode written out: the call schedules this block's instructions differently)
                     const double lenw = (double)len + (dropped ? kListDropped : 0.0), srw = (double)searched + (double)scans * kScanUnit;
-                    out_dev[kNSum - 1] = lenw; out_dev[kNSum - 2] = srw;
-                    if (out_mapped) { out_mapped[kNSum - 1] = lenw; out_mapped[kNSum - 2] = srw; }
+                    out_dev[kFeedbackListSlot] = lenw; out_dev[kFeedbackCountSlot] = srw;
+                    if (out_mapped) { out_mapped[kFeedbackListSlot] = lenw; out_mapped[kFeedbackCountSlot] = srw; }
                 }
             }
             __syncthreads();
@@ -1558,8 +1559,9 @@ __global__ __launch_bounds__(512) void k_reduce_solve(const double *__restrict__
             for (int c = t; c < 2 * kShards; c += 512) counters_to_clear[c * kShardStride] = 0;
         } else if (t == 0) {
             // summed over the ranks by the all-reduce (k_final_reduce put them in the record)
-            s_len = (s_sum[kNSum - 1] >= kListDropped) ? 0xFFFFFFFFu : (uint32_t)s_sum[kNSum - 1];
-            const double sr = s_sum[kNSum - 2], sc = floor(sr / kScanUnit);
+            // (feedback_decode written out: the call schedules this block's instructions differently)
+            s_len = (s_sum[kFeedbackListSlot] >= kListDropped) ? 0xFFFFFFFFu : (uint32_t)s_sum[kFeedbackListSlot];
+            const double sr = s_sum[kFeedbackCountSlot], sc = floor(sr / kScanUnit);
             s_unc = (uint32_t)(sr - sc * kScanUnit); s_scan = (uint32_t)sc;
         }
     }
@@ -1580,8 +1582,8 @@ __global__ __launch_bounds__(512) void k_reduce_solve(const double *__restrict__
         if (t == 0) {
             loop->iters = it;
             r.solved = 0;
-            r.pad = (int32_t)unc;
-            r.list_len = (int32_t)len; r.reserved = (int32_t)scans;
+            r.searched = (int32_t)unc;
+            r.list_len = (int32_t)len; r.scans = (int32_t)scans;
         }
         // many pairs had to be searched again (the cloud moved): the separate kernels do that faster; this pass is complete
         if (cfg.tree && (unc > cfg.uncertified_limit || (cfg.walk_in_loop && len > cfg.list_limit))) { if (t == 0) { loop->stop = 1; loop->reason = LOOP_SLOW; } return; }
@@ -1618,6 +1620,7 @@ __global__ __launch_bounds__(512) void k_reduce_solve(const double *__restrict__
 #endif
     if (cfg.eps_rotation > 0.f && cfg.eps_translation > 0.f && !cfg.fixed_iters) {
         // convergence on the increment (engine.cpp, symmicp_align): the pass that applies this increment still runs
+        // (solve::small_increment written out: the call turns the two compares into their negations)
         const double tr = ((double)Xi[0] + Xi[5] + Xi[10] - 1.0) * 0.5;
         const double ang = acos(tr > 1.0 ? 1.0 : (tr < -1.0 ? -1.0 : tr));
         const double tn = sqrt((double)Xi[3] * Xi[3] + (double)Xi[7] * Xi[7] + (double)Xi[11] * Xi[11]);

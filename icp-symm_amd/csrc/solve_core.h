@@ -497,5 +497,15 @@ SYMMICP_HD inline void mat4_mul(const float A[16], const float B[16], float C[16
     for (int k = 0; k < 16; ++k) C[k] = T[k];
 }
 
+// Convergence on the increment (the reference only has the diff threshold, myicp.cpp:123): the rotation angle of Xi, from its trace, and
+// the norm of its translation are both below their eps.  Callers ask only when both eps are positive and the iteration count is not fixed.
+SYMMICP_HD inline bool small_increment(const float Xi[16], float eps_rotation, float eps_translation)
+{
+    const double tr = ((double)Xi[0] + Xi[5] + Xi[10] - 1.0) * 0.5;
+    const double ang = acos(tr > 1.0 ? 1.0 : (tr < -1.0 ? -1.0 : tr));
+    const double tn = sqrt((double)Xi[3] * Xi[3] + (double)Xi[7] * Xi[7] + (double)Xi[11] * Xi[11]);
+    return ang < eps_rotation && tn < eps_translation;
+}
+
 }  // namespace solve
 }  // namespace symmicp

@@ -11,11 +11,7 @@ namespace symmicp {
 constexpr int kNSum = SYMMICP_NSUM;   // 40 doubles per reduction record
 constexpr int kNAcc = 37;             // live accumulators (rest of the record is 0)
 constexpr int kNAccW = 38;            // ... of the weighted passes (robust loss): slot 37 = the unweighted pair count
-// TREE passes: the final reduce leaves the work list's length in slot 39 (and the pairs searched in 38); appends dropped for lack of
-// room (must not happen) add this to the length, so that it survives the sum over ranks
-constexpr double kListDropped = 4294967296.0;
-// ... and slot 38 carries two counts: the pairs searched (below 2^32) + kScanUnit x those of them that reached a scan
-constexpr double kScanUnit = 4294967296.0;
+// (TREE passes: the final reduce leaves the work list's length in slot 39 and the pairs searched and scanned in 38: loop_plan.h)
 constexpr int kLeaf = 8;              // target points per leaf (8 x 16 B = one 128-B line)
 constexpr int kFan = 8;               // children per tree node
 constexpr int kMaxTreeLevels = 12;
@@ -139,9 +135,11 @@ struct LoopRecord {          // one per pass, host-mapped
     float rcond;
     int32_t status;                  // status of that solve
     int32_t solved;                  // 1: increment / X are valid (the loop went on)
-    int32_t pad;                     // (pairs searched in this pass)
-    int32_t list_len, reserved;      // work-list length of this pass (queries handed to the tree walk); reserved: pairs that reached a scan
+    int32_t searched;                // pairs searched in this pass
+    int32_t list_len, scans;         // work-list length of this pass (queries handed to the tree walk); searched pairs that reached a scan
 };
+static_assert(sizeof(LoopRecord) == 472 && offsetof(LoopRecord, searched) == 460 && offsetof(LoopRecord, list_len) == 464 && offsetof(LoopRecord, scans) == 468,
+              "LoopRecord keeps its layout");
 
 // ---- pair rejection (kernels_select.hip): trim fraction, one-to-one, median distance, reciprocal ----
 // what a reciprocal pass adds to the claim (k_recip_check): the index over the ORIGINAL source, whose tq carries the caller's row in w,
