@@ -54,8 +54,12 @@
 //                              M other points within R.  Unless --quiet each filter prints one line with the counts before and after
 //     --min-cluster EPS:M      small-cluster removal of both clouds (after --sor and --ror): every connected part of a cloud (points
 //                              closer than EPS) with fewer than M points goes -- floating blobs that pass both point filters
-//     --out aligned.pcd        write the source moved by the result (the reference only prints its result; after --sor / --ror / --min-cluster the
-//                              filtered source)
+//     --remove-plane D[:H[:MIN]]  plane removal of both clouds (after --sor and --ror, before --min-cluster): the points within D of each
+//                              cloud's dominant plane go -- the floor or table that joins the objects on it into one cluster.  H RANSAC
+//                              hypotheses (default 1000); a plane with fewer than MIN points (default 3) is left alone
+//     --plane-axis X,Y,Z:DEG   with --remove-plane: only planes whose normal lies within DEG degrees (0 < DEG <= 90) of the axis
+//     --out aligned.pcd        write the source moved by the result (the reference only prints its result; after --sor / --ror / --remove-plane /
+//                              --min-cluster the filtered source)
 //     --quiet                  no per-iteration lines
 //   Without file names it registers cat.pcd to cat_out.pcd from the working directory: the reference's own run.
 // Exit code: the symmicp status of the alignment (0 = ok).
@@ -74,7 +78,7 @@
 static int usage(const char *argv0, const char *complaint)
 {
     std::fprintf(stderr, "%s\nusage: %s [--mode quirks|paper|plane|gicp|color|ndt] [--ndt-resolution L] [--ndt-neighbors 1|7] [--ndt-min-points N] [--ndt-level L:ITERS]... [--color-weight L] [--corr identity|tree] [--iters N] [--threshold D] [--loss none|huber|tukey|cauchy|gm]"
-                 " [--loss-scale S] [--gicp-epsilon E] [--max-dist D] [--trim F] [--one-to-one] [--reciprocal] [--median-factor F] [--scale LEAF:ITERS[:MAXDIST]]... [--init global --fpfh-radius R --ransac-dist D [--ransac-iters H] [--seed S] [--init-voxel L] [--init-keypoints iss --iss-radius R [--iss-nms-radius R2] [--iss-min-neighbors K]]] [--init fgr --fpfh-radius R --fgr-dist D [--fgr-iters N] [--fgr-tuples N] [--seed S] [--init-voxel L] [--init-keypoints iss ...]] [--evaluate D [--information]] [--sor K:S] [--ror R:M] [--min-cluster EPS:M] [--out file.pcd] [--quiet] [source.pcd target.pcd]\n",
+                 " [--loss-scale S] [--gicp-epsilon E] [--max-dist D] [--trim F] [--one-to-one] [--reciprocal] [--median-factor F] [--scale LEAF:ITERS[:MAXDIST]]... [--init global --fpfh-radius R --ransac-dist D [--ransac-iters H] [--seed S] [--init-voxel L] [--init-keypoints iss --iss-radius R [--iss-nms-radius R2] [--iss-min-neighbors K]]] [--init fgr --fpfh-radius R --fgr-dist D [--fgr-iters N] [--fgr-tuples N] [--seed S] [--init-voxel L] [--init-keypoints iss ...]] [--evaluate D [--information]] [--sor K:S] [--ror R:M] [--remove-plane D[:H[:MIN]] [--plane-axis X,Y,Z:DEG]] [--min-cluster EPS:M] [--out file.pcd] [--quiet] [source.pcd target.pcd]\n",
                  complaint, argv0);
     return 64;
 }
@@ -105,6 +109,9 @@ int main(int argc, char **argv)
     float sor_mul = 0.f, ror_radius = 0.f;
     int cluster_min = 0;
     float cluster_eps = 0.f;
+    float plane_dist = 0.f, plane_axis[3] = {0.f, 0.f, 0.f}, plane_deg = 0.f;
+    int plane_hyp = 1000, plane_min = 3;
+    bool have_plane_axis = false;
     bool quiet = false;
     bool ndt = false, have_ndt_option = false;
     float ndt_resolution = 0.f;
@@ -322,12 +329,51 @@ int main(int argc, char **argv)
             }
             if (!ok) return usage(argv[0], "--min-cluster needs EPS:M with a distance EPS > 0 and M >= 1 points");
         }
+        else if (a == "--remove-plane") {
+            // D[:H[:MIN]]
+            const char *v = value("--remove-plane");
+            char *end = nullptr;
+            plane_dist = std::strtof(v, &end);
+            bool ok = end != v && (*end == ':' || *end == 0) && std::isfinite(plane_dist) && plane_dist > 0.f;
+            if (ok && *end == ':') {
+                const char *w = end + 1;
+                const long h = std::strtol(w, &end, 10);
+                ok = end != w && (*end == ':' || *end == 0) && h >= 1 && h <= (1l << 24);
+                plane_hyp = (int)h;
+                if (ok && *end == ':') {
+                    w = end + 1;
+                    const long m = std::strtol(w, &end, 10);
+                    ok = end != w && *end == 0 && m >= 0 && m <= 0x7fffffffl;
+                    plane_min = (int)m;
+                }
+            }
+            if (!ok) return usage(argv[0], "--remove-plane needs D[:H[:MIN]] with a distance D > 0, 1 <= H <= 16777216 hypotheses and MIN >= 0 points");
+        }
+        else if (a == "--plane-axis") {
+            // X,Y,Z:DEG
+            const char *v = value("--plane-axis");
+            char *end = nullptr;
+            bool ok = true;
+            for (int k = 0; k < 3 && ok; k++) {
+                plane_axis[k] = std::strtof(v, &end);
+                ok = end != v && *end == (k < 2 ? ',' : ':') && std::isfinite(plane_axis[k]);
+                v = end + 1;
+            }
+            if (ok) {
+                plane_deg = std::strtof(v, &end);
+                ok = end != v && *end == 0 && plane_deg > 0.f && plane_deg <= 90.f;
+            }
+            ok = ok && (plane_axis[0] != 0.f || plane_axis[1] != 0.f || plane_axis[2] != 0.f);
+            if (!ok) return usage(argv[0], "--plane-axis needs X,Y,Z:DEG with a non-zero axis and 0 < DEG <= 90");
+            have_plane_axis = true;
+        }
         else if (a == "--quiet") { icp.setVerbose(false); quiet = true; }
         else if (!a.empty() && a[0] == '-') return usage(argv[0], ("unknown option " + a).c_str());
         else files.push_back(a);
     }
     if (files.empty()) files = {"cat.pcd", "cat_out.pcd"};
     if (files.size() != 2) return usage(argv[0], "expected two PCD files");
+    if (have_plane_axis && !(plane_dist > 0.f)) return usage(argv[0], "--plane-axis needs --remove-plane");
     if (have_ndt_option && !ndt) return usage(argv[0], "--ndt-resolution, --ndt-neighbors, --ndt-min-points and --ndt-level need --mode ndt");
     if (ndt) {
         if (ndt_levels.empty() && !(ndt_resolution > 0.f)) return usage(argv[0], "--mode ndt needs --ndt-resolution L (or --ndt-level L:ITERS)");
@@ -407,6 +453,18 @@ int main(int argc, char **argv)
         if (!quiet)
             std::printf("%s outlier removal: source %zu -> %zu, target %zu -> %zu\n", f == 0 ? "statistical" : "radius", ns,
                         icp.GetSrcCloud()->points.size(), nt, icp.GetTgtCloud()->points.size());
+    }
+    if (plane_dist > 0.f) {
+        const size_t ns = icp.GetSrcCloud()->points.size(), nt = icp.GetTgtCloud()->points.size();
+        const int st = icp.removePlane(plane_dist, plane_hyp, plane_min, plane_axis, plane_deg);
+        if (st != SYMMICP_OK) { std::fprintf(stderr, "%s\n", icp.lastError()); return st; }
+        if (!quiet) {
+            double ps[4], pt[4];
+            icp.planeRemoved(ps, pt);
+            std::printf("plane removal: source %zu -> %zu, target %zu -> %zu\n", ns, icp.GetSrcCloud()->points.size(), nt,
+                        icp.GetTgtCloud()->points.size());
+            std::printf("  source plane %.6f %.6f %.6f %.6f  target plane %.6f %.6f %.6f %.6f\n", ps[0], ps[1], ps[2], ps[3], pt[0], pt[1], pt[2], pt[3]);
+        }
     }
     if (cluster_min > 0) {
         const size_t ns = icp.GetSrcCloud()->points.size(), nt = icp.GetTgtCloud()->points.size();

@@ -52,7 +52,8 @@ void read_switches(Switches &w)
     w.compact_blocks = (int)num("SYMMICP_COMPACT_BLOCKS", 1280);
     w.feature_nn_splits = (int)num("SYMMICP_FEATURE_NN_SPLITS", 0);
     w.feature_nn_queries = (int)num("SYMMICP_FEATURE_NN_QUERIES", 0);
-    w.tune.wave_mode_max = (uint32_t)num("SYMMICP_WAVE_MODE_MAX", 20000);
+    w.plane_score = (int)num("SYMMICP_PLANE_SCORE", 0);
+    w.tune.wave_mode_max =(uint32_t)num("SYMMICP_WAVE_MODE_MAX", 20000);
     w.tune.cells_chunk = (uint32_t)num("SYMMICP_CELLS_CHUNK", 16);
     w.tune.cells_queries = (uint32_t)num("SYMMICP_CELLS_QUERIES", 0);
     w.tune.walk_budget = (uint32_t)num("SYMMICP_WALK_BUDGET", 160);

@@ -12,6 +12,7 @@
 //   engine_eval.cpp      registration evaluation (symmicp_evaluate_registration, symmicp_evaluate, symmicp_information_from_sums)
 //   engine_fgr.cpp       Fast Global Registration (symmicp_ctx_fgr, symmicp_ctx_fgr_pass)
 //   engine_posegraph.cpp pose-graph optimisation (symmicp_ctx_posegraph_optimize, symmicp_ctx_posegraph_pass, the two host helpers)
+//   engine_plane.cpp     RANSAC plane segmentation (symmicp_ctx_segment_plane, symmicp_ctx_plane_hypotheses)
 //   engine_ndt.cpp       SYMMICP_MODE_NDT: configuration, Gauss constants, the voxel map (build, read-back, symmicp_ctx_ndt_map), pass arguments
 #pragma once
 #include <hip/hip_runtime.h>
@@ -107,6 +108,7 @@ struct Switches {
     int cert_head = 4;                     // ... passes of the fused head of a run that goes out in one piece (run_batch)
     int pass_blocks = 2048, id_blocks = 2048, acc_blocks = 512, fused_blocks = 512, compact_blocks = 1280;
     int feature_nn_splits = 0, feature_nn_queries = 0;      // symmicp_ctx_feature_nn: candidate splits / queries per thread (0: chosen from the sizes)
+    int plane_score = 0;                   // symmicp_ctx_segment_plane: the scoring kernel (launch_plane_score's shape; A/B runs)
     PassTuning tune;                       // wave_mode_max, cells_chunk, walk_budget
 };
 

@@ -161,6 +161,7 @@ int MyICP::removeOutliers(int filter, int k, float std_mul, float radius, int mi
 	if (!ctx) { error_ = "symmicp_create failed: no usable gfx950 HIP device (there is no CPU fallback)"; return SYMMICP_ERR_HIP; }
 	pcl::PointCloud<PointT> *clouds[2] = {cloud_src.get(), cloud_tgt.get()};
 	std::vector<int32_t> rows[2];
+	double planes[2][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}};
 	for (int s = 0; s < 2; s++) {
 		const size_t n = clouds[s]->points.size();
 		if (n == 0) { error_ = "outlier removal: a cloud is empty"; return SYMMICP_ERR_SIZE; }
@@ -181,6 +182,22 @@ int MyICP::removeOutliers(int filter, int k, float std_mul, float radius, int mi
 			if (st == SYMMICP_ERR_SIZE) st = SYMMICP_OK;      // (the sizes were not asked for: the labels are written)
 			if (st == SYMMICP_OK)
 				for (size_t i = 0; i < n; i++) if (rows[s][i] >= 0) rows[s][count++] = (int32_t)i;
+		} else if (filter == 3) {
+			// the dominant plane: the rows that are NOT among its final inliers; a cloud without a plane keeps every row
+			std::vector<int32_t> on(n);
+			float plane4[4];
+			symmicp_plane_result res;
+			size_t on_count = 0;
+			st = symmicp_ctx_segment_plane(ctx, xyz, fs, 1, n, &plane_cfg_, plane4, &res, on.data(), n, &on_count, nullptr, nullptr, nullptr);
+			if (st == SYMMICP_ERR_NO_CONSENSUS) { st = SYMMICP_OK; on_count = 0; }
+			if (st == SYMMICP_OK) {
+				for (int a = 0; a < 4; a++) planes[s][a] = res.plane[a];
+				size_t at = 0;
+				for (size_t i = 0; i < n; i++) {
+					if (at < on_count && (size_t)on[at] == i) at++;
+					else rows[s][count++] = (int32_t)i;
+				}
+			}
 		} else {
 			st = filter == 0 ? symmicp_ctx_statistical_outlier_removal(ctx, xyz, fs, 1, n, k, std_mul, rows[s].data(), n, &count, nullptr, nullptr)
 			                 : symmicp_ctx_radius_outlier_removal(ctx, xyz, fs, 1, n, radius, min_neighbors, rows[s].data(), n, &count, nullptr);
@@ -205,6 +222,7 @@ int MyICP::removeOutliers(int filter, int k, float std_mul, float radius, int mi
 		if (with_int) ints[s]->resize(m);
 		(s == 0 ? removed_src_ : removed_tgt_) = n - m;
 	}
+	if (filter == 3) std::memcpy(planes_, planes, sizeof(planes_));
 	return SYMMICP_OK;
 }
 
@@ -221,6 +239,17 @@ int MyICP::removeRadiusOutliers(float radius, int min_neighbors)
 int MyICP::removeSmallClusters(float eps, int min_size)
 {
 	return removeOutliers(2, 0, 0.f, eps, min_size);
+}
+
+int MyICP::removePlane(float max_dist, int hypotheses, int min_inliers, const float axis[3], float max_angle_deg)
+{
+	symmicp_plane_config_default(&plane_cfg_);
+	plane_cfg_.max_dist = max_dist;
+	plane_cfg_.hypotheses = hypotheses < 0 ? 0u : (uint32_t)hypotheses;
+	plane_cfg_.min_inliers = min_inliers;
+	for (int a = 0; a < 3; a++) plane_cfg_.axis[a] = axis ? axis[a] : 0.f;
+	plane_cfg_.max_angle_deg = max_angle_deg;
+	return removeOutliers(3, 0, 0.f, 0.f, 0);
 }
 
 int MyICP::align(float out4x4[16], const float *guess4x4)

@@ -449,6 +449,21 @@ void launch_ransac_eval(const float *pq8, uint32_t m, const float *hyp, const ui
                         float max_dist2, int32_t *inliers, hipStream_t s);
 void launch_ransac_argmax(const uint8_t *status, const int32_t *inliers, uint32_t H, unsigned long long *best, hipStream_t s);
 
+// RANSAC plane segmentation (kernels_plane.hip; symmicp_ctx_segment_plane).  pts4 [n][4] = p.xyz, 0 about the pivot; hyp4 [H][4] = n, d;
+// axis: null, or the unit axis of the constraint.  score: inliers[h] += the points within max_dist of survivor h; the survivor count stays
+// on the device (the grid is sized for H).  shape: 0 the kernel in use (hypotheses in lanes, the chunk staged in LDS); the others are
+// the A/B shapes of kernels_plane.hip (SYMMICP_PLANE_SCORE; profiles/plane_workload.py).  mask [n]: the inlier flags of the winner named by the arg-max key
+// `best` (launch_ransac_argmax), nd_out [4] its (n, d); zeros when the key is 0.
+constexpr int kPlaneChunk = 512;          // points a workgroup of the scoring kernel stages at a time (tests/_segplane_ref.py: K_CHUNK)
+constexpr int kPlaneLaneHyps = 2;         // evaluated hypotheses per lane: 256 * kPlaneLaneHyps per workgroup (K_BATCH)
+constexpr int kPlaneBlocks = 2048;        // workgroups of a scoring launch, about: 8 resident on each of 256 CUs
+void launch_plane_hyp(const float *pts4, uint32_t n, uint32_t H, unsigned long long base, const float *axis, float cos_min, float *hyp4,
+                      uint8_t *status, int32_t *inliers, uint32_t *surv, uint32_t *n_surv, hipStream_t s);
+void launch_plane_score(const float *pts4, uint32_t n, const float *hyp4, const uint32_t *surv, const uint32_t *n_surv, uint32_t H, float max_dist,
+                        int32_t *inliers, int shape, hipStream_t s);
+void launch_plane_mask(const float *pts4, uint32_t n, const float *hyp4, const unsigned long long *best, float max_dist, uint8_t *mask,
+                       float *nd_out, hipStream_t s);
+
 // Fast Global Registration (kernels_fgr.hip; symmicp_ctx_fgr).  pq8 as RANSAC's.  Tuple test: flags [trials + 1] (the last word 0) = 1 for
 // an accepted trial; after an exclusive scan of them (rank [trials + 1], rank[trials] = the accepted count) the scatter writes the
 // draws of the trials of rank < max_tuples to set [3 * max_tuples].  The loop: one workgroup, every pass of it in one launch.

@@ -22,6 +22,7 @@ UNIQUE_ID_BYTES = 128
 OK, ERR_ARG, ERR_SIZE, ERR_DEGENERATE, ERR_IO, ERR_HIP, ERR_STATE, ERR_COMM = range(8)
 ERR_NO_CONSENSUS = 8
 RANSAC_EVALUATED, RANSAC_REPEATED, RANSAC_EDGE, RANSAC_DEGENERATE, RANSAC_FAR = range(5)      # per-hypothesis status of ransac()
+PLANE_EVALUATED, PLANE_REPEATED, PLANE_DEGENERATE, PLANE_OFF_AXIS = range(4)                  # ... of segment_plane()
 MODE_QUIRKS, MODE_PAPER, MODE_P2P, MODE_PLANE, MODE_GICP, MODE_COLOR, MODE_NDT = 0, 1, 2, 3, 5, 7, 9      # (4, 6 and 8 are unassigned)
 CORR_IDENTITY, CORR_BRUTE, CORR_TREE = 0, 1, 2
 APPLY_DEFAULT, APPLY_INCREMENTAL, APPLY_CUMULATIVE = 0, 1, 2
@@ -110,6 +111,18 @@ class ClusterConfig(C.Structure):
     """symmicp_cluster_config"""
     _fields_ = [("struct_size", C.c_uint32), ("eps", C.c_float), ("min_points", C.c_int32), ("min_cluster_size", C.c_int32),
                 ("max_cluster_size", C.c_int32), ("reserved", C.c_int32)]
+
+
+class PlaneConfig(C.Structure):
+    """symmicp_plane_config"""
+    _fields_ = [("struct_size", C.c_uint32), ("hypotheses", C.c_uint32), ("seed", C.c_uint64), ("max_dist", C.c_float),
+                ("min_inliers", C.c_int32), ("refits", C.c_int32), ("axis", C.c_float * 3), ("max_angle_deg", C.c_float),
+                ("reserved", C.c_int32)]
+
+
+class PlaneResult(C.Structure):
+    _fields_ = [("best_hypothesis", C.c_int32), ("evaluated", C.c_int32), ("inliers_ransac", C.c_int32), ("inliers_final", C.c_int32),
+                ("rmse_final", C.c_double), ("plane", C.c_double * 4)]
 
 
 class NdtConfig(C.Structure):
@@ -217,6 +230,7 @@ EXPORTS = [
     "symmicp_statistical_outlier_removal", "symmicp_ctx_statistical_outlier_removal",
     "symmicp_radius_outlier_removal", "symmicp_ctx_radius_outlier_removal",
     "symmicp_cluster_config_default", "symmicp_cluster", "symmicp_ctx_cluster",
+    "symmicp_plane_config_default", "symmicp_segment_plane", "symmicp_ctx_segment_plane", "symmicp_ctx_plane_hypotheses",
     "symmicp_ndt_config_default", "symmicp_set_ndt", "symmicp_get_ndt", "symmicp_ndt_gauss", "symmicp_ndt_weight", "symmicp_get_ndt_state",
     "symmicp_ctx_ndt_map", "symmicp_ndt_map", "symmicp_get_ndt_map",
     "symmicp_posegraph_config_default", "symmicp_posegraph_optimize", "symmicp_ctx_posegraph_optimize", "symmicp_ctx_posegraph_pass",
@@ -388,6 +402,12 @@ def lib():
     L.symmicp_cluster_config_default.restype = None
     L.symmicp_cluster.argtypes = [C.c_int] + clu
     L.symmicp_ctx_cluster.argtypes = [vp] + clu
+    plc = [fp, C.c_size_t, C.c_size_t, C.c_size_t, C.POINTER(PlaneConfig)]
+    L.symmicp_plane_config_default.argtypes = [C.POINTER(PlaneConfig)]
+    L.symmicp_plane_config_default.restype = None
+    L.symmicp_segment_plane.argtypes = [C.c_int] + plc + [fp, C.POINTER(PlaneResult), i32p, C.c_size_t, szp, dp, u8p, i32p]
+    L.symmicp_ctx_segment_plane.argtypes = [vp] + plc + [fp, C.POINTER(PlaneResult), i32p, C.c_size_t, szp, dp, u8p, i32p]
+    L.symmicp_ctx_plane_hypotheses.argtypes = [vp] + plc + [fp, u8p, fp]
     ndp = C.POINTER(NdtConfig)
     L.symmicp_ndt_config_default.argtypes = [ndp]
     L.symmicp_ndt_config_default.restype = None
@@ -968,6 +988,88 @@ def pack_clusters(xyz, nrm, labels):
     rows = np.concatenate(rows).astype(np.int32) if rows else np.zeros(0, np.int32)
     return dict(xyz=np.ascontiguousarray(xyz[rows]), nrm=None if nrm is None else np.ascontiguousarray(nrm[rows]),
                 ranges=np.array(ranges, np.int64).reshape(-1, 2), labels=np.array(kept, np.int32), rows=rows, skipped=skipped)
+
+
+def plane_config(max_dist, hypotheses=1000, seed=0, refits=1, min_inliers=3, axis=None, max_angle_deg=0.0):
+    cfg = PlaneConfig()
+    lib().symmicp_plane_config_default(C.byref(cfg))
+    cfg.max_dist, cfg.hypotheses, cfg.seed, cfg.refits, cfg.min_inliers = float(max_dist), int(hypotheses), int(seed), int(refits), int(min_inliers)
+    if axis is not None:
+        cfg.axis[:] = [float(v) for v in axis]
+    cfg.max_angle_deg = float(max_angle_deg)
+    return cfg
+
+
+def _plane_call(fn, head, xyz, cfg, cap=None, strides=None, want=True):
+    """fn(*head, <the C arguments>) -> (status, dict(plane [4] f64, plane32 [4] f32, rows [cap] int32 or None, count, best_hypothesis,
+    evaluated, inliers_ransac, inliers_final, rmse_final[, distance [n] f64, hyp_status [H] uint8, hyp_inliers [H] int32])).  cap None: the
+    count only (rows_out == NULL, cap 0).  strides = (n, row stride, col stride) reads xyz as a flat f32 buffer."""
+    xyz, n, xr, xc = _outlier_cloud(xyz, strides)
+    H = int(cfg.hypotheses)
+    rows = None if cap is None else np.full(max(cap, 1), -1, np.int32)
+    dist = np.zeros(max(n, 1), np.float64) if want else None
+    status = np.zeros(max(H, 1), np.uint8) if want else None
+    inl = np.zeros(max(H, 1), np.int32) if want else None
+    plane = np.zeros(4, np.float32)
+    res = PlaneResult()
+    count = C.c_size_t(0)
+    st = fn(*head, _fptr(xyz), xr, xc, n, C.byref(cfg), _fptr(plane), C.byref(res), None if rows is None else _i32ptr(rows),
+            0 if cap is None else cap, C.byref(count), None if dist is None else dist.ctypes.data_as(C.POINTER(C.c_double)),
+            None if status is None else status.ctypes.data_as(C.POINTER(C.c_uint8)), None if inl is None else _i32ptr(inl))
+    r = dict(plane=np.array(res.plane[:], np.float64), plane32=plane, rows=rows, count=int(count.value), best_hypothesis=res.best_hypothesis,
+             evaluated=res.evaluated, inliers_ransac=res.inliers_ransac, inliers_final=res.inliers_final, rmse_final=res.rmse_final)
+    if want:
+        r["distance"], r["hyp_status"], r["hyp_inliers"] = dist[:n], status[:H], inl[:H]
+    return st, r
+
+
+def _segment_plane(fn, head, xyz, cfg, return_info):
+    """one call with cap = n, which always suffices -> (status, (plane, rows) or the dict of _plane_call with rows cut to the count)"""
+    st, r = _plane_call(fn, head, xyz, cfg, cap=len(xyz), want=return_info)
+    r["rows"] = r["rows"][:r["count"]].copy()
+    r["status"] = st
+    return st, (r if return_info else (r["plane"], r["rows"]))
+
+
+def segment_plane(xyz, max_dist, hypotheses=1000, seed=0, refits=1, min_inliers=3, axis=None, max_angle_deg=0.0, return_info=False, device=-1):
+    """RANSAC plane segmentation on the GPU (symmicp_segment_plane; include/symmicp.h defines the result) -> (plane [4] float64 = (n, d)
+    with n . x + d = 0, rows [K] int32: the rows within max_dist of it, ascending).  axis / max_angle_deg: only planes whose normal lies
+    within that angle of the axis (PCL's perpendicular-plane model).  With return_info a dict (plane=, plane32=, rows=, count=,
+    best_hypothesis=, evaluated=, inliers_ransac=, inliers_final=, rmse_final=, distance= [N] f64, hyp_status= [H], hyp_inliers= [H]).
+    Raises SymmIcpError (ERR_NO_CONSENSUS) when no plane reaches max(3, min_inliers) rows."""
+    cfg = plane_config(max_dist, hypotheses, seed, refits, min_inliers, axis, max_angle_deg)
+    st, r = _segment_plane(lib().symmicp_segment_plane, (int(device),), xyz, cfg, return_info)
+    if st != OK:
+        raise SymmIcpError(st, "segment_plane")
+    return r
+
+
+def _segment_planes(one, xyz, max_dist, max_planes, min_inliers, hypotheses, seed, refits, axis, max_angle_deg):
+    xyz = _cloud(xyz)
+    labels = np.full(len(xyz), -1, np.int32)
+    planes = []
+    for k in range(int(max_planes)):
+        left = np.nonzero(labels < 0)[0]
+        if len(left) < max(3, int(min_inliers)):
+            break
+        cfg = plane_config(max_dist, hypotheses, int(seed) + k, refits, min_inliers, axis, max_angle_deg)
+        st, r = one(np.ascontiguousarray(xyz[left]), cfg)
+        if st == ERR_NO_CONSENSUS:
+            break
+        if st != OK:
+            raise SymmIcpError(st, "segment_planes")
+        plane, rows = r
+        labels[left[rows]] = k
+        planes.append(plane)
+    return np.array(planes, np.float64).reshape(-1, 4), labels
+
+
+def segment_planes(xyz, max_dist, max_planes, min_inliers, hypotheses=1000, seed=0, refits=1, axis=None, max_angle_deg=0.0, device=-1):
+    """planes peeled one at a time -> (planes [P,4] float64, labels [N] int32: the plane of every row, -1 for rows on none).  Plane k is
+    segment_plane on the rows not yet labelled, with seed + k; the loop stops at max_planes or at the first plane with fewer than
+    max(3, min_inliers) rows.  A host loop over segment_plane."""
+    one = lambda sub, cfg: _segment_plane(lib().symmicp_segment_plane, (int(device),), sub, cfg, False)
+    return _segment_planes(one, xyz, max_dist, max_planes, min_inliers, hypotheses, seed, refits, axis, max_angle_deg)
 
 
 def _features(f):
@@ -1834,6 +1936,35 @@ class Engine:
         neighbors)"""
         return _cluster_call(self._L.symmicp_ctx_cluster, (self._h,), xyz, cfg, cap, strides)
 
+    def segment_plane(self, xyz, max_dist, hypotheses=1000, seed=0, refits=1, min_inliers=3, axis=None, max_angle_deg=0.0, return_info=False,
+                      check=True):
+        """segment_plane on this context (symmicp_ctx_segment_plane, one call with cap = n).  check=False: (status, result) instead of
+        raising."""
+        cfg = plane_config(max_dist, hypotheses, seed, refits, min_inliers, axis, max_angle_deg)
+        st, r = _segment_plane(self._L.symmicp_ctx_segment_plane, (self._h,), xyz, cfg, return_info)
+        if not check:
+            return st, r
+        self._chk(st)
+        return r
+
+    def segment_plane_raw(self, xyz, cfg, cap=None, strides=None, want=True):
+        """one call of symmicp_ctx_segment_plane with a caller-chosen cap (None: rows_out == NULL) -> (status, dict) of _plane_call"""
+        return _plane_call(self._L.symmicp_ctx_segment_plane, (self._h,), xyz, cfg, cap, strides, want)
+
+    def segment_planes(self, xyz, max_dist, max_planes, min_inliers, hypotheses=1000, seed=0, refits=1, axis=None, max_angle_deg=0.0):
+        """segment_planes on this context"""
+        one = lambda sub, cfg: _segment_plane(self._L.symmicp_ctx_segment_plane, (self._h,), sub, cfg, False)
+        return _segment_planes(one, xyz, max_dist, max_planes, min_inliers, hypotheses, seed, refits, axis, max_angle_deg)
+
+    def plane_hypotheses(self, xyz, cfg, strides=None):
+        """test entry (symmicp_ctx_plane_hypotheses) -> dict(hyp [H,4] f32 = n, d about the pivot, hyp_status [H] uint8, pivot [3] f32)"""
+        xyz, n, xr, xc = _outlier_cloud(xyz, strides)
+        H = int(cfg.hypotheses)
+        hyp, status, pivot = np.zeros((H, 4), np.float32), np.zeros(H, np.uint8), np.zeros(3, np.float32)
+        self._chk(self._L.symmicp_ctx_plane_hypotheses(self._h, _fptr(xyz), xr, xc, n, C.byref(cfg), _fptr(hyp),
+                                                       status.ctypes.data_as(C.POINTER(C.c_uint8)), _fptr(pivot)))
+        return dict(hyp=hyp, hyp_status=status, pivot=pivot)
+
     def remove_radius_outlier_raw(self, xyz, radius, min_neighbors, cap=None, strides=None):
         """one call of symmicp_ctx_radius_outlier_removal with a caller-chosen cap (None: rows_out == NULL) -> (status, rows, count,
         neighbors); nothing is raised"""
@@ -2171,6 +2302,7 @@ class MyICP:
         self._have_src = self._have_tgt = False         # normals supplied by the caller through setInput* (not estimated here)
         self.multistart_results = []
         self._removed = (0, 0)
+        self._planes = (np.zeros(4), np.zeros(4))
 
     def alignMultiStart(self, guesses):
         """one batch on the object's clouds, a problem per guess [B, 4, 4] (Engine.align_multistart with the object's mode, max_iters,
@@ -2470,8 +2602,29 @@ class MyICP:
             raise SymmIcpError(ERR_ARG, "removeSmallClusters: min_size must be >= 1")
         return self._filter_clouds(lambda e, x: np.nonzero(e.cluster_dbscan(x, eps, 1, min_size, 0) >= 0)[0].astype(np.int32))
 
+    def removePlane(self, max_dist, hypotheses=1000, min_inliers=3, axis=(0.0, 0.0, 0.0), max_angle_deg=0.0):
+        """as removeStatisticalOutliers, with Engine.segment_plane (seed 0, one refit): the final inliers of the dominant plane go from EACH
+        cloud -- the floor or the table that joins the objects standing on it into one cluster.  A cloud without a plane of
+        max(3, min_inliers) points loses nothing.  planeRemoved() has the two planes."""
+        planes = []
+
+        def keep(e, x):
+            st, r = e.segment_plane(x, max_dist, hypotheses, 0, 1, min_inliers, axis, max_angle_deg, check=False)
+            if st not in (OK, ERR_NO_CONSENSUS):
+                e._chk(st)
+            planes.append(r[0] if st == OK else np.zeros(4))
+            return np.setdiff1d(np.arange(len(x), dtype=np.int32), r[1] if st == OK else np.zeros(0, np.int32))
+
+        st = self._filter_clouds(keep)
+        self._planes = tuple(planes)
+        return st
+
+    def planeRemoved(self):
+        """(source, target) planes [4] float64 of the last removePlane: n, d with n . x + d = 0; zeros for a cloud without one"""
+        return self._planes
+
     def outliersRemoved(self):
-        """(source, target) points removed by the last removeStatisticalOutliers / removeRadiusOutliers / removeSmallClusters"""
+        """(source, target) points removed by the last removeStatisticalOutliers / removeRadiusOutliers / removeSmallClusters / removePlane"""
         return self._removed
 
     def estimateNormals(self):

@@ -184,6 +184,16 @@ public:
 	// cloud -- points closer than eps -- with fewer than min_size points goes.  A floating blob of a dozen points passes both filters
 	// above, because each of its points has close neighbours; this one removes it.
 	int removeSmallClusters(float eps, int min_size);
+	// The same edit for the dominant plane (symmicp_ctx_segment_plane: seed 0, one refit): the final inliers of the plane with the most
+	// points within max_dist go from EACH held cloud -- the floor or the table that joins the objects standing on it into one cluster.
+	// axis (null or all zero: none) and max_angle_deg restrict the planes to those whose normal lies within that angle of the axis.
+	// A cloud in which no plane reaches max(3, min_inliers) points loses nothing; that is not an error.  planeRemoved reports the two
+	// planes (n, d with n . x + d = 0 in the cloud's own coordinates; zeros for a cloud without one; either may be null).
+	int removePlane(float max_dist, int hypotheses = 1000, int min_inliers = 3, const float axis[3] = nullptr, float max_angle_deg = 0.f);
+	void planeRemoved(double src[4], double tgt[4]) const
+	{
+		for (int a = 0; a < 4; a++) { if (src) src[a] = planes_[0][a]; if (tgt) tgt[a] = planes_[1][a]; }
+	}
 	void outliersRemoved(size_t *src, size_t *tgt) const { if (src) *src = removed_src_; if (tgt) *tgt = removed_tgt_; }
 	const char *lastError() const { return error_.c_str(); }
 
@@ -232,6 +242,8 @@ private:
 	std::vector<symmicp_batch_result> multi_results_;
 	int best_start_ = -1;
 	size_t removed_src_ = 0, removed_tgt_ = 0;
-	int removeOutliers(int filter, int k, float std_mul, float radius, int min_neighbors);      // filter: 0 statistical, 1 radius, 2 small clusters
+	int removeOutliers(int filter, int k, float std_mul, float radius, int min_neighbors);      // filter: 0 statistical, 1 radius, 2 small clusters, 3 the plane of plane_cfg_
+	symmicp_plane_config plane_cfg_{};
+	double planes_[2][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}};
 	std::string error_;
 };

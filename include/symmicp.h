@@ -731,6 +731,90 @@ int symmicp_cluster(int device, const float *xyz, size_t row_stride, size_t col_
                     const symmicp_cluster_config *cfg, int32_t *labels_out, size_t *clusters_out, int32_t *sizes_out,
                     size_t cap, uint8_t *core_out, int32_t *neighbors_out);
 
+/* ---- RANSAC plane segmentation (PCL's SACSegmentation with SACMODEL_PLANE / SACMODEL_PERPENDICULAR_PLANE, Open3D's
+ * segment_plane; DESIGN.md 4, "Plane segmentation") ---------------------------------------------------------------------------
+ * The plane with the most points of a cloud within max_dist: the floor or the table that joins every object standing on it into one
+ * connected part, found and removed before the clustering above.  Defined by its arithmetic; the result is a function of the inputs
+ * alone, bit for bit on the device part.
+ *   Pivot.  c = the fp64 mean of the n points, summed in ascending row order, rounded to fp32; the device works on
+ *     p_i = xyz_i - c (fp32).
+ *   Samples.  Hypothesis h (0 <= h < hypotheses) draws the rows c_k = ((u(3h + k) >> 32) * n) >> 32, k = 0, 1, 2, where u is the
+ *     SplitMix64 sequence of (seed, stream 2): symmicp_ctx_ransac's (stream 0; symmicp_ctx_fgr has stream 1) with
+ *       base = mix64(seed * 0x9E3779B97F4A7C15 + 2 * 0xD1B54A32D192ED03 + 0x2545F4914F6CDD1D).
+ *     No rejection loop; every hypothesis gets a status, the checks in this order, with a, b, c = the sample's p, u = b - a,
+ *     v = c - a, w = u x v (fp32, unfused; dot(x, y) = (x0 y0 + x1 y1) + x2 y2):
+ *       1 REPEATED    two draws are equal
+ *       2 DEGENERATE  |w|^2 < 1e-4 |u|^2 |v|^2, or that product not > 0 (the sine bound of symmicp_ctx_ransac)
+ *       3 OFF_AXIS    only with an axis (below): |dot(n, a^)| < cos_min
+ *       0 EVALUATED
+ *   Hypothesis.  n = w / sqrt(|w|^2),  d = -dot(n, a).
+ *   Score.  inliers(h) = the number of rows i with fabsf(dot(n, p_i) + d) <= max_dist (fp32).  The winner is the evaluated
+ *     hypothesis with the most inliers, ties to the lowest h.  None evaluated, or a winner with fewer than max(3, min_inliers)
+ *     inliers: SYMMICP_ERR_NO_CONSENSUS, plane = 0, *count_out = 0 (result keeps best_hypothesis, evaluated and inliers_ransac;
+ *     rows_out and distance_out are not written).
+ *   Axis constraint (PCL's perpendicular-plane model: planes whose normal lies within max_angle_deg of an axis).  axis all zero:
+ *     off.  Otherwise a^ = axis normalised in fp64 (length = sqrt((x x + y y) + z z)) and rounded to fp32, and
+ *     cos_min = (float)cos(max_angle_deg * pi / 180) in fp64, 0 < max_angle_deg <= 90.
+ *   Refit.  `refits` times (0 .. 8), on the host in fp64 over the current inlier set (at first the winner's fp32 set) in ascending
+ *     row order, on x_i = xyz_i - (double)c, unfused: the mean m (sequential sums divided by the count k), the scatter matrix
+ *     sum (x - m)(x - m)^T (sequential), its eigenvectors by the cyclic Jacobi of the normals pre-step (at most 12 sweeps), n = the
+ *     eigenvector of the smallest eigenvalue (the lowest index among equal ones) divided by sqrt((n0 n0 + n1 n1) + n2 n2),
+ *     d = -dot(n, m); then the inlier set is recomputed in fp64: |dot(n, x_i) + d| <= (double)max_dist.  Fewer than
+ *     max(3, min_inliers) rows left: SYMMICP_ERR_NO_CONSENSUS as above.
+ *   Result.  Oriented so that dot(n, a^) >= 0 with an axis; otherwise the component of n with the largest magnitude (the lowest
+ *     axis among equal ones) is positive.  result->plane = (n, d - dot(n, (double)c)): the plane n . xyz + d = 0 in the caller's
+ *     coordinates, composed in fp64; plane4_out is its rounding to fp32.  With refits == 0 it is the winner's fp32 (n, d) widened.
+ *     distance_out[i] = dot(n, x_i) + d about the pivot, fp64, signed; rmse_final = sqrt of the mean of its square over the final
+ *     inlier set (sequential).
+ * Output.  plane4_out, result and *count_out are required.  rows_out [cap]: the final inlier rows in ascending order, *count_out
+ *   their number.  SYMMICP_ERR_SIZE when the count exceeds cap: everything but the rows is written -- call again with room (rows_out
+ *   may be NULL with cap == 0 to ask for the count).  distance_out [n], status_out [hypotheses] (uint8) and inliers_out
+ *   [hypotheses] (int32, 0 unless evaluated) may be NULL.
+ * SYMMICP_ERR_ARG, all decided on the host before a device is needed: NULL xyz / cfg / plane4_out / result / count_out; NULL
+ *   rows_out with cap > 0; n < 3 or n > 2^31 - 1; cfg->struct_size != sizeof(symmicp_plane_config); hypotheses outside 1 .. 2^24;
+ *   max_dist not finite and > 0; min_inliers < 0 or > n; refits outside 0 .. 8; a non-finite axis, or with an axis given a
+ *   max_angle_deg outside (0, 90]; non-finite coordinates.
+ * xyz strided as in symmicp_set_source.  The ctx form runs on the context's stream and arenas: the context's clouds, index,
+ * attributes, certificates and states stay exactly as they were.  A sharded job computes the full result on every rank (the
+ * output is deterministic). */
+typedef struct {
+    uint32_t struct_size;      /* = sizeof(symmicp_plane_config), checked */
+    uint32_t hypotheses;       /* H, 1 .. 2^24; default 1 000 */
+    uint64_t seed;
+    float    max_dist;         /* finite, > 0 (the caller sets it; default 0) */
+    int32_t  min_inliers;      /* 0 .. n; fewer than max(3, min_inliers) is no consensus; default 3 */
+    int32_t  refits;           /* 0 .. 8, default 1 */
+    float    axis[3];          /* all zero: no constraint */
+    float    max_angle_deg;    /* (0, 90] with an axis */
+    int32_t  reserved;
+} symmicp_plane_config;
+typedef struct {
+    int32_t best_hypothesis;   /* -1: none */
+    int32_t evaluated;         /* hypotheses with status EVALUATED */
+    int32_t inliers_ransac;    /* the winner's inliers (fp32, on the device) */
+    int32_t inliers_final;     /* after the refits */
+    double  rmse_final;        /* over the final inliers */
+    double  plane[4];          /* n, d in the caller's coordinates */
+} symmicp_plane_result;
+#define SYMMICP_PLANE_EVALUATED 0
+#define SYMMICP_PLANE_REPEATED 1
+#define SYMMICP_PLANE_DEGENERATE 2
+#define SYMMICP_PLANE_OFF_AXIS 3
+void symmicp_plane_config_default(symmicp_plane_config *cfg);
+int symmicp_ctx_segment_plane(symmicp_ctx *ctx, const float *xyz, size_t row_stride, size_t col_stride, size_t n,
+                              const symmicp_plane_config *cfg, float plane4_out[4], symmicp_plane_result *result,
+                              int32_t *rows_out, size_t cap, size_t *count_out, double *distance_out, uint8_t *status_out,
+                              int32_t *inliers_out);
+/* the same on a context of its own, created on `device` (-1 = current) and destroyed again */
+int symmicp_segment_plane(int device, const float *xyz, size_t row_stride, size_t col_stride, size_t n,
+                          const symmicp_plane_config *cfg, float plane4_out[4], symmicp_plane_result *result,
+                          int32_t *rows_out, size_t cap, size_t *count_out, double *distance_out, uint8_t *status_out,
+                          int32_t *inliers_out);
+/* test entry: the 4 floats (n, d about the pivot) the device computed for every hypothesis: hyp_out [hypotheses][4], written for
+ * status EVALUATED and OFF_AXIS, zero otherwise; status_out [hypotheses] and pivot_out [3] = c may be NULL.  Arguments as above. */
+int symmicp_ctx_plane_hypotheses(symmicp_ctx *ctx, const float *xyz, size_t row_stride, size_t col_stride, size_t n,
+                                 const symmicp_plane_config *cfg, float *hyp_out, uint8_t *status_out, float pivot_out[3]);
+
 /* ---- feature matching and RANSAC: global registration from FPFH features ("Feature matching and RANSAC") -------
  * All three run on the context's stream and temporary arena; the context's source, target, index and certificates stay exactly
  * as they were.  A sharded job computes the full result on every rank (the outputs are deterministic).
