@@ -108,22 +108,6 @@ __device__ __forceinline__ int32_t ndt_cell_row(const NdtGrid &g, float cx, floa
     return ndt_find(g, (uint32_t)(ix + (uint64_t)g.nx * (iy + (uint64_t)g.ny * iz)));
 }
 
-// block reduction of a weighted record: wave sums, then the waves' rows in a fixed order (as kernels_pass.hip's)
-__device__ __forceinline__ void ndt_block_reduce_store(AccN<kNAccW> &a, double *partials, uint32_t col)
-{
-    __shared__ double red[(kPassThreads / 64) * kNSum];
-    acc_wave_reduce(a, red + (threadIdx.x >> 6) * kNSum);
-    __syncthreads();
-    if (threadIdx.x < kNSum) {
-        double s = 0.0;
-        if (threadIdx.x < kNAccW) {
-#pragma unroll
-            for (int w = 0; w < kPassThreads / 64; w++) s += red[w * kNSum + threadIdx.x];
-        }
-        partials[(size_t)col * kNSum + threadIdx.x] = s;
-    }
-}
-
 // One source point per thread per trip.  Streaming: 12 B per point; per item one table probe (8 B, mostly one) and the voxel's record as
 // four 16-byte loads -- a Morton-sorted share keeps neighbouring lanes in the same few voxels, so the records come out of L1 / L2 --
 // and 84 fp64 FMAs (three acc_row of 28).
@@ -176,7 +160,7 @@ __global__ __launch_bounds__(kPassThreads) void k_pass_ndt(NdtPassArgs a)
             acc_pair_sums(acc, px, py, pz, mx, my, mz, d2, w);
         }
     }
-    ndt_block_reduce_store(acc, a.partials, blockIdx.x);
+    acc_block_reduce_store(acc, a.partials, blockIdx.x);      // (pass_rows.h: the weighted record, as the pass kernels sum it)
 }
 
 __global__ __launch_bounds__(256) void k_ndt_corr(NdtPassArgs a, const uint32_t *__restrict__ order, int32_t *__restrict__ idx_out,

@@ -29,7 +29,7 @@
 // that reaches a strictly smaller d2 and flags equal distances; a flagged group of points is scanned again with the row
 // comparison (rare).
 // CERT: scan everything within (nearest + pad) and keep the second-nearest distance, so that the result carries a pair
-// certificate (see k_search_cells in kernels_pass.hip).
+// certificate (see pair_search.h).
 #include <cstdlib>
 #include "symmicp_internal.h"
 #include "device_common.h"

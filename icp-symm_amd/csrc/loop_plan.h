@@ -1,7 +1,7 @@
 // loop_plan.h -- the scheduling rules of the ICP loop as plain functions over plain values: what a pass tells the next one (PassFeedback and
 // the two record slots that carry it), the grid sizes, the plan of one TREE pass, when a device-driven run may start and how it is cut
 // into chunks.  engine_loop.cpp launches what these functions decide ("Converged passes", describes the loop); the two
-// reduce kernels of kernels_pass.hip share the slot codec.  Plain C++17: no HIP header, no context, so that a host program can call
+// reduce kernels of kernels_reduce.hip share the slot codec.  Plain C++17: no HIP header, no context, so that a host program can call
 // every rule (tests/cpp/loop_plan.cpp).
 #pragma once
 #include <math.h>

@@ -1,5 +1,5 @@
 // oct_walk.h -- exact per-thread walk of the sparse octree (TargetIndex::onodes), shared by k_search_walk
-// (kernels_pass.hip) and the packet search's per-lane regime (kernels_packet.hip).
+// (kernels_search.hip) and the packet search's per-lane regime (kernels_packet.hip).
 #pragma once
 #include "symmicp_internal.h"
 #include "device_common.h"

@@ -1,8 +1,9 @@
 // pass_rows.h -- the rows of one pair and the wave-level sum of a record: what every accumulating kernel shares.
 //
-// Included by kernels_pass.hip (the pass kernels of the big pair) and kernels_batch.hip (one workgroup per small problem): the
-// accumulators, the per-mode rows (acc_pair / acc_plane / acc_gicp / acc_color), the gates (pair_step) and the wave64 sum of the
-// 37 accumulators live here ONCE, so both translation units form a pair's terms from the same source.
+// Included by kernels_pass.hip (the pass kernels of the big pair), kernels_batch.hip (one workgroup per small problem) and
+// kernels_ndt.hip: the accumulators, the per-mode rows (acc_pair / acc_plane / acc_gicp / acc_color), the gates (pair_step), the
+// source row of a pair (load_src_row, transform_point, write_back), the wave64 sum of the 37 accumulators and the block's record
+// (acc_block_reduce_store) live here ONCE, so every translation unit forms a pair's terms from the same source.
 //
 // fp32 expressions here must stay UNFUSED (the including file is compiled with -ffp-contract=off and carries
 // `#pragma clang fp contract(off)`) and keep the association written: the CPU oracle and tests/_record_ref.py use the same
@@ -228,7 +229,18 @@ __device__ __forceinline__ void acc_obj(AccN<NA> &acc, float px, float py, float
     else acc_pair(acc, px, py, pz, npx, npy, npz, qx, qy, qz, nqx, nqy, nqz, d2, pivot, p2p, loss, scale);
 }
 
-// What the pair step reads of the pass's arguments.  k_pass_fused fills it through in_vgpr (see there); the other kernels take it as
+// k_pass_fused holds what its streaming loop needs of its arguments (HotParams) in VECTOR registers.  The kernel's three argument structs are ~150
+// scalars, all live across the loop (the scan behind it needs them); with 102 scalar registers per wave the compiler parked them in the
+// lanes of a vector register and fetched them back one v_readlane at a time: 85 of the loop's 291 vector instructions per tile.  Values
+// that pass through in_vgpr are opaque to it: they stay where they are (and VGPR operands issue faster than scalar ones).
+template <typename T>
+__device__ __forceinline__ T in_vgpr(T v)
+{
+    asm volatile("" : "+v"(v));
+    return v;
+}
+
+// What the pair step reads of the pass's arguments.  k_pass_fused fills it through in_vgpr; the other kernels take it as
 // it is (hot_params).
 struct HotParams {
     Affine X;
@@ -251,12 +263,59 @@ __device__ __forceinline__ HotParams hot_params(const PassArgs &a)
     return h;
 }
 
+// The transform of a device-driven loop, as k_reduce_solve left it in the loop state, into h.X: vector loads through a pointer the
+// compiler cannot see through, so that the transform arrives in VGPRs (in_vgpr).  The caller looks at it behind its first tile's loads.
+__device__ __forceinline__ void loop_transform(HotParams &h, const LoopState *loop)
+{
+    const float4 *xp = reinterpret_cast<const float4 *>(&in_vgpr(loop)->Xapply);
+    const float4 r0 = xp[0], r1 = xp[1], r2 = xp[2];
+    h.X.m[0] = r0.x; h.X.m[1] = r0.y; h.X.m[2] = r0.z; h.X.m[3] = r0.w;
+    h.X.m[4] = r1.x; h.X.m[5] = r1.y; h.X.m[6] = r1.z; h.X.m[7] = r1.w;
+    h.X.m[8] = r2.x; h.X.m[9] = r2.y; h.X.m[10] = r2.z; h.X.m[11] = r2.w;
+    h.X.nrm_w = reinterpret_cast<const float *>(xp)[12];
+}
+
 // Does an instantiation read the source normals?  Every record but PLANE's and COLOR's uses them; those read them only to write them
 // back or to gate on them (min_normal_dot).
 template <int OBJ>
 __device__ __forceinline__ bool reads_src_normals(bool writeback, float min_ndot)
 {
     return (OBJ != kObjPlane && OBJ != kObjColor) || writeback || min_ndot > -1.0f;
+}
+
+// A source row as stored: the position and the normal -- zeros where the instantiation does not read the normals (need_n =
+// reads_src_normals): pair_step and write_back take them as they are
+struct SrcRow {
+    float3 p, n;
+};
+
+__device__ __forceinline__ float3 load_src_normal(const CloudSoA &in, uint32_t i, bool need_n)
+{
+    float3 n = make_float3(0.0f, 0.0f, 0.0f);
+    if (need_n) { n.x = in.nx[i]; n.y = in.ny[i]; n.z = in.nz[i]; }
+    return n;
+}
+
+__device__ __forceinline__ SrcRow load_src_row(const CloudSoA &in, uint32_t i, bool need_n)
+{
+    SrcRow r;
+    r.p = make_float3(in.x[i], in.y[i], in.z[i]);
+    r.n = load_src_normal(in, i, need_n);
+    return r;
+}
+
+// applyTransform (func.cpp:104-121) of a position
+__device__ __forceinline__ float3 transform_point(const Affine &X, float3 p)
+{
+    return make_float3(xf_row(X.m + 0, p.x, p.y, p.z, 1.0f), xf_row(X.m + 4, p.x, p.y, p.z, 1.0f), xf_row(X.m + 8, p.x, p.y, p.z, 1.0f));
+}
+
+// the optional write-back of a pass: the moved position p of row i, and its normal n_in moved by a.X
+__device__ __forceinline__ void write_back(const PassArgs &a, uint32_t i, float3 p, float3 n_in)
+{
+    a.out.x[i] = p.x; a.out.y[i] = p.y; a.out.z[i] = p.z;
+    a.out.nx[i] = xf_row(a.X.m + 0, n_in.x, n_in.y, n_in.z, a.X.nrm_w); a.out.ny[i] = xf_row(a.X.m + 4, n_in.x, n_in.y, n_in.z, a.X.nrm_w);
+    a.out.nz[i] = xf_row(a.X.m + 8, n_in.x, n_in.y, n_in.z, a.X.nrm_w);
 }
 
 // The pair step of every accumulating kernel: the gates (max_correspondence_distance, then min_normal_dot), then the record.  (nx, ny, nz)
@@ -288,6 +347,18 @@ __device__ __forceinline__ ColorPair color_pair(const PassArgs &a, uint32_t i, u
     c.ip = a.src_int[i];
     c.lam = a.color_lam; c.om = a.color_om;
     return c;
+}
+
+// The pair step of source row i with target j (a row, or a sorted position: whatever the kernel's tgt_color is indexed by): COLOR's
+// instantiations gather the pair's extra data here, the others take none
+template <int OBJ, bool T = false, int NA>
+__device__ __forceinline__ void pair_step_at(AccN<NA> &acc, const HotParams &h, const PassArgs &a, uint32_t i, uint32_t j, float3 n, float3 p,
+                                             const float4 &q, const float4 &nq, float d2, uint32_t tau)
+{
+    if constexpr (OBJ == kObjColor) {
+        const ColorPair cp = color_pair(a, i, j);
+        pair_step<OBJ, T>(acc, h, n.x, n.y, n.z, p.x, p.y, p.z, q, nq, d2, tau, &cp);
+    } else pair_step<OBJ, T>(acc, h, n.x, n.y, n.z, p.x, p.y, p.z, q, nq, d2, tau);
 }
 
 // one step of a sum on the VALU's DPP cross-lane network (no LDS traffic): row_shr 1,2,4,8 builds 16-lane row sums.  A double moves
@@ -340,6 +411,26 @@ __device__ __forceinline__ void acc_wave_reduce(AccN<NA> &a, double *red_wave)
         x = dpp_add_f64<0x114, 0xf>(x);      // row_shr:4
         x = dpp_add_f64<0x118, 0xf>(x);      // row_shr:8  -> lane 15 of each row holds the row sum
         if ((lane & 15) == 15) red_wave[k + 10 * (lane >> 4)] = x;
+    }
+}
+
+// block reduction: wave sums, then LDS across the 4 waves; fixed order -> deterministic.
+// record k of block b lands at partials[b * kNSum + k]: one contiguous 320-byte burst per block.  (Round 2 stored it transposed,
+// [k][block], so that the reduce could read along the blocks: 40 scattered 8-byte stores per block into lines shared with up to 15
+// other blocks -- on other XCDs, i.e. other L2s -- and a reduce whose load phase alone took 5.9 us of k_reduce_solve's 11.5.)
+template <int NA>
+__device__ __forceinline__ void acc_block_reduce_store(AccN<NA> &a, double *partials, uint32_t col)
+{
+    __shared__ double red[(kPassThreads / 64) * kNSum];
+    acc_wave_reduce(a, red + (threadIdx.x >> 6) * kNSum);
+    __syncthreads();
+    if (threadIdx.x < kNSum) {
+        double s = 0.0;
+        if (threadIdx.x < NA) {
+#pragma unroll
+            for (int w = 0; w < kPassThreads / 64; w++) s += red[w * kNSum + threadIdx.x];
+        }
+        partials[(size_t)col * kNSum + threadIdx.x] = s;
     }
 }
 

@@ -1,7 +1,7 @@
 // solve_core.h -- the O(1) part of estimateTransformSymm (reference ICP/func.cpp:76-102): from one 40-double
 // reduction record to the 4x4 increment.  ONE source for both sides: host_solve.cpp wraps these functions for the host
 // (the tested reference, north_star: "the 6x6 solve stays on the host"), and k_final_reduce calls the same code on the
-// device so that a converged alignment can run pass after pass without a host round trip (kernels_pass.hip).
+// device so that a converged alignment can run pass after pass without a host round trip (kernels_reduce.hip).
 //
 // The reference solves two N x 3 least-squares problems with a JacobiSVD pseudo-inverse (func.cpp:64-73, :87-88).  For
 // full column rank that is the normal-equation solution, and the normal-equation blocks (M^T M, N^T N, M^T N, M^T c,

@@ -200,7 +200,7 @@ struct PassArgs {
     int32_t budget_walk;                // this pass's thread-per-query walk runs with a visit budget + retry launch (see k_search_walk)
     int32_t refresh_records;            // k_accumulate may replace stale copies (0 in a pass that may still be repaired)
     float4 *cert;                       // per pair: (ref.xyz, clear radius L around ref; L <= 0: no single certificate); bit 0 of L's word: certk[i] is valid
-    uint4 *certk;                       // per pair, 2 x uint4: the neighbourhood certificate's members (8 sorted positions; see hood_test in kernels_pass.hip)
+    uint4 *certk;                       // per pair, 2 x uint4: the neighbourhood certificate's members (8 sorted positions; see hood_test in pair_search.h)
     float2 *hoodr;                      // ... its radius T and the radius hint for the pair's next scan
     int32_t make_hood;                  // k_search_cells keeps neighbourhoods in this pass (existing ones are honoured either way)
     int32_t use_slack;                  // 0 on the first pass of an alignment (certificates not valid yet)
@@ -262,7 +262,7 @@ struct BatchArgs {
 };
 void launch_batch_align(const BatchArgs &a, uint32_t n_problems, hipStream_t s);
 
-// ---- kernel launchers (kernels.hip) ---------------------------------------
+// ---- kernel launchers (kernels_pass.hip, kernels_search.hip, kernels_reduce.hip) ---------------------------------------
 void launch_pass_identity(const PassArgs &a, CloudSoA tgt, int blocks, bool vec4_ok, hipStream_t s);
 void launch_pass_indexed(const PassArgs &a, const float4 *tn /* pair records */, int blocks, hipStream_t s);
 // ev: null, or 5 events recorded before cells / after cells / (same again) / after walk / after accumulate
@@ -272,12 +272,17 @@ void launch_pass_indexed(const PassArgs &a, const float4 *tn /* pair records */,
 void launch_pass_tree_split(const PassArgs &a, const TargetIndex &ix, const WorkLists &wl, int acc_blocks, uint32_t walk_blocks,
                             int stage, int compact_blocks, const PassTuning &tune, hipStream_t s, hipEvent_t *ev);
 void launch_pass_tree_first(const PassArgs &a, const TargetIndex &ix, const WorkLists &wl, int acc_blocks, hipStream_t s, hipEvent_t *ev);
+// the search kernels behind launch_pass_tree_split and launch_loop_stragglers (kernels_search.hip): k_search_cells; k_search_walk on the work
+// list (and the retry list); the walk of the straggler stage
+void launch_search_cells(const PassArgs &a, const TargetIndex &ix, const WorkLists &wl, const PassTuning &tune, hipStream_t s);
+void launch_search_walk(const PassArgs &a, const TargetIndex &ix, const WorkLists &wl, uint32_t walk_blocks, const PassTuning &tune, hipStream_t s);
+void launch_straggler_walk(const PassArgs &a, const TargetIndex &ix, const WorkLists &wl, const PassTuning &tune, hipStream_t s);
 uint32_t walk_blocks_full(const WorkLists &wl);
 uint32_t shard_capacity(uint32_t n_points);
 // keep_nonempty: leave the append-list counters alone when the work list is not empty (stage-1 passes)
 void launch_final_reduce(const double *partials, int blocks, double *out_dev, double *out_host_mapped, uint32_t *ticket,
                          unsigned long long seq, uint32_t *counters_to_clear, int keep_nonempty, hipStream_t s);
-// fused pass of a converged alignment (k_pass_fused) and the device-side end of a pass (k_reduce_solve): see kernels_pass.hip
+// fused pass of a converged alignment (k_pass_fused) (kernels_pass.hip) and the device-side end of a pass (k_reduce_solve, kernels_reduce.hip)
 void launch_pass_fused(const PassArgs &a, const TargetIndex &ix, const WorkLists &wl, int blocks, hipStream_t s);
 // ... the same pass for a chunk in which no pair needs a scan (k_pass_certified): an unsettled pair makes the pass incomplete (LOOP_REDO_PASS)
 void launch_pass_certified(const PassArgs &a, const TargetIndex &ix, const WorkLists &wl, int blocks, hipStream_t s);

@@ -182,6 +182,41 @@ def test_tree_follows_previous_pairs_across_iterations(sym, oracle):
             assert np.array_equal(idx, ri) and np.array_equal(d2, rd)
 
 
+def test_crowded_cells_in_later_passes(sym, oracle):
+    """Crowded cells in the scans of the later passes (scan_round in pair_search.h): a thread scans at most 16 points of a (query,
+    cell) item itself and hands the rest of the cell over in chunks of 16, as sub-items that the whole block scans afterwards.  A
+    cluster of 48 target points within 1e-3 of one spot of a plane patch puts more than 32 points -- two sub-items at least -- into
+    one grid cell, and 64 of the source points lie within 0.02 of it: their bounded scans reach that cell in every pass.  Every
+    pass's pairs must be brute force's, index and distance, bit for bit."""
+    rng = np.random.default_rng(11)
+    spot = np.float32([0.3137, 0.6291, 0.0])
+    patch = np.concatenate([rng.random((4096, 2), dtype=np.float32), np.zeros((4096, 1), np.float32)], 1)
+    tgt = np.concatenate([patch, spot + rng.uniform(-1e-3, 1e-3, (48, 3)).astype(np.float32) / np.float32(np.sqrt(3.0))]).astype(np.float32)
+    tgt = tgt[rng.permutation(len(tgt))]
+    near = rng.uniform(-0.02, 0.02, (64, 2)).astype(np.float32) / np.float32(np.sqrt(2.0))
+    src = np.concatenate([rng.random((960, 2), dtype=np.float32), spot[:2] + near])
+    src = np.concatenate([src, np.full((1024, 1), 0.01, np.float32)], 1).astype(np.float32)
+    up = lambda n: np.tile(np.float32([0, 0, 1]), (n, 1))
+    with sym.Engine(mode=sym.MODE_P2P, corr=sym.CORR_TREE, apply=sym.APPLY_INCREMENTAL) as e:
+        e.set_target(tgt, up(len(tgt)))
+        e.set_source(src, up(len(src)))
+        e.begin()
+        # precondition, from the grid the index chose: some cell holds more than 32 target points (else no sub-item is ever made)
+        info = e.index_info()
+        assert info["grid_level"] > 0
+        cell = np.floor((tgt - info["origin"]) * info["inv_h"]).astype(np.int64)
+        assert cell.min() >= 0 and cell.max() < info["gdim"]
+        _, per_cell = np.unique(cell, axis=0, return_counts=True)
+        assert per_cell.max() > 32, (per_cell.max(), info["grid_level"], info["h"])
+        for it in range(4):          # the first pass, then three more
+            if it:
+                e.step()
+            idx, d2 = e.correspondences()
+            p, _ = e.source()
+            ri, rd = oracle.nn_brute(p, tgt)
+            assert np.array_equal(idx, ri) and np.array_equal(d2, rd), (it, np.nonzero(idx != ri)[0][:5])
+
+
 # ----------------------------------------------------------------------------------------------
 # a1 + a4 + a5 + a7: the whole RegisterSymm loop (myicp.cpp:100-150)
 # ----------------------------------------------------------------------------------------------
@@ -1051,7 +1086,7 @@ def test_pair_certificates_stay_exact_under_small_and_large_moves(sym, oracle):
 
 @pytest.mark.parametrize("workload", ["c4", "c5"])
 def test_neighbourhood_certificates_hold_what_they_claim(sym, oracle, workload):
-    """Neighbourhood certificates (hood_test in kernels_pass.hip): a scan keeps every target point closer to the query's
+    """Neighbourhood certificates (hood_test in pair_search.h): a scan keeps every target point closer to the query's
     reference position than T; later passes decide the pair among those points alone.  Let an alignment converge from the
     identity (its later passes drift by fractions of the point spacing: single certificates run out of room and the
     neighbourhoods take over), check every pass against
