@@ -45,6 +45,9 @@
 //     --init-keypoints iss     match and run RANSAC on the ISS keypoints of both clouds only (features still come from the full clouds)
 //     --iss-radius R           their salient radius (required with --init-keypoints iss; some 6 point spacings)
 //     --iss-nms-radius R2      their non-maximum radius (default: two thirds of R)   --iss-min-neighbors K   (default 5)
+//     --orient-normals K       the normals this program estimates (for the alignment, and for --init global / fgr) are oriented consistently
+//                              over each cloud's K-NN graph (3 .. 16; symmicp_ctx_orient_normals, viewpoint at the origin): two scans of one
+//                              surface then agree on the side their normals point to, which FPFH matching needs
 //     --evaluate D             after the result block, one line with the result's fitness, inlier RMSE and inliers / source points at
 //                              distance D (> 0) on the full clouds: the share of source points with a target point within D
 //     --information            with --evaluate: also the six rows of the 6x6 information matrix (rotation first, about the origin)
@@ -78,7 +81,7 @@
 static int usage(const char *argv0, const char *complaint)
 {
     std::fprintf(stderr, "%s\nusage: %s [--mode quirks|paper|plane|gicp|color|ndt] [--ndt-resolution L] [--ndt-neighbors 1|7] [--ndt-min-points N] [--ndt-level L:ITERS]... [--color-weight L] [--corr identity|tree] [--iters N] [--threshold D] [--loss none|huber|tukey|cauchy|gm]"
-                 " [--loss-scale S] [--gicp-epsilon E] [--max-dist D] [--trim F] [--one-to-one] [--reciprocal] [--median-factor F] [--scale LEAF:ITERS[:MAXDIST]]... [--init global --fpfh-radius R --ransac-dist D [--ransac-iters H] [--seed S] [--init-voxel L] [--init-keypoints iss --iss-radius R [--iss-nms-radius R2] [--iss-min-neighbors K]]] [--init fgr --fpfh-radius R --fgr-dist D [--fgr-iters N] [--fgr-tuples N] [--seed S] [--init-voxel L] [--init-keypoints iss ...]] [--evaluate D [--information]] [--sor K:S] [--ror R:M] [--remove-plane D[:H[:MIN]] [--plane-axis X,Y,Z:DEG]] [--min-cluster EPS:M] [--out file.pcd] [--quiet] [source.pcd target.pcd]\n",
+                 " [--loss-scale S] [--gicp-epsilon E] [--max-dist D] [--trim F] [--one-to-one] [--reciprocal] [--median-factor F] [--scale LEAF:ITERS[:MAXDIST]]... [--init global --fpfh-radius R --ransac-dist D [--ransac-iters H] [--seed S] [--init-voxel L] [--init-keypoints iss --iss-radius R [--iss-nms-radius R2] [--iss-min-neighbors K]]] [--init fgr --fpfh-radius R --fgr-dist D [--fgr-iters N] [--fgr-tuples N] [--seed S] [--init-voxel L] [--init-keypoints iss ...]] [--orient-normals K] [--evaluate D [--information]] [--sor K:S] [--ror R:M] [--remove-plane D[:H[:MIN]] [--plane-axis X,Y,Z:DEG]] [--min-cluster EPS:M] [--out file.pcd] [--quiet] [source.pcd target.pcd]\n",
                  complaint, argv0);
     return 64;
 }
@@ -89,6 +92,7 @@ int main(int argc, char **argv)
     std::string out_path;
     MyICP icp;
     bool quirks = true;                      // (the class default)
+    int orient_k = 0;
     symmicp_loss loss = SYMMICP_LOSS_NONE;
     float loss_scale = 0.f;
     bool have_scale = false;
@@ -279,6 +283,10 @@ int main(int argc, char **argv)
         else if (a == "--iss-radius") { number("--iss-radius", value("--iss-radius"), ginit.iss_salient_radius); have_iss_option = true; }
         else if (a == "--iss-nms-radius") { number("--iss-nms-radius", value("--iss-nms-radius"), ginit.iss_non_max_radius); have_iss_option = true; }
         else if (a == "--iss-min-neighbors") { ginit.iss_min_neighbors = std::atoi(value("--iss-min-neighbors")); have_iss_option = true; }
+        else if (a == "--orient-normals") {
+            orient_k = std::atoi(value("--orient-normals"));
+            if (orient_k < 3 || orient_k > 16) return usage(argv[0], "--orient-normals needs K in 3 .. 16");
+        }
         else if (a == "--seed") { ginit.seed = std::strtoull(value("--seed"), nullptr, 10); have_init_option = true; }
         else if (a == "--evaluate") {
             number("--evaluate", value("--evaluate"), eval_dist);
@@ -412,6 +420,8 @@ int main(int argc, char **argv)
         if (!tree) return usage(argv[0], "--scale needs --corr tree (identity pairing cannot pair clouds of different sizes)");
         icp.setVoxelLevels(levels);
     }
+    icp.setOrientNormals(orient_k);
+    ginit.orient_k = orient_k;
     if (init_global) {
         const bool fgr = ginit.method == MyICP::GlobalInit::FGR;
         if (have_fgr_option && !fgr) return usage(argv[0], "--fgr-dist, --fgr-iters and --fgr-tuples need --init fgr");

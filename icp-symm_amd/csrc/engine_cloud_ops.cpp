@@ -2,6 +2,7 @@
 // intensity gradient of colored ICP, voxel-grid downsampling.  Each runs on a context the caller owns (symmicp_ctx_*), whose target,
 // source, index and certificates stay as they are, or as a one-shot on a context of its own (with_own_context).
 #include "engine_internal.h"
+#include "orient_core.h"
 
 // ---- the scratch index of an operation ------------------------------------------------------------------------------------
 // The caller's cloud uploaded and a box tree built over its Morton order, behind the target's arrays in the keep-arena; the destructor
@@ -521,6 +522,149 @@ int symmicp_cluster(int device, const float *xyz, size_t row_stride, size_t col_
     if (cluster_args_error(xyz, row_stride, col_stride, n, cfg, labels_out, clusters_out, sizes_out, cap)) return SYMMICP_ERR_ARG;
     return with_own_context(device, [&](symmicp_ctx *c) {
         return symmicp_ctx_cluster(c, xyz, row_stride, col_stride, n, cfg, labels_out, clusters_out, sizes_out, cap, core_out, neighbors_out);
+    });
+}
+
+// ---- consistent normal orientation (kernels_orient.hip, orient_core.h; DESIGN.md 4, "Normal orientation") ----------------------------
+// Like the intensity gradient below: the cloud's own scratch index and the exact k-NN walk (launch_knn), then Boruvka rounds over those
+// lists.  The host reads one word per round (the hooks so far) and stops at a round without any; the counts of the result are O(n) over
+// the read-back flags and components, on the host.
+static const char *orient_args_error(const float *xyz, size_t xr, size_t xc, const float *nrm, size_t nr, size_t nc, size_t n,
+                                     const symmicp_orient_config *cfg, const float *nrm_out, const int32_t *tree_out, const size_t *tree_count)
+{
+    if (!xyz || !nrm || !cfg || !nrm_out) return "orient_normals: xyz, nrm, cfg and nrm_out are required";
+    if (tree_out && !tree_count) return "orient_normals: tree_out needs tree_count";
+    if (n == 0 || n > 0x7fffffffull) return "orient_normals: n must be in 1 .. 2^31 - 1";
+    if (cfg->struct_size != sizeof(symmicp_orient_config)) return "orient_normals: cfg->struct_size is not sizeof(symmicp_orient_config)";
+    if (cfg->k < 3 || cfg->k > 16 || (size_t)cfg->k > n) return "orient_normals: k must be in 3 .. 16 and <= n";
+    if (cfg->seed_rule != SYMMICP_ORIENT_VIEWPOINT && cfg->seed_rule != SYMMICP_ORIENT_DIRECTION) return "orient_normals: unknown seed_rule";
+    if (!std::isfinite(cfg->ref[0]) || !std::isfinite(cfg->ref[1]) || !std::isfinite(cfg->ref[2])) return "orient_normals: ref is not finite";
+    if (cfg->seed_rule == SYMMICP_ORIENT_DIRECTION && cfg->ref[0] == 0.f && cfg->ref[1] == 0.f && cfg->ref[2] == 0.f)
+        return "orient_normals: the direction is zero";
+    if (!coords_finite(xyz, xr, xc, n)) return "orient_normals: a coordinate is not finite";
+    if (!coords_finite(nrm, nr, nc, n)) return "orient_normals: a normal is not finite";
+    return nullptr;
+}
+
+void symmicp_orient_config_default(symmicp_orient_config *cfg)
+{
+    if (!cfg) return;
+    std::memset(cfg, 0, sizeof(*cfg));
+    cfg->struct_size = (uint32_t)sizeof(*cfg);
+    cfg->k = 16;      // (the cat of tests/golden is one component at 16 and four at 10)
+    cfg->seed_rule = SYMMICP_ORIENT_VIEWPOINT;
+}
+
+int symmicp_ctx_orient_normals(symmicp_ctx *c, const float *xyz, size_t xyz_row_stride, size_t xyz_col_stride, const float *nrm,
+                               size_t nrm_row_stride, size_t nrm_col_stride, size_t n, const symmicp_orient_config *cfg, float *nrm_out,
+                               uint8_t *flip_out, int32_t *component_out, int32_t *tree_out, size_t *tree_count, symmicp_orient_result *result)
+{
+    if (!c) return SYMMICP_ERR_ARG;
+    if (const char *msg = orient_args_error(xyz, xyz_row_stride, xyz_col_stride, nrm, nrm_row_stride, nrm_col_stride, n, cfg, nrm_out, tree_out,
+                                            tree_count))
+        return fail(c, SYMMICP_ERR_ARG, msg);
+    if (tree_count) *tree_count = 0;
+    const int k = cfg->k;
+    const uint32_t n32 = (uint32_t)n;
+    // both clouds packed by row: the kernels gather normals by the rows the neighbour lists name
+    std::vector<float> rows(6 * n);
+    for (size_t i = 0; i < n; i++)
+        for (int a = 0; a < 3; a++) {
+            rows[3 * i + a] = xyz[i * xyz_row_stride + a * xyz_col_stride];
+            rows[3 * n + 3 * i + a] = nrm[i * nrm_row_stride + a * nrm_col_stride];
+        }
+    std::vector<uint8_t> flip(n);
+    std::vector<int32_t> comp(n);
+    unsigned long long graph_edges = 0;
+    uint32_t hooked = 0;
+    int rounds = 0;
+    {
+        ScratchIndex si;
+        if (int st = si.begin(c, xyz, xyz_row_stride, xyz_col_stride, nullptr, 0, 0, n, n * (16 * (size_t)k + 96) + 65536)) return st;
+        DevBuf<int32_t> d_knn, d_tree, d_comp;
+        DevBuf<float> d_d2, d_rows, d_out;
+        DevBuf<uint32_t> d_erow, d_eww, d_words, d_mid, d_hi, d_small;
+        DevBuf<unsigned long long> d_best;
+        DevBuf<uint8_t> d_flip;
+        HIP_TRY(c, d_best.alloc_temp(c->arena, n + 1));      // [n] the slots, [n] the edge count
+        HIP_TRY(c, d_knn.alloc_temp(c->arena, n * (size_t)k));
+        HIP_TRY(c, d_d2.alloc_temp(c->arena, n * (size_t)k));
+        HIP_TRY(c, d_erow.alloc_temp(c->arena, n * (size_t)k));
+        HIP_TRY(c, d_eww.alloc_temp(c->arena, n * (size_t)k));
+        HIP_TRY(c, d_rows.alloc_temp(c->arena, 6 * n));
+        HIP_TRY(c, d_out.alloc_temp(c->arena, 3 * n));
+        HIP_TRY(c, d_words.alloc_temp(c->arena, n));
+        HIP_TRY(c, d_mid.alloc_temp(c->arena, n));
+        HIP_TRY(c, d_hi.alloc_temp(c->arena, n));
+        HIP_TRY(c, d_tree.alloc_temp(c->arena, 2 * n));
+        HIP_TRY(c, d_comp.alloc_temp(c->arena, n));
+        HIP_TRY(c, d_small.alloc_temp(c->arena, 2));         // [0] the hooks so far, [1] the walk guard
+        HIP_TRY(c, d_flip.alloc_temp(c->arena, n));
+        const float *d_xyz = d_rows.p, *d_nrm = d_rows.p + 3 * n;
+        unsigned long long *d_edges = d_best.p + n;
+        HIP_TRY(c, hipMemcpyAsync(d_rows.p, rows.data(), sizeof(float) * 6 * n, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipMemsetAsync(d_edges, 0, sizeof(unsigned long long), c->stream));
+        HIP_TRY(c, hipMemsetAsync(d_small.p, 0, 2 * sizeof(uint32_t), c->stream));
+        launch_knn(si.ix, k, d_knn.p, d_d2.p, c->stream);
+        launch_orient_edges(d_knn.p, d_nrm, n32, k, d_erow.p, d_eww.p, d_edges, d_words.p, c->stream);
+        for (int round = 0;; round++) {
+            if (round > symmicp::orient::kMaxRounds) return fail(c, SYMMICP_ERR_INTERNAL, "orient_normals: more than 32 rounds");
+            launch_orient_round(d_erow.p, d_eww.p, d_words.p, d_mid.p, n32, k, d_best.p, d_hi.p, d_nrm, d_tree.p, d_small.p, c->stream);
+            uint32_t state[2] = {0, 0};
+            HIP_TRY(c, hipMemcpyAsync(state, d_small.p, sizeof(state), hipMemcpyDeviceToHost, c->stream));
+            if (int st = stream_done(c)) return st;
+            if (state[1]) return fail(c, SYMMICP_ERR_INTERNAL, "orient_normals: a walk up the parents exceeded the hooks of its round");
+            if (state[0] >= n32) return fail(c, SYMMICP_ERR_INTERNAL, "orient_normals: more tree edges than a forest has");
+            const uint32_t hooks = state[0] - hooked;
+            hooked = state[0];
+            if (hooks == 0) break;
+            rounds++;
+            launch_orient_flatten(d_mid.p, d_words.p, n32, hooks + 1, d_small.p + 1, c->stream);
+        }
+        // the slots of the rounds are free now: min_row <- d_hi, seed_key <- d_best, root_flip <- d_mid
+        launch_orient_finish(d_words.p, d_xyz, d_nrm, n32, cfg->seed_rule, cfg->ref, d_hi.p, d_best.p, d_mid.p, d_out.p, d_flip.p, d_comp.p, c->stream);
+        HIP_TRY(c, hipGetLastError());
+        HIP_TRY(c, hipMemcpyAsync(nrm_out, d_out.p, sizeof(float) * 3 * n, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(flip.data(), d_flip.p, n, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(comp.data(), d_comp.p, sizeof(int32_t) * n, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(&graph_edges, d_edges, sizeof(graph_edges), hipMemcpyDeviceToHost, c->stream));
+        if (tree_out && hooked) HIP_TRY(c, hipMemcpyAsync(tree_out, d_tree.p, sizeof(int32_t) * 2 * hooked, hipMemcpyDeviceToHost, c->stream));
+        if (int st = stream_done(c)) return st;
+    }
+    if (tree_count) *tree_count = hooked;
+    std::vector<uint32_t> size(n, 0);
+    uint64_t components = 0, largest = 0, flipped = 0;
+    for (size_t i = 0; i < n; i++) {
+        if (comp[i] < 0 || (size_t)comp[i] > i) return fail(c, SYMMICP_ERR_INTERNAL, "orient_normals: a row's component is not its lowest row");
+        components += (size_t)comp[i] == i ? 1 : 0;
+        const uint64_t s = ++size[(size_t)comp[i]];
+        largest = s > largest ? s : largest;
+        flipped += flip[i];
+    }
+    if (components + hooked != n) return fail(c, SYMMICP_ERR_INTERNAL, "orient_normals: tree edges and components do not add up to n");
+    if (flip_out) std::memcpy(flip_out, flip.data(), n);
+    if (component_out) std::memcpy(component_out, comp.data(), sizeof(int32_t) * n);
+    if (result) {
+        std::memset(result, 0, sizeof(*result));
+        result->graph_edges = graph_edges;
+        result->tree_edges = hooked;
+        result->components = components;
+        result->largest_component = largest;
+        result->flipped = flipped;
+        result->rounds = rounds;
+    }
+    return SYMMICP_OK;
+}
+
+int symmicp_orient_normals(int device, const float *xyz, size_t xyz_row_stride, size_t xyz_col_stride, const float *nrm, size_t nrm_row_stride,
+                           size_t nrm_col_stride, size_t n, const symmicp_orient_config *cfg, float *nrm_out, uint8_t *flip_out,
+                           int32_t *component_out, int32_t *tree_out, size_t *tree_count, symmicp_orient_result *result)
+{
+    if (orient_args_error(xyz, xyz_row_stride, xyz_col_stride, nrm, nrm_row_stride, nrm_col_stride, n, cfg, nrm_out, tree_out, tree_count))
+        return SYMMICP_ERR_ARG;
+    return with_own_context(device, [&](symmicp_ctx *c) {
+        return symmicp_ctx_orient_normals(c, xyz, xyz_row_stride, xyz_col_stride, nrm, nrm_row_stride, nrm_col_stride, n, cfg, nrm_out, flip_out,
+                                          component_out, tree_out, tree_count, result);
     });
 }
 

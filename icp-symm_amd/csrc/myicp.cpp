@@ -123,8 +123,9 @@ void MyICP::setInputTarget(const float *xyz, const float *normals, size_t n)
 	fill_pn(*cloud_tgt, normals, *cloud_pn_tgt);
 }
 
-void MyICP::estimateNormals()
+int MyICP::estimateNormals()
 {
+	int orient_status = SYMMICP_OK;
 	// myicp.cpp:152-172: NormalEstimation, KdTree, setKSearch(10), viewpoint (0,0,0), then concatenateFields -- from the
 	// clouds as they are NOW, on every call (GetSrcCloud / GetTgtCloud hand out the clouds themselves: a caller may have
 	// edited them).  Normals the caller supplied through setInput* are kept.
@@ -146,9 +147,21 @@ void MyICP::estimateNormals()
 			symmicp_ctx *ctx = context();
 			int st = ctx ? symmicp_ctx_estimate_normals(ctx, &j.c->points[0].x, sizeof(PointT) / sizeof(float), 1, n, 10, nullptr, nrm.data(), nullptr) : SYMMICP_ERR_HIP;
 			if (st != SYMMICP_OK) error_ = "symmicp_estimate_normals failed";
+			// setOrientNormals: the estimate's signs made consistent along the cloud (never a caller's normals: those took the branch above)
+			if (st == SYMMICP_OK && orient_k_ != 0) {
+				symmicp_orient_config oc;
+				symmicp_orient_config_default(&oc);
+				oc.k = orient_k_;
+				std::vector<float> out(3 * n);
+				st = symmicp_ctx_orient_normals(ctx, &j.c->points[0].x, sizeof(PointT) / sizeof(float), 1, nrm.data(), 3, 1, n, &oc, out.data(), nullptr, nullptr,
+				                                nullptr, nullptr, nullptr);
+				if (st == SYMMICP_OK) nrm.swap(out);
+				else { error_ = std::string("normal orientation: ") + symmicp_last_error(ctx); orient_status = st; }
+			}
 		}
 		fill_pn(*j.c, nrm.data(), *j.pn);
 	}
+	return orient_status;
 }
 
 // Outlier removal: the kept rows of both clouds first (an error leaves both as they were), then every per-point array of each cloud
@@ -260,7 +273,7 @@ int MyICP::align(float out4x4[16], const float *guess4x4)
 	if (ctx_ && ctx_no_src_normals_ && mode_ != SYMMICP_MODE_PLANE) { symmicp_destroy(ctx_); ctx_ = nullptr; }   // (it would refuse the mode)
 	symmicp_ctx *ctx = context();
 	if (!ctx) { error_ = "symmicp_create failed: no usable gfx950 HIP device (there is no CPU fallback)"; result_.status = SYMMICP_ERR_HIP; return SYMMICP_ERR_HIP; }
-	estimateNormals();                                                     // myicp.cpp:105
+	if (int ost = estimateNormals()) { result_.status = ost; return ost; }  // myicp.cpp:105 (only setOrientNormals can fail it)
 	symmicp_config cfg;
 	symmicp_config_default(&cfg);
 	cfg.mode = mode_; cfg.corr = corr_; cfg.max_iters = max_iters; cfg.diff_threshold = diff_threshold;
@@ -404,7 +417,7 @@ int MyICP::alignMultiStart(const float *guesses4x4, size_t n_guesses, float out4
 	cfg.mode = mode_; cfg.max_iters = max_iters; cfg.diff_threshold = diff_threshold; cfg.max_corr_dist = max_corr_dist_;
 	const bool in_scope = (mode_ == SYMMICP_MODE_PAPER || mode_ == SYMMICP_MODE_P2P || mode_ == SYMMICP_MODE_PLANE) &&
 	                      ns <= SYMMICP_BATCH_MAX_POINTS && nt <= SYMMICP_BATCH_MAX_POINTS;
-	if (in_scope) estimateNormals();      // (a call the batch refuses needs none)
+	if (in_scope) { if (int ost = estimateNormals()) return ost; }      // (a call the batch refuses needs none)
 	else { fill_pn(*cloud_src, nullptr, *cloud_pn_src); fill_pn(*cloud_tgt, nullptr, *cloud_pn_tgt); }
 	const bool source_normals = mode_ != SYMMICP_MODE_PLANE || have_src_normals_;
 	// the packed pools of the batch call
@@ -545,6 +558,15 @@ int MyICP::globalInit(symmicp_ctx *ctx)
 		if (!c.have) {
 			int st = symmicp_ctx_estimate_normals(ctx, c.xyz.data(), 3, 1, c.m, g.normal_k, nullptr, c.n.data(), nullptr);
 			if (st != SYMMICP_OK) return failed(st, "normals of the downsampled cloud");
+			if (g.orient_k != 0) {
+				symmicp_orient_config oc;
+				symmicp_orient_config_default(&oc);
+				oc.k = g.orient_k;
+				std::vector<float> out(3 * c.m);
+				st = symmicp_ctx_orient_normals(ctx, c.xyz.data(), 3, 1, c.n.data(), 3, 1, c.m, &oc, out.data(), nullptr, nullptr, nullptr, nullptr, nullptr);
+				if (st != SYMMICP_OK) return failed(st, "normal orientation");
+				c.n.swap(out);
+			}
 		}
 		c.f.resize(33 * c.m);
 		int st = symmicp_ctx_fpfh(ctx, c.xyz.data(), 3, 1, c.n.data(), 3, 1, c.m, g.fpfh_radius, c.f.data(), nullptr, nullptr);

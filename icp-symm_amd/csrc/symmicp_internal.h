@@ -443,6 +443,22 @@ constexpr uint32_t kClusterNoise = 0xffffffffu;
 void launch_cluster_roots(const TargetIndex &ix, float r2, const int32_t *count_rows, int32_t min_points, uint32_t *parent_rows,
                           unsigned long long *stats, hipStream_t s);
 
+// normal orientation (kernels_orient.hip; symmicp_ctx_orient_normals; the state words, keys and the hook rule are orient_core.h's).
+// Everything is indexed by ORIGINAL row; xyz3 / nrm3 / nrm_out are packed [n][3].
+//   edges    knn_rows [n][k] = launch_knn's -> erow / eww [k][n] (lists and weight words, transposed), *edge_count (zeroed) += |E|,
+//            words [n] = every row a root
+//   round    best [n] / best_hi [n]: the candidate slots, reset here; words (flat) -> words_mid with this round's hooks; tree [n][2] and
+//            *counter (zeroed before the first round) take the hooked edges
+//   flatten  words_mid -> words, flat again; bound = the round's hooks + 1; *err (zeroed) |= 1 when a walk was longer
+//   finish   rule 0 = viewpoint at ref, 1 = direction ref; min_row [n], seed_key [n], root_flip [n] are scratch
+void launch_orient_edges(const int32_t *knn_rows, const float *nrm3, uint32_t n, int k, uint32_t *erow, uint32_t *eww, unsigned long long *edge_count,
+                         uint32_t *words, hipStream_t s);
+void launch_orient_round(const uint32_t *erow, const uint32_t *eww, const uint32_t *words, uint32_t *words_mid, uint32_t n, int k,
+                         unsigned long long *best, uint32_t *best_hi, const float *nrm3, int32_t *tree, uint32_t *counter, hipStream_t s);
+void launch_orient_flatten(const uint32_t *words_mid, uint32_t *words, uint32_t n, uint32_t bound, uint32_t *err, hipStream_t s);
+void launch_orient_finish(const uint32_t *words, const float *xyz3, const float *nrm3, uint32_t n, int rule, const float ref[3], uint32_t *min_row,
+                          unsigned long long *seed_key, uint32_t *root_flip, float *nrm_out, uint8_t *flip_out, int32_t *component_out, hipStream_t s);
+
 // feature matching and RANSAC (kernels_global.hip; symmicp_ctx_feature_nn, symmicp_ctx_ransac).  feature_nn: fa / fb packed [n][33];
 // splits > 1 needs feature_nn_partial_bytes of `partial`.  ransac: pq8 [m][8] = p.xyz, 0, q.xyz, 0 about the pivots; hyp [H][12].
 void launch_feature_nn(const float *fa, uint32_t na, const float *fb, uint32_t nb, int queries_per_thread, uint32_t splits, void *partial,

@@ -21,6 +21,8 @@ NSUM = 40
 UNIQUE_ID_BYTES = 128
 OK, ERR_ARG, ERR_SIZE, ERR_DEGENERATE, ERR_IO, ERR_HIP, ERR_STATE, ERR_COMM = range(8)
 ERR_NO_CONSENSUS = 8
+ERR_INTERNAL = 9
+ORIENT_VIEWPOINT, ORIENT_DIRECTION = 0, 1
 RANSAC_EVALUATED, RANSAC_REPEATED, RANSAC_EDGE, RANSAC_DEGENERATE, RANSAC_FAR = range(5)      # per-hypothesis status of ransac()
 PLANE_EVALUATED, PLANE_REPEATED, PLANE_DEGENERATE, PLANE_OFF_AXIS = range(4)                  # ... of segment_plane()
 MODE_QUIRKS, MODE_PAPER, MODE_P2P, MODE_PLANE, MODE_GICP, MODE_COLOR, MODE_NDT = 0, 1, 2, 3, 5, 7, 9      # (4, 6 and 8 are unassigned)
@@ -31,7 +33,7 @@ _LOSS_NAMES = {"none": LOSS_NONE, "huber": LOSS_HUBER, "tukey": LOSS_TUKEY, "cau
                "geman_mcclure": LOSS_GEMAN_MCCLURE}
 
 _STATUS_NAMES = {0: "OK", 1: "ERR_ARG", 2: "ERR_SIZE", 3: "ERR_DEGENERATE", 4: "ERR_IO", 5: "ERR_HIP",
-                 6: "ERR_STATE", 7: "ERR_COMM", 8: "ERR_NO_CONSENSUS"}
+                 6: "ERR_STATE", 7: "ERR_COMM", 8: "ERR_NO_CONSENSUS", 9: "ERR_INTERNAL"}
 
 
 class SymmIcpError(RuntimeError):
@@ -111,6 +113,17 @@ class ClusterConfig(C.Structure):
     """symmicp_cluster_config"""
     _fields_ = [("struct_size", C.c_uint32), ("eps", C.c_float), ("min_points", C.c_int32), ("min_cluster_size", C.c_int32),
                 ("max_cluster_size", C.c_int32), ("reserved", C.c_int32)]
+
+
+class OrientConfig(C.Structure):
+    """symmicp_orient_config"""
+    _fields_ = [("struct_size", C.c_uint32), ("k", C.c_int32), ("seed_rule", C.c_int32), ("ref", C.c_float * 3)]
+
+
+class OrientResult(C.Structure):
+    """symmicp_orient_result"""
+    _fields_ = [("graph_edges", C.c_uint64), ("tree_edges", C.c_uint64), ("components", C.c_uint64), ("largest_component", C.c_uint64),
+                ("flipped", C.c_uint64), ("rounds", C.c_int32), ("reserved", C.c_int32)]
 
 
 class PlaneConfig(C.Structure):
@@ -230,6 +243,7 @@ EXPORTS = [
     "symmicp_statistical_outlier_removal", "symmicp_ctx_statistical_outlier_removal",
     "symmicp_radius_outlier_removal", "symmicp_ctx_radius_outlier_removal",
     "symmicp_cluster_config_default", "symmicp_cluster", "symmicp_ctx_cluster",
+    "symmicp_orient_config_default", "symmicp_orient_normals", "symmicp_ctx_orient_normals",
     "symmicp_plane_config_default", "symmicp_segment_plane", "symmicp_ctx_segment_plane", "symmicp_ctx_plane_hypotheses",
     "symmicp_ndt_config_default", "symmicp_set_ndt", "symmicp_get_ndt", "symmicp_ndt_gauss", "symmicp_ndt_weight", "symmicp_get_ndt_state",
     "symmicp_ctx_ndt_map", "symmicp_ndt_map", "symmicp_get_ndt_map",
@@ -402,6 +416,12 @@ def lib():
     L.symmicp_cluster_config_default.restype = None
     L.symmicp_cluster.argtypes = [C.c_int] + clu
     L.symmicp_ctx_cluster.argtypes = [vp] + clu
+    ori = [fp, C.c_size_t, C.c_size_t, fp, C.c_size_t, C.c_size_t, C.c_size_t, C.POINTER(OrientConfig), fp, u8p, i32p, i32p, szp,
+           C.POINTER(OrientResult)]
+    L.symmicp_orient_config_default.argtypes = [C.POINTER(OrientConfig)]
+    L.symmicp_orient_config_default.restype = None
+    L.symmicp_orient_normals.argtypes = [C.c_int] + ori
+    L.symmicp_ctx_orient_normals.argtypes = [vp] + ori
     plc = [fp, C.c_size_t, C.c_size_t, C.c_size_t, C.POINTER(PlaneConfig)]
     L.symmicp_plane_config_default.argtypes = [C.POINTER(PlaneConfig)]
     L.symmicp_plane_config_default.restype = None
@@ -958,6 +978,69 @@ def euclidean_clusters(xyz, tolerance, min_size=1, max_size=0, device=-1):
     """PCL's EuclideanClusterExtraction on the GPU (symmicp_cluster with min_points = 1): the connected parts of the cloud under
     'closer than tolerance', those of min_size .. max_size points (0 = no bound) -> a list of ascending row arrays, largest first."""
     return clusters_from_labels(cluster_dbscan(xyz, tolerance, 1, min_size, max_size, device=device))
+
+
+def orient_config(k=16, viewpoint=None, direction=None):
+    """symmicp_orient_config: the seed of every component is the row closest to `viewpoint` (the default, at the origin), or the
+    extreme row along `direction` (Open3D's rule with (0, 0, 1)); give at most one of the two"""
+    if viewpoint is not None and direction is not None:
+        raise ValueError("orient_normals: give a viewpoint or a direction, not both")
+    cfg = OrientConfig()
+    lib().symmicp_orient_config_default(C.byref(cfg))
+    cfg.k = int(k)
+    ref = direction if direction is not None else viewpoint
+    if direction is not None:
+        cfg.seed_rule = ORIENT_DIRECTION
+    if ref is not None:
+        cfg.ref[:] = [float(v) for v in ref]
+    return cfg
+
+
+def _orient_call(fn, head, xyz, nrm, cfg, strides=None, want=True):
+    """fn(*head, <the C arguments>) -> (status, nrm_out [n,3] f32, flip [n] uint8 or None, component [n] int32 or None, tree [count,2]
+    int32 (as the device left it) or None, OrientResult).  strides = (n, xyz row, xyz col, nrm row, nrm col) reads both as flat f32
+    buffers."""
+    if strides is None:
+        xyz, nrm = _cloud(xyz), _cloud(nrm)
+        n, xr, xc, nr, nc = xyz.shape[0], 3, 1, 3, 1
+    else:
+        n, xr, xc, nr, nc = strides
+        xyz, nrm = np.ascontiguousarray(xyz, np.float32), np.ascontiguousarray(nrm, np.float32)
+    out = np.zeros((max(n, 1), 3), np.float32)
+    flip = np.zeros(max(n, 1), np.uint8) if want else None
+    comp = np.full(max(n, 1), -2, np.int32) if want else None
+    tree = np.full((max(n, 1), 2), -1, np.int32) if want else None
+    count, res = C.c_size_t(0), OrientResult()
+    st = fn(*head, _fptr(xyz), xr, xc, _fptr(nrm), nr, nc, n, C.byref(cfg), _fptr(out),
+            None if flip is None else flip.ctypes.data_as(C.POINTER(C.c_uint8)), None if comp is None else _i32ptr(comp),
+            None if tree is None else _i32ptr(tree), C.byref(count) if want else None, C.byref(res))
+    return (st, out[:n], None if flip is None else flip[:n], None if comp is None else comp[:n],
+            None if tree is None else tree[:int(count.value)], res)
+
+
+def _orient_normals(fn, head, xyz, nrm, cfg, return_info):
+    st, out, flip, comp, tree, res = _orient_call(fn, head, xyz, nrm, cfg, want=return_info)
+    if st != OK:
+        return st, None
+    if not return_info:
+        return st, out
+    tree = tree[np.lexsort((tree[:, 1], tree[:, 0]))]
+    return st, dict(normals=out, flip=flip.astype(bool), component=comp, tree=tree, graph_edges=int(res.graph_edges), tree_edges=int(res.tree_edges),
+                    components=int(res.components), largest_component=int(res.largest_component), flipped=int(res.flipped), rounds=int(res.rounds))
+
+
+def orient_normals(xyz, nrm, k=16, viewpoint=None, direction=None, return_info=False, device=-1):
+    """consistent normal orientation on the GPU (symmicp_orient_normals; include/symmicp.h defines the result) -> normals [N,3]: `nrm`
+    with the signs of some rows inverted so that neighbouring normals agree, one orientation propagated along the minimum spanning
+    forest of the symmetrised k-NN graph (Hoppe et al. 1992).  Every connected component of that graph is seeded on its own: at its row
+    closest to `viewpoint` (default: the origin), flipped towards it, or at its extreme row along `direction`, flipped along it.  The
+    result does not depend on the signs of `nrm`.  With return_info dict(normals=, flip= [N] bool, component= [N] int32 (the lowest
+    row of the row's component), tree= [N - components, 2] int32 sorted (lo, hi), graph_edges=, tree_edges=, components=,
+    largest_component=, flipped=, rounds=)."""
+    st, r = _orient_normals(lib().symmicp_orient_normals, (int(device),), xyz, nrm, orient_config(k, viewpoint, direction), return_info)
+    if st != OK:
+        raise SymmIcpError(st, "orient_normals")
+    return r
 
 
 def pack_clusters(xyz, nrm, labels):
@@ -1931,6 +2014,16 @@ class Engine:
         self._chk(st)
         return r
 
+    def orient_normals(self, xyz, nrm, k=16, viewpoint=None, direction=None, return_info=False):
+        """orient_normals on this context (symmicp_ctx_orient_normals); its target, source and index stay as they are"""
+        st, r = _orient_normals(self._L.symmicp_ctx_orient_normals, (self._h,), xyz, nrm, orient_config(k, viewpoint, direction), return_info)
+        self._chk(st)
+        return r
+
+    def orient_normals_raw(self, xyz, nrm, cfg, strides=None, want=True):
+        """one call of symmicp_ctx_orient_normals -> (status, normals, flip, component, tree, OrientResult)"""
+        return _orient_call(self._L.symmicp_ctx_orient_normals, (self._h,), xyz, nrm, cfg, strides, want)
+
     def cluster_dbscan_raw(self, xyz, cfg, cap=None, strides=None):
         """one call of symmicp_ctx_cluster with a caller-chosen cap (None: sizes_out == NULL) -> (status, labels, clusters, sizes, core,
         neighbors)"""
@@ -2303,6 +2396,13 @@ class MyICP:
         self.multistart_results = []
         self._removed = (0, 0)
         self._planes = (np.zeros(4), np.zeros(4))
+        self._orient_k = 0
+
+    def setOrientNormals(self, k):
+        """consistent normal orientation (orient_normals; 0, the default: off): the normals pre-step of each cloud is followed by the
+        orientation over the k-NN graph, viewpoint at the origin.  Applies to normals the class estimates itself, never to supplied
+        ones; an out-of-range k raises ERR_ARG from align()."""
+        self._orient_k = int(k)
 
     def alignMultiStart(self, guesses):
         """one batch on the object's clouds, a problem per guess [B, 4, 4] (Engine.align_multistart with the object's mode, max_iters,
@@ -2427,12 +2527,14 @@ class MyICP:
 
     def setGlobalInit(self, fpfh_radius, max_dist, voxel_leaf=0.0, normal_k=10, hypotheses=100000, seed=0, mutual=True, max_ratio=0.0,
                       edge_ratio=0.9, refits=1, iss=False, iss_salient_radius=0.0, iss_non_max_radius=0.0, iss_gamma21=0.975, iss_gamma32=0.975,
-                      iss_min_neighbors=5, method="ransac", fgr_iterations=64, fgr_division_factor=1.4, fgr_tuple_scale=0.95, fgr_max_tuples=1000):
+                      iss_min_neighbors=5, method="ransac", fgr_iterations=64, fgr_division_factor=1.4, fgr_tuple_scale=0.95, fgr_max_tuples=1000,
+                      orient_k=0):
         """global initialisation: with it set and no guess given, align() first voxel-downsamples both clouds with voxel_leaf (0: as
         given), estimates normals on the downsampled clouds when the caller supplied none (normal_k neighbours, viewpoint at the
         origin), computes FPFH features at fpfh_radius, their correspondences and a RANSAC transform, and starts the ordinary
         alignment (voxel levels included) from it.  A failure (ERR_NO_CONSENSUS among them) raises SymmIcpError.  FPFH matching
-        needs normals oriented alike in both clouds.  With iss the features are still computed on the full (downsampled) clouds, but only
+        needs normals oriented alike in both clouds: orient_k > 0 follows the estimate with orient_normals over the orient_k-NN graph
+        (viewpoint at the origin; an out-of-range value raises ERR_ARG from align()).  With iss the features are still computed on the full (downsampled) clouds, but only
         the rows of their ISS keypoints (Engine.iss_keypoints with the iss_* values) are matched and given to RANSAC; fewer than 3
         keypoints in either cloud raises ERR_NO_CONSENSUS (no fall-back to the full cloud).  method "fgr" gives the correspondences to
         Fast Global Registration (Engine.fgr with max_dist, seed and the fgr_* values) instead of RANSAC, which is not run then; every
@@ -2445,7 +2547,7 @@ class MyICP:
                             iss_non_max_radius=float(iss_non_max_radius), iss_gamma21=float(iss_gamma21), iss_gamma32=float(iss_gamma32),
                             iss_min_neighbors=int(iss_min_neighbors), method=method, fgr_iterations=int(fgr_iterations),
                             fgr_division_factor=float(fgr_division_factor), fgr_tuple_scale=float(fgr_tuple_scale),
-                            fgr_max_tuples=int(fgr_max_tuples))
+                            fgr_max_tuples=int(fgr_max_tuples), orient_k=int(orient_k))
 
     def clearGlobalInit(self):
         self._global = None
@@ -2465,6 +2567,8 @@ class MyICP:
                 xyz, nrm = d["xyz"], d["nrm"]
             if nrm is None:
                 nrm, _ = e.estimate_normals(xyz, g["normal_k"])
+                if g["orient_k"] != 0:
+                    nrm = e.orient_normals(xyz, nrm, g["orient_k"])
             clouds.append((xyz, e.fpfh(xyz, nrm, g["fpfh_radius"])))
         (src, fs), (tgt, ft) = clouds
         kp = None
@@ -2630,10 +2734,13 @@ class MyICP:
     def estimateNormals(self):
         # myicp.cpp:152-172: k = 10, flipped toward the origin.  Point-to-plane uses the target's normals only: in MODE_PLANE the
         # source's are not estimated (the engine runs without them unless the caller supplied them); GICP needs both
+        def estimate(xyz):
+            nrm, _ = estimate_normals(xyz, 10)
+            return orient_normals(xyz, nrm, self._orient_k) if self._orient_k != 0 else nrm
         if self.normals_src is None and self._cfg["mode"] != MODE_PLANE:
-            self.normals_src, _ = estimate_normals(self.cloud_src, 10)
+            self.normals_src = estimate(self.cloud_src)
         if self.normals_tgt is None:
-            self.normals_tgt, _ = estimate_normals(self.cloud_tgt, 10)
+            self.normals_tgt = estimate(self.cloud_tgt)
 
     def RegisterP2P(self):
         # myicp.cpp:43-59: the reference stub applies an identity guess and computes nothing

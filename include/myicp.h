@@ -50,6 +50,15 @@ public:
 	                                                               // GICP the normals of both clouds (as PAPER)
 	void setCorrespondence(symmicp_corr c) { corr_ = c; }          // default SYMMICP_CORR_IDENTITY (= the reference)
 	void setVerbose(bool v) { verbose_ = v; }
+	// consistent normal orientation (symmicp_ctx_orient_normals; k = 0, the default: off): the normals pre-step of each cloud is followed
+	// by the orientation over the k-NN graph, viewpoint at the origin, so that two clouds of one surface get normals on the same side
+	// where a flip towards the viewpoint alone would not.  Applies to normals the class estimates itself, never to supplied ones;
+	// checked by align(), which returns SYMMICP_ERR_ARG for a k outside 3 .. 16 or above a cloud's count.
+	void setOrientNormals(int k) { orient_k_ = k; }
+	// the point-normal clouds the last align() ran on (x y z and the normal it used per point: supplied, or estimated and, with
+	// setOrientNormals, oriented); empty before the first align()
+	pcl::PointCloud<pcl::PointNormal>::Ptr GetSrcPointNormals() const { return cloud_pn_src; }
+	pcl::PointCloud<pcl::PointNormal>::Ptr GetTgtPointNormals() const { return cloud_pn_tgt; }
 	// robust loss of the PAPER loop (symmicp_set_robust_loss; default SYMMICP_LOSS_NONE): checked by align(), which
 	// returns SYMMICP_ERR_ARG for a loss with SYMMICP_MODE_QUIRKS or a scale that is not finite and > 0
 	void setRobustLoss(symmicp_loss loss, float scale) { loss_ = loss; loss_scale_ = scale; }
@@ -106,10 +115,13 @@ public:
 	// correspondences (mutual, max_ratio) and a RANSAC transform (max_dist, hypotheses, seed, edge_ratio, refits), and starts the
 	// ordinary alignment (voxel levels included) from it.  A failure of any step -- SYMMICP_ERR_NO_CONSENSUS from RANSAC among
 	// them -- is returned from align() with lastError() saying so; there is no silent fall-back to the identity.  FPFH matching
-	// needs normals oriented alike in both clouds: with estimated normals that is the caller's viewpoint to arrange.
+	// needs normals oriented alike in both clouds: with estimated normals orient_k > 0 arranges that within every connected part of
+	// each cloud (symmicp_ctx_orient_normals, viewpoint at the origin); what remains the caller's part is a cloud in separate parts,
+	// each seeded on its own, and a viewpoint inside the object.
 	struct GlobalInit {
 		float voxel_leaf = 0.f;
 		int normal_k = 10;
+		int orient_k = 0;             // > 0: the estimated normals are oriented consistently over the orient_k-NN graph (3 .. 16); 0: off
 		float fpfh_radius = 0.f;      // required: finite, > 0
 		float max_dist = 0.f;         // required: finite, > 0
 		unsigned hypotheses = 100000;
@@ -204,7 +216,8 @@ private:
 	pcl::PointCloud<PointT>::Ptr cloud_src, cloud_tgt;
 	pcl::PointCloud<pcl::PointNormal>::Ptr cloud_pn_src, cloud_pn_tgt;
 
-	void estimateNormals();
+	int estimateNormals();               // SYMMICP_OK, or what setOrientNormals' step returned
+	int orient_k_ = 0;
 
 	symmicp_ctx *context();              // one libsymmicp context for the life of the object (stream, arenas, code objects)
 

@@ -38,8 +38,10 @@ typedef enum {
     SYMMICP_ERR_HIP = 5,           /* HIP runtime error or no gfx950-capable device */
     SYMMICP_ERR_STATE = 6,         /* call out of order (e.g. step before begin) */
     SYMMICP_ERR_COMM = 7,          /* RCCL or shared-memory exchange error */
-    SYMMICP_ERR_NO_CONSENSUS = 8   /* symmicp_ctx_ransac: no hypothesis was evaluated, or the best one has fewer than 3 inliers;
+    SYMMICP_ERR_NO_CONSENSUS = 8,  /* symmicp_ctx_ransac: no hypothesis was evaluated, or the best one has fewer than 3 inliers;
                                       symmicp_ctx_fgr: no trial passed the tuple test */
+    SYMMICP_ERR_INTERNAL = 9       /* a bound the library's own reasoning guarantees did not hold (symmicp_ctx_orient_normals: more than
+                                      32 rounds, or a walk up the parents longer than the round's hooks) */
 } symmicp_status;
 
 /* Arithmetic mode.  QUIRKS reproduces the reference exactly as written:
@@ -731,6 +733,74 @@ int symmicp_cluster(int device, const float *xyz, size_t row_stride, size_t col_
                     const symmicp_cluster_config *cfg, int32_t *labels_out, size_t *clusters_out, int32_t *sizes_out,
                     size_t cap, uint8_t *core_out, int32_t *neighbors_out);
 
+/* ---- consistent normal orientation (Hoppe et al. 1992; Open3D's orient_normals_consistent_tangent_plane; DESIGN.md 4, "Normal
+ * orientation") ---------------------------------------------------------------------------------------------------------------
+ * Gives the normals of a cloud one common side per connected part: a flip towards a viewpoint is right only where the viewpoint
+ * sees the surface, so on a full model or a merged scan it is wrong for a good part of the rows, and two clouds of one surface
+ * then disagree there.  One orientation is propagated along the minimum spanning forest of the neighbour graph, edges weighted by
+ * how parallel the two normals are.  Defined by its arithmetic: fp32, unfused, in the association written; the result is a function
+ * of the inputs alone, bit for bit (the forest is unique, so it does not depend on the order in which the device finds it).
+ * Inputs: xyz [n], nrm [n] (unoriented; zero normals are allowed), cfg = {k, seed_rule, ref[3]}.
+ *   1. Graph.  S(i) = the k-NN set of symmicp_ctx_knn without row i itself, left out by ROW as symmicp_ctx_intensity_gradient does (a
+ *      duplicate of the point is a member; among more than k exact duplicates a row may be missing from its own set, and S(i) then has
+ *      k members).  E = { {i, j} : j in S(i) or i in S(j) }: the symmetrised k-NN graph.  It is never stored symmetrised.
+ *   2. Weight.  d(i,j) = (nx_i*nx_j + ny_i*ny_j) + nz_i*nz_j;  w = fmaxf(1.0f - fabsf(d), 0.0f);  s(i,j) = d < 0: "these two normals
+ *      disagree".  d(i,j) == d(j,i) exactly.
+ *   3. Order.  Edges are ordered by the triple (bits of w as uint32, lo = min(i,j), hi = max(i,j)): strict and total, so the minimum
+ *      spanning forest F of (E, order) is unique.
+ *   4. Components.  The connected components of E = the trees of F.  component_out[i] = the lowest row of i's component.
+ *   5. Seed, one per component.
+ *      SYMMICP_ORIENT_VIEWPOINT (the default, ref = the origin): the row with the smallest d2 = (dx*dx + dy*dy) + dz*dz, dx = x - ref.x
+ *        and so on, compared as fp32 bits, ties to the lowest row.  It is flipped iff the flip test of the normals pre-step
+ *        (symmicp_ctx_estimate_normals) flips it: in fp64 from the fp32 values,
+ *        ((ref.x - x)*nx + (ref.y - y)*ny) + (ref.z - z)*nz < 0.
+ *      SYMMICP_ORIENT_DIRECTION (Open3D's rule with ref = +z): the row with the largest p = ((x*ref.x + y*ref.y) + z*ref.z) + 0.0f (a
+ *        NaN p, an overflow of both signs, counts as -inf), ties to the lowest row.  Flipped iff (nx*ref.x + ny*ref.y) + nz*ref.z < 0.
+ *      The closest point to a viewpoint, or the extreme point along a direction, is where the surface's normal is parallel to the line
+ *      of sight: the sign test is at its most reliable there.
+ *   6. Propagation.  flip(i) = flip(seed) XOR (the number of edges with s = 1 on the tree path from i to its component's seed is odd).
+ *   7. Output.  nrm_out [n][3] packed (required): nrm[i] with the sign bits of its three components inverted when flip(i); the bits
+ *      are otherwise untouched.  Optional, each may be NULL: flip_out [n] (0 / 1); component_out [n]; tree_out [n - 1][2]: the edges
+ *      (lo, hi) of F in an unspecified order, *tree_count their number = n - components (tree_count is required with tree_out and is
+ *      always set when given); result (below).
+ * nrm_out does not depend on the signs of the input normals: w uses |d|, and negating one normal inverts s on every edge at that row,
+ * which inverts its own flip and nobody else's (the exception is an exact zero: a d, or a seed's test value, that is exactly 0 reads
+ * as "agree" / "keep" under either sign).  So the stage is idempotent, and a normals pre-step with any viewpoint may precede it.
+ * What remains the caller's part: every component is seeded on its own (result->components says how many there are; default k = 16:
+ * the cat of tests/golden is one component at k = 16 and four at k = 10), and a viewpoint inside a closed object orients it inwards.
+ * Method: Boruvka rounds over the lists of symmicp_ctx_knn with the sign carried as a parity (csrc/orient_core.h); rounds <=
+ * ceil(log2 n).  SYMMICP_ERR_INTERNAL if a bound of that reasoning fails (more than 32 rounds; a walk longer than the round's hooks).
+ * SYMMICP_ERR_ARG, all decided on the host before a device is needed: NULL xyz / nrm / cfg / nrm_out; tree_out without tree_count;
+ *   n == 0 or n > 2^31 - 1; cfg->struct_size != sizeof(symmicp_orient_config); k outside 3 .. 16 or above n; a seed_rule that is
+ *   neither of the two; a non-finite ref, or a zero ref with SYMMICP_ORIENT_DIRECTION; non-finite coordinates; non-finite normals.
+ * xyz and nrm strided as in symmicp_set_source.  The ctx form runs on the context's stream and arenas like symmicp_ctx_knn: the
+ * context's source, target, index, attributes and certificates stay exactly as they were. */
+typedef enum { SYMMICP_ORIENT_VIEWPOINT = 0, SYMMICP_ORIENT_DIRECTION = 1 } symmicp_orient_seed;
+typedef struct {
+    uint32_t struct_size;       /* = sizeof(symmicp_orient_config), checked */
+    int32_t  k;                 /* 3 .. 16, <= n; default 16 (the cat of tests/golden: one component at 16, four at 10) */
+    int32_t  seed_rule;         /* symmicp_orient_seed; default SYMMICP_ORIENT_VIEWPOINT */
+    float    ref[3];            /* the viewpoint, or the direction; default 0 0 0 */
+} symmicp_orient_config;
+typedef struct {
+    uint64_t graph_edges;       /* |E| */
+    uint64_t tree_edges;        /* |F| = n - components */
+    uint64_t components;
+    uint64_t largest_component; /* rows of the largest component */
+    uint64_t flipped;           /* rows with flip(i) = 1 */
+    int32_t  rounds;            /* Boruvka rounds that joined something */
+    int32_t  reserved;
+} symmicp_orient_result;
+void symmicp_orient_config_default(symmicp_orient_config *cfg);
+int symmicp_ctx_orient_normals(symmicp_ctx *ctx, const float *xyz, size_t xyz_row_stride, size_t xyz_col_stride, const float *nrm,
+                               size_t nrm_row_stride, size_t nrm_col_stride, size_t n, const symmicp_orient_config *cfg, float *nrm_out,
+                               uint8_t *flip_out, int32_t *component_out, int32_t *tree_out, size_t *tree_count,
+                               symmicp_orient_result *result);
+/* the same on a context of its own, created on `device` (-1 = current) and destroyed again */
+int symmicp_orient_normals(int device, const float *xyz, size_t xyz_row_stride, size_t xyz_col_stride, const float *nrm,
+                           size_t nrm_row_stride, size_t nrm_col_stride, size_t n, const symmicp_orient_config *cfg, float *nrm_out,
+                           uint8_t *flip_out, int32_t *component_out, int32_t *tree_out, size_t *tree_count, symmicp_orient_result *result);
+
 /* ---- RANSAC plane segmentation (PCL's SACSegmentation with SACMODEL_PLANE / SACMODEL_PERPENDICULAR_PLANE, Open3D's
  * segment_plane; DESIGN.md 4, "Plane segmentation") ---------------------------------------------------------------------------
  * The plane with the most points of a cloud within max_dist: the floor or the table that joins every object standing on it into one
@@ -820,8 +890,9 @@ int symmicp_ctx_plane_hypotheses(symmicp_ctx *ctx, const float *xyz, size_t row_
  * as they were.  A sharded job computes the full result on every rank (the outputs are deterministic).
  *
  * FPFH matching relies on normals that are oriented alike in both clouds: two scans of one surface whose normals point to
- * different sides of it give unrelated histograms.  Estimated normals are flipped towards a viewpoint; choosing viewpoints that
- * orient both clouds consistently is the caller's part.
+ * different sides of it give unrelated histograms.  Estimated normals are flipped towards a viewpoint, which is right only where
+ * the viewpoint sees the surface; symmicp_ctx_orient_normals then makes them consistent within every connected part of a cloud.
+ * What remains the caller's part is a cloud in separate parts, each seeded on its own, and a viewpoint inside the object.
  *
  * symmicp_ctx_feature_nn: exact nearest neighbour in feature space.  fa [na][33] (queries) and fb [nb][33] (candidates), packed
  * fp32 as symmicp_ctx_fpfh writes them.  Defined by its arithmetic (fp32, unfused):
