@@ -9,7 +9,6 @@
 // There is no CPU fallback: without a HIP device every entry point fails loudly.
 #include "engine_internal.h"
 #include "robust_loss.h"
-#include <limits>
 
 void read_switches(Switches &w)
 {
@@ -154,26 +153,12 @@ int symmicp_create(const symmicp_config *cfg, symmicp_ctx **out)
     return SYMMICP_OK;
 }
 
-extern "C++" hipError_t keep_alloc(symmicp_ctx *c, void **out, size_t bytes)
-{
-    bytes = (bytes + 255) & ~(size_t)255;
-    if (!bytes) bytes = 256;
-    if (c->keep.base && c->keep.off + bytes <= c->keep.cap) { *out = c->keep.base + c->keep.off; c->keep.off += bytes; return hipSuccess; }
-    void *p = nullptr;
-    const hipError_t e = hipMalloc(&p, bytes);
-    if (e == hipSuccess) { c->keep_extra.push_back(p); *out = p; }
-    return e;
-}
-
 extern "C++" void free_target(symmicp_ctx *c)
 {
-    // (the arrays live in the keep-arena, which stays allocated for the next target)
-    for (void *p : c->keep_extra) hipFree(p);
-    c->keep_extra.clear();
-    c->keep.off = 0;
-    hipFree(c->dbg); hipFree(c->dbg_trace); c->dbg_trace = nullptr;
-    c->ctop = nullptr; c->dbg = nullptr; c->ix = TargetIndex{}; c->tgt_block = nullptr; c->tq = nullptr; c->tn = nullptr; c->boxes = nullptr; c->cells = nullptr; c->onodes = nullptr;
-    c->have_index = false; c->n_t = 0;
+    c->tgt_store.reset();      // (the arrays live in its block, which stays allocated for the next target)
+    hipFree(c->ix.dbg); hipFree(c->ix.dbg_trace);
+    c->ix = TargetIndex{}; c->tgt_block = nullptr;
+    c->have_index = false; c->target_surface_like = false; c->n_t = 0;
     c->have_tgt_color = false;
     c->ndt.map.valid = false; c->ndt.pass_valid = false;
     c->notes = IndexNotes{};
@@ -187,7 +172,7 @@ extern "C++" void forget_source(symmicp_ctx *c)
     c->n_loc = c->n_s_total = c->src_off = 0;
     c->src_no_normals = false;
     c->have_src_int = false;
-    drop_reverse_index(c->rej.src_ix, false);
+    c->rej.src_ix.drop();
 }
 
 static void free_source(symmicp_ctx *c)
@@ -208,11 +193,11 @@ void symmicp_destroy(symmicp_ctx *c)
     shm_close(c);
     free_target(c);
     free_source(c);
-    hipFree(c->partials); hipFree(c->d_sums); hipFree(c->ticket); hipFree(c->arena.base); hipFree(c->keep.base);
+    hipFree(c->partials); hipFree(c->d_sums); hipFree(c->ticket); hipFree(c->arena.base);
     hipFree(c->rej.keys); hipFree(c->rej.ws); hipFree(c->rej.table);
     hipFree(c->tgt_color); hipFree(c->src_int);
     c->ndt.map.release();
-    drop_reverse_index(c->rej.src_ix, true);
+    c->tgt_store.release(); c->rej.src_ix.store.release();      // (their destructors, at the delete below, find nothing left)
     if (c->h_sums) hipHostFree(c->h_sums);
     hipFree(c->d_loop);
     if (c->h_loop) hipHostFree(c->h_loop);
@@ -490,7 +475,7 @@ int symmicp_set_target_intensity(symmicp_ctx *c, const float *intensity, size_t 
     if (!intensity || !grad) return fail(c, SYMMICP_ERR_ARG, "null target intensity or gradient (symmicp_ctx_intensity_gradient estimates one)");
     if (!c->tgt_block) return fail(c, SYMMICP_ERR_STATE, "symmicp_set_target_intensity follows symmicp_set_target");
     if (n != c->n_t) return fail(c, SYMMICP_ERR_SIZE, "target intensity: n differs from the target's count");
-    if (c->cfg.corr != SYMMICP_CORR_IDENTITY && !c->tq) return fail(c, SYMMICP_ERR_STATE, "target was set under a different corr mode");
+    if (c->cfg.corr != SYMMICP_CORR_IDENTITY && !c->ix.tq) return fail(c, SYMMICP_ERR_STATE, "target was set under a different corr mode");
     std::vector<float> hi, hg;
     if (!stage_finite(intensity, stride, 0, n, 1, hi) || !stage_finite(grad, grs, gcs, n, 3, hg))
         return fail(c, SYMMICP_ERR_ARG, "target intensity or gradient: non-finite value");
@@ -505,7 +490,7 @@ int symmicp_set_target_intensity(symmicp_ctx *c, const float *intensity, size_t 
     HIP_TRY(c, hipMemcpyAsync(di.p, hi.data(), sizeof(float) * n, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipMemcpyAsync(dg.p, hg.data(), sizeof(float) * 3 * n, hipMemcpyHostToDevice, c->stream));
     // (identity pairing reads the planar target in the caller's order; BRUTE's tq is in that order too and says so in its w words)
-    launch_color_permute_target(di.p, dg.p, c->cfg.corr == SYMMICP_CORR_IDENTITY ? nullptr : c->tq, (uint32_t)n, c->tgt_color, c->stream);
+    launch_color_permute_target(di.p, dg.p, c->cfg.corr == SYMMICP_CORR_IDENTITY ? nullptr : c->ix.tq, (uint32_t)n, c->tgt_color, c->stream);
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     HIP_TRY(c, hipGetLastError());
     c->have_tgt_color = true;
@@ -535,315 +520,6 @@ float symmicp_robust_weight(int loss, float scale, float r)
     return loss == SYMMICP_LOSS_NONE ? 1.0f : robust_weight(loss, scale, r);
 }
 
-// host strided cloud -> device block of 6 planar arrays.  The usual layouts never touch a host staging loop: records with
-// contiguous x y z (packed AoS, PointXYZ, PointNormal) are copied as they are and split into columns on the device;
-// column-major matrices (Eigen) are copied column by column.  Anything else goes through a host transpose.  nrm == NULL: the normal
-// columns are zero-filled (a PLANE source: no kernel is ever handed an unallocated normal array).
-extern "C++" int upload_planar(symmicp_ctx *c, const float *xyz, size_t xr, size_t xc, const float *nrm, size_t nr, size_t nc,
-                              size_t n, DevBuf<float> &block, bool temp, double centroid[3])
-{
-    if (centroid) {
-        // fp64, in row order (the oracle's order: the pivot has to come out bit-identical)
-        double s[3] = {0, 0, 0};
-        for (size_t i = 0; i < n; i++)
-            for (int k = 0; k < 3; k++) s[k] += (double)xyz[i * xr + k * xc];
-        for (int k = 0; k < 3; k++) centroid[k] = s[k] / (double)n;
-    }
-    if (temp) HIP_TRY(c, block.alloc_temp(c->arena, 6 * n));
-    else { HIP_TRY(c, keep_alloc(c, (void **)&block.p, sizeof(float) * 6 * n)); block.owned = false; }
-    float *col[6];
-    for (int k = 0; k < 6; k++) col[k] = block.p + (size_t)k * n;
-    struct Part { const float *base; size_t rs, cs; int first_col; } parts[2] = {{xyz, xr, xc, 0}, {nrm, nr, nc, 3}};
-    if (!nrm) HIP_TRY(c, hipMemsetAsync(col[3], 0, sizeof(float) * 3 * n, c->stream));
-    for (const Part &p : parts) {
-        if (!p.base) continue;
-        if (p.cs == 1 && p.rs >= 3) {
-            const size_t fl = (n - 1) * p.rs + 3;                  // floats from the first x to the last z
-            DevBuf<float> raw;
-            HIP_TRY(c, raw.alloc_temp(c->arena, fl));
-            HIP_TRY(c, hipMemcpyAsync(raw.p, p.base, sizeof(float) * fl, hipMemcpyHostToDevice, c->stream));
-            launch_deinterleave3(raw.p, p.rs, 0, (uint32_t)n, col[p.first_col], col[p.first_col + 1], col[p.first_col + 2], c->stream);
-            HIP_TRY(c, hipStreamSynchronize(c->stream));           // raw is freed on scope exit
-        } else if (p.rs == 1 && p.cs >= n) {
-            for (int k = 0; k < 3; k++)
-                HIP_TRY(c, hipMemcpyAsync(col[p.first_col + k], p.base + (size_t)k * p.cs, sizeof(float) * n, hipMemcpyHostToDevice, c->stream));
-            HIP_TRY(c, hipStreamSynchronize(c->stream));
-        } else {
-            std::vector<float> stage(3 * n);
-            for (size_t i = 0; i < n; i++)
-                for (int k = 0; k < 3; k++) stage[(size_t)k * n + i] = p.base[i * p.rs + k * p.cs];
-            HIP_TRY(c, hipMemcpyAsync(col[p.first_col], stage.data(), sizeof(float) * 3 * n, hipMemcpyHostToDevice, c->stream));
-            HIP_TRY(c, hipStreamSynchronize(c->stream));
-        }
-    }
-    HIP_TRY(c, hipGetLastError());
-    return SYMMICP_OK;
-}
-
-// Morton order of a planar cloud: fills order[n] (sorted position -> row) and, optionally, keeps the sorted keys.
-extern "C++" int morton_order(symmicp_ctx *c, const CloudSoA &cl, uint32_t n, DevBuf<uint32_t> &vals, DevBuf<uint32_t> *keys_out,
-                        float origin[3], float *h0_out)
-{
-    DevBuf<uint32_t> bbox, keys_local, kt, vt, ws;
-    DevBuf<uint32_t> &keys = keys_out ? *keys_out : keys_local;
-    const size_t wse = radix_sort_ws_elems(n);
-    HIP_TRY(c, bbox.alloc_temp(c->arena, 6));
-    HIP_TRY(c, keys.alloc_temp(c->arena, n));
-    HIP_TRY(c, vals.alloc_temp(c->arena, n));
-    HIP_TRY(c, kt.alloc_temp(c->arena, n));
-    HIP_TRY(c, vt.alloc_temp(c->arena, n));
-    HIP_TRY(c, ws.alloc_temp(c->arena, wse));
-    launch_bbox(cl.x, cl.y, cl.z, n, bbox.p, c->stream);
-    uint32_t hb[6];
-    HIP_TRY(c, hipMemcpyAsync(hb, bbox.p, sizeof(hb), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    float lo[3], hi[3];
-    for (int k = 0; k < 3; k++) { lo[k] = ord2f(hb[k]); hi[k] = ord2f(hb[3 + k]); }
-    float emax = 0.f;
-    for (int k = 0; k < 3; k++) {
-        if (!std::isfinite(lo[k]) || !std::isfinite(hi[k])) return fail(c, SYMMICP_ERR_ARG, "cloud has non-finite coordinates");
-        emax = std::fmax(emax, hi[k] - lo[k]);
-    }
-    if (!(emax > 0.f)) emax = 1.f;
-    const float h0 = emax * 1.00001f / (float)(1 << kMortonBits);
-    launch_morton(cl.x, cl.y, cl.z, n, lo[0], lo[1], lo[2], 1.0f / h0, keys.p, vals.p, c->stream);
-    radix_sort_pairs(keys.p, vals.p, kt.p, vt.p, n, 3 * kMortonBits, ws.p, wse, c->stream);
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    HIP_TRY(c, hipGetLastError());
-    for (int k = 0; k < 3; k++) origin[k] = lo[k];
-    *h0_out = h0;
-    return SYMMICP_OK;
-}
-
-// Search index over a planar cloud: Morton sort -> float4 gather -> (optional) dense cell table at the
-// chosen octree level -> implicit 8-ary box tree.  tq/tn must already be allocated (n float4 each).
-// sparse octree over the sorted keys (levels 0..kMortonBits, built bottom-up); see TargetIndex::onodes
-static int build_octree(symmicp_ctx *c, const uint32_t *keys, const float4 *tq, uint32_t n, uint32_t leaf_max, float4 **onodes_out, TargetIndex *ix)
-{
-    constexpr int NL = kMortonBits + 1;
-    DevBuf<uint32_t> nid;                         // [NL][n]: id of the node that starts at point i, per level
-    DevBuf<uint32_t> scan_ws, first;
-    float4 *nodes = nullptr;
-    HIP_TRY(c, nid.alloc_temp(c->arena, (size_t)NL * n));
-    HIP_TRY(c, scan_ws.alloc_temp(c->arena, (size_t)n / 2048 + 2));
-    for (int l = 0; l < NL; l++) {
-        launch_oct_flags(keys, n, l, nid.p + (size_t)l * n, c->stream);
-        launch_exclusive_scan(nid.p + (size_t)l * n, n, scan_ws.p, c->stream);
-    }
-    // node counts: exclusive scan value at the last point, +1 if the last point starts a node (host checks the keys)
-    uint32_t last_excl[NL], kl[2] = {0, 0};
-    for (int l = 0; l < NL; l++)
-        HIP_TRY(c, hipMemcpyAsync(&last_excl[l], nid.p + (size_t)l * n + (n - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-    if (n >= 2) HIP_TRY(c, hipMemcpyAsync(kl, keys + (n - 2), 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    uint32_t cnt[NL];
-    size_t total = 0;
-    for (int l = 0; l < NL; l++) {
-        const int shift = 3 * (kMortonBits - l);
-        const bool last_starts = (n == 1) || (shift < 30 && (kl[1] >> shift) != (kl[0] >> shift));
-        cnt[l] = last_excl[l] + (last_starts ? 1u : 0u);
-        ix->olevel_off[l] = (uint32_t)total;
-        total += cnt[l];
-    }
-    ix->olevel_off[NL] = (uint32_t)total;
-    for (int l = 0; l < NL; l++)
-        // child_first is a 28-bit field of the node word: targets beyond ~268M distinct finest cells are refused
-        if (cnt[l] > kOctCfMask) return fail(c, SYMMICP_ERR_SIZE, "octree level exceeds 2^28 nodes (target cloud too large for SYMMICP_CORR_TREE)");
-    HIP_TRY(c, first.alloc_temp(c->arena, total + 1));
-    HIP_TRY(c, keep_alloc(c, (void **)&nodes, sizeof(float4) * 2 * total));
-    for (int l = 0; l < NL; l++)
-        launch_oct_first(keys, n, l, nid.p + (size_t)l * n, first.p + ix->olevel_off[l], c->stream);
-    for (int l = NL - 1; l >= 0; l--) {
-        const bool bottom = (l == NL - 1);
-        launch_oct_nodes(l, tq, n, first.p + ix->olevel_off[l], cnt[l], bottom ? nullptr : nid.p + (size_t)(l + 1) * n,
-                         bottom ? 0u : cnt[l + 1], bottom ? nullptr : nodes + 2 * (size_t)ix->olevel_off[l + 1],
-                         nodes + 2 * (size_t)ix->olevel_off[l], leaf_max, c->stream);
-    }
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    HIP_TRY(c, hipGetLastError());
-    *onodes_out = nodes;
-    ix->onodes = *onodes_out;
-    return SYMMICP_OK;
-}
-
-// The outputs (*boxes_out, *cells_out, *onodes_out, *ctop_out) belong to the caller's context as soon as they are set:
-// on failure the caller's free_target() / cleanup releases them.
-extern "C++" int build_index(symmicp_ctx *c, const CloudSoA &cl, uint32_t n, bool want_grid, float4 *tq, float4 *tn,
-                            float4 **boxes_out, uint2 **cells_out, TargetIndex *ix_out, int32_t *glevel_out, int32_t *nlevels_out,
-                            float4 **onodes_out, uint32_t **ctop_out, IndexNotes *notes)
-{
-    DevBuf<uint32_t> order, keys;
-    float origin[3], h0;
-    int st = morton_order(c, cl, n, order, &keys, origin, &h0);
-    if (st != SYMMICP_OK) return st;
-    if (notes) { *notes = IndexNotes{}; for (int k = 0; k < 3; k++) notes->origin[k] = origin[k]; notes->h0 = h0; }
-    launch_gather_f4(cl.x, cl.y, cl.z, cl.nx, cl.ny, cl.nz, order.p, n, tq, tn, c->stream);
-    TargetIndex ix{};
-    ix.tq = tq; ix.tn = tn; ix.n = n;
-    int glevel = 0;
-    if (want_grid) {
-        DevBuf<uint32_t> hist;
-        HIP_TRY(c, hist.alloc_temp(c->arena, 16));
-        launch_level_hist(keys.p, n, hist.p, c->stream);
-        uint32_t hh[16];
-        HIP_TRY(c, hipMemcpyAsync(hh, hist.p, sizeof(hh), hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        if (notes) std::memcpy(notes->hist, hh, sizeof(hh));
-        // finest level whose occupied cells still hold >= ppc points on average
-        const double ppc = c->sw.grid_ppc;
-        int lcap = c->sw.grid_maxlevel;                  // the table is two-level: memory follows the occupied super-cells
-        if (lcap > kMortonBits) lcap = kMortonBits;
-        glevel = 1;
-        double occ = 1.0;
-        for (int l = 1; l <= lcap; l++) {
-            occ += (double)hh[l];
-            if ((double)n / occ >= ppc) glevel = l;
-        }
-        if (c->sw.grid_level >= 0) glevel = c->sw.grid_level;   // 0 disables the grid phase
-        if (glevel > lcap) glevel = lcap;
-        if (glevel < 0) glevel = 0;
-        // Is the target a surface or a volume?  Occupied cells grow ~4x per octree level on a surface and ~8x in a volume
-        // (measured one level above the grid level, where cells still hold several points).  On surface-like targets the
-        // queries of a packet share most of their search (offset surfaces: every ball touches the target in a wide disc), so
-        // the first pass runs as packets (kernels_packet.hip) over an octree with larger leaves; in a volume cloud the
-        // neighbours are half a spacing away, nothing is shared, and the per-thread walk stays (100k uniform cube, first
-        // pass: 0.11 ms per-thread walk, 0.31 ms packets; 1M surface pair: 1.69 ms against 0.87 ms).
-        {
-            double occ_l[kMortonBits + 1];
-            double o = 1.0;
-            occ_l[0] = 1.0;
-            for (int l = 1; l <= kMortonBits; l++) { o += (double)hh[l]; occ_l[l] = o; }
-            const int lg = glevel >= 2 ? glevel - 1 : 1;
-            const double growth = occ_l[lg] / occ_l[lg - 1];
-            c->target_surface_like = growth < 5.5;
-            if (c->sw.first_pass >= 0) c->target_surface_like = c->sw.first_pass == 1;      // SYMMICP_FIRST_PASS=packet|walk: A/B runs
-        }
-    }
-    ix.glevel = glevel;
-    if (glevel > 0) {
-        const int ltop = glevel > 3 ? glevel - 3 : 0;
-        const size_t ntop = (size_t)1 << (3 * ltop);
-        // block numbers of the occupied super-cells: exclusive scan of their start flags
-        DevBuf<uint32_t> nid_top, scan_ws;
-        HIP_TRY(c, nid_top.alloc_temp(c->arena, n));
-        HIP_TRY(c, scan_ws.alloc_temp(c->arena, (size_t)n / 2048 + 2));
-        launch_oct_flags(keys.p, n, ltop, nid_top.p, c->stream);
-        launch_exclusive_scan(nid_top.p, n, scan_ws.p, c->stream);
-        uint32_t last_excl = 0, kl[2] = {0, 0};
-        HIP_TRY(c, hipMemcpyAsync(&last_excl, nid_top.p + (n - 1), sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-        if (n >= 2) HIP_TRY(c, hipMemcpyAsync(kl, keys.p + (n - 2), 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        const int tshift = 3 * (kMortonBits - ltop);
-        const bool last_starts = (n == 1) || (tshift < 30 && (kl[1] >> tshift) != (kl[0] >> tshift));
-        const size_t nblocks = (size_t)last_excl + (last_starts ? 1 : 0);
-        if (notes) { notes->nblocks = (uint32_t)nblocks; notes->ctop_len = (uint32_t)ntop; }
-        HIP_TRY(c, keep_alloc(c, (void **)ctop_out, sizeof(uint32_t) * ntop));
-        HIP_TRY(c, hipMemsetAsync(*ctop_out, 0xFF, sizeof(uint32_t) * ntop, c->stream));
-        HIP_TRY(c, keep_alloc(c, (void **)cells_out, sizeof(uint2) * nblocks * 512));
-        HIP_TRY(c, hipMemsetAsync(*cells_out, 0, sizeof(uint2) * nblocks * 512, c->stream));
-        launch_cell_table(keys.p, n, glevel, nid_top.p, *ctop_out, *cells_out, c->stream);
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        ix.ctop = *ctop_out;
-        ix.cells = *cells_out;
-        ix.gdim = 1 << glevel;
-        ix.ox = origin[0]; ix.oy = origin[1]; ix.oz = origin[2];
-        ix.h = h0 * (float)(1 << (kMortonBits - glevel));
-        ix.inv_h = (1.0f / h0) / (float)(1 << (kMortonBits - glevel));
-    }
-    // tree levels: level 0 = leaves of kLeaf points, each level padded to a multiple of kFan
-    uint32_t cnt[kMaxTreeLevels], pad[kMaxTreeLevels];
-    int nl = 0;
-    uint32_t m = (n + kLeaf - 1) / kLeaf;
-    size_t total = 0;
-    while (true) {
-        cnt[nl] = m;
-        pad[nl] = (m <= (uint32_t)kFan) ? m : ((m + kFan - 1) / kFan) * kFan;
-        ix.level_off[nl] = (uint32_t)total;
-        total += pad[nl];
-        nl++;
-        if (m <= (uint32_t)kFan) break;
-        m = pad[nl - 1] / kFan;
-        if (nl >= kMaxTreeLevels) return fail(c, SYMMICP_ERR_SIZE, "tree too deep");
-    }
-    ix.top = nl - 1;
-    ix.ntop = cnt[nl - 1];
-    HIP_TRY(c, keep_alloc(c, (void **)boxes_out, sizeof(float4) * 2 * total));
-    float4 *boxes = *boxes_out;
-    launch_leaf_boxes(tq, n, boxes + 2 * (size_t)ix.level_off[0], pad[0], c->stream);
-    for (int l = 1; l < nl; l++)
-        launch_node_boxes(boxes + 2 * (size_t)ix.level_off[l - 1], pad[l - 1], boxes + 2 * (size_t)ix.level_off[l], pad[l], c->stream);
-    ix.boxes = boxes;
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    HIP_TRY(c, hipGetLastError());
-    if (onodes_out) {
-        uint32_t leaf_max = c->target_surface_like ? 24u : 8u;      // (packets: 12 / 16 / 20 / 24 / 28 points per leaf: 0.425 / 0.411 / 0.394 / 0.389 / 0.394 ms first pass of the 1M surface pair)
-        if (c->sw.oct_leaf > 0) leaf_max = (uint32_t)c->sw.oct_leaf;
-        if (notes) notes->leaf_max = leaf_max;
-        st = build_octree(c, keys.p, tq, n, leaf_max, onodes_out, &ix);
-        if (st != SYMMICP_OK) return st;
-    }
-    *ix_out = ix;
-    if (glevel_out) *glevel_out = glevel;
-    if (nlevels_out) *nlevels_out = nl;
-    return SYMMICP_OK;
-}
-
-extern "C++" void drop_reverse_index(ReverseIndex &ri, bool release)
-{
-    for (void *p : ri.extra) hipFree(p);
-    ri.extra.clear();
-    ri.keep.off = 0;
-    ri.ix = TargetIndex{};
-    ri.valid = false;
-    if (release) { hipFree(ri.keep.base); ri.keep = Arena{}; }
-}
-
-// The source index of reciprocal passes: build_index as the k-NN path calls it (no grid; leaves of 8 points whatever the target looks
-// like and whatever SYMMICP_OCT_LEAF says), with the keep-arena swapped for ri's for the length of the build.  The pair records (tn) are not needed: they go to the scratch
-// arena.  Persistent: tq 16 B, the octree ~64 B and the run tree ~5 B per point.
-extern "C++" int build_reverse_index(symmicp_ctx *c, const CloudSoA &cl, uint32_t n, const uint32_t *labels, ReverseIndex &ri)
-{
-    drop_reverse_index(ri, false);
-    const size_t want = (size_t)n * 96 + ((size_t)4 << 20);
-    if (ri.keep.cap < want) {
-        hipFree(ri.keep.base);
-        ri.keep = Arena{};
-        if (hipMalloc((void **)&ri.keep.base, want) == hipSuccess) ri.keep.cap = want;
-        else (void)hipGetLastError();      // every keep_alloc then falls back to its own hipMalloc
-    }
-    arena_begin(c->arena, (size_t)n * 128 + ((size_t)1 << 20));
-    const bool surf0 = c->target_surface_like;
-    const int leaf0 = c->sw.oct_leaf;
-    c->target_surface_like = false;
-    c->sw.oct_leaf = 0;                   // (SYMMICP_OCT_LEAF tunes the target's octree for the packet search: not this one)
-    std::swap(c->keep, ri.keep);
-    std::swap(c->keep_extra, ri.extra);
-    auto body = [&]() -> int {
-        float4 *tq = nullptr, *boxes = nullptr, *onodes = nullptr;
-        uint2 *cells = nullptr;
-        DevBuf<float4> tn;
-        HIP_TRY(c, keep_alloc(c, (void **)&tq, sizeof(float4) * ((size_t)n + 8)));
-        HIP_TRY(c, hipMemsetAsync(tq + n, 0, sizeof(float4) * 8, c->stream));
-        HIP_TRY(c, tn.alloc_temp(c->arena, 2 * (size_t)n));
-        TargetIndex ix{};
-        int st = build_index(c, cl, n, /*want_grid=*/false, tq, tn.p, &boxes, &cells, &ix, nullptr, nullptr, &onodes);
-        if (st != SYMMICP_OK) return st;
-        launch_relabel_tq(tq, n, labels, c->stream);
-        HIP_TRY(c, hipStreamSynchronize(c->stream));      // (tn is about to go out of scope)
-        HIP_TRY(c, hipGetLastError());
-        ri.ix = ix;
-        return SYMMICP_OK;
-    };
-    const int st = body();
-    std::swap(c->keep, ri.keep);
-    std::swap(c->keep_extra, ri.extra);
-    c->target_surface_like = surf0;
-    c->sw.oct_leaf = leaf0;
-    if (st != SYMMICP_OK) { (void)hipStreamSynchronize(c->stream); drop_reverse_index(ri, false); return st; }
-    ri.valid = true;
-    return SYMMICP_OK;
-}
-
 int symmicp_set_target(symmicp_ctx *c, const float *xyz, size_t xr, size_t xc, const float *nrm, size_t nr, size_t nc, size_t n)
 {
     if (!c) return SYMMICP_ERR_ARG;
@@ -854,21 +530,14 @@ int symmicp_set_target(symmicp_ctx *c, const float *xyz, size_t xr, size_t xc, c
     const double t0 = now_s();
     free_target(c);
     c->begun = false;
-    {
-        // the target's persistent arrays: planar cloud 24 B, tq 16, pair records 32, octree ~64, run tree ~5, cell table
-        const size_t want = n * 160 + ((size_t)16 << 20);
-        if (c->keep.cap < want) {
-            hipFree(c->keep.base);
-            c->keep = Arena{};
-            if (hipMalloc((void **)&c->keep.base, want + want / 8) == hipSuccess) c->keep.cap = want + want / 8;
-            else (void)hipGetLastError();      // every keep_alloc then falls back to its own hipMalloc
-        }
-    }
+    // the target's persistent arrays: planar cloud 24 B, tq 16, pair records 32, octree ~64, run tree ~5, cell table
+    const size_t want = n * 160 + ((size_t)16 << 20);
+    c->tgt_store.reserve(want, want / 8);
     // temporaries of the upload and of the index build: ~80 B per point (11 octree-level id arrays, sort buffers, raw rows)
     arena_begin(c->arena, n * (96 + 4 * (xr + nr)) + ((size_t)1 << 20));
     double cen[3];
     DevBuf<float> tblock;
-    int st = upload_planar(c, xyz, xr, xc, nrm, nr, nc, n, tblock, /*temp=*/false, cen);
+    int st = upload_planar(c, xyz, xr, xc, nrm, nr, nc, n, tblock, &c->tgt_store, cen);
     if (st != SYMMICP_OK) return st;
     c->tgt_block = tblock.release();
     soa_from_block(c->tgt_block, n, c->tgt);
@@ -886,27 +555,33 @@ int symmicp_set_target(symmicp_ctx *c, const float *xyz, size_t xr, size_t xc, c
     if (c->cfg.corr == SYMMICP_CORR_IDENTITY) return SYMMICP_OK;
 
     const double t1 = now_s();
-    HIP_TRY(c, keep_alloc(c, (void **)&c->tq, sizeof(float4) * (n + 8)));     // + 8: the packet search reads a leaf's points in groups of 8
-    HIP_TRY(c, hipMemsetAsync(c->tq + n, 0, sizeof(float4) * 8, c->stream));
-    HIP_TRY(c, keep_alloc(c, (void **)&c->tn, sizeof(float4) * 2 * n));      // (point, normal) pair records
+    // (SYMMICP_OCT_LEAF > 0 sets the octree's leaf size; otherwise the build chooses it from what the cloud looks like)
+    IndexRequest rq{nullptr, nullptr, /*grid=*/true, /*oct_leaf=*/c->sw.oct_leaf > 0 ? c->sw.oct_leaf : 0};
+    HIP_TRY(c, c->tgt_store.alloc((void **)&rq.tq, sizeof(float4) * (n + 8)));     // + 8: the packet search reads a leaf's points in groups of 8
+    HIP_TRY(c, hipMemsetAsync(rq.tq + n, 0, sizeof(float4) * 8, c->stream));
+    HIP_TRY(c, c->tgt_store.alloc((void **)&rq.tn, sizeof(float4) * 2 * n));      // (point, normal) pair records
+    TargetIndex &ix = c->ix;      // (empty since free_target)
+    ix.tq = rq.tq; ix.tn = rq.tn; ix.n = c->n_t;      // all a BRUTE target has of an index
     if (c->cfg.corr == SYMMICP_CORR_BRUTE) {
-        launch_iota_f4(c->tgt.x, c->tgt.y, c->tgt.z, c->tgt.nx, c->tgt.ny, c->tgt.nz, c->n_t, c->tq, c->tn, c->stream);
+        launch_iota_f4(c->tgt.x, c->tgt.y, c->tgt.z, c->tgt.nx, c->tgt.ny, c->tgt.nz, c->n_t, rq.tq, rq.tn, c->stream);
         HIP_TRY(c, hipStreamSynchronize(c->stream));
         c->st.build_ms = (now_s() - t1) * 1e3;
         return SYMMICP_OK;
     }
-    st = build_index(c, c->tgt, c->n_t, /*want_grid=*/true, c->tq, c->tn, &c->boxes, &c->cells, &c->ix, &c->st.grid_level, &c->st.tree_levels,
-                     &c->onodes, &c->ctop, &c->notes);
+    BuiltIndex b;
+    st = build_index(c, c->tgt_store, c->tgt, c->n_t, rq, &b);
     if (st != SYMMICP_OK) { free_target(c); return st; }
+    ix = b.ix;
+    c->target_surface_like = b.surface_like;
+    c->notes = b.notes;
+    c->st.grid_level = b.grid_level; c->st.tree_levels = b.tree_levels;
     if (c->sw.debug_counters) {
-        HIP_TRY(c, hipMalloc((void **)&c->dbg, 12 * sizeof(unsigned long long)));
-        HIP_TRY(c, hipMemset(c->dbg, 0, 12 * sizeof(unsigned long long)));
-        c->ix.dbg = c->dbg;
+        HIP_TRY(c, hipMalloc((void **)&ix.dbg, 12 * sizeof(unsigned long long)));
+        HIP_TRY(c, hipMemset(ix.dbg, 0, 12 * sizeof(unsigned long long)));
     }
     if (!c->sw.debug_trace.empty()) {          // (alone: the production kernel with a timing-only trace)
-        HIP_TRY(c, hipMalloc((void **)&c->dbg_trace, ((size_t)1 << 22) * 8));      // (kTraceWords)
-        HIP_TRY(c, hipMemset(c->dbg_trace, 0, ((size_t)1 << 22) * 8));
-        c->ix.dbg_trace = c->dbg_trace;
+        HIP_TRY(c, hipMalloc((void **)&ix.dbg_trace, ((size_t)1 << 22) * 8));      // (kTraceWords)
+        HIP_TRY(c, hipMemset(ix.dbg_trace, 0, ((size_t)1 << 22) * 8));
     }
     c->have_index = true;
     c->st.build_ms = (now_s() - t1) * 1e3;
@@ -937,7 +612,7 @@ int symmicp_set_source(symmicp_ctx *c, const float *xyz, size_t xr, size_t xc, c
     const size_t r0 = bc > 0 ? b0 : 0;
     arena_begin(c->arena, nu * (56 + 4 * (xr + nr)) + ((size_t)1 << 20));      // (+8 B per point: the packet table's temporaries)
     DevBuf<float> full;
-    int st = upload_planar(c, xyz + r0 * xr, xr, xc, nrm ? nrm + r0 * nr : nullptr, nr, nc, nu, full, /*temp=*/true, nullptr);
+    int st = upload_planar(c, xyz + r0 * xr, xr, xc, nrm ? nrm + r0 * nr : nullptr, nr, nc, nu, full, /*store=*/nullptr, nullptr);
     if (st != SYMMICP_OK) return st;
     c->src_no_normals = !nrm;
     CloudSoA fs;
@@ -1120,8 +795,9 @@ int symmicp_get_correspondences(symmicp_ctx *c, int32_t *idx, float *d2, size_t 
         return SYMMICP_OK;
     }
     const int mode = c->cfg.corr == SYMMICP_CORR_IDENTITY ? 0 : (c->cfg.corr == SYMMICP_CORR_BRUTE ? 1 : 2);
-    if (mode == 0 && d2) {
-        // the identity pass streams without storing distances: evaluate them now from the current source positions
+    if (mode != 1 && d2) {
+        // the identity pass streams without storing distances, the tree passes store one only for the pairs they searched: evaluate all
+        // of them now, at the positions of the last pass
         const bool incr = resolved_apply(c->cfg) == SYMMICP_APPLY_INCREMENTAL;
         Affine X{};
         float I[16];
@@ -1129,21 +805,11 @@ int symmicp_get_correspondences(symmicp_ctx *c, int32_t *idx, float *d2, size_t 
         const float *m = incr ? I : c->X;
         for (int k = 0; k < 12; k++) X.m[k] = m[k];
         X.nrm_w = 0.f;
-        launch_identity_d2(incr ? c->cur : c->src0, X, c->tgt, c->src_off, c->n_loc, c->d2, c->stream);
-    }
-    if (mode == 2 && d2) {
-        // the tree passes store a distance only for the pairs they searched: evaluate all of them at the positions of the last pass
-        const bool incr = resolved_apply(c->cfg) == SYMMICP_APPLY_INCREMENTAL;
-        Affine X{};
-        float I[16];
-        identity16(I);
-        const float *m = incr ? I : c->X;
-        for (int k = 0; k < 12; k++) X.m[k] = m[k];
-        X.nrm_w = 0.f;
-        launch_pairs_d2(incr ? c->cur : c->src0, X, c->pos, c->tq, c->n_t, c->n_loc, c->d2, c->stream);
+        if (mode == 0) launch_identity_d2(incr ? c->cur : c->src0, X, c->tgt, c->src_off, c->n_loc, c->d2, c->stream);
+        else launch_pairs_d2(incr ? c->cur : c->src0, X, c->pos, c->ix.tq, c->n_t, c->n_loc, c->d2, c->stream);
     }
     // (after a pass with a rejector -- trim fraction, one-to-one, median -- a row that was no candidate, or was rejected, is reported as rejected)
-    launch_corr_out(c->pos, c->best64, c->d2, c->tq, c->src_order, c->n_loc, mode, c->src_off, d_idx.p, d_d2.p,
+    launch_corr_out(c->pos, c->best64, c->d2, c->ix.tq, c->src_order, c->n_loc, mode, c->src_off, d_idx.p, d_d2.p,
                     c->rej.keys_valid() ? c->rej.keys : nullptr, c->rej.last.tau_bits, c->stream);
     if (idx) HIP_TRY(c, hipMemcpyAsync(idx, d_idx.p, sizeof(int32_t) * need, hipMemcpyDeviceToHost, c->stream));
     if (d2) HIP_TRY(c, hipMemcpyAsync(d2, d_d2.p, sizeof(float) * need, hipMemcpyDeviceToHost, c->stream));
@@ -1170,35 +836,6 @@ int symmicp_get_source(symmicp_ctx *c, float *xyz, float *nrm, size_t cap)
     if (xyz) HIP_TRY(c, hipMemcpyAsync(xyz, dx.p, sizeof(float) * 3 * need, hipMemcpyDeviceToHost, c->stream));
     if (nrm) HIP_TRY(c, hipMemcpyAsync(nrm, dn.p, sizeof(float) * 3 * need, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    return SYMMICP_OK;
-}
-
-// diagnostic: the pair certificates as they stand, in the share's sorted order: (ref.xyz, L), the neighbourhood's 8 members and radius, the
-// current winner, target points named by their ROW in the caller's target cloud (the device holds sorted positions)
-int symmicp_get_certificates(symmicp_ctx *c, float *cert4, uint32_t *hood8, float *hood_radius, int32_t *winner_row, size_t cap)
-{
-    if (!c || !cert4) return SYMMICP_ERR_ARG;
-    if (!c->begun || !c->cert) return fail(c, SYMMICP_ERR_STATE, "no tree pass has run yet");
-    if (cap < c->n_loc) return fail(c, SYMMICP_ERR_SIZE, "output too small");
-    HIP_TRY(c, hipSetDevice(c->device));
-    HIP_TRY(c, hipMemcpyAsync(cert4, c->cert, sizeof(float) * 4 * c->n_loc, hipMemcpyDeviceToHost, c->stream));
-    std::vector<int32_t> pos(winner_row ? c->n_loc : 0);
-    std::vector<float> tq((hood8 || winner_row) ? (size_t)c->n_t * 4 : 0);
-    if (hood8) HIP_TRY(c, hipMemcpyAsync(hood8, c->certk, sizeof(uint32_t) * 8 * c->n_loc, hipMemcpyDeviceToHost, c->stream));
-    std::vector<float> tr(hood_radius ? (size_t)c->n_loc * 2 : 0);
-    if (hood_radius) HIP_TRY(c, hipMemcpyAsync(tr.data(), c->hoodr, sizeof(float) * 2 * c->n_loc, hipMemcpyDeviceToHost, c->stream));
-    if (winner_row) HIP_TRY(c, hipMemcpyAsync(pos.data(), c->pos, sizeof(int32_t) * c->n_loc, hipMemcpyDeviceToHost, c->stream));
-    if (!tq.empty()) HIP_TRY(c, hipMemcpyAsync(tq.data(), c->tq, sizeof(float) * 4 * c->n_t, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    auto row_of = [&](uint32_t p) -> uint32_t {
-        if (p >= c->n_t) return 0xFFFFFFFFu;
-        uint32_t r; std::memcpy(&r, &tq[(size_t)p * 4 + 3], 4); return r;      // the row rides in the w slot of the sorted point
-    };
-    for (size_t i = 0; i < c->n_loc; i++) {
-        if (hood8) for (int k = 0; k < 8; k++) hood8[i * 8 + k] = row_of(hood8[i * 8 + k]);
-        if (winner_row) winner_row[i] = pos[i] < 0 ? -1 : (int32_t)row_of((uint32_t)pos[i]);
-        if (hood_radius) hood_radius[i] = tr[i * 2];
-    }
     return SYMMICP_OK;
 }
 

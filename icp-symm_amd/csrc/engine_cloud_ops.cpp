@@ -4,58 +4,8 @@
 #include "engine_internal.h"
 #include "orient_core.h"
 
-// ---- the scratch index of an operation ------------------------------------------------------------------------------------
-// The caller's cloud uploaded and a box tree built over its Morton order, behind the target's arrays in the keep-arena; the destructor
-// gives all of it back (stream sync, the overflow allocations freed, keep.off and target_surface_like restored), on every exit.
-// Declare it BEFORE the DevBufs that work on its index: they have to be destroyed before this destructor syncs and rewinds.
+// Every operation runs on a ScratchIndex (engine_index.cpp): the caller's cloud and a box tree over it behind the target's arrays, given back on every exit.
 namespace {
-struct ScratchIndex {
-    TargetIndex ix{};
-    ScratchIndex() = default;
-    ScratchIndex(const ScratchIndex &) = delete;
-    ScratchIndex &operator=(const ScratchIndex &) = delete;
-    ~ScratchIndex()
-    {
-        if (!c) return;      // begin() never got as far as saving the state
-        (void)hipStreamSynchronize(c->stream);
-        while (c->keep_extra.size() > extra0) { hipFree(c->keep_extra.back()); c->keep_extra.pop_back(); }
-        c->keep.off = keep_off0;
-        c->target_surface_like = surf0;
-    }
-    // nrm may be NULL (zero normals).  temp_bytes: what the caller will take from the arena afterwards.
-    int begin(symmicp_ctx *ctx, const float *xyz, size_t xr, size_t xc, const float *nrm, size_t nr, size_t nc, size_t n, size_t temp_bytes)
-    {
-        HIP_TRY(ctx, hipSetDevice(ctx->device));
-        if (ctx->keep.cap == 0) {
-            // no target yet: give the keep-arena the size this cloud needs (a later set_target reuses it)
-            const size_t want = n * 96 + ((size_t)4 << 20);
-            if (hipMalloc((void **)&ctx->keep.base, want) == hipSuccess) { ctx->keep.cap = want; ctx->keep.off = 0; }
-            else (void)hipGetLastError();
-        }
-        c = ctx;
-        keep_off0 = c->keep.off;
-        extra0 = c->keep_extra.size();
-        surf0 = c->target_surface_like;
-        arena_begin(c->arena, n * (96 + 4 * (xr + (nrm ? nr : 0))) + temp_bytes + ((size_t)1 << 20));
-        DevBuf<float> block;      // (from the keep-arena: not owned)
-        if (int st = upload_planar(c, xyz, xr, xc, nrm, nr, nc, n, block, /*temp=*/false, nullptr)) return st;
-        CloudSoA cl;
-        soa_from_block(block.p, n, cl);
-        float4 *tq = nullptr, *tn = nullptr, *boxes = nullptr;
-        uint2 *cells = nullptr;
-        if (keep_alloc(c, (void **)&tq, sizeof(float4) * (n + 8)) != hipSuccess || keep_alloc(c, (void **)&tn, sizeof(float4) * 2 * n) != hipSuccess) {
-            (void)hipGetLastError();
-            return fail(c, SYMMICP_ERR_HIP, "out of device memory");
-        }
-        return build_index(c, cl, (uint32_t)n, /*want_grid=*/false, tq, tn, &boxes, &cells, &ix, nullptr, nullptr);
-    }
-
-private:
-    symmicp_ctx *c = nullptr;      // set once the three words below are saved
-    size_t keep_off0 = 0, extra0 = 0;
-    bool surf0 = false;
-};
-
 // the tail of every read-back: wait for the stream, then report what a launch on it left behind
 int stream_done(symmicp_ctx *c)
 {
@@ -92,7 +42,7 @@ extern "C" {
 // ---- normals pre-step (MyICP::estimateNormals, myicp.cpp:152-172) --------------------------------
 // Runs on a context the caller owns (its stream and arenas are reused: a tracker that estimates normals per scan pays no
 // context set-up); the context's target and source stay as they are -- what the estimate allocates behind the target's arrays
-// in the keep-arena is released again.
+// in the target's store is released again.
 // symmicp_ctx_knn runs the same index build and walk, and reads back the neighbour set (rows, d2) instead of the normals.
 static bool normals_args_ok(const float *xyz, size_t n, int k)
 {
@@ -729,7 +679,7 @@ static int voxel_downsample(symmicp_ctx *c, const float *xyz, size_t xr, size_t 
     arena_begin(c->arena, n * (128 + 4 * (xr + (with_nrm ? nr : 0))) + ((size_t)1 << 20));
     const uint32_t n32 = (uint32_t)n;
     DevBuf<float> block;
-    int st = upload_planar(c, xyz, xr, xc, with_nrm ? nrm : nullptr, nr, nc, n, block, /*temp=*/true, nullptr);
+    int st = upload_planar(c, xyz, xr, xc, with_nrm ? nrm : nullptr, nr, nc, n, block, /*store=*/nullptr, nullptr);
     if (st != SYMMICP_OK) return st;
     CloudSoA cl;
     soa_from_block(block.p, n, cl);

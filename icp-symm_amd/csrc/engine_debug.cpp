@@ -8,11 +8,11 @@ void dump_packet_trace(symmicp_ctx *c)
 {
     if (FILE *f = std::fopen(c->sw.debug_trace.c_str(), "wb")) {
         std::vector<unsigned long long> t(kTraceWords);
-        hipMemcpy(t.data(), c->dbg_trace, t.size() * 8, hipMemcpyDeviceToHost);
+        hipMemcpy(t.data(), c->ix.dbg_trace, t.size() * 8, hipMemcpyDeviceToHost);
         std::fwrite(t.data(), 8, t.size(), f);
         std::fclose(f);
     }
-    hipMemset(c->dbg_trace, 0, kTraceWords * 8);
+    hipMemset(c->ix.dbg_trace, 0, kTraceWords * 8);
 }
 
 

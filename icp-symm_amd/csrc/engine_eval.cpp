@@ -90,31 +90,25 @@ int eval_run(symmicp_ctx *c, EvalArgs args, const float *X16, const float *X_def
     for (size_t k = 0; k < K; k++)
         for (int e = 0; e < 12; e++) X12[12 * k + e] = X16 ? X16[16 * k + e] : X_default[e];
     std::vector<double> sums(K * kEvalNSum);
-    char *d = nullptr;
-    HIP_TRY(c, hipMalloc((void **)&d, total));
-    auto body = [&]() -> int {
-        HIP_TRY(c, hipMemcpyAsync(d + o_X, X12.data(), sizeof(float) * 12 * K, hipMemcpyHostToDevice, c->stream));
-        args.r2 = max_dist > 0.f ? max_dist * max_dist : std::numeric_limits<float>::infinity();
-        args.nn = reinterpret_cast<int32_t *>(d + o_nn);
-        args.d2 = reinterpret_cast<float *>(d + o_d2);
-        args.partials = reinterpret_cast<double *>(d + o_part);
-        for (size_t k0 = 0; k0 < K; k0 += Kc) {
-            const size_t kn = std::min(Kc, K - k0);
-            args.X12 = reinterpret_cast<const float *>(d + o_X) + 12 * k0;
-            launch_eval(args, (uint32_t)kn, reinterpret_cast<double *>(d + o_sums) + k0 * kEvalNSum, c->stream);
-            HIP_TRY(c, hipGetLastError());
-            if (nn_out) HIP_TRY(c, hipMemcpyAsync(nn_out + k0 * ns, args.nn, sizeof(int32_t) * kn * ns, hipMemcpyDeviceToHost, c->stream));
-            if (d2_out) HIP_TRY(c, hipMemcpyAsync(d2_out + k0 * ns, args.d2, sizeof(float) * kn * ns, hipMemcpyDeviceToHost, c->stream));
-            HIP_TRY(c, hipStreamSynchronize(c->stream));      // (the next chunk writes the same arrays)
-        }
-        HIP_TRY(c, hipMemcpyAsync(sums.data(), d + o_sums, sizeof(double) * K * kEvalNSum, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        return SYMMICP_OK;
-    };
-    const int st = body();
-    (void)hipStreamSynchronize(c->stream);
-    (void)hipFree(d);
-    if (st != SYMMICP_OK) return st;
+    OwnSearch own(c);      // (no index of its own: the block, freed once the stream is done with it on every exit)
+    HIP_TRY(c, hipMalloc((void **)&own.d, total));
+    char *d = own.d;
+    HIP_TRY(c, hipMemcpyAsync(d + o_X, X12.data(), sizeof(float) * 12 * K, hipMemcpyHostToDevice, c->stream));
+    args.r2 = max_dist > 0.f ? max_dist * max_dist : std::numeric_limits<float>::infinity();
+    args.nn = reinterpret_cast<int32_t *>(d + o_nn);
+    args.d2 = reinterpret_cast<float *>(d + o_d2);
+    args.partials = reinterpret_cast<double *>(d + o_part);
+    for (size_t k0 = 0; k0 < K; k0 += Kc) {
+        const size_t kn = std::min(Kc, K - k0);
+        args.X12 = reinterpret_cast<const float *>(d + o_X) + 12 * k0;
+        launch_eval(args, (uint32_t)kn, reinterpret_cast<double *>(d + o_sums) + k0 * kEvalNSum, c->stream);
+        HIP_TRY(c, hipGetLastError());
+        if (nn_out) HIP_TRY(c, hipMemcpyAsync(nn_out + k0 * ns, args.nn, sizeof(int32_t) * kn * ns, hipMemcpyDeviceToHost, c->stream));
+        if (d2_out) HIP_TRY(c, hipMemcpyAsync(d2_out + k0 * ns, args.d2, sizeof(float) * kn * ns, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));      // (the next chunk writes the same arrays)
+    }
+    HIP_TRY(c, hipMemcpyAsync(sums.data(), d + o_sums, sizeof(double) * K * kEvalNSum, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
     for (size_t k = 0; k < K; k++) {
         const double *s = sums.data() + k * kEvalNSum;
         symmicp_evaluation &e = out[k];
@@ -148,37 +142,29 @@ int symmicp_ctx_evaluate_registration(symmicp_ctx *c, const float *src_xyz, size
     planar_stage(src_xyz, src_row_stride, src_col_stride, ns, hs);
     planar_stage(tgt_xyz, tgt_row_stride, tgt_col_stride, nt, ht);
     const size_t o_t = 0, o_s = (sizeof(float) * 3 * nt + 255) & ~(size_t)255, total = o_s + sizeof(float) * 3 * ns;
-    char *d = nullptr;
-    HIP_TRY(c, hipMalloc((void **)&d, total));
-    ReverseIndex ri;       // (a scratch index: the context's own indexes stay as they were)
-    auto body = [&]() -> int {
-        float *t = reinterpret_cast<float *>(d + o_t), *s = reinterpret_cast<float *>(d + o_s);
-        HIP_TRY(c, hipMemcpyAsync(t, ht.data(), sizeof(float) * 3 * nt, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(c, hipMemcpyAsync(s, hs.data(), sizeof(float) * 3 * ns, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        CloudSoA ct{t, t + nt, t + 2 * nt, t, t + nt, t + 2 * nt};      // (no normals: the build reads the slots and nothing keeps them)
-        if (int st = build_reverse_index(c, ct, (uint32_t)nt, nullptr, ri)) return st;
-        // the source's Morton order: the lanes of a wave then walk one region of the tree.  The points stay where they are and are read
-        // through the order (12 B gathered per row and transform; the results are written by caller row either way)
-        CloudSoA cs{s, s + ns, s + 2 * ns, s, s + ns, s + 2 * ns};
-        arena_begin(c->arena, ns * 24 + ((size_t)1 << 20));
-        DevBuf<uint32_t> order;
-        float origin[3], h0;
-        if (int st = morton_order(c, cs, (uint32_t)ns, order, nullptr, origin, &h0)) return st;
-        EvalArgs a{};
-        a.ix = ri.ix;
-        a.sx = cs.x; a.sy = cs.y; a.sz = cs.z;
-        a.order = order.p; a.gather = 1; a.ns = (uint32_t)ns;
-        a.tx = ct.x; a.ty = ct.y; a.tz = ct.z;
-        float I[16];
-        identity16(I);
-        return eval_run(c, a, X16, I, K, max_dist, out, nn_out, d2_out);
-    };
-    const int st = body();
-    (void)hipStreamSynchronize(c->stream);
-    drop_reverse_index(ri, true);
-    (void)hipFree(d);
-    return st;
+    OwnSearch own(c);      // (a scratch index: the context's own indexes stay as they were)
+    HIP_TRY(c, hipMalloc((void **)&own.d, total));
+    float *t = reinterpret_cast<float *>(own.d + o_t), *s = reinterpret_cast<float *>(own.d + o_s);
+    HIP_TRY(c, hipMemcpyAsync(t, ht.data(), sizeof(float) * 3 * nt, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(s, hs.data(), sizeof(float) * 3 * ns, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    CloudSoA ct{t, t + nt, t + 2 * nt, t, t + nt, t + 2 * nt};      // (no normals: the build reads the slots and nothing keeps them)
+    if (int st = build_reverse_index(c, ct, (uint32_t)nt, nullptr, own.ri)) return st;
+    // the source's Morton order: the lanes of a wave then walk one region of the tree.  The points stay where they are and are read
+    // through the order (12 B gathered per row and transform; the results are written by caller row either way)
+    CloudSoA cs{s, s + ns, s + 2 * ns, s, s + ns, s + 2 * ns};
+    arena_begin(c->arena, ns * 24 + ((size_t)1 << 20));
+    DevBuf<uint32_t> order;
+    float origin[3], h0;
+    if (int st = morton_order(c, cs, (uint32_t)ns, order, nullptr, origin, &h0)) return st;
+    EvalArgs a{};
+    a.ix = own.ri.ix;
+    a.sx = cs.x; a.sy = cs.y; a.sz = cs.z;
+    a.order = order.p; a.gather = 1; a.ns = (uint32_t)ns;
+    a.tx = ct.x; a.ty = ct.y; a.tz = ct.z;
+    float I[16];
+    identity16(I);
+    return eval_run(c, a, X16, I, K, max_dist, out, nn_out, d2_out);
 }
 
 int symmicp_evaluate_registration(int device, const float *src_xyz, size_t src_row_stride, size_t src_col_stride, size_t ns,
@@ -202,23 +188,18 @@ int symmicp_evaluate(symmicp_ctx *c, const float *X16, size_t K, float max_dist,
     HIP_TRY(c, hipSetDevice(c->device));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     // a TREE context walks its own index; the others get a scratch one over the target they hold, dropped before returning
+    // (a BRUTE context's c->ix holds tq and tn only, an IDENTITY context's nothing: have_index is false on both)
     const bool own = c->cfg.corr == SYMMICP_CORR_TREE && c->have_index && c->ix.onodes;
-    ReverseIndex ri;
-    auto body = [&]() -> int {
-        if (!own)
-            if (int st = build_reverse_index(c, c->tgt, c->n_t, nullptr, ri)) return st;
-        EvalArgs a{};
-        a.ix = own ? c->ix : ri.ix;
-        a.ix.dbg = nullptr; a.ix.dbg_trace = nullptr;
-        a.sx = c->src0.x; a.sy = c->src0.y; a.sz = c->src0.z;      // the source as set_source received it, in the share's order
-        a.order = c->src_order; a.gather = 0; a.ns = c->n_loc;
-        a.tx = c->tgt.x; a.ty = c->tgt.y; a.tz = c->tgt.z;
-        return eval_run(c, a, X16, c->X, K, max_dist, out, nn_out, d2_out);
-    };
-    const int st = body();
-    (void)hipStreamSynchronize(c->stream);
-    if (!own) drop_reverse_index(ri, true);
-    return st;
+    OwnSearch scratch(c);
+    if (!own)
+        if (int st = build_reverse_index(c, c->tgt, c->n_t, nullptr, scratch.ri)) return st;
+    EvalArgs a{};
+    a.ix = own ? c->ix : scratch.ri.ix;
+    a.ix.dbg = nullptr; a.ix.dbg_trace = nullptr;
+    a.sx = c->src0.x; a.sy = c->src0.y; a.sz = c->src0.z;      // the source as set_source received it, in the share's order
+    a.order = c->src_order; a.gather = 0; a.ns = c->n_loc;
+    a.tx = c->tgt.x; a.ty = c->tgt.y; a.tz = c->tgt.z;
+    return eval_run(c, a, X16, c->X, K, max_dist, out, nn_out, d2_out);
 }
 
 }  // extern "C"

@@ -1,6 +1,7 @@
 // engine_internal.h -- what the host-side translation units of libsymmicp share: the context, its scratch arenas, the environment
 // switches, the RCCL loader and the helpers every entry point uses.
-//   engine.cpp           lifetime, configuration, uploads, index build, set_target / set_source, getters, statistics
+//   engine.cpp           lifetime, configuration, set_target / set_source, getters, statistics
+//   engine_index.cpp     the index: its store (IndexStore), upload_planar, morton_order, build_index, ScratchIndex, the reverse index
 //   engine_cloud_ops.cpp stand-alone cloud operations on a scratch index: normals and k-NN, radius search, FPFH, ISS keypoints, intensity
 //                        gradient; voxel downsampling
 //   engine_loop.cpp      the iteration loop: one pass (run_pass), device-driven runs of passes (run_batch), begin / step / align, result block;
@@ -148,14 +149,51 @@ struct IndexNotes {
     uint32_t nblocks = 0, ctop_len = 0;        // occupied super-cell blocks of the cell table, length of ctop
 };
 
-// An index with storage of its own, for the reverse search of reciprocal passes: build_index allocates through the context's keep-arena,
-// which belongs to the target (set_target and the ScratchIndex of engine_cloud_ops.cpp rewind it), so build_reverse_index points it at this one
-// for the length of the build.
-struct ReverseIndex {
-    Arena keep;
+// The device memory of one index: a block that only grows, bump-allocated in 256-byte steps, and the allocations that did not fit it.
+// The context's target owns one (the scratch index of a cloud operation goes behind the target's arrays, under a mark), every
+// ReverseIndex one.  (engine_index.cpp)
+struct IndexStore {
+    struct Mark { size_t off = 0, extras = 0; };
+    IndexStore() = default;
+    IndexStore(const IndexStore &) = delete;
+    IndexStore &operator=(const IndexStore &) = delete;
+    ~IndexStore() { release(); }
+    hipError_t alloc(void **out, size_t bytes);      // from the block when it fits, else a hipMalloc of its own (tracked)
+    // cap() < want: the block is replaced by one of want + slack bytes (contents dead); if that fails, every alloc falls back
+    void reserve(size_t want, size_t slack);
+    Mark mark() const { return Mark{blk.off, extra.size()}; }
+    void rewind(Mark m);                             // what was allocated since the mark is given back (beside the block: freed)
+    void reset() { rewind(Mark{}); }                 // empty; the block is kept for the next index
+    void release();                                  // everything freed; idempotent
+    size_t cap() const { return blk.cap; }
+    size_t used() const { return blk.off; }
+    size_t beside() const { return extra.size(); }   // allocations that did not fit the block
+
+private:
+    Arena blk;
     std::vector<void *> extra;
+};
+
+// What build_index is asked for, and what it returns
+struct IndexRequest {
+    float4 *tq, *tn;      // the caller's arrays: n sorted points (the target's and the reverse index's: + 8 zeroed, the packet search reads a
+                          // leaf's points in groups of 8) and n (point, normal) pair records
+    bool grid;            // the cell table, and with it the surface-like decision
+    int oct_leaf;         // -1: no octree; 0: leaves of 24 points on a surface-like cloud, else of 8; > 0: that size
+};
+struct BuiltIndex {
+    TargetIndex ix{};
+    bool surface_like = false;      // (grid only) decides the first-pass regime
+    int32_t grid_level = 0, tree_levels = 0;
+    IndexNotes notes;
+};
+
+// An index with a store of its own: the source index of reciprocal passes, the scratch index of the evaluation and of the reverse probe
+struct ReverseIndex {
+    IndexStore store;
     TargetIndex ix{};
     bool valid = false;
+    void drop() { store.reset(); ix = TargetIndex{}; valid = false; }      // back to "not built"; the block is kept for the next build
 };
 
 // The rejectors of a context (symmicp_set_trim_fraction / _one_to_one / _median_factor / _reciprocal): what is set, the buffers a rejecting
@@ -227,8 +265,7 @@ struct NdtState {
 struct symmicp_ctx {
     Switches sw;                     // environment switches as they stood at symmicp_create
     Arena arena;                     // temporaries of one public call
-    Arena keep;                      // the target's persistent arrays (reused by the next set_target)
-    std::vector<void *> keep_extra;  // ... and those that did not fit
+    IndexStore tgt_store;            // the target's persistent arrays (reused by the next set_target)
     ShmExchange shm;
     symmicp_config cfg{};
     int loss = SYMMICP_LOSS_NONE;    // robust loss (symmicp_set_robust_loss) and its scale: read by every pass
@@ -256,16 +293,10 @@ struct symmicp_ctx {
     uint32_t n_t = 0;
     float *tgt_block = nullptr;      // 6 planar arrays
     CloudSoA tgt{};
-    float4 *tq = nullptr, *tn = nullptr;
-    float4 *boxes = nullptr;
-    float4 *onodes = nullptr;
-    uint2 *cells = nullptr;
-    uint32_t *ctop = nullptr;
-    unsigned long long *dbg = nullptr;   // debug counters (SYMMICP_DEBUG_COUNTERS)
-    unsigned long long *dbg_trace = nullptr;   // per-packet trace of the first pass (SYMMICP_DEBUG_TRACE=file)
-    TargetIndex ix{};
-    bool have_index = false;
-    bool target_surface_like = false;   // decides the first-pass regime (build_index)
+    TargetIndex ix{};                   // TREE: the whole index; BRUTE: tq, tn and n only; IDENTITY: empty.  dbg / dbg_trace: own allocations
+                                        // (SYMMICP_DEBUG_COUNTERS; SYMMICP_DEBUG_TRACE=file, the per-packet trace of the first pass)
+    bool have_index = false;            // the tree index exists (TREE)
+    bool target_surface_like = false;   // decides the first-pass regime (set_target, from build_index's result)
     IndexNotes notes;                   // (tests: symmicp_ctx_index_info)
     float pivot[3] = {0, 0, 0};
     // source share
@@ -358,8 +389,6 @@ inline hipError_t grow(T *&p, size_t &cap, size_t want)
     return e;
 }
 
-// persistent allocation for the target: from the context's keep-arena when it fits, else its own hipMalloc (tracked)
-hipError_t keep_alloc(symmicp_ctx *c, void **out, size_t bytes);
 // rewind the arena and make sure it holds `want` bytes (contents are dead: called at the start of a public call)
 void arena_begin(Arena &a, size_t want);
 
@@ -415,25 +444,47 @@ inline int resolved_apply(const symmicp_config &c)
 void free_target(symmicp_ctx *c);
 void forget_source(symmicp_ctx *c);
 void flush_events(symmicp_ctx *c);
-// the octree over cl (n points, a planar cloud in device memory) into ri's own storage, its tq relabelled through labels (device,
-// [n]; null: the row).  Rewinds the context's scratch arena.  release: back to the state before the first build (the storage is freed).
+// engine_index.cpp
+// the octree over cl (n points, a planar cloud in device memory) into ri's own store, its tq relabelled through labels (device, [n];
+// null: the row).  Rewinds the context's scratch arena.  On failure ri is dropped.
 int build_reverse_index(symmicp_ctx *c, const CloudSoA &cl, uint32_t n, const uint32_t *labels, ReverseIndex &ri);
-void drop_reverse_index(ReverseIndex &ri, bool release);
-// host strided cloud -> device block of 6 planar arrays, from the scratch arena (temp) or the keep-arena; nrm null: zero normals;
-// centroid: null, or the fp64 mean of xyz in row order.  (This and build_index are shared by two files of the library only: hidden, so
-// the library's dynamic symbols stay what they were.)
+// What a one-shot search allocates for itself: a reverse index and one device block.  Kernels on the stream may still use both when an
+// error path leaves: the destructor synchronises the stream, then frees them.
+struct OwnSearch {
+    symmicp_ctx *c;
+    char *d = nullptr;
+    ReverseIndex ri;
+    explicit OwnSearch(symmicp_ctx *ctx) : c(ctx) {}
+    ~OwnSearch() { (void)hipStreamSynchronize(c->stream); ri.store.release(); if (d) (void)hipFree(d); }
+};
+// host strided cloud -> device block of 6 planar arrays, from `store` or (null) from the scratch arena; nrm null: zero normals;
+// centroid: null, or the fp64 mean of xyz in row order.  (This and build_index are hidden, so the library's dynamic symbols stay what they were.)
 __attribute__((visibility("hidden")))
 int upload_planar(symmicp_ctx *c, const float *xyz, size_t xr, size_t xc, const float *nrm, size_t nr, size_t nc, size_t n, DevBuf<float> &block,
-                  bool temp, double centroid[3]);
-// the index over cl (n points, planar, device memory) into tq / tn and what it allocates through keep_alloc; does not rewind the scratch
-// arena.  The outputs belong to the caller's context as soon as they are set: on failure the caller's free_target() / scope releases them.
+                  IndexStore *store, double centroid[3]);
+// the index over cl (n points, planar, device memory) into rq.tq / rq.tn and what it allocates from `store`.  Of the context it uses the stream,
+// the scratch arena (not rewound), the grid-tuning switches and the error string, and writes nothing else.
 __attribute__((visibility("hidden")))
-int build_index(symmicp_ctx *c, const CloudSoA &cl, uint32_t n, bool want_grid, float4 *tq, float4 *tn, float4 **boxes_out, uint2 **cells_out,
-                TargetIndex *ix_out, int32_t *glevel_out, int32_t *nlevels_out, float4 **onodes_out = nullptr, uint32_t **ctop_out = nullptr,
-                IndexNotes *notes = nullptr);
+int build_index(symmicp_ctx *c, IndexStore &store, const CloudSoA &cl, uint32_t n, const IndexRequest &rq, BuiltIndex *out);
 // Morton order of a planar cloud, temporaries and result from the context's scratch arena: vals[n] = sorted position -> row (keys_out:
 // null, or it keeps the sorted keys); origin / h0_out: the Morton frame.  SYMMICP_ERR_ARG for non-finite coordinates.
 int morton_order(symmicp_ctx *c, const CloudSoA &cl, uint32_t n, DevBuf<uint32_t> &vals, DevBuf<uint32_t> *keys_out, float origin[3], float *h0_out);
+// The scratch index of a cloud operation: the caller's cloud uploaded and a box tree built over its Morton order, behind the target's arrays
+// in the target's store; the destructor gives all of it back (stream sync, then the store rewound to the mark), on every exit.
+// Declare it BEFORE the DevBufs that work on its index: they have to be destroyed before this destructor syncs and rewinds.
+struct ScratchIndex {
+    TargetIndex ix{};
+    ScratchIndex() = default;
+    ScratchIndex(const ScratchIndex &) = delete;
+    ScratchIndex &operator=(const ScratchIndex &) = delete;
+    ~ScratchIndex();
+    // nrm may be NULL (zero normals).  temp_bytes: what the caller will take from the arena afterwards.
+    int begin(symmicp_ctx *ctx, const float *xyz, size_t xr, size_t xc, const float *nrm, size_t nr, size_t nc, size_t n, size_t temp_bytes);
+
+private:
+    symmicp_ctx *c = nullptr;      // set once the mark is taken
+    IndexStore::Mark mark;
+};
 // A one-shot entry: f(c) on a default context of its own on `device`, destroyed again.  The entry checks its arguments first, so that a
 // bad call returns SYMMICP_ERR_ARG without touching the device.
 template <class F>

@@ -30,7 +30,7 @@ static int prepare_rejectors(symmicp_ctx *c, RejectArgs &r)
         j.src_ix_builds++;
         if (c->sw.debug_host) {
             std::fprintf(stderr, "[symmicp host] source index: %u points, %zu bytes in its arena (+%zu allocations beside it), built in %.3f ms\n", c->n_loc,
-                         j.src_ix.keep.off, j.src_ix.extra.size(), (now_s() - t0) * 1e3);
+                         j.src_ix.store.used(), j.src_ix.store.beside(), (now_s() - t0) * 1e3);
         }
     }
     j.recip_args.six = j.src_ix.ix;
@@ -173,8 +173,8 @@ static int launch_identity(symmicp_ctx *c, const PassArgs &a)
 static int launch_brute(symmicp_ctx *c, const PassArgs &a)
 {
     const int blocks = capped_blocks(c->n_loc, host_pass_cap(c->sw.pass_blocks), false, 1);
-    launch_nn_brute(a.in, c->n_loc, a.X, c->tq, c->n_t, c->best64, c->stream);
-    launch_pass_indexed(a, c->tn, blocks, c->stream);
+    launch_nn_brute(a.in, c->n_loc, a.X, c->ix.tq, c->n_t, c->best64, c->stream);
+    launch_pass_indexed(a, c->ix.tn, blocks, c->stream);
     return blocks;
 }
 
@@ -270,7 +270,7 @@ static int run_pass(symmicp_ctx *c, const float Xapply[16], bool from_cur, bool 
     }
     if (ev) c->ev_used++;
     c->t_last_done = now_s(); c->n_pass_timed++;
-    if (c->dbg_trace && first) dump_packet_trace(c);
+    if (c->ix.dbg_trace && first) dump_packet_trace(c);
     if (c->ix.dbg) print_pass_counters(c, first, tree_pass ? (long long)list_len : -1);
     std::memcpy(c->last.s, c->h_sums, sizeof(double) * kNSum);
     if (tree_pass) c->last.s[kFeedbackListSlot] = c->last.s[kFeedbackCountSlot] = 0.0;      // those slots carried the feedback, not sums
@@ -574,7 +574,7 @@ static int check_ready(symmicp_ctx *c)
     if (c->cfg.corr == SYMMICP_CORR_IDENTITY && c->n_s_total != c->n_t)
         return fail(c, SYMMICP_ERR_SIZE, "identity pairing needs N_s == N_t (func.cpp:21)");
     if (c->cfg.corr == SYMMICP_CORR_TREE && !c->have_index) return fail(c, SYMMICP_ERR_STATE, "target index missing");
-    if (c->cfg.corr != SYMMICP_CORR_IDENTITY && !c->tq) return fail(c, SYMMICP_ERR_STATE, "target was set under a different corr mode");
+    if (c->cfg.corr != SYMMICP_CORR_IDENTITY && !c->ix.tq) return fail(c, SYMMICP_ERR_STATE, "target was set under a different corr mode");
     if (c->cfg.mode == SYMMICP_MODE_COLOR) {
         if (c->nranks > 1) return fail(c, SYMMICP_ERR_STATE, "SYMMICP_MODE_COLOR runs on single-rank contexts only");
         if (!c->have_src_int || !c->have_tgt_color)

@@ -309,7 +309,7 @@ int symmicp_ctx_ndt_map(symmicp_ctx *c, const float *xyz, size_t row_stride, siz
     NdtMap map;
     auto body = [&]() -> int {
         DevBuf<float> block;
-        if (int st = upload_planar(c, xyz, row_stride, col_stride, nullptr, 0, 0, n, block, /*temp=*/true, nullptr)) return st;
+        if (int st = upload_planar(c, xyz, row_stride, col_stride, nullptr, 0, 0, n, block, /*store=*/nullptr, nullptr)) return st;
         CloudSoA cl;
         soa_from_block(block.p, n, cl);
         if (int st = ndt_build(c, cl, n, *cfg, map)) return st;

@@ -14,7 +14,7 @@ int copy_back(symmicp_ctx *c, void *dst, const void *src, size_t bytes)
     return SYMMICP_OK;
 }
 
-bool has_target_index(const symmicp_ctx *c) { return c->have_index && c->cfg.corr == SYMMICP_CORR_TREE && c->tq && c->boxes && c->onodes; }
+bool has_target_index(const symmicp_ctx *c) { return c->have_index && c->cfg.corr == SYMMICP_CORR_TREE && c->ix.tq && c->ix.boxes && c->ix.onodes; }
 
 void fill_info(const symmicp_ctx *c, symmicp_index_info *o)
 {
@@ -65,18 +65,47 @@ int symmicp_ctx_index_arrays(symmicp_ctx *c, float *tq, float *tn, float *boxes,
     HIP_TRY(c, hipSetDevice(c->device));
     const size_t f4 = sizeof(float4);
     const struct { void *dst; const void *src; size_t bytes; } parts[] = {
-        {tq, c->tq, f4 * o.n},
-        {tn, c->tn, f4 * 2 * o.n},
-        {boxes, c->boxes, f4 * 2 * o.n_boxes},
-        {ctop, c->ctop, sizeof(uint32_t) * (o.grid_level > 0 ? o.ctop_len : 0)},
-        {cells, c->cells, sizeof(uint2) * 512 * (size_t)(o.grid_level > 0 ? o.n_blocks : 0)},
-        {onodes, c->onodes, f4 * 2 * o.n_onodes},
+        {tq, c->ix.tq, f4 * o.n},
+        {tn, c->ix.tn, f4 * 2 * o.n},
+        {boxes, c->ix.boxes, f4 * 2 * o.n_boxes},
+        {ctop, c->ix.ctop, sizeof(uint32_t) * (o.grid_level > 0 ? o.ctop_len : 0)},
+        {cells, c->ix.cells, sizeof(uint2) * 512 * (size_t)(o.grid_level > 0 ? o.n_blocks : 0)},
+        {onodes, c->ix.onodes, f4 * 2 * o.n_onodes},
     };
     for (const auto &p : parts) {
         const int st = copy_back(c, p.dst, p.src, p.bytes);
         if (st != SYMMICP_OK) { (void)hipStreamSynchronize(c->stream); return st; }
     }
     HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return SYMMICP_OK;
+}
+
+// diagnostic: the pair certificates as they stand, in the share's sorted order: (ref.xyz, L), the neighbourhood's 8 members and radius, the
+// current winner, target points named by their ROW in the caller's target cloud (the device holds sorted positions)
+int symmicp_get_certificates(symmicp_ctx *c, float *cert4, uint32_t *hood8, float *hood_radius, int32_t *winner_row, size_t cap)
+{
+    if (!c || !cert4) return SYMMICP_ERR_ARG;
+    if (!c->begun || !c->cert) return fail(c, SYMMICP_ERR_STATE, "no tree pass has run yet");
+    if (cap < c->n_loc) return fail(c, SYMMICP_ERR_SIZE, "output too small");
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, hipMemcpyAsync(cert4, c->cert, sizeof(float) * 4 * c->n_loc, hipMemcpyDeviceToHost, c->stream));
+    std::vector<int32_t> pos(winner_row ? c->n_loc : 0);
+    std::vector<float> tq((hood8 || winner_row) ? (size_t)c->n_t * 4 : 0);
+    if (hood8) HIP_TRY(c, hipMemcpyAsync(hood8, c->certk, sizeof(uint32_t) * 8 * c->n_loc, hipMemcpyDeviceToHost, c->stream));
+    std::vector<float> tr(hood_radius ? (size_t)c->n_loc * 2 : 0);
+    if (hood_radius) HIP_TRY(c, hipMemcpyAsync(tr.data(), c->hoodr, sizeof(float) * 2 * c->n_loc, hipMemcpyDeviceToHost, c->stream));
+    if (winner_row) HIP_TRY(c, hipMemcpyAsync(pos.data(), c->pos, sizeof(int32_t) * c->n_loc, hipMemcpyDeviceToHost, c->stream));
+    if (!tq.empty()) HIP_TRY(c, hipMemcpyAsync(tq.data(), c->ix.tq, sizeof(float) * 4 * c->n_t, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    auto row_of = [&](uint32_t p) -> uint32_t {
+        if (p >= c->n_t) return 0xFFFFFFFFu;
+        uint32_t r; std::memcpy(&r, &tq[(size_t)p * 4 + 3], 4); return r;      // the row rides in the w slot of the sorted point
+    };
+    for (size_t i = 0; i < c->n_loc; i++) {
+        if (hood8) for (int k = 0; k < 8; k++) hood8[i * 8 + k] = row_of(hood8[i * 8 + k]);
+        if (winner_row) winner_row[i] = pos[i] < 0 ? -1 : (int32_t)row_of((uint32_t)pos[i]);
+        if (hood_radius) hood_radius[i] = tr[i * 2];
+    }
     return SYMMICP_OK;
 }
 
@@ -190,38 +219,31 @@ int symmicp_ctx_reverse_nn_probe(symmicp_ctx *c, const float *db_xyz, const int3
     const size_t o_db = 0, o_lab = o_db + ((sizeof(float) * 3 * n_db + 255) & ~(size_t)255), o_raw = o_lab + ((sizeof(uint32_t) * n_db + 255) & ~(size_t)255),
                  raw_n = std::max(n_db, n_q), o_out = o_raw + ((sizeof(float) * 3 * raw_n + 255) & ~(size_t)255),
                  o_d2 = o_out + ((sizeof(int32_t) * n_q + 255) & ~(size_t)255), total = o_d2 + sizeof(float) * n_q;
-    char *d = nullptr;
-    HIP_TRY(c, hipMalloc((void **)&d, total));
-    ReverseIndex ri;       // (its own index: the context's source index stays as it was)
-    auto body = [&]() -> int {
-        float *raw = reinterpret_cast<float *>(d + o_raw), *col = reinterpret_cast<float *>(d + o_db);
-        HIP_TRY(c, hipMemcpyAsync(raw, db_xyz, sizeof(float) * 3 * n_db, hipMemcpyHostToDevice, c->stream));
-        if (labels) HIP_TRY(c, hipMemcpyAsync(d + o_lab, labels, sizeof(uint32_t) * n_db, hipMemcpyHostToDevice, c->stream));
-        launch_deinterleave3(raw, 3, 0, (uint32_t)n_db, col, col + n_db, col + 2 * n_db, c->stream);
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        CloudSoA cl{col, col + n_db, col + 2 * n_db, col, col + n_db, col + 2 * n_db};      // (no normals: the build reads the slots and nothing keeps them)
-        if (int st = build_reverse_index(c, cl, (uint32_t)n_db, labels ? reinterpret_cast<const uint32_t *>(d + o_lab) : nullptr, ri)) return st;
-        HIP_TRY(c, hipMemcpyAsync(raw, q_xyz, sizeof(float) * 3 * n_q, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        launch_reverse_nn_probe(ri.ix, inv, raw, (uint32_t)n_q, reinterpret_cast<int32_t *>(d + o_out), reinterpret_cast<float *>(d + o_d2), c->stream);
-        HIP_TRY(c, hipGetLastError());
-        HIP_TRY(c, hipMemcpyAsync(label_out, d + o_out, sizeof(int32_t) * n_q, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(c, hipMemcpyAsync(d2_out, d + o_d2, sizeof(float) * n_q, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        return SYMMICP_OK;
-    };
-    const int st = body();
-    (void)hipStreamSynchronize(c->stream);
-    drop_reverse_index(ri, true);
-    (void)hipFree(d);
-    return st;
+    OwnSearch own(c);      // (its own index: the context's source index stays as it was)
+    HIP_TRY(c, hipMalloc((void **)&own.d, total));
+    char *d = own.d;
+    float *raw = reinterpret_cast<float *>(d + o_raw), *col = reinterpret_cast<float *>(d + o_db);
+    HIP_TRY(c, hipMemcpyAsync(raw, db_xyz, sizeof(float) * 3 * n_db, hipMemcpyHostToDevice, c->stream));
+    if (labels) HIP_TRY(c, hipMemcpyAsync(d + o_lab, labels, sizeof(uint32_t) * n_db, hipMemcpyHostToDevice, c->stream));
+    launch_deinterleave3(raw, 3, 0, (uint32_t)n_db, col, col + n_db, col + 2 * n_db, c->stream);
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    CloudSoA cl{col, col + n_db, col + 2 * n_db, col, col + n_db, col + 2 * n_db};      // (no normals: the build reads the slots and nothing keeps them)
+    if (int st = build_reverse_index(c, cl, (uint32_t)n_db, labels ? reinterpret_cast<const uint32_t *>(d + o_lab) : nullptr, own.ri)) return st;
+    HIP_TRY(c, hipMemcpyAsync(raw, q_xyz, sizeof(float) * 3 * n_q, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    launch_reverse_nn_probe(own.ri.ix, inv, raw, (uint32_t)n_q, reinterpret_cast<int32_t *>(d + o_out), reinterpret_cast<float *>(d + o_d2), c->stream);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipMemcpyAsync(label_out, d + o_out, sizeof(int32_t) * n_q, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(d2_out, d + o_d2, sizeof(float) * n_q, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return SYMMICP_OK;
 }
 
 int symmicp_ctx_reciprocal_info(const symmicp_ctx *c, int32_t *index_valid, uint64_t *index_bytes, uint64_t *index_builds, uint64_t *table_words)
 {
     if (!c) return SYMMICP_ERR_ARG;
     if (index_valid) *index_valid = c->rej.src_ix.valid ? 1 : 0;
-    if (index_bytes) *index_bytes = c->rej.src_ix.keep.cap;
+    if (index_bytes) *index_bytes = c->rej.src_ix.store.cap();
     if (index_builds) *index_builds = c->rej.src_ix_builds;
     if (table_words) *table_words = c->rej.table_cap;
     return SYMMICP_OK;

@@ -1,4 +1,4 @@
-"""The search index restated in numpy (kernels_build.hip, build_index / build_octree in engine.cpp, the packet table of set_source).
+"""The search index restated in numpy (kernels_build.hip, build_index / build_octree in engine_index.cpp, the packet table of set_source).
 
 Plain numpy, fp32 where the device uses fp32 (the build is compiled with contraction off, so every float below is the device's
 bit for bit), integers everywhere else: nothing here has a tolerance.  `build_reference(xyz, nrm)` returns a dict with the keys of

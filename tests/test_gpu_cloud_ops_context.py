@@ -196,6 +196,90 @@ def test_keep_arena_is_still_the_targets(sym, cat, twin, bad):
         assert differing(snapshot(e), twin["s_swap"], HOOD) == []
 
 
+# ---- the reverse index beside the target's store ---------------------------------------------------------------------------------
+# symmicp_evaluate on a context without a tree index, the reverse probe and the reciprocal passes build an index with a store of its own
+# while the context holds a target in its store: the target's arrays, the scratch index of a cloud operation and that index must not meet.
+
+@pytest.mark.parametrize("corr", ["BRUTE", "IDENTITY"])
+def test_evaluate_on_a_context_without_a_tree_index(sym, cat, corr):
+    """BRUTE and IDENTITY contexts get a scratch reverse index over the target they hold: the alignment and the correspondences after it
+    are those of a context that never evaluated; after a cloud operation the swapped pair aligns as on a fresh context"""
+    kw = dict(mode=sym.MODE_PAPER, corr=getattr(sym, "CORR_" + corr), max_iters=20, apply=sym.APPLY_INCREMENTAL)
+
+    def state(e):
+        return [*e.correspondences(), *e.source(), e.pivot()]
+
+    with sym.Engine(**kw) as e, sym.Engine(**kw) as t, sym.Engine(**kw) as fresh:
+        load(e, cat)
+        load(t, cat)
+        assert same_result(e.align(), t.align())
+        X = e.transform()
+        ev = e.evaluate(X, R_RADIUS, want_pairs=True)
+        one_shot = sym.evaluate_registration(cat["src"], cat["tgt"], X, R_RADIUS, want_pairs=True)
+        assert ev["inliers"] == one_shot["inliers"] > 0 and differing([ev["nn"], ev["d2"]], [one_shot["nn"], one_shot["d2"]]) == []
+        assert differing(state(e), state(t)) == []
+        assert same_result(e.align(), t.align())
+        assert differing(state(e), state(t)) == []
+        rows, d2 = e.knn(cat["tgt"], 7)
+        assert rows.min() >= 0 and rows.max() < len(cat["tgt"]) and (np.diff(d2, axis=1) >= 0).all()
+        assert differing(state(e), state(t)) == []
+        load(e, cat, swap=True)
+        load(fresh, cat, swap=True)
+        assert same_result(e.align(), fresh.align())
+        assert differing(state(e), state(fresh)) == []
+        assert e.evaluate(None, R_RADIUS)["inliers"] == fresh.evaluate(None, R_RADIUS)["inliers"]
+
+
+def test_failure_inside_the_reverse_build(sym, cat, bad):
+    """the reverse probe over a database with one NaN coordinate is refused by the index build, in the probe's own store: the context's
+    target index, its source index and the last pass's states stay as they were, and the next pass is the twin's"""
+    kw = dict(mode=sym.MODE_PAPER, corr=sym.CORR_TREE, max_iters=6, fixed_iters=1)
+
+    def state(e):
+        info = e.reciprocal_info()
+        out = dict(zip(("corr", "corr_d2"), e.correspondences()))
+        out.update(("ix." + k, np.asarray(v)) for k, v in e.index_arrays().items())
+        return out, (e.rejection_state(), e.reciprocal_state(), info["index_valid"], info["index_builds"])
+
+    with sym.Engine(**kw) as e, sym.Engine(**kw) as t:
+        for x in (e, t):
+            load(x, cat)
+            x.set_reciprocal(True)
+        assert np.array_equal(e.begin()["sums"], t.begin()["sums"])
+        arrays, scalars = state(e)
+        assert scalars[2:] == (True, 1)
+        q = cat["tgt"][:70]
+        assert status_of(sym, lambda: e.reverse_nn_probe(bad, q)) == sym.ERR_ARG
+        arrays1, scalars1 = state(e)
+        assert differing(arrays1, arrays) == [] and scalars1 == scalars
+        assert np.array_equal(e.step()["sums"], t.step()["sums"]) and e.reciprocal_state() == t.reciprocal_state()
+        lab, d2 = e.reverse_nn_probe(cat["src"], q)
+        assert lab.min() >= 0 and lab.max() < len(cat["src"]) and np.isfinite(d2).all()
+        assert np.array_equal(e.step()["sums"], t.step()["sums"]) and e.reciprocal_info()["index_builds"] == 1
+
+
+def test_target_scratch_and_reverse_index_on_one_context(sym, cat):
+    """a reciprocal alignment (the source index in its own store), knn (a scratch index behind the target's arrays) and evaluate (the
+    target's own index): the next alignment and the snapshot are the twin's, and the source index was built once"""
+    e, t = engine(sym), engine(sym)
+    with e, t:
+        for x in (e, t):
+            load(x, cat)
+            x.set_reciprocal(True)
+        assert same_result(e.align(), t.align())
+        s = snapshot(e)
+        assert differing(s, snapshot(t), HOOD) == []
+        rows, _ = e.knn(cat["tgt"], 7)
+        assert rows.min() >= 0 and rows.max() < len(cat["tgt"])
+        ev = e.evaluate(None, R_RADIUS)
+        assert 0 < ev["inliers"] <= len(cat["src"])
+        assert differing(snapshot(e), s) == []
+        assert same_result(e.align(), t.align())
+        assert differing(snapshot(e), snapshot(t), HOOD) == []
+        assert e.reciprocal_state() == t.reciprocal_state()
+        assert e.reciprocal_info() == t.reciprocal_info() and e.reciprocal_info()["index_builds"] == 1
+
+
 def test_no_target_yet(sym, cat, twin):
     """on a context without a target the operation sizes the keep-arena itself; the target set afterwards reuses it"""
     src = cat["src"]

@@ -1032,7 +1032,7 @@ def test_forced_repair_path_in_a_subprocess(sym):
 @pytest.mark.parametrize("regime", ["packet", "packet:1", "packet:4", "walk"])
 def test_first_pass_regimes_forced_in_a_subprocess(sym, regime):
     """The first pass of an alignment runs as 64-query packets (kernels_packet.hip) on surface-like targets and as the
-    per-thread octree walk on volume-like ones (engine.cpp, build_index).  SYMMICP_FIRST_PASS forces one regime on every
+    per-thread octree walk on volume-like ones (engine_index.cpp, build_index).  SYMMICP_FIRST_PASS forces one regime on every
     target -- volume clouds, tiny and ragged sizes, duplicates and ties, far queries included: pairs and distances must
     stay bit-exact against the oracle either way."""
     import subprocess
