@@ -1,5 +1,5 @@
 // cluster_core.h -- the concurrent union-find of symmicp_ctx_cluster (include/symmicp.h, "DBSCAN"), shared by the kernels
-// (kernels_cluster.hip: agent-scope atomics) and a host program (tests/cpp/cluster_core.cpp: plain loads and stores).
+// (kernels_cluster.hip, kernels_region.hip: agent-scope atomics) and a host program (tests/cpp/cluster_core.cpp: plain loads and stores).
 //
 // parent[] is indexed by CALLER ROW and starts as parent[x] == x.  One invariant carries everything:
 //
@@ -41,6 +41,18 @@ struct SerialOps {
         return old;
     }
 };
+
+#if defined(__HIPCC__)
+// relaxed agent-scope atomics: parent[] words are read and swapped by lanes of every XCD within one launch
+struct AgentOps {
+    __device__ static __forceinline__ uint32_t load(const uint32_t *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+    __device__ static __forceinline__ uint32_t cas(uint32_t *p, uint32_t expected, uint32_t desired)
+    {
+        (void)__hip_atomic_compare_exchange_strong(p, &expected, desired, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        return expected;      // the value found (unchanged when the swap happened)
+    }
+};
+#endif
 
 // the root of x, halving the path on the way (every second link is cut to the grandparent; a lost swap only means somebody else
 // cut it first)

@@ -1,4 +1,4 @@
-// engine_cloud_ops.cpp -- the stand-alone cloud operations of libsymmicp: normals and k-NN, radius search, FPFH, ISS keypoints, outlier removal, clustering, the
+// engine_cloud_ops.cpp -- the stand-alone cloud operations of libsymmicp: normals and k-NN, radius search, FPFH, ISS keypoints, outlier removal, clustering, region growing, the
 // intensity gradient of colored ICP, voxel-grid downsampling.  Each runs on a context the caller owns (symmicp_ctx_*), whose target,
 // source, index and certificates stay as they are, or as a one-shot on a context of its own (with_own_context).
 #include "engine_internal.h"
@@ -33,6 +33,32 @@ int outlier_compact(symmicp_ctx *c, const char *who, size_t n, Keep &&keep, int3
     if (count > cap) return fail(c, SYMMICP_ERR_SIZE, std::string(who) + ": " + std::to_string(count) + " kept rows do not fit cap " + std::to_string(cap));
     size_t at = 0;
     for (size_t i = 0; i < n; i++) if (keep(i)) rows_out[at++] = (int32_t)i;
+    return SYMMICP_OK;
+}
+// the host tail of the clustering and of the region growing, O(n) and sequential by definition.  root [n]: every row's representative, or
+// kClusterNoise; a part's representative is a row that is its own root and can_lead (a core row, a seed row).  Parts numbered in ascending
+// order of their representative, size = all their rows; then the size filter: the parts that stay, renumbered in the same order; then the cap
+// protocol: labels and the count always, the sizes when they fit.
+template <class CanLead>
+int number_parts(symmicp_ctx *c, const char *who, const char *parts, const char *bad_root, size_t n, const std::vector<uint32_t> &root,
+                 CanLead &&can_lead, int32_t lo, int32_t hi, int32_t *labels_out, size_t *count_out, int32_t *sizes_out, size_t cap)
+{
+    std::vector<int32_t> label(n, -1), size;
+    for (size_t i = 0; i < n; i++)
+        if (root[i] == (uint32_t)i && can_lead(i)) { label[i] = (int32_t)size.size(); size.push_back(0); }
+    for (size_t i = 0; i < n; i++) {
+        if (root[i] == kClusterNoise) continue;
+        if (root[i] >= n || label[root[i]] < 0) return fail(c, SYMMICP_ERR_HIP, std::string(who) + ": " + bad_root);
+        size[(size_t)label[root[i]]]++;
+    }
+    std::vector<int32_t> renum(size.size(), -1), kept;
+    for (size_t k = 0; k < size.size(); k++)
+        if ((lo == 0 || size[k] >= lo) && (hi == 0 || size[k] <= hi)) { renum[k] = (int32_t)kept.size(); kept.push_back(size[k]); }
+    for (size_t i = 0; i < n; i++) labels_out[i] = root[i] == kClusterNoise ? -1 : renum[(size_t)label[root[i]]];
+    *count_out = kept.size();
+    if (kept.size() > cap)
+        return fail(c, SYMMICP_ERR_SIZE, std::string(who) + ": " + std::to_string(kept.size()) + " " + parts + " do not fit cap " + std::to_string(cap));
+    for (size_t k = 0; k < kept.size(); k++) sizes_out[k] = kept[k];
     return SYMMICP_OK;
 }
 }  // namespace
@@ -386,7 +412,7 @@ int symmicp_radius_outlier_removal(int device, const float *xyz, size_t row_stri
 // ---- DBSCAN / Euclidean cluster extraction (kernels_cluster.hip, kernels_fpfh.hip; DESIGN.md 4, "Clustering") -------------------------
 // Like the radius filter above: the cloud's own scratch index, the count pass of the radius search (the core test), then the union-find
 // over the implicit radius graph and the border pass.  The per-row representative is read back; the dense numbering, the sizes and the
-// size filter are O(n), sequential by definition, and run on the host.
+// size filter are O(n), sequential by definition, and run on the host (number_parts).
 static const char *cluster_args_error(const float *xyz, size_t xr, size_t xc, size_t n, const symmicp_cluster_config *cfg, const int32_t *labels_out,
                                       const size_t *clusters_out, const int32_t *sizes_out, size_t cap)
 {
@@ -445,25 +471,8 @@ int symmicp_ctx_cluster(symmicp_ctx *c, const float *xyz, size_t row_stride, siz
         if (d_stats.p) std::fprintf(stderr, "symmicp cluster: n %zu, %llu unions, %llu lost compare-and-swaps\n", n, stats[0], stats[1]);
     }
     if (core_out) for (size_t i = 0; i < n; i++) core_out[i] = nb[i] >= need ? 1 : 0;
-    // clusters numbered in ascending order of their representative (its lowest core row), sizes = core + border rows
-    std::vector<int32_t> label(n, -1), size;
-    for (size_t i = 0; i < n; i++)
-        if (root[i] == (uint32_t)i && nb[i] >= need) { label[i] = (int32_t)size.size(); size.push_back(0); }
-    for (size_t i = 0; i < n; i++) {
-        if (root[i] == kClusterNoise) continue;
-        if (root[i] >= n || label[root[i]] < 0) return fail(c, SYMMICP_ERR_HIP, "cluster: a row's representative is not a cluster's lowest core row");
-        size[(size_t)label[root[i]]]++;
-    }
-    // the size filter: the clusters that stay, renumbered in the same order
-    const int32_t lo = cfg->min_cluster_size, hi = cfg->max_cluster_size;
-    std::vector<int32_t> renum(size.size(), -1), kept;
-    for (size_t k = 0; k < size.size(); k++)
-        if ((lo == 0 || size[k] >= lo) && (hi == 0 || size[k] <= hi)) { renum[k] = (int32_t)kept.size(); kept.push_back(size[k]); }
-    for (size_t i = 0; i < n; i++) labels_out[i] = root[i] == kClusterNoise ? -1 : renum[(size_t)label[root[i]]];
-    *clusters_out = kept.size();
-    if (kept.size() > cap) return fail(c, SYMMICP_ERR_SIZE, "cluster: " + std::to_string(kept.size()) + " clusters do not fit cap " + std::to_string(cap));
-    for (size_t k = 0; k < kept.size(); k++) sizes_out[k] = kept[k];
-    return SYMMICP_OK;
+    return number_parts(c, "cluster", "clusters", "a row's representative is not a cluster's lowest core row", n, root,
+                        [&](size_t i) { return nb[i] >= need; }, cfg->min_cluster_size, cfg->max_cluster_size, labels_out, clusters_out, sizes_out, cap);
 }
 
 int symmicp_cluster(int device, const float *xyz, size_t row_stride, size_t col_stride, size_t n, const symmicp_cluster_config *cfg,
@@ -472,6 +481,108 @@ int symmicp_cluster(int device, const float *xyz, size_t row_stride, size_t col_
     if (cluster_args_error(xyz, row_stride, col_stride, n, cfg, labels_out, clusters_out, sizes_out, cap)) return SYMMICP_ERR_ARG;
     return with_own_context(device, [&](symmicp_ctx *c) {
         return symmicp_ctx_cluster(c, xyz, row_stride, col_stride, n, cfg, labels_out, clusters_out, sizes_out, cap, core_out, neighbors_out);
+    });
+}
+
+// ---- region-growing segmentation (kernels_region.hip; DESIGN.md 4, "Region growing") ---------------------------------------------------
+// Like the clustering above with the normals sorted next to the points (ScratchIndex::begin takes them): seed flags from the curvature, the
+// union-find over the implicit smooth graph on the seeds, the border pass over the rest, and the clustering's host tail.  The count of
+// smooth neighbours is one more walk, launched only when smooth_out is given.
+static const char *region_args_error(const float *xyz, size_t xr, size_t xc, const float *nrm, size_t nr, size_t nc, const float *curv, size_t cs,
+                                     size_t n, const symmicp_region_config *cfg, const int32_t *labels_out, const size_t *regions_out,
+                                     const int32_t *sizes_out, size_t cap)
+{
+    if (!xyz || !nrm || !cfg || !labels_out || !regions_out) return "region_growing: xyz, nrm, cfg, labels_out and regions_out are required";
+    if (!sizes_out && cap > 0) return "region_growing: sizes_out is required when cap > 0";
+    if (n == 0 || n > 0x7fffffffull) return "region_growing: n must be in 1 .. 2^31 - 1";
+    if (cfg->struct_size != sizeof(symmicp_region_config)) return "region_growing: cfg->struct_size is not sizeof(symmicp_region_config)";
+    if (!std::isfinite(cfg->eps) || !(cfg->eps > 0.f)) return "region_growing: eps must be finite and > 0";
+    if (!std::isfinite(cfg->smoothness_cos) || !(cfg->smoothness_cos >= 0.f) || !(cfg->smoothness_cos <= 1.f))
+        return "region_growing: smoothness_cos must be in [0, 1]";
+    if (std::isnan(cfg->curvature_threshold)) return "region_growing: curvature_threshold is NaN";
+    if (cfg->min_region_size < 0 || cfg->max_region_size < 0) return "region_growing: min_region_size and max_region_size must be >= 0";
+    if (cfg->min_region_size > 0 && cfg->max_region_size > 0 && cfg->max_region_size < cfg->min_region_size)
+        return "region_growing: max_region_size is below min_region_size";
+    if (!coords_finite(xyz, xr, xc, n)) return "region_growing: a coordinate is not finite";
+    if (!coords_finite(nrm, nr, nc, n)) return "region_growing: a normal is not finite";
+    if (curv)
+        for (size_t i = 0; i < n; i++)
+            if (std::isnan(curv[i * cs])) return "region_growing: a curvature is NaN";
+    return nullptr;
+}
+
+void symmicp_region_config_default(symmicp_region_config *cfg)
+{
+    if (!cfg) return;
+    std::memset(cfg, 0, sizeof(*cfg));
+    cfg->struct_size = (uint32_t)sizeof(*cfg);
+    cfg->smoothness_cos = 0.8660254f;
+    cfg->curvature_threshold = 0.05f;
+}
+
+int symmicp_ctx_region_growing(symmicp_ctx *c, const float *xyz, size_t xyz_row_stride, size_t xyz_col_stride, const float *nrm, size_t nrm_row_stride,
+                               size_t nrm_col_stride, const float *curv, size_t curv_stride, size_t n, const symmicp_region_config *cfg,
+                               int32_t *labels_out, size_t *regions_out, int32_t *sizes_out, size_t cap, uint8_t *seed_out, int32_t *smooth_out)
+{
+    if (!c) return SYMMICP_ERR_ARG;
+    if (const char *msg = region_args_error(xyz, xyz_row_stride, xyz_col_stride, nrm, nrm_row_stride, nrm_col_stride, curv, curv_stride, n, cfg,
+                                            labels_out, regions_out, sizes_out, cap))
+        return fail(c, SYMMICP_ERR_ARG, msg);
+    std::vector<uint32_t> root(n);
+    std::vector<int32_t> seed(n);
+    std::vector<float> curv_rows;
+    if (curv) {
+        curv_rows.resize(n);
+        for (size_t i = 0; i < n; i++) curv_rows[i] = curv[i * curv_stride];
+    }
+    {
+        ScratchIndex si;
+        if (int st = si.begin(c, xyz, xyz_row_stride, xyz_col_stride, nrm, nrm_row_stride, nrm_col_stride, n, n * 16 + 8192)) return st;
+        DevBuf<int32_t> d_seed, d_smooth;
+        DevBuf<uint32_t> d_parent;
+        DevBuf<float> d_curv;
+        DevBuf<unsigned long long> d_stats;
+        HIP_TRY(c, d_seed.alloc_temp(c->arena, n));
+        HIP_TRY(c, d_parent.alloc_temp(c->arena, n));
+        if (curv) {
+            HIP_TRY(c, d_curv.alloc_temp(c->arena, n));
+            HIP_TRY(c, hipMemcpyAsync(d_curv.p, curv_rows.data(), sizeof(float) * n, hipMemcpyHostToDevice, c->stream));
+        }
+        if (smooth_out) HIP_TRY(c, d_smooth.alloc_temp(c->arena, n));
+        if (c->sw.debug_counters) {
+            HIP_TRY(c, d_stats.alloc_temp(c->arena, 4));
+            HIP_TRY(c, hipMemsetAsync(d_stats.p, 0, 4 * sizeof(unsigned long long), c->stream));
+        }
+        const float r2 = cfg->eps * cfg->eps;
+        launch_region_seeds(d_curv.p, cfg->curvature_threshold, (uint32_t)n, d_seed.p, c->stream);
+        launch_region_roots(si.ix, r2, cfg->smoothness_cos, d_seed.p, curv != nullptr, d_parent.p, d_stats.p, c->stream);
+        if (smooth_out) launch_region_smooth_count(si.ix, r2, cfg->smoothness_cos, d_smooth.p, c->stream);
+        HIP_TRY(c, hipGetLastError());
+        unsigned long long stats[4] = {0, 0, 0, 0};
+        HIP_TRY(c, hipMemcpyAsync(seed.data(), d_seed.p, sizeof(int32_t) * n, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(root.data(), d_parent.p, sizeof(uint32_t) * n, hipMemcpyDeviceToHost, c->stream));
+        if (smooth_out) HIP_TRY(c, hipMemcpyAsync(smooth_out, d_smooth.p, sizeof(int32_t) * n, hipMemcpyDeviceToHost, c->stream));
+        if (d_stats.p) HIP_TRY(c, hipMemcpyAsync(stats, d_stats.p, sizeof(stats), hipMemcpyDeviceToHost, c->stream));
+        if (int st = stream_done(c)) return st;
+        if (d_stats.p)
+            std::fprintf(stderr, "symmicp region_growing: n %zu, %llu unions, %llu lost compare-and-swaps, %llu edges examined, %llu normal loads\n", n,
+                         stats[0], stats[1], stats[2], stats[3]);
+    }
+    if (seed_out) for (size_t i = 0; i < n; i++) seed_out[i] = seed[i] ? 1 : 0;
+    return number_parts(c, "region_growing", "regions", "a row's representative is not a region's lowest seed row", n, root,
+                        [&](size_t i) { return seed[i] != 0; }, cfg->min_region_size, cfg->max_region_size, labels_out, regions_out, sizes_out, cap);
+}
+
+int symmicp_region_growing(int device, const float *xyz, size_t xyz_row_stride, size_t xyz_col_stride, const float *nrm, size_t nrm_row_stride,
+                           size_t nrm_col_stride, const float *curv, size_t curv_stride, size_t n, const symmicp_region_config *cfg,
+                           int32_t *labels_out, size_t *regions_out, int32_t *sizes_out, size_t cap, uint8_t *seed_out, int32_t *smooth_out)
+{
+    if (region_args_error(xyz, xyz_row_stride, xyz_col_stride, nrm, nrm_row_stride, nrm_col_stride, curv, curv_stride, n, cfg, labels_out, regions_out,
+                          sizes_out, cap))
+        return SYMMICP_ERR_ARG;
+    return with_own_context(device, [&](symmicp_ctx *c) {
+        return symmicp_ctx_region_growing(c, xyz, xyz_row_stride, xyz_col_stride, nrm, nrm_row_stride, nrm_col_stride, curv, curv_stride, n, cfg,
+                                          labels_out, regions_out, sizes_out, cap, seed_out, smooth_out);
     });
 }
 

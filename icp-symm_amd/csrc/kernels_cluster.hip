@@ -24,15 +24,7 @@ namespace symmicp {
 
 constexpr int kClusterThreads = 256;
 
-// relaxed agent-scope atomics: parent[] words are read and swapped by lanes of every XCD within one launch
-struct AgentOps {
-    __device__ static __forceinline__ uint32_t load(const uint32_t *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-    __device__ static __forceinline__ uint32_t cas(uint32_t *p, uint32_t expected, uint32_t desired)
-    {
-        (void)__hip_atomic_compare_exchange_strong(p, &expected, desired, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        return expected;      // the value found (unchanged when the swap happened)
-    }
-};
+using cluster::AgentOps;      // relaxed agent-scope atomics (cluster_core.h)
 
 __global__ __launch_bounds__(kClusterThreads) void k_cluster_init(uint32_t *parent, uint32_t n)
 {
@@ -104,13 +96,23 @@ __global__ __launch_bounds__(kClusterThreads) void k_cluster_border(TargetIndex 
 
 static dim3 cluster_grid(uint32_t n) { return dim3((n + kClusterThreads - 1) / kClusterThreads); }
 
+void launch_cluster_init(uint32_t *parent_rows, uint32_t n, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_cluster_init, cluster_grid(n), dim3(kClusterThreads), 0, s, parent_rows, n);
+}
+
+void launch_cluster_flatten(const int32_t *count_rows, int32_t need, uint32_t *parent_rows, uint32_t n, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_cluster_flatten, cluster_grid(n), dim3(kClusterThreads), 0, s, count_rows, need, parent_rows, n);
+}
+
 void launch_cluster_roots(const TargetIndex &ix, float r2, const int32_t *count_rows, int32_t min_points, uint32_t *parent_rows,
                           unsigned long long *stats, hipStream_t s)
 {
     const int32_t need = min_points - 1;
-    hipLaunchKernelGGL(k_cluster_init, cluster_grid(ix.n), dim3(kClusterThreads), 0, s, parent_rows, ix.n);
+    launch_cluster_init(parent_rows, ix.n, s);
     hipLaunchKernelGGL(k_cluster_union, cluster_grid(ix.n), dim3(kClusterThreads), 0, s, ix, r2, count_rows, need, parent_rows, stats);
-    hipLaunchKernelGGL(k_cluster_flatten, cluster_grid(ix.n), dim3(kClusterThreads), 0, s, count_rows, need, parent_rows, ix.n);
+    launch_cluster_flatten(count_rows, need, parent_rows, ix.n, s);
     if (need > 0) hipLaunchKernelGGL(k_cluster_border, cluster_grid(ix.n), dim3(kClusterThreads), 0, s, ix, r2, count_rows, need, parent_rows);
 }
 

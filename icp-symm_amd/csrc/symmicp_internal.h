@@ -442,6 +442,21 @@ void launch_knn_mean_dist(const TargetIndex &ix, int k, double *mean_rows, hipSt
 constexpr uint32_t kClusterNoise = 0xffffffffu;
 void launch_cluster_roots(const TargetIndex &ix, float r2, const int32_t *count_rows, int32_t min_points, uint32_t *parent_rows,
                           unsigned long long *stats, hipStream_t s);
+// its first and third step on their own (the region growing runs them around its own union): parent_rows[row] = row; then, once every
+// union is done, parent_rows[row] = the root of row for the rows with count_rows[row] >= need
+void launch_cluster_init(uint32_t *parent_rows, uint32_t n, hipStream_t s);
+void launch_cluster_flatten(const int32_t *count_rows, int32_t need, uint32_t *parent_rows, uint32_t n, hipStream_t s);
+
+// region growing (kernels_region.hip; symmicp_ctx_region_growing).  ix carries the normals (ix.tn).  seed_rows [n] int32 0 / 1 and
+// parent_rows [n] by ORIGINAL row; curv_rows [n] by ORIGINAL row or null (every row a seed).  launch_region_roots leaves in parent_rows
+// the representative (lowest seed row) of the row's region, or kClusterNoise.  stats (may be null): four zeroed words, += unite calls,
+// lost compare-and-swaps, edges examined by the union kernel (in range, at a higher sorted position) and normal loads among them.
+void launch_region_seeds(const float *curv_rows, float threshold, uint32_t n, int32_t *seed_rows, hipStream_t s);
+// border: run the pass over the non-seed rows (false when every row is a seed)
+void launch_region_roots(const TargetIndex &ix, float r2, float smoothness_cos, const int32_t *seed_rows, bool border, uint32_t *parent_rows,
+                         unsigned long long *stats, hipStream_t s);
+// smooth_rows [n] by ORIGINAL row = |{ j : smooth(row, j) }|
+void launch_region_smooth_count(const TargetIndex &ix, float r2, float smoothness_cos, int32_t *smooth_rows, hipStream_t s);
 
 // normal orientation (kernels_orient.hip; symmicp_ctx_orient_normals; the state words, keys and the hook rule are orient_core.h's).
 // Everything is indexed by ORIGINAL row; xyz3 / nrm3 / nrm_out are packed [n][3].

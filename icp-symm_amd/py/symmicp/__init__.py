@@ -115,6 +115,12 @@ class ClusterConfig(C.Structure):
                 ("max_cluster_size", C.c_int32), ("reserved", C.c_int32)]
 
 
+class RegionConfig(C.Structure):
+    """symmicp_region_config"""
+    _fields_ = [("struct_size", C.c_uint32), ("eps", C.c_float), ("smoothness_cos", C.c_float), ("curvature_threshold", C.c_float),
+                ("min_region_size", C.c_int32), ("max_region_size", C.c_int32)]
+
+
 class OrientConfig(C.Structure):
     """symmicp_orient_config"""
     _fields_ = [("struct_size", C.c_uint32), ("k", C.c_int32), ("seed_rule", C.c_int32), ("ref", C.c_float * 3)]
@@ -243,6 +249,7 @@ EXPORTS = [
     "symmicp_statistical_outlier_removal", "symmicp_ctx_statistical_outlier_removal",
     "symmicp_radius_outlier_removal", "symmicp_ctx_radius_outlier_removal",
     "symmicp_cluster_config_default", "symmicp_cluster", "symmicp_ctx_cluster",
+    "symmicp_region_config_default", "symmicp_region_growing", "symmicp_ctx_region_growing",
     "symmicp_orient_config_default", "symmicp_orient_normals", "symmicp_ctx_orient_normals",
     "symmicp_plane_config_default", "symmicp_segment_plane", "symmicp_ctx_segment_plane", "symmicp_ctx_plane_hypotheses",
     "symmicp_ndt_config_default", "symmicp_set_ndt", "symmicp_get_ndt", "symmicp_ndt_gauss", "symmicp_ndt_weight", "symmicp_get_ndt_state",
@@ -416,6 +423,12 @@ def lib():
     L.symmicp_cluster_config_default.restype = None
     L.symmicp_cluster.argtypes = [C.c_int] + clu
     L.symmicp_ctx_cluster.argtypes = [vp] + clu
+    reg = [fp, C.c_size_t, C.c_size_t, fp, C.c_size_t, C.c_size_t, fp, C.c_size_t, C.c_size_t, C.POINTER(RegionConfig), i32p, szp, i32p,
+           C.c_size_t, u8p, i32p]
+    L.symmicp_region_config_default.argtypes = [C.POINTER(RegionConfig)]
+    L.symmicp_region_config_default.restype = None
+    L.symmicp_region_growing.argtypes = [C.c_int] + reg
+    L.symmicp_ctx_region_growing.argtypes = [vp] + reg
     ori = [fp, C.c_size_t, C.c_size_t, fp, C.c_size_t, C.c_size_t, C.c_size_t, C.POINTER(OrientConfig), fp, u8p, i32p, i32p, szp,
            C.POINTER(OrientResult)]
     L.symmicp_orient_config_default.argtypes = [C.POINTER(OrientConfig)]
@@ -978,6 +991,73 @@ def euclidean_clusters(xyz, tolerance, min_size=1, max_size=0, device=-1):
     """PCL's EuclideanClusterExtraction on the GPU (symmicp_cluster with min_points = 1): the connected parts of the cloud under
     'closer than tolerance', those of min_size .. max_size points (0 = no bound) -> a list of ascending row arrays, largest first."""
     return clusters_from_labels(cluster_dbscan(xyz, tolerance, 1, min_size, max_size, device=device))
+
+
+def region_cos(deg):
+    """the smoothness bound of an angle in degrees: THE conversion (the reference of the tests uses it too)"""
+    return np.float32(np.cos(np.deg2rad(np.float64(deg))))
+
+
+def region_config(eps, smoothness_deg=30.0, curvature_threshold=0.05, min_region_size=0, max_region_size=0, smoothness_cos=None):
+    """symmicp_region_config; smoothness_cos, when given, is taken as it is instead of region_cos(smoothness_deg)"""
+    cfg = RegionConfig()
+    lib().symmicp_region_config_default(C.byref(cfg))
+    cfg.eps, cfg.curvature_threshold = float(eps), float(curvature_threshold)
+    cfg.smoothness_cos = float(region_cos(smoothness_deg) if smoothness_cos is None else smoothness_cos)
+    cfg.min_region_size, cfg.max_region_size = int(min_region_size), int(max_region_size)
+    return cfg
+
+
+def _region_call(fn, head, xyz, nrm, curv, cfg, cap=None, strides=None, want=True):
+    """fn(*head, <the C arguments>) -> (status, labels [n] int32, regions, sizes [cap] int32 or None, seed [n] uint8 or None,
+    smooth [n] int32 or None).  cap None: sizes_out == NULL, cap 0.  strides = (n, xyz row, xyz col, nrm row, nrm col, curv stride)
+    reads all three as flat f32 buffers.  curv None: every row a seed."""
+    if strides is None:
+        xyz, nrm = _cloud(xyz), _cloud(nrm)
+        n, xr, xc, nr, nc, cs = xyz.shape[0], 3, 1, 3, 1, 1
+        if len(nrm) != n:
+            raise ValueError("a normal per point")
+        if curv is not None:
+            curv = _scalar(curv, n)
+    else:
+        n, xr, xc, nr, nc, cs = strides
+        xyz, nrm = np.ascontiguousarray(xyz, np.float32), np.ascontiguousarray(nrm, np.float32)
+        curv = None if curv is None else np.ascontiguousarray(curv, np.float32)
+    labels = np.full(max(n, 1), -2, np.int32)
+    sizes = None if cap is None else np.full(max(cap, 1), -1, np.int32)
+    seed = np.zeros(max(n, 1), np.uint8) if want else None
+    smooth = np.zeros(max(n, 1), np.int32) if want else None
+    regions = C.c_size_t(0)
+    st = fn(*head, _fptr(xyz), xr, xc, _fptr(nrm), nr, nc, None if curv is None else _fptr(curv), cs, n, C.byref(cfg), _i32ptr(labels),
+            C.byref(regions), None if sizes is None else _i32ptr(sizes), 0 if cap is None else cap,
+            None if seed is None else seed.ctypes.data_as(C.POINTER(C.c_uint8)), None if smooth is None else _i32ptr(smooth))
+    return st, labels[:n], int(regions.value), sizes, None if seed is None else seed[:n], None if smooth is None else smooth[:n]
+
+
+def _region_growing(fn, head, xyz, nrm, curv, cfg, return_info):
+    """one call with cap = n, which always suffices -> (status, labels or dict(labels=, regions=, sizes=, seed=, smooth=))"""
+    st, labels, regions, sizes, seed, smooth = _region_call(fn, head, xyz, nrm, curv, cfg, cap=len(xyz), want=return_info)
+    if st != OK:
+        return st, None
+    if not return_info:
+        return st, labels
+    return st, dict(labels=labels, regions=regions, sizes=sizes[:regions].copy(), seed=seed.astype(bool), smooth=smooth)
+
+
+def region_growing(xyz, nrm, eps, smoothness_deg=30.0, curvature=None, curvature_threshold=0.05, min_region_size=0, max_region_size=0,
+                   return_info=False, device=-1):
+    """region-growing segmentation on the GPU (symmicp_region_growing; include/symmicp.h defines the result) -> labels [N] int32: the
+    smooth surface part of every row, numbered in ascending order of the regions' lowest seed rows, -1 for unlabelled.  Two rows within
+    eps are joined when their normals (of any sign) are within smoothness_deg of each other; regions are the connected parts of that graph
+    on the SEED rows (curvature <= curvature_threshold; every row when curvature is None, e.g. estimate_normals' second result), and a
+    non-seed row joins the region of its nearest smooth seed neighbour.  Regions whose size lies outside [min_region_size,
+    max_region_size] (0 = no bound) become -1.  With return_info dict(labels=, regions=, sizes= [regions] int32, seed= [N] bool,
+    smooth= [N] int32: smooth neighbours per row)."""
+    cfg = region_config(eps, smoothness_deg, curvature_threshold, min_region_size, max_region_size)
+    st, r = _region_growing(lib().symmicp_region_growing, (int(device),), xyz, nrm, curvature, cfg, return_info)
+    if st != OK:
+        raise SymmIcpError(st, "region_growing")
+    return r
 
 
 def orient_config(k=16, viewpoint=None, direction=None):
@@ -2028,6 +2108,19 @@ class Engine:
         """one call of symmicp_ctx_cluster with a caller-chosen cap (None: sizes_out == NULL) -> (status, labels, clusters, sizes, core,
         neighbors)"""
         return _cluster_call(self._L.symmicp_ctx_cluster, (self._h,), xyz, cfg, cap, strides)
+
+    def region_growing(self, xyz, nrm, eps, smoothness_deg=30.0, curvature=None, curvature_threshold=0.05, min_region_size=0, max_region_size=0,
+                       return_info=False):
+        """region_growing on this context (symmicp_ctx_region_growing, one call with cap = n); its clouds and index stay as they are"""
+        cfg = region_config(eps, smoothness_deg, curvature_threshold, min_region_size, max_region_size)
+        st, r = _region_growing(self._L.symmicp_ctx_region_growing, (self._h,), xyz, nrm, curvature, cfg, return_info)
+        self._chk(st)
+        return r
+
+    def region_growing_raw(self, xyz, nrm, curv, cfg, cap=None, strides=None, want=True):
+        """one call of symmicp_ctx_region_growing with a caller-chosen cap (None: sizes_out == NULL) -> (status, labels, regions, sizes,
+        seed, smooth); want=False passes NULL for seed_out and smooth_out"""
+        return _region_call(self._L.symmicp_ctx_region_growing, (self._h,), xyz, nrm, curv, cfg, cap, strides, want)
 
     def segment_plane(self, xyz, max_dist, hypotheses=1000, seed=0, refits=1, min_inliers=3, axis=None, max_angle_deg=0.0, return_info=False,
                       check=True):

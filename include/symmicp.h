@@ -733,6 +733,62 @@ int symmicp_cluster(int device, const float *xyz, size_t row_stride, size_t col_
                     const symmicp_cluster_config *cfg, int32_t *labels_out, size_t *clusters_out, int32_t *sizes_out,
                     size_t cap, uint8_t *core_out, int32_t *neighbors_out);
 
+/* ---- region-growing segmentation (Rabbani et al. 2006; PCL's RegionGrowing; DESIGN.md 4, "Region growing") -------------------
+ * Splits a cloud where its surface BENDS, not where it has a gap: a box on a table, or the three faces at a box corner, are one
+ * Euclidean cluster and several regions.  The labels go where the clustering's go (symmicp_batch_align pair by pair, for example
+ * the faces of an object).  Defined by its arithmetic; the result is a function of the inputs alone, bit for bit (it does not
+ * depend on the order in which the device meets the edges, nor on the row order beyond the numbering).
+ * Inputs: xyz [n]; nrm [n], required, of any sign, used as given (no normalisation: smoothness_cos is a bound on the dot product
+ *   itself); curv [n] or NULL, element i at curv[i * curv_stride] (symmicp_ctx_estimate_normals' curv_out with stride 1).
+ * Neighbourhoods.  N(i) is exactly the neighbourhood of symmicp_ctx_radius_search at radius eps: r2 = eps * eps in fp32, d2 the
+ *   fp32 (dx*dx + dy*dy) + dz*dz, unfused, members d2 <= r2; row i itself is left out by ROW (a duplicate of it is a member).
+ * Smooth edges.  smooth(i, j) iff j in N(i) and fabsf((nix*njx + niy*njy) + niz*njz) >= smoothness_cos, the dot product in fp32,
+ *   unfused, in that association (a NaN from an overflow compares false).  Both halves are symmetric bit for bit, so the graph is
+ *   undirected; inverting the sign of any normal changes nothing.  smooth_out[i] = |{ j : smooth(i, j) }|, over all rows.
+ * Seeds.  Row i is a SEED iff curv == NULL or curv[i] <= curvature_threshold, compared in fp32 (seed_out[i] = 1).
+ * Regions.  A region is a connected component of the smooth graph restricted to the seed rows; its REPRESENTATIVE is its lowest
+ *   seed row.  A seed without a smooth seed neighbour is a region of one.
+ * Border rows.  A non-seed row i joins ONE region: among the seed rows j with smooth(i, j) the one that minimises the 64-bit key
+ *   (d2 bits << 32) | representative(j) -- the clustering's border rule with the smoothness test added.
+ * Unlabelled rows.  Every other row: label -1.
+ * Labels.  The regions are numbered 0 .. R - 1 in ascending order of their representative row.
+ * Size filter, output, cap.  Exactly symmicp_ctx_cluster's: a region's size is its seed rows plus its border rows; a region whose
+ *   size lies outside [min_region_size, max_region_size] (0 = no bound on that side) becomes -1 and the rest are renumbered in the
+ *   same order.  labels_out [n] and *regions_out are required; sizes_out [cap]; SYMMICP_ERR_SIZE when R exceeds cap: the labels,
+ *   the count and the per-point arrays are written, the sizes are not (sizes_out may be NULL with cap == 0).  seed_out [n] and
+ *   smooth_out [n] may be NULL and describe the points BEFORE the size filter; smooth_out costs one more walk of the tree, which
+ *   runs only when it is given.
+ * Identity.  With smoothness_cos = 0 and curv == NULL the result is symmicp_ctx_cluster's at min_points = 1, label for label.
+ * Departures from PCL's RegionGrowing, all deliberate: PCL takes k-nearest neighbourhoods, which are not symmetric; it grows in
+ *   curvature order, so a point that two regions could claim goes to whichever reaches it first (a function of the scan order);
+ *   and it opens a region from any leftover point, so nothing stays unlabelled.  Here the neighbourhood is the symmetric radius
+ *   graph, a contested row goes by the key above, and a high-curvature row that no seed reaches smoothly stays -1.  PCL's residual
+ *   test, a k-NN neighbourhood mode and colour-based growing are not provided.
+ * SYMMICP_ERR_ARG, all decided on the host before a device is needed, the outputs untouched: NULL xyz / nrm / cfg / labels_out /
+ *   regions_out; NULL sizes_out with cap > 0; n == 0 or n > 2^31 - 1; cfg->struct_size != sizeof(symmicp_region_config); eps not
+ *   finite or not > 0; smoothness_cos not finite or outside [0, 1]; a NaN curvature_threshold (+-inf are allowed); a negative size
+ *   bound, or max_region_size < min_region_size with both > 0; non-finite coordinates or normal components; a NaN in curv.
+ * xyz and nrm strided as in symmicp_set_source.  The ctx form runs on the context's stream and arenas: the context's clouds, index,
+ * attributes, certificates and states stay exactly as they were.  A sharded job computes the full result on every rank. */
+typedef struct {
+    uint32_t struct_size;          /* = sizeof(symmicp_region_config), checked */
+    float    eps;                  /* neighbourhood radius, finite, > 0 (the caller sets it; default 0) */
+    float    smoothness_cos;       /* in [0, 1]; default 0.8660254f (30 degrees, PCL's default) */
+    float    curvature_threshold;  /* not NaN, +inf allowed; default 0.05f (PCL's default) */
+    int32_t  min_region_size;      /* >= 0, 0 = none */
+    int32_t  max_region_size;      /* >= 0, 0 = none; if both > 0, max >= min */
+} symmicp_region_config;
+void symmicp_region_config_default(symmicp_region_config *cfg);
+int symmicp_ctx_region_growing(symmicp_ctx *ctx, const float *xyz, size_t xyz_row_stride, size_t xyz_col_stride, const float *nrm,
+                               size_t nrm_row_stride, size_t nrm_col_stride, const float *curv, size_t curv_stride, size_t n,
+                               const symmicp_region_config *cfg, int32_t *labels_out, size_t *regions_out, int32_t *sizes_out,
+                               size_t cap, uint8_t *seed_out, int32_t *smooth_out);
+/* the same on a context of its own, created on `device` (-1 = current) and destroyed again */
+int symmicp_region_growing(int device, const float *xyz, size_t xyz_row_stride, size_t xyz_col_stride, const float *nrm,
+                           size_t nrm_row_stride, size_t nrm_col_stride, const float *curv, size_t curv_stride, size_t n,
+                           const symmicp_region_config *cfg, int32_t *labels_out, size_t *regions_out, int32_t *sizes_out,
+                           size_t cap, uint8_t *seed_out, int32_t *smooth_out);
+
 /* ---- consistent normal orientation (Hoppe et al. 1992; Open3D's orient_normals_consistent_tangent_plane; DESIGN.md 4, "Normal
  * orientation") ---------------------------------------------------------------------------------------------------------------
  * Gives the normals of a cloud one common side per connected part: a flip towards a viewpoint is right only where the viewpoint
